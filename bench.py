@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: grid<->spectral round trips per second at T30 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res t30|t63] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res t30|t63] [--batch B] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one device-resident batch of B synthetic 2-D
 fields: grid_to_spec followed by spec_to_grid(.,kcos=1) (spectral.f90:98-122), FP64.
@@ -660,6 +660,34 @@ def collect_errors(node, path=""):
     return found
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs: bytes written in all, over every rank (the limit is 64 MB)
+DUMP_SEED = 20240229           # fixes which fields of the batch are written when the batch is larger than that
+
+
+def dump_outputs(torch, outdir, spec, grid, rank, world):
+    """--dump-outputs DIR: what the timed path returned in its last step -- the spectra of grid_to_spec and the grids of
+    spec_to_grid(kcos=1) -- as DIR/grid_to_spec.npy (float64 [n, nx, mx, 2], real and imaginary parts) and
+    DIR/spec_to_grid.npy (float64 [n, il, ix]).  n fields of the batch: all of them if they fit DUMP_BYTES, else a seeded
+    sample in ascending order (the same fields in every run).  With N > 1 each rank writes its own shard as <name>_rank<r>.npy."""
+    nb = grid.shape[0]
+    per_field = (grid[0].numel() + 2 * spec[0].numel()) * 8
+    n = min(nb, DUMP_BYTES // world // per_field)
+    if n < nb:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nb, n, replace=False))
+    else:
+        idx = np.arange(nb)
+    sel = torch.from_numpy(idx).to(grid.device)
+    arrays = {"grid_to_spec": torch.view_as_real(spec.index_select(0, sel)), "spec_to_grid": grid.index_select(0, sel)}
+    os.makedirs(outdir, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy().astype(np.float64, copy=False)
+        fname = name + (".npy" if world == 1 else "_rank%d.npy" % rank)
+        np.save(os.path.join(outdir, fname), a)
+        files[fname] = list(a.shape)
+    return {"dir": outdir, "files": files, "fields": int(n), "of_fields": int(nb), "sample_seed": DUMP_SEED if n < nb else None}
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -851,9 +879,14 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="do not measure `roofline.traffic` with rocprofv3 counter passes of a child run (N = 1 only; "
                                                           "falls back to the committed per-field figures of profiles/pmc_traffic.json)")
     ap.add_argument("--fused", type=int, default=-1, help="1 fused single-pass kernels, 0 four-kernel path, -1 auto")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float64; a fixed seeded "
+                         "sample of the batch when the whole of it is over 60 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ       # torchrun / torch.distributed.run started us
     if not launched and args.gpus > 1:
         raise SystemExit(self_launch(args, sys.argv[1:]))                # one rank per GPU; this process only waits
@@ -940,6 +973,8 @@ def main():
     tail = sorted(blocks[-3:])
     elapsed = tail[len(tail) // 2]
     best_block = min(blocks)
+    # the outputs of the last timed step, before anything else runs on the plan
+    dumped = dump_outputs(torch, args.dump_outputs, spec, out, rank, world) if args.dump_outputs else None
 
     # per-kernel launch durations: HIP events on the launch stream, outside the timed region
     sp.set_profiling(True)
@@ -1048,6 +1083,8 @@ def main():
                 res["cpu_baseline_fast_math"] = fast
             res["cpu_baseline_socket"] = cpu_baseline_socket(args.res, "fast" if fast else "")
             res["gpu_over_cpu_socket"] = value / res["cpu_baseline_socket"]["value"]
+        if dumped:
+            res["dump_outputs"] = dumped
         flatten_for_driver(res, args.res)
         res["errors"] = collect_errors(res)          # every side measurement that failed, by path: none is hidden in a nested string
         print(json.dumps(res))

@@ -218,6 +218,69 @@ def make_output():
     print("wrote", out, os.path.getsize(out) // 1024, "KiB")
 
 
+LIVE_STEP_CASES = ((1, 1200.0, False), (2, 2400.0, True), (1, 4800.0, True))   # step_field: j1, dt, filtered (eps = rob)
+LIVE_DYN_CASES = ((1, 1, 1200.0), (1, 2, 2400.0), (2, 2, 4800.0))             # first_step's two steps, then a leapfrog step
+
+
+def make_live():
+    """ref_live.npz: the reference's outputs for the extra seeds of the *_live tests of tests/test_oracle_golden.py, whole
+    arrays, each as its synth.digest(): the C oracle reproduces them bit for bit, so a digest pins them as an array would."""
+    import dynstep
+    from oracle.pyoracle import Oracle
+    d = {}
+    for tag in ("t30", "t63"):                     # test_against_live_reference
+        r = Reference(tag)
+        S = synth.spectra(3, r.trunc, first=100, full_rows=True)
+        G = synth.grids(3, r.ix, r.il, first=100)
+        for b in range(3):
+            for kcos in (1, 2):
+                d["rt_%s_s2g_%d_%d" % (tag, b, kcos)] = synth.digest(r.spec_to_grid(S[b], kcos))
+            d["rt_%s_g2s_%d" % (tag, b)] = synth.digest(r.grid_to_spec(G[b]))
+        d["rt_%s_loop" % tag] = synth.digest(r.roundtrip_loop(G[:2]))
+    for tag in ("t30k5", "t30k7", "t63k16"):       # test_other_level_counts_live
+        r = Reference(tag)
+        if tag == "t63k16":
+            o = Oracle(r.trunc, r.ix, r.iy, r.kx)
+            o.set_sigma(synth.SIGMA_L16)
+            r.set_sigma(*[o.table(n) for n in ("hsg", "dhs", "fsg", "dhsr", "fsgr")])
+        r.tail_init(2400.0)
+        div, t, ps = synth.tail_inputs(r.kx, r.nx, r.mx, seed=1234)
+        for i, a in enumerate(r.implicit_terms(div, t, ps)):
+            d["lev_%s_imp%d" % (tag, i)] = synth.digest(a)
+        T, phis = synth.cfield((r.kx, r.nx, r.mx), 77, 250.0), synth.cfield((r.nx, r.mx), 78, 500.0)
+        d["lev_%s_geop" % tag] = synth.digest(r.geopotential(T, phis))
+    r = Reference("t30")
+    o = Oracle(r.trunc, r.ix, r.iy, r.kx)
+    d["sf_wil_rob"] = np.array(r.wil_rob())        # test_step_field_live
+    F3, D3, F2, D2 = step_inputs(r.kx, r.nx, r.mx)
+    for c, (j1, dt, eps) in enumerate(LIVE_STEP_CASES):
+        for dim, (F, D) in ((3, (F3, D3)), (2, (F2, D2))):
+            a, b = r.step_field(j1, dt, d["sf_wil_rob"][1] if eps else 0.0, F, D)
+            d["sf_%d_%dd_field" % (c, dim)], d["sf_%d_%dd_fdt" % (c, dim)] = synth.digest(a), synth.digest(b)
+    for dt in (1200.0, 4800.0):                    # test_spectral_tendencies_live
+        r.tail_init(dt)
+        for i, a in enumerate(r.spectral_tendencies(*spectend_inputs(r.kx, r.nx, r.mx), j2=2)):
+            d["stend_dt%d_%d" % (int(dt), i)] = synth.digest(a)
+    st = dynstep.state(o, 8100)                    # test_dynamics_step_live
+    for c, (j1, j2, dt) in enumerate(LIVE_DYN_CASES):
+        r.tail_init(dt)
+        st, phi = r.step(j1, j2, dt, st)
+        for n in ("vor", "div", "t", "tr", "ps"):
+            d["dyn_%d_%s" % (c, n)] = synth.digest(st[n])
+        d["dyn_%d_phi" % c] = synth.digest(phi)
+    for tag in ("t30", "t63"):                     # test_output_fields_live
+        r = Reference(tag)
+        o = Oracle(r.trunc, r.ix, r.iy, r.kx)
+        st = dynstep.state(o, 7100)
+        phi = o.geopotential(st["t"][0], st["phis"])
+        outs = r.output(st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])
+        for n, a in zip(("u", "v", "t", "q", "phi", "ps"), outs):
+            d["out_%s_%s" % (tag, n)] = synth.digest(a.view(np.int32))
+    out = os.path.join(HERE, "ref_live.npz")
+    np.savez_compressed(out, **d)
+    print("wrote", out, os.path.getsize(out) // 1024, "KiB")
+
+
 def make(tag, nb_grid, dts, imp_dts, lean):
     r = Reference(tag)
     tr, ix, il, kx, nx, mx = r.trunc, r.ix, r.il, r.kx, r.nx, r.mx
@@ -295,6 +358,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "spectend":  # only the get_spectral_tendencies fixture
         make_spectend()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":      # only the fixture of the extra-seed (*_live) tests
+        make_live()
+        sys.exit(0)
     make("t30", nb_grid=2, dts=DTS, imp_dts=(1200.0, 4800.0), lean=False)
     make("t63", nb_grid=1, dts=(4800.0,), imp_dts=(4800.0,), lean=True)
     make_extra()
@@ -303,3 +369,4 @@ if __name__ == "__main__":
     make_dynstep()
     make_output()
     make_longrun()
+    make_live()

@@ -11,6 +11,16 @@ import numpy as np
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
+def digest(a):
+    """sha256 of an array's values (-0.0 counted as +0.0): for finite arrays of one dtype and shape, equal digests
+    <=> np.array_equal.  Lets a golden file pin a whole array bit for bit without storing it."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind in "fc":
+        a = a + a.dtype.type(0)
+    return hashlib.sha256(str((a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
 def splitmix64(seed, n):
     """n uniform doubles in [0,1) from splitmix64 stream `seed` (vectorised, counter-based)."""
     with np.errstate(over="ignore"):

@@ -52,16 +52,6 @@ def test_fortran_sources_keep_reference_api():
     assert declared == bound, (sorted(declared - bound), sorted(bound - declared))
 
 
-def test_reference_callers_resolve_against_dropins():
-    """Build container only: compile the drop-ins against the reference's own types/params and check its callers'
-    `use ..., only:` lists (and two whole caller files) against them (fortran/check_reference_callers.sh)."""
-    if not os.path.isdir("/root/reference/source") or not os.path.exists("/opt/rocm/lib/llvm/bin/flang"):
-        pytest.skip("needs /root/reference and flang (build container)")
-    r = subprocess.run([os.path.join(FDIR, "check_reference_callers.sh")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "compile unchanged against the drop-in" in r.stdout
-
-
 @pytest.mark.parametrize("tag", ["t30", "t63"])
 def test_driver_fails_loudly_without_gpu(tag):
     try:

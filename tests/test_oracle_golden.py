@@ -2,8 +2,9 @@
 
 1. against the committed golden vectors (reference outputs produced by the flang build of
    /root/reference/source, tests/golden/make_golden.py) -- runs everywhere;
-2. against the live reference library oracle/_ref (when it has been built) on extra seeds.
-The restatement is expected to be bit-exact; the assertion bar is 1e-15 relative.
+2. against the reference's outputs for extra seeds, whole arrays (tests/golden/ref_live.npz: their digests, recorded
+   from the flang build by make_golden.py) -- runs everywhere too.
+The restatement is expected to be bit-exact; the assertion bar is 1e-15 relative, bit for bit where a digest pins it.
 """
 import os
 
@@ -21,6 +22,16 @@ TAGS = ("t30", "t63")
 def close(x, ref, tol=EXACT):
     assert x.shape == ref.shape
     assert synth.relerr(x, ref) <= tol
+
+
+def live_golden():
+    return np.load(os.path.join(GOLDEN, "ref_live.npz"))
+
+
+def pinned(x, z, key):
+    """x is, bit for bit, the whole array of the reference's output that ref_live.npz holds the digest of under `key`."""
+    assert np.all(np.isfinite(x)), key
+    assert synth.digest(x) == str(z[key]), key
 
 
 @pytest.mark.parametrize("tag", TAGS)
@@ -124,23 +135,19 @@ def test_tail(tag, golden, oracle_factory):
 
 @pytest.mark.parametrize("tag", TAGS)
 def test_against_live_reference(tag, oracle_factory):
-    """Extra seeds against oracle/_ref when it exists (build container; prebuilt on the GPU box)."""
-    from oracle.pyoracle import Reference
-    if not Reference.available(tag):
-        pytest.skip("oracle/_ref not built")
-    r, o = Reference(tag), oracle_factory(tag)
+    """Extra seeds against the reference's outputs for them (tests/golden/ref_live.npz), whole arrays."""
+    z, o = live_golden(), oracle_factory(tag)
     S = synth.spectra(3, o.trunc, first=100, full_rows=True)
     G = synth.grids(3, o.ix, o.il, first=100)
     for b in range(3):
         for kcos in (1, 2):
-            close(o.spec_to_grid(S[b], kcos), r.spec_to_grid(S[b], kcos))
-        close(o.grid_to_spec(G[b]), r.grid_to_spec(G[b]))
+            pinned(o.spec_to_grid(S[b], kcos), z, "rt_%s_s2g_%d_%d" % (tag, b, kcos))
+        pinned(o.grid_to_spec(G[b]), z, "rt_%s_g2s_%d" % (tag, b))
     # round-trip accuracy of the reference itself is only ~5e-5 (first-guess Gaussian latitudes)
     s2 = o.grid_to_spec(o.spec_to_grid(synth.spectra(1, o.trunc)[0], 1))
     err = np.max(np.abs(s2 - synth.spectra(1, o.trunc)[0])[:-1])
     assert 1e-6 < err < 5e-3
-    out = o.roundtrip_loop(G[:2]); ref = r.roundtrip_loop(G[:2])
-    close(out, ref)
+    pinned(o.roundtrip_loop(G[:2]), z, "rt_%s_loop" % tag)
 
 
 EXTRA = ("t30", "t63", "t30k5", "t30k7", "t63k16")
@@ -174,18 +181,16 @@ def test_other_level_counts_and_geopotential(tag, golden, oracle_factory):
 
 @pytest.mark.parametrize("tag", ("t30k5", "t30k7", "t63k16"))
 def test_other_level_counts_live(tag, oracle_factory):
-    from oracle.pyoracle import Reference
-    if not Reference.available(tag):
-        pytest.skip("oracle/_ref not built")
-    r, o = Reference(tag), oracle_factory(tag)
-    if tag == "t63k16":
-        r.set_sigma(*[o.table(n) for n in ("hsg", "dhs", "fsg", "dhsr", "fsgr")])
-    r.tail_init(2400.0); o.tail_init(2400.0)
+    """implicit_terms and get_geopotential at 5, 7 and 16 levels on another seed, whole arrays (tests/golden/ref_live.npz)."""
+    z, o = live_golden(), oracle_factory(tag)
+    o.tail_init(2400.0)
     div, t, ps = synth.tail_inputs(o.kx, o.nx, o.mx, seed=1234)
-    for x, y in zip(o.implicit_terms(div, t, ps), r.implicit_terms(div, t, ps)):
-        close(x, y)
+    outs = o.implicit_terms(div, t, ps)
+    assert len(outs) == 3
+    for i, x in enumerate(outs):
+        pinned(x, z, "lev_%s_imp%d" % (tag, i))
     T, phis = synth.cfield((o.kx, o.nx, o.mx), 77, 250.0), synth.cfield((o.nx, o.mx), 78, 500.0)
-    close(o.geopotential(T, phis), r.geopotential(T, phis))
+    pinned(o.geopotential(T, phis), z, "lev_%s_geop" % tag)
 
 
 STEP_CASES = {"t30": None, "t30k5": (slice(None), slice(None, None, 2), slice(None, None, 2)),
@@ -224,20 +229,15 @@ def test_step_field_pinned(tag, oracle_factory):
 
 
 def test_step_field_live(oracle_factory):
-    """The same against the live flang build, full arrays (build container only)."""
-    from oracle.pyoracle import Reference
-    if not Reference.available("t30"):
-        pytest.skip("oracle/_ref not built")
-    r, o = Reference("t30"), oracle_factory("t30")
-    if not hasattr(r.lib, "ref_step_field_3d"):
-        pytest.skip("oracle/_ref predates the step_field extraction")
-    wil, rob = r.wil_rob()
+    """The same against the flang build's outputs for other steps, full arrays (tests/golden/ref_live.npz)."""
+    from golden.make_golden import LIVE_STEP_CASES
+    z, o = live_golden(), oracle_factory("t30")
+    wil, rob = z["sf_wil_rob"]
     F3, D3, F2, D2 = step_inputs(o.kx, o.nx, o.mx)
-    for j1, dt, eps in ((1, 1200.0, 0.0), (2, 2400.0, rob), (1, 4800.0, rob)):
-        for F, D in ((F3, D3), (F2, D2)):
-            a, b = o.step_field(j1, dt, eps, wil, F, D)
-            ra, rb = r.step_field(j1, dt, eps, F, D)
-            close(a, ra); assert np.array_equal(b, rb)
+    for c, (j1, dt, filtered) in enumerate(LIVE_STEP_CASES):
+        for dim, (F, D) in ((3, (F3, D3)), (2, (F2, D2))):
+            a, b = o.step_field(j1, dt, rob if filtered else 0.0, wil, F, D)
+            pinned(a, z, "sf_%d_%dd_field" % (c, dim)); pinned(b, z, "sf_%d_%dd_fdt" % (c, dim))
 
 
 SPECTEND_CASES = {"t30": None, "t30k5": None, "t63k16": (slice(None), slice(None, None, 5), slice(None, None, 3))}
@@ -264,19 +264,15 @@ def test_spectral_tendencies_pinned(tag, oracle_factory):
 
 
 def test_spectral_tendencies_live(oracle_factory):
-    """The same against the live flang build, full arrays and another dt (build container only)."""
-    from oracle.pyoracle import Reference
+    """The same against the flang build's outputs, full arrays and another dt (tests/golden/ref_live.npz)."""
     from golden.make_golden import spectend_inputs
-    if not Reference.available("t30"):
-        pytest.skip("oracle/_ref not built")
-    r, o = Reference("t30"), oracle_factory("t30")
-    if not hasattr(r.lib, "ref_spectral_tendencies"):
-        pytest.skip("oracle/_ref predates the get_spectral_tendencies extraction")
+    z, o = live_golden(), oracle_factory("t30")
     for dt in (1200.0, 4800.0):
-        r.tail_init(dt); o.tail_init(dt)
-        ins = spectend_inputs(o.kx, o.nx, o.mx)
-        for x, y in zip(o.spectral_tendencies(*ins), r.spectral_tendencies(*ins, j2=2)):
-            close(x, y)
+        o.tail_init(dt)
+        outs = o.spectral_tendencies(*spectend_inputs(o.kx, o.nx, o.mx))
+        assert len(outs) == 4
+        for i, x in enumerate(outs):
+            pinned(x, z, "stend_dt%d_%d" % (int(dt), i))
 
 
 @pytest.mark.parametrize("tag", ["t30", "t30k5", "t63k16"])
@@ -324,23 +320,18 @@ def test_two_day_run_pinned(case, oracle_factory):
 
 
 def test_dynamics_step_live(oracle_factory):
-    """The same against the live flang build: the start-up sequence of first_step and a leapfrog step, chained, full arrays,
-    bit for bit (build container only)."""
-    from oracle.pyoracle import Reference
+    """The same against the flang build's outputs: the start-up sequence of first_step and a leapfrog step, chained, full
+    arrays, bit for bit (tests/golden/ref_live.npz)."""
+    from golden.make_golden import LIVE_DYN_CASES
     import dynstep
-    if not Reference.available("t30"):
-        pytest.skip("oracle/_ref not built")
-    r, o = Reference("t30"), oracle_factory("t30")
-    if not hasattr(r.lib, "ref_step"):
-        pytest.skip("oracle/_ref predates the adiabatic step build")
-    st_r = st_o = dynstep.state(o, 8100)
-    for j1, j2, dt, eps in ((1, 1, 1200.0, 0.0), (1, 2, 2400.0, 0.0), (2, 2, 4800.0, dynstep.ROB)):
-        r.tail_init(dt); o.tail_init(dt)
-        st_r, phi = r.step(j1, j2, dt, st_r)
-        st_o, out = dynstep.oracle_dynamics_step(o, st_o, j1, dt, eps, j2=j2)
+    z, o = live_golden(), oracle_factory("t30")
+    st_o = dynstep.state(o, 8100)
+    for c, (j1, j2, dt) in enumerate(LIVE_DYN_CASES):
+        o.tail_init(dt)
+        st_o, out = dynstep.oracle_dynamics_step(o, st_o, j1, dt, 0.0 if j1 == 1 else dynstep.ROB, j2=j2)
         for n in ("vor", "div", "t", "tr", "ps"):
-            assert np.array_equal(st_o[n], st_r[n]), (j1, j2, n)
-        assert np.array_equal(out["phi"], phi)
+            pinned(st_o[n], z, "dyn_%d_%s" % (c, n))
+        pinned(out["phi"], z, "dyn_%d_phi" % c)
 
 
 @pytest.mark.parametrize("tag", ["t30", "t30k5", "t63k16"])
@@ -362,20 +353,17 @@ def test_output_fields_pinned(tag, oracle_factory):
 
 
 def test_output_fields_live(oracle_factory):
-    """The same against the live flang build at T30 L8 and T63 L8 on another seed, whole arrays (build container only)."""
-    from oracle.pyoracle import Reference
+    """The same against the flang build's outputs at T30 L8 and T63 L8 on another seed, whole arrays (tests/golden/ref_live.npz)."""
     import dynstep
+    z = live_golden()
     for tag in ("t30", "t63"):
-        if not Reference.available(tag):
-            pytest.skip("oracle/_ref not built")
-        r, o = Reference(tag), oracle_factory(tag)
-        if not hasattr(r.lib, "ref_output_fields"):
-            pytest.skip("oracle/_ref predates the output-field extraction")
+        o = oracle_factory(tag)
         st = dynstep.state(o, 7100)
         phi = o.geopotential(st["t"][0], st["phis"])
-        args = (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])
-        for n, a, b in zip(("u", "v", "t", "q", "phi", "ps"), o.output(*args), r.output(*args)):
-            assert np.array_equal(a.view(np.int32), b.view(np.int32)), (tag, n)
+        outs = o.output(st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])
+        assert len(outs) == 6
+        for n, a in zip(("u", "v", "t", "q", "phi", "ps"), outs):
+            pinned(a.view(np.int32), z, "out_%s_%s" % (tag, n))
 
 
 def test_step_restatements_selfconsistent(oracle_factory):

@@ -22,6 +22,29 @@ def _free_port():
         return s.getsockname()[1]
 
 
+# The ranks are CPU processes and must not open the GPU on a machine that has one (8 ranks + this process would exceed
+# what may share a device): no device is visible to them, so torch answers "no GPU" from the environment instead of
+# initialising the runtime, and they synchronise with a CPU collective -- dist.barrier() probes the runtime for a device.
+_CPU_ONLY = {"CUDA_VISIBLE_DEVICES": "", "HIP_VISIBLE_DEVICES": "", "PYTORCH_NVML_BASED_CUDA_CHECK": "1"}
+
+
+def _cpu_barrier():
+    dist.all_reduce(torch.zeros(1))
+
+
+def _spawn(fn, args, world):
+    saved = {k: os.environ.get(k) for k in _CPU_ONLY}
+    os.environ.update(_CPU_ONLY)
+    try:
+        mp.spawn(fn, args=args, nprocs=world, join=True)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 def _worker(rank, world, port, kx, outdir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -49,14 +72,14 @@ def _worker(rank, world, port, kx, outdir):
     np.save(os.path.join(outdir, "imp_%d.npy" % rank), np.concatenate([d2[klo:khi].ravel(), t2[klo:khi].ravel()]))
     # (3) timing contract: max over ranks
     assert sh.max_over_ranks(1.0 + rank) == float(world)
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world,kx", [(2, 8), (2, 7)])
 def test_two_rank_sharding(world, kx, tmp_path):
     port = _free_port()
-    mp.spawn(_worker, args=(world, port, kx, str(tmp_path)), nprocs=world, join=True)
+    _spawn(_worker, (world, port, kx, str(tmp_path)), world)
     import speedy_f90_amd as s
     from oracle.pyoracle import Oracle
     from golden.make_golden import tail_inputs
@@ -89,7 +112,7 @@ def _step_worker(rank, world, port, kx, outdir):
         st, fin = s.sharding.sharded_step_host(o, st, rank, world, 2, 2, 2400.0, ROB, WIL, SDRAG)
     np.savez(os.path.join(outdir, "step_%d.npz" % rank), **{n: st[n] for n in ("vor", "div", "t", "tr", "ps")},
              **{n: fin[n] for n in ("vordt", "divdt", "tdt", "trdt", "psdt", "phi", "U", "V", "PL")})
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -102,7 +125,7 @@ def test_multi_rank_sharded_step(world, kx, tmp_path):
     UNSHARDED oracle step's prognostics and tendencies bit for bit -- equal (world 2) and ragged (world 3, 8 levels) blocks.
     This is the test that catches a level coupling left out of the exchange (round 3: psdt / get_spectral_tendencies)."""
     port = _free_port()
-    mp.spawn(_step_worker, args=(world, port, kx, str(tmp_path)), nprocs=world, join=True)
+    _spawn(_step_worker, (world, port, kx, str(tmp_path)), world)
     import speedy_f90_amd as s
     from oracle.pyoracle import Oracle
     from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, state
@@ -137,7 +160,7 @@ def _transposed_worker(rank, world, port, kx, outdir):
     np.savez(os.path.join(outdir, "tstep_%d.npz" % rank), c0=fin["range"][0], c1=fin["range"][1],
              **{n: st[n] for n in ("vor", "div", "t", "tr", "ps")},
              **{n: fin[n] for n in ("vordt", "divdt", "tdt", "trdt", "psdt", "phi", "U", "V", "PL")})
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -150,7 +173,7 @@ def test_multi_rank_transposed_step(world, kx, tmp_path):
     chained steps every rank must hold, on ITS coefficients, the unsharded oracle step's prognostics and tendencies bit for bit,
     the ranges must tile the spectrum, and its levels' direct-batch operands must have come home complete."""
     port = _free_port()
-    mp.spawn(_transposed_worker, args=(world, port, kx, str(tmp_path)), nprocs=world, join=True)
+    _spawn(_transposed_worker, (world, port, kx, str(tmp_path)), world)
     import speedy_f90_amd as s
     from oracle.pyoracle import Oracle
     from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, state
