@@ -492,29 +492,21 @@ int four_from_host(spdy_plan *p, const double *src, int nb)
     return SPDY_OK;
 }
 
-// Launch one transform kernel; when profiling is on, bracket it with HIP events recorded on
-// the very stream it runs on (kind: SPDY_K_*).
 // Fused single-pass kernels exist for T30.  Measured on MI355X (tools/small_batch.sh) they beat the
 // four-kernel path at every batch size (one launch and no HBM intermediate: 2x even at 8..91 fields), so
 // "auto" means fused whenever the resolution has them.
-bool use_fused(const spdy_plan *p, int nb)
-{
-    (void)nb;
-    return p->tab.trunc == 30 && p->fused_mode != 0;
-}
-// T63: fused field-pair kernels for the plain transforms (spdy_fused_t63.inc); the operator-fused modes use the
-// multi-kernel sequences
-// T63, direct transform: below ~80 fields a launch is one field pair per workgroup on a fraction of the CUs and costs the
+bool fused30(const spdy_plan *p) { return p->tab.trunc == 30 && p->fused_mode != 0; }
+// T63: fused field-pair kernels (spdy_fused_t63.inc).
+// Direct transform: below ~80 fields a launch is one field pair per workgroup on a fraction of the CUs and costs the
 // pair's pipeline latency (26 us, tools/t63_small_batch.py); the four-kernel pipeline spreads such a batch over more
 // workgroups (21-24 us).  Until round 3 "auto" switched to it there -- and with it a field's BITS depended on whether it
 // travelled in a batch of 79 or 80 (the two paths agree to rounding, not bitwise).  A drop-in must not do that to its host:
 // auto now means the fused kernels at every batch size (the whole-pair walk accumulates every field the same way whatever
 // the batch; the inverse transform's by-chunk walk for small batches is bit-identical to its whole-pair walk), at the price
 // of ~4 us on a lone small direct transform.  spdy_plan_set_fused(0) still selects the four-kernel path.
-bool use_fused63(const spdy_plan *p, int nb) { (void)nb; return p->tab.trunc == 63 && p->fused_mode != 0; }
 // The composite entry points (uvspec/grad -> grid, vdspec, the mixed batches) are one fused launch against two to four
 // four-kernel sequences: the fused kernels win there at any size.
-bool use_fused63_composite(const spdy_plan *p) { return p->tab.trunc == 63 && p->fused_mode != 0; }
+bool fused63(const spdy_plan *p) { return p->tab.trunc == 63 && p->fused_mode != 0; }
 // T30: a step's whole direct batch is ONE mixed-tile launch (MODE 3) -- what a latency-bound, model-sized batch wants.  At
 // throughput sizes (the launch streams: >= 16 MB of grids) the launch count does not matter and the mixed-mode direct kernel --
 // out of registers, it reads its vds factors where it uses them -- runs at 0.48 of the HBM roofline where the pair kernel
@@ -526,6 +518,8 @@ bool one_mixed_launch(const spdy_plan *p, long fields)
     return !spdy::streams(fields * (long)grid_elems(p) * 8);
 }
 
+// Launch one transform kernel; when profiling is on, bracket it with HIP events recorded on
+// the very stream it runs on (kind: SPDY_K_*).
 template <class F> int timed(spdy_plan *p, int kind, F &&launch)
 {
     if (!p->profiling || p->capturing) { HIP_TRY(launch()); return SPDY_OK; }
@@ -539,12 +533,171 @@ template <class F> int timed(spdy_plan *p, int kind, F &&launch)
     return SPDY_OK;
 }
 
+/* ---------------------------------------------------------------- composite transforms: one builder per direction */
+// A model step's inverse batch (tendencies.f90:89-123): npairs (vor, div) -> uvspec -> (ug, vg); plain spectra from up to
+// SPDY_MAX_SPEC_SEGS source arrays (none empty) into ONE grid stack, d_kcos indexed along it; ngrad psi -> grad -> (gx, gy).
+struct InverseReq {
+    int npairs; const double *vor, *dv; double *ug, *vg; int kcos_pairs;
+    int nseg; spdy_spec_seg seg[SPDY_MAX_SPEC_SEGS]; const int *d_kcos; int kcos_all; double *grid;
+    int ngrad; const double *psi; double *gx, *gy; int kcos_grad;
+};
+
+/* T63, row f1: uvspec / grad evaluated where the fused inverse kernel loads its operands (csrc/spdy_fused_t63.inc,
+ * t63_derive_to_lds: each derived spectrum is formed once per chunk and staged through LDS) -- segments U, V of (vor, div) and
+ * d/dlambda, d/dmu of psi.  Model-sized launches only; larger ones keep the operator kernel in front, into the plan's
+ * temporaries (it runs at 4-6 TB/s there and the transform launch is not latency-bound).  $SPDY_T63_NODERIVE /
+ * spdy_plan_set_option("t63_derive", 0): always the operator kernel (A/B runs, the determinism test).
+ * One fused launch over r's pairs (if `pairs`), its first nseg plain segments and its gradient (if `grad`).                  */
+int inverse63(spdy_plan *p, const InverseReq &r, bool pairs, int nseg, bool grad)
+{
+    const int npairs = pairs ? r.npairs : 0, ngrad = grad ? r.ngrad : 0;
+    const int uv_op = 2 * ((npairs + 1) / 2), grad_op = 2 * ((ngrad + 1) / 2);
+    int plain = 0;
+    for (int i = 0; i < nseg; ++i) plain += (r.seg[i].nb + 1) / 2;
+    const bool derive = p->t63_derive && spdy::s2g_t63_derives(p->num_cu, uv_op + plain + grad_op, npairs ? uv_op : grad_op, uv_op + grad_op);
+    const size_t off = (size_t)npairs * spec_elems(p);
+    if (!derive && (npairs || ngrad)) {
+        RC(ensure_four(p));
+        if (npairs && ngrad)
+            KERNEL(spdy::launch_uvspec_grad(p->dev, npairs, r.vor, r.dv, p->tmp_c, p->tmp_d, ngrad, r.psi, p->tmp_c + off, p->tmp_d + off, p->stream));
+        else if (npairs) KERNEL(spdy::launch_uvspec(p->dev, npairs, r.vor, r.dv, p->tmp_c, p->tmp_d, p->stream));
+        else KERNEL(spdy::launch_grad(p->dev, ngrad, r.psi, p->tmp_c, p->tmp_d, p->stream));
+    }
+    spdy::T63Batch b{};
+    int k = 0;
+    if (npairs && derive) {
+        b.seg[k++] = spdy::T63Seg{r.vor, r.ug, r.dv, nullptr, npairs, r.kcos_pairs, 0, spdy::T63_OP_U};
+        b.seg[k++] = spdy::T63Seg{r.dv, r.vg, r.vor, nullptr, npairs, r.kcos_pairs, 0, spdy::T63_OP_V};
+    } else if (npairs) {
+        b.seg[k++] = spdy::T63Seg{p->tmp_c, r.ug, nullptr, nullptr, npairs, r.kcos_pairs, 0, 0};
+        b.seg[k++] = spdy::T63Seg{p->tmp_d, r.vg, nullptr, nullptr, npairs, r.kcos_pairs, 0, 0};
+    }
+    for (int i = 0, first = 0; i < nseg; first += r.seg[i++].nb)
+        b.seg[k++] = spdy::T63Seg{r.seg[i].d_spec, r.grid + first * grid_elems(p), nullptr, r.d_kcos ? r.d_kcos + first : nullptr,
+                                  r.seg[i].nb, r.kcos_all, 0, 0};
+    if (ngrad && derive) {
+        b.seg[k++] = spdy::T63Seg{r.psi, r.gx, r.psi, nullptr, ngrad, r.kcos_grad, 0, spdy::T63_OP_GX};
+        b.seg[k++] = spdy::T63Seg{r.psi, r.gy, r.psi, nullptr, ngrad, r.kcos_grad, 0, spdy::T63_OP_GY};
+    } else if (ngrad) {
+        b.seg[k++] = spdy::T63Seg{p->tmp_c + off, r.gx, nullptr, nullptr, ngrad, r.kcos_grad, 0, 0};
+        b.seg[k++] = spdy::T63Seg{p->tmp_d + off, r.gy, nullptr, nullptr, ngrad, r.kcos_grad, 0, 0};
+    }
+    b.nseg = k;
+    return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
+}
+
+// r's pairs (mode 1) or gradient (mode 2) on their own, with the two inverse transforms that always follow the operator
+int derived_alone(spdy_plan *p, const InverseReq &r, int mode)
+{
+    const int nb = mode == 1 ? r.npairs : r.ngrad, kcos = mode == 1 ? r.kcos_pairs : r.kcos_grad;
+    double *g0 = mode == 1 ? r.ug : r.gx, *g1 = mode == 1 ? r.vg : r.gy;
+    if (fused30(p)) {
+        spdy::S2gFused f;
+        f.mode = mode; f.nb = nb; f.kcos_all = kcos; f.grid = g0; f.grid2 = g1;
+        f.spec = mode == 1 ? r.vor : r.psi;
+        f.spec2 = mode == 1 ? r.dv : nullptr;
+        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused(p->dev, f, p->num_cu * p->wg_per_cu, p->stream); });
+    }
+    if (fused63(p)) return inverse63(p, r, mode == 1, 0, mode == 2);
+    RC(ensure_four(p));
+    if (mode == 1) KERNEL(spdy::launch_uvspec(p->dev, nb, r.vor, r.dv, p->tmp_c, p->tmp_d, p->stream));
+    else KERNEL(spdy::launch_grad(p->dev, nb, r.psi, p->tmp_c, p->tmp_d, p->stream));
+    RC(spdy_spec_to_grid_dev(p, nb, p->tmp_c, nullptr, kcos, g0));
+    return spdy_spec_to_grid_dev(p, nb, p->tmp_d, nullptr, kcos, g1);
+}
+
+// Pairs and plain fields together are one launch: T30 mode 3 with the gradient, T63 one segmented launch that takes the gradient
+// too while the operator route's temporaries (max_batch spectra) hold pairs and gradient.  Otherwise each part goes on its own.
+// (rows of psdy that grad leaves untouched -- l > trunc+1 inside row nx -- are never read by the transforms)
+int inverse_batch(spdy_plan *p, InverseReq r)
+{
+    r.kcos_pairs = r.kcos_pairs == 1 ? 1 : 2;   // fourier.f90:47-51: anything but 1 means "times cosgr"
+    r.kcos_grad = r.kcos_grad == 1 ? 1 : 2;
+    int nplain = 0;
+    for (int i = 0; i < r.nseg; ++i) nplain += r.seg[i].nb;
+    const bool mixed = r.npairs > 0 && nplain > 0;
+    if (mixed && fused30(p)) {
+        spdy::S2gFused f;
+        f.mode = 3; f.nb = r.npairs; f.spec = r.vor; f.spec2 = r.dv; f.kcos_all = r.kcos_pairs; f.grid = r.ug; f.grid2 = r.vg;
+        for (int i = 0; i < r.nseg; ++i) { f.plain[i] = r.seg[i].d_spec; f.nplain[i] = r.seg[i].nb; }
+        f.kcos_p = r.d_kcos; f.kcos_all_p = r.kcos_all; f.grid_p = r.grid;
+        f.ngrad = r.ngrad; f.psi = r.psi; f.gx = r.gx; f.gy = r.gy; f.kcos_grad = r.kcos_grad; f.zero = p->d_zero_spec;
+        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused(p->dev, f, p->num_cu * p->wg_per_cu, p->stream); });
+    }
+    if (mixed && fused63(p)) {
+        const bool grad_joins = r.npairs + r.ngrad <= p->max_batch;
+        RC(inverse63(p, r, true, r.nseg, grad_joins));
+        return r.ngrad && !grad_joins ? derived_alone(p, r, 2) : SPDY_OK;
+    }
+    if (r.npairs) RC(derived_alone(p, r, 1));
+    for (int i = 0, first = 0; i < r.nseg; first += r.seg[i++].nb)
+        RC(spdy_spec_to_grid_dev(p, r.seg[i].nb, r.seg[i].d_spec, r.d_kcos ? r.d_kcos + first : nullptr, r.kcos_all,
+                                 r.grid + first * grid_elems(p)));
+    if (r.ngrad) RC(derived_alone(p, r, 2));
+    return SPDY_OK;
+}
+
+// A model step's direct batch (tendencies.f90:212-234): npairs (u, v) grid pairs, scaled on load by cosgr (kcos 2) or cosgr2,
+// whose spectra go through vds into (vorm, divm) -- raw: the scaled pairs' spectra themselves, vds left to the caller -- and
+// nplain plain grids -> spec.
+struct DirectReq {
+    int npairs; const double *ug, *vg; double *vorm, *divm; int kcos; bool raw;
+    int nplain; const double *grid; double *spec;
+};
+
+int direct_batch(spdy_plan *p, const DirectReq &r)
+{
+    if (!r.npairs && !r.nplain) return SPDY_OK;
+    const double *sc = r.kcos == 2 ? p->dev.cosgr : p->dev.cosgr2;
+    if (fused63(p)) {
+        // model-sized (row f1): the pairs are ONE segment of the staged form, whose contraction applies vds to their spectra in
+        // registers; otherwise two scaled segments into the plan's temporaries (raw: into vorm, divm) and vds as a kernel behind
+        const bool vds_in = r.npairs > 0 && !r.raw && spdy::g2s_t63_staged(p->dev, p->num_cu, r.npairs + (r.nplain + 1) / 2);
+        const bool vds_behind = r.npairs > 0 && !r.raw && !vds_in;
+        if (vds_behind) RC(ensure_four(p));
+        spdy::T63Batch b{};
+        int k = 0;
+        if (vds_in) {
+            b.seg[k++] = spdy::T63Seg{r.ug, r.vorm, sc, nullptr, r.npairs, 1, 0, spdy::T63_OP_VDS};
+            b.vds_src2 = r.vg; b.vds_dst2 = r.divm;
+        } else if (r.npairs > 0) {
+            b.seg[k++] = spdy::T63Seg{r.ug, vds_behind ? p->tmp_c : r.vorm, sc, nullptr, r.npairs, 1, 0, 0};
+            b.seg[k++] = spdy::T63Seg{r.vg, vds_behind ? p->tmp_d : r.divm, sc, nullptr, r.npairs, 1, 0, 0};
+        }
+        b.seg[k++] = spdy::T63Seg{r.grid, r.spec, nullptr, nullptr, r.nplain, 1, 0, 0};
+        b.nseg = k;
+        RC(timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63_batch(p->dev, b, p->num_cu, p->stream); }));
+        if (vds_behind) KERNEL(spdy::launch_vds(p->dev, r.npairs, p->tmp_c, p->tmp_d, r.vorm, r.divm, p->stream));
+        return SPDY_OK;
+    }
+    spdy::G2sFused f;
+    f.nb = r.npairs; f.grid = r.ug; f.gscale = sc; f.spec = r.vorm; f.grid2 = r.vg; f.spec2 = r.divm;
+    if (fused30(p) && r.npairs > 0 && r.nplain > 0 && one_mixed_launch(p, 2L * r.npairs + r.nplain)) {
+        f.nplain = r.nplain; f.grid_p = r.grid; f.spec_p = r.spec;
+        return timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused(p->dev, f, p->num_cu * p->wg_per_cu, p->stream); });
+    }
+    if (r.npairs > 0 && fused30(p)) {
+        // one pass: the pair (ug[i], vg[i]) is one tile, vds is applied to the two spectra while they are in LDS
+        f.allow_split = !in_host_stage(p, r.ug);
+        KERNEL(spdy::launch_g2s_fused(p->dev, f, p->num_cu * p->wg_per_cu, p->stream));
+    } else if (r.npairs > 0) {
+        RC(ensure_four(p));
+        KERNEL(spdy::launch_fourier_dir(p->dev, r.npairs, r.ug, sc, p->four, p->stream));
+        KERNEL(spdy::launch_legendre_dir(p->dev, r.npairs, p->four, p->tmp_c, p->stream));
+        KERNEL(spdy::launch_fourier_dir(p->dev, r.npairs, r.vg, sc, p->four, p->stream));
+        KERNEL(spdy::launch_legendre_dir(p->dev, r.npairs, p->four, p->tmp_d, p->stream));
+        KERNEL(spdy::launch_vds(p->dev, r.npairs, p->tmp_c, p->tmp_d, r.vorm, r.divm, p->stream));
+    }
+    if (r.nplain) RC(spdy_grid_to_spec_dev(p, r.nplain, r.grid, r.spec));
+    return SPDY_OK;
+}
+
 }  // namespace
 
 namespace spdy_detail {
 bool use_raw63(const spdy_plan *p, int npairs)
 {
-    return p->tab.trunc == 63 && p->fused_mode != 0 && p->tab.kx <= 16 && npairs <= p->max_batch && p->tab.implicit_ready && p->tab.sigma_ready;
+    return fused63(p) && p->tab.kx <= 16 && npairs <= p->max_batch && p->tab.implicit_ready && p->tab.sigma_ready;
 }
 
 int direct_batch_raw63(spdy_plan *p, int npairs, const double *ug, const double *vg, int kcos, int nplain, const double *grid, double *spec,
@@ -552,17 +705,12 @@ int direct_batch_raw63(spdy_plan *p, int npairs, const double *ug, const double 
 {
     RC(check_batch(p, npairs));
     RC(check_batch(p, nplain));
+    if (!fused63(p)) return fail(SPDY_ERR_STATE, "the raw direct batch needs the fused T63 kernels");
     if (!raw_u || !raw_v) {
         RC(ensure_four(p));
         raw_u = p->tmp_c; raw_v = p->tmp_d;
     }
-    const double *sc = kcos == 2 ? p->dev.cosgr : p->dev.cosgr2;
-    spdy::T63Batch b{};
-    b.nseg = 3;
-    b.seg[0] = spdy::T63Seg{ug, raw_u, sc, nullptr, npairs, 1, 0, 0};
-    b.seg[1] = spdy::T63Seg{vg, raw_v, sc, nullptr, npairs, 1, 0, 0};
-    b.seg[2] = spdy::T63Seg{grid, spec, nullptr, nullptr, nplain, 1, 0, 0};
-    return timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
+    return direct_batch(p, DirectReq{npairs, ug, vg, raw_u, raw_v, kcos, true, nplain, grid, spec});
 }
 }  // namespace spdy_detail
 
@@ -852,11 +1000,12 @@ int spdy_spec_to_grid_dev(spdy_plan *p, int nb, const double *d_spec, const int 
     NEED_DEVICE(p);
     RC(check_batch(p, nb));
     if (nb && (!d_spec || !d_grid)) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (use_fused(p, nb))
-        return timed(p, SPDY_K_S2G_FUSED, [&] {
-            return spdy::launch_s2g_fused(p->dev, nb, d_spec, d_kcos, kcos_all, d_grid, p->num_cu * p->wg_per_cu, p->stream);
-        });
-    if (use_fused63_composite(p))               // (the inverse kernel serves every batch size: by-chunk items for small ones)
+    if (fused30(p)) {
+        spdy::S2gFused f;
+        f.nb = nb; f.spec = d_spec; f.d_kcos = d_kcos; f.kcos_all = kcos_all; f.grid = d_grid;
+        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused(p->dev, f, p->num_cu * p->wg_per_cu, p->stream); });
+    }
+    if (fused63(p))               // (the inverse kernel serves every batch size: by-chunk items for small ones)
         return timed(p, SPDY_K_S2G_FUSED, [&] {
             return spdy::launch_s2g_fused_t63(p->dev, nb, d_spec, d_kcos, kcos_all, d_grid, p->num_cu, p->stream);
         });
@@ -871,12 +1020,12 @@ int spdy_grid_to_spec_dev(spdy_plan *p, int nb, const double *d_grid, double *d_
     NEED_DEVICE(p);
     RC(check_batch(p, nb));
     if (nb && (!d_spec || !d_grid)) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (use_fused(p, nb))
-        return timed(p, SPDY_K_G2S_FUSED, [&] {
-            return spdy::launch_g2s_fused(p->dev, nb, d_grid, nullptr, d_spec, p->num_cu * p->wg_per_cu, p->stream, nullptr, nullptr, 0, nullptr,
-                                          nullptr, !in_host_stage(p, d_grid));
-        });
-    if (use_fused63(p, nb))
+    if (fused30(p)) {
+        spdy::G2sFused f;
+        f.nb = nb; f.grid = d_grid; f.spec = d_spec; f.allow_split = !in_host_stage(p, d_grid);
+        return timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused(p->dev, f, p->num_cu * p->wg_per_cu, p->stream); });
+    }
+    if (fused63(p))
         return timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63(p->dev, nb, d_grid, nullptr, d_spec, p->num_cu, p->stream); });
     RC(ensure_four(p));
     RC(timed(p, SPDY_K_FOURIER_DIR, [&] { return spdy::launch_fourier_dir(p->dev, nb, d_grid, nullptr, p->four, p->stream); }));
@@ -1019,29 +1168,6 @@ int spdy_uvspec_dev(spdy_plan *p, int nb, const double *vor, const double *dv, d
     KERNEL(spdy::launch_uvspec(p->dev, nb, vor, dv, u, v, p->stream));
     return SPDY_OK;
 }
-/* T63, row f1: uvspec / grad evaluated where the fused inverse kernel loads its operands (csrc/spdy_fused_t63.inc,
- * t63_inv_load_b_op) -- segments U, V of (vor, div) and d/dlambda, d/dmu of psi.  Model-sized launches only; larger ones keep
- * the operator kernel in front (it runs at 4-6 TB/s there and the transform launch is not latency-bound).  $SPDY_T63_NODERIVE /
- * spdy_plan_set_option("t63_derive", 0): always the operator kernel (A/B runs, the determinism test).                        */
-static int append_uv_segs(spdy::T63Batch &b, int k, int npairs, const double *vor, const double *dv, double *ug, double *vg, int kcos)
-{
-    b.seg[k++] = spdy::T63Seg{vor, ug, dv, nullptr, npairs, kcos, 0, spdy::T63_OP_U};
-    b.seg[k++] = spdy::T63Seg{dv, vg, vor, nullptr, npairs, kcos, 0, spdy::T63_OP_V};
-    return k;
-}
-static int append_grad_segs(spdy::T63Batch &b, int k, int ngrad, const double *psi, double *gx, double *gy, int kcos)
-{
-    b.seg[k++] = spdy::T63Seg{psi, gx, psi, nullptr, ngrad, kcos, 0, spdy::T63_OP_GX};
-    b.seg[k++] = spdy::T63Seg{psi, gy, psi, nullptr, ngrad, kcos, 0, spdy::T63_OP_GY};
-    return k;
-}
-static bool derive63(const spdy_plan *p, int op_fields_each, int nsets, int plain_fields_pairs)
-{
-    // op_fields_each fields in each of nsets derived segments (pairs are formed inside a segment)
-    const int op_pairs = nsets * ((op_fields_each + 1) / 2);
-    return p->t63_derive && spdy::s2g_t63_derives(p->num_cu, op_pairs + plain_fields_pairs, op_pairs);
-}
-
 /* uvspec / grad followed by the two inverse transforms their callers always do, in one pass where the fused
  * kernels exist; otherwise the operator kernel into plan-owned temporaries and two ordinary transforms.      */
 static int derived_to_grid(spdy_plan *p, int nb, int mode, const double *in0, const double *in1, double *g0, double *g1, int kcos)
@@ -1049,32 +1175,8 @@ static int derived_to_grid(spdy_plan *p, int nb, int mode, const double *in0, co
     NEED_DEVICE(p);
     RC(check_batch(p, nb));
     if (nb && (!in0 || (mode == 1 && !in1) || !g0 || !g1)) return fail(SPDY_ERR_ARG, "null device pointer");
-    kcos = kcos == 1 ? 1 : 2;   // fourier.f90:47-51: anything but 1 means "times cosgr"
-    if (use_fused(p, nb))
-        return timed(p, SPDY_K_S2G_FUSED, [&] {
-            return spdy::launch_s2g_fused(p->dev, nb, in0, nullptr, kcos, g0, p->num_cu * p->wg_per_cu, p->stream, mode, in1, g1);
-        });
-    if (use_fused63_composite(p) && derive63(p, nb, 2, 0)) {   // T63, model-sized: the operator rides in the transform launch
-        spdy::T63Batch b{};
-        b.nseg = mode == 1 ? append_uv_segs(b, 0, nb, in0, in1, g0, g1, kcos) : append_grad_segs(b, 0, nb, in0, g0, g1, kcos);
-        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    RC(ensure_four(p));
-    if (mode == 1) KERNEL(spdy::launch_uvspec(p->dev, nb, in0, in1, p->tmp_c, p->tmp_d, p->stream));
-    else {
-        // rows of psdy that grad leaves untouched (l > trunc+1 inside row nx) are never read by the transform
-        KERNEL(spdy::launch_grad(p->dev, nb, in0, p->tmp_c, p->tmp_d, p->stream));
-    }
-    if (use_fused63_composite(p)) {             // both derived spectra in ONE fused launch (two segments)
-        spdy::T63Batch b{};
-        b.nseg = 2;
-        b.seg[0] = spdy::T63Seg{p->tmp_c, g0, nullptr, nullptr, nb, kcos, 0, 0};
-        b.seg[1] = spdy::T63Seg{p->tmp_d, g1, nullptr, nullptr, nb, kcos, 0, 0};
-        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    RC(spdy_spec_to_grid_dev(p, nb, p->tmp_c, nullptr, kcos, g0));
-    RC(spdy_spec_to_grid_dev(p, nb, p->tmp_d, nullptr, kcos, g1));
-    return SPDY_OK;
+    if (mode == 1) return inverse_batch(p, InverseReq{nb, in0, in1, g0, g1, kcos, 0, {}, nullptr, 1, nullptr, 0, nullptr, nullptr, nullptr, 2});
+    return inverse_batch(p, InverseReq{0, nullptr, nullptr, nullptr, nullptr, 2, 0, {}, nullptr, 1, nullptr, nb, in0, g0, g1, kcos});
 }
 int spdy_uvspec_to_grid_dev(spdy_plan *p, int nb, const double *vor, const double *dv, double *ug, double *vg, int kcos)
 {
@@ -1115,114 +1217,23 @@ int spdy_vdspec_dev(spdy_plan *p, int nb, const double *ug, const double *vg, do
     NEED_DEVICE(p);
     RC(check_batch(p, nb));
     if (nb && (!ug || !vg || !vorm || !divm)) return fail(SPDY_ERR_ARG, "null device pointer");
-    const double *sc = kcos == 2 ? p->dev.cosgr : p->dev.cosgr2;
-    if (use_fused(p, nb)) {
-        // one pass: the pair (ug[i], vg[i]) is one tile, vds is applied to the two spectra while they are in LDS
-        KERNEL(spdy::launch_g2s_fused(p->dev, nb, ug, sc, vorm, p->num_cu * p->wg_per_cu, p->stream, vg, divm, 0, nullptr, nullptr,
-                                      !in_host_stage(p, ug)));
-        return SPDY_OK;
-    }
-    if (use_fused63_composite(p) && spdy::g2s_t63_staged(p->dev, p->num_cu, nb)) {
-        // T63, model-sized (row f1, round 6): the pairs (ug[i], vg[i]) as ONE segment of the staged form -- rows launch, then the
-        // contraction applies vds to the pair's spectra in registers: no vds launch, no raw spectra in HBM
-        spdy::T63Batch b{};
-        b.nseg = 1;
-        b.seg[0] = spdy::T63Seg{ug, vorm, sc, nullptr, nb, 1, 0, spdy::T63_OP_VDS};
-        b.vds_src2 = vg; b.vds_dst2 = divm;
-        return timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    if (use_fused63_composite(p)) {             // both scaled transforms in ONE fused launch (two segments) + vds
-        RC(ensure_four(p));
-        spdy::T63Batch b{};
-        b.nseg = 2;
-        b.seg[0] = spdy::T63Seg{ug, p->tmp_c, sc, nullptr, nb, 1, 0, 0};
-        b.seg[1] = spdy::T63Seg{vg, p->tmp_d, sc, nullptr, nb, 1, 0, 0};
-        RC(timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63_batch(p->dev, b, p->num_cu, p->stream); }));
-        KERNEL(spdy::launch_vds(p->dev, nb, p->tmp_c, p->tmp_d, vorm, divm, p->stream));
-        return SPDY_OK;
-    }
-    RC(ensure_four(p));
-    KERNEL(spdy::launch_fourier_dir(p->dev, nb, ug, sc, p->four, p->stream));
-    KERNEL(spdy::launch_legendre_dir(p->dev, nb, p->four, p->tmp_c, p->stream));
-    KERNEL(spdy::launch_fourier_dir(p->dev, nb, vg, sc, p->four, p->stream));
-    KERNEL(spdy::launch_legendre_dir(p->dev, nb, p->four, p->tmp_d, p->stream));
-    KERNEL(spdy::launch_vds(p->dev, nb, p->tmp_c, p->tmp_d, vorm, divm, p->stream));
-    return SPDY_OK;
+    return direct_batch(p, DirectReq{nb, ug, vg, vorm, divm, kcos, false, 0, nullptr, nullptr});
 }
 
 int spdy_inverse_batch_dev(spdy_plan *p, int npairs, const double *vor, const double *dv, double *ug, double *vg, int kcos_pairs,
                            int nplain, const double *spec, const int *d_kcos, int kcos_all, double *grid)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, npairs));
-    RC(check_batch(p, nplain));
-    if ((npairs && (!vor || !dv || !ug || !vg)) || (nplain && (!spec || !grid))) return fail(SPDY_ERR_ARG, "null device pointer");
-    kcos_pairs = kcos_pairs == 1 ? 1 : 2;
-    if (use_fused(p, npairs) && npairs > 0 && nplain > 0)
-        return timed(p, SPDY_K_S2G_FUSED, [&] {
-            return spdy::launch_s2g_fused(p->dev, npairs, vor, nullptr, kcos_pairs, ug, p->num_cu * p->wg_per_cu, p->stream, 3, dv, vg,
-                                          nplain, spec, d_kcos, kcos_all, grid);
-        });
-    if (npairs > 0 && nplain > 0 && use_fused63_composite(p)) {
-        // T63: U, V and the plain spectra as three segments of ONE fused launch; uvspec on load (model sizes) or as a kernel in front
-        spdy::T63Batch b{};
-        b.nseg = 3;
-        if (derive63(p, npairs, 2, (nplain + 1) / 2)) append_uv_segs(b, 0, npairs, vor, dv, ug, vg, kcos_pairs);
-        else {
-            RC(ensure_four(p));
-            KERNEL(spdy::launch_uvspec(p->dev, npairs, vor, dv, p->tmp_c, p->tmp_d, p->stream));
-            b.seg[0] = spdy::T63Seg{p->tmp_c, ug, nullptr, nullptr, npairs, kcos_pairs, 0, 0};
-            b.seg[1] = spdy::T63Seg{p->tmp_d, vg, nullptr, nullptr, npairs, kcos_pairs, 0, 0};
-        }
-        b.seg[2] = spdy::T63Seg{spec, grid, nullptr, d_kcos, nplain, kcos_all, 0, 0};
-        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    if (npairs) RC(spdy_uvspec_to_grid_dev(p, npairs, vor, dv, ug, vg, kcos_pairs));
-    if (nplain) RC(spdy_spec_to_grid_dev(p, nplain, spec, d_kcos, kcos_all, grid));
-    return SPDY_OK;
+    return spdy_inverse_batch_grad_dev(p, npairs, vor, dv, ug, vg, kcos_pairs, nplain, spec, d_kcos, kcos_all, grid, 0, nullptr, nullptr,
+                                       nullptr, 2);
 }
 
 int spdy_inverse_batch_grad_dev(spdy_plan *p, int npairs, const double *vor, const double *dv, double *ug, double *vg, int kcos_pairs,
                                 int nplain, const double *spec, const int *d_kcos, int kcos_all, double *grid,
                                 int ngrad, const double *psi, double *gx, double *gy, int kcos_grad)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, npairs));
-    RC(check_batch(p, nplain));
-    RC(check_batch(p, ngrad));
-    if ((npairs && (!vor || !dv || !ug || !vg)) || (nplain && (!spec || !grid)) || (ngrad && (!psi || !gx || !gy)))
-        return fail(SPDY_ERR_ARG, "null device pointer");
-    kcos_pairs = kcos_pairs == 1 ? 1 : 2;
-    kcos_grad = kcos_grad == 1 ? 1 : 2;
-    if (use_fused(p, npairs) && npairs > 0 && nplain > 0 && ngrad > 0)   // T30: uvspec pairs, gradients and plain fields in ONE launch
-        return timed(p, SPDY_K_S2G_FUSED, [&] {
-            return spdy::launch_s2g_fused(p->dev, npairs, vor, nullptr, kcos_pairs, ug, p->num_cu * p->wg_per_cu, p->stream, 3, dv, vg,
-                                          nplain, spec, d_kcos, kcos_all, grid, ngrad, psi, gx, gy, kcos_grad, p->d_zero_spec);
-        });
-    if (use_fused63_composite(p) && npairs > 0 && nplain > 0 && ngrad > 0 && npairs + ngrad <= p->max_batch) {
-        // T63: U, V, d/dlambda, d/dmu and the plain spectra are five segments of ONE fused launch (the gradient alone would be a
-        // one-workgroup launch of a full pipeline latency).  Model sizes: uvspec and grad are evaluated on load (row f1, round 6 --
-        // no operator launch); larger batches: ONE operator launch (uvspec | grad) into the plan's temporaries in front.
-        spdy::T63Batch b{};
-        b.nseg = 5;
-        if (derive63(p, npairs, 2, (nplain + 1) / 2 + 2 * ((ngrad + 1) / 2))) {
-            append_uv_segs(b, 0, npairs, vor, dv, ug, vg, kcos_pairs);
-            append_grad_segs(b, 3, ngrad, psi, gx, gy, kcos_grad);
-        } else {
-            RC(ensure_four(p));
-            const size_t off = (size_t)npairs * spec_elems(p);
-            KERNEL(spdy::launch_uvspec_grad(p->dev, npairs, vor, dv, p->tmp_c, p->tmp_d, ngrad, psi, p->tmp_c + off, p->tmp_d + off, p->stream));
-            b.seg[0] = spdy::T63Seg{p->tmp_c, ug, nullptr, nullptr, npairs, kcos_pairs, 0, 0};
-            b.seg[1] = spdy::T63Seg{p->tmp_d, vg, nullptr, nullptr, npairs, kcos_pairs, 0, 0};
-            b.seg[3] = spdy::T63Seg{p->tmp_c + off, gx, nullptr, nullptr, ngrad, kcos_grad, 0, 0};
-            b.seg[4] = spdy::T63Seg{p->tmp_d + off, gy, nullptr, nullptr, ngrad, kcos_grad, 0, 0};
-        }
-        b.seg[2] = spdy::T63Seg{spec, grid, nullptr, d_kcos, nplain, kcos_all, 0, 0};
-        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    RC(spdy_inverse_batch_dev(p, npairs, vor, dv, ug, vg, kcos_pairs, nplain, spec, d_kcos, kcos_all, grid));
-    if (ngrad) RC(spdy_grad_to_grid_dev(p, ngrad, psi, gx, gy, kcos_grad));
-    return SPDY_OK;
+    const spdy_spec_seg seg{nplain, spec};
+    return spdy_inverse_batch_segs_dev(p, npairs, vor, dv, ug, vg, kcos_pairs, nplain ? 1 : 0, &seg, d_kcos, kcos_all, grid,
+                                       ngrad, psi, gx, gy, kcos_grad);
 }
 
 int spdy_inverse_batch_segs_dev(spdy_plan *p, int npairs, const double *vor, const double *dv, double *ug, double *vg, int kcos_pairs,
@@ -1232,71 +1243,21 @@ int spdy_inverse_batch_segs_dev(spdy_plan *p, int npairs, const double *vor, con
     NEED_DEVICE(p);
     if (nseg < 0 || nseg > SPDY_MAX_SPEC_SEGS || (nseg && !segs)) return fail(SPDY_ERR_ARG, "0..SPDY_MAX_SPEC_SEGS segments");
     // drop empty segments, total the plain fields
-    spdy_spec_seg sg[SPDY_MAX_SPEC_SEGS];
-    int ns = 0, nplain = 0;
+    InverseReq r{npairs, vor, dv, ug, vg, kcos_pairs, 0, {}, d_kcos, kcos_all, grid, ngrad, psi, gx, gy, kcos_grad};
+    int nplain = 0;
     for (int i = 0; i < nseg; ++i) {
         if (segs[i].nb < 0) return fail(SPDY_ERR_ARG, "negative segment size");
         if (segs[i].nb == 0) continue;
         if (!segs[i].d_spec) return fail(SPDY_ERR_ARG, "null device pointer");
-        sg[ns++] = segs[i];
+        r.seg[r.nseg++] = segs[i];
         nplain += segs[i].nb;
     }
-    if (ns <= 1)
-        return spdy_inverse_batch_grad_dev(p, npairs, vor, dv, ug, vg, kcos_pairs, nplain, ns ? sg[0].d_spec : nullptr, d_kcos, kcos_all, grid,
-                                           ngrad, psi, gx, gy, kcos_grad);
     RC(check_batch(p, npairs));
     RC(check_batch(p, nplain));
     RC(check_batch(p, ngrad));
-    if ((npairs && (!vor || !dv || !ug || !vg)) || !grid || (ngrad && (!psi || !gx || !gy))) return fail(SPDY_ERR_ARG, "null device pointer");
-    kcos_pairs = kcos_pairs == 1 ? 1 : 2;
-    kcos_grad = kcos_grad == 1 ? 1 : 2;
-    if (use_fused(p, npairs) && npairs > 0) {                                 // T30: one mixed launch, source array looked up per field
-        spdy::PlainSegs ps{{nullptr, nullptr, nullptr}, {0x7fffffff, 0x7fffffff, 0x7fffffff}};
-        for (int i = 1, first = sg[0].nb; i < ns; first += sg[i].nb, ++i) { ps.spec[i - 1] = sg[i].d_spec; ps.first[i - 1] = first; }
-        return timed(p, SPDY_K_S2G_FUSED, [&] {
-            return spdy::launch_s2g_fused(p->dev, npairs, vor, nullptr, kcos_pairs, ug, p->num_cu * p->wg_per_cu, p->stream, 3, dv, vg,
-                                          nplain, sg[0].d_spec, d_kcos, kcos_all, grid, ngrad, psi, gx, gy, kcos_grad, p->d_zero_spec, &ps);
-        });
-    }
-    if (use_fused63_composite(p) && npairs > 0 && npairs + ngrad <= p->max_batch) {
-        // T63: U, V, the gradient pair and every source array are segments of ONE fused launch; uvspec | grad on load at model sizes
-        // (row f1, round 6), otherwise as one operator launch in front
-        int plain_pairs = 0;
-        for (int i = 0; i < ns; ++i) plain_pairs += (sg[i].nb + 1) / 2;
-        const bool derive = derive63(p, npairs, 2, plain_pairs + 2 * ((ngrad + 1) / 2));
-        const size_t off = (size_t)npairs * spec_elems(p);
-        spdy::T63Batch b{};
-        int k = 0;
-        if (derive) k = append_uv_segs(b, k, npairs, vor, dv, ug, vg, kcos_pairs);
-        else {
-            RC(ensure_four(p));
-            if (ngrad) KERNEL(spdy::launch_uvspec_grad(p->dev, npairs, vor, dv, p->tmp_c, p->tmp_d, ngrad, psi, p->tmp_c + off, p->tmp_d + off, p->stream));
-            else KERNEL(spdy::launch_uvspec(p->dev, npairs, vor, dv, p->tmp_c, p->tmp_d, p->stream));
-            b.seg[k++] = spdy::T63Seg{p->tmp_c, ug, nullptr, nullptr, npairs, kcos_pairs, 0, 0};
-            b.seg[k++] = spdy::T63Seg{p->tmp_d, vg, nullptr, nullptr, npairs, kcos_pairs, 0, 0};
-        }
-        size_t first = 0;
-        for (int i = 0; i < ns; ++i) {
-            b.seg[k++] = spdy::T63Seg{sg[i].d_spec, grid + first * grid_elems(p), nullptr, d_kcos ? d_kcos + first : nullptr, sg[i].nb, kcos_all, 0, 0};
-            first += sg[i].nb;
-        }
-        if (ngrad && derive) k = append_grad_segs(b, k, ngrad, psi, gx, gy, kcos_grad);
-        else if (ngrad) {
-            b.seg[k++] = spdy::T63Seg{p->tmp_c + off, gx, nullptr, nullptr, ngrad, kcos_grad, 0, 0};
-            b.seg[k++] = spdy::T63Seg{p->tmp_d + off, gy, nullptr, nullptr, ngrad, kcos_grad, 0, 0};
-        }
-        b.nseg = k;
-        return timed(p, SPDY_K_S2G_FUSED, [&] { return spdy::launch_s2g_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    // any other plan: the separate calls
-    if (npairs) RC(spdy_uvspec_to_grid_dev(p, npairs, vor, dv, ug, vg, kcos_pairs));
-    size_t first = 0;
-    for (int i = 0; i < ns; ++i) {
-        RC(spdy_spec_to_grid_dev(p, sg[i].nb, sg[i].d_spec, d_kcos ? d_kcos + first : nullptr, kcos_all, grid + first * grid_elems(p)));
-        first += sg[i].nb;
-    }
-    if (ngrad) RC(spdy_grad_to_grid_dev(p, ngrad, psi, gx, gy, kcos_grad));
-    return SPDY_OK;
+    if ((npairs && (!vor || !dv || !ug || !vg)) || (nplain && !grid) || (ngrad && (!psi || !gx || !gy)))
+        return fail(SPDY_ERR_ARG, "null device pointer");
+    return inverse_batch(p, r);
 }
 
 int spdy_direct_batch_dev(spdy_plan *p, int npairs, const double *ug, const double *vg, double *vorm, double *divm, int kcos,
@@ -1306,38 +1267,7 @@ int spdy_direct_batch_dev(spdy_plan *p, int npairs, const double *ug, const doub
     RC(check_batch(p, npairs));
     RC(check_batch(p, nplain));
     if ((npairs && (!ug || !vg || !vorm || !divm)) || (nplain && (!grid || !spec))) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (use_fused(p, npairs) && npairs > 0 && nplain > 0 && one_mixed_launch(p, 2L * npairs + nplain)) {
-        const double *sc = kcos == 2 ? p->dev.cosgr : p->dev.cosgr2;
-        return timed(p, SPDY_K_G2S_FUSED, [&] {
-            return spdy::launch_g2s_fused(p->dev, npairs, ug, sc, vorm, p->num_cu * p->wg_per_cu, p->stream, vg, divm, nplain, grid, spec);
-        });
-    }
-    if (npairs > 0 && nplain > 0 && use_fused63_composite(p) && spdy::g2s_t63_staged(p->dev, p->num_cu, npairs + (nplain + 1) / 2)) {
-        // T63, model-sized: the (u, v) pairs (vds in the contraction) and the plain grids as two segments of the staged form
-        const double *sc = kcos == 2 ? p->dev.cosgr : p->dev.cosgr2;
-        spdy::T63Batch b{};
-        b.nseg = 2;
-        b.seg[0] = spdy::T63Seg{ug, vorm, sc, nullptr, npairs, 1, 0, spdy::T63_OP_VDS};
-        b.vds_src2 = vg; b.vds_dst2 = divm;
-        b.seg[1] = spdy::T63Seg{grid, spec, nullptr, nullptr, nplain, 1, 0, 0};
-        return timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63_batch(p->dev, b, p->num_cu, p->stream); });
-    }
-    if (npairs > 0 && nplain > 0 && use_fused63_composite(p)) {
-        // T63: the scaled u, v grids and the plain grids as three segments of ONE fused launch, then vds
-        RC(ensure_four(p));
-        const double *sc = kcos == 2 ? p->dev.cosgr : p->dev.cosgr2;
-        spdy::T63Batch b{};
-        b.nseg = 3;
-        b.seg[0] = spdy::T63Seg{ug, p->tmp_c, sc, nullptr, npairs, 1, 0, 0};
-        b.seg[1] = spdy::T63Seg{vg, p->tmp_d, sc, nullptr, npairs, 1, 0, 0};
-        b.seg[2] = spdy::T63Seg{grid, spec, nullptr, nullptr, nplain, 1, 0, 0};
-        RC(timed(p, SPDY_K_G2S_FUSED, [&] { return spdy::launch_g2s_fused_t63_batch(p->dev, b, p->num_cu, p->stream); }));
-        KERNEL(spdy::launch_vds(p->dev, npairs, p->tmp_c, p->tmp_d, vorm, divm, p->stream));
-        return SPDY_OK;
-    }
-    if (npairs) RC(spdy_vdspec_dev(p, npairs, ug, vg, vorm, divm, kcos));
-    if (nplain) RC(spdy_grid_to_spec_dev(p, nplain, grid, spec));
-    return SPDY_OK;
+    return direct_batch(p, DirectReq{npairs, ug, vg, vorm, divm, kcos, false, nplain, grid, spec});
 }
 
 #define HOST_1IN_1OUT(name, devfn)                                                 \

@@ -281,8 +281,7 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *p, const double *ug, const do
     NEED_DEVICE(p);
     const int kx = p->tab.kx, P = 3 * kx;
     if (!ug || !vg || !grid || !pvor || !pdiv || !pspec) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (p->tab.trunc == 63 && p->fused_mode != 0 && kx <= 16 && P <= p->max_batch && p->tab.implicit_ready && p->tab.sigma_ready && vor && div && t && tr &&
-        ps && phis && d_tcorh && d_qcorh && phi && (j1 == 1 || j1 == 2)) {
+    if (use_raw63(p, P) && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi && (j1 == 1 || j1 == 2)) {
         // T63: the transform kernel leaves the pairs' spectra un-vds'ed in the plan's temporaries; the spectral step applies
         // vds where it reads them -- direct batch + everything after it = 2 launches instead of 3
         RC(direct_batch_raw63(p, P, ug, vg, kcos, P + 1, grid, pspec));

@@ -1021,20 +1021,18 @@ extern "C" __attribute__((visibility("default"))) int spdy_debug_timeline(long l
 }
 #endif
 
-hipError_t launch_s2g_fused(const DevPlan &p, int nb, const double *spec, const int *d_kcos, int kcos_all, double *grid,
-                            int max_wg, hipStream_t s, int mode, const double *spec2, double *grid2, int nplain,
-                            const double *spec_p, const int *kcos_p, int kcos_all_p, double *grid_p,
-                            int ngrad, const double *psi, double *gx, double *gy, int kcos_grad, const double *zero,
-                            const PlainSegs *segs)
+hipError_t launch_s2g_fused(const DevPlan &p, const S2gFused &r, int max_wg, hipStream_t s)
 {
+    const int mode = r.mode, nb = r.nb, ngrad = r.ngrad;
+    const int nplain = r.nplain[0] + r.nplain[1] + r.nplain[2] + r.nplain[3];
     if (nb <= 0 && nplain <= 0) return hipSuccess;
-    if (mode < 0 || mode > 3 || (mode != 0 && !grid2) || ((mode == 1 || mode == 3) && !spec2)) return hipErrorInvalidValue;
-    if (mode == 3 && (nb <= 0 || nplain <= 0 || !spec_p || !grid_p)) return hipErrorInvalidValue;
-    if (ngrad < 0 || (ngrad > 0 && (mode != 3 || !psi || !gx || !gy || !zero || !p.gradx_e))) return hipErrorInvalidValue;
-    S2gMixed mx{spec_p, kcos_p, kcos_all_p, grid_p, mode == 3 ? nb : 0, mode == 3 ? nplain : 0, ngrad, kcos_grad, psi, gx, gy, zero,
-                {nullptr, nullptr, nullptr}, {0x7fffffff, 0x7fffffff, 0x7fffffff}};
-    if (segs)
-        for (int i = 0; i < 3; ++i) { mx.seg_spec[i] = segs->spec[i]; mx.seg_first[i] = segs->first[i]; }
+    if (mode < 0 || mode > 3 || (mode != 0 && !r.grid2) || ((mode == 1 || mode == 3) && !r.spec2)) return hipErrorInvalidValue;
+    if (mode == 3 && (nb <= 0 || nplain <= 0 || !r.plain[0] || !r.grid_p)) return hipErrorInvalidValue;
+    if (ngrad < 0 || (ngrad > 0 && (mode != 3 || !r.psi || !r.gx || !r.gy || !r.zero || !p.gradx_e))) return hipErrorInvalidValue;
+    S2gMixed mx{r.plain[0], r.kcos_p, r.kcos_all_p, r.grid_p, mode == 3 ? nb : 0, mode == 3 ? nplain : 0, ngrad, r.kcos_grad, r.psi, r.gx,
+                r.gy, r.zero, {nullptr, nullptr, nullptr}, {0x7fffffff, 0x7fffffff, 0x7fffffff}};
+    for (int i = 1, first = r.nplain[0]; i < 4; first += r.nplain[i++])
+        if (r.nplain[i] > 0) { mx.seg_spec[i - 1] = r.plain[i]; mx.seg_first[i - 1] = first; }
     const int ntiles = mode == 3 ? nb + ngrad + (nplain + t30::BT - 1) / t30::BT : mode ? nb : (nb + t30::BT - 1) / t30::BT, nwg = max_wg;
     const dim3 grd(ntiles < nwg ? ntiles : nwg), blk(t30::NTHR);
     // grid-side bytes of this launch: pairs write two grids each
@@ -1045,9 +1043,9 @@ hipError_t launch_s2g_fused(const DevPlan &p, int nb, const double *spec, const 
     const dim3 grd3(3 * ntiles);
 #define SPDY_S2G_LAUNCH(M)                                                                                                        \
     do {                                                                                                                          \
-        if (by_part) hipLaunchKernelGGL((s2g_fused_t30_kernel<M, false, true>), grd3, blk, t30::S2G_LDS, s, p, nb, spec, spec2, d_kcos, kcos_all, grid, grid2, mx); \
-        else if (stream) hipLaunchKernelGGL((s2g_fused_t30_kernel<M, true>), grd, blk, t30::S2G_LDS, s, p, nb, spec, spec2, d_kcos, kcos_all, grid, grid2, mx); \
-        else hipLaunchKernelGGL((s2g_fused_t30_kernel<M, false>), grd, blk, t30::S2G_LDS, s, p, nb, spec, spec2, d_kcos, kcos_all, grid, grid2, mx);       \
+        if (by_part) hipLaunchKernelGGL((s2g_fused_t30_kernel<M, false, true>), grd3, blk, t30::S2G_LDS, s, p, nb, r.spec, r.spec2, r.d_kcos, r.kcos_all, r.grid, r.grid2, mx); \
+        else if (stream) hipLaunchKernelGGL((s2g_fused_t30_kernel<M, true>), grd, blk, t30::S2G_LDS, s, p, nb, r.spec, r.spec2, r.d_kcos, r.kcos_all, r.grid, r.grid2, mx); \
+        else hipLaunchKernelGGL((s2g_fused_t30_kernel<M, false>), grd, blk, t30::S2G_LDS, s, p, nb, r.spec, r.spec2, r.d_kcos, r.kcos_all, r.grid, r.grid2, mx);       \
     } while (0)
     if (mode == 1) SPDY_S2G_LAUNCH(1);
     else if (mode == 2) SPDY_S2G_LAUNCH(2);
@@ -1057,17 +1055,16 @@ hipError_t launch_s2g_fused(const DevPlan &p, int nb, const double *spec, const 
     return hipGetLastError();
 }
 
-hipError_t launch_g2s_fused(const DevPlan &p, int nb, const double *grid, const double *gscale, double *spec, int max_wg,
-                            hipStream_t s, const double *grid2, double *spec2, int nplain, const double *grid_p, double *spec_p,
-                            bool allow_split)
+hipError_t launch_g2s_fused(const DevPlan &p, const G2sFused &r, int max_wg, hipStream_t s)
 {
+    const int nb = r.nb, nplain = r.nplain;
     const bool mixed = nplain > 0;                            // pairs (grid, grid2 -> spec, spec2) + plain fields (grid_p -> spec_p)
     if (nb <= 0 && !mixed) return hipSuccess;
     if (p.trunc != t30::TRUNC || p.ix != t30::IX || p.il != t30::IL || !p.pa_dir2) return hipErrorInvalidValue;
-    const bool pair = grid2 != nullptr;                       // vdspec in one pass: (grid, grid2) -> (spec, spec2)
-    if (pair && (!gscale || !spec2)) return hipErrorInvalidValue;
-    if (mixed && (!grid_p || !spec_p || (nb > 0 && !pair))) return hipErrorInvalidValue;
-    const G2sMixed mx{grid_p, spec_p, mixed ? nb : 0, nplain};
+    const bool pair = r.grid2 != nullptr;                     // vdspec in one pass: (grid, grid2) -> (spec, spec2)
+    if (pair && (!r.gscale || !r.spec2)) return hipErrorInvalidValue;
+    if (mixed && (!r.grid_p || !r.spec_p || (nb > 0 && !pair))) return hipErrorInvalidValue;
+    const G2sMixed mx{r.grid_p, r.spec_p, mixed ? nb : 0, nplain};
     const int ntiles = mixed ? nb + (nplain + t30::BT - 1) / t30::BT : pair ? nb : (nb + t30::BT - 1) / t30::BT, nwg = max_wg > 0 ? max_wg : 256;
     const dim3 grd(ntiles < nwg ? ntiles : nwg), blk(t30::NTHR);
     const bool stream = stream_policy((long)((pair || mixed) ? 2L * nb : nb) * t30::IL * t30::IX * 8 + (mixed ? (long)nplain * t30::IL * t30::IX * 8 : 0));
@@ -1079,17 +1076,17 @@ hipError_t launch_g2s_fused(const DevPlan &p, int nb, const double *grid, const 
     const bool no_split = p.lo.t30_nosplit != 0;
     // (up to a sixth as many tiles as CUs: at twice the T30 L8 step's 37 tiles -- T30 L16, 73 tiles, 219 workgroups -- the
     // captured step is 2 us SLOWER with the split form, 41.8 vs 39.7 us, although the launch on its own still gains)
-    const bool by_split = allow_split && 6 * ntiles <= nwg && !no_split && !stream;
+    const bool by_split = r.allow_split && 6 * ntiles <= nwg && !no_split && !stream;
     const dim3 grd3(3 * ntiles);
 #define SPDY_G2S_LAUNCH(M)                                                                                                        \
     do {                                                                                                                          \
-        if (by_split) hipLaunchKernelGGL((g2s_fused_t30_kernel<M, false, 3>), grd3, blk, t30::G2S_LDS, s, p, nb, grid, grid2, gscale, spec, spec2, mx); \
-        else if (stream) hipLaunchKernelGGL((g2s_fused_t30_kernel<M, true>), grd, blk, t30::G2S_LDS, s, p, nb, grid, grid2, gscale, spec, spec2, mx); \
-        else hipLaunchKernelGGL((g2s_fused_t30_kernel<M, false>), grd, blk, t30::G2S_LDS, s, p, nb, grid, grid2, gscale, spec, spec2, mx);       \
+        if (by_split) hipLaunchKernelGGL((g2s_fused_t30_kernel<M, false, 3>), grd3, blk, t30::G2S_LDS, s, p, nb, r.grid, r.grid2, r.gscale, r.spec, r.spec2, mx); \
+        else if (stream) hipLaunchKernelGGL((g2s_fused_t30_kernel<M, true>), grd, blk, t30::G2S_LDS, s, p, nb, r.grid, r.grid2, r.gscale, r.spec, r.spec2, mx); \
+        else hipLaunchKernelGGL((g2s_fused_t30_kernel<M, false>), grd, blk, t30::G2S_LDS, s, p, nb, r.grid, r.grid2, r.gscale, r.spec, r.spec2, mx);       \
     } while (0)
     if (mixed) SPDY_G2S_LAUNCH(3);
     else if (pair) SPDY_G2S_LAUNCH(2);
-    else if (gscale) SPDY_G2S_LAUNCH(1);
+    else if (r.gscale) SPDY_G2S_LAUNCH(1);
     else SPDY_G2S_LAUNCH(0);
 #undef SPDY_G2S_LAUNCH
     return hipGetLastError();

@@ -1396,12 +1396,13 @@ static int t63_finish_batch(T63Batch &b)
     return (int)fields;
 }
 
-// Whether a launch of `pairs` field pairs, `op_pairs` of them derived on load (T63_OP_*), takes the by-chunk form with its
-// one-item-per-workgroup operator region -- the only form that derives (callers otherwise run the operator kernel first)
-bool s2g_t63_derives(int max_wg, int pairs, int op_pairs)
+// Whether a launch of `pairs` field pairs takes the by-chunk form with its one-item-per-workgroup operator region -- the only form
+// that derives (callers otherwise run the operator kernel first) -- and its derived pairs (T63_OP_*) fit that region.  The size
+// threshold is set by the lead operator's `lead_op_pairs` (U / V, or the gradient when it is alone); the region holds all `op_pairs`.
+bool s2g_t63_derives(int max_wg, int pairs, int lead_op_pairs, int op_pairs)
 {
     const int nwg = max_wg > 0 ? max_wg : 256;
-    return op_pairs > 0 && 2 * pairs <= nwg && 2 * op_pairs * t63::NCH <= nwg;
+    return lead_op_pairs > 0 && 2 * pairs <= nwg && 2 * lead_op_pairs * t63::NCH <= nwg && op_pairs * t63::NCH <= nwg;
 }
 
 hipError_t launch_s2g_fused_t63_batch(const DevPlan &p, T63Batch b, int max_wg, hipStream_t s)
@@ -1472,7 +1473,7 @@ hipError_t launch_g2s_fused_t63_batch(const DevPlan &p, T63Batch b, int max_wg, 
     const bool stream = stream_policy((long)fields * t63::IL * t63::IX * 8);
     const bool no_split = p.lo.t63_nosplit != 0;
     // (round 5's three-pairs-per-workgroup form of this transform -- one wave per SIMD, accumulators in AGPRs; same bits, 6 us
-    // slower at B = 1536 -- left the product in round 6: tools/experiments/r06_t63_three_pair_kernel.patch, DESIGN 4.3)
+    // slower at B = 1536 -- left the product in round 6: tools/experiments/r05_spdy_t63_tri.inc, DESIGN 4.3)
     if (any_vds && !g2s_t63_staged(p, max_wg, b.npairs)) return hipErrorInvalidValue;     // (vds rides in the staged form only)
     if (g2s_t63_staged(p, max_wg, b.npairs)) {
         // small batch, staged: the row FFTs over (pair, chunk, field) items, four per workgroup (one round of workgroups), then

@@ -82,28 +82,48 @@ hipError_t launch_fourier_dir(const DevPlan &p, int nb, const double *grid, cons
                               hipStream_t s);
 
 // Fused persistent T30 kernels (whole transform in one pass through LDS; at most max_wg workgroups)
-// mode 0: plain.  mode 1: uvspec fused -- tile i = (vor[i], div[i]) = (spec, spec2) -> (ug, vg) = (grid, grid2).
-// mode 2: grad fused -- tile i = psi[i] = spec -> (d/dx, d/dy) = (grid, grid2).  In modes 1/2 nb counts tiles and
-// kcos_all applies to both outputs.
-// mode 3: a model step's whole inverse batch in one launch -- nb (vor, div) pairs as in mode 1 plus nplain ordinary
-// fields spec_p -> grid_p with their own kcos (kcos_p per field, or kcos_all_p)
-// mode 3: further source arrays of the plain spectra (S2gMixed::seg_spec / seg_first; first = 0x7fffffff: unused)
-struct PlainSegs { const double *spec[3]; int first[3]; };
-hipError_t launch_s2g_fused(const DevPlan &p, int nb, const double *spec, const int *d_kcos, int kcos_all, double *grid,
-                            int max_wg, hipStream_t s, int mode = 0, const double *spec2 = nullptr, double *grid2 = nullptr,
-                            int nplain = 0, const double *spec_p = nullptr, const int *kcos_p = nullptr, int kcos_all_p = 1,
-                            double *grid_p = nullptr, int ngrad = 0, const double *psi = nullptr, double *gx = nullptr,
-                            double *gy = nullptr, int kcos_grad = 2, const double *zero = nullptr, const PlainSegs *segs = nullptr);
-// (mode 3, ngrad > 0: gradient tiles psi[i] -> gx[i], gy[i] ride along as uvspec tiles with vor = `zero` and the grad tables)
-// grid2 / spec2 non-null: vdspec in one pass -- tile i is the pair (grid[i], grid2[i]) scaled by gscale, the
-// outputs are vds of the pair's spectra: vorticity -> spec, divergence -> spec2 (nb pairs)
-// nplain > 0: a model step's whole direct batch in one launch -- nb (u,v) pairs as above plus nplain ordinary fields
-// grid_p -> spec_p (unscaled)
-hipError_t launch_g2s_fused(const DevPlan &p, int nb, const double *grid, const double *gscale, double *spec, int max_wg,
-                            hipStream_t s, const double *grid2 = nullptr, double *spec2 = nullptr, int nplain = 0,
-                            const double *grid_p = nullptr, double *spec_p = nullptr, bool allow_split = true);
-// (allow_split = false: never the three-workgroups-per-tile form -- its workgroups read every tile three times, which is the
-// wrong trade when the rows are host-mapped staging memory read across the link)
+// One inverse launch.  mode 0: plain -- nb fields spec -> grid, kcos per field (d_kcos) or kcos_all.  mode 1: uvspec fused -- tile
+// i = (vor[i], div[i]) = (spec, spec2) -> (ug, vg) = (grid, grid2).  mode 2: grad fused -- tile i = psi[i] = spec -> (d/dx, d/dy) =
+// (grid, grid2).  In modes 1/2 nb counts tiles and kcos_all applies to both outputs.
+// mode 3: a model step's whole inverse batch -- nb (vor, div) pairs as in mode 1, plain fields from up to four source arrays
+// (plain[i] holds nplain[i] of them; their grids are ONE stack grid_p) with their own kcos (kcos_p per field, or kcos_all_p), and
+// ngrad gradient tiles psi[i] -> gx[i], gy[i] that ride along as uvspec tiles with vor = `zero` and the grad tables
+struct S2gFused {
+    int mode = 0, nb = 0;
+    const double *spec = nullptr, *spec2 = nullptr;
+    const int *d_kcos = nullptr;
+    int kcos_all = 1;
+    double *grid = nullptr, *grid2 = nullptr;
+    const double *plain[4] = {nullptr, nullptr, nullptr, nullptr};
+    int nplain[4] = {0, 0, 0, 0};
+    const int *kcos_p = nullptr;
+    int kcos_all_p = 1;
+    double *grid_p = nullptr;
+    int ngrad = 0, kcos_grad = 2;
+    const double *psi = nullptr;
+    double *gx = nullptr, *gy = nullptr;
+    const double *zero = nullptr;
+};
+hipError_t launch_s2g_fused(const DevPlan &p, const S2gFused &r, int max_wg, hipStream_t s);
+// One direct launch: nb fields grid -> spec, gscale (nullptr or a per-latitude factor) applied on load.
+// grid2 / spec2 non-null: vdspec in one pass -- tile i is the pair (grid[i], grid2[i]) scaled by gscale, the outputs are vds of the
+// pair's spectra: vorticity -> spec, divergence -> spec2 (nb pairs).
+// nplain > 0: a model step's whole direct batch in one launch -- nb (u,v) pairs as above plus nplain ordinary fields grid_p -> spec_p
+// (unscaled).
+// allow_split = false: never the three-workgroups-per-tile form -- its workgroups read every tile three times, which is the wrong
+// trade when the rows are host-mapped staging memory read across the link
+struct G2sFused {
+    int nb = 0;
+    const double *grid = nullptr, *gscale = nullptr;
+    double *spec = nullptr;
+    const double *grid2 = nullptr;
+    double *spec2 = nullptr;
+    int nplain = 0;
+    const double *grid_p = nullptr;
+    double *spec_p = nullptr;
+    bool allow_split = true;
+};
+hipError_t launch_g2s_fused(const DevPlan &p, const G2sFused &r, int max_wg, hipStream_t s);
 
 // SIMD of each of the eight waves of nwg workgroups shaped like the fused T63 kernels' (d_out: 8 ints per workgroup)
 hipError_t launch_wave_placement(int *d_out, int nwg, hipStream_t s);
@@ -138,8 +158,9 @@ struct T63Batch {
     T63Seg seg[T63_MAX_SEG];
 };
 hipError_t launch_s2g_fused_t63_batch(const DevPlan &p, T63Batch b, int max_wg, hipStream_t s);
-// whether an inverse launch of `pairs` field pairs may carry `op_pairs` derived ones (model-sized launches: the by-chunk form)
-bool s2g_t63_derives(int max_wg, int pairs, int op_pairs);
+// whether an inverse launch of `pairs` field pairs may carry its derived ones (model-sized launches: the by-chunk form) --
+// lead_op_pairs of U / V (or of the gradient, when it is the only operator), op_pairs of all operators together
+bool s2g_t63_derives(int max_wg, int pairs, int lead_op_pairs, int op_pairs);
 hipError_t launch_g2s_fused_t63_batch(const DevPlan &p, T63Batch b, int max_wg, hipStream_t s);
 // whether a direct launch of `pairs` field pairs takes the STAGED form (rows launch + contraction launch: model-sized batches) --
 // the form that can apply vds to T63_OP_VDS segments (callers otherwise run vds as a kernel behind the launch)

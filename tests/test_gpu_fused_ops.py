@@ -54,8 +54,8 @@ def test_uvspec_and_grad_to_grid(res, nb, kcos, oracle_factory):
 @pytest.mark.parametrize("nb", [1, 2, 5, 16, 20])
 def test_t63_operators_derived_on_load(nb, oracle_factory):
     """Row f1 at T63 (round 6): model-sized inverse launches evaluate uvspec / grad where the fused kernel loads its operands
-    (csrc/spdy_fused_t63.inc: t63_inv_load_b_op -- the n +- 1 neighbours by lane exchange inside the wave, halo groups at the
-    edge of a wave's slots) instead of running an operator kernel in front.  Checked (a) against the reference's own call
+    (csrc/spdy_fused_t63.inc: t63_derive_to_lds -- each chunk's derived spectra formed once from the n +- 1 neighbours and
+    staged through LDS for the contraction) instead of running an operator kernel in front.  Checked (a) against the reference's own call
     sequence (uvspec / grad, then spec_to_grid: spectral.f90:98-110, 124-144, 173-196) through the oracle, at 1e-12, with the
     dead part of the rhomboid (l > trunc + 1) holding finite junk -- the reference's stencils read those entries at n + 1,
     whatever they hold, and so must the fold; (b) against the operator-kernel route of the same library (option
@@ -237,7 +237,7 @@ def test_inverse_batch_one_launch(res, npairs, nplain):
 
 
 @pytest.mark.parametrize("res,npairs,nplain,ngrad", [("t30", 8, 32, 1), ("t30", 1, 1, 1), ("t30", 5, 3, 4), ("t30", 300, 299, 7),
-                                                     ("t63", 3, 5, 1), ("t63f", 16, 64, 1), ("t63f", 3, 4, 3)])
+                                                     ("t63", 3, 5, 1), ("t63f", 16, 64, 1), ("t63f", 3, 4, 3), ("t63f", 2, 1, 42)])
 def test_inverse_batch_with_gradient(res, npairs, nplain, ngrad):
     """spdy_inverse_batch_grad_dev = spdy_inverse_batch_dev + spdy_grad_to_grid_dev (tendencies.f90:89-107, 121-123): ONE launch
     at T30 (gradient tiles ride along as uvspec tiles with a zero vorticity and the grad tables), one five-segment fused launch at T63."""
@@ -258,7 +258,9 @@ def test_inverse_batch_with_gradient(res, npairs, nplain, ngrad):
     sp.inverse_batch_grad_dev(vor, div, got[0], got[1], spl, got[2], psi, got[3], got[4], kcos_pairs=2, kcos=1, kcos_grad=kg)
     sp.synchronize()
     for a, b in zip(got, want):
-        if res == "t63":     # the separate calls form other field pairs than the one launch -- equal to rounding is the contract
+        # the separate calls form other field pairs than the one launch -- equal to rounding is the contract; with many gradients
+        # the one launch is too large to derive on load and runs the operator kernel where the separate pair call derives
+        if res == "t63" or ngrad > npairs + nplain:
             ok(a.cpu().numpy(), b.cpu().numpy(), 1e-13)
         else:
             assert torch.equal(a, b)
@@ -267,7 +269,8 @@ def test_inverse_batch_with_gradient(res, npairs, nplain, ngrad):
 
 @pytest.mark.parametrize("res,npairs,segsizes,ngrad", [("t30", 8, (8, 8, 8, 8), 1), ("t30", 5, (5, 5, 5, 5), 1), ("t30", 7, (7, 1, 3, 2), 0),
                                                        ("t30", 3, (1, 0, 4), 2), ("t30", 300, (299, 301), 7),
-                                                       ("t63f", 16, (16, 16, 16, 16), 1), ("t63f", 5, (5, 3, 1, 2), 0), ("t63", 3, (2, 3), 1)])
+                                                       ("t63f", 16, (16, 16, 16, 16), 1), ("t63f", 5, (5, 3, 1, 2), 0), ("t63", 3, (2, 3), 1),
+                                                       ("t63f", 2, (1, 1, 1), 42)])
 def test_inverse_batch_segments(res, npairs, segsizes, ngrad):
     """spdy_inverse_batch_segs_dev: the plain spectra read in place from up to four separate arrays (what tendencies.f90:89-101
     does with vor, div, t, tr) must give the bits of the single-array call on the concatenated stack -- odd segment sizes put
