@@ -148,7 +148,7 @@ const char *spdy_last_error(void);
  * Names: sia_half coa_half cosgr cosgr2 hsg dhs fsg dhsr fsgr work ifac epsi wt poly nsh2
  *        el2 elm2 el4 trfilt gradx gradym gradyp uvdx uvdym uvdyp vddym vddyp
  *        dmp dmpd dmps dmp1 dmp1d dmp1s tref tref1 tref2 tref3 xc xd xj dhsx elz
- *        xgeop1 xgeop2 corf tcorv qcorv coriol                                             */
+ *        xgeop1 xgeop2 corf tcorv qcorv coriol sigl sigh grdsig grdscp wvi entr               */
 int spdy_get_table(const spdy_plan *plan, const char *name, double *buf, int cap);
 
 /* ---- grid <-> spectral transforms --------------------------------------------------------
@@ -434,6 +434,36 @@ int spdy_grad_to_grid(spdy_plan *plan, int nb, const double *psi, double *gx, do
 int spdy_output_workspace(spdy_plan *plan);
 int spdy_output_batch_dev(spdy_plan *plan, const double *vor, const double *div, const double *t, const double *q, const double *phi,
                           const double *ps, float *u_out, float *v_out, float *t_out, float *q_out, float *phi_out, float *ps_out);
+
+/* ---- column physics: the precipitation block of get_physical_tendencies (physics.f90:110-138) ----------------------------
+ * Replaces, on the device, the thermodynamic fields (physics.f90:110-115: psg = exp(pslg), rps, qg = max(qg, 0), se = cp*tg +
+ * phig), spec_hum_to_rel_hum per level (:117-119; humidity.f90:16-28, 46-79), deep convection (:126; convection.f90:26-235), the
+ * scaling of the convective fluxes for k >= 2 (:128-131), icnv = kx - iptop (:133), large-scale condensation (:136;
+ * large_scale_condensation.f90:32-83) and ttend = ttend + tt_cnv + tt_lsc, qtend = qtend + qt_cnv + qt_lsc (:138-139).  A host
+ * "with physics" calls it between spdy_grid_tendencies_dev and the direct batch (tendencies.f90:203-206).  What stays on the host:
+ * radiation, surface fluxes, vertical diffusion and SPPT (physics.f90:141-250), which need the boundary fields (SST, land, albedo).
+ * One thread per column; 5 <= kx <= 16 (SPDY_ERR_ARG otherwise), sigma levels as for the geopotential (SPDY_ERR_STATE without).
+ * Results follow the reference's order of operations without contraction: decisions (convection or not, its top, condensation)
+ * are the reference's wherever no decision is within rounding of its threshold.  Both calls can be captured in a graph; `out` is
+ * read at call time.  The tables the block uses are spdy_get_table's sigl sigh grdsig grdscp wvi entr (physics.f90:12-39,
+ * convection.f90:63-71).                                                                                                        */
+typedef struct {                      /* per state; any member may be NULL = not written; nb states back to back            */
+    double *precnv, *precls, *cbmf;   /* (ix,il)                                                                            */
+    int *iptop, *icnv;                /* (ix,il): iptop after condensation, icnv before it (kx - iptop; -1 = no convection)   */
+    double *qsat, *rh, *se;           /* (ix,il,kx)                                                                         */
+} spdy_moist_out;
+/* Gridded inputs of nb <= max_batch states (tg, qg, phig (ix,il,kx), pslg (ix,il) each); ttend / qtend (ix,il,kx) are updated in
+ * place.  Inputs are not modified (the clamp of qg is local, as in the reference).                                                */
+int spdy_moist_columns_dev(spdy_plan *plan, int nb, const double *tg, const double *qg, const double *phig,
+                           const double *pslg, double *ttend, double *qtend, const spdy_moist_out *out);
+/* One model state from its spectra -- time level 1 as get_grid_point_tendencies passes it (tendencies.f90:203-204): t, q =
+ * tr(:,:,:,1,1), phi (the geopotential of t(:,:,:,1), spdy_geopotential_dev), ps (mx,nx).  ONE inverse launch of the 3 kx + 1 plain
+ * fields (the four-segment inverse path, kcos 1, physics.f90:102-107 for the fields this block reads) into plan workspace, then the
+ * column kernel.  ttend / qtend are the operands spdy_grid_tendencies_dev documents (plain_out[kx:2kx], [2kx:3kx]).  max_batch >=
+ * 3 kx + 1.  spdy_moist_workspace allocates the workspace ((3 kx + 1) grids) ahead of time, e.g. before a graph capture.        */
+int spdy_moist_workspace(spdy_plan *plan);
+int spdy_moist_physics_dev(spdy_plan *plan, const double *t, const double *q, const double *phi, const double *ps,
+                           double *ttend, double *qtend, const spdy_moist_out *out);
 
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,

@@ -106,6 +106,9 @@ SIGNATURES = {
     "spdy_spectral_step_dev": [c_void_p] * 12 + [c_double, c_int, c_double, c_double, c_double, c_void_p],
     "spdy_output_workspace": [c_void_p],
     "spdy_output_batch_dev": [c_void_p] * 13,
+    "spdy_moist_columns_dev": [c_void_p, c_int] + [c_void_p] * 7,
+    "spdy_moist_workspace": [c_void_p],
+    "spdy_moist_physics_dev": [c_void_p] * 8,
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

@@ -540,6 +540,7 @@ struct InverseReq {
     int npairs; const double *vor, *dv; double *ug, *vg; int kcos_pairs;
     int nseg; spdy_spec_seg seg[SPDY_MAX_SPEC_SEGS]; const int *d_kcos; int kcos_all; double *grid;
     int ngrad; const double *psi; double *gx, *gy; int kcos_grad;
+    bool plain_one = false;   // plain segments without pairs still as ONE launch (the fused kernels' mixed forms)
 };
 
 /* T63, row f1: uvspec / grad evaluated where the fused inverse kernel loads its operands (csrc/spdy_fused_t63.inc,
@@ -615,7 +616,7 @@ int inverse_batch(spdy_plan *p, InverseReq r)
     r.kcos_grad = r.kcos_grad == 1 ? 1 : 2;
     int nplain = 0;
     for (int i = 0; i < r.nseg; ++i) nplain += r.seg[i].nb;
-    const bool mixed = r.npairs > 0 && nplain > 0;
+    const bool mixed = (r.npairs > 0 || r.plain_one) && nplain > 0;
     if (mixed && fused30(p)) {
         spdy::S2gFused f;
         f.mode = 3; f.nb = r.npairs; f.spec = r.vor; f.spec2 = r.dv; f.kcos_all = r.kcos_pairs; f.grid = r.ug; f.grid2 = r.vg;
@@ -711,6 +712,17 @@ int direct_batch_raw63(spdy_plan *p, int npairs, const double *ug, const double 
         raw_u = p->tmp_c; raw_v = p->tmp_d;
     }
     return direct_batch(p, DirectReq{npairs, ug, vg, raw_u, raw_v, kcos, true, nplain, grid, spec});
+}
+
+int inverse_plain_one(spdy_plan *p, int nseg, const spdy_spec_seg *segs, double *grid)
+{
+    InverseReq r{0, nullptr, nullptr, nullptr, nullptr, 2, 0, {}, nullptr, 1, grid, 0, nullptr, nullptr, nullptr, 2};
+    int nplain = 0;
+    for (int i = 0; i < nseg && i < SPDY_MAX_SPEC_SEGS; ++i)
+        if (segs[i].nb > 0) { r.seg[r.nseg++] = segs[i]; nplain += segs[i].nb; }
+    RC(check_batch(p, nplain));
+    r.plain_one = true;
+    return inverse_batch(p, r);
 }
 }  // namespace spdy_detail
 

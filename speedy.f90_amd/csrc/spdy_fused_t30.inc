@@ -1026,8 +1026,10 @@ hipError_t launch_s2g_fused(const DevPlan &p, const S2gFused &r, int max_wg, hip
     const int mode = r.mode, nb = r.nb, ngrad = r.ngrad;
     const int nplain = r.nplain[0] + r.nplain[1] + r.nplain[2] + r.nplain[3];
     if (nb <= 0 && nplain <= 0) return hipSuccess;
-    if (mode < 0 || mode > 3 || (mode != 0 && !r.grid2) || ((mode == 1 || mode == 3) && !r.spec2)) return hipErrorInvalidValue;
-    if (mode == 3 && (nb <= 0 || nplain <= 0 || !r.plain[0] || !r.grid_p)) return hipErrorInvalidValue;
+    // (mode 3 with nb = 0: plain segments only, one launch -- no pair tile reads spec / spec2 or writes grid / grid2)
+    const bool pairs = mode == 1 || mode == 2 || (mode == 3 && nb > 0);
+    if (mode < 0 || mode > 3 || (pairs && !r.grid2) || ((mode == 1 || (mode == 3 && nb > 0)) && !r.spec2)) return hipErrorInvalidValue;
+    if (mode == 3 && (nb < 0 || nplain <= 0 || !r.plain[0] || !r.grid_p)) return hipErrorInvalidValue;
     if (ngrad < 0 || (ngrad > 0 && (mode != 3 || !r.psi || !r.gx || !r.gy || !r.zero || !p.gradx_e))) return hipErrorInvalidValue;
     S2gMixed mx{r.plain[0], r.kcos_p, r.kcos_all_p, r.grid_p, mode == 3 ? nb : 0, mode == 3 ? nplain : 0, ngrad, r.kcos_grad, r.psi, r.gx,
                 r.gy, r.zero, {nullptr, nullptr, nullptr}, {0x7fffffff, 0x7fffffff, 0x7fffffff}};

@@ -272,4 +272,20 @@ hipError_t launch_output_cast(const DevPlan &p, const OutputCast &c, hipStream_t
 hipError_t prepare_device_kernels();
 hipError_t prepare_device_step_kernels(int kx);
 
+// Moist physics of nb states of (ix, il, kx) grids (csrc/spdy_physics.hip): physics.f90:110-138, one thread per column.
+// Per-level tables are bottom up: entry r belongs to the reference's level k = kx - r.  Output pointers may be null.
+constexpr int MOIST_KMAX = 16;
+struct MoistCols {
+    int nb, ncol, kx;
+    const double *tg, *qg, *phig, *pslg;
+    double *ttend, *qtend;                        // (ix, il, kx) per state, updated in place
+    double *precnv, *precls, *cbmf;               // (ix, il) per state
+    int *iptop, *icnv;                            // (ix, il) per state
+    double *qsat, *rh, *se;                       // (ix, il, kx) per state
+    double fsg[MOIST_KMAX], wvi2[MOIST_KMAX], entr[MOIST_KMAX], grdsig[MOIST_KMAX], grdscp[MOIST_KMAX];
+    double rhref[MOIST_KMAX], dqmax[MOIST_KMAX], pfact[MOIST_KMAX];
+    double fm0;
+};
+hipError_t launch_moist_columns(const MoistCols &a, hipStream_t s);
+
 }  // namespace spdy

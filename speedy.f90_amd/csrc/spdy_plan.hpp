@@ -43,6 +43,7 @@ struct spdy_plan {
     const double *d_zero_spec = nullptr;         // one all-zero spectrum (gradient tiles of the mixed inverse kernel)
     double *tmp_c = nullptr, *tmp_d = nullptr;   // max_batch spectra each; allocated with `four` (multi-kernel operator sequences)
     double *out_grid = nullptr, *out_spec = nullptr;   // output path: (5kx+1) grids, (3kx+1) spectra (spdy_output_workspace)
+    double *moist_grid = nullptr;     // moist physics from spectra: (3kx+1) grids t | q | phi | ln ps (spdy_moist_workspace)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
     double *d_dmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -80,6 +81,8 @@ int ensure_four(spdy_plan *p);        // four-kernel path workspace
 int direct_batch_raw63(spdy_plan *p, int npairs, const double *ug, const double *vg, int kcos, int nplain, const double *grid, double *spec,
                        double *raw_u = nullptr, double *raw_v = nullptr);
 bool use_raw63(const spdy_plan *p, int npairs);   // whether a step's direct batch of npairs (u, v) pairs takes that route
+// the plain spectra of nseg segments (kcos 1) -> ONE grid stack, as one launch of the fused inverse kernels (spdy_moist_physics_dev)
+int inverse_plain_one(spdy_plan *p, int nseg, const spdy_spec_seg *segs, double *grid);
 int upload_level_tables(spdy_plan *p);
 void release_comms(spdy_plan *p);     // plan teardown: RCCL communicators of this plan are shut down, their handles stay valid but dead
 

@@ -38,6 +38,57 @@ const uint32_t kSiaT63[48] = {
 
 inline float bits_to_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
+// physical_constants.f90:21, convection.f90:15-22, large_scale_condensation.f90:24-27 (default-real literals widened;
+// 1.e+5, 6.0, 0.5, 4.0 and 10.0 are exact in float32)
+const double kP0 = static_cast<double>(1.e+5f);
+const double kTrcnv = static_cast<double>(6.0f), kEntmax = static_cast<double>(0.5f);
+const double kTrlsc = static_cast<double>(4.0f), kRhlsc = static_cast<double>(0.9f), kDrhlsc = static_cast<double>(0.1f);
+const double kRhblsc = static_cast<double>(0.95f), kQsmax = static_cast<double>(10.0f);
+// physics.f90:37 takes log(0.99) of a default real: the float32 log of float32 0.99, pinned like the Gaussian rows above
+const uint32_t kLog099 = 0xBC24AA20u;
+
+// physics.f90:12-39 (initialize_physics) and the level constants of convection.f90:55-71 (entr, fm0) and
+// large_scale_condensation.f90:47-66 (rhref, dqmax, dhs*prg) -- functions of the sigma levels only
+void make_physics(HostTables &t)
+{
+    const int kx = t.kx;
+    t.sigl.assign(kx, 0.0); t.sigh.assign(kx + 1, 0.0); t.grdsig.assign(kx, 0.0); t.grdscp.assign(kx, 0.0);
+    t.wvi.assign(2 * kx, 0.0); t.entr.assign(kx > 2 ? kx - 2 : 0, 0.0);
+    t.lsc_rhref.assign(kx, 0.0); t.lsc_dqmax.assign(kx, 0.0); t.lsc_pfact.assign(kx, 0.0);
+    t.sigh[0] = t.hsg[0];
+    for (int k = 0; k < kx; ++k) {
+        t.sigl[k] = std::log(t.fsg[k]);
+        t.sigh[k + 1] = t.hsg[k + 1];
+        t.grdsig[k] = kGrav / (t.dhs[k] * kP0);
+        t.grdscp[k] = t.grdsig[k] / kCp;
+    }
+    for (int k = 0; k + 1 < kx; ++k) {
+        t.wvi[k] = 1.0 / (t.sigl[k + 1] - t.sigl[k]);
+        t.wvi[kx + k] = (std::log(t.sigh[k + 1]) - t.sigl[k]) * t.wvi[k];
+    }
+    if (kx >= 2) t.wvi[2 * kx - 1] = (static_cast<double>(bits_to_float(kLog099)) - t.sigl[kx - 1]) * t.wvi[kx - 2];
+    // convection.f90:55-71: fm0 = p0*dhs(kx)/(grav*trcnv*3600.0); entrainment profile up to sigma = 0.5, normalised to entmax
+    t.fm0 = kP0 * t.dhs[kx - 1] / (kGrav * kTrcnv * 3600.0);
+    double sentr = 0.0;
+    for (int k = 1; k + 1 < kx; ++k) {
+        const double e = t.fsg[k] - 0.5 > 0.0 ? t.fsg[k] - 0.5 : 0.0;
+        t.entr[k - 1] = e * e;                       // (max(0.0, fsg(k) - 0.5))**2.0
+        sentr = sentr + t.entr[k - 1];
+    }
+    sentr = kEntmax / sentr;
+    for (auto &e : t.entr) e = e * sentr;
+    // large_scale_condensation.f90:47-66, per level k = 2..kx
+    const double rtlsc = 1.0 / (kTrlsc * 3600.0), prg = kP0 / kGrav;
+    for (int k = 1; k < kx; ++k) {
+        const double sig2 = t.fsg[k] * t.fsg[k];     // fsg(k)**2.0
+        double rhref = kRhlsc + kDrhlsc * (sig2 - 1.0);
+        if (k == kx - 1) rhref = rhref > kRhblsc ? rhref : kRhblsc;
+        t.lsc_rhref[k] = rhref;
+        t.lsc_dqmax[k] = kQsmax * sig2 * rtlsc;
+        t.lsc_pfact[k] = t.dhs[k] * prg;
+    }
+}
+
 // Everything that is a function of the half levels hsg alone:
 //   geometry.f90:51-60 (dhs, fsg, dhsr, fsgr), geopotential.f90:22-30 + :52-53 (xgeop1, xgeop2, corf),
 //   horizontal_diffusion.f90:70-82 (tcorv, qcorv)
@@ -68,6 +119,7 @@ void make_sigma_derived(HostTables &t)
         t.tcorv[k] = std::pow(t.fsg[k], rgam);
         if (k > 1) t.qcorv[k] = std::pow(t.fsg[k], qexp);
     }
+    make_physics(t);
     t.sigma_ready = true;
 }
 
@@ -82,6 +134,7 @@ void make_geometry(HostTables &t)
     t.dhs.assign(t.kx, 0.0); t.fsg.assign(t.kx, 0.0); t.dhsr.assign(t.kx, 0.0); t.fsgr.assign(t.kx, 0.0);
     t.xgeop1.assign(t.kx, 0.0); t.xgeop2.assign(t.kx, 0.0); t.corf.assign(t.kx, 0.0);
     t.tcorv.assign(t.kx, 0.0); t.qcorv.assign(t.kx, 0.0);
+    for (auto *v : {&t.sigl, &t.sigh, &t.grdsig, &t.grdscp, &t.wvi, &t.entr, &t.lsc_rhref, &t.lsc_dqmax, &t.lsc_pfact}) v->clear();
     t.sigma_ready = false;
     if (lev) {
         for (int k = 0; k <= t.kx; ++k) t.hsg[k] = static_cast<double>(lev[k]);
@@ -458,7 +511,8 @@ const double *HostTables::lookup(const std::string &name, int *count, std::vecto
         {"dmpd", &dmpd}, {"dmps", &dmps}, {"dmp1", &dmp1}, {"dmp1d", &dmp1d}, {"dmp1s", &dmp1s},
         {"tref", &tref}, {"tref1", &tref1}, {"tref2", &tref2}, {"tref3", &tref3}, {"xc", &xc}, {"xd", &xd},
         {"xj", &xj}, {"dhsx", &dhsx}, {"elz", &elz}, {"xgeop1", &xgeop1}, {"xgeop2", &xgeop2}, {"corf", &corf},
-        {"tcorv", &tcorv}, {"qcorv", &qcorv}, {"coriol", &coriol}};
+        {"tcorv", &tcorv}, {"qcorv", &qcorv}, {"coriol", &coriol}, {"sigl", &sigl}, {"sigh", &sigh}, {"grdsig", &grdsig},
+        {"grdscp", &grdscp}, {"wvi", &wvi}, {"entr", &entr}};
     for (const auto &e : ents)
         if (name == e.n) { *count = static_cast<int>(e.v->size()); return e.v->data(); }
     if (name == "ifac") {

@@ -2,7 +2,8 @@
 //
 // Reproduces, value for value, the tables the reference builds once at start-up:
 //   geometry.f90:35-89, fftpack.f90:1-67 (rffti1), legendre.f90:23-71,158-237,
-//   spectral.f90:20-82, horizontal_diffusion.f90:36-82, implicit.f90:36-165.
+//   spectral.f90:20-82, horizontal_diffusion.f90:36-82, implicit.f90:36-165, physics.f90:12-39 and the level
+//   constants of convection.f90:55-71 and large_scale_condensation.f90:47-66.
 // The reference is FP64 in storage only; unsuffixed literals and float() are float32 first
 // (SURVEY.md Appendix A).  Those sub-expressions are evaluated in float here too -- an
 // "improved" table (exact pi, true Gaussian nodes, double 1/ix) breaks parity at 1e-8.
@@ -39,6 +40,12 @@ struct HostTables {
     std::vector<double> xgeop1, xgeop2, corf;
     // horizontal_diffusion.f90:70-82 (valid when sigma_ready): tcorv[kx], qcorv[kx]
     std::vector<double> tcorv, qcorv;
+    // physics.f90:12-39 initialize_physics (valid when sigma_ready): sigl[kx], sigh[kx+1] (= sigh(0:kx)), grdsig[kx],
+    // grdscp[kx], wvi[2*kx] (column-major wvi(kx,2)); convection.f90 level constants: entr[kx-2] (= entr(2:kx-1), after the
+    // normalisation by sentr) and fm0; large_scale_condensation.f90:47-66 per level k (index k-1; 0 at k = 1): rhref, dqmax
+    // and pfact = dhs*prg
+    std::vector<double> sigl, sigh, grdsig, grdscp, wvi, entr, lsc_rhref, lsc_dqmax, lsc_pfact;
+    double fm0 = 0.0;
 
     // Builds everything except the dt-dependent implicit tables.  Returns "" or an error text.
     std::string build(int trunc, int ix, int iy, int kx);

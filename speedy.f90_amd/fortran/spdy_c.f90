@@ -22,6 +22,13 @@ module spdy_c
         type(c_ptr) :: field, fdt
     end type
 
+    !> spdy_moist_out (include/spdy.h): optional outputs of the moist physics (c_null_ptr = not written)
+    type, bind(C) :: spdy_moist_out
+        type(c_ptr) :: precnv = c_null_ptr, precls = c_null_ptr, cbmf = c_null_ptr
+        type(c_ptr) :: iptop = c_null_ptr, icnv = c_null_ptr
+        type(c_ptr) :: qsat = c_null_ptr, rh = c_null_ptr, se = c_null_ptr
+    end type
+
     interface
         function spdy_plan_create(trunc, ix, iy, kx, max_batch, device, plan) bind(C, name="spdy_plan_create") result(rc)
             import :: c_int, c_ptr
@@ -631,6 +638,26 @@ module spdy_c
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, d_vor, d_div, d_ug, d_vg, d_spec, d_kcos, d_grid, d_psi, d_gx, d_gy
             integer(c_int), value :: npairs, kcos_pairs, nplain, kcos_all, ngrad, kcos_grad
+            integer(c_int) :: rc
+        end function
+        function spdy_moist_columns_dev(plan, nb, tg, qg, phig, pslg, ttend, qtend, out) &
+                & bind(C, name="spdy_moist_columns_dev") result(rc)
+            import :: c_int, c_ptr, spdy_moist_out
+            type(c_ptr), value :: plan, tg, qg, phig, pslg, ttend, qtend
+            integer(c_int), value :: nb
+            type(spdy_moist_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_moist_workspace(plan) bind(C, name="spdy_moist_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int) :: rc
+        end function
+        function spdy_moist_physics_dev(plan, t, q, phi, ps, ttend, qtend, out) &
+                & bind(C, name="spdy_moist_physics_dev") result(rc)
+            import :: c_int, c_ptr, spdy_moist_out
+            type(c_ptr), value :: plan, t, q, phi, ps, ttend, qtend
+            type(spdy_moist_out), intent(in) :: out
             integer(c_int) :: rc
         end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)

@@ -25,6 +25,16 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+class MoistOut(ctypes.Structure):
+    """spdy_moist_out (include/spdy.h): optional outputs of the moist physics, device pointers or None."""
+    _fields_ = [("precnv", ctypes.c_void_p), ("precls", ctypes.c_void_p), ("cbmf", ctypes.c_void_p), ("iptop", ctypes.c_void_p),
+                ("icnv", ctypes.c_void_p), ("qsat", ctypes.c_void_p), ("rh", ctypes.c_void_p), ("se", ctypes.c_void_p)]
+
+
+MOIST_2D = ("precnv", "precls", "cbmf", "iptop", "icnv")   # (ix,il) per state; iptop / icnv int32
+MOIST_3D = ("qsat", "rh", "se")                             # (ix,il,kx) per state
+
+
 class Graph:
     """A captured sequence of device-resident calls (spdy_graph_* in include/spdy.h)."""
 
@@ -500,3 +510,73 @@ class Spectral:
         check(self.lib.spdy_device_table(self.h, dmp_name.encode(), ctypes.byref(a)))
         check(self.lib.spdy_device_table(self.h, dmp1_name.encode(), ctypes.byref(b)))
         check(self.lib.spdy_hdiff_dev(self.h, field.shape[0], self._dp(field), self._dp(fdt_in), a, b, self._dp(out)))
+
+    # ------------------------------------------------------------------ moist physics (physics.f90:110-138)
+    @staticmethod
+    def _moist_out(out):
+        o = MoistOut()
+        for name, t in (out or {}).items():
+            if name not in MOIST_2D + MOIST_3D:
+                raise ValueError("unknown moist output %r" % name)
+            if t is not None:
+                setattr(o, name, t.data_ptr())
+        return o
+
+    def moist_columns_dev(self, tg, qg, phig, pslg, ttend, qtend, out=None):
+        """Precipitation block on nb gridded states: tg, qg, phig, ttend, qtend [nb,kx,il,ix] (or [kx,il,ix]), pslg [nb,il,ix];
+        ttend / qtend in place.  out: dict of optional device outputs (MOIST_2D [nb,il,ix], iptop/icnv int32; MOIST_3D like tg)."""
+        self._sync_stream()
+        nb = tg.shape[0] if tg.dim() == 4 else 1
+        o = self._moist_out(out)
+        check(self.lib.spdy_moist_columns_dev(self.h, nb, *[self._dp(x) for x in (tg, qg, phig, pslg, ttend, qtend)], ctypes.byref(o)))
+
+    def moist_workspace(self):
+        check(self.lib.spdy_moist_workspace(self.h))
+
+    def moist_physics_dev(self, t, q, phi, ps, ttend, qtend, out=None):
+        """The same from one state's spectra (time level 1: t, q [kx,nx,mx], phi [kx,nx,mx], ps [nx,mx] complex128): one inverse
+        launch into plan workspace, then the column kernel.  ttend / qtend [kx,il,ix] in place."""
+        self._sync_stream()
+        o = self._moist_out(out)
+        check(self.lib.spdy_moist_physics_dev(self.h, *[self._dp(x) for x in (t, q, phi, ps, ttend, qtend)], ctypes.byref(o)))
+
+    def moist_columns(self, tg, qg, phig, pslg, ttend, qtend):
+        """NumPy convenience: spdy_moist_columns_dev on copies in plan-owned device memory.  Returns a dict with the updated
+        ttend, qtend and every optional output (shapes as the inputs; iptop / icnv int32)."""
+        ins = [np.ascontiguousarray(a, np.float64) for a in (tg, qg, phig, pslg, ttend, qtend)]
+        grid3 = ins[0].shape
+        if grid3[-3:] != (self.kx,) + self.grid_shape or any(a.shape != grid3 for a in (ins[1], ins[2], ins[4], ins[5])):
+            raise ValueError("tg, qg, phig, ttend, qtend must be [nb,] kx, il, ix")
+        lead = grid3[:-3]
+        nb = int(np.prod(lead)) if lead else 1
+        if ins[3].shape != lead + self.grid_shape:
+            raise ValueError("pslg must be [nb,] il, ix")
+        res = {"ttend": np.empty(grid3), "qtend": np.empty(grid3)}
+        for n in MOIST_2D:
+            res[n] = np.empty(lead + self.grid_shape, np.int32 if n in ("iptop", "icnv") else np.float64)
+        for n in MOIST_3D:
+            res[n] = np.empty(grid3)
+        bufs = []
+        try:
+            def alloc(nbytes):
+                ptr = ctypes.c_void_p()
+                check(self.lib.spdy_dev_alloc(self.h, max(nbytes, 8), ctypes.byref(ptr)))
+                bufs.append(ptr)
+                return ptr
+            d_in = []
+            for a in ins:
+                d = alloc(a.nbytes)
+                check(self.lib.spdy_dev_upload(self.h, d, _p(a), a.nbytes))
+                d_in.append(d)
+            o = MoistOut()
+            d_out = {}
+            for n in MOIST_2D + MOIST_3D:
+                d_out[n] = alloc(res[n].nbytes)
+                setattr(o, n, d_out[n].value)
+            check(self.lib.spdy_moist_columns_dev(self.h, nb, *d_in, ctypes.byref(o)))
+            for n, d in (("ttend", d_in[4]), ("qtend", d_in[5])) + tuple(d_out.items()):
+                check(self.lib.spdy_dev_download(self.h, _p(res[n]), d, res[n].nbytes))
+        finally:
+            for b in bufs:
+                self.lib.spdy_dev_free(self.h, b)
+        return res

@@ -1,0 +1,187 @@
+"""GPU: moist physics on the device (csrc/spdy_physics.hip; physics.f90:110-138) -- against the flang-built reference's
+fixture, batch composition, the path from spectra, and a whole time step with the block in it, plain and captured."""
+import os
+
+import numpy as np
+import pytest
+
+import moist
+import synth
+from conftest import GOLDEN, TOL, VARIANTS
+from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, wave_relerr
+from dynstep import state as dyn_state
+
+pytestmark = pytest.mark.gpu
+
+RES = {"t30": ("t30", 8), "t30k5": ("t30", 5), "t30k7": ("t30", 7), "t63k16": ("t63", 16)}
+FLOATS = ("ttend", "qtend", "precnv", "precls", "cbmf", "qsat", "rh", "se")
+INTS = ("iptop", "icnv")
+
+
+def make_plan(tag, max_batch=64):
+    import speedy_f90_amd as s
+    res, kx = RES[tag]
+    sp = s.Spectral(res, kx=kx, max_batch=max_batch, device=0)
+    if kx == 16:
+        sp.set_sigma(synth.SIGMA_L16)
+    return sp
+
+
+@pytest.mark.parametrize("tag", sorted(RES))
+def test_moist_columns_vs_reference(tag):
+    """spdy_moist_columns_dev with every optional output against the reference: integers identical, floats within TOL."""
+    z = np.load(os.path.join(GOLDEN, "ref_moist.npz"))
+    ix, il, kx = moist.VARIANTS[tag]
+    tab = moist.tables(moist.HSG[kx])
+    ins = moist.grid_inputs(tab, (1, il, ix), int(z[tag + "_seed"]))
+    sub = z[tag + "_sub"]
+    sp = make_plan(tag)
+    r = sp.moist_columns(*ins)
+    sp.close()
+    worst = 0.0
+    for n in INTS:
+        assert np.array_equal(r[n].reshape(-1, il * ix)[:, sub].squeeze(), z["%s_%s" % (tag, n)]), n
+    for n in FLOATS:
+        e = synth.relerr(r[n].reshape(-1, il * ix)[:, sub].squeeze(), z["%s_%s" % (tag, n)])
+        worst = max(worst, e)
+        assert e <= TOL, (n, e)
+    if kx == 5:            # convection.f90:198: the loop do k = kx-3, 3, -1 is empty -- no column convects
+        assert np.all(r["icnv"] == -1)
+    else:
+        assert r["icnv"].max() > 0
+    print("\n[moist columns %s vs reference] worst %.1e" % (tag, worst))
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _outs(nb, kx, il, ix):
+    import torch
+    o = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("precnv", "precls", "cbmf")}
+    o.update({n: torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda") for n in INTS})
+    o.update({n: torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda") for n in ("qsat", "rh", "se")})
+    return o
+
+
+def test_null_outputs_and_batch_composition():
+    """All optional outputs NULL leaves ttend / qtend bit-equal to the full call; nb = 1, 7, 64 states in one launch are each
+    bit-equal to the same state launched alone."""
+    import torch
+    sp = make_plan("t30", 64)
+    ix, il, kx = moist.VARIANTS["t30"]
+    tab = moist.tables(moist.HSG[kx])
+    for nb in (1, 7, 64):
+        tg, qg, phig, pslg, tt, qt = (_dev(a) for a in moist.grid_inputs(tab, (nb, il, ix), 9100 + nb))
+        T, Q, out = tt.clone(), qt.clone(), _outs(nb, kx, il, ix)
+        sp.moist_columns_dev(tg, qg, phig, pslg, T, Q, out)
+        T0, Q0 = tt.clone(), qt.clone()
+        sp.moist_columns_dev(tg, qg, phig, pslg, T0, Q0, None)
+        torch.cuda.synchronize()
+        assert torch.equal(T, T0) and torch.equal(Q, Q0), nb
+        for b in range(nb):
+            Tb, Qb, ob = tt[b:b + 1].clone(), qt[b:b + 1].clone(), _outs(1, kx, il, ix)
+            sp.moist_columns_dev(tg[b:b + 1], qg[b:b + 1], phig[b:b + 1], pslg[b:b + 1], Tb, Qb, ob)
+            torch.cuda.synchronize()
+            assert torch.equal(Tb[0], T[b]) and torch.equal(Qb[0], Q[b]), (nb, b)
+            for n in ob:
+                assert torch.equal(ob[n][0], out[n][b]), (nb, b, n)
+    sp.close()
+
+
+@pytest.mark.parametrize("tag", ["t30", "t63k16"])
+def test_moist_physics_from_spectra(tag, oracle_factory):
+    """spdy_moist_physics_dev (one inverse launch + the column kernel) against the restatement on the oracle's transforms."""
+    import torch
+    kx = RES[tag][1]
+    sp, o = make_plan(tag, 4 * kx + 4), oracle_factory(tag)
+    st = moist.state(o, dyn_state(sp, 8000), 4242)
+    phi = o.geopotential(st["t"][0], st["phis"])
+    il, ix = sp.il, sp.ix
+    tt0 = synth.splitmix64(77, kx * il * ix).reshape(kx, il, ix) * 1e-4
+    qt0 = synth.splitmix64(78, kx * il * ix).reshape(kx, il, ix) * 1e-7
+    rec = {}
+    tt, qt = tt0.copy(), qt0.copy()
+    moist.make_hook(rec)(o, st, None, None, tt, qt)
+    assert rec["margin"].min() >= moist.MIN_MARGIN
+    T, Q, out = _dev(tt0), _dev(qt0), _outs(1, kx, il, ix)
+    sp.moist_physics_dev(_dev(st["t"][0]), _dev(st["tr"][0]), _dev(phi), _dev(st["ps"][0]), T, Q, out)
+    torch.cuda.synchronize()
+    worst = max(synth.relerr(T.cpu().numpy(), tt), synth.relerr(Q.cpu().numpy(), qt))
+    for n in ("precnv", "precls", "cbmf", "qsat", "rh", "se"):
+        worst = max(worst, synth.relerr(out[n].cpu().numpy()[0], rec[n]))
+    for n in INTS:
+        assert np.array_equal(out[n].cpu().numpy()[0], rec[n]), n
+    print("\n[moist physics from spectra %s] worst %.1e, min margin %.1e" % (tag, worst, rec["margin"].min()))
+    assert worst <= TOL
+    sp.close()
+
+
+def _step(sp, D, W, kx, dt, physics):
+    """One model step: inverse batch (+ grad ps) -> grid tendencies -> [geopotential + moist physics] -> direct batch + spectral
+    step (tendencies.f90:89-234, time_stepping.f90)."""
+    ug, vg, plain_g, px, py, U, V, PL, pvor, pdiv, pspec, phi, phim = W
+    sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g,
+                              D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
+    sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
+    if physics:            # tendencies.f90:203-206 with time level j1 = 1
+        sp.geopotential_dev(D["t"][0], D["phis"], phim)
+        sp.moist_physics_dev(D["t"][0], D["tr"][0], phim, D["ps"][0], PL[kx:2 * kx], PL[2 * kx:3 * kx])
+    sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
+                                      D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
+
+
+@pytest.mark.parametrize("tag", ["t30", "t63k16"])
+def test_step_with_moist_physics(tag, oracle_factory):
+    """A whole T30 L8 / T63 L16 step with the moist block between the grid tendencies and the direct batch against
+    oracle_dynamics_step(physics=moist hook) within TOL; the same step captured and replayed is bit-equal to the plain launches,
+    and its graph has exactly 3 nodes more than the adiabatic step's (geopotential, the inverse launch, the column kernel)."""
+    import torch
+    kx = VARIANTS[tag][3]
+    sp, o = make_plan(tag, 4 * kx + 4), oracle_factory(tag)
+    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
+    dt = 2400.0
+    sp.initialize_implicit(dt); o.tail_init(dt)
+    st = moist.state(o, dyn_state(sp, 8000), 5150)
+    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")
+    c128 = lambda *s: torch.zeros(s, dtype=torch.complex128, device="cuda")
+    P = 3 * kx
+    W = (f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix), f64(P, il, ix), f64(P, il, ix),
+         f64(P + 1, il, ix), c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx), c128(kx, nx, mx))
+    fresh = lambda: {n: _dev(st[n]) for n in st}
+    sp.moist_workspace()
+    sp.use_own_stream()
+    # plain launches
+    D = fresh()
+    _step(sp, D, W, kx, dt, True)
+    sp.synchronize()
+    plain = {n: D[n].clone() for n in ("vor", "div", "t", "tr", "ps")}
+    PLd = W[7].cpu().numpy()
+    rec = {}
+    ref, out = oracle_dynamics_step(o, st, 2, dt, ROB, physics=moist.make_hook(rec))
+    assert rec["margin"].min() >= moist.MIN_MARGIN
+    assert rec["branch"]["no_conv"] < rec["branch"]["columns"] and rec["branch"]["lsc_interior"] > 0
+    worst = synth.relerr(PLd, out["PL"])
+    for n in ("ps", "vor", "div", "t", "tr"):
+        got = plain[n].cpu().numpy()
+        worst = max(worst, synth.relerr(got, ref[n]), wave_relerr(got, ref[n]))
+    print("\n[step with moist physics %s vs oracle] worst %.1e; branches %s" % (tag, worst, rec["branch"]))
+    assert worst <= TOL, worst
+    # captured and replayed: bit-equal
+    D = fresh()
+    torch.cuda.synchronize()
+    with sp.graph_capture() as g:
+        _step(sp, D, W, kx, dt, True)
+    g.launch()
+    sp.synchronize()
+    for n in plain:
+        assert torch.equal(D[n], plain[n]), n
+    D0 = fresh()
+    torch.cuda.synchronize()
+    with sp.graph_capture() as g0:
+        _step(sp, D0, W, kx, dt, False)
+    n1, n0 = g.num_nodes(), g0.num_nodes()
+    print("[graph nodes %s] adiabatic %d, with moist physics %d" % (tag, n0, n1))
+    assert n1 - n0 == 3, (n0, n1)
+    g.close(); g0.close(); sp.close()

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Rate of the moist-physics column kernel (spdy_moist_columns_dev, csrc/spdy_physics.hip) at T30 L8 and T63 L16 over nb states,
+timed with HIP events on the plan's stream, against the byte model of DESIGN.md (per column: reads 5 kx + 1 doubles -- tg, qg,
+phig, ttend, qtend and pslg -- writes 5 kx + 3 doubles and 2 ints with every optional output requested), and the extra time of a
+captured model step with the block in it (geopotential + inverse launch + column kernel) over the adiabatic step.
+
+    python tools/moist_rate.py [--reps 200] [--json out.json]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import torch  # noqa: E402
+
+import moist  # noqa: E402
+import synth  # noqa: E402
+import speedy_f90_amd as s  # noqa: E402
+from dynstep import ROB, SDRAG, WIL, state as dyn_state  # noqa: E402
+
+HBM = 8.0e12
+
+
+def bytes_per_state(kx, ncol):
+    return ncol * ((5 * kx + 1 + 5 * kx + 3) * 8 + 2 * 4)
+
+
+def time_fn(fn, reps):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps      # us
+
+
+def kernel_rates(res, kx, nbs, reps):
+    sp = s.Spectral(res, kx=kx, max_batch=max(nbs), device=0)
+    if kx == 16:
+        sp.set_sigma(synth.SIGMA_L16)
+    il, ix = sp.il, sp.ix
+    tab = moist.tables(moist.HSG[kx])
+    one = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in moist.grid_inputs(tab, (1, il, ix), 1)]
+    rows = []
+    for nb in nbs:
+        tg, qg, phig, pslg, tt, qt = [x.expand((nb,) + tuple(x.shape[1:])).contiguous() for x in one]
+        out = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("precnv", "precls", "cbmf")}
+        out.update({n: torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda") for n in ("iptop", "icnv")})
+        out.update({n: torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda") for n in ("qsat", "rh", "se")})
+        us = time_fn(lambda: sp.moist_columns_dev(tg, qg, phig, pslg, tt, qt, out), reps)
+        bw = bytes_per_state(kx, il * ix) * nb / (us * 1e-6)
+        rows.append({"res": res, "kx": kx, "nb": nb, "us": round(us, 2), "bytes": bytes_per_state(kx, il * ix) * nb,
+                     "TB_s": round(bw / 1e12, 3), "frac_8TBs": round(bw / HBM, 3)})
+        print(json.dumps(rows[-1]), flush=True)
+    sp.close()
+    return rows
+
+
+def step_extra(res, kx, reps):
+    import speedy_f90_amd as s
+    sp = s.Spectral(res, kx=kx, max_batch=4 * kx + 4, device=0)
+    if kx == 16:
+        sp.set_sigma(synth.SIGMA_L16)
+    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
+    dt = 2400.0
+    sp.initialize_implicit(dt)
+    st = dyn_state(sp, 8000)
+    D = {n: torch.from_numpy(np.ascontiguousarray(st[n])).cuda() for n in st}
+    f64 = lambda *sh: torch.zeros(sh, dtype=torch.float64, device="cuda")
+    c128 = lambda *sh: torch.zeros(sh, dtype=torch.complex128, device="cuda")
+    P = 3 * kx
+    ug, vg, plain_g, px, py = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix)
+    U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
+    pvor, pdiv, pspec, phi, phim = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx), c128(kx, nx, mx)
+    sp.moist_workspace()
+    sp.use_own_stream()
+
+    def step(physics):
+        sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g,
+                                  D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
+        sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
+        if physics:
+            sp.geopotential_dev(D["t"][0], D["phis"], phim)
+            sp.moist_physics_dev(D["t"][0], D["tr"][0], phim, D["ps"][0], PL[kx:2 * kx], PL[2 * kx:3 * kx])
+        sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
+                                          D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
+    res_ = {}
+    for physics in (False, True):
+        with sp.graph_capture() as g:
+            step(physics)
+        # the state evolves under replay; a few hundred adiabatic / moist steps stay finite at these amplitudes
+        res_["with" if physics else "without"] = {"us": round(time_fn(g.launch, reps), 2), "nodes": g.num_nodes()}
+        g.close()
+    res_["extra_us"] = round(res_["with"]["us"] - res_["without"]["us"], 2)
+    row = {"res": res, "kx": kx, "captured_step": res_}
+    print(json.dumps(row), flush=True)
+    sp.close()
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    out = {"kernel": kernel_rates("t30", 8, [1, 16, 64, 256, 512], a.reps) + kernel_rates("t63", 16, [1, 16, 64], a.reps),
+           "step": [step_extra("t30", 8, a.reps), step_extra("t63", 16, a.reps)]}
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
