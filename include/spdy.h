@@ -342,8 +342,7 @@ int spdy_sharded_step_workspace(spdy_comm *comm);
 int spdy_sharded_step_dev(spdy_comm *comm, double *vor, double *div, double *t, double *tr, double *ps, const double *phis,
                           const double *d_tcorh, const double *d_qcorh, double sdrag, int j1, int j2, double dt, double eps, double wil,
                           double *phi, double *tend_out);
-int spdy_sharded_step_grid_dev(spdy_comm *comm, const double *vor, const double *div, const double *t, const double *tr,
-                               const double *ps, int j2);
+int spdy_sharded_step_grid_dev(spdy_comm *comm, double *vor, double *div, double *t, double *tr, double *ps, int j2);
 int spdy_sharded_step_operands(spdy_comm *comm, double **u, double **v, double **plain, int *lo, int *hi);
 int spdy_sharded_step_spectral_dev(spdy_comm *comm, double *vor, double *div, double *t, double *tr, double *ps, const double *phis,
                                    const double *d_tcorh, const double *d_qcorh, double sdrag, int j1, double dt, double eps, double wil,
@@ -362,13 +361,19 @@ int spdy_sharded_step_stacks(spdy_comm *comm, double **grid_stack, size_t *grid_
  * Each exchange is one grouped ncclSend / ncclRecv per peer on the plan's stream (in-process groups: 2-D peer copies).  Per rank
  * and step it receives (R - 1) / R of 6 nl + 9 nl + 1 grids and 9 nl + 1 + 4 nl + 1 spectra -- a third of the all-gather form's
  * bytes at 8 ranks (spdy_comm_describe prints both) -- and does 1 / R of the column kernels' work.  Same kernels' expressions
- * on the same values: bit-identical to the all-gather form and to the unsharded step (tests/test_gpu_sharded_step.py).
+ * on the same values: bit-identical to the all-gather form and to the unsharded step at T30, equal to rounding (1e-13) at T63,
+ * where vds is applied before exchange 3 and the bits of the staged T63 direct batch's vdspec depend on the batch size
+ * (tests/test_gpu_sharded_step.py).
  * STATE: nothing is replicated any more.  After a transposed step the caller's prognostic arrays are current on (all levels x
- * own coefficients) only; the next spdy_sharded_step_grid_dev completes what it reads IN PLACE in the caller's arrays (which is
- * why they are not really const there), and spdy_sharded_state_gather_dev makes them whole on every rank (output, restart,
- * switching the form).  phi and tend_out are written on the own coefficients; spdy_sharded_gather_ranges_dev completes any
- * such array (rows of mx nx complex values; <= 4 kx + 2 rows).  The physics hook (spdy_sharded_step_operands between the two
- * halves) is unchanged.                                                                                                      */
+ * own coefficients) only (with one rank: whole, unless $SPDY_COMM_FORCE).  Every transposed spdy_sharded_step_grid_dev, eager or
+ * captured, first completes what it reads IN PLACE in the caller's arrays (exchange 4: on a whole state it moves values that are
+ * already there), and spdy_sharded_state_gather_dev makes them whole on every rank (output, restart, switching the form; eager
+ * only, SPDY_ERR_STATE inside a capture).  Switching back to the all-gather form (spdy_comm_set_option "transpose" 0) needs an
+ * eager spdy_sharded_state_gather_dev after the last eager transposed step, and is refused for good (SPDY_ERR_STATE: create a
+ * new communicator) once a transposed step of the communicator has been recorded into a graph, whose replays leave the state
+ * range-sharded whatever the host has called since.  phi and tend_out are written on the own coefficients;
+ * spdy_sharded_gather_ranges_dev completes any such array (rows of mx nx complex values; <= 4 kx + 2 rows).  The physics hook
+ * (spdy_sharded_step_operands between the two halves) is unchanged.                                                         */
 int spdy_comm_set_option(spdy_comm *comm, const char *name, int value);      /* "transpose" 0 | 1; "force", "dry" as $SPDY_COMM_FORCE / _DRY */
 int spdy_sharded_state_gather_dev(spdy_comm *comm, double *vor, double *div, double *t, double *tr, double *ps);
 int spdy_sharded_gather_ranges_dev(spdy_comm *comm, int narr, double *const *arrays, const int *nrows);

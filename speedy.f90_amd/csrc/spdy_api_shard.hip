@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -78,7 +79,7 @@ struct spdy_comm_group {
     std::vector<spdy_comm *> member;
     std::vector<hipEvent_t> ready, done;
     std::vector<int> device;
-    std::vector<double *> arr[SPDY_COMM_MAX_ARRAYS];      // the running collective's arrays, by rank
+    std::vector<std::array<double *, SPDY_COMM_MAX_ARRAYS>> arr;     // the running collective's arrays, by rank
 };
 
 struct spdy_comm {
@@ -99,8 +100,10 @@ struct spdy_comm {
     // the TRANSPOSED form of the step (spdy_comm_set_option "transpose"): levels <-> point ranges on the grid side, levels <->
     // coefficient ranges on the spectral side (see transpose_blocks)
     int transpose = 0;
-    bool ranges_valid = false;        // the caller's prognostics are current only on (all levels x own coefficients): the next grid
-                                      // half, or spdy_sharded_state_gather_dev, brings in what it reads
+    // a transposed spectral half (nranks > 1 or force) leaves the caller's prognostics current on (all levels x own coefficients)
+    // only; every transposed grid half completes what it reads (exchange 4).  The flags guard switching the form back:
+    bool ranges_eager = false;        // an eager transposed spectral half ran since the last spdy_sharded_state_gather_dev
+    bool ranges_captured = false;     // one was recorded into a graph: any replay leaves the state range-sharded, at any time
     double *Gb = nullptr;             // gridded prognostics, all levels of the own points: 6 kx slabs of npts
     double *Ob = nullptr;             // grid tendencies' results, all levels of the own points: 9 kx + nranks slabs of npts
     double *Tb = nullptr;             // direct batches' outputs, all levels of the own coefficients: 9 kx + nranks slabs of ne
@@ -178,17 +181,13 @@ int group_barrier(spdy_comm_group *g)
     return SPDY_OK;
 }
 
-/* In place: each of the narr arrays d[a] is partitioned into nranks blocks, block r = doubles [off[r], off[r] + cnt[r]); this
- * rank has filled block `rank` of every array, afterwards every rank holds all blocks.  RCCL: ONE grouped operation on the
- * plan's stream (graph-capturable) -- equal, densely packed blocks: one in-place ncclAllGather per array (each rank's block
- * travels over its own xGMI link); anything else: one ncclBroadcast per rank and array.                              */
+// (inside an in-process collective: a HIP error on this rank must not leave the peers waiting at the next barrier)
 void group_break(spdy_comm_group *g)
 {
     std::lock_guard<std::mutex> lk(g->mu);
     g->broken = true;
     g->cv.notify_all();
 }
-// (inside an in-process collective: a HIP error on this rank must not leave the peers waiting at the next barrier)
 #define HIP_TRY_GROUP(g_, expr)                                                                            \
     do {                                                                                                   \
         hipError_t e_ = (expr);                                                                            \
@@ -198,34 +197,58 @@ void group_break(spdy_comm_group *g)
         }                                                                                                  \
     } while (0)
 
+// a collective of an in-process group (the protocol at spdy_comm_group): registers this rank's narr arrays `mine`; for every rank
+// q, itself included, pull(q, q's registered arrays) issues this rank's copies on the plan's stream and returns an SPDY code
+template <class Pull>
+int group_exchange(spdy_comm *c, int narr, double *const *mine, Pull pull)
+{
+    spdy_plan *p = c->plan;
+    spdy_comm_group *g = c->grp;
+    const int me = c->rank;
+    NOT_CAPTURING(p, "a collective of an in-process communicator (peer copies ordered by events of other ranks' streams)");
+    for (int a = 0; a < narr; ++a) g->arr[me][a] = mine[a];
+    HIP_TRY_GROUP(g, hipEventRecord(g->ready[me], p->stream));
+    RC(group_barrier(g));
+    for (int q = 0; q < c->nranks; ++q) {
+        if (q != me) HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->ready[q], 0));
+        if (const int rc = pull(q, g->arr[q].data())) { group_break(g); return rc; }
+    }
+    HIP_TRY_GROUP(g, hipEventRecord(g->done[me], p->stream));
+    RC(group_barrier(g));
+    // (the events belong to the GROUP and live until spdy_comm_group_destroy: a peer that has already finished its step and
+    // destroyed its communicator cannot pull done[q] away from under this wait)
+    for (int q = 0; q < c->nranks; ++q)
+        if (q != me) HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->done[q], 0));
+    return SPDY_OK;
+}
+
+// 2-D device copy, pitches and width in doubles (a peer's memory too: peer access is enabled both ways when a rank joins its group)
+hipError_t copy2d(hipStream_t s, double *dst, size_t dpitch, const double *src, size_t spitch, size_t width, size_t height)
+{
+    if (!width || !height) return hipSuccess;
+    const size_t D = sizeof(double);
+    return hipMemcpy2DAsync(dst, dpitch * D, src, spitch * D, width * D, height, hipMemcpyDeviceToDevice, s);
+}
+
+/* In place: each of the narr arrays d[a] is partitioned into nranks blocks, block r = doubles [off[r], off[r] + cnt[r]); this
+ * rank has filled block `rank` of every array, afterwards every rank holds all blocks.  RCCL: ONE grouped operation on the
+ * plan's stream (graph-capturable) -- equal, densely packed blocks: one in-place ncclAllGather per array (each rank's block
+ * travels over its own xGMI link); anything else: one ncclBroadcast per rank and array.                              */
 int allgather_blocks(spdy_comm *c, int narr, double *const *d, const size_t *off, const size_t *cnt)
 {
     spdy_plan *p = c->plan;
     if (narr == 0 || c->dry) return SPDY_OK;
-    if (c->grp) {
-        spdy_comm_group *g = c->grp;
-        NOT_CAPTURING(p, "a collective of an in-process communicator (peer copies ordered by events of other ranks' streams)");
-        for (int a = 0; a < narr; ++a) g->arr[a][c->rank] = d[a];
-        HIP_TRY_GROUP(g, hipEventRecord(g->ready[c->rank], p->stream));
-        RC(group_barrier(g));
-        for (int q = 0; q < c->nranks; ++q) {
-            if (q == c->rank || cnt[q] == 0) continue;
-            HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->ready[q], 0));
+    if (c->grp)
+        return group_exchange(c, narr, d, [&](int q, double *const *theirs) -> int {
+            if (q == c->rank || cnt[q] == 0) return SPDY_OK;
             for (int a = 0; a < narr; ++a) {
-                if (g->device[q] == p->device)
-                    HIP_TRY_GROUP(g, hipMemcpyAsync(d[a] + off[q], g->arr[a][q] + off[q], cnt[q] * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+                if (c->grp->device[q] == p->device)
+                    HIP_TRY(hipMemcpyAsync(d[a] + off[q], theirs[a] + off[q], cnt[q] * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
                 else
-                    HIP_TRY_GROUP(g, hipMemcpyPeerAsync(d[a] + off[q], p->device, g->arr[a][q] + off[q], g->device[q], cnt[q] * sizeof(double), p->stream));
+                    HIP_TRY(hipMemcpyPeerAsync(d[a] + off[q], p->device, theirs[a] + off[q], c->grp->device[q], cnt[q] * sizeof(double), p->stream));
             }
-        }
-        HIP_TRY_GROUP(g, hipEventRecord(g->done[c->rank], p->stream));
-        RC(group_barrier(g));
-        // (the events belong to the GROUP and live until spdy_comm_group_destroy: a peer that has already finished its step and
-        // destroyed its communicator cannot pull done[q] away from under this wait)
-        for (int q = 0; q < c->nranks; ++q)
-            if (q != c->rank) HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->done[q], 0));
-        return SPDY_OK;
-    }
+            return SPDY_OK;
+        });
     if (c->nranks == 1 && !c->force) return SPDY_OK;
     bool even = c->force < 2;
     for (int r = 0; r < c->nranks; ++r) even = even && cnt[r] == cnt[0] && off[r] == off[0] + (size_t)r * cnt[0];
@@ -246,14 +269,15 @@ int allgather_blocks(spdy_comm *c, int narr, double *const *d, const size_t *off
  * LevelShard, csrc/spdy_kernels.hpp):
  *   by level : rank r holds ITS block -- nslab_r = F nl_r + X slabs -- over the whole horizontal domain (H doubles per slab);
  *   by range : rank r holds ALL blocks over ITS horizontal range [h0[r], h0[r] + len[r]) of every slab.
- * to_ranges: by level -> by range; otherwise back.  `lev` is the by-level array addressed like the whole stack (block r at slab
- * slab0_r, pitch H); `rng` the by-range array with pitch rp doubles per slab: len[rank] for the compact range stacks, H for a
- * whole array updated in place on a range (then rng == lev is allowed: what is read and what is written never overlap).
- * In-process groups: every rank PULLS its pieces with 2-D device copies (the protocol of allgather_blocks).  RCCL: one grouped
- * ncclSend / ncclRecv per peer on the plan's stream (graph-capturable) -- each rank's piece travels over its own xGMI link --
- * with the strided side packed / unpacked through c->stage by 2-D copies; force >= 1 sends the rank's own piece through RCCL too
- * (so that a 1-GPU box exercises the route).                                                                          */
-int transpose_blocks(spdy_comm *c, bool to_ranges, int F, int X, size_t H, const size_t *h0, const size_t *len, double *lev, double *rng, size_t rp)
+ * to_ranges: by level -> by range; otherwise back.  `own` is this rank's block of the by-level stack (nslab_rank slabs, pitch H);
+ * `rng` the by-range array with pitch rp doubles per slab: len[rank] for the compact range stacks, H for a whole array updated
+ * on a range.  Such a whole array may be the by-level stack itself (own == rng + slab0_rank H: in place; what is read and what
+ * is written never overlap).
+ * In-process groups: every rank PULLS its pieces with 2-D device copies (group_exchange).  RCCL: one grouped ncclSend /
+ * ncclRecv per peer on the plan's stream (graph-capturable) -- each rank's piece travels over its own xGMI link -- with the
+ * strided side packed / unpacked through c->stage by 2-D copies; force >= 1 sends the rank's own piece through RCCL too (so that
+ * a 1-GPU box exercises the route).                                                                                   */
+int transpose_blocks(spdy_comm *c, bool to_ranges, int F, int X, size_t H, const size_t *h0, const size_t *len, double *own, double *rng, size_t rp)
 {
     spdy_plan *p = c->plan;
     if (c->dry) return SPDY_OK;
@@ -264,34 +288,20 @@ int transpose_blocks(spdy_comm *c, bool to_ranges, int F, int X, size_t H, const
         level_range(kx, r, R, &lo, &hi);
         slab0[r] = (size_t)F * lo + (size_t)X * r; nslab[r] = (size_t)F * (hi - lo) + X;
     }
-    const size_t D = sizeof(double);
-    auto copy2d = [&](double *dst, size_t dpitch, const double *src, size_t spitch, size_t width, size_t height, int src_dev) -> hipError_t {
-        if (!width || !height) return hipSuccess;
-        (void)src_dev;      // (peer access is enabled both ways when a rank joins its group; unified addressing finds the device)
-        return hipMemcpy2DAsync(dst, dpitch * D, src, spitch * D, width * D, height, hipMemcpyDeviceToDevice, p->stream);
-    };
+    const bool whole = rp == H;                                 // the by-range side is a whole array (strided)
+    const bool inplace = whole && own == rng + slab0[me] * H;    // ... and own is its block: the own piece is where it belongs
+    hipStream_t s = p->stream;
     if (c->grp) {
-        spdy_comm_group *g = c->grp;
-        NOT_CAPTURING(p, "a collective of an in-process communicator (peer copies ordered by events of other ranks' streams)");
-        g->arr[0][me] = to_ranges ? lev : rng;
-        HIP_TRY_GROUP(g, hipEventRecord(g->ready[me], p->stream));
-        RC(group_barrier(g));
-        for (int q = 0; q < R; ++q) {
-            if (q != me) HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->ready[q], 0));
-            const double *src = g->arr[0][q];
-            if (to_ranges)      // block q, my range: out of q's by-level array
-                HIP_TRY_GROUP(g, copy2d(rng + slab0[q] * rp, rp, src + slab0[q] * H + h0[me], H, len[me], nslab[q], g->device[q]));
-            else {              // my block, range q: out of q's by-range array (its pitch: compact = len[q], in place = H)
-                const size_t qp = rp == H ? H : len[q], qoff = rp == H ? h0[q] : 0;
-                if (q == me && rp == H && rng == lev) continue;             // in place: the own piece is where it belongs
-                HIP_TRY_GROUP(g, copy2d(lev + slab0[me] * H + h0[q], H, src + slab0[me] * qp + qoff, qp, len[q], nslab[me], g->device[q]));
+        double *mine = to_ranges ? own : rng;
+        return group_exchange(c, 1, &mine, [&](int q, double *const *theirs) -> int {
+            if (to_ranges)      // block q, my range: out of q's block
+                HIP_TRY(copy2d(s, rng + slab0[q] * rp, rp, theirs[0] + h0[me], H, len[me], nslab[q]));
+            else if (q != me || !inplace) {     // my block, range q: out of q's by-range array (its pitch: compact = len[q], whole = H)
+                const size_t qp = whole ? H : len[q], qoff = whole ? h0[q] : 0;
+                HIP_TRY(copy2d(s, own + h0[q], H, theirs[0] + slab0[me] * qp + qoff, qp, len[q], nslab[me]));
             }
-        }
-        HIP_TRY_GROUP(g, hipEventRecord(g->done[me], p->stream));
-        RC(group_barrier(g));
-        for (int q = 0; q < R; ++q)
-            if (q != me) HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->done[q], 0));
-        return SPDY_OK;
+            return SPDY_OK;
+        });
     }
     // RCCL (one process per GPU)
     const bool self_rccl = c->force >= 1;
@@ -302,8 +312,8 @@ int transpose_blocks(spdy_comm *c, bool to_ranges, int F, int X, size_t H, const
     if (to_ranges) {
         // pack: for every peer q the own block's slabs restricted to range q, contiguous [nslab_me][len_q] at st + nslab_me h0[q]
         for (int q = 0; q < R; ++q) {
-            if (q == me && !self_rccl) HIP_TRY(copy2d(rng + slab0[me] * rp, rp, lev + slab0[me] * H + h0[me], H, len[me], nslab[me], p->device));
-            else HIP_TRY(copy2d(st + nslab[me] * h0[q], len[q], lev + slab0[me] * H + h0[q], H, len[q], nslab[me], p->device));
+            if (q == me && !self_rccl) HIP_TRY(copy2d(s, rng + slab0[me] * rp, rp, own + h0[me], H, len[me], nslab[me]));
+            else HIP_TRY(copy2d(s, st + nslab[me] * h0[q], len[q], own + h0[q], H, len[q], nslab[me]));
         }
         if (R > 1 || self_rccl) {
             if (rp != len[me]) return fail(SPDY_ERR_ARG, "RCCL transposition to ranges needs a compact range stack");
@@ -316,15 +326,14 @@ int transpose_blocks(spdy_comm *c, bool to_ranges, int F, int X, size_t H, const
             NCCL_TRY(rccl().GroupEnd());
         }
     } else {
-        const bool inplace = rp == H;
         if (R > 1 || self_rccl) {
-            if (inplace)            // the by-range side is strided too: pack what every peer q gets (its block, my range) behind the receive area
+            if (whole)              // the by-range side is strided too: pack what every peer q gets (its block, my range) behind the receive area
                 for (int q = 0; q < R; ++q)
-                    if (q != me || self_rccl) HIP_TRY(copy2d(st + nslab[me] * H + slab0[q] * len[me], len[me], rng + slab0[q] * H + h0[me], H, len[me], nslab[q], p->device));
+                    if (q != me || self_rccl) HIP_TRY(copy2d(s, st + nslab[me] * H + slab0[q] * len[me], len[me], rng + slab0[q] * H + h0[me], H, len[me], nslab[q]));
             NCCL_TRY(rccl().GroupStart());
             for (int q = 0; q < R; ++q) {
                 if (q == me && !self_rccl) continue;
-                const double *sendp = inplace ? st + nslab[me] * H + slab0[q] * len[me] : rng + slab0[q] * rp;
+                const double *sendp = whole ? st + nslab[me] * H + slab0[q] * len[me] : rng + slab0[q] * rp;
                 if (nslab[q] * len[me]) NCCL_GROUP_TRY(rccl().Send(sendp, nslab[q] * len[me], ncclDouble, q, c->comm, p->stream));
                 if (nslab[me] * len[q]) NCCL_GROUP_TRY(rccl().Recv(st + nslab[me] * h0[q], nslab[me] * len[q], ncclDouble, q, c->comm, p->stream));
             }
@@ -332,8 +341,8 @@ int transpose_blocks(spdy_comm *c, bool to_ranges, int F, int X, size_t H, const
         }
         for (int q = 0; q < R; ++q) {       // unpack (own piece: straight from the by-range array unless it went through RCCL)
             if (q == me && !self_rccl) {
-                if (!(inplace && rng == lev)) HIP_TRY(copy2d(lev + slab0[me] * H + h0[me], H, rng + slab0[me] * rp + (inplace ? h0[me] : 0), rp, len[me], nslab[me], p->device));
-            } else HIP_TRY(copy2d(lev + slab0[me] * H + h0[q], H, st + nslab[me] * h0[q], len[q], len[q], nslab[me], p->device));
+                if (!inplace) HIP_TRY(copy2d(s, own + h0[me], H, rng + slab0[me] * rp + (whole ? h0[me] : 0), rp, len[me], nslab[me]));
+            } else HIP_TRY(copy2d(s, own + h0[q], H, st + nslab[me] * h0[q], len[q], len[q], nslab[me]));
         }
     }
     return SPDY_OK;
@@ -403,7 +412,7 @@ int spdy_comm_group_create(int nranks, spdy_comm_group **grp)
     g->ready.assign(nranks, nullptr);
     g->done.assign(nranks, nullptr);
     g->device.assign(nranks, -1);
-    for (auto &a : g->arr) a.assign(nranks, nullptr);
+    g->arr.assign(nranks, {});
     *grp = g;
     return SPDY_OK;
 }
@@ -584,36 +593,23 @@ int allgather_ranges(spdy_comm *c, double *arr, size_t nrows, size_t H, const si
     spdy_plan *p = c->plan;
     if (c->dry || !nrows) return SPDY_OK;
     const int R = c->nranks, me = c->rank;
-    const size_t D = sizeof(double);
-    if (c->grp) {
-        spdy_comm_group *g = c->grp;
-        NOT_CAPTURING(p, "a collective of an in-process communicator (peer copies ordered by events of other ranks' streams)");
-        g->arr[0][me] = arr;
-        HIP_TRY_GROUP(g, hipEventRecord(g->ready[me], p->stream));
-        RC(group_barrier(g));
-        for (int q = 0; q < R; ++q) {
-            if (q == me || !len[q]) continue;
-            HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->ready[q], 0));
-            HIP_TRY_GROUP(g, hipMemcpy2DAsync(arr + h0[q], H * D, g->arr[0][q] + h0[q], H * D, len[q] * D, nrows, hipMemcpyDeviceToDevice, p->stream));
-        }
-        HIP_TRY_GROUP(g, hipEventRecord(g->done[me], p->stream));
-        RC(group_barrier(g));
-        for (int q = 0; q < R; ++q)
-            if (q != me) HIP_TRY_GROUP(g, hipStreamWaitEvent(p->stream, g->done[q], 0));
-        return SPDY_OK;
-    }
+    hipStream_t s = p->stream;
+    if (c->grp)
+        return group_exchange(c, 1, &arr, [&](int q, double *const *theirs) -> int {
+            if (q != me) HIP_TRY(copy2d(s, arr + h0[q], H, theirs[0] + h0[q], H, len[q], nrows));
+            return SPDY_OK;
+        });
     if (R == 1 && !c->force) return SPDY_OK;
     if (!c->stage) return fail(SPDY_ERR_STATE, "no staging buffer (spdy_sharded_step_workspace)");
     // compact [nrows][len_q] pieces side by side in the staging buffer: piece q at nrows h0[q]; one broadcast per rank
     double *st = c->stage;
-    HIP_TRY(hipMemcpy2DAsync(st + nrows * h0[me], len[me] * D, arr + h0[me], H * D, len[me] * D, nrows, hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(copy2d(s, st + nrows * h0[me], len[me], arr + h0[me], H, len[me], nrows));
     NCCL_TRY(rccl().GroupStart());
     for (int q = 0; q < R; ++q)
         if (len[q]) NCCL_GROUP_TRY(rccl().Broadcast(st + nrows * h0[q], st + nrows * h0[q], nrows * len[q], ncclDouble, q, c->comm, p->stream));
     NCCL_TRY(rccl().GroupEnd());
     for (int q = 0; q < R; ++q)
-        if (q != me && len[q])
-            HIP_TRY(hipMemcpy2DAsync(arr + h0[q], H * D, st + nrows * h0[q], len[q] * D, len[q] * D, nrows, hipMemcpyDeviceToDevice, p->stream));
+        if (q != me) HIP_TRY(copy2d(s, arr + h0[q], H, st + nrows * h0[q], len[q], len[q], nrows));
     return SPDY_OK;
 }
 int need_sharded(spdy_comm *c)
@@ -674,7 +670,9 @@ int spdy_comm_set_option(spdy_comm *c, const char *name, int value)
     if (c->plan->capturing) return fail(SPDY_ERR_STATE, "communicator options cannot change while a graph capture is open");
     const std::string n(name);
     if (n == "transpose") {
-        if (c->ranges_valid && !value) return fail(SPDY_ERR_STATE, "the state is range-sharded: spdy_sharded_state_gather_dev first");
+        if (!value && c->ranges_captured)
+            return fail(SPDY_ERR_STATE, "a transposed step was captured into a graph (replays leave the state range-sharded): create a new communicator");
+        if (!value && c->ranges_eager) return fail(SPDY_ERR_STATE, "the state is range-sharded: spdy_sharded_state_gather_dev first");
         c->transpose = value != 0;
     } else if (n == "force") c->force = value;
     else if (n == "dry") c->dry = value;
@@ -727,7 +725,7 @@ int spdy_sharded_step_stacks(spdy_comm *c, double **grid_stack, size_t *grid_dou
     return SPDY_OK;
 }
 
-int spdy_sharded_step_grid_dev(spdy_comm *c, const double *vor, const double *div, const double *t, const double *tr, const double *ps, int j2)
+int spdy_sharded_step_grid_dev(spdy_comm *c, double *vor, double *div, double *t, double *tr, double *ps, int j2)
 {
     NEED_COMM(c);
     spdy_plan *p = c->plan;
@@ -739,35 +737,31 @@ int spdy_sharded_step_grid_dev(spdy_comm *c, const double *vor, const double *di
     const Shard s = shard_of(c);
     const int kx = p->tab.kx;
     const Ranges rg = ranges_of(c);
-    // (inside a graph capture the exchange is always recorded: a replayed step follows a transposed step; on a whole state it
-    // moves values that are already there)
-    if (c->transpose && (c->ranges_valid || p->capturing) && (c->nranks > 1 || c->force)) {
+    const size_t slot = (size_t)(j2 - 1) * kx * s.ss, lev = slot + (size_t)s.lo * s.ss;    // time level j2; this rank's levels of it
+    if (c->transpose && (c->nranks > 1 || c->force)) {
         // Transposed form, exchange 4 (coefficient ranges -> levels), done where its result is first read: the previous step
         // left the new prognostics on (all levels x own coefficients); this rank's inverse batch reads time level j2 of ITS
         // levels at all coefficients, and the level-free ps whole.  In place in the caller's arrays (the part written here is
-        // exactly what this rank did not compute itself).
-        const size_t slot = (size_t)(j2 - 1) * kx * s.ss;
-        for (const double *arr : {vor, div, t, tr}) {
-            double *a2 = const_cast<double *>(arr) + slot;
-            RC(transpose_blocks(c, false, 1, 0, s.ss, rg.s0.data(), rg.sl.data(), a2, a2, s.ss));
-        }
-        RC(allgather_ranges(c, const_cast<double *>(ps) + (size_t)(j2 - 1) * s.ss, 1, s.ss, rg.s0.data(), rg.sl.data()));
+        // exactly what this rank did not compute itself).  Issued in every transposed step, eager or captured: a replayed graph
+        // leaves the state range-sharded without the host knowing, and on a whole state the exchange moves values already there.
+        for (double *arr : {vor, div, t, tr})
+            RC(transpose_blocks(c, false, 1, 0, s.ss, rg.s0.data(), rg.sl.data(), arr + lev, arr + slot, s.ss));
+        RC(allgather_ranges(c, ps + (size_t)(j2 - 1) * s.ss, 1, s.ss, rg.s0.data(), rg.sl.data()));
     }
-    const size_t lev = (size_t)(j2 - 1) * kx * s.ss + (size_t)s.lo * s.ss;     // this rank's levels of time level j2
-    double *Gb = c->G + (size_t)6 * s.lo * s.gs;                                // its block: ug | vg | vorg | divg | tg | trg, nl each
+    double *own = c->G + (size_t)6 * s.lo * s.gs;                               // its block: ug | vg | vorg | divg | tg | trg, nl each
     const spdy_spec_seg segs[4] = {{s.nl, vor + lev}, {s.nl, div + lev}, {s.nl, t + lev}, {s.nl, tr + lev}};
-    RC(spdy_inverse_batch_segs_dev(p, s.nl, vor + lev, div + lev, Gb, Gb + (size_t)s.nl * s.gs, 2, 4, segs, nullptr, 1,
-                                   Gb + (size_t)2 * s.nl * s.gs, 1, ps + (size_t)(j2 - 1) * s.ss, c->px, c->py, 2));
+    RC(spdy_inverse_batch_segs_dev(p, s.nl, vor + lev, div + lev, own, own + (size_t)s.nl * s.gs, 2, 4, segs, nullptr, 1,
+                                   own + (size_t)2 * s.nl * s.gs, 1, ps + (size_t)(j2 - 1) * s.ss, c->px, c->py, 2));
     if (c->transpose) {
         // exchange 1 (levels -> point ranges), the grid tendencies of ALL levels on the own points, exchange 2 (back: every
-        // rank's direct-batch operands come home).  1 / R of the column kernel's work per rank, nothing replicated.
+        // rank's direct-batch operands come home into U | V | PL, its block of the operand stack).  1 / R of the column kernel's
+        // work per rank, nothing replicated.
         const int me = c->rank;
-        RC(transpose_blocks(c, true, 6, 0, s.gs, rg.g0.data(), rg.gl.data(), c->G, c->Gb, rg.gl[me]));
+        RC(transpose_blocks(c, true, 6, 0, s.gs, rg.g0.data(), rg.gl.data(), own, c->Gb, rg.gl[me]));
         spdy::GridTend gt{c->Gb, c->Gb, c->Gb, c->Gb, c->Gb, c->Gb, c->px, c->py, c->U, c->V, c->PL, spdy::LevelShard{c->nranks, c->rank},
                           (int)rg.gl[me], (int)rg.g0[me], c->Ob};
         if (rg.gl[me]) KERNEL(spdy::launch_grid_tendencies(p->dev, gt, p->stream));
-        double *olev = c->U - ((size_t)9 * s.lo + me) * s.gs;                   // addressed like the whole operand stack: only the own block exists
-        RC(transpose_blocks(c, false, 9, 1, s.gs, rg.g0.data(), rg.gl.data(), olev, c->Ob, rg.gl[me]));
+        RC(transpose_blocks(c, false, 9, 1, s.gs, rg.g0.data(), rg.gl.data(), c->U, c->Ob, rg.gl[me]));
         return SPDY_OK;
     }
     std::vector<size_t> off(c->nranks), cnt(c->nranks);
@@ -796,23 +790,23 @@ int spdy_sharded_step_spectral_dev(spdy_comm *c, double *vor, double *div, doubl
     RC(spdy_sharded_step_workspace(c));
     const Shard s = shard_of(c);
     const int kx = p->tab.kx, P = 3 * s.nl;
-    double *Tb = c->T + ((size_t)9 * s.lo + c->rank) * s.ss;                    // this rank's block: A | B | C (3 nl each) | psdt
-    double *A = Tb, *B = Tb + (size_t)P * s.ss, *C = Tb + (size_t)2 * P * s.ss;
+    double *own = c->T + ((size_t)9 * s.lo + c->rank) * s.ss;                   // this rank's block: A | B | C (3 nl each) | psdt
+    double *A = own, *B = own + (size_t)P * s.ss, *C = own + (size_t)2 * P * s.ss;
     const bool raw = !c->transpose && use_raw63(p, P);     // (transposed form: vds needs whole rows -- applied here, before the exchange)
     if (raw) RC(direct_batch_raw63(p, P, c->U, c->V, 2, P + 1, c->PL, C, A, B));
     else RC(spdy_direct_batch_dev(p, P, c->U, c->V, A, B, 2, P + 1, c->PL, C));
     if (c->transpose) {
         // exchange 3 (levels -> coefficient ranges), then the spectral step of ALL levels on the own coefficients.  The new state
-        // stays range-sharded: exchange 4 runs at the start of the next grid half (or spdy_sharded_state_gather_dev).
+        // stays range-sharded: exchange 4 runs at the start of the next grid half (spdy_sharded_state_gather_dev: whole again).
         const Ranges rg = ranges_of(c);
         const int me = c->rank;
-        RC(transpose_blocks(c, true, 9, 1, s.ss, rg.s0.data(), rg.sl.data(), c->T, c->Tb, rg.sl[me]));
+        RC(transpose_blocks(c, true, 9, 1, s.ss, rg.s0.data(), rg.sl.data(), own, c->Tb, rg.sl[me]));
         if (!tend_out) tend_out = c->tend;
         spdy::SpecStep a{c->Tb, c->Tb, c->Tb, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
                          p->tab.ix == 4 * p->tab.iy, nullptr, nullptr, spdy::LevelShard{c->nranks, c->rank}, tend_out,
                          (int)(rg.s0[me] / 2), (int)(rg.sl[me] / 2)};
         if (rg.sl[me]) KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
-        c->ranges_valid = c->nranks > 1 || c->force;
+        if (c->nranks > 1 || c->force) (p->capturing ? c->ranges_captured : c->ranges_eager) = true;
         return SPDY_OK;
     }
     std::vector<size_t> off(c->nranks), cnt(c->nranks);
@@ -832,7 +826,7 @@ int spdy_sharded_step_spectral_dev(spdy_comm *c, double *vor, double *div, doubl
 
 /* Every rank ends up with the complete arrays again: rows x (mx nx complex) arrays that the transposed form's spectral half
  * left current on (all rows x own coefficients) only -- the prognostics (2 kx rows each; ps: 2), phi (kx), the final tendencies
- * (4 kx + 1).  No-op for the all-gather form and for one rank.  Marks the state whole: the next grid half skips exchange 4.   */
+ * (4 kx + 1).  No-op for the all-gather form and for one rank.                                                              */
 int spdy_sharded_gather_ranges_dev(spdy_comm *c, int narr, double *const *arr, const int *nrows)
 {
     NEED_COMM(c);
@@ -850,15 +844,17 @@ int spdy_sharded_gather_ranges_dev(spdy_comm *c, int narr, double *const *arr, c
     return SPDY_OK;
 }
 
+// the prognostics, eagerly only: afterwards the host knows that the state is whole (spdy_comm_set_option may switch the form back)
 int spdy_sharded_state_gather_dev(spdy_comm *c, double *vor, double *div, double *t, double *tr, double *ps)
 {
     NEED_COMM(c);
+    NOT_CAPTURING(c->plan, "spdy_sharded_state_gather_dev (the host marks the state whole when it is called, not when a graph runs)");
     if (!vor || !div || !t || !tr || !ps) return fail(SPDY_ERR_ARG, "null device pointer");
     const int kx = c->plan->tab.kx;
     double *arr[5] = {vor, div, t, tr, ps};
     const int rows[5] = {2 * kx, 2 * kx, 2 * kx, 2 * kx, 2};
     RC(spdy_sharded_gather_ranges_dev(c, 5, arr, rows));
-    c->ranges_valid = false;
+    c->ranges_eager = false;
     return SPDY_OK;
 }
 

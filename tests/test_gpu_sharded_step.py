@@ -170,8 +170,8 @@ def test_sharded_step_transposed_in_process_ranks(tag, world, oracle_factory, mo
     """The TRANSPOSED form of the level-sharded step (spdy_comm_set_option "transpose"; include/spdy.h): levels <-> point ranges
     around the grid-space column kernel, levels <-> coefficient ranges around the spectral step (tendencies.f90:109-197, 242-293,
     implicit.f90:168-217 are independent in the horizontal), four exchanges instead of two all-gathers, nothing replicated.
-    Real multi-rank runs with in-process ranks on one GPU, two chained steps (the second one starts with exchange 4 in the
-    caller's arrays), then the state gather.  Against the oracle's call-by-call step at 1e-12; against the unsharded device step
+    Real multi-rank runs with in-process ranks on one GPU, two chained steps (each starts with exchange 4 in the caller's arrays;
+    on the first one's whole state it moves values that are already there), then the state gather.  Against the oracle's call-by-call step at 1e-12; against the unsharded device step
     BIT FOR BIT at T30 (same kernels' expressions on the same values, whatever the rank count) and to rounding at T63 L16 (there
     the unsharded step applies vds inside the spectral step, the transposed form before its exchange)."""
     import speedy_f90_amd as s
@@ -439,6 +439,7 @@ def test_sharded_step_transposed_rccl_world1_in_graph(tag, oracle_factory, monke
     (the second starts with exchange 4 in the caller's arrays), then the gather, against the oracle and the unsharded device step."""
     import torch
     import speedy_f90_amd as s
+    from speedy_f90_amd._lib import SpdyError
     kx = VARIANTS[tag][3]
     o = oracle_factory(tag)
     o.tail_init(DT)
@@ -477,6 +478,14 @@ def test_sharded_step_transposed_rccl_world1_in_graph(tag, oracle_factory, monke
         assert np.array_equal(got, whole[n]) if exact else synth.relerr(got, whole[n]) <= 1e-13, n
     if exact:
         assert np.array_equal(tend.cpu().numpy(), whole["tend"]) and np.array_equal(phi.cpu().numpy(), whole["phi"])
+    # the host cannot know whether the graph was replayed since the gather: the form stays transposed for good, and a gather
+    # (which would record "whole" on the host) is refused inside a capture
+    with pytest.raises(SpdyError, match="new communicator") as e:
+        comm.set_option("transpose", 0)
+    assert e.value.code == -5                       # SPDY_ERR_STATE
+    with pytest.raises(SpdyError, match="capture"):
+        with sp.graph_capture():
+            comm.state_gather_(D["vor"], D["div"], D["t"], D["tr"], D["ps"])
     print("\n[transposed step over RCCL, world 1 forced, %s] %d graph nodes; librccl: %s" % (tag, nodes, d["librccl"]))
     g.close(); comm.close(); sp.close()
 
@@ -518,7 +527,18 @@ def _rccl_rank(rank, world, port, tag, q, transpose=False):
         if transpose:
             comm.state_gather_(D["vor"], D["div"], D["t"], D["tr"], D["ps"])
             sp.synchronize()
-        err = max(max(synth.relerr(D[n].cpu().numpy(), ref[n]), wave_relerr(D[n].cpu().numpy(), ref[n])) for n in PROGS)
+        worst_err = lambda: max(max(synth.relerr(D[n].cpu().numpy(), ref[n]), wave_relerr(D[n].cpu().numpy(), ref[n])) for n in PROGS)
+        err = worst_err()
+        if transpose:
+            # a replay after the gather leaves the state range-sharded again without the host knowing: the eager step after it
+            # must still bring in the other ranks' coefficients first (exchange 4), or it reads stale ones
+            g.launch()
+            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, DT, ROB, WIL, phi)
+            comm.state_gather_(D["vor"], D["div"], D["t"], D["tr"], D["ps"])
+            sp.synchronize()
+            for _ in range(2):
+                ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
+            err = max(err, worst_err())
         g.close(); comm.close(); sp.close()
         q.put((rank, err))
     finally:
@@ -532,7 +552,8 @@ def test_sharded_step_rccl_ranks(world, tag, transpose):
     all-gathers included -- into a graph, replays it twice from NaN-poisoned exchange stacks and must hold the oracle's
     prognostics.  world 3 with 8 levels: ragged blocks -> grouped ncclBroadcast; world 8 at T30 L8 is config 3's own rank
     count (one level per rank), world 8 at T63 L16 two levels per rank.  transpose: the transposed form (four grouped
-    ncclSend / ncclRecv exchanges, then the state gather).  Skipped on boxes with fewer GPUs."""
+    ncclSend / ncclRecv exchanges, then the state gather; then one more replay, an eager step and a second gather against two
+    more oracle steps).  Skipped on boxes with fewer GPUs."""
     import torch
     if torch.cuda.device_count() < world:
         pytest.skip("needs %d GPUs, %d visible" % (world, torch.cuda.device_count()))
