@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: grid<->spectral round trips per second at T30 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res t30|t63] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res t30|t63] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one device-resident batch of B synthetic 2-D
 fields: grid_to_spec followed by spec_to_grid(.,kcos=1) (spectral.f90:98-122), FP64.
@@ -11,12 +11,15 @@ N > 1 (one rank per GPU): the batch index (field x level) is sharded, every rank
 B fields, no data-path collective -> weak scaling; value = all ranks' round trips / max-over-ranks
 time.  `python bench.py --gpus N` on its own starts the N ranks itself (it re-executes under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); started
-by a launcher (RANK / WORLD_SIZE in the environment) it runs as that rank.  The N > 1 line also
-carries `multi_gpu`: the RCCL communicator the C ABI created (spdy_comm_create), the level all-gather
-of the semi-implicit solve (implicit.f90:174-216) through it, and a level-sharded step graph with
-spdy_implicit_terms_sharded_dev captured -- timed with and without the gather, outside `value`.
+by a launcher (RANK / WORLD_SIZE in the environment) it runs as that rank.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with these extra objects:
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, the timed blocks, config,
+path_hbm_frac).  --full adds every side measurement below; --no-pmc, --no-extras, --no-cpu-baseline and --no-multi
+leave single ones out of it, and --force-multi adds `multi_gpu` at N = 1.
+  multi_gpu              : (N > 1) the RCCL communicator the C ABI created (spdy_comm_create), the level all-gather of
+                           the semi-implicit solve (implicit.f90:174-216) through it, and a level-sharded step graph
+                           with spdy_implicit_terms_sharded_dev captured -- timed with and without the gather
   roofline               : dominant kernel's algorithmic bytes per launch / its HIP-event launch time
   cpu_baseline           : the reference's own CPU path (oracle/_ref, flang -O2 build = the parity oracle) -- or the C
                            port if that is absent -- timed on ONE host core on a bounded sample of the same fields
@@ -550,10 +553,11 @@ def live_pmc_traffic(res, nb, fused, timeout_s=150.0):
         for counter in ("FETCH_SIZE", "WRITE_SIZE", None):
             out = os.path.join(tmp, counter or "trace")
             # (the third pass: kernel trace only, the K steps replayed as ONE graph like the timed region -- the kernels' average
-            # durations in the launch mode `value` is measured in)
+            # durations in the launch mode `value` is measured in.  --full without its side measurements: the child also
+            # runs the eager HIP-event profile steps, which the counter medians and the trace averages have always included)
             cmd = [exe, "--kernel-trace"] + (["--pmc", counter] if counter else ["--stats"]) + ["-d", out, "-o", "p", "--", sys.executable,
                    os.path.join(ROOT, "bench.py"), "--res", res, "--batch", str(nb), "--fused", str(fused), "--steps", "4" if counter else "20", "--warmup", "2",
-                   "--no-cpu-baseline", "--no-extras", "--no-pmc"] + (["--no-graph"] if counter else [])
+                   "--full", "--no-cpu-baseline", "--no-extras", "--no-pmc"] + (["--no-graph"] if counter else [])
             left = timeout_s - (time.perf_counter() - t0)
             if left < 20:
                 return None, "rocprofv3 passes ran out of time"
@@ -597,6 +601,69 @@ def live_pmc_traffic(res, nb, fused, timeout_s=150.0):
     out["_calls_in_graph"] = {kind: m["avg_us_in_graph"][1] for kind, m in med.items() if "avg_us_in_graph" in m}
     return out, ("measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (two passes of this command with --steps 4, "
                  "%d dispatches per kernel, median), (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 per launch; %.0f s" % (n, time.perf_counter() - t0))
+
+
+def roofline(torch, sp, dev, args, nb, world, prof, prof_steps):
+    """The `roofline` object of a --full line (rank 0): the dominant kernel of `prof` (HIP-event launch times of `prof_steps`
+    eager steps) against its algorithmic bytes, with the HBM traffic per launch measured or looked up."""
+    ab = algorithmic_bytes(sp)
+    kinds = {k: (ms / max(cnt, 1)) for k, (ms, cnt) in prof.items() if cnt}
+    dom = max(kinds, key=kinds.get)
+    dom_ms = kinds[dom]
+    achieved = ab[dom] * nb / (dom_ms * 1e-3) / 1e9
+    # HBM traffic per launch: NOT measured in this run (PMC counters need rocprofv3 passes of their own) -- the per-field
+    # figure of the committed counter passes (profiles/pmc_traffic.json: 2 x FETCH_SIZE + WRITE_SIZE per launch / fields,
+    # source file named there) times this run's batch; `traffic_source` says so
+    traffic, traffic_source, mfma_util, mfma_source = None, None, None, None
+    rocprof_us, rocprof_calls = {}, {}
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            per_field = tj.get(args.res, {}).get(dom)
+            traffic = per_field * nb if per_field else None
+            if traffic:
+                src = tj.get("sources", {}).get("%s/%s" % (args.res, dom)) or tj.get("source", "committed")      # (per entry: the file may carry passes of several rounds)
+                traffic_source = "profiles/pmc_traffic.json (%s): rocprofv3 PMC passes of an earlier run of this command, bytes per field x %d fields; not measured in this run" % (src, nb)
+            # FP64 matrix-pipe utilisation of the dominant kernel: its matrix instructions are a fixed count per field
+            # (SQ_VALU_MFMA_BUSY_CYCLES of the committed counter pass: 16 cycles per v_mfma_f64_4x4x4_4b, summed over the
+            # SIMDs) -- divided by THIS run's launch duration x shader clock x SIMDs
+            busy = tj.get("counters", {}).get("%s/%s" % (args.res, dom), {}).get("mfma_busy_cycles_per_field")
+            if busy:
+                props = torch.cuda.get_device_properties(dev)
+                clock_hz = float(getattr(props, "clock_rate", 2400000)) * 1e3
+                simds = 4 * props.multi_processor_count
+                mfma_util = busy * nb / (dom_ms * 1e-3 * clock_hz * simds)
+                mfma_source = ("SQ_VALU_MFMA_BUSY_CYCLES per field of the committed PMC pass (%s) x %d fields / (this run's launch time x "
+                               "%.2f GHz x %d SIMDs)" % (tj.get("source", "committed"), nb, clock_hz * 1e-9, simds))
+        except Exception:
+            traffic = None
+    # ... unless this run can measure it itself (N = 1; rank 0 is the only rank): a child run of this command under rocprofv3
+    if world == 1 and not args.no_pmc:
+        live, note = live_pmc_traffic(args.res, nb, args.fused)
+        if live and dom in live:
+            traffic, traffic_source = live[dom], note
+            traffic_all = {k: v for k, v in live.items() if not k.startswith("_")}
+            rocprof_us, rocprof_calls = live.get("_avg_us_in_graph", {}), live.get("_calls_in_graph", {})
+        else:
+            traffic_all = None
+            traffic_source = (traffic_source or "") + " [live rocprofv3 passes unavailable: %s]" % note
+    else:
+        traffic_all = None
+    return {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+            "traffic_over_algorithmic": (traffic / (ab[dom] * nb)) if traffic else None, "traffic_all_kernels": traffic_all,
+            # the same kernel's average duration by rocprofv3 --kernel-trace --stats of a child run that replays the K steps as one
+            # graph (the timed region's launch mode; `launch_ms` above is from HIP events around eager launches), and the fraction it gives
+            "launch_ms_rocprof_in_graph": (rocprof_us[dom] * 1e-3) if dom in rocprof_us else None,
+            "frac_rocprof_in_graph": (ab[dom] * nb / (rocprof_us[dom] * 1e-6) / 1e9 / HBM_PEAK_GBS) if dom in rocprof_us else None,
+            "rocprof_in_graph_us": rocprof_us or None, "rocprof_in_graph_calls": rocprof_calls or None,
+            "launch_ms": dom_ms, "bytes_per_launch": ab[dom] * nb,
+            "mfma_util": mfma_util, "mfma_util_source": mfma_source,
+            "all_kernels_ms": kinds,
+            "launch_ms_method": "HIP events around each kernel on the launch stream, %d EAGER steps outside the timed region; "
+                                "the timed blocks replay one graph of the K steps, so sum(all_kernels_ms) exceeds ms_per_step "
+                                "by the event overhead (a few %%): `frac` is on the conservative side" % prof_steps}
 
 
 def flatten_for_driver(res, this_res):
@@ -869,14 +936,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--res", default="t30", choices=["t30", "t63"])
     ap.add_argument("--batch", type=int, default=0, help="fields per GPU (default 6144 at T30, 1536 at T63)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, run the side measurements too: per-kernel times and `roofline`, "
+                                                        "`extras`, the CPU baselines (N = 1), `multi_gpu` (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-graph", action="store_true", help="issue the timed steps as eager launches instead of one HIP graph replay")
-    ap.add_argument("--no-multi", action="store_true", help="N > 1: skip the `multi_gpu` side measurements (RCCL all-gather, level-sharded step graph)")
-    ap.add_argument("--force-multi", action="store_true", help="run the `multi_gpu` measurements at N = 1 too (with SPDY_COMM_FORCE=1 the collectives are really issued)")
+    ap.add_argument("--no-multi", action="store_true", help="--full, N > 1: skip the `multi_gpu` side measurements (RCCL all-gather, level-sharded step graph)")
+    ap.add_argument("--force-multi", action="store_true", help="--full: run the `multi_gpu` measurements at N = 1 too (with SPDY_COMM_FORCE=1 the collectives are really issued)")
     ap.add_argument("--multi-timeout", type=float, default=90.0, help="seconds before the `multi_gpu` measurements are abandoned")
     ap.add_argument("--dry-launch", action="store_true", help="start the ranks, print each rank's launcher environment as JSON, exit (no GPU needed)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the model-shaped / operator-fused / T63 side measurements")
-    ap.add_argument("--no-pmc", action="store_true", help="do not measure `roofline.traffic` with rocprofv3 counter passes of a child run (N = 1 only; "
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the model-shaped / operator-fused / T63 side measurements")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not measure `roofline.traffic` with rocprofv3 counter passes of a child run (N = 1 only; "
                                                           "falls back to the committed per-field figures of profiles/pmc_traffic.json)")
     ap.add_argument("--fused", type=int, default=-1, help="1 fused single-pass kernels, 0 four-kernel path, -1 auto")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -887,6 +956,8 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.force_multi and not args.full:
+        raise SystemExit("--force-multi is a side measurement: it needs --full")
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ       # torchrun / torch.distributed.run started us
     if not launched and args.gpus > 1:
         raise SystemExit(self_launch(args, sys.argv[1:]))                # one rank per GPU; this process only waits
@@ -976,61 +1047,21 @@ def main():
     # the outputs of the last timed step, before anything else runs on the plan
     dumped = dump_outputs(torch, args.dump_outputs, spec, out, rank, world) if args.dump_outputs else None
 
-    # per-kernel launch durations: HIP events on the launch stream, outside the timed region
-    sp.set_profiling(True)
-    prof_steps = max(5, min(20, args.steps))
-    for _ in range(prof_steps):
-        step()
-    prof = sp.get_profile()
-    sp.set_profiling(False)
+    # A plain run runs nothing more on the GPU: its line is made from the timed blocks alone.  --full adds the side
+    # measurements (none of them inside `value`).
+    prof, prof_steps = None, None
+    if args.full:
+        # per-kernel launch durations: HIP events on the launch stream, outside the timed region
+        sp.set_profiling(True)
+        prof_steps = max(5, min(20, args.steps))
+        for _ in range(prof_steps):
+            step()
+        prof = sp.get_profile()
+        sp.set_profiling(False)
 
     res = None
     if rank == 0:
-        ab = algorithmic_bytes(sp)
         value = world * nb * args.steps / elapsed
-        kinds = {k: (ms / max(cnt, 1)) for k, (ms, cnt) in prof.items() if cnt}
-        dom = max(kinds, key=kinds.get)
-        dom_ms = kinds[dom]
-        achieved = ab[dom] * nb / (dom_ms * 1e-3) / 1e9
-        # HBM traffic per launch: NOT measured in this run (PMC counters need rocprofv3 passes of their own) -- the per-field
-        # figure of the committed counter passes (profiles/pmc_traffic.json: 2 x FETCH_SIZE + WRITE_SIZE per launch / fields,
-        # source file named there) times this run's batch; `traffic_source` says so
-        traffic, traffic_source, mfma_util, mfma_source = None, None, None, None
-        rocprof_us, rocprof_calls = {}, {}
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                per_field = tj.get(args.res, {}).get(dom)
-                traffic = per_field * nb if per_field else None
-                if traffic:
-                    src = tj.get("sources", {}).get("%s/%s" % (args.res, dom)) or tj.get("source", "committed")      # (per entry: the file may carry passes of several rounds)
-                    traffic_source = "profiles/pmc_traffic.json (%s): rocprofv3 PMC passes of an earlier run of this command, bytes per field x %d fields; not measured in this run" % (src, nb)
-                # FP64 matrix-pipe utilisation of the dominant kernel: its matrix instructions are a fixed count per field
-                # (SQ_VALU_MFMA_BUSY_CYCLES of the committed counter pass: 16 cycles per v_mfma_f64_4x4x4_4b, summed over the
-                # SIMDs) -- divided by THIS run's launch duration x shader clock x SIMDs
-                busy = tj.get("counters", {}).get("%s/%s" % (args.res, dom), {}).get("mfma_busy_cycles_per_field")
-                if busy:
-                    props = torch.cuda.get_device_properties(dev)
-                    clock_hz = float(getattr(props, "clock_rate", 2400000)) * 1e3
-                    simds = 4 * props.multi_processor_count
-                    mfma_util = busy * nb / (dom_ms * 1e-3 * clock_hz * simds)
-                    mfma_source = ("SQ_VALU_MFMA_BUSY_CYCLES per field of the committed PMC pass (%s) x %d fields / (this run's launch time x "
-                                   "%.2f GHz x %d SIMDs)" % (tj.get("source", "committed"), nb, clock_hz * 1e-9, simds))
-            except Exception:
-                traffic = None
-        # ... unless this run can measure it itself (N = 1; rank 0 is the only rank): a child run of this command under rocprofv3
-        if world == 1 and not args.no_pmc:
-            live, note = live_pmc_traffic(args.res, nb, args.fused)
-            if live and dom in live:
-                traffic, traffic_source = live[dom], note
-                traffic_all = {k: v for k, v in live.items() if not k.startswith("_")}
-                rocprof_us, rocprof_calls = live.get("_avg_us_in_graph", {}), live.get("_calls_in_graph", {})
-            else:
-                traffic_all = None
-                traffic_source = (traffic_source or "") + " [live rocprofv3 passes unavailable: %s]" % note
-        else:
-            traffic_all = None
         res = {
             "metric": "spectral transforms/sec (grid<->spec round-trip) at %s L8" % args.res.upper(),
             "value": value, "unit": "round trips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1044,24 +1075,12 @@ def main():
                                    % (args.res.upper(), sp.ix, sp.il, sp.trunc, nb),
                        "fields_per_gpu": nb, "resolution": args.res, "parallelism": "batch-shard x%d" % world},
             "transforms_per_s": 2 * value,
-            "path_hbm_frac": value / world * ab["round_trip"] / (HBM_PEAK_GBS * 1e9),
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "traffic_over_algorithmic": (traffic / (ab[dom] * nb)) if traffic else None, "traffic_all_kernels": traffic_all,
-                         # the same kernel's average duration by rocprofv3 --kernel-trace --stats of a child run that replays the K steps as one
-                         # graph (the timed region's launch mode; `launch_ms` above is from HIP events around eager launches), and the fraction it gives
-                         "launch_ms_rocprof_in_graph": (rocprof_us[dom] * 1e-3) if dom in rocprof_us else None,
-                         "frac_rocprof_in_graph": (ab[dom] * nb / (rocprof_us[dom] * 1e-6) / 1e9 / HBM_PEAK_GBS) if dom in rocprof_us else None,
-                         "rocprof_in_graph_us": rocprof_us or None, "rocprof_in_graph_calls": rocprof_calls or None,
-                         "launch_ms": dom_ms, "bytes_per_launch": ab[dom] * nb,
-                         "mfma_util": mfma_util, "mfma_util_source": mfma_source,
-                         "all_kernels_ms": kinds,
-                         "launch_ms_method": "HIP events around each kernel on the launch stream, %d EAGER steps outside the timed region; "
-                                             "the timed blocks replay one graph of the K steps, so sum(all_kernels_ms) exceeds ms_per_step "
-                                             "by the event overhead (a few %%): `frac` is on the conservative side" % prof_steps},
+            "path_hbm_frac": value / world * algorithmic_bytes(sp)["round_trip"] / (HBM_PEAK_GBS * 1e9),
         }
+        if args.full:
+            res["roofline"] = roofline(torch, sp, dev, args, nb, world, prof, prof_steps)
     # N > 1 (every rank takes part; never fatal, never inside `value`): what a level-sharded step adds
-    if (world > 1 and not args.no_multi and args.res == "t30") or args.force_multi:
+    if args.full and ((world > 1 and not args.no_multi and args.res == "t30") or args.force_multi):
         with Watchdog(args.multi_timeout, rank, res):
             try:
                 multi = multi_gpu_report(s, torch, synth, sp, dev, rank, world)
@@ -1070,12 +1089,12 @@ def main():
         if rank == 0:
             res["multi_gpu"] = multi
     if rank == 0:
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:
                 res["extras"] = extras(s, torch, synth, sp, dev, args)
             except Exception as e:   # the extras never break the headline line
                 res["extras"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.res)                     # the parity oracle's build (flang -O2), one core
             res["gpu_over_cpu_core"] = value / res["cpu_baseline"]["value"]
             fast = cpu_baseline(args.res, "fast")                            # upstream-like -Ofast build, one core
