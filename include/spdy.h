@@ -148,7 +148,8 @@ const char *spdy_last_error(void);
  * Names: sia_half coa_half cosgr cosgr2 hsg dhs fsg dhsr fsgr work ifac epsi wt poly nsh2
  *        el2 elm2 el4 trfilt gradx gradym gradyp uvdx uvdym uvdyp vddym vddyp
  *        dmp dmpd dmps dmp1 dmp1d dmp1s tref tref1 tref2 tref3 xc xd xj dhsx elz
- *        xgeop1 xgeop2 corf tcorv qcorv coriol sigl sigh grdsig grdscp wvi entr               */
+ *        xgeop1 xgeop2 corf tcorv qcorv coriol sigl sigh grdsig grdscp wvi entr fband
+ *        fsol ozone ozupp zenit stratz (the last five after spdy_radiation_set_date)            */
 int spdy_get_table(const spdy_plan *plan, const char *name, double *buf, int cap);
 
 /* ---- grid <-> spectral transforms --------------------------------------------------------
@@ -469,6 +470,45 @@ int spdy_moist_columns_dev(spdy_plan *plan, int nb, const double *tg, const doub
 int spdy_moist_workspace(spdy_plan *plan);
 int spdy_moist_physics_dev(spdy_plan *plan, const double *t, const double *q, const double *phi, const double *ps,
                            double *ttend, double *qtend, const spdy_moist_out *out);
+
+/* ---- column physics: radiation (physics.f90:146-166 and :180-186) -----------------------------------------------------------
+ * The reference splits radiation in two halves with the surface fluxes between them, and so does the device: the DOWN half
+ * (compute_sw set: gse, clouds with qcloud = qa(:,:,kx-1), the shortwave fluxes, tt_rsw = dfabs*rps*grdscp and the longwave
+ * transmissivities tau2 / stratc; always: the downward longwave fluxes) and the UP half (the upward longwave fluxes from the
+ * caller's surface temperature ts and surface emission fsfcu = slru(:,:,3), tt_rlw = dfabs*rps*grdscp, then
+ * ttend = (ttend + tt_rsw) + tt_rlw in place).  A host with physics calls spdy_moist_columns_dev, the down half, its own surface
+ * fluxes (which read ssrd and slrd), then the up half.
+ * What the reference keeps in module state (tau2, stratc, flux) is the caller's RADIATION STATE: device memory of
+ * nb * spdy_radiation_state_size(plan) doubles, one block per model state, kept across steps (and graph replays).  The first
+ * call on a state must have compute_sw = 1, as the reference's first step has (mod(1, nstrad) == 1).  On steps without
+ * shortwave the reference reads tt_rsw uninitialised (a local array without save); the device holds the last shortwave call's
+ * tt_rsw in the state instead, as ssrd, ssr, tsr and tau2 are held -- a documented deviation.
+ * Boundary fields: spdy_radiation_set_date makes the zonal forcing of a date (get_zonal_average_fields + solar,
+ * shortwave_radiation.f90:238-329) -- on a device plan it also copies them into plan memory, stream-ordered on the plan's
+ * stream, so a captured graph picks up a new date on its next replay (not callable during a capture).  Per column the caller
+ * passes the land fraction fmask and the surface albedo albsfc (spdy_rad_surface).
+ * Inputs: tg, qg, phig (ix,il,kx), pslg (ix,il) as for spdy_moist_columns_dev (qg is clamped locally), and the moist block's
+ * rh (ix,il,kx), precnv, precls (ix,il) and iptop (int, ix,il); rh / precnv / precls / iptop / sfc are read with compute_sw
+ * only and may be NULL otherwise.  fband(nint(T)) is indexed with the index clamped to [100, 400], so any temperature is safe.
+ * Checks: kx outside [5, 16] SPDY_ERR_ARG; no sigma levels or no date set SPDY_ERR_STATE; a NULL required pointer with nb > 0
+ * SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE.  Both halves can be captured in a graph; `out` is read at call time.    */
+typedef struct {                      /* per state, (ix,il) each, nb states back to back                                      */
+    const double *fmask, *albsfc;     /* land fraction [0, 1], surface albedo                                                  */
+} spdy_rad_surface;
+typedef struct {                      /* per state; any member may be NULL = not written                                      */
+    double *cloudc, *clstr;           /* (ix,il) clouds: total and stratiform cover      -- compute_sw calls only             */
+    int *icltop;                      /* (ix,il) cloud top level (kx + 1 = none)           -- compute_sw calls only             */
+    double *ssrd, *ssr, *tsr;         /* (ix,il) shortwave: surface down, surface net, top net -- compute_sw calls only (held)  */
+    double *slrd, *slr, *olr;         /* (ix,il) longwave: surface down (down half), surface net up and outgoing (up half)      */
+    double *tt_rsw, *tt_rlw;          /* (ix,il,kx) heating rates: tt_rsw on compute_sw down calls, tt_rlw on up calls        */
+} spdy_rad_out;
+int spdy_radiation_set_date(spdy_plan *plan, double tyear);   /* tyear: fraction of the year, 0 = 1 January 0h                */
+int spdy_radiation_state_size(const spdy_plan *plan);        /* doubles per model state (> 0), or an SPDY_ERR code          */
+int spdy_radiation_down_dev(spdy_plan *plan, int nb, int compute_sw, const double *tg, const double *qg, const double *phig,
+                            const double *pslg, const double *rh, const double *precnv, const double *precls, const int *iptop,
+                            const spdy_rad_surface *sfc, double *state, const spdy_rad_out *out);
+int spdy_radiation_up_dev(spdy_plan *plan, int nb, const double *tg, const double *pslg, const double *ts, const double *fsfcu,
+                          double *state, double *ttend, const spdy_rad_out *out);
 
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,

@@ -109,6 +109,10 @@ SIGNATURES = {
     "spdy_moist_columns_dev": [c_void_p, c_int] + [c_void_p] * 7,
     "spdy_moist_workspace": [c_void_p],
     "spdy_moist_physics_dev": [c_void_p] * 8,
+    "spdy_radiation_set_date": [c_void_p, c_double],
+    "spdy_radiation_state_size": [c_void_p],
+    "spdy_radiation_down_dev": [c_void_p, c_int, c_int] + [c_void_p] * 11,
+    "spdy_radiation_up_dev": [c_void_p, c_int] + [c_void_p] * 7,
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

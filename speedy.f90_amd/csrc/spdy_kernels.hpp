@@ -288,4 +288,26 @@ struct MoistCols {
 };
 hipError_t launch_moist_columns(const MoistCols &a, hipStream_t s);
 
+// Radiation of nb states of (ix, il, kx) grids (csrc/spdy_radiation.hip): physics.f90:146-163 (phase 0), :166 (phase 1) and
+// :180-186 (phase 2), one thread per column.  Per-level tables are top down: entry k belongs to the reference's level k + 1.  Output pointers may be
+// null.  The radiation state of a model state is rad_state_fields(kx) fields of ncol doubles: tau2 (4 kx, band-major),
+// stratc (2), tt_rsw (kx), flux (4), the longwave dfabs of the downward half (kx), slrd (1).
+constexpr int RAD_KMAX = 16;
+__host__ __device__ constexpr int rad_state_fields(int kx) { return 6 * kx + 7; }
+struct RadCols {
+    int nb, ncol, ix, il, kx, compute_sw;
+    const double *tg, *qg, *phig, *pslg;          // (ix, il, kx) / (ix, il) per state
+    const double *rh, *precnv, *precls;           // down, compute_sw only: (ix, il, kx), (ix, il), (ix, il)
+    const int *iptop;
+    const double *fmask, *albsfc;                 // (ix, il) per state
+    const double *ts, *fsfcu;                     // up: (ix, il) per state
+    const double *zonal;                          // [5][il]: fsol ozone ozupp zenit stratz (device, plan-owned)
+    double *state, *ttend;
+    double *cloudc, *clstr, *ssrd, *ssr, *tsr, *slrd, *slr, *olr, *tt_rsw, *tt_rlw;
+    int *icltop;
+    double dhs[RAD_KMAX], abs1[RAD_KMAX], wvi2[RAD_KMAX], grdscp[RAD_KMAX];
+    double eps1;                                  // epslw/(dhs(1) + dhs(2))
+};
+hipError_t launch_radiation(const RadCols &a, int phase, hipStream_t s);   // 0 shortwave, 1 longwave down, 2 up
+
 }  // namespace spdy

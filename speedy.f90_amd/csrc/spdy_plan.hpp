@@ -44,6 +44,7 @@ struct spdy_plan {
     double *tmp_c = nullptr, *tmp_d = nullptr;   // max_batch spectra each; allocated with `four` (multi-kernel operator sequences)
     double *out_grid = nullptr, *out_spec = nullptr;   // output path: (5kx+1) grids, (3kx+1) spectra (spdy_output_workspace)
     double *moist_grid = nullptr;     // moist physics from spectra: (3kx+1) grids t | q | phi | ln ps (spdy_moist_workspace)
+    double *d_radzonal = nullptr;     // [5][il] zonal radiation forcing fsol | ozone | ozupp | zenit | stratz (spdy_radiation_set_date)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
     double *d_dmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -89,6 +89,28 @@ void make_physics(HostTables &t)
     }
 }
 
+// longwave_radiation.f90:197-220 radset.  (0.148 - 3.0e-6*(jtemp - 247)**2) is default real: the integer square is converted
+// and the product and difference are float32 operations; the result is widened and multiplied by eps1 = 1.0 - epslw in double.
+// The kernels (csrc/spdy_radiation.hip, fband_row) evaluate the same expression in registers.
+void make_fband(HostTables &t)
+{
+    const double eps1 = 1.0 - static_cast<double>(0.05f);
+    t.fband.assign(4 * 301, 0.0);
+    auto at = [&](int jt, int jb) -> double & { return t.fband[(jt - 100) + 301 * (jb - 1)]; };
+    for (int jt = 200; jt <= 320; ++jt) {
+        const float d2 = static_cast<float>((jt - 247) * (jt - 247)), d3 = static_cast<float>((jt - 282) * (jt - 282));
+        const float d4 = static_cast<float>((jt - 315) * (jt - 315));
+        at(jt, 2) = static_cast<double>(0.148f - 3.0e-6f * d2) * eps1;
+        at(jt, 3) = static_cast<double>(0.356f - 5.2e-6f * d3) * eps1;
+        at(jt, 4) = static_cast<double>(0.314f + 1.0e-5f * d4) * eps1;
+        at(jt, 1) = eps1 - (at(jt, 2) + at(jt, 3) + at(jt, 4));
+    }
+    for (int jb = 1; jb <= 4; ++jb) {
+        for (int jt = 100; jt <= 199; ++jt) at(jt, jb) = at(200, jb);
+        for (int jt = 321; jt <= 400; ++jt) at(jt, jb) = at(320, jb);
+    }
+}
+
 // Everything that is a function of the half levels hsg alone:
 //   geometry.f90:51-60 (dhs, fsg, dhsr, fsgr), geopotential.f90:22-30 + :52-53 (xgeop1, xgeop2, corf),
 //   horizontal_diffusion.f90:70-82 (tcorv, qcorv)
@@ -411,6 +433,7 @@ std::string HostTables::build(int trunc_, int ix_, int iy_, int kx_)
     make_legendre(*this);
     make_spectral(*this);
     make_hdiff(*this);
+    make_fband(*this);
     dmp1.assign(mx * nx, 0.0); dmp1d.assign(mx * nx, 0.0); dmp1s.assign(mx * nx, 0.0);
     return "";
 }
@@ -499,6 +522,59 @@ std::string HostTables::build_implicit(double dt)
     return "";
 }
 
+// shortwave_radiation.f90:238-329.  Default-real subexpressions are float32 first: asin(1.0) is the float32 pi/2, 10.0/365.0
+// the float32 quotient; csol = 4.0*solc, the parameters solc, epssw and the literals in double expressions are float32 values
+// widened.  sia(j) = -sia_half(j), sia(il+1-j) = sia_half(j), coa likewise symmetric (geometry.f90:68-73).
+std::string HostTables::set_date(double ty)
+{
+    if (!(ty == ty)) return "tyear is not a number";
+    const double asin1 = static_cast<double>(std::asin(1.0f));       // float32 pi/2, widened
+    const double solc = static_cast<double>(342.0f), epssw = static_cast<double>(0.020f);
+    // get_zonal_average_fields
+    const double alpha = static_cast<double>(4.0f * std::asin(1.0f)) * (ty + static_cast<double>(10.0f / 365.0f));
+    const double dalpha = 0.0;
+    const double cz = std::cos(alpha - dalpha);
+    const double coz1 = 1.0 * (0.0 > cz ? 0.0 : cz);
+    const double coz2 = static_cast<double>(1.8f), azen = 1.0, fs0 = 6.0;
+    const double rzen = -(std::cos(alpha) * static_cast<double>(23.45f) * asin1 / 90.0);
+    // solar (Hartmann 1994)
+    const double pigr = 2.0 * asin1;
+    const double a = 2.0 * pigr * ty;
+    const double ca1 = std::cos(a), sa1 = std::sin(a);
+    const double ca2 = ca1 * ca1 - sa1 * sa1, sa2 = 2. * sa1 * ca1;
+    const double ca3 = ca1 * ca2 - sa1 * sa2, sa3 = sa1 * ca2 + sa2 * ca1;
+    auto F = [](float x) { return static_cast<double>(x); };
+    const double decl = F(0.006918f) - F(0.399912f) * ca1 + F(0.070257f) * sa1 - F(0.006758f) * ca2 + F(0.000907f) * sa2 -
+                        F(0.002697f) * ca3 + F(0.001480f) * sa3;
+    const double fdis = F(1.000110f) + F(0.034221f) * ca1 + F(0.001280f) * sa1 + F(0.000719f) * ca2 + F(0.000077f) * sa2;
+    const double cdecl = std::cos(decl), sdecl = std::sin(decl), tdecl = sdecl / cdecl;
+    const double csolp = 4.0 * solc / pigr;
+    fsol.assign(il, 0.0); ozone.assign(il, 0.0); ozupp.assign(il, 0.0); zenit.assign(il, 0.0); stratz.assign(il, 0.0);
+    const double crz = std::cos(rzen), srz = std::sin(rzen);
+    for (int j = 0; j < il; ++j) {
+        const int h = j < iy ? j : il - 1 - j;
+        const double sia = j < iy ? -sia_half[h] : sia_half[h], coa = coa_half[h];
+        double ch0 = -tdecl * sia / coa;
+        ch0 = -1.0 > ch0 ? -1.0 : ch0;
+        ch0 = 1.0 < ch0 ? 1.0 : ch0;
+        const double h0 = std::acos(ch0), sh0 = std::sin(h0);
+        const double topsr = csolp * fdis * (h0 * sia * sdecl + sh0 * coa * cdecl);
+        const double flat2 = 1.5 * (sia * sia) - 0.5;
+        fsol[j] = topsr;
+        const double ozu = 0.5 * epssw;
+        const double ozo = F(0.4f) * epssw * (1.0 + coz1 * sia + coz2 * flat2);
+        const double zb = 1.0 - (coa * crz + sia * srz);
+        zenit[j] = 1.0 + azen * (zb * zb);                               // **nzen, nzen = 2
+        ozupp[j] = fsol[j] * ozu * zenit[j];
+        ozone[j] = fsol[j] * ozo * zenit[j];
+        const double sz = fs0 - fsol[j];
+        stratz[j] = sz > 0.0 ? sz : 0.0;
+    }
+    tyear = ty;
+    date_ready = true;
+    return "";
+}
+
 const double *HostTables::lookup(const std::string &name, int *count, std::vector<double> &scratch) const
 {
     struct Ent { const char *n; const std::vector<double> *v; };
@@ -512,7 +588,11 @@ const double *HostTables::lookup(const std::string &name, int *count, std::vecto
         {"tref", &tref}, {"tref1", &tref1}, {"tref2", &tref2}, {"tref3", &tref3}, {"xc", &xc}, {"xd", &xd},
         {"xj", &xj}, {"dhsx", &dhsx}, {"elz", &elz}, {"xgeop1", &xgeop1}, {"xgeop2", &xgeop2}, {"corf", &corf},
         {"tcorv", &tcorv}, {"qcorv", &qcorv}, {"coriol", &coriol}, {"sigl", &sigl}, {"sigh", &sigh}, {"grdsig", &grdsig},
-        {"grdscp", &grdscp}, {"wvi", &wvi}, {"entr", &entr}};
+        {"grdscp", &grdscp}, {"wvi", &wvi}, {"entr", &entr}, {"fband", &fband},
+        {"fsol", &fsol}, {"ozone", &ozone}, {"ozupp", &ozupp}, {"zenit", &zenit}, {"stratz", &stratz}};
+    // the zonal radiation forcing before spdy_radiation_set_date: known, but empty
+    for (const char *z : {"fsol", "ozone", "ozupp", "zenit", "stratz"})
+        if (name == z && !date_ready) { *count = 0; scratch.assign(1, 0.0); return scratch.data(); }
     for (const auto &e : ents)
         if (name == e.n) { *count = static_cast<int>(e.v->size()); return e.v->data(); }
     if (name == "ifac") {

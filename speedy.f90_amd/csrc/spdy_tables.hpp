@@ -3,7 +3,8 @@
 // Reproduces, value for value, the tables the reference builds once at start-up:
 //   geometry.f90:35-89, fftpack.f90:1-67 (rffti1), legendre.f90:23-71,158-237,
 //   spectral.f90:20-82, horizontal_diffusion.f90:36-82, implicit.f90:36-165, physics.f90:12-39 and the level
-//   constants of convection.f90:55-71 and large_scale_condensation.f90:47-66.
+//   constants of convection.f90:55-71 and large_scale_condensation.f90:47-66; radset (longwave_radiation.f90:197-220)
+//   and, per date, get_zonal_average_fields + solar (shortwave_radiation.f90:238-329).
 // The reference is FP64 in storage only; unsuffixed literals and float() are float32 first
 // (SURVEY.md Appendix A).  Those sub-expressions are evaluated in float here too -- an
 // "improved" table (exact pi, true Gaussian nodes, double 1/ix) breaks parity at 1e-8.
@@ -46,6 +47,13 @@ struct HostTables {
     // and pfact = dhs*prg
     std::vector<double> sigl, sigh, grdsig, grdscp, wvi, entr, lsc_rhref, lsc_dqmax, lsc_pfact;
     double fm0 = 0.0;
+    // longwave_radiation.f90:197-220 radset: fband(100:400,4) column-major, entry (t - 100) + 301*(jb - 1)
+    std::vector<double> fband;
+    // shortwave_radiation.f90:238-329 get_zonal_average_fields + solar at the date set by set_date (valid when date_ready): one
+    // value per latitude [il] (the reference's (ix,il) fields are constant along i), j = 0 southernmost
+    std::vector<double> fsol, ozone, ozupp, zenit, stratz;
+    bool date_ready = false;
+    double tyear = 0.0;
 
     // Builds everything except the dt-dependent implicit tables.  Returns "" or an error text.
     std::string build(int trunc, int ix, int iy, int kx);
@@ -54,6 +62,8 @@ struct HostTables {
     std::string set_sigma(const double *hsg_in);
     // implicit.f90:36-165 (+ dmp1* of :50-56).  Returns "" or an error text.
     std::string build_implicit(double dt);
+    // The zonal radiation forcing of the date tyear (fraction of the year, 0 = 1 Jan 0h).  Returns "" or an error text.
+    std::string set_date(double tyear);
     // Named lookup for spdy_get_table; nullptr if unknown. *count receives the length.
     const double *lookup(const std::string &name, int *count, std::vector<double> &scratch) const;
 };

@@ -29,6 +29,19 @@ module spdy_c
         type(c_ptr) :: qsat = c_null_ptr, rh = c_null_ptr, se = c_null_ptr
     end type
 
+    !> spdy_rad_surface (include/spdy.h): per-column boundary fields of the radiation (land fraction, surface albedo)
+    type, bind(C) :: spdy_rad_surface
+        type(c_ptr) :: fmask = c_null_ptr, albsfc = c_null_ptr
+    end type
+
+    !> spdy_rad_out (include/spdy.h): optional outputs of the radiation (c_null_ptr = not written)
+    type, bind(C) :: spdy_rad_out
+        type(c_ptr) :: cloudc = c_null_ptr, clstr = c_null_ptr, icltop = c_null_ptr
+        type(c_ptr) :: ssrd = c_null_ptr, ssr = c_null_ptr, tsr = c_null_ptr
+        type(c_ptr) :: slrd = c_null_ptr, slr = c_null_ptr, olr = c_null_ptr
+        type(c_ptr) :: tt_rsw = c_null_ptr, tt_rlw = c_null_ptr
+    end type
+
     interface
         function spdy_plan_create(trunc, ix, iy, kx, max_batch, device, plan) bind(C, name="spdy_plan_create") result(rc)
             import :: c_int, c_ptr
@@ -658,6 +671,34 @@ module spdy_c
             import :: c_int, c_ptr, spdy_moist_out
             type(c_ptr), value :: plan, t, q, phi, ps, ttend, qtend
             type(spdy_moist_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_radiation_set_date(plan, tyear) bind(C, name="spdy_radiation_set_date") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: plan
+            real(c_double), value :: tyear
+            integer(c_int) :: rc
+        end function
+        function spdy_radiation_state_size(plan) bind(C, name="spdy_radiation_state_size") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int) :: rc
+        end function
+        function spdy_radiation_down_dev(plan, nb, compute_sw, tg, qg, phig, pslg, rh, precnv, precls, iptop, sfc, state, out) &
+                & bind(C, name="spdy_radiation_down_dev") result(rc)
+            import :: c_int, c_ptr, spdy_rad_surface, spdy_rad_out
+            type(c_ptr), value :: plan, tg, qg, phig, pslg, rh, precnv, precls, iptop, state
+            integer(c_int), value :: nb, compute_sw
+            type(spdy_rad_surface), intent(in) :: sfc
+            type(spdy_rad_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_radiation_up_dev(plan, nb, tg, pslg, ts, fsfcu, state, ttend, out) &
+                & bind(C, name="spdy_radiation_up_dev") result(rc)
+            import :: c_int, c_ptr, spdy_rad_out
+            type(c_ptr), value :: plan, tg, pslg, ts, fsfcu, state, ttend
+            integer(c_int), value :: nb
+            type(spdy_rad_out), intent(in) :: out
             integer(c_int) :: rc
         end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)

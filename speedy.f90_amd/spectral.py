@@ -35,6 +35,22 @@ MOIST_2D = ("precnv", "precls", "cbmf", "iptop", "icnv")   # (ix,il) per state; 
 MOIST_3D = ("qsat", "rh", "se")                             # (ix,il,kx) per state
 
 
+class RadSurface(ctypes.Structure):
+    """spdy_rad_surface (include/spdy.h): land fraction and surface albedo, device pointers."""
+    _fields_ = [("fmask", ctypes.c_void_p), ("albsfc", ctypes.c_void_p)]
+
+
+class RadOut(ctypes.Structure):
+    """spdy_rad_out (include/spdy.h): optional outputs of the radiation, device pointers or None."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("cloudc", "clstr", "icltop", "ssrd", "ssr", "tsr", "slrd", "slr", "olr",
+                                                "tt_rsw", "tt_rlw")]
+
+
+RAD_SW_2D = ("cloudc", "clstr", "icltop", "ssrd", "ssr", "tsr")   # (ix,il) per state, compute_sw calls; icltop int32
+RAD_2D = ("slrd", "slr", "olr")                                    # (ix,il) per state
+RAD_3D = ("tt_rsw", "tt_rlw")                                      # (ix,il,kx) per state
+
+
 class Graph:
     """A captured sequence of device-resident calls (spdy_graph_* in include/spdy.h)."""
 
@@ -539,6 +555,110 @@ class Spectral:
         self._sync_stream()
         o = self._moist_out(out)
         check(self.lib.spdy_moist_physics_dev(self.h, *[self._dp(x) for x in (t, q, phi, ps, ttend, qtend)], ctypes.byref(o)))
+
+    # ------------------------------------------------------------------ radiation (physics.f90:146-166, :180-186)
+    def radiation_set_date(self, tyear):
+        """Zonal radiation forcing of the date tyear (fraction of the year; get_zonal_average_fields + solar).  On a device plan
+        the upload is ordered on the plan's stream: a graph replayed after this call uses the new date."""
+        if self.device >= 0:
+            self._sync_stream()
+        check(self.lib.spdy_radiation_set_date(self.h, float(tyear)))
+
+    def radiation_state_size(self):
+        """Doubles of radiation state per model state (the caller's device buffer holds nb of them)."""
+        return check(self.lib.spdy_radiation_state_size(self.h))
+
+    @staticmethod
+    def _rad_out(out):
+        o = RadOut()
+        for name, t in (out or {}).items():
+            if name not in RAD_SW_2D + RAD_2D + RAD_3D:
+                raise ValueError("unknown radiation output %r" % name)
+            if t is not None:
+                setattr(o, name, t.data_ptr())
+        return o
+
+    def radiation_down_dev(self, compute_sw, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, state, out=None):
+        """Down half on nb gridded states: tg, qg, phig, rh [nb,kx,il,ix] (or [kx,il,ix]); pslg, precnv, precls, iptop (int32),
+        fmask, albsfc [nb,il,ix]; state [nb * radiation_state_size()] float64.  rh .. albsfc are read with compute_sw only and
+        may be None otherwise.  out: dict of optional device outputs (RAD_SW_2D, RAD_2D [nb,il,ix]; RAD_3D like tg)."""
+        self._sync_stream()
+        nb = tg.shape[0] if tg.dim() == 4 else 1
+        sfc = RadSurface(self._dp(fmask) if fmask is not None else None, self._dp(albsfc) if albsfc is not None else None)
+        ptr = lambda x: None if x is None else self._dp(x)
+        check(self.lib.spdy_radiation_down_dev(self.h, nb, 1 if compute_sw else 0, *[ptr(x) for x in (tg, qg, phig, pslg, rh, precnv,
+                                               precls, iptop)], ctypes.byref(sfc), self._dp(state), ctypes.byref(self._rad_out(out))))
+
+    def radiation_up_dev(self, tg, pslg, ts, fsfcu, state, ttend, out=None):
+        """Up half: ts, fsfcu (= slru(:,:,3)) [nb,il,ix]; ttend [nb,kx,il,ix] in place (+ tt_rsw + tt_rlw)."""
+        self._sync_stream()
+        nb = tg.shape[0] if tg.dim() == 4 else 1
+        check(self.lib.spdy_radiation_up_dev(self.h, nb, *[self._dp(x) for x in (tg, pslg, ts, fsfcu, state, ttend)],
+                                             ctypes.byref(self._rad_out(out))))
+
+    def radiation_columns(self, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, ts, fsfcu, ttend, compute_sw=True,
+                          state=None):
+        """NumPy convenience: both radiation halves on copies in plan-owned device memory.  Shapes as radiation_down_dev (NumPy).
+        state: the radiation state to start from (as returned under "state"); None starts a fresh one (then compute_sw must be
+        set).  Returns a dict with the updated ttend, every optional output (those of the shortwave only with compute_sw) and the
+        updated state."""
+        ins = {"tg": tg, "qg": qg, "phig": phig, "pslg": pslg, "ts": ts, "fsfcu": fsfcu, "ttend": ttend}
+        if compute_sw:
+            ins.update(rh=rh, precnv=precnv, precls=precls, fmask=fmask, albsfc=albsfc)
+        ins = {k: np.ascontiguousarray(v, np.float64) for k, v in ins.items()}
+        grid3 = ins["tg"].shape
+        if grid3[-3:] != (self.kx,) + self.grid_shape:
+            raise ValueError("tg must be [nb,] kx, il, ix")
+        lead = grid3[:-3]
+        nb = int(np.prod(lead)) if lead else 1
+        for k, v in ins.items():
+            want = grid3 if k in ("tg", "qg", "phig", "rh", "ttend") else lead + self.grid_shape
+            if v.shape != want:
+                raise ValueError("%s must have shape %s" % (k, want))
+        if compute_sw:
+            ins["iptop"] = np.ascontiguousarray(iptop, np.int32)
+            if ins["iptop"].shape != lead + self.grid_shape:
+                raise ValueError("iptop must be [nb,] il, ix")
+        nst = self.radiation_state_size() * nb
+        if state is None and not compute_sw:
+            raise ValueError("the first call on a radiation state must have compute_sw set")
+        st = np.zeros(nst) if state is None else np.ascontiguousarray(state, np.float64)
+        if st.shape != (nst,):
+            raise ValueError("state must hold %d doubles" % nst)
+        names = RAD_2D + ("tt_rlw",) + ((RAD_SW_2D + ("tt_rsw",)) if compute_sw else ())
+        res = {n: np.empty(grid3 if n in RAD_3D else lead + self.grid_shape, np.int32 if n == "icltop" else np.float64)
+               for n in names}
+        bufs = []
+        try:
+            def alloc(nbytes):
+                ptr = ctypes.c_void_p()
+                check(self.lib.spdy_dev_alloc(self.h, max(nbytes, 8), ctypes.byref(ptr)))
+                bufs.append(ptr)
+                return ptr
+            d = {}
+            for k, a in list(ins.items()) + [("state", st)]:
+                d[k] = alloc(a.nbytes)
+                check(self.lib.spdy_dev_upload(self.h, d[k], _p(a), a.nbytes))
+            o = RadOut()
+            d_out = {}
+            for n in names:
+                d_out[n] = alloc(res[n].nbytes)
+                setattr(o, n, d_out[n].value)
+            sfc = RadSurface(d["fmask"].value, d["albsfc"].value) if compute_sw else RadSurface()
+            g = lambda k: d.get(k)
+            check(self.lib.spdy_radiation_down_dev(self.h, nb, 1 if compute_sw else 0, g("tg"), g("qg"), g("phig"), g("pslg"),
+                                                   g("rh"), g("precnv"), g("precls"), g("iptop"), ctypes.byref(sfc), d["state"],
+                                                   ctypes.byref(o)))
+            check(self.lib.spdy_radiation_up_dev(self.h, nb, d["tg"], d["pslg"], d["ts"], d["fsfcu"], d["state"], d["ttend"],
+                                                 ctypes.byref(o)))
+            res["ttend"] = np.empty(grid3)
+            res["state"] = np.empty(nst)
+            for n, dp in (("ttend", d["ttend"]), ("state", d["state"])) + tuple(d_out.items()):
+                check(self.lib.spdy_dev_download(self.h, _p(res[n]), dp, res[n].nbytes))
+        finally:
+            for b in bufs:
+                self.lib.spdy_dev_free(self.h, b)
+        return res
 
     def moist_columns(self, tg, qg, phig, pslg, ttend, qtend):
         """NumPy convenience: spdy_moist_columns_dev on copies in plan-owned device memory.  Returns a dict with the updated
