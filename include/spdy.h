@@ -441,6 +441,11 @@ int spdy_output_workspace(spdy_plan *plan);
 int spdy_output_batch_dev(spdy_plan *plan, const double *vor, const double *div, const double *t, const double *q, const double *phi,
                           const double *ps, float *u_out, float *v_out, float *t_out, float *q_out, float *phi_out, float *ps_out);
 
+/* Column physics (spdy_moist_columns_dev, spdy_moist_physics_dev, spdy_radiation_down_dev, spdy_radiation_up_dev) checks its
+ * arguments in one order, and the first check that fails gives the code: a NULL plan, kx outside [5, 16] and nb outside
+ * [0, max_batch] SPDY_ERR_ARG; no sigma levels, then (radiation) no date, SPDY_ERR_STATE; a NULL required pointer SPDY_ERR_ARG;
+ * then the call's own conditions (spdy_moist_physics_dev: max_batch); a host-only plan SPDY_ERR_NO_DEVICE last.             */
+
 /* ---- column physics: the precipitation block of get_physical_tendencies (physics.f90:110-138) ----------------------------
  * Replaces, on the device, the thermodynamic fields (physics.f90:110-115: psg = exp(pslg), rps, qg = max(qg, 0), se = cp*tg +
  * phig), spec_hum_to_rel_hum per level (:117-119; humidity.f90:16-28, 46-79), deep convection (:126; convection.f90:26-235), the

@@ -341,84 +341,4 @@ int spdy_output_batch_dev(spdy_plan *p, const double *vor, const double *div, co
     return SPDY_OK;
 }
 
-/* ---------------------------------------------------------------- moist physics (physics.f90:110-138) */
-namespace {
-// argument checks that need no device (a host-only plan answers them)
-int moist_args(const spdy_plan *p, int nb, bool ok_ptrs)
-{
-    NEED_PLAN(p);
-    const int kx = p->tab.kx;
-    if (kx < 5 || kx > spdy::MOIST_KMAX) return fail(SPDY_ERR_ARG, "moist physics: kx=%d outside [5, %d]", kx, (int)spdy::MOIST_KMAX);
-    RC(check_batch(p, nb));
-    if (!ok_ptrs) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (!p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "moist physics needs sigma levels (kx in {5,7,8} or spdy_plan_set_sigma)");
-    return SPDY_OK;
-}
-
-// the kernel's view of the plan's physics tables: bottom up, entry r = level kx - r
-spdy::MoistCols moist_cols(const spdy_plan *p, int nb, const double *tg, const double *qg, const double *phig, const double *pslg,
-                           double *ttend, double *qtend, const spdy_moist_out *out)
-{
-    const HostTables &t = p->tab;
-    const int kx = t.kx;
-    spdy::MoistCols a{};
-    a.nb = nb; a.ncol = t.ix * t.il; a.kx = kx;
-    a.tg = tg; a.qg = qg; a.phig = phig; a.pslg = pslg; a.ttend = ttend; a.qtend = qtend;
-    if (out) {
-        a.precnv = out->precnv; a.precls = out->precls; a.cbmf = out->cbmf; a.iptop = out->iptop; a.icnv = out->icnv;
-        a.qsat = out->qsat; a.rh = out->rh; a.se = out->se;
-    }
-    for (int r = 0; r < kx; ++r) {
-        const int k = kx - 1 - r;                     // 0-based level index
-        a.fsg[r] = t.fsg[k];
-        a.wvi2[r] = t.wvi[kx + k];
-        a.entr[r] = k >= 1 && k <= kx - 2 ? t.entr[k - 1] : 0.0;
-        a.grdsig[r] = t.grdsig[k];
-        a.grdscp[r] = t.grdscp[k];
-        a.rhref[r] = t.lsc_rhref[k];
-        a.dqmax[r] = t.lsc_dqmax[k];
-        a.pfact[r] = t.lsc_pfact[k];
-    }
-    a.fm0 = t.fm0;
-    return a;
-}
-}  // namespace
-
-int spdy_moist_columns_dev(spdy_plan *p, int nb, const double *tg, const double *qg, const double *phig, const double *pslg,
-                           double *ttend, double *qtend, const spdy_moist_out *out)
-{
-    RC(moist_args(p, nb, !nb || (tg && qg && phig && pslg && ttend && qtend)));
-    NEED_DEVICE(p);
-    KERNEL(spdy::launch_moist_columns(moist_cols(p, nb, tg, qg, phig, pslg, ttend, qtend, out), p->stream));
-    return SPDY_OK;
-}
-
-int spdy_moist_workspace(spdy_plan *p)
-{
-    NEED_DEVICE(p);
-    if (p->moist_grid) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the moist-physics workspace (call spdy_moist_workspace before the capture)");
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(3 * p->tab.kx + 1) * grid_elems(p) * sizeof(double), &ptr));
-    p->moist_grid = static_cast<double *>(ptr);
-    return SPDY_OK;
-}
-
-int spdy_moist_physics_dev(spdy_plan *p, const double *t, const double *q, const double *phi, const double *ps, double *ttend,
-                           double *qtend, const spdy_moist_out *out)
-{
-    RC(moist_args(p, 1, t && q && phi && ps && ttend && qtend));
-    const int kx = p->tab.kx;
-    if (p->max_batch < 3 * kx + 1) return fail(SPDY_ERR_ARG, "max_batch must be >= 3*kx+1 for the moist physics from spectra");
-    NEED_DEVICE(p);
-    RC(spdy_moist_workspace(p));
-    // physics.f90:102-107 for the fields the block reads: ONE inverse launch of t, q, phi (kx levels each) and ps, kcos 1
-    const spdy_spec_seg segs[4] = {{kx, t}, {kx, q}, {kx, phi}, {1, ps}};
-    RC(inverse_plain_one(p, 4, segs, p->moist_grid));
-    const size_t L = (size_t)kx * grid_elems(p);
-    const double *g = p->moist_grid;
-    KERNEL(spdy::launch_moist_columns(moist_cols(p, 1, g, g + L, g + 2 * L, g + 3 * L, ttend, qtend, out), p->stream));
-    return SPDY_OK;
-}
-
 }  // extern "C"

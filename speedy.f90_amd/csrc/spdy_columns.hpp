@@ -1,0 +1,49 @@
+// Launch and addressing layer of the column-physics kernels (csrc/spdy_physics.hip, csrc/spdy_radiation.hip).
+//
+// One thread per (state, column): nb * ncol threads in blocks of COLUMN_BLOCK, threads with consecutive longitude in
+// consecutive lanes, so every level load and store is one coalesced access per wave.  Each kernel comes as <8> and <16>:
+// KMAX is the number of levels its loops are unrolled over (with runtime level < kx predicates), 8 for kx <= 8, else 16.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "spdy_kernels.hpp"
+
+namespace spdy {
+
+constexpr int COLUMN_BLOCK = 64;
+
+// default-real literals and parameters of the reference are float32 values widened to double
+__host__ __device__ constexpr double F(float x) { return static_cast<double>(x); }
+
+// physical_constants.f90:22
+__device__ constexpr double kCp = F(1004.0f);
+
+// This thread's place in the launch: gid = b * ncol + col for state b and column col.  The threads past the last column of the
+// last state (gid >= nb * ncol) return at once.
+__device__ inline long column_gid() { return (long)blockIdx.x * COLUMN_BLOCK + threadIdx.x; }
+
+// This thread's column: level l (0-based, in the grid's memory order) of a (ix, il, kx) grid of the state at base + l * ncol, a
+// (ix, il) field at gid.
+struct Column {
+    long gid, b, col, base;
+    __device__ Column(long g, int ncol, int kx) : gid(g)
+    {
+        b = g / ncol;
+        col = g - b * ncol;
+        base = b * ncol * kx + col;
+    }
+};
+
+// The launch of a column kernel whose arguments `a` have nb, ncol and kx: k8 for kx <= 8, k16 for kx <= COLUMN_KMAX.
+template <class Args>
+hipError_t launch_columns(void (*k8)(Args), void (*k16)(Args), const Args &a, hipStream_t s)
+{
+    if (a.kx < 5 || a.kx > COLUMN_KMAX || a.nb < 0 || a.ncol <= 0) return hipErrorInvalidValue;
+    const long n = (long)a.nb * a.ncol;
+    if (!n) return hipSuccess;
+    const dim3 grd((unsigned)((n + COLUMN_BLOCK - 1) / COLUMN_BLOCK)), blk(COLUMN_BLOCK);
+    hipLaunchKernelGGL(a.kx <= 8 ? k8 : k16, grd, blk, 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace spdy

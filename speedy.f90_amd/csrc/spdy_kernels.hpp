@@ -272,9 +272,12 @@ hipError_t launch_output_cast(const DevPlan &p, const OutputCast &c, hipStream_t
 hipError_t prepare_device_kernels();
 hipError_t prepare_device_step_kernels(int kx);
 
-// Moist physics of nb states of (ix, il, kx) grids (csrc/spdy_physics.hip): physics.f90:110-138, one thread per column.
-// Per-level tables are bottom up: entry r belongs to the reference's level k = kx - r.  Output pointers may be null.
-constexpr int MOIST_KMAX = 16;
+// Column physics of nb states of (ix, il, kx) grids, one thread per column, 5 <= kx <= COLUMN_KMAX: the launch and addressing
+// layer the schemes share is csrc/spdy_columns.hpp, their C ABI csrc/spdy_api_physics.hip.
+constexpr int COLUMN_KMAX = 16;
+
+// Moist physics (csrc/spdy_physics.hip): physics.f90:110-138.  Per-level tables are bottom up: entry r belongs to the
+// reference's level k = kx - r.  Output pointers may be null.
 struct MoistCols {
     int nb, ncol, kx;
     const double *tg, *qg, *phig, *pslg;
@@ -282,17 +285,16 @@ struct MoistCols {
     double *precnv, *precls, *cbmf;               // (ix, il) per state
     int *iptop, *icnv;                            // (ix, il) per state
     double *qsat, *rh, *se;                       // (ix, il, kx) per state
-    double fsg[MOIST_KMAX], wvi2[MOIST_KMAX], entr[MOIST_KMAX], grdsig[MOIST_KMAX], grdscp[MOIST_KMAX];
-    double rhref[MOIST_KMAX], dqmax[MOIST_KMAX], pfact[MOIST_KMAX];
+    double fsg[COLUMN_KMAX], wvi2[COLUMN_KMAX], entr[COLUMN_KMAX], grdsig[COLUMN_KMAX], grdscp[COLUMN_KMAX];
+    double rhref[COLUMN_KMAX], dqmax[COLUMN_KMAX], pfact[COLUMN_KMAX];
     double fm0;
 };
 hipError_t launch_moist_columns(const MoistCols &a, hipStream_t s);
 
-// Radiation of nb states of (ix, il, kx) grids (csrc/spdy_radiation.hip): physics.f90:146-163 (phase 0), :166 (phase 1) and
-// :180-186 (phase 2), one thread per column.  Per-level tables are top down: entry k belongs to the reference's level k + 1.  Output pointers may be
-// null.  The radiation state of a model state is rad_state_fields(kx) fields of ncol doubles: tau2 (4 kx, band-major),
-// stratc (2), tt_rsw (kx), flux (4), the longwave dfabs of the downward half (kx), slrd (1).
-constexpr int RAD_KMAX = 16;
+// Radiation (csrc/spdy_radiation.hip): physics.f90:146-163 (phase 0), :166 (phase 1) and :180-186 (phase 2).  Per-level
+// tables are top down: entry k belongs to the reference's level k + 1.  Output pointers may be null.  The radiation state of a
+// model state is rad_state_fields(kx) fields of ncol doubles: tau2 (4 kx, band-major), stratc (2), tt_rsw (kx), flux (4), the
+// longwave dfabs of the downward half (kx), slrd (1).
 __host__ __device__ constexpr int rad_state_fields(int kx) { return 6 * kx + 7; }
 struct RadCols {
     int nb, ncol, ix, il, kx, compute_sw;
@@ -305,7 +307,7 @@ struct RadCols {
     double *state, *ttend;
     double *cloudc, *clstr, *ssrd, *ssr, *tsr, *slrd, *slr, *olr, *tt_rsw, *tt_rlw;
     int *icltop;
-    double dhs[RAD_KMAX], abs1[RAD_KMAX], wvi2[RAD_KMAX], grdscp[RAD_KMAX];
+    double dhs[COLUMN_KMAX], abs1[COLUMN_KMAX], wvi2[COLUMN_KMAX], grdscp[COLUMN_KMAX];
     double eps1;                                  // epslw/(dhs(1) + dhs(2))
 };
 hipError_t launch_radiation(const RadCols &a, int phase, hipStream_t s);   // 0 shortwave, 1 longwave down, 2 up

@@ -2,39 +2,38 @@
 // fields, spec_hum_to_rel_hum (humidity.f90:16-28, get_qsat :46-79), deep convection (convection.f90:26-235) with the
 // scaling of its fluxes, and large-scale condensation (large_scale_condensation.f90:32-83).
 //
-// One thread per (state, column).  Threads with consecutive longitude are consecutive lanes, so every level load and store
-// is one coalesced 512-byte access per wave.  The reference addresses the convection scheme from the surface up (kx, kx-1,
-// kx-3 .. 3, itop .. kx-1), so the column is held in registers BOTTOM UP: r = kx - k for the reference's level k (r = 0 is the
-// lowest level).  With the level count a runtime value every index the scheme uses is then a compile-time r, the loops are
+// Layout and launch as every column kernel (csrc/spdy_columns.hpp).  The reference addresses the convection scheme from the
+// surface up (kx, kx-1, kx-3 .. 3, itop .. kx-1), so the column is held in registers BOTTOM UP: r = kx - k for the reference's
+// level k (r = 0 is the lowest level).  With the level count a runtime value every index the scheme uses is then a compile-time r, the loops are
 // unrolled over KMAX with r < kx predicates, and no per-thread array is ever indexed at run time (which would put it in
 // scratch).  The per-level tables come in the kernel arguments in the same bottom-up order.
 #include <hip/hip_runtime.h>
 
-#include "spdy_kernels.hpp"
+#include "spdy_columns.hpp"
 
 namespace spdy {
 namespace {
 
 template <int KMAX>
-__global__ __launch_bounds__(64) void moist_columns_kernel(const MoistCols a)
+__global__ __launch_bounds__(COLUMN_BLOCK) void moist_columns_kernel(const MoistCols a)
 {
     // the threshold decisions (psa > psmin, mss0 > mss2, dqa < 0, ...) must see the reference's roundings: no contraction
 #pragma clang fp contract(off)
-    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const long gid = column_gid();
     if (gid >= (long)a.nb * a.ncol) return;
     const int kx = a.kx, ncol = a.ncol;
-    const long b = gid / ncol, col = gid - b * ncol;
-    const long base = b * ncol * kx + col;          // level k (1-based) of this column at base + (k - 1) * ncol
+    const Column c(gid, ncol, kx);
+    const long base = c.base;          // level k (1-based) of this column at base + (k - 1) * ncol
     auto at = [&](int r) { return base + (long)(kx - 1 - r) * ncol; };
 
     // physical_constants.f90:22-26, humidity.f90:61-66, convection.f90:15-20, :46-49, large_scale_condensation.f90:24, :50-52;
-    // default-real literals are float32 values widened to double, e0 is a double literal
-    const double cp = (double)1004.0f, alhc = (double)2501.0f;
-    const double e0 = 6.108e-3, c1 = (double)17.269f, c2 = (double)21.875f;
-    const double t0 = (double)273.16f, t1 = (double)35.86f, t2 = (double)7.66f;
-    const double psmin = (double)0.8f, rhbl = (double)0.9f, rhil = (double)0.7f, smf = (double)0.8f, fqmax = 5.0;
+    // e0 is a double literal
+    const double cp = kCp, alhc = F(2501.0f);
+    const double e0 = 6.108e-3, c1 = F(17.269f), c2 = F(21.875f);
+    const double t0 = F(273.16f), t1 = F(35.86f), t2 = F(7.66f);
+    const double psmin = F(0.8f), rhbl = F(0.9f), rhil = F(0.7f), smf = F(0.8f), fqmax = 5.0;
     const double rdps = 2.0 / (1.0 - psmin), rlhc = 1.0 / alhc;
-    const double rtlsc = 1.0 / ((double)4.0f * 3600.0), tfact = alhc / cp;
+    const double rtlsc = 1.0 / (F(4.0f) * 3600.0), tfact = alhc / cp;
 
     // physics.f90:110-120: psg, rps, the clamp of qg, se; then qsat and rh level by level
     const double psa = exp(a.pslg[gid]);
@@ -182,13 +181,7 @@ __global__ __launch_bounds__(64) void moist_columns_kernel(const MoistCols a)
 
 hipError_t launch_moist_columns(const MoistCols &a, hipStream_t s)
 {
-    if (a.kx < 5 || a.kx > 16 || a.nb < 0 || a.ncol <= 0) return hipErrorInvalidValue;
-    const long n = (long)a.nb * a.ncol;
-    if (!n) return hipSuccess;
-    const dim3 grd((unsigned)((n + 63) / 64)), blk(64);
-    if (a.kx <= 8) hipLaunchKernelGGL(moist_columns_kernel<8>, grd, blk, 0, s, a);
-    else hipLaunchKernelGGL(moist_columns_kernel<16>, grd, blk, 0, s, a);
-    return hipGetLastError();
+    return launch_columns(moist_columns_kernel<8>, moist_columns_kernel<16>, a, s);
 }
 
 }  // namespace spdy

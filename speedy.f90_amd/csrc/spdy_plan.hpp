@@ -1,5 +1,6 @@
 // Internal: the plan object behind include/spdy.h and the helpers shared by the C-ABI translation units
-// (spdy_api.hip: plan, transforms, operators, graphs; spdy_api_step.hip: time-step tail, collectives, output).
+// (spdy_api.hip: plan, transforms, operators, graphs; spdy_api_step.hip: time-step tail, output; spdy_api_shard.hip:
+// collectives; spdy_api_physics.hip: column physics).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,7 +62,7 @@ struct spdy_plan {
     struct Span { int kind; hipEvent_t t0, t1; };
     std::vector<Span> spans;
     std::vector<spdy_graph *> graphs; // graphs captured from this plan that are still alive
-    std::vector<struct spdy_comm *> comms;   // communicators created on this plan that are still alive (spdy_api_step.hip)
+    std::vector<struct spdy_comm *> comms;   // communicators created on this plan that are still alive (spdy_api_shard.hip)
 };
 
 namespace spdy_detail {

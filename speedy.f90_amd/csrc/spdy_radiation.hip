@@ -9,23 +9,19 @@
 // the reference keeps in module state between them and across steps (tau2, stratc, flux; the shortwave heating of the last
 // shortwave step) is the caller's radiation state: rad_state_fields(kx) fields of ncol doubles per model state.
 //
-// Layout as in csrc/spdy_physics.hip: one thread per (state, column), consecutive longitudes in consecutive lanes, so every
-// level access is one coalesced access per wave.  Levels are indexed TOP DOWN here, k = 0 .. kx-1 for the reference's level
-// k + 1 (both schemes sweep from the top first); loops are unrolled over KMAX with k < kx predicates, so no per-thread array
-// is indexed at run time.  What the reference reads at a level that depends on kx (nl1 = kx - 1, kx) is loaded from memory
-// at that runtime address instead.  No contraction, and the reference's association order throughout.
+// Layout and launch as every column kernel (csrc/spdy_columns.hpp).  Levels are indexed TOP DOWN here, k = 0 .. kx-1 for the
+// reference's level k + 1 (both schemes sweep from the top first); loops are unrolled over KMAX with k < kx predicates, so no
+// per-thread array is indexed at run time.  What the reference reads at a level that depends on kx (nl1 = kx - 1, kx) is loaded
+// from memory at that runtime address instead.  No contraction, and the reference's association order throughout.
 #include <hip/hip_runtime.h>
 
-#include "spdy_kernels.hpp"
+#include "spdy_columns.hpp"
 
 namespace spdy {
 namespace {
 
-// default-real literals and parameters of the reference are float32 values widened to double
-__host__ __device__ constexpr double F(float x) { return static_cast<double>(x); }
-
-// physical_constants.f90:22,29; mod_radcon.f90:26-27; shortwave_radiation.f90:14-54
-__device__ constexpr double kCp = F(1004.0f), kSbc = F(5.67e-8f), kEpslw = F(0.05f), kEmisfc = F(0.98f);
+// physical_constants.f90:29; mod_radcon.f90:26-27; shortwave_radiation.f90:14-54
+__device__ constexpr double kSbc = F(5.67e-8f), kEpslw = F(0.05f), kEmisfc = F(0.98f);
 
 // fband(nint(ta), 1:4) (longwave_radiation.f90:197-220), evaluated in registers bit-equal to the plan's table (spdy_tables.cpp
 // make_fband).  Fortran nint rounds half away from zero: round().  The index is clamped to the table's range [100, 400]; rows
@@ -83,35 +79,27 @@ __device__ inline void blackbody(const double (&ta)[KMAX], int kx, const double 
     }
 }
 
-// Per-thread addressing shared by the kernels: level k (0-based, top down) of a grid at base + k * ncol, radiation state field
-// f at st + f * ncol.  State fields: tau2 (k, jb) at jb * kx + k, stratc at 4 kx, tt_rsw at 4 kx + 2, flux at 5 kx + 2, the
-// longwave dfabs at 5 kx + 6, slrd at 6 kx + 6 (rad_state_fields(kx) = 6 kx + 7).
-struct Col {
-    long gid, base;
-    double *st;
-    int j;
-    __device__ Col(const RadCols &a, long g)
-    {
-        gid = g;
-        const long b = g / a.ncol, col = g - b * a.ncol;
-        base = b * a.ncol * a.kx + col;
-        st = a.state + b * a.ncol * rad_state_fields(a.kx) + col;
-        j = (int)(col / a.ix);
-    }
-};
+// The radiation state of this column: field f at st + f * ncol.  State fields: tau2 (k, jb) at jb * kx + k, stratc at 4 kx,
+// tt_rsw at 4 kx + 2, flux at 5 kx + 2, the longwave dfabs at 5 kx + 6, slrd at 6 kx + 6 (rad_state_fields(kx) = 6 kx + 7).
+__device__ inline double *column_state(const RadCols &a, const Column &c)
+{
+    return a.state + c.b * a.ncol * rad_state_fields(a.kx) + c.col;
+}
 
 // physics.f90:147-162 and shortwave_radiation.f90:74-234, :332-410 (compute_sw calls only): gse, clouds, the shortwave
 // fluxes and heating, and the longwave transmissivities and stratospheric terms the longwave halves read from the state.
 template <int KMAX>
-__global__ __launch_bounds__(64) void radiation_sw_kernel(const RadCols a)
+__global__ __launch_bounds__(COLUMN_BLOCK) void radiation_sw_kernel(const RadCols a)
 {
 #pragma clang fp contract(off)
-    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const long gid = column_gid();
     if (gid >= (long)a.nb * a.ncol) return;
     const int kx = a.kx, ncol = a.ncol;
-    const Col c(a, gid);
+    const Column c(gid, ncol, kx);
     const long base = c.base;
-    auto S = [&](int f) -> double & { return c.st[(long)f * ncol]; };
+    double *const st = column_state(a, c);
+    const int j = (int)(c.col / a.ix);                                // latitude row
+    auto S = [&](int f) -> double & { return st[(long)f * ncol]; };
     const int f_tau = 0, f_stratc = 4 * kx, f_ttrsw = 4 * kx + 2;
     auto qa_at = [&](long o) { const double q = a.qg[o]; return q > 0.0 ? q : 0.0; };   // qg = max(qg, 0.0), local
 
@@ -162,7 +150,7 @@ __global__ __launch_bounds__(64) void radiation_sw_kernel(const RadCols a)
     const double absdry = F(0.033f), abswv1 = F(0.022f), abswv2 = F(15.000f);
     const double fband2 = F(0.05f), fband1 = 1.0 - fband2;
     const double *z = a.zonal;
-    const int il = a.il, j = c.j;
+    const int il = a.il;
     const double fsol = z[j], ozone = z[il + j], ozupp = z[2 * il + j], zenit = z[3 * il + j], stratz = z[4 * il + j];
     // 1. tau2(:,:,:,3): albcl*cloudc at icltop (<= kx), then albcls*clstr at kx.  Only icltop and kx hold a value: t3cl, t3kx.
     // (icltop = 2 is never scaled by the flux in 3.3 but still enters 4.2 -- the reference's order, kept.)
@@ -275,14 +263,15 @@ __global__ __launch_bounds__(64) void radiation_sw_kernel(const RadCols a)
 // get_downward_longwave_rad_fluxes (longwave_radiation.f90:16-117), level by level from the top, with the transmissivities of
 // the state (made by the last radiation_sw_kernel on it)
 template <int KMAX>
-__global__ __launch_bounds__(64) void radiation_lwdown_kernel(const RadCols a)
+__global__ __launch_bounds__(COLUMN_BLOCK) void radiation_lwdown_kernel(const RadCols a)
 {
 #pragma clang fp contract(off)
-    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const long gid = column_gid();
     if (gid >= (long)a.nb * a.ncol) return;
     const int kx = a.kx, ncol = a.ncol;
-    const Col c(a, gid);
-    auto S = [&](int f) -> double & { return c.st[(long)f * ncol]; };
+    const Column c(gid, ncol, kx);
+    double *const st = column_state(a, c);
+    auto S = [&](int f) -> double & { return st[(long)f * ncol]; };
     const int f_tau = 0, f_flux = 5 * kx + 2, f_dfabs = 5 * kx + 6, f_slrd = 6 * kx + 6;
 
     double ta[KMAX];
@@ -334,15 +323,16 @@ __global__ __launch_bounds__(64) void radiation_lwdown_kernel(const RadCols a)
 }
 
 template <int KMAX>
-__global__ __launch_bounds__(64) void radiation_up_kernel(const RadCols a)
+__global__ __launch_bounds__(COLUMN_BLOCK) void radiation_up_kernel(const RadCols a)
 {
 #pragma clang fp contract(off)
-    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const long gid = column_gid();
     if (gid >= (long)a.nb * a.ncol) return;
     const int kx = a.kx, ncol = a.ncol;
-    const Col c(a, gid);
+    const Column c(gid, ncol, kx);
     const long base = c.base;
-    auto S = [&](int f) { return c.st[(long)f * ncol]; };
+    double *const st = column_state(a, c);
+    auto S = [&](int f) { return st[(long)f * ncol]; };
     const int f_tau = 0, f_stratc = 4 * kx, f_ttrsw = 4 * kx + 2, f_flux = 5 * kx + 2, f_dfabs = 5 * kx + 6, f_slrd = 6 * kx + 6;
 
     const double psa = exp(a.pslg[gid]);
@@ -405,16 +395,11 @@ __global__ __launch_bounds__(64) void radiation_up_kernel(const RadCols a)
 
 hipError_t launch_radiation(const RadCols &a, int phase, hipStream_t s)
 {
-    if (a.kx < 5 || a.kx > RAD_KMAX || a.nb < 0 || a.ncol <= 0 || a.ix <= 0 || a.il <= 0 || phase < 0 || phase > 2)
-        return hipErrorInvalidValue;
-    const long n = (long)a.nb * a.ncol;
-    if (!n) return hipSuccess;
-    const dim3 grd((unsigned)((n + 63) / 64)), blk(64);
-    const bool k8 = a.kx <= 8;
-    if (phase == 0) hipLaunchKernelGGL(k8 ? radiation_sw_kernel<8> : radiation_sw_kernel<16>, grd, blk, 0, s, a);
-    else if (phase == 1) hipLaunchKernelGGL(k8 ? radiation_lwdown_kernel<8> : radiation_lwdown_kernel<16>, grd, blk, 0, s, a);
-    else hipLaunchKernelGGL(k8 ? radiation_up_kernel<8> : radiation_up_kernel<16>, grd, blk, 0, s, a);
-    return hipGetLastError();
+    if (a.ix <= 0 || a.il <= 0) return hipErrorInvalidValue;
+    if (phase == 0) return launch_columns(radiation_sw_kernel<8>, radiation_sw_kernel<16>, a, s);
+    if (phase == 1) return launch_columns(radiation_lwdown_kernel<8>, radiation_lwdown_kernel<16>, a, s);
+    if (phase == 2) return launch_columns(radiation_up_kernel<8>, radiation_up_kernel<16>, a, s);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace spdy

@@ -25,6 +25,23 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _out_struct(cls, out):
+    """An optional-output struct (MoistOut, RadOut) holding the device pointers of the dict `out` (name -> tensor or None)."""
+    o = cls()
+    fields = [f[0] for f in cls._fields_]
+    for name, t in (out or {}).items():
+        if name not in fields:
+            raise ValueError("unknown %s field %r" % (cls.__name__, name))
+        if t is not None:
+            setattr(o, name, t.data_ptr())
+    return o
+
+
+def _nb(tg):
+    """states in a device level stack: [nb, kx, il, ix] or one [kx, il, ix]"""
+    return tg.shape[0] if tg.dim() == 4 else 1
+
+
 class MoistOut(ctypes.Structure):
     """spdy_moist_out (include/spdy.h): optional outputs of the moist physics, device pointers or None."""
     _fields_ = [("precnv", ctypes.c_void_p), ("precls", ctypes.c_void_p), ("cbmf", ctypes.c_void_p), ("iptop", ctypes.c_void_p),
@@ -528,23 +545,12 @@ class Spectral:
         check(self.lib.spdy_hdiff_dev(self.h, field.shape[0], self._dp(field), self._dp(fdt_in), a, b, self._dp(out)))
 
     # ------------------------------------------------------------------ moist physics (physics.f90:110-138)
-    @staticmethod
-    def _moist_out(out):
-        o = MoistOut()
-        for name, t in (out or {}).items():
-            if name not in MOIST_2D + MOIST_3D:
-                raise ValueError("unknown moist output %r" % name)
-            if t is not None:
-                setattr(o, name, t.data_ptr())
-        return o
-
     def moist_columns_dev(self, tg, qg, phig, pslg, ttend, qtend, out=None):
         """Precipitation block on nb gridded states: tg, qg, phig, ttend, qtend [nb,kx,il,ix] (or [kx,il,ix]), pslg [nb,il,ix];
         ttend / qtend in place.  out: dict of optional device outputs (MOIST_2D [nb,il,ix], iptop/icnv int32; MOIST_3D like tg)."""
         self._sync_stream()
-        nb = tg.shape[0] if tg.dim() == 4 else 1
-        o = self._moist_out(out)
-        check(self.lib.spdy_moist_columns_dev(self.h, nb, *[self._dp(x) for x in (tg, qg, phig, pslg, ttend, qtend)], ctypes.byref(o)))
+        o = _out_struct(MoistOut, out)
+        check(self.lib.spdy_moist_columns_dev(self.h, _nb(tg), *[self._dp(x) for x in (tg, qg, phig, pslg, ttend, qtend)], ctypes.byref(o)))
 
     def moist_workspace(self):
         check(self.lib.spdy_moist_workspace(self.h))
@@ -553,7 +559,7 @@ class Spectral:
         """The same from one state's spectra (time level 1: t, q [kx,nx,mx], phi [kx,nx,mx], ps [nx,mx] complex128): one inverse
         launch into plan workspace, then the column kernel.  ttend / qtend [kx,il,ix] in place."""
         self._sync_stream()
-        o = self._moist_out(out)
+        o = _out_struct(MoistOut, out)
         check(self.lib.spdy_moist_physics_dev(self.h, *[self._dp(x) for x in (t, q, phi, ps, ttend, qtend)], ctypes.byref(o)))
 
     # ------------------------------------------------------------------ radiation (physics.f90:146-166, :180-186)
@@ -568,33 +574,22 @@ class Spectral:
         """Doubles of radiation state per model state (the caller's device buffer holds nb of them)."""
         return check(self.lib.spdy_radiation_state_size(self.h))
 
-    @staticmethod
-    def _rad_out(out):
-        o = RadOut()
-        for name, t in (out or {}).items():
-            if name not in RAD_SW_2D + RAD_2D + RAD_3D:
-                raise ValueError("unknown radiation output %r" % name)
-            if t is not None:
-                setattr(o, name, t.data_ptr())
-        return o
-
     def radiation_down_dev(self, compute_sw, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, state, out=None):
         """Down half on nb gridded states: tg, qg, phig, rh [nb,kx,il,ix] (or [kx,il,ix]); pslg, precnv, precls, iptop (int32),
         fmask, albsfc [nb,il,ix]; state [nb * radiation_state_size()] float64.  rh .. albsfc are read with compute_sw only and
         may be None otherwise.  out: dict of optional device outputs (RAD_SW_2D, RAD_2D [nb,il,ix]; RAD_3D like tg)."""
         self._sync_stream()
-        nb = tg.shape[0] if tg.dim() == 4 else 1
         sfc = RadSurface(self._dp(fmask) if fmask is not None else None, self._dp(albsfc) if albsfc is not None else None)
         ptr = lambda x: None if x is None else self._dp(x)
-        check(self.lib.spdy_radiation_down_dev(self.h, nb, 1 if compute_sw else 0, *[ptr(x) for x in (tg, qg, phig, pslg, rh, precnv,
-                                               precls, iptop)], ctypes.byref(sfc), self._dp(state), ctypes.byref(self._rad_out(out))))
+        check(self.lib.spdy_radiation_down_dev(self.h, _nb(tg), 1 if compute_sw else 0, *[ptr(x) for x in (tg, qg, phig, pslg, rh,
+                                               precnv, precls, iptop)], ctypes.byref(sfc), self._dp(state),
+                                               ctypes.byref(_out_struct(RadOut, out))))
 
     def radiation_up_dev(self, tg, pslg, ts, fsfcu, state, ttend, out=None):
         """Up half: ts, fsfcu (= slru(:,:,3)) [nb,il,ix]; ttend [nb,kx,il,ix] in place (+ tt_rsw + tt_rlw)."""
         self._sync_stream()
-        nb = tg.shape[0] if tg.dim() == 4 else 1
-        check(self.lib.spdy_radiation_up_dev(self.h, nb, *[self._dp(x) for x in (tg, pslg, ts, fsfcu, state, ttend)],
-                                             ctypes.byref(self._rad_out(out))))
+        check(self.lib.spdy_radiation_up_dev(self.h, _nb(tg), *[self._dp(x) for x in (tg, pslg, ts, fsfcu, state, ttend)],
+                                             ctypes.byref(_out_struct(RadOut, out))))
 
     def radiation_columns(self, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, ts, fsfcu, ttend, compute_sw=True,
                           state=None):
@@ -628,22 +623,11 @@ class Spectral:
         names = RAD_2D + ("tt_rlw",) + ((RAD_SW_2D + ("tt_rsw",)) if compute_sw else ())
         res = {n: np.empty(grid3 if n in RAD_3D else lead + self.grid_shape, np.int32 if n == "icltop" else np.float64)
                for n in names}
-        bufs = []
-        try:
-            def alloc(nbytes):
-                ptr = ctypes.c_void_p()
-                check(self.lib.spdy_dev_alloc(self.h, max(nbytes, 8), ctypes.byref(ptr)))
-                bufs.append(ptr)
-                return ptr
-            d = {}
-            for k, a in list(ins.items()) + [("state", st)]:
-                d[k] = alloc(a.nbytes)
-                check(self.lib.spdy_dev_upload(self.h, d[k], _p(a), a.nbytes))
-            o = RadOut()
-            d_out = {}
-            for n in names:
-                d_out[n] = alloc(res[n].nbytes)
-                setattr(o, n, d_out[n].value)
+        res.update(ttend=np.empty(grid3), state=np.empty(nst))
+        ins["state"] = st
+
+        def call(d):
+            o = RadOut(**{n: d[n].value for n in names})
             sfc = RadSurface(d["fmask"].value, d["albsfc"].value) if compute_sw else RadSurface()
             g = lambda k: d.get(k)
             check(self.lib.spdy_radiation_down_dev(self.h, nb, 1 if compute_sw else 0, g("tg"), g("qg"), g("phig"), g("pslg"),
@@ -651,14 +635,7 @@ class Spectral:
                                                    ctypes.byref(o)))
             check(self.lib.spdy_radiation_up_dev(self.h, nb, d["tg"], d["pslg"], d["ts"], d["fsfcu"], d["state"], d["ttend"],
                                                  ctypes.byref(o)))
-            res["ttend"] = np.empty(grid3)
-            res["state"] = np.empty(nst)
-            for n, dp in (("ttend", d["ttend"]), ("state", d["state"])) + tuple(d_out.items()):
-                check(self.lib.spdy_dev_download(self.h, _p(res[n]), dp, res[n].nbytes))
-        finally:
-            for b in bufs:
-                self.lib.spdy_dev_free(self.h, b)
-        return res
+        return self._on_device(ins, res, call)
 
     def moist_columns(self, tg, qg, phig, pslg, ttend, qtend):
         """NumPy convenience: spdy_moist_columns_dev on copies in plan-owned device memory.  Returns a dict with the updated
@@ -676,27 +653,29 @@ class Spectral:
             res[n] = np.empty(lead + self.grid_shape, np.int32 if n in ("iptop", "icnv") else np.float64)
         for n in MOIST_3D:
             res[n] = np.empty(grid3)
-        bufs = []
+        ins = dict(zip(("tg", "qg", "phig", "pslg", "ttend", "qtend"), ins))
+
+        def call(d):
+            o = MoistOut(**{n: d[n].value for n in MOIST_2D + MOIST_3D})
+            check(self.lib.spdy_moist_columns_dev(self.h, nb, *[d[n] for n in ins], ctypes.byref(o)))
+        return self._on_device(ins, res, call)
+
+    def _on_device(self, ins, res, call):
+        """Copy the NumPy arrays of ins (name -> array) into plan-owned device memory and allocate a buffer for each array of res
+        (name -> array) that ins does not hold; call(d) with d: name -> device pointer; copy every buffer of res back into its
+        array and return res.  The buffers are freed whatever happens."""
+        d = {}
         try:
-            def alloc(nbytes):
+            for n, a in list(ins.items()) + [(n, a) for n, a in res.items() if n not in ins]:
                 ptr = ctypes.c_void_p()
-                check(self.lib.spdy_dev_alloc(self.h, max(nbytes, 8), ctypes.byref(ptr)))
-                bufs.append(ptr)
-                return ptr
-            d_in = []
-            for a in ins:
-                d = alloc(a.nbytes)
-                check(self.lib.spdy_dev_upload(self.h, d, _p(a), a.nbytes))
-                d_in.append(d)
-            o = MoistOut()
-            d_out = {}
-            for n in MOIST_2D + MOIST_3D:
-                d_out[n] = alloc(res[n].nbytes)
-                setattr(o, n, d_out[n].value)
-            check(self.lib.spdy_moist_columns_dev(self.h, nb, *d_in, ctypes.byref(o)))
-            for n, d in (("ttend", d_in[4]), ("qtend", d_in[5])) + tuple(d_out.items()):
-                check(self.lib.spdy_dev_download(self.h, _p(res[n]), d, res[n].nbytes))
+                check(self.lib.spdy_dev_alloc(self.h, max(a.nbytes, 8), ctypes.byref(ptr)))
+                d[n] = ptr
+                if n in ins:
+                    check(self.lib.spdy_dev_upload(self.h, ptr, _p(a), a.nbytes))
+            call(d)
+            for n, a in res.items():
+                check(self.lib.spdy_dev_download(self.h, _p(a), d[n], a.nbytes))
         finally:
-            for b in bufs:
-                self.lib.spdy_dev_free(self.h, b)
+            for ptr in d.values():
+                self.lib.spdy_dev_free(self.h, ptr)
         return res

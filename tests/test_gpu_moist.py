@@ -13,21 +13,11 @@ from dynstep import state as dyn_state
 
 pytestmark = pytest.mark.gpu
 
-RES = {"t30": ("t30", 8), "t30k5": ("t30", 5), "t30k7": ("t30", 7), "t63k16": ("t63", 16)}
 FLOATS = ("ttend", "qtend", "precnv", "precls", "cbmf", "qsat", "rh", "se")
 INTS = ("iptop", "icnv")
 
 
-def make_plan(tag, max_batch=64):
-    import speedy_f90_amd as s
-    res, kx = RES[tag]
-    sp = s.Spectral(res, kx=kx, max_batch=max_batch, device=0)
-    if kx == 16:
-        sp.set_sigma(synth.SIGMA_L16)
-    return sp
-
-
-@pytest.mark.parametrize("tag", sorted(RES))
+@pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_moist_columns_vs_reference(tag):
     """spdy_moist_columns_dev with every optional output against the reference: integers identical, floats within TOL."""
     z = np.load(os.path.join(GOLDEN, "ref_moist.npz"))
@@ -35,7 +25,7 @@ def test_moist_columns_vs_reference(tag):
     tab = moist.tables(moist.HSG[kx])
     ins = moist.grid_inputs(tab, (1, il, ix), int(z[tag + "_seed"]))
     sub = z[tag + "_sub"]
-    sp = make_plan(tag)
+    sp = moist.plan(tag)
     r = sp.moist_columns(*ins)
     sp.close()
     worst = 0.0
@@ -52,11 +42,6 @@ def test_moist_columns_vs_reference(tag):
     print("\n[moist columns %s vs reference] worst %.1e" % (tag, worst))
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _outs(nb, kx, il, ix):
     import torch
     o = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("precnv", "precls", "cbmf")}
@@ -69,11 +54,11 @@ def test_null_outputs_and_batch_composition():
     """All optional outputs NULL leaves ttend / qtend bit-equal to the full call; nb = 1, 7, 64 states in one launch are each
     bit-equal to the same state launched alone."""
     import torch
-    sp = make_plan("t30", 64)
+    sp = moist.plan("t30", 64)
     ix, il, kx = moist.VARIANTS["t30"]
     tab = moist.tables(moist.HSG[kx])
     for nb in (1, 7, 64):
-        tg, qg, phig, pslg, tt, qt = (_dev(a) for a in moist.grid_inputs(tab, (nb, il, ix), 9100 + nb))
+        tg, qg, phig, pslg, tt, qt = (moist.dev(a) for a in moist.grid_inputs(tab, (nb, il, ix), 9100 + nb))
         T, Q, out = tt.clone(), qt.clone(), _outs(nb, kx, il, ix)
         sp.moist_columns_dev(tg, qg, phig, pslg, T, Q, out)
         T0, Q0 = tt.clone(), qt.clone()
@@ -94,8 +79,8 @@ def test_null_outputs_and_batch_composition():
 def test_moist_physics_from_spectra(tag, oracle_factory):
     """spdy_moist_physics_dev (one inverse launch + the column kernel) against the restatement on the oracle's transforms."""
     import torch
-    kx = RES[tag][1]
-    sp, o = make_plan(tag, 4 * kx + 4), oracle_factory(tag)
+    kx = moist.RES[tag][1]
+    sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
     st = moist.state(o, dyn_state(sp, 8000), 4242)
     phi = o.geopotential(st["t"][0], st["phis"])
     il, ix = sp.il, sp.ix
@@ -105,8 +90,8 @@ def test_moist_physics_from_spectra(tag, oracle_factory):
     tt, qt = tt0.copy(), qt0.copy()
     moist.make_hook(rec)(o, st, None, None, tt, qt)
     assert rec["margin"].min() >= moist.MIN_MARGIN
-    T, Q, out = _dev(tt0), _dev(qt0), _outs(1, kx, il, ix)
-    sp.moist_physics_dev(_dev(st["t"][0]), _dev(st["tr"][0]), _dev(phi), _dev(st["ps"][0]), T, Q, out)
+    T, Q, out = moist.dev(tt0), moist.dev(qt0), _outs(1, kx, il, ix)
+    sp.moist_physics_dev(moist.dev(st["t"][0]), moist.dev(st["tr"][0]), moist.dev(phi), moist.dev(st["ps"][0]), T, Q, out)
     torch.cuda.synchronize()
     worst = max(synth.relerr(T.cpu().numpy(), tt), synth.relerr(Q.cpu().numpy(), qt))
     for n in ("precnv", "precls", "cbmf", "qsat", "rh", "se"):
@@ -139,7 +124,7 @@ def test_step_with_moist_physics(tag, oracle_factory):
     and its graph has exactly 3 nodes more than the adiabatic step's (geopotential, the inverse launch, the column kernel)."""
     import torch
     kx = VARIANTS[tag][3]
-    sp, o = make_plan(tag, 4 * kx + 4), oracle_factory(tag)
+    sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
     nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
     dt = 2400.0
     sp.initialize_implicit(dt); o.tail_init(dt)
@@ -149,7 +134,7 @@ def test_step_with_moist_physics(tag, oracle_factory):
     P = 3 * kx
     W = (f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix), f64(P, il, ix), f64(P, il, ix),
          f64(P + 1, il, ix), c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx), c128(kx, nx, mx))
-    fresh = lambda: {n: _dev(st[n]) for n in st}
+    fresh = lambda: {n: moist.dev(st[n]) for n in st}
     sp.moist_workspace()
     sp.use_own_stream()
     # plain launches

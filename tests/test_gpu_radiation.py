@@ -13,17 +13,7 @@ from conftest import GOLDEN, TOL
 
 pytestmark = pytest.mark.gpu
 
-RES = {"t30": ("t30", 8), "t30k5": ("t30", 5), "t30k7": ("t30", 7), "t63k16": ("t63", 16)}
 ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
-
-
-def make_plan(tag, max_batch=64):
-    import speedy_f90_amd as s
-    res, kx = RES[tag]
-    sp = s.Spectral(res, kx=kx, max_batch=max_batch, device=0)
-    if kx == 16:
-        sp.set_sigma(synth.SIGMA_L16)
-    return sp
 
 
 def _g(c, n, il, ix):
@@ -39,7 +29,7 @@ def _assert_close(got, want, key):
     return e
 
 
-@pytest.mark.parametrize("tag", sorted(RES))
+@pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_radiation_columns_vs_reference(tag):
     """radiation_columns with every optional output against the reference at both dates (integers identical, floats within TOL),
     then the step without shortwave on the held state against the reference and the restatement."""
@@ -51,7 +41,7 @@ def test_radiation_columns_vs_reference(tag):
     c = radiation.columns(tab, ncol, int(z[tag + "_seed"]), zon0)
     sub = z[tag + "_sub"]
     G = lambda n: _g(c, n, il, ix)
-    sp = make_plan(tag)
+    sp = moist.plan(tag)
     worst = 0.0
     for di, ty in enumerate(radiation.DATES):
         sp.radiation_set_date(ty)
@@ -72,19 +62,13 @@ def test_radiation_columns_vs_reference(tag):
     print("\n[radiation columns %s vs reference] worst %.1e" % (tag, worst))
 
 
-def _dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
 def _inputs(tab, nb, il, ix, seed, sp):
     """nb states of columns as device grids: (dict of tensors, restated columns, zonal per column)"""
     zl = {n: sp.table(n) for n in ZON}
     zon = radiation.zonal_columns(zl, nb, il, ix)
     c = radiation.columns(tab, nb * il * ix, seed, zon)
-    d = {n: _dev(radiation.grids(c[n], nb, il, ix)) for n in c if n != "iptop"}
-    d["iptop"] = _dev(radiation.grids(c["iptop"], nb, il, ix).astype(np.int32))
+    d = {n: moist.dev(radiation.grids(c[n], nb, il, ix)) for n in c if n != "iptop"}
+    d["iptop"] = moist.dev(radiation.grids(c["iptop"], nb, il, ix).astype(np.int32))
     return d, c, zon
 
 
@@ -107,7 +91,7 @@ def test_batch_composition_and_null_outputs():
     """A state's output bits do not depend on nb or on its position in the batch; NULL outputs leave ttend and the state
     bit-equal."""
     import torch
-    sp = make_plan("t30", 64)
+    sp = moist.plan("t30", 64)
     sp.radiation_set_date(radiation.DATES[0])
     ix, il, kx = moist.VARIANTS["t30"]
     tab = moist.tables(moist.HSG[kx])
@@ -142,7 +126,7 @@ def test_chain_capture_and_date(tag):
     between two replays changes the replayed result to the new date's."""
     import torch
     nb = 2
-    sp = make_plan(tag, 64)
+    sp = moist.plan(tag, 64)
     ix, il, kx = moist.VARIANTS[tag]
     tab = moist.tables(moist.HSG[kx])
     sp.radiation_set_date(radiation.DATES[0])
@@ -218,7 +202,7 @@ def test_argument_checks_and_index_clamp():
     values equal to the clamped restatement."""
     import torch
     import speedy_f90_amd as s
-    sp = make_plan("t30", 8)
+    sp = moist.plan("t30", 8)
     ix, il, kx = moist.VARIANTS["t30"]
     tab = moist.tables(moist.HSG[kx])
     S = sp.radiation_state_size()
@@ -244,7 +228,7 @@ def test_argument_checks_and_index_clamp():
     sp.close()
 
     # out-of-range temperatures: the index is clamped to [100, 400] (rows 200 / 320 of the table)
-    sp = make_plan("t30", 8)
+    sp = moist.plan("t30", 8)
     sp.radiation_set_date(radiation.DATES[1])
     zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
     c = radiation.columns(tab, il * ix, 9500, zon)

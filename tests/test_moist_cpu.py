@@ -10,7 +10,6 @@ import moist
 import synth
 from conftest import GOLDEN
 
-RES = {"t30": ("t30", 8), "t30k5": ("t30", 5), "t30k7": ("t30", 7), "t63k16": ("t63", 16)}
 TABLES = ("sigl", "sigh", "grdsig", "grdscp", "wvi", "entr")
 FLOATS = ("ttend", "qtend", "precnv", "precls", "cbmf", "qsat", "rh", "se")
 INTS = ("iptop", "icnv")
@@ -18,10 +17,7 @@ INTS = ("iptop", "icnv")
 
 @pytest.fixture(scope="module")
 def pkg():
-    import speedy_f90_amd as s
-    if not os.path.exists(s.LIB_PATH):
-        s.build()
-    return s
+    return moist.package()
 
 
 @pytest.fixture(scope="module")
@@ -29,17 +25,9 @@ def ref():
     return np.load(os.path.join(GOLDEN, "ref_moist.npz"))
 
 
-def host_plan(pkg, tag, max_batch=64):
-    res, kx = RES[tag]
-    sp = pkg.Spectral(res, kx=kx, max_batch=max_batch, device=-1)
-    if kx == 16:
-        sp.set_sigma(synth.SIGMA_L16)
-    return sp
-
-
-@pytest.mark.parametrize("tag", sorted(RES))
+@pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_physics_tables_bit_equal(tag, pkg, ref):
-    sp = host_plan(pkg, tag)
+    sp = moist.plan(tag, device=-1)
     for n in TABLES:
         assert np.array_equal(sp.table(n), ref["%s_tab_%s" % (tag, n)]), n
 
@@ -53,7 +41,7 @@ def test_fixture_coverage(ref):
     for n in ("psmin_cut", "conv_ktop2", "conv_lqthr", "no_conv", "secondary_flux", "lsc_kx", "lsc_interior", "qsat_warm",
               "qsat_cold", "q_clamp"):
         assert counts[n] >= 0.01 * ncol, (n, counts[n])
-    for tag in RES:
+    for tag in moist.RES:
         assert float(ref[tag + "_min_margin"]) >= moist.MIN_MARGIN, tag
 
 
@@ -72,7 +60,7 @@ def pick(a, sub, ncol):
     return np.asarray(a).reshape(-1, ncol)[:, sub].squeeze()
 
 
-@pytest.mark.parametrize("tag", sorted(RES))
+@pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_restatement_matches_reference(tag, ref):
     tab, ins, sub = reference_case(tag, ref)
     ncol = ins[3].size
@@ -96,16 +84,16 @@ def test_cabi_argument_checks(pkg):
         sp = pkg.Spectral("t30", kx=kx, max_batch=64, device=-1)
         assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs, None) == -1
         assert lib.spdy_moist_physics_dev(sp.h, *ptrs, None) == -1
-    sp = host_plan(pkg, "t30", max_batch=4)
+    sp = moist.plan("t30", 4, device=-1)
     assert lib.spdy_moist_columns_dev(sp.h, 5, *ptrs, None) == -1            # nb > max_batch
     assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs[:4], None, dummy, None) == -1   # NULL ttend
     assert lib.spdy_moist_columns_dev(sp.h, 4, *ptrs, None) == -3            # valid: no device
     assert lib.spdy_moist_physics_dev(sp.h, *ptrs, None) == -1               # max_batch < 3 kx + 1
-    sp = host_plan(pkg, "t30", max_batch=25)
+    sp = moist.plan("t30", 25, device=-1)
     assert lib.spdy_moist_physics_dev(sp.h, *ptrs[:4], None, dummy, None) == -1      # NULL ttend
     assert lib.spdy_moist_physics_dev(sp.h, *ptrs, None) == -3
     assert lib.spdy_moist_workspace(sp.h) == -3
     out = pkg.spectral.MoistOut()
     assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs, ctypes.byref(out)) == -3
-    sp = host_plan(pkg, "t63k16")
+    sp = moist.plan("t63k16", device=-1)
     assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs, None) == -3

@@ -11,16 +11,12 @@ import radiation
 import synth
 from conftest import GOLDEN, TOL
 
-RES = {"t30": ("t30", 8), "t30k5": ("t30", 5), "t30k7": ("t30", 7), "t63k16": ("t63", 16)}
 ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
 
 
 @pytest.fixture(scope="module")
 def pkg():
-    import speedy_f90_amd as s
-    if not os.path.exists(s.LIB_PATH):
-        s.build()
-    return s
+    return moist.package()
 
 
 @pytest.fixture(scope="module")
@@ -28,22 +24,14 @@ def ref():
     return np.load(os.path.join(GOLDEN, "ref_radiation.npz"))
 
 
-def host_plan(pkg, tag, max_batch=64):
-    res, kx = RES[tag]
-    sp = pkg.Spectral(res, kx=kx, max_batch=max_batch, device=-1)
-    if kx == 16:
-        sp.set_sigma(synth.SIGMA_L16)
-    return sp
-
-
 def zonal_ref(ref, tag, di):
     return {n: ref["%s_d%d_%s" % (tag, di, n)] for n in ZON}
 
 
-@pytest.mark.parametrize("tag", sorted(RES))
+@pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_radiation_tables_bit_equal(tag, pkg, ref):
     """fband and, after spdy_radiation_set_date, the zonal forcing of both dates, bit for bit."""
-    sp = host_plan(pkg, tag)
+    sp = moist.plan(tag, device=-1)
     assert np.array_equal(sp.table("fband"), ref["fband"].ravel())
     assert np.array_equal(radiation.FBAND, ref["fband"])
     for n in ZON:
@@ -64,7 +52,7 @@ def test_fixture_coverage(ref):
     assert ncol == 96 * 48
     for n in ("cltop_nl1", "cltop_mid", "cltop_iptop", "cltop_2", "cltop_none", "strat_land", "strat_sea", "polar_night"):
         assert counts[n] >= 0.01 * ncol, (n, counts[n])
-    for tag in RES:
+    for tag in moist.RES:
         il = moist.VARIANTS[tag][1]
         s0, s1 = ref["%s_d0_stratz" % tag], ref["%s_d1_stratz" % tag]
         assert np.any(s0[il // 2:] > 0) and np.any(s1[:il // 2] > 0), tag
@@ -93,7 +81,7 @@ def check(got, ref, key, sub):
 
 
 @pytest.mark.parametrize("di", [0, 1])
-@pytest.mark.parametrize("tag", sorted(RES))
+@pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_restatement_matches_reference(tag, di, ref):
     tab, c, sub, zon = reference_case(tag, ref, di)
     r1, r2 = radiation.two_steps(tab, c, zon)
@@ -118,7 +106,7 @@ def test_cabi_argument_checks(pkg):
     sp = pkg.Spectral("t30", kx=6, max_batch=64, device=-1)
     lib.spdy_radiation_set_date(sp.h, ctypes.c_double(0.1))
     assert down(sp, 1) == -5 and upc(sp, 1) == -5        # no sigma levels
-    sp = host_plan(pkg, "t30", max_batch=4)
+    sp = moist.plan("t30", 4, device=-1)
     assert lib.spdy_radiation_state_size(sp.h) == (6 * 8 + 7) * 96 * 48
     assert down(sp, 1) == -5 and upc(sp, 1) == -5        # no date
     assert lib.spdy_radiation_set_date(sp.h, ctypes.c_double(0.25)) == 0
@@ -129,6 +117,6 @@ def test_cabi_argument_checks(pkg):
     assert upc(sp, 1, ptrs=[d] * 5 + [None]) == -1                    # NULL ttend
     assert down(sp, 4) == -3 and upc(sp, 4) == -3                     # valid: no device
     assert down(sp, 0, ptrs=[None] * 8) == -3                         # nb = 0 needs no pointers
-    sp = host_plan(pkg, "t63k16")
+    sp = moist.plan("t63k16", device=-1)
     sp.radiation_set_date(0.5)
     assert down(sp, 1) == -3 and upc(sp, 1) == -3
