@@ -441,18 +441,20 @@ int spdy_output_workspace(spdy_plan *plan);
 int spdy_output_batch_dev(spdy_plan *plan, const double *vor, const double *div, const double *t, const double *q, const double *phi,
                           const double *ps, float *u_out, float *v_out, float *t_out, float *q_out, float *phi_out, float *ps_out);
 
-/* Column physics (spdy_moist_columns_dev, spdy_moist_physics_dev, spdy_radiation_down_dev, spdy_radiation_up_dev) checks its
- * arguments in one order, and the first check that fails gives the code: a NULL plan, kx outside [5, 16] and nb outside
- * [0, max_batch] SPDY_ERR_ARG; no sigma levels, then (radiation) no date, SPDY_ERR_STATE; a NULL required pointer SPDY_ERR_ARG;
- * then the call's own conditions (spdy_moist_physics_dev: max_batch); a host-only plan SPDY_ERR_NO_DEVICE last.             */
+/* Column physics (spdy_moist_columns_dev, spdy_moist_physics_dev, spdy_radiation_down_dev, spdy_radiation_up_dev,
+ * spdy_surface_fluxes_dev, spdy_pbl_dev, spdy_column_physics_dev) checks its arguments in one order, and the first check that
+ * fails gives the code: a NULL plan, kx outside [5, 16] and nb outside [0, max_batch] SPDY_ERR_ARG; no sigma levels, then
+ * (radiation, the chain) no date, then (surface fluxes, the chain) no orography, SPDY_ERR_STATE; a NULL required pointer
+ * SPDY_ERR_ARG; then the call's own conditions (spdy_moist_physics_dev: max_batch); a host-only plan SPDY_ERR_NO_DEVICE last. */
 
 /* ---- column physics: the precipitation block of get_physical_tendencies (physics.f90:110-138) ----------------------------
  * Replaces, on the device, the thermodynamic fields (physics.f90:110-115: psg = exp(pslg), rps, qg = max(qg, 0), se = cp*tg +
  * phig), spec_hum_to_rel_hum per level (:117-119; humidity.f90:16-28, 46-79), deep convection (:126; convection.f90:26-235), the
  * scaling of the convective fluxes for k >= 2 (:128-131), icnv = kx - iptop (:133), large-scale condensation (:136;
  * large_scale_condensation.f90:32-83) and ttend = ttend + tt_cnv + tt_lsc, qtend = qtend + qt_cnv + qt_lsc (:138-139).  A host
- * "with physics" calls it between spdy_grid_tendencies_dev and the direct batch (tendencies.f90:203-206).  What stays on the host:
- * radiation, surface fluxes, vertical diffusion and SPPT (physics.f90:141-250), which need the boundary fields (SST, land, albedo).
+ * "with physics" calls it between spdy_grid_tendencies_dev and the direct batch (tendencies.f90:203-206).  The blocks that follow
+ * it in get_physical_tendencies have device forms of their own below (radiation, surface fluxes, boundary layer); only SPPT
+ * (physics.f90:208-222, off in the reference's params.f90) has none.
  * One thread per column; 5 <= kx <= 16 (SPDY_ERR_ARG otherwise), sigma levels as for the geopotential (SPDY_ERR_STATE without).
  * Results follow the reference's order of operations without contraction: decisions (convection or not, its top, condensation)
  * are the reference's wherever no decision is within rounding of its threshold.  Both calls can be captured in a graph; `out` is
@@ -481,8 +483,8 @@ int spdy_moist_physics_dev(spdy_plan *plan, const double *t, const double *q, co
  * (compute_sw set: gse, clouds with qcloud = qa(:,:,kx-1), the shortwave fluxes, tt_rsw = dfabs*rps*grdscp and the longwave
  * transmissivities tau2 / stratc; always: the downward longwave fluxes) and the UP half (the upward longwave fluxes from the
  * caller's surface temperature ts and surface emission fsfcu = slru(:,:,3), tt_rlw = dfabs*rps*grdscp, then
- * ttend = (ttend + tt_rsw) + tt_rlw in place).  A host with physics calls spdy_moist_columns_dev, the down half, its own surface
- * fluxes (which read ssrd and slrd), then the up half.
+ * ttend = (ttend + tt_rsw) + tt_rlw in place).  A host with physics calls spdy_moist_columns_dev, the down half, the surface
+ * fluxes (spdy_surface_fluxes_dev, which read ssrd and slrd and give ts and fsfcu), then the up half.
  * What the reference keeps in module state (tau2, stratc, flux) is the caller's RADIATION STATE: device memory of
  * nb * spdy_radiation_state_size(plan) doubles, one block per model state, kept across steps (and graph replays).  The first
  * call on a state must have compute_sw = 1, as the reference's first step has (mod(1, nstrad) == 1).  On steps without
@@ -514,6 +516,67 @@ int spdy_radiation_down_dev(spdy_plan *plan, int nb, int compute_sw, const doubl
                             const spdy_rad_surface *sfc, double *state, const spdy_rad_out *out);
 int spdy_radiation_up_dev(spdy_plan *plan, int nb, const double *tg, const double *pslg, const double *ts, const double *fsfcu,
                           double *state, double *ttend, const spdy_rad_out *out);
+
+/* ---- column physics: surface fluxes (physics.f90:169-170) and the boundary layer (:193-205) ---------------------------------
+ * spdy_surface_fluxes_dev is get_surface_fluxes with lfluxland = .true. (surface_fluxes.f90:97-295) between the radiation halves:
+ * it reads the down half's ssrd / slrd, the winds and the lowest two levels, and writes what the up half needs -- ts (= tsfc) and
+ * fsfcu (= slru(:,:,3)) -- and flux3, the four averaged fluxes ustr3 vstr3 shf3 evap3 (4 (ix,il) fields per state) that
+ * spdy_pbl_dev reads.  spdy_pbl_dev is get_vertical_diffusion_tend (vertical_diffusion.f90:57-142: shallow convection, moisture
+ * diffusion where sigh(k) > 0.5, damping of super-adiabatic lapse rates) on the moist block's se, rh, qsat and icnv, then the
+ * surface-flux tendencies of level kx and utend += ut_pbl, vtend += vt_pbl, ttend += tt_pbl, qtend += qt_pbl in place
+ * (physics.f90:197-205).  ut_pbl / vt_pbl are zero above level kx, so utend / vtend are read and written at level kx only (the
+ * reference's + 0.0 elsewhere changes no bit but the sign of a -0.0).  It follows the up half: the reference sums
+ * (ttend + tt_rsw) + tt_rlw before + tt_pbl.
+ * Not built: SPPT (physics.f90:208-222; sppt_on is .false. in params.f90) and the second get_surface_fluxes call
+ * (sea_coupling_flag > 0, lfluxland = .false.: the reference's sea model stops for those flags and that path reads ks unset).
+ * Reproduced as the reference has them: fhum0 = 0, so q1 = qa(:,:,kx) and the relative humidity is never read (rh is no argument
+ * of the surface call); hfluxn(:,:,2) = .. - slru + shf + alhc*evap; t0 computed twice; ftemp0*t1 + gtemp0*t2 evaluated.
+ * Boundary fields per column: spdy_sfc_boundary (the land model's stl_am / soilw_am, the sea model's sst_am, mod_radcon's snowc,
+ * alb_l, alb_s).  spdy_surface_set_orography takes the surface geopotential phis0 (host, (ix,il)), keeps it and forog
+ * (set_orog_land_sfc_drag, surface_fluxes.f90:300-309; spdy_get_table "phis0", "forog") in plan memory, copied on the plan's
+ * stream like the fields of spdy_radiation_set_date (not callable during a capture); without it the surface call is
+ * SPDY_ERR_STATE.  The level tables of the vertical diffusion are spdy_get_table's vd_scalars (cshc cvdi fshcq fshcse fvdiq
+ * fvdise), vd_rsig, vd_rsig1, vd_drh0, vd_fvdiq2 (kx each; vd_drh0 / vd_fvdiq2 entry k-1 belong to the levels k, k+1).
+ * spdy_column_physics_dev is the whole of physics.f90:110-205 on gridded states: the five calls in the reference's order (moist,
+ * down, surface, up, boundary layer) with the intermediates in plan workspace (spdy_column_physics_workspace allocates it ahead
+ * of a capture: (3 kx + 12) grids for each of max_batch states).  A member of `out` that is set takes the place of the workspace
+ * field.  ssrd is written by compute_sw calls and read by every call, so it stays where the last compute_sw call put it: the
+ * workspace, or the caller's rad.ssrd, which must then be passed on the calls without shortwave too.  All calls can be captured
+ * in a graph; `out` is read at call time.                                                                                       */
+typedef struct {                      /* (ix,il) per state, nb states back to back, device pointers, all required              */
+    const double *fmask;              /* land fraction [0, 1]                                                                  */
+    const double *sst;                /* sea surface temperature (sst_am)                                                      */
+    const double *stl, *soilw;        /* land surface temperature (stl_am), soil water availability (soilw_am)                 */
+    const double *snowc, *alb_l, *alb_s;   /* snow cover, land and sea albedo (mod_radcon)                                     */
+} spdy_sfc_boundary;
+typedef struct {                      /* per state; any member may be NULL = not written                                      */
+    double *ustr, *vstr, *shf, *evap, *slru;   /* (ix,il,3): land, sea, weighted by the land fraction                          */
+    double *hfluxn;                   /* (ix,il,2): net heat flux into land and sea (the land and sea models' input)           */
+    double *tskin, *u0, *v0, *t0;     /* (ix,il)                                                                              */
+} spdy_sfc_out;
+typedef struct {                      /* per state; any member may be NULL = not written                                      */
+    double *ut_pbl, *vt_pbl;          /* (ix,il): level kx (zero above)                                                       */
+    double *tt_pbl, *qt_pbl;          /* (ix,il,kx)                                                                           */
+} spdy_pbl_out;
+typedef struct {                      /* per state; any member may be NULL                                                    */
+    spdy_moist_out moist;
+    spdy_rad_out rad;
+    spdy_sfc_out sfc;
+    spdy_pbl_out pbl;
+    double *ts, *fsfcu;               /* (ix,il): the surface call's required outputs                                         */
+} spdy_column_physics_out;
+int spdy_surface_set_orography(spdy_plan *plan, const double *phis0);
+int spdy_surface_fluxes_dev(spdy_plan *plan, int nb, const double *ug, const double *vg, const double *tg, const double *qg,
+                            const double *phig, const double *pslg, const double *ssrd, const double *slrd,
+                            const spdy_sfc_boundary *bnd, double *ts, double *fsfcu, double *flux3, const spdy_sfc_out *out);
+int spdy_pbl_dev(spdy_plan *plan, int nb, const double *qg, const double *phig, const double *pslg, const double *se,
+                 const double *rh, const double *qsat, const int *icnv, const double *flux3, double *utend, double *vtend,
+                 double *ttend, double *qtend, const spdy_pbl_out *out);
+int spdy_column_physics_workspace(spdy_plan *plan);
+int spdy_column_physics_dev(spdy_plan *plan, int nb, int compute_sw, const double *ug, const double *vg, const double *tg,
+                            const double *qg, const double *phig, const double *pslg, const spdy_sfc_boundary *bnd,
+                            const double *albsfc, double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                            const spdy_column_physics_out *out);
 
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,

@@ -113,6 +113,11 @@ SIGNATURES = {
     "spdy_radiation_state_size": [c_void_p],
     "spdy_radiation_down_dev": [c_void_p, c_int, c_int] + [c_void_p] * 11,
     "spdy_radiation_up_dev": [c_void_p, c_int] + [c_void_p] * 7,
+    "spdy_surface_set_orography": [c_void_p, c_void_p],
+    "spdy_surface_fluxes_dev": [c_void_p, c_int] + [c_void_p] * 13,
+    "spdy_pbl_dev": [c_void_p, c_int] + [c_void_p] * 13,
+    "spdy_column_physics_workspace": [c_void_p],
+    "spdy_column_physics_dev": [c_void_p, c_int, c_int] + [c_void_p] * 14,
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

@@ -1,5 +1,7 @@
-// C ABI of the column physics (include/spdy.h, "column physics"): the precipitation block (physics.f90:110-138) and the
-// radiation schemes (physics.f90:146-166 and :180-186).  Kernels: csrc/spdy_physics.hip, csrc/spdy_radiation.hip.
+// C ABI of the column physics (include/spdy.h, "column physics"): the precipitation block (physics.f90:110-138), the
+// radiation schemes (physics.f90:146-166 and :180-186), the surface fluxes (:169-170), the boundary layer (:193-205) and the
+// whole chain.  Kernels: csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip.
+#include <cmath>
 #include <cstring>
 
 #include "spdy_plan.hpp"
@@ -16,13 +18,14 @@ int check_kx(const spdy_plan *p, const char *scheme)
 }
 
 // argument checks that need no device (a host-only plan answers them), in the order include/spdy.h gives
-int column_args(const spdy_plan *p, const char *scheme, int nb, bool need_date, bool ok_ptrs)
+int column_args(const spdy_plan *p, const char *scheme, int nb, bool need_date, bool ok_ptrs, bool need_orog = false)
 {
     NEED_PLAN(p);
     RC(check_kx(p, scheme));
     RC(check_batch(p, nb));
     if (!p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "%s needs sigma levels (kx in {5,7,8} or spdy_plan_set_sigma)", scheme);
     if (need_date && !p->tab.date_ready) return fail(SPDY_ERR_STATE, "radiation needs a date (spdy_radiation_set_date)");
+    if (need_orog && !p->tab.orog_ready) return fail(SPDY_ERR_STATE, "%s needs the orography (spdy_surface_set_orography)", scheme);
     if (!ok_ptrs) return fail(SPDY_ERR_ARG, "null device pointer");
     return SPDY_OK;
 }
@@ -87,6 +90,54 @@ spdy::RadCols rad_cols(const spdy_plan *p, int nb, const double *tg, const doubl
     }
     a.eps1 = static_cast<double>(0.05f) / (t.dhs[0] + t.dhs[1]);
     return a;
+}
+
+spdy::SfcCols sfc_cols(const spdy_plan *p, int nb, const double *ug, const double *vg, const double *tg, const double *qg,
+                       const double *phig, const double *pslg, const double *ssrd, const double *slrd, const spdy_sfc_boundary *b,
+                       double *ts, double *fsfcu, double *flux3, const spdy_sfc_out *out)
+{
+    const HostTables &t = p->tab;
+    const int kx = t.kx;
+    spdy::SfcCols a{};
+    a.nb = nb; a.ncol = t.ix * t.il; a.ix = t.ix; a.kx = kx;
+    a.ug = ug; a.vg = vg; a.tg = tg; a.qg = qg; a.phig = phig; a.pslg = pslg; a.ssrd = ssrd; a.slrd = slrd;
+    if (b) {
+        a.fmask = b->fmask; a.sst = b->sst; a.stl = b->stl; a.soilw = b->soilw; a.snowc = b->snowc; a.alb_l = b->alb_l;
+        a.alb_s = b->alb_s;
+    }
+    a.phis0 = p->d_orog; a.forog = p->d_orog + a.ncol; a.sqcoa = p->d_orog + 2 * (size_t)a.ncol;
+    a.ts = ts; a.fsfcu = fsfcu; a.flux3 = flux3;
+    if (out) {
+        a.ustr = out->ustr; a.vstr = out->vstr; a.shf = out->shf; a.evap = out->evap; a.slru = out->slru; a.hfluxn = out->hfluxn;
+        a.tskin = out->tskin; a.u0 = out->u0; a.v0 = out->v0; a.t0 = out->t0;
+    }
+    a.wvi2_kx = t.wvi[2 * kx - 1]; a.sigl_kx = t.sigl[kx - 1]; a.rgas = t.rgas;
+    return a;
+}
+
+spdy::PblCols pbl_cols(const spdy_plan *p, int nb, const double *qg, const double *phig, const double *pslg, const double *se,
+                       const double *rh, const double *qsat, const int *icnv, const double *flux3, double *utend, double *vtend,
+                       double *ttend, double *qtend, const spdy_pbl_out *out)
+{
+    const HostTables &t = p->tab;
+    const int kx = t.kx;
+    spdy::PblCols a{};
+    a.nb = nb; a.ncol = t.ix * t.il; a.kx = kx;
+    a.qg = qg; a.phig = phig; a.pslg = pslg; a.se = se; a.rh = rh; a.qsat = qsat; a.icnv = icnv; a.flux3 = flux3;
+    a.utend = utend; a.vtend = vtend; a.ttend = ttend; a.qtend = qtend;
+    if (out) { a.ut_pbl = out->ut_pbl; a.vt_pbl = out->vt_pbl; a.tt_pbl = out->tt_pbl; a.qt_pbl = out->qt_pbl; }
+    for (int k = 0; k < kx; ++k) {
+        a.rsig[k] = t.vd_rsig[k]; a.rsig1[k] = t.vd_rsig1[k]; a.drh0[k] = t.vd_drh0[k]; a.fvdiq2[k] = t.vd_fvdiq2[k];
+        if (t.sigh[k + 1] > 0.5) a.diffmask |= 1 << k;               // vertical_diffusion.f90:113, level k + 1
+    }
+    a.fshcq = t.vd_scalars[2]; a.fshcse = t.vd_scalars[3]; a.fvdise = t.vd_scalars[5];
+    a.grdsig_kx = t.grdsig[kx - 1]; a.grdscp_kx = t.grdscp[kx - 1];
+    return a;
+}
+
+bool boundary_ok(const spdy_sfc_boundary *b)
+{
+    return b && b->fmask && b->sst && b->stl && b->soilw && b->snowc && b->alb_l && b->alb_s;
 }
 }  // namespace
 
@@ -188,6 +239,104 @@ int spdy_radiation_up_dev(spdy_plan *p, int nb, const double *tg, const double *
     spdy::RadCols a = rad_cols(p, nb, tg, nullptr, nullptr, pslg, ttend, state, out);
     a.ts = ts; a.fsfcu = fsfcu;
     KERNEL(spdy::launch_radiation(a, 2, p->stream));
+    return SPDY_OK;
+}
+
+/* ---------------------------------------------------------------- surface fluxes (physics.f90:169-170), boundary layer (:193-205) */
+int spdy_surface_set_orography(spdy_plan *p, const double *phis0)
+{
+    NEED_PLAN(p);
+    NOT_CAPTURING(p, "spdy_surface_set_orography (host table build + upload)");
+    const std::string err = p->tab.set_orography(phis0);
+    if (!err.empty()) return fail(SPDY_ERR_ARG, "surface_set_orography: %s", err.c_str());
+    if (p->device < 0) return SPDY_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    const HostTables &t = p->tab;
+    const size_t ncol = (size_t)t.ix * t.il, n = 2 * ncol + t.il;
+    if (!p->d_orog) {
+        void *ptr;
+        RC(dev_alloc(p, n * sizeof(double), &ptr));
+        p->d_orog = static_cast<double *>(ptr);
+    }
+    // stream-ordered like spdy_radiation_set_date's fields; sqrt(coa(j)) per latitude, coa symmetric (geometry.f90:68-73)
+    std::vector<double> h(n);
+    std::memcpy(h.data(), t.phis0.data(), sizeof(double) * ncol);
+    std::memcpy(h.data() + ncol, t.forog.data(), sizeof(double) * ncol);
+    for (int j = 0; j < t.il; ++j) h[2 * ncol + j] = std::sqrt(t.coa_half[j < t.iy ? j : t.il - 1 - j]);
+    HIP_TRY(hipMemcpyAsync(p->d_orog, h.data(), n * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
+int spdy_surface_fluxes_dev(spdy_plan *p, int nb, const double *ug, const double *vg, const double *tg, const double *qg,
+                            const double *phig, const double *pslg, const double *ssrd, const double *slrd,
+                            const spdy_sfc_boundary *bnd, double *ts, double *fsfcu, double *flux3, const spdy_sfc_out *out)
+{
+    const bool ok = ug && vg && tg && qg && phig && pslg && ssrd && slrd && boundary_ok(bnd) && ts && fsfcu && flux3;
+    RC(column_args(p, "surface fluxes", nb, false, !nb || ok, true));
+    NEED_DEVICE(p);
+    KERNEL(spdy::launch_surface_fluxes(sfc_cols(p, nb, ug, vg, tg, qg, phig, pslg, ssrd, slrd, bnd, ts, fsfcu, flux3, out), p->stream));
+    return SPDY_OK;
+}
+
+int spdy_pbl_dev(spdy_plan *p, int nb, const double *qg, const double *phig, const double *pslg, const double *se, const double *rh,
+                 const double *qsat, const int *icnv, const double *flux3, double *utend, double *vtend, double *ttend,
+                 double *qtend, const spdy_pbl_out *out)
+{
+    const bool ok = qg && phig && pslg && se && rh && qsat && icnv && flux3 && utend && vtend && ttend && qtend;
+    RC(column_args(p, "vertical diffusion", nb, false, !nb || ok));
+    NEED_DEVICE(p);
+    KERNEL(spdy::launch_pbl(pbl_cols(p, nb, qg, phig, pslg, se, rh, qsat, icnv, flux3, utend, vtend, ttend, qtend, out), p->stream));
+    return SPDY_OK;
+}
+
+/* ---------------------------------------------------------------- the whole chain (physics.f90:110-205) */
+int spdy_column_physics_workspace(spdy_plan *p)
+{
+    NEED_PLAN(p);
+    RC(check_kx(p, "column physics"));
+    NEED_DEVICE(p);
+    if (p->physics_ws) return SPDY_OK;
+    NOT_CAPTURING(p, "allocating the column-physics workspace (call spdy_column_physics_workspace before the capture)");
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(3 * p->tab.kx + 12) * grid_elems(p) * p->max_batch * sizeof(double), &ptr));
+    p->physics_ws = static_cast<double *>(ptr);
+    return SPDY_OK;
+}
+
+int spdy_column_physics_dev(spdy_plan *p, int nb, int compute_sw, const double *ug, const double *vg, const double *tg,
+                            const double *qg, const double *phig, const double *pslg, const spdy_sfc_boundary *bnd,
+                            const double *albsfc, double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                            const spdy_column_physics_out *out)
+{
+    const bool ok = ug && vg && tg && qg && phig && pslg && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
+                    vtend && ttend && qtend;
+    RC(column_args(p, "column physics", nb, true, !nb || ok, true));
+    NEED_DEVICE(p);
+    RC(spdy_column_physics_workspace(p));
+    // the intermediates, each max_batch states long so that a field's place does not depend on nb
+    const size_t g = grid_elems(p) * p->max_batch, L = (size_t)p->tab.kx * g;
+    double *w = p->physics_ws, *w2 = w + 3 * L;
+    // the caller's optional outputs take the place of the workspace where both exist.  ssrd is written by shortwave calls only
+    // and read by every call (the reference holds it in get_physical_tendencies): it stays where the last shortwave call put it
+    spdy_moist_out mo{};
+    spdy_rad_out ro{};
+    spdy_sfc_out so{};
+    double *ts = nullptr, *fsfcu = nullptr;
+    if (out) { mo = out->moist; ro = out->rad; so = out->sfc; ts = out->ts; fsfcu = out->fsfcu; }
+    auto pick = [](auto *&dst, auto *ws) { if (!dst) dst = ws; };
+    pick(mo.se, w); pick(mo.rh, w + L); pick(mo.qsat, w + 2 * L);
+    pick(mo.precnv, w2); pick(mo.precls, w2 + g); pick(ro.ssrd, w2 + 2 * g); pick(ro.slrd, w2 + 3 * g);
+    pick(ts, w2 + 4 * g); pick(fsfcu, w2 + 5 * g);
+    double *flux3 = w2 + 6 * g;
+    pick(mo.iptop, reinterpret_cast<int *>(w2 + 10 * g)); pick(mo.icnv, reinterpret_cast<int *>(w2 + 11 * g));
+    spdy_rad_surface rs{bnd ? bnd->fmask : nullptr, albsfc};
+    RC(spdy_moist_columns_dev(p, nb, tg, qg, phig, pslg, ttend, qtend, &mo));
+    RC(spdy_radiation_down_dev(p, nb, compute_sw, tg, qg, phig, pslg, mo.rh, mo.precnv, mo.precls, mo.iptop, &rs, rad_state, &ro));
+    RC(spdy_surface_fluxes_dev(p, nb, ug, vg, tg, qg, phig, pslg, ro.ssrd, ro.slrd, bnd, ts, fsfcu, flux3, &so));
+    RC(spdy_radiation_up_dev(p, nb, tg, pslg, ts, fsfcu, rad_state, ttend, &ro));
+    RC(spdy_pbl_dev(p, nb, qg, phig, pslg, mo.se, mo.rh, mo.qsat, mo.icnv, flux3, utend, vtend, ttend, qtend,
+                    out ? &out->pbl : nullptr));
     return SPDY_OK;
 }
 

@@ -1,4 +1,5 @@
-// Launch and addressing layer of the column-physics kernels (csrc/spdy_physics.hip, csrc/spdy_radiation.hip).
+// Launch and addressing layer of the column-physics kernels (csrc/spdy_physics.hip, csrc/spdy_radiation.hip,
+// csrc/spdy_surface.hip), and the one device function they share (get_qsat).
 //
 // One thread per (state, column): nb * ncol threads in blocks of COLUMN_BLOCK, threads with consecutive longitude in
 // consecutive lanes, so every level load and store is one coalesced access per wave.  Each kernel comes as <8> and <16>:
@@ -17,6 +18,18 @@ __host__ __device__ constexpr double F(float x) { return static_cast<double>(x);
 
 // physical_constants.f90:22
 __device__ constexpr double kCp = F(1004.0f);
+
+// get_qsat (humidity.f90:46-79) for sig > 0: saturation specific humidity [g/kg] at temperature ta, normalised pressure ps and
+// sigma sig.  e0 is a double literal, the other constants default reals; the reference's association order, no contraction.
+__device__ inline double get_qsat(double ta, double ps, double sig)
+{
+#pragma clang fp contract(off)
+    const double e0 = 6.108e-3, c1 = F(17.269f), c2 = F(21.875f);
+    const double t0 = F(273.16f), t1 = F(35.86f), t2 = F(7.66f);
+    const double x = ta >= t0 ? c1 * (ta - t0) / (ta - t1) : c2 * (ta - t0) / (ta - t2);
+    const double e = e0 * exp(x);
+    return 622.0 * e / (sig * ps - 0.378f * e);
+}
 
 // This thread's place in the launch: gid = b * ncol + col for state b and column col.  The threads past the last column of the
 // last state (gid >= nb * ncol) return at once.

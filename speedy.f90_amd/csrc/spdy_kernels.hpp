@@ -312,4 +312,33 @@ struct RadCols {
 };
 hipError_t launch_radiation(const RadCols &a, int phase, hipStream_t s);   // 0 shortwave, 1 longwave down, 2 up
 
+// Surface fluxes (csrc/spdy_surface.hip, surface_fluxes_kernel): get_surface_fluxes with lfluxland = .true.
+// (surface_fluxes.f90:97-295).  Required outputs ts, fsfcu and flux3 (4 fields per state: ustr3 vstr3 shf3 evap3); the others
+// may be null.  Three-plane outputs are (ix, il, 3) per state (land, sea, weighted), hfluxn (ix, il, 2).
+struct SfcCols {
+    int nb, ncol, ix, kx;
+    const double *ug, *vg, *tg, *qg, *phig, *pslg;   // (ix, il, kx) / (ix, il) per state
+    const double *ssrd, *slrd;                       // (ix, il) per state: the down half of the radiation
+    const double *fmask, *sst, *stl, *soilw, *snowc, *alb_l, *alb_s;   // (ix, il) per state
+    const double *phis0, *forog, *sqcoa;             // plan-owned: (ix, il), (ix, il), [il] sqrt(coa(j))
+    double *ts, *fsfcu, *flux3;
+    double *ustr, *vstr, *shf, *evap, *slru, *hfluxn, *tskin, *u0, *v0, *t0;
+    double wvi2_kx, sigl_kx, rgas;                   // wvi(kx,2), sigl(kx), rgas = akap*cp
+};
+hipError_t launch_surface_fluxes(const SfcCols &a, hipStream_t s);
+
+// Vertical diffusion and the boundary-layer sums (csrc/spdy_surface.hip, pbl_kernel): vertical_diffusion.f90:57-142 and
+// physics.f90:197-205.  Per-level tables are top down: entry k belongs to the reference's level k + 1.  utend / vtend are read
+// and written at level kx only; ut_pbl / vt_pbl (level kx, (ix, il) per state), tt_pbl / qt_pbl may be null.
+struct PblCols {
+    int nb, ncol, kx, diffmask;                      // diffmask bit k: sigh(k + 1) > 0.5 (the moisture diffusion of level k + 1)
+    const double *qg, *phig, *pslg, *se, *rh, *qsat, *flux3;
+    const int *icnv;
+    double *utend, *vtend, *ttend, *qtend;
+    double *ut_pbl, *vt_pbl, *tt_pbl, *qt_pbl;
+    double rsig[COLUMN_KMAX], rsig1[COLUMN_KMAX], drh0[COLUMN_KMAX], fvdiq2[COLUMN_KMAX];
+    double fshcq, fshcse, fvdise, grdsig_kx, grdscp_kx;
+};
+hipError_t launch_pbl(const PblCols &a, hipStream_t s);
+
 }  // namespace spdy

@@ -26,11 +26,8 @@ __global__ __launch_bounds__(COLUMN_BLOCK) void moist_columns_kernel(const Moist
     const long base = c.base;          // level k (1-based) of this column at base + (k - 1) * ncol
     auto at = [&](int r) { return base + (long)(kx - 1 - r) * ncol; };
 
-    // physical_constants.f90:22-26, humidity.f90:61-66, convection.f90:15-20, :46-49, large_scale_condensation.f90:24, :50-52;
-    // e0 is a double literal
+    // physical_constants.f90:22-26, convection.f90:15-20, :46-49, large_scale_condensation.f90:24, :50-52
     const double cp = kCp, alhc = F(2501.0f);
-    const double e0 = 6.108e-3, c1 = F(17.269f), c2 = F(21.875f);
-    const double t0 = F(273.16f), t1 = F(35.86f), t2 = F(7.66f);
     const double psmin = F(0.8f), rhbl = F(0.9f), rhil = F(0.7f), smf = F(0.8f), fqmax = 5.0;
     const double rdps = 2.0 / (1.0 - psmin), rlhc = 1.0 / alhc;
     const double rtlsc = 1.0 / (F(4.0f) * 3600.0), tfact = alhc / cp;
@@ -47,9 +44,7 @@ __global__ __launch_bounds__(COLUMN_BLOCK) void moist_columns_kernel(const Moist
             const double tg = a.tg[o], q = a.qg[o];
             qa[r] = q > 0.0 ? q : 0.0;                                 // max(qg, 0.0)
             se[r] = cp * tg + a.phig[o];
-            const double x = tg >= t0 ? c1 * (tg - t0) / (tg - t1) : c2 * (tg - t0) / (tg - t2);
-            const double e = e0 * exp(x);
-            qs[r] = 622.0 * e / (a.fsg[r] * psa - 0.378f * e);
+            qs[r] = get_qsat(tg, psa, a.fsg[r]);
             if (a.se) a.se[o] = se[r];
             if (a.qsat) a.qsat[o] = qs[r];
             if (a.rh) a.rh[o] = qa[r] / qs[r];

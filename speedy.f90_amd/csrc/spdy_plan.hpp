@@ -46,6 +46,8 @@ struct spdy_plan {
     double *out_grid = nullptr, *out_spec = nullptr;   // output path: (5kx+1) grids, (3kx+1) spectra (spdy_output_workspace)
     double *moist_grid = nullptr;     // moist physics from spectra: (3kx+1) grids t | q | phi | ln ps (spdy_moist_workspace)
     double *d_radzonal = nullptr;     // [5][il] zonal radiation forcing fsol | ozone | ozupp | zenit | stratz (spdy_radiation_set_date)
+    double *d_orog = nullptr;         // phis0 (ix,il) | forog (ix,il) | sqrt(coa(j)) [il] (spdy_surface_set_orography)
+    double *physics_ws = nullptr;     // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
     double *d_dmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

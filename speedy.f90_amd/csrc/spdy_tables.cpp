@@ -87,6 +87,22 @@ void make_physics(HostTables &t)
         t.lsc_dqmax[k] = kQsmax * sig2 * rtlsc;
         t.lsc_pfact[k] = t.dhs[k] * prg;
     }
+    // vertical_diffusion.f90:57-77, :80-81, :114-115.  dhs(kx)/3600.0 divides a double by a widened float32; (nl1 - 1)*3600.0 is
+    // a float32 product; trshc*cp and trvds*cp are double products of widened parameters
+    const int nl1 = kx - 1;
+    const double trshc = static_cast<double>(6.0f), trvdi = static_cast<double>(24.0f), trvds = static_cast<double>(6.0f);
+    const double rhgrad = static_cast<double>(0.5f);
+    const double cshc = t.dhs[kx - 1] / static_cast<double>(3600.0f);
+    const double cvdi = (t.sigh[nl1] - t.sigh[1]) / static_cast<double>(static_cast<float>(nl1 - 1) * 3600.0f);
+    const double fvdiq = cvdi / trvdi;
+    t.vd_scalars = {cshc, cvdi, cshc / trshc, cshc / (trshc * kCp), fvdiq, cvdi / (trvds * kCp)};
+    t.vd_rsig.assign(kx, 0.0); t.vd_rsig1.assign(kx, 0.0); t.vd_drh0.assign(kx, 0.0); t.vd_fvdiq2.assign(kx, 0.0);
+    for (int k = 0; k < kx; ++k) t.vd_rsig[k] = 1.0 / t.dhs[k];
+    for (int k = 0; k < nl1; ++k) {
+        t.vd_rsig1[k] = 1.0 / (1.0 - t.sigh[k + 1]);
+        t.vd_drh0[k] = rhgrad * (t.fsg[k + 1] - t.fsg[k]);
+        t.vd_fvdiq2[k] = fvdiq * t.sigh[k + 1];
+    }
 }
 
 // longwave_radiation.f90:197-220 radset.  (0.148 - 3.0e-6*(jtemp - 247)**2) is default real: the integer square is converted
@@ -156,7 +172,9 @@ void make_geometry(HostTables &t)
     t.dhs.assign(t.kx, 0.0); t.fsg.assign(t.kx, 0.0); t.dhsr.assign(t.kx, 0.0); t.fsgr.assign(t.kx, 0.0);
     t.xgeop1.assign(t.kx, 0.0); t.xgeop2.assign(t.kx, 0.0); t.corf.assign(t.kx, 0.0);
     t.tcorv.assign(t.kx, 0.0); t.qcorv.assign(t.kx, 0.0);
-    for (auto *v : {&t.sigl, &t.sigh, &t.grdsig, &t.grdscp, &t.wvi, &t.entr, &t.lsc_rhref, &t.lsc_dqmax, &t.lsc_pfact}) v->clear();
+    for (auto *v : {&t.sigl, &t.sigh, &t.grdsig, &t.grdscp, &t.wvi, &t.entr, &t.lsc_rhref, &t.lsc_dqmax, &t.lsc_pfact, &t.vd_scalars,
+                    &t.vd_rsig, &t.vd_rsig1, &t.vd_drh0, &t.vd_fvdiq2})
+        v->clear();
     t.sigma_ready = false;
     if (lev) {
         for (int k = 0; k <= t.kx; ++k) t.hsg[k] = static_cast<double>(lev[k]);
@@ -575,6 +593,25 @@ std::string HostTables::set_date(double ty)
     return "";
 }
 
+// surface_fluxes.f90:300-309: rhdrag = 1.0/(grav*hdrag); forog = 1.0 + rhdrag*(1.0 - exp(-max(phi0, 0.0)*rhdrag)), glibc exp as
+// the reference's build calls it
+std::string HostTables::set_orography(const double *phis0_in)
+{
+    if (!phis0_in) return "null phis0";
+    const size_t n = static_cast<size_t>(ix) * il;
+    for (size_t i = 0; i < n; ++i)
+        if (!(phis0_in[i] == phis0_in[i])) return "phis0 holds a NaN";
+    const double rhdrag = 1.0 / (kGrav * static_cast<double>(2000.0f));
+    phis0.assign(phis0_in, phis0_in + n);
+    forog.assign(n, 0.0);
+    for (size_t i = 0; i < n; ++i) {
+        const double ph = phis0[i] > 0.0 ? phis0[i] : 0.0;
+        forog[i] = 1.0 + rhdrag * (1.0 - std::exp(-ph * rhdrag));
+    }
+    orog_ready = true;
+    return "";
+}
+
 const double *HostTables::lookup(const std::string &name, int *count, std::vector<double> &scratch) const
 {
     struct Ent { const char *n; const std::vector<double> *v; };
@@ -589,10 +626,15 @@ const double *HostTables::lookup(const std::string &name, int *count, std::vecto
         {"xj", &xj}, {"dhsx", &dhsx}, {"elz", &elz}, {"xgeop1", &xgeop1}, {"xgeop2", &xgeop2}, {"corf", &corf},
         {"tcorv", &tcorv}, {"qcorv", &qcorv}, {"coriol", &coriol}, {"sigl", &sigl}, {"sigh", &sigh}, {"grdsig", &grdsig},
         {"grdscp", &grdscp}, {"wvi", &wvi}, {"entr", &entr}, {"fband", &fband},
+        {"vd_scalars", &vd_scalars}, {"vd_rsig", &vd_rsig}, {"vd_rsig1", &vd_rsig1}, {"vd_drh0", &vd_drh0},
+        {"vd_fvdiq2", &vd_fvdiq2}, {"phis0", &phis0}, {"forog", &forog},
         {"fsol", &fsol}, {"ozone", &ozone}, {"ozupp", &ozupp}, {"zenit", &zenit}, {"stratz", &stratz}};
     // the zonal radiation forcing before spdy_radiation_set_date: known, but empty
     for (const char *z : {"fsol", "ozone", "ozupp", "zenit", "stratz"})
         if (name == z && !date_ready) { *count = 0; scratch.assign(1, 0.0); return scratch.data(); }
+    // the orography tables before spdy_surface_set_orography likewise
+    for (const char *z : {"phis0", "forog"})
+        if (name == z && !orog_ready) { *count = 0; scratch.assign(1, 0.0); return scratch.data(); }
     for (const auto &e : ents)
         if (name == e.n) { *count = static_cast<int>(e.v->size()); return e.v->data(); }
     if (name == "ifac") {

@@ -47,6 +47,14 @@ struct HostTables {
     // and pfact = dhs*prg
     std::vector<double> sigl, sigh, grdsig, grdscp, wvi, entr, lsc_rhref, lsc_dqmax, lsc_pfact;
     double fm0 = 0.0;
+    // vertical_diffusion.f90:57-77 (valid when sigma_ready): vd_scalars = cshc cvdi fshcq fshcse fvdiq fvdise; vd_rsig[kx] =
+    // 1/dhs(k), vd_rsig1[kx] = 1/(1 - sigh(k)) (entry kx unused = 0); and per pair of levels k, k + 1 (index k-1; last 0) the
+    // vd_drh0 = rhgrad*(fsg(k+1) - fsg(k)) and vd_fvdiq2 = fvdiq*sigh(k) of :80-81 (k = kx - 1) and :114-115
+    std::vector<double> vd_scalars, vd_rsig, vd_rsig1, vd_drh0, vd_fvdiq2;
+    // surface_fluxes.f90:300-309 set_orog_land_sfc_drag at the surface geopotential set by set_orography (valid when
+    // orog_ready): phis0 and forog (ix, il), j = 0 southernmost
+    std::vector<double> phis0, forog;
+    bool orog_ready = false;
     // longwave_radiation.f90:197-220 radset: fband(100:400,4) column-major, entry (t - 100) + 301*(jb - 1)
     std::vector<double> fband;
     // shortwave_radiation.f90:238-329 get_zonal_average_fields + solar at the date set by set_date (valid when date_ready): one
@@ -64,6 +72,8 @@ struct HostTables {
     std::string build_implicit(double dt);
     // The zonal radiation forcing of the date tyear (fraction of the year, 0 = 1 Jan 0h).  Returns "" or an error text.
     std::string set_date(double tyear);
+    // Keeps the surface geopotential phis0[ix*il] and builds forog from it.  Returns "" or an error text.
+    std::string set_orography(const double *phis0_in);
     // Named lookup for spdy_get_table; nullptr if unknown. *count receives the length.
     const double *lookup(const std::string &name, int *count, std::vector<double> &scratch) const;
 };

@@ -42,6 +42,33 @@ module spdy_c
         type(c_ptr) :: tt_rsw = c_null_ptr, tt_rlw = c_null_ptr
     end type
 
+    !> spdy_sfc_boundary (include/spdy.h): per-column boundary fields of the surface fluxes, all required
+    type, bind(C) :: spdy_sfc_boundary
+        type(c_ptr) :: fmask = c_null_ptr, sst = c_null_ptr, stl = c_null_ptr, soilw = c_null_ptr
+        type(c_ptr) :: snowc = c_null_ptr, alb_l = c_null_ptr, alb_s = c_null_ptr
+    end type
+
+    !> spdy_sfc_out (include/spdy.h): optional outputs of the surface fluxes (c_null_ptr = not written)
+    type, bind(C) :: spdy_sfc_out
+        type(c_ptr) :: ustr = c_null_ptr, vstr = c_null_ptr, shf = c_null_ptr, evap = c_null_ptr, slru = c_null_ptr
+        type(c_ptr) :: hfluxn = c_null_ptr
+        type(c_ptr) :: tskin = c_null_ptr, u0 = c_null_ptr, v0 = c_null_ptr, t0 = c_null_ptr
+    end type
+
+    !> spdy_pbl_out (include/spdy.h): optional outputs of the boundary layer (c_null_ptr = not written)
+    type, bind(C) :: spdy_pbl_out
+        type(c_ptr) :: ut_pbl = c_null_ptr, vt_pbl = c_null_ptr, tt_pbl = c_null_ptr, qt_pbl = c_null_ptr
+    end type
+
+    !> spdy_column_physics_out (include/spdy.h): the optional outputs of every block of the chain, and ts / fsfcu
+    type, bind(C) :: spdy_column_physics_out
+        type(spdy_moist_out) :: moist
+        type(spdy_rad_out) :: rad
+        type(spdy_sfc_out) :: sfc
+        type(spdy_pbl_out) :: pbl
+        type(c_ptr) :: ts = c_null_ptr, fsfcu = c_null_ptr
+    end type
+
     interface
         function spdy_plan_create(trunc, ix, iy, kx, max_batch, device, plan) bind(C, name="spdy_plan_create") result(rc)
             import :: c_int, c_ptr
@@ -699,6 +726,42 @@ module spdy_c
             type(c_ptr), value :: plan, tg, pslg, ts, fsfcu, state, ttend
             integer(c_int), value :: nb
             type(spdy_rad_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_set_orography(plan, phis0) bind(C, name="spdy_surface_set_orography") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, phis0
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_fluxes_dev(plan, nb, ug, vg, tg, qg, phig, pslg, ssrd, slrd, bnd, ts, fsfcu, flux3, out) &
+                & bind(C, name="spdy_surface_fluxes_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_sfc_out
+            type(c_ptr), value :: plan, ug, vg, tg, qg, phig, pslg, ssrd, slrd, ts, fsfcu, flux3
+            integer(c_int), value :: nb
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_sfc_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_pbl_dev(plan, nb, qg, phig, pslg, se, rh, qsat, icnv, flux3, utend, vtend, ttend, qtend, out) &
+                & bind(C, name="spdy_pbl_dev") result(rc)
+            import :: c_int, c_ptr, spdy_pbl_out
+            type(c_ptr), value :: plan, qg, phig, pslg, se, rh, qsat, icnv, flux3, utend, vtend, ttend, qtend
+            integer(c_int), value :: nb
+            type(spdy_pbl_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_column_physics_workspace(plan) bind(C, name="spdy_column_physics_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int) :: rc
+        end function
+        function spdy_column_physics_dev(plan, nb, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend, &
+                & ttend, qtend, out) bind(C, name="spdy_column_physics_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_column_physics_out
+            type(c_ptr), value :: plan, ug, vg, tg, qg, phig, pslg, albsfc, rad_state, utend, vtend, ttend, qtend
+            integer(c_int), value :: nb, compute_sw
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_column_physics_out), intent(in) :: out
             integer(c_int) :: rc
         end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)

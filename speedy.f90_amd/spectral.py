@@ -68,6 +68,34 @@ RAD_2D = ("slrd", "slr", "olr")                                    # (ix,il) per
 RAD_3D = ("tt_rsw", "tt_rlw")                                      # (ix,il,kx) per state
 
 
+class SfcBoundary(ctypes.Structure):
+    """spdy_sfc_boundary (include/spdy.h): boundary fields of the surface fluxes, device pointers, all required."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("fmask", "sst", "stl", "soilw", "snowc", "alb_l", "alb_s")]
+
+
+class SfcOut(ctypes.Structure):
+    """spdy_sfc_out (include/spdy.h): optional outputs of the surface fluxes, device pointers or None."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("ustr", "vstr", "shf", "evap", "slru", "hfluxn", "tskin", "u0", "v0", "t0")]
+
+
+class PblOut(ctypes.Structure):
+    """spdy_pbl_out (include/spdy.h): optional outputs of the boundary layer, device pointers or None."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("ut_pbl", "vt_pbl", "tt_pbl", "qt_pbl")]
+
+
+class ColumnPhysicsOut(ctypes.Structure):
+    """spdy_column_physics_out (include/spdy.h): the optional outputs of every block of the chain, and ts / fsfcu."""
+    _fields_ = [("moist", MoistOut), ("rad", RadOut), ("sfc", SfcOut), ("pbl", PblOut), ("ts", ctypes.c_void_p),
+                ("fsfcu", ctypes.c_void_p)]
+
+
+SFC_BOUNDARY = tuple(f[0] for f in SfcBoundary._fields_)
+SFC_3 = ("ustr", "vstr", "shf", "evap", "slru")            # (ix,il,3) per state: land, sea, weighted
+SFC_2D = ("tskin", "u0", "v0", "t0")                       # (ix,il) per state
+PBL_2D = ("ut_pbl", "vt_pbl")                              # (ix,il) per state: level kx
+PBL_3D = ("tt_pbl", "qt_pbl")                              # (ix,il,kx) per state
+
+
 class Graph:
     """A captured sequence of device-resident calls (spdy_graph_* in include/spdy.h)."""
 
@@ -590,6 +618,146 @@ class Spectral:
         self._sync_stream()
         check(self.lib.spdy_radiation_up_dev(self.h, _nb(tg), *[self._dp(x) for x in (tg, pslg, ts, fsfcu, state, ttend)],
                                              ctypes.byref(_out_struct(RadOut, out))))
+
+    # ------------------------------------------------------------------ surface fluxes, boundary layer (physics.f90:169-170, :193-205)
+    def surface_set_orography(self, phis0):
+        """Surface geopotential phis0 [il, ix]: the plan keeps it and forog (set_orog_land_sfc_drag); on a device plan the upload
+        is ordered on the plan's stream."""
+        if self.device >= 0:
+            self._sync_stream()
+        a = np.ascontiguousarray(phis0, np.float64)
+        if a.shape != self.grid_shape:
+            raise ValueError("phis0 must be [il, ix]")
+        check(self.lib.spdy_surface_set_orography(self.h, _p(a)))
+
+    def _boundary(self, bnd):
+        return SfcBoundary(*[self._dp(bnd[n]) for n in SFC_BOUNDARY])
+
+    def surface_fluxes_dev(self, ug, vg, tg, qg, phig, pslg, ssrd, slrd, bnd, ts, fsfcu, flux3, out=None):
+        """get_surface_fluxes on nb gridded states: ug .. phig [nb,kx,il,ix] (or [kx,il,ix]); pslg, ssrd, slrd and the fields of
+        bnd (dict: SFC_BOUNDARY) [nb,il,ix]; writes ts, fsfcu [nb,il,ix] and flux3 [nb,4,il,ix] (ustr3 vstr3 shf3 evap3).  out: dict
+        of optional device outputs (SFC_3 [nb,3,il,ix], hfluxn [nb,2,il,ix], SFC_2D [nb,il,ix])."""
+        self._sync_stream()
+        b = self._boundary(bnd)
+        check(self.lib.spdy_surface_fluxes_dev(self.h, _nb(tg), *[self._dp(x) for x in (ug, vg, tg, qg, phig, pslg, ssrd, slrd)],
+                                               ctypes.byref(b), self._dp(ts), self._dp(fsfcu), self._dp(flux3),
+                                               ctypes.byref(_out_struct(SfcOut, out))))
+
+    def pbl_dev(self, qg, phig, pslg, se, rh, qsat, icnv, flux3, utend, vtend, ttend, qtend, out=None):
+        """get_vertical_diffusion_tend, the surface-flux tendencies and the four sums: qg, phig, se, rh, qsat [nb,kx,il,ix] (or
+        [kx,il,ix]), pslg, icnv (int32) [nb,il,ix], flux3 [nb,4,il,ix]; utend (level kx only), vtend, ttend, qtend in place.  out:
+        dict of optional device outputs (PBL_2D [nb,il,ix], PBL_3D like qg)."""
+        self._sync_stream()
+        check(self.lib.spdy_pbl_dev(self.h, _nb(qg), *[self._dp(x) for x in (qg, phig, pslg, se, rh, qsat, icnv, flux3, utend, vtend,
+                                                                            ttend, qtend)], ctypes.byref(_out_struct(PblOut, out))))
+
+    def column_physics_workspace(self):
+        check(self.lib.spdy_column_physics_workspace(self.h))
+
+    def column_physics_dev(self, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, state, utend, vtend, ttend, qtend, out=None):
+        """physics.f90:110-205 on nb gridded states: moist block, radiation down, surface fluxes, radiation up, boundary layer, the
+        intermediates in plan workspace.  out: dict with optional dicts "moist", "rad", "sfc", "pbl" (as the single calls take
+        them) and optional tensors "ts", "fsfcu"."""
+        self._sync_stream()
+        out = out or {}
+        o = ColumnPhysicsOut(_out_struct(MoistOut, out.get("moist")), _out_struct(RadOut, out.get("rad")),
+                             _out_struct(SfcOut, out.get("sfc")), _out_struct(PblOut, out.get("pbl")),
+                             None if out.get("ts") is None else self._dp(out["ts"]),
+                             None if out.get("fsfcu") is None else self._dp(out["fsfcu"]))
+        b = self._boundary(bnd)
+        check(self.lib.spdy_column_physics_dev(self.h, _nb(tg), 1 if compute_sw else 0, *[self._dp(x) for x in (ug, vg, tg, qg, phig,
+                                               pslg)], ctypes.byref(b), None if albsfc is None else self._dp(albsfc),
+                                               self._dp(state), *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+
+    def _grid_args(self, ins, names3, ref="tg"):
+        """ins (name -> array) as float64 arrays, shapes checked against the level stack ins[ref]: names3 are level stacks, the
+        others (ix,il) fields.  Returns (ins, the level stack's shape, its leading (batch) shape, nb)."""
+        ins = {k: np.ascontiguousarray(v, np.float64) for k, v in ins.items()}
+        grid3 = ins[ref].shape
+        if grid3[-3:] != (self.kx,) + self.grid_shape:
+            raise ValueError("%s must be [nb,] kx, il, ix" % ref)
+        lead = grid3[:-3]
+        for k, v in ins.items():
+            want = grid3 if k in names3 else lead + self.grid_shape
+            if v.shape != want:
+                raise ValueError("%s must have shape %s" % (k, want))
+        return ins, grid3, lead, int(np.prod(lead)) if lead else 1
+
+    def _sfc_results(self, lead):
+        res = {n: np.empty(lead + (3,) + self.grid_shape) for n in SFC_3}
+        res["hfluxn"] = np.empty(lead + (2,) + self.grid_shape)
+        res.update({n: np.empty(lead + self.grid_shape) for n in SFC_2D + ("ts", "fsfcu")})
+        res["flux3"] = np.empty(lead + (4,) + self.grid_shape)
+        return res
+
+    def surface_columns(self, ug, vg, tg, qg, phig, pslg, ssrd, slrd, bnd):
+        """NumPy convenience: spdy_surface_fluxes_dev on copies in plan-owned device memory.  bnd: dict of the SFC_BOUNDARY fields.
+        Returns a dict with ts, fsfcu, flux3 [nb,4,il,ix] and every optional output."""
+        ins = dict(ug=ug, vg=vg, tg=tg, qg=qg, phig=phig, pslg=pslg, ssrd=ssrd, slrd=slrd, **{n: bnd[n] for n in SFC_BOUNDARY})
+        ins, _, lead, nb = self._grid_args(ins, ("ug", "vg", "tg", "qg", "phig"))
+        res = self._sfc_results(lead)
+
+        def call(d):
+            b = SfcBoundary(*[d[n].value for n in SFC_BOUNDARY])
+            o = SfcOut(**{n: d[n].value for n in SFC_3 + ("hfluxn",) + SFC_2D})
+            check(self.lib.spdy_surface_fluxes_dev(self.h, nb, *[d[n] for n in ("ug", "vg", "tg", "qg", "phig", "pslg", "ssrd", "slrd")],
+                                                   ctypes.byref(b), d["ts"], d["fsfcu"], d["flux3"], ctypes.byref(o)))
+        return self._on_device(ins, res, call)
+
+    def pbl_columns(self, qg, phig, pslg, se, rh, qsat, icnv, flux3, utend, vtend, ttend, qtend):
+        """NumPy convenience: spdy_pbl_dev on copies in plan-owned device memory.  Returns a dict with the updated utend, vtend,
+        ttend, qtend and every optional output."""
+        names3 = ("qg", "phig", "se", "rh", "qsat", "utend", "vtend", "ttend", "qtend")
+        ins = dict(qg=qg, phig=phig, pslg=pslg, se=se, rh=rh, qsat=qsat, utend=utend, vtend=vtend, ttend=ttend, qtend=qtend)
+        ins, grid3, lead, nb = self._grid_args(ins, names3, "qg")
+        ins["icnv"] = np.ascontiguousarray(icnv, np.int32)
+        ins["flux3"] = np.ascontiguousarray(flux3, np.float64)
+        if ins["icnv"].shape != lead + self.grid_shape or ins["flux3"].shape != lead + (4,) + self.grid_shape:
+            raise ValueError("icnv must be [nb,] il, ix and flux3 [nb,] 4, il, ix")
+        res = {n: np.empty(grid3) for n in ("utend", "vtend", "ttend", "qtend") + PBL_3D}
+        res.update({n: np.empty(lead + self.grid_shape) for n in PBL_2D})
+
+        def call(d):
+            o = PblOut(**{n: d[n].value for n in PBL_2D + PBL_3D})
+            check(self.lib.spdy_pbl_dev(self.h, nb, *[d[n] for n in ("qg", "phig", "pslg", "se", "rh", "qsat", "icnv", "flux3", "utend",
+                                                                     "vtend", "ttend", "qtend")], ctypes.byref(o)))
+        return self._on_device(ins, res, call)
+
+    def column_physics(self, ug, vg, tg, qg, phig, pslg, bnd, albsfc, utend, vtend, ttend, qtend, compute_sw=True, state=None):
+        """NumPy convenience: spdy_column_physics_dev on copies in plan-owned device memory.  state: the radiation state to start
+        from (as returned under "state"); None starts a fresh one (then compute_sw must be set).  On calls without shortwave the
+        plan's workspace holds the ssrd of the last call with it.  Returns a dict with the updated tendencies, every optional
+        output of every block (those of the shortwave only with compute_sw) and the updated state."""
+        names3 = ("ug", "vg", "tg", "qg", "phig", "utend", "vtend", "ttend", "qtend")
+        ins = dict(ug=ug, vg=vg, tg=tg, qg=qg, phig=phig, pslg=pslg, utend=utend, vtend=vtend, ttend=ttend, qtend=qtend,
+                   **{n: bnd[n] for n in SFC_BOUNDARY})
+        if compute_sw:
+            ins["albsfc"] = albsfc
+        ins, grid3, lead, nb = self._grid_args(ins, names3)
+        nst = self.radiation_state_size() * nb
+        if state is None and not compute_sw:
+            raise ValueError("the first call on a radiation state must have compute_sw set")
+        ins["state"] = np.zeros(nst) if state is None else np.ascontiguousarray(state, np.float64)
+        if ins["state"].shape != (nst,):
+            raise ValueError("state must hold %d doubles" % nst)
+        rad = tuple(n for n in RAD_2D + ("tt_rlw",) + ((RAD_SW_2D + ("tt_rsw",)) if compute_sw else ()) if n != "ssrd")
+        res = self._sfc_results(lead)
+        del res["flux3"]
+        res.update({n: np.empty(grid3) for n in ("utend", "vtend", "ttend", "qtend") + MOIST_3D + PBL_3D})
+        res["state"] = np.empty(nst)
+        res.update({n: np.empty(lead + self.grid_shape, np.int32 if n in ("iptop", "icnv") else np.float64) for n in MOIST_2D + PBL_2D})
+        res.update({n: np.empty(grid3 if n in RAD_3D else lead + self.grid_shape, np.int32 if n == "icltop" else np.float64)
+                    for n in rad})
+
+        def call(d):
+            o = ColumnPhysicsOut(MoistOut(**{n: d[n].value for n in MOIST_2D + MOIST_3D}), RadOut(**{n: d[n].value for n in rad}),
+                                 SfcOut(**{n: d[n].value for n in SFC_3 + ("hfluxn",) + SFC_2D}),
+                                 PblOut(**{n: d[n].value for n in PBL_2D + PBL_3D}), d["ts"].value, d["fsfcu"].value)
+            b = SfcBoundary(*[d[n].value for n in SFC_BOUNDARY])
+            check(self.lib.spdy_column_physics_dev(self.h, nb, 1 if compute_sw else 0, *[d[n] for n in ("ug", "vg", "tg", "qg", "phig",
+                                                   "pslg")], ctypes.byref(b), d.get("albsfc"), d["state"],
+                                                   *[d[n] for n in ("utend", "vtend", "ttend", "qtend")], ctypes.byref(o)))
+        return self._on_device(ins, res, call)
 
     def radiation_columns(self, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, ts, fsfcu, ttend, compute_sw=True,
                           state=None):
