@@ -132,6 +132,8 @@ int spdy_plan_set_fused(spdy_plan *plan, int mode);
  *   "t30_part", "t30_split", "t63_split", "t63_stage", "t63_derive"   0 = the form named by $SPDY_T30_NOPART, $SPDY_T30_NOSPLIT,
  *                       $SPDY_T63_NOSPLIT, $SPDY_T63_NOSTAGE, $SPDY_T63_NODERIVE; 1 = the default form
  *   "t63_np2_from" >= 1, "wt_min_mb" >= 0                              as $SPDY_T63_NP2_FROM, $SPDY_WT_MIN_MB
+ *   "physics_fused"     the column-physics chain as ONE launch (1) or as its five calls (0), same bits either way; any other
+ *                       value is SPDY_ERR_ARG.  Never set: spdy_column_physics_dev makes the five calls, spdy_physics_dev the one launch
  * Not while a graph capture is open (SPDY_ERR_STATE); captured graphs keep the forms they were captured with.       */
 int spdy_plan_set_option(spdy_plan *plan, const char *name, int value);
 int spdy_plan_get_profile(spdy_plan *plan, double *ms, int *launches);
@@ -442,10 +444,10 @@ int spdy_output_batch_dev(spdy_plan *plan, const double *vor, const double *div,
                           const double *ps, float *u_out, float *v_out, float *t_out, float *q_out, float *phi_out, float *ps_out);
 
 /* Column physics (spdy_moist_columns_dev, spdy_moist_physics_dev, spdy_radiation_down_dev, spdy_radiation_up_dev,
- * spdy_surface_fluxes_dev, spdy_pbl_dev, spdy_column_physics_dev) checks its arguments in one order, and the first check that
+ * spdy_surface_fluxes_dev, spdy_pbl_dev, spdy_column_physics_dev, spdy_physics_dev) checks its arguments in one order, and the first check that
  * fails gives the code: a NULL plan, kx outside [5, 16] and nb outside [0, max_batch] SPDY_ERR_ARG; no sigma levels, then
  * (radiation, the chain) no date, then (surface fluxes, the chain) no orography, SPDY_ERR_STATE; a NULL required pointer
- * SPDY_ERR_ARG; then the call's own conditions (spdy_moist_physics_dev: max_batch); a host-only plan SPDY_ERR_NO_DEVICE last. */
+ * SPDY_ERR_ARG; then the call's own conditions (spdy_moist_physics_dev, spdy_physics_dev: max_batch); a host-only plan SPDY_ERR_NO_DEVICE last. */
 
 /* ---- column physics: the precipitation block of get_physical_tendencies (physics.f90:110-138) ----------------------------
  * Replaces, on the device, the thermodynamic fields (physics.f90:110-115: psg = exp(pslg), rps, qg = max(qg, 0), se = cp*tg +
@@ -577,6 +579,24 @@ int spdy_column_physics_dev(spdy_plan *plan, int nb, int compute_sw, const doubl
                             const double *qg, const double *phig, const double *pslg, const spdy_sfc_boundary *bnd,
                             const double *albsfc, double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
                             const spdy_column_physics_out *out);
+/* The chain as ONE launch (spdy_plan_set_option "physics_fused"; csrc/spdy_column_chain.hip): one thread runs the six blocks for
+ * its column with the same instructions as the five calls, so the results are the same bits.  precnv, precls, iptop, icnv, slrd,
+ * ts, fsfcu and the four averaged fluxes then pass from block to block in registers and are stored only where a member of `out`
+ * asks for them; se, rh, qsat go through the workspace as before, and ssrd and the radiation state are written as before.
+ *
+ * spdy_physics_dev is what get_grid_point_tendencies calls (tendencies.f90:203-206; physics.f90:94-205): ONE model state from the
+ * spectra of time level 1 -- vor, div, t, q = tr(:,:,:,1,1), phi (spdy_geopotential_dev of t) (mx,nx,kx) complex, ps (mx,nx).
+ * ONE inverse launch (the segmented inverse path: kx (vor, div) pairs through uvspec with kcos 2, and the 3 kx + 1 plain fields t,
+ * q, phi, ps with kcos 1; physics.f90:94-104) into plan workspace, then the chain on those grids -- by default as one launch,
+ * with "physics_fused" 0 as the five calls.  utend, vtend, ttend, qtend are the operands spdy_grid_tendencies_dev documents
+ * (u_out[0:kx], v_out[0:kx], plain_out[kx:2kx], plain_out[2kx:3kx]), updated in place; bnd, albsfc, rad_state and out as for
+ * spdy_column_physics_dev with nb = 1.  max_batch >= 3 kx + 1 (SPDY_ERR_ARG otherwise).  spdy_physics_workspace allocates the
+ * workspace ((5 kx + 1) grids and one state's chain workspace of (3 kx + 12) grids) ahead of time, e.g. before a graph capture;
+ * with it spdy_physics_dev allocates nothing and can be captured.                                                              */
+int spdy_physics_workspace(spdy_plan *plan);
+int spdy_physics_dev(spdy_plan *plan, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
+                     const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
+                     double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out);
 
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,

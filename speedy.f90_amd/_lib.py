@@ -118,6 +118,8 @@ SIGNATURES = {
     "spdy_pbl_dev": [c_void_p, c_int] + [c_void_p] * 13,
     "spdy_column_physics_workspace": [c_void_p],
     "spdy_column_physics_dev": [c_void_p, c_int, c_int] + [c_void_p] * 14,
+    "spdy_physics_workspace": [c_void_p],
+    "spdy_physics_dev": [c_void_p, c_int] + [c_void_p] * 14,
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

@@ -933,6 +933,7 @@ int spdy_plan_set_option(spdy_plan *p, const char *name, int value)
     else if (n == "t63_derive") p->t63_derive = value != 0;
     else if (n == "t63_np2_from") { if (value < 1) return fail(SPDY_ERR_ARG, "t63_np2_from must be >= 1"); lo.t63_np2_from = value; }
     else if (n == "wt_min_mb") { if (value < 0) return fail(SPDY_ERR_ARG, "wt_min_mb must be >= 0"); lo.wt_min_mb = value; }
+    else if (n == "physics_fused") { if (value != 0 && value != 1) return fail(SPDY_ERR_ARG, "physics_fused must be 0 or 1"); p->physics_fused = value; }
     else return fail(SPDY_ERR_ARG, "unknown launch option '%s'", name);
     return SPDY_OK;
 }

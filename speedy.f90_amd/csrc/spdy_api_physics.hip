@@ -1,6 +1,7 @@
 // C ABI of the column physics (include/spdy.h, "column physics"): the precipitation block (physics.f90:110-138), the
 // radiation schemes (physics.f90:146-166 and :180-186), the surface fluxes (:169-170), the boundary layer (:193-205) and the
-// whole chain.  Kernels: csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip.
+// whole chain, on gridded states and from spectra.  Kernels: csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip,
+// csrc/spdy_column_chain.hip.
 #include <cmath>
 #include <cstring>
 
@@ -138,6 +139,53 @@ spdy::PblCols pbl_cols(const spdy_plan *p, int nb, const double *qg, const doubl
 bool boundary_ok(const spdy_sfc_boundary *b)
 {
     return b && b->fmask && b->sst && b->stl && b->soilw && b->snowc && b->alb_l && b->alb_s;
+}
+
+// physics.f90:110-205 on nb gridded states, arguments checked: the five calls, or (fused) the one-launch kernel.  w is the chain's
+// workspace of (3 kx + 12) fields, each g doubles long (g >= nb grids).
+int column_chain(spdy_plan *p, bool fused, int nb, int compute_sw, const double *ug, const double *vg, const double *tg,
+                 const double *qg, const double *phig, const double *pslg, const spdy_sfc_boundary *bnd, const double *albsfc,
+                 double *rad_state, double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out,
+                 double *w, size_t g)
+{
+    const size_t L = (size_t)p->tab.kx * g;
+    double *w2 = w + 3 * L;
+    // the caller's optional outputs take the place of the workspace where both exist.  ssrd is written by shortwave calls only
+    // and read by every call (the reference holds it in get_physical_tendencies): it stays where the last shortwave call put it
+    spdy_moist_out mo{};
+    spdy_rad_out ro{};
+    spdy_sfc_out so{};
+    double *ts = nullptr, *fsfcu = nullptr;
+    if (out) { mo = out->moist; ro = out->rad; so = out->sfc; ts = out->ts; fsfcu = out->fsfcu; }
+    auto pick = [](auto *&dst, auto *ws) { if (!dst) dst = ws; };
+    pick(mo.se, w); pick(mo.rh, w + L); pick(mo.qsat, w + 2 * L);
+    pick(ro.ssrd, w2 + 2 * g);
+    const spdy_pbl_out *po = out ? &out->pbl : nullptr;
+    if (fused) {
+        // one launch: what only the next block reads stays in registers and is stored only where the caller asked for it
+        if (!nb) return SPDY_OK;
+        spdy::ChainCols c{};
+        c.nb = nb; c.ncol = p->tab.ix * p->tab.il; c.kx = p->tab.kx;
+        c.moist = moist_cols(p, nb, tg, qg, phig, pslg, ttend, qtend, &mo);
+        c.rad = rad_cols(p, nb, tg, qg, phig, pslg, ttend, rad_state, &ro);
+        c.rad.compute_sw = compute_sw ? 1 : 0;
+        c.rad.rh = mo.rh; c.rad.fmask = bnd->fmask; c.rad.albsfc = albsfc;
+        c.sfc = sfc_cols(p, nb, ug, vg, tg, qg, phig, pslg, nullptr, nullptr, bnd, ts, fsfcu, nullptr, &so);
+        c.pbl = pbl_cols(p, nb, qg, phig, pslg, mo.se, mo.rh, mo.qsat, nullptr, nullptr, utend, vtend, ttend, qtend, po);
+        KERNEL(spdy::launch_column_chain(c, p->stream));
+        return SPDY_OK;
+    }
+    pick(mo.precnv, w2); pick(mo.precls, w2 + g); pick(ro.slrd, w2 + 3 * g);
+    pick(ts, w2 + 4 * g); pick(fsfcu, w2 + 5 * g);
+    double *flux3 = w2 + 6 * g;
+    pick(mo.iptop, reinterpret_cast<int *>(w2 + 10 * g)); pick(mo.icnv, reinterpret_cast<int *>(w2 + 11 * g));
+    spdy_rad_surface rs{bnd ? bnd->fmask : nullptr, albsfc};
+    RC(spdy_moist_columns_dev(p, nb, tg, qg, phig, pslg, ttend, qtend, &mo));
+    RC(spdy_radiation_down_dev(p, nb, compute_sw, tg, qg, phig, pslg, mo.rh, mo.precnv, mo.precls, mo.iptop, &rs, rad_state, &ro));
+    RC(spdy_surface_fluxes_dev(p, nb, ug, vg, tg, qg, phig, pslg, ro.ssrd, ro.slrd, bnd, ts, fsfcu, flux3, &so));
+    RC(spdy_radiation_up_dev(p, nb, tg, pslg, ts, fsfcu, rad_state, ttend, &ro));
+    RC(spdy_pbl_dev(p, nb, qg, phig, pslg, mo.se, mo.rh, mo.qsat, mo.icnv, flux3, utend, vtend, ttend, qtend, po));
+    return SPDY_OK;
 }
 }  // namespace
 
@@ -314,30 +362,47 @@ int spdy_column_physics_dev(spdy_plan *p, int nb, int compute_sw, const double *
     RC(column_args(p, "column physics", nb, true, !nb || ok, true));
     NEED_DEVICE(p);
     RC(spdy_column_physics_workspace(p));
-    // the intermediates, each max_batch states long so that a field's place does not depend on nb
-    const size_t g = grid_elems(p) * p->max_batch, L = (size_t)p->tab.kx * g;
-    double *w = p->physics_ws, *w2 = w + 3 * L;
-    // the caller's optional outputs take the place of the workspace where both exist.  ssrd is written by shortwave calls only
-    // and read by every call (the reference holds it in get_physical_tendencies): it stays where the last shortwave call put it
-    spdy_moist_out mo{};
-    spdy_rad_out ro{};
-    spdy_sfc_out so{};
-    double *ts = nullptr, *fsfcu = nullptr;
-    if (out) { mo = out->moist; ro = out->rad; so = out->sfc; ts = out->ts; fsfcu = out->fsfcu; }
-    auto pick = [](auto *&dst, auto *ws) { if (!dst) dst = ws; };
-    pick(mo.se, w); pick(mo.rh, w + L); pick(mo.qsat, w + 2 * L);
-    pick(mo.precnv, w2); pick(mo.precls, w2 + g); pick(ro.ssrd, w2 + 2 * g); pick(ro.slrd, w2 + 3 * g);
-    pick(ts, w2 + 4 * g); pick(fsfcu, w2 + 5 * g);
-    double *flux3 = w2 + 6 * g;
-    pick(mo.iptop, reinterpret_cast<int *>(w2 + 10 * g)); pick(mo.icnv, reinterpret_cast<int *>(w2 + 11 * g));
-    spdy_rad_surface rs{bnd ? bnd->fmask : nullptr, albsfc};
-    RC(spdy_moist_columns_dev(p, nb, tg, qg, phig, pslg, ttend, qtend, &mo));
-    RC(spdy_radiation_down_dev(p, nb, compute_sw, tg, qg, phig, pslg, mo.rh, mo.precnv, mo.precls, mo.iptop, &rs, rad_state, &ro));
-    RC(spdy_surface_fluxes_dev(p, nb, ug, vg, tg, qg, phig, pslg, ro.ssrd, ro.slrd, bnd, ts, fsfcu, flux3, &so));
-    RC(spdy_radiation_up_dev(p, nb, tg, pslg, ts, fsfcu, rad_state, ttend, &ro));
-    RC(spdy_pbl_dev(p, nb, qg, phig, pslg, mo.se, mo.rh, mo.qsat, mo.icnv, flux3, utend, vtend, ttend, qtend,
-                    out ? &out->pbl : nullptr));
+    // the workspace fields are each max_batch states long, so that a field's place does not depend on nb
+    return column_chain(p, p->physics_fused == 1, nb, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend,
+                        ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch);
+}
+
+/* ---------------------------------------------------------------- one state's physics from its spectra (physics.f90:94-205) */
+int spdy_physics_workspace(spdy_plan *p)
+{
+    NEED_PLAN(p);
+    RC(check_kx(p, "physics"));
+    NEED_DEVICE(p);
+    if (p->physics_grid) return SPDY_OK;
+    NOT_CAPTURING(p, "allocating the physics workspace (call spdy_physics_workspace before the capture)");
+    // the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
+    RC(ensure_four(p));
+    // 5 kx + 1 grids u | v | t | q | phi | ln ps, then one state's chain workspace (3 kx + 12 grids)
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * sizeof(double), &ptr));
+    p->physics_grid = static_cast<double *>(ptr);
     return SPDY_OK;
+}
+
+int spdy_physics_dev(spdy_plan *p, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
+                     const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
+                     double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out)
+{
+    const bool ok = vor && div && t && q && phi && ps && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
+                    vtend && ttend && qtend;
+    RC(column_args(p, "physics", 1, true, ok, true));
+    const int kx = p->tab.kx;
+    if (p->max_batch < 3 * kx + 1) return fail(SPDY_ERR_ARG, "max_batch must be >= 3*kx+1 for the physics from spectra");
+    NEED_DEVICE(p);
+    RC(spdy_physics_workspace(p));
+    // physics.f90:94-104: ONE inverse launch -- kx (vor, div) pairs through uvspec with kcos 2, t, q, phi (kx each) and ps with kcos 1
+    const size_t L = (size_t)kx * grid_elems(p);
+    double *g = p->physics_grid;
+    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{kx, t}, {kx, q}, {kx, phi}, {1, ps}};
+    RC(spdy_inverse_batch_segs_dev(p, kx, vor, div, g, g + L, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, g + 2 * L, 0, nullptr,
+                                   nullptr, nullptr, 2));
+    return column_chain(p, p->physics_fused != 0, 1, compute_sw, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, g + 5 * L, bnd, albsfc,
+                        rad_state, utend, vtend, ttend, qtend, out, g + 5 * L + grid_elems(p), grid_elems(p));
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // Launch and addressing layer of the column-physics kernels (csrc/spdy_physics.hip, csrc/spdy_radiation.hip,
-// csrc/spdy_surface.hip), and the one device function they share (get_qsat).
+// csrc/spdy_surface.hip, csrc/spdy_column_chain.hip), the one device function they share (get_qsat), and what one block of the
+// chain hands to a later one per column.
 //
 // One thread per (state, column): nb * ncol threads in blocks of COLUMN_BLOCK, threads with consecutive longitude in
 // consecutive lanes, so every level load and store is one coalesced access per wave.  Each kernel comes as <8> and <16>:
@@ -46,6 +47,23 @@ struct Column {
         base = b * ncol * kx + col;
     }
 };
+
+// A kernel's by-value argument struct (its ONE argument) where the launch put it: at the start of the kernarg segment, in the
+// constant address space.  The schemes are device functions that take their arguments by reference; handed the kernel's own
+// parameter they would read a private copy of it, which the compiler splits into scalars that are all loaded at the kernel's
+// entry (every level table: hundreds of SGPRs, spilled).  Read in place each table entry is a scalar load where it is used, as
+// it is in a kernel that names its parameter directly.  The device functions are templates on the argument type for this.
+#define SPDY_KERNARG __attribute__((address_space(4)))
+template <class Args>
+__device__ __forceinline__ const SPDY_KERNARG Args &kernel_args()
+{
+    return *(const SPDY_KERNARG Args *)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+// What a block hands to the later blocks of the chain, per column.  The one-launch chain keeps these in registers; the kernels of
+// the single blocks store them (where the caller gave a place) and the next kernel loads them.
+struct MoistHand { double precnv, precls; int iptop, icnv; };       // iptop after condensation, icnv before it
+struct SfcHand { double ts, fsfcu, flux3[4]; };                     // flux3: ustr3 vstr3 shf3 evap3
 
 // The launch of a column kernel whose arguments `a` have nb, ncol and kx: k8 for kx <= 8, k16 for kx <= COLUMN_KMAX.
 template <class Args>

@@ -341,4 +341,18 @@ struct PblCols {
 };
 hipError_t launch_pbl(const PblCols &a, hipStream_t s);
 
+// The whole chain in one launch (csrc/spdy_column_chain.hip): moist, shortwave (rad.compute_sw), longwave down, surface fluxes,
+// longwave up, boundary layer for each column, in the reference's order.  The four argument sets are those of the five calls
+// with one difference: precnv, precls, iptop, icnv, slrd, ts, fsfcu and flux3 pass from block to block in registers, so their
+// OUTPUT pointers (moist.*, rad.slrd, sfc.ts / fsfcu / flux3) may be null = not stored, and the matching input pointers are not
+// read.  se, rh, qsat and ssrd are read back from where moist.* / rad.ssrd put them, so those must be set.
+struct ChainCols {
+    int nb, ncol, kx;                                // as in each of the four
+    MoistCols moist;
+    RadCols rad;
+    SfcCols sfc;
+    PblCols pbl;
+};
+hipError_t launch_column_chain(const ChainCols &a, hipStream_t s);
+
 }  // namespace spdy

@@ -48,6 +48,9 @@ struct spdy_plan {
     double *d_radzonal = nullptr;     // [5][il] zonal radiation forcing fsol | ozone | ozupp | zenit | stratz (spdy_radiation_set_date)
     double *d_orog = nullptr;         // phis0 (ix,il) | forog (ix,il) | sqrt(coa(j)) [il] (spdy_surface_set_orography)
     double *physics_ws = nullptr;     // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
+    double *physics_grid = nullptr;   // physics from spectra: (5kx+1) grids u | v | t | q | phi | ln ps, then one state's chain workspace
+                                      // of (3kx+12) grids (spdy_physics_workspace)
+    int physics_fused = -1;           // column physics in one launch: -1 unset (spdy_physics_dev only), 0 never, 1 always (spdy_plan_set_option)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
     double *d_dmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

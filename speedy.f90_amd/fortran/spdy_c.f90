@@ -764,6 +764,20 @@ module spdy_c
             type(spdy_column_physics_out), intent(in) :: out
             integer(c_int) :: rc
         end function
+        function spdy_physics_workspace(plan) bind(C, name="spdy_physics_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int) :: rc
+        end function
+        function spdy_physics_dev(plan, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, qtend, &
+                & out) bind(C, name="spdy_physics_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_column_physics_out
+            type(c_ptr), value :: plan, vor, div, t, q, phi, ps, albsfc, rad_state, utend, vtend, ttend, qtend
+            integer(c_int), value :: compute_sw
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_column_physics_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: plan

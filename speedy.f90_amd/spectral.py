@@ -659,15 +659,32 @@ class Spectral:
         intermediates in plan workspace.  out: dict with optional dicts "moist", "rad", "sfc", "pbl" (as the single calls take
         them) and optional tensors "ts", "fsfcu"."""
         self._sync_stream()
-        out = out or {}
-        o = ColumnPhysicsOut(_out_struct(MoistOut, out.get("moist")), _out_struct(RadOut, out.get("rad")),
-                             _out_struct(SfcOut, out.get("sfc")), _out_struct(PblOut, out.get("pbl")),
-                             None if out.get("ts") is None else self._dp(out["ts"]),
-                             None if out.get("fsfcu") is None else self._dp(out["fsfcu"]))
+        o = self._column_physics_out(out)
         b = self._boundary(bnd)
         check(self.lib.spdy_column_physics_dev(self.h, _nb(tg), 1 if compute_sw else 0, *[self._dp(x) for x in (ug, vg, tg, qg, phig,
                                                pslg)], ctypes.byref(b), None if albsfc is None else self._dp(albsfc),
                                                self._dp(state), *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+
+    def _column_physics_out(self, out):
+        out = out or {}
+        return ColumnPhysicsOut(_out_struct(MoistOut, out.get("moist")), _out_struct(RadOut, out.get("rad")),
+                                _out_struct(SfcOut, out.get("sfc")), _out_struct(PblOut, out.get("pbl")),
+                                None if out.get("ts") is None else self._dp(out["ts"]),
+                                None if out.get("fsfcu") is None else self._dp(out["fsfcu"]))
+
+    def physics_workspace(self):
+        check(self.lib.spdy_physics_workspace(self.h))
+
+    def physics_dev(self, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, state, utend, vtend, ttend, qtend, out=None):
+        """physics.f90:94-205 on one state from its spectra (time level 1: vor, div, t, q, phi [kx,nx,mx], ps [nx,mx] complex128):
+        one inverse launch into plan workspace, then the column physics (one launch, or the five calls with the plan option
+        "physics_fused" 0).  utend, vtend, ttend, qtend [kx,il,ix] in place; bnd, albsfc, state and out as column_physics_dev."""
+        self._sync_stream()
+        o = self._column_physics_out(out)
+        b = self._boundary(bnd)
+        check(self.lib.spdy_physics_dev(self.h, 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
+                                        ctypes.byref(b), None if albsfc is None else self._dp(albsfc), self._dp(state),
+                                        *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
 
     def _grid_args(self, ins, names3, ref="tg"):
         """ins (name -> array) as float64 arrays, shapes checked against the level stack ins[ref]: names3 are level stacks, the

@@ -1,0 +1,177 @@
+"""The whole column physics inside a time step: the reference side of tests/test_gpu_physics_step.py.
+
+get_physical_tendencies (physics.f90:94-205) on the spectra of time level 1: the oracle supplies uvspec + spec_to_grid(., 2) of
+(vor, div), spec_to_grid(., 1) of t, q, phi, ps and the geopotential; the blocks are the NumPy restatements (surface.chain, pinned to
+the flang-built reference by tests/golden/ref_surface.npz).  The state is moist.state(o, dynstep.state(sp, seed), seed2); the
+boundary fields are drawn per column around the lowest-level grid temperature of that state, as surface._draw draws them.
+
+Columns of a transformed state cannot be redrawn one by one, so the committed SEEDS are those for which every decision margin the
+chain reports is >= MIN_MARGIN in every column on every step of the tests (found by running this module's reference side on the
+CPU: tests/test_physics_step_cpu.py repeats that for the first step).  Boundary values are per-column inputs: a column whose
+SURFACE decisions are too close gets new ones from the next stream."""
+import numpy as np
+
+import moist
+import radiation
+import surface
+import synth
+from dynstep import state as dyn_state
+
+MIN_MARGIN = surface.MIN_MARGIN
+ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
+# tag -> (dynstep.state seed, moist.state seed, boundary seed)
+SEEDS = {"t30": (8000, 5150, 31000), "t63k16": (8000, 5150, 31000)}
+# The seeded state is not a balanced atmosphere: with the whole physics in it, three consecutive steps stay finite only with
+# a short step (T30 L8: 2400 s and 900 s overflow on the third step, T63 L16: 300 s and 120 s; found on the CPU with this module's reference side)
+DT = {"t30": 300.0, "t63k16": 50.0}
+
+
+def grids_of(o, st):
+    """physics.f90:94-104 with the oracle: ug, vg, tg, qg, phig [kx, il, ix] and pslg [il, ix] of time level 1"""
+    kx = o.kx
+    phi = o.geopotential(st["t"][0], st["phis"])
+    uv = [o.uvspec(st["vor"][0, k], st["div"][0, k]) for k in range(kx)]
+    ug = np.stack([o.spec_to_grid(u, 2) for u, _ in uv])
+    vg = np.stack([o.spec_to_grid(v, 2) for _, v in uv])
+    tg, qg, phig = (np.stack([o.spec_to_grid(a[k], 1) for k in range(kx)]) for a in (st["t"][0], st["tr"][0], phi))
+    return {"ug": ug, "vg": vg, "tg": tg, "qg": qg, "phig": phig, "pslg": o.spec_to_grid(st["ps"][0], 1)}
+
+
+def draw_boundary(tlow, seed):
+    """fmask, albsfc (radiation._draw's recipe) and the surface boundary fields (surface._draw's) around tlow [ncol]"""
+    n = tlow.size
+    u = synth.splitmix64(seed, n * 11).reshape(11, n)
+    return {"fmask": np.where(u[0] < 1 / 3, 0.0, np.where(u[0] < 2 / 3, 1.0, u[1])), "albsfc": 0.07 + 0.6 * u[2],
+            "sst": tlow + 24.0 * u[3] - 8.0, "stl": tlow + 16.0 * u[4] - 8.0, "soilw": np.where(u[5] < 0.25, 0.0, u[6]),
+            "snowc": np.where(u[7] < 0.5, 0.0, u[8]), "alb_l": 0.1 + 0.5 * u[9], "alb_s": 0.07 + 0.5 * u[10]}
+
+
+def columns_of(g, bnd, phis0, ut, vt, tt, qt):
+    """surface.chain's column dict from grids [kx, il, ix] / [il, ix] and per-column boundary fields"""
+    kx = g["tg"].shape[0]
+    c = {n: np.ascontiguousarray(g[n]).reshape(kx, -1) for n in ("ug", "vg", "tg", "qg", "phig")}
+    c["pslg"] = g["pslg"].reshape(-1)
+    c.update(utend=ut.reshape(kx, -1), vtend=vt.reshape(kx, -1), ttend=tt.reshape(kx, -1), qtend=qt.reshape(kx, -1))
+    c.update(bnd)
+    c["phis0"] = phis0.reshape(-1)
+    return c
+
+
+class Case:
+    """One resolution's plan-independent reference data: tables, state, orography, zonal forcing, boundary fields."""
+
+    def __init__(self, tag, sp, o, date=0):
+        s1, s2, sb = SEEDS[tag]
+        self.tag, self.o = tag, o
+        self.kx, self.il, self.ix = o.kx, o.il, o.ix
+        self.tab = moist.tables(moist.HSG[self.kx])
+        self.st = moist.state(o, dyn_state(sp, s1), s2)
+        self.phis0 = o.spec_to_grid(self.st["phis"], 1)
+        self.sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, self.il, self.ix)
+        self.set_date(sp, date)
+        g = grids_of(o, self.st)
+        zero = np.zeros((self.kx, self.il, self.ix))
+        self.bnd = draw_boundary(g["tg"][-1].reshape(-1), sb)
+        for attempt in range(1, 50):          # boundary values only: the surface scheme's own decisions
+            r, _ = surface.chain(self.tab, columns_of(g, self.bnd, self.phis0, zero, zero, zero, zero), self.zon, self.sqcoa)
+            bad = np.nonzero(r["sfc"]["margin"] < MIN_MARGIN)[0]
+            if bad.size == 0:
+                break
+            new = draw_boundary(g["tg"][-1].reshape(-1), sb + 7919 * attempt)
+            for k in self.bnd:
+                self.bnd[k][bad] = new[k][bad]
+        else:
+            raise RuntimeError("could not draw boundary values clear of ties")
+
+    def set_date(self, sp, date):
+        """the zonal forcing of radiation.DATES[date] from the plan's tables (spdy_radiation_set_date on sp)"""
+        sp.radiation_set_date(radiation.DATES[date])
+        self.zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, self.il, self.ix)
+
+    def physics(self, st, compute_sw, rad_state, ut, vt, tt, qt, bnd=None):
+        """get_physical_tendencies on st: ut .. qt [kx, il, ix] updated in place; returns surface.chain's outputs (+ "grids")"""
+        g = grids_of(self.o, st)
+        c = columns_of(g, bnd or self.bnd, self.phis0, ut, vt, tt, qt)
+        r, _ = surface.chain(self.tab, c, self.zon, self.sqcoa, compute_sw, rad_state)
+        shp = ut.shape
+        for a, n in ((ut, "utend"), (vt, "vtend"), (tt, "ttend"), (qt, "qtend")):
+            a[...] = r["pbl"][n].reshape(shp)
+        r["grids"] = g
+        return r
+
+    def hook(self, compute_sw, rad_state, record, bnd=None):
+        """physics= hook of dynstep.oracle_dynamics_step"""
+        def hook(o, st, ut, vt, tt, qt):
+            record.clear()
+            record.update(self.physics(st, compute_sw, rad_state, ut, vt, tt, qt, bnd))
+        return hook
+
+
+def check_coverage(r, label=""):
+    """The margins first, then that the state exercises the physics; prints the branch counts."""
+    assert float(r["margin"].min()) >= MIN_MARGIN, (label, float(r["margin"].min()), int(np.argmin(r["margin"])))
+    mb = r["moist"]["branch"]
+    sb = {k: int(v.sum()) for k, v in r["sfc"]["branch_cols"].items()}
+    print("[physics branches %s] moist %s; surface %s" % (label, mb, sb))
+    assert 0 < mb["no_conv"] < mb["columns"]                                   # some but not all columns convect
+    assert mb["lsc_interior"] + mb["lsc_kx"] > 0                               # large-scale condensation occurs
+    unstable = sb["land_clamp_hi"] + sb["land_mid_unstable"] + sb["sea_clamp_hi"] + sb["sea_mid_unstable"]
+    stable = sb["land_clamp_lo"] + sb["land_mid_stable"] + sb["sea_clamp_lo"] + sb["sea_mid_stable"]
+    assert unstable > 0 and stable > 0                                         # both stability branches of the surface scheme
+
+
+def expected(r, kx, il, ix):
+    """the chain's outputs under the names of spdy_column_physics_out, shaped as the device writes one state"""
+    g3, g2 = (kx, il, ix), (il, ix)
+    m, d, s, up, p = r["moist"], r["down"], r["sfc"], r["up"], r["pbl"]
+    out = {"moist": {n: m[n].reshape(g3 if m[n].ndim == 2 else g2) for n in ("precnv", "precls", "cbmf", "iptop", "icnv", "qsat", "rh", "se")},
+           "rad": {n: d[n].reshape(g3 if d[n].ndim == 2 else g2) for n in ("cloudc", "clstr", "icltop", "ssrd", "ssr", "tsr", "slrd", "tt_rsw")
+                   if n in d},
+           "sfc": {n: s[n].reshape((-1,) + g2) for n in surface.SFC_3 + ("hfluxn",)}, "pbl": {}}
+    out["rad"].update(slr=up["slr"].reshape(g2), olr=up["olr"].reshape(g2), tt_rlw=up["tt_rlw"].reshape(g3))
+    out["sfc"].update({n: s[n].reshape(g2) for n in ("tskin", "u0", "v0", "t0")})
+    out["pbl"].update(ut_pbl=p["ut_pbl"].reshape(g2), vt_pbl=p["vt_pbl"].reshape(g2), tt_pbl=p["tt_pbl"].reshape(g3),
+                      qt_pbl=p["qt_pbl"].reshape(g3))
+    out["ts"], out["fsfcu"] = s["ts"].reshape(g2), s["slru"][2].reshape(g2)
+    return out
+
+
+def rad_state_array(state, kx):
+    """the restatement's radiation state in the device's layout: [6 kx + 7, ncol] (csrc/spdy_radiation_column.hpp)"""
+    n = state["slrd"].size
+    return np.concatenate([state["tau2"].reshape(4 * kx, n), state["stratc"], state["tt_rsw"], state["flux"], state["dfabs"],
+                           state["slrd"].reshape(1, n)])
+
+
+# ------------------------------------------------------------------------------------------------ device side (torch)
+def device_outs(nb, kx, il, ix):
+    """every optional output of every block, as column_physics_dev / physics_dev take them"""
+    import torch
+    z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device="cuda")
+    g3, g2 = (nb, kx, il, ix), (nb, il, ix)
+    moist_o = {n: z(*g2) for n in ("precnv", "precls", "cbmf")}
+    moist_o.update({n: z(*g2, dt=torch.int32) for n in ("iptop", "icnv")})
+    moist_o.update({n: z(*g3) for n in ("qsat", "rh", "se")})
+    rad = {n: z(*g2) for n in ("cloudc", "clstr", "ssrd", "ssr", "tsr", "slrd", "slr", "olr")}
+    rad["icltop"] = z(*g2, dt=torch.int32)
+    rad.update({n: z(*g3) for n in ("tt_rsw", "tt_rlw")})
+    sfc = {n: z(nb, 3, il, ix) for n in surface.SFC_3}
+    sfc["hfluxn"] = z(nb, 2, il, ix)
+    sfc.update({n: z(*g2) for n in ("tskin", "u0", "v0", "t0")})
+    pbl = {n: z(*g2) for n in ("ut_pbl", "vt_pbl")}
+    pbl.update({n: z(*g3) for n in ("tt_pbl", "qt_pbl")})
+    return {"moist": moist_o, "rad": rad, "sfc": sfc, "pbl": pbl, "ts": z(*g2), "fsfcu": z(*g2)}
+
+
+def flat_outs(out):
+    f = {}
+    for k, v in out.items():
+        if isinstance(v, dict):
+            f.update({"%s.%s" % (k, n): t for n, t in v.items()})
+        else:
+            f[k] = v
+    return f
+
+
+def device_boundary(bnd, il, ix):
+    return {n: moist.dev(np.ascontiguousarray(v).reshape(1, il, ix)) for n, v in bnd.items()}
