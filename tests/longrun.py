@@ -15,6 +15,8 @@ with a seeded smooth vorticity field on every level (winds of 20-30 m/s, the mag
 terms carry the evolution.  Both stay bounded for the 2 days (nothing but the horizontal diffusion damps them: no physics, no
 surface drag); at 2.5 times the "wind" amplitude the adiabatic core blows up within a day.
 
+The same two cases run WITH the whole physics over boundary() below: tests/physstep.py (reference_run).
+
 Shared by the golden-vector generator (tests/golden/make_golden.py: ref_run72.npz from the flang-built reference), the CPU
 test that chains the C oracle's call-by-call step against it and the GPU test that replays the captured device step."""
 import numpy as np
@@ -69,6 +71,31 @@ def rest_state(ex, seed=4242, height=2000.0, wind=0.0):
     tcorh = ex.grid_to_spec(gam1 * phis0)                                             # forcing.f90:73-81, gamlat = gamma/(1000 grav)
     return {"vor": vor, "div": z.copy(), "t": np.stack([t, t]), "tr": np.stack([q, q]), "ps": np.stack([ps, ps]),
             "phis": phis, "tcorh": tcorh, "qcorh": tcorh * (-2.0e-3)}
+
+
+def latitudes(sia_half):
+    """the il Gaussian latitudes (radians) from the plan's / oracle's table "sia_half" (geometry.f90:64-73)"""
+    s = np.asarray(sia_half, np.float64)
+    return np.arcsin(np.concatenate([-s[::-1], s]))
+
+
+def boundary(phis0, lat, seed):
+    """Smooth, plausible boundary fields per column for the run WITH physics (tests/physstep.py: reference_run) over the
+    orography phis0 [il, ix] at the latitudes lat [il]: land where the orography rises (full land above 200 m), a sea surface
+    temperature of 271.5 K at the poles and 300.5 K at the equator, a land temperature that falls with height and latitude, both
+    with 0.3 K of seeded noise; soil water, snow where the land is below 268 K, albedos that follow the snow and the latitude.
+    The stock run reads all of these from its boundary file.  Every field is even in the latitude.  Returns the dict
+    physstep.Case takes as bnd (fields [il * ix])."""
+    il, ix = phis0.shape
+    c2, s2 = np.repeat(np.cos(lat) ** 2, ix), np.repeat(np.sin(lat) ** 2, ix)
+    h = phis0.reshape(-1) / 9.81
+    u = synth.splitmix64(seed, 3 * il * ix).reshape(3, -1)
+    fmask = np.clip(h / 200.0, 0.0, 1.0)
+    stl = 250.0 + 45.0 * c2 - 6.0e-3 * h
+    snowc = np.clip((268.0 - stl) / 20.0, 0.0, 1.0)          # from the land temperature without its noise
+    return {"fmask": fmask, "albsfc": 0.07 + 0.3 * fmask * (0.3 + 0.7 * s2), "sst": 271.5 + 29.0 * c2 + 0.3 * u[0],
+            "stl": stl + 0.3 * u[1], "soilw": 0.1 + 0.8 * c2 * (0.5 + 0.5 * u[2]), "snowc": snowc, "alb_l": 0.15 + 0.4 * snowc,
+            "alb_s": np.full(il * ix, 0.07)}
 
 
 def run(step, tail_init, st, nsteps=NSTEPS, checkpoints=CHECKPOINTS, rob=None):

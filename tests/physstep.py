@@ -11,10 +11,12 @@ CPU: tests/test_physics_step_cpu.py repeats that for the first step).  Boundary 
 SURFACE decisions are too close gets new ones from the next stream."""
 import numpy as np
 
+import longrun
 import moist
 import radiation
 import surface
 import synth
+from dynstep import ROB, oracle_dynamics_step
 from dynstep import state as dyn_state
 
 MIN_MARGIN = surface.MIN_MARGIN
@@ -22,8 +24,23 @@ ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
 # tag -> (dynstep.state seed, moist.state seed, boundary seed)
 SEEDS = {"t30": (8000, 5150, 31000), "t63k16": (8000, 5150, 31000)}
 # The seeded state is not a balanced atmosphere: with the whole physics in it, three consecutive steps stay finite only with
-# a short step (T30 L8: 2400 s and 900 s overflow on the third step, T63 L16: 300 s and 120 s; found on the CPU with this module's reference side)
+# a short step (T30 L8: 2400 s and 900 s overflow on the third step, T63 L16: 300 s and 120 s; found on the CPU with this module's
+# reference side).  That is a property of the seeded state, not of the physics: from the reference's rest state (longrun.rest_state)
+# the step with the whole physics runs the start-up sequence and 72 leapfrog steps at the model's own delt = 2400 s (reference_run
+# below, tests/test_physics_run_cpu.py, tests/test_gpu_physics_run.py).
 DT = {"t30": 300.0, "t63k16": 50.0}
+
+# ---- the two-day run with the whole physics (T30 L8, longrun.CASES)
+RUN_SEED = 778            # boundary noise (longrun.boundary): the smallest margin of the 74 steps is 6.3e-10 ("wind"), 3.3e-10 ("rest")
+RUN_MARGIN = 1e-11        # no decision of any column on any step closer to its threshold: > 100 x the device's single-step error level
+NSTRAD = 3                # speedy.f90:35
+RESYNC = (10, 37, 38, 72)  # leapfrog steps before which the whole state is recorded: two shortwave steps, two without
+
+
+def shortwave_step(n):
+    """compute_shortwave of leapfrog step n (1-based; n <= 0: the two start-up steps): .true. initially
+    (shortwave_radiation.f90:67), then mod(model_step, nstrad) == 1 (speedy.f90:21,35)"""
+    return n <= 0 or n % NSTRAD == 1
 
 
 def grids_of(o, st):
@@ -60,15 +77,20 @@ def columns_of(g, bnd, phis0, ut, vt, tt, qt):
 class Case:
     """One resolution's plan-independent reference data: tables, state, orography, zonal forcing, boundary fields."""
 
-    def __init__(self, tag, sp, o, date=0):
-        s1, s2, sb = SEEDS[tag]
+    def __init__(self, tag, sp, o, date=0, st=None, bnd=None):
+        """st, bnd: a given state (the orography is its phis on the grid) and the boundary fields to use with it as they are;
+        without them both are drawn from SEEDS[tag]"""
         self.tag, self.o = tag, o
         self.kx, self.il, self.ix = o.kx, o.il, o.ix
         self.tab = moist.tables(moist.HSG[self.kx])
-        self.st = moist.state(o, dyn_state(sp, s1), s2)
+        self.st = moist.state(o, dyn_state(sp, SEEDS[tag][0]), SEEDS[tag][1]) if st is None else st
         self.phis0 = o.spec_to_grid(self.st["phis"], 1)
         self.sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, self.il, self.ix)
         self.set_date(sp, date)
+        if bnd is not None:
+            self.bnd = bnd
+            return
+        sb = SEEDS[tag][2]
         g = grids_of(o, self.st)
         zero = np.zeros((self.kx, self.il, self.ix))
         self.bnd = draw_boundary(g["tg"][-1].reshape(-1), sb)
@@ -107,6 +129,66 @@ class Case:
         return hook
 
 
+def run_case(sp, o, name, seed=RUN_SEED):
+    """the Case of the two-day run `name` of longrun.CASES: the reference's rest state over the seeded orography, longrun.boundary's
+    fields over that orography"""
+    st = longrun.rest_state(o, wind=longrun.CASES[name])
+    bnd = longrun.boundary(o.spec_to_grid(st["phis"], 1), longrun.latitudes(sp.table("sia_half")), seed)
+    return Case("t30", sp, o, st=st, bnd=bnd)
+
+
+def reference_run(case, resync=()):
+    """The reference side of the run with the whole physics: longrun.run (start-up steps + 72 leapfrog steps at delt = 2400 s)
+    with oracle_dynamics_step and case.hook, the reference's shortwave cadence, ONE radiation state, RAW filter off in the
+    start-up steps.  Returns
+      cps  {n: prognostics after leapfrog step n, + "rad" (rad_state_array) and "ssrd" (the held ssrd)} for n in longrun.CHECKPOINTS,
+      log  one entry per step (74): n, sw, margin (the smallest of all columns), convecting columns, branch counts,
+      pre  {n: what leapfrog step n starts from and gives} for n in resync: "st" (both time levels), "rs" (the radiation state
+           dict, held ssrd included), "new" / "out" (oracle_dynamics_step's results), "rec" (the chain's outputs of that step)."""
+    o, kx = case.o, case.kx
+    rs, rec, log, pre, extra, count = {}, {}, [], {}, {}, [0]
+    copy = lambda d: {k: np.array(v, copy=True) for k, v in d.items()}
+
+    def step(j1, j2, dt, st):
+        count[0] += 1
+        n = count[0] - 2
+        sw = shortwave_step(n)
+        if n in resync:
+            pre[n] = {"st": copy(st), "rs": copy(rs)}
+        new, out = oracle_dynamics_step(o, st, j1, dt, 0.0 if j1 == 1 else ROB, j2=j2, physics=case.hook(sw, rs, rec))
+        mb = rec["moist"]["branch"]
+        br = {k: int(v.sum()) for k, v in surface.branch_cols(rec).items()}
+        log.append({"n": n, "sw": sw, "margin": float(rec["margin"].min()), "convecting": mb["columns"] - mb["no_conv"],
+                    "moist": dict(mb), "branches": br})
+        if n in resync:
+            pre[n].update(new=copy(new), out=out, rec=dict(rec))
+        if n in longrun.CHECKPOINTS:
+            extra[n] = {"rad": rad_state_array(rs, kx), "ssrd": rs["ssrd_held"].copy()}
+        return new
+    cps = longrun.run(step, o.tail_init, case.st)
+    for n in cps:
+        cps[n].update(extra[n])
+    return cps, log, pre
+
+
+# ---- tests/golden/ref_physrun.npz: the restatements on columns of the "wind" run, pinned to the flang-built reference
+PHYSRUN_STEPS = (70, 72)          # the grids before leapfrog step 70 (70 mod 3 = 1: shortwave) and 72 (none, on the held state)
+PHYSRUN_INPUTS = ("ug", "vg", "tg", "qg", "phig", "pslg", "utend", "vtend", "ttend", "qtend", "albsfc", "phis0") + surface.BOUNDARY
+RAD_STATE = ("tau2", "stratc", "tt_rsw", "flux", "dfabs", "slrd", "ssrd_held")
+
+
+def chain_outputs(r, c):
+    """what ref_physrun.npz stores of surface.chain's outputs r on columns c ([.., ncol] each): everything ref_surface.npz stores,
+    and the moist block's and the longwave scheme's results that feed it"""
+    m, s, p = r["moist"], r["sfc"], r["pbl"]
+    out = {n: s[n] for n in surface.SFC_3 + ("hfluxn",) + surface.SFC_2D}
+    out.update(forog=surface.forog(c["phis0"]), ssrd=r["ssrd"], slrd=r["down"]["slrd"], ut_pbl=p["ut_pbl"], vt_pbl=p["vt_pbl"],
+               tt_pbl=p["tt_pbl"], qt_pbl=p["qt_pbl"], utend=p["utend"][-1], vtend=p["vtend"][-1], ttend=p["ttend"], qtend=p["qtend"],
+               icnv=m["icnv"], iptop=m["iptop"], precnv=m["precnv"], precls=m["precls"], cbmf=m["cbmf"], slr=r["up"]["slr"],
+               olr=r["up"]["olr"])
+    return out
+
+
 def check_coverage(r, label=""):
     """The margins first, then that the state exercises the physics; prints the branch counts."""
     assert float(r["margin"].min()) >= MIN_MARGIN, (label, float(r["margin"].min()), int(np.argmin(r["margin"])))
@@ -141,6 +223,15 @@ def rad_state_array(state, kx):
     n = state["slrd"].size
     return np.concatenate([state["tau2"].reshape(4 * kx, n), state["stratc"], state["tt_rsw"], state["flux"], state["dfabs"],
                            state["slrd"].reshape(1, n)])
+
+
+def rad_state_rows(kx):
+    """name -> rows of rad_state_array"""
+    rows, at = {}, 0
+    for n, size in (("tau2", 4 * kx), ("stratc", 2), ("tt_rsw", kx), ("flux", 4), ("dfabs", kx), ("slrd", 1)):
+        rows[n] = slice(at, at + size)
+        at += size
+    return rows
 
 
 # ------------------------------------------------------------------------------------------------ device side (torch)

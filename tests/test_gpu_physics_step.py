@@ -147,18 +147,21 @@ def test_one_launch_equals_five_calls(tag, nb):
     sp.close()
 
 
-def _step(sp, D, W, kx, dt, physics, sw=False, P=None):
-    """_step of tests/test_gpu_moist.py with geopotential_dev + physics_dev in place of the moist call"""
+def _step(sp, D, W, kx, dt, physics, sw=False, P=None, j1=2, j2=2, eps=ROB, out=None):
+    """_step of tests/test_gpu_moist.py with geopotential_dev + physics_dev in place of the moist call: step(j1, j2, dt) of
+    time_stepping.f90:35-121.  The dynamics read time level j2 (tendencies.f90:89-107); the physics always read level 1
+    (physics.f90:94-104).  out: physics_dev's optional outputs (e.g. {"rad": {"ssrd": held}} to supply the held ssrd)."""
     ug, vg, plain_g, px, py, U, V, PL, pvor, pdiv, pspec, phi, phim = W
-    sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g,
-                              D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
+    lv = j2 - 1
+    sp.inverse_batch_segs_dev(D["vor"][lv], D["div"][lv], ug, vg, [D[n][lv] for n in ("vor", "div", "t", "tr")], plain_g,
+                              D["ps"][lv:lv + 1], px, py, kcos_pairs=2, kcos=1)
     sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-    if physics:            # tendencies.f90:203-206 with time level j1 = 1
+    if physics:            # tendencies.f90:203-206
         sp.geopotential_dev(D["t"][0], D["phis"], phim)
         sp.physics_dev(sw, D["vor"][0], D["div"][0], D["t"][0], D["tr"][0], phim, D["ps"][0], P["bnd"], P["bnd"]["albsfc"], P["rad"],
-                       U[:kx], V[:kx], PL[kx:2 * kx], PL[2 * kx:3 * kx])
+                       U[:kx], V[:kx], PL[kx:2 * kx], PL[2 * kx:3 * kx], out)
     sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                      D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
+                                      D["tcorh"], D["qcorh"], SDRAG, j1, dt, eps, WIL, phi, kcos=2)
 
 
 def _workspace(sp, kx):
