@@ -121,3 +121,22 @@ def pin_launch_options(sp):
     """The launch options at their defaults, whatever the environment set when the plan was made."""
     for name, value in (("t30_part", 1), ("t30_split", 1), ("t63_split", 1), ("t63_stage", 1), ("t63_derive", 1), ("wt_min_mb", 6)):
         sp.set_option(name, value)
+
+
+# ------------------------------------------------------------------------------------------------------- per-column error
+def column_err(got, ref, scale=None):
+    """Per-column error of a column-physics output [.., ncol] or [ncol] (NumPy): max over the leading axes of |got - ref| divided
+    by the column's own scale -- max|ref| of the column, or where `scale` is given (the output is a difference of large terms, and
+    the scale has to come from its operands) the larger of the two; scale is [ncol], or shaped like ref where the operands differ
+    from level to level.  Columns are independent and span orders of magnitude, so one number per array (synth.relerr) hides a
+    small column that is wrong.  Where the reference is exactly 0 in a whole column (no convection, polar night, nothing above
+    level kx), the device must be exactly 0 there: any other value gives inf.  NaN in `got` gives inf."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    n = ref.shape[-1]
+    d = np.abs(got - ref).reshape(-1, n)
+    own = np.max(np.abs(ref).reshape(-1, n), axis=0)
+    s = np.broadcast_to(own, d.shape) if scale is None else np.maximum(np.broadcast_to(np.asarray(scale, np.float64), ref.shape).reshape(-1, n), own)
+    dmax = np.max(d, axis=0)
+    e = np.max(np.where(s > 0, d / np.where(s > 0, s, 1.0), np.where(d > 0, np.inf, 0.0)), axis=0)
+    e = np.where((own == 0) & (dmax > 0), np.inf, e)
+    return np.where(np.isnan(e), np.inf, e)

@@ -6,6 +6,7 @@ on, and a physics hook for dynstep.oracle_dynamics_step.  Pinned to the flang-bu
 Arrays are NumPy C-order views of the reference's column-major ones: a level stack (ix,il,kx) is [kx, il, ix]; the restatement
 works on [kx, ncol] (any number of columns), vectorised over columns and looping over k as the reference does.  Default-real
 literals of the reference are float32 values widened to double: f32(x) below."""
+import contextlib
 import os
 
 import numpy as np
@@ -92,8 +93,31 @@ def get_qsat(ta, ps, sig):
     return 622.0 * q / (sig * ps - f32(0.378) * q)
 
 
-def _margin(a, b):
-    """relative distance of a decision a > b (or a >= b, a < b) from its tie"""
+# Ties.  A NEAR tie (0 < margin < MIN_MARGIN) of a decision with a computed side is one the device and the reference may decide
+# differently, and the column is always drawn again.  A decision whose two sides are bit-identical on the device and in the
+# reference (inputs, literals, results of clamps: class (i) of tests/thresholds.py, marked exact=True below) is fully determined
+# by the reference's operator AT the tie and one ulp next to it.  By default such a decision is held to the margin rule like any
+# other, so an exact tie (margin 0) is drawn again with the near ones: the drawn columns of the committed fixtures.  Inside
+# `with exact_ties():` a class-(i) decision reports no margin at all (inf), so that columns constructed ON a threshold and on its
+# one-ulp neighbours survive the redraw rule, which goes on removing the near ties of every other decision.
+EXACT_TIES = False
+
+
+@contextlib.contextmanager
+def exact_ties():
+    global EXACT_TIES
+    old, EXACT_TIES = EXACT_TIES, True
+    try:
+        yield
+    finally:
+        EXACT_TIES = old
+
+
+def _margin(a, b, exact=False):
+    """relative distance of a decision a > b (or a >= b, a < b) from its tie; exact=True marks a class-(i) decision, which inside
+    exact_ties() is clear (inf) wherever it stands"""
+    if exact and EXACT_TIES:
+        return np.full(np.broadcast(a, b).shape, np.inf)
     s = np.maximum(np.abs(a), np.abs(b))
     return np.where(s > 0, np.abs(a - b) / np.where(s > 0, s, 1.0), np.inf)
 
@@ -120,7 +144,7 @@ def column_block(tab, tg, qg, phig, pslg, ttend, qtend):
     qsat = np.stack([get_qsat(tg[k], psg, fsg[k]) for k in range(kx)])
     rh = qa / qsat
     warm = tg >= T0
-    margin = np.minimum(margin, np.min(_margin(tg, np.full_like(tg, T0)), axis=0))
+    margin = np.minimum(margin, np.min(_margin(tg, np.full_like(tg, T0), exact=True), axis=0))
 
     # diagnose_convection (convection.f90:158-235)
     nl1, nlp = kx - 1, kx + 1

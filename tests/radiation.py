@@ -102,12 +102,15 @@ def zonal(sia_half, coa_half, tyear):
     return out
 
 
-def _margin(a, b):
-    return moist._margin(a, b)
+def _margin(a, b, exact=False):
+    return moist._margin(a, b, exact)
 
 
-def _tie(t):
-    """relative distance of t from the nearest half-integer (a tie of nint)"""
+def _tie(t, exact=False):
+    """relative distance of t from the nearest half-integer (a tie of nint); exact=True marks an input temperature (class (i) of
+    tests/thresholds.py: nint's rounding half away from zero decides), clear inside moist.exact_ties()"""
+    if exact and moist.EXACT_TIES:
+        return np.full(np.shape(t), np.inf)
     return np.abs(t - (np.floor(t) + 0.5)) / np.maximum(np.abs(t), 1.0)
 
 
@@ -124,7 +127,7 @@ def down(tab, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, zon,
     rps = 1.0 / psg
     qa = np.maximum(qg, 0.0)
     out = {}
-    margin = np.min(_tie(tg), axis=0)
+    margin = np.min(_tie(tg, exact=True), axis=0)
     if compute_sw:
         se = CP * tg + phig
         gse = (se[kx - 2] - se[kx - 1]) / (phig[kx - 2] - phig[kx - 1])
@@ -134,10 +137,12 @@ def down(tab, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, zon,
         margin = np.minimum(margin, _margin(rh[nl1 - 1], np.full(n, RHCL1)))
         cloudc = np.where(c, rh[nl1 - 1] - RHCL1, 0.0)
         icltop = np.where(c, nl1, nlp)
+        qacl_open = np.zeros(n, bool)        # qa within one ulp of qacl at a level where the other half of the test holds
         for k in range(3, kx - 1):
             drh = rh[k - 1] - RHCL1
-            margin = np.minimum(margin, np.minimum(_margin(drh, cloudc), _margin(qa[k - 1], np.full(n, QACL))))
+            margin = np.minimum(margin, np.minimum(_margin(drh, cloudc), _margin(qa[k - 1], np.full(n, QACL), exact=True)))
             up = (drh > cloudc) & (qa[k - 1] > QACL)
+            qacl_open |= (drh > cloudc) & (np.abs(qa[k - 1] - QACL) <= np.spacing(QACL))
             cloudc = np.where(up, drh, cloudc)
             icltop = np.where(up, k, icltop)
         pr1 = np.minimum(PMAXCL, f32(86.4) * (precnv + precls))
@@ -229,6 +234,7 @@ def down(tab, tg, qg, phig, pslg, rh, precnv, precls, iptop, fmask, albsfc, zon,
                               "cltop_iptop": iptop < icl_rh, "cltop_2": icltop == 2, "cltop_none": icltop == nlp,
                               "strat_land": (fmask > 0) & (clstr > 0), "strat_sea": (fmask < 1) & (clsea > 0),
                               "polar_night": zon["stratz"] > 0, "fband_low": np.any(nint(tg) < 200, axis=0)}
+        out["ties"] = {"qacl_open": qacl_open, "icl_rh": icl_rh, "cloudc_rh": m, "pr1": pr1}
 
     # get_downward_longwave_rad_fluxes
     tau2 = state["tau2"]

@@ -32,8 +32,8 @@ PBL_BRANCHES = ("shc_cnv_drh", "shc_cnv_nodrh", "shc_nocnv_drh", "shc_nocnv_nodr
                 "qdiff_none", "damp_some", "damp_none")
 
 
-def _margin(a, b):
-    return moist._margin(np.asarray(a, np.float64), np.broadcast_to(np.asarray(b, np.float64), np.shape(a)))
+def _margin(a, b, exact=False):
+    return moist._margin(np.asarray(a, np.float64), np.broadcast_to(np.asarray(b, np.float64), np.shape(a)), exact)
 
 
 def forog(phis0):
@@ -80,7 +80,7 @@ def fluxes(tab, ug, vg, tg, qg, phig, pslg, ssrd, slrd, bnd, phis0, fo, sqcoa):
     t22 = ta + rcp * phi
     t21 = t22 - rcp * phis0
     lapse = ta > tb
-    margin = _margin(ta, tb)
+    margin = _margin(ta, tb, exact=True)
     t11 = np.where(lapse, FTEMP0 * t11 + gtemp0 * t21, ta)
     t12 = np.where(lapse, FTEMP0 * t12 + gtemp0 * t22, ta)
     t0 = t12 + fmask * (t11 - t12)
@@ -132,14 +132,14 @@ def fluxes(tab, ug, vg, tg, qg, phig, pslg, ssrd, slrd, bnd, phis0, fo, sqcoa):
     ustr2, vstr2 = -cdsdv * ua, -cdsdv * va
     shf2 = CHS * CP * den2 * (tsea - t12)
     qs2 = get_qsat(tsea, psa, 1.0)
-    margin = np.minimum(margin, _margin(tsea, moist.T0))
+    margin = np.minimum(margin, _margin(tsea, moist.T0, exact=True))
     evap2 = CHS * den2 * (qs2 - q1)
     slru2 = esbc * np.power(tsea, 4.0)
     hf2 = ssrd * (1.0 - alb_s) + slrd - slru2 + shf2 + ALHC * evap2
     w = lambda a, b: np.stack([a, b, b + fmask * (a - b)])
     out = {"ustr": w(ustr1, ustr2), "vstr": w(vstr1, vstr2), "shf": w(shf1, shf2), "evap": w(evap1, evap2), "slru": w(slru1, slru2),
            "hfluxn": np.stack([hf1, hf2]), "ts": tsea + fmask * (stl - tsea), "tskin": tsea + fmask * (tskin - tsea), "u0": u0,
-           "v0": v0, "t0": t12 + fmask * (t11 - t12), "margin": margin}
+           "v0": v0, "t0": t12 + fmask * (t11 - t12), "margin": margin, "den0": den0, "dq": dq}
     br = {"lapse": lapse, "inversion": ~lapse, "evap_pos": wet, "evap_zero": ~wet}
     for side, b in (("land", land_br), ("sea", sea_br)):
         for n, v in zip(("clamp_hi", "mid_unstable", "mid_stable", "clamp_lo"), b):
@@ -269,7 +269,9 @@ def chain(tab, c, zon, sqcoa, compute_sw=True, state=None):
     p = pbl(tab, c["qg"], c["phig"], c["pslg"], m["se"], m["rh"], m["qsat"], m["icnv"], f3, c["utend"], c["vtend"], up["ttend"],
             m["qtend"])
     margin = np.minimum(np.minimum(m["margin"], r["margin"]), np.minimum(s["margin"], p["margin"]))
-    margin = np.minimum(margin, np.minimum(up["margin"], np.min(radiation._tie(c["tg"]), axis=0)))
+    # ts = tsea + fmask*(stl - tsea) is a rounding sum, except at fmask = 0 where it is the input sst itself (class (i))
+    up_margin = np.where(c["fmask"] == 0.0, np.inf, up["margin"]) if moist.EXACT_TIES else up["margin"]
+    margin = np.minimum(margin, np.minimum(up_margin, np.min(radiation._tie(c["tg"], exact=True), axis=0)))
     return {"moist": m, "down": r, "sfc": s, "up": up, "pbl": p, "flux3": f3, "ssrd": ssrd, "margin": margin}, st
 
 

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import guards
 import moist
 import synth
 from conftest import GOLDEN, TOL, VARIANTS
@@ -19,7 +20,8 @@ INTS = ("iptop", "icnv")
 
 @pytest.mark.parametrize("tag", sorted(moist.RES))
 def test_moist_columns_vs_reference(tag):
-    """spdy_moist_columns_dev with every optional output against the reference: integers identical, floats within TOL."""
+    """spdy_moist_columns_dev with every optional output against the reference on the stored sample, and against the restatement
+    on EVERY column (array norm and, per column by its own scale, guards.column_err): integers identical, floats within TOL."""
     z = np.load(os.path.join(GOLDEN, "ref_moist.npz"))
     ix, il, kx = moist.VARIANTS[tag]
     tab = moist.tables(moist.HSG[kx])
@@ -35,6 +37,19 @@ def test_moist_columns_vs_reference(tag):
         e = synth.relerr(r[n].reshape(-1, il * ix)[:, sub].squeeze(), z["%s_%s" % (tag, n)])
         worst = max(worst, e)
         assert e <= TOL, (n, e)
+    want = moist.block(tab, *ins)
+    worst_col = 0.0
+    for n in INTS:
+        assert np.array_equal(r[n].reshape(-1), want[n].reshape(-1)), n
+    for n in FLOATS:
+        g, w = r[n].reshape(-1, il * ix), want[n].reshape(-1, il * ix)
+        e = synth.relerr(g, w)
+        assert e <= TOL, (n, "every column", e)
+        if n not in ("ttend", "qtend"):      # sums of large terms: by the array norm here, by their operands in test_gpu_thresholds.py
+            ec = float(guards.column_err(g, w).max())
+            worst_col = max(worst_col, ec)
+            assert ec <= TOL, (n, "per column", ec)
+    print("[moist columns %s vs restatement, every column] per column worst %.1e" % (tag, worst_col))
     if kx == 5:            # convection.f90:198: the loop do k = kx-3, 3, -1 is empty -- no column convects
         assert np.all(r["icnv"] == -1)
     else:
