@@ -598,6 +598,66 @@ int spdy_physics_dev(spdy_plan *plan, int compute_sw, const double *vor, const d
                      const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
                      double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out);
 
+/* ---- surface models: the slab land, sea and ice models and the daily forcing (coupler.f90, land_model.f90, sea_model.f90,
+ * forcing.f90) -------------------------------------------------------------------------------------------------------------
+ * The reference's main loop (speedy.f90:27-54) calls set_forcing(1) on the first step of every day and couple_sea_land after
+ * EVERY step; the next step's surface fluxes read what they leave.  A spdy_surface_model holds all of it in device memory, so a
+ * run with physics exchanges nothing with the host between outputs:
+ *   create    takes the fields as the reference holds them after land_model_init / sea_model_init (host arrays; reading files,
+ *             fillsf, forchk and the soil-water formula stay with the caller): fmask, alb0 (ix,il); stl12, snowd12, soilw12,
+ *             sst12, sice12 (ix,il,12); sstan3 (ix,il,3; may be NULL without SPDY_SURFACE_SST_ANOMALY).  It builds on the host
+ *             and keeps in device memory fmask_l, fmask_s, rhcapl, cdland (land_model.f90:75-87, :159-180) and rhcaps, rhcapi,
+ *             cdsea, cdice (sea_model.f90:137-150, :204-250) for the time step delt [s]; spdy_surface_model_table reads them
+ *             like spdy_get_table.  flags: SPDY_SURFACE_LAND_COUPLING (land_coupling_flag), SPDY_SURFACE_ICE_COUPLING
+ *             (ice_coupling_flag), SPDY_SURFACE_SST_ANOMALY (sst_anomaly_coupling_flag); the reference's defaults are all
+ *             three (SPDY_SURFACE_DEFAULT).  On a host-only plan create builds the tables; every device call is then
+ *             SPDY_ERR_NO_DEVICE.  Destroy the model before its plan.
+ *   set_date  imont1 (1 .. 12), tmonth and tyear as date.f90:147-151 makes them (float32 expressions, widened): the host
+ *             computes the weights and months of forin5 / forint (interpolation.f90:16-69) and copies them to model memory on
+ *             the plan's stream, then calls spdy_radiation_set_date(tyear).  Not callable during a capture; a captured call
+ *             picks the new date up on its next replay.  spdy_surface_model_set_sst_anomaly replaces the window sstan3
+ *             (obs_ssta's shift, sea_model.f90:366-384; the file read is the caller's), stream-ordered likewise.
+ *   couple    the whole of couple_sea_land(day) as ONE launch, one thread per column: the three land and three sea
+ *             interpolations, the adjustment over the freezing point (sea_model.f90:284-305), with day == 0 the initialisation
+ *             of stl_lm, sst_om (= 0), tice_om, sice_om, otherwise run_land_model and run_sea_model, then stl_am, snowd_am,
+ *             soilw_am, sst_am, sice_am, tice_am, sstan_am, ssti_om.  hfluxn (ix,il,2), shf, evap (ix,il,3), ssrd (ix,il) are the
+ *             arrays spdy_physics_dev writes through `out` (sfc.hfluxn, sfc.shf, sfc.evap, rad.ssrd); NULL is allowed with
+ *             day == 0 only.  No contraction, as in the column physics.  Capturable with day > 0 (day == 0, the initialisation,
+ *             is SPDY_ERR_STATE inside a capture: it has to have run before forcing or couple(day > 0) are accepted).
+ *   forcing   set_forcing(1) parts 2 and 4 (forcing.f90:55-62, :84-99): one column kernel makes snowc, alb_l, alb_s, albsfc and
+ *             corh = refrh1*(qref - qsfc), then the plan's direct transform of that one field writes the caller's qcorh (mx,nx)
+ *             (device).  Needs the orography (spdy_surface_set_orography).  Capturable.  tcorh does not depend on time and is
+ *             the caller's.
+ *   boundary  hands out the model's own arrays for spdy_physics_dev (bnd->fmask = fmask_l; sst_am, stl_am, soilw_am, snowc,
+ *             alb_l, alb_s) and albsfc.  The pointers never change, so a captured step sees each update on its next replay.
+ *   field     every prognostic and diagnostic field by the reference's name: stlcl_ob snowdcl_ob soilwcl_ob stl_lm stl_am
+ *             snowd_am soilw_am sstcl_ob sicecl_ob ticecl_ob sstan_ob sst_om tice_om sice_om sst_am sstan_am sice_am tice_am
+ *             ssti_om snowc alb_l alb_s albsfc corh, and the constants fmask_l fmask_s alb0 rhcapl cdland rhcaps rhcapi cdsea
+ *             cdice (device pointers to (ix,il) doubles; writable, e.g. for a restart).
+ * Order of calls of one step: on the first step of a day forcing; the step {spdy_physics_dev ... dynamics}; the
+ * host's newdate, and set_date when the day changed (and set_sst_anomaly where obs_ssta would run); couple(day).
+ * Checks: a NULL required pointer SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE; couple or forcing before set_date, and
+ * forcing or couple(day > 0) before couple(0), SPDY_ERR_STATE.
+ * Not built: sea_coupling_flag > 0 (the reference stops for it, sea_model.f90:188-198: no ocean-model climatology, hfseacl = 0,
+ * beta = 1) and the ablco2 trend (increase_co2 is a .false. parameter, shortwave_radiation.f90).                                */
+typedef struct spdy_surface_model spdy_surface_model;
+typedef struct {                      /* host arrays, j = 0 southernmost                                                      */
+    const double *fmask, *alb0;       /* (ix,il)                                                                              */
+    const double *stl12, *snowd12, *soilw12, *sst12, *sice12;   /* (ix,il,12)                                                  */
+    const double *sstan3;             /* (ix,il,3)                                                                            */
+} spdy_surface_clim;
+enum { SPDY_SURFACE_LAND_COUPLING = 1, SPDY_SURFACE_ICE_COUPLING = 2, SPDY_SURFACE_SST_ANOMALY = 4, SPDY_SURFACE_DEFAULT = 7 };
+int spdy_surface_model_create(spdy_plan *plan, const spdy_surface_clim *host, double delt, int flags, spdy_surface_model **m);
+int spdy_surface_model_destroy(spdy_surface_model *m);
+int spdy_surface_model_table(const spdy_surface_model *m, const char *name, double *buf, int cap);
+int spdy_surface_model_set_date(spdy_surface_model *m, int imont1, double tmonth, double tyear);
+int spdy_surface_model_set_sst_anomaly(spdy_surface_model *m, const double *sstan3);
+int spdy_surface_model_couple_dev(spdy_surface_model *m, int day, const double *hfluxn, const double *shf, const double *evap,
+                                  const double *ssrd);
+int spdy_surface_model_forcing_dev(spdy_surface_model *m, double *qcorh);
+int spdy_surface_model_boundary(spdy_surface_model *m, spdy_sfc_boundary *bnd, const double **albsfc);
+int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d_ptr);
+
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,
  * time_stepping.f90:56-121: ~90 inverse and ~70 direct transforms plus the spectral operators, 7 horizontal

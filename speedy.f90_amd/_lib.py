@@ -120,6 +120,15 @@ SIGNATURES = {
     "spdy_column_physics_dev": [c_void_p, c_int, c_int] + [c_void_p] * 14,
     "spdy_physics_workspace": [c_void_p],
     "spdy_physics_dev": [c_void_p, c_int] + [c_void_p] * 14,
+    "spdy_surface_model_create": [c_void_p, c_void_p, c_double, c_int, ctypes.POINTER(c_void_p)],
+    "spdy_surface_model_destroy": [c_void_p],
+    "spdy_surface_model_table": [c_void_p, c_char_p, c_void_p, c_int],
+    "spdy_surface_model_set_date": [c_void_p, c_int, c_double, c_double],
+    "spdy_surface_model_set_sst_anomaly": [c_void_p, c_void_p],
+    "spdy_surface_model_couple_dev": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "spdy_surface_model_forcing_dev": [c_void_p, c_void_p],
+    "spdy_surface_model_boundary": [c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
+    "spdy_surface_model_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

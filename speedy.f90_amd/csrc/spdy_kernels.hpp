@@ -355,4 +355,43 @@ struct ChainCols {
 };
 hipError_t launch_column_chain(const ChainCols &a, hipStream_t s);
 
+// The slab land, sea and ice models and the daily forcing (csrc/spdy_surfmodel.hip): couple_sea_land (coupler.f90:30-38) and
+// set_forcing parts 2 and 4 (forcing.f90:55-62, :84-99), one thread per column of ONE state.  A surface model keeps its fields in
+// one device array of SM_TOTAL fields of ncol doubles: field n at f + n * ncol, month mo (0-based) of a climatology c at
+// f + (c + mo) * ncol.
+enum SurfField {
+    // constants of land_model_init / sea_model_init
+    SM_FMASK_L, SM_FMASK_S, SM_ALB0, SM_RHCAPL, SM_CDLAND, SM_RHCAPS, SM_RHCAPI, SM_CDSEA, SM_CDICE,
+    // land model, sea and ice model, by the reference's names
+    SM_STLCL_OB, SM_SNOWDCL_OB, SM_SOILWCL_OB, SM_STL_LM, SM_STL_AM, SM_SNOWD_AM, SM_SOILW_AM,
+    SM_SSTCL_OB, SM_SICECL_OB, SM_TICECL_OB, SM_SSTAN_OB, SM_SST_OM, SM_TICE_OM, SM_SICE_OM,
+    SM_SST_AM, SM_SSTAN_AM, SM_SICE_AM, SM_TICE_AM, SM_SSTI_OM,
+    // set_forcing: mod_radcon's fields and the gridded humidity correction
+    SM_SNOWC, SM_ALB_L, SM_ALB_S, SM_ALBSFC, SM_CORH,
+    SM_NFIELDS,
+    SM_STL12 = SM_NFIELDS, SM_SNOWD12 = SM_STL12 + 12, SM_SOILW12 = SM_SNOWD12 + 12, SM_SST12 = SM_SOILW12 + 12,
+    SM_SICE12 = SM_SST12 + 12, SM_SSTAN3 = SM_SICE12 + 12, SM_TOTAL = SM_SSTAN3 + 3
+};
+// The date as the interpolations need it (interpolation.f90:16-69), in model memory: forin5's five months (0-based: imon-2 ..
+// imon+2) and weights wm2 wm1 w0 wp1 wp2; forint's two months (imon, imon2) and weight wmon; forint(2, sstan3)'s second slot
+struct SurfDate {
+    double w5[5], wmon;
+    int m5[5], m2[2], s2, pad;
+};
+enum { SURF_LAND = 1, SURF_ICE = 2, SURF_SSTAN = 4 };   // the SPDY_SURFACE_* flags of include/spdy.h
+struct SurfCols {
+    int ncol, day, flags;
+    double *f;                                       // the model's fields
+    const SurfDate *date;
+    const double *hfluxn, *shf, *evap, *ssrd;        // (ix,il,2), (ix,il,3), (ix,il,3), (ix,il): read with day > 0 only
+};
+hipError_t launch_surface_couple(const SurfCols &a, hipStream_t s);
+struct SurfForcingCols {
+    int ncol;
+    double *f;
+    const double *phis0;                             // plan-owned (ix, il)
+    double gamlat, pexp;                             // gamma/(1000 grav), 1/(rgas gamlat) (forcing.f90:86, :112)
+};
+hipError_t launch_surface_forcing(const SurfForcingCols &a, hipStream_t s);
+
 }  // namespace spdy

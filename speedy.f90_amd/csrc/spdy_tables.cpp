@@ -650,4 +650,105 @@ const double *HostTables::lookup(const std::string &name, int *count, std::vecto
     return nullptr;
 }
 
+std::string SurfaceTables::build(const HostTables &t, const double *fmask, const double *alb0, double delt)
+{
+    if (!fmask || !alb0) return "null fmask or alb0";
+    if (!(delt > 0.0)) return "delt must be positive";
+    const int ix = t.ix, il = t.il, iy = t.iy;
+    const size_t n = static_cast<size_t>(ix) * il;
+    for (size_t i = 0; i < n; ++i)
+        if (!(fmask[i] == fmask[i]) || !(alb0[i] == alb0[i])) return "fmask or alb0 holds a NaN";
+    auto F = [](float x) { return static_cast<double>(x); };
+    const double thrsh = F(0.1f), third = F(1.0f / 3.0f);
+    // land_model.f90:75-87, sea_model.f90:137-150
+    fmask_l.assign(fmask, fmask + n);
+    fmask_s.assign(n, 0.0);
+    for (size_t i = 0; i < n; ++i) {
+        if (fmask_l[i] >= thrsh) {
+            if (fmask[i] > 1.0 - thrsh) fmask_l[i] = 1.0;
+        } else {
+            fmask_l[i] = 0.0;
+        }
+        fmask_s[i] = 1.0 - fmask[i];
+        if (fmask_s[i] >= thrsh) {
+            if (fmask_s[i] > 1.0 - thrsh) fmask_s[i] = 1.0;
+        } else {
+            fmask_s[i] = 0.0;
+        }
+    }
+    // land_model.f90:141-180
+    const double hcapl = 1.0 * F(2.50e+6f), hcapli = F(5.0f) * F(1.93e+6f), tdland = F(40.0f);
+    rhcapl.assign(n, 0.0); cdland.assign(n, 0.0);
+    for (size_t i = 0; i < n; ++i) {
+        const double dmask = fmask_l[i] < third ? 0.0 : 1.0;
+        rhcapl[i] = alb0[i] < F(0.4f) ? delt / hcapl : delt / hcapli;
+        cdland[i] = dmask * tdland / (1. + dmask * tdland);
+    }
+    // sea_model.f90:104-118, :152-153, :204-250
+    const double depth_ml = F(60.0f), dept0_ml = F(40.0f), depth_ice = F(2.5f), dept0_ice = F(1.5f), tdsst = F(90.0f),
+                 tdice = F(30.0f);
+    const double asin1 = F(std::asin(1.0f)), crad = F(std::asin(1.0f) / 90.0f);
+    std::vector<double> dmask(n, 1.0), sm(n, 0.0);                        // l_globe
+    for (int j = 1; j < il - 1; ++j)
+        for (int i = 0; i < ix; ++i)
+            sm[(size_t)j * ix + i] = 0.25 * (dmask[(size_t)(j - 1) * ix + i] + 2 * dmask[(size_t)j * ix + i] + dmask[(size_t)(j + 1) * ix + i]);
+    for (int j = 1; j < il - 1; ++j)
+        for (int i = 0; i < ix; ++i) dmask[(size_t)j * ix + i] = sm[(size_t)j * ix + i];
+    rhcaps.assign(n, 0.0); rhcapi.assign(n, 0.0); cdsea.assign(n, 0.0); cdice.assign(n, 0.0);
+    for (int j = 0; j < il; ++j) {
+        const int h = j < iy ? j : il - 1 - j;
+        const double radang = j < iy ? -std::asin(t.sia_half[h]) : std::asin(t.sia_half[h]);      // geometry.f90:74-75
+        const double deglat = radang * 90.0 / asin1;
+        const double coslat = std::cos(crad * deglat);
+        const double hcaps = F(4.18e+6f) * (depth_ml + (dept0_ml - depth_ml) * (coslat * coslat * coslat));
+        const double hcapi = F(1.93e+6f) * (depth_ice + (dept0_ice - depth_ice) * (coslat * coslat));
+        for (int i = 0; i < ix; ++i) {
+            const size_t c = (size_t)j * ix + i;
+            if (fmask_s[c] < third) dmask[c] = 0;
+            rhcaps[c] = delt / hcaps;
+            rhcapi[c] = delt / hcapi;
+            cdsea[c] = dmask[c] * tdsst / (1. + dmask[c] * tdsst);
+            cdice[c] = dmask[c] * tdice / (1. + dmask[c] * tdice);
+        }
+    }
+    return "";
+}
+
+const std::vector<double> *SurfaceTables::lookup(const std::string &name) const
+{
+    struct Ent { const char *n; const std::vector<double> *v; };
+    const Ent ents[] = {{"fmask_l", &fmask_l}, {"fmask_s", &fmask_s}, {"rhcapl", &rhcapl}, {"cdland", &cdland},
+                        {"rhcaps", &rhcaps}, {"rhcapi", &rhcapi}, {"cdsea", &cdsea}, {"cdice", &cdice}};
+    for (const auto &e : ents)
+        if (name == e.n) return e.v;
+    return nullptr;
+}
+
+// interpolation.f90:16-69: c0 = 1.0/12.0 is a float32 quotient widened; everything that meets tmonth (real(p)) is double
+std::string surface_date_weights(int imont1, double tmonth, SurfaceDateWeights *w)
+{
+    if (imont1 < 1 || imont1 > 12) return "imont1 outside 1 .. 12";
+    if (!(tmonth >= 0.0 && tmonth <= 1.0)) return "tmonth outside [0, 1]";
+    const int imon = imont1 - 1;
+    for (int k = 0; k < 5; ++k) w->m5[k] = (imon + k - 2 + 12) % 12;
+    const double c0 = static_cast<double>(1.0f / 12.0f);
+    const double t0 = c0 * tmonth, t1 = c0 * (1.0 - tmonth), t2 = 0.25 * tmonth * (1 - tmonth);
+    w->w5[0] = -t1 + t2;
+    w->w5[1] = -c0 + 8 * t1 - 6 * t2;
+    w->w5[2] = 7 * c0 + 10 * t2;
+    w->w5[3] = -c0 + 8 * t0 - 6 * t2;
+    w->w5[4] = -t0 + t2;
+    w->m2[0] = imon;
+    if (tmonth <= 0.5) {
+        w->m2[1] = (imon + 11) % 12;
+        w->s2 = 0;
+        w->wmon = 0.5 - tmonth;
+    } else {
+        w->m2[1] = (imon + 1) % 12;
+        w->s2 = 2;
+        w->wmon = tmonth - 0.5;
+    }
+    return "";
+}
+
 }  // namespace spdy

@@ -78,4 +78,22 @@ struct HostTables {
     const double *lookup(const std::string &name, int *count, std::vector<double> &scratch) const;
 };
 
+// The constant fields of the slab surface models, (ix, il) each, j = 0 southernmost: land_model.f90:75-87 and :159-180
+// (fmask_l, rhcapl, cdland), sea_model.f90:137-150 and :204-250 (fmask_s, rhcaps, rhcapi, cdsea, cdice; l_globe with the
+// latitudinal smoothing of dmask).  thrsh = 0.1, flandmin = fseamin = 1./3., the depths and times are float32 values widened.
+struct SurfaceTables {
+    std::vector<double> fmask_l, fmask_s, rhcapl, cdland, rhcaps, rhcapi, cdsea, cdice;
+    // fmask, alb0: (ix, il) as boundaries.f90 holds them; delt: the time step in seconds.  Returns "" or an error text.
+    std::string build(const HostTables &t, const double *fmask, const double *alb0, double delt);
+    const std::vector<double> *lookup(const std::string &name) const;
+};
+
+// The weights and 0-based months of forin5 and forint (interpolation.f90:16-69) for the month imont1 (1 .. 12) and the fraction
+// tmonth of it: w5 = wm2 wm1 w0 wp1 wp2 at m5 = imon-2 .. imon+2; wmon at m2 = (imon, imon2); s2 is forint(2, sstan3)'s imon2.
+struct SurfaceDateWeights {
+    double w5[5], wmon;
+    int m5[5], m2[2], s2;
+};
+std::string surface_date_weights(int imont1, double tmonth, SurfaceDateWeights *w);
+
 }  // namespace spdy

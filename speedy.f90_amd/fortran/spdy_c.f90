@@ -42,6 +42,12 @@ module spdy_c
         type(c_ptr) :: tt_rsw = c_null_ptr, tt_rlw = c_null_ptr
     end type
 
+    !> spdy_surface_clim (include/spdy.h): the host arrays a surface model is made from (c_loc of the caller's fields)
+    type, bind(C) :: spdy_surface_clim
+        type(c_ptr) :: fmask = c_null_ptr, alb0 = c_null_ptr, stl12 = c_null_ptr, snowd12 = c_null_ptr, soilw12 = c_null_ptr
+        type(c_ptr) :: sst12 = c_null_ptr, sice12 = c_null_ptr, sstan3 = c_null_ptr
+    end type
+
     !> spdy_sfc_boundary (include/spdy.h): per-column boundary fields of the surface fluxes, all required
     type, bind(C) :: spdy_sfc_boundary
         type(c_ptr) :: fmask = c_null_ptr, sst = c_null_ptr, stl = c_null_ptr, soilw = c_null_ptr
@@ -776,6 +782,67 @@ module spdy_c
             integer(c_int), value :: compute_sw
             type(spdy_sfc_boundary), intent(in) :: bnd
             type(spdy_column_physics_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        ! the surface models (include/spdy.h): this file is one-to-one with the header; the drop-in's own physics still runs on
+        ! the host and does not call these
+        function spdy_surface_model_create(plan, clim, delt, flags, model) bind(C, name="spdy_surface_model_create") result(rc)
+            import :: c_int, c_ptr, c_double, spdy_surface_clim
+            type(c_ptr), value :: plan
+            type(spdy_surface_clim), intent(in) :: clim
+            real(c_double), value :: delt
+            integer(c_int), value :: flags
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_destroy(model) bind(C, name="spdy_surface_model_destroy") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: model
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_table(model, name, buf, cap) bind(C, name="spdy_surface_model_table") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: model, buf
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: cap
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_set_date(model, imont1, tmonth, tyear) bind(C, name="spdy_surface_model_set_date") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: model
+            integer(c_int), value :: imont1
+            real(c_double), value :: tmonth, tyear
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_set_sst_anomaly(model, sstan3) bind(C, name="spdy_surface_model_set_sst_anomaly") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: model, sstan3
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_couple_dev(model, day, hfluxn, shf, evap, ssrd) bind(C, name="spdy_surface_model_couple_dev") &
+                & result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: model, hfluxn, shf, evap, ssrd
+            integer(c_int), value :: day
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_forcing_dev(model, qcorh) bind(C, name="spdy_surface_model_forcing_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: model, qcorh
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_boundary(model, bnd, albsfc) bind(C, name="spdy_surface_model_boundary") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary
+            type(c_ptr), value :: model
+            type(spdy_sfc_boundary), intent(out) :: bnd
+            type(c_ptr), intent(out) :: albsfc
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_field(model, name, d_ptr) bind(C, name="spdy_surface_model_field") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: model
+            character(kind=c_char), intent(in) :: name(*)
+            type(c_ptr), intent(out) :: d_ptr
             integer(c_int) :: rc
         end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)

@@ -13,6 +13,7 @@ accept/return NumPy arrays; *_dev methods take torch CUDA tensors (device memory
 it is; kernels run on torch's current stream unless use_own_stream() was called).
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -148,6 +149,133 @@ class _GraphCapture:
         return False
 
 
+class DeviceField:
+    """Device memory that a plan-side object owns, usable wherever a ``*_dev`` method takes a tensor (data_ptr()).
+    ``numpy()`` and ``upload()`` are synchronising copies through a fresh host buffer, meant for tests, outputs and restarts:
+    they wait for everything enqueued on the plan's stream, so a run keeps them out of its step loop."""
+
+    def __init__(self, sp, ptr, shape):
+        self.sp, self.ptr, self.shape = sp, int(ptr), tuple(shape)
+
+    def data_ptr(self):
+        return self.ptr
+
+    def numpy(self):
+        """A host copy, after everything enqueued on the plan's stream: allocates, blocks the host."""
+        out = np.empty(self.shape)
+        check(self.sp.lib.spdy_dev_download(self.sp.h, _p(out), ctypes.c_void_p(self.ptr), out.nbytes))
+        return out
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != self.shape:
+            raise ValueError("expected shape %s" % (self.shape,))
+        check(self.sp.lib.spdy_dev_upload(self.sp.h, ctypes.c_void_p(self.ptr), _p(a), a.nbytes))
+
+
+class SurfaceClim(ctypes.Structure):
+    """spdy_surface_clim (include/spdy.h): the host fields a surface model is made from."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("fmask", "alb0", "stl12", "snowd12", "soilw12", "sst12", "sice12", "sstan3")]
+
+
+SURFACE_LAND_COUPLING, SURFACE_ICE_COUPLING, SURFACE_SST_ANOMALY, SURFACE_DEFAULT = 1, 2, 4, 7
+SURFACE_TABLES = ("fmask_l", "fmask_s", "rhcapl", "cdland", "rhcaps", "rhcapi", "cdsea", "cdice")
+SURFACE_FIELDS = ("stlcl_ob", "snowdcl_ob", "soilwcl_ob", "stl_lm", "stl_am", "snowd_am", "soilw_am", "sstcl_ob", "sicecl_ob",
+                  "ticecl_ob", "sstan_ob", "sst_om", "tice_om", "sice_om", "sst_am", "sstan_am", "sice_am", "tice_am", "ssti_om",
+                  "snowc", "alb_l", "alb_s", "albsfc", "corh")
+
+
+class SurfaceModel:
+    """The slab land, sea and ice models and the daily forcing on the device (spdy_surface_model_* in include/spdy.h).
+
+    clim: dict of host arrays fmask, alb0 [il, ix]; stl12, snowd12, soilw12, sst12, sice12 [12, il, ix]; sstan3 [3, il, ix] (may
+    be absent without SURFACE_SST_ANOMALY).  One step of a run: on the first step of a day forcing_dev(qcorh); the step; the
+    host's newdate and, when the day changed, set_date; couple_dev(day, hfluxn, shf, evap, ssrd)."""
+
+    def __init__(self, sp, clim, delt, flags=SURFACE_DEFAULT):
+        self.sp, self.lib, self.flags = sp, sp.lib, int(flags)
+        shapes = {"fmask": (), "alb0": (), "stl12": (12,), "snowd12": (12,), "soilw12": (12,), "sst12": (12,), "sice12": (12,),
+                  "sstan3": (3,)}
+        host, c = {}, SurfaceClim()
+        for n, lead in shapes.items():
+            if clim.get(n) is None:
+                continue
+            host[n] = np.ascontiguousarray(clim[n], np.float64)
+            if host[n].shape != lead + sp.grid_shape:
+                raise ValueError("%s must have shape %s" % (n, lead + sp.grid_shape))
+            setattr(c, n, host[n].ctypes.data)
+        if sp.device >= 0:
+            sp._sync_stream()
+        h = ctypes.c_void_p()
+        check(self.lib.spdy_surface_model_create(sp.h, ctypes.byref(c), float(delt), self.flags, ctypes.byref(h)))
+        self.h = h
+        # the plan closes its models first; the references of models that are gone are dropped here
+        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.spdy_surface_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def table(self, name):
+        """A host table of land_model_init / sea_model_init (SURFACE_TABLES), [il, ix]."""
+        n = check(self.lib.spdy_surface_model_table(self.h, name.encode(), None, 0))
+        out = np.zeros(n)
+        check(self.lib.spdy_surface_model_table(self.h, name.encode(), _p(out), n))
+        return out.reshape(self.sp.grid_shape)
+
+    def set_date(self, imont1, tmonth, tyear):
+        """The date of the interpolations and of the zonal radiation forcing (date.f90:147-151's imont1, tmonth, tyear); the
+        upload is ordered on the plan's stream, so a graph replayed after this call uses the new date."""
+        self.sp._sync_stream()
+        check(self.lib.spdy_surface_model_set_date(self.h, int(imont1), float(tmonth), float(tyear)))
+
+    def set_sst_anomaly(self, sstan3):
+        """Replaces the three-month window of SST anomalies [3, il, ix] (obs_ssta's shift)."""
+        a = np.ascontiguousarray(sstan3, np.float64)
+        if a.shape != (3,) + self.sp.grid_shape:
+            raise ValueError("sstan3 must be [3, il, ix]")
+        self.sp._sync_stream()
+        check(self.lib.spdy_surface_model_set_sst_anomaly(self.h, _p(a)))
+
+    def couple_dev(self, day, hfluxn=None, shf=None, evap=None, ssrd=None):
+        """couple_sea_land(day) in one launch: hfluxn [2, il, ix], shf, evap [3, il, ix], ssrd [il, ix] device tensors as
+        physics_dev writes them (None allowed with day == 0)."""
+        self.sp._sync_stream()
+        ptr = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+        check(self.lib.spdy_surface_model_couple_dev(self.h, int(day), ptr(hfluxn), ptr(shf), ptr(evap), ptr(ssrd)))
+
+    def forcing_dev(self, qcorh):
+        """set_forcing(1) parts 2 and 4: snowc, alb_l, alb_s, albsfc, and qcorh [nx, mx] complex128 (device tensor) written."""
+        self.sp._sync_stream()
+        check(self.lib.spdy_surface_model_forcing_dev(self.h, ctypes.c_void_p(qcorh.data_ptr())))
+
+    def boundary_struct(self):
+        """(SfcBoundary of the model's own device arrays, device pointer of albsfc) for the C calls."""
+        b, alb = SfcBoundary(), ctypes.c_void_p()
+        check(self.lib.spdy_surface_model_boundary(self.h, ctypes.byref(b), ctypes.byref(alb)))
+        return b, alb
+
+    def field(self, name):
+        """A field of the model by the reference's name (SURFACE_FIELDS, SURFACE_TABLES, alb0): a DeviceField [il, ix] in the
+        model's own device memory."""
+        p = ctypes.c_void_p()
+        check(self.lib.spdy_surface_model_field(self.h, name.encode(), ctypes.byref(p)))
+        return DeviceField(self.sp, p.value, self.sp.grid_shape)
+
+    def boundary(self):
+        """(bnd, albsfc) for Spectral.physics_dev: DeviceFields of the model's own arrays (bnd["fmask"] = fmask_l)."""
+        names = {"fmask": "fmask_l", "sst": "sst_am", "stl": "stl_am", "soilw": "soilw_am", "snowc": "snowc", "alb_l": "alb_l",
+                 "alb_s": "alb_s"}
+        return {k: self.field(v) for k, v in names.items()}, self.field("albsfc")
+
+
 class Spectral:
     """One transform plan = the module state `initialize_spectral` builds (spectral.f90:20)."""
 
@@ -164,6 +292,10 @@ class Spectral:
 
     def close(self):
         if getattr(self, "h", None):
+            for ref in getattr(self, "_models", []):       # a surface model must go before its plan (include/spdy.h)
+                m = ref()
+                if m is not None:
+                    m.close()
             self.lib.spdy_plan_destroy(self.h)
             self.h = None
 
