@@ -5,6 +5,8 @@ Only what the hot path needs lives here:
     fortran/   ISO_C_BINDING drop-in for the reference's `spectral` module (the real host)
     spectral.py  Python mirror of that module over the same C-ABI (ctypes), used by tests,
                  smoke() and bench.py
+    columns.py   the column physics and the surface models of the same plan: one field table,
+                 the ctypes structures and output buffers derived from it
 
 The directory name contains a dot, so import it through the repo-root shim
 ``import speedy_f90_amd`` (speedy_f90_amd.py).

@@ -235,25 +235,6 @@ def rad_state_rows(kx):
 
 
 # ------------------------------------------------------------------------------------------------ device side (torch)
-def device_outs(nb, kx, il, ix):
-    """every optional output of every block, as column_physics_dev / physics_dev take them"""
-    import torch
-    z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device="cuda")
-    g3, g2 = (nb, kx, il, ix), (nb, il, ix)
-    moist_o = {n: z(*g2) for n in ("precnv", "precls", "cbmf")}
-    moist_o.update({n: z(*g2, dt=torch.int32) for n in ("iptop", "icnv")})
-    moist_o.update({n: z(*g3) for n in ("qsat", "rh", "se")})
-    rad = {n: z(*g2) for n in ("cloudc", "clstr", "ssrd", "ssr", "tsr", "slrd", "slr", "olr")}
-    rad["icltop"] = z(*g2, dt=torch.int32)
-    rad.update({n: z(*g3) for n in ("tt_rsw", "tt_rlw")})
-    sfc = {n: z(nb, 3, il, ix) for n in surface.SFC_3}
-    sfc["hfluxn"] = z(nb, 2, il, ix)
-    sfc.update({n: z(*g2) for n in ("tskin", "u0", "v0", "t0")})
-    pbl = {n: z(*g2) for n in ("ut_pbl", "vt_pbl")}
-    pbl.update({n: z(*g3) for n in ("tt_pbl", "qt_pbl")})
-    return {"moist": moist_o, "rad": rad, "sfc": sfc, "pbl": pbl, "ts": z(*g2), "fsfcu": z(*g2)}
-
-
 def flat_outs(out):
     f = {}
     for k, v in out.items():

@@ -37,9 +37,8 @@ def _device_run(sp, case, c, events, fault=None):
     M = s.SurfaceModel(sp, shaped, sm.DELT)
     D = {n: moist.dev(case.st[n]) for n in case.st}
     W = _workspace(sp, KX)
-    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
-    F = {"hfluxn": z(1, 2, il, ix), "shf": z(1, 3, il, ix), "evap": z(1, 3, il, ix), "ssrd": z(1, il, ix)}
-    out = {"sfc": {k: F[k] for k in ("hfluxn", "shf", "evap")}, "rad": {"ssrd": F["ssrd"]}}
+    out = sp.column_outputs(1, ("sfc", "rad"), names=("hfluxn", "shf", "evap", "ssrd"))
+    F = dict(out["sfc"], **out["rad"])
     bnd, albsfc = M.boundary()
     P = {"bnd": dict(bnd, albsfc=albsfc),
          "rad": torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")}

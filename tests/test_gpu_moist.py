@@ -57,14 +57,6 @@ def test_moist_columns_vs_reference(tag):
     print("\n[moist columns %s vs reference] worst %.1e" % (tag, worst))
 
 
-def _outs(nb, kx, il, ix):
-    import torch
-    o = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("precnv", "precls", "cbmf")}
-    o.update({n: torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda") for n in INTS})
-    o.update({n: torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda") for n in ("qsat", "rh", "se")})
-    return o
-
-
 def test_null_outputs_and_batch_composition():
     """All optional outputs NULL leaves ttend / qtend bit-equal to the full call; nb = 1, 7, 64 states in one launch are each
     bit-equal to the same state launched alone."""
@@ -74,14 +66,14 @@ def test_null_outputs_and_batch_composition():
     tab = moist.tables(moist.HSG[kx])
     for nb in (1, 7, 64):
         tg, qg, phig, pslg, tt, qt = (moist.dev(a) for a in moist.grid_inputs(tab, (nb, il, ix), 9100 + nb))
-        T, Q, out = tt.clone(), qt.clone(), _outs(nb, kx, il, ix)
+        T, Q, out = tt.clone(), qt.clone(), sp.column_outputs(nb, "moist")
         sp.moist_columns_dev(tg, qg, phig, pslg, T, Q, out)
         T0, Q0 = tt.clone(), qt.clone()
         sp.moist_columns_dev(tg, qg, phig, pslg, T0, Q0, None)
         torch.cuda.synchronize()
         assert torch.equal(T, T0) and torch.equal(Q, Q0), nb
         for b in range(nb):
-            Tb, Qb, ob = tt[b:b + 1].clone(), qt[b:b + 1].clone(), _outs(1, kx, il, ix)
+            Tb, Qb, ob = tt[b:b + 1].clone(), qt[b:b + 1].clone(), sp.column_outputs(1, "moist")
             sp.moist_columns_dev(tg[b:b + 1], qg[b:b + 1], phig[b:b + 1], pslg[b:b + 1], Tb, Qb, ob)
             torch.cuda.synchronize()
             assert torch.equal(Tb[0], T[b]) and torch.equal(Qb[0], Q[b]), (nb, b)
@@ -105,7 +97,7 @@ def test_moist_physics_from_spectra(tag, oracle_factory):
     tt, qt = tt0.copy(), qt0.copy()
     moist.make_hook(rec)(o, st, None, None, tt, qt)
     assert rec["margin"].min() >= moist.MIN_MARGIN
-    T, Q, out = moist.dev(tt0), moist.dev(qt0), _outs(1, kx, il, ix)
+    T, Q, out = moist.dev(tt0), moist.dev(qt0), sp.column_outputs(1, "moist")
     sp.moist_physics_dev(moist.dev(st["t"][0]), moist.dev(st["tr"][0]), moist.dev(phi), moist.dev(st["ps"][0]), T, Q, out)
     torch.cuda.synchronize()
     worst = max(synth.relerr(T.cpu().numpy(), tt), synth.relerr(Q.cpu().numpy(), qt))

@@ -59,7 +59,7 @@ def test_physics_from_spectra(tag, oracle_factory):
         if step == 1:
             physstep.check_coverage(r, tag)
         assert float(r["margin"].min()) >= physstep.MIN_MARGIN
-        T, out = [moist.dev(a) for a in t0], physstep.device_outs(1, kx, il, ix)
+        T, out = [moist.dev(a) for a in t0], sp.column_outputs(1)
         if sw:
             ssrd = out["rad"]["ssrd"]
         else:                          # ssrd stays where the shortwave call put it (include/spdy.h)
@@ -108,7 +108,7 @@ def _run_gridded(sp, nb, kx, il, ix, d1, d2, with_out):
     res = {"state": S}
     for i, d, sw in ((1, d1, True), (2, d2, False)):
         T = [d[n].clone() for n in TEND]
-        out = physstep.device_outs(nb, kx, il, ix) if with_out else None
+        out = sp.column_outputs(nb) if with_out else None
         if with_out and i == 2:        # ssrd stays where the shortwave call put it (include/spdy.h)
             out["rad"]["ssrd"] = res["out1.rad.ssrd"]
         sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T, out)

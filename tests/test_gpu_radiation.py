@@ -72,15 +72,6 @@ def _inputs(tab, nb, il, ix, seed, sp):
     return d, c, zon
 
 
-def _outs(nb, kx, il, ix):
-    import torch
-    o = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("cloudc", "clstr", "ssrd", "ssr", "tsr",
-                                                                                   "slrd", "slr", "olr")}
-    o["icltop"] = torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda")
-    o.update({n: torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda") for n in ("tt_rsw", "tt_rlw")})
-    return o
-
-
 def _run(sp, d, nb, st, T, out, sw=True):
     sp.radiation_down_dev(sw, d["tg"], d["qg"], d["phig"], d["pslg"], d["rh"], d["precnv"], d["precls"], d["iptop"], d["fmask"],
                           d["albsfc"], st, out)
@@ -99,7 +90,7 @@ def test_batch_composition_and_null_outputs():
     for nb in (1, 5, 64):
         d, _, _ = _inputs(tab, nb, il, ix, 9300 + nb, sp)
         st = torch.zeros(nb * S, dtype=torch.float64, device="cuda")
-        T, out = d["ttend_m"].clone(), _outs(nb, kx, il, ix)
+        T, out = d["ttend_m"].clone(), sp.column_outputs(nb, "rad")
         _run(sp, d, nb, st, T, out)
         st0 = torch.zeros_like(st)
         T0 = d["ttend_m"].clone()
@@ -109,7 +100,7 @@ def test_batch_composition_and_null_outputs():
         for b in sorted({0, nb // 2, nb - 1}):
             one = {n: v[b:b + 1].contiguous() for n, v in d.items()}
             s1 = torch.zeros(S, dtype=torch.float64, device="cuda")
-            T1, o1 = one["ttend_m"].clone(), _outs(1, kx, il, ix)
+            T1, o1 = one["ttend_m"].clone(), sp.column_outputs(1, "rad")
             _run(sp, one, 1, s1, T1, o1)
             torch.cuda.synchronize()
             assert torch.equal(T1[0], T[b]), (nb, b)
@@ -144,11 +135,9 @@ def test_chain_capture_and_date(tag):
     def fresh():
         D = {n: d[n] for n in ("tg", "qg", "phig", "pslg", "fmask", "albsfc", "ts", "fsfcu", "tg2", "ts2", "fsfcu2")}
         D["T"], D["Q"], D["T2"] = d["ttend"].clone(), d["qtend"].clone(), d["ttend2"].clone()
-        D["mo"] = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("precnv", "precls")}
-        D["mo"]["iptop"] = torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda")
-        D["mo"]["rh"] = torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda")
+        D["mo"] = sp.column_outputs(nb, "moist", names=("precnv", "precls", "iptop", "rh"))
         D["st"] = torch.full((nb * S,), float("nan"), dtype=torch.float64, device="cuda")
-        D["out"], D["out2"] = _outs(nb, kx, il, ix), _outs(nb, kx, il, ix)
+        D["out"], D["out2"] = sp.column_outputs(nb, "rad"), sp.column_outputs(nb, "rad")
         return D
 
     P = fresh()

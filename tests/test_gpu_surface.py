@@ -104,24 +104,6 @@ def _device_inputs(c, r, nb, kx, il, ix):
     return d
 
 
-def _zeros(shape, dtype=None):
-    import torch
-    return torch.zeros(shape, dtype=dtype or torch.float64, device="cuda")
-
-
-def _sfc_outs(nb, il, ix):
-    o = {n: _zeros((nb, 3, il, ix)) for n in surface.SFC_3}
-    o["hfluxn"] = _zeros((nb, 2, il, ix))
-    o.update({n: _zeros((nb, il, ix)) for n in ("tskin", "u0", "v0", "t0")})
-    return o
-
-
-def _pbl_outs(nb, kx, il, ix):
-    o = {n: _zeros((nb, il, ix)) for n in ("ut_pbl", "vt_pbl")}
-    o.update({n: _zeros((nb, kx, il, ix)) for n in ("tt_pbl", "qt_pbl")})
-    return o
-
-
 def test_batch_composition():
     """A state's output bits do not depend on nb or on its position in the batch (nb = 1 against the same state inside nb = 3)."""
     import torch
@@ -133,8 +115,8 @@ def test_batch_composition():
     d = _device_inputs(c, r, nb, kx, il, ix)
 
     def run(D, n):
-        o = {"ts": _zeros((n, il, ix)), "fsfcu": _zeros((n, il, ix)), "flux3": _zeros((n, 4, il, ix)), "sfc": _sfc_outs(n, il, ix),
-             "pbl": _pbl_outs(n, kx, il, ix)}
+        o = sp.column_outputs(n, ("sfc", "pbl"))
+        o.update(ts=torch.zeros_like(D["pslg"]), fsfcu=torch.zeros_like(D["pslg"]), flux3=torch.zeros_like(D["flux3"]))
         o.update({k: D[s].clone() for k, s in (("U", "utend"), ("V", "vtend"), ("T", "ttend_up"), ("Q", "qtend_m"))})
         sp.surface_fluxes_dev(D["ug"], D["vg"], D["tg"], D["qg"], D["phig"], D["pslg"], D["ssrd"], D["slrd"], D, o["ts"], o["fsfcu"],
                               o["flux3"], o["sfc"])
@@ -180,9 +162,7 @@ def test_column_physics_chain_and_capture(tag):
         D = {"st": torch.full((nb * S,), float("nan"), dtype=torch.float64, device="cuda")}
         for i, d in ((1, d1), (2, d2)):
             D["t%d" % i] = [d[n].clone() for n in ("utend", "vtend", "ttend", "qtend")]
-            D["o%d" % i] = {"sfc": _sfc_outs(nb, il, ix), "pbl": _pbl_outs(nb, kx, il, ix), "ts": _zeros((nb, il, ix)),
-                            "fsfcu": _zeros((nb, il, ix)), "rad": {"slrd": _zeros((nb, il, ix)), "olr": _zeros((nb, il, ix))},
-                            "moist": {"icnv": _zeros((nb, il, ix), torch.int32), "precnv": _zeros((nb, il, ix))}}
+            D["o%d" % i] = sp.column_outputs(nb, names=SFC_OUT + PBL_OUT + ("slrd", "olr", "icnv", "precnv"))
         return D
 
     def chain(D):
@@ -226,15 +206,13 @@ def test_column_physics_chain_and_capture(tag):
 
     # the five single device calls: bit-equal
     Q = fresh()
-    mo = {n: _zeros((nb, kx, il, ix)) for n in ("se", "rh", "qsat")}
-    mo.update({n: _zeros((nb, il, ix)) for n in ("precnv", "precls")})
-    mo.update({n: _zeros((nb, il, ix), torch.int32) for n in ("iptop", "icnv")})
-    ssrd = _zeros((nb, il, ix))
+    mo = sp.column_outputs(nb, "moist", names=("se", "rh", "qsat", "precnv", "precls", "iptop", "icnv"))
+    ssrd = torch.zeros_like(d1["pslg"])
     for i, d, sw in ((1, d1, True), (2, d2, False)):
         U, V, T, Qt = Q["t%d" % i]
         o = Q["o%d" % i]
         ro = dict(o["rad"], ssrd=ssrd) if sw else dict(o["rad"])
-        flux3 = _zeros((nb, 4, il, ix))
+        flux3 = torch.zeros((nb, 4, il, ix), dtype=torch.float64, device="cuda")
         sp.moist_columns_dev(d["tg"], d["qg"], d["phig"], d["pslg"], T, Qt, mo)
         sp.radiation_down_dev(sw, d["tg"], d["qg"], d["phig"], d["pslg"], mo["rh"], mo["precnv"], mo["precls"], mo["iptop"],
                               d["fmask"], d["albsfc"], Q["st"], ro)
@@ -298,9 +276,44 @@ def test_state_errors_on_device():
     import speedy_f90_amd as s
     ix, il, kx = moist.VARIANTS["t30"]
     sp = moist.plan("t30", 4)
-    g3, g2 = _zeros((1, kx, il, ix)), _zeros((1, il, ix))
+    import torch
+    g3, g2, g4 = (torch.zeros((1,) + lead + (il, ix), dtype=torch.float64, device="cuda") for lead in ((kx,), (), (4,)))
     bnd = {n: g2 for n in surface.BOUNDARY}
     with pytest.raises(s.SpdyError) as e:
-        sp.surface_fluxes_dev(g3, g3, g3, g3, g3, g2, g2, g2, bnd, g2.clone(), g2.clone(), _zeros((1, 4, il, ix)))
+        sp.surface_fluxes_dev(g3, g3, g3, g3, g3, g2, g2, g2, bnd, g2.clone(), g2.clone(), g4)
     assert e.value.code == -5
+    sp.close()
+
+
+def test_column_physics_numpy_form_equals_device_form():
+    """column_physics (the NumPy form of the chain) on a shortwave step, then without shortwave on the returned state, at the
+    smallest grid and level count: the returned keys are the documented ones (no shortwave-only key on the second call) and every
+    returned array is bit-equal to the tensor column_physics_dev leaves in column_outputs buffers given the same inputs -- the
+    same kernels on the same bytes."""
+    import torch
+    nb, tag = 2, "t30k5"
+    ix, il, kx = moist.VARIANTS[tag]
+    sp, tab, c, zon, sqcoa = _case(tag, 9800, nb)
+    _orography(sp, c, il, ix, nb)
+    tend, sw_only = ("utend", "vtend", "ttend", "qtend"), {"cloudc", "clstr", "icltop", "ssr", "tsr", "tt_rsw"}
+    always = set(tend + ("state", "ts", "fsfcu", "precnv", "precls", "cbmf", "iptop", "icnv", "qsat", "rh", "se", "slrd", "slr", "olr",
+                         "tt_rlw", "ut_pbl", "vt_pbl", "tt_pbl", "qt_pbl") + SFC_OUT)       # rad.ssrd stays in the plan's workspace
+    out = sp.column_outputs(nb)            # one set for both steps: the caller's rad.ssrd is read by the step without shortwave
+    by_name = {n: t for b in ("moist", "rad", "sfc", "pbl") for n, t in out[b].items()}
+    by_name.update(ts=out["ts"], fsfcu=out["fsfcu"])
+    by_name["state"] = torch.zeros(nb * sp.radiation_state_size(), dtype=torch.float64, device="cuda")
+    state = None
+    for cols, sw in ((c, True), (_second_step(c, tab, kx), False)):
+        g = {n: radiation.grids(cols[n], nb, il, ix) for n in ("ug", "vg", "tg", "qg", "phig", "pslg", "albsfc") + tend + surface.BOUNDARY}
+        res = sp.column_physics(*[g[n] for n in ("ug", "vg", "tg", "qg", "phig", "pslg")], {n: g[n] for n in surface.BOUNDARY},
+                                g["albsfc"] if sw else None, *[g[n] for n in tend], compute_sw=sw, state=state)
+        state = res["state"]
+        assert set(res) == always | (sw_only if sw else set()), sorted(set(res) ^ always)
+        d = {n: moist.dev(a) for n, a in g.items()}
+        sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"] if sw else None,
+                              by_name["state"], *[d[n] for n in tend], out)
+        torch.cuda.synchronize()
+        for n, a in res.items():
+            want = (d[n] if n in tend else by_name[n]).cpu().numpy()
+            assert a.dtype == want.dtype and np.array_equal(a, want), (sw, n)
     sp.close()

@@ -61,7 +61,7 @@ def _chain(sp, kx, il, ix, calls, fused):
     res, ssrd = {}, None
     for i, (d, sw) in enumerate(calls, 1):
         T = [d[n].clone() for n in th.TEND]
-        out = physstep.device_outs(1, kx, il, ix)
+        out = sp.column_outputs(1)
         if sw:
             ssrd = out["rad"]["ssrd"]
         else:                              # ssrd stays where the shortwave call put it (include/spdy.h)
@@ -82,7 +82,7 @@ def _single_calls(sp, kx, il, ix, calls):
     res, ssrd = {}, None
     for i, (d, sw) in enumerate(calls, 1):
         U, V, T, Q = [d[n].clone() for n in th.TEND]
-        o = physstep.device_outs(1, kx, il, ix)
+        o = sp.column_outputs(1)
         if sw:
             ssrd = o["rad"]["ssrd"]
         else:

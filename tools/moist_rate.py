@@ -52,9 +52,7 @@ def kernel_rates(res, kx, nbs, reps):
     rows = []
     for nb in nbs:
         tg, qg, phig, pslg, tt, qt = [x.expand((nb,) + tuple(x.shape[1:])).contiguous() for x in one]
-        out = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("precnv", "precls", "cbmf")}
-        out.update({n: torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda") for n in ("iptop", "icnv")})
-        out.update({n: torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda") for n in ("qsat", "rh", "se")})
+        out = sp.column_outputs(nb, "moist")
         us = time_fn(lambda: sp.moist_columns_dev(tg, qg, phig, pslg, tt, qt, out), reps)
         bw = bytes_per_state(kx, il * ix) * nb / (us * 1e-6)
         rows.append({"res": res, "kx": kx, "nb": nb, "us": round(us, 2), "bytes": bytes_per_state(kx, il * ix) * nb,

@@ -68,10 +68,7 @@ def rates(res, kx, nbs, reps):
     for nb in nbs:
         d = {n: x.expand((nb,) + tuple(x.shape[1:])).contiguous() for n, x in one.items()}
         st = torch.zeros(nb * S, dtype=torch.float64, device="cuda")
-        out = {n: torch.zeros((nb, il, ix), dtype=torch.float64, device="cuda") for n in ("cloudc", "clstr", "ssrd", "ssr", "tsr",
-                                                                                         "slrd", "slr", "olr")}
-        out["icltop"] = torch.zeros((nb, il, ix), dtype=torch.int32, device="cuda")
-        out.update({n: torch.zeros((nb, kx, il, ix), dtype=torch.float64, device="cuda") for n in ("tt_rsw", "tt_rlw")})
+        out = sp.column_outputs(nb, "rad")
         T = d["ttend_m"].clone()
 
         def down(sw):

@@ -53,9 +53,8 @@ def run(tag, reps, repeats, rows):
     date = sm.Date(1982, 1, 15)
     W = _workspace(sp, kx)
     D = {n: moist.dev(case.st[n]) for n in case.st}
-    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
-    F = {"hfluxn": z(1, 2, il, ix), "shf": z(1, 3, il, ix), "evap": z(1, 3, il, ix), "ssrd": z(1, il, ix)}
-    out = {"sfc": {k: F[k] for k in ("hfluxn", "shf", "evap")}, "rad": {"ssrd": F["ssrd"]}}
+    out = sp.column_outputs(1, ("sfc", "rad"), names=("hfluxn", "shf", "evap", "ssrd"))
+    F = dict(out["sfc"], **out["rad"])
     bnd, albsfc = M.boundary()
     rad = lambda: torch.zeros(sp.radiation_state_size(), dtype=torch.float64, device="cuda")
     Pp = {"bnd": physstep.device_boundary(case.bnd, il, ix), "rad": rad()}       # the parent's step: caller-owned arrays
