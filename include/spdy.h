@@ -455,8 +455,8 @@ int spdy_output_batch_dev(spdy_plan *plan, const double *vor, const double *div,
  * scaling of the convective fluxes for k >= 2 (:128-131), icnv = kx - iptop (:133), large-scale condensation (:136;
  * large_scale_condensation.f90:32-83) and ttend = ttend + tt_cnv + tt_lsc, qtend = qtend + qt_cnv + qt_lsc (:138-139).  A host
  * "with physics" calls it between spdy_grid_tendencies_dev and the direct batch (tendencies.f90:203-206).  The blocks that follow
- * it in get_physical_tendencies have device forms of their own below (radiation, surface fluxes, boundary layer); only SPPT
- * (physics.f90:208-222, off in the reference's params.f90) has none.
+ * it in get_physical_tendencies have device forms of their own below (radiation, surface fluxes, boundary layer, and SPPT,
+ * physics.f90:208-222, which is off in the reference's params.f90).
  * One thread per column; 5 <= kx <= 16 (SPDY_ERR_ARG otherwise), sigma levels as for the geopotential (SPDY_ERR_STATE without).
  * Results follow the reference's order of operations without contraction: decisions (convection or not, its top, condensation)
  * are the reference's wherever no decision is within rounding of its threshold.  Both calls can be captured in a graph; `out` is
@@ -529,7 +529,8 @@ int spdy_radiation_up_dev(spdy_plan *plan, int nb, const double *tg, const doubl
  * (physics.f90:197-205).  ut_pbl / vt_pbl are zero above level kx, so utend / vtend are read and written at level kx only (the
  * reference's + 0.0 elsewhere changes no bit but the sign of a -0.0).  It follows the up half: the reference sums
  * (ttend + tt_rsw) + tt_rlw before + tt_pbl.
- * Not built: SPPT (physics.f90:208-222; sppt_on is .false. in params.f90) and the second get_surface_fluxes call
+ * SPPT (physics.f90:208-222; sppt_on is .false. in params.f90) is the spdy_*_sppt_dev form of the chain, below ("SPPT").
+ * Not built: the second get_surface_fluxes call
  * (sea_coupling_flag > 0, lfluxland = .false.: the reference's sea model stops for those flags and that path reads ks unset).
  * Reproduced as the reference has them: fhum0 = 0, so q1 = qa(:,:,kx) and the relative humidity is never read (rh is no argument
  * of the surface call); hfluxn(:,:,2) = .. - slru + shf + alhc*evap; t0 computed twice; ftemp0*t1 + gtemp0*t2 evaluated.
@@ -597,6 +598,67 @@ int spdy_physics_workspace(spdy_plan *plan);
 int spdy_physics_dev(spdy_plan *plan, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
                      const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
                      double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out);
+
+/* ---- SPPT: stochastically perturbed parametrisation tendencies (sppt.f90, physics.f90:85-88 and :207-222) -----------------------
+ * The reference's model-error scheme: a random pattern, AR(1) in time per spectral coefficient, multiplies the physics' part of
+ * each tendency.  A spdy_sppt is the pattern, device-resident and owned by the object:
+ *   create    on a plan (max_batch >= kx on a device plan) for nsteps steps per day; mu: kx doubles on the host, the taper per
+ *             level, top down (NULL = all ones, the reference's).  Host tables (spdy_sppt_table, like spdy_get_table; served by a
+ *             host-only plan too; a buffer with cap below the table's length is SPDY_ERR_ARG): "phi" (1) = exp(-(24/nsteps)/6.0);
+ *             "f0" (1) = sqrt(stddev**2 (1 - phi**2) / (2 sum_{n=1..trunc} (2n+1) exp(-0.5 (len_decorr/rearth)**2 n(n+1)))) with
+ *             stddev = 0.33 (float32, widened) and len_decorr = 500000; "sigma" (mx,nx) = f0 exp(-0.25 len_decorr**2 el2) over the
+ *             whole rectangle, sigma(1,1) = f0 (the reference perturbs the global mean too), the same on every level; "mu" (kx);
+ *             "first" (1) = (1 - phi**2)**(-0.5).  Destroy the pattern before its plan.
+ *   advance   gen_sppt() without its return copy, three launches: (1) eta is drawn, or copied from d_eta ((mx,nx,kx) complex,
+ *             device; NULL = draw), and each part clipped to +-10; the counter `draws` (64 bits, in the object's DEVICE memory) is
+ *             read on the device: 0 gives spec = first * sigma * eta, otherwise spec = phi * spec + sigma * eta; (2) the plan's
+ *             inverse transform of the kx fields, kcos 1 -- the reference never truncates sppt_spec and draws imaginary parts for
+ *             m = 0, its spec_to_grid reads neither and neither does the plan's; (3) the clip to +-1 into "pattern", and
+ *             draws += 1, with or without d_eta.  Nothing is allocated, so it can be captured: ONE captured advance serves the
+ *             first step and every later one, and each replay draws new noise.
+ *   reset     a new seed and draws = 0 (the next advance is a first one); stream-ordered, not callable during a capture.
+ *   field     device pointers that never change: "eta", "spec" (mx,nx,kx) complex, "pattern" (ix,il,kx).
+ *   draws     downloads the counter (synchronises the plan's stream).
+ * The generator (csrc/spdy_sppt.hip) is Philox4x32-10 -- multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ * 0xBB67AE85 -- with key (seed & 0xffffffff, seed >> 32) and counter (coefficient index in storage order, part, draws & 0xffffffff,
+ * draws >> 32), part 0 for the real and 1 for the imaginary part.  Of the output words w0..w3
+ *     r1 = (double((w0 >> 5) * 2**26 + (w1 >> 6)) + 1) * 2**-53   in (0, 1],
+ *     r2 =  double((w2 >> 5) * 2**26 + (w3 >> 6))      * 2**-53   in [0, 1),
+ * and the part is the reference's randn (sppt.f90:102-116) as written: u = sqrt(-2 log r1), v = (2.0f * 6.28318530718f) * r2 (the
+ * float32 product 12.566370964050293: 4 pi, not 2 pi), u sin v.  A coefficient's noise depends on (seed, draws, index) only.
+ *
+ * The application: spdy_column_physics_sppt_dev / spdy_physics_sppt_dev are spdy_column_physics_dev / spdy_physics_dev followed
+ * by physics.f90:212-221: per level k each of utend, vtend, ttend, qtend becomes
+ *     (1 + pattern * mu(k)) * (tend - tend_dyn) + tend_dyn,        tend_dyn = the value at entry,
+ * in this order, without contraction.  ut_pbl / vt_pbl are zero above level kx, so utend / vtend are left alone there (that
+ * changes no bit but the sign of a -0.0, as for spdy_pbl_dev).  d_pattern: (ix,il,kx) per state, nb states, device, already
+ * clipped; mu: kx doubles on the host (NULL = 1), read at call time like `out`.  spdy_physics_sppt_dev reads s's current pattern
+ * and mu and does NOT advance s: a step calls spdy_sppt_advance_dev, then spdy_physics_sppt_dev (the reference advances once per
+ * physics call, both start-up steps included).  "physics_fused" selects the form as for the calls without SPPT, and both forms
+ * give the same bits: the five calls between a kernel that saves the dynamics tendencies and one that applies the factor (two
+ * more launches), or the one-launch kernel's SPPT instantiation (no more launches: the thread keeps level kx of utend and vtend
+ * in registers and passes ttend and qtend through the workspace).  Everything else -- `out`, the radiation state, the checks and
+ * their order (d_pattern / s count as required pointers; s of another plan SPDY_ERR_ARG) -- is as without SPPT.  The _workspace
+ * calls allocate what the calls without SPPT need and (2 kx + 2) grids per state for the dynamics tendencies (max_batch states /
+ * one state) ahead of a capture.                                                                                              */
+typedef struct spdy_sppt spdy_sppt;
+int spdy_sppt_create(spdy_plan *plan, int nsteps, const double *mu, unsigned long long seed, spdy_sppt **s);
+int spdy_sppt_destroy(spdy_sppt *s);
+int spdy_sppt_reset(spdy_sppt *s, unsigned long long seed);
+int spdy_sppt_table(const spdy_sppt *s, const char *name, double *buf, int cap);
+int spdy_sppt_field(spdy_sppt *s, const char *name, double **d_ptr);
+int spdy_sppt_draws(spdy_sppt *s, long long *draws);
+int spdy_sppt_advance_dev(spdy_sppt *s, const double *d_eta);
+int spdy_column_physics_sppt_workspace(spdy_plan *plan);
+int spdy_column_physics_sppt_dev(spdy_plan *plan, int nb, const double *d_pattern, const double *mu, int compute_sw,
+                                 const double *ug, const double *vg, const double *tg, const double *qg, const double *phig,
+                                 const double *pslg, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
+                                 double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out);
+int spdy_physics_sppt_workspace(spdy_plan *plan);
+int spdy_physics_sppt_dev(spdy_plan *plan, spdy_sppt *s, int compute_sw, const double *vor, const double *div, const double *t,
+                          const double *q, const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc,
+                          double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                          const spdy_column_physics_out *out);
 
 /* ---- surface models: the slab land, sea and ice models and the daily forcing (coupler.f90, land_model.f90, sea_model.f90,
  * forcing.f90) -------------------------------------------------------------------------------------------------------------

@@ -129,6 +129,17 @@ SIGNATURES = {
     "spdy_surface_model_forcing_dev": [c_void_p, c_void_p],
     "spdy_surface_model_boundary": [c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_surface_model_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
+    "spdy_sppt_create": [c_void_p, c_int, c_void_p, ctypes.c_ulonglong, ctypes.POINTER(c_void_p)],
+    "spdy_sppt_destroy": [c_void_p],
+    "spdy_sppt_reset": [c_void_p, ctypes.c_ulonglong],
+    "spdy_sppt_table": [c_void_p, c_char_p, c_void_p, c_int],
+    "spdy_sppt_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
+    "spdy_sppt_draws": [c_void_p, ctypes.POINTER(ctypes.c_longlong)],
+    "spdy_sppt_advance_dev": [c_void_p, c_void_p],
+    "spdy_column_physics_sppt_workspace": [c_void_p],
+    "spdy_column_physics_sppt_dev": [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 14,
+    "spdy_physics_sppt_workspace": [c_void_p],
+    "spdy_physics_sppt_dev": [c_void_p, c_void_p, c_int] + [c_void_p] * 14,
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

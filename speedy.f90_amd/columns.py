@@ -230,6 +230,80 @@ class SurfaceModel:
         return {k: self.field(v) for k, v in names.items()}, self.field("albsfc")
 
 
+SPPT_TABLES = ("phi", "f0", "first", "sigma", "mu")
+SPPT_FIELDS = ("eta", "spec", "pattern")
+
+
+class Sppt:
+    """The SPPT pattern on the device (spdy_sppt_* in include/spdy.h): gen_sppt of sppt.f90 with a counter-based generator.
+
+    nsteps: steps per day; mu: the taper per level, kx values top down (None = all ones).  One step of a run: advance_dev(), then
+    Spectral.physics_sppt_dev(self, ...), which reads the pattern and mu and does not advance."""
+
+    def __init__(self, sp, nsteps, mu=None, seed=0):
+        self.sp, self.lib = sp, sp.lib
+        if mu is not None:
+            mu = np.ascontiguousarray(mu, np.float64)
+            if mu.shape != (sp.kx,):
+                raise ValueError("mu must hold kx values")
+        if sp.device >= 0:
+            sp._sync_stream()
+        h = ctypes.c_void_p()
+        check(self.lib.spdy_sppt_create(sp.h, int(nsteps), None if mu is None else _p(mu), int(seed), ctypes.byref(h)))
+        self.h = h
+        # the plan closes its objects first (as its surface models)
+        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.spdy_sppt_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def table(self, name):
+        """A host table (SPPT_TABLES): phi, f0, first as floats, sigma [nx, mx], mu [kx]."""
+        n = check(self.lib.spdy_sppt_table(self.h, name.encode(), None, 0))
+        out = np.zeros(n)
+        check(self.lib.spdy_sppt_table(self.h, name.encode(), _p(out), n))
+        return float(out[0]) if n == 1 and name != "mu" else out.reshape((self.sp.nx, self.sp.mx)) if name == "sigma" else out
+
+    def field(self, name):
+        """"eta", "spec" ([kx, nx, mx] complex128, as a DeviceField of [kx, nx, mx, 2] float64) or "pattern" [kx, il, ix]: the
+        object's own device memory; the pointers never change."""
+        p = ctypes.c_void_p()
+        check(self.lib.spdy_sppt_field(self.h, name.encode(), ctypes.byref(p)))
+        sp = self.sp
+        return DeviceField(sp, p.value, (sp.kx,) + sp.grid_shape if name == "pattern" else (sp.kx, sp.nx, sp.mx, 2))
+
+    def numpy(self, name):
+        """A host copy of a field after everything enqueued on the plan's stream: eta and spec as complex128 [kx, nx, mx]."""
+        a = self.field(name).numpy()
+        return a if name == "pattern" else a.view(np.complex128)[..., 0]
+
+    def reset(self, seed):
+        """A new seed and draws = 0: the next advance is a first one.  Stream-ordered; not during a capture."""
+        self.sp._sync_stream()
+        check(self.lib.spdy_sppt_reset(self.h, int(seed)))
+
+    def draws(self):
+        """The number of advances since create / reset (downloads the device counter: synchronises the plan's stream)."""
+        self.sp._sync_stream()
+        n = ctypes.c_longlong()
+        check(self.lib.spdy_sppt_draws(self.h, ctypes.byref(n)))
+        return n.value
+
+    def advance_dev(self, eta=None):
+        """gen_sppt(): noise (drawn on the device, or eta [kx, nx, mx] complex128 device tensor), AR(1) update, the plan's inverse
+        transform, the clip into "pattern"; capturable, each replay draws new noise."""
+        self.sp._sync_stream()
+        check(self.lib.spdy_sppt_advance_dev(self.h, None if eta is None else ctypes.c_void_p(eta.data_ptr())))
+
+
 class ColumnPhysics:
     """The column-physics calls of a plan (a mixin of spectral.Spectral)."""
 
@@ -358,6 +432,39 @@ class ColumnPhysics:
         check(self.lib.spdy_physics_dev(self.h, 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
                                         ctypes.byref(b), self._dp(albsfc), self._dp(state),
                                         *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+
+    # ------------------------------------------------------------------ SPPT (physics.f90:85-88, :207-222)
+    def column_physics_sppt_workspace(self):
+        check(self.lib.spdy_column_physics_sppt_workspace(self.h))
+
+    def physics_sppt_workspace(self):
+        check(self.lib.spdy_physics_sppt_workspace(self.h))
+
+    def column_physics_sppt_dev(self, pattern, mu, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, state, utend, vtend, ttend,
+                                qtend, out=None):
+        """column_physics_dev followed by SPPT: pattern [nb,kx,il,ix] (device, clipped), mu kx host values top down (None = 1);
+        each tendency becomes (1 + pattern*mu(k))*(tend - tend_dyn) + tend_dyn with tend_dyn its value at entry."""
+        self._sync_stream()
+        o = self._column_physics_out(out)
+        b = self._boundary(bnd)
+        if mu is not None:
+            mu = np.ascontiguousarray(mu, np.float64)
+            if mu.shape != (self.kx,):
+                raise ValueError("mu must hold kx values")
+        check(self.lib.spdy_column_physics_sppt_dev(self.h, _nb(tg), self._dp(pattern), None if mu is None else _p(mu),
+                                                    1 if compute_sw else 0, *[self._dp(x) for x in (ug, vg, tg, qg, phig, pslg)],
+                                                    ctypes.byref(b), self._dp(albsfc), self._dp(state),
+                                                    *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+
+    def physics_sppt_dev(self, sppt, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, state, utend, vtend, ttend, qtend, out=None):
+        """physics_dev followed by SPPT with the current pattern and the mu of sppt (a Sppt of this plan), which is not advanced:
+        call sppt.advance_dev() first."""
+        self._sync_stream()
+        o = self._column_physics_out(out)
+        b = self._boundary(bnd)
+        check(self.lib.spdy_physics_sppt_dev(self.h, sppt.h, 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
+                                             ctypes.byref(b), self._dp(albsfc), self._dp(state),
+                                             *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
 
     # ------------------------------------------------------------------ NumPy conveniences: inputs and results by name, shaped by FIELDS
     def _grid_args(self, ins, ref="tg"):

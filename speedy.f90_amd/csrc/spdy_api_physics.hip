@@ -1,6 +1,6 @@
 // C ABI of the column physics (include/spdy.h, "column physics"): the precipitation block (physics.f90:110-138), the
 // radiation schemes (physics.f90:146-166 and :180-186), the surface fluxes (:169-170), the boundary layer (:193-205) and the
-// whole chain, on gridded states and from spectra.  Kernels: csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip,
+// whole chain, on gridded states and from spectra, without and with SPPT (:207-222).  Kernels: csrc/spdy_sppt.hip, csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip,
 // csrc/spdy_column_chain.hip.
 #include <cmath>
 #include <cstring>
@@ -141,14 +141,21 @@ bool boundary_ok(const spdy_sfc_boundary *b)
     return b && b->fmask && b->sst && b->stl && b->soilw && b->snowc && b->alb_l && b->alb_s;
 }
 
+// SPPT around the chain (physics.f90:85-88, :207-222): the clipped pattern of the nb states, the taper (host, kx values top
+// down, null = 1) and the place of the dynamics tendencies, (2 kx + 2) fields each g doubles long like the chain's workspace
+struct SpptUse { const double *pattern, *mu; double *save; };
+
 // physics.f90:110-205 on nb gridded states, arguments checked: the five calls, or (fused) the one-launch kernel.  w is the chain's
-// workspace of (3 kx + 12) fields, each g doubles long (g >= nb grids).
+// workspace of (3 kx + 12) fields, each g doubles long (g >= nb grids).  With sppt the five calls lie between a save and an apply
+// kernel, and the one launch is the kernel's SPPT instantiation.
 int column_chain(spdy_plan *p, bool fused, int nb, int compute_sw, const double *ug, const double *vg, const double *tg,
                  const double *qg, const double *phig, const double *pslg, const spdy_sfc_boundary *bnd, const double *albsfc,
                  double *rad_state, double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out,
-                 double *w, size_t g)
+                 double *w, size_t g, const SpptUse *sppt = nullptr)
 {
     const size_t L = (size_t)p->tab.kx * g;
+    double mu[spdy::COLUMN_KMAX];
+    for (int k = 0; k < spdy::COLUMN_KMAX; ++k) mu[k] = sppt && sppt->mu && k < p->tab.kx ? sppt->mu[k] : 1.0;
     double *w2 = w + 3 * L;
     // the caller's optional outputs take the place of the workspace where both exist.  ssrd is written by shortwave calls only
     // and read by every call (the reference holds it in get_physical_tendencies): it stays where the last shortwave call put it
@@ -172,8 +179,22 @@ int column_chain(spdy_plan *p, bool fused, int nb, int compute_sw, const double 
         c.rad.rh = mo.rh; c.rad.fmask = bnd->fmask; c.rad.albsfc = albsfc;
         c.sfc = sfc_cols(p, nb, ug, vg, tg, qg, phig, pslg, nullptr, nullptr, bnd, ts, fsfcu, nullptr, &so);
         c.pbl = pbl_cols(p, nb, qg, phig, pslg, mo.se, mo.rh, mo.qsat, nullptr, nullptr, utend, vtend, ttend, qtend, po);
-        KERNEL(spdy::launch_column_chain(c, p->stream));
+        if (!sppt) {
+            KERNEL(spdy::launch_column_chain(c, p->stream));
+            return SPDY_OK;
+        }
+        spdy::ChainSpptCols cs{};
+        cs.c = c; cs.pattern = sppt->pattern; cs.save_t = sppt->save; cs.save_q = sppt->save + L;
+        std::memcpy(cs.mu, mu, sizeof(mu));
+        KERNEL(spdy::launch_column_chain_sppt(cs, p->stream));
         return SPDY_OK;
+    }
+    spdy::SpptCols sc{};
+    if (sppt) {
+        sc.nb = nb; sc.ncol = p->tab.ix * p->tab.il; sc.kx = p->tab.kx; sc.pattern = sppt->pattern;
+        sc.utend = utend; sc.vtend = vtend; sc.ttend = ttend; sc.qtend = qtend; sc.save = sppt->save; sc.g = g;
+        std::memcpy(sc.mu, mu, sizeof(mu));
+        KERNEL(spdy::launch_sppt_save(sc, p->stream));
     }
     pick(mo.precnv, w2); pick(mo.precls, w2 + g); pick(ro.slrd, w2 + 3 * g);
     pick(ts, w2 + 4 * g); pick(fsfcu, w2 + 5 * g);
@@ -185,6 +206,20 @@ int column_chain(spdy_plan *p, bool fused, int nb, int compute_sw, const double 
     RC(spdy_surface_fluxes_dev(p, nb, ug, vg, tg, qg, phig, pslg, ro.ssrd, ro.slrd, bnd, ts, fsfcu, flux3, &so));
     RC(spdy_radiation_up_dev(p, nb, tg, pslg, ts, fsfcu, rad_state, ttend, &ro));
     RC(spdy_pbl_dev(p, nb, qg, phig, pslg, mo.se, mo.rh, mo.qsat, mo.icnv, flux3, utend, vtend, ttend, qtend, po));
+    if (sppt) KERNEL(spdy::launch_sppt_apply(sc, p->stream));
+    return SPDY_OK;
+}
+
+int sppt_workspace(spdy_plan *p, double **ws, size_t states, const char *scheme, const char *what)
+{
+    NEED_PLAN(p);
+    RC(check_kx(p, scheme));
+    NEED_DEVICE(p);
+    if (*ws) return SPDY_OK;
+    NOT_CAPTURING(p, what);
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(2 * p->tab.kx + 2) * grid_elems(p) * states * sizeof(double), &ptr));
+    *ws = static_cast<double *>(ptr);
     return SPDY_OK;
 }
 }  // namespace
@@ -367,6 +402,28 @@ int spdy_column_physics_dev(spdy_plan *p, int nb, int compute_sw, const double *
                         ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch);
 }
 
+int spdy_column_physics_sppt_workspace(spdy_plan *p)
+{
+    RC(spdy_column_physics_workspace(p));
+    return sppt_workspace(p, &p->sppt_ws, p->max_batch, "column physics",
+                          "allocating the SPPT workspace (call spdy_column_physics_sppt_workspace before the capture)");
+}
+
+int spdy_column_physics_sppt_dev(spdy_plan *p, int nb, const double *d_pattern, const double *mu, int compute_sw, const double *ug,
+                                 const double *vg, const double *tg, const double *qg, const double *phig, const double *pslg,
+                                 const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state, double *utend, double *vtend,
+                                 double *ttend, double *qtend, const spdy_column_physics_out *out)
+{
+    const bool ok = d_pattern && ug && vg && tg && qg && phig && pslg && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state &&
+                    utend && vtend && ttend && qtend;
+    RC(column_args(p, "column physics", nb, true, !nb || ok, true));
+    NEED_DEVICE(p);
+    RC(spdy_column_physics_sppt_workspace(p));
+    const SpptUse use{d_pattern, mu, p->sppt_ws};
+    return column_chain(p, p->physics_fused == 1, nb, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend,
+                        ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch, &use);
+}
+
 /* ---------------------------------------------------------------- one state's physics from its spectra (physics.f90:94-205) */
 int spdy_physics_workspace(spdy_plan *p)
 {
@@ -403,6 +460,37 @@ int spdy_physics_dev(spdy_plan *p, int compute_sw, const double *vor, const doub
                                    nullptr, nullptr, 2));
     return column_chain(p, p->physics_fused != 0, 1, compute_sw, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, g + 5 * L, bnd, albsfc,
                         rad_state, utend, vtend, ttend, qtend, out, g + 5 * L + grid_elems(p), grid_elems(p));
+}
+
+int spdy_physics_sppt_workspace(spdy_plan *p)
+{
+    RC(spdy_physics_workspace(p));
+    return sppt_workspace(p, &p->sppt_grid, 1, "physics",
+                          "allocating the SPPT workspace (call spdy_physics_sppt_workspace before the capture)");
+}
+
+int spdy_physics_sppt_dev(spdy_plan *p, spdy_sppt *sp, int compute_sw, const double *vor, const double *div, const double *t,
+                          const double *q, const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc,
+                          double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                          const spdy_column_physics_out *out)
+{
+    const bool ok = sp && vor && div && t && q && phi && ps && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
+                    vtend && ttend && qtend;
+    RC(column_args(p, "physics", 1, true, ok, true));
+    if (sp->plan != p) return fail(SPDY_ERR_ARG, "the SPPT pattern belongs to another plan");
+    const int kx = p->tab.kx;
+    if (p->max_batch < 3 * kx + 1) return fail(SPDY_ERR_ARG, "max_batch must be >= 3*kx+1 for the physics from spectra");
+    NEED_DEVICE(p);
+    RC(spdy_physics_sppt_workspace(p));
+    // the inverse launch of spdy_physics_dev; the pattern is the one the last spdy_sppt_advance_dev left
+    const size_t L = (size_t)kx * grid_elems(p);
+    double *g = p->physics_grid;
+    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{kx, t}, {kx, q}, {kx, phi}, {1, ps}};
+    RC(spdy_inverse_batch_segs_dev(p, kx, vor, div, g, g + L, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, g + 2 * L, 0, nullptr,
+                                   nullptr, nullptr, 2));
+    const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->sppt_grid};
+    return column_chain(p, p->physics_fused != 0, 1, compute_sw, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, g + 5 * L, bnd, albsfc,
+                        rad_state, utend, vtend, ttend, qtend, out, g + 5 * L + grid_elems(p), grid_elems(p), &use);
 }
 
 }  // extern "C"

@@ -1,0 +1,138 @@
+// C ABI of the SPPT pattern (include/spdy.h, "SPPT"): gen_sppt of sppt.f90 device-resident.  Kernels: csrc/spdy_sppt.hip; host
+// tables: csrc/spdy_tables.cpp (SpptTables).  The application to the tendencies is part of the column physics
+// (csrc/spdy_api_physics.hip).
+#include <cstring>
+
+#include "spdy_plan.hpp"
+
+using namespace spdy_detail;
+
+namespace {
+#define NEED_SPPT(s)                                                    \
+    do {                                                                \
+        if (!(s)) return fail(SPDY_ERR_ARG, "null SPPT pattern");       \
+    } while (0)
+
+size_t coefs(const spdy_plan *p) { return (size_t)p->tab.mx * p->tab.nx * p->tab.kx; }
+
+// the counter and the seed, stream-ordered as spdy_radiation_set_date's fields; the pattern is zero until the first advance
+int restart(spdy_sppt *s, unsigned long long seed)
+{
+    spdy_plan *p = s->plan;
+    const spdy::SpptState h{0ull, seed};
+    HIP_TRY(hipMemcpyAsync(s->d_state, &h, sizeof(h), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int spdy_sppt_create(spdy_plan *p, int nsteps, const double *mu, unsigned long long seed, spdy_sppt **out)
+{
+    NEED_PLAN(p);
+    if (!out) return fail(SPDY_ERR_ARG, "null result pointer");
+    NOT_CAPTURING(p, "spdy_sppt_create (host table build + upload)");
+    spdy_sppt *s = new spdy_sppt;
+    s->plan = p;
+    const std::string err = s->tab.build(p->tab, nsteps, mu);
+    if (!err.empty()) { delete s; return fail(SPDY_ERR_ARG, "sppt_create: %s", err.c_str()); }
+    *out = s;
+    if (p->device < 0) return SPDY_OK;
+    auto cleanup = [&](int rc) { spdy_sppt_destroy(s); *out = nullptr; return rc; };
+    if (p->max_batch < p->tab.kx) return cleanup(fail(SPDY_ERR_ARG, "max_batch must be >= kx for the SPPT pattern's transform"));
+    if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
+    const size_t nc = coefs(p), ng = grid_elems(p) * p->tab.kx, nsig = s->tab.sigma.size();
+    const size_t bytes = (4 * nc + ng + nsig) * sizeof(double);
+    if (hipMalloc(reinterpret_cast<void **>(&s->d_eta), bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(spdy::SpptState)) != hipSuccess)
+        return cleanup(fail(SPDY_ERR_HIP, "sppt_create: hipMalloc of %zu bytes failed", bytes));
+    s->d_spec = s->d_eta + 2 * nc; s->d_pattern = s->d_spec + 2 * nc; s->d_sigma = s->d_pattern + ng;
+    if (hipMemsetAsync(s->d_eta, 0, bytes, p->stream) != hipSuccess ||
+        hipMemcpyAsync(s->d_sigma, s->tab.sigma.data(), nsig * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess)
+        return cleanup(fail(SPDY_ERR_HIP, "sppt_create: upload failed"));
+    int rc = restart(s, seed);
+    // one transform of the zero spectra: whatever the plan's inverse path allocates on its first call exists before a capture
+    if (!rc) rc = spdy_spec_to_grid_dev(p, p->tab.kx, s->d_spec, nullptr, 1, s->d_pattern);
+    if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(SPDY_ERR_HIP, "sppt_create: the first transform failed");
+    return rc ? cleanup(rc) : SPDY_OK;
+}
+
+int spdy_sppt_destroy(spdy_sppt *s)
+{
+    if (!s) return SPDY_OK;
+    if (s->d_eta || s->d_state) {
+        (void)hipSetDevice(s->plan->device);
+        (void)hipStreamSynchronize(s->plan->stream);
+        if (s->d_eta) (void)hipFree(s->d_eta);
+        if (s->d_state) (void)hipFree(s->d_state);
+    }
+    delete s;
+    return SPDY_OK;
+}
+
+int spdy_sppt_reset(spdy_sppt *s, unsigned long long seed)
+{
+    NEED_SPPT(s);
+    spdy_plan *p = s->plan;
+    NOT_CAPTURING(p, "spdy_sppt_reset (upload)");
+    NEED_DEVICE(p);
+    return restart(s, seed);
+}
+
+int spdy_sppt_table(const spdy_sppt *s, const char *name, double *buf, int cap)
+{
+    NEED_SPPT(s);
+    if (!name) return fail(SPDY_ERR_ARG, "null table name");
+    const std::vector<double> *v = s->tab.lookup(name);
+    if (!v) return fail(SPDY_ERR_ARG, "unknown SPPT table '%s'", name);
+    const int n = static_cast<int>(v->size());
+    if (buf && cap < n) return fail(SPDY_ERR_ARG, "SPPT table '%s' has %d values, the buffer %d", name, n, cap);
+    if (buf) std::memcpy(buf, v->data(), sizeof(double) * (size_t)n);
+    return n;
+}
+
+int spdy_sppt_field(spdy_sppt *s, const char *name, double **d_ptr)
+{
+    NEED_SPPT(s);
+    if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
+    double *const *f = !std::strcmp(name, "eta") ? &s->d_eta : !std::strcmp(name, "spec") ? &s->d_spec
+                       : !std::strcmp(name, "pattern") ? &s->d_pattern : nullptr;
+    if (!f) return fail(SPDY_ERR_ARG, "unknown SPPT field '%s'", name);
+    NEED_DEVICE(s->plan);
+    *d_ptr = *f;
+    return SPDY_OK;
+}
+
+int spdy_sppt_draws(spdy_sppt *s, long long *draws)
+{
+    NEED_SPPT(s);
+    if (!draws) return fail(SPDY_ERR_ARG, "null result pointer");
+    spdy_plan *p = s->plan;
+    NOT_CAPTURING(p, "spdy_sppt_draws (download)");
+    NEED_DEVICE(p);
+    spdy::SpptState h{};
+    HIP_TRY(hipMemcpyAsync(&h, s->d_state, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    *draws = (long long)h.draws;
+    return SPDY_OK;
+}
+
+int spdy_sppt_advance_dev(spdy_sppt *s, const double *d_eta)
+{
+    NEED_SPPT(s);
+    spdy_plan *p = s->plan;
+    NEED_DEVICE(p);
+    spdy::SpptNoise a{};
+    a.n = (int)coefs(p); a.nspec = p->tab.mx * p->tab.nx;
+    a.state = s->d_state; a.sigma = s->d_sigma; a.eta_in = d_eta; a.eta = s->d_eta; a.spec = s->d_spec;
+    a.phi = s->tab.phi[0]; a.first = s->tab.first[0];
+    KERNEL(spdy::launch_sppt_noise(a, p->stream));
+    // sppt.f90:93-95: the reference never truncates sppt_spec and draws imaginary parts for m = 0; its spec_to_grid reads neither
+    // (legendre.f90:93, fourier.f90:34-38), and neither does the plan's inverse
+    RC(spdy_spec_to_grid_dev(p, p->tab.kx, s->d_spec, nullptr, 1, s->d_pattern));
+    KERNEL(spdy::launch_sppt_clip(s->d_pattern, (long)(grid_elems(p) * p->tab.kx), s->d_state, p->stream));
+    return SPDY_OK;
+}
+
+}  // extern "C"

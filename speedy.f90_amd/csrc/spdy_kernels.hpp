@@ -355,6 +355,45 @@ struct ChainCols {
 };
 hipError_t launch_column_chain(const ChainCols &a, hipStream_t s);
 
+// SPPT (csrc/spdy_sppt.hip; sppt.f90, physics.f90:207-222).  The pattern object's counter and seed live in device memory, so
+// one captured advance serves the first step and every later one and each replay draws new noise.
+struct SpptState { unsigned long long draws, seed; };
+// gen_sppt up to the AR(1) update: one thread per complex coefficient of the (mx, nx, kx) rectangle in storage order.  eta_in
+// null: the coefficient's two Philox4x32-10 draws (include/spdy.h); otherwise eta_in is copied.  Both parts are clipped to +-10,
+// eta is stored, and spec = first * sigma * eta where state->draws == 0, phi * spec + sigma * eta otherwise.
+struct SpptNoise {
+    int n, nspec;                                    // mx * nx * kx coefficients, mx * nx per level
+    const SpptState *state;
+    const double *sigma, *eta_in;                    // (mx, nx); (mx, nx, kx) complex or null
+    double *eta, *spec;                              // (mx, nx, kx) complex
+    double phi, first;
+};
+hipError_t launch_sppt_noise(const SpptNoise &a, hipStream_t s);
+// the clip of the transformed pattern to +-1 in place, n = ix * il * kx values; thread 0 then counts the advance (draws += 1)
+hipError_t launch_sppt_clip(double *pattern, long n, SpptState *state, hipStream_t s);
+// physics.f90:85-88 and :207-222 around the five calls: save copies the dynamics tendencies (ttend, qtend on every level, utend,
+// vtend on level kx) into `save`, (2 kx + 2) fields each g doubles long; apply makes each tendency
+// (1 + pattern * mu(k)) * (tend - tend_dyn) + tend_dyn.  pattern is (ix, il, kx) per state; mu is top down.
+struct SpptCols {
+    int nb, ncol, kx;
+    const double *pattern;
+    double *utend, *vtend, *ttend, *qtend, *save;
+    size_t g;
+    double mu[COLUMN_KMAX];
+};
+hipError_t launch_sppt_save(const SpptCols &a, hipStream_t s);
+hipError_t launch_sppt_apply(const SpptCols &a, hipStream_t s);
+// The one-launch chain with SPPT (csrc/spdy_column_chain.hip): the thread keeps its column's entry values of utend and vtend
+// (level kx) in registers, those of ttend and qtend go through save_t / save_q ((ix, il, kx) per state, as se, rh and qsat
+// travel), and the factor is applied after the boundary layer.  Same instructions on the same values as save + chain + apply.
+struct ChainSpptCols {
+    ChainCols c;
+    const double *pattern;
+    double *save_t, *save_q;
+    double mu[COLUMN_KMAX];
+};
+hipError_t launch_column_chain_sppt(const ChainSpptCols &a, hipStream_t s);
+
 // The slab land, sea and ice models and the daily forcing (csrc/spdy_surfmodel.hip): couple_sea_land (coupler.f90:30-38) and
 // set_forcing parts 2 and 4 (forcing.f90:55-62, :84-99), one thread per column of ONE state.  A surface model keeps its fields in
 // one device array of SM_TOTAL fields of ncol doubles: field n at f + n * ncol, month mo (0-based) of a climatology c at

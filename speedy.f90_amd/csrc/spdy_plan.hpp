@@ -1,6 +1,6 @@
 // Internal: the plan object behind include/spdy.h and the helpers shared by the C-ABI translation units
 // (spdy_api.hip: plan, transforms, operators, graphs; spdy_api_step.hip: time-step tail, output; spdy_api_shard.hip:
-// collectives; spdy_api_physics.hip: column physics).
+// collectives; spdy_api_physics.hip: column physics; spdy_api_surfmodel.hip, spdy_api_sppt.hip: the objects made on a plan).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +50,9 @@ struct spdy_plan {
     double *physics_ws = nullptr;     // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
     double *physics_grid = nullptr;   // physics from spectra: (5kx+1) grids u | v | t | q | phi | ln ps, then one state's chain workspace
                                       // of (3kx+12) grids (spdy_physics_workspace)
+    double *sppt_ws = nullptr;        // SPPT on gridded states: the dynamics tendencies, (2kx+2) grids per state, max_batch states
+                                      // (spdy_column_physics_sppt_workspace)
+    double *sppt_grid = nullptr;      // SPPT from spectra: one state's (2kx+2) grids (spdy_physics_sppt_workspace)
     int physics_fused = -1;           // column physics in one launch: -1 unset (spdy_physics_dev only), 0 never, 1 always (spdy_plan_set_option)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
@@ -68,6 +71,16 @@ struct spdy_plan {
     std::vector<Span> spans;
     std::vector<spdy_graph *> graphs; // graphs captured from this plan that are still alive
     std::vector<struct spdy_comm *> comms;   // communicators created on this plan that are still alive (spdy_api_shard.hip)
+};
+
+// The SPPT pattern behind include/spdy.h's spdy_sppt (csrc/spdy_api_sppt.hip); spdy_physics_sppt_dev reads pattern and mu.
+struct spdy_sppt {
+    spdy_plan *plan = nullptr;
+    spdy::SpptTables tab;
+    spdy::SpptState *d_state = nullptr;   // the counter and the seed
+    double *d_sigma = nullptr;            // (mx, nx)
+    double *d_eta = nullptr, *d_spec = nullptr;   // (mx, nx, kx) complex
+    double *d_pattern = nullptr;          // (ix, il, kx)
 };
 
 namespace spdy_detail {

@@ -6,8 +6,9 @@
 // ((ttend + tt_rsw) + tt_rlw before + tt_pbl): surface_fluxes_kernel turns the down half's ssrd / slrd into the ts and
 // slru(:,:,3) the up half reads and the four averaged fluxes, pbl_kernel reads those after the up half.
 //
-// Out of scope, as in the reference's own configuration: SPPT (physics.f90:208-222; sppt_on is .false. in params.f90 and it needs
-// a random spectral pattern) and the second get_surface_fluxes call (sea_coupling_flag > 0, lfluxland = .false.: the reference's
+// SPPT (physics.f90:208-222; sppt_on is .false. in params.f90) follows the boundary layer: csrc/spdy_sppt.hip makes the pattern and
+// brackets the five calls, csrc/spdy_column_chain.hip applies it in the one launch.  Out of scope, as in the reference's own
+// configuration: the second get_surface_fluxes call (sea_coupling_flag > 0, lfluxland = .false.: the reference's
 // sea model stops with "not implemented" for those flags and that path reads ks unset).  Only lfluxland = .true. is built.
 //
 // Reproduced as they are: fhum0 = 0, so both rel_hum_to_spec_hum branches are dead, q1 = qa(:,:,kx) and rh is never read -- it

@@ -751,4 +751,37 @@ std::string surface_date_weights(int imont1, double tmonth, SurfaceDateWeights *
     return "";
 }
 
+// ---- sppt.f90:28-41, :76-84 ----------------------------------------------------------------------
+std::string SpptTables::build(const HostTables &t, int nsteps, const double *mu_in)
+{
+    if (nsteps <= 0) return "nsteps must be positive";
+    const double time_decorr = static_cast<double>(6.0f), len_decorr = static_cast<double>(500000.0f);
+    const double stddev = static_cast<double>(0.33f);
+    const double ph = std::exp(-(24 / static_cast<double>(nsteps)) / time_decorr);
+    // f0 = sum((2n+1) exp(-0.5 (len_decorr/rearth)**2 n (n+1)), n = 1 .. trunc), left to right as the reference writes it
+    const double r = len_decorr / kRearth, r2 = r * r;
+    double sum = 0.0;
+    for (int n = 1; n <= t.trunc; ++n) sum = sum + (2 * n + 1) * std::exp(-(0.5 * r2 * n * (n + 1)));
+    const double var = 1 - ph * ph;
+    const double f = std::sqrt((stddev * stddev * var) / (2 * sum));
+    phi.assign(1, ph);
+    f0.assign(1, f);
+    first.assign(1, std::pow(var, static_cast<double>(-0.5f)));
+    const double c = 0.25 * (len_decorr * len_decorr);
+    sigma.assign(t.el2.size(), 0.0);
+    for (size_t i = 0; i < sigma.size(); ++i) sigma[i] = f * std::exp(-(c * t.el2[i]));
+    mu.assign(t.kx, 1.0);
+    if (mu_in) mu.assign(mu_in, mu_in + t.kx);
+    return "";
+}
+
+const std::vector<double> *SpptTables::lookup(const std::string &name) const
+{
+    const std::pair<const char *, const std::vector<double> *> all[] = {
+        {"phi", &phi}, {"f0", &f0}, {"first", &first}, {"sigma", &sigma}, {"mu", &mu}};
+    for (const auto &e : all)
+        if (name == e.first) return e.second;
+    return nullptr;
+}
+
 }  // namespace spdy

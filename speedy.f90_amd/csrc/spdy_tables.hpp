@@ -96,4 +96,15 @@ struct SurfaceDateWeights {
 };
 std::string surface_date_weights(int imont1, double tmonth, SurfaceDateWeights *w);
 
+// The constants of the SPPT pattern (sppt.f90:28-41, :76-84) for nsteps steps per day: phi = exp(-(24/nsteps)/6.0), f0 and
+// sigma (mx, nx) = f0 exp(-0.25 len_decorr**2 el2) over the whole rectangle, sigma(1,1) = f0 included (the reference perturbs the
+// global mean too; sigma is the same on every level), first = (1 - phi**2)**(-0.5), the factor of the first AR(1) step, and the
+// taper mu[kx].  stddev = 0.33 is a float32 value widened, len_decorr = 500000 and time_decorr = 6 are exact.
+struct SpptTables {
+    std::vector<double> phi, f0, first, sigma, mu;   // phi, f0, first: one value each
+    // mu: kx values or null = all ones.  Returns "" or an error text.
+    std::string build(const HostTables &t, int nsteps, const double *mu_in);
+    const std::vector<double> *lookup(const std::string &name) const;
+};
+
 }  // namespace spdy

@@ -845,6 +845,79 @@ module spdy_c
             type(c_ptr), intent(out) :: d_ptr
             integer(c_int) :: rc
         end function
+        ! SPPT (include/spdy.h): the pattern object and the column physics with it
+        function spdy_sppt_create(plan, nsteps, mu, seed, s) bind(C, name="spdy_sppt_create") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: plan, mu
+            integer(c_int), value :: nsteps
+            integer(c_long_long), value :: seed
+            type(c_ptr), intent(out) :: s
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_destroy(s) bind(C, name="spdy_sppt_destroy") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: s
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_reset(s, seed) bind(C, name="spdy_sppt_reset") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: s
+            integer(c_long_long), value :: seed
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_table(s, name, buf, cap) bind(C, name="spdy_sppt_table") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: s, buf
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: cap
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_field(s, name, d_ptr) bind(C, name="spdy_sppt_field") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: s
+            character(kind=c_char), intent(in) :: name(*)
+            type(c_ptr), intent(out) :: d_ptr
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_draws(s, draws) bind(C, name="spdy_sppt_draws") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: s
+            integer(c_long_long), intent(out) :: draws
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_advance_dev(s, d_eta) bind(C, name="spdy_sppt_advance_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: s, d_eta
+            integer(c_int) :: rc
+        end function
+        function spdy_column_physics_sppt_workspace(plan) bind(C, name="spdy_column_physics_sppt_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int) :: rc
+        end function
+        function spdy_column_physics_sppt_dev(plan, nb, d_pattern, mu, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, &
+                & rad_state, utend, vtend, ttend, qtend, out) bind(C, name="spdy_column_physics_sppt_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_column_physics_out
+            type(c_ptr), value :: plan, d_pattern, mu, ug, vg, tg, qg, phig, pslg, albsfc, rad_state, utend, vtend, ttend, qtend
+            integer(c_int), value :: nb, compute_sw
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_column_physics_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
+        function spdy_physics_sppt_workspace(plan) bind(C, name="spdy_physics_sppt_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int) :: rc
+        end function
+        function spdy_physics_sppt_dev(plan, s, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, &
+                & qtend, out) bind(C, name="spdy_physics_sppt_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_column_physics_out
+            type(c_ptr), value :: plan, s, vor, div, t, q, phi, ps, albsfc, rad_state, utend, vtend, ttend, qtend
+            integer(c_int), value :: compute_sw
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_column_physics_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: plan

@@ -19,8 +19,8 @@ import numpy as np
 from ._lib import check, load
 from .columns import (MOIST_2D, MOIST_3D, PBL_2D, PBL_3D, RAD_2D, RAD_3D, RAD_SW_2D, SFC_2D, SFC_3, SFC_BOUNDARY,  # noqa: F401
                       SURFACE_DEFAULT, SURFACE_FIELDS, SURFACE_ICE_COUPLING, SURFACE_LAND_COUPLING, SURFACE_SST_ANOMALY,
-                      SURFACE_TABLES, ColumnPhysics, ColumnPhysicsOut, DeviceField, MoistOut, PblOut, RadOut, RadSurface,
-                      SfcBoundary, SfcOut, SurfaceClim, SurfaceModel, _p)
+                      SPPT_FIELDS, SPPT_TABLES, SURFACE_TABLES, ColumnPhysics, ColumnPhysicsOut, DeviceField, MoistOut, PblOut, RadOut,
+                      RadSurface, SfcBoundary, SfcOut, Sppt, SurfaceClim, SurfaceModel, _p)
 
 RESOLUTIONS = {"t30": (30, 96, 24), "t63": (63, 192, 48)}   # trunc, ix, iy
 
