@@ -12,13 +12,14 @@ import pytest
 
 import coupledrun
 import longrun
+import modelstep
 import moist
 import physstep
 import surfmodel as sm
 import synth
 from conftest import TOL
+from modelstep import PROG
 from test_gpu_physics_run import KX, _checkpoint_errors
-from test_gpu_physics_step import PROG, _step, _workspace
 
 pytestmark = pytest.mark.gpu
 
@@ -35,27 +36,24 @@ def _device_run(sp, case, c, events, fault=None):
     il, ix, dt = sp.il, sp.ix, longrun.DELT
     shaped = {k: np.ascontiguousarray(v).reshape(v.shape[:-1] + (il, ix)) for k, v in c.items()}
     M = s.SurfaceModel(sp, shaped, sm.DELT)
-    D = {n: moist.dev(case.st[n]) for n in case.st}
-    W = _workspace(sp, KX)
+    D, W = modelstep.device_state(case.st), modelstep.Workspace(sp)
     out = sp.column_outputs(1, ("sfc", "rad"), names=("hfluxn", "shf", "evap", "ssrd"))
     F = dict(out["sfc"], **out["rad"])
     bnd, albsfc = M.boundary()
-    P = {"bnd": dict(bnd, albsfc=albsfc),
-         "rad": torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")}
+    P = {"bnd": dict(bnd, albsfc=albsfc), "rad": modelstep.radiation_state(sp)}
+    phys = lambda sw: modelstep.whole_physics(P, sw, out)
     torch.cuda.synchronize()
     date = sm.Date(*coupledrun.START)
     M.set_date(date.imont1, date.tmonth, date.tyear)
     M.couple_dev(0)                                           # initialize_coupler
     M.forcing_dev(D["qcorh"])                                 # set_forcing(0)
-    sp.initialize_implicit(0.5 * dt); _step(sp, D, W, KX, 0.5 * dt, True, physstep.shortwave_step(-1), P, 1, 1, 0.0, out=out); sp.synchronize()
-    sp.initialize_implicit(dt); _step(sp, D, W, KX, dt, True, physstep.shortwave_step(0), P, 1, 2, 0.0, out=out); sp.synchronize()
-    sp.initialize_implicit(2.0 * dt)
+    modelstep.startup(sp, dt, lambda j1, j2, dt_, n: modelstep.step(sp, D, W, dt_, j1, j2, 0.0, phys(physstep.shortwave_step(n))))
     couple = lambda: M.couple_dev(1, F["hfluxn"], F["shf"], F["evap"], F["ssrd"])     # day only tells 0 from > 0
     graphs = {}
     for sw in (True, False):
         for last in (False, True):
             with sp.graph_capture() as g:
-                _step(sp, D, W, KX, 2.0 * dt, True, sw, P, out=out)
+                modelstep.step(sp, D, W, 2.0 * dt, physics=phys(sw))
                 if last:
                     couple()
             graphs[sw, last] = g

@@ -6,10 +6,11 @@ import numpy as np
 import pytest
 
 import guards
+import modelstep
 import moist
 import synth
 from conftest import GOLDEN, TOL, VARIANTS
-from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, wave_relerr
+from dynstep import ROB, oracle_dynamics_step, wave_relerr
 from dynstep import state as dyn_state
 
 pytestmark = pytest.mark.gpu
@@ -110,20 +111,6 @@ def test_moist_physics_from_spectra(tag, oracle_factory):
     sp.close()
 
 
-def _step(sp, D, W, kx, dt, physics):
-    """One model step: inverse batch (+ grad ps) -> grid tendencies -> [geopotential + moist physics] -> direct batch + spectral
-    step (tendencies.f90:89-234, time_stepping.f90)."""
-    ug, vg, plain_g, px, py, U, V, PL, pvor, pdiv, pspec, phi, phim = W
-    sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g,
-                              D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
-    sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-    if physics:            # tendencies.f90:203-206 with time level j1 = 1
-        sp.geopotential_dev(D["t"][0], D["phis"], phim)
-        sp.moist_physics_dev(D["t"][0], D["tr"][0], phim, D["ps"][0], PL[kx:2 * kx], PL[2 * kx:3 * kx])
-    sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                      D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
-
-
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
 def test_step_with_moist_physics(tag, oracle_factory):
     """A whole T30 L8 / T63 L16 step with the moist block between the grid tendencies and the direct batch against
@@ -132,24 +119,19 @@ def test_step_with_moist_physics(tag, oracle_factory):
     import torch
     kx = VARIANTS[tag][3]
     sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
-    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
     dt = 2400.0
     sp.initialize_implicit(dt); o.tail_init(dt)
     st = moist.state(o, dyn_state(sp, 8000), 5150)
-    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")
-    c128 = lambda *s: torch.zeros(s, dtype=torch.complex128, device="cuda")
-    P = 3 * kx
-    W = (f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix), f64(P, il, ix), f64(P, il, ix),
-         f64(P + 1, il, ix), c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx), c128(kx, nx, mx))
-    fresh = lambda: {n: moist.dev(st[n]) for n in st}
+    W = modelstep.Workspace(sp)
+    fresh = lambda: modelstep.device_state(st)
     sp.moist_workspace()
     sp.use_own_stream()
     # plain launches
     D = fresh()
-    _step(sp, D, W, kx, dt, True)
+    modelstep.step(sp, D, W, dt, physics=modelstep.moist_physics())
     sp.synchronize()
     plain = {n: D[n].clone() for n in ("vor", "div", "t", "tr", "ps")}
-    PLd = W[7].cpu().numpy()
+    PLd = W.PL.cpu().numpy()
     rec = {}
     ref, out = oracle_dynamics_step(o, st, 2, dt, ROB, physics=moist.make_hook(rec))
     assert rec["margin"].min() >= moist.MIN_MARGIN
@@ -164,7 +146,7 @@ def test_step_with_moist_physics(tag, oracle_factory):
     D = fresh()
     torch.cuda.synchronize()
     with sp.graph_capture() as g:
-        _step(sp, D, W, kx, dt, True)
+        modelstep.step(sp, D, W, dt, physics=modelstep.moist_physics())
     g.launch()
     sp.synchronize()
     for n in plain:
@@ -172,7 +154,7 @@ def test_step_with_moist_physics(tag, oracle_factory):
     D0 = fresh()
     torch.cuda.synchronize()
     with sp.graph_capture() as g0:
-        _step(sp, D0, W, kx, dt, False)
+        modelstep.step(sp, D0, W, dt)
     n1, n0 = g.num_nodes(), g0.num_nodes()
     print("[graph nodes %s] adiabatic %d, with moist physics %d" % (tag, n0, n1))
     assert n1 - n0 == 3, (n0, n1)

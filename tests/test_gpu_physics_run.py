@@ -8,12 +8,14 @@ import numpy as np
 import pytest
 
 import longrun
+import modelstep
 import moist
 import physstep
 import synth
 from conftest import TOL
 from dynstep import wave_relerr
-from test_gpu_physics_step import PROG, TEND, _errors, _step, _workspace
+from modelstep import PROG
+from test_gpu_physics_step import TEND, _errors
 
 pytestmark = pytest.mark.gpu
 
@@ -55,20 +57,16 @@ def _device_run(sp, case, adiabatic_nodes=False):
     captured once each and replayed in the reference's cadence; nothing but replays between checkpoints.  The radiation state
     starts as NaN.  Returns ({n: clones of the prognostics and the radiation state after leapfrog step n}, node counts)."""
     import torch
-    il, ix, dt = sp.il, sp.ix, longrun.DELT
-    D = {n: moist.dev(case.st[n]) for n in case.st}
-    W = _workspace(sp, KX)
-    P = {"bnd": physstep.device_boundary(case.bnd, il, ix),
-         "rad": torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")}
+    dt = longrun.DELT
+    D, W, P = modelstep.device_state(case.st), modelstep.Workspace(sp), modelstep.physics_buffers(sp, case.bnd)
     torch.cuda.synchronize()
-    sp.initialize_implicit(0.5 * dt); _step(sp, D, W, KX, 0.5 * dt, True, physstep.shortwave_step(-1), P, 1, 1, 0.0); sp.synchronize()
-    sp.initialize_implicit(dt); _step(sp, D, W, KX, dt, True, physstep.shortwave_step(0), P, 1, 2, 0.0); sp.synchronize()
-    sp.initialize_implicit(2.0 * dt)
+    phys = lambda sw: modelstep.whole_physics(P, sw)
+    modelstep.startup(sp, dt, lambda j1, j2, dt_, n: modelstep.step(sp, D, W, dt_, j1, j2, 0.0, phys(physstep.shortwave_step(n))))
     graphs = {}
     torch.cuda.synchronize()
     for sw in (True, False):
         with sp.graph_capture() as g:
-            _step(sp, D, W, KX, 2.0 * dt, True, sw, P)
+            modelstep.step(sp, D, W, 2.0 * dt, physics=phys(sw))
         graphs[sw] = g
     nodes = {sw: g.num_nodes() for sw, g in graphs.items()}
     out = {}
@@ -80,7 +78,7 @@ def _device_run(sp, case, adiabatic_nodes=False):
             torch.cuda.synchronize()                      # the clones are torch's stream's, the next replay the plan's
     if adiabatic_nodes:
         with sp.graph_capture() as g0:
-            _step(sp, D, W, KX, 2.0 * dt, False)
+            modelstep.step(sp, D, W, 2.0 * dt)
         nodes["adiabatic"] = g0.num_nodes()
         g0.close()
     for g in graphs.values():
@@ -146,7 +144,7 @@ def test_resynchronised_steps(name, oracle_factory):
     assert sorted(pre) == sorted(physstep.RESYNC)
     sp.initialize_implicit(dt)
     bnd = physstep.device_boundary(case.bnd, il, ix)
-    W = _workspace(sp, KX)
+    W = modelstep.Workspace(sp)
     errs = {}
     for n in physstep.RESYNC:
         sw, st = physstep.shortwave_step(n), pre[n]["st"]
@@ -179,16 +177,16 @@ def test_resynchronised_steps(name, oracle_factory):
         for name, e in _rad_errors(S.cpu().numpy().reshape(-1, ncol), after).items():
             errs["%s state %s" % (label, name)] = e
         # (ii) the whole step
-        D = {k: moist.dev(v) for k, v in st.items()}
+        D = modelstep.device_state(st)
         P = {"bnd": bnd, "rad": moist.dev(physstep.rad_state_array(pre[n]["rs"], KX).reshape(-1))}
         torch.cuda.synchronize()
-        _step(sp, D, W, KX, dt, True, sw, P, out={"rad": {"ssrd": held}})
+        modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, sw, out={"rad": {"ssrd": held}}))
         sp.synchronize()
         label = "step %d whole" % n
         for k in PROG:
             g = D[k].cpu().numpy()
             errs["%s %s" % (label, k)] = max(synth.relerr(g, pre[n]["new"][k]), wave_relerr(g, pre[n]["new"][k]))
-        errs["%s PL" % label] = synth.relerr(W[7].cpu().numpy(), pre[n]["out"]["PL"])
+        errs["%s PL" % label] = synth.relerr(W.PL.cpu().numpy(), pre[n]["out"]["PL"])
         for name, e in _rad_errors(P["rad"].cpu().numpy().reshape(-1, ncol), after).items():
             errs["%s state %s" % (label, name)] = e
     assert all(v == v for v in errs.values()), [k for k, v in errs.items() if v != v]

@@ -5,18 +5,19 @@ against oracle_dynamics_step, captured and replayed, and twice from the same inp
 import numpy as np
 import pytest
 
+import modelstep
 import moist
 import physstep
 import radiation
 import surface
 import synth
 from conftest import TOL, VARIANTS
-from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, wave_relerr
+from dynstep import ROB, oracle_dynamics_step, wave_relerr
+from modelstep import PROG
 
 pytestmark = pytest.mark.gpu
 
 TEND = ("utend", "vtend", "ttend", "qtend")
-PROG = ("vor", "div", "t", "tr", "ps")
 
 
 def _plan_case(tag, oracle_factory):
@@ -147,49 +148,6 @@ def test_one_launch_equals_five_calls(tag, nb):
     sp.close()
 
 
-def _step(sp, D, W, kx, dt, physics, sw=False, P=None, j1=2, j2=2, eps=ROB, out=None):
-    """_step of tests/test_gpu_moist.py with geopotential_dev + physics_dev in place of the moist call: step(j1, j2, dt) of
-    time_stepping.f90:35-121.  The dynamics read time level j2 (tendencies.f90:89-107); the physics always read level 1
-    (physics.f90:94-104).  out: physics_dev's optional outputs (e.g. {"rad": {"ssrd": held}} to supply the held ssrd)."""
-    ug, vg, plain_g, px, py, U, V, PL, pvor, pdiv, pspec, phi, phim = W
-    lv = j2 - 1
-    sp.inverse_batch_segs_dev(D["vor"][lv], D["div"][lv], ug, vg, [D[n][lv] for n in ("vor", "div", "t", "tr")], plain_g,
-                              D["ps"][lv:lv + 1], px, py, kcos_pairs=2, kcos=1)
-    sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-    if physics:            # tendencies.f90:203-206
-        sp.geopotential_dev(D["t"][0], D["phis"], phim)
-        sp.physics_dev(sw, D["vor"][0], D["div"][0], D["t"][0], D["tr"][0], phim, D["ps"][0], P["bnd"], P["bnd"]["albsfc"], P["rad"],
-                       U[:kx], V[:kx], PL[kx:2 * kx], PL[2 * kx:3 * kx], out)
-    sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                      D["tcorh"], D["qcorh"], SDRAG, j1, dt, eps, WIL, phi, kcos=2)
-
-
-def _workspace(sp, kx):
-    import torch
-    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
-    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")
-    c128 = lambda *s: torch.zeros(s, dtype=torch.complex128, device="cuda")
-    P = 3 * kx
-    return (f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix), f64(P, il, ix), f64(P, il, ix),
-            f64(P + 1, il, ix), c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx), c128(kx, nx, mx))
-
-
-def _three_steps(sp, case, kx, dt, run):
-    """three consecutive steps, shortwave on the first only (nstrad = 3), one radiation state held throughout; run(D, W, P, sw)
-    performs one step.  Returns the prognostics and the PL operands after each step."""
-    import torch
-    D = {n: moist.dev(case.st[n]) for n in case.st}
-    W = _workspace(sp, kx)
-    P = {"bnd": physstep.device_boundary(case.bnd, sp.il, sp.ix),
-         "rad": torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")}
-    after = []
-    for step in range(3):
-        run(D, W, P, step == 0)
-        sp.synchronize()
-        after.append(dict({n: D[n].clone() for n in PROG}, PL=W[7].clone(), rad=P["rad"].clone()))
-    return after, D, W, P
-
-
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
 def test_step_with_whole_physics(tag, oracle_factory):
     """Three consecutive T30 L8 / T63 L16 steps with the whole physics against three oracle_dynamics_step(physics=hook) calls:
@@ -203,8 +161,8 @@ def test_step_with_whole_physics(tag, oracle_factory):
     sp.initialize_implicit(dt); o.tail_init(dt)
     sp.physics_workspace()
     sp.use_own_stream()
-    plain_run = lambda D, W, P, sw: _step(sp, D, W, kx, dt, True, sw, P)
-    got, _, _, _ = _three_steps(sp, case, kx, dt, plain_run)
+    plain_run = lambda D, W, P, sw: modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, sw))
+    got, _, _, _ = modelstep.three_steps(sp, case, dt, plain_run)
     # the reference: margins and coverage first, then the comparison
     st, rs, rec, worst = case.st, {}, {}, 0.0
     refs = []
@@ -222,7 +180,7 @@ def test_step_with_whole_physics(tag, oracle_factory):
     assert worst <= TOL, worst
 
     # determinism: a second run from the same inputs
-    again, _, _, _ = _three_steps(sp, case, kx, dt, plain_run)
+    again, _, _, _ = modelstep.three_steps(sp, case, dt, plain_run)
     for step in range(3):
         for n in got[step]:
             assert torch.equal(again[step][n], got[step][n]), ("second run", step, n)
@@ -234,10 +192,10 @@ def test_step_with_whole_physics(tag, oracle_factory):
         if sw not in graphs:
             torch.cuda.synchronize()
             with sp.graph_capture() as g:
-                _step(sp, D, W, kx, dt, True, sw, P)
+                plain_run(D, W, P, sw)
             graphs[sw] = g
         graphs[sw].launch()
-    cap, D, W, P = _three_steps(sp, case, kx, dt, captured_run)
+    cap, D, W, P = modelstep.three_steps(sp, case, dt, captured_run)
     for step in range(3):
         for n in got[step]:
             assert torch.equal(cap[step][n], got[step][n]), ("captured", step, n)
@@ -254,9 +212,9 @@ def test_step_with_whole_physics(tag, oracle_factory):
     for step in range(3):
         graphs[step == 0].launch()
         sp.synchronize()
-        rep.append(dict({n: D[n].clone() for n in PROG}, PL=W[7].clone(), rad=P["rad"].clone()))
+        rep.append(modelstep.snapshot(D, W, P))
     case2 = type("C", (), {"st": case.st, "bnd": bnd2})
-    new, _, _, _ = _three_steps(sp, case2, kx, dt, plain_run)
+    new, _, _, _ = modelstep.three_steps(sp, case2, dt, plain_run)
     changed = 0
     for step in range(3):
         for n in new[step]:
@@ -265,21 +223,21 @@ def test_step_with_whole_physics(tag, oracle_factory):
     assert changed >= 12                                  # the replays followed the new date and boundary values
 
     # node counts against the adiabatic step
-    D0 = {n: moist.dev(case.st[n]) for n in case.st}
+    D0 = modelstep.device_state(case.st)
     torch.cuda.synchronize()
     with sp.graph_capture() as g0:
-        _step(sp, D0, W, kx, dt, False)
+        modelstep.step(sp, D0, W, dt)
     n0, n1, n1s = g0.num_nodes(), graphs[False].num_nodes(), graphs[True].num_nodes()
     print("[graph nodes %s] adiabatic %d, whole physics in one launch %d (shortwave %d)" % (tag, n0, n1, n1s))
     assert n1 - n0 == 3 and n1s - n0 == 3, (n0, n1, n1s)
     sp.set_option("physics_fused", 0)
     with sp.graph_capture() as g5:
-        _step(sp, D0, W, kx, dt, True, True, P)
+        plain_run(D0, W, P, True)
     print("[graph nodes %s] whole physics as five calls, shortwave: %d" % (tag, g5.num_nodes()))
     assert g5.num_nodes() - n0 > 3
     # spdy_physics_dev under option 0 against the default, bit for bit
     sp.radiation_set_date(radiation.DATES[0])
-    five, _, _, _ = _three_steps(sp, case, kx, dt, plain_run)
+    five, _, _, _ = modelstep.three_steps(sp, case, dt, plain_run)
     for step in range(3):
         for n in got[step]:
             assert torch.equal(five[step][n], got[step][n]), ("five calls", step, n)

@@ -23,6 +23,7 @@ import threading
 import numpy as np
 import pytest
 
+import modelstep
 import synth
 from conftest import TOL, VARIANTS
 from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, state, wave_relerr
@@ -43,28 +44,17 @@ def make_plan(tag, device=0):
 
 
 def unsharded_device_steps(sp, st, nsteps):
-    """The three-call device step (tests/test_gpu_step.py) on one plan: prognostics, tendencies and direct-batch operands."""
+    """The three-call device step (tests/modelstep.py) on one plan: prognostics, tendencies and direct-batch operands."""
     import torch
-    kx, nx, mx, il, ix = sp.kx, sp.nx, sp.mx, sp.il, sp.ix
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    D = {n: dev(st[n]) for n in st}
-    P = 3 * kx
-    c128 = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device="cuda")
-    f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
-    ug, vg, plain_g, px, py = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix)
-    U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
-    pvor, pdiv, pspec, phi = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx)
+    kx = sp.kx
+    D, W = modelstep.device_state(st), modelstep.Workspace(sp)
     for _ in range(nsteps):
-        sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g, D["ps"][1:2], px, py,
-                                  kcos_pairs=2, kcos=1)
-        sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-        sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"],
-                                          D["qcorh"], SDRAG, 2, DT, ROB, WIL, phi, kcos=2)
+        modelstep.step(sp, D, W, DT)
     torch.cuda.synchronize()
     out = {n: D[n].cpu().numpy() for n in PROGS}
-    out["phi"] = phi.cpu().numpy()
-    out["tend"] = np.concatenate([pvor[:kx].cpu().numpy(), pdiv.cpu().numpy(), pspec[P:].cpu().numpy()])   # vordt | divdt | tdt | trdt | psdt
-    out["U"], out["V"], out["PL"] = U.cpu().numpy(), V.cpu().numpy(), PL.cpu().numpy()
+    out["phi"] = W.phi.cpu().numpy()
+    out["tend"] = np.concatenate([W.pvor[:kx].cpu().numpy(), W.pdiv.cpu().numpy(), W.pspec[3 * kx:].cpu().numpy()])   # vordt | divdt | tdt | trdt | psdt
+    out["U"], out["V"], out["PL"] = W.U.cpu().numpy(), W.V.cpu().numpy(), W.PL.cpu().numpy()
     return out
 
 
@@ -310,22 +300,13 @@ def test_sharded_step_physics_hook(monkeypatch):
     import speedy_f90_amd as s
     monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
     sp = make_plan("t30")
-    kx, nx, mx, il, ix = sp.kx, sp.nx, sp.mx, sp.il, sp.ix
     st = state(sp, 8000)
-    D = {n: torch.from_numpy(np.ascontiguousarray(st[n])).cuda() for n in st}
-    P = 3 * kx
-    c128 = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device="cuda")
-    f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
-    ug, vg, plain_g, px, py = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix)
-    U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
-    pvor, pdiv, pspec, phi = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx)
-    inc = [torch.from_numpy(a).cuda() for a in _physics_increment(kx, il, ix)]
-    sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g, D["ps"][1:2], px, py,
-                              kcos_pairs=2, kcos=1)
-    sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-    U[:kx] += inc[0]; V[:kx] += inc[1]; PL[kx:2 * kx] += inc[2]; PL[2 * kx:3 * kx] += inc[3]
-    sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"],
-                                      SDRAG, 2, DT, ROB, WIL, phi, kcos=2)
+    D, W = modelstep.device_state(st), modelstep.Workspace(sp)
+    inc = [torch.from_numpy(a).cuda() for a in _physics_increment(sp.kx, sp.il, sp.ix)]
+
+    def add_increments(sp, D, W):
+        W.utend += inc[0]; W.vtend += inc[1]; W.ttend += inc[2]; W.qtend += inc[3]
+    modelstep.step(sp, D, W, DT, physics=add_increments)
     torch.cuda.synchronize()
     whole = {n: D[n].cpu().numpy() for n in PROGS}
     group = s.sharding.LocalGroup(sp.lib, 2)

@@ -5,13 +5,15 @@ captured {advance; physics} replayed, and three consecutive time steps with SPPT
 import numpy as np
 import pytest
 
+import modelstep
 import moist
 import physstep
 import sppt
 import synth
 from conftest import TOL, VARIANTS
-from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, wave_relerr
-from test_gpu_physics_step import PROG, TEND, _gridded, _plan_case, _three_steps
+from dynstep import ROB, oracle_dynamics_step, wave_relerr
+from modelstep import PROG
+from test_gpu_physics_step import TEND, _gridded, _plan_case
 
 pytestmark = pytest.mark.gpu
 
@@ -240,21 +242,6 @@ def test_captured_advance_and_physics(tag, oracle_factory):
     sp.close()
 
 
-def _step(sp, D, W, kx, dt, sw, P, pat, advance=True):
-    """_step of tests/test_gpu_physics_step.py with SPPT: advance_dev, then physics_sppt_dev in place of physics_dev"""
-    ug, vg, plain_g, px, py, U, V, PL, pvor, pdiv, pspec, phi, phim = W
-    sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g,
-                              D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
-    sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-    sp.geopotential_dev(D["t"][0], D["phis"], phim)
-    if advance:
-        pat.advance_dev()
-    sp.physics_sppt_dev(pat, sw, D["vor"][0], D["div"][0], D["t"][0], D["tr"][0], phim, D["ps"][0], P["bnd"], P["bnd"]["albsfc"],
-                        P["rad"], U[:kx], V[:kx], PL[kx:2 * kx], PL[2 * kx:3 * kx])
-    sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                      D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
-
-
 @pytest.mark.parametrize("tag", TAGS)
 def test_three_steps_with_sppt(tag, oracle_factory):
     """The three-step case of tests/test_gpu_physics_step.py with SPPT on every step (noise drawn on the device) against
@@ -267,7 +254,8 @@ def test_three_steps_with_sppt(tag, oracle_factory):
     sp.physics_sppt_workspace()
     sp.use_own_stream()
     pat = s.Sppt(sp, 36, mu, seed=SEED)
-    got, _, _, _ = _three_steps(sp, case, kx, dt, lambda D, W, P, sw: _step(sp, D, W, kx, dt, sw, P, pat))
+    sppt_step = lambda D, W, P, sw, advance=True: modelstep.step(sp, D, W, dt, physics=modelstep.sppt_physics(P, sw, pat, advance))
+    got, _, _, _ = modelstep.three_steps(sp, case, dt, sppt_step)
     assert pat.draws() == 3
     ref = sppt.Pattern(o)
     st, rs, rec, refs = case.st, {}, {}, []
@@ -302,8 +290,8 @@ def test_three_steps_with_sppt(tag, oracle_factory):
 
     def skipping(D, W, P, sw):
         count[0] += 1
-        _step(sp, D, W, kx, dt, sw, P, pat, advance=count[0] != 2)
-    bad = worst_of(_three_steps(sp, case, kx, dt, skipping)[0])
+        sppt_step(D, W, P, sw, advance=count[0] != 2)
+    bad = worst_of(modelstep.three_steps(sp, case, dt, skipping)[0])
     print("[three steps with SPPT %s, advance skipped on step 2] worst %.1e" % (tag, bad))
     assert bad > TOL, bad
     sp.close()

@@ -13,9 +13,10 @@ import os
 import numpy as np
 import pytest
 
+import modelstep
 import synth
 from conftest import TOL, VARIANTS
-from dynstep import ROB, WIL, SDRAG, state, oracle_dynamics_step, wave_relerr
+from dynstep import ROB, WIL, SDRAG, state, wave_relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -270,76 +271,6 @@ def test_output_path(tag, oracle_factory):
     g.close(); sp.close()
 
 
-def run_dynamical_core_steps(sp, o, tag, one_launch_tail, nsteps=2, collect=False):
-    """Captures a COMPLETE adiabatic time step of the dynamical core on device-resident state into one graph, replays it
-    `nsteps` times against the oracle's call-by-call sequence and returns, per step, {array: (relerr, wave_relerr)} for the
-    grid tendencies U, V, PL, the geopotential, the spectral tendencies the step leaves in place (separate-kernel tail only:
-    the one-launch tail keeps them in registers) and the five prognostics."""
-    import torch
-    kx = VARIANTS[tag][3]
-    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
-    dt = 2400.0
-    sp.initialize_implicit(dt); o.tail_init(dt)
-    st = state(sp, 8000)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    D = {n: dev(st[n]) for n in st}
-    P = 3 * kx
-    c128 = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device="cuda")
-    f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
-    ug, vg, plain_g = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix)     # plain = vorg | divg | tg | trg
-    px, py = f64(1, il, ix), f64(1, il, ix)
-    U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
-    pvor, pdiv, pspec, phi = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx)
-    plain_src = [D[n][1] for n in ("vor", "div", "t", "tr")]       # time level 2 of the four prognostic arrays, read in place
-    sp.use_own_stream()
-    torch.cuda.synchronize()
-    with sp.graph_capture() as g:
-        if one_launch_tail:      # ... and everything that goes to the grid as one call (one fused launch at T63)
-            sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, plain_src, plain_g, D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
-        else:
-            sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, plain_src, plain_g, kcos_pairs=2, kcos=1)
-            sp.grad_to_grid_dev(D["ps"][1:2], px, py, 2)
-        sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-        if one_launch_tail == "composite":   # direct batch + spectral step as one call (T63: vds applied on read, 5 launches)
-            sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                              D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
-        else:
-            sp.direct_batch_dev(U, V, pvor, pdiv, PL, pspec, kcos=2)
-        if one_launch_tail == "composite":
-            pass
-        elif one_launch_tail:    # the five spectral-space kernels below as ONE launch (spdy_spectral_step_dev)
-            sp.spectral_step_dev(pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"],
-                                 SDRAG, 2, dt, ROB, WIL, phi)
-        else:
-            sp.tendency_combine_dev(pdiv, pspec)
-            vordt, divdt, tdt, trdt, psdt = pvor[:kx], pdiv[:kx], pdiv[kx:2 * kx], pdiv[2 * kx:], pspec[P]
-            sp.spectral_tendencies_dev(D["div"][0], D["t"][0], D["ps"][0], D["phis"], divdt, tdt, psdt, phi)
-            sp.implicit_terms_dev(divdt, tdt, psdt)
-            sp.hdiff_step_dev(D["vor"][0], D["div"][0], D["t"][0], D["tr"][0], D["tcorh"], D["qcorh"], SDRAG, vordt, divdt, tdt, trdt)
-            sp.step_fields_dev([(D["ps"], psdt), (D["vor"], vordt), (D["div"], divdt), (D["t"], tdt), (D["tr"], trdt)], 2, dt, ROB, WIL)
-    ref, errs = st, {}
-    for step in range(nsteps):
-        g.launch()                                      # the graph is the whole step: nothing else runs between replays
-        sp.synchronize()
-        ref, out = oracle_dynamics_step(o, ref, 2, dt, ROB)
-        e = {}
-        for n, a in (("U", U), ("V", V), ("PL", PL)):
-            e[n] = (synth.relerr(a.cpu().numpy(), out[n]),) * 2
-        e["phi"] = (synth.relerr(phi.cpu().numpy(), out["phi"]), wave_relerr(phi.cpu().numpy(), out["phi"]))
-        if one_launch_tail == "composite":
-            vordt, divdt, tdt, trdt, psdt = pvor[:kx], pdiv[:kx], pdiv[kx:2 * kx], pdiv[2 * kx:], pspec[P]
-        if not one_launch_tail or one_launch_tail == "composite":
-            # the tendencies the spectral side leaves behind (after implicit correction and diffusion): the quantity the
-            # north star's 1e-12 names
-            for n, a in (("vordt", vordt), ("divdt", divdt), ("tdt", tdt), ("trdt", trdt), ("psdt", psdt)):
-                e[n] = (synth.relerr(a.cpu().numpy(), out[n]), wave_relerr(a.cpu().numpy(), out[n]))
-        for n in ("ps", "vor", "div", "t", "tr"):
-            e[n] = (synth.relerr(D[n].cpu().numpy(), ref[n]), wave_relerr(D[n].cpu().numpy(), ref[n]))
-        errs["step%d" % (step + 1)] = {k: (float(v[0]), float(v[1])) for k, v in e.items()}
-    g.close()
-    return errs
-
-
 @pytest.mark.parametrize("tag", ["t30", "t30k5", "t63k16"])
 def test_dynamical_core_step_vs_reference_step(tag):
     """The device step against the REFERENCE'S OWN step(): golden vectors of one call of time_stepping.f90 step(j1, j2, dt) --
@@ -354,35 +285,25 @@ def test_dynamical_core_step_vs_reference_step(tag):
     z = np.load(os.path.join(ROOT, "tests", "golden", "ref_dynstep.npz"))
     kx = VARIANTS[tag][3]
     sp = make_plan(tag, 4 * kx + 4)
-    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
     sub = DYN63_SUB if tag == "t63k16" else STEP_SUB
     st = state(sp, 8000)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    P = 3 * kx
-    c128 = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device="cuda")
-    f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
     for j1, j2, dt in (DYNSTEP_CASES if tag == "t30" else DYNSTEP_CASES[1:]):
         sp.initialize_implicit(dt)
-        D = {n: dev(st[n]) for n in st}
-        ug, vg, plain_g, px, py = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix)
-        U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
-        pvor, pdiv, pspec, phi = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx)
-        lv = j2 - 1
-        sp.inverse_batch_segs_dev(D["vor"][lv], D["div"][lv], ug, vg, [D[n][lv] for n in ("vor", "div", "t", "tr")], plain_g,
-                                  D["ps"][lv:lv + 1], px, py, kcos_pairs=2, kcos=1)
-        sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-        sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                          D["tcorh"], D["qcorh"], SDRAG, j1, dt, 0.0 if j1 == 1 else ROB, WIL, phi, kcos=2)
+        D, W = modelstep.device_state(st), modelstep.Workspace(sp)
+        modelstep.step(sp, D, W, dt, j1, j2, 0.0 if j1 == 1 else ROB)
         sp.synchronize()
         key = "%s_j%d%d_" % (tag, j1, j2)
         worst = 0.0
         for n in ("vor", "div", "t", "tr"):
             got, ref = D[n].cpu().numpy()[(Ellipsis,) + sub[1:]], z[key + n]
             worst = max(worst, synth.relerr(got, ref), wave_relerr(got, ref))
-        worst = max(worst, synth.relerr(D["ps"].cpu().numpy(), z[key + "ps"]), wave_relerr(phi.cpu().numpy()[sub], z[key + "phi"]))
+        worst = max(worst, synth.relerr(D["ps"].cpu().numpy(), z[key + "ps"]), wave_relerr(W.phi.cpu().numpy()[sub], z[key + "phi"]))
         print("\n[device step vs reference step() %s j1=%d j2=%d dt=%g] worst relative error %.1e" % (tag, j1, j2, dt, worst))
         assert worst <= TOL, (tag, j1, j2, worst)
     sp.close()
+
+
+FORMS = {False: "separate", True: "one_launch", "composite": "composite"}
 
 
 @pytest.mark.parametrize("one_launch_tail", [False, True, "composite"])
@@ -401,7 +322,7 @@ def test_dynamical_core_step_graph(tag, one_launch_tail, oracle_factory):
         norm -- the leapfrog adds dt * tendency (relative error <= 1e-12) to a filtered state that is exact to rounding."""
     kx = VARIANTS[tag][3]
     sp, o = make_plan(tag, 4 * kx + 4), oracle_factory(tag)
-    errs = run_dynamical_core_steps(sp, o, tag, one_launch_tail)
+    errs = modelstep.run_dynamical_core_steps(sp, o, FORMS[one_launch_tail])
     sp.close()
     print("\n[step errors %s one_launch=%s] " % (tag, one_launch_tail) + "; ".join(
         "%s: " % st + " ".join("%s %.1e/%.1e" % (n, e[0], e[1]) for n, e in d.items()) for st, d in errs.items()))
@@ -426,30 +347,13 @@ def test_two_day_run_vs_reference(case, oracle_factory):
     z = np.load(os.path.join(ROOT, "tests", "golden", "ref_run72.npz"))
     o = oracle_factory("t30")
     sp = make_plan("t30", 36)
-    kx, nx, mx, il, ix = sp.kx, sp.nx, sp.mx, sp.il, sp.ix
     st = longrun.rest_state(o, wind=longrun.CASES[case])
-    D = {n: torch.from_numpy(np.ascontiguousarray(st[n])).cuda() for n in st}
-    P = 3 * kx
-    c128 = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device="cuda")
-    f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")
-    ug, vg, plain_g, px, py = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix)
-    U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
-    pvor, pdiv, pspec, phi = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx)
-
-    def step(j1, j2, dt):
-        lv = j2 - 1
-        sp.inverse_batch_segs_dev(D["vor"][lv], D["div"][lv], ug, vg, [D[n][lv] for n in ("vor", "div", "t", "tr")], plain_g,
-                                  D["ps"][lv:lv + 1], px, py, kcos_pairs=2, kcos=1)
-        sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-        sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                          D["tcorh"], D["qcorh"], SDRAG, j1, dt, 0.0 if j1 == 1 else ROB, WIL, phi, kcos=2)
+    D, W = modelstep.device_state(st), modelstep.Workspace(sp)
     sp.use_own_stream()
     torch.cuda.synchronize()
-    sp.initialize_implicit(0.5 * longrun.DELT); step(1, 1, 0.5 * longrun.DELT); sp.synchronize()
-    sp.initialize_implicit(longrun.DELT); step(1, 2, longrun.DELT); sp.synchronize()
-    sp.initialize_implicit(2.0 * longrun.DELT)
+    modelstep.startup(sp, longrun.DELT, lambda j1, j2, dt, n: modelstep.step(sp, D, W, dt, j1, j2, 0.0))
     with sp.graph_capture() as g:
-        step(2, 2, 2.0 * longrun.DELT)
+        modelstep.step(sp, D, W, 2.0 * longrun.DELT)
     lines, worst = [], 0.0
     for n in range(1, longrun.NSTEPS + 1):
         g.launch()

@@ -17,10 +17,11 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import torch  # noqa: E402
 
+import modelstep  # noqa: E402
 import moist  # noqa: E402
 import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
-from dynstep import ROB, SDRAG, WIL, state as dyn_state  # noqa: E402
+from dynstep import state as dyn_state  # noqa: E402
 
 HBM = 8.0e12
 
@@ -63,37 +64,18 @@ def kernel_rates(res, kx, nbs, reps):
 
 
 def step_extra(res, kx, reps):
-    import speedy_f90_amd as s
     sp = s.Spectral(res, kx=kx, max_batch=4 * kx + 4, device=0)
     if kx == 16:
         sp.set_sigma(synth.SIGMA_L16)
-    nx, mx, il, ix = sp.nx, sp.mx, sp.il, sp.ix
     dt = 2400.0
     sp.initialize_implicit(dt)
-    st = dyn_state(sp, 8000)
-    D = {n: torch.from_numpy(np.ascontiguousarray(st[n])).cuda() for n in st}
-    f64 = lambda *sh: torch.zeros(sh, dtype=torch.float64, device="cuda")
-    c128 = lambda *sh: torch.zeros(sh, dtype=torch.complex128, device="cuda")
-    P = 3 * kx
-    ug, vg, plain_g, px, py = f64(kx, il, ix), f64(kx, il, ix), f64(4 * kx, il, ix), f64(1, il, ix), f64(1, il, ix)
-    U, V, PL = f64(P, il, ix), f64(P, il, ix), f64(P + 1, il, ix)
-    pvor, pdiv, pspec, phi, phim = c128(P, nx, mx), c128(P, nx, mx), c128(P + 1, nx, mx), c128(kx, nx, mx), c128(kx, nx, mx)
+    D, W = modelstep.device_state(dyn_state(sp, 8000)), modelstep.Workspace(sp)
     sp.moist_workspace()
     sp.use_own_stream()
-
-    def step(physics):
-        sp.inverse_batch_segs_dev(D["vor"][1], D["div"][1], ug, vg, [D[n][1] for n in ("vor", "div", "t", "tr")], plain_g,
-                                  D["ps"][1:2], px, py, kcos_pairs=2, kcos=1)
-        sp.grid_tendencies_dev(ug, vg, plain_g[2 * kx:3 * kx], plain_g[:kx], plain_g[kx:2 * kx], plain_g[3 * kx:], px, py, U, V, PL)
-        if physics:
-            sp.geopotential_dev(D["t"][0], D["phis"], phim)
-            sp.moist_physics_dev(D["t"][0], D["tr"][0], phim, D["ps"][0], PL[kx:2 * kx], PL[2 * kx:3 * kx])
-        sp.direct_batch_spectral_step_dev(U, V, PL, pvor, pdiv, pspec, D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"],
-                                          D["tcorh"], D["qcorh"], SDRAG, 2, dt, ROB, WIL, phi, kcos=2)
     res_ = {}
     for physics in (False, True):
         with sp.graph_capture() as g:
-            step(physics)
+            modelstep.step(sp, D, W, dt, physics=modelstep.moist_physics() if physics else None)
         # the state evolves under replay; a few hundred adiabatic / moist steps stay finite at these amplitudes
         res_["with" if physics else "without"] = {"us": round(time_fn(g.launch, reps), 2), "nodes": g.num_nodes()}
         g.close()

@@ -3,7 +3,7 @@
 (option 0), and of a whole captured time step with the whole physics in it.
 
 (a) spdy_column_physics_dev on gridded states, plain launches, with and without shortwave: T30 L8 at nb 1 / 64, T63 L16 at nb 1 / 16.
-(b) the captured step of tests/test_gpu_physics_step.py (inverse batch, grid tendencies, [geopotential + spdy_physics_dev], direct
+(b) the captured step of tests/modelstep.py (inverse batch, grid tendencies, [geopotential + spdy_physics_dev], direct
     batch + spectral step): adiabatic, with the physics as five calls, with the physics in one launch.
 Timing as tools/surface_rate.py: HIP events, 10 warm-up calls, the median of --repeats timings of --reps calls with the range.
 The forms compared are interleaved repeat by repeat in one process, so that clock and thermal drift fall on all of them alike.
@@ -21,6 +21,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import torch  # noqa: E402
 
+import modelstep  # noqa: E402
 import moist  # noqa: E402
 import physstep  # noqa: E402
 import radiation  # noqa: E402
@@ -28,7 +29,6 @@ import surface  # noqa: E402
 import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
 from conftest import VARIANTS  # noqa: E402
-from test_gpu_physics_step import _step, _workspace  # noqa: E402
 
 TEND = ("utend", "vtend", "ttend", "qtend")
 
@@ -109,11 +109,8 @@ def step(tag, reps, repeats, rows):
     dt = physstep.DT[tag]
     sp.initialize_implicit(dt)
     sp.physics_workspace()
-    W = _workspace(sp, kx)
-    P = {"bnd": physstep.device_boundary(case.bnd, sp.il, sp.ix),
-         "rad": torch.zeros(sp.radiation_state_size(), dtype=torch.float64, device="cuda")}
-    D = {n: moist.dev(case.st[n]) for n in case.st}
-    _step(sp, D, W, kx, dt, True, True, P)           # a shortwave step first: the radiation state is whole
+    W, P, D = modelstep.Workspace(sp), modelstep.physics_buffers(sp, case.bnd, 0.0), modelstep.device_state(case.st)
+    modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, True))     # a shortwave step first: the radiation state is whole
     sp.synchronize()
     graphs = {}
     for name, opt, phys, sw in (("adiabatic", None, False, False), ("five_calls_sw", 0, True, True), ("five_calls", 0, True, False),
@@ -124,7 +121,7 @@ def step(tag, reps, repeats, rows):
         Dg = {n: D[n].clone() for n in D}
         torch.cuda.synchronize()
         with sp.graph_capture() as g:
-            _step(sp, Dg, W, kx, dt, phys, sw, P)
+            modelstep.step(sp, Dg, W, dt, physics=modelstep.whole_physics(P, sw) if phys else None)
         graphs[name] = (g, Dg)
     print("graph nodes:", {n: g.num_nodes() for n, (g, _) in graphs.items()}, flush=True)
     fns = {}

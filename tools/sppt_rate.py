@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of SPPT on the device: the pattern's advance alone (captured: noise + AR(1), inverse transform, clip) and
-the captured time step of tests/test_gpu_sppt.py with the whole physics, without SPPT (spdy_physics_dev: the path as it was) and
+the captured time step of tests/modelstep.py with the whole physics, without SPPT (spdy_physics_dev: the path as it was) and
 with it ({advance; spdy_physics_sppt_dev}), the physics as five calls and in one launch; T30 L8 and T63 L16, no shortwave.
 Timing as tools/physics_step_rate.py: HIP events, 10 warm-up calls, the median of --repeats timings of --reps calls with the
 range, the forms interleaved repeat by repeat in one process.
@@ -18,14 +18,13 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
 
+import modelstep  # noqa: E402
 import moist  # noqa: E402
 import physstep  # noqa: E402
 import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
 from conftest import VARIANTS  # noqa: E402
 from physics_step_rate import report, time_interleaved  # noqa: E402
-from test_gpu_physics_step import _step, _workspace  # noqa: E402
-from test_gpu_sppt import _step as _step_sppt  # noqa: E402
 
 
 def step(tag, reps, repeats, rows):
@@ -41,12 +40,9 @@ def step(tag, reps, repeats, rows):
     dt = physstep.DT[tag]
     sp.initialize_implicit(dt)
     sp.physics_sppt_workspace()
-    W = _workspace(sp, kx)
-    P = {"bnd": physstep.device_boundary(case.bnd, sp.il, sp.ix),
-         "rad": torch.zeros(sp.radiation_state_size(), dtype=torch.float64, device="cuda")}
-    D = {n: moist.dev(case.st[n]) for n in case.st}
+    W, P, D = modelstep.Workspace(sp), modelstep.physics_buffers(sp, case.bnd, 0.0), modelstep.device_state(case.st)
     pat = s.Sppt(sp, 36, np.clip(np.linspace(-0.5, 1.5, kx), 0.0, 1.0), seed=1)
-    _step(sp, D, W, kx, dt, True, True, P)           # a shortwave step first: the radiation state is whole
+    modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, True))     # a shortwave step first: the radiation state is whole
     sp.synchronize()
     graphs = {}
     with sp.graph_capture() as g:
@@ -57,10 +53,7 @@ def step(tag, reps, repeats, rows):
         Dg = {n: D[n].clone() for n in D}           # every graph steps its own copy of the state
         torch.cuda.synchronize()
         with sp.graph_capture() as g:
-            if sppt:
-                _step_sppt(sp, Dg, W, kx, dt, False, P, pat)
-            else:
-                _step(sp, Dg, W, kx, dt, True, False, P)
+            modelstep.step(sp, Dg, W, dt, physics=modelstep.sppt_physics(P, False, pat) if sppt else modelstep.whole_physics(P, False))
         graphs[name] = (g, Dg)
     print("graph nodes:", {n: g.num_nodes() for n, (g, _) in graphs.items()}, flush=True)
     torch.cuda.synchronize()

@@ -4,7 +4,7 @@ HIP events, 10 warm-up calls, the median of --repeats timings of --reps calls wi
 repeat in one process.  For T30 L8 and T63 L16:
 
 (a) spdy_surface_model_couple_dev and spdy_surface_model_forcing_dev alone, plain launches;
-(b) the captured step of tests/test_gpu_physics_step.py with the whole physics (no shortwave): as the parent commit has it
+(b) the captured step of tests/modelstep.py with the whole physics (no shortwave): as the parent commit has it
     (caller-owned boundary arrays, no flux outputs), reading the surface model's arrays and writing hfluxn / shf / evap / ssrd,
     and the same with couple_dev as the graph's last node;
 (c) a model day: 36 replays of the step with couple_dev, one spdy_surface_model_set_date and one forcing_dev, against 36 replays
@@ -24,6 +24,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 import torch  # noqa: E402
 
 import longrun  # noqa: E402
+import modelstep  # noqa: E402
 import moist  # noqa: E402
 import physstep  # noqa: E402
 import surfmodel as sm  # noqa: E402
@@ -31,7 +32,6 @@ import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
 from conftest import VARIANTS  # noqa: E402
 from physics_step_rate import report, time_interleaved  # noqa: E402
-from test_gpu_physics_step import _step, _workspace  # noqa: E402
 
 
 def run(tag, reps, repeats, rows):
@@ -51,20 +51,19 @@ def run(tag, reps, repeats, rows):
     c = sm.climatology(case.phis0, longrun.latitudes(sp.table("sia_half")))
     M = s.SurfaceModel(sp, {k: np.ascontiguousarray(v).reshape(v.shape[:-1] + (il, ix)) for k, v in c.items()}, sm.DELT)
     date = sm.Date(1982, 1, 15)
-    W = _workspace(sp, kx)
-    D = {n: moist.dev(case.st[n]) for n in case.st}
+    W, D = modelstep.Workspace(sp), modelstep.device_state(case.st)
     out = sp.column_outputs(1, ("sfc", "rad"), names=("hfluxn", "shf", "evap", "ssrd"))
     F = dict(out["sfc"], **out["rad"])
     bnd, albsfc = M.boundary()
-    rad = lambda: torch.zeros(sp.radiation_state_size(), dtype=torch.float64, device="cuda")
-    Pp = {"bnd": physstep.device_boundary(case.bnd, il, ix), "rad": rad()}       # the parent's step: caller-owned arrays
-    Pm = {"bnd": dict(bnd, albsfc=albsfc), "rad": rad()}
+    Pp = modelstep.physics_buffers(sp, case.bnd, 0.0)                            # the parent's step: caller-owned arrays
+    Pm = {"bnd": dict(bnd, albsfc=albsfc), "rad": modelstep.radiation_state(sp, 0.0)}
+    step = lambda D_, P, sw, o_=None: modelstep.step(sp, D_, W, dt, physics=modelstep.whole_physics(P, sw, o_))
     torch.cuda.synchronize()
     M.set_date(date.imont1, date.tmonth, date.tyear)
     M.couple_dev(0)
     M.forcing_dev(D["qcorh"])
-    _step(sp, D, W, kx, dt, True, True, Pp)            # a shortwave step first on each radiation state
-    _step(sp, D, W, kx, dt, True, True, Pm, out=out)
+    step(D, Pp, True)                                  # a shortwave step first on each radiation state
+    step(D, Pm, True, out)
     sp.synchronize()
     couple = lambda: M.couple_dev(1, F["hfluxn"], F["shf"], F["evap"], F["ssrd"])
     # (a)
@@ -76,7 +75,7 @@ def run(tag, reps, repeats, rows):
         Dg = {n: D[n].clone() for n in D}              # every graph steps its own copy of the state
         torch.cuda.synchronize()
         with sp.graph_capture() as g:
-            _step(sp, Dg, W, kx, dt, True, False, P, out=o_)
+            step(Dg, P, False, o_)
             if last:
                 couple()
         graphs[name] = g
