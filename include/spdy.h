@@ -720,6 +720,57 @@ int spdy_surface_model_forcing_dev(spdy_surface_model *m, double *qcorh);
 int spdy_surface_model_boundary(spdy_surface_model *m, spdy_sfc_boundary *bnd, const double **albsfc);
 int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d_ptr);
 
+/* ---- diagnostics: the run's guard (check_diagnostics, diagnostics.f90:16-75) ------------------------------------------------------
+ * The one call of the reference's main loop (speedy.f90:27-54) that looks at the state after every step: per level k, from the
+ * spectra of time level 2,
+ *     reke(k) = sum_{m=2..mx} sum_{n=1..nx} elm2(m,n) |vor(m,n,k)|**2      (the reference's -Re(inverse_laplacian(vor) conjg(vor)):
+ *     deke(k) = the same over div                                           the zonal column m = 1 left out, the whole rectangle)
+ *     temp(k) = sqrt(0.5) * Re t(1,1,k)                                     (sqrt(0.5) in float32, widened: 0.707106769084930...)
+ * and the run stops when for any level reke > 500, deke > 500, temp < 180 or temp > 320.  A spdy_diagnostics keeps all of it in
+ * device memory, so the guard runs inside a captured, replayed step and nothing is downloaded for it:
+ *   create    on a plan; owns history -- capacity rows of (3,kx) doubles reke | deke | temp, the memory order of the reference's
+ *             diag(kx,3); step s goes to row s mod capacity --, the four limits, and per level a state: the number of the next
+ *             step (64 bits; first_step >= 0 at first), the level's first offending step with the mask of what tripped there, and
+ *             the level's three numbers of the run's first offending step, outside the ring so that no wrap overwrites them.  On a
+ *             host-only plan create succeeds and every device call is SPDY_ERR_NO_DEVICE.  Destroy the object before its plan.
+ *   check_dev ONE launch on three device arrays of (mx,nx,kx) complex spectra and the plan's elm2; one workgroup per level.  It
+ *             allocates nothing and takes no host value that changes from step to step: a captured call records step s, s + 1, ...
+ *             on successive replays, with the pointers it was captured with.  temp is one load and one multiply, bit for bit the
+ *             reference's; the sums have a fixed thread-to-coefficient map and a fixed reduction tree and no atomics, so they are
+ *             the same bits on every run and within 2 (mx nx - 1) 2**-53 of the reference's sequential sums (every term is >= 0).
+ *             Mask bits: SPDY_DIAG_REKE, _DEKE, _TEMP_LOW, _TEMP_HIGH are the reference's four comparisons, strict, as written (a
+ *             NaN satisfies none: the reference would run on); SPDY_DIAG_NONFINITE is set when any of the level's three numbers
+ *             is not finite.  A level's first nonzero mask is sticky: later in-range steps do not clear it, later offences do
+ *             not replace it.
+ *   set_limits reke, deke, temp low, temp high (host; NULL = 500, 500, 180, 320); reset: a new next step, no offence, an empty
+ *             history.  Both stream-ordered, not callable during a capture; a captured check_dev uses them on its next replay.
+ *   status    synchronises the plan's stream and downloads the state: next_step; bad_step = -1 when nothing has tripped,
+ *             otherwise the earliest offending step over all levels, bad_level the lowest level index (0-based) that tripped at
+ *             that step, bad_mask the OR of the masks of all levels that tripped at it, bad_row the (3,kx) row of that step (left
+ *             alone when nothing tripped).  Any of the five result pointers may be NULL.  SPDY_ERR_STATE inside a capture, or if
+ *             the levels' step counters disagree (a check_dev still in flight on another stream).
+ *   read      synchronises and downloads count rows starting at step into rows (count,3,kx); SPDY_ERR_ARG for steps not yet
+ *             written (or from before the last reset) or already overwritten; SPDY_ERR_STATE inside a capture.
+ *   field     device pointers that never change: "history", "state", "limits".
+ *   format    host only, no object needed: the reference's three lines (diagnostics.f90:72-74) for one (3,kx) row -- ' step =',
+ *             i6, ' reke =', then f8.2 fields; the deke and temp lines with 13x; for kx > 10 Fortran's format reversion: each
+ *             further record holds up to ten f8.2 fields and nothing else.  Every record ends with a newline.  Returns the
+ *             number of characters without the terminator (buf NULL: the size query); cap below that + 1 is SPDY_ERR_ARG.
+ * A device-resident main loop: forcing, step, check_dev on time level 2, couple; status once per output interval.
+ * Checks: a NULL object, NULL spectra, rows or name, capacity < 1, a negative step: SPDY_ERR_ARG.                               */
+enum { SPDY_DIAG_REKE = 1, SPDY_DIAG_DEKE = 2, SPDY_DIAG_TEMP_LOW = 4, SPDY_DIAG_TEMP_HIGH = 8, SPDY_DIAG_NONFINITE = 16 };
+typedef struct spdy_diagnostics spdy_diagnostics;
+int spdy_diagnostics_create(spdy_plan *plan, int capacity, long long first_step, spdy_diagnostics **d);
+int spdy_diagnostics_destroy(spdy_diagnostics *d);
+int spdy_diagnostics_set_limits(spdy_diagnostics *d, const double *limits);
+int spdy_diagnostics_reset(spdy_diagnostics *d, long long next_step);
+int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const double *div, const double *t);
+int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask,
+                            double *bad_row);
+int spdy_diagnostics_read(spdy_diagnostics *d, long long step, int count, double *rows);
+int spdy_diagnostics_field(spdy_diagnostics *d, const char *name, void **d_ptr);
+int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf, int cap);
+
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,
  * time_stepping.f90:56-121: ~90 inverse and ~70 direct transforms plus the spectral operators, 7 horizontal

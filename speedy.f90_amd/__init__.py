@@ -12,5 +12,6 @@ The directory name contains a dot, so import it through the repo-root shim
 ``import speedy_f90_amd`` (speedy_f90_amd.py).
 """
 from ._lib import LIB_PATH, SpdyError, build, load  # noqa: F401
-from .spectral import RESOLUTIONS, DeviceField, Graph, Spectral, Sppt, SurfaceModel, check  # noqa: F401
+from .spectral import (RESOLUTIONS, DeviceField, Diagnostics, DiagnosticsStop, Graph, Spectral, Sppt, SurfaceModel,  # noqa: F401
+                       check)
 from . import sharding  # noqa: F401

@@ -140,6 +140,16 @@ SIGNATURES = {
     "spdy_column_physics_sppt_dev": [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 14,
     "spdy_physics_sppt_workspace": [c_void_p],
     "spdy_physics_sppt_dev": [c_void_p, c_void_p, c_int] + [c_void_p] * 14,
+    "spdy_diagnostics_create": [c_void_p, c_int, ctypes.c_longlong, ctypes.POINTER(c_void_p)],
+    "spdy_diagnostics_destroy": [c_void_p],
+    "spdy_diagnostics_set_limits": [c_void_p, c_void_p],
+    "spdy_diagnostics_reset": [c_void_p, ctypes.c_longlong],
+    "spdy_diagnostics_check_dev": [c_void_p, c_void_p, c_void_p, c_void_p],
+    "spdy_diagnostics_status": [c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int),
+                                ctypes.POINTER(c_int), c_void_p],
+    "spdy_diagnostics_read": [c_void_p, ctypes.c_longlong, c_int, c_void_p],
+    "spdy_diagnostics_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
+    "spdy_diagnostics_format": [c_int, ctypes.c_longlong, c_void_p, c_char_p, c_int],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

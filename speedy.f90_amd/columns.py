@@ -304,6 +304,117 @@ class Sppt:
         check(self.lib.spdy_sppt_advance_dev(self.h, None if eta is None else ctypes.c_void_p(eta.data_ptr())))
 
 
+DIAG_REKE, DIAG_DEKE, DIAG_TEMP_LOW, DIAG_TEMP_HIGH, DIAG_NONFINITE = 1, 2, 4, 8, 16
+DIAG_REFERENCE = DIAG_REKE | DIAG_DEKE | DIAG_TEMP_LOW | DIAG_TEMP_HIGH      # what stops the reference (diagnostics.f90:61-62)
+DIAG_FIELDS = ("history", "state", "limits")
+
+
+class DiagnosticsStop(RuntimeError):
+    """The state left the accepted range: the reference's `stop 'Model variables out of accepted range'`."""
+
+    def __init__(self, msg, status):
+        super().__init__(msg)
+        self.status = status
+
+
+class Diagnostics:
+    """check_diagnostics on the device (spdy_diagnostics_* in include/spdy.h): per level reke, deke and temp of each checked step
+    in a ring of `capacity` rows, the step counter and the sticky first offence, all in device memory.
+
+    One step of a device-resident run: forcing, the step, check_dev on time level 2, couple; status() or raise_if_stopped() once
+    per output interval.  check_dev is one launch and capturable: each replay records the next step."""
+
+    def __init__(self, sp, capacity=64, first_step=0):
+        self.sp, self.lib, self.capacity = sp, sp.lib, int(capacity)
+        if sp.device >= 0:
+            sp._sync_stream()
+        h = ctypes.c_void_p()
+        check(self.lib.spdy_diagnostics_create(sp.h, self.capacity, int(first_step), ctypes.byref(h)))
+        self.h = h
+        # the plan closes its objects first (as its surface models)
+        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.spdy_diagnostics_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_limits(self, limits=None):
+        """reke, deke, temp low, temp high (None = the reference's 500, 500, 180, 320).  Stream-ordered; not during a capture."""
+        if limits is not None:
+            limits = np.ascontiguousarray(limits, np.float64)
+            if limits.shape != (4,):
+                raise ValueError("limits must hold four values")
+        self.sp._sync_stream()
+        check(self.lib.spdy_diagnostics_set_limits(self.h, None if limits is None else _p(limits)))
+
+    def reset(self, next_step=0):
+        """A new next step, no offence, an empty history.  Stream-ordered; not during a capture."""
+        self.sp._sync_stream()
+        check(self.lib.spdy_diagnostics_reset(self.h, int(next_step)))
+
+    def check_dev(self, vor, div, t):
+        """One launch on [kx, nx, mx] complex128 device tensors (time level 2 of the prognostics): the step's row, the range test,
+        the counter."""
+        self.sp._sync_stream()
+        check(self.lib.spdy_diagnostics_check_dev(self.h, *[ctypes.c_void_p(x.data_ptr()) for x in (vor, div, t)]))
+
+    def status(self):
+        """{"next_step", "bad_step" (-1: nothing tripped), "bad_level", "bad_mask", "bad_row" ([3, kx] or None)}; synchronises
+        the plan's stream."""
+        self.sp._sync_stream()
+        nxt, bad, lev, mask = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int(), ctypes.c_int()
+        row = np.zeros((3, self.sp.kx))
+        check(self.lib.spdy_diagnostics_status(self.h, ctypes.byref(nxt), ctypes.byref(bad), ctypes.byref(lev), ctypes.byref(mask), _p(row)))
+        return {"next_step": nxt.value, "bad_step": bad.value, "bad_level": lev.value, "bad_mask": mask.value,
+                "bad_row": row if bad.value >= 0 else None}
+
+    def read(self, step, count=1):
+        """The rows of steps step .. step + count - 1 as [count, 3, kx] (reke | deke | temp); synchronises the plan's stream."""
+        self.sp._sync_stream()
+        rows = np.zeros((int(count), 3, self.sp.kx))
+        check(self.lib.spdy_diagnostics_read(self.h, int(step), int(count), _p(rows)))
+        return rows
+
+    def field(self, name):
+        """"history" as a DeviceField [capacity, 3, kx], "limits" [4]; "state" as the device address (per-level records)."""
+        p = ctypes.c_void_p()
+        check(self.lib.spdy_diagnostics_field(self.h, name.encode(), ctypes.byref(p)))
+        if name == "state":
+            return p.value
+        return DeviceField(self.sp, p.value, (self.capacity, 3, self.sp.kx) if name == "history" else (4,))
+
+    def format(self, step, row):
+        """The reference's three printed lines (diagnostics.f90:72-74) for one [3, kx] row."""
+        return format_diagnostics(self.lib, step, row)
+
+    def raise_if_stopped(self):
+        """Raises DiagnosticsStop where the reference would stop: the status holds one of its four comparisons.  The message is
+        the reference's three lines and its stop message.  Returns the status otherwise (a non-finite value alone does not stop
+        the reference and is left to the caller: status["bad_mask"] & DIAG_NONFINITE)."""
+        st = self.status()
+        if st["bad_mask"] & DIAG_REFERENCE:
+            raise DiagnosticsStop(self.format(st["bad_step"], st["bad_row"]) + "Model variables out of accepted range", st)
+        return st
+
+
+def format_diagnostics(lib, step, row):
+    """spdy_diagnostics_format for a [3, kx] row (host only)"""
+    row = np.ascontiguousarray(row, np.float64)
+    if row.ndim != 2 or row.shape[0] != 3:
+        raise ValueError("row must be [3, kx]")
+    n = check(lib.spdy_diagnostics_format(row.shape[1], int(step), _p(row), None, 0))
+    buf = ctypes.create_string_buffer(n + 1)
+    check(lib.spdy_diagnostics_format(row.shape[1], int(step), _p(row), buf, n + 1))
+    return buf.value.decode()
+
+
 class ColumnPhysics:
     """The column-physics calls of a plan (a mixin of spectral.Spectral)."""
 

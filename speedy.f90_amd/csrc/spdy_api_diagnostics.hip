@@ -1,0 +1,231 @@
+// C ABI of the run's guard (include/spdy.h, "diagnostics"): check_diagnostics of diagnostics.f90 device-resident.  Kernel:
+// csrc/spdy_diagnostics.hip.  The object owns the history ring, the limits and the per-level state; the host side here creates
+// and resets them, downloads them (status, read) and writes the reference's three lines (format).
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "spdy_plan.hpp"
+
+using namespace spdy_detail;
+
+namespace {
+#define NEED_DIAG(d)                                                        \
+    do {                                                                    \
+        if (!(d)) return fail(SPDY_ERR_ARG, "null diagnostics object");     \
+    } while (0)
+
+constexpr int MAX_CAPACITY = 1 << 20;
+
+size_t row_doubles(const spdy_diagnostics *d) { return (size_t)3 * d->plan->tab.kx; }
+
+// the state of a run that starts at next_step and an empty ring, stream-ordered
+int restart(spdy_diagnostics *d, long long next_step)
+{
+    spdy_plan *p = d->plan;
+    spdy::DiagLevel l{};
+    l.next_step = next_step; l.bad_step = -1; l.row_step = -1;
+    const std::vector<spdy::DiagLevel> h((size_t)p->tab.kx, l);
+    HIP_TRY(hipMemsetAsync(d->d_history, 0, (size_t)d->capacity * row_doubles(d) * sizeof(double), p->stream));
+    HIP_TRY(hipMemcpyAsync(d->d_state, h.data(), h.size() * sizeof(l), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    d->start_step = next_step;
+    return SPDY_OK;
+}
+
+int upload_limits(spdy_diagnostics *d, const double *limits)
+{
+    static const double stock[4] = {500.0, 500.0, 180.0, 320.0};             // diagnostics.f90:61-62
+    spdy_plan *p = d->plan;
+    HIP_TRY(hipMemcpyAsync(d->d_limits, limits ? limits : stock, sizeof(stock), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
+int download_state(spdy_diagnostics *d, std::vector<spdy::DiagLevel> &h)
+{
+    spdy_plan *p = d->plan;
+    h.resize((size_t)p->tab.kx);
+    HIP_TRY(hipMemcpyAsync(h.data(), d->d_state, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    for (const auto &l : h)
+        if (l.next_step != h[0].next_step) return fail(SPDY_ERR_STATE, "the levels' step counters disagree (%lld, %lld)", h[0].next_step, l.next_step);
+    return SPDY_OK;
+}
+
+// Fortran's f8.2
+void f8_2(double x, char *out)
+{
+    char tmp[400];
+    if (std::isnan(x)) std::snprintf(tmp, sizeof(tmp), "%8s", "NaN");
+    else if (std::isinf(x)) std::snprintf(tmp, sizeof(tmp), "%8s", x > 0 ? "Inf" : "-Inf");
+    else std::snprintf(tmp, sizeof(tmp), "%8.2f", x);
+    std::memcpy(out, std::strlen(tmp) == 8 ? tmp : "********", 8);
+}
+}  // namespace
+
+extern "C" {
+
+int spdy_diagnostics_create(spdy_plan *p, int capacity, long long first_step, spdy_diagnostics **out)
+{
+    NEED_PLAN(p);
+    if (!out) return fail(SPDY_ERR_ARG, "null result pointer");
+    if (capacity < 1 || capacity > MAX_CAPACITY) return fail(SPDY_ERR_ARG, "diagnostics_create: capacity %d is not in 1 .. %d", capacity, MAX_CAPACITY);
+    if (first_step < 0) return fail(SPDY_ERR_ARG, "diagnostics_create: first_step %lld is negative", first_step);
+    NOT_CAPTURING(p, "spdy_diagnostics_create (allocation + upload)");
+    spdy_diagnostics *d = new spdy_diagnostics;
+    d->plan = p; d->capacity = capacity; d->start_step = first_step;
+    *out = d;
+    if (p->device < 0) return SPDY_OK;
+    auto cleanup = [&](int rc) { spdy_diagnostics_destroy(d); *out = nullptr; return rc; };
+    if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
+    const size_t nhist = (size_t)capacity * row_doubles(d);
+    const size_t bytes = (nhist + 4) * sizeof(double) + (size_t)p->tab.kx * sizeof(spdy::DiagLevel);
+    if (hipMalloc(reinterpret_cast<void **>(&d->d_history), bytes) != hipSuccess)
+        return cleanup(fail(SPDY_ERR_HIP, "diagnostics_create: hipMalloc of %zu bytes failed", bytes));
+    d->d_limits = d->d_history + nhist;
+    d->d_state = reinterpret_cast<spdy::DiagLevel *>(d->d_limits + 4);
+    int rc = upload_limits(d, nullptr);
+    if (!rc) rc = restart(d, first_step);
+    return rc ? cleanup(rc) : SPDY_OK;
+}
+
+int spdy_diagnostics_destroy(spdy_diagnostics *d)
+{
+    if (!d) return SPDY_OK;
+    if (d->d_history) {
+        (void)hipSetDevice(d->plan->device);
+        (void)hipStreamSynchronize(d->plan->stream);
+        (void)hipFree(d->d_history);
+    }
+    delete d;
+    return SPDY_OK;
+}
+
+int spdy_diagnostics_set_limits(spdy_diagnostics *d, const double *limits)
+{
+    NEED_DIAG(d);
+    spdy_plan *p = d->plan;
+    NOT_CAPTURING(p, "spdy_diagnostics_set_limits (upload)");
+    NEED_DEVICE(p);
+    return upload_limits(d, limits);
+}
+
+int spdy_diagnostics_reset(spdy_diagnostics *d, long long next_step)
+{
+    NEED_DIAG(d);
+    if (next_step < 0) return fail(SPDY_ERR_ARG, "diagnostics_reset: next_step %lld is negative", next_step);
+    spdy_plan *p = d->plan;
+    NOT_CAPTURING(p, "spdy_diagnostics_reset (upload)");
+    NEED_DEVICE(p);
+    return restart(d, next_step);
+}
+
+int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const double *div, const double *t)
+{
+    NEED_DIAG(d);
+    if (!vor || !div || !t) return fail(SPDY_ERR_ARG, "diagnostics_check_dev: null spectra");
+    spdy_plan *p = d->plan;
+    NEED_DEVICE(p);
+    spdy::DiagArgs a{};
+    a.vor = vor; a.div = div; a.t = t;
+    a.elm2 = p->dev.elm2; a.limits = d->d_limits; a.history = d->d_history; a.state = d->d_state;
+    a.nspec = p->tab.mx * p->tab.nx; a.mx = p->tab.mx; a.kx = p->tab.kx; a.capacity = d->capacity;
+    KERNEL(spdy::launch_diagnostics(a, p->stream));
+    return SPDY_OK;
+}
+
+int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask, double *bad_row)
+{
+    NEED_DIAG(d);
+    spdy_plan *p = d->plan;
+    NOT_CAPTURING(p, "spdy_diagnostics_status (download)");
+    NEED_DEVICE(p);
+    std::vector<spdy::DiagLevel> h;
+    RC(download_state(d, h));
+    const int kx = p->tab.kx;
+    long long first = -1;
+    for (const auto &l : h)
+        if (l.bad_step >= 0 && (first < 0 || l.bad_step < first)) first = l.bad_step;
+    int level = -1, mask = 0;
+    for (int k = 0; k < kx && first >= 0; ++k) {
+        if (h[k].bad_step == first) { mask |= h[k].bad_mask; if (level < 0) level = k; }
+        // every level stopped refreshing its saved row at the first offence of any level
+        if (h[k].row_step != first)
+            return fail(SPDY_ERR_STATE, "level %d saved the row of step %lld, the first offence is at step %lld", k, h[k].row_step, first);
+    }
+    if (next_step) *next_step = h[0].next_step;
+    if (bad_step) *bad_step = first;
+    if (bad_level) *bad_level = level;
+    if (bad_mask) *bad_mask = mask;
+    if (bad_row && first >= 0)
+        for (int k = 0; k < kx; ++k)
+            for (int i = 0; i < 3; ++i) bad_row[i * kx + k] = h[k].row[i];
+    return SPDY_OK;
+}
+
+int spdy_diagnostics_read(spdy_diagnostics *d, long long step, int count, double *rows)
+{
+    NEED_DIAG(d);
+    if (!rows) return fail(SPDY_ERR_ARG, "null result pointer");
+    if (count < 1) return fail(SPDY_ERR_ARG, "diagnostics_read: count %d", count);
+    spdy_plan *p = d->plan;
+    NOT_CAPTURING(p, "spdy_diagnostics_read (download)");
+    NEED_DEVICE(p);
+    std::vector<spdy::DiagLevel> h;
+    RC(download_state(d, h));
+    const long long next = h[0].next_step, oldest = std::max(d->start_step, next - d->capacity);
+    if (step < oldest || count > next - step)
+        return fail(SPDY_ERR_ARG, "diagnostics_read: steps %lld .. %lld asked, the ring holds %lld .. %lld", step, step + count - 1, oldest, next - 1);
+    const size_t nrow = row_doubles(d);
+    for (int i = 0; i < count; ++i)
+        HIP_TRY(hipMemcpyAsync(rows + (size_t)i * nrow, d->d_history + (size_t)((step + i) % d->capacity) * nrow, nrow * sizeof(double),
+                               hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
+int spdy_diagnostics_field(spdy_diagnostics *d, const char *name, void **d_ptr)
+{
+    NEED_DIAG(d);
+    if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
+    const int which = !std::strcmp(name, "history") ? 0 : !std::strcmp(name, "state") ? 1 : !std::strcmp(name, "limits") ? 2 : -1;
+    if (which < 0) return fail(SPDY_ERR_ARG, "unknown diagnostics field '%s'", name);
+    NEED_DEVICE(d->plan);
+    *d_ptr = which == 0 ? (void *)d->d_history : which == 1 ? (void *)d->d_state : (void *)d->d_limits;
+    return SPDY_OK;
+}
+
+// diagnostics.f90:72-74: ' step =', i6, ' reke =', (10f8.2) / 13x, ' deke =', (10f8.2) / 13x, ' temp =', (10f8.2); past ten values
+// format reversion goes back to the group (10f8.2): records of up to ten f8.2 fields and nothing else
+int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf, int cap)
+{
+    if (kx < 1) return fail(SPDY_ERR_ARG, "diagnostics_format: kx %d", kx);
+    if (!row) return fail(SPDY_ERR_ARG, "null row");
+    std::string s;
+    char f[32];
+    for (int i = 0; i < 3; ++i) {
+        if (i == 0) {
+            std::snprintf(f, sizeof(f), "%6lld", step);
+            s += " step =";
+            s += std::strlen(f) == 6 ? f : "******";
+        } else {
+            s += std::string(13, ' ');
+        }
+        s += i == 0 ? " reke =" : i == 1 ? " deke =" : " temp =";
+        for (int k = 0; k < kx; ++k) {
+            if (k && k % 10 == 0) s += '\n';
+            f8_2(row[i * kx + k], f);
+            s.append(f, 8);
+        }
+        s += '\n';
+    }
+    const int n = (int)s.size();
+    if (!buf) return n;
+    if (cap < n + 1) return fail(SPDY_ERR_ARG, "diagnostics_format: %d characters and the terminator, the buffer holds %d", n, cap);
+    std::memcpy(buf, s.c_str(), (size_t)n + 1);
+    return n;
+}
+
+}  // extern "C"

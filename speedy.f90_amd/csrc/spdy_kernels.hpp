@@ -433,4 +433,24 @@ struct SurfForcingCols {
 };
 hipError_t launch_surface_forcing(const SurfForcingCols &a, hipStream_t s);
 
+// check_diagnostics (csrc/spdy_diagnostics.hip; diagnostics.f90:16-75).  One DiagLevel per level in device memory, written by
+// that level's workgroup only: the number of the next step, the level's first offending step (-1: none) with its mask, and the
+// level's three numbers of step row_step -- the latest step, until some level has tripped: then that step's, for good.
+enum { DIAG_REKE = 1, DIAG_DEKE = 2, DIAG_TEMP_LOW = 4, DIAG_TEMP_HIGH = 8, DIAG_NONFINITE = 16 };   // SPDY_DIAG_* of include/spdy.h
+struct DiagLevel {
+    long long next_step, bad_step, row_step;
+    int bad_mask, pad;
+    double row[3];                                   // reke, deke, temp
+};
+// ONE launch, one workgroup per level: the level's sums over the (mx, nx) rectangle without m = 1, temp, the range test against
+// limits (reke, deke, temp low, temp high), row (next_step mod capacity) of history ([capacity][3][kx]) and the state's update.
+struct DiagArgs {
+    const double *vor, *div, *t;                     // (mx, nx, kx) complex
+    const double *elm2, *limits;                     // (mx, nx); 4
+    double *history;
+    DiagLevel *state;                                // [kx]
+    int nspec, mx, kx, capacity;                     // nspec = mx * nx
+};
+hipError_t launch_diagnostics(const DiagArgs &a, hipStream_t s);
+
 }  // namespace spdy

@@ -1,6 +1,7 @@
 // Internal: the plan object behind include/spdy.h and the helpers shared by the C-ABI translation units
 // (spdy_api.hip: plan, transforms, operators, graphs; spdy_api_step.hip: time-step tail, output; spdy_api_shard.hip:
-// collectives; spdy_api_physics.hip: column physics; spdy_api_surfmodel.hip, spdy_api_sppt.hip: the objects made on a plan).
+// collectives; spdy_api_physics.hip: column physics; spdy_api_surfmodel.hip, spdy_api_sppt.hip,
+// spdy_api_diagnostics.hip: the objects made on a plan).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,6 +82,16 @@ struct spdy_sppt {
     double *d_sigma = nullptr;            // (mx, nx)
     double *d_eta = nullptr, *d_spec = nullptr;   // (mx, nx, kx) complex
     double *d_pattern = nullptr;          // (ix, il, kx)
+};
+
+// The run's guard behind include/spdy.h's spdy_diagnostics (csrc/spdy_api_diagnostics.hip): one device allocation, history | limits | state.
+struct spdy_diagnostics {
+    spdy_plan *plan = nullptr;
+    int capacity = 0;
+    long long start_step = 0;             // the first step since create / reset: nothing before it is in the ring
+    double *d_history = nullptr;          // [capacity][3][kx]
+    double *d_limits = nullptr;           // reke, deke, temp low, temp high
+    spdy::DiagLevel *d_state = nullptr;   // [kx]
 };
 
 namespace spdy_detail {

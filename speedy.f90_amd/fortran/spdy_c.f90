@@ -918,6 +918,66 @@ module spdy_c
             type(spdy_column_physics_out), intent(in) :: out
             integer(c_int) :: rc
         end function
+        ! diagnostics (include/spdy.h): check_diagnostics on the device, the history ring and the sticky stop flag
+        function spdy_diagnostics_create(plan, capacity, first_step, d) bind(C, name="spdy_diagnostics_create") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: plan
+            integer(c_int), value :: capacity
+            integer(c_long_long), value :: first_step
+            type(c_ptr), intent(out) :: d
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_destroy(d) bind(C, name="spdy_diagnostics_destroy") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: d
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_set_limits(d, limits) bind(C, name="spdy_diagnostics_set_limits") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: d, limits
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_reset(d, next_step) bind(C, name="spdy_diagnostics_reset") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: d
+            integer(c_long_long), value :: next_step
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_check_dev(d, vor, div, t) bind(C, name="spdy_diagnostics_check_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: d, vor, div, t
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_status(d, next_step, bad_step, bad_level, bad_mask, bad_row) &
+                & bind(C, name="spdy_diagnostics_status") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: d, bad_row
+            integer(c_long_long), intent(out) :: next_step, bad_step
+            integer(c_int), intent(out) :: bad_level, bad_mask
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_read(d, step, count, rows) bind(C, name="spdy_diagnostics_read") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: d, rows
+            integer(c_long_long), value :: step
+            integer(c_int), value :: count
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_field(d, name, d_ptr) bind(C, name="spdy_diagnostics_field") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: d
+            character(kind=c_char), intent(in) :: name(*)
+            type(c_ptr), intent(out) :: d_ptr
+            integer(c_int) :: rc
+        end function
+        function spdy_diagnostics_format(kx, step, row, buf, cap) bind(C, name="spdy_diagnostics_format") result(rc)
+            import :: c_int, c_ptr, c_long_long, c_char
+            integer(c_int), value :: kx, cap
+            integer(c_long_long), value :: step
+            type(c_ptr), value :: row
+            character(kind=c_char), intent(inout) :: buf(*)
+            integer(c_int) :: rc
+        end function
         function spdy_output_workspace(plan) bind(C, name="spdy_output_workspace") result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: plan

@@ -21,6 +21,8 @@ from .columns import (MOIST_2D, MOIST_3D, PBL_2D, PBL_3D, RAD_2D, RAD_3D, RAD_SW
                       SURFACE_DEFAULT, SURFACE_FIELDS, SURFACE_ICE_COUPLING, SURFACE_LAND_COUPLING, SURFACE_SST_ANOMALY,
                       SPPT_FIELDS, SPPT_TABLES, SURFACE_TABLES, ColumnPhysics, ColumnPhysicsOut, DeviceField, MoistOut, PblOut, RadOut,
                       RadSurface, SfcBoundary, SfcOut, Sppt, SurfaceClim, SurfaceModel, _p)
+from .columns import (DIAG_DEKE, DIAG_FIELDS, DIAG_NONFINITE, DIAG_REFERENCE, DIAG_REKE, DIAG_TEMP_HIGH, DIAG_TEMP_LOW,  # noqa: F401
+                      Diagnostics, DiagnosticsStop, format_diagnostics)
 
 RESOLUTIONS = {"t30": (30, 96, 24), "t63": (63, 192, 48)}   # trunc, ix, iy
 
