@@ -285,6 +285,46 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *plan, const double *d_ug, con
                                         double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,
                                         int j1, double dt, double eps, double wil, double *phi);
 
+/* ---- ensemble time step: nmem model states through ONE step's launches ---------------------------------
+ * A T30 L8 step is four or five launches, each bound by its fixed costs, not by bytes: an ensemble amortises them.  An ensemble
+ * array is the single-state array with every level dimension kx widened to nmem*kx, member-major inside it:
+ *     vor, div, t, tr  (mx,nx,kx,nmem,2)   ps (mx,nx,nmem,2)     time level lv of all members = one stack of nmem*kx fields
+ *     phis, d_tcorh, d_qcorh (mx,nx)       shared by all members
+ *     phi              (mx,nx,kx,nmem)
+ *     ug, vg, tg, vorg, divg, trg (ix,il,kx,nmem)                px, py (ix,il,nmem)
+ *     u_out, v_out, pvor, pdiv  [3][nmem][kx]                    group-major: the group stride is nmem*kx fields
+ *     plain_out, pspec          [3][nmem][kx] + [nmem]           the level-free fields of the members behind the three groups
+ * so the transforms are the existing calls with larger counts (inverse: nmem*kx pairs, plain segments of nmem*kx, nmem gradient
+ * fields; direct: 3*nmem*kx pairs, 3*nmem*kx + nmem plain fields), and utend, vtend, ttend, qtend of all members -- the first
+ * nmem*kx fields of u_out, v_out and the second and third group of plain_out -- are nmem states back to back as the column physics
+ * takes them.  Member e of the column kernels works on level slot e*kx + k, its level-free slot is 3*nmem*kx + e.  The kernels are
+ * those of the single-state calls with the member in blockIdx.y: same expressions, same order, and with nmem = 1 the same
+ * addresses, so a member's results do not depend on the ensemble it travels in wherever the transforms' do not (T30: bit for
+ * bit; T63: the pairs' spectra to rounding where the launch form differs, see spdy_direct_batch_spectral_step_dev).
+ *   spdy_ens_grid_tendencies_dev / _spectral_step_dev / _geopotential_dev   the single-state calls for nmem members, one launch
+ *   spdy_ens_direct_batch_spectral_step_dev   ONE direct batch of all members, then the spectral step; the routes of the
+ *       single-state call (T63: the raw pairs' spectra in the plan's temporaries) where the batch fits them, silently the plain
+ *       direct batch followed by the spectral step otherwise
+ *   spdy_ens_physics_dev   spdy_physics_dev for nmem members: ONE inverse launch of time level 1 of all members (vor .. phi
+ *       (mx,nx,kx,nmem), ps (mx,nx,nmem)), then the column physics with nb = nmem; the fields of bnd, albsfc, rad_state and the
+ *       optional outputs are per member, back to back, as spdy_column_physics_dev takes them.  spdy_ens_physics_workspace(nmem)
+ *       allocates its workspace (not possible during a capture; a larger nmem later allocates anew).
+ * Checks, in this order: a NULL plan, nmem < 1, kx > 16 with nmem > 1 (physics: kx outside [5, 16]) and
+ * max_batch < nmem*(3*kx+1) SPDY_ERR_ARG; what the single-state call needs first (spdy_implicit_init, sigma levels; physics: sigma
+ * levels, date, orography) SPDY_ERR_STATE; a NULL required pointer, then j1 outside {1, 2} SPDY_ERR_ARG; a host-only plan
+ * SPDY_ERR_NO_DEVICE last.  Every call can be captured.  Not covered: SPPT (a pattern object holds one pattern), the sharded step. */
+int spdy_ens_grid_tendencies_dev(spdy_plan *plan, int nmem, const double *ug, const double *vg, const double *tg, const double *vorg,
+                                 const double *divg, const double *trg, const double *px, const double *py, double *u_out,
+                                 double *v_out, double *plain_out);
+int spdy_ens_spectral_step_dev(spdy_plan *plan, int nmem, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
+                               double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,
+                               int j1, double dt, double eps, double wil, double *phi);
+int spdy_ens_direct_batch_spectral_step_dev(spdy_plan *plan, int nmem, const double *d_ug, const double *d_vg, const double *d_grid,
+                                            int kcos, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
+                                            double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh,
+                                            double sdrag, int j1, double dt, double eps, double wil, double *phi);
+int spdy_ens_geopotential_dev(spdy_plan *plan, int nmem, const double *t, const double *phis, double *phi);
+
 /* ---- multi-GPU: level-sharded time steps (one process per GPU with RCCL over xGMI, or ranks inside one process) -------
  * The transform batch shards over (field x level) with no communication.  What couples levels in a step is exchanged:
  * implicit_terms' operands (implicit.f90:174-216) with spdy_implicit_terms_sharded_dev, or -- the complete adiabatic step --
@@ -598,6 +638,12 @@ int spdy_physics_workspace(spdy_plan *plan);
 int spdy_physics_dev(spdy_plan *plan, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
                      const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
                      double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out);
+/* the same for nmem members of an ensemble ("ensemble time step" above: layout, checks) */
+int spdy_ens_physics_workspace(spdy_plan *plan, int nmem);
+int spdy_ens_physics_dev(spdy_plan *plan, int nmem, int compute_sw, const double *vor, const double *div, const double *t,
+                         const double *q, const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc,
+                         double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                         const spdy_column_physics_out *out);
 
 /* ---- SPPT: stochastically perturbed parametrisation tendencies (sppt.f90, physics.f90:85-88 and :207-222) -----------------------
  * The reference's model-error scheme: a random pattern, AR(1) in time per spectral coefficient, multiplies the physics' part of

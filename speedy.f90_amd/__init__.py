@@ -7,6 +7,7 @@ Only what the hot path needs lives here:
                  smoke() and bench.py
     columns.py   the column physics and the surface models of the same plan: one field table,
                  the ctypes structures and output buffers derived from it
+    ensemble.py  E model states through one time step's launches: the layout, the views, the step
 
 The directory name contains a dot, so import it through the repo-root shim
 ``import speedy_f90_amd`` (speedy_f90_amd.py).
@@ -14,4 +15,5 @@ The directory name contains a dot, so import it through the repo-root shim
 from ._lib import LIB_PATH, SpdyError, build, load  # noqa: F401
 from .spectral import (RESOLUTIONS, DeviceField, Diagnostics, DiagnosticsStop, Graph, Spectral, Sppt, SurfaceModel,  # noqa: F401
                        check)
+from .ensemble import Ensemble  # noqa: F401
 from . import sharding  # noqa: F401

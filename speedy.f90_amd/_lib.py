@@ -104,6 +104,13 @@ SIGNATURES = {
     "spdy_grid_tendencies_dev": [c_void_p] * 12,
     "spdy_tendency_combine_dev": [c_void_p, c_void_p, c_void_p],
     "spdy_spectral_step_dev": [c_void_p] * 12 + [c_double, c_int, c_double, c_double, c_double, c_void_p],
+    "spdy_ens_grid_tendencies_dev": [c_void_p, c_int] + [c_void_p] * 11,
+    "spdy_ens_spectral_step_dev": [c_void_p, c_int] + [c_void_p] * 11 + [c_double, c_int, c_double, c_double, c_double, c_void_p],
+    "spdy_ens_direct_batch_spectral_step_dev": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 11
+                                               + [c_double, c_int, c_double, c_double, c_double, c_void_p],
+    "spdy_ens_geopotential_dev": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "spdy_ens_physics_workspace": [c_void_p, c_int],
+    "spdy_ens_physics_dev": [c_void_p, c_int, c_int] + [c_void_p] * 14,
     "spdy_output_workspace": [c_void_p],
     "spdy_output_batch_dev": [c_void_p] * 13,
     "spdy_moist_columns_dev": [c_void_p, c_int] + [c_void_p] * 7,

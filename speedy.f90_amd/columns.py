@@ -544,6 +544,20 @@ class ColumnPhysics:
                                         ctypes.byref(b), self._dp(albsfc), self._dp(state),
                                         *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
 
+    def ens_physics_workspace(self, nmem):
+        check(self.lib.spdy_ens_physics_workspace(self.h, int(nmem)))
+
+    def ens_physics_dev(self, nmem, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, state, utend, vtend, ttend, qtend, out=None):
+        """physics_dev for nmem members (ensemble.py's layout): time level 1 of all members, vor, div, t, q, phi [nmem,kx,nx,mx], ps
+        [nmem,nx,mx]; ONE inverse launch, then the column physics with nb = nmem.  utend .. qtend [nmem,kx,il,ix] in place; the fields
+        of bnd, albsfc, state and out are per member, back to back, as column_physics_dev takes them for nb states."""
+        self._sync_stream()
+        o = self._column_physics_out(out)
+        b = self._boundary(bnd)
+        check(self.lib.spdy_ens_physics_dev(self.h, int(nmem), 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
+                                            ctypes.byref(b), self._dp(albsfc), self._dp(state),
+                                            *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+
     # ------------------------------------------------------------------ SPPT (physics.f90:85-88, :207-222)
     def column_physics_sppt_workspace(self):
         check(self.lib.spdy_column_physics_sppt_workspace(self.h))

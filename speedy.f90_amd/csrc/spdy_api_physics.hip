@@ -462,6 +462,55 @@ int spdy_physics_dev(spdy_plan *p, int compute_sw, const double *vor, const doub
                         rad_state, utend, vtend, ttend, qtend, out, g + 5 * L + grid_elems(p), grid_elems(p));
 }
 
+/* ---------------------------------------------------------------- the physics of nmem members from their spectra (include/spdy.h, ensemble) */
+// the member count against the plan: the first checks of both calls
+static int ens_physics_members(const spdy_plan *p, int nmem)
+{
+    NEED_PLAN(p);
+    if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_physics: nmem=%d < 1", nmem);
+    RC(check_kx(p, "ens_physics"));
+    if ((long)p->max_batch < (long)nmem * (3 * p->tab.kx + 1))
+        return fail(SPDY_ERR_ARG, "ens_physics: max_batch=%d must be >= nmem*(3*kx+1)=%ld", p->max_batch, (long)nmem * (3 * p->tab.kx + 1));
+    return SPDY_OK;
+}
+
+int spdy_ens_physics_workspace(spdy_plan *p, int nmem)
+{
+    RC(ens_physics_members(p, nmem));
+    NEED_DEVICE(p);
+    if (p->ens_physics_grid && p->ens_physics_nmem >= nmem) return SPDY_OK;
+    NOT_CAPTURING(p, "allocating the ensemble physics workspace (call spdy_ens_physics_workspace before the capture)");
+    RC(ensure_four(p));   // (the operator route of the T63 inverse launch, as spdy_physics_workspace)
+    // a smaller earlier workspace stays with the plan until it is destroyed: a captured graph may still point into it
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * nmem * sizeof(double), &ptr));
+    p->ens_physics_grid = static_cast<double *>(ptr);
+    p->ens_physics_nmem = nmem;
+    return SPDY_OK;
+}
+
+int spdy_ens_physics_dev(spdy_plan *p, int nmem, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
+                         const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
+                         double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out)
+{
+    const bool ok = vor && div && t && q && phi && ps && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
+                    vtend && ttend && qtend;
+    RC(ens_physics_members(p, nmem));
+    RC(column_args(p, "ens_physics", nmem, true, ok, true));
+    NEED_DEVICE(p);
+    RC(spdy_ens_physics_workspace(p, nmem));
+    // physics.f90:94-104 for all members in ONE inverse launch: nmem kx (vor, div) pairs through uvspec with kcos 2; t, q, phi
+    // (nmem kx each) and ps (nmem) with kcos 1.  The grids are nmem states back to back at state stride kx: the chain's nb = nmem.
+    const int kx = p->tab.kx, nk = nmem * kx;
+    const size_t g1 = grid_elems(p) * nmem, L = (size_t)kx * g1;
+    double *g = p->ens_physics_grid;
+    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{nk, t}, {nk, q}, {nk, phi}, {nmem, ps}};
+    double *ug = g, *vg = g + L, *tg = g + 2 * L, *qg = g + 3 * L, *phig = g + 4 * L, *pslg = g + 5 * L;
+    RC(spdy_inverse_batch_segs_dev(p, nk, vor, div, ug, vg, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, tg, 0, nullptr, nullptr, nullptr, 2));
+    return column_chain(p, p->physics_fused != 0, nmem, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend,
+                        ttend, qtend, out, g + 5 * L + g1, g1);
+}
+
 int spdy_physics_sppt_workspace(spdy_plan *p)
 {
     RC(spdy_physics_workspace(p));

@@ -759,7 +759,7 @@ int spdy_sharded_step_grid_dev(spdy_comm *c, double *vor, double *div, double *t
         const int me = c->rank;
         RC(transpose_blocks(c, true, 6, 0, s.gs, rg.g0.data(), rg.gl.data(), own, c->Gb, rg.gl[me]));
         spdy::GridTend gt{c->Gb, c->Gb, c->Gb, c->Gb, c->Gb, c->Gb, c->px, c->py, c->U, c->V, c->PL, spdy::LevelShard{c->nranks, c->rank},
-                          (int)rg.gl[me], (int)rg.g0[me], c->Ob};
+                          (int)rg.gl[me], (int)rg.g0[me], c->Ob, 1};
         if (rg.gl[me]) KERNEL(spdy::launch_grid_tendencies(p->dev, gt, p->stream));
         RC(transpose_blocks(c, false, 9, 1, s.gs, rg.g0.data(), rg.gl.data(), c->U, c->Ob, rg.gl[me]));
         return SPDY_OK;
@@ -772,7 +772,7 @@ int spdy_sharded_step_grid_dev(spdy_comm *c, double *vor, double *div, double *t
     }
     double *arr[1] = {c->G};
     RC(allgather_blocks(c, 1, arr, off.data(), cnt.data()));
-    spdy::GridTend g{c->G, c->G, c->G, c->G, c->G, c->G, c->px, c->py, c->U, c->V, c->PL, spdy::LevelShard{c->nranks, c->rank}};
+    spdy::GridTend g{c->G, c->G, c->G, c->G, c->G, c->G, c->px, c->py, c->U, c->V, c->PL, spdy::LevelShard{c->nranks, c->rank}, 0, 0, nullptr, 1};
     KERNEL(spdy::launch_grid_tendencies(p->dev, g, p->stream));
     return SPDY_OK;
 }
@@ -804,7 +804,7 @@ int spdy_sharded_step_spectral_dev(spdy_comm *c, double *vor, double *div, doubl
         if (!tend_out) tend_out = c->tend;
         spdy::SpecStep a{c->Tb, c->Tb, c->Tb, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
                          p->tab.ix == 4 * p->tab.iy, nullptr, nullptr, spdy::LevelShard{c->nranks, c->rank}, tend_out,
-                         (int)(rg.s0[me] / 2), (int)(rg.sl[me] / 2)};
+                         (int)(rg.s0[me] / 2), (int)(rg.sl[me] / 2), 1};
         if (rg.sl[me]) KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
         if (c->nranks > 1 || c->force) (p->capturing ? c->ranges_captured : c->ranges_eager) = true;
         return SPDY_OK;
@@ -819,7 +819,7 @@ int spdy_sharded_step_spectral_dev(spdy_comm *c, double *vor, double *div, doubl
     RC(allgather_blocks(c, 1, arr, off.data(), cnt.data()));
     if (!tend_out) tend_out = c->tend;
     spdy::SpecStep a{c->T, c->T, c->T, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
-                     p->tab.ix == 4 * p->tab.iy, raw ? c->T : nullptr, raw ? c->T : nullptr, spdy::LevelShard{c->nranks, c->rank}, tend_out};
+                     p->tab.ix == 4 * p->tab.iy, raw ? c->T : nullptr, raw ? c->T : nullptr, spdy::LevelShard{c->nranks, c->rank}, tend_out, 0, 0, 1};
     KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
     return SPDY_OK;
 }

@@ -12,6 +12,55 @@
 using spdy::HostTables;
 using namespace spdy_detail;
 
+namespace {
+// The checks of the ensemble calls that need no device (a host-only plan answers them), in the order include/spdy.h gives.
+int ens_args(const spdy_plan *p, int nmem, const char *what, bool need_implicit, bool need_sigma, bool ok_ptrs, int j1 = 1)
+{
+    NEED_PLAN(p);
+    const int kx = p->tab.kx;
+    if (nmem < 1) return fail(SPDY_ERR_ARG, "%s: nmem=%d < 1", what, nmem);
+    if (nmem > 1 && kx > 16) return fail(SPDY_ERR_ARG, "%s: more than one member needs kx <= 16 (kx=%d)", what, kx);
+    if ((long)p->max_batch < (long)nmem * (3 * kx + 1))
+        return fail(SPDY_ERR_ARG, "%s: max_batch=%d must be >= nmem*(3*kx+1)=%ld", what, p->max_batch, (long)nmem * (3 * kx + 1));
+    if (need_implicit && !p->tab.implicit_ready) return fail(SPDY_ERR_STATE, "%s needs spdy_implicit_init first", what);
+    if (need_sigma && !p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "%s needs sigma levels", what);
+    if (!ok_ptrs) return fail(SPDY_ERR_ARG, "null device pointer");
+    if (j1 != 1 && j1 != 2) return fail(SPDY_ERR_ARG, "j1 must be 1 or 2");
+    return SPDY_OK;
+}
+
+// the one-launch spectral step of nmem members (kx <= 16), arguments checked; raw_u / raw_v: SpecStep
+int spectral_step_launch(spdy_plan *p, int nmem, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
+                         double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1,
+                         double dt, double eps, double wil, double *phi, const double *raw_u, const double *raw_v)
+{
+    const spdy::SpecStep a{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
+                           p->tab.ix == 4 * p->tab.iy, raw_u, raw_v, spdy::LevelShard{}, nullptr, 0, 0, nmem};
+    KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
+    return SPDY_OK;
+}
+
+// the direct batch of nmem members (3 nmem kx pairs, 3 nmem kx + nmem plain fields) and their spectral step, arguments checked
+int direct_batch_spectral_step(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *grid, int kcos, double *pvor,
+                               double *pdiv, double *pspec, double *vor, double *div, double *t, double *tr, double *ps,
+                               const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1, double dt,
+                               double eps, double wil, double *phi)
+{
+    const int P = 3 * nmem * p->tab.kx;
+    if (use_raw63(p, P)) {
+        // T63: the transform kernel leaves the pairs' spectra un-vds'ed in the plan's temporaries; the spectral step applies
+        // vds where it reads them -- direct batch + everything after it = 2 launches instead of 3
+        RC(direct_batch_raw63(p, P, ug, vg, kcos, P + nmem, grid, pspec));
+        return spectral_step_launch(p, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil,
+                                    phi, p->tmp_c, p->tmp_d);
+    }
+    // every other plan and batch: the plain direct batch, whatever form its size takes, then the spectral step
+    RC(spdy_direct_batch_dev(p, P, ug, vg, pvor, pdiv, kcos, P + nmem, grid, pspec));
+    return spectral_step_launch(p, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi,
+                                nullptr, nullptr);
+}
+}  // namespace
+
 extern "C" {
 
 /* ---------------------------------------------------------------- sigma levels */
@@ -149,7 +198,15 @@ int spdy_geopotential_dev(spdy_plan *p, const double *t, const double *phis, dou
     NEED_DEVICE(p);
     if (!p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "geopotential needs sigma levels (kx in {5,7,8} or spdy_plan_set_sigma)");
     if (!t || !phis || !phi) return fail(SPDY_ERR_ARG, "null device pointer");
-    KERNEL(spdy::launch_geopotential(p->dev, t, phis, phi, p->stream));
+    KERNEL(spdy::launch_geopotential(p->dev, 1, t, phis, phi, p->stream));
+    return SPDY_OK;
+}
+
+int spdy_ens_geopotential_dev(spdy_plan *p, int nmem, const double *t, const double *phis, double *phi)
+{
+    RC(ens_args(p, nmem, "ens_geopotential", false, true, t && phis && phi));
+    NEED_DEVICE(p);
+    KERNEL(spdy::launch_geopotential(p->dev, nmem, t, phis, phi, p->stream));
     return SPDY_OK;
 }
 
@@ -233,7 +290,18 @@ int spdy_grid_tendencies_dev(spdy_plan *p, const double *ug, const double *vg, c
     NEED_DEVICE(p);
     if (!p->tab.implicit_ready) return fail(SPDY_ERR_STATE, "grid_tendencies needs the reference temperature profile: call spdy_implicit_init first");
     if (!ug || !vg || !tg || !vorg || !divg || !trg || !px || !py || !u_out || !v_out || !plain_out) return fail(SPDY_ERR_ARG, "null device pointer");
-    const spdy::GridTend g{ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out};
+    const spdy::GridTend g{ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out, spdy::LevelShard{}, 0, 0, nullptr, 1};
+    KERNEL(spdy::launch_grid_tendencies(p->dev, g, p->stream));
+    return SPDY_OK;
+}
+
+int spdy_ens_grid_tendencies_dev(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *tg, const double *vorg,
+                                 const double *divg, const double *trg, const double *px, const double *py, double *u_out,
+                                 double *v_out, double *plain_out)
+{
+    RC(ens_args(p, nmem, "ens_grid_tendencies", true, false, ug && vg && tg && vorg && divg && trg && px && py && u_out && v_out && plain_out));
+    NEED_DEVICE(p);
+    const spdy::GridTend g{ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out, spdy::LevelShard{}, 0, 0, nullptr, nmem};
     KERNEL(spdy::launch_grid_tendencies(p->dev, g, p->stream));
     return SPDY_OK;
 }
@@ -267,10 +335,21 @@ int spdy_spectral_step_dev(spdy_plan *p, double *pvor, double *pdiv, double *psp
         const spdy_step_op ops[5] = {{1, ps, psdt}, {kx, vor, pvor}, {kx, div, divdt}, {kx, t, tdt}, {kx, tr, trdt}};
         return spdy_step_fields_dev(p, 5, ops, j1, dt, eps, wil);
     }
-    const spdy::SpecStep a{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
-                           p->tab.ix == 4 * p->tab.iy, nullptr, nullptr};
-    KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
-    return SPDY_OK;
+    return spectral_step_launch(p, 1, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi, nullptr,
+                                nullptr);
+}
+
+int spdy_ens_spectral_step_dev(spdy_plan *p, int nmem, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
+                               double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,
+                               int j1, double dt, double eps, double wil, double *phi)
+{
+    RC(ens_args(p, nmem, "ens_spectral_step", true, true,
+                pvor && pdiv && pspec && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi, j1));
+    NEED_DEVICE(p);
+    if (p->tab.kx > 16)   // (one member: the separate kernels)
+        return spdy_spectral_step_dev(p, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi);
+    return spectral_step_launch(p, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi,
+                                nullptr, nullptr);
 }
 
 int spdy_direct_batch_spectral_step_dev(spdy_plan *p, const double *ug, const double *vg, const double *grid, int kcos, double *pvor,
@@ -281,17 +360,26 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *p, const double *ug, const do
     NEED_DEVICE(p);
     const int kx = p->tab.kx, P = 3 * kx;
     if (!ug || !vg || !grid || !pvor || !pdiv || !pspec) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (use_raw63(p, P) && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi && (j1 == 1 || j1 == 2)) {
-        // T63: the transform kernel leaves the pairs' spectra un-vds'ed in the plan's temporaries; the spectral step applies
-        // vds where it reads them -- direct batch + everything after it = 2 launches instead of 3
-        RC(direct_batch_raw63(p, P, ug, vg, kcos, P + 1, grid, pspec));
-        const spdy::SpecStep a{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
-                               p->tab.ix == 4 * p->tab.iy, p->tmp_c, p->tmp_d};
-        KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
-        return SPDY_OK;
-    }
+    if (use_raw63(p, P) && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi && (j1 == 1 || j1 == 2))
+        return direct_batch_spectral_step(p, 1, ug, vg, grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag,
+                                          j1, dt, eps, wil, phi);
     RC(spdy_direct_batch_dev(p, P, ug, vg, pvor, pdiv, kcos, P + 1, grid, pspec));
     return spdy_spectral_step_dev(p, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi);
+}
+
+int spdy_ens_direct_batch_spectral_step_dev(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *grid, int kcos,
+                                            double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t, double *tr,
+                                            double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,
+                                            int j1, double dt, double eps, double wil, double *phi)
+{
+    RC(ens_args(p, nmem, "ens_direct_batch_spectral_step", true, true,
+                ug && vg && grid && pvor && pdiv && pspec && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi, j1));
+    NEED_DEVICE(p);
+    if (p->tab.kx > 16)   // (one member: the separate kernels behind the direct batch)
+        return spdy_direct_batch_spectral_step_dev(p, ug, vg, grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh,
+                                                   sdrag, j1, dt, eps, wil, phi);
+    return direct_batch_spectral_step(p, nmem, ug, vg, grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag,
+                                      j1, dt, eps, wil, phi);
 }
 
 /* ---------------------------------------------------------------- output path */

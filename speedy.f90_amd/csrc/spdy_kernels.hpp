@@ -201,8 +201,8 @@ struct HdiffStep {
     double sdrag;
 };
 hipError_t launch_hdiff_step(const DevPlan &p, const HdiffStep &h, hipStream_t s);
-// get_geopotential (geopotential.f90:33-57)
-hipError_t launch_geopotential(const DevPlan &p, const double *t, const double *phis, double *phi, hipStream_t s);
+// get_geopotential (geopotential.f90:33-57) of nmem members: t, phi [nmem][kx], phis shared
+hipError_t launch_geopotential(const DevPlan &p, int nmem, const double *t, const double *phis, double *phi, hipStream_t s);
 // get_spectral_tendencies (tendencies.f90:242-293); phi is written as the reference's module variable is
 hipError_t launch_spectral_tendencies(const DevPlan &p, const double *div, const double *t, const double *ps, const double *phis,
                                       double *divdt, double *tdt, double *psdt, double *phi, hipStream_t s);
@@ -230,6 +230,10 @@ struct GridTend {
     // plain [3 nl_q] | the level-free field, restricted to these points (u, v, plain are ignored).
     int npts, pt0;
     double *tr_out;
+    // Ensemble form (nmem >= 1 members, blockIdx.y; not with sh): every level dimension above is nmem*kx, member-major -- the
+    // inputs (nmem, kx) grids each, px, py (nmem), the outputs group-major [3][nmem][kx] (+ the nmem level-free fields behind
+    // plain's groups).  Member e works on level slot e*kx + k with group stride nmem*kx; nmem = 1 is the layout above.
+    int nmem;
 };
 hipError_t launch_grid_tendencies(const DevPlan &p, const GridTend &g, hipStream_t s);
 // Whether a fused launch with this many grid-side bytes streams them (non-temporal loads / stores; >= 16 MB): the size from which
@@ -261,6 +265,10 @@ struct SpecStep {
     // coefficient index); the prognostics, phi and tend_out are the whole arrays as ever and are read / written at these
     // coefficients only.  No raw pairs (vds needs the neighbouring rows): raw_u must be null.
     int e0, ne;
+    // Ensemble form (nmem >= 1 members, blockIdx.y; not with sh): prognostics [2][nmem][kx] / ps [2][nmem], phi [nmem][kx],
+    // pvor / pdiv / pspec / raw_u / raw_v group-major [3][nmem][kx] (+ the nmem level-free fields behind pspec's groups); phis,
+    // tcorh, qcorh are shared.  nmem = 1 is the layout above.
+    int nmem;
 };
 hipError_t launch_spectral_step(const DevPlan &p, const SpecStep &a, hipStream_t s);
 // output path (input_output.f90:184-206)

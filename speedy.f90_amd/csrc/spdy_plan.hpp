@@ -51,6 +51,8 @@ struct spdy_plan {
     double *physics_ws = nullptr;     // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
     double *physics_grid = nullptr;   // physics from spectra: (5kx+1) grids u | v | t | q | phi | ln ps, then one state's chain workspace
                                       // of (3kx+12) grids (spdy_physics_workspace)
+    double *ens_physics_grid = nullptr;   // ensemble physics from spectra: ens_physics_nmem x (5kx+1) grids u | v | t | q | phi (nmem, kx each) |
+    int ens_physics_nmem = 0;             // ln ps (nmem), then the chain workspace of (3kx+12) fields of nmem grids (spdy_ens_physics_workspace)
     double *sppt_ws = nullptr;        // SPPT on gridded states: the dynamics tendencies, (2kx+2) grids per state, max_batch states
                                       // (spdy_column_physics_sppt_workspace)
     double *sppt_grid = nullptr;      // SPPT from spectra: one state's (2kx+2) grids (spdy_physics_sppt_workspace)

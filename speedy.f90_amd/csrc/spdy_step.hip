@@ -217,13 +217,15 @@ __global__ void geopotential_kernel(DevPlan p, const double *__restrict__ t, con
 {
     const int sz = p.mx * p.nx, e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= sz) return;
-    geopotential_column(p, e, sz, e % p.mx == 0, t, ld(phis, e), phi);
+    const long mo = (long)blockIdx.y * p.kx * sz * 2;                      // the member's [kx] stack (doubles); phis is shared
+    geopotential_column(p, e, sz, e % p.mx == 0, t + mo, ld(phis, e), phi + mo);
 }
 
-hipError_t launch_geopotential(const DevPlan &p, const double *t, const double *phis, double *phi, hipStream_t s)
+hipError_t launch_geopotential(const DevPlan &p, int nmem, const double *t, const double *phis, double *phi, hipStream_t s)
 {
     const int sz = p.mx * p.nx;
-    hipLaunchKernelGGL(geopotential_kernel, dim3((sz + 63) / 64), dim3(64), 0, s, p, t, phis, phi);
+    if (nmem < 1 || nmem > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(geopotential_kernel, dim3((sz + 63) / 64, nmem), dim3(64), 0, s, p, t, phis, phi);
     return hipGetLastError();
 }
 
@@ -350,6 +352,9 @@ __global__ void grid_tendencies_serial_kernel(DevPlan p, GridTend g)
 // instruction stream while the block waits, like the recurrences of the spectral step).
 // SH: level-sharded form (LevelShard, spdy_kernels.hpp): the six inputs come from ONE level-block stack that holds all levels,
 // the outputs are this rank's own levels only, laid out as ITS direct-batch operands.  Same expressions, same order.
+// Ensemble form (GridTend::nmem, never SH): blockIdx.y is the member e; it reads level slot e*kx + k of the (nmem, kx) inputs and
+// writes slot e*kx + k of the group-major outputs, whose group stride is nmem*kx; its level-free field is slot 3*nmem*kx + e.
+// Only these base offsets differ from the single state's (nmem = 1: the same addresses); they are uniform over the block.
 // Owner of level k among R ranks with blocks [kx r / R, kx (r + 1) / R): r = (R (k + 1) - 1) / kx.
 struct LevelBlock { int r, lo, nl; };
 __device__ __forceinline__ LevelBlock level_block(int k, int kx, int R)
@@ -375,10 +380,13 @@ __global__ __launch_bounds__(GT_BX * KM) void grid_tendencies_kernel(DevPlan p, 
 #define LV(a_, k_) (a_)[(long)(k_) * gsz + i]
 #define S(b_, k_) (b_)[(k_) * BX + tx]
     // where this thread's level of input field f lives, and where (whether) its outputs go
-    int og = kx, ok = k, o_ps = 3 * kx;                                    // output group stride, level slot, slot of the level-free field
+    // the member's stacks: a uniform offset on the base pointers, the level slot k inside them is the single state's
+    const int nmem = SH ? 1 : g.nmem, mem = SH ? 0 : blockIdx.y;
+    const long mo = (long)mem * kx * gsz;
+    int og = nmem * kx, ok = k, o_ps = 3 * nmem * kx + mem;                // output group stride, level slot, slot of the level-free field
     bool own = true;
     double ug_c, vg_c, tg_c, tr_c, dv, vor_in;
-    double *out_u = g.u, *out_v = g.v, *out_pl = g.plain;
+    double *out_u = g.u + mo, *out_v = g.v + mo, *out_pl = g.plain + mo;
     if (SH) {
         const LevelBlock b = level_block(k, kx, g.sh.nranks);
         const long s0 = (long)6 * b.lo + (k - b.lo);                       // slab of (field 0, level k) in the F = 6 block stack
@@ -391,10 +399,11 @@ __global__ __launch_bounds__(GT_BX * KM) void grid_tendencies_kernel(DevPlan p, 
             og = b.nl; ok = k - b.lo; own = true;
         }
     } else {
-        ug_c = LV(g.ug, k); vg_c = LV(g.vg, k); tg_c = LV(g.tg, k); tr_c = LV(g.trg, k); dv = LV(g.divg, k); vor_in = LV(g.vorg, k);
+        ug_c = LV(g.ug + mo, k); vg_c = LV(g.vg + mo, k); tg_c = LV(g.tg + mo, k); tr_c = LV(g.trg + mo, k); dv = LV(g.divg + mo, k);
+        vor_in = LV(g.vorg + mo, k);
     }
     const double vor = vor_in + p.coriol[j];                                               // (:103-107 coriolis)
-    const double px = g.px[ig], py = g.py[ig], rgas = p.rgas, akap = p.akap;
+    const double px = (g.px + (long)mem * gsz)[ig], py = (g.py + (long)mem * gsz)[ig], rgas = p.rgas, akap = p.akap;   // (one grid per member)
     const double dhr = p.dhsr[k], trefk = p.tref[k];
     const double tgg = tg_c - trefk;                                                       // (:149)
     if (tx == 0) stab[k] = p.dhs[k];
@@ -476,6 +485,8 @@ hipError_t launch_grid_tendencies(const DevPlan &p, const GridTend &g, hipStream
 {
     const int gsz = p.ix * p.il;
     if (g.sh.nranks >= 1 && (p.kx > 16 || g.sh.nranks > p.kx || g.sh.rank < 0 || g.sh.rank >= g.sh.nranks)) return hipErrorInvalidValue;
+    // members: the block-per-levels kernel only, and not in the sharded forms
+    if (g.nmem < 1 || g.nmem > 65535 || (g.nmem > 1 && (p.kx > 16 || g.sh.nranks >= 1))) return hipErrorInvalidValue;
     if (p.kx > 16) hipLaunchKernelGGL(grid_tendencies_serial_kernel, dim3((gsz + 63) / 64), dim3(64), 0, s, p, g);
     else if (g.sh.nranks >= 1) {
         if (g.tr_out && (g.npts <= 0 || g.pt0 < 0 || g.pt0 + g.npts > gsz)) return hipErrorInvalidValue;
@@ -490,9 +501,9 @@ hipError_t launch_grid_tendencies(const DevPlan &p, const GridTend &g, hipStream
         // 16 points x kx levels per block: at model sizes the kernel is a latency chain per block, and 4x as many (smaller)
         // blocks spread its LDS traffic and loads over 4x as many CUs (T30: 72 -> 288 blocks; T63 L16 step 92.3 -> 89.2 us)
         constexpr int bx = GT_BX;
-        const dim3 grd((gsz + bx - 1) / bx), blk(bx, p.kx);
+        const dim3 grd((gsz + bx - 1) / bx, g.nmem), blk(bx, p.kx);
         const size_t lds = grid_tendencies_lds(p.kx, bx);
-        const bool wt = write_through_policy(p, (long)(9 * p.kx + 1) * gsz * 8);     // the launch's output: [3kx] + [3kx] + [3kx+1] grids
+        const bool wt = write_through_policy(p, (long)g.nmem * (9 * p.kx + 1) * gsz * 8);   // the launch's output: [3kx] + [3kx] + [3kx+1] grids per member
 #define GT_LAUNCH(KM_, FULL_)                                                                                     \
     do {                                                                                                          \
         if (wt) hipLaunchKernelGGL((grid_tendencies_kernel<KM_, FULL_, false, true>), grd, blk, lds, s, p, g);    \
@@ -546,6 +557,9 @@ hipError_t launch_tendency_combine(const DevPlan &p, double *pdiv, double *pspec
 // SH: level-sharded form -- the direct batches' outputs of all ranks arrive as ONE level-block stack (LevelShard, F = 9, X = 1;
 // SpecStep::sh) and the final tendencies leave through tend_out in the plain layout; everything else (the prognostics, the
 // solve, the leapfrog) is on the full columns as ever, redundantly on every rank.  Same expressions, same order.
+// Ensemble form (SpecStep::nmem, never SH): blockIdx.y is the member e.  Its prognostics are the [kx] stack e of each time level
+// (time levels nmem*kx fields apart; ps: field e, nmem apart), its direct-batch outputs level slot e*kx + k of each group (group
+// stride nmem*kx, level-free slot 3*nmem*kx + e).  Only these base offsets differ (nmem = 1: the same addresses); all are uniform.
 template <int NJ, bool FULL, bool SH>
 __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecStep &a)
 {
@@ -561,6 +575,11 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
     const int es = TR ? ec - a.e0 : ec;                                    // index into the direct batches' outputs
     const long ssz = TR ? a.ne : sz;                                       // ... and their slab size
     const long i = (long)k * sz + ec;                                     // this thread's (level, coefficient)
+    // the member's arrays: uniform offsets on the base pointers, every index below is the single state's
+    const int nmem = SH ? 1 : a.nmem, mem = SH ? 0 : blockIdx.y;
+    const long mo = (long)mem * kx * sz * 2, mp = (long)mem * sz * 2;      // its [kx] stack / its level-free field (doubles)
+    double *const a_vor = a.vor + mo, *const a_div = a.div + mo, *const a_t = a.t + mo, *const a_tr = a.tr + mo, *const a_ps = a.ps + mp;
+    double *const a_phi = a.phi + mo, *const a_pvor = a.pvor + mo, *const a_pdiv = a.pdiv + mo;
     const size_t PL = (size_t)kx * 2 * BX;                                 // doubles per complex plane [kx][BX]
     double *sdiv = sm, *stdt = sm + PL, *sy = sm + 2 * PL;
     auto at = [&](double *b, int kk) { return b + ((size_t)kk * BX + tx) * 2; };
@@ -572,20 +591,22 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
     // geopotential and the surface-pressure tendency (consumed by one level row each, but a load under a lane-dependent
     // condition is a branch and a full wait).  Requested where they are used, each was one more trip to memory on the block's
     // critical path.
-    const long lvl2 = (long)kx * sz;
-    const cpx vor2 = ld(a.vor, lvl2 + i), div2 = ld(a.div, lvl2 + i), t2 = ld(a.t, lvl2 + i), tr2 = ld(a.tr, lvl2 + i);
+    const long lvl2 = (long)nmem * kx * sz, psl2 = (long)nmem * sz;     // time level 2 of a prognostic / of ps, from time level 1
+    const cpx vor2 = ld(a_vor, lvl2 + i), div2 = ld(a_div, lvl2 + i), t2 = ld(a_t, lvl2 + i), tr2 = ld(a_tr, lvl2 + i);
     // the direct batch's outputs: group f of stack X (A = pvor / raw_u, B = pdiv / raw_v, C = pspec) at this thread's level is
     // element  (lv + f * L) + off_X  of pointer p_X.  Plain layout: three stacks [3 kx] with their own pointers.  Level-block
     // layout: one pointer, block of this level's owner = [A | B | C] (3 nl each) + its copy of the level-free psdt.
-    long lv = (long)k * sz, L = (long)kx * sz, offB = 0, offC = 0, ipsdt = (long)3 * kx * sz + es;
-    const double *pA = a.raw_u ? a.raw_u : a.pvor, *pB = a.raw_u ? a.raw_v : a.pdiv, *pC = a.pspec;
+    long lv = (long)k * sz, L = lvl2, offB = 0, offC = 0, ipsdt = 3 * lvl2 + es;
+    const double *pA = (a.raw_u ? a.raw_u : a.pvor) + mo, *pB = (a.raw_u ? a.raw_v : a.pdiv) + mo, *pC = a.pspec + mo;
+    double *const a_psdt = a.pspec + mp;                                  // + 3 * lvl2: the member's level-free field behind pspec's three groups
+    const double *pP = a_psdt;
     if (SH) {
         const LevelBlock b = level_block(k, kx, a.sh.nranks);
         lv = ((long)9 * b.lo + b.r + (k - b.lo)) * ssz; L = (long)b.nl * ssz; offB = 3 * L; offC = 6 * L;
         ipsdt = (long)9 * (kx / a.sh.nranks) * ssz + es;                  // block 0 = [9 nl_0] + psdt, nl_0 = floor(kx / R)
-        pA = pB = pC = a.pvor;
+        pA = pB = pC = pP = a.pvor;
     }
-    const cpx ps2 = ld(a.ps, sz + ec), phs = ld(a.phis, ec), psdt_in = ld(pC, ipsdt);
+    const cpx ps2 = ld(a_ps, psl2 + ec), phs = ld(a.phis, ec), psdt_in = ld(pP, ipsdt);
     // ---- tendency combination on the direct batch's outputs
     cpx vordt, pd0, pd1, pd2;
     if (a.raw_u) {
@@ -627,11 +648,11 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
     // hydrostatic integration -- are then short loops over LDS by ONE wave each (k = 0 and k = 1 run them side by side),
     // and everything else (tdt, divdt updates, phi write-out) is per (coefficient, level) again.  As one thread per
     // coefficient reading global memory level by level this phase was 40 us at T63 L16.
-    const cpx ps1 = ld(a.ps, ec);
+    const cpx ps1 = ld(a_ps, ec);
     double *sdv = sm + 3 * PL, *st1 = sm + 4 * PL, *ssig = sm + 5 * PL;                                  // ssig: kx + 1 rows
     double *smisc = ssig + (size_t)(kx + 1) * 2 * BX;                                                     // rows: dmean, psdt
-    put(sdv, k, ld(a.div, i));
-    put(st1, k, ld(a.t, i));
+    put(sdv, k, ld(a_div, i));
+    put(st1, k, ld(a_t, i));
     // implicit-solve operands, fetched now and consumed four barriers later (lds_sync leaves them in flight): this thread's row
     // of xj(:,:,l) into registers, its share of the xd / xc matrices (row-major copies, the same for every lane of a wave)
     // on the way to LDS.  Fetched where they are used, the three mat-vecs were half of this kernel's time.
@@ -721,7 +742,7 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
         const cpx dumk1 = k < kx - 1 ? (p.tref[k + 1] - p.tref[k]) * sig1 : cpx{0.0, 0.0};
         tdt = ((tdt - p.dhsr[k] * (dumk1 + dumk)) + p.tref3[k] * (sig1 + sig)) - p.tref2[k] * dmean;
         const cpx ph = get(sy, k);
-        if (valid) st(a.phi, i, ph);
+        if (valid) st(a_phi, i, ph);
         const cpx x = (valid ? ph : cpx{0.0, 0.0}) + p.rgtref[k] * ps1;
         divdt = divdt - p.el2[ec] * (-x);
     }
@@ -794,7 +815,7 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
     {
         const double dmp = p.dmp_t[0][ec], dmpd = p.dmp_t[1][ec], dmps = p.dmp_t[2][ec];
         const double dmp1 = p.dmp_t[3][ec], dmp1d = p.dmp_t[4][ec], dmp1s = p.dmp_t[5][ec];
-        vo = ld(a.vor, i); dv = ld(a.div, i); t1v = ld(a.t, i); tr1 = ld(a.tr, i);
+        vo = ld(a_vor, i); dv = ld(a_div, i); t1v = ld(a_t, i); tr1 = ld(a_tr, i);
         vordt = hd(vo, vordt, dmp, dmp1);
         divdt = hd(dv, divdt, dmpd, dmp1d);
         const cpx ctmp = t1v + p.tcorv[k] * ld(a.tcorh, ec);
@@ -826,17 +847,17 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
     };
     // (each thread reads back what it parked itself: no barrier needed)
     if (SH) {           // the operands are other ranks' blocks too (and, raw, neighbouring rows of other threads): tendencies leave apart
-        stepf(a.vor, i, lvl2, vo, get(sl2, k), vordt, a.tend_out, i);
-        stepf(a.div, i, lvl2, dv, get(sl2 + PL, k), divdt, a.tend_out, lvl2 + i);
-        stepf(a.t, i, lvl2, t1v, get(sl2 + 2 * PL, k), tdt, a.tend_out, 2 * lvl2 + i);
-        stepf(a.tr, i, lvl2, tr1, get(sl2 + 3 * PL, k), trdt, a.tend_out, 3 * lvl2 + i);
-        if (k == 0) stepf(a.ps, ec, sz, ps1, get(sl2 + 4 * PL, 0), psdt, a.tend_out, 4 * lvl2 + ec);
+        stepf(a_vor, i, lvl2, vo, get(sl2, k), vordt, a.tend_out, i);
+        stepf(a_div, i, lvl2, dv, get(sl2 + PL, k), divdt, a.tend_out, lvl2 + i);
+        stepf(a_t, i, lvl2, t1v, get(sl2 + 2 * PL, k), tdt, a.tend_out, 2 * lvl2 + i);
+        stepf(a_tr, i, lvl2, tr1, get(sl2 + 3 * PL, k), trdt, a.tend_out, 3 * lvl2 + i);
+        if (k == 0) stepf(a_ps, ec, sz, ps1, get(sl2 + 4 * PL, 0), psdt, a.tend_out, 4 * lvl2 + ec);
     } else {
-        stepf(a.vor, i, lvl2, vo, get(sl2, k), vordt, a.pvor, i);
-        stepf(a.div, i, lvl2, dv, get(sl2 + PL, k), divdt, a.pdiv, i);
-        stepf(a.t, i, lvl2, t1v, get(sl2 + 2 * PL, k), tdt, a.pdiv, (long)kx * sz + i);
-        stepf(a.tr, i, lvl2, tr1, get(sl2 + 3 * PL, k), trdt, a.pdiv, (long)2 * kx * sz + i);
-        if (k == 0) stepf(a.ps, ec, sz, ps1, get(sl2 + 4 * PL, 0), psdt, a.pspec, (long)3 * kx * sz + ec);
+        stepf(a_vor, i, lvl2, vo, get(sl2, k), vordt, a_pvor, i);
+        stepf(a_div, i, lvl2, dv, get(sl2 + PL, k), divdt, a_pdiv, i);
+        stepf(a_t, i, lvl2, t1v, get(sl2 + 2 * PL, k), tdt, a_pdiv, lvl2 + i);
+        stepf(a_tr, i, lvl2, tr1, get(sl2 + 3 * PL, k), trdt, a_pdiv, 2 * lvl2 + i);
+        if (k == 0) stepf(a_ps, ec, psl2, ps1, get(sl2 + 4 * PL, 0), psdt, a_psdt, 3 * lvl2 + ec);
     }
     STEP_MARK(7);
 }
@@ -856,7 +877,8 @@ hipError_t launch_spectral_step(const DevPlan &p, const SpecStep &a, hipStream_t
     if (p.kx > 16) return hipErrorInvalidValue;
     const int bx = spectral_step_bx(p);
     const size_t lds = spectral_step_lds(p.kx, bx);
-    dim3 grd((sz + bx - 1) / bx), blk(bx, p.kx);
+    if (a.nmem < 1 || a.nmem > 65535 || (a.nmem > 1 && a.sh.nranks >= 1)) return hipErrorInvalidValue;   // members: not in the sharded forms
+    dim3 grd((sz + bx - 1) / bx, a.nmem), blk(bx, p.kx);
     if (a.sh.nranks >= 1) {
         if (a.sh.nranks > p.kx || !a.tend_out) return hipErrorInvalidValue;
         if (a.ne > 0) {                                                    // transposed form: this rank's coefficient range only

@@ -1,0 +1,123 @@
+"""An ensemble of E model states that goes through ONE time step's launches (include/spdy.h, "ensemble time step").
+
+The layout is the single-state layout with every level dimension kx widened to E*kx, member-major inside it:
+
+    vor, div, t, tr   complex128 (2, E, kx, nx, mx)      time level lv of all members = one contiguous stack of E*kx fields
+    ps                complex128 (2, E, nx, mx)
+    phis, tcorh, qcorh           (nx, mx)                shared by all members
+    phi, phim                    (E, kx, nx, mx)         the step's geopotential, the physics' (time level 1)
+    ug, vg                       (E, kx, il, ix)
+    plain_g                      (4, E, kx, il, ix)      vorg | divg | tg | trg
+    px, py                       (E, il, ix)
+    U, V                         (3, E, kx, il, ix)      group-major operands of the direct batch: utend | -u T' | -u q
+    PL                           (3 E kx + E, il, ix)    KE | ttend | qtend (E*kx each), then the E level-free fields
+    pvor, pdiv / pspec           like U, V / PL, complex (nx, mx) fields
+
+so the transforms are the existing calls with larger counts, the physics tendencies of all members are the first E*kx fields of
+U, V and the second and third group of PL (states back to back at stride kx, what the column chain takes as nb = E), and member e of
+the two column kernels works on level slot e*kx + k with group stride E*kx.
+
+`step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  Not covered: SPPT (one pattern object
+holds one pattern), the level-sharded step."""
+import numpy as np
+
+PROG = ("vor", "div", "t", "tr", "ps")
+SHARED = ("phis", "tcorh", "qcorh")
+ROB, WIL = float(np.float32(0.05)), float(np.float32(0.53))          # params.f90:32-33 (float32 literals widened)
+SDRAG = 1.0 / (float(np.float32(24.0 * 30.0)) * 3600.0)              # time_stepping.f90:77, dynamical_constants.f90:22
+
+
+def shapes(nmem, kx, nx, mx, il, ix):
+    """name -> (shape, is complex) of every array of an E-member ensemble (no device needed)"""
+    E, s, g = nmem, (nx, mx), (il, ix)
+    out = {n: ((2, E, kx) + s, True) for n in ("vor", "div", "t", "tr")}
+    out["ps"] = ((2, E) + s, True)
+    out.update({n: (s, True) for n in SHARED})
+    out.update(phi=((E, kx) + s, True), phim=((E, kx) + s, True))
+    out.update(ug=((E, kx) + g, False), vg=((E, kx) + g, False), plain_g=((4, E, kx) + g, False), px=((E,) + g, False),
+               py=((E,) + g, False))
+    out.update(U=((3, E, kx) + g, False), V=((3, E, kx) + g, False), PL=((3 * E * kx + E,) + g, False))
+    out.update(pvor=((3, E, kx) + s, True), pdiv=((3, E, kx) + s, True), pspec=((3 * E * kx + E,) + s, True))
+    return out
+
+
+class Ensemble:
+    """The prognostics and the step's scratch of E members on the device, per-member views of them, and the step."""
+
+    def __init__(self, sp, nmem, device="cuda", sdrag=SDRAG, rob=ROB, wil=WIL):
+        import torch
+        if nmem < 1:
+            raise ValueError("an ensemble has at least one member")
+        need = nmem * max(3 * sp.kx + 1, 4 * sp.kx)      # the direct batch's plain fields; the inverse batch's (vorg | divg | tg | trg)
+        if sp.max_batch < need:
+            raise ValueError("the plan's max_batch must be >= nmem*max(3*kx+1, 4*kx) = %d" % need)
+        self.sp, self.nmem, self.kx = sp, nmem, sp.kx
+        self.sdrag, self.rob, self.wil = sdrag, rob, wil
+        for n, (shape, cplx) in shapes(nmem, sp.kx, sp.nx, sp.mx, sp.il, sp.ix).items():
+            setattr(self, n, torch.zeros(shape, dtype=torch.complex128 if cplx else torch.float64, device=device))
+        E, kx, g = nmem, sp.kx, self.plain_g
+        self.vorg, self.divg, self.tg, self.trg = g[0], g[1], g[2], g[3]
+        self.PLg = self.PL[:3 * E * kx].view(3, E, kx, sp.il, sp.ix)             # the three level groups of PL ...
+        self.PLs = self.PL[3 * E * kx:]                                          # ... and the E level-free fields
+        # the physics tendencies of all members (tendencies.f90:203-206): (E, kx) grids each
+        self.utend, self.vtend, self.ttend, self.qtend = self.U[0], self.V[0], self.PLg[1], self.PLg[2]
+
+    # ------------------------------------------------------------------ views
+    def member(self, e):
+        """the single-state dict of views of member e: vor, div, t, tr (2, kx, nx, mx), ps (2, nx, mx) and the shared phis, tcorh,
+        qcorh.  A time level of a member, D[n][lv], is contiguous; the two time levels are E*kx (ps: E) fields apart."""
+        D = {n: getattr(self, n)[:, e] for n in PROG}
+        D.update({n: getattr(self, n) for n in SHARED})
+        return D
+
+    def set_member(self, e, st):
+        """member e's prognostics from a single-state dict of host arrays (vor .. tr (2, kx, nx, mx), ps (2, nx, mx))"""
+        import torch
+        for n in PROG:
+            getattr(self, n)[:, e].copy_(torch.as_tensor(np.ascontiguousarray(st[n], np.complex128)))
+
+    def set_shared(self, st):
+        import torch
+        for n in SHARED:
+            getattr(self, n).copy_(torch.as_tensor(np.ascontiguousarray(st[n], np.complex128)))
+
+    # ------------------------------------------------------------------ the step
+    def physics_workspace(self):
+        """before a capture that contains a step with physics"""
+        self.sp.ens_physics_workspace(self.nmem)
+
+    def step(self, j1, j2, dt, physics=None, eps=None):
+        """step(j1, j2, dt) for every member.  The dynamics read time level j2 (tendencies.f90:89-107), the physics time level 1
+        (physics.f90:94-104).  physics: None (adiabatic) or a dict with "sw" (compute the shortwave on this step), "bnd" (dict of
+        SFC_BOUNDARY fields, (E, il, ix) each), "albsfc" (E, il, ix), "rad" (E radiation states back to back) and optionally "out"
+        (spdy_column_physics_out as a dict, every field E states long).  eps: the Robert filter's coefficient; by default
+        the reference's, 0 when j1 == 1 and rob otherwise (time_stepping.f90:108-112)."""
+        sp, E, kx, lv = self.sp, self.nmem, self.kx, j2 - 1
+        eps = (0.0 if j1 == 1 else self.rob) if eps is None else eps
+        flat = lambda a: a.view((-1,) + tuple(a.shape[-2:]))
+        vor, div, t, tr = (flat(getattr(self, n)[lv]) for n in ("vor", "div", "t", "tr"))
+        # everything that goes to the grid as one call: E*kx pairs, four plain segments of E*kx, E gradient fields
+        sp.inverse_batch_segs_dev(vor, div, flat(self.ug), flat(self.vg), [vor, div, t, tr], flat(self.plain_g), self.ps[lv], self.px,
+                                  self.py, kcos_pairs=2, kcos=1)
+        sp.ens_grid_tendencies_dev(E, self.ug, self.vg, self.tg, self.vorg, self.divg, self.trg, self.px, self.py, self.U, self.V,
+                                   self.PL)
+        if physics is not None:
+            sp.ens_geopotential_dev(E, self.t[0], self.phis, self.phim)
+            sp.ens_physics_dev(E, physics["sw"], self.vor[0], self.div[0], self.t[0], self.tr[0], self.phim, self.ps[0], physics["bnd"],
+                               physics["albsfc"], physics["rad"], self.utend, self.vtend, self.ttend, self.qtend, physics.get("out"))
+        sp.ens_direct_batch_spectral_step_dev(E, self.U, self.V, self.PL, self.pvor, self.pdiv, self.pspec, self.vor, self.div, self.t,
+                                              self.tr, self.ps, self.phis, self.tcorh, self.qcorh, self.sdrag, j1, dt, eps, self.wil,
+                                              self.phi, kcos=2)
+
+    def startup(self, delt, physics=None):
+        """first_step (time_stepping.f90:12-24): the forward half step, the first leapfrog step and the three initialize_implicit
+        calls.  physics: None, or a function n -> the physics dict of step n (n = -1, 0 number the two steps)."""
+        sp = self.sp
+        phys = (lambda n: None) if physics is None else physics
+        sp.initialize_implicit(0.5 * delt)
+        self.step(1, 1, 0.5 * delt, phys(-1))
+        sp.synchronize()
+        sp.initialize_implicit(delt)
+        self.step(1, 2, delt, phys(0))
+        sp.synchronize()
+        sp.initialize_implicit(2.0 * delt)

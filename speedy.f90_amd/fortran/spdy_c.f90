@@ -784,6 +784,53 @@ module spdy_c
             type(spdy_column_physics_out), intent(in) :: out
             integer(c_int) :: rc
         end function
+        ! the ensemble time step (include/spdy.h): nmem members through one step's launches; the drop-in steps one state and does
+        ! not call these
+        function spdy_ens_grid_tendencies_dev(plan, nmem, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out) &
+                & bind(C, name="spdy_ens_grid_tendencies_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out
+            integer(c_int), value :: nmem
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_spectral_step_dev(plan, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, &
+                & dt, eps, wil, phi) bind(C, name="spdy_ens_spectral_step_dev") result(rc)
+            import :: c_double, c_int, c_ptr
+            type(c_ptr), value :: plan, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi
+            real(c_double), value :: sdrag, dt, eps, wil
+            integer(c_int), value :: nmem, j1
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_direct_batch_spectral_step_dev(plan, nmem, d_ug, d_vg, d_grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, &
+                & ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi) &
+                & bind(C, name="spdy_ens_direct_batch_spectral_step_dev") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: plan, d_ug, d_vg, d_grid, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi
+            integer(c_int), value :: nmem, kcos, j1
+            real(c_double), value :: sdrag, dt, eps, wil
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_geopotential_dev(plan, nmem, t, phis, phi) bind(C, name="spdy_ens_geopotential_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, t, phis, phi
+            integer(c_int), value :: nmem
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_physics_workspace(plan, nmem) bind(C, name="spdy_ens_physics_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int), value :: nmem
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_physics_dev(plan, nmem, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, &
+                & qtend, out) bind(C, name="spdy_ens_physics_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_column_physics_out
+            type(c_ptr), value :: plan, vor, div, t, q, phi, ps, albsfc, rad_state, utend, vtend, ttend, qtend
+            integer(c_int), value :: nmem, compute_sw
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_column_physics_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
         ! the surface models (include/spdy.h): this file is one-to-one with the header; the drop-in's own physics still runs on
         ! the host and does not call these
         function spdy_surface_model_create(plan, clim, delt, flags, model) bind(C, name="spdy_surface_model_create") result(rc)

@@ -455,6 +455,37 @@ class Spectral(ColumnPhysics):
                                                            *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt), float(eps),
                                                            float(wil), self._dp(phi)))
 
+    # ------------------------------------------------------------------ ensemble time step (layout: ensemble.py)
+    def ens_grid_tendencies_dev(self, nmem, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out):
+        """grid_tendencies_dev for nmem members in one launch: inputs (nmem, kx) grids each, px, py (nmem); outputs group-major,
+        u_out, v_out (3, nmem, kx), plain_out (3, nmem, kx) followed by the nmem level-free fields."""
+        self._sync_stream()
+        args = (ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out)
+        check(self.lib.spdy_ens_grid_tendencies_dev(self.h, int(nmem), *[self._dp(x) for x in args]))
+
+    def ens_spectral_step_dev(self, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh, sdrag, j1, dt, eps, wil, phi):
+        """spectral_step_dev for nmem members in one launch: prognostics (2, nmem, kx, nx, mx) / ps (2, nmem, nx, mx), phi
+        (nmem, kx, nx, mx), pvor, pdiv, pspec group-major; phis, tcorh, qcorh are shared."""
+        self._sync_stream()
+        args = (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh)
+        check(self.lib.spdy_ens_spectral_step_dev(self.h, int(nmem), *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt),
+                                                  float(eps), float(wil), self._dp(phi)))
+
+    def ens_direct_batch_spectral_step_dev(self, nmem, ug, vg, grid, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh, sdrag,
+                                           j1, dt, eps, wil, phi, kcos=2):
+        """direct_batch_spectral_step_dev for nmem members: 3*nmem*kx pairs and 3*nmem*kx + nmem plain fields through one
+        direct batch, then ens_spectral_step_dev."""
+        self._sync_stream()
+        args = (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh)
+        check(self.lib.spdy_ens_direct_batch_spectral_step_dev(self.h, int(nmem), self._dp(ug), self._dp(vg), self._dp(grid), int(kcos),
+                                                               *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt),
+                                                               float(eps), float(wil), self._dp(phi)))
+
+    def ens_geopotential_dev(self, nmem, t, phis, phi):
+        """geopotential_dev for nmem members: t, phi (nmem, kx, nx, mx), phis shared"""
+        self._sync_stream()
+        check(self.lib.spdy_ens_geopotential_dev(self.h, int(nmem), self._dp(t), self._dp(phis), self._dp(phi)))
+
     def output_batch_dev(self, vor, div, t, q, phi, ps, u_out, v_out, t_out, q_out, phi_out, ps_out):
         """input_output.f90:184-206 on device-resident state: complex128 [kx,nx,mx] (ps [nx,mx]) in, float32 [kx,il,ix]
         (ps_out [il,ix]) out."""

@@ -1,0 +1,168 @@
+#!/usr/bin/env python3
+"""What an ensemble member costs: graph replays of the E-member step (speedy.f90_amd/ensemble.py) against the single-state
+captured step of tests/modelstep.py, adiabatic and with the whole physics, T30 L8 and T63 L16.
+
+Per size and E it prints one JSON row: microseconds per step (median of --repeats timings of --reps replays, with the range),
+microseconds per member-step, the speed-up per member over E single-state steps measured in the same process, and the launches'
+byte model (below) as a fraction of 8 TB/s.  Timing as tools/physics_step_rate.py: HIP events around the replays, 10 warm-up
+replays, the forms interleaved repeat by repeat; every repeat starts from the same state.
+
+The comparison with an earlier build: --single-only times the single-state step alone and works with a library that has no
+ensemble entry points; select it with $SPDY_LIB.  Run that and this build's --single-only alternately, twice each: the difference
+between two runs of the same build is the run-to-run spread a difference between the builds has to exceed.
+
+    python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
+    SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import torch  # noqa: E402
+
+import modelstep  # noqa: E402
+import moist  # noqa: E402
+import physstep  # noqa: E402
+import synth  # noqa: E402
+import speedy_f90_amd as s  # noqa: E402
+from conftest import VARIANTS  # noqa: E402
+
+HBM = 8.0e12
+
+
+def byte_model(sp, physics):
+    """bytes one member's step moves through HBM if every launch reads its inputs and writes its outputs once: the inverse batch
+    (6 kx + 1 spectra in, 6 kx + 2 grids out), the grid tendencies (6 kx + 2 grids in, 9 kx + 1 out), the direct batch (9 kx + 1
+    grids in, as many spectra out), the spectral step (those spectra and both time levels of the prognostics in; the prognostics,
+    the tendencies and phi out); with physics the geopotential, its inverse launch (5 kx + 1 fields) and the chain (those grids,
+    the four tendencies in and out, 9 boundary fields, the radiation state of 6 kx + 7 fields in and out)"""
+    kx, spec, grid = sp.kx, sp.nx * sp.mx * 16, sp.il * sp.ix * 8
+    prog = 2 * (4 * kx + 1)
+    b = (6 * kx + 1) * spec + 2 * (6 * kx + 2) * grid + 2 * (9 * kx + 1) * grid + 2 * (9 * kx + 1) * spec
+    b += (prog + 3) * spec + (prog + 4 * kx + 1 + kx) * spec
+    if physics:
+        b += 2 * kx * spec + (5 * kx + 1) * (spec + 2 * grid) + (8 * kx + 9 + 2 * (6 * kx + 7)) * grid
+    return b
+
+
+def time_interleaved(fns, rearm, reps, repeats):
+    for fn in fns.values():
+        for _ in range(10):
+            fn()
+    us = {n: [] for n in fns}
+    for _ in range(repeats):
+        for n, fn in fns.items():
+            rearm()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            us[n].append(a.elapsed_time(b) * 1e3 / reps)
+    return {n: (float(np.median(v)), min(v), max(v)) for n, v in us.items()}
+
+
+def run(tag, members, reps, repeats, label, rows):
+    from oracle.pyoracle import Oracle, build
+    build()
+    kx = VARIANTS[tag][3]
+    o = Oracle(*VARIANTS[tag])
+    if tag in synth.SIGMA_SETS:
+        o.set_sigma(synth.SIGMA_SETS[tag])
+    emax = max(members) if members else 1
+    sp = moist.plan(tag, emax * (4 * kx + 4))
+    case = physstep.Case(tag, sp, o)
+    sp.surface_set_orography(case.phis0)
+    dt = physstep.DT[tag]
+    sp.initialize_implicit(dt)
+    sp.physics_workspace()
+    # the single-state step
+    W, P, D0 = modelstep.Workspace(sp), modelstep.physics_buffers(sp, case.bnd, 0.0), modelstep.device_state(case.st)
+    D = {n: D0[n].clone() for n in D0}
+    modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, True))     # a shortwave step first: the radiation state is whole
+    sp.synchronize()
+    rad0 = P["rad"].clone()
+    graphs, rearms = {}, []
+    for name, phys in (("single adiabatic", False), ("single physics", True)):
+        torch.cuda.synchronize()
+        with sp.graph_capture() as g:
+            modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, False) if phys else None)
+        graphs[name] = g
+
+    def rearm_single():
+        for n in D:
+            D[n].copy_(D0[n])
+        P["rad"].copy_(rad0)
+    rearms.append(rearm_single)
+    ens = {}
+    for E in members:
+        en = s.Ensemble(sp, E)
+        en.set_shared(case.st)
+        for e in range(E):
+            en.set_member(e, case.st)
+        dev = physstep.device_boundary(case.bnd, sp.il, sp.ix)
+        bnd = {n: v.expand((E,) + tuple(v.shape[1:])).contiguous() for n, v in dev.items()}
+        PE = {"bnd": bnd, "albsfc": bnd["albsfc"], "rad": rad0.repeat(E), "sw": False}
+        en.physics_workspace()
+        start = {n: getattr(en, n).clone() for n in ("vor", "div", "t", "tr", "ps")}
+        for name, phys in (("E=%d adiabatic" % E, None), ("E=%d physics" % E, PE)):
+            torch.cuda.synchronize()
+            with sp.graph_capture() as g:
+                en.step(2, 2, dt, phys, eps=modelstep.ROB)
+            graphs[name] = g
+
+        def rearm(en=en, start=start, PE=PE, E=E):
+            for n, v in start.items():
+                getattr(en, n).copy_(v)
+            PE["rad"].copy_(rad0.repeat(E))
+        rearms.append(rearm)
+        ens[E] = en
+    nodes = {n: g.num_nodes() for n, g in graphs.items()}
+    t = time_interleaved({n: g.launch for n, g in graphs.items()}, lambda: [r() for r in rearms], reps, repeats)
+    for name, (med, lo, hi) in t.items():
+        phys = name.endswith("physics")
+        E = 1 if name.startswith("single") else int(name.split()[0][2:])
+        one = t["single physics" if phys else "single adiabatic"][0]
+        row = {"label": label, "size": tag, "form": name, "members": E, "nodes": nodes[name], "us_per_step": round(med, 2),
+               "us_min": round(lo, 2), "us_max": round(hi, 2), "us_per_member_step": round(med / E, 2),
+               "speedup_per_member_vs_single": round(one / (med / E), 2),
+               "byte_model_fraction_of_8TBps": round(E * byte_model(sp, phys) / (med * 1e-6) / HBM, 4)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for g in graphs.values():
+        g.close()
+    sp.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", nargs="+", default=["t30", "t63k16"])
+    ap.add_argument("--members", nargs="+", type=int, default=[1, 2, 4, 8, 16, 32])
+    ap.add_argument("--single-only", action="store_true")
+    ap.add_argument("--label", default="this build")
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    if a.single_only:          # a library from before the ensemble entry points: bind (on first use) without them
+        from speedy_f90_amd import _lib
+        for n in [n for n in _lib.SIGNATURES if n.startswith("spdy_ens_")]:
+            del _lib.SIGNATURES[n]
+    rows = []
+    with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
+        for tag in a.sizes:
+            run(tag, [] if a.single_only else a.members, a.reps, a.repeats, a.label, rows)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
