@@ -114,6 +114,9 @@ newer "$OUT/libspeedy_ref_t63.so" || build_one t63 "$T63"
 newer "$OUT/libspeedy_ref_t30k5.so" || build_one t30k5 's/kx = 8 /kx = 5 /' -O2 '/hsg(:8) = /d; /hsg(:9) = /d'
 newer "$OUT/libspeedy_ref_t30k7.so" || build_one t30k7 's/kx = 8 /kx = 7 /' -O2 '/hsg(:9) = /d'
 newer "$OUT/libspeedy_ref_t63k16.so" || build_one t63k16 "$T63; s/kx = 8 /kx = 16/"
+# 12 levels, inside the 9..15 class of the step kernels (tests/levels.py); half levels through ref_set_sigma like the 16-level
+# build.  geometry.f90 needs no patch: its dead branches assign at most 9 of the 13 half levels.
+newer "$OUT/libspeedy_ref_t30k12.so" || build_one t30k12 's/kx = 8 /kx = 12/'
 # CPU-baseline variant mirroring upstream's -Ofast (gfortran.makefile:18): value-unsafe optimisation allowed, AVX2+FMA
 # (x86-64-v3 rather than -march=native: the .so is built here and timed on the GPU box's host CPU)
 newer "$OUT/libspeedy_ref_t30fast.so" || build_one t30fast '' '-O3 -ffast-math -march=x86-64-v3'

@@ -83,6 +83,7 @@ __global__ void implicit_kernel(DevPlan p, double *__restrict__ divdt, double *_
 }
 
 static size_t implicit_lds(int kx) { return (size_t)3 * kx * 64 * 16; }
+constexpr int IMPLICIT_MAX_KX = 32;  // SPDY_MAX_KX (include/spdy.h; spdy_plan_create refuses more): 96 KiB
 
 constexpr size_t spectral_step_lds(int kx, int bx = 16)   // 5 planes + (kx+1) sigma rows + 2 rows + row-major xd, xc + 5 level tables + 4 planes and a row (time level 2)
 {
@@ -96,8 +97,10 @@ hipError_t prepare_device_step_kernels(int kx)
 {
     static_assert(grid_tendencies_lds(16) <= 64 * 1024, "the grid-tendencies kernel fits the default dynamic LDS limit");
     if (implicit_lds(kx) > 64 * 1024) {
+        // the limit belongs to the kernel, not to a plan: always what the largest level count needs, so that a plan of fewer
+        // levels created later does not lower it under a live plan of more
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(implicit_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)implicit_lds(kx));
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)implicit_lds(IMPLICIT_MAX_KX));
         if (e != hipSuccess) return e;
     }
     static_assert(spectral_step_lds_max() <= 64 * 1024, "the one-launch spectral step fits the default dynamic LDS limit");

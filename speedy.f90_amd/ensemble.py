@@ -44,7 +44,9 @@ def shapes(nmem, kx, nx, mx, il, ix):
 class Ensemble:
     """The prognostics and the step's scratch of E members on the device, per-member views of them, and the step."""
 
-    def __init__(self, sp, nmem, device="cuda", sdrag=SDRAG, rob=ROB, wil=WIL):
+    def __init__(self, sp, nmem, device="cuda", sdrag=SDRAG, rob=ROB, wil=WIL, arrays=None):
+        """arrays: optionally {name: tensor} of caller-made contiguous tensors on `device` to use for those arrays in place of fresh
+        ones, each of the shape and type `shapes` gives (a host that places the ensemble inside its own allocations)."""
         import torch
         if nmem < 1:
             raise ValueError("an ensemble has at least one member")
@@ -53,8 +55,17 @@ class Ensemble:
             raise ValueError("the plan's max_batch must be >= nmem*max(3*kx+1, 4*kx) = %d" % need)
         self.sp, self.nmem, self.kx = sp, nmem, sp.kx
         self.sdrag, self.rob, self.wil = sdrag, rob, wil
+        given = dict(arrays or {})
         for n, (shape, cplx) in shapes(nmem, sp.kx, sp.nx, sp.mx, sp.il, sp.ix).items():
-            setattr(self, n, torch.zeros(shape, dtype=torch.complex128 if cplx else torch.float64, device=device))
+            dtype = torch.complex128 if cplx else torch.float64
+            a = given.pop(n, None)
+            if a is None:
+                a = torch.zeros(shape, dtype=dtype, device=device)
+            elif tuple(a.shape) != shape or a.dtype != dtype or not a.is_contiguous():
+                raise ValueError("array %s must be a contiguous tensor of shape %s and type %s" % (n, shape, dtype))
+            setattr(self, n, a)
+        if given:
+            raise ValueError("not arrays of an ensemble: %s" % sorted(given))
         E, kx, g = nmem, sp.kx, self.plain_g
         self.vorg, self.divg, self.tg, self.trg = g[0], g[1], g[2], g[3]
         self.PLg = self.PL[:3 * E * kx].view(3, E, kx, sp.il, sp.ix)             # the three level groups of PL ...

@@ -144,15 +144,29 @@ def three_steps(sp, case, dt, run):
     return after, D, W, P
 
 
-def run_dynamical_core_steps(sp, o, form, nsteps=2):
+def oracle_dynamical_core_steps(o, sp, nsteps=2, dt=2400.0):
+    """the oracle's side of run_dynamical_core_steps: [(state after step n, its out dict)], to be computed once and shared"""
+    o.tail_init(dt)
+    ref, seq = dyn_state(sp, 8000), []
+    for n in range(nsteps):
+        ref, out = oracle_dynamics_step(o, ref, 2, dt, ROB)
+        seq.append((ref, out))
+    return seq
+
+
+def run_dynamical_core_steps(sp, o, form, nsteps=2, ref_steps=None, keep=None):
     """Captures a COMPLETE adiabatic time step of the dynamical core on device-resident state into one graph, replays it
     `nsteps` times against the oracle's call-by-call sequence and returns, per step, {array: (relerr, wave_relerr)} for the
     grid tendencies U, V, PL, the geopotential, the spectral tendencies the step leaves in place ("one_launch" keeps them in
-    registers) and the five prognostics."""
+    registers) and the five prognostics.  ref_steps: the oracle's sequence where the caller holds it already
+    (oracle_dynamical_core_steps; o is not used then).  keep: a list that receives, per step, host copies of U, V, PL, phi and
+    the prognostics as the device left them."""
     import torch
     import synth
     dt = 2400.0
-    sp.initialize_implicit(dt); o.tail_init(dt)
+    sp.initialize_implicit(dt)
+    if ref_steps is None:
+        o.tail_init(dt)
     st = dyn_state(sp, 8000)
     D, W = device_state(st), Workspace(sp)
     sp.use_own_stream()
@@ -164,7 +178,9 @@ def run_dynamical_core_steps(sp, o, form, nsteps=2):
     for n in range(nsteps):
         g.launch()                                      # the graph is the whole step: nothing else runs between replays
         sp.synchronize()
-        ref, out = oracle_dynamics_step(o, ref, 2, dt, ROB)
+        ref, out = oracle_dynamics_step(o, ref, 2, dt, ROB) if ref_steps is None else ref_steps[n]
+        if keep is not None:
+            keep.append(dict({k: getattr(W, k).cpu().numpy() for k in ("U", "V", "PL", "phi")}, **{k: D[k].cpu().numpy() for k in PROG}))
         e = {k: (synth.relerr(a.cpu().numpy(), out[k]),) * 2 for k, a in (("U", W.U), ("V", W.V), ("PL", W.PL))}
         e["phi"] = err(W.phi, out["phi"])
         if form != "one_launch":

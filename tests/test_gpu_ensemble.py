@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import ensemblestep as es
+import levels
 import modelstep
 import moist
 import physstep
@@ -24,13 +25,19 @@ def _plan(tag, nmem):
     return moist.plan(tag, nmem * (4 * kx + 4))
 
 
-@pytest.mark.parametrize("E,kx", [(3, 8), (2, 5), (2, 7), (17, 8)])
+def _plan_of_levels(kx, nmem):
+    """the plan of kx levels: the reference's own sets (TAGS), any other count on tests/levels.py's half levels"""
+    return _plan(TAGS[kx], nmem) if kx in TAGS else levels.plan("t30", kx, nmem * (4 * kx + 4))
+
+
+@pytest.mark.parametrize("E,kx", [(3, 8), (2, 5), (2, 7), (17, 8), (2, 1), (3, 4), (2, 6), (2, 9), (3, 12), (2, 15)])
 @pytest.mark.parametrize("seq", ["leapfrog", "startup"])
 def test_member_equals_single_adiabatic(E, kx, seq):
     """T30: two consecutive leapfrog steps / the start-up pair; every member's prognostics, phi and its slices of U, V, PL bit-equal
     to the single-state step on that member's state.  kx = 5, 7: the FULL = false kernels; E = 17 pushes the transform launches
-    out of the model-sized form."""
-    sp = _plan(TAGS[kx], E)
+    out of the model-sized form.  kx = 1, 4, 6: the small blocks of the 8-bound kernels; 9, 12, 15: the 16-bound kernels' FULL =
+    false forms, which nothing else runs with members (tests/levels.py)."""
+    sp = _plan_of_levels(kx, E)
     steps = es.LEAPFROG if seq == "leapfrog" else es.STARTUP
     sts = es.member_states(sp, E)
     snaps = es.run_ensemble(sp, es.build(sp, sts), steps, DELT)

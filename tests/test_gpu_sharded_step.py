@@ -23,6 +23,7 @@ import threading
 import numpy as np
 import pytest
 
+import levels
 import modelstep
 import synth
 from conftest import TOL, VARIANTS
@@ -33,8 +34,25 @@ DT = 2400.0
 PROGS = ("vor", "div", "t", "tr", "ps")
 
 
+def level_count(tag):
+    """tag: a key of conftest.VARIANTS, or a (trunc_tag, kx) pair of tests/levels.py"""
+    return tag[1] if isinstance(tag, tuple) else VARIANTS[tag][3]
+
+
+def is_t30(tag):
+    return (tag[0] if isinstance(tag, tuple) else tag).startswith("t30")
+
+
+def oracle_of(tag, oracle_factory):
+    return levels.oracle(*tag) if isinstance(tag, tuple) else oracle_factory(tag)
+
+
 def make_plan(tag, device=0):
     import speedy_f90_amd as s
+    if isinstance(tag, tuple):
+        sp = levels.plan(tag[0], tag[1], 4 * tag[1] + 4, device)
+        sp.initialize_implicit(DT)
+        return sp
     trunc, ix, iy, kx = VARIANTS[tag]
     sp = s.Spectral((trunc, ix, iy), kx=kx, max_batch=4 * kx + 4, device=device)
     if tag in synth.SIGMA_SETS:
@@ -110,8 +128,8 @@ def _rank_thread(rank, group, tag, st, nsteps, results, errors, device=0, transp
 def test_sharded_step_in_process_ranks(tag, world, oracle_factory, monkeypatch):
     import speedy_f90_amd as s
     monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
-    kx = VARIANTS[tag][3]
-    o = oracle_factory(tag)
+    kx = level_count(tag)
+    o = oracle_of(tag, oracle_factory)
     o.tail_init(DT)
     sp0 = make_plan(tag)
     st = state(sp0, 8000)
@@ -164,10 +182,16 @@ def test_sharded_step_transposed_in_process_ranks(tag, world, oracle_factory, mo
     on the first one's whole state it moves values that are already there), then the state gather.  Against the oracle's call-by-call step at 1e-12; against the unsharded device step
     BIT FOR BIT at T30 (same kernels' expressions on the same values, whatever the rank count) and to rounding at T63 L16 (there
     the unsharded step applies vds inside the spectral step, the transposed form before its exchange)."""
+    transposed_in_process_ranks(tag, world, oracle_factory, monkeypatch)
+
+
+def transposed_in_process_ranks(tag, world, oracle_factory, monkeypatch, pays=0.6):
+    """the body of test_sharded_step_transposed_in_process_ranks.  pays: from four ranks on every rank of the transposed form
+    receives less than this part of the all-gather form's bytes (0.6 for the equal level blocks of that test's cases)"""
     import speedy_f90_amd as s
     monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
-    kx = VARIANTS[tag][3]
-    o = oracle_factory(tag)
+    kx = level_count(tag)
+    o = oracle_of(tag, oracle_factory)
     o.tail_init(DT)
     sp0 = make_plan(tag)
     st = state(sp0, 8000)
@@ -187,7 +211,7 @@ def test_sharded_step_transposed_in_process_ranks(tag, world, oracle_factory, mo
     for _ in range(nsteps):
         ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
     ref_tend = np.concatenate([out["vordt"], out["divdt"], out["tdt"], out["trdt"], out["psdt"][None]])
-    exact = tag.startswith("t30")
+    exact = is_t30(tag)
     worst, covered = 0.0, 0
     for r in range(world):
         got = results[r]
@@ -223,7 +247,7 @@ def test_sharded_step_transposed_in_process_ranks(tag, world, oracle_factory, mo
         d = got["describe"]
         assert d["form"] == "transpose" and d["nranks"] == world and d["rank"] == r
         if world >= 4:      # (at two ranks the four exchanges move about what the two all-gathers do; the form pays from four ranks on)
-            assert d["bytes_received_per_step_transposed_form"] < 0.6 * d["bytes_received_per_step_allgather_form"], d
+            assert d["bytes_received_per_step_transposed_form"] < pays * d["bytes_received_per_step_allgather_form"], d
     assert covered == results[0]["vor"].shape[-1] * results[0]["vor"].shape[-2]
     print("\n[transposed sharded step %s, %d in-process ranks] worst relative error vs the oracle %.1e; %s the unsharded device step"
           % (tag, world, worst, "bits equal to" if exact else "within 1e-13 of"))

@@ -424,3 +424,65 @@ def test_step_restatements_selfconsistent(oracle_factory):
     assert np.array_equal(phi, rphi)
     for x, y in ((A, rdiv), (B, rt), (C, rps)):
         assert synth.relerr(x, y) < 1e-14
+
+
+def _levels12(o, golden_of):
+    """the oracle at 12 levels (tests/levels.py) against golden_of(key): the sigma tables, get_geopotential and, at two time steps,
+    tref*, implicit_terms, do_horizontal_diffusion and one adiabatic step(2, 2, dt) with its get_tendencies -- BIT FOR BIT"""
+    import dynstep
+    from golden.make_golden_levels import DTS, SUB, geop_inputs
+    cut = lambda a: a[SUB]
+    same = lambda a, key: (a.shape == golden_of(key).shape and np.array_equal(a, golden_of(key)), key)
+    for name in ("hsg", "dhs", "fsg", "dhsr", "fsgr", "tcorv", "qcorv"):
+        assert np.array_equal(o.table(name), golden_of(name)), name
+    assert np.all(np.isfinite(o.table("fsgr")))
+    T, phis = geop_inputs(o.kx, o.nx, o.mx)
+    ok, key = same(cut(o.geopotential(T, phis)), "geop")
+    assert ok, key
+    div, t, ps = tail_inputs(o.kx, o.nx, o.mx)
+    st = dynstep.state(o, 8000)
+    for dt in DTS:
+        key = "dt%d_" % int(dt)
+        o.tail_init(dt)
+        for name in ("tref", "tref2", "tref3"):
+            assert np.array_equal(o.table(name), golden_of(key + name)), (dt, name)
+        a, b, c = o.implicit_terms(div, t, ps)
+        h = o.hdiff(t, div, o.table("dmpd").reshape(o.nx, o.mx), o.table("dmp1d").reshape(o.nx, o.mx))
+        for x, name in ((cut(a), "imp_div_out"), (cut(b), "imp_t_out"), (c, "imp_ps_out"), (cut(h), "hdiff3d")):
+            assert np.all(np.isfinite(x)), (dt, name)
+            ok, k = same(x, key + name)
+            assert ok, k
+        new, out = dynstep.oracle_dynamics_step(o, st, 2, dt, dynstep.ROB, j2=2, before_diffusion=True)
+        key += "j22_"
+        for n in ("vor", "div", "t", "tr"):
+            ok, k = same(new[n][(Ellipsis,) + SUB[1:]], key + n)
+            assert ok, k
+        assert same(new["ps"], key + "ps")[0] and same(cut(out["phi"]), key + "phi")[0], key
+        for n in ("vordt", "divdt", "tdt", "psdt", "trdt"):             # get_tendencies: before the diffusion and the leapfrog
+            a = out["pre_" + n]
+            ok, k = same(a if n == "psdt" else cut(a), key + n)
+            assert ok, k
+
+
+def test_levels12_pinned():
+    """The oracle inside the 9..15 level class of the step kernels: at kx = 12 against the flang build of the reference with
+    kx = 12 (oracle/build_ref.sh t30k12; tests/golden/ref_levels.npz, tests/golden/make_golden_levels.py)."""
+    import levels
+    z = np.load(os.path.join(GOLDEN, "ref_levels.npz"))
+    _levels12(levels.oracle("t30", 12), lambda key: z[key])
+
+
+def test_levels12_live():
+    """The same against the flang build itself, where oracle/_ref holds it: nothing between the reference and the oracle."""
+    import levels
+    from oracle.pyoracle import Reference
+    from golden import make_golden_levels as mg
+    levels.oracle("t30", 12)                                  # (builds oracle/_ref where the reference's sources are present)
+    if not Reference.available(mg.TAG):
+        pytest.skip("no flang build of the reference at 12 levels here")
+    d = mg.make(mg.reference())
+    _levels12(levels.oracle("t30", 12), lambda key: d[key])
+    z = np.load(os.path.join(GOLDEN, "ref_levels.npz"))       # and the committed file is what the build gives
+    assert sorted(z.files) == sorted(d)
+    for k in z.files:
+        assert np.array_equal(z[k], d[k]), k
