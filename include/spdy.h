@@ -134,6 +134,10 @@ int spdy_plan_set_fused(spdy_plan *plan, int mode);
  *   "t63_np2_from" >= 1, "wt_min_mb" >= 0                              as $SPDY_T63_NP2_FROM, $SPDY_WT_MIN_MB
  *   "physics_fused"     the column-physics chain as ONE launch (1) or as its five calls (0), same bits either way; any other
  *                       value is SPDY_ERR_ARG.  Never set: spdy_column_physics_dev makes the five calls, spdy_physics_dev the one launch
+ *   "ens_member_qcorh"  1: spdy_ens_spectral_step_dev and spdy_ens_direct_batch_spectral_step_dev read d_qcorh as (mx,nx,nmem), a
+ *                       field per member ("ensemble time step" below); 0 (the default): one shared (mx,nx) field.  Read when the
+ *                       call is enqueued; the single-state calls ignore it.  Any other value is SPDY_ERR_ARG.  It describes
+ *                       an argument, not a launch form, so it alone may be set while a capture is open.
  * Not while a graph capture is open (SPDY_ERR_STATE); captured graphs keep the forms they were captured with.       */
 int spdy_plan_set_option(spdy_plan *plan, const char *name, int value);
 int spdy_plan_get_profile(spdy_plan *plan, double *ms, int *launches);
@@ -289,7 +293,7 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *plan, const double *d_ug, con
  * A T30 L8 step is four or five launches, each bound by its fixed costs, not by bytes: an ensemble amortises them.  An ensemble
  * array is the single-state array with every level dimension kx widened to nmem*kx, member-major inside it:
  *     vor, div, t, tr  (mx,nx,kx,nmem,2)   ps (mx,nx,nmem,2)     time level lv of all members = one stack of nmem*kx fields
- *     phis, d_tcorh, d_qcorh (mx,nx)       shared by all members
+ *     phis, d_tcorh, d_qcorh (mx,nx)       shared by all members; with the plan option "ens_member_qcorh" d_qcorh is (mx,nx,nmem)
  *     phi              (mx,nx,kx,nmem)
  *     ug, vg, tg, vorg, divg, trg (ix,il,kx,nmem)                px, py (ix,il,nmem)
  *     u_out, v_out, pvor, pdiv  [3][nmem][kx]                    group-major: the group stride is nmem*kx fields
@@ -312,7 +316,15 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *plan, const double *d_ug, con
  * Checks, in this order: a NULL plan, nmem < 1, kx > 16 with nmem > 1 (physics: kx outside [5, 16]) and
  * max_batch < nmem*(3*kx+1) SPDY_ERR_ARG; what the single-state call needs first (spdy_implicit_init, sigma levels; physics: sigma
  * levels, date, orography) SPDY_ERR_STATE; a NULL required pointer, then j1 outside {1, 2} SPDY_ERR_ARG; a host-only plan
- * SPDY_ERR_NO_DEVICE last.  Every call can be captured.  Not covered: SPPT (a pattern object holds one pattern), the sharded step. */
+ * SPDY_ERR_NO_DEVICE last.  Every call can be captured.  Not covered: SPPT (a pattern object holds one pattern), the sharded step.
+ * A coupled ensemble needs the option "ens_member_qcorh": qcorh = grid_to_spec(corh) and corh is made from the member's own stl_am
+ * and sst_am ("surface models" below), so once the members' land and sea temperatures differ no two members have the same qcorh.
+ * d_tcorh depends neither on time nor on the member and stays shared.  In the kernel it is one more uniform member offset (a
+ * stride of 0 or mx*nx complex); no expression changes.  The surface models and the guard of all members are one object each
+ * (spdy_ens_surface_model_create, spdy_ens_diagnostics_create), one launch per call.  Order of calls of a coupled ensemble step: on
+ * a day's first step forcing_dev(qcorh (mx,nx,nmem)); the step, its physics reading the model's boundary arrays and writing
+ * hfluxn, shf, evap, ssrd of all members; check_dev on time level 2; the host's newdate, and set_date when the day changed;
+ * couple_dev(day).                                                                                                              */
 int spdy_ens_grid_tendencies_dev(spdy_plan *plan, int nmem, const double *ug, const double *vg, const double *tg, const double *vorg,
                                  const double *divg, const double *trg, const double *px, const double *py, double *u_out,
                                  double *v_out, double *plain_out);
@@ -746,6 +758,18 @@ int spdy_physics_sppt_dev(spdy_plan *plan, spdy_sppt *s, int compute_sw, const d
  * host's newdate, and set_date when the day changed (and set_sst_anomaly where obs_ssta would run); couple(day).
  * Checks: a NULL required pointer SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE; couple or forcing before set_date, and
  * forcing or couple(day > 0) before couple(0), SPDY_ERR_STATE.
+ * nmem members (spdy_ens_surface_model_create; spdy_surface_model_create is that call with nmem = 1; nmem < 1 SPDY_ERR_ARG): the
+ * same object type.  Held once: what no kernel writes -- fmask_s, alb0, rhcapl, cdland, rhcaps, rhcapi, cdsea, cdice, the five
+ * 12-month fields, sstan3 and the date, which set_date, set_sst_anomaly and table serve unchanged: the date and the anomaly window
+ * are the ensemble's.  Held per member, (ix,il,nmem) each (member e of a field is ix*il doubles after member e - 1): every field
+ * couple or forcing writes, stlcl_ob .. corh in field's list, and fmask_l, replicated, since the physics takes every boundary field
+ * per state.  So boundary hands out (ix,il,nmem) arrays, the shape spdy_ens_physics_dev takes, and corh of all members is one stack
+ * of nmem grids.  couple takes hfluxn (ix,il,2,nmem), shf, evap (ix,il,3,nmem), ssrd (ix,il,nmem) -- what spdy_ens_physics_dev writes
+ * through `out` -- and is ONE launch with the member in blockIdx.y; forcing is one such launch and ONE spdy_grid_to_spec_dev of nmem
+ * fields into the caller's qcorh (mx,nx,nmem) (nmem > max_batch: SPDY_ERR_ARG).  The member enters as uniform base offsets only: a
+ * member's fields are bit for bit those of a single model given the same inputs.  field returns the base of the (ix,il,nmem) stack
+ * of a per-member field; spdy_surface_model_members(m, name) is nmem for such a field, 1 for a field held once, SPDY_ERR_ARG for an
+ * unknown name, and with name NULL the object's nmem.
  * Not built: sea_coupling_flag > 0 (the reference stops for it, sea_model.f90:188-198: no ocean-model climatology, hfseacl = 0,
  * beta = 1) and the ablco2 trend (increase_co2 is a .false. parameter, shortwave_radiation.f90).                                */
 typedef struct spdy_surface_model spdy_surface_model;
@@ -756,6 +780,7 @@ typedef struct {                      /* host arrays, j = 0 southernmost        
 } spdy_surface_clim;
 enum { SPDY_SURFACE_LAND_COUPLING = 1, SPDY_SURFACE_ICE_COUPLING = 2, SPDY_SURFACE_SST_ANOMALY = 4, SPDY_SURFACE_DEFAULT = 7 };
 int spdy_surface_model_create(spdy_plan *plan, const spdy_surface_clim *host, double delt, int flags, spdy_surface_model **m);
+int spdy_ens_surface_model_create(spdy_plan *plan, int nmem, const spdy_surface_clim *host, double delt, int flags, spdy_surface_model **m);
 int spdy_surface_model_destroy(spdy_surface_model *m);
 int spdy_surface_model_table(const spdy_surface_model *m, const char *name, double *buf, int cap);
 int spdy_surface_model_set_date(spdy_surface_model *m, int imont1, double tmonth, double tyear);
@@ -765,6 +790,7 @@ int spdy_surface_model_couple_dev(spdy_surface_model *m, int day, const double *
 int spdy_surface_model_forcing_dev(spdy_surface_model *m, double *qcorh);
 int spdy_surface_model_boundary(spdy_surface_model *m, spdy_sfc_boundary *bnd, const double **albsfc);
 int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d_ptr);
+int spdy_surface_model_members(const spdy_surface_model *m, const char *name);
 
 /* ---- diagnostics: the run's guard (check_diagnostics, diagnostics.f90:16-75) ------------------------------------------------------
  * The one call of the reference's main loop (speedy.f90:27-54) that looks at the state after every step: per level k, from the
@@ -803,10 +829,23 @@ int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d
  *             further record holds up to ten f8.2 fields and nothing else.  Every record ends with a newline.  Returns the
  *             number of characters without the terminator (buf NULL: the size query); cap below that + 1 is SPDY_ERR_ARG.
  * A device-resident main loop: forcing, step, check_dev on time level 2, couple; status once per output interval.
+ * nmem members (spdy_ens_diagnostics_create; spdy_diagnostics_create is that call with nmem = 1; nmem < 1 SPDY_ERR_ARG): the same
+ * object type.  check_dev takes one time level of the ensemble, (mx,nx,kx,nmem) complex, and is ONE launch on a (kx, nmem) grid
+ * with the same thread-to-coefficient map and reduction tree: member e's numbers are bit for bit a single object's on its slice.
+ * History row s holds (3,kx,nmem): member e's (3,kx) block starts at ((s mod capacity)*nmem + e)*3*kx doubles.  The state is
+ * [nmem][kx] records, and the sticky first offence is per member: the scan for an earlier offence reads the member's own levels
+ * only, so a member that leaves the range freezes its own saved row while every other member's row and ring go on following the
+ * step.  The limits are shared.  Host calls by member, not callable inside a capture:
+ *   spdy_ens_diagnostics_status(d, member, ...) and spdy_ens_diagnostics_read(d, member, step, count, rows) are status and read for
+ *             one member (rows (count,3,kx)); a member outside [0, nmem) is SPDY_ERR_ARG.  The unsuffixed status and read on an
+ *             object with nmem > 1 are SPDY_ERR_ARG.
+ *   spdy_ens_diagnostics_stopped(d, bad_step)  one synchronisation and one download: bad_step[e] (nmem values) = -1 or member e's
+ *             first offending step; returns the number of members that tripped.
  * Checks: a NULL object, NULL spectra, rows or name, capacity < 1, a negative step: SPDY_ERR_ARG.                               */
 enum { SPDY_DIAG_REKE = 1, SPDY_DIAG_DEKE = 2, SPDY_DIAG_TEMP_LOW = 4, SPDY_DIAG_TEMP_HIGH = 8, SPDY_DIAG_NONFINITE = 16 };
 typedef struct spdy_diagnostics spdy_diagnostics;
 int spdy_diagnostics_create(spdy_plan *plan, int capacity, long long first_step, spdy_diagnostics **d);
+int spdy_ens_diagnostics_create(spdy_plan *plan, int nmem, int capacity, long long first_step, spdy_diagnostics **d);
 int spdy_diagnostics_destroy(spdy_diagnostics *d);
 int spdy_diagnostics_set_limits(spdy_diagnostics *d, const double *limits);
 int spdy_diagnostics_reset(spdy_diagnostics *d, long long next_step);
@@ -814,6 +853,10 @@ int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const dou
 int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask,
                             double *bad_row);
 int spdy_diagnostics_read(spdy_diagnostics *d, long long step, int count, double *rows);
+int spdy_ens_diagnostics_status(spdy_diagnostics *d, int member, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask,
+                                double *bad_row);
+int spdy_ens_diagnostics_read(spdy_diagnostics *d, int member, long long step, int count, double *rows);
+int spdy_ens_diagnostics_stopped(spdy_diagnostics *d, long long *bad_step);
 int spdy_diagnostics_field(spdy_diagnostics *d, const char *name, void **d_ptr);
 int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf, int cap);
 

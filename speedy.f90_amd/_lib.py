@@ -128,6 +128,8 @@ SIGNATURES = {
     "spdy_physics_workspace": [c_void_p],
     "spdy_physics_dev": [c_void_p, c_int] + [c_void_p] * 14,
     "spdy_surface_model_create": [c_void_p, c_void_p, c_double, c_int, ctypes.POINTER(c_void_p)],
+    "spdy_ens_surface_model_create": [c_void_p, c_int, c_void_p, c_double, c_int, ctypes.POINTER(c_void_p)],
+    "spdy_surface_model_members": [c_void_p, c_char_p],
     "spdy_surface_model_destroy": [c_void_p],
     "spdy_surface_model_table": [c_void_p, c_char_p, c_void_p, c_int],
     "spdy_surface_model_set_date": [c_void_p, c_int, c_double, c_double],
@@ -148,6 +150,11 @@ SIGNATURES = {
     "spdy_physics_sppt_workspace": [c_void_p],
     "spdy_physics_sppt_dev": [c_void_p, c_void_p, c_int] + [c_void_p] * 14,
     "spdy_diagnostics_create": [c_void_p, c_int, ctypes.c_longlong, ctypes.POINTER(c_void_p)],
+    "spdy_ens_diagnostics_create": [c_void_p, c_int, c_int, ctypes.c_longlong, ctypes.POINTER(c_void_p)],
+    "spdy_ens_diagnostics_status": [c_void_p, c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
+                                    ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p],
+    "spdy_ens_diagnostics_read": [c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p],
+    "spdy_ens_diagnostics_stopped": [c_void_p, ctypes.POINTER(ctypes.c_longlong)],
     "spdy_diagnostics_destroy": [c_void_p],
     "spdy_diagnostics_set_limits": [c_void_p, c_void_p],
     "spdy_diagnostics_reset": [c_void_p, ctypes.c_longlong],

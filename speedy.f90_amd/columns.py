@@ -145,10 +145,13 @@ class SurfaceModel:
 
     clim: dict of host arrays fmask, alb0 [il, ix]; stl12, snowd12, soilw12, sst12, sice12 [12, il, ix]; sstan3 [3, il, ix] (may
     be absent without SURFACE_SST_ANOMALY).  One step of a run: on the first step of a day forcing_dev(qcorh); the step; the
-    host's newdate and, when the day changed, set_date; couple_dev(day, hfluxn, shf, evap, ssrd)."""
+    host's newdate and, when the day changed, set_date; couple_dev(day, hfluxn, shf, evap, ssrd).
 
-    def __init__(self, sp, clim, delt, flags=SURFACE_DEFAULT):
-        self.sp, self.lib, self.flags = sp, sp.lib, int(flags)
+    nmem > 1: the models of an ensemble's members in one object, one launch per call.  What no kernel writes (the constants, the
+    climatologies, the date) is held once; every field couple_dev or forcing_dev writes, and fmask_l, is [nmem, il, ix]."""
+
+    def __init__(self, sp, clim, delt, flags=SURFACE_DEFAULT, nmem=1):
+        self.sp, self.lib, self.flags, self.nmem = sp, sp.lib, int(flags), int(nmem)
         host, c = {}, SurfaceClim()
         for n in _names("surface_clim"):
             if clim.get(n) is None:
@@ -161,7 +164,7 @@ class SurfaceModel:
         if sp.device >= 0:
             sp._sync_stream()
         h = ctypes.c_void_p()
-        check(self.lib.spdy_surface_model_create(sp.h, ctypes.byref(c), float(delt), self.flags, ctypes.byref(h)))
+        check(self.lib.spdy_ens_surface_model_create(sp.h, self.nmem, ctypes.byref(c), float(delt), self.flags, ctypes.byref(h)))
         self.h = h
         # the plan closes its models first; the references of models that are gone are dropped here
         sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
@@ -200,13 +203,15 @@ class SurfaceModel:
 
     def couple_dev(self, day, hfluxn=None, shf=None, evap=None, ssrd=None):
         """couple_sea_land(day) in one launch: hfluxn [2, il, ix], shf, evap [3, il, ix], ssrd [il, ix] device tensors as
-        physics_dev writes them (None allowed with day == 0)."""
+        physics_dev writes them (None allowed with day == 0); with nmem members [nmem, 2, il, ix] .. [nmem, il, ix], as
+        ens_physics_dev writes them."""
         self.sp._sync_stream()
         ptr = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
         check(self.lib.spdy_surface_model_couple_dev(self.h, int(day), ptr(hfluxn), ptr(shf), ptr(evap), ptr(ssrd)))
 
     def forcing_dev(self, qcorh):
-        """set_forcing(1) parts 2 and 4: snowc, alb_l, alb_s, albsfc, and qcorh [nx, mx] complex128 (device tensor) written."""
+        """set_forcing(1) parts 2 and 4: snowc, alb_l, alb_s, albsfc, and qcorh [nx, mx] complex128 (device tensor; with nmem
+        members [nmem, nx, mx], one transform call) written."""
         self.sp._sync_stream()
         check(self.lib.spdy_surface_model_forcing_dev(self.h, ctypes.c_void_p(qcorh.data_ptr())))
 
@@ -216,15 +221,22 @@ class SurfaceModel:
         check(self.lib.spdy_surface_model_boundary(self.h, ctypes.byref(b), ctypes.byref(alb)))
         return b, alb
 
+    def members(self, name=None):
+        """How many members hold their own copy of a field: nmem for what a kernel writes and for fmask_l, 1 for a field held
+        once; with no name the object's nmem."""
+        return check(self.lib.spdy_surface_model_members(self.h, None if name is None else name.encode()))
+
     def field(self, name):
-        """A field of the model by the reference's name (SURFACE_FIELDS, SURFACE_TABLES, alb0): a DeviceField [il, ix] in the
-        model's own device memory."""
+        """A field of the model by the reference's name (SURFACE_FIELDS, SURFACE_TABLES, alb0): a DeviceField in the model's own
+        device memory, [il, ix], or [nmem, il, ix] where a model of nmem > 1 members holds the field per member."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_surface_model_field(self.h, name.encode(), ctypes.byref(p)))
-        return DeviceField(self.sp, p.value, self.sp.grid_shape)
+        lead = (self.nmem,) if self.nmem > 1 and self.members(name) > 1 else ()
+        return DeviceField(self.sp, p.value, lead + self.sp.grid_shape)
 
     def boundary(self):
-        """(bnd, albsfc) for Spectral.physics_dev: DeviceFields of the model's own arrays (bnd["fmask"] = fmask_l)."""
+        """(bnd, albsfc) for Spectral.physics_dev: DeviceFields of the model's own arrays (bnd["fmask"] = fmask_l); with nmem
+        members the [nmem, il, ix] views Ensemble.step's physics takes."""
         names = {"fmask": "fmask_l", "sst": "sst_am", "stl": "stl_am", "soilw": "soilw_am", "snowc": "snowc", "alb_l": "alb_l",
                  "alb_s": "alb_s"}
         return {k: self.field(v) for k, v in names.items()}, self.field("albsfc")
@@ -322,14 +334,17 @@ class Diagnostics:
     in a ring of `capacity` rows, the step counter and the sticky first offence, all in device memory.
 
     One step of a device-resident run: forcing, the step, check_dev on time level 2, couple; status() or raise_if_stopped() once
-    per output interval.  check_dev is one launch and capturable: each replay records the next step."""
+    per output interval.  check_dev is one launch and capturable: each replay records the next step.
 
-    def __init__(self, sp, capacity=64, first_step=0):
-        self.sp, self.lib, self.capacity = sp, sp.lib, int(capacity)
+    nmem > 1: the guard of an ensemble's members in one object and one launch.  Every member has its own rows, counter and sticky
+    first offence; the limits are shared.  status and read then take the member."""
+
+    def __init__(self, sp, capacity=64, first_step=0, nmem=1):
+        self.sp, self.lib, self.capacity, self.nmem = sp, sp.lib, int(capacity), int(nmem)
         if sp.device >= 0:
             sp._sync_stream()
         h = ctypes.c_void_p()
-        check(self.lib.spdy_diagnostics_create(sp.h, self.capacity, int(first_step), ctypes.byref(h)))
+        check(self.lib.spdy_ens_diagnostics_create(sp.h, self.nmem, self.capacity, int(first_step), ctypes.byref(h)))
         self.h = h
         # the plan closes its objects first (as its surface models)
         sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
@@ -360,35 +375,46 @@ class Diagnostics:
         check(self.lib.spdy_diagnostics_reset(self.h, int(next_step)))
 
     def check_dev(self, vor, div, t):
-        """One launch on [kx, nx, mx] complex128 device tensors (time level 2 of the prognostics): the step's row, the range test,
-        the counter."""
+        """One launch on [kx, nx, mx] complex128 device tensors (time level 2 of the prognostics; with nmem members [nmem, kx,
+        nx, mx], e.g. ens.vor[1]): the step's row, the range test, the counter."""
         self.sp._sync_stream()
         check(self.lib.spdy_diagnostics_check_dev(self.h, *[ctypes.c_void_p(x.data_ptr()) for x in (vor, div, t)]))
 
-    def status(self):
-        """{"next_step", "bad_step" (-1: nothing tripped), "bad_level", "bad_mask", "bad_row" ([3, kx] or None)}; synchronises
-        the plan's stream."""
+    def status(self, member=0):
+        """{"next_step", "bad_step" (-1: nothing tripped), "bad_level", "bad_mask", "bad_row" ([3, kx] or None)} of one member;
+        synchronises the plan's stream."""
         self.sp._sync_stream()
         nxt, bad, lev, mask = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int(), ctypes.c_int()
         row = np.zeros((3, self.sp.kx))
-        check(self.lib.spdy_diagnostics_status(self.h, ctypes.byref(nxt), ctypes.byref(bad), ctypes.byref(lev), ctypes.byref(mask), _p(row)))
+        check(self.lib.spdy_ens_diagnostics_status(self.h, int(member), ctypes.byref(nxt), ctypes.byref(bad), ctypes.byref(lev),
+                                                   ctypes.byref(mask), _p(row)))
         return {"next_step": nxt.value, "bad_step": bad.value, "bad_level": lev.value, "bad_mask": mask.value,
                 "bad_row": row if bad.value >= 0 else None}
 
-    def read(self, step, count=1):
-        """The rows of steps step .. step + count - 1 as [count, 3, kx] (reke | deke | temp); synchronises the plan's stream."""
+    def read(self, step, count=1, member=0):
+        """The rows of steps step .. step + count - 1 of one member as [count, 3, kx] (reke | deke | temp); synchronises the
+        plan's stream."""
         self.sp._sync_stream()
         rows = np.zeros((int(count), 3, self.sp.kx))
-        check(self.lib.spdy_diagnostics_read(self.h, int(step), int(count), _p(rows)))
+        check(self.lib.spdy_ens_diagnostics_read(self.h, int(member), int(step), int(count), _p(rows)))
         return rows
 
+    def stopped(self):
+        """The members' first offending steps, -1 where a member has not tripped: one synchronisation, one download."""
+        self.sp._sync_stream()
+        bad = (ctypes.c_longlong * self.nmem)()
+        check(self.lib.spdy_ens_diagnostics_stopped(self.h, bad))
+        return list(bad)
+
     def field(self, name):
-        """"history" as a DeviceField [capacity, 3, kx], "limits" [4]; "state" as the device address (per-level records)."""
+        """"history" as a DeviceField [capacity, 3, kx] ([capacity, nmem, 3, kx] with nmem > 1 members), "limits" [4]; "state" as
+        the device address (per-level records)."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_diagnostics_field(self.h, name.encode(), ctypes.byref(p)))
         if name == "state":
             return p.value
-        return DeviceField(self.sp, p.value, (self.capacity, 3, self.sp.kx) if name == "history" else (4,))
+        lead = (self.capacity,) + ((self.nmem,) if self.nmem > 1 else ())
+        return DeviceField(self.sp, p.value, lead + (3, self.sp.kx) if name == "history" else (4,))
 
     def format(self, step, row):
         """The reference's three printed lines (diagnostics.f90:72-74) for one [3, kx] row."""
@@ -397,11 +423,20 @@ class Diagnostics:
     def raise_if_stopped(self):
         """Raises DiagnosticsStop where the reference would stop: the status holds one of its four comparisons.  The message is
         the reference's three lines and its stop message.  Returns the status otherwise (a non-finite value alone does not stop
-        the reference and is left to the caller: status["bad_mask"] & DIAG_NONFINITE)."""
-        st = self.status()
-        if st["bad_mask"] & DIAG_REFERENCE:
-            raise DiagnosticsStop(self.format(st["bad_step"], st["bad_row"]) + "Model variables out of accepted range", st)
-        return st
+        the reference and is left to the caller: status["bad_mask"] & DIAG_NONFINITE).  With nmem > 1 members: the first member
+        the reference would have stopped is named in front of its three lines, and the list of every member's status is
+        returned otherwise."""
+        if self.nmem == 1:
+            st = self.status()
+            if st["bad_mask"] & DIAG_REFERENCE:
+                raise DiagnosticsStop(self.format(st["bad_step"], st["bad_row"]) + "Model variables out of accepted range", st)
+            return st
+        sts = [self.status(e) if b >= 0 else None for e, b in enumerate(self.stopped())]
+        for e, st in enumerate(sts):
+            if st is not None and st["bad_mask"] & DIAG_REFERENCE:
+                raise DiagnosticsStop(" member %d\n" % e + self.format(st["bad_step"], st["bad_row"])
+                                      + "Model variables out of accepted range", dict(st, member=e))
+        return [self.status(e) if st is None else st for e, st in enumerate(sts)]
 
 
 def format_diagnostics(lib, step, row):

@@ -923,9 +923,15 @@ int spdy_plan_set_option(spdy_plan *p, const char *name, int value)
 {
     NEED_PLAN(p);
     if (!name) return fail(SPDY_ERR_ARG, "null option name");
-    if (p->capturing) return fail(SPDY_ERR_STATE, "launch options cannot change while a graph capture is open");
     spdy::LaunchOpts &lo = p->dev.lo;
     const std::string n(name);
+    // an argument layout, not a launch form: each call reads it as it is enqueued, so it may change between the calls of a capture
+    if (n == "ens_member_qcorh") {
+        if (value != 0 && value != 1) return fail(SPDY_ERR_ARG, "ens_member_qcorh must be 0 or 1");
+        p->ens_member_qcorh = value != 0;
+        return SPDY_OK;
+    }
+    if (p->capturing) return fail(SPDY_ERR_STATE, "launch options cannot change while a graph capture is open");
     if (n == "t30_part") lo.t30_nopart = !value;
     else if (n == "t30_split") lo.t30_nosplit = !value;
     else if (n == "t63_split") lo.t63_nosplit = !value;

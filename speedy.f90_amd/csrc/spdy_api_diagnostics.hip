@@ -18,7 +18,8 @@ namespace {
 
 constexpr int MAX_CAPACITY = 1 << 20;
 
-size_t row_doubles(const spdy_diagnostics *d) { return (size_t)3 * d->plan->tab.kx; }
+size_t row_doubles(const spdy_diagnostics *d) { return (size_t)3 * d->plan->tab.kx; }           // one member's (3, kx) block
+size_t levels(const spdy_diagnostics *d) { return (size_t)d->nmem * d->plan->tab.kx; }            // DiagLevel records
 
 // the state of a run that starts at next_step and an empty ring, stream-ordered
 int restart(spdy_diagnostics *d, long long next_step)
@@ -26,8 +27,8 @@ int restart(spdy_diagnostics *d, long long next_step)
     spdy_plan *p = d->plan;
     spdy::DiagLevel l{};
     l.next_step = next_step; l.bad_step = -1; l.row_step = -1;
-    const std::vector<spdy::DiagLevel> h((size_t)p->tab.kx, l);
-    HIP_TRY(hipMemsetAsync(d->d_history, 0, (size_t)d->capacity * row_doubles(d) * sizeof(double), p->stream));
+    const std::vector<spdy::DiagLevel> h(levels(d), l);
+    HIP_TRY(hipMemsetAsync(d->d_history, 0, (size_t)d->capacity * d->nmem * row_doubles(d) * sizeof(double), p->stream));
     HIP_TRY(hipMemcpyAsync(d->d_state, h.data(), h.size() * sizeof(l), hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     d->start_step = next_step;
@@ -46,11 +47,32 @@ int upload_limits(spdy_diagnostics *d, const double *limits)
 int download_state(spdy_diagnostics *d, std::vector<spdy::DiagLevel> &h)
 {
     spdy_plan *p = d->plan;
-    h.resize((size_t)p->tab.kx);
+    h.resize(levels(d));
     HIP_TRY(hipMemcpyAsync(h.data(), d->d_state, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     for (const auto &l : h)
         if (l.next_step != h[0].next_step) return fail(SPDY_ERR_STATE, "the levels' step counters disagree (%lld, %lld)", h[0].next_step, l.next_step);
+    return SPDY_OK;
+}
+
+// the first offending step of the member whose levels are h[0 .. kx) (-1: none)
+long long first_offence(const spdy::DiagLevel *h, int kx)
+{
+    long long first = -1;
+    for (int k = 0; k < kx; ++k)
+        if (h[k].bad_step >= 0 && (first < 0 || h[k].bad_step < first)) first = h[k].bad_step;
+    return first;
+}
+
+int need_member(const spdy_diagnostics *d, int member, const char *what)
+{
+    if (member < 0 || member >= d->nmem) return fail(SPDY_ERR_ARG, "%s: member %d is not in 0 .. %d", what, member, d->nmem - 1);
+    return SPDY_OK;
+}
+
+int need_single(const spdy_diagnostics *d, const char *what, const char *form)
+{
+    if (d->nmem > 1) return fail(SPDY_ERR_ARG, "%s: the object checks %d members, use %s with a member", what, d->nmem, form);
     return SPDY_OK;
 }
 
@@ -69,19 +91,25 @@ extern "C" {
 
 int spdy_diagnostics_create(spdy_plan *p, int capacity, long long first_step, spdy_diagnostics **out)
 {
+    return spdy_ens_diagnostics_create(p, 1, capacity, first_step, out);
+}
+
+int spdy_ens_diagnostics_create(spdy_plan *p, int nmem, int capacity, long long first_step, spdy_diagnostics **out)
+{
     NEED_PLAN(p);
+    if (nmem < 1 || nmem > 65535) return fail(SPDY_ERR_ARG, "diagnostics_create: nmem=%d is not in 1 .. 65535", nmem);
     if (!out) return fail(SPDY_ERR_ARG, "null result pointer");
     if (capacity < 1 || capacity > MAX_CAPACITY) return fail(SPDY_ERR_ARG, "diagnostics_create: capacity %d is not in 1 .. %d", capacity, MAX_CAPACITY);
     if (first_step < 0) return fail(SPDY_ERR_ARG, "diagnostics_create: first_step %lld is negative", first_step);
     NOT_CAPTURING(p, "spdy_diagnostics_create (allocation + upload)");
     spdy_diagnostics *d = new spdy_diagnostics;
-    d->plan = p; d->capacity = capacity; d->start_step = first_step;
+    d->plan = p; d->capacity = capacity; d->nmem = nmem; d->start_step = first_step;
     *out = d;
     if (p->device < 0) return SPDY_OK;
     auto cleanup = [&](int rc) { spdy_diagnostics_destroy(d); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
-    const size_t nhist = (size_t)capacity * row_doubles(d);
-    const size_t bytes = (nhist + 4) * sizeof(double) + (size_t)p->tab.kx * sizeof(spdy::DiagLevel);
+    const size_t nhist = (size_t)capacity * nmem * row_doubles(d);
+    const size_t bytes = (nhist + 4) * sizeof(double) + levels(d) * sizeof(spdy::DiagLevel);
     if (hipMalloc(reinterpret_cast<void **>(&d->d_history), bytes) != hipSuccess)
         return cleanup(fail(SPDY_ERR_HIP, "diagnostics_create: hipMalloc of %zu bytes failed", bytes));
     d->d_limits = d->d_history + nhist;
@@ -131,7 +159,7 @@ int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const dou
     spdy::DiagArgs a{};
     a.vor = vor; a.div = div; a.t = t;
     a.elm2 = p->dev.elm2; a.limits = d->d_limits; a.history = d->d_history; a.state = d->d_state;
-    a.nspec = p->tab.mx * p->tab.nx; a.mx = p->tab.mx; a.kx = p->tab.kx; a.capacity = d->capacity;
+    a.nspec = p->tab.mx * p->tab.nx; a.mx = p->tab.mx; a.kx = p->tab.kx; a.capacity = d->capacity; a.nmem = d->nmem;
     KERNEL(spdy::launch_diagnostics(a, p->stream));
     return SPDY_OK;
 }
@@ -139,19 +167,27 @@ int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const dou
 int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask, double *bad_row)
 {
     NEED_DIAG(d);
+    RC(need_single(d, "diagnostics_status", "spdy_ens_diagnostics_status"));
+    return spdy_ens_diagnostics_status(d, 0, next_step, bad_step, bad_level, bad_mask, bad_row);
+}
+
+int spdy_ens_diagnostics_status(spdy_diagnostics *d, int member, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask,
+                                double *bad_row)
+{
+    NEED_DIAG(d);
+    RC(need_member(d, member, "diagnostics_status"));
     spdy_plan *p = d->plan;
     NOT_CAPTURING(p, "spdy_diagnostics_status (download)");
     NEED_DEVICE(p);
-    std::vector<spdy::DiagLevel> h;
-    RC(download_state(d, h));
+    std::vector<spdy::DiagLevel> all;
+    RC(download_state(d, all));
     const int kx = p->tab.kx;
-    long long first = -1;
-    for (const auto &l : h)
-        if (l.bad_step >= 0 && (first < 0 || l.bad_step < first)) first = l.bad_step;
+    const spdy::DiagLevel *const h = all.data() + (size_t)member * kx;               // the member's levels
+    const long long first = first_offence(h, kx);
     int level = -1, mask = 0;
     for (int k = 0; k < kx && first >= 0; ++k) {
         if (h[k].bad_step == first) { mask |= h[k].bad_mask; if (level < 0) level = k; }
-        // every level stopped refreshing its saved row at the first offence of any level
+        // every level of the member stopped refreshing its saved row at the first offence of any of them
         if (h[k].row_step != first)
             return fail(SPDY_ERR_STATE, "level %d saved the row of step %lld, the first offence is at step %lld", k, h[k].row_step, first);
     }
@@ -168,6 +204,14 @@ int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long
 int spdy_diagnostics_read(spdy_diagnostics *d, long long step, int count, double *rows)
 {
     NEED_DIAG(d);
+    RC(need_single(d, "diagnostics_read", "spdy_ens_diagnostics_read"));
+    return spdy_ens_diagnostics_read(d, 0, step, count, rows);
+}
+
+int spdy_ens_diagnostics_read(spdy_diagnostics *d, int member, long long step, int count, double *rows)
+{
+    NEED_DIAG(d);
+    RC(need_member(d, member, "diagnostics_read"));
     if (!rows) return fail(SPDY_ERR_ARG, "null result pointer");
     if (count < 1) return fail(SPDY_ERR_ARG, "diagnostics_read: count %d", count);
     spdy_plan *p = d->plan;
@@ -180,10 +224,27 @@ int spdy_diagnostics_read(spdy_diagnostics *d, long long step, int count, double
         return fail(SPDY_ERR_ARG, "diagnostics_read: steps %lld .. %lld asked, the ring holds %lld .. %lld", step, step + count - 1, oldest, next - 1);
     const size_t nrow = row_doubles(d);
     for (int i = 0; i < count; ++i)
-        HIP_TRY(hipMemcpyAsync(rows + (size_t)i * nrow, d->d_history + (size_t)((step + i) % d->capacity) * nrow, nrow * sizeof(double),
+        HIP_TRY(hipMemcpyAsync(rows + (size_t)i * nrow, d->d_history + ((size_t)((step + i) % d->capacity) * d->nmem + member) * nrow, nrow * sizeof(double),
                                hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return SPDY_OK;
+}
+
+int spdy_ens_diagnostics_stopped(spdy_diagnostics *d, long long *bad_step)
+{
+    NEED_DIAG(d);
+    if (!bad_step) return fail(SPDY_ERR_ARG, "null result pointer");
+    spdy_plan *p = d->plan;
+    NOT_CAPTURING(p, "spdy_ens_diagnostics_stopped (download)");
+    NEED_DEVICE(p);
+    std::vector<spdy::DiagLevel> h;
+    RC(download_state(d, h));                                                   // one synchronisation, one download
+    int stopped = 0;
+    for (int e = 0; e < d->nmem; ++e) {
+        bad_step[e] = first_offence(h.data() + (size_t)e * p->tab.kx, p->tab.kx);
+        stopped += bad_step[e] >= 0;
+    }
+    return stopped;
 }
 
 int spdy_diagnostics_field(spdy_diagnostics *d, const char *name, void **d_ptr)

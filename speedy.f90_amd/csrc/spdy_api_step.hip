@@ -29,13 +29,15 @@ int ens_args(const spdy_plan *p, int nmem, const char *what, bool need_implicit,
     return SPDY_OK;
 }
 
-// the one-launch spectral step of nmem members (kx <= 16), arguments checked; raw_u / raw_v: SpecStep
+// the one-launch spectral step of nmem members (kx <= 16), arguments checked; raw_u / raw_v: SpecStep.  The plan option
+// "ens_member_qcorh" is read here, when the call is enqueued; one member's qcorh is the same field either way.
 int spectral_step_launch(spdy_plan *p, int nmem, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
                          double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1,
                          double dt, double eps, double wil, double *phi, const double *raw_u, const double *raw_v)
 {
     const spdy::SpecStep a{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
-                           p->tab.ix == 4 * p->tab.iy, raw_u, raw_v, spdy::LevelShard{}, nullptr, 0, 0, nmem};
+                           p->tab.ix == 4 * p->tab.iy, raw_u, raw_v, spdy::LevelShard{}, nullptr, 0, 0, nmem,
+                           nmem > 1 && p->ens_member_qcorh};
     KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
     return SPDY_OK;
 }

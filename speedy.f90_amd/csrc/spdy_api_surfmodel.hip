@@ -10,9 +10,10 @@ using namespace spdy_detail;
 struct spdy_surface_model {
     spdy_plan *plan = nullptr;
     int flags = 0;
+    int nmem = 1;                     // members: every field a kernel writes, and fmask_l, is held (nmem, il, ix)
     size_t ncol = 0;
     spdy::SurfaceTables tab;
-    double *d_f = nullptr;            // SM_TOTAL fields of ncol doubles (csrc/spdy_kernels.hpp: SurfField)
+    double *d_f = nullptr;            // surf_total(nmem) fields of ncol doubles (csrc/spdy_kernels.hpp: SurfField, surf_slot)
     spdy::SurfDate *d_date = nullptr;
     bool date_ready = false;          // spdy_surface_model_set_date has run
     bool started = false;             // spdy_surface_model_couple_dev(day = 0) has been issued
@@ -24,7 +25,8 @@ namespace {
         if (!(m)) return fail(SPDY_ERR_ARG, "null surface model");      \
     } while (0)
 
-double *field(const spdy_surface_model *m, int n) { return m->d_f + (size_t)n * m->ncol; }
+// member 0 of a field held per member (the base of its (nmem, il, ix) stack), the field itself where it is held once
+double *field(const spdy_surface_model *m, int n) { return m->d_f + (size_t)spdy::surf_slot(n, m->nmem, 0) * m->ncol; }
 
 // stream-ordered upload as spdy_radiation_set_date's: the synchronisation keeps the caller's array alive until the copy is done
 int upload(spdy_surface_model *m, void *dst, const void *src, size_t bytes)
@@ -52,7 +54,13 @@ extern "C" {
 
 int spdy_surface_model_create(spdy_plan *p, const spdy_surface_clim *host, double delt, int flags, spdy_surface_model **out)
 {
+    return spdy_ens_surface_model_create(p, 1, host, delt, flags, out);
+}
+
+int spdy_ens_surface_model_create(spdy_plan *p, int nmem, const spdy_surface_clim *host, double delt, int flags, spdy_surface_model **out)
+{
     NEED_PLAN(p);
+    if (nmem < 1 || nmem > 65535) return fail(SPDY_ERR_ARG, "surface_model_create: nmem=%d is not in 1 .. 65535", nmem);
     if (!host || !out) return fail(SPDY_ERR_ARG, "null climatology or result pointer");
     if (flags & ~SPDY_SURFACE_DEFAULT) return fail(SPDY_ERR_ARG, "surface_model_create: unknown flag in %d", flags);
     const bool ssta = flags & SPDY_SURFACE_SST_ANOMALY;
@@ -61,22 +69,25 @@ int spdy_surface_model_create(spdy_plan *p, const spdy_surface_clim *host, doubl
         return fail(SPDY_ERR_ARG, "surface_model_create: null field");
     NOT_CAPTURING(p, "spdy_surface_model_create (host table build + upload)");
     spdy_surface_model *m = new spdy_surface_model;
-    m->plan = p; m->flags = flags; m->ncol = grid_elems(p);
+    m->plan = p; m->flags = flags; m->nmem = nmem; m->ncol = grid_elems(p);
     const std::string err = m->tab.build(p->tab, host->fmask, host->alb0, delt);
     if (!err.empty()) { delete m; return fail(SPDY_ERR_ARG, "surface_model_create: %s", err.c_str()); }
     *out = m;
     if (p->device < 0) return SPDY_OK;
     auto cleanup = [&](int rc) { spdy_surface_model_destroy(m); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
-    const size_t n = m->ncol, bytes = (size_t)spdy::SM_TOTAL * n * sizeof(double);
+    const size_t n = m->ncol, total = (size_t)spdy::surf_total(nmem) * n, bytes = total * sizeof(double);
     if (hipMalloc(reinterpret_cast<void **>(&m->d_f), bytes) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&m->d_date), sizeof(spdy::SurfDate)) != hipSuccess)
         return cleanup(fail(SPDY_ERR_HIP, "surface_model_create: hipMalloc of %zu bytes failed", bytes));
     // one staging array: the constants, zeros for the model's own fields, the climatologies
-    std::vector<double> h((size_t)spdy::SM_TOTAL * n, 0.0);
-    auto put = [&](int at, const double *src, int nf) { std::memcpy(h.data() + (size_t)at * n, src, sizeof(double) * n * nf); };
+    std::vector<double> h(total, 0.0);
+    auto put = [&](int at, const double *src, int nf, int e = 0) {
+        std::memcpy(h.data() + (size_t)spdy::surf_slot(at, nmem, e) * n, src, sizeof(double) * n * nf);
+    };
     const spdy::SurfaceTables &t = m->tab;
-    put(spdy::SM_FMASK_L, t.fmask_l.data(), 1); put(spdy::SM_FMASK_S, t.fmask_s.data(), 1); put(spdy::SM_ALB0, host->alb0, 1);
+    for (int e = 0; e < nmem; ++e) put(spdy::SM_FMASK_L, t.fmask_l.data(), 1, e);
+    put(spdy::SM_FMASK_S, t.fmask_s.data(), 1); put(spdy::SM_ALB0, host->alb0, 1);
     put(spdy::SM_RHCAPL, t.rhcapl.data(), 1); put(spdy::SM_CDLAND, t.cdland.data(), 1); put(spdy::SM_RHCAPS, t.rhcaps.data(), 1);
     put(spdy::SM_RHCAPI, t.rhcapi.data(), 1); put(spdy::SM_CDSEA, t.cdsea.data(), 1); put(spdy::SM_CDICE, t.cdice.data(), 1);
     put(spdy::SM_STL12, host->stl12, 12); put(spdy::SM_SNOWD12, host->snowd12, 12); put(spdy::SM_SOILW12, host->soilw12, 12);
@@ -152,7 +163,7 @@ int spdy_surface_model_couple_dev(spdy_surface_model *m, int day, const double *
     // the initialisation marks the model as started: it must have run, not only been recorded
     if (day == 0) NOT_CAPTURING(p, "spdy_surface_model_couple_dev(day = 0)");
     spdy::SurfCols a{};
-    a.ncol = (int)m->ncol; a.day = day; a.flags = m->flags; a.f = m->d_f; a.date = m->d_date;
+    a.ncol = (int)m->ncol; a.day = day; a.flags = m->flags; a.f = m->d_f; a.date = m->d_date; a.nmem = m->nmem;
     a.hfluxn = hfluxn; a.shf = shf; a.evap = evap; a.ssrd = ssrd;
     KERNEL(spdy::launch_surface_couple(a, p->stream));
     if (day == 0) m->started = true;
@@ -164,17 +175,19 @@ int spdy_surface_model_forcing_dev(spdy_surface_model *m, double *qcorh)
     NEED_MODEL(m);
     spdy_plan *p = m->plan;
     if (!qcorh) return fail(SPDY_ERR_ARG, "null device pointer");
+    if (m->nmem > p->max_batch) return fail(SPDY_ERR_ARG, "surface_model_forcing: nmem=%d exceeds the plan's max_batch=%d", m->nmem, p->max_batch);
     NEED_DEVICE(p);
     if (!m->date_ready) return fail(SPDY_ERR_STATE, "the surface model needs a date (spdy_surface_model_set_date)");
     if (!m->started) return fail(SPDY_ERR_STATE, "the surface model needs couple(day = 0) first");
     if (!p->tab.orog_ready) return fail(SPDY_ERR_STATE, "the forcing needs the orography (spdy_surface_set_orography)");
     spdy::SurfForcingCols a{};
-    a.ncol = (int)m->ncol; a.f = m->d_f; a.phis0 = p->d_orog;
+    a.ncol = (int)m->ncol; a.f = m->d_f; a.phis0 = p->d_orog; a.nmem = m->nmem;
     // forcing.f90:112 gamlat = gamma/(1000. * grav), :86 pexp = 1./(rgas * gamlat)
     a.gamlat = static_cast<double>(6.0f) / (static_cast<double>(1000.0f) * p->tab.grav);
     a.pexp = 1. / (p->tab.rgas * a.gamlat);
     KERNEL(spdy::launch_surface_forcing(a, p->stream));
-    return spdy_grid_to_spec_dev(p, 1, field(m, spdy::SM_CORH), qcorh);
+    // corh of all members is one stack of nmem grids: ONE transform call into the caller's (mx, nx, nmem)
+    return spdy_grid_to_spec_dev(p, m->nmem, field(m, spdy::SM_CORH), qcorh);
 }
 
 int spdy_surface_model_boundary(spdy_surface_model *m, spdy_sfc_boundary *bnd, const double **albsfc)
@@ -198,6 +211,15 @@ int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d
     NEED_DEVICE(m->plan);
     *d_ptr = field(m, i);
     return SPDY_OK;
+}
+
+int spdy_surface_model_members(const spdy_surface_model *m, const char *name)
+{
+    NEED_MODEL(m);
+    if (!name) return m->nmem;
+    const int i = field_index(name);
+    if (i < 0) return fail(SPDY_ERR_ARG, "unknown surface-model field '%s'", name);
+    return spdy::surf_per_member(i) ? m->nmem : 1;
 }
 
 }  // extern "C"

@@ -13,6 +13,10 @@
 // 0 alone with ordinary vector stores.  The one thing a workgroup reads of the others is their bad_step, to stop refreshing its
 // saved row once any level has tripped at an EARLIER step: what this launch writes there is the current step s, which that test
 // (bad_step < s) ignores whether it is seen or not, so the read does not depend on the order the workgroups run in.
+//
+// nmem members: a (kx, nmem) grid.  Workgroup (k, e) is the single object's workgroup k on member e's slice of the spectra, on
+// state[e][.] and on block e of the history row: the same thread-to-coefficient map and reduction tree, so the same bits.  The
+// "earlier offence" scan reads the member's own kx levels only: a member that trips freezes its own saved row and no other's.
 #include "spdy_kernels.hpp"
 
 namespace spdy {
@@ -32,20 +36,21 @@ __device__ inline double wave_sum(double x)
 __global__ __launch_bounds__(DIAG_BLOCK) void diagnostics_kernel(const DiagArgs a)
 {
     __shared__ double part[2][DIAG_WAVES];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    DiagLevel *const me = a.state + k;
+    const int k = blockIdx.x, mem = blockIdx.y, tid = threadIdx.x;
+    DiagLevel *const mine = a.state + (size_t)mem * a.kx, *const me = mine + k;   // the member's levels, this level
+    const size_t ms = 2 * (size_t)mem * a.kx * a.nspec;                          // the member's (mx, nx, kx) slice (doubles)
     const long long s = me->next_step;                // read by every thread before the barrier, written by thread 0 after it
     int earlier = 0;                                  // some level's first offence lies before this step: the saved row is final
     for (int j = tid; j < a.kx; j += DIAG_BLOCK) {
-        const long long b = a.state[j].bad_step;
+        const long long b = mine[j].bad_step;
         earlier |= b >= 0 && b < s;
     }
     double t0 = 0.0, lim[4] = {0.0, 0.0, 0.0, 0.0};
     if (tid == 0) {
-        t0 = a.t[2 * (size_t)k * a.nspec];
+        t0 = a.t[ms + 2 * (size_t)k * a.nspec];
         for (int i = 0; i < 4; ++i) lim[i] = a.limits[i];
     }
-    const double *const v = a.vor + 2 * (size_t)k * a.nspec, *const d = a.div + 2 * (size_t)k * a.nspec;
+    const double *const v = a.vor + ms + 2 * (size_t)k * a.nspec, *const d = a.div + ms + 2 * (size_t)k * a.nspec;
     double sv = 0.0, sd = 0.0;
     for (int i = tid; i < a.nspec; i += DIAG_BLOCK) {
         const double e = a.elm2[i], vr = v[2 * i], vi = v[2 * i + 1], dr = d[2 * i], di = d[2 * i + 1];
@@ -64,7 +69,7 @@ __global__ __launch_bounds__(DIAG_BLOCK) void diagnostics_kernel(const DiagArgs 
     int mask = (reke > lim[0] ? DIAG_REKE : 0) | (deke > lim[1] ? DIAG_DEKE : 0) | (temp < lim[2] ? DIAG_TEMP_LOW : 0) |
                (temp > lim[3] ? DIAG_TEMP_HIGH : 0);
     if (!(isfinite(reke) && isfinite(deke) && isfinite(temp))) mask |= DIAG_NONFINITE;
-    double *const row = a.history + (size_t)(s % a.capacity) * 3 * a.kx;
+    double *const row = a.history + ((size_t)(s % a.capacity) * a.nmem + mem) * 3 * a.kx;
     row[k] = reke; row[a.kx + k] = deke; row[2 * a.kx + k] = temp;
     if (!frozen) {                                    // until a level trips every level's saved row follows the step
         me->row_step = s;
@@ -79,9 +84,9 @@ __global__ __launch_bounds__(DIAG_BLOCK) void diagnostics_kernel(const DiagArgs 
 hipError_t launch_diagnostics(const DiagArgs &a, hipStream_t s)
 {
     if (a.kx <= 0 || a.mx <= 0 || a.nspec <= 0 || a.nspec % a.mx || a.capacity < 1 || !a.vor || !a.div || !a.t || !a.elm2 ||
-        !a.limits || !a.history || !a.state)
+        !a.limits || !a.history || !a.state || a.nmem < 1 || a.nmem > 65535)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(diagnostics_kernel, dim3((unsigned)a.kx), dim3(DIAG_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(diagnostics_kernel, dim3((unsigned)a.kx, (unsigned)a.nmem), dim3(DIAG_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -269,6 +269,8 @@ struct SpecStep {
     // pvor / pdiv / pspec / raw_u / raw_v group-major [3][nmem][kx] (+ the nmem level-free fields behind pspec's groups); phis,
     // tcorh, qcorh are shared.  nmem = 1 is the layout above.
     int nmem;
+    // non-zero: qcorh is (mx, nx, nmem), member e's own field (the plan option "ens_member_qcorh"); tcorh stays shared
+    int member_qcorh;
 };
 hipError_t launch_spectral_step(const DevPlan &p, const SpecStep &a, hipStream_t s);
 // output path (input_output.f90:184-206)
@@ -405,7 +407,10 @@ hipError_t launch_column_chain_sppt(const ChainSpptCols &a, hipStream_t s);
 // The slab land, sea and ice models and the daily forcing (csrc/spdy_surfmodel.hip): couple_sea_land (coupler.f90:30-38) and
 // set_forcing parts 2 and 4 (forcing.f90:55-62, :84-99), one thread per column of ONE state.  A surface model keeps its fields in
 // one device array of SM_TOTAL fields of ncol doubles: field n at f + n * ncol, month mo (0-based) of a climatology c at
-// f + (c + mo) * ncol.
+// f + (c + mo) * ncol.  A model of nmem > 1 members (blockIdx.y of both kernels) holds what no kernel writes once and every field
+// a kernel writes, SM_STLCL_OB .. SM_CORH, as (nmem, il, ix): member e of field n is ncol doubles after member e - 1 of field n.
+// fmask_l is (nmem, il, ix) too, replicated (the physics takes every boundary field per state).  surf_slot gives the place of
+// (field, member) in units of ncol doubles; with nmem = 1 it is n, the layout above.
 enum SurfField {
     // constants of land_model_init / sea_model_init
     SM_FMASK_L, SM_FMASK_S, SM_ALB0, SM_RHCAPL, SM_CDLAND, SM_RHCAPS, SM_RHCAPI, SM_CDSEA, SM_CDICE,
@@ -419,6 +424,17 @@ enum SurfField {
     SM_STL12 = SM_NFIELDS, SM_SNOWD12 = SM_STL12 + 12, SM_SOILW12 = SM_SNOWD12 + 12, SM_SST12 = SM_SOILW12 + 12,
     SM_SICE12 = SM_SST12 + 12, SM_SSTAN3 = SM_SICE12 + 12, SM_TOTAL = SM_SSTAN3 + 3
 };
+constexpr int SM_NMEMBER = 1 + SM_NFIELDS - SM_STLCL_OB;   // fields held per member: fmask_l and SM_STLCL_OB .. SM_CORH
+__host__ __device__ inline bool surf_per_member(int n) { return n == SM_FMASK_L || (n >= SM_STLCL_OB && n < SM_NFIELDS); }
+// [fmask_l (nmem)] [fmask_s .. cdice] [SM_STLCL_OB .. SM_CORH (nmem each)] [the climatologies and sstan3]
+__host__ __device__ inline long surf_slot(int n, int nmem, int e)
+{
+    if (n == SM_FMASK_L) return e;
+    if (n < SM_STLCL_OB) return (long)nmem - 1 + n;
+    if (n < SM_NFIELDS) return (long)nmem - 1 + SM_STLCL_OB + (long)(n - SM_STLCL_OB) * nmem + e;
+    return (long)(nmem - 1) * SM_NMEMBER + n;
+}
+inline long surf_total(int nmem) { return (long)(nmem - 1) * SM_NMEMBER + SM_TOTAL; }
 // The date as the interpolations need it (interpolation.f90:16-69), in model memory: forin5's five months (0-based: imon-2 ..
 // imon+2) and weights wm2 wm1 w0 wp1 wp2; forint's two months (imon, imon2) and weight wmon; forint(2, sstan3)'s second slot
 struct SurfDate {
@@ -430,7 +446,8 @@ struct SurfCols {
     int ncol, day, flags;
     double *f;                                       // the model's fields
     const SurfDate *date;
-    const double *hfluxn, *shf, *evap, *ssrd;        // (ix,il,2), (ix,il,3), (ix,il,3), (ix,il): read with day > 0 only
+    const double *hfluxn, *shf, *evap, *ssrd;        // (ix,il,2), (ix,il,3), (ix,il,3), (ix,il) per member: read with day > 0 only
+    int nmem;                                        // members: ONE launch, the member in blockIdx.y, its arrays at uniform offsets
 };
 hipError_t launch_surface_couple(const SurfCols &a, hipStream_t s);
 struct SurfForcingCols {
@@ -438,6 +455,7 @@ struct SurfForcingCols {
     double *f;
     const double *phis0;                             // plan-owned (ix, il)
     double gamlat, pexp;                             // gamma/(1000 grav), 1/(rgas gamlat) (forcing.f90:86, :112)
+    int nmem;                                        // as SurfCols::nmem; phis0 is shared
 };
 hipError_t launch_surface_forcing(const SurfForcingCols &a, hipStream_t s);
 
@@ -452,12 +470,15 @@ struct DiagLevel {
 };
 // ONE launch, one workgroup per level: the level's sums over the (mx, nx) rectangle without m = 1, temp, the range test against
 // limits (reke, deke, temp low, temp high), row (next_step mod capacity) of history ([capacity][3][kx]) and the state's update.
+// nmem members: a (kx, nmem) grid, the member in blockIdx.y.  Member e reads slice e of the (mx, nx, kx, nmem) spectra, owns
+// state[e][.] -- its own counter, its own sticky first offence: it reads no other member's -- and block e of each history row.
 struct DiagArgs {
-    const double *vor, *div, *t;                     // (mx, nx, kx) complex
-    const double *elm2, *limits;                     // (mx, nx); 4
-    double *history;
-    DiagLevel *state;                                // [kx]
+    const double *vor, *div, *t;                     // (mx, nx, kx, nmem) complex
+    const double *elm2, *limits;                     // (mx, nx); 4: shared
+    double *history;                                 // [capacity][nmem][3][kx]
+    DiagLevel *state;                                // [nmem][kx]
     int nspec, mx, kx, capacity;                     // nspec = mx * nx
+    int nmem;
 };
 hipError_t launch_diagnostics(const DiagArgs &a, hipStream_t s);
 

@@ -66,6 +66,7 @@ struct spdy_plan {
     int num_cu = 256;
     int wg_per_cu = 1;                // fused kernels: one 448-thread wave-specialised workgroup per CU
     int fused_mode = -1;              // -1 auto, 0 four-kernel path, 1 fused kernels (T30 only)
+    bool ens_member_qcorh = false;    // the ensemble spectral steps read d_qcorh as (mx, nx, nmem), a field per member (spdy_plan_set_option)
     bool t63_derive = true;           // T63 model-sized inverse batches evaluate uvspec / grad on load ($SPDY_T63_NODERIVE, spdy_plan_set_option)
     // optional per-kernel timing (HIP events on the launch stream)
     bool profiling = false;
@@ -90,10 +91,11 @@ struct spdy_sppt {
 struct spdy_diagnostics {
     spdy_plan *plan = nullptr;
     int capacity = 0;
+    int nmem = 1;                         // members checked by one launch (spdy_ens_diagnostics_create)
     long long start_step = 0;             // the first step since create / reset: nothing before it is in the ring
-    double *d_history = nullptr;          // [capacity][3][kx]
-    double *d_limits = nullptr;           // reke, deke, temp low, temp high
-    spdy::DiagLevel *d_state = nullptr;   // [kx]
+    double *d_history = nullptr;          // [capacity][nmem][3][kx]
+    double *d_limits = nullptr;           // reke, deke, temp low, temp high: shared by the members
+    spdy::DiagLevel *d_state = nullptr;   // [nmem][kx]
 };
 
 namespace spdy_detail {

@@ -563,6 +563,7 @@ hipError_t launch_tendency_combine(const DevPlan &p, double *pdiv, double *pspec
 // Ensemble form (SpecStep::nmem, never SH): blockIdx.y is the member e.  Its prognostics are the [kx] stack e of each time level
 // (time levels nmem*kx fields apart; ps: field e, nmem apart), its direct-batch outputs level slot e*kx + k of each group (group
 // stride nmem*kx, level-free slot 3*nmem*kx + e).  Only these base offsets differ (nmem = 1: the same addresses); all are uniform.
+// With SpecStep::member_qcorh its qcorh is field e of a (mx, nx, nmem) stack (one more such offset), otherwise the shared one.
 template <int NJ, bool FULL, bool SH>
 __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecStep &a)
 {
@@ -830,7 +831,7 @@ __device__ __forceinline__ void spectral_step_body(const DevPlan &p, const SpecS
         vordt = hd(vo, vordt, dmps, dmp1s);
         divdt = hd(dv, divdt, dmps, dmp1s);
         tdt = hd(ctmp, tdt, dmps, dmp1s);
-        const cpx cq = tr1 + p.qcorv[k] * ld(a.qcorh, ec);
+        const cpx cq = tr1 + p.qcorv[k] * ld(a.qcorh + (!SH && a.member_qcorh ? mp : 0), ec);
         trdt = hd(cq, trdt, dmpd, dmp1d);
     }
     STEP_MARK(6);

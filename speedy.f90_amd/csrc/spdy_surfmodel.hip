@@ -4,6 +4,10 @@
 // SurfField), read and written by its column's thread only.  The date weights are read from model memory (SurfDate), so a
 // captured launch picks a new date up on its next replay.
 //
+// nmem members go through ONE launch of each kernel: blockIdx.y is the member, which enters only as uniform offsets -- of its own
+// fields in the model's array (surf_slot, csrc/spdy_kernels.hpp) and of its state in the flux arrays.  Every expression below
+// is the single state's, on the same values in the same order.
+//
 // Unsuffixed literals of the reference are float32 values widened: sstfr = 273.2 - 1.8 is a float32
 // difference, anom0 = 20., albsea .. emisfc, sbc, alhc, sd2sc.  sea_coupling_flag is 0 (the reference stops otherwise), so
 // hfseacl = 0, beta = 1, sst_om is initialised to 0 and no ocean-model climatology exists.
@@ -20,17 +24,22 @@ __global__ __launch_bounds__(SURF_BLOCK) void surface_couple_kernel(const SurfCo
     const long i = (long)blockIdx.x * SURF_BLOCK + threadIdx.x;
     const long ncol = a.ncol;
     if (i >= ncol) return;
+    const int nmem = a.nmem, mem = blockIdx.y;
     double *const f = a.f + i;
     const SurfDate &d = *a.date;
-    auto at = [&](int n) -> double & { return f[(long)n * ncol]; };
+    auto at = [&](int n) -> double & { return f[surf_slot(n, nmem, mem) * ncol]; };               // a field by its name
+    const double *const cl = f + surf_slot(SM_NFIELDS, nmem, 0) * ncol;
+    auto clim = [&](int n) { return cl[(long)(n - SM_NFIELDS) * ncol]; };                         // a month of a climatology
+    const long mo = (long)mem * ncol;
+    const double *const hfluxn = a.hfluxn + 2 * mo, *const shf = a.shf + 3 * mo, *const evap = a.evap + 3 * mo, *const ssrd = a.ssrd + mo;
     // interpolation.f90:38-69 and :16-35 at this column
     auto forin5 = [&](int c) {
-        return d.w5[0] * at(c + d.m5[0]) + d.w5[1] * at(c + d.m5[1]) + d.w5[2] * at(c + d.m5[2]) + d.w5[3] * at(c + d.m5[3]) +
-               d.w5[4] * at(c + d.m5[4]);
+        return d.w5[0] * clim(c + d.m5[0]) + d.w5[1] * clim(c + d.m5[1]) + d.w5[2] * clim(c + d.m5[2]) + d.w5[3] * clim(c + d.m5[3]) +
+               d.w5[4] * clim(c + d.m5[4]);
     };
     auto forint = [&](int c, int m0, int m1) {
-        const double x = at(c + m0);
-        return x + d.wmon * (at(c + m1) - x);
+        const double x = clim(c + m0);
+        return x + d.wmon * (clim(c + m1) - x);
     };
     const double sstfr = F(273.2f - 1.8f);
 
@@ -47,7 +56,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void surface_couple_kernel(const SurfCo
     } else if (a.flags & SURF_LAND) {
         // run_land_model
         double tanom = at(SM_STL_LM) - stlcl;
-        tanom = at(SM_CDLAND) * (tanom + at(SM_RHCAPL) * a.hfluxn[i]);
+        tanom = at(SM_CDLAND) * (tanom + at(SM_RHCAPL) * hfluxn[i]);
         const double stl = tanom + stlcl;
         at(SM_STL_LM) = stl;
         at(SM_STL_AM) = stl;
@@ -91,11 +100,11 @@ __global__ __launch_bounds__(SURF_BLOCK) void surface_couple_kernel(const SurfCo
         if (a.flags & SURF_ICE) {
             // run_sea_model, with sice_am / tice_am of the previous call
             const double albsea = F(0.07f), albice = F(0.60f), emisfc = F(0.98f), sbc = F(5.67e-8f), alhc = F(2501.0f);
-            const double hfl2 = a.hfluxn[ncol + i];
+            const double hfl2 = hfluxn[ncol + i];
             const double tice_am = at(SM_TICE_AM), sice_am = at(SM_SICE_AM);
             const double fr2 = sstfr * sstfr, ti2 = tice_am * tice_am;
-            const double difice = (albsea - albice) * a.ssrd[i] + emisfc * sbc * (fr2 * fr2 - ti2 * ti2) + a.shf[ncol + i] +
-                                  a.evap[ncol + i] * alhc;
+            const double difice = (albsea - albice) * ssrd[i] + emisfc * sbc * (fr2 * fr2 - ti2 * ti2) + shf[ncol + i] +
+                                  evap[ncol + i] * alhc;
             const double hflux_i = hfl2 + difice * (1.0 - sice_am);
             // 1. ocean mixed layer
             double hflux = hfl2 - 0.0 - sicecl * (hflux_i + 1.0 * (sstfr - tice_om));
@@ -135,8 +144,9 @@ __global__ __launch_bounds__(SURF_BLOCK) void surface_forcing_kernel(const SurfF
     const long i = (long)blockIdx.x * SURF_BLOCK + threadIdx.x;
     const long ncol = a.ncol;
     if (i >= ncol) return;
+    const int nmem = a.nmem, mem = blockIdx.y;
     double *const f = a.f + i;
-    auto at = [&](int n) -> double & { return f[(long)n * ncol]; };
+    auto at = [&](int n) -> double & { return f[surf_slot(n, nmem, mem) * ncol]; };
     // forcing.f90:55-62, mod_radcon.f90:22-24, land_model.f90:43
     const double albsea = F(0.07f), albice = F(0.60f), albsn = F(0.60f), sd2sc = F(60.0f), refrh1 = F(0.7f);
     const double alb0 = at(SM_ALB0), fl = at(SM_FMASK_L), fs = at(SM_FMASK_S);
@@ -161,8 +171,8 @@ __global__ __launch_bounds__(SURF_BLOCK) void surface_forcing_kernel(const SurfF
 template <class Args>
 hipError_t launch(void (*k)(Args), const Args &a, hipStream_t s)
 {
-    if (a.ncol <= 0 || !a.f) return hipErrorInvalidValue;
-    const dim3 grd((unsigned)((a.ncol + SURF_BLOCK - 1) / SURF_BLOCK)), blk(SURF_BLOCK);
+    if (a.ncol <= 0 || !a.f || a.nmem < 1 || a.nmem > 65535) return hipErrorInvalidValue;
+    const dim3 grd((unsigned)((a.ncol + SURF_BLOCK - 1) / SURF_BLOCK), (unsigned)a.nmem), blk(SURF_BLOCK);
     hipLaunchKernelGGL(k, grd, blk, 0, s, a);
     return hipGetLastError();
 }

@@ -5,6 +5,8 @@ The layout is the single-state layout with every level dimension kx widened to E
     vor, div, t, tr   complex128 (2, E, kx, nx, mx)      time level lv of all members = one contiguous stack of E*kx fields
     ps                complex128 (2, E, nx, mx)
     phis, tcorh, qcorh           (nx, mx)                shared by all members
+    qcorh with member_qcorh      (E, nx, mx)             a field per member: what a coupled ensemble needs, since qcorh is made
+                                                         from the member's own land and sea temperatures (SurfaceModel.forcing_dev)
     phi, phim                    (E, kx, nx, mx)         the step's geopotential, the physics' (time level 1)
     ug, vg                       (E, kx, il, ix)
     plain_g                      (4, E, kx, il, ix)      vorg | divg | tg | trg
@@ -17,6 +19,11 @@ so the transforms are the existing calls with larger counts, the physics tendenc
 U, V and the second and third group of PL (states back to back at stride kx, what the column chain takes as nb = E), and member e of
 the two column kernels works on level slot e*kx + k with group stride E*kx.
 
+One step of a coupled ensemble, with a SurfaceModel and a Diagnostics of nmem = E: on a day's first step
+model.forcing_dev(ens.qcorh); ens.step with the model's boundary() as bnd / albsfc and hfluxn, shf, evap, ssrd in "out";
+guard.check_dev on time level 2 (ens.vor[1], ens.div[1], ens.t[1]); the host's newdate, and set_date when the day changed;
+model.couple_dev(day, hfluxn, shf, evap, ssrd).
+
 `step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  Not covered: SPPT (one pattern object
 holds one pattern), the level-sharded step."""
 import numpy as np
@@ -27,12 +34,14 @@ ROB, WIL = float(np.float32(0.05)), float(np.float32(0.53))          # params.f9
 SDRAG = 1.0 / (float(np.float32(24.0 * 30.0)) * 3600.0)              # time_stepping.f90:77, dynamical_constants.f90:22
 
 
-def shapes(nmem, kx, nx, mx, il, ix):
+def shapes(nmem, kx, nx, mx, il, ix, member_qcorh=False):
     """name -> (shape, is complex) of every array of an E-member ensemble (no device needed)"""
     E, s, g = nmem, (nx, mx), (il, ix)
     out = {n: ((2, E, kx) + s, True) for n in ("vor", "div", "t", "tr")}
     out["ps"] = ((2, E) + s, True)
     out.update({n: (s, True) for n in SHARED})
+    if member_qcorh:
+        out["qcorh"] = ((E,) + s, True)
     out.update(phi=((E, kx) + s, True), phim=((E, kx) + s, True))
     out.update(ug=((E, kx) + g, False), vg=((E, kx) + g, False), plain_g=((4, E, kx) + g, False), px=((E,) + g, False),
                py=((E,) + g, False))
@@ -44,8 +53,9 @@ def shapes(nmem, kx, nx, mx, il, ix):
 class Ensemble:
     """The prognostics and the step's scratch of E members on the device, per-member views of them, and the step."""
 
-    def __init__(self, sp, nmem, device="cuda", sdrag=SDRAG, rob=ROB, wil=WIL, arrays=None):
-        """arrays: optionally {name: tensor} of caller-made contiguous tensors on `device` to use for those arrays in place of fresh
+    def __init__(self, sp, nmem, device="cuda", sdrag=SDRAG, rob=ROB, wil=WIL, arrays=None, member_qcorh=False):
+        """member_qcorh: qcorh is (E, nx, mx), a humidity correction per member (the plan option "ens_member_qcorh", set by step).
+        arrays: optionally {name: tensor} of caller-made contiguous tensors on `device` to use for those arrays in place of fresh
         ones, each of the shape and type `shapes` gives (a host that places the ensemble inside its own allocations)."""
         import torch
         if nmem < 1:
@@ -54,9 +64,9 @@ class Ensemble:
         if sp.max_batch < need:
             raise ValueError("the plan's max_batch must be >= nmem*max(3*kx+1, 4*kx) = %d" % need)
         self.sp, self.nmem, self.kx = sp, nmem, sp.kx
-        self.sdrag, self.rob, self.wil = sdrag, rob, wil
+        self.sdrag, self.rob, self.wil, self.member_qcorh = sdrag, rob, wil, bool(member_qcorh)
         given = dict(arrays or {})
-        for n, (shape, cplx) in shapes(nmem, sp.kx, sp.nx, sp.mx, sp.il, sp.ix).items():
+        for n, (shape, cplx) in shapes(nmem, sp.kx, sp.nx, sp.mx, sp.il, sp.ix, self.member_qcorh).items():
             dtype = torch.complex128 if cplx else torch.float64
             a = given.pop(n, None)
             if a is None:
@@ -76,9 +86,12 @@ class Ensemble:
     # ------------------------------------------------------------------ views
     def member(self, e):
         """the single-state dict of views of member e: vor, div, t, tr (2, kx, nx, mx), ps (2, nx, mx) and the shared phis, tcorh,
-        qcorh.  A time level of a member, D[n][lv], is contiguous; the two time levels are E*kx (ps: E) fields apart."""
+        qcorh (with member_qcorh: the member's own qcorh).  A time level of a member, D[n][lv], is contiguous; the two time levels
+        are E*kx (ps: E) fields apart."""
         D = {n: getattr(self, n)[:, e] for n in PROG}
         D.update({n: getattr(self, n) for n in SHARED})
+        if self.member_qcorh:
+            D["qcorh"] = self.qcorh[e]
         return D
 
     def set_member(self, e, st):
@@ -88,6 +101,7 @@ class Ensemble:
             getattr(self, n)[:, e].copy_(torch.as_tensor(np.ascontiguousarray(st[n], np.complex128)))
 
     def set_shared(self, st):
+        """phis, tcorh and qcorh from host arrays; with member_qcorh, st["qcorh"] (nx, mx) goes to every member"""
         import torch
         for n in SHARED:
             getattr(self, n).copy_(torch.as_tensor(np.ascontiguousarray(st[n], np.complex128)))
@@ -116,6 +130,7 @@ class Ensemble:
             sp.ens_geopotential_dev(E, self.t[0], self.phis, self.phim)
             sp.ens_physics_dev(E, physics["sw"], self.vor[0], self.div[0], self.t[0], self.tr[0], self.phim, self.ps[0], physics["bnd"],
                                physics["albsfc"], physics["rad"], self.utend, self.vtend, self.ttend, self.qtend, physics.get("out"))
+        sp.set_option("ens_member_qcorh", 1 if self.member_qcorh else 0)      # read when the call below is enqueued
         sp.ens_direct_batch_spectral_step_dev(E, self.U, self.V, self.PL, self.pvor, self.pdiv, self.pspec, self.vor, self.div, self.t,
                                               self.tr, self.ps, self.phis, self.tcorh, self.qcorh, self.sdrag, j1, dt, eps, self.wil,
                                               self.phi, kcos=2)

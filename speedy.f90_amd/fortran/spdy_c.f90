@@ -842,6 +842,22 @@ module spdy_c
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function
+        function spdy_ens_surface_model_create(plan, nmem, clim, delt, flags, model) &
+                & bind(C, name="spdy_ens_surface_model_create") result(rc)
+            import :: c_int, c_ptr, c_double, spdy_surface_clim
+            type(c_ptr), value :: plan
+            integer(c_int), value :: nmem
+            type(spdy_surface_clim), intent(in) :: clim
+            real(c_double), value :: delt
+            integer(c_int), value :: flags
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        function spdy_surface_model_members(model, name) bind(C, name="spdy_surface_model_members") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: model, name       ! name: c_loc of a null-terminated string, or c_null_ptr for the object's nmem
+            integer(c_int) :: rc
+        end function
         function spdy_surface_model_destroy(model) bind(C, name="spdy_surface_model_destroy") result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: model
@@ -972,6 +988,36 @@ module spdy_c
             integer(c_int), value :: capacity
             integer(c_long_long), value :: first_step
             type(c_ptr), intent(out) :: d
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_diagnostics_create(plan, nmem, capacity, first_step, d) bind(C, name="spdy_ens_diagnostics_create") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: plan
+            integer(c_int), value :: nmem, capacity
+            integer(c_long_long), value :: first_step
+            type(c_ptr), intent(out) :: d
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_diagnostics_status(d, member, next_step, bad_step, bad_level, bad_mask, bad_row) &
+                & bind(C, name="spdy_ens_diagnostics_status") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: d, bad_row
+            integer(c_int), value :: member
+            integer(c_long_long), intent(out) :: next_step, bad_step
+            integer(c_int), intent(out) :: bad_level, bad_mask
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_diagnostics_read(d, member, step, count, rows) bind(C, name="spdy_ens_diagnostics_read") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: d, rows
+            integer(c_int), value :: member, count
+            integer(c_long_long), value :: step
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_diagnostics_stopped(d, bad_step) bind(C, name="spdy_ens_diagnostics_stopped") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: d
+            integer(c_long_long), intent(out) :: bad_step(*)
             integer(c_int) :: rc
         end function
         function spdy_diagnostics_destroy(d) bind(C, name="spdy_diagnostics_destroy") result(rc)

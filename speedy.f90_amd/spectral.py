@@ -320,7 +320,7 @@ class Spectral(ColumnPhysics):
 
     def set_option(self, name, value):
         """Launch-policy switch of this plan (spdy_plan_set_option): "t30_part", "t30_split", "t63_split", "t63_stage",
-        "t63_derive" (0 / 1), "t63_np2_from", "wt_min_mb"."""
+        "t63_derive" (0 / 1), "t63_np2_from", "wt_min_mb", "physics_fused", "ens_member_qcorh" (0 / 1)."""
         check(self.lib.spdy_plan_set_option(self.h, name.encode(), int(value)))
 
     def wave_placement(self):

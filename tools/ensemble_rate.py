@@ -11,9 +11,18 @@ The comparison with an earlier build: --single-only times the single-state step 
 ensemble entry points; select it with $SPDY_LIB.  Run that and this build's --single-only alternately, twice each: the difference
 between two runs of the same build is the run-to-run spread a difference between the builds has to exceed.
 
+--coupled measures a RUN's step instead: graph replays of {the step with the physics, check_dev on time level 2, couple_dev(1)}.
+The batched form is one SurfaceModel and one Diagnostics of E members (two launches behind the step, whatever E, and a humidity
+correction per member); the per-member form is E single objects on the members' views, 2 E launches, which is all a library from
+before the batched objects can do.  --earlier-library binds such a library ($SPDY_LIB): what it lacks is left out, the member
+forms of one member are its unsuffixed calls, and only the per-member form (and, without --coupled, what it has) is measured.
+
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
-    SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent"""
+    SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
+    python tools/ensemble_rate.py --coupled --members 1 2 4 8 16
+    SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -141,11 +150,126 @@ def run(tag, members, reps, repeats, label, rows):
     sp.close()
 
 
+def earlier_library():
+    """Bind a library from before this build's newest entry points: drop what it lacks from the table; one member's member forms
+    are its unsuffixed calls; the option it does not know describes the layout it always has."""
+    from speedy_f90_amd import _lib
+    from speedy_f90_amd import spectral
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    missing = [n for n in _lib.SIGNATURES if not hasattr(raw, n)]
+    for n in missing:
+        del _lib.SIGNATURES[n]
+    lib = _lib.load()
+    shims = {"spdy_ens_surface_model_create": lambda h, nmem, *a: lib.spdy_surface_model_create(h, *a),
+             "spdy_ens_diagnostics_create": lambda h, nmem, *a: lib.spdy_diagnostics_create(h, *a),
+             "spdy_ens_diagnostics_status": lambda d, member, *a: lib.spdy_diagnostics_status(d, *a),
+             "spdy_ens_diagnostics_read": lambda d, member, *a: lib.spdy_diagnostics_read(d, *a),
+             "spdy_surface_model_members": lambda m, name: 1}
+    for n in missing:
+        if n in shims:
+            setattr(lib, n, shims[n])
+    if "spdy_ens_surface_model_create" in missing:
+        plain = spectral.Spectral.set_option
+        spectral.Spectral.set_option = lambda self, name, value: None if name == "ens_member_qcorh" and not value else plain(self, name, value)
+    return missing
+
+
+def run_coupled(tag, members, reps, repeats, label, rows, batched):
+    """graph replays of {step with physics, check_dev, couple_dev(1)}: per-member objects, and (batched) one object for all"""
+    import longrun
+    import surfmodel as sm
+    from oracle.pyoracle import Oracle, build
+    build()
+    kx = VARIANTS[tag][3]
+    o = Oracle(*VARIANTS[tag])
+    if tag in synth.SIGMA_SETS:
+        o.set_sigma(synth.SIGMA_SETS[tag])
+    sp = moist.plan(tag, max(members) * (4 * kx + 4))
+    case = physstep.Case(tag, sp, o)
+    sp.surface_set_orography(case.phis0)
+    dt = physstep.DT[tag]
+    sp.initialize_implicit(dt)
+    c = sm.climatology(case.phis0, longrun.latitudes(sp.table("sia_half")))
+    clim = {k: np.ascontiguousarray(v).reshape(v.shape[:-1] + sp.grid_shape) for k, v in c.items()}
+    date = sm.Date(1982, 1, 15)
+    names = ("hfluxn", "shf", "evap", "ssrd")
+    P1 = modelstep.physics_buffers(sp, case.bnd, 0.0)
+    D1 = modelstep.device_state(case.st)
+    sp.physics_workspace()
+    modelstep.step(sp, D1, modelstep.Workspace(sp), dt, physics=modelstep.whole_physics(P1, True))   # a whole radiation state
+    sp.synchronize()
+    rad0 = P1["rad"].clone()
+    dev = physstep.device_boundary(case.bnd, sp.il, sp.ix)
+
+    def model(nmem):
+        M = s.SurfaceModel(sp, clim, sm.DELT, nmem=nmem) if nmem > 1 else s.SurfaceModel(sp, clim, sm.DELT)
+        M.set_date(date.imont1, date.tmonth, date.tyear)
+        M.couple_dev(0)
+        return M
+    graphs, rearms, keep = {}, [], []
+    for E in members:
+        for form in ("per-member",) + (("batched",) if batched else ()):
+            en = s.Ensemble(sp, E, member_qcorh=True) if form == "batched" else s.Ensemble(sp, E)
+            en.set_shared(case.st)
+            for e in range(E):
+                en.set_member(e, case.st)
+            out = sp.column_outputs(E, ("sfc", "rad"), names=names)
+            F = dict(out["sfc"], **out["rad"])
+            if form == "batched":
+                M, G = model(E), (s.Diagnostics(sp, 64, 0, E) if E > 1 else s.Diagnostics(sp, 64, 0))
+                M.forcing_dev(en.qcorh)
+                bnd, albsfc = M.boundary()
+                keep.append((M, G))
+            else:
+                Ms, Gs = [model(1) for _ in range(E)], [s.Diagnostics(sp, 64, 0) for _ in range(E)]
+                b = {n: v.expand((E,) + tuple(v.shape[1:])).contiguous() for n, v in dev.items()}
+                bnd, albsfc = b, b["albsfc"]
+                keep.append((Ms, Gs))
+            PE = {"bnd": bnd, "albsfc": albsfc, "rad": rad0.repeat(E), "sw": False, "out": out}
+            en.physics_workspace()
+            start = {n: getattr(en, n).clone() for n in ("vor", "div", "t", "tr", "ps")}
+            torch.cuda.synchronize()
+            with sp.graph_capture() as g:
+                en.step(2, 2, dt, PE, eps=modelstep.ROB)
+                if form == "batched":
+                    G.check_dev(en.vor[1], en.div[1], en.t[1])
+                    M.couple_dev(1, *[F[k] for k in names])
+                else:
+                    for e in range(E):
+                        Gs[e].check_dev(en.vor[1, e], en.div[1, e], en.t[1, e])
+                    for e in range(E):
+                        Ms[e].couple_dev(1, *[F[k][e] for k in names])
+            graphs["coupled %s E=%d" % (form, E)] = g
+            keep.append((en, PE, out))
+
+            def rearm(en=en, start=start, PE=PE, E=E):
+                for n, v in start.items():
+                    getattr(en, n).copy_(v)
+                PE["rad"].copy_(rad0.repeat(E))
+            rearms.append(rearm)
+    nodes = {n: g.num_nodes() for n, g in graphs.items()}
+    t = time_interleaved({n: g.launch for n, g in graphs.items()}, lambda: [r() for r in rearms], reps, repeats)
+    for name, (med, lo, hi) in t.items():
+        E = int(name.split("=")[1])
+        row = {"label": label, "size": tag, "form": name, "members": E, "nodes": nodes[name], "us_per_step": round(med, 2),
+               "us_min": round(lo, 2), "us_max": round(hi, 2), "us_per_member_step": round(med / E, 2)}
+        per = t.get("coupled per-member E=%d" % E)
+        if "batched" in name and per:
+            row["us_saved_vs_per_member"] = round(per[0] - med, 2)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for g in graphs.values():
+        g.close()
+    sp.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["t30", "t63k16"])
     ap.add_argument("--members", nargs="+", type=int, default=[1, 2, 4, 8, 16, 32])
     ap.add_argument("--single-only", action="store_true")
+    ap.add_argument("--coupled", action="store_true")
+    ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
@@ -155,10 +279,16 @@ def main():
         from speedy_f90_amd import _lib
         for n in [n for n in _lib.SIGNATURES if n.startswith("spdy_ens_")]:
             del _lib.SIGNATURES[n]
+    batched = True
+    if a.earlier_library:
+        batched = "spdy_ens_surface_model_create" not in earlier_library()
     rows = []
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
-            run(tag, [] if a.single_only else a.members, a.reps, a.repeats, a.label, rows)
+            if a.coupled:
+                run_coupled(tag, a.members, a.reps, a.repeats, a.label, rows, batched)
+            else:
+                run(tag, [] if a.single_only else a.members, a.reps, a.repeats, a.label, rows)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(rows, f, indent=1)
