@@ -283,7 +283,9 @@ int spdy_spectral_step_dev(spdy_plan *plan, double *pvor, double *pdiv, double *
  * implicit.f90:168-217, time_stepping.f90:62-167).  At T30 exactly those two calls; at T63, where vds is not part of the
  * transform kernel, the pairs' spectra stay in the plan's temporaries and vds (spectral.f90:146-171) is applied where the
  * spectral step reads them: 2 launches instead of 3.  pvor, pdiv, pspec receive the truncated tendencies as with the
- * separate calls; results agree with them to rounding.                                                              */
+ * separate calls; results agree with them to rounding.  Checks, in this order: the plan and its device; what the spectral
+ * step needs (spdy_implicit_init, sigma levels) SPDY_ERR_STATE; a NULL pointer, then j1 outside {1, 2} SPDY_ERR_ARG; only
+ * then the direct batch's own (max_batch) -- a call that fails enqueues nothing.                                      */
 int spdy_direct_batch_spectral_step_dev(spdy_plan *plan, const double *d_ug, const double *d_vg, const double *d_grid, int kcos,
                                         double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t, double *tr,
                                         double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,

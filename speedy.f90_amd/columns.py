@@ -568,16 +568,20 @@ class ColumnPhysics:
     def physics_workspace(self):
         check(self.lib.spdy_physics_workspace(self.h))
 
+    def _physics(self, fn, lead, compute_sw, spectra, bnd, albsfc, state, tends, out):
+        """The marshalling of the three physics-from-spectra calls: the C function, its leading arguments, the shared ones."""
+        self._sync_stream()
+        o = self._column_physics_out(out)
+        b = self._boundary(bnd)
+        check(fn(self.h, *lead, 1 if compute_sw else 0, *[self._dp(x) for x in spectra], ctypes.byref(b), self._dp(albsfc),
+                 self._dp(state), *[self._dp(x) for x in tends], ctypes.byref(o)))
+
     def physics_dev(self, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, state, utend, vtend, ttend, qtend, out=None):
         """physics.f90:94-205 on one state from its spectra (time level 1: vor, div, t, q, phi [kx,nx,mx], ps [nx,mx] complex128):
         one inverse launch into plan workspace, then the column physics (one launch, or the five calls with the plan option
         "physics_fused" 0).  utend, vtend, ttend, qtend [kx,il,ix] in place; bnd, albsfc, state and out as column_physics_dev."""
-        self._sync_stream()
-        o = self._column_physics_out(out)
-        b = self._boundary(bnd)
-        check(self.lib.spdy_physics_dev(self.h, 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
-                                        ctypes.byref(b), self._dp(albsfc), self._dp(state),
-                                        *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+        self._physics(self.lib.spdy_physics_dev, (), compute_sw, (vor, div, t, q, phi, ps), bnd, albsfc, state,
+                      (utend, vtend, ttend, qtend), out)
 
     def ens_physics_workspace(self, nmem):
         check(self.lib.spdy_ens_physics_workspace(self.h, int(nmem)))
@@ -586,12 +590,8 @@ class ColumnPhysics:
         """physics_dev for nmem members (ensemble.py's layout): time level 1 of all members, vor, div, t, q, phi [nmem,kx,nx,mx], ps
         [nmem,nx,mx]; ONE inverse launch, then the column physics with nb = nmem.  utend .. qtend [nmem,kx,il,ix] in place; the fields
         of bnd, albsfc, state and out are per member, back to back, as column_physics_dev takes them for nb states."""
-        self._sync_stream()
-        o = self._column_physics_out(out)
-        b = self._boundary(bnd)
-        check(self.lib.spdy_ens_physics_dev(self.h, int(nmem), 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
-                                            ctypes.byref(b), self._dp(albsfc), self._dp(state),
-                                            *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+        self._physics(self.lib.spdy_ens_physics_dev, (int(nmem),), compute_sw, (vor, div, t, q, phi, ps), bnd, albsfc, state,
+                      (utend, vtend, ttend, qtend), out)
 
     # ------------------------------------------------------------------ SPPT (physics.f90:85-88, :207-222)
     def column_physics_sppt_workspace(self):
@@ -619,12 +619,8 @@ class ColumnPhysics:
     def physics_sppt_dev(self, sppt, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, state, utend, vtend, ttend, qtend, out=None):
         """physics_dev followed by SPPT with the current pattern and the mu of sppt (a Sppt of this plan), which is not advanced:
         call sppt.advance_dev() first."""
-        self._sync_stream()
-        o = self._column_physics_out(out)
-        b = self._boundary(bnd)
-        check(self.lib.spdy_physics_sppt_dev(self.h, sppt.h, 1 if compute_sw else 0, *[self._dp(x) for x in (vor, div, t, q, phi, ps)],
-                                             ctypes.byref(b), self._dp(albsfc), self._dp(state),
-                                             *[self._dp(x) for x in (utend, vtend, ttend, qtend)], ctypes.byref(o)))
+        self._physics(self.lib.spdy_physics_sppt_dev, (sppt.h,), compute_sw, (vor, div, t, q, phi, ps), bnd, albsfc, state,
+                      (utend, vtend, ttend, qtend), out)
 
     # ------------------------------------------------------------------ NumPy conveniences: inputs and results by name, shaped by FIELDS
     def _grid_args(self, ins, ref="tg"):

@@ -1,7 +1,8 @@
 // C ABI of the column physics (include/spdy.h, "column physics"): the precipitation block (physics.f90:110-138), the
 // radiation schemes (physics.f90:146-166 and :180-186), the surface fluxes (:169-170), the boundary layer (:193-205) and the
 // whole chain, on gridded states and from spectra, without and with SPPT (:207-222).  Kernels: csrc/spdy_sppt.hip, csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip,
-// csrc/spdy_column_chain.hip.
+// csrc/spdy_column_chain.hip.  The physics from spectra is one body (physics_from_spectra) for one state, nmem members and one state
+// with SPPT; the single state is nmem = 1 on a workspace of its own.
 #include <cmath>
 #include <cstring>
 
@@ -222,6 +223,69 @@ int sppt_workspace(spdy_plan *p, double **ws, size_t states, const char *scheme,
     *ws = static_cast<double *>(ptr);
     return SPDY_OK;
 }
+
+// ---- the physics of nmem states from their spectra: one body for spdy_physics_dev, spdy_ens_physics_dev, spdy_physics_sppt_dev ----
+struct FromSpectra {   // the arguments the three calls share, in their order
+    int compute_sw;
+    const double *vor, *div, *t, *q, *phi, *ps;
+    const spdy_sfc_boundary *bnd;
+    const double *albsfc;
+    double *rad_state, *utend, *vtend, *ttend, *qtend;
+    const spdy_column_physics_out *out;
+};
+
+// The member count against the plan and max_batch against the ONE inverse launch of 3 kx + 1 plain fields per member: the first checks
+// of the ensemble calls, the last of the single-state ones.
+int physics_members(const spdy_plan *p, int nmem, bool ens)
+{
+    NEED_PLAN(p);
+    if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_physics: nmem=%d < 1", nmem);
+    RC(check_kx(p, ens ? "ens_physics" : "physics"));
+    const long need = (long)nmem * (3 * p->tab.kx + 1);
+    if (p->max_batch >= need) return SPDY_OK;
+    if (ens) return fail(SPDY_ERR_ARG, "ens_physics: max_batch=%d must be >= nmem*(3*kx+1)=%ld", p->max_batch, need);
+    return fail(SPDY_ERR_ARG, "max_batch must be >= 3*kx+1 for the physics from spectra");
+}
+
+// The checks that need no device, in each call's documented order.  With SPPT the pattern is one of the required pointers, and its
+// plan is tested after them.
+int physics_args(const spdy_plan *p, int nmem, bool ens, const FromSpectra &a, bool with_sppt = false, const spdy_sppt *sppt = nullptr)
+{
+    const bool ok = (!with_sppt || sppt) && a.vor && a.div && a.t && a.q && a.phi && a.ps && boundary_ok(a.bnd) &&
+                    (!a.compute_sw || a.albsfc) && a.rad_state && a.utend && a.vtend && a.ttend && a.qtend;
+    if (ens) RC(physics_members(p, nmem, true));
+    RC(column_args(p, ens ? "ens_physics" : "physics", nmem, true, ok, true));
+    if (sppt && sppt->plan != p) return fail(SPDY_ERR_ARG, "the SPPT pattern belongs to another plan");
+    return ens ? SPDY_OK : physics_members(p, 1, false);
+}
+
+// the workspace w (spdy_plan::PhysicsGrids) for at least nmem states; the plan and kx are checked
+int physics_grids(spdy_plan *p, spdy_plan::PhysicsGrids *w, int nmem, const char *what)
+{
+    NEED_DEVICE(p);
+    if (w->nmem >= nmem) return SPDY_OK;
+    NOT_CAPTURING(p, what);
+    RC(ensure_four(p));   // the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
+    // a smaller earlier workspace stays with the plan until it is destroyed: a captured graph may still point into it
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * nmem * sizeof(double), &ptr));
+    *w = {static_cast<double *>(ptr), nmem};
+    return SPDY_OK;
+}
+
+// physics.f90:94-205 for nmem states, arguments checked and w allocated: ONE inverse launch of time level 1 -- nmem kx (vor, div)
+// pairs through uvspec with kcos 2; t, q, phi (nmem kx each) and ps (nmem) with kcos 1 (physics.f90:94-104) -- into w's grids, nmem
+// states back to back at state stride kx, then the chain with nb = nmem on w's chain workspace.
+int physics_from_spectra(spdy_plan *p, int nmem, const spdy_plan::PhysicsGrids &w, const SpptUse *sppt, const FromSpectra &a)
+{
+    const int kx = p->tab.kx, nk = nmem * kx;
+    const size_t g1 = grid_elems(p) * nmem, L = (size_t)kx * g1;
+    double *ug = w.g, *vg = ug + L, *tg = ug + 2 * L, *qg = ug + 3 * L, *phig = ug + 4 * L, *pslg = ug + 5 * L;
+    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{nk, a.t}, {nk, a.q}, {nk, a.phi}, {nmem, a.ps}};
+    RC(spdy_inverse_batch_segs_dev(p, nk, a.vor, a.div, ug, vg, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, tg, 0, nullptr, nullptr, nullptr, 2));
+    return column_chain(p, p->physics_fused != 0, nmem, a.compute_sw, ug, vg, tg, qg, phig, pslg, a.bnd, a.albsfc, a.rad_state, a.utend,
+                        a.vtend, a.ttend, a.qtend, a.out, pslg + g1, g1, sppt);
+}
 }  // namespace
 
 extern "C" {
@@ -424,91 +488,39 @@ int spdy_column_physics_sppt_dev(spdy_plan *p, int nb, const double *d_pattern, 
                         ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch, &use);
 }
 
-/* ---------------------------------------------------------------- one state's physics from its spectra (physics.f90:94-205) */
+/* ---------------------------------------------------------------- the physics from spectra (physics.f90:94-205): one state, nmem members, one state with SPPT */
 int spdy_physics_workspace(spdy_plan *p)
 {
     NEED_PLAN(p);
     RC(check_kx(p, "physics"));
-    NEED_DEVICE(p);
-    if (p->physics_grid) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the physics workspace (call spdy_physics_workspace before the capture)");
-    // the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
-    RC(ensure_four(p));
-    // 5 kx + 1 grids u | v | t | q | phi | ln ps, then one state's chain workspace (3 kx + 12 grids)
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * sizeof(double), &ptr));
-    p->physics_grid = static_cast<double *>(ptr);
-    return SPDY_OK;
+    return physics_grids(p, &p->physics_grid, 1, "allocating the physics workspace (call spdy_physics_workspace before the capture)");
 }
 
 int spdy_physics_dev(spdy_plan *p, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
                      const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
                      double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out)
 {
-    const bool ok = vor && div && t && q && phi && ps && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
-                    vtend && ttend && qtend;
-    RC(column_args(p, "physics", 1, true, ok, true));
-    const int kx = p->tab.kx;
-    if (p->max_batch < 3 * kx + 1) return fail(SPDY_ERR_ARG, "max_batch must be >= 3*kx+1 for the physics from spectra");
-    NEED_DEVICE(p);
+    const FromSpectra a{compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, qtend, out};
+    RC(physics_args(p, 1, false, a));
     RC(spdy_physics_workspace(p));
-    // physics.f90:94-104: ONE inverse launch -- kx (vor, div) pairs through uvspec with kcos 2, t, q, phi (kx each) and ps with kcos 1
-    const size_t L = (size_t)kx * grid_elems(p);
-    double *g = p->physics_grid;
-    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{kx, t}, {kx, q}, {kx, phi}, {1, ps}};
-    RC(spdy_inverse_batch_segs_dev(p, kx, vor, div, g, g + L, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, g + 2 * L, 0, nullptr,
-                                   nullptr, nullptr, 2));
-    return column_chain(p, p->physics_fused != 0, 1, compute_sw, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, g + 5 * L, bnd, albsfc,
-                        rad_state, utend, vtend, ttend, qtend, out, g + 5 * L + grid_elems(p), grid_elems(p));
-}
-
-/* ---------------------------------------------------------------- the physics of nmem members from their spectra (include/spdy.h, ensemble) */
-// the member count against the plan: the first checks of both calls
-static int ens_physics_members(const spdy_plan *p, int nmem)
-{
-    NEED_PLAN(p);
-    if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_physics: nmem=%d < 1", nmem);
-    RC(check_kx(p, "ens_physics"));
-    if ((long)p->max_batch < (long)nmem * (3 * p->tab.kx + 1))
-        return fail(SPDY_ERR_ARG, "ens_physics: max_batch=%d must be >= nmem*(3*kx+1)=%ld", p->max_batch, (long)nmem * (3 * p->tab.kx + 1));
-    return SPDY_OK;
+    return physics_from_spectra(p, 1, p->physics_grid, nullptr, a);
 }
 
 int spdy_ens_physics_workspace(spdy_plan *p, int nmem)
 {
-    RC(ens_physics_members(p, nmem));
-    NEED_DEVICE(p);
-    if (p->ens_physics_grid && p->ens_physics_nmem >= nmem) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the ensemble physics workspace (call spdy_ens_physics_workspace before the capture)");
-    RC(ensure_four(p));   // (the operator route of the T63 inverse launch, as spdy_physics_workspace)
-    // a smaller earlier workspace stays with the plan until it is destroyed: a captured graph may still point into it
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * nmem * sizeof(double), &ptr));
-    p->ens_physics_grid = static_cast<double *>(ptr);
-    p->ens_physics_nmem = nmem;
-    return SPDY_OK;
+    RC(physics_members(p, nmem, true));
+    return physics_grids(p, &p->ens_physics_grid, nmem,
+                         "allocating the ensemble physics workspace (call spdy_ens_physics_workspace before the capture)");
 }
 
 int spdy_ens_physics_dev(spdy_plan *p, int nmem, int compute_sw, const double *vor, const double *div, const double *t, const double *q,
                          const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc, double *rad_state,
                          double *utend, double *vtend, double *ttend, double *qtend, const spdy_column_physics_out *out)
 {
-    const bool ok = vor && div && t && q && phi && ps && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
-                    vtend && ttend && qtend;
-    RC(ens_physics_members(p, nmem));
-    RC(column_args(p, "ens_physics", nmem, true, ok, true));
-    NEED_DEVICE(p);
+    const FromSpectra a{compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, qtend, out};
+    RC(physics_args(p, nmem, true, a));
     RC(spdy_ens_physics_workspace(p, nmem));
-    // physics.f90:94-104 for all members in ONE inverse launch: nmem kx (vor, div) pairs through uvspec with kcos 2; t, q, phi
-    // (nmem kx each) and ps (nmem) with kcos 1.  The grids are nmem states back to back at state stride kx: the chain's nb = nmem.
-    const int kx = p->tab.kx, nk = nmem * kx;
-    const size_t g1 = grid_elems(p) * nmem, L = (size_t)kx * g1;
-    double *g = p->ens_physics_grid;
-    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{nk, t}, {nk, q}, {nk, phi}, {nmem, ps}};
-    double *ug = g, *vg = g + L, *tg = g + 2 * L, *qg = g + 3 * L, *phig = g + 4 * L, *pslg = g + 5 * L;
-    RC(spdy_inverse_batch_segs_dev(p, nk, vor, div, ug, vg, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, tg, 0, nullptr, nullptr, nullptr, 2));
-    return column_chain(p, p->physics_fused != 0, nmem, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend,
-                        ttend, qtend, out, g + 5 * L + g1, g1);
+    return physics_from_spectra(p, nmem, p->ens_physics_grid, nullptr, a);
 }
 
 int spdy_physics_sppt_workspace(spdy_plan *p)
@@ -523,23 +535,11 @@ int spdy_physics_sppt_dev(spdy_plan *p, spdy_sppt *sp, int compute_sw, const dou
                           double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
                           const spdy_column_physics_out *out)
 {
-    const bool ok = sp && vor && div && t && q && phi && ps && boundary_ok(bnd) && (!compute_sw || albsfc) && rad_state && utend &&
-                    vtend && ttend && qtend;
-    RC(column_args(p, "physics", 1, true, ok, true));
-    if (sp->plan != p) return fail(SPDY_ERR_ARG, "the SPPT pattern belongs to another plan");
-    const int kx = p->tab.kx;
-    if (p->max_batch < 3 * kx + 1) return fail(SPDY_ERR_ARG, "max_batch must be >= 3*kx+1 for the physics from spectra");
-    NEED_DEVICE(p);
+    const FromSpectra a{compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, qtend, out};
+    RC(physics_args(p, 1, false, a, true, sp));
     RC(spdy_physics_sppt_workspace(p));
-    // the inverse launch of spdy_physics_dev; the pattern is the one the last spdy_sppt_advance_dev left
-    const size_t L = (size_t)kx * grid_elems(p);
-    double *g = p->physics_grid;
-    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{kx, t}, {kx, q}, {kx, phi}, {1, ps}};
-    RC(spdy_inverse_batch_segs_dev(p, kx, vor, div, g, g + L, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, g + 2 * L, 0, nullptr,
-                                   nullptr, nullptr, 2));
-    const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->sppt_grid};
-    return column_chain(p, p->physics_fused != 0, 1, compute_sw, g, g + L, g + 2 * L, g + 3 * L, g + 4 * L, g + 5 * L, bnd, albsfc,
-                        rad_state, utend, vtend, ttend, qtend, out, g + 5 * L + grid_elems(p), grid_elems(p), &use);
+    const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->sppt_grid};   // the pattern the last spdy_sppt_advance_dev left
+    return physics_from_spectra(p, 1, p->physics_grid, &use, a);
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // C ABI (include/spdy.h), second half: the spectral-space tail of a time step (horizontal diffusion, semi-implicit
 // solve, spectral tendencies, geopotential, leapfrog/RAW filter) and the output path.  (Multi-GPU: spdy_api_shard.hip.)
+// Geopotential, grid tendencies, spectral step and direct batch + spectral step have one body each, taking the member count:
+// the single-state call and its ensemble form are one argument check (step_args) and one call of it, with nmem = 1 or nmem.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -13,53 +15,90 @@ using spdy::HostTables;
 using namespace spdy_detail;
 
 namespace {
-// The checks of the ensemble calls that need no device (a host-only plan answers them), in the order include/spdy.h gives.
-int ens_args(const spdy_plan *p, int nmem, const char *what, bool need_implicit, bool need_sigma, bool ok_ptrs, int j1 = 1)
+// The argument checks of a step call (ens false: nmem = 1) and of its ensemble form, each in the order it documents.  Single state:
+// the device first, then the state, the pointers and j1; neither kx nor max_batch is tested.  Ensemble: include/spdy.h, "ensemble time
+// step" -- what needs no device first (a host-only plan answers it), the device last.  no_implicit / no_sigma: the failure's text
+// where the call needs spdy_implicit_init / sigma levels, null where it does not.
+int step_args(const spdy_plan *p, bool ens, int nmem, const char *what, const char *no_implicit, const char *no_sigma, bool ok_ptrs,
+              int j1 = 1)
 {
+    if (!ens) NEED_DEVICE(p);
     NEED_PLAN(p);
     const int kx = p->tab.kx;
-    if (nmem < 1) return fail(SPDY_ERR_ARG, "%s: nmem=%d < 1", what, nmem);
-    if (nmem > 1 && kx > 16) return fail(SPDY_ERR_ARG, "%s: more than one member needs kx <= 16 (kx=%d)", what, kx);
-    if ((long)p->max_batch < (long)nmem * (3 * kx + 1))
-        return fail(SPDY_ERR_ARG, "%s: max_batch=%d must be >= nmem*(3*kx+1)=%ld", what, p->max_batch, (long)nmem * (3 * kx + 1));
-    if (need_implicit && !p->tab.implicit_ready) return fail(SPDY_ERR_STATE, "%s needs spdy_implicit_init first", what);
-    if (need_sigma && !p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "%s needs sigma levels", what);
+    if (ens) {
+        if (nmem < 1) return fail(SPDY_ERR_ARG, "%s: nmem=%d < 1", what, nmem);
+        if (nmem > 1 && kx > 16) return fail(SPDY_ERR_ARG, "%s: more than one member needs kx <= 16 (kx=%d)", what, kx);
+        if ((long)p->max_batch < (long)nmem * (3 * kx + 1))
+            return fail(SPDY_ERR_ARG, "%s: max_batch=%d must be >= nmem*(3*kx+1)=%ld", what, p->max_batch, (long)nmem * (3 * kx + 1));
+    }
+    if (no_implicit && !p->tab.implicit_ready) return fail(SPDY_ERR_STATE, "%s", no_implicit);
+    if (no_sigma && !p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "%s", no_sigma);
     if (!ok_ptrs) return fail(SPDY_ERR_ARG, "null device pointer");
     if (j1 != 1 && j1 != 2) return fail(SPDY_ERR_ARG, "j1 must be 1 or 2");
+    if (ens) NEED_DEVICE(p);
     return SPDY_OK;
 }
 
-// the one-launch spectral step of nmem members (kx <= 16), arguments checked; raw_u / raw_v: SpecStep.  The plan option
-// "ens_member_qcorh" is read here, when the call is enqueued; one member's qcorh is the same field either way.
-int spectral_step_launch(spdy_plan *p, int nmem, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
-                         double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1,
-                         double dt, double eps, double wil, double *phi, const double *raw_u, const double *raw_v)
+// The operations on nmem members, arguments checked (step_args): what the extern "C" pairs below enqueue.
+int geopotential(spdy_plan *p, int nmem, const double *t, const double *phis, double *phi)
 {
-    const spdy::SpecStep a{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, phi, sdrag, dt, eps, wil, j1,
-                           p->tab.ix == 4 * p->tab.iy, raw_u, raw_v, spdy::LevelShard{}, nullptr, 0, 0, nmem,
+    KERNEL(spdy::launch_geopotential(p->dev, nmem, t, phis, phi, p->stream));
+    return SPDY_OK;
+}
+
+int grid_tendencies(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *tg, const double *vorg, const double *divg,
+                    const double *trg, const double *px, const double *py, double *u_out, double *v_out, double *plain_out)
+{
+    const spdy::GridTend g{ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out, spdy::LevelShard{}, 0, 0, nullptr, nmem};
+    KERNEL(spdy::launch_grid_tendencies(p->dev, g, p->stream));
+    return SPDY_OK;
+}
+
+// what the spectral step takes behind the plan (and the member count), in the calls' order
+struct StepFields {
+    double *pvor, *pdiv, *pspec, *vor, *div, *t, *tr, *ps;
+    const double *phis, *d_tcorh, *d_qcorh;
+    double sdrag;
+    int j1;
+    double dt, eps, wil, *phi;
+    bool ptrs() const { return pvor && pdiv && pspec && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi; }
+};
+
+// raw_u / raw_v: SpecStep (the pairs' spectra before vds, or null).  The plan option "ens_member_qcorh" is read here, when the call
+// is enqueued; one member's qcorh is the same field either way.
+int spectral_step(spdy_plan *p, int nmem, const StepFields &f, const double *raw_u, const double *raw_v)
+{
+    const int kx = p->tab.kx;
+    if (kx > 16) {   // the fused kernel holds one level per thread row (64 x kx <= 1024 threads): issue the separate kernels.
+                     // One member only (step_args), and never the raw spectra (use_raw63)
+        RC(spdy_tendency_combine_dev(p, f.pdiv, f.pspec));
+        const size_t L = (size_t)kx * spec_elems(p);
+        double *divdt = f.pdiv, *tdt = f.pdiv + L, *trdt = f.pdiv + 2 * L, *psdt = f.pspec + 3 * L;
+        RC(spdy_spectral_tendencies_dev(p, f.div, f.t, f.ps, f.phis, divdt, tdt, psdt, f.phi));
+        RC(spdy_implicit_terms_dev(p, divdt, tdt, psdt));
+        RC(spdy_hdiff_step_dev(p, f.vor, f.div, f.t, f.tr, f.d_tcorh, f.d_qcorh, f.sdrag, f.pvor, divdt, tdt, trdt));
+        const spdy_step_op ops[5] = {{1, f.ps, psdt}, {kx, f.vor, f.pvor}, {kx, f.div, divdt}, {kx, f.t, tdt}, {kx, f.tr, trdt}};
+        return spdy_step_fields_dev(p, 5, ops, f.j1, f.dt, f.eps, f.wil);
+    }
+    const spdy::SpecStep a{f.pvor, f.pdiv, f.pspec, f.vor, f.div, f.t, f.tr, f.ps, f.phis, f.d_tcorh, f.d_qcorh, f.phi, f.sdrag, f.dt,
+                           f.eps, f.wil, f.j1, p->tab.ix == 4 * p->tab.iy, raw_u, raw_v, spdy::LevelShard{}, nullptr, 0, 0, nmem,
                            nmem > 1 && p->ens_member_qcorh};
     KERNEL(spdy::launch_spectral_step(p->dev, a, p->stream));
     return SPDY_OK;
 }
 
-// the direct batch of nmem members (3 nmem kx pairs, 3 nmem kx + nmem plain fields) and their spectral step, arguments checked
-int direct_batch_spectral_step(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *grid, int kcos, double *pvor,
-                               double *pdiv, double *pspec, double *vor, double *div, double *t, double *tr, double *ps,
-                               const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1, double dt,
-                               double eps, double wil, double *phi)
+// the direct batch of nmem members (3 nmem kx pairs, 3 nmem kx + nmem plain fields) and their spectral step
+int direct_batch_spectral_step(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *grid, int kcos,
+                               const StepFields &f)
 {
     const int P = 3 * nmem * p->tab.kx;
-    if (use_raw63(p, P)) {
-        // T63: the transform kernel leaves the pairs' spectra un-vds'ed in the plan's temporaries; the spectral step applies
-        // vds where it reads them -- direct batch + everything after it = 2 launches instead of 3
-        RC(direct_batch_raw63(p, P, ug, vg, kcos, P + nmem, grid, pspec));
-        return spectral_step_launch(p, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil,
-                                    phi, p->tmp_c, p->tmp_d);
-    }
-    // every other plan and batch: the plain direct batch, whatever form its size takes, then the spectral step
-    RC(spdy_direct_batch_dev(p, P, ug, vg, pvor, pdiv, kcos, P + nmem, grid, pspec));
-    return spectral_step_launch(p, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi,
-                                nullptr, nullptr);
+    // T63: the transform kernel leaves the pairs' spectra un-vds'ed in the plan's temporaries; the spectral step applies vds
+    // where it reads them -- direct batch + everything after it = 2 launches instead of 3.  Every other plan and batch: the plain
+    // direct batch, whatever form its size takes, then the spectral step
+    const bool raw = use_raw63(p, P);
+    RC(raw ? direct_batch_raw63(p, P, ug, vg, kcos, P + nmem, grid, f.pspec)
+           : spdy_direct_batch_dev(p, P, ug, vg, f.pvor, f.pdiv, kcos, P + nmem, grid, f.pspec));
+    return spectral_step(p, nmem, f, raw ? p->tmp_c : nullptr, raw ? p->tmp_d : nullptr);   // (they exist once the raw batch is enqueued)
 }
 }  // namespace
 
@@ -197,19 +236,15 @@ int spdy_implicit_terms(spdy_plan *p, double *divdt, double *tdt, double *psdt)
 /* ---------------------------------------------------------------- spectral side of a time step */
 int spdy_geopotential_dev(spdy_plan *p, const double *t, const double *phis, double *phi)
 {
-    NEED_DEVICE(p);
-    if (!p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "geopotential needs sigma levels (kx in {5,7,8} or spdy_plan_set_sigma)");
-    if (!t || !phis || !phi) return fail(SPDY_ERR_ARG, "null device pointer");
-    KERNEL(spdy::launch_geopotential(p->dev, 1, t, phis, phi, p->stream));
-    return SPDY_OK;
+    RC(step_args(p, false, 1, "geopotential", nullptr, "geopotential needs sigma levels (kx in {5,7,8} or spdy_plan_set_sigma)",
+                 t && phis && phi));
+    return geopotential(p, 1, t, phis, phi);
 }
 
 int spdy_ens_geopotential_dev(spdy_plan *p, int nmem, const double *t, const double *phis, double *phi)
 {
-    RC(ens_args(p, nmem, "ens_geopotential", false, true, t && phis && phi));
-    NEED_DEVICE(p);
-    KERNEL(spdy::launch_geopotential(p->dev, nmem, t, phis, phi, p->stream));
-    return SPDY_OK;
+    RC(step_args(p, true, nmem, "ens_geopotential", nullptr, "ens_geopotential needs sigma levels", t && phis && phi));
+    return geopotential(p, nmem, t, phis, phi);
 }
 
 int spdy_geopotential(spdy_plan *p, const double *t, const double *phis, double *phi)
@@ -289,23 +324,18 @@ int spdy_step_field(spdy_plan *p, int nlev, int j1, double dt, double eps, doubl
 int spdy_grid_tendencies_dev(spdy_plan *p, const double *ug, const double *vg, const double *tg, const double *vorg, const double *divg,
                              const double *trg, const double *px, const double *py, double *u_out, double *v_out, double *plain_out)
 {
-    NEED_DEVICE(p);
-    if (!p->tab.implicit_ready) return fail(SPDY_ERR_STATE, "grid_tendencies needs the reference temperature profile: call spdy_implicit_init first");
-    if (!ug || !vg || !tg || !vorg || !divg || !trg || !px || !py || !u_out || !v_out || !plain_out) return fail(SPDY_ERR_ARG, "null device pointer");
-    const spdy::GridTend g{ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out, spdy::LevelShard{}, 0, 0, nullptr, 1};
-    KERNEL(spdy::launch_grid_tendencies(p->dev, g, p->stream));
-    return SPDY_OK;
+    RC(step_args(p, false, 1, "grid_tendencies", "grid_tendencies needs the reference temperature profile: call spdy_implicit_init first",
+                 nullptr, ug && vg && tg && vorg && divg && trg && px && py && u_out && v_out && plain_out));
+    return grid_tendencies(p, 1, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out);
 }
 
 int spdy_ens_grid_tendencies_dev(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *tg, const double *vorg,
                                  const double *divg, const double *trg, const double *px, const double *py, double *u_out,
                                  double *v_out, double *plain_out)
 {
-    RC(ens_args(p, nmem, "ens_grid_tendencies", true, false, ug && vg && tg && vorg && divg && trg && px && py && u_out && v_out && plain_out));
-    NEED_DEVICE(p);
-    const spdy::GridTend g{ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out, spdy::LevelShard{}, 0, 0, nullptr, nmem};
-    KERNEL(spdy::launch_grid_tendencies(p->dev, g, p->stream));
-    return SPDY_OK;
+    RC(step_args(p, true, nmem, "ens_grid_tendencies", "ens_grid_tendencies needs spdy_implicit_init first", nullptr,
+                 ug && vg && tg && vorg && divg && trg && px && py && u_out && v_out && plain_out));
+    return grid_tendencies(p, nmem, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out);
 }
 
 int spdy_tendency_combine_dev(spdy_plan *p, double *pdiv, double *pspec)
@@ -320,53 +350,33 @@ int spdy_spectral_step_dev(spdy_plan *p, double *pvor, double *pdiv, double *psp
                            double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1, double dt,
                            double eps, double wil, double *phi)
 {
-    NEED_DEVICE(p);
-    if (!p->tab.implicit_ready) return fail(SPDY_ERR_STATE, "spectral_step needs spdy_implicit_init first");
-    if (!p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "spectral_step needs sigma levels");
-    if (!pvor || !pdiv || !pspec || !vor || !div || !t || !tr || !ps || !phis || !d_tcorh || !d_qcorh || !phi)
-        return fail(SPDY_ERR_ARG, "null device pointer");
-    if (j1 != 1 && j1 != 2) return fail(SPDY_ERR_ARG, "j1 must be 1 or 2");
-    const int kx = p->tab.kx;
-    if (kx > 16) {   // the fused kernel holds one level per thread row (64 x kx <= 1024 threads): issue the separate kernels
-        RC(spdy_tendency_combine_dev(p, pdiv, pspec));
-        const size_t L = (size_t)kx * spec_elems(p);
-        double *divdt = pdiv, *tdt = pdiv + L, *trdt = pdiv + 2 * L, *psdt = pspec + 3 * L;
-        RC(spdy_spectral_tendencies_dev(p, div, t, ps, phis, divdt, tdt, psdt, phi));
-        RC(spdy_implicit_terms_dev(p, divdt, tdt, psdt));
-        RC(spdy_hdiff_step_dev(p, vor, div, t, tr, d_tcorh, d_qcorh, sdrag, pvor, divdt, tdt, trdt));
-        const spdy_step_op ops[5] = {{1, ps, psdt}, {kx, vor, pvor}, {kx, div, divdt}, {kx, t, tdt}, {kx, tr, trdt}};
-        return spdy_step_fields_dev(p, 5, ops, j1, dt, eps, wil);
-    }
-    return spectral_step_launch(p, 1, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi, nullptr,
-                                nullptr);
+    const StepFields f{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi};
+    RC(step_args(p, false, 1, "spectral_step", "spectral_step needs spdy_implicit_init first", "spectral_step needs sigma levels",
+                 f.ptrs(), j1));
+    return spectral_step(p, 1, f, nullptr, nullptr);
 }
 
 int spdy_ens_spectral_step_dev(spdy_plan *p, int nmem, double *pvor, double *pdiv, double *pspec, double *vor, double *div, double *t,
                                double *tr, double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,
                                int j1, double dt, double eps, double wil, double *phi)
 {
-    RC(ens_args(p, nmem, "ens_spectral_step", true, true,
-                pvor && pdiv && pspec && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi, j1));
-    NEED_DEVICE(p);
-    if (p->tab.kx > 16)   // (one member: the separate kernels)
-        return spdy_spectral_step_dev(p, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi);
-    return spectral_step_launch(p, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi,
-                                nullptr, nullptr);
+    const StepFields f{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi};
+    RC(step_args(p, true, nmem, "ens_spectral_step", "ens_spectral_step needs spdy_implicit_init first",
+                 "ens_spectral_step needs sigma levels", f.ptrs(), j1));
+    return spectral_step(p, nmem, f, nullptr, nullptr);
 }
 
+// The device, then the spectral step's state, every pointer and j1 are checked before the direct batch is enqueued (its own batch-size
+// checks follow): a call that fails has put nothing on the stream, or into a capture.
 int spdy_direct_batch_spectral_step_dev(spdy_plan *p, const double *ug, const double *vg, const double *grid, int kcos, double *pvor,
                                         double *pdiv, double *pspec, double *vor, double *div, double *t, double *tr, double *ps,
                                         const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag, int j1, double dt,
                                         double eps, double wil, double *phi)
 {
-    NEED_DEVICE(p);
-    const int kx = p->tab.kx, P = 3 * kx;
-    if (!ug || !vg || !grid || !pvor || !pdiv || !pspec) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (use_raw63(p, P) && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi && (j1 == 1 || j1 == 2))
-        return direct_batch_spectral_step(p, 1, ug, vg, grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag,
-                                          j1, dt, eps, wil, phi);
-    RC(spdy_direct_batch_dev(p, P, ug, vg, pvor, pdiv, kcos, P + 1, grid, pspec));
-    return spdy_spectral_step_dev(p, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi);
+    const StepFields f{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi};
+    RC(step_args(p, false, 1, "spectral_step", "spectral_step needs spdy_implicit_init first", "spectral_step needs sigma levels",
+                 ug && vg && grid && f.ptrs(), j1));
+    return direct_batch_spectral_step(p, 1, ug, vg, grid, kcos, f);
 }
 
 int spdy_ens_direct_batch_spectral_step_dev(spdy_plan *p, int nmem, const double *ug, const double *vg, const double *grid, int kcos,
@@ -374,14 +384,10 @@ int spdy_ens_direct_batch_spectral_step_dev(spdy_plan *p, int nmem, const double
                                             double *ps, const double *phis, const double *d_tcorh, const double *d_qcorh, double sdrag,
                                             int j1, double dt, double eps, double wil, double *phi)
 {
-    RC(ens_args(p, nmem, "ens_direct_batch_spectral_step", true, true,
-                ug && vg && grid && pvor && pdiv && pspec && vor && div && t && tr && ps && phis && d_tcorh && d_qcorh && phi, j1));
-    NEED_DEVICE(p);
-    if (p->tab.kx > 16)   // (one member: the separate kernels behind the direct batch)
-        return spdy_direct_batch_spectral_step_dev(p, ug, vg, grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh,
-                                                   sdrag, j1, dt, eps, wil, phi);
-    return direct_batch_spectral_step(p, nmem, ug, vg, grid, kcos, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag,
-                                      j1, dt, eps, wil, phi);
+    const StepFields f{pvor, pdiv, pspec, vor, div, t, tr, ps, phis, d_tcorh, d_qcorh, sdrag, j1, dt, eps, wil, phi};
+    RC(step_args(p, true, nmem, "ens_direct_batch_spectral_step", "ens_direct_batch_spectral_step needs spdy_implicit_init first",
+                 "ens_direct_batch_spectral_step needs sigma levels", ug && vg && grid && f.ptrs(), j1));
+    return direct_batch_spectral_step(p, nmem, ug, vg, grid, kcos, f);
 }
 
 /* ---------------------------------------------------------------- output path */

@@ -49,10 +49,10 @@ struct spdy_plan {
     double *d_radzonal = nullptr;     // [5][il] zonal radiation forcing fsol | ozone | ozupp | zenit | stratz (spdy_radiation_set_date)
     double *d_orog = nullptr;         // phis0 (ix,il) | forog (ix,il) | sqrt(coa(j)) [il] (spdy_surface_set_orography)
     double *physics_ws = nullptr;     // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
-    double *physics_grid = nullptr;   // physics from spectra: (5kx+1) grids u | v | t | q | phi | ln ps, then one state's chain workspace
-                                      // of (3kx+12) grids (spdy_physics_workspace)
-    double *ens_physics_grid = nullptr;   // ensemble physics from spectra: ens_physics_nmem x (5kx+1) grids u | v | t | q | phi (nmem, kx each) |
-    int ens_physics_nmem = 0;             // ln ps (nmem), then the chain workspace of (3kx+12) fields of nmem grids (spdy_ens_physics_workspace)
+    // physics from spectra of nmem states: u | v | t | q | phi (nmem*kx grids each) | ln ps (nmem), then the chain workspace of
+    // (3kx+12) fields of nmem grids.  The chain's part is not scratch: it holds ssrd from one shortwave step to the next, so the
+    // single state and the ensemble each keep their own (spdy_physics_workspace, spdy_ens_physics_workspace)
+    struct PhysicsGrids { double *g = nullptr; int nmem = 0; } physics_grid, ens_physics_grid;
     double *sppt_ws = nullptr;        // SPPT on gridded states: the dynamics tendencies, (2kx+2) grids per state, max_batch states
                                       // (spdy_column_physics_sppt_workspace)
     double *sppt_grid = nullptr;      // SPPT from spectra: one state's (2kx+2) grids (spdy_physics_sppt_workspace)

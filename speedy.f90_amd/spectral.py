@@ -426,11 +426,19 @@ class Spectral(ColumnPhysics):
         self._sync_stream()
         check(self.lib.spdy_implicit_terms_dev(self.h, self._dp(divdt), self._dp(tdt), self._dp(psdt)))
 
+    def _members(self, name, nmem, *args):
+        """The step call spdy_<name>(plan, ...) or, with a member count, its ensemble form spdy_ens_<name>(plan, nmem, ...); args:
+        tensors (or None), and numbers already cast."""
+        self._sync_stream()
+        fn, lead = (getattr(self.lib, "spdy_" + name), ()) if nmem is None else (getattr(self.lib, "spdy_ens_" + name), (int(nmem),))
+        check(fn(self.h, *lead, *[x if isinstance(x, (int, float)) else self._dp(x) for x in args]))
+
+    def _spectral_step(self, name, nmem, lead, fields, sdrag, j1, dt, eps, wil, phi):
+        self._members(name, nmem, *lead, *fields, float(sdrag), int(j1), float(dt), float(eps), float(wil), phi)
+
     def grid_tendencies_dev(self, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out):
         """tendencies.f90:105-197 on the gridded prognostics; outputs are the operands of one direct_batch_dev launch."""
-        self._sync_stream()
-        args = (ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out)
-        check(self.lib.spdy_grid_tendencies_dev(self.h, *[self._dp(x) for x in args]))
+        self._members("grid_tendencies_dev", None, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out)
 
     def tendency_combine_dev(self, pdiv, pspec):
         """In place on the direct batch's outputs: divdt -= laplacian(KE), tdt += ttend, trdt += trtend, psdt(1,1) = 0."""
@@ -440,51 +448,38 @@ class Spectral(ColumnPhysics):
     def spectral_step_dev(self, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh, sdrag, j1, dt, eps, wil, phi):
         """Everything after the direct batch in one launch: tendency_combine, spectral_tendencies, implicit_terms, hdiff_step
         and step_fields of ps, vor, div, t, tr (prognostics [2,kx,nx,mx] / ps [2,nx,mx], both time levels)."""
-        self._sync_stream()
-        args = (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh)
-        check(self.lib.spdy_spectral_step_dev(self.h, *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt), float(eps),
-                                              float(wil), self._dp(phi)))
+        self._spectral_step("spectral_step_dev", None, (), (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh), sdrag, j1, dt,
+                            eps, wil, phi)
 
     def direct_batch_spectral_step_dev(self, ug, vg, grid, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh, sdrag, j1, dt,
                                        eps, wil, phi, kcos=2):
         """direct_batch_dev(ug, vg [3kx] -> pvor, pdiv; grid [3kx+1] -> pspec) + spectral_step_dev as one call (at T63 vds is
         applied where the spectral step reads the pairs' spectra: one launch less)."""
-        self._sync_stream()
-        args = (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh)
-        check(self.lib.spdy_direct_batch_spectral_step_dev(self.h, self._dp(ug), self._dp(vg), self._dp(grid), int(kcos),
-                                                           *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt), float(eps),
-                                                           float(wil), self._dp(phi)))
+        self._spectral_step("direct_batch_spectral_step_dev", None, (ug, vg, grid, int(kcos)),
+                            (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh), sdrag, j1, dt, eps, wil, phi)
 
     # ------------------------------------------------------------------ ensemble time step (layout: ensemble.py)
     def ens_grid_tendencies_dev(self, nmem, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out):
         """grid_tendencies_dev for nmem members in one launch: inputs (nmem, kx) grids each, px, py (nmem); outputs group-major,
         u_out, v_out (3, nmem, kx), plain_out (3, nmem, kx) followed by the nmem level-free fields."""
-        self._sync_stream()
-        args = (ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out)
-        check(self.lib.spdy_ens_grid_tendencies_dev(self.h, int(nmem), *[self._dp(x) for x in args]))
+        self._members("grid_tendencies_dev", nmem, ug, vg, tg, vorg, divg, trg, px, py, u_out, v_out, plain_out)
 
     def ens_spectral_step_dev(self, nmem, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh, sdrag, j1, dt, eps, wil, phi):
         """spectral_step_dev for nmem members in one launch: prognostics (2, nmem, kx, nx, mx) / ps (2, nmem, nx, mx), phi
         (nmem, kx, nx, mx), pvor, pdiv, pspec group-major; phis, tcorh, qcorh are shared."""
-        self._sync_stream()
-        args = (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh)
-        check(self.lib.spdy_ens_spectral_step_dev(self.h, int(nmem), *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt),
-                                                  float(eps), float(wil), self._dp(phi)))
+        self._spectral_step("spectral_step_dev", nmem, (), (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh), sdrag, j1, dt,
+                            eps, wil, phi)
 
     def ens_direct_batch_spectral_step_dev(self, nmem, ug, vg, grid, pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh, sdrag,
                                            j1, dt, eps, wil, phi, kcos=2):
         """direct_batch_spectral_step_dev for nmem members: 3*nmem*kx pairs and 3*nmem*kx + nmem plain fields through one
         direct batch, then ens_spectral_step_dev."""
-        self._sync_stream()
-        args = (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh)
-        check(self.lib.spdy_ens_direct_batch_spectral_step_dev(self.h, int(nmem), self._dp(ug), self._dp(vg), self._dp(grid), int(kcos),
-                                                               *[self._dp(x) for x in args], float(sdrag), int(j1), float(dt),
-                                                               float(eps), float(wil), self._dp(phi)))
+        self._spectral_step("direct_batch_spectral_step_dev", nmem, (ug, vg, grid, int(kcos)),
+                            (pvor, pdiv, pspec, vor, div, t, tr, ps, phis, tcorh, qcorh), sdrag, j1, dt, eps, wil, phi)
 
     def ens_geopotential_dev(self, nmem, t, phis, phi):
         """geopotential_dev for nmem members: t, phi (nmem, kx, nx, mx), phis shared"""
-        self._sync_stream()
-        check(self.lib.spdy_ens_geopotential_dev(self.h, int(nmem), self._dp(t), self._dp(phis), self._dp(phi)))
+        self._members("geopotential_dev", nmem, t, phis, phi)
 
     def output_batch_dev(self, vor, div, t, q, phi, ps, u_out, v_out, t_out, q_out, phi_out, ps_out):
         """input_output.f90:184-206 on device-resident state: complex128 [kx,nx,mx] (ps [nx,mx]) in, float32 [kx,il,ix]
@@ -494,8 +489,7 @@ class Spectral(ColumnPhysics):
         check(self.lib.spdy_output_batch_dev(self.h, *[self._dp(x) for x in args]))
 
     def geopotential_dev(self, t, phis, phi):
-        self._sync_stream()
-        check(self.lib.spdy_geopotential_dev(self.h, self._dp(t), self._dp(phis), self._dp(phi)))
+        self._members("geopotential_dev", None, t, phis, phi)
 
     def spectral_tendencies_dev(self, div, t, ps, phis, divdt, tdt, psdt, phi):
         """tendencies.f90:242-293 -- div, t, ps: time level j2 of the prognostics; divdt, tdt, psdt in place; phi out."""

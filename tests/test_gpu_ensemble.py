@@ -309,3 +309,52 @@ def test_per_member_guard_and_coupling(oracle_factory):
     assert not np.array_equal(got[0][0], got[1][0])
     assert any(not np.array_equal(got[0][1][k], got[1][1][k]) for k in sm.FIELDS)
     sp.close()
+
+
+def test_single_state_and_ensemble_interleaved_on_one_plan(oracle_factory):
+    """T30 L8: a single state (modelstep.step with spdy_physics_dev) and an ensemble of E = 2 (Ensemble.step, physics on) take turns on
+    ONE plan for three steps, shortwave on the first only, no ssrd supplied through `out` on either side: step n of the single state,
+    step n of the ensemble, step n + 1 of the single state, ...  The single state's prognostics and PL after every step, and every
+    member after every step, are bit-equal to the same steps run alone on a fresh plan.  The physics from spectra of the two forms
+    is one body, but each form keeps a workspace of its own, and the held ssrd lives there between shortwave steps: a shared
+    workspace would hand the one run the other's ssrd on steps 2 and 3.  All three states differ."""
+    import radiation
+    E, dt = 2, physstep.DT["t30"]
+    sp, o = _plan("t30", E), oracle_factory("t30")
+    sts, bnds = _physics_members(sp, o, E + 1)               # members 0, 1; the single state is the third
+    phis0 = o.spec_to_grid(sts[0]["phis"], 1)
+
+    def run(sp, single, ensemble):
+        sp.initialize_implicit(dt)
+        D, W, P1 = modelstep.device_state(sts[E]), modelstep.Workspace(sp), modelstep.physics_buffers(sp, bnds[E])
+        ens, P = es.build(sp, sts[:E]), _ens_physics(sp, bnds[:E])
+        one, many = [], []
+        for n in range(3):
+            if single:
+                modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P1, n == 0))
+                sp.synchronize()
+                one.append(modelstep.snapshot(D, W, P1))
+            if ensemble:
+                ens.step(2, 2, dt, dict(P, sw=n == 0), eps=ROB)
+                sp.synchronize()
+                many.append(dict(es.snapshot(ens), rad=P["rad"].clone()))
+        return one, many
+
+    one, many = run(sp, True, True)
+    sp.close()
+    alone = {}
+    for which in ("single", "ensemble"):
+        sp = _plan("t30", E)
+        sp.radiation_set_date(radiation.DATES[0])
+        sp.surface_set_orography(phis0)
+        alone[which] = run(sp, which == "single", which == "ensemble")[which == "ensemble"]
+        sp.close()
+    assert np.isfinite(one[-1]["vor"].cpu().numpy()).all() and np.isfinite(many[-1]["vor"].cpu().numpy()).all()
+    for n in range(3):
+        bad = [k for k in one[n] if not es.same_bits(one[n][k], alone["single"][n][k])]
+        assert bad == [], ("single state", n, bad)
+        for e in range(E):
+            got, want = es.member_of(many[n], e), es.member_of(alone["ensemble"][n], e)
+            bad = [k for k in es.COMPARED if not es.same_bits(got[k], want[k])]
+            assert bad == [], ("member", e, n, bad)
+        assert es.same_bits(many[n]["rad"], alone["ensemble"][n]["rad"]), ("radiation states", n)
