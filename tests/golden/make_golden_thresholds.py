@@ -37,6 +37,7 @@ import make_golden_moist as mg  # noqa: E402
 import make_golden_radiation as mr  # noqa: E402
 import make_golden_surface as ms  # noqa: E402
 import moist  # noqa: E402
+import physlevels  # noqa: E402
 import radiation  # noqa: E402
 import surface  # noqa: E402
 import synth  # noqa: E402
@@ -93,10 +94,7 @@ def reference_call(lib, c, sw, held, il, ix, kx):
 
 
 def init(tag, lib):
-    ix, il, kx = moist.VARIANTS[tag]
-    tab = moist.tables(moist.HSG[kx])
-    f = lambda a: np.asfortranarray(a, np.float64)
-    lib.moist_init(ctypes.c_int(1 if kx == 16 else 0), P(f(tab["hsg"])), P(f(tab["dhs"])), P(f(tab["fsg"])))
+    ix, il, kx, tab = mg.init_levels(tag, lib)
     lib.rad_tables(P(np.zeros((4, 301))))
     t = [np.zeros(6)] + [np.zeros(kx) for _ in ms.TABLES[1:]]
     lib.sfc_tables(*[P(x) for x in t])
@@ -111,8 +109,10 @@ def date(lib, tyear, il, ix):
     return {n: z[n][:, 0].copy() for n in mr.ZON}
 
 
-def run(tag, lib):
-    ix, il, kx = moist.VARIANTS[tag]
+def run(tag, lib, seed=None):
+    """seed: the thresholds.build seed of a variant outside thresholds.TAGS whose constructed columns are wanted all the same
+    (make_golden_physlevels.py)"""
+    ix, il, kx, _, _ = physlevels.variant(tag)
     ncol = il * ix
     tab = init(tag, lib)
     d = {tag + "_tyear": np.array(TYEARS)}
@@ -121,13 +121,14 @@ def run(tag, lib):
     d[tag + "_year_digest"] = np.array(synth.digest(year))
     if tag in ("t30", "t63k16"):
         d[tag + "_year"] = year
-    if tag not in th.TAGS:
+    if tag not in th.TAGS and seed is None:
         return d
+    seed = th.SEED[tag] if seed is None else seed
     coa = np.zeros(il)
     lib.sfc_coa(P(coa))
     sqcoa = np.repeat(np.sqrt(coa), ix)
     zon = radiation.zonal_columns(date(lib, radiation.DATES[0], il, ix), 1, il, ix)
-    c, sub, r1, r2 = th.build(tab, ncol, th.SEED[tag], zon, sqcoa)
+    c, sub, r1, r2 = th.build(tab, ncol, seed, zon, sqcoa)
     H = th.hits(tab, c, r1, zon)
     for row in th.CLASS_I:
         for side in row["sides"]:
@@ -149,7 +150,7 @@ def run(tag, lib):
                 continue
             d["%s_c%d_%s" % (tag, step, n)] = v[kx - 1, sub] if n in ("utend", "vtend") else v[..., sub]
     print("%s: %d stored columns, restatement against the reference worst %.1e" % (tag, sub.size, worst))
-    d[tag + "_seed"] = np.int64(th.SEED[tag])
+    d[tag + "_seed"] = np.int64(seed)
     d[tag + "_sub"] = sub
     d[tag + "_forog"] = forog.reshape(-1)[sub]
     d[tag + "_in_names"] = np.array(INPUTS)

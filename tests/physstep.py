@@ -77,20 +77,22 @@ def columns_of(g, bnd, phis0, ut, vt, tt, qt):
 class Case:
     """One resolution's plan-independent reference data: tables, state, orography, zonal forcing, boundary fields."""
 
-    def __init__(self, tag, sp, o, date=0, st=None, bnd=None):
+    def __init__(self, tag, sp, o, date=0, st=None, bnd=None, hsg=None, seeds=None):
         """st, bnd: a given state (the orography is its phis on the grid) and the boundary fields to use with it as they are;
-        without them both are drawn from SEEDS[tag]"""
+        without them both are drawn from seeds (default SEEDS[tag]).  hsg: the half levels of sp and o where they are not
+        moist.HSG's (a plan of tests/levels.py)"""
         self.tag, self.o = tag, o
         self.kx, self.il, self.ix = o.kx, o.il, o.ix
-        self.tab = moist.tables(moist.HSG[self.kx])
-        self.st = moist.state(o, dyn_state(sp, SEEDS[tag][0]), SEEDS[tag][1]) if st is None else st
+        self.tab = moist.tables(moist.HSG[self.kx] if hsg is None else hsg)
+        seeds = SEEDS[tag] if seeds is None else seeds
+        self.st = moist.state(o, dyn_state(sp, seeds[0]), seeds[1]) if st is None else st
         self.phis0 = o.spec_to_grid(self.st["phis"], 1)
         self.sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, self.il, self.ix)
         self.set_date(sp, date)
         if bnd is not None:
             self.bnd = bnd
             return
-        sb = SEEDS[tag][2]
+        sb = seeds[2]
         g = grids_of(o, self.st)
         zero = np.zeros((self.kx, self.il, self.ix))
         self.bnd = draw_boundary(g["tg"][-1].reshape(-1), sb)

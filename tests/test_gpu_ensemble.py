@@ -133,10 +133,11 @@ def test_member_zero_against_oracle(oracle_factory):
 
 
 # ---------------------------------------------------------------------------------------------- with the whole physics
-def _physics_members(sp, o, E):
-    """E physically shaped states over member 0's orography, per-member boundary fields; member 0 is physstep's own case"""
-    case = physstep.Case("t30", sp, o)
-    d0, m0, b0 = physstep.SEEDS["t30"]
+def _physics_members(sp, o, E, hsg=None, seeds=None):
+    """E physically shaped states over member 0's orography, per-member boundary fields; member 0 is physstep's own case.  hsg,
+    seeds: the half levels of sp and o and the case's seeds at a count of tests/levels.py"""
+    d0, m0, b0 = seeds = physstep.SEEDS["t30"] if seeds is None else seeds
+    case = physstep.Case("t30", sp, o, hsg=hsg, seeds=seeds)
     sts, bnds = [case.st], [case.bnd]
     for e in range(1, E):
         st = moist.state(o, es.dyn_state(sp, d0 + 1000 * e), m0 + 10 * e)

@@ -20,10 +20,15 @@ pytestmark = pytest.mark.gpu
 TEND = ("utend", "vtend", "ttend", "qtend")
 
 
-def _plan_case(tag, oracle_factory):
-    kx = VARIANTS[tag][3]
-    sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
-    case = physstep.Case(tag, sp, o)
+def _plan_case(tag, oracle_factory, levels_case=None):
+    """levels_case: (sp, o, half levels, physstep.Case seeds) of a count outside conftest.VARIANTS (tests/levels.py)"""
+    if levels_case is None:
+        kx = VARIANTS[tag][3]
+        sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
+        case = physstep.Case(tag, sp, o)
+    else:
+        sp, o, hsg, seeds = levels_case
+        kx, case = sp.kx, physstep.Case(tag, sp, o, hsg=hsg, seeds=seeds)
     sp.surface_set_orography(case.phis0)
     return sp, o, case, kx
 
@@ -44,8 +49,12 @@ def test_physics_from_spectra(tag, oracle_factory):
     """spdy_physics_dev on a shortwave call and a call without shortwave on the held state: the four tendencies, every optional
     output of every block and the radiation state against the reference within TOL, integers identical.
     Measured on MI355X: worst 4.3e-14 (t30), 8.8e-14 (t63k16) over 68 arrays."""
+    check_physics_from_spectra(tag, *_plan_case(tag, oracle_factory))
+
+
+def check_physics_from_spectra(tag, sp, o, case, kx):
+    """the body of test_physics_from_spectra on a plan, its oracle and their physstep.Case; returns the worst (array, error)"""
     import torch
-    sp, o, case, kx = _plan_case(tag, oracle_factory)
     il, ix = sp.il, sp.ix
     st = case.st
     phi = o.geopotential(st["t"][0], st["phis"])
@@ -81,15 +90,22 @@ def test_physics_from_spectra(tag, oracle_factory):
                                                                              ", ".join("%s %.1e" % kv for kv in top[:8])))
     assert top[0][1] <= TOL, top[0]
     sp.close()
+    return top[0]
 
 
-def _gridded(tag, nb, seed):
-    """nb gridded states of surface.columns with the plan that holds their date and orography"""
+def _gridded(tag, nb, seed, plan=None, keep=None):
+    """nb gridded states of surface.columns with the plan that holds their date and orography.  plan: (sp, its half levels) of a
+    count outside moist.VARIANTS (tests/levels.py), used in place of the plan of tag.  keep: a dict that receives the reference
+    side of the states (tab, zon, sqcoa, and the columns c1, c2 of the two calls)"""
     import torch
-    ix, il, kx = moist.VARIANTS[tag]
-    sp = moist.plan(tag, 64)
+    if plan is None:
+        ix, il, kx = moist.VARIANTS[tag]
+        sp, hsg = moist.plan(tag, 64), moist.HSG[kx]
+    else:
+        sp, hsg = plan
+        ix, il, kx = sp.ix, sp.il, sp.kx
     sp.radiation_set_date(radiation.DATES[0])
-    tab = moist.tables(moist.HSG[kx])
+    tab = moist.tables(hsg)
     zon = radiation.zonal_columns({n: sp.table(n) for n in physstep.ZON}, nb, il, ix)
     sqcoa = surface.sqcoa_columns(sp.table("coa_half"), nb, il, ix)
     c = surface.columns(tab, nb * il * ix, seed, zon, sqcoa)
@@ -99,6 +115,8 @@ def _gridded(tag, nb, seed):
     G = lambda a: moist.dev(radiation.grids(a, nb, il, ix))
     c2 = dict(c, tg=c["tg2"], ug=c["vg"], vg=c["ug"], sst=c["sst"] + 0.5, stl=c["stl"] - 0.5, ttend=c["ttend2"])
     names = ("ug", "vg", "tg", "qg", "phig", "pslg", "albsfc") + TEND + surface.BOUNDARY
+    if keep is not None:
+        keep.update(tab=tab, zon=zon, sqcoa=sqcoa, c1=c, c2=c2)
     return sp, kx, il, ix, {n: G(c[n]) for n in names}, {n: G(c2[n]) for n in names}
 
 

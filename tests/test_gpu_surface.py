@@ -27,12 +27,17 @@ def _close(got, want, key):
     return e
 
 
-def _case(tag, seed, nb=1, date=0):
-    """(plan with date and no orography yet, tables, columns, zonal and sqrt(coa) per column)"""
-    ix, il, kx = moist.VARIANTS[tag]
-    sp = moist.plan(tag, 64)
+def _case(tag, seed, nb=1, date=0, plan=None):
+    """(plan with date and no orography yet, tables, columns, zonal and sqrt(coa) per column).  plan: (sp, its half levels) of a
+    count outside moist.VARIANTS (tests/levels.py), used in place of the plan of tag"""
+    if plan is None:
+        ix, il, kx = moist.VARIANTS[tag]
+        sp, hsg = moist.plan(tag, 64), moist.HSG[kx]
+    else:
+        sp, hsg = plan
+        ix, il = sp.ix, sp.il
     sp.radiation_set_date(radiation.DATES[date])
-    tab = moist.tables(moist.HSG[kx])
+    tab = moist.tables(hsg)
     zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, nb, il, ix)
     sqcoa = surface.sqcoa_columns(sp.table("coa_half"), nb, il, ix)
     c = surface.columns(tab, nb * il * ix, seed, zon, sqcoa)

@@ -139,16 +139,22 @@ def test_threshold_columns_on_device(tag):
     """Measured on MI355X, worst per-column error per block (t30 / t30k5): against the reference moist 9.4e-15 / 2.4e-15 (precls),
     rad 1.4e-15 / 4.1e-16, sfc 3.9e-16 / 2.1e-15, pbl and tendencies 1.6e-16 / 1.1e-15; every column against the restatement
     moist 1.9e-13 / 3.5e-14 (precls), rad 2.7e-14 / 2.1e-14, sfc 2.8e-15 / 3.8e-15, pbl and tendencies 1.3e-15 / 2.9e-15."""
-    import torch
     ref = np.load(os.path.join(GOLDEN, "ref_thresholds.npz"))
     ix, il, kx = moist.VARIANTS[tag]
-    tab = moist.tables(moist.HSG[kx])
-    sp = moist.plan(tag, 4)
+    check_threshold_columns(tag, moist.plan(tag, 4), moist.tables(moist.HSG[kx]), int(ref[tag + "_seed"]), ref[tag + "_sub"],
+                            lambda step: _stored(ref, tag, step))
+
+
+def check_threshold_columns(tag, sp, tab, seed, ref_sub, stored):
+    """the body of test_threshold_columns_on_device on a plan sp with the tables tab of its levels: thresholds.build(seed), whose
+    stored columns are ref_sub; stored(step) gives the fixture's outputs of call 1 / 2 by name"""
+    import torch
+    ix, il, kx = sp.ix, sp.il, sp.kx
     sp.radiation_set_date(radiation.DATES[0])
     zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
     sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, il, ix)
-    c, sub, r1, r2 = th.build(tab, il * ix, int(ref[tag + "_seed"]), zon, sqcoa)
-    assert np.array_equal(sub, ref[tag + "_sub"])
+    c, sub, r1, r2 = th.build(tab, il * ix, seed, zon, sqcoa)
+    assert np.array_equal(sub, ref_sub)
     sp.surface_set_orography(c["phis0"].reshape(il, ix))
     c2 = th.second(c)
     calls = [(_dev(c, il, ix), True), (_dev(c2, il, ix), False)]
@@ -166,7 +172,7 @@ def test_threshold_columns_on_device(tag):
     for step, cc, r in ((1, c, r1), (2, c2, r2)):
         got = {n[2:]: v for n, v in one.items() if n.startswith("%d." % step) and not n.endswith("state")}
         sc = th.scales(tab, cc, r)
-        _against(got, _stored(ref, tag, step), kx, sc, sub, True, "call %d vs reference" % step, worst_ref)
+        _against(got, stored(step), kx, sc, sub, True, "call %d vs reference" % step, worst_ref)
         mine = th.flat(r, kx)
         if step == 2:
             mine = {n: v for n, v in mine.items() if n not in th.SW_ONLY}
