@@ -12,7 +12,9 @@
  *        grid  g(ix,il)            ix*il doubles, longitude fastest, j=1 southernmost
  *        spec  s(mx,nx) complex    mx*nx (re,im) pairs, zonal wavenumber index fastest
  *        four  f(2*mx,il)          re/im interleaved Fourier coefficients per latitude
- *    A batch of nb fields is nb such arrays back to back (e.g. a (mx,nx,kx) level stack).
+ *    A batch of nb fields is nb such arrays back to back (e.g. a (mx,nx,kx) level stack).  An output field depends on the
+ *    inputs the reference reads for that field and on nothing else the batch holds, non-finite values included: a NaN, an
+ *    infinity or an overflow in one field -- or in an entry the reference never reads -- changes no bit of another field.
  *  - Functions without suffix take HOST pointers: they copy in, run the HIP kernels, copy out
  *    and synchronise (signature-compatible with the reference, PCIe-bound).
  *    Functions ending in _dev take DEVICE pointers, are asynchronous on the plan's stream and
@@ -306,7 +308,10 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *plan, const double *d_ug, con
  * takes them.  Member e of the column kernels works on level slot e*kx + k, its level-free slot is 3*nmem*kx + e.  The kernels are
  * those of the single-state calls with the member in blockIdx.y: same expressions, same order, and with nmem = 1 the same
  * addresses, so a member's results do not depend on the ensemble it travels in wherever the transforms' do not (T30: bit for
- * bit; T63: the pairs' spectra to rounding where the launch form differs, see spdy_direct_batch_spectral_step_dev).
+ * bit; T63: the pairs' spectra to rounding where the launch form differs, see spdy_direct_batch_spectral_step_dev).  Members are
+ * fields of those batches and states of the column physics, so the contract of a batch (Conventions) holds between them: what one
+ * member holds, non-finite values included, changes no bit of another member, of its radiation state, surface-model fields or
+ * guard rows; a member that goes non-finite is flagged by the guard (SPDY_DIAG_NONFINITE) and the others run on.
  *   spdy_ens_grid_tendencies_dev / _spectral_step_dev / _geopotential_dev   the single-state calls for nmem members, one launch
  *   spdy_ens_direct_batch_spectral_step_dev   ONE direct batch of all members, then the spectral step; the routes of the
  *       single-state call (T63: the raw pairs' spectra in the plan's temporaries) where the batch fits them, silently the plain

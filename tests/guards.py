@@ -94,27 +94,50 @@ def route(tag, direction, nb, num_cu, pairs=False, max_batch=None):
         T63 s2g: "chunk_wt" / "chunk" (one (pair, chunk) item per workgroup step, written through or not), "stream", "resident"
         T63 g2s: "staged" (row FFTs, then the contraction), "split" (two workgroups per pair), "stream", "resident"
     A T30 tile is 2 plain fields or 1 pair; a T63 work unit is a field pair (pairs: two segments of nb fields, 2 ceil(nb/2) units)."""
-    nwg = max_wg(tag, num_cu)
     fields = 2 * nb if pairs else nb
+    if tag == "t30":
+        return route_units(tag, direction, nb if pairs else (nb + 1) // 2, fields, num_cu)
+    units = 2 * ((nb + 1) // 2) if pairs else (nb + 1) // 2     # T63 pairs: one segment per member, each (nb + 1) / 2 units
+    # (vdspec: the staged form takes the pairs as ONE segment)
+    return route_units(tag, direction, units, fields, num_cu, staged_units=nb if pairs else units, max_batch=max_batch)
+
+
+def route_units(tag, direction, units, fields, num_cu, staged_units=None, max_batch=None):
+    """route() for a launch given by its work units (T30 tiles, T63 field pairs) and the fields of grids it reads or writes --
+    what a mixed launch (pairs, plain segments and a gradient together) comes to.  staged_units: the units of the T63 direct
+    launch as the staged form would take it (vdspec pairs one unit each), where that differs."""
+    nwg = max_wg(tag, num_cu)
     gbytes = fields * GRID_BYTES[tag]
     stream = gbytes >= STREAM_MIN
     if tag == "t30":
-        tiles = nb if pairs else (nb + 1) // 2
+        tiles = units
         if direction == "s2g":
             return "part" if 3 * tiles <= nwg and not stream else "stream" if stream else "resident"
         return "split" if 6 * tiles <= nwg and not stream else "stream" if stream else "resident"
-    units = 2 * ((nb + 1) // 2) if pairs else (nb + 1) // 2     # T63 pairs: one segment per member, each (nb + 1) / 2 units
     if direction == "s2g":
         if 2 * units <= nwg:
             return "chunk_wt" if gbytes >= WT_MIN else "chunk"
         return "stream" if stream else "resident"
     rows_ws = min(3 * max_batch + 2, 258)                        # the plan's row workspace (csrc/spdy_api.hip, upload_all)
     staged = lambda u: 2 * u <= rows_ws and 3 * u <= nwg
-    if staged(nb if pairs else units):                           # (vdspec: the staged form takes the pairs as ONE segment)
+    if staged(units if staged_units is None else staged_units):
         return "staged"
     if 2 * units <= nwg:
         return "split"
     return "stream" if stream else "resident"
+
+
+def mixed_units(tag, direction, npairs, plain, ngrad=0):
+    """(units, fields, staged_units) of ONE mixed launch for route_units: npairs operator pairs, plain segments of `plain` fields
+    each (a tuple; the direct batch has one) and ngrad gradients (csrc/spdy_api.hip: inverse_batch, direct_batch).  T30 tiles: a
+    pair or a gradient each, two plain fields of the concatenated segments.  T63 units: pairs formed inside each segment -- the
+    operator pairs and the gradient are two segments each; the staged direct form takes the (u, v) pairs as one unit each."""
+    half = lambda n: (n + 1) // 2
+    fields = 2 * (npairs + ngrad) + sum(plain)
+    if tag == "t30":
+        return npairs + ngrad + half(sum(plain)), fields, None
+    units = 2 * half(npairs) + 2 * half(ngrad) + sum(half(n) for n in plain)
+    return units, fields, (npairs + sum(half(n) for n in plain) if direction == "g2s" else None)
 
 
 def pin_launch_options(sp):

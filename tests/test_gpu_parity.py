@@ -137,6 +137,33 @@ def test_inactive_coefficients_are_ignored(plans, oracle_factory):
     for fused in (1, 0):
         sp.set_fused(fused)
         ok(sp.spec_to_grid(junk, 1), ref)
+    # ... and the same with NON-FINITE values there, which a kernel that reads such an entry and multiplies it by a zero operand
+    # does not survive (1e300 * 0 is 0, NaN * 0 is not): the output has the BITS of the clean run.  T30 and T63, fused and
+    # four-kernel, three fields (a partial T30 tile, an odd T63 pair); legendre_inv and fourier_inv on their own.  (Every inverse
+    # launch form and the plain segments of the mixed call: test_gpu_isolation.py::test_dead_entries_every_inverse_form.)
+    nan, inf = float("nan"), float("inf")
+    for tag in TAGS:
+        sp, o = plans(tag), oracle_factory(tag)
+        S = synth.spectra(3, sp.trunc, first=5, full_rows=True)
+        dead = np.add.outer(np.arange(sp.nx), np.arange(sp.mx)) > sp.trunc + 1
+        variants = []
+        for fill in (complex(nan, nan), complex(inf, -inf)):
+            junk = S.copy(); junk[:, dead] = fill
+            variants.append(junk)
+        junk = S.copy(); junk.imag[:, :, 0] = nan
+        variants.append(junk)
+        for fused in (1, 0):
+            sp = plans(tag, fused=fused)
+            clean = sp.spec_to_grid(S, 2)
+            ok(clean[1], o.spec_to_grid(S[1], 2))
+            for i, junk in enumerate(variants):
+                got = sp.spec_to_grid(junk, 2)
+                assert got.tobytes() == clean.tobytes(), (tag, fused, i)
+            clean = sp.legendre_inv(S)
+            for i, junk in enumerate(variants[:2]):               # (Im(m' = 0) is an output of this stage: fourier_inv drops it)
+                assert sp.legendre_inv(junk).tobytes() == clean.tobytes(), (tag, fused, "legendre_inv", i)
+            four = clean.copy(); four[:, :, 1] = nan              # Im(m' = 0) of every row (fourier.f90:34-36)
+            assert sp.fourier_inv(four, 2).tobytes() == sp.fourier_inv(clean, 2).tobytes(), (tag, fused, "fourier_inv")
 
 
 def test_max_batch_enforced(plans):

@@ -4,7 +4,8 @@ a vector-memory store of more than 64 bits whose data VGPRs are written again be
 last lanes of each 16-lane row are read late: with one wait state -- all the compiler (ROCm 7.2) inserts, and none for a buffer
 store with an SGPR soffset -- tools/store_valu_hazard.hip still finds wrong dwords; with two it finds none.
 
-    python tools/scan_store_hazard.py [file.s ...]      (default: compiles csrc/spdy_kernels.hip and csrc/spdy_step.hip to ISA)
+    python tools/scan_store_hazard.py [file.s ...]      (default: compiles every kernel file of libspdy.so to ISA -- csrc/*.hip
+                                                         without the host-only spdy_api*.hip -- with the Makefile's HIPFLAGS)
 Reports every (kernel, store, offending instruction) with fewer than WAIT wait states in between."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,16 +59,35 @@ def scan(path):
             window.append((regs(datatok), 0, s, ln))
     return nstores, found
 
+def make_var(name):
+    """the value speedy.f90_amd/Makefile gives a variable"""
+    mk = os.path.join(ROOT, "speedy.f90_amd")
+    return subprocess.check_output(["make", "-s", "--no-print-directory", "-C", mk, "--eval", "scan-print-var: ; @echo $(%s)" % name,
+                                    "scan-print-var"], text=True).strip()
+
+def kernel_sources():
+    csrc = os.path.join(ROOT, "speedy.f90_amd", "csrc")
+    return sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hip") and not f.startswith("spdy_api"))
+
+def compile_isa(tmp):
+    """device assembly of every kernel file, with the flags libspdy.so is built with"""
+    from concurrent.futures import ThreadPoolExecutor
+    hipcc, flags = make_var("HIPCC"), make_var("HIPFLAGS").split()
+    def one(src):
+        out = os.path.join(tmp, os.path.basename(src)[:-4] + ".s")
+        subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "--no-gpu-bundle-output", "-S", src, "-o", out])
+        return out
+    with ThreadPoolExecutor(max_workers=min(4, os.cpu_count() or 1)) as pool:
+        return list(pool.map(one, kernel_sources()))
+
 def main():
     files = sys.argv[1:]
-    tmp = None
     if not files:
-        tmp = tempfile.mkdtemp(prefix="scan_isa_")
-        for src in ("spdy_kernels", "spdy_step"):
-            out = os.path.join(tmp, src + ".s")
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-w", "--cuda-device-only", "--no-gpu-bundle-output",
-                                   "-S", os.path.join(ROOT, "speedy.f90_amd", "csrc", src + ".hip"), "-o", out])
-            files.append(out)
+        with tempfile.TemporaryDirectory(prefix="scan_isa_") as tmp:
+            return report(compile_isa(tmp))
+    return report(files)
+
+def report(files):
     total = 0
     for f in files:
         n, found = scan(f)
