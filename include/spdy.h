@@ -502,6 +502,36 @@ int spdy_output_workspace(spdy_plan *plan);
 int spdy_output_batch_dev(spdy_plan *plan, const double *vor, const double *div, const double *t, const double *q, const double *phi,
                           const double *ps, float *u_out, float *v_out, float *t_out, float *q_out, float *phi_out, float *ps_out);
 
+/* ---- ensemble output: every member's snapshot, the ensemble mean and the spread, in one call ----------------
+ * spdy_output_batch_dev for the nmem members of an ensemble ("ensemble time step" above: layout) and, from the same grid values,
+ * the statistics an ensemble is run for.  Inputs: time level 1 of the ensemble, vor .. phi (mx,nx,kx,nmem) complex, ps
+ * (mx,nx,nmem); phi is the caller's, as in the single-state call.  Outputs, float: the fields of `members` (ix,il,kx,nmem), its ps
+ * (ix,il,nmem); the fields of `mean` and `spread` (ix,il,kx), their ps (ix,il).  Each of the three structs may be NULL = that
+ * group is not wanted; at least one must be given, and inside a given struct all six pointers are required (8-byte aligned).
+ * Per grid point, level and quantity, with x_e the FP64 value of member e -- u, v, t as they are, q * (double)1.0e-3f, phi / grav,
+ * (double)1.e+5f * exp(ps), the expressions of spdy_output_batch_dev --
+ *     members   (float)x_e: the bits of spdy_output_batch_dev on the same grid value; written for every member
+ *     mean      (sum x_e) / n                              over the n members in use, in FP64, rounded to float at the store
+ *     spread    sqrt(sum (x_e - mean)^2 / (n - 1))         the sample standard deviation; n = 1: +0; n = 0: NaN, as the mean
+ * d_use: NULL = all members, or nmem ints on the device, non-zero = the member is in use.  A member not in use is skipped by a
+ * select, never multiplied by zero: it may hold NaN or inf and the statistics are, bit for bit, those of the ensemble without it.
+ * The spread is formed in two passes (the sum, then the squared deviations from the finished mean), sequentially in ascending
+ * member order, without atomics: results are bit-reproducible, and x_e near 288 with a spread of 1e-6 loses nothing.
+ * Two launches' worth of work: ONE inverse batch of all members (nmem*kx pairs, the segments t | q | phi of nmem*kx fields and ps
+ * of nmem, read in place: no gather copy) into the workspace of (5 kx + 1) nmem grids, then one epilogue kernel.
+ * spdy_ens_output_workspace(nmem) allocates the workspace (not possible during a capture; a larger nmem later allocates anew);
+ * the call itself can be captured.  Checks, in this order: a NULL plan, nmem < 1, max_batch < nmem*(3*kx+1) SPDY_ERR_ARG; a NULL
+ * required pointer or no output group SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last.  A failing call enqueues nothing. */
+typedef struct {                      /* one group of output fields: device pointers, all six required                          */
+    float *u, *v, *t, *q, *phi;       /* (ix,il,kx), as `members` (ix,il,kx,nmem)                                               */
+    float *ps;                        /* (ix,il), as `members` (ix,il,nmem)                                                     */
+} spdy_output_fields;
+int spdy_ens_output_workspace(spdy_plan *plan, int nmem);
+int spdy_ens_output_batch_dev(spdy_plan *plan, int nmem, const double *vor, const double *div, const double *t,
+                              const double *q, const double *phi, const double *ps, const int *d_use,
+                              const spdy_output_fields *members, const spdy_output_fields *mean,
+                              const spdy_output_fields *spread);
+
 /* Column physics (spdy_moist_columns_dev, spdy_moist_physics_dev, spdy_radiation_down_dev, spdy_radiation_up_dev,
  * spdy_surface_fluxes_dev, spdy_pbl_dev, spdy_column_physics_dev, spdy_physics_dev) checks its arguments in one order, and the first check that
  * fails gives the code: a NULL plan, kx outside [5, 16] and nb outside [0, max_batch] SPDY_ERR_ARG; no sigma levels, then

@@ -113,6 +113,8 @@ SIGNATURES = {
     "spdy_ens_physics_dev": [c_void_p, c_int, c_int] + [c_void_p] * 14,
     "spdy_output_workspace": [c_void_p],
     "spdy_output_batch_dev": [c_void_p] * 13,
+    "spdy_ens_output_workspace": [c_void_p, c_int],
+    "spdy_ens_output_batch_dev": [c_void_p, c_int] + [c_void_p] * 10,
     "spdy_moist_columns_dev": [c_void_p, c_int] + [c_void_p] * 7,
     "spdy_moist_workspace": [c_void_p],
     "spdy_moist_physics_dev": [c_void_p] * 8,

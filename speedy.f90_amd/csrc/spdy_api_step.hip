@@ -4,6 +4,7 @@
 // the single-state call and its ensemble form are one argument check (step_args) and one call of it, with nmem = 1 or nmem.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -99,6 +100,16 @@ int direct_batch_spectral_step(spdy_plan *p, int nmem, const double *ug, const d
     RC(raw ? direct_batch_raw63(p, P, ug, vg, kcos, P + nmem, grid, f.pspec)
            : spdy_direct_batch_dev(p, P, ug, vg, f.pvor, f.pdiv, kcos, P + nmem, grid, f.pspec));
     return spectral_step(p, nmem, f, raw ? p->tmp_c : nullptr, raw ? p->tmp_d : nullptr);   // (they exist once the raw batch is enqueued)
+}
+
+// the first checks of the two ensemble output calls: what needs no device
+int ens_output_members(const spdy_plan *p, int nmem)
+{
+    NEED_PLAN(p);
+    if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_output: nmem=%d < 1", nmem);
+    const long need = (long)nmem * (3 * p->tab.kx + 1);
+    if (p->max_batch < need) return fail(SPDY_ERR_ARG, "ens_output: max_batch=%d must be >= nmem*(3*kx+1)=%ld", p->max_batch, need);
+    return SPDY_OK;
 }
 }  // namespace
 
@@ -434,6 +445,56 @@ int spdy_output_batch_dev(spdy_plan *p, const double *vor, const double *div, co
         c.src[i] = p->out_grid + (size_t)i * kx * gs; c.dst[i] = dst[i];
     }
     KERNEL(spdy::launch_output_cast(p->dev, c, p->stream));
+    return SPDY_OK;
+}
+
+/* ---------------------------------------------------------------- ensemble output (include/spdy.h, "ensemble output") */
+int spdy_ens_output_workspace(spdy_plan *p, int nmem)
+{
+    RC(ens_output_members(p, nmem));
+    NEED_DEVICE(p);
+    if (p->ens_out_grid.nmem >= nmem) return SPDY_OK;
+    NOT_CAPTURING(p, "allocating the ensemble output workspace (call spdy_ens_output_workspace before the capture)");
+    RC(ensure_four(p));   // the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
+    // a smaller earlier workspace stays with the plan until it is destroyed: a captured graph may still point into it
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(5 * p->tab.kx + 1) * grid_elems(p) * nmem * sizeof(double), &ptr));
+    p->ens_out_grid = {static_cast<double *>(ptr), nmem};
+    return SPDY_OK;
+}
+
+int spdy_ens_output_batch_dev(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q,
+                              const double *phi, const double *ps, const int *d_use, const spdy_output_fields *members,
+                              const spdy_output_fields *mean, const spdy_output_fields *spread)
+{
+    RC(ens_output_members(p, nmem));
+    if (!vor || !div || !t || !q || !phi || !ps) return fail(SPDY_ERR_ARG, "null device pointer");
+    if (!members && !mean && !spread) return fail(SPDY_ERR_ARG, "ens_output: no output group (members, mean, spread all NULL)");
+    spdy::EnsOutput c{};
+    const spdy_output_fields *grp[3] = {members, mean, spread};
+    float **dst[3] = {c.members, c.mean, c.spread};
+    for (int g = 0; g < 3; ++g) {
+        if (!grp[g]) continue;
+        float *f[6] = {grp[g]->u, grp[g]->v, grp[g]->t, grp[g]->q, grp[g]->phi, grp[g]->ps};
+        for (int i = 0; i < 6; ++i) {
+            if (!f[i]) return fail(SPDY_ERR_ARG, "null device pointer");
+            if (reinterpret_cast<uintptr_t>(f[i]) % 8) return fail(SPDY_ERR_ARG, "ens_output: output fields must be 8-byte aligned");
+            dst[g][i] = f[i];
+        }
+    }
+    RC(spdy_ens_output_workspace(p, nmem));
+    // time level 1 of all members to the grid as ONE inverse batch, read in place: nmem*kx pairs, the segments t | q | phi | ps
+    const int kx = p->tab.kx, nk = nmem * kx;
+    const size_t L = (size_t)nk * grid_elems(p);
+    double *ug = p->ens_out_grid.g, *vg = ug + L, *tg = ug + 2 * L;
+    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{nk, t}, {nk, q}, {nk, phi}, {nmem, ps}};
+    RC(spdy_inverse_batch_segs_dev(p, nk, vor, div, ug, vg, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, tg, 0, nullptr, nullptr, nullptr, 2));
+    // input_output.f90:200-206, as spdy_output_batch_dev: u, v, t as they are; q*1.0e-3; phi/grav; p0*exp(ps) -- then real(., sp)
+    const int kind[6] = {0, 0, 0, 1, 2, 3};
+    const double fac[6] = {1.0, 1.0, 1.0, static_cast<double>(1.0e-3f), p->tab.grav, static_cast<double>(1.e+5f)};
+    for (int i = 0; i < 6; ++i) { c.kind[i] = kind[i]; c.factor[i] = fac[i]; }
+    c.nmem = nmem; c.kx = kx; c.src = ug; c.use = d_use;
+    KERNEL(spdy::launch_ens_output(p->dev, c, p->stream));
     return SPDY_OK;
 }
 

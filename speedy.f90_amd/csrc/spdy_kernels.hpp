@@ -278,6 +278,19 @@ struct GatherOps { int nops, nfld[8]; const double *src[8]; double *dst[8]; };
 hipError_t launch_gather_spectra(const DevPlan &p, const GatherOps &g, hipStream_t s);
 struct OutputCast { int nops, nfld[8], kind[8]; double factor[8]; const double *src[8]; float *dst[8]; };
 hipError_t launch_output_cast(const DevPlan &p, const OutputCast &c, hipStream_t s);
+// Ensemble output: OutputCast's epilogue for nmem members in one launch, and the mean and the spread over the members (two-pass, FP64,
+// sequential in ascending member order).  src: the gridded stacks u | v | t | q | phi (nmem*kx grids each, member-major) | ps
+// (nmem grids); kind / factor per quantity as OutputCast's.  use: null (all members) or nmem device ints, non-zero = the member
+// enters the statistics (the member outputs are written for every member).  members[i]: (ix,il,kx,nmem) float, ps (ix,il,nmem);
+// mean[i], spread[i]: (ix,il,kx), ps (ix,il).  A group is wanted if its entry 0 is non-null, and then all six are; 8-byte aligned.
+struct EnsOutput {
+    int nmem, kx, kind[6];
+    double factor[6];
+    const double *src;
+    const int *use;
+    float *members[6], *mean[6], *spread[6];
+};
+hipError_t launch_ens_output(const DevPlan &p, const EnsOutput &c, hipStream_t s);
 // once per device, before the first launch: raises the dynamic-LDS limit of every kernel that needs > 64 KB
 hipError_t prepare_device_kernels();
 hipError_t prepare_device_step_kernels(int kx);

@@ -45,6 +45,8 @@ struct spdy_plan {
     const double *d_zero_spec = nullptr;         // one all-zero spectrum (gradient tiles of the mixed inverse kernel)
     double *tmp_c = nullptr, *tmp_d = nullptr;   // max_batch spectra each; allocated with `four` (multi-kernel operator sequences)
     double *out_grid = nullptr, *out_spec = nullptr;   // output path: (5kx+1) grids, (3kx+1) spectra (spdy_output_workspace)
+    // ensemble output: (5kx+1) grids per member, u | v | t | q | phi (nmem*kx each) | ps (nmem) (spdy_ens_output_workspace)
+    struct EnsOutGrids { double *g = nullptr; int nmem = 0; } ens_out_grid;
     double *moist_grid = nullptr;     // moist physics from spectra: (3kx+1) grids t | q | phi | ln ps (spdy_moist_workspace)
     double *d_radzonal = nullptr;     // [5][il] zonal radiation forcing fsol | ozone | ozupp | zenit | stratz (spdy_radiation_set_date)
     double *d_orog = nullptr;         // phis0 (ix,il) | forog (ix,il) | sqrt(coa(j)) [il] (spdy_surface_set_orography)

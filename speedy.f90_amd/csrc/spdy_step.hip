@@ -953,4 +953,101 @@ hipError_t launch_output_cast(const DevPlan &p, const OutputCast &c, hipStream_t
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Ensemble output: the epilogue of output_cast_kernel for nmem members at once, and the ensemble mean and spread.  One thread
+// owns one pair of adjacent grid points of one quantity (blockIdx.z) and one level (blockIdx.y) and walks the members in
+// ascending order: x_e by output_cast_kernel's expression, (float)x_e to the member's field, and over the members whose d_use
+// entry is non-zero (all, if d_use is null; n of them)
+//     mean = (sum x_e) / n        spread = sqrt(sum (x_e - mean)^2 / (n - 1))        in FP64, rounded to float32 at the store.
+// TWO PASSES: the sum, then the squared deviations from the finished mean -- the second pass loads the members again and
+// evaluates the same expression on the same bits.  No atomics, no cross-thread reduction, one fixed order: bit-reproducible.  A
+// member left out is a select (its value never enters an operation), so it may hold NaN or inf and is indistinguishable from an
+// absent one.  n = 1: spread +0; n = 0: both NaN.  The loads of ENS_OUT_CHUNK members are issued before the first of them is
+// used (a T30 launch has one or two waves per SIMD: the members' latencies must overlap inside the thread); past the last
+// member a chunk reloads the last member's pair and drops it.  WT: DESIGN.md 4.5 (launch_ens_output).  ens_out_value is
+// output_cast_kernel's expression under the file's contraction setting (it holds no a*b + c); the statistics are compiled without
+// contraction, so that neither the member's value nor a sum depends on what the compiler fuses at which member.
+// ------------------------------------------------------------------------------------------
+constexpr int ENS_OUT_CHUNK = 8;
+
+__device__ __forceinline__ double2 ens_out_value(int kind, double f, double2 v)
+{
+    double a = v.x, b = v.y;
+    if (kind == 1) { a = a * f; b = b * f; }
+    else if (kind == 2) { a = a / f; b = b / f; }
+    else if (kind == 3) { a = f * exp(a); b = f * exp(b); }
+    return make_double2(a, b);
+}
+
+template <bool WT>
+__device__ __forceinline__ void ens_out_store(float *p, double a, double b)
+{
+    if (WT) st1_wt(reinterpret_cast<double *>(p), __hiloint2double(__float_as_int((float)b), __float_as_int((float)a)));
+    else *reinterpret_cast<float2 *>(p) = make_float2((float)a, (float)b);
+}
+
+template <bool WT>
+__global__ __launch_bounds__(256) void ens_output_kernel(EnsOutput c, int gsz)
+{
+#pragma clang fp contract(off)   // the statistics: x_e, each sum, each deviation and its square are one rounded operation each
+    const int op = blockIdx.z, nlev = op < 5 ? c.kx : 1, k = blockIdx.y, nmem = c.nmem;
+    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (k >= nlev || i >= gsz) return;
+    const long mstride = (long)nlev * gsz, at = (long)k * gsz + i;           // member e's pair: at + e * mstride
+    const double *__restrict__ src = c.src + (long)op * nmem * c.kx * gsz + at;   // u | v | t | q | phi (nmem*kx grids each) | ps (nmem)
+    const int *__restrict__ use = c.use;
+    const int kind = c.kind[op];
+    const double f = c.factor[op];
+    float *mem = c.members[op], *mean_out = c.mean[op], *spread_out = c.spread[op];
+    double sa = 0.0, sb = 0.0;
+    int n = 0;
+    for (int e0 = 0; e0 < nmem; e0 += ENS_OUT_CHUNK) {
+        double2 v[ENS_OUT_CHUNK];
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j)
+            v[j] = *reinterpret_cast<const double2 *>(src + (long)min(e0 + j, nmem - 1) * mstride);
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j) {
+            const int e = e0 + j;
+            if (e < nmem) {
+                const double2 x = ens_out_value(kind, f, v[j]);
+                if (mem) ens_out_store<WT>(mem + at + e * mstride, x.x, x.y);
+                if (!use || use[e] != 0) { sa = sa + x.x; sb = sb + x.y; ++n; }
+            }
+        }
+    }
+    if (!mean_out && !spread_out) return;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const double ma = n > 0 ? sa / (double)n : qnan, mb = n > 0 ? sb / (double)n : qnan;
+    if (mean_out) ens_out_store<WT>(mean_out + at, ma, mb);
+    if (!spread_out) return;
+    double qa = 0.0, qb = 0.0;
+    for (int e0 = 0; n > 1 && e0 < nmem; e0 += ENS_OUT_CHUNK) {
+        double2 v[ENS_OUT_CHUNK];
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j)
+            v[j] = *reinterpret_cast<const double2 *>(src + (long)min(e0 + j, nmem - 1) * mstride);
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j) {
+            const int e = e0 + j;
+            if (e < nmem && (!use || use[e] != 0)) {
+                const double2 x = ens_out_value(kind, f, v[j]);
+                const double da = x.x - ma, db = x.y - mb;
+                qa = qa + da * da; qb = qb + db * db;
+            }
+        }
+    }
+    const double m1 = (double)(n - 1);
+    ens_out_store<WT>(spread_out + at, n > 1 ? sqrt(qa / m1) : (n == 1 ? 0.0 : qnan), n > 1 ? sqrt(qb / m1) : (n == 1 ? 0.0 : qnan));
+}
+
+hipError_t launch_ens_output(const DevPlan &p, const EnsOutput &c, hipStream_t s)
+{
+    const int gsz = p.ix * p.il;                                    // even
+    if (c.nmem < 1 || c.kx < 1 || c.kx > 65535 || !c.src || gsz % 2) return hipErrorInvalidValue;
+    const int groups = (c.members[0] ? c.nmem : 0) + (c.mean[0] ? 1 : 0) + (c.spread[0] ? 1 : 0);
+    if (groups == 0) return hipErrorInvalidValue;
+    const dim3 grd((unsigned)((gsz / 2 + 255) / 256), c.kx, 6), blk(256);
+    // the launch's output: float32, 5 kx + 1 grids per member and per statistic
+    if (write_through_policy(p, (long)groups * (5 * c.kx + 1) * gsz * 4)) hipLaunchKernelGGL(ens_output_kernel<true>, grd, blk, 0, s, c, gsz);
+    else hipLaunchKernelGGL(ens_output_kernel<false>, grd, blk, 0, s, c, gsz);
+    return hipGetLastError();
+}
+
 }  // namespace spdy

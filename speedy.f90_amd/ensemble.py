@@ -24,8 +24,9 @@ model.forcing_dev(ens.qcorh); ens.step with the model's boundary() as bnd / albs
 guard.check_dev on time level 2 (ens.vor[1], ens.div[1], ens.t[1]); the host's newdate, and set_date when the day changed;
 model.couple_dev(day, hfluxn, shf, evap, ssrd).
 
-`step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  Not covered: SPPT (one pattern object
-holds one pattern), the level-sharded step."""
+`step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  `output` gives every member's float32
+snapshot (input_output.f90:184-206) and the ensemble mean and spread from one call (include/spdy.h, "ensemble output").  Not
+covered: SPPT (one pattern object holds one pattern), the level-sharded step."""
 import numpy as np
 
 PROG = ("vor", "div", "t", "tr", "ps")
@@ -134,6 +135,52 @@ class Ensemble:
         sp.ens_direct_batch_spectral_step_dev(E, self.U, self.V, self.PL, self.pvor, self.pdiv, self.pspec, self.vor, self.div, self.t,
                                               self.tr, self.ps, self.phis, self.tcorh, self.qcorh, self.sdrag, j1, dt, eps, self.wil,
                                               self.phi, kcos=2)
+
+    # ------------------------------------------------------------------ output
+    def output_workspace(self):
+        """before a capture that contains output"""
+        self.sp.ens_output_workspace(self.nmem)
+
+    def output_shapes(self):
+        """group -> {field: shape} of what output returns (float32)"""
+        E, kx, g = self.nmem, self.kx, (self.sp.il, self.sp.ix)
+        lev = lambda lead: dict({n: lead + (kx,) + g for n in ("u", "v", "t", "q", "phi")}, ps=lead + g)
+        return {"members": lev((E,)), "mean": lev(()), "spread": lev(())}
+
+    def output(self, members=True, stats=True, use=None, phi=None, out=None):
+        """The snapshot of every member and the ensemble statistics from time level 1, one call (input_output.f90:184-206 per member):
+        {"members": {u, v, t, q, phi (E, kx, il, ix), ps (E, il, ix)}, "mean": {.. (kx, il, ix), ps (il, ix)}, "spread": {..}} of
+        float32 device tensors; without `members` / `stats` the group(s) are left out.  mean = sum / n and spread = the sample
+        standard deviation (n - 1) over the n members in use, formed in FP64; n = 1 gives spread 0, n = 0 NaN.
+        use: None (all members), or a sequence or an int32 device tensor of E entries, non-zero = the member enters the statistics
+        (the member fields are written for every member).  From a guard of the ensemble, once per output interval (its one
+        synchronisation): use = [s == -1 for s in guard.stopped()] -- members the guard has not stopped have -1.
+        phi: the geopotential of time level 1, (E, kx, nx, mx); by default self.phi.
+        out: {group: {field: tensor}} of caller-made float32 tensors of output_shapes() to write into; inside a capture pass `out`
+        and `use` as device tensors, after output_workspace(): the call then allocates nothing."""
+        import torch
+        if not members and not stats:
+            raise ValueError("output: neither members nor stats wanted")
+        dev = self.vor.device
+        if use is not None and not torch.is_tensor(use):
+            use = torch.tensor([1 if u else 0 for u in use], dtype=torch.int32, device=dev)
+        if use is not None and (use.dtype != torch.int32 or use.numel() != self.nmem or not use.is_contiguous()):
+            raise ValueError("use must be %d contiguous int32 entries" % self.nmem)
+        res = {}
+        for grp, shp in self.output_shapes().items():
+            if not (members if grp == "members" else stats):
+                continue
+            given = (out or {}).get(grp)
+            if given is None:
+                given = {n: torch.empty(sh, dtype=torch.float32, device=dev) for n, sh in shp.items()}
+            for n, sh in shp.items():
+                a = given[n]
+                if tuple(a.shape) != sh or a.dtype != torch.float32 or not a.is_contiguous():
+                    raise ValueError("out[%s][%s] must be a contiguous float32 tensor of shape %s" % (grp, n, sh))
+            res[grp] = given
+        self.sp.ens_output_batch_dev(self.nmem, self.vor[0], self.div[0], self.t[0], self.tr[0], self.phi if phi is None else phi,
+                                     self.ps[0], res.get("members"), res.get("mean"), res.get("spread"), use)
+        return res
 
     def startup(self, delt, physics=None):
         """first_step (time_stepping.f90:12-24): the forward half step, the first leapfrog step and the three initialize_implicit

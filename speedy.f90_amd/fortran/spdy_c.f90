@@ -75,6 +75,11 @@ module spdy_c
         type(c_ptr) :: ts = c_null_ptr, fsfcu = c_null_ptr
     end type
 
+    !> spdy_output_fields (include/spdy.h): one group of float fields of spdy_ens_output_batch_dev, all six required
+    type, bind(C) :: spdy_output_fields
+        type(c_ptr) :: u = c_null_ptr, v = c_null_ptr, t = c_null_ptr, q = c_null_ptr, phi = c_null_ptr, ps = c_null_ptr
+    end type
+
     interface
         function spdy_plan_create(trunc, ix, iy, kx, max_batch, device, plan) bind(C, name="spdy_plan_create") result(rc)
             import :: c_int, c_ptr
@@ -1080,6 +1085,21 @@ module spdy_c
                 & bind(C, name="spdy_output_batch_dev") result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, vor, div, t, q, phi, ps, u_out, v_out, t_out, q_out, phi_out, ps_out
+            integer(c_int) :: rc
+        end function
+        ! the ensemble output (include/spdy.h): members, mean, spread are c_loc of a spdy_output_fields, or c_null_ptr = not wanted;
+        ! d_use is a device array of nmem c_int, or c_null_ptr = all members
+        function spdy_ens_output_workspace(plan, nmem) bind(C, name="spdy_ens_output_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int), value :: nmem
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_output_batch_dev(plan, nmem, vor, div, t, q, phi, ps, d_use, members, mean, spread) &
+                & bind(C, name="spdy_ens_output_batch_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, vor, div, t, q, phi, ps, d_use, members, mean, spread
+            integer(c_int), value :: nmem
             integer(c_int) :: rc
         end function
     end interface

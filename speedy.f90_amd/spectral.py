@@ -40,6 +40,11 @@ class HdiffOp(ctypes.Structure):      # spdy_hdiff_op
                 ("d_dmp1", ctypes.c_void_p), ("fdt_out", ctypes.c_void_p)]
 
 
+class OutputFields(ctypes.Structure):  # spdy_output_fields
+    NAMES = ("u", "v", "t", "q", "phi", "ps")
+    _fields_ = [(n, ctypes.c_void_p) for n in NAMES]
+
+
 class Graph:
     """A captured sequence of device-resident calls (spdy_graph_* in include/spdy.h)."""
 
@@ -487,6 +492,21 @@ class Spectral(ColumnPhysics):
         self._sync_stream()
         args = (vor, div, t, q, phi, ps, u_out, v_out, t_out, q_out, phi_out, ps_out)
         check(self.lib.spdy_output_batch_dev(self.h, *[self._dp(x) for x in args]))
+
+    # ------------------------------------------------------------------ ensemble output (include/spdy.h, "ensemble output")
+    def ens_output_workspace(self, nmem):
+        """before a capture that contains ens_output_batch_dev"""
+        check(self.lib.spdy_ens_output_workspace(self.h, int(nmem)))
+
+    def ens_output_batch_dev(self, nmem, vor, div, t, q, phi, ps, members=None, mean=None, spread=None, use=None):
+        """output_batch_dev for the nmem members of an ensemble, and the ensemble mean and spread: time level 1 of the ensemble in,
+        complex128 (nmem, kx, nx, mx) (ps (nmem, nx, mx)).  members, mean, spread: None (not wanted) or a dict u, v, t, q, phi, ps
+        of float32 tensors -- members (nmem, kx, il, ix), ps (nmem, il, ix); mean and spread (kx, il, ix), ps (il, ix).  use: None
+        (all members) or an int32 device tensor of nmem entries, non-zero = the member enters the statistics."""
+        self._sync_stream()
+        groups = [None if g is None else OutputFields(*[g[n].data_ptr() for n in OutputFields.NAMES]) for g in (members, mean, spread)]
+        check(self.lib.spdy_ens_output_batch_dev(self.h, int(nmem), *[self._dp(x) for x in (vor, div, t, q, phi, ps, use)],
+                                                 *[None if g is None else ctypes.byref(g) for g in groups]))
 
     def geopotential_dev(self, t, phis, phi):
         self._members("geopotential_dev", None, t, phis, phi)

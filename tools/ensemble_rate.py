@@ -17,9 +17,17 @@ correction per member); the per-member form is E single objects on the members' 
 before the batched objects can do.  --earlier-library binds such a library ($SPDY_LIB): what it lacks is left out, the member
 forms of one member are its unsuffixed calls, and only the per-member form (and, without --coupled, what it has) is measured.
 
+--output measures the ensemble OUTPUT instead (include/spdy.h, "ensemble output"): graph replays of Ensemble.output with members and
+statistics -- one inverse batch of all members and one epilogue kernel, whatever E -- against E replays' worth of the single-state
+spdy_output_batch_dev on the members' views in one graph (3 E launches: the only way to the same member fields without the call,
+and it gives no statistics), and the call's inverse batch captured alone.  The epilogue's time is taken as the difference of the
+first and the last -- a difference of two graph replays, not a kernel trace -- and its byte model ((5 kx + 1) E FP64 grids read
+once, (E + 2) (5 kx + 1) float32 grids written) is given as a fraction of 8 TB/s, as is the whole call's.
+
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
     python tools/ensemble_rate.py --coupled --members 1 2 4 8 16
+    python tools/ensemble_rate.py --output --json profiles/ensemble_output_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
 import ctypes
@@ -263,12 +271,66 @@ def run_coupled(tag, members, reps, repeats, label, rows, batched):
     sp.close()
 
 
+def run_output(tag, members, reps, repeats, label, rows):
+    """graph replays of the ensemble output call, of E single-state output calls, and of the call's inverse batch alone"""
+    import ensemblestep
+    kx = VARIANTS[tag][3]
+    sp = moist.plan(tag, max(members) * (4 * kx + 4))
+    spec, grid = sp.nx * sp.mx * 16, sp.il * sp.ix
+    graphs, keep = {}, []
+    for E in members:
+        en = ensemblestep.build(sp, ensemblestep.member_states(sp, E))
+        sp.ens_geopotential_dev(E, en.t[0], en.phis, en.phi)                 # phi of time level 1: an input of the snapshot
+        zeros = lambda shapes: {n: torch.zeros(sh, dtype=torch.float32, device="cuda") for n, sh in shapes.items()}
+        out = {g: zeros(sh) for g, sh in en.output_shapes().items()}
+        per = zeros(en.output_shapes()["members"])
+        flat = lambda a: a.view((-1,) + tuple(a.shape[-2:]))
+        ug, vg = (torch.zeros((E * kx, sp.il, sp.ix), dtype=torch.float64, device="cuda") for _ in range(2))
+        plain = torch.zeros((3 * E * kx + E, sp.il, sp.ix), dtype=torch.float64, device="cuda")
+        en.output_workspace()
+        single = lambda e: sp.output_batch_dev(en.vor[0, e], en.div[0, e], en.t[0, e], en.tr[0, e], en.phi[e], en.ps[0, e],
+                                               *[per[n][e] for n in ("u", "v", "t", "q", "phi", "ps")])
+        single(0)                                                           # its workspace, before the capture
+        torch.cuda.synchronize()
+        with sp.graph_capture() as g:
+            en.output(out=out)
+        graphs["output E=%d ensemble call" % E] = g
+        with sp.graph_capture() as g:
+            for e in range(E):
+                single(e)
+        graphs["output E=%d single calls" % E] = g
+        with sp.graph_capture() as g:
+            sp.inverse_batch_segs_dev(flat(en.vor[0]), flat(en.div[0]), ug, vg, [flat(en.t[0]), flat(en.tr[0]), flat(en.phi), en.ps[0]],
+                                      plain, kcos_pairs=2, kcos=1)
+        graphs["output E=%d inverse batch alone" % E] = g
+        keep.append((en, out, per, ug, vg, plain))
+    nodes = {n: g.num_nodes() for n, g in graphs.items()}
+    t = time_interleaved({n: g.launch for n, g in graphs.items()}, lambda: None, reps, repeats)
+    for name, (med, lo, hi) in t.items():
+        E = int(name.split("=")[1].split()[0])
+        row = {"label": label, "size": tag, "form": name, "members": E, "nodes": nodes[name], "us_per_call": round(med, 2),
+               "us_min": round(lo, 2), "us_max": round(hi, 2)}
+        if name.endswith("ensemble call"):
+            singles, inv = t["output E=%d single calls" % E][0], t["output E=%d inverse batch alone" % E][0]
+            epi_bytes = (5 * kx + 1) * grid * (8 * E + 4 * (E + 2))
+            call_bytes = epi_bytes + E * (5 * kx + 1) * (spec + 8 * grid)
+            row.update(speedup_vs_single_calls=round(singles / med, 2), us_epilogue_by_difference=round(med - inv, 2),
+                       epilogue_bytes=epi_bytes, call_byte_model_fraction_of_8TBps=round(call_bytes / (med * 1e-6) / HBM, 4),
+                       epilogue_byte_model_fraction_of_8TBps=round(epi_bytes / ((med - inv) * 1e-6) / HBM, 4) if med > inv else None)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for g in graphs.values():
+        g.close()
+    sp.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["t30", "t63k16"])
     ap.add_argument("--members", nargs="+", type=int, default=[1, 2, 4, 8, 16, 32])
     ap.add_argument("--single-only", action="store_true")
     ap.add_argument("--coupled", action="store_true")
+    ap.add_argument("--output", action="store_true")
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
     ap.add_argument("--reps", type=int, default=200)
@@ -285,7 +347,9 @@ def main():
     rows = []
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
-            if a.coupled:
+            if a.output:
+                run_output(tag, a.members, a.reps, a.repeats, a.label, rows)
+            elif a.coupled:
                 run_coupled(tag, a.members, a.reps, a.repeats, a.label, rows, batched)
             else:
                 run(tag, [] if a.single_only else a.members, a.reps, a.repeats, a.label, rows)
