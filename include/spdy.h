@@ -323,7 +323,8 @@ int spdy_direct_batch_spectral_step_dev(spdy_plan *plan, const double *d_ug, con
  * Checks, in this order: a NULL plan, nmem < 1, kx > 16 with nmem > 1 (physics: kx outside [5, 16]) and
  * max_batch < nmem*(3*kx+1) SPDY_ERR_ARG; what the single-state call needs first (spdy_implicit_init, sigma levels; physics: sigma
  * levels, date, orography) SPDY_ERR_STATE; a NULL required pointer, then j1 outside {1, 2} SPDY_ERR_ARG; a host-only plan
- * SPDY_ERR_NO_DEVICE last.  Every call can be captured.  Not covered: SPPT (a pattern object holds one pattern), the sharded step.
+ * SPDY_ERR_NO_DEVICE last.  Every call can be captured.  SPPT: a pattern object of nmem members and spdy_ens_physics_sppt_dev ("SPPT" below).  Not covered: the
+ * sharded step.
  * A coupled ensemble needs the option "ens_member_qcorh": qcorh = grid_to_spec(corh) and corh is made from the member's own stl_am
  * and sst_am ("surface models" below), so once the members' land and sea temperatures differ no two members have the same qcorh.
  * d_tcorh depends neither on time nor on the member and stays shared.  In the kernel it is one more uniform member offset (a
@@ -735,14 +736,38 @@ int spdy_ens_physics_dev(spdy_plan *plan, int nmem, int compute_sw, const double
  * in registers and passes ttend and qtend through the workspace).  Everything else -- `out`, the radiation state, the checks and
  * their order (d_pattern / s count as required pointers; s of another plan SPDY_ERR_ARG) -- is as without SPPT.  The _workspace
  * calls allocate what the calls without SPPT need and (2 kx + 2) grids per state for the dynamics tendencies (max_batch states /
- * one state) ahead of a capture.                                                                                              */
+ * one state) ahead of a capture.
+ *
+ * The ensemble form ("ensemble time step" above): a spdy_sppt made by spdy_ens_sppt_create holds nmem patterns, member-major in the
+ * layout of every other ensemble array -- "eta" and "spec" (mx,nx,kx,nmem) complex, "pattern" (ix,il,kx,nmem), member e starting
+ * e*kx fields in -- and one {draws, seed} pair per member in device memory; the tables are shared.  seeds: nmem values on the
+ * host.  A device plan needs max_batch >= nmem*kx.  spdy_sppt_create, _reset and _draws are the one-member / member-0 case of
+ * spdy_ens_sppt_create, _reset and _draws; spdy_sppt_members gives nmem (a host-only plan answers it too); _table, _field, _destroy
+ * and spdy_sppt_advance_dev work on an object of any nmem, d_eta then being (mx,nx,kx,nmem).  The advance is the same three
+ * launches whatever nmem is: the noise kernel takes the member from blockIdx.y, reads that member's counter and seed, and counts
+ * the generator's coefficient index INSIDE the member (0 .. mx*nx*kx-1), so member e draws exactly what a one-member object with
+ * seeds[e] draws; the first / AR(1) branch is each member's own, so one launch may take the first-draw branch for a member just
+ * reset (spdy_ens_sppt_reset: that member only) and the AR(1) branch for the others; ONE inverse transform of nmem*kx fields; the
+ * clip of all members, one thread per member counting that member's advance.  Members are fields of a batch: nothing one member
+ * holds, non-finite values included, changes a bit of another member's eta, spec, pattern or counter.
+ * spdy_ens_physics_sppt_dev is spdy_ens_physics_dev followed by physics.f90:212-221 per member with that member's pattern and the
+ * shared mu: ONE inverse launch of time level 1 of all members, then the chain's SPPT form with nb = nmem, in both
+ * "physics_fused" forms the same bits; it does not advance s.  Checks as spdy_ens_physics_dev with s a required pointer; then s of
+ * another plan, then spdy_sppt_members(s) != nmem SPDY_ERR_ARG (spdy_physics_sppt_dev: an s of more than one member).
+ * spdy_ens_physics_sppt_workspace(nmem) allocates what spdy_ens_physics_workspace does and (2 kx + 2) grids per member.  Checks
+ * of the object calls: a NULL plan / object, nmem < 1, NULL seeds or result pointer, a member outside [0, nmem) SPDY_ERR_ARG; an
+ * open capture (create, reset, draws) SPDY_ERR_STATE; a host-only plan SPDY_ERR_NO_DEVICE last.                                */
 typedef struct spdy_sppt spdy_sppt;
 int spdy_sppt_create(spdy_plan *plan, int nsteps, const double *mu, unsigned long long seed, spdy_sppt **s);
+int spdy_ens_sppt_create(spdy_plan *plan, int nmem, int nsteps, const double *mu, const unsigned long long *seeds, spdy_sppt **s);
+int spdy_sppt_members(const spdy_sppt *s);
 int spdy_sppt_destroy(spdy_sppt *s);
 int spdy_sppt_reset(spdy_sppt *s, unsigned long long seed);
+int spdy_ens_sppt_reset(spdy_sppt *s, int member, unsigned long long seed);
 int spdy_sppt_table(const spdy_sppt *s, const char *name, double *buf, int cap);
 int spdy_sppt_field(spdy_sppt *s, const char *name, double **d_ptr);
 int spdy_sppt_draws(spdy_sppt *s, long long *draws);
+int spdy_ens_sppt_draws(spdy_sppt *s, int member, long long *draws);
 int spdy_sppt_advance_dev(spdy_sppt *s, const double *d_eta);
 int spdy_column_physics_sppt_workspace(spdy_plan *plan);
 int spdy_column_physics_sppt_dev(spdy_plan *plan, int nb, const double *d_pattern, const double *mu, int compute_sw,
@@ -754,6 +779,11 @@ int spdy_physics_sppt_dev(spdy_plan *plan, spdy_sppt *s, int compute_sw, const d
                           const double *q, const double *phi, const double *ps, const spdy_sfc_boundary *bnd, const double *albsfc,
                           double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
                           const spdy_column_physics_out *out);
+int spdy_ens_physics_sppt_workspace(spdy_plan *plan, int nmem);
+int spdy_ens_physics_sppt_dev(spdy_plan *plan, int nmem, spdy_sppt *s, int compute_sw, const double *vor, const double *div,
+                              const double *t, const double *q, const double *phi, const double *ps, const spdy_sfc_boundary *bnd,
+                              const double *albsfc, double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                              const spdy_column_physics_out *out);
 
 /* ---- surface models: the slab land, sea and ice models and the daily forcing (coupler.f90, land_model.f90, sea_model.f90,
  * forcing.f90) -------------------------------------------------------------------------------------------------------------

@@ -141,16 +141,22 @@ SIGNATURES = {
     "spdy_surface_model_boundary": [c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_surface_model_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
     "spdy_sppt_create": [c_void_p, c_int, c_void_p, ctypes.c_ulonglong, ctypes.POINTER(c_void_p)],
+    "spdy_ens_sppt_create": [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
+    "spdy_sppt_members": [c_void_p],
     "spdy_sppt_destroy": [c_void_p],
     "spdy_sppt_reset": [c_void_p, ctypes.c_ulonglong],
+    "spdy_ens_sppt_reset": [c_void_p, c_int, ctypes.c_ulonglong],
     "spdy_sppt_table": [c_void_p, c_char_p, c_void_p, c_int],
     "spdy_sppt_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
     "spdy_sppt_draws": [c_void_p, ctypes.POINTER(ctypes.c_longlong)],
+    "spdy_ens_sppt_draws": [c_void_p, c_int, ctypes.POINTER(ctypes.c_longlong)],
     "spdy_sppt_advance_dev": [c_void_p, c_void_p],
     "spdy_column_physics_sppt_workspace": [c_void_p],
     "spdy_column_physics_sppt_dev": [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 14,
     "spdy_physics_sppt_workspace": [c_void_p],
     "spdy_physics_sppt_dev": [c_void_p, c_void_p, c_int] + [c_void_p] * 14,
+    "spdy_ens_physics_sppt_workspace": [c_void_p, c_int],
+    "spdy_ens_physics_sppt_dev": [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 14,
     "spdy_diagnostics_create": [c_void_p, c_int, ctypes.c_longlong, ctypes.POINTER(c_void_p)],
     "spdy_ens_diagnostics_create": [c_void_p, c_int, c_int, ctypes.c_longlong, ctypes.POINTER(c_void_p)],
     "spdy_ens_diagnostics_status": [c_void_p, c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),

@@ -250,19 +250,29 @@ class Sppt:
     """The SPPT pattern on the device (spdy_sppt_* in include/spdy.h): gen_sppt of sppt.f90 with a counter-based generator.
 
     nsteps: steps per day; mu: the taper per level, kx values top down (None = all ones).  One step of a run: advance_dev(), then
-    Spectral.physics_sppt_dev(self, ...), which reads the pattern and mu and does not advance."""
+    Spectral.physics_sppt_dev(self, ...), which reads the pattern and mu and does not advance.
 
-    def __init__(self, sp, nsteps, mu=None, seed=0):
+    nmem > 1 (or seeds given): one pattern per member of an ensemble, member-major, advanced together by the same three launches;
+    seeds: one per member (default seed + e), each member drawing what a one-member object with its seed draws.  The step is then
+    advance_dev() and Spectral.ens_physics_sppt_dev(nmem, self, ...): Ensemble.step does both when its physics has "sppt"."""
+
+    def __init__(self, sp, nsteps, mu=None, seed=0, nmem=1, seeds=None):
         self.sp, self.lib = sp, sp.lib
         if mu is not None:
             mu = np.ascontiguousarray(mu, np.float64)
             if mu.shape != (sp.kx,):
                 raise ValueError("mu must hold kx values")
+        if seeds is not None and nmem not in (1, len(seeds)):
+            raise ValueError("seeds must hold nmem values")
+        nmem = int(nmem) if seeds is None else len(seeds)
+        if seeds is None:
+            seeds = [int(seed) + e for e in range(max(nmem, 0))]
+        seeds = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], np.uint64)
         if sp.device >= 0:
             sp._sync_stream()
         h = ctypes.c_void_p()
-        check(self.lib.spdy_sppt_create(sp.h, int(nsteps), None if mu is None else _p(mu), int(seed), ctypes.byref(h)))
-        self.h = h
+        check(self.lib.spdy_ens_sppt_create(sp.h, nmem, int(nsteps), None if mu is None else _p(mu), _p(seeds), ctypes.byref(h)))
+        self.h, self.nmem = h, nmem
         # the plan closes its objects first (as its surface models)
         sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
 
@@ -284,34 +294,41 @@ class Sppt:
         check(self.lib.spdy_sppt_table(self.h, name.encode(), _p(out), n))
         return float(out[0]) if n == 1 and name != "mu" else out.reshape((self.sp.nx, self.sp.mx)) if name == "sigma" else out
 
+    def members(self):
+        """the number of patterns the object holds"""
+        return check(self.lib.spdy_sppt_members(self.h))
+
     def field(self, name):
         """"eta", "spec" ([kx, nx, mx] complex128, as a DeviceField of [kx, nx, mx, 2] float64) or "pattern" [kx, il, ix]: the
-        object's own device memory; the pointers never change."""
+        object's own device memory; the pointers never change.  With nmem > 1 every shape has the members in front: [nmem, kx, ..]."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_sppt_field(self.h, name.encode(), ctypes.byref(p)))
         sp = self.sp
-        return DeviceField(sp, p.value, (sp.kx,) + sp.grid_shape if name == "pattern" else (sp.kx, sp.nx, sp.mx, 2))
+        lead = (self.nmem, sp.kx) if self.nmem > 1 else (sp.kx,)
+        return DeviceField(sp, p.value, lead + (sp.grid_shape if name == "pattern" else (sp.nx, sp.mx, 2)))
 
     def numpy(self, name):
-        """A host copy of a field after everything enqueued on the plan's stream: eta and spec as complex128 [kx, nx, mx]."""
+        """A host copy of a field after everything enqueued on the plan's stream: eta and spec as complex128 [kx, nx, mx]
+        ([nmem, kx, nx, mx] with nmem > 1)."""
         a = self.field(name).numpy()
         return a if name == "pattern" else a.view(np.complex128)[..., 0]
 
-    def reset(self, seed):
-        """A new seed and draws = 0: the next advance is a first one.  Stream-ordered; not during a capture."""
+    def reset(self, seed, member=0):
+        """A new seed and draws = 0 for that member only: its next advance is a first one.  Stream-ordered; not during a capture."""
         self.sp._sync_stream()
-        check(self.lib.spdy_sppt_reset(self.h, int(seed)))
+        check(self.lib.spdy_ens_sppt_reset(self.h, int(member), int(seed)))
 
-    def draws(self):
-        """The number of advances since create / reset (downloads the device counter: synchronises the plan's stream)."""
+    def draws(self, member=0):
+        """The member's number of advances since create / reset (downloads the device counter: synchronises the plan's stream)."""
         self.sp._sync_stream()
         n = ctypes.c_longlong()
-        check(self.lib.spdy_sppt_draws(self.h, ctypes.byref(n)))
+        check(self.lib.spdy_ens_sppt_draws(self.h, int(member), ctypes.byref(n)))
         return n.value
 
     def advance_dev(self, eta=None):
-        """gen_sppt(): noise (drawn on the device, or eta [kx, nx, mx] complex128 device tensor), AR(1) update, the plan's inverse
-        transform, the clip into "pattern"; capturable, each replay draws new noise."""
+        """gen_sppt() for every member: noise (drawn on the device, or eta [kx, nx, mx] / [nmem, kx, nx, mx] complex128 device
+        tensor), AR(1) update, the plan's inverse transform, the clip into "pattern"; three launches whatever nmem is; capturable,
+        each replay draws new noise."""
         self.sp._sync_stream()
         check(self.lib.spdy_sppt_advance_dev(self.h, None if eta is None else ctypes.c_void_p(eta.data_ptr())))
 
@@ -569,7 +586,7 @@ class ColumnPhysics:
         check(self.lib.spdy_physics_workspace(self.h))
 
     def _physics(self, fn, lead, compute_sw, spectra, bnd, albsfc, state, tends, out):
-        """The marshalling of the three physics-from-spectra calls: the C function, its leading arguments, the shared ones."""
+        """The marshalling of the physics-from-spectra calls: the C function, its leading arguments, the shared ones."""
         self._sync_stream()
         o = self._column_physics_out(out)
         b = self._boundary(bnd)
@@ -620,6 +637,16 @@ class ColumnPhysics:
         """physics_dev followed by SPPT with the current pattern and the mu of sppt (a Sppt of this plan), which is not advanced:
         call sppt.advance_dev() first."""
         self._physics(self.lib.spdy_physics_sppt_dev, (sppt.h,), compute_sw, (vor, div, t, q, phi, ps), bnd, albsfc, state,
+                      (utend, vtend, ttend, qtend), out)
+
+    def ens_physics_sppt_workspace(self, nmem):
+        check(self.lib.spdy_ens_physics_sppt_workspace(self.h, int(nmem)))
+
+    def ens_physics_sppt_dev(self, nmem, sppt, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, state, utend, vtend, ttend, qtend,
+                             out=None):
+        """ens_physics_dev followed by SPPT, each member with its own current pattern of sppt (a Sppt of this plan with nmem members)
+        and the shared mu; sppt is not advanced: call sppt.advance_dev() first."""
+        self._physics(self.lib.spdy_ens_physics_sppt_dev, (int(nmem), sppt.h), compute_sw, (vor, div, t, q, phi, ps), bnd, albsfc, state,
                       (utend, vtend, ttend, qtend), out)
 
     # ------------------------------------------------------------------ NumPy conveniences: inputs and results by name, shaped by FIELDS

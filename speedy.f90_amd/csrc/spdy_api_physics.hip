@@ -1,8 +1,8 @@
 // C ABI of the column physics (include/spdy.h, "column physics"): the precipitation block (physics.f90:110-138), the
 // radiation schemes (physics.f90:146-166 and :180-186), the surface fluxes (:169-170), the boundary layer (:193-205) and the
 // whole chain, on gridded states and from spectra, without and with SPPT (:207-222).  Kernels: csrc/spdy_sppt.hip, csrc/spdy_physics.hip, csrc/spdy_radiation.hip, csrc/spdy_surface.hip,
-// csrc/spdy_column_chain.hip.  The physics from spectra is one body (physics_from_spectra) for one state, nmem members and one state
-// with SPPT; the single state is nmem = 1 on a workspace of its own.
+// csrc/spdy_column_chain.hip.  The physics from spectra is one body (physics_from_spectra) for one state and nmem members, each without
+// and with SPPT; the single state is nmem = 1 on a workspace of its own.
 #include <cmath>
 #include <cstring>
 
@@ -224,8 +224,8 @@ int sppt_workspace(spdy_plan *p, double **ws, size_t states, const char *scheme,
     return SPDY_OK;
 }
 
-// ---- the physics of nmem states from their spectra: one body for spdy_physics_dev, spdy_ens_physics_dev, spdy_physics_sppt_dev ----
-struct FromSpectra {   // the arguments the three calls share, in their order
+// ---- the physics of nmem states from their spectra: one body for spdy_physics_dev, spdy_ens_physics_dev and their SPPT forms ----
+struct FromSpectra {   // the arguments the four calls share, in their order
     int compute_sw;
     const double *vor, *div, *t, *q, *phi, *ps;
     const spdy_sfc_boundary *bnd;
@@ -248,7 +248,7 @@ int physics_members(const spdy_plan *p, int nmem, bool ens)
 }
 
 // The checks that need no device, in each call's documented order.  With SPPT the pattern is one of the required pointers, and its
-// plan is tested after them.
+// plan and its member count are tested after them.
 int physics_args(const spdy_plan *p, int nmem, bool ens, const FromSpectra &a, bool with_sppt = false, const spdy_sppt *sppt = nullptr)
 {
     const bool ok = (!with_sppt || sppt) && a.vor && a.div && a.t && a.q && a.phi && a.ps && boundary_ok(a.bnd) &&
@@ -256,6 +256,7 @@ int physics_args(const spdy_plan *p, int nmem, bool ens, const FromSpectra &a, b
     if (ens) RC(physics_members(p, nmem, true));
     RC(column_args(p, ens ? "ens_physics" : "physics", nmem, true, ok, true));
     if (sppt && sppt->plan != p) return fail(SPDY_ERR_ARG, "the SPPT pattern belongs to another plan");
+    if (sppt && sppt->nmem != nmem) return fail(SPDY_ERR_ARG, "the SPPT object holds %d patterns, the call has %d states", sppt->nmem, nmem);
     return ens ? SPDY_OK : physics_members(p, 1, false);
 }
 
@@ -488,7 +489,7 @@ int spdy_column_physics_sppt_dev(spdy_plan *p, int nb, const double *d_pattern, 
                         ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch, &use);
 }
 
-/* ---------------------------------------------------------------- the physics from spectra (physics.f90:94-205): one state, nmem members, one state with SPPT */
+/* ---------------------------------------------------------------- the physics from spectra (physics.f90:94-205): one state, nmem members, each with SPPT */
 int spdy_physics_workspace(spdy_plan *p)
 {
     NEED_PLAN(p);
@@ -540,6 +541,32 @@ int spdy_physics_sppt_dev(spdy_plan *p, spdy_sppt *sp, int compute_sw, const dou
     RC(spdy_physics_sppt_workspace(p));
     const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->sppt_grid};   // the pattern the last spdy_sppt_advance_dev left
     return physics_from_spectra(p, 1, p->physics_grid, &use, a);
+}
+
+int spdy_ens_physics_sppt_workspace(spdy_plan *p, int nmem)
+{
+    RC(spdy_ens_physics_workspace(p, nmem));
+    spdy_plan::SpptGrids *w = &p->ens_sppt_grid;
+    if (w->nmem >= nmem) return SPDY_OK;
+    NOT_CAPTURING(p, "allocating the ensemble SPPT workspace (call spdy_ens_physics_sppt_workspace before the capture)");
+    // like the physics workspace, a smaller earlier one stays with the plan: a captured graph may still point into it
+    void *ptr;
+    RC(dev_alloc(p, (size_t)(2 * p->tab.kx + 2) * grid_elems(p) * nmem * sizeof(double), &ptr));
+    *w = {static_cast<double *>(ptr), nmem};
+    return SPDY_OK;
+}
+
+int spdy_ens_physics_sppt_dev(spdy_plan *p, int nmem, spdy_sppt *sp, int compute_sw, const double *vor, const double *div,
+                              const double *t, const double *q, const double *phi, const double *ps, const spdy_sfc_boundary *bnd,
+                              const double *albsfc, double *rad_state, double *utend, double *vtend, double *ttend, double *qtend,
+                              const spdy_column_physics_out *out)
+{
+    const FromSpectra a{compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, qtend, out};
+    RC(physics_args(p, nmem, true, a, true, sp));
+    RC(spdy_ens_physics_sppt_workspace(p, nmem));
+    // the patterns the last spdy_sppt_advance_dev left: nmem states back to back, what the chain takes as nb = nmem
+    const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->ens_sppt_grid.g};
+    return physics_from_spectra(p, nmem, p->ens_physics_grid, &use, a);
 }
 
 }  // extern "C"

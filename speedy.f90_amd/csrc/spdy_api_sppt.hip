@@ -2,6 +2,7 @@
 // tables: csrc/spdy_tables.cpp (SpptTables).  The application to the tendencies is part of the column physics
 // (csrc/spdy_api_physics.hip).
 #include <cstring>
+#include <vector>
 
 #include "spdy_plan.hpp"
 
@@ -15,47 +16,70 @@ namespace {
 
 size_t coefs(const spdy_plan *p) { return (size_t)p->tab.mx * p->tab.nx * p->tab.kx; }
 
-// the counter and the seed, stream-ordered as spdy_radiation_set_date's fields; the pattern is zero until the first advance
-int restart(spdy_sppt *s, unsigned long long seed)
+// the counters and the seeds of members [first, first + n), stream-ordered as spdy_radiation_set_date's fields; a pattern is zero
+// until its first advance
+int restart(spdy_sppt *s, int first, int n, const unsigned long long *seeds)
 {
     spdy_plan *p = s->plan;
-    const spdy::SpptState h{0ull, seed};
-    HIP_TRY(hipMemcpyAsync(s->d_state, &h, sizeof(h), hipMemcpyHostToDevice, p->stream));
+    std::vector<spdy::SpptState> h((size_t)n);
+    for (int e = 0; e < n; ++e) h[e] = spdy::SpptState{0ull, seeds[e]};
+    HIP_TRY(hipMemcpyAsync(s->d_state + first, h.data(), sizeof(spdy::SpptState) * (size_t)n, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
+int need_member(const spdy_sppt *s, int member)
+{
+    if (member < 0 || member >= s->nmem) return fail(SPDY_ERR_ARG, "SPPT member %d outside [0, %d)", member, s->nmem);
     return SPDY_OK;
 }
 }  // namespace
 
 extern "C" {
 
-int spdy_sppt_create(spdy_plan *p, int nsteps, const double *mu, unsigned long long seed, spdy_sppt **out)
+int spdy_ens_sppt_create(spdy_plan *p, int nmem, int nsteps, const double *mu, const unsigned long long *seeds, spdy_sppt **out)
 {
     NEED_PLAN(p);
-    if (!out) return fail(SPDY_ERR_ARG, "null result pointer");
+    if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_sppt_create: nmem=%d < 1", nmem);
+    if (!seeds || !out) return fail(SPDY_ERR_ARG, "null seeds or result pointer");
     NOT_CAPTURING(p, "spdy_sppt_create (host table build + upload)");
     spdy_sppt *s = new spdy_sppt;
-    s->plan = p;
+    s->plan = p; s->nmem = nmem;
     const std::string err = s->tab.build(p->tab, nsteps, mu);
     if (!err.empty()) { delete s; return fail(SPDY_ERR_ARG, "sppt_create: %s", err.c_str()); }
     *out = s;
     if (p->device < 0) return SPDY_OK;
     auto cleanup = [&](int rc) { spdy_sppt_destroy(s); *out = nullptr; return rc; };
-    if (p->max_batch < p->tab.kx) return cleanup(fail(SPDY_ERR_ARG, "max_batch must be >= kx for the SPPT pattern's transform"));
+    const long nk = (long)nmem * p->tab.kx;
+    if (p->max_batch < nk)
+        return cleanup(fail(SPDY_ERR_ARG, "max_batch=%d must be >= nmem*kx=%ld for the SPPT patterns' transform", p->max_batch, nk));
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
-    const size_t nc = coefs(p), ng = grid_elems(p) * p->tab.kx, nsig = s->tab.sigma.size();
+    const size_t nc = coefs(p) * nmem, ng = grid_elems(p) * nk, nsig = s->tab.sigma.size();
     const size_t bytes = (4 * nc + ng + nsig) * sizeof(double);
     if (hipMalloc(reinterpret_cast<void **>(&s->d_eta), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(spdy::SpptState)) != hipSuccess)
+        hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(spdy::SpptState) * (size_t)nmem) != hipSuccess)
         return cleanup(fail(SPDY_ERR_HIP, "sppt_create: hipMalloc of %zu bytes failed", bytes));
     s->d_spec = s->d_eta + 2 * nc; s->d_pattern = s->d_spec + 2 * nc; s->d_sigma = s->d_pattern + ng;
     if (hipMemsetAsync(s->d_eta, 0, bytes, p->stream) != hipSuccess ||
         hipMemcpyAsync(s->d_sigma, s->tab.sigma.data(), nsig * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess)
         return cleanup(fail(SPDY_ERR_HIP, "sppt_create: upload failed"));
-    int rc = restart(s, seed);
-    // one transform of the zero spectra: whatever the plan's inverse path allocates on its first call exists before a capture
-    if (!rc) rc = spdy_spec_to_grid_dev(p, p->tab.kx, s->d_spec, nullptr, 1, s->d_pattern);
+    int rc = restart(s, 0, nmem, seeds);
+    // one transform of the zero spectra of all members: whatever the plan's inverse path allocates on its first call of this size
+    // exists before a capture
+    if (!rc) rc = spdy_spec_to_grid_dev(p, (int)nk, s->d_spec, nullptr, 1, s->d_pattern);
     if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(SPDY_ERR_HIP, "sppt_create: the first transform failed");
     return rc ? cleanup(rc) : SPDY_OK;
+}
+
+int spdy_sppt_create(spdy_plan *p, int nsteps, const double *mu, unsigned long long seed, spdy_sppt **out)
+{
+    return spdy_ens_sppt_create(p, 1, nsteps, mu, &seed, out);
+}
+
+int spdy_sppt_members(const spdy_sppt *s)
+{
+    NEED_SPPT(s);
+    return s->nmem;
 }
 
 int spdy_sppt_destroy(spdy_sppt *s)
@@ -71,14 +95,17 @@ int spdy_sppt_destroy(spdy_sppt *s)
     return SPDY_OK;
 }
 
-int spdy_sppt_reset(spdy_sppt *s, unsigned long long seed)
+int spdy_ens_sppt_reset(spdy_sppt *s, int member, unsigned long long seed)
 {
     NEED_SPPT(s);
+    RC(need_member(s, member));
     spdy_plan *p = s->plan;
     NOT_CAPTURING(p, "spdy_sppt_reset (upload)");
     NEED_DEVICE(p);
-    return restart(s, seed);
+    return restart(s, member, 1, &seed);
 }
+
+int spdy_sppt_reset(spdy_sppt *s, unsigned long long seed) { return spdy_ens_sppt_reset(s, 0, seed); }
 
 int spdy_sppt_table(const spdy_sppt *s, const char *name, double *buf, int cap)
 {
@@ -104,34 +131,38 @@ int spdy_sppt_field(spdy_sppt *s, const char *name, double **d_ptr)
     return SPDY_OK;
 }
 
-int spdy_sppt_draws(spdy_sppt *s, long long *draws)
+int spdy_ens_sppt_draws(spdy_sppt *s, int member, long long *draws)
 {
     NEED_SPPT(s);
+    RC(need_member(s, member));
     if (!draws) return fail(SPDY_ERR_ARG, "null result pointer");
     spdy_plan *p = s->plan;
     NOT_CAPTURING(p, "spdy_sppt_draws (download)");
     NEED_DEVICE(p);
     spdy::SpptState h{};
-    HIP_TRY(hipMemcpyAsync(&h, s->d_state, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(&h, s->d_state + member, sizeof(h), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     *draws = (long long)h.draws;
     return SPDY_OK;
 }
+
+int spdy_sppt_draws(spdy_sppt *s, long long *draws) { return spdy_ens_sppt_draws(s, 0, draws); }
 
 int spdy_sppt_advance_dev(spdy_sppt *s, const double *d_eta)
 {
     NEED_SPPT(s);
     spdy_plan *p = s->plan;
     NEED_DEVICE(p);
+    const int nk = s->nmem * p->tab.kx;
     spdy::SpptNoise a{};
-    a.n = (int)coefs(p); a.nspec = p->tab.mx * p->tab.nx;
+    a.n = (int)coefs(p); a.nspec = p->tab.mx * p->tab.nx; a.nmem = s->nmem;
     a.state = s->d_state; a.sigma = s->d_sigma; a.eta_in = d_eta; a.eta = s->d_eta; a.spec = s->d_spec;
     a.phi = s->tab.phi[0]; a.first = s->tab.first[0];
     KERNEL(spdy::launch_sppt_noise(a, p->stream));
     // sppt.f90:93-95: the reference never truncates sppt_spec and draws imaginary parts for m = 0; its spec_to_grid reads neither
-    // (legendre.f90:93, fourier.f90:34-38), and neither does the plan's inverse
-    RC(spdy_spec_to_grid_dev(p, p->tab.kx, s->d_spec, nullptr, 1, s->d_pattern));
-    KERNEL(spdy::launch_sppt_clip(s->d_pattern, (long)(grid_elems(p) * p->tab.kx), s->d_state, p->stream));
+    // (legendre.f90:93, fourier.f90:34-38), and neither does the plan's inverse.  The members are nmem * kx fields of ONE launch.
+    RC(spdy_spec_to_grid_dev(p, nk, s->d_spec, nullptr, 1, s->d_pattern));
+    KERNEL(spdy::launch_sppt_clip(s->d_pattern, (long)(grid_elems(p) * p->tab.kx), s->nmem, s->d_state, p->stream));
     return SPDY_OK;
 }
 

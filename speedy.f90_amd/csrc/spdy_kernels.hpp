@@ -378,22 +378,25 @@ struct ChainCols {
 };
 hipError_t launch_column_chain(const ChainCols &a, hipStream_t s);
 
-// SPPT (csrc/spdy_sppt.hip; sppt.f90, physics.f90:207-222).  The pattern object's counter and seed live in device memory, so
-// one captured advance serves the first step and every later one and each replay draws new noise.
+// SPPT (csrc/spdy_sppt.hip; sppt.f90, physics.f90:207-222).  The pattern object's counters and seeds live in device memory, so
+// one captured advance serves the first step and every later one and each replay draws new noise.  A pattern object holds nmem
+// patterns, member-major (member e starts e * kx fields in), and one {draws, seed} per member.
 struct SpptState { unsigned long long draws, seed; };
-// gen_sppt up to the AR(1) update: one thread per complex coefficient of the (mx, nx, kx) rectangle in storage order.  eta_in
-// null: the coefficient's two Philox4x32-10 draws (include/spdy.h); otherwise eta_in is copied.  Both parts are clipped to +-10,
-// eta is stored, and spec = first * sigma * eta where state->draws == 0, phi * spec + sigma * eta otherwise.
+// gen_sppt up to the AR(1) update: one thread per complex coefficient of a member's (mx, nx, kx) rectangle in storage order, the
+// member in blockIdx.y.  eta_in null: the coefficient's two Philox4x32-10 draws (include/spdy.h) with the member's seed and
+// counter and the index INSIDE the member; otherwise eta_in is copied.  Both parts are clipped to +-10, eta is stored, and spec =
+// first * sigma * eta where the member's draws == 0, phi * spec + sigma * eta otherwise: the branch is the member's own.
 struct SpptNoise {
-    int n, nspec;                                    // mx * nx * kx coefficients, mx * nx per level
-    const SpptState *state;
-    const double *sigma, *eta_in;                    // (mx, nx); (mx, nx, kx) complex or null
-    double *eta, *spec;                              // (mx, nx, kx) complex
+    int n, nspec, nmem;                              // mx * nx * kx coefficients per member, mx * nx per level
+    const SpptState *state;                          // [nmem]
+    const double *sigma, *eta_in;                    // (mx, nx), shared; (mx, nx, kx, nmem) complex or null
+    double *eta, *spec;                              // (mx, nx, kx, nmem) complex
     double phi, first;
 };
 hipError_t launch_sppt_noise(const SpptNoise &a, hipStream_t s);
-// the clip of the transformed pattern to +-1 in place, n = ix * il * kx values; thread 0 then counts the advance (draws += 1)
-hipError_t launch_sppt_clip(double *pattern, long n, SpptState *state, hipStream_t s);
+// the clip of the transformed patterns to +-1 in place, n = ix * il * kx values per member, the member in blockIdx.y; the member's
+// thread 0 then counts its advance (draws += 1)
+hipError_t launch_sppt_clip(double *pattern, long n, int nmem, SpptState *state, hipStream_t s);
 // physics.f90:85-88 and :207-222 around the five calls: save copies the dynamics tendencies (ttend, qtend on every level, utend,
 // vtend on level kx) into `save`, (2 kx + 2) fields each g doubles long; apply makes each tendency
 // (1 + pattern * mu(k)) * (tend - tend_dyn) + tend_dyn.  pattern is (ix, il, kx) per state; mu is top down.

@@ -58,6 +58,8 @@ struct spdy_plan {
     double *sppt_ws = nullptr;        // SPPT on gridded states: the dynamics tendencies, (2kx+2) grids per state, max_batch states
                                       // (spdy_column_physics_sppt_workspace)
     double *sppt_grid = nullptr;      // SPPT from spectra: one state's (2kx+2) grids (spdy_physics_sppt_workspace)
+    // SPPT from the spectra of nmem members: (2kx+2) fields of nmem grids; grows like ens_physics_grid (spdy_ens_physics_sppt_workspace)
+    struct SpptGrids { double *g = nullptr; int nmem = 0; } ens_sppt_grid;
     int physics_fused = -1;           // column physics in one launch: -1 unset (spdy_physics_dev only), 0 never, 1 always (spdy_plan_set_option)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
@@ -79,14 +81,16 @@ struct spdy_plan {
     std::vector<struct spdy_comm *> comms;   // communicators created on this plan that are still alive (spdy_api_shard.hip)
 };
 
-// The SPPT pattern behind include/spdy.h's spdy_sppt (csrc/spdy_api_sppt.hip); spdy_physics_sppt_dev reads pattern and mu.
+// The SPPT patterns behind include/spdy.h's spdy_sppt (csrc/spdy_api_sppt.hip), one per member, member-major like every ensemble
+// array; spdy_physics_sppt_dev and spdy_ens_physics_sppt_dev read pattern and mu.  The tables are shared by the members.
 struct spdy_sppt {
     spdy_plan *plan = nullptr;
+    int nmem = 1;
     spdy::SpptTables tab;
-    spdy::SpptState *d_state = nullptr;   // the counter and the seed
+    spdy::SpptState *d_state = nullptr;   // [nmem] each member's counter and seed
     double *d_sigma = nullptr;            // (mx, nx)
-    double *d_eta = nullptr, *d_spec = nullptr;   // (mx, nx, kx) complex
-    double *d_pattern = nullptr;          // (ix, il, kx)
+    double *d_eta = nullptr, *d_spec = nullptr;   // (mx, nx, kx, nmem) complex
+    double *d_pattern = nullptr;          // (ix, il, kx, nmem)
 };
 
 // The run's guard behind include/spdy.h's spdy_diagnostics (csrc/spdy_api_diagnostics.hip): one device allocation, history | limits | state.

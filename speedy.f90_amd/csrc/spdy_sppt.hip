@@ -3,7 +3,8 @@
 // the column physics.  The inverse transform between the update and the clip is the plan's own (csrc/spdy_api_sppt.hip).
 //
 // The generator is Philox4x32-10 as include/spdy.h defines it: key (seed lo, seed hi), counter (coefficient index in storage
-// order, part, draws lo, draws hi), so a coefficient's noise depends on (seed, draws, index) only -- not on the launch geometry.
+// order inside the member, part, draws lo, draws hi), so a coefficient's noise depends on (seed, draws, index) only -- not on the
+// launch geometry, and not on the ensemble the member travels in.
 // randn is the reference's (sppt.f90:102-116), float32 literals widened: u = sqrt(-2 log r1), v = (2.0f * 6.28318530718f) r2
 // (4 pi: the reference's factor), u sin v.  Full-precision log, sqrt and sin, no contraction.
 #include "spdy_columns.hpp"
@@ -44,37 +45,41 @@ __device__ inline double sppt_randn(unsigned idx, unsigned part, unsigned long l
 // min(lim, |x|) * sign(1, x) (sppt.f90:66-68, :98)
 __device__ inline double sppt_clip(double x, double lim) { return fmin(lim, fabs(x)) * copysign(1.0, x); }
 
+// the member is blockIdx.y: its own {draws, seed}, its own branch, and the generator's index counts inside the member, so member e
+// draws what a one-member object with its seed draws and the 32-bit counter word is bounded by mx * nx * kx whatever nmem is
 __global__ __launch_bounds__(SPPT_BLOCK) void sppt_noise_kernel(const SpptNoise a)
 {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * SPPT_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    const unsigned long long draws = a.state->draws, seed = a.state->seed;
+    const SpptState *const st = a.state + blockIdx.y;
+    const unsigned long long draws = st->draws, seed = st->seed;
+    const long o = 2 * ((long)blockIdx.y * a.n + i);
     double re, im;
     if (a.eta_in) {
-        re = a.eta_in[2 * (long)i]; im = a.eta_in[2 * (long)i + 1];
+        re = a.eta_in[o]; im = a.eta_in[o + 1];
     } else {
         re = sppt_randn((unsigned)i, 0u, draws, seed); im = sppt_randn((unsigned)i, 1u, draws, seed);
     }
     re = sppt_clip(re, 10.0); im = sppt_clip(im, 10.0);
-    a.eta[2 * (long)i] = re; a.eta[2 * (long)i + 1] = im;
+    a.eta[o] = re; a.eta[o + 1] = im;
     const double sg = a.sigma[i % a.nspec];
     double sr, si;
     if (draws == 0) {                                 // sppt.f90:84, left to right
         const double c = a.first * sg;
         sr = c * re; si = c * im;
     } else {                                          // :89
-        sr = a.phi * a.spec[2 * (long)i] + sg * re; si = a.phi * a.spec[2 * (long)i + 1] + sg * im;
+        sr = a.phi * a.spec[o] + sg * re; si = a.phi * a.spec[o + 1] + sg * im;
     }
-    a.spec[2 * (long)i] = sr; a.spec[2 * (long)i + 1] = si;
+    a.spec[o] = sr; a.spec[o + 1] = si;
 }
 
 __global__ __launch_bounds__(SPPT_BLOCK) void sppt_clip_kernel(double *pattern, long n, SpptState *state)
 {
     const long i = (long)blockIdx.x * SPPT_BLOCK + threadIdx.x;
     // every launch before this one on the stream has read the counter (the noise kernel), every launch after it sees the new one
-    if (i == 0) state->draws = state->draws + 1;
-    if (i < n) pattern[i] = sppt_clip(pattern[i], 1.0);
+    if (i == 0) state[blockIdx.y].draws = state[blockIdx.y].draws + 1;
+    if (i < n) pattern[(long)blockIdx.y * n + i] = sppt_clip(pattern[(long)blockIdx.y * n + i], 1.0);
 }
 
 __global__ __launch_bounds__(COLUMN_BLOCK) void sppt_save_kernel(const SpptCols a)
@@ -123,15 +128,17 @@ dim3 column_grid(const SpptCols &a) { return dim3((unsigned)(((long)a.nb * a.nco
 
 hipError_t launch_sppt_noise(const SpptNoise &a, hipStream_t s)
 {
-    if (a.n <= 0 || a.nspec <= 0 || a.n % a.nspec || !a.state || !a.sigma || !a.eta || !a.spec) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sppt_noise_kernel, dim3((a.n + SPPT_BLOCK - 1) / SPPT_BLOCK), dim3(SPPT_BLOCK), 0, s, a);
+    if (a.n <= 0 || a.nspec <= 0 || a.n % a.nspec || a.nmem < 1 || a.nmem > 65535 || !a.state || !a.sigma || !a.eta || !a.spec)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sppt_noise_kernel, dim3((a.n + SPPT_BLOCK - 1) / SPPT_BLOCK, a.nmem), dim3(SPPT_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_sppt_clip(double *pattern, long n, SpptState *state, hipStream_t s)
+hipError_t launch_sppt_clip(double *pattern, long n, int nmem, SpptState *state, hipStream_t s)
 {
-    if (n <= 0 || !pattern || !state) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sppt_clip_kernel, dim3((unsigned)((n + SPPT_BLOCK - 1) / SPPT_BLOCK)), dim3(SPPT_BLOCK), 0, s, pattern, n, state);
+    if (n <= 0 || nmem < 1 || nmem > 65535 || !pattern || !state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sppt_clip_kernel, dim3((unsigned)((n + SPPT_BLOCK - 1) / SPPT_BLOCK), nmem), dim3(SPPT_BLOCK), 0, s, pattern, n,
+                       state);
     return hipGetLastError();
 }
 

@@ -25,8 +25,9 @@ guard.check_dev on time level 2 (ens.vor[1], ens.div[1], ens.t[1]); the host's n
 model.couple_dev(day, hfluxn, shf, evap, ssrd).
 
 `step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  `output` gives every member's float32
-snapshot (input_output.f90:184-206) and the ensemble mean and spread from one call (include/spdy.h, "ensemble output").  Not
-covered: SPPT (one pattern object holds one pattern), the level-sharded step."""
+snapshot (input_output.f90:184-206) and the ensemble mean and spread from one call (include/spdy.h, "ensemble output").  SPPT:
+physics["sppt"], a Sppt with one pattern per member, is advanced and applied by `step` (include/spdy.h, "SPPT").  Not covered: the
+level-sharded step."""
 import numpy as np
 
 PROG = ("vor", "div", "t", "tr", "ps")
@@ -108,16 +109,21 @@ class Ensemble:
             getattr(self, n).copy_(torch.as_tensor(np.ascontiguousarray(st[n], np.complex128)))
 
     # ------------------------------------------------------------------ the step
-    def physics_workspace(self):
-        """before a capture that contains a step with physics"""
-        self.sp.ens_physics_workspace(self.nmem)
+    def physics_workspace(self, sppt=False):
+        """before a capture that contains a step with physics; sppt: for a step whose physics has "sppt" """
+        if sppt:
+            self.sp.ens_physics_sppt_workspace(self.nmem)
+        else:
+            self.sp.ens_physics_workspace(self.nmem)
 
     def step(self, j1, j2, dt, physics=None, eps=None):
         """step(j1, j2, dt) for every member.  The dynamics read time level j2 (tendencies.f90:89-107), the physics time level 1
         (physics.f90:94-104).  physics: None (adiabatic) or a dict with "sw" (compute the shortwave on this step), "bnd" (dict of
         SFC_BOUNDARY fields, (E, il, ix) each), "albsfc" (E, il, ix), "rad" (E radiation states back to back) and optionally "out"
-        (spdy_column_physics_out as a dict, every field E states long).  eps: the Robert filter's coefficient; by default
-        the reference's, 0 when j1 == 1 and rob otherwise (time_stepping.f90:108-112)."""
+        (spdy_column_physics_out as a dict, every field E states long) and "sppt" (a Sppt of this plan with nmem == E: it is
+        advanced, all members in three launches, and each member's pattern multiplies the physics' part of its tendencies; the
+        reference advances once per physics call, the start-up steps included).  eps: the Robert filter's coefficient; by
+        default the reference's, 0 when j1 == 1 and rob otherwise (time_stepping.f90:108-112)."""
         sp, E, kx, lv = self.sp, self.nmem, self.kx, j2 - 1
         eps = (0.0 if j1 == 1 else self.rob) if eps is None else eps
         flat = lambda a: a.view((-1,) + tuple(a.shape[-2:]))
@@ -129,8 +135,16 @@ class Ensemble:
                                    self.PL)
         if physics is not None:
             sp.ens_geopotential_dev(E, self.t[0], self.phis, self.phim)
-            sp.ens_physics_dev(E, physics["sw"], self.vor[0], self.div[0], self.t[0], self.tr[0], self.phim, self.ps[0], physics["bnd"],
-                               physics["albsfc"], physics["rad"], self.utend, self.vtend, self.ttend, self.qtend, physics.get("out"))
+            args = (physics["sw"], self.vor[0], self.div[0], self.t[0], self.tr[0], self.phim, self.ps[0], physics["bnd"],
+                    physics["albsfc"], physics["rad"], self.utend, self.vtend, self.ttend, self.qtend, physics.get("out"))
+            pat = physics.get("sppt")
+            if pat is None:
+                sp.ens_physics_dev(E, *args)
+            else:
+                if pat.nmem != E:
+                    raise ValueError("physics[\"sppt\"] must hold one pattern per member")
+                pat.advance_dev()
+                sp.ens_physics_sppt_dev(E, pat, *args)
         sp.set_option("ens_member_qcorh", 1 if self.member_qcorh else 0)      # read when the call below is enqueued
         sp.ens_direct_batch_spectral_step_dev(E, self.U, self.V, self.PL, self.pvor, self.pdiv, self.pspec, self.vor, self.div, self.t,
                                               self.tr, self.ps, self.phis, self.tcorh, self.qcorh, self.sdrag, j1, dt, eps, self.wil,

@@ -986,6 +986,48 @@ module spdy_c
             type(spdy_column_physics_out), intent(in) :: out
             integer(c_int) :: rc
         end function
+        ! the ensemble form: nmem patterns in one object (seeds: nmem 64-bit values on the host), one advance for all members
+        function spdy_ens_sppt_create(plan, nmem, nsteps, mu, seeds, s) bind(C, name="spdy_ens_sppt_create") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, mu, seeds
+            integer(c_int), value :: nmem, nsteps
+            type(c_ptr), intent(out) :: s
+            integer(c_int) :: rc
+        end function
+        function spdy_sppt_members(s) bind(C, name="spdy_sppt_members") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: s
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_sppt_reset(s, member, seed) bind(C, name="spdy_ens_sppt_reset") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: s
+            integer(c_int), value :: member
+            integer(c_long_long), value :: seed
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_sppt_draws(s, member, draws) bind(C, name="spdy_ens_sppt_draws") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: s
+            integer(c_int), value :: member
+            integer(c_long_long), intent(out) :: draws
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_physics_sppt_workspace(plan, nmem) bind(C, name="spdy_ens_physics_sppt_workspace") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int), value :: nmem
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_physics_sppt_dev(plan, nmem, s, compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, &
+                & ttend, qtend, out) bind(C, name="spdy_ens_physics_sppt_dev") result(rc)
+            import :: c_int, c_ptr, spdy_sfc_boundary, spdy_column_physics_out
+            type(c_ptr), value :: plan, s, vor, div, t, q, phi, ps, albsfc, rad_state, utend, vtend, ttend, qtend
+            integer(c_int), value :: nmem, compute_sw
+            type(spdy_sfc_boundary), intent(in) :: bnd
+            type(spdy_column_physics_out), intent(in) :: out
+            integer(c_int) :: rc
+        end function
         ! diagnostics (include/spdy.h): check_diagnostics on the device, the history ring and the sticky stop flag
         function spdy_diagnostics_create(plan, capacity, first_step, d) bind(C, name="spdy_diagnostics_create") result(rc)
             import :: c_int, c_ptr, c_long_long

@@ -24,10 +24,17 @@ and it gives no statistics), and the call's inverse batch captured alone.  The e
 first and the last -- a difference of two graph replays, not a kernel trace -- and its byte model ((5 kx + 1) E FP64 grids read
 once, (E + 2) (5 kx + 1) float32 grids written) is given as a fraction of 8 TB/s, as is the whole call's.
 
+--sppt measures SPPT for an ensemble instead (include/spdy.h, "SPPT"; at T30 L8, E = 1, 4 and 16 and 100 replays per timing unless
+told otherwise), both sides of each comparison in the same run: (a) the captured advance of one pattern object of E members --
+three launches whatever E -- against E captured advances of single objects replayed back to back; (b) the captured ensemble step
+with the whole physics and SPPT (Ensemble.step with physics["sppt"]) against the same step without SPPT and against E single-state
+captured steps with SPPT (tests/modelstep.py's sppt_physics), each on a state, a workspace and a pattern object of its own.
+
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
     python tools/ensemble_rate.py --coupled --members 1 2 4 8 16
     python tools/ensemble_rate.py --output --json profiles/ensemble_output_rate.json
+    python tools/ensemble_rate.py --sppt --json profiles/ensemble_sppt_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
 import ctypes
@@ -324,22 +331,128 @@ def run_output(tag, members, reps, repeats, label, rows):
     sp.close()
 
 
+def run_sppt(tag, members, reps, repeats, label, rows):
+    """graph replays of (a) the ensemble advance and E single advances, (b) the ensemble step with the physics without and with SPPT
+    and E single-state steps with SPPT"""
+    from oracle.pyoracle import Oracle, build
+    build()
+    kx = VARIANTS[tag][3]
+    o = Oracle(*VARIANTS[tag])
+    if tag in synth.SIGMA_SETS:
+        o.set_sigma(synth.SIGMA_SETS[tag])
+    emax = max(members)
+    sp = moist.plan(tag, emax * (4 * kx + 4))
+    case = physstep.Case(tag, sp, o)
+    sp.surface_set_orography(case.phis0)
+    dt = physstep.DT[tag]
+    sp.initialize_implicit(dt)
+    sp.physics_sppt_workspace()
+    # the single-state steps: a state, a workspace, a radiation state and a pattern object per member
+    D0 = modelstep.device_state(case.st)
+    P0 = modelstep.physics_buffers(sp, case.bnd, 0.0)
+    modelstep.step(sp, {n: v.clone() for n, v in D0.items()}, modelstep.Workspace(sp), dt, physics=modelstep.whole_physics(P0, True))
+    sp.synchronize()
+    rad0 = P0["rad"].clone()                                   # after a shortwave step: the radiation state is whole
+    seed = lambda e: 1000 + e
+    singles = []
+    for e in range(emax):
+        D, W = {n: v.clone() for n, v in D0.items()}, modelstep.Workspace(sp)
+        P = {"bnd": P0["bnd"], "rad": rad0.clone()}
+        pat = s.Sppt(sp, 36, seed=seed(e))
+        torch.cuda.synchronize()
+        with sp.graph_capture() as ga:
+            pat.advance_dev()
+        with sp.graph_capture() as gs:
+            modelstep.step(sp, D, W, dt, physics=modelstep.sppt_physics(P, False, pat))
+        singles.append((D, W, P, pat, ga, gs))
+    fns, nodes, rearms, keep = {}, {}, [], []
+
+    def rearm_singles():
+        for D, _, P, pat, _, _ in singles:
+            for n in modelstep.PROG:
+                D[n].copy_(D0[n])
+            P["rad"].copy_(rad0)
+    rearms.append(rearm_singles)
+    for E in members:
+        en = s.Ensemble(sp, E)
+        en.set_shared(case.st)
+        for e in range(E):
+            en.set_member(e, case.st)
+        dev = physstep.device_boundary(case.bnd, sp.il, sp.ix)
+        bnd = {n: v.expand((E,) + tuple(v.shape[1:])).contiguous() for n, v in dev.items()}
+        PE = {"bnd": bnd, "albsfc": bnd["albsfc"], "rad": rad0.repeat(E), "sw": False}
+        pat = s.Sppt(sp, 36, seeds=[seed(e) for e in range(E)])
+        en.physics_workspace(sppt=True)
+        start = {n: getattr(en, n).clone() for n in modelstep.PROG}
+        torch.cuda.synchronize()
+        graphs = {}
+        with sp.graph_capture() as g:
+            pat.advance_dev()
+        graphs["advance E=%d ensemble" % E] = g
+        with sp.graph_capture() as g:
+            en.step(2, 2, dt, PE, eps=modelstep.ROB)
+        graphs["step E=%d ensemble physics" % E] = g
+        with sp.graph_capture() as g:
+            en.step(2, 2, dt, dict(PE, sppt=pat), eps=modelstep.ROB)
+        graphs["step E=%d ensemble physics + SPPT" % E] = g
+        for n, g in graphs.items():
+            fns[n], nodes[n] = g.launch, g.num_nodes()
+
+        def all_of(which, E=E):
+            def fn():
+                for x in singles[:E]:
+                    x[which].launch()
+            return fn
+        fns["advance E=%d single objects" % E], nodes["advance E=%d single objects" % E] = all_of(4), E * singles[0][4].num_nodes()
+        fns["step E=%d single states physics + SPPT" % E] = all_of(5)
+        nodes["step E=%d single states physics + SPPT" % E] = E * singles[0][5].num_nodes()
+
+        def rearm(en=en, start=start, PE=PE, E=E):
+            for n, v in start.items():
+                getattr(en, n).copy_(v)
+            PE["rad"].copy_(rad0.repeat(E))
+        rearms.append(rearm)
+        keep.append((en, PE, pat, graphs))
+    t = time_interleaved(fns, lambda: [r() for r in rearms], reps, repeats)
+    for name, (med, lo, hi) in t.items():
+        E = int(name.split("=")[1].split()[0])
+        row = {"label": label, "size": tag, "form": name, "members": E, "nodes": nodes[name], "us": round(med, 2), "us_min": round(lo, 2),
+               "us_max": round(hi, 2), "us_per_member": round(med / E, 2)}
+        if name.endswith("ensemble"):
+            row["speedup_vs_single_objects"] = round(t["advance E=%d single objects" % E][0] / med, 2)
+        if name.endswith("ensemble physics + SPPT"):
+            row["us_over_step_without_sppt"] = round(med - t["step E=%d ensemble physics" % E][0], 2)
+            row["speedup_vs_single_states"] = round(t["step E=%d single states physics + SPPT" % E][0] / med, 2)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for _, _, _, graphs in keep:
+        for g in graphs.values():
+            g.close()
+    for x in singles:
+        x[4].close(); x[5].close()
+    sp.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes", nargs="+", default=["t30", "t63k16"])
-    ap.add_argument("--members", nargs="+", type=int, default=[1, 2, 4, 8, 16, 32])
+    ap.add_argument("--sizes", nargs="+")
+    ap.add_argument("--members", nargs="+", type=int)
     ap.add_argument("--single-only", action="store_true")
     ap.add_argument("--coupled", action="store_true")
     ap.add_argument("--output", action="store_true")
+    ap.add_argument("--sppt", action="store_true")
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
-    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--reps", type=int)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--json")
     a = ap.parse_args()
+    a.sizes = a.sizes or (["t30"] if a.sppt else ["t30", "t63k16"])
+    a.members = a.members or ([1, 4, 16] if a.sppt else [1, 2, 4, 8, 16, 32])
+    a.reps = a.reps or (100 if a.sppt else 200)
     if a.single_only:          # a library from before the ensemble entry points: bind (on first use) without them
         from speedy_f90_amd import _lib
-        for n in [n for n in _lib.SIGNATURES if n.startswith("spdy_ens_")]:
+        for n in [n for n in _lib.SIGNATURES if n.startswith("spdy_ens_") or n == "spdy_sppt_members"]:
             del _lib.SIGNATURES[n]
     batched = True
     if a.earlier_library:
@@ -347,7 +460,9 @@ def main():
     rows = []
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
-            if a.output:
+            if a.sppt:
+                run_sppt(tag, a.members, a.reps, a.repeats, a.label, rows)
+            elif a.output:
                 run_output(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.coupled:
                 run_coupled(tag, a.members, a.reps, a.repeats, a.label, rows, batched)
