@@ -927,6 +927,74 @@ int spdy_ens_diagnostics_stopped(spdy_diagnostics *d, long long *bad_step);
 int spdy_diagnostics_field(spdy_diagnostics *d, const char *name, void **d_ptr);
 int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf, int cap);
 
+/* ---- ensemble analysis: the LETKF update of all members on the device -----------------------------------------
+ * The reference has no analysis; this section defines one, and tests/letkf.py restates it in NumPy.  A forecast-analysis cycle
+ * then stays in device memory: Ensemble steps, spdy_ens_letkf_dev, first_step again.
+ * State analysed, per member: the gridded true wind u, v, t, q (the model's g/kg), each with kx levels, and ps = log(p/p0).  An
+ * observation {var: SPDY_OBS_*; lev 0..kx-1 (ignored for PS); lon, lat in degrees; value; error > 0} is in those units.
+ *   operator      H is bilinear in longitude and latitude at model level lev.  Column i is at i*360/ix, periodic; row j at
+ *                 -/+ asin(sia_half), south first (geometry.f90:70-75); poleward of the outermost row that row has weight 1.  The
+ *                 four points are (j0,i0) (j0,i1) (j1,i0) (j1,i1) with weights (1-a)(1-b), a(1-b), (1-a)b, ab, and
+ *                 hx_e = ((w0 x0 + w1 x1) + w2 x2) + w3 x3; hxmean = (sum of hx_e, e ascending) / E; Y_e = hx_e - hxmean;
+ *                 d = value - hxmean.
+ *   localisation  w = GC(dist/c_h) GC(|ln fsg[k] - ln sigma_o|/c_v) for column c, level k and observation o: GC the fifth-order
+ *                 function of Gaspari and Cohn (support r < 2), c_h = sigma_h sqrt(10/3), c_v = sigma_v sqrt(10/3), sigma_o =
+ *                 fsg[lev] (1 for PS), dist = 2 rearth asin(min(1, |p_c - p_o|/2)) on unit vectors, rearth = 6.371e6 m.
+ *                 sigma_v <= 0: no vertical factor.  An observation with w == 0 takes no part in any operation.
+ *   local problem r_o = w_o / error_o^2; C = sum_o r_o Y_o Y_o^T, b = sum_o r_o Y_o d_o, each element summed over o ascending;
+ *                 A = (E-1)/rho I + C = V Lambda V^T; wbar = V Lambda^-1 V^T b; W = V diag(sqrt((E-1)/lambda_i)) V^T;
+ *                 T = W + wbar 1^T - I.
+ *   increments    dx_e = sum_f (x_f - xmean) T[f][e] for every analysed variable at (c, k); ps uses T of level kx-1.  With no
+ *                 observation in range and rho = 1, T and the increments are exactly zero; with rho != 1 they are pure inflation.
+ * spdy_letkf_create allocates everything the calls below use (observation tables for max_obs observations, (4 kx + 1) nmem grids
+ * and as many spectra) and runs one inverse and one direct batch of the analysis' shape, so nothing is allocated afterwards and
+ * both *_dev calls can be captured.  2 <= nmem <= 32 and the local problems of kx levels must fit a compute unit's LDS (kx = 16 at
+ * nmem = 32 does); max_batch >= nmem (2 kx + 1); the plan needs sigma levels (their ln fsg is read here, once).
+ * spdy_letkf_set_localization: sigma_h in metres (> 0), sigma_v in ln sigma, rho > 0; read when an analysis call is enqueued, so a
+ * captured graph keeps the values of its capture.  spdy_letkf_set_obs validates every field of every observation before it
+ * changes anything, builds the stencils, unit vectors, ln sigma_o and 1/error^2 on the host and uploads them (stream-ordered,
+ * synchronising; not inside a capture; should a copy fail, SPDY_ERR_HIP, the object is left with no observations, not with a
+ * mixture); the device arrays do not move, so a captured analysis replays with the observations of
+ * the latest set_obs as long as their number is that of the capture.  spdy_letkf_table (the host side; returns the count; buf NULL
+ * = count only): "stencil_index" (4 per observation, j*ix+i as doubles), "stencil_weight" (4), "unit" (3), "lnsigma", "rinv".
+ * spdy_letkf_field (device, valid after an analysis call): "hx" (nmem per observation), "hxmean", "y" (nmem), "departure".
+ * spdy_letkf_analyse_grid_dev: the ensemble on the grid, member-major, u .. q (ix,il,kx,nmem), ps (ix,il,nmem); the increments in
+ * the same shapes; an output may be its input.  Two launches: the observation kernel, then one workgroup per grid column that
+ * scans the observations in chunks, keeps those in range in ascending order (ballot and prefix counts, no atomics), forms C and b
+ * of every level in LDS, solves each level by a parallel cyclic Jacobi (round-robin pairs; an odd E is padded by a decoupled
+ * row; sweeps end at convergence or after a fixed count) and writes the increments.  Any number of observations may be in range
+ * of a column.  Results are bit-reproducible, and a column's result depends on no observation out of its range.
+ * spdy_ens_letkf_dev: the analysis of time level 1 of an ensemble ("ensemble time step" above: layout), in place -- ONE
+ * spdy_inverse_batch_segs_dev (nmem*kx pairs, the segments t | q of nmem*kx fields and ps of nmem, read in place), the two
+ * kernels, ONE spdy_direct_batch_dev (nmem*kx pairs with kcos = 2, 2 nmem kx + nmem plain fields), and a kernel that adds
+ * vdspec(du, dv) to vor and div and grid_to_spec(dt | dq | dps) to t, q and ps; a spectral increment equal to zero leaves the
+ * coefficient's bits, so with no observations and rho = 1 the state is unchanged.  Five launches whatever nmem is -- six where the
+ * direct batch streams (16 MB of grids or more: spdy_direct_batch_dev then goes out as its two launches).  Time level 2
+ * is not touched and phi is stale afterwards: the run continues with first_step, as a model started from an analysis does.
+ * Members are coupled by construction: a non-finite member makes every column it touches non-finite (as NaN, after the full
+ * count of sweeps), and there is no member mask -- the caller builds the analysis ensemble from members the guard has not stopped.
+ * Checks, in this order -- create: a NULL plan, nmem outside [2, 32], max_obs < 0, a NULL result pointer, max_batch, the LDS
+ * size SPDY_ERR_ARG; no sigma levels, an open capture SPDY_ERR_STATE.  set_obs: a NULL object, nobs outside [0, max_obs], NULL
+ * observations, the first invalid field of the first invalid observation (var, lev, lon, lat, value, error) SPDY_ERR_ARG; an open
+ * capture SPDY_ERR_STATE.  The *_dev calls: a NULL object SPDY_ERR_ARG; no localisation set SPDY_ERR_STATE; a NULL pointer
+ * SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last (spdy_letkf_field: after its name check).  create, set_localization,
+ * set_obs and table work on a host-only plan.  A failing call enqueues nothing.                                                 */
+typedef struct spdy_letkf spdy_letkf;
+enum { SPDY_OBS_U, SPDY_OBS_V, SPDY_OBS_T, SPDY_OBS_Q, SPDY_OBS_PS };
+typedef struct {
+    int var, lev;
+    double lon, lat, value, error;
+} spdy_obs;
+int spdy_letkf_create(spdy_plan *plan, int nmem, int max_obs, spdy_letkf **l);
+int spdy_letkf_destroy(spdy_letkf *l);
+int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h_m, double sigma_v_lnsigma, double rho);
+int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host);
+int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap);
+int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr);
+int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg,
+                                const double *psg, double *du, double *dv, double *dt, double *dq, double *dps);
+int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps);
+
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,
  * time_stepping.f90:56-121: ~90 inverse and ~70 direct transforms plus the spectral operators, 7 horizontal

@@ -8,6 +8,7 @@ Only what the hot path needs lives here:
     columns.py   the column physics and the surface models of the same plan: one field table,
                  the ctypes structures and output buffers derived from it
     ensemble.py  E model states through one time step's launches: the layout, the views, the step
+    letkf.py     the ensemble analysis: observations in, the LETKF update of all members on the device
 
 The directory name contains a dot, so import it through the repo-root shim
 ``import speedy_f90_amd`` (speedy_f90_amd.py).
@@ -16,4 +17,5 @@ from ._lib import LIB_PATH, SpdyError, build, load  # noqa: F401
 from .spectral import (RESOLUTIONS, DeviceField, Diagnostics, DiagnosticsStop, Graph, Spectral, Sppt, SurfaceModel,  # noqa: F401
                        check)
 from .ensemble import Ensemble  # noqa: F401
+from .letkf import OBS_PS, OBS_Q, OBS_T, OBS_U, OBS_V, Letkf  # noqa: F401
 from . import sharding  # noqa: F401

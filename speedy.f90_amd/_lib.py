@@ -172,6 +172,14 @@ SIGNATURES = {
     "spdy_diagnostics_read": [c_void_p, ctypes.c_longlong, c_int, c_void_p],
     "spdy_diagnostics_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
     "spdy_diagnostics_format": [c_int, ctypes.c_longlong, c_void_p, c_char_p, c_int],
+    "spdy_letkf_create": [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)],
+    "spdy_letkf_destroy": [c_void_p],
+    "spdy_letkf_set_localization": [c_void_p, c_double, c_double, c_double],
+    "spdy_letkf_set_obs": [c_void_p, c_int, c_void_p],
+    "spdy_letkf_table": [c_void_p, c_char_p, c_void_p, c_int],
+    "spdy_letkf_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
+    "spdy_letkf_analyse_grid_dev": [c_void_p] * 11,
+    "spdy_ens_letkf_dev": [c_void_p] * 6,
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

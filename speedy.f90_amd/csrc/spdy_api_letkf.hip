@@ -1,0 +1,320 @@
+// C ABI of the ensemble analysis (include/spdy.h, "ensemble analysis"): the observation ingestion on the host, the
+// analysis of a gridded ensemble and the five-launch analysis of an ensemble's spectral state.  Kernels: csrc/spdy_letkf.hip.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "spdy_plan.hpp"
+
+using namespace spdy_detail;
+
+namespace {
+#define NEED_LETKF(l)                                                   \
+    do {                                                                \
+        if (!(l)) return fail(SPDY_ERR_ARG, "null analysis object");    \
+    } while (0)
+
+constexpr double kPi = 3.14159265358979323846;
+constexpr size_t kLdsLimit = 160 * 1024;      // LDS of a gfx950 compute unit
+
+// bilinear stencil of one observation: four grid points (j0,i0) (j0,i1) (j1,i0) (j1,i1) and their weights.  Columns are
+// periodic; poleward of the outermost row that row has weight 1.
+void stencil(const spdy_letkf *l, double lon, double lat, int *idx, double *wgt)
+{
+    const int ix = l->plan->tab.ix, il = l->plan->tab.il;
+    double x = std::fmod(lon, 360.0);
+    if (x < 0.0) x += 360.0;
+    x = x / (360.0 / ix);
+    int i0 = (int)std::floor(x);
+    double a = x - i0;
+    if (i0 >= ix) { i0 = 0; a = 0.0; }        // -1e-20 + 360 rounds to 360
+    const int i1 = (i0 + 1) % ix;
+    int j0, j1;
+    double b = 0.0;
+    const std::vector<double> &lt = l->lat;
+    if (lat <= lt[0]) j0 = j1 = 0;
+    else if (lat >= lt[il - 1]) j0 = j1 = il - 1;
+    else {
+        j0 = 0;
+        while (j0 + 2 < il && lat >= lt[j0 + 1]) ++j0;
+        j1 = j0 + 1;
+        b = (lat - lt[j0]) / (lt[j1] - lt[j0]);
+    }
+    idx[0] = j0 * ix + i0; idx[1] = j0 * ix + i1; idx[2] = j1 * ix + i0; idx[3] = j1 * ix + i1;
+    wgt[0] = (1.0 - a) * (1.0 - b); wgt[1] = a * (1.0 - b); wgt[2] = (1.0 - a) * b; wgt[3] = a * b;
+}
+
+void unit_vector(double lon, double lat, double *u)
+{
+    const double rl = lon * (kPi / 180.0), rp = lat * (kPi / 180.0);
+    u[0] = std::cos(rp) * std::cos(rl); u[1] = std::cos(rp) * std::sin(rl); u[2] = std::sin(rp);
+}
+
+int upload(spdy_plan *p, void *dst, const void *src, size_t bytes)
+{
+    if (bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream));
+    return SPDY_OK;
+}
+
+// the argument checks the two analysis calls share, in the documented order; the device last
+int analysis_ready(spdy_letkf *l, bool ptrs_ok)
+{
+    NEED_LETKF(l);
+    if (!l->loc_set) return fail(SPDY_ERR_STATE, "letkf: spdy_letkf_set_localization first");
+    if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
+    NEED_DEVICE(l->plan);
+    return SPDY_OK;
+}
+
+int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
+{
+    spdy_plan *p = l->plan;
+    const int kx = p->tab.kx, ncol = (int)grid_elems(p);
+    spdy::LetkfObs o{};
+    o.nobs = l->nobs; o.nmem = l->nmem; o.kx = kx; o.ncol = ncol;
+    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.value = l->d_value;
+    o.hx = l->d_hx; o.hxmean = l->d_hxmean; o.y = l->d_y; o.dep = l->d_dep;
+    spdy::LetkfCols c{};
+    c.nobs = l->nobs; c.nmem = l->nmem; c.kx = kx; c.ncol = ncol; c.nlv = l->nlv;
+    c.ch = l->sigma_h * std::sqrt(10.0 / 3.0); c.cv = l->sigma_v > 0.0 ? l->sigma_v * std::sqrt(10.0 / 3.0) : 0.0;
+    c.diag = (double)(l->nmem - 1) / l->rho;
+    c.colunit = l->d_colunit; c.lnfsg = l->d_lnfsg; c.ounit = l->d_ounit; c.olns = l->d_olns; c.rinv = l->d_rinv;
+    c.y = l->d_y; c.dep = l->d_dep;
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = dx[v]; }
+    KERNEL(spdy::launch_letkf_obs(o, p->stream));
+    KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
+    return SPDY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
+{
+    NEED_PLAN(p);
+    if (nmem < 2 || nmem > spdy::LETKF_MAX_MEMBERS)
+        return fail(SPDY_ERR_ARG, "letkf_create: nmem=%d outside [2, %d]", nmem, spdy::LETKF_MAX_MEMBERS);
+    if (max_obs < 0) return fail(SPDY_ERR_ARG, "letkf_create: max_obs=%d < 0", max_obs);
+    if (!out) return fail(SPDY_ERR_ARG, "null result pointer");
+    const spdy::HostTables &t = p->tab;
+    const int kx = t.kx, il = t.il, ix = t.ix;
+    const long need = (long)nmem * (2 * kx + 1);
+    if (p->max_batch < need)
+        return fail(SPDY_ERR_ARG, "letkf_create: max_batch=%d must be >= nmem*(2*kx+1)=%ld", p->max_batch, need);
+    int nlv = 4;
+    while (nlv > 1 && spdy::letkf_lds_bytes(nmem, kx, nlv) > kLdsLimit) nlv /= 2;
+    if (spdy::letkf_lds_bytes(nmem, kx, nlv) > kLdsLimit)
+        return fail(SPDY_ERR_ARG, "letkf_create: nmem=%d at kx=%d needs %zu bytes of LDS, a compute unit has %zu", nmem, kx,
+                    spdy::letkf_lds_bytes(nmem, kx, nlv), kLdsLimit);
+    if (!t.sigma_ready) return fail(SPDY_ERR_STATE, "letkf_create needs sigma levels");
+    NOT_CAPTURING(p, "spdy_letkf_create (allocation + upload)");
+    spdy_letkf *l = new spdy_letkf;
+    l->plan = p; l->nmem = nmem; l->max_obs = max_obs; l->nlv = nlv; l->lds = spdy::letkf_lds_bytes(nmem, kx, nlv);
+    // geometry.f90:70-75: sia(j) = -sia_half(j), sia(il+1-j) = sia_half(j), radang = asin(sia); in degrees, south first
+    l->lat.resize(il);
+    for (int j = 0; j < il; ++j) {
+        const int h = j < t.iy ? j : il - 1 - j;
+        l->lat[j] = (j < t.iy ? -std::asin(t.sia_half[h]) : std::asin(t.sia_half[h])) * (180.0 / kPi);
+    }
+    l->lnfsg.resize(kx);
+    for (int k = 0; k < kx; ++k) l->lnfsg[k] = std::log(t.fsg[k]);
+    *out = l;
+    if (p->device < 0) return SPDY_OK;
+    auto cleanup = [&](int rc) { spdy_letkf_destroy(l); *out = nullptr; return rc; };
+    if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
+    const size_t ncol = grid_elems(p), nf = (size_t)(4 * kx + 1) * nmem, M = (size_t)(max_obs > 0 ? max_obs : 1), E = (size_t)nmem;
+    // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | value | hx | hxmean | y | dep ; then the ints
+    const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 2 * E), ni = 6 * M;
+    if (hipMalloc(reinterpret_cast<void **>(&l->d_base), nd * sizeof(double) + ni * sizeof(int)) != hipSuccess)
+        return cleanup(fail(SPDY_ERR_HIP, "letkf_create: hipMalloc of %zu bytes failed", nd * sizeof(double) + ni * sizeof(int)));
+    double *d = l->d_base;
+    l->d_grid = d; d += nf * ncol;
+    l->d_spec = d; d += nf * spec_elems(p);
+    l->d_colunit = d; d += 3 * ncol;
+    l->d_lnfsg = d; d += kx;
+    l->d_swgt = d; d += 4 * M;
+    l->d_ounit = d; d += 3 * M;
+    l->d_olns = d; d += M;
+    l->d_rinv = d; d += M;
+    l->d_value = d; d += M;
+    l->d_hx = d; d += M * E;
+    l->d_hxmean = d; d += M;
+    l->d_y = d; d += M * E;
+    l->d_dep = d; d += M;
+    int *q = reinterpret_cast<int *>(d);
+    l->d_sidx = q; q += 4 * M;
+    l->d_var = q; q += M;
+    l->d_lev = q;
+    std::vector<double> cu(3 * ncol);
+    for (int j = 0; j < il; ++j)
+        for (int i = 0; i < ix; ++i) {
+            double u[3];
+            unit_vector(i * (360.0 / ix), l->lat[j], u);
+            for (int c = 0; c < 3; ++c) cu[c * ncol + (size_t)j * ix + i] = u[c];
+        }
+    if (hipMemsetAsync(l->d_base, 0, nd * sizeof(double) + ni * sizeof(int), p->stream) != hipSuccess ||
+        hipMemcpyAsync(l->d_colunit, cu.data(), cu.size() * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+        hipMemcpyAsync(l->d_lnfsg, l->lnfsg.data(), kx * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+        hipStreamSynchronize(p->stream) != hipSuccess)
+        return cleanup(fail(SPDY_ERR_HIP, "letkf_create: upload failed"));
+    if (spdy::letkf_prepare(l->lds) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "letkf_create: %zu bytes of LDS refused", l->lds));
+    // one inverse and one direct batch of the zero workspace, in the shapes spdy_ens_letkf_dev uses: whatever the plan's two
+    // transform paths allocate on their first call of this size exists before a capture
+    const int nk = nmem * kx;
+    const size_t L = (size_t)nk * ncol, LS = (size_t)nk * spec_elems(p);
+    double *g = l->d_grid, *s = l->d_spec;
+    int rc = ensure_four(p);
+    const spdy_spec_seg segs[3] = {{nk, s + 2 * LS}, {nk, s + 3 * LS}, {nmem, s + 4 * LS}};
+    if (!rc) rc = spdy_inverse_batch_segs_dev(p, nk, s, s + LS, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2);
+    if (!rc) rc = spdy_direct_batch_dev(p, nk, g, g + L, s, s + LS, 2, 2 * nk + nmem, g + 2 * L, s + 2 * LS);
+    if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(SPDY_ERR_HIP, "letkf_create: the first transforms failed");
+    return rc ? cleanup(rc) : SPDY_OK;
+}
+
+int spdy_letkf_destroy(spdy_letkf *l)
+{
+    if (!l) return SPDY_OK;
+    if (l->d_base) {
+        (void)hipSetDevice(l->plan->device);
+        (void)hipStreamSynchronize(l->plan->stream);
+        (void)hipFree(l->d_base);
+    }
+    delete l;
+    return SPDY_OK;
+}
+
+int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h, double sigma_v, double rho)
+{
+    NEED_LETKF(l);
+    if (!(sigma_h > 0.0) || !std::isfinite(sigma_h)) return fail(SPDY_ERR_ARG, "letkf: sigma_h must be finite and > 0");
+    if (!std::isfinite(sigma_v)) return fail(SPDY_ERR_ARG, "letkf: sigma_v must be finite (<= 0: no vertical localisation)");
+    if (!(rho > 0.0) || !std::isfinite(rho)) return fail(SPDY_ERR_ARG, "letkf: rho must be finite and > 0");
+    l->sigma_h = sigma_h; l->sigma_v = sigma_v; l->rho = rho; l->loc_set = true;
+    return SPDY_OK;
+}
+
+int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
+{
+    NEED_LETKF(l);
+    if (nobs < 0 || nobs > l->max_obs) return fail(SPDY_ERR_ARG, "letkf_set_obs: nobs=%d outside [0, max_obs=%d]", nobs, l->max_obs);
+    if (nobs && !host) return fail(SPDY_ERR_ARG, "null observations");
+    spdy_plan *p = l->plan;
+    const int kx = p->tab.kx;
+    for (int o = 0; o < nobs; ++o) {
+        const spdy_obs &b = host[o];
+        if (b.var < SPDY_OBS_U || b.var > SPDY_OBS_PS) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: var=%d", o, b.var);
+        if (b.var != SPDY_OBS_PS && (b.lev < 0 || b.lev >= kx))
+            return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: lev=%d outside [0, %d)", o, b.lev, kx);
+        if (!std::isfinite(b.lon)) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: lon is not finite", o);
+        if (!(std::fabs(b.lat) <= 90.0)) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: lat outside [-90, 90]", o);
+        if (!std::isfinite(b.value)) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: value is not finite", o);
+        if (!(b.error > 0.0) || !std::isfinite(b.error))
+            return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: error must be finite and > 0", o);
+    }
+    NOT_CAPTURING(p, "spdy_letkf_set_obs (upload)");
+    const size_t n = (size_t)nobs;
+    std::vector<int> sidx(4 * n), var(n), lev(n);
+    std::vector<double> swgt(4 * n), unit(3 * n), lns(n), rinv(n), value(n);
+    for (size_t o = 0; o < n; ++o) {
+        const spdy_obs &b = host[o];
+        stencil(l, b.lon, b.lat, &sidx[4 * o], &swgt[4 * o]);
+        unit_vector(b.lon, b.lat, &unit[3 * o]);
+        var[o] = b.var;
+        lev[o] = b.var == SPDY_OBS_PS ? 0 : b.lev;
+        lns[o] = b.var == SPDY_OBS_PS ? 0.0 : l->lnfsg[b.lev];
+        rinv[o] = 1.0 / (b.error * b.error);
+        value[o] = b.value;
+    }
+    if (p->device >= 0) {
+        HIP_TRY(hipSetDevice(p->device));
+        auto all = [&]() -> int {
+            RC(upload(p, l->d_sidx, sidx.data(), 4 * n * sizeof(int)));
+            RC(upload(p, l->d_var, var.data(), n * sizeof(int)));
+            RC(upload(p, l->d_lev, lev.data(), n * sizeof(int)));
+            RC(upload(p, l->d_swgt, swgt.data(), 4 * n * sizeof(double)));
+            RC(upload(p, l->d_ounit, unit.data(), 3 * n * sizeof(double)));
+            RC(upload(p, l->d_olns, lns.data(), n * sizeof(double)));
+            RC(upload(p, l->d_rinv, rinv.data(), n * sizeof(double)));
+            RC(upload(p, l->d_value, value.data(), n * sizeof(double)));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            return SPDY_OK;
+        };
+        if (const int rc = all()) {
+            // the device tables may be partly new: the object holds no observations now, and no copy is still reading the host
+            // arrays when they go
+            (void)hipStreamSynchronize(p->stream);
+            l->nobs = 0;
+            l->h_sidx.clear(); l->h_swgt.clear(); l->h_unit.clear(); l->h_lns.clear(); l->h_rinv.clear();
+            return rc;
+        }
+    }
+    l->nobs = nobs;
+    l->h_sidx.swap(sidx); l->h_swgt.swap(swgt); l->h_unit.swap(unit); l->h_lns.swap(lns); l->h_rinv.swap(rinv);
+    return SPDY_OK;
+}
+
+int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap)
+{
+    NEED_LETKF(l);
+    if (!name) return fail(SPDY_ERR_ARG, "null table name");
+    const bool index = !std::strcmp(name, "stencil_index");
+    const std::vector<double> *v = !std::strcmp(name, "stencil_weight") ? &l->h_swgt : !std::strcmp(name, "unit") ? &l->h_unit
+                                   : !std::strcmp(name, "lnsigma") ? &l->h_lns : !std::strcmp(name, "rinv") ? &l->h_rinv : nullptr;
+    if (!index && !v) return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
+    const int n = static_cast<int>(index ? l->h_sidx.size() : v->size());
+    if (buf && cap < n) return fail(SPDY_ERR_ARG, "analysis table '%s' has %d values, the buffer %d", name, n, cap);
+    if (buf && index)
+        for (int i = 0; i < n; ++i) buf[i] = l->h_sidx[i];
+    else if (buf && n)
+        std::memcpy(buf, v->data(), sizeof(double) * (size_t)n);
+    return n;
+}
+
+int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
+{
+    NEED_LETKF(l);
+    if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
+    double *const *f = !std::strcmp(name, "hx") ? &l->d_hx : !std::strcmp(name, "hxmean") ? &l->d_hxmean
+                       : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep : nullptr;
+    if (!f) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
+    NEED_DEVICE(l->plan);
+    *d_ptr = *f;
+    return SPDY_OK;
+}
+
+int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
+                                double *du, double *dv, double *dt, double *dq, double *dps)
+{
+    RC(analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps));
+    const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
+    double *dx[spdy::LETKF_VARS] = {du, dv, dt, dq, dps};
+    return analyse_grid(l, x, dx);
+}
+
+int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps)
+{
+    RC(analysis_ready(l, vor && div && t && q && ps));
+    spdy_plan *p = l->plan;
+    const int kx = p->tab.kx, nmem = l->nmem, nk = nmem * kx;
+    const size_t L = (size_t)nk * grid_elems(p), LS = (size_t)nk * spec_elems(p);
+    double *g = l->d_grid, *s = l->d_spec;
+    // time level 1 of all members to the grid, read in place: nmem*kx pairs (true wind), the segments t | q | ps
+    const spdy_spec_seg segs[3] = {{nk, t}, {nk, q}, {nmem, ps}};
+    RC(spdy_inverse_batch_segs_dev(p, nk, vor, div, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2));
+    // the increments take the place of the gridded ensemble
+    double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
+    RC(analyse_grid(l, x, x));
+    // vdspec(du, dv, 2) next to grid_to_spec(dt | dq | dps), then into the prognostics
+    RC(spdy_direct_batch_dev(p, nk, g, g + L, s, s + LS, 2, 2 * nk + nmem, g + 2 * L, s + 2 * LS));
+    spdy::LetkfAdd a{};
+    a.nops = spdy::LETKF_VARS;
+    double *dst[spdy::LETKF_VARS] = {vor, div, t, q, ps};
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) {
+        a.dst[v] = dst[v]; a.src[v] = s + (size_t)v * LS;
+        a.n[v] = (long)(v < 4 ? LS : (size_t)nmem * spec_elems(p));
+    }
+    KERNEL(spdy::launch_spec_add(a, p->stream));
+    return SPDY_OK;
+}
+
+}  // extern "C"

@@ -498,4 +498,41 @@ struct DiagArgs {
 };
 hipError_t launch_diagnostics(const DiagArgs &a, hipStream_t s);
 
+// The ensemble analysis (csrc/spdy_letkf.hip; include/spdy.h, "ensemble analysis").  Gridded ensemble arrays are
+// member-major: field (e, k) of a level variable starts (e * kx + k) * ncol doubles in, the surface field of member e e * ncol.
+enum { LETKF_VARS = 5 };                             // u, v, t, q, ps: the SPDY_OBS_* order
+constexpr int LETKF_MAX_MEMBERS = 32;
+// hx, hxmean, y, departure of every observation, one thread each: the four-point stencil the host made, the members in ascending
+// order.
+struct LetkfObs {
+    int nobs, nmem, kx, ncol;
+    const int *var, *lev, *sidx;                     // [nobs], [nobs] (0 for ps), [nobs][4] grid points j * ix + i
+    const double *swgt, *value;                      // [nobs][4], [nobs]
+    const double *x[LETKF_VARS];                     // the gridded ensemble
+    double *hx, *hxmean, *y, *dep;                   // [nobs][nmem], [nobs], [nobs][nmem], [nobs]
+};
+hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s);
+// The local analyses: one workgroup per grid column.  nlv levels' eigenproblems are in flight at a time (1, 2 or 4: what the LDS
+// holds; the results do not depend on it); lds = letkf_lds_bytes(nmem, kx, nlv).
+struct LetkfCols {
+    int nobs, nmem, kx, ncol, nlv;
+    double ch, cv, diag;                             // c_h in metres, c_v (<= 0: no vertical factor), (nmem - 1) / rho
+    const double *colunit, *lnfsg;                   // [3][ncol] unit vectors of the columns, [kx] ln fsg
+    const double *ounit, *olns, *rinv;               // [nobs][3], [nobs] ln sigma_o, [nobs] 1 / error^2
+    const double *y, *dep;                           // as LetkfObs
+    const double *x[LETKF_VARS];
+    double *dx[LETKF_VARS];                          // the increments; may be x
+};
+size_t letkf_lds_bytes(int nmem, int kx, int nlv);
+hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s);
+hipError_t letkf_prepare(size_t lds);                // before the first launch on a device: admits a compute unit's whole LDS
+// dst[i] += src[i] for nops arrays in one launch; an increment equal to zero leaves the destination's bits (a -0.0 included)
+struct LetkfAdd {
+    int nops;
+    long n[LETKF_VARS];
+    double *dst[LETKF_VARS];
+    const double *src[LETKF_VARS];
+};
+hipError_t launch_spec_add(const LetkfAdd &a, hipStream_t s);
+
 }  // namespace spdy

@@ -1,0 +1,350 @@
+// The ensemble analysis on the device (include/spdy.h, "ensemble analysis"): the observation-space quantities, the
+// local ensemble transforms of every grid column and level, and the kernel that adds the spectral increments to the prognostics.
+// The transforms around them are the plan's own (csrc/spdy_api_letkf.hip).
+//
+// Everything here is bit-reproducible: no atomics, every sum in a fixed order (observations ascending, members ascending), every
+// loop with a fixed bound.  The Jacobi sweeps end at the convergence test or after LETKF_SWEEPS; a NaN fails every test, so a
+// non-finite input runs the full count and leaves NaN, it does not hang.  No contraction, as in the other column kernels.
+#include "spdy_kernels.hpp"
+
+namespace spdy {
+namespace {
+
+constexpr int LETKF_BLOCK = 256;     // threads of a column's workgroup: four waves
+constexpr int LETKF_CHUNK = 256;     // observations scanned per step: one per thread
+constexpr int LETKF_TILE = 16;       // observations in range staged in LDS per accumulation step
+constexpr int LETKF_SWEEPS = 16;     // the most Jacobi sweeps (E = 32 converges in 7 to 9)
+constexpr int LETKF_MAX_KX = 32;
+constexpr double LETKF_REARTH = 6.371e6;
+constexpr double LETKF_TOL = 0x1p-53;   // a pair with |a_pq| <= tol * sqrt(a_pp a_qq) is not rotated
+
+// the workgroup's LDS, in doubles from the 16-byte aligned base; every offset is even
+struct LetkfLds {
+    int C, B, V, S, X, ty, rtab, td, lwh, lidx, misc, total;
+    __host__ __device__ LetkfLds(int ep, int kx, int nlv)
+    {
+        int o = 0;
+        C = o; o += kx * ep * ep;            // A = (E-1)/rho I + C of every level, later T of the level
+        B = o; o += kx * ep;                 // b of every level
+        V = o; o += nlv * ep * ep;           // eigenvectors, per level in flight
+        S = o; o += nlv * 6 * ep;            // lambda | V^T b / lambda | sqrt((E-1)/lambda) | wbar | (c, s), (p, q) (int) of the pairs
+        X = o; o += nlv * LETKF_VARS * ep;   // the members' values of the five variables
+        ty = o; o += LETKF_TILE * ep;        // Y of the staged observations
+        rtab = o; o += kx * LETKF_TILE;      // r = w / error^2 per level and staged observation
+        td = o; o += LETKF_TILE;             // their departures
+        lwh = o; o += LETKF_CHUNK;           // horizontal weights of the chunk's observations in range
+        lidx = o; o += LETKF_CHUNK / 2;      // their indices (int)
+        misc = o; o += (16 + LETKF_MAX_KX) / 2;   // int: wave counts [4], sweep flags [4], rotation marks [4], touched [kx]
+        total = o;
+    }
+};
+
+// Gaspari and Cohn (1999), eq. 4.10; support r < 2.  The inner branch in Horner form; the outer branch, r^5/12 - r^4/2 + 5r^3/8 +
+// 5r^2/3 - 5r + 4 - 2/(3r), in its factored form (2 - r)^4 (r^2 + 2r - 1/2) / (12 r): the sum of powers cancels down to its last
+// bits where the weight fades out, and a weight wrong by a few 1e-16 there, times 1/error^2, times a thousand observations, moves
+// an analysis at the edge of their range by 1e-12; the product has no cancellation and cannot round below zero.
+__device__ inline double letkf_gc(double r)
+{
+#pragma clang fp contract(off)
+    if (!(r < 2.0)) return r != r ? r : 0.0;
+    if (r <= 1.0) return (((-0.25 * r + 0.5) * r + 0.625) * r - 5.0 / 3.0) * (r * r) + 1.0;
+    const double s = 2.0 - r, s2 = s * s;
+    return (s2 * s2) * ((r + 2.0) * r - 0.5) / (12.0 * r);
+}
+
+// round-robin pair m of round r among n (even) players: the last player stays, the others turn
+__device__ inline void letkf_pair(int m, int r, int n, int &p, int &q)
+{
+    if (m == 0) { p = n - 1; q = r; return; }
+    p = (r + m) % (n - 1);
+    q = (r - m + n - 1) % (n - 1);
+}
+
+__device__ inline size_t letkf_at(int v, int e, int k, int kx, int ncol, int col)
+{
+    return v < 4 ? ((size_t)e * kx + k) * ncol + col : (size_t)e * ncol + col;
+}
+
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObs a)
+{
+#pragma clang fp contract(off)
+    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (o >= a.nobs) return;
+    const int v = a.var[o], k = a.lev[o];
+    const double *const x = a.x[v];
+    const int i0 = a.sidx[4 * o], i1 = a.sidx[4 * o + 1], i2 = a.sidx[4 * o + 2], i3 = a.sidx[4 * o + 3];
+    const double w0 = a.swgt[4 * o], w1 = a.swgt[4 * o + 1], w2 = a.swgt[4 * o + 2], w3 = a.swgt[4 * o + 3];
+    double sum = 0.0;
+    for (int e = 0; e < a.nmem; ++e) {
+        const double *const f = x + letkf_at(v, e, k, a.kx, a.ncol, 0);
+        const double h = ((w0 * f[i0] + w1 * f[i1]) + w2 * f[i2]) + w3 * f[i3];
+        a.hx[(size_t)o * a.nmem + e] = h;
+        sum += h;
+    }
+    const double mean = sum / a.nmem;
+    a.hxmean[o] = mean;
+    for (int e = 0; e < a.nmem; ++e) a.y[(size_t)o * a.nmem + e] = a.hx[(size_t)o * a.nmem + e] - mean;
+    a.dep[o] = a.value[o] - mean;
+}
+
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const LetkfCols a)
+{
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) char letkf_smem[];
+    double *const sm = reinterpret_cast<double *>(letkf_smem);
+    const int E = a.nmem, ep = (E + 1) & ~1, ee = ep * ep, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, col = blockIdx.x;
+    const LetkfLds L(ep, kx, a.nlv);
+    double *const C = sm + L.C, *const B = sm + L.B, *const ty = sm + L.ty, *const rtab = sm + L.rtab, *const td = sm + L.td,
+                  *const lwh = sm + L.lwh;
+    int *const lidx = reinterpret_cast<int *>(sm + L.lidx), *const misc = reinterpret_cast<int *>(sm + L.misc);
+    int *const wcount = misc, *const flag = misc + 4, *const rot = misc + 8, *const touched = misc + 16;
+
+    // A = (E - 1) / rho I (an odd E: one decoupled row more), b = 0
+    for (int el = tid; el < kx * ee; el += LETKF_BLOCK) {
+        const int i = (el % ee) / ep, j = el % ep;
+        C[el] = i == j ? (i < E ? a.diag : 1.0) : 0.0;
+    }
+    for (int el = tid; el < kx * ep; el += LETKF_BLOCK) B[el] = 0.0;
+    if (tid < kx) touched[tid] = 0;
+    const double cx = a.colunit[col], cy = a.colunit[ncol + col], cz = a.colunit[2 * ncol + col];
+    __syncthreads();
+
+    // ---- C and b of every level: the observations in ascending order, chunk by chunk
+    for (int base = 0; base < a.nobs; base += LETKF_CHUNK) {
+        const int o = base + tid;
+        double wh = 0.0;
+        if (o < a.nobs) {
+            const double dx = cx - a.ounit[3 * (size_t)o], dy = cy - a.ounit[3 * (size_t)o + 1], dz = cz - a.ounit[3 * (size_t)o + 2];
+            const double chord = sqrt((dx * dx + dy * dy) + dz * dz);
+            const double dist = 2.0 * LETKF_REARTH * asin(fmin(1.0, 0.5 * chord));
+            wh = letkf_gc(dist / a.ch);
+        }
+        // the chunk's observations in range, compacted in ascending order: ballot and prefix counts
+        const bool keep = wh != 0.0;
+        const unsigned long long mask = __ballot(keep);
+        const int lane = tid & 63, wave = tid >> 6;
+        if (lane == 0) wcount[wave] = __popcll(mask);
+        __syncthreads();
+        int pos = __popcll(mask & ((1ull << lane) - 1ull)), nc = 0;
+        for (int w = 0; w < LETKF_BLOCK / 64; ++w) {
+            const int c = wcount[w];
+            if (w < wave) pos += c;
+            nc += c;
+        }
+        if (keep) { lidx[pos] = o; lwh[pos] = wh; }
+        __syncthreads();
+        for (int t0 = 0; t0 < nc; t0 += LETKF_TILE) {
+            const int nt = min(LETKF_TILE, nc - t0);
+            for (int x = tid; x < nt * kx; x += LETKF_BLOCK) {
+                const int t = x / kx, k = x % kx, oo = lidx[t0 + t];
+                double w = lwh[t0 + t];
+                if (a.cv > 0.0) w = w * letkf_gc(fabs(a.lnfsg[k] - a.olns[oo]) / a.cv);
+                rtab[k * LETKF_TILE + t] = w * a.rinv[oo];
+            }
+            for (int x = tid; x < nt * ep; x += LETKF_BLOCK) {
+                const int t = x / ep, e = x % ep;
+                ty[x] = e < E ? a.y[(size_t)lidx[t0 + t] * E + e] : 0.0;
+            }
+            if (tid < nt) td[tid] = a.dep[lidx[t0 + tid]];
+            __syncthreads();
+            for (int el = tid; el < kx * ee; el += LETKF_BLOCK) {
+                const int k = el / ee, i = (el % ee) / ep, j = el % ep;
+                double acc = C[el];
+                for (int t = 0; t < nt; ++t) {
+                    const double r = rtab[k * LETKF_TILE + t];
+                    if (r != 0.0) acc += r * (ty[t * ep + i] * ty[t * ep + j]);
+                }
+                C[el] = acc;
+            }
+            for (int el = tid; el < kx * ep; el += LETKF_BLOCK) {
+                const int k = el / ep, i = el % ep;
+                double acc = B[el];
+                bool any = false;
+                for (int t = 0; t < nt; ++t) {
+                    const double r = rtab[k * LETKF_TILE + t];
+                    if (r != 0.0) { acc += r * (ty[t * ep + i] * td[t]); any = true; }
+                }
+                B[el] = acc;
+                if (any && i == 0) touched[k] = 1;      // tile after tile may: always the same value
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- per level: A = V Lambda V^T by parallel cyclic Jacobi, T, the increments; nlv levels at a time, tpl threads each
+    const int nlv = a.nlv, tpl = LETKF_BLOCK / nlv, lv = tid / tpl, lt = tid % tpl, half = ep / 2;
+    double *const V = sm + L.V + lv * ee, *const S = sm + L.S + lv * 6 * ep, *const X = sm + L.X + lv * LETKF_VARS * ep;
+    double *const lam = S, *const hh = S + ep, *const gf = S + 2 * ep, *const wbar = S + 3 * ep, *const cs = S + 4 * ep;
+    int *const pq = reinterpret_cast<int *>(S + 5 * ep);
+    // the two phases' work without a division: rows as (pair, column) with 32 lanes per pair, columns as (row, pair) with 16
+    // lanes per row -- neighbouring lanes then touch neighbouring words of one row of A, not one word of neighbouring rows
+    const int rj = lt & 31, rm = lt >> 5, rstep = tpl >> 5, cm = lt & 15, ci = lt >> 4, cstep = tpl >> 4;
+    for (int k0 = 0; k0 < kx; k0 += nlv) {
+        const int k = k0 + lv;
+        const bool act = k < kx;
+        double *const A = C + (act ? k : 0) * ee;
+        const double *const Bk = B + (act ? k : 0) * ep;
+        if (act)
+            for (int el = lt; el < ee; el += tpl) V[el] = el / ep == el % ep ? 1.0 : 0.0;
+        if (lt == 0) flag[lv] = act && touched[k];      // a level no observation reaches is diagonal already
+        __syncthreads();
+        for (int sweep = 0; sweep < LETKF_SWEEPS; ++sweep) {
+            bool any = false;
+            for (int l = 0; l < nlv; ++l) any = any || flag[l];
+            if (!any) break;                            // the same for every thread
+            const bool go = flag[lv] != 0;
+            if (lt == 0) rot[lv] = 0;
+            __syncthreads();
+            for (int r = 0; r < ep - 1; ++r) {
+                if (go && lt < half) {
+                    int p, q;
+                    letkf_pair(lt, r, ep, p, q);
+                    const double app = A[p * ep + p], aqq = A[q * ep + q], apq = A[p * ep + q];
+                    double c = 1.0, s = 0.0;
+                    if (!(fabs(apq) <= LETKF_TOL * sqrt(app * aqq))) {
+                        const double theta = (aqq - app) / (2.0 * apq);
+                        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                        c = 1.0 / sqrt(t * t + 1.0);
+                        s = t * c;
+                        rot[lv] = 1;                    // several lanes may: all write the same value
+                    }
+                    cs[2 * lt] = c; cs[2 * lt + 1] = s;
+                    pq[2 * lt] = p; pq[2 * lt + 1] = q;
+                }
+                __syncthreads();
+                if (go && rj < ep)                      // rows: A <- J^T A
+                    for (int m = rm; m < half; m += rstep) {
+                        const int p = pq[2 * m], q = pq[2 * m + 1];
+                        const double c = cs[2 * m], s = cs[2 * m + 1], x = A[p * ep + rj], y = A[q * ep + rj];
+                        A[p * ep + rj] = c * x - s * y;
+                        A[q * ep + rj] = s * x + c * y;
+                    }
+                __syncthreads();
+                if (go && cm < half) {                  // columns: A <- A J, V <- V J; the rotated pair's element is zero
+                    const int p = pq[2 * cm], q = pq[2 * cm + 1];
+                    const double c = cs[2 * cm], s = cs[2 * cm + 1];
+                    for (int i = ci; i < ep; i += cstep) {
+                        double x = A[i * ep + p], y = A[i * ep + q];
+                        double xn = c * x - s * y, yn = s * x + c * y;
+                        if (s != 0.0 && i == p) yn = 0.0;
+                        if (s != 0.0 && i == q) xn = 0.0;
+                        A[i * ep + p] = xn; A[i * ep + q] = yn;
+                        x = V[i * ep + p]; y = V[i * ep + q];
+                        V[i * ep + p] = c * x - s * y;
+                        V[i * ep + q] = s * x + c * y;
+                    }
+                }
+                __syncthreads();
+            }
+            if (lt == 0 && go) flag[lv] = rot[lv];      // no pair rotated: converged
+            __syncthreads();
+        }
+        // T = V diag(sqrt((E-1)/lambda)) V^T + wbar 1^T - I with wbar = V Lambda^-1 V^T b, into the place of A
+        if (act && lt < ep) lam[lt] = A[lt * ep + lt];
+        __syncthreads();
+        if (act && lt < ep) {
+            double vtb = 0.0;
+            for (int g = 0; g < ep; ++g) vtb += V[g * ep + lt] * Bk[g];
+            hh[lt] = vtb / lam[lt];
+            gf[lt] = sqrt((double)(E - 1) / lam[lt]);
+        }
+        __syncthreads();
+        if (act && lt < ep) {
+            double w = 0.0;
+            for (int i = 0; i < ep; ++i) w += V[lt * ep + i] * hh[i];
+            wbar[lt] = w;
+        }
+        __syncthreads();
+        if (act)
+            for (int el = lt; el < ee; el += tpl) {
+                const int f = el / ep, e = el % ep;
+                double acc = 0.0;
+                int i = e;                              // the sum starts at i = e: the lanes' rows of V on different banks
+                for (int n = 0; n < ep; ++n) {
+                    acc += (V[f * ep + i] * gf[i]) * V[e * ep + i];
+                    i = i + 1 == ep ? 0 : i + 1;
+                }
+                A[el] = (acc + wbar[f]) - (f == e ? 1.0 : 0.0);
+            }
+        // the increments of u, v, t, q at this level, of ps at the lowest: dx_e = sum_f (x_f - mean) T[f][e]
+        const int nvar = act ? (k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1) : 0;
+        for (int x = lt; x < nvar * ep; x += tpl) {
+            const int v = x / ep, e = x % ep;
+            X[x] = e < E ? a.x[v][letkf_at(v, e, k, kx, ncol, col)] : 0.0;
+        }
+        __syncthreads();
+        for (int x = lt; x < nvar * ep; x += tpl) {
+            const int v = x / ep, e = x % ep;
+            if (e >= E) continue;
+            const double *const xv = X + v * ep;
+            double sum = 0.0;
+            for (int f = 0; f < E; ++f) sum += xv[f];
+            const double mean = sum / E;
+            double d = 0.0;
+            for (int f = 0; f < E; ++f) d += (xv[f] - mean) * A[f * ep + e];
+            a.dx[v][letkf_at(v, e, k, kx, ncol, col)] = d;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(LETKF_BLOCK) void spec_add_kernel(const LetkfAdd a)
+{
+    const int op = blockIdx.y;
+    const long i = (long)blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (i >= a.n[op]) return;
+    const double d = a.src[op][i];
+    if (d != 0.0) a.dst[op][i] = a.dst[op][i] + d;
+}
+
+}  // namespace
+
+size_t letkf_lds_bytes(int nmem, int kx, int nlv) { return sizeof(double) * (size_t)LetkfLds((nmem + 1) & ~1, kx, nlv).total; }
+
+// the whole LDS of a compute unit, whatever this object needs: objects of other sizes launch the same kernel
+hipError_t letkf_prepare(size_t lds)
+{
+    constexpr size_t whole = 160 * 1024;
+    if (lds > whole) return hipErrorInvalidValue;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(letkf_transform_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole);
+}
+
+hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s)
+{
+    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.ncol < 1 || !a.hx || !a.hxmean || !a.y || !a.dep)
+        return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!a.x[v]) return hipErrorInvalidValue;
+    if (!a.nobs) return hipSuccess;
+    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.value) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(letkf_obs_kernel, dim3((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s)
+{
+    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 ||
+        (a.nlv != 1 && a.nlv != 2 && a.nlv != 4) || lds != letkf_lds_bytes(a.nmem, a.kx, a.nlv) || !(a.ch > 0.0) || !(a.diag > 0.0) ||
+        !a.colunit || !a.lnfsg)
+        return hipErrorInvalidValue;
+    if (a.nobs && (!a.ounit || !a.olns || !a.rinv || !a.y || !a.dep)) return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!a.x[v] || !a.dx[v]) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(letkf_transform_kernel, dim3(a.ncol), dim3(LETKF_BLOCK), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_add(const LetkfAdd &a, hipStream_t s)
+{
+    if (a.nops < 1 || a.nops > LETKF_VARS) return hipErrorInvalidValue;
+    long most = 0;
+    for (int i = 0; i < a.nops; ++i) {
+        if (a.n[i] < 0 || !a.dst[i] || !a.src[i]) return hipErrorInvalidValue;
+        most = a.n[i] > most ? a.n[i] : most;
+    }
+    if (!most) return hipSuccess;
+    hipLaunchKernelGGL(spec_add_kernel, dim3((unsigned)((most + LETKF_BLOCK - 1) / LETKF_BLOCK), a.nops), dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace spdy

@@ -104,6 +104,26 @@ struct spdy_diagnostics {
     spdy::DiagLevel *d_state = nullptr;   // [nmem][kx]
 };
 
+// The ensemble analysis behind include/spdy.h's spdy_letkf (csrc/spdy_api_letkf.hip): the observation tables on the host, and
+// one device allocation that holds their copies, the observation-space fields and the analysis' two workspaces.
+struct spdy_letkf {
+    spdy_plan *plan = nullptr;
+    int nmem = 0, max_obs = 0, nobs = 0;
+    int nlv = 1;                          // levels whose eigenproblems a workgroup keeps in flight
+    size_t lds = 0;                       // dynamic LDS of the transform kernel
+    double sigma_h = 0.0, sigma_v = 0.0, rho = 1.0;
+    bool loc_set = false;
+    std::vector<double> lat, lnfsg;       // [il] latitudes in degrees, south first; [kx] ln fsg
+    std::vector<int> h_sidx;              // the tables of spdy_letkf_table
+    std::vector<double> h_swgt, h_unit, h_lns, h_rinv;
+    double *d_base = nullptr;
+    double *d_grid = nullptr, *d_spec = nullptr;   // (4kx+1) nmem grids u | v | t | q | ps, and as many spectra
+    double *d_colunit = nullptr, *d_lnfsg = nullptr;
+    double *d_swgt = nullptr, *d_ounit = nullptr, *d_olns = nullptr, *d_rinv = nullptr, *d_value = nullptr;
+    double *d_hx = nullptr, *d_hxmean = nullptr, *d_y = nullptr, *d_dep = nullptr;
+    int *d_sidx = nullptr, *d_var = nullptr, *d_lev = nullptr;
+};
+
 namespace spdy_detail {
 
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -26,8 +26,9 @@ model.couple_dev(day, hfluxn, shf, evap, ssrd).
 
 `step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  `output` gives every member's float32
 snapshot (input_output.f90:184-206) and the ensemble mean and spread from one call (include/spdy.h, "ensemble output").  SPPT:
-physics["sppt"], a Sppt with one pattern per member, is advanced and applied by `step` (include/spdy.h, "SPPT").  Not covered: the
-level-sharded step."""
+physics["sppt"], a Sppt with one pattern per member, is advanced and applied by `step` (include/spdy.h, "SPPT").  `analyse` is the
+LETKF update of time level 1 from a Letkf's observations (include/spdy.h, "ensemble analysis").  Not covered: the level-sharded
+step."""
 import numpy as np
 
 PROG = ("vor", "div", "t", "tr", "ps")
@@ -195,6 +196,18 @@ class Ensemble:
         self.sp.ens_output_batch_dev(self.nmem, self.vor[0], self.div[0], self.t[0], self.tr[0], self.phi if phi is None else phi,
                                      self.ps[0], res.get("members"), res.get("mean"), res.get("spread"), use)
         return res
+
+    # ------------------------------------------------------------------ analysis
+    def analyse(self, letkf):
+        """The LETKF update of time level 1 of every member, in place (include/spdy.h, "ensemble analysis"): five launches whatever
+        E is (six once the direct batch is of streaming size), capturable.  letkf: a Letkf of this plan with nmem == E, its
+        observations set.  Time level 2 and phi are stale afterwards: continue with startup(delt).  Members are coupled: every
+        member must be finite."""
+        if getattr(letkf, "sp", None) is not self.sp:
+            raise ValueError("analyse: the Letkf must belong to the ensemble's plan")
+        if letkf.nmem != self.nmem:
+            raise ValueError("analyse: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
+        letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0])
 
     def startup(self, delt, physics=None):
         """first_step (time_stepping.f90:12-24): the forward half step, the first leapfrog step and the three initialize_implicit

@@ -80,6 +80,12 @@ module spdy_c
         type(c_ptr) :: u = c_null_ptr, v = c_null_ptr, t = c_null_ptr, q = c_null_ptr, phi = c_null_ptr, ps = c_null_ptr
     end type
 
+    !> spdy_obs (include/spdy.h, "ensemble analysis"): var SPDY_OBS_*, lev 0-based (ignored for PS), degrees, the model's units
+    type, bind(C) :: spdy_obs
+        integer(c_int) :: var = 0_c_int, lev = 0_c_int
+        real(c_double) :: lon = 0.0_c_double, lat = 0.0_c_double, value = 0.0_c_double, error = 1.0_c_double
+    end type
+
     interface
         function spdy_plan_create(trunc, ix, iy, kx, max_batch, device, plan) bind(C, name="spdy_plan_create") result(rc)
             import :: c_int, c_ptr
@@ -1144,8 +1150,61 @@ module spdy_c
             integer(c_int), value :: nmem
             integer(c_int) :: rc
         end function
+        ! the ensemble analysis (include/spdy.h): host is c_loc of an array of spdy_obs; the device pointers are those of time
+        ! level 1 of the ensemble (spdy_ens_letkf_dev) or of a gridded ensemble (spdy_letkf_analyse_grid_dev)
+        function spdy_letkf_create(plan, nmem, max_obs, l) bind(C, name="spdy_letkf_create") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan
+            integer(c_int), value :: nmem, max_obs
+            type(c_ptr), intent(out) :: l
+            integer(c_int) :: rc
+        end function
+        function spdy_letkf_destroy(l) bind(C, name="spdy_letkf_destroy") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l
+            integer(c_int) :: rc
+        end function
+        function spdy_letkf_set_localization(l, sigma_h_m, sigma_v_lnsigma, rho) bind(C, name="spdy_letkf_set_localization") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: l
+            real(c_double), value :: sigma_h_m, sigma_v_lnsigma, rho
+            integer(c_int) :: rc
+        end function
+        function spdy_letkf_set_obs(l, nobs, host) bind(C, name="spdy_letkf_set_obs") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, host
+            integer(c_int), value :: nobs
+            integer(c_int) :: rc
+        end function
+        function spdy_letkf_table(l, name, buf, cap) bind(C, name="spdy_letkf_table") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: l, buf
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: cap
+            integer(c_int) :: rc
+        end function
+        function spdy_letkf_field(l, name, d_ptr) bind(C, name="spdy_letkf_field") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: l
+            character(kind=c_char), intent(in) :: name(*)
+            type(c_ptr), intent(out) :: d_ptr
+            integer(c_int) :: rc
+        end function
+        function spdy_letkf_analyse_grid_dev(l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps) &
+                & bind(C, name="spdy_letkf_analyse_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_letkf_dev(l, vor, div, t, q, ps) bind(C, name="spdy_ens_letkf_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, vor, div, t, q, ps
+            integer(c_int) :: rc
+        end function
     end interface
 
+    integer(c_int), parameter :: SPDY_OBS_U = 0_c_int, SPDY_OBS_V = 1_c_int, SPDY_OBS_T = 2_c_int, SPDY_OBS_Q = 3_c_int, &
+        & SPDY_OBS_PS = 4_c_int                                !! spdy_obs%var (include/spdy.h)
     integer(c_int), parameter :: SPDY_DEVICE_AUTO = -2_c_int   !! $SPDY_DEVICE, else the launcher's local rank (include/spdy.h)
 
     !> Work a drop-in module has deferred on the device and that must be issued before the plan's tables change (time_stepping's

@@ -1,0 +1,136 @@
+"""The ensemble analysis on the device (spdy_letkf_* in include/spdy.h, "ensemble analysis").
+
+A Letkf belongs to a plan and an ensemble size.  One analysis: set_obs(...), then Ensemble.analyse(letkf) on the spectral state
+(five launches, six where the direct batch is of streaming size; in place, time level 1) or analyse_grid(...) on a gridded
+ensemble; fields() gives the observation-space quantities of that call, so observation-minus-background statistics need no
+second operator.  After an analysis the run continues
+with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled: build the analysis ensemble from
+members the guard has not stopped, a non-finite member makes every column it touches non-finite."""
+import ctypes
+import weakref
+
+import numpy as np
+
+from ._lib import check
+from .columns import DeviceField, _p
+
+OBS_U, OBS_V, OBS_T, OBS_Q, OBS_PS = range(5)
+LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv")
+LETKF_FIELDS = ("hx", "hxmean", "y", "departure")
+
+
+class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
+    _fields_ = [("var", ctypes.c_int), ("lev", ctypes.c_int), ("lon", ctypes.c_double), ("lat", ctypes.c_double),
+                ("value", ctypes.c_double), ("error", ctypes.c_double)]
+
+
+class _DeviceView:
+    """a DeviceField of float64 as the array interface torch.as_tensor wraps without a copy"""
+
+    def __init__(self, f):
+        self.__cuda_array_interface__ = {"shape": f.shape, "typestr": "<f8", "data": (f.ptr, False), "version": 2}
+
+
+class Letkf:
+    """sigma_h: horizontal localisation scale in metres; sigma_v: vertical scale in ln sigma (<= 0: none); rho: multiplicative
+    inflation of the background covariance.  2 <= nmem <= 32; the plan needs max_batch >= nmem (2 kx + 1)."""
+
+    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0):
+        self.sp, self.lib = sp, sp.lib
+        if sp.device >= 0:
+            sp._sync_stream()
+        h = ctypes.c_void_p()
+        check(self.lib.spdy_letkf_create(sp.h, int(nmem), int(max_obs), ctypes.byref(h)))
+        self.h, self.nmem, self.max_obs, self.nobs = h, int(nmem), int(max_obs), 0
+        # the plan closes its objects first (as its surface models)
+        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
+        self.set_localization(sigma_h, sigma_v, rho)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.spdy_letkf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_localization(self, sigma_h, sigma_v=0.0, rho=1.0):
+        """read when an analysis is enqueued: a captured analysis keeps the values of its capture"""
+        check(self.lib.spdy_letkf_set_localization(self.h, float(sigma_h), float(sigma_v), float(rho)))
+
+    def set_obs(self, var, lev, lon, lat, value, error):
+        """The observations of the next analysis, arrays of one length (0 .. max_obs): var OBS_U .. OBS_PS, lev 0 .. kx-1 (ignored
+        for OBS_PS), lon, lat in degrees, value and error in the model's units (q in g/kg, ps as log(p/p0)).  Every field is
+        validated before anything changes.  Synchronises the plan's stream; not inside a capture."""
+        cols = [np.atleast_1d(np.asarray(a)) for a in (var, lev, lon, lat, value, error)]
+        n = cols[0].shape[0]
+        if any(c.ndim != 1 or c.shape[0] != n for c in cols):
+            raise ValueError("set_obs: var, lev, lon, lat, value, error must be one-dimensional arrays of one length")
+        if n > self.max_obs:
+            raise ValueError("set_obs: %d observations, the object holds %d" % (n, self.max_obs))
+        obs = (Obs * max(n, 1))()
+        for o in range(n):
+            obs[o] = Obs(int(cols[0][o]), int(cols[1][o]), float(cols[2][o]), float(cols[3][o]), float(cols[4][o]), float(cols[5][o]))
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        rc = self.lib.spdy_letkf_set_obs(self.h, n, ctypes.cast(obs, ctypes.c_void_p))
+        if rc == -4:                  # SPDY_ERR_HIP: a copy failed, the object holds no observations now
+            self.nobs = 0
+        check(rc)
+        self.nobs = n
+
+    def table(self, name):
+        """A host table of the current observations (LETKF_TABLES): stencil_index [nobs, 4] (grid points j*ix+i, int64),
+        stencil_weight [nobs, 4], unit [nobs, 3], lnsigma [nobs], rinv [nobs]."""
+        n = check(self.lib.spdy_letkf_table(self.h, name.encode(), None, 0))
+        out = np.zeros(n)
+        check(self.lib.spdy_letkf_table(self.h, name.encode(), _p(out), n))
+        if name == "stencil_index":
+            return out.astype(np.int64).reshape(-1, 4)
+        return out.reshape(-1, 4) if name == "stencil_weight" else out.reshape(-1, 3) if name == "unit" else out
+
+    def field(self, name):
+        """A device field of the latest analysis call (LETKF_FIELDS): hx, y [nobs, nmem], hxmean, departure [nobs]; a DeviceField
+        in the object's own memory, the pointers never change."""
+        p = ctypes.c_void_p()
+        check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
+        return DeviceField(self.sp, p.value, (self.nobs, self.nmem) if name in ("hx", "y") else (self.nobs,))
+
+    def fields(self):
+        """{"hx": [nobs, nmem], "hxmean": [nobs], "departure": [nobs]} of the latest analysis call: float64 device tensors that
+        are views of the object's own memory (no copy; the next analysis call overwrites them, and they die with the object)."""
+        import torch
+        dev, out = "cuda:%d" % self.sp.device, {}
+        for name in ("hx", "hxmean", "departure"):
+            f = self.field(name)
+            out[name] = torch.as_tensor(_DeviceView(f), device=dev) if self.nobs else torch.empty(f.shape, dtype=torch.float64, device=dev)
+        return out
+
+    def analyse_grid(self, ug, vg, tg, qg, psg, out=None):
+        """The increments (du, dv, dt, dq, dps) of a gridded ensemble: ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] float64
+        device tensors; out: five tensors of those shapes to write into (they may be the inputs), by default fresh ones.
+        Two launches; capturable when `out` is given."""
+        import torch
+        sp, E = self.sp, self.nmem
+        x = (ug, vg, tg, qg, psg)
+        shp = [(E, sp.kx) + sp.grid_shape] * 4 + [(E,) + sp.grid_shape]
+        if out is None:
+            out = tuple(torch.empty_like(a) for a in x)
+        if len(out) != 5:
+            raise ValueError("analyse_grid: out must hold five tensors")
+        for a, s in list(zip(x, shp)) + list(zip(out, shp)):
+            if tuple(a.shape) != s or a.dtype != torch.float64 or not a.is_contiguous():
+                raise ValueError("analyse_grid: expected a contiguous float64 tensor of shape %s, got %s" % (s, tuple(a.shape)))
+        if sp.device >= 0:
+            sp._sync_stream()
+        check(self.lib.spdy_letkf_analyse_grid_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in x + tuple(out)]))
+        return tuple(out)
+
+    def analyse_dev(self, vor, div, t, q, ps):
+        """spdy_ens_letkf_dev: time level 1 of an ensemble, in place (Ensemble.analyse)"""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        check(self.lib.spdy_ens_letkf_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]))

@@ -24,6 +24,8 @@ from .columns import (MOIST_2D, MOIST_3D, PBL_2D, PBL_3D, RAD_2D, RAD_3D, RAD_SW
 from .columns import (DIAG_DEKE, DIAG_FIELDS, DIAG_NONFINITE, DIAG_REFERENCE, DIAG_REKE, DIAG_TEMP_HIGH, DIAG_TEMP_LOW,  # noqa: F401
                       Diagnostics, DiagnosticsStop, format_diagnostics)
 
+from .letkf import LETKF_FIELDS, LETKF_TABLES, Letkf, Obs  # noqa: F401,E402
+
 RESOLUTIONS = {"t30": (30, 96, 24), "t63": (63, 192, 48)}   # trunc, ix, iy
 
 

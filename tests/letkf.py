@@ -1,0 +1,328 @@
+"""The ensemble analysis restated in NumPy (include/spdy.h, "ensemble analysis"): the observation operator, the localisation
+weights, the local problem and the increments, exactly as the header defines them, with two routes for the eigenproblem --
+numpy.linalg.eigh and a cyclic Jacobi of its own -- whose difference measures what rounding alone does on given inputs.  Also the
+helpers that build small observation sets and gridded ensembles for the tests.
+
+Arrays are C-order views of the library's: a gridded ensemble is {"u", "v", "t", "q": (E, kx, il, ix), "ps": (E, il, ix)}; an
+observation set is a dict of equal-length arrays var, lev, lon, lat, value, error."""
+import numpy as np
+
+U, V, T, Q, PS = range(5)
+VARS = ("u", "v", "t", "q", "ps")
+REARTH = 6.371e6
+EPS = float(np.finfo(np.float64).eps)
+CHUNK = 256          # LETKF_CHUNK of csrc/spdy_letkf.hip: observations the transform kernel scans per step
+
+
+class Geometry:
+    """what the definition reads from a plan: the grid and the levels (a host-only plan serves)"""
+
+    def __init__(self, sp):
+        self.ix, self.il, self.kx = sp.ix, sp.il, sp.kx
+        s = sp.table("sia_half")
+        self.lat = np.concatenate([-np.degrees(np.arcsin(s)), np.degrees(np.arcsin(s))[::-1]])       # south first
+        self.lon = np.arange(self.ix) * (360.0 / self.ix)
+        self.lnfsg = np.log(sp.table("fsg"))
+        lo, la = np.meshgrid(self.lon, self.lat)
+        self.colunit = unit(lo.ravel(), la.ravel())                                                 # (ncol, 3), column j*ix+i
+
+
+def unit(lon, lat):
+    rl, rp = np.radians(np.asarray(lon, np.float64)), np.radians(np.asarray(lat, np.float64))
+    return np.stack([np.cos(rp) * np.cos(rl), np.cos(rp) * np.sin(rl), np.sin(rp)], axis=-1)
+
+
+def make_obs(var, lev, lon, lat, value, error):
+    n = len(var)
+    return {"var": np.asarray(var, np.int64).reshape(n), "lev": np.asarray(lev, np.int64).reshape(n),
+            "lon": np.asarray(lon, np.float64).reshape(n), "lat": np.asarray(lat, np.float64).reshape(n),
+            "value": np.asarray(value, np.float64).reshape(n), "error": np.asarray(error, np.float64).reshape(n)}
+
+
+def concat(*sets):
+    return {k: np.concatenate([s[k] for s in sets]) for k in sets[0]}
+
+
+def args(obs):
+    """the arguments of Letkf.set_obs"""
+    return [obs[k] for k in ("var", "lev", "lon", "lat", "value", "error")]
+
+
+def stencil(g, lon, lat):
+    """-> (index (nobs, 4) of grid points j*ix+i, weight (nobs, 4)): (j0,i0) (j0,i1) (j1,i0) (j1,i1)"""
+    idx, wgt = np.zeros((len(lon), 4), np.int64), np.zeros((len(lon), 4))
+    for o, (lo, la) in enumerate(zip(lon, lat)):
+        x = np.fmod(lo, 360.0)
+        if x < 0.0:
+            x += 360.0
+        x = x / (360.0 / g.ix)
+        i0 = int(np.floor(x))
+        a = x - i0
+        if i0 >= g.ix:
+            i0, a = 0, 0.0
+        i1 = (i0 + 1) % g.ix
+        if la <= g.lat[0]:
+            j0, j1, b = 0, 0, 0.0
+        elif la >= g.lat[-1]:
+            j0, j1, b = g.il - 1, g.il - 1, 0.0
+        else:
+            j0 = min(int(np.searchsorted(g.lat, la, side="right")) - 1, g.il - 2)
+            j1 = j0 + 1
+            b = (la - g.lat[j0]) / (g.lat[j1] - g.lat[j0])
+        idx[o] = (j0 * g.ix + i0, j0 * g.ix + i1, j1 * g.ix + i0, j1 * g.ix + i1)
+        wgt[o] = ((1.0 - a) * (1.0 - b), a * (1.0 - b), (1.0 - a) * b, a * b)
+    return idx, wgt
+
+
+def dense_rows(g, idx, wgt):
+    """the stencils as rows of H over the grid: equal points of a stencil add up"""
+    H = np.zeros((idx.shape[0], g.ix * g.il))
+    for o in range(idx.shape[0]):
+        np.add.at(H[o], idx[o], wgt[o])
+    return H
+
+
+def obs_space(g, x, obs):
+    """-> hx (nobs, E), hxmean, Y (nobs, E), d"""
+    idx, w = stencil(g, obs["lon"], obs["lat"])
+    E, n = x["ps"].shape[0], len(obs["var"])
+    hx = np.zeros((n, E))
+    for o in range(n):
+        v = int(obs["var"][o])
+        f = x[VARS[v]].reshape(E, -1, g.il * g.ix)[:, 0 if v == PS else int(obs["lev"][o])]
+        i = idx[o]
+        hx[o] = ((w[o, 0] * f[:, i[0]] + w[o, 1] * f[:, i[1]]) + w[o, 2] * f[:, i[2]]) + w[o, 3] * f[:, i[3]]
+    s = np.zeros(n)
+    for e in range(E):
+        s = s + hx[:, e]
+    hxmean = s / E
+    return hx, hxmean, hx - hxmean[:, None], obs["value"] - hxmean
+
+
+def gc(r):
+    """Gaspari and Cohn's fifth-order function as the kernel evaluates it; support r < 2.  The outer branch r^5/12 - r^4/2 + 5r^3/8
+    + 5r^2/3 - 5r + 4 - 2/(3r) is taken in its factored form (2 - r)^4 (r^2 + 2r - 1/2) / (12 r), which does not cancel where the
+    weight fades out"""
+    r = np.asarray(r, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inner = (((-0.25 * r + 0.5) * r + 0.625) * r - 5.0 / 3.0) * (r * r) + 1.0
+        s = 2.0 - r
+        s2 = s * s
+        outer = (s2 * s2) * ((r + 2.0) * r - 0.5) / (12.0 * r)
+    return np.where(r < 2.0, np.where(r <= 1.0, inner, outer), 0.0)
+
+
+def gc_powers(r):
+    """the outer branch as the sum of powers of Gaspari and Cohn's eq. 4.10 (1 < r < 2)"""
+    return r ** 5 / 12.0 - r ** 4 / 2.0 + 5.0 * r ** 3 / 8.0 + 5.0 * r ** 2 / 3.0 - 5.0 * r + 4.0 - 2.0 / (3.0 * r)
+
+
+def distance(pc, po):
+    """great-circle distance in metres of unit vectors pc (nc, 3) and po (no, 3) -> (nc, no)"""
+    d = pc[:, None, :] - po[None, :, :]
+    chord = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+    return 2.0 * REARTH * np.arcsin(np.minimum(1.0, 0.5 * chord))
+
+
+def lnsigma(g, obs):
+    return np.where(obs["var"] == PS, 0.0, g.lnfsg[np.where(obs["var"] == PS, 0, obs["lev"])])
+
+
+def weights(g, obs, cols, sigma_h, sigma_v):
+    """-> w (ncols, kx, nobs)"""
+    wh = gc(distance(g.colunit[cols], unit(obs["lon"], obs["lat"])) / (sigma_h * np.sqrt(10.0 / 3.0)))
+    if sigma_v > 0.0:
+        wv = gc(np.abs(g.lnfsg[:, None] - lnsigma(g, obs)[None, :]) / (sigma_v * np.sqrt(10.0 / 3.0)))
+        return wh[:, None, :] * wv[None, :, :]
+    return np.repeat(wh[:, None, :], g.kx, axis=1)
+
+
+def pair(m, r, n):
+    """round-robin pair m of round r among n (even) players"""
+    if m == 0:
+        return n - 1, r
+    return (r + m) % (n - 1), (r - m + n - 1) % (n - 1)
+
+
+def jacobi(A, sweeps=30):
+    """cyclic Jacobi on a batch of symmetric matrices (N, n, n) -> (lam (N, n), V (N, n, n)): round-robin pairs, an odd n padded by
+    a decoupled row, a pair rotated unless |a_pq| <= eps/2 sqrt(a_pp a_qq), sweeps until no pair of any matrix rotates"""
+    N, n0 = A.shape[0], A.shape[1]
+    n = n0 + (n0 & 1)
+    M = np.zeros((n, n, N))                                      # the batch last: a pair's rows and columns are whole slabs
+    M[:n0, :n0] = np.moveaxis(A, 0, -1)
+    if n != n0:
+        M[n0, n0] = 1.0
+    Vv = np.zeros((n, n, N))
+    Vv[np.arange(n), np.arange(n)] = 1.0
+    for _ in range(sweeps):
+        rotated = False
+        for r in range(n - 1):
+            pq = [pair(m, r, n) for m in range(n // 2)]
+            p, q = np.array([a for a, _ in pq]), np.array([b for _, b in pq])
+            app, aqq, apq = M[p, p], M[q, q], M[p, q]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rot = ~(np.abs(apq) <= 0.5 * EPS * np.sqrt(app * aqq))
+                theta = (aqq - app) / (2.0 * apq)
+                t = np.copysign(1.0, theta) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+            c = np.where(rot, 1.0 / np.sqrt(t * t + 1.0), 1.0)
+            s = np.where(rot, t * c, 0.0)
+            rotated = rotated or bool(rot.any())
+            Mp, Mq = M[p], M[q]
+            M[p], M[q] = c[:, None] * Mp - s[:, None] * Mq, s[:, None] * Mp + c[:, None] * Mq
+            Mp, Mq = M[:, p], M[:, q]
+            M[:, p], M[:, q] = c[None] * Mp - s[None] * Mq, s[None] * Mp + c[None] * Mq
+            M[p, q] = np.where(rot, 0.0, M[p, q])
+            M[q, p] = np.where(rot, 0.0, M[q, p])
+            Vp, Vq = Vv[:, p], Vv[:, q]
+            Vv[:, p], Vv[:, q] = c[None] * Vp - s[None] * Vq, s[None] * Vp + c[None] * Vq
+        if not rotated:
+            break
+    lam = np.moveaxis(M[np.arange(n), np.arange(n)], -1, 0)
+    Vv = np.moveaxis(Vv, -1, 0)
+    if n != n0:      # the decoupled row keeps its place: column n0 of V stays e_n0
+        return lam[:, :n0], Vv[:, :n0, :n0]
+    return lam, Vv
+
+
+def local_problem(Y, d, r):
+    """C (E, E) and b (E) of one local problem: each element summed over the observations in ascending order; an observation with
+    r == 0 takes no part"""
+    E = Y.shape[1]
+    C, b = np.zeros((E, E)), np.zeros(E)
+    for o in np.nonzero(r != 0.0)[0]:
+        C = C + r[o] * (Y[o][:, None] * Y[o][None, :])
+        b = b + r[o] * (Y[o] * d[o])
+    return C, b
+
+
+def transform(C, b, E, rho, route="eigh"):
+    """batched: C (N, E, E), b (N, E) -> T (N, E, E), W, wbar, lam"""
+    A = C + ((E - 1) / rho) * np.eye(E)
+    lam, Vv = np.linalg.eigh(A) if route == "eigh" else jacobi(A)
+    W = np.einsum("nfi,ni,nei->nfe", Vv, np.sqrt((E - 1) / lam), Vv)
+    wbar = np.einsum("nfi,ni->nf", Vv, np.einsum("ngi,ng->ni", Vv, b) / lam)
+    return W + wbar[:, :, None] - np.eye(E), W, wbar, lam
+
+
+def problems(g, x, obs, sigma_h, sigma_v, cols=None):
+    """C (ncols, kx, E, E) and b (ncols, kx, E) of the local problems at the grid columns `cols` (default: all)"""
+    cols = np.arange(g.ix * g.il) if cols is None else np.asarray(cols)
+    E, kx, nc, n = x["ps"].shape[0], g.kx, len(cols), len(obs["var"])
+    C, b = np.zeros((nc, kx, E, E)), np.zeros((nc, kx, E))
+    if n:
+        _, _, Y, d = obs_space(g, x, obs)
+        r = weights(g, obs, cols, sigma_h, sigma_v) * (1.0 / (obs["error"] * obs["error"]))[None, None, :]
+        for o in np.nonzero((r != 0.0).any(axis=(0, 1)))[0]:      # ascending; r == 0 adds an exact zero
+            C += r[:, :, o, None, None] * (Y[o][:, None] * Y[o][None, :])
+            b += r[:, :, o, None] * (Y[o] * d[o])
+    return C, b
+
+
+def increments(g, x, C, b, rho, route="eigh", cols=None):
+    """-> ({"u" .. "q": (E, kx, ncols), "ps": (E, ncols)}, the largest condition number of A)"""
+    cols = np.arange(g.ix * g.il) if cols is None else np.asarray(cols)
+    nc, kx, E = b.shape
+    Tm, _, _, lam = transform(C.reshape(-1, E, E), b.reshape(-1, E), E, rho, route)
+    Tm = Tm.reshape(nc, kx, E, E)
+    out = {}
+    for v in VARS:
+        f = x[v].reshape(E, -1, g.il * g.ix)[:, :, cols]                     # (E, kx or 1, ncols)
+        s = np.zeros(f.shape[1:])
+        for e in range(E):
+            s = s + f[e]
+        xp = f - (s / E)[None]
+        Tv = Tm if v != "ps" else Tm[:, kx - 1:kx]
+        out[v] = np.einsum("fkc,ckfe->ekc", xp, Tv)
+    out["ps"] = out["ps"][:, 0]
+    return out, float(np.max(lam.max(axis=1) / lam.min(axis=1)))
+
+
+def analyse(g, x, obs, sigma_h, sigma_v, rho, route="eigh", cols=None):
+    """The increments of the gridded ensemble x at the grid columns `cols` (default: all), and the largest condition number"""
+    C, b = problems(g, x, obs, sigma_h, sigma_v, cols)
+    return increments(g, x, C, b, rho, route, cols)
+
+
+def at_columns(a, cols):
+    """a device result (E, kx, il, ix) / (E, il, ix) at grid columns, in the shape `increments` gives"""
+    return a.reshape(a.shape[:-2] + (-1,))[..., cols]
+
+
+def perturbation_scale(x):
+    """max |x_e - mean| per variable"""
+    return {v: float(np.max(np.abs(x[v] - x[v].mean(axis=0)))) for v in VARS}
+
+
+# ---------------------------------------------------------------------------------------------------- inputs of the tests
+SCALE = {"u": (5.0, 3.0), "v": (0.0, 3.0), "t": (260.0, 2.0), "q": (4.0, 0.8), "ps": (0.0, 0.01)}      # (base, member spread)
+
+
+def ensemble(g, E, seed=0):
+    """a gridded ensemble of E different members: a smooth base state plus white member noise of SCALE's spread"""
+    rng = np.random.default_rng(seed)
+    lo, la = np.meshgrid(np.radians(g.lon), np.radians(g.lat))
+    x = {}
+    for v in VARS:
+        base, s = SCALE[v]
+        shape = (E, g.kx, g.il, g.ix) if v != "ps" else (E, g.il, g.ix)
+        lev = np.arange(g.kx)[:, None, None] if v != "ps" else 0.0
+        x[v] = base + 3.0 * s * np.cos(la) * np.sin(2.0 * lo + 0.3 * lev) + s * rng.standard_normal(shape)
+    return x
+
+
+def observe(g, x, var, lev, lon, lat, err_factor, seed=1):
+    """observations of member 0 with errors err_factor * SCALE's spread: value = H x_0 + error * noise"""
+    rng = np.random.default_rng(seed)
+    err = err_factor * np.array([SCALE[VARS[v]][1] for v in var])
+    obs = make_obs(var, lev, lon, lat, np.zeros(len(var)), err)
+    hx, _, _, _ = obs_space(g, x, obs)
+    obs["value"] = hx[:, 0] + err * rng.standard_normal(len(var))
+    return obs
+
+
+def edge_points(g):
+    """(lon, lat) of the operator's edge cases: on a grid point, between columns ix-1 and 0, poleward of the outermost row at both
+    poles, at lon = 360, at negative longitude, on the outermost rows themselves"""
+    return [(float(g.lon[5]), float(g.lat[7])), (359.0, 12.3), (float(g.lon[-1]) + 1.7, -33.0), (10.0, 89.9), (200.0, -89.5),
+            (77.0, 90.0), (300.0, -90.0), (360.0, 45.0), (-12.5, -5.0), (-360.0, 0.0), (725.0, 60.0), (40.0, float(g.lat[0])),
+            (41.0, float(g.lat[-1])), (0.0, 0.0)]
+
+
+def edge_obs(g, x, nrandom=26, err_factor=0.5, seed=3):
+    """about 40 observations: every edge point with a cycling variable and level, then random ones"""
+    rng = np.random.default_rng(seed)
+    pts = edge_points(g) + [(float(rng.uniform(-400, 400)), float(rng.uniform(-90, 90))) for _ in range(nrandom)]
+    var = [o % 5 for o in range(len(pts))]
+    lev = [(3 * o) % g.kx for o in range(len(pts))]
+    return observe(g, x, var, lev, [p[0] for p in pts], [p[1] for p in pts], err_factor, seed)
+
+
+def clustered_obs(g, x, n=1500, centre=(100.0, 20.0), half_width=3.0, err_factor=0.125, seed=5):
+    """n observations of every variable and level within half_width degrees of centre: all in range of the columns around it"""
+    rng = np.random.default_rng(seed)
+    var = rng.integers(0, 5, n)
+    lev = rng.integers(0, g.kx, n)
+    lon = centre[0] + rng.uniform(-half_width, half_width, n)
+    lat = centre[1] + rng.uniform(-half_width, half_width, n)
+    return observe(g, x, var, lev, lon, lat, err_factor, seed)
+
+
+def sparse_obs(g, x, n=60, err_factor=0.125, seed=7):
+    """n observations spread over the globe"""
+    rng = np.random.default_rng(seed)
+    return observe(g, x, rng.integers(0, 5, n), rng.integers(0, g.kx, n), rng.uniform(0, 360, n),
+                   np.degrees(np.arcsin(rng.uniform(-1, 1, n))), err_factor, seed)
+
+
+def columns_for(g, obs, sigma_h, most=48, outside=16, seed=11):
+    """columns to compare at: up to `most` in range of an observation (the nearest ones and the farthest ones among them) and
+    `outside` that are out of range of all"""
+    rng = np.random.default_rng(seed)
+    dmin = distance(g.colunit, unit(obs["lon"], obs["lat"])).min(axis=1)
+    inside = np.nonzero(dmin < 2.0 * sigma_h * np.sqrt(10.0 / 3.0))[0]
+    inside = inside[np.argsort(dmin[inside])]
+    if len(inside) > most:
+        inside = np.concatenate([inside[:most // 2], inside[-(most // 4):], rng.choice(inside[most // 2:-(most // 4)], most // 4, False)])
+    out = np.nonzero(dmin >= 2.0 * sigma_h * np.sqrt(10.0 / 3.0))[0]
+    return np.concatenate([inside, rng.choice(out, min(outside, len(out)), False)]).astype(np.int64)

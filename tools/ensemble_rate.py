@@ -30,11 +30,19 @@ three launches whatever E -- against E captured advances of single objects repla
 with the whole physics and SPPT (Ensemble.step with physics["sppt"]) against the same step without SPPT and against E single-state
 captured steps with SPPT (tests/modelstep.py's sppt_physics), each on a state, a workspace and a pattern object of its own.
 
+--letkf measures the ensemble ANALYSIS instead (include/spdy.h, "ensemble analysis"; T30 L8, E = 4, 16 and 32, 100 replays per timing
+unless told otherwise): graph replays of Ensemble.analyse -- five launches, six where the direct batch streams (here from E = 16 on) -- with a network of 416 columns (26 x 16) that
+observes u, v, t, q at every level and ps, 13 728 observations, sigma_h = 500 km, sigma_v = 0.1, rho = 1.1; each observation has the
+members' spread at its place as error and a value one such error around their mean.  Next to it the captured ensemble step with
+the whole physics, whose 36 replays are the model side of one six-hour cycle.  Every repeat starts from the same state; inside a
+repeat the replays analyse the state the replay before left.
+
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
     python tools/ensemble_rate.py --coupled --members 1 2 4 8 16
     python tools/ensemble_rate.py --output --json profiles/ensemble_output_rate.json
     python tools/ensemble_rate.py --sppt --json profiles/ensemble_sppt_rate.json
+    python tools/ensemble_rate.py --letkf --json profiles/ensemble_letkf_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
 import ctypes
@@ -433,6 +441,84 @@ def run_sppt(tag, members, reps, repeats, label, rows):
     sp.close()
 
 
+def run_letkf(tag, members, reps, repeats, label, rows):
+    """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle)"""
+    import ensemblestep
+    from oracle.pyoracle import Oracle, build
+    build()
+    kx = VARIANTS[tag][3]
+    o = Oracle(*VARIANTS[tag])
+    if tag in synth.SIGMA_SETS:
+        o.set_sigma(synth.SIGMA_SETS[tag])
+    sp = moist.plan(tag, max(members) * (4 * kx + 4))
+    case = physstep.Case(tag, sp, o)
+    sp.surface_set_orography(case.phis0)
+    dt = physstep.DT[tag]
+    sp.initialize_implicit(dt)
+    sp.physics_workspace()
+    P = modelstep.physics_buffers(sp, case.bnd, 0.0)
+    modelstep.step(sp, modelstep.device_state(case.st), modelstep.Workspace(sp), dt, physics=modelstep.whole_physics(P, True))
+    sp.synchronize()
+    rad0 = P["rad"].clone()                                   # after a shortwave step: the radiation state is whole
+    # the network: 26 x 16 columns, u, v, t, q at every level and ps
+    lon, lat = np.meshgrid((np.arange(26) + 0.5) * (360.0 / 26), -75.0 + 10.0 * np.arange(16))
+    var = np.concatenate([np.repeat(np.arange(4), kx), [4]])
+    lev = np.concatenate([np.tile(np.arange(kx), 4), [0]])
+    nloc, per = lon.size, var.size
+    cols = [np.tile(var, nloc), np.tile(lev, nloc), np.repeat(lon.ravel(), per), np.repeat(lat.ravel(), per)]
+    nobs = nloc * per
+    rng = np.random.default_rng(0)
+    fns, nodes, rearms, keep = {}, {}, [], []
+    for E in members:
+        # the members: the case's state plus a hundredth of the differences between seeded states (0.3 K in t)
+        ms = ensemblestep.member_states(sp, E + 1)
+        en = s.Ensemble(sp, E)
+        en.set_shared(case.st)
+        for e in range(E):
+            en.set_member(e, {n: case.st[n] + 0.01 * (ms[e + 1][n] - ms[0][n]) for n in modelstep.PROG})
+        start = {n: getattr(en, n).clone() for n in modelstep.PROG}
+        lt = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1)
+        lt.set_obs(*cols, np.zeros(nobs), np.ones(nobs))
+        en.analyse(lt)                                        # a first call gives H x of every member: the values come from it
+        torch.cuda.synchronize()
+        f = lt.fields()
+        spread = f["hx"].std(dim=1).cpu().numpy() + 1e-300
+        lt.set_obs(*cols, f["hxmean"].cpu().numpy() + spread * rng.standard_normal(nobs), spread)
+        dev = physstep.device_boundary(case.bnd, sp.il, sp.ix)
+        bnd = {n: v.expand((E,) + tuple(v.shape[1:])).contiguous() for n, v in dev.items()}
+        PE = {"bnd": bnd, "albsfc": bnd["albsfc"], "rad": rad0.repeat(E), "sw": False}
+        en.physics_workspace()
+        for n, v in start.items():
+            getattr(en, n).copy_(v)
+        torch.cuda.synchronize()
+        with sp.graph_capture() as g:
+            en.analyse(lt)
+        fns["analysis E=%d" % E], nodes["analysis E=%d" % E] = g.launch, g.num_nodes()
+        with sp.graph_capture() as gs:
+            en.step(2, 2, dt, PE, eps=modelstep.ROB)
+        fns["step E=%d physics" % E], nodes["step E=%d physics" % E] = gs.launch, gs.num_nodes()
+
+        def rearm(en=en, start=start, PE=PE, E=E):
+            for n, v in start.items():
+                getattr(en, n).copy_(v)
+            PE["rad"].copy_(rad0.repeat(E))
+        rearms.append(rearm)
+        keep.append((en, lt, PE, g, gs))
+    t = time_interleaved(fns, lambda: [r() for r in rearms], reps, repeats)
+    for name, (med, lo, hi) in t.items():
+        E = int(name.split("=")[1].split()[0])
+        row = {"label": label, "size": tag, "form": name, "members": E, "observations": nobs, "nodes": nodes[name], "us": round(med, 2),
+               "us_min": round(lo, 2), "us_max": round(hi, 2)}
+        if name.startswith("analysis"):
+            cycle = 36 * t["step E=%d physics" % E][0]
+            row.update(us_36_steps=round(cycle, 1), analysis_share_of_cycle=round(med / (med + cycle), 4))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for _, lt, _, g, gs in keep:
+        g.close(); gs.close(); lt.close()
+    sp.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+")
@@ -441,15 +527,16 @@ def main():
     ap.add_argument("--coupled", action="store_true")
     ap.add_argument("--output", action="store_true")
     ap.add_argument("--sppt", action="store_true")
+    ap.add_argument("--letkf", action="store_true")
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
     ap.add_argument("--reps", type=int)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--json")
     a = ap.parse_args()
-    a.sizes = a.sizes or (["t30"] if a.sppt else ["t30", "t63k16"])
-    a.members = a.members or ([1, 4, 16] if a.sppt else [1, 2, 4, 8, 16, 32])
-    a.reps = a.reps or (100 if a.sppt else 200)
+    a.sizes = a.sizes or (["t30"] if a.sppt or a.letkf else ["t30", "t63k16"])
+    a.members = a.members or ([4, 16, 32] if a.letkf else [1, 4, 16] if a.sppt else [1, 2, 4, 8, 16, 32])
+    a.reps = a.reps or (100 if a.sppt or a.letkf else 200)
     if a.single_only:          # a library from before the ensemble entry points: bind (on first use) without them
         from speedy_f90_amd import _lib
         for n in [n for n in _lib.SIGNATURES if n.startswith("spdy_ens_") or n == "spdy_sppt_members"]:
@@ -460,7 +547,9 @@ def main():
     rows = []
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
-            if a.sppt:
+            if a.letkf:
+                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows)
+            elif a.sppt:
                 run_sppt(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.output:
                 run_output(tag, a.members, a.reps, a.repeats, a.label, rows)

@@ -1,0 +1,87 @@
+/* Host check of the observation ingestion (include/spdy.h, "ensemble analysis"): spdy_letkf_set_obs and spdy_letkf_table on a
+ * host-only plan, fed the operator's edge cases, nobs = 0 and nobs = max_obs.  Built by `make hostcheck` in speedy.f90_amd with
+ * the address and undefined-behaviour sanitizers on the host code of the plan, the tables and the analysis; exits 0 when every
+ * stencil is a convex combination of four grid points and every rejection is the documented code. */
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "spdy.h"
+
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            fprintf(stderr, "line %d: %s -- %s\n", __LINE__, #cond, spdy_last_error()); \
+            return 1;                                                        \
+        }                                                                    \
+    } while (0)
+
+static int tables_ok(spdy_letkf *l, int nobs, int ncol)
+{
+    static const char *const names[5] = {"stencil_index", "stencil_weight", "unit", "lnsigma", "rinv"};
+    static const int per[5] = {4, 4, 3, 1, 1};
+    for (int t = 0; t < 5; ++t) {
+        const int n = spdy_letkf_table(l, names[t], NULL, 0);
+        if (n != per[t] * nobs) return 0;
+        double *buf = malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));
+        if (spdy_letkf_table(l, names[t], buf, n) != n) { free(buf); return 0; }
+        if (n > 0 && spdy_letkf_table(l, names[t], buf, n - 1) != SPDY_ERR_ARG) { free(buf); return 0; }
+        for (int o = 0; o < nobs; ++o) {
+            double sum = 0.0;
+            for (int c = 0; c < per[t]; ++c) {
+                const double v = buf[per[t] * o + c];
+                if (!isfinite(v)) { free(buf); return 0; }
+                if (t == 0 && (v < 0 || v >= ncol || v != floor(v))) { free(buf); return 0; }
+                if (t == 1 && (v < 0.0 || v > 1.0)) { free(buf); return 0; }
+                sum += t == 2 ? v * v : v;
+            }
+            if ((t == 1 || t == 2) && fabs(sum - 1.0) > 1e-14) { free(buf); return 0; }
+        }
+        free(buf);
+    }
+    return 1;
+}
+
+int main(void)
+{
+    enum { KX = 5, IX = 96, IY = 24, MAXOBS = 64 };
+    spdy_plan *p = NULL;
+    spdy_letkf *l = NULL;
+    CHECK(spdy_plan_create(30, IX, IY, KX, 3 * (2 * KX + 1), SPDY_DEVICE_NONE, &p) == SPDY_OK);
+    CHECK(spdy_letkf_create(p, 3, MAXOBS, &l) == SPDY_OK);
+    CHECK(spdy_letkf_set_localization(l, 5.0e5, 0.1, 1.1) == SPDY_OK);
+    /* on a grid point's longitude, between columns ix-1 and 0, poleward of the outermost rows, the poles, lon = 360, negative
+     * and large longitudes, the equator */
+    static const double pts[][2] = {{18.75, 12.0}, {359.0, 12.3}, {358.1, -33.0}, {10.0, 89.9}, {200.0, -89.5}, {77.0, 90.0},
+                                    {300.0, -90.0}, {360.0, 45.0}, {-12.5, -5.0}, {-360.0, 0.0}, {725.0, 60.0}, {-1e-20, 1.0},
+                                    {1e6, -1.0}, {0.0, 0.0}};
+    const int npts = (int)(sizeof(pts) / sizeof(pts[0]));
+    spdy_obs obs[MAXOBS];
+    for (int o = 0; o < MAXOBS; ++o) {
+        obs[o].var = o % 5; obs[o].lev = obs[o].var == SPDY_OBS_PS ? 99 : (3 * o) % KX;      /* lev is ignored for PS */
+        obs[o].lon = pts[o % npts][0] + 0.37 * (o / npts); obs[o].lat = pts[o % npts][1];
+        obs[o].value = 1.0 + o; obs[o].error = 0.5 + o;
+    }
+    CHECK(spdy_letkf_set_obs(l, 0, NULL) == SPDY_OK && tables_ok(l, 0, IX * 2 * IY));
+    CHECK(spdy_letkf_set_obs(l, npts, obs) == SPDY_OK && tables_ok(l, npts, IX * 2 * IY));
+    CHECK(spdy_letkf_set_obs(l, MAXOBS, obs) == SPDY_OK && tables_ok(l, MAXOBS, IX * 2 * IY));
+    /* rejections leave the tables alone */
+    CHECK(spdy_letkf_set_obs(l, MAXOBS + 1, obs) == SPDY_ERR_ARG);
+    CHECK(spdy_letkf_set_obs(l, -1, obs) == SPDY_ERR_ARG && spdy_letkf_set_obs(l, 1, NULL) == SPDY_ERR_ARG);
+    spdy_obs bad = obs[0];
+    bad.var = 5; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG); bad = obs[0];
+    bad.lev = KX; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG); bad = obs[0];
+    bad.lat = 90.0001; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG); bad = obs[0];
+    bad.lon = INFINITY; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG); bad = obs[0];
+    bad.value = NAN; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG); bad = obs[0];
+    bad.error = 0.0; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG); bad = obs[0];
+    bad.error = NAN; CHECK(spdy_letkf_set_obs(l, 1, &bad) == SPDY_ERR_ARG);
+    CHECK(tables_ok(l, MAXOBS, IX * 2 * IY));
+    CHECK(spdy_letkf_table(l, "nothing", NULL, 0) == SPDY_ERR_ARG);
+    double *d = NULL;
+    CHECK(spdy_letkf_field(l, "hx", &d) == SPDY_ERR_NO_DEVICE);
+    CHECK(spdy_ens_letkf_dev(l, (double *)obs, (double *)obs, (double *)obs, (double *)obs, (double *)obs) == SPDY_ERR_NO_DEVICE);
+    CHECK(spdy_letkf_destroy(l) == SPDY_OK && spdy_plan_destroy(p) == SPDY_OK);
+    printf("letkf host check ok: %d edge observations, 0 and %d observations\n", npts, (int)MAXOBS);
+    return 0;
+}
