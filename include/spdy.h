@@ -973,12 +973,46 @@ int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf
  * is not touched and phi is stale afterwards: the run continues with first_step, as a model started from an analysis does.
  * Members are coupled by construction: a non-finite member makes every column it touches non-finite (as NaN, after the full
  * count of sweeps), and there is no member mask -- the caller builds the analysis ensemble from members the guard has not stopped.
+ * Weight interpolation (Yang, Kalnay, Hunt and Bowler 2009): T varies slowly in space, because the localisation function is smooth
+ * over several grid spacings, so the local problems may be solved on a coarse subset of the columns only, and every other column
+ * gets T by bilinear interpolation from the four coarse columns around it.
+ *   stride        (si, sj): si divides ix, 1 <= si <= ix/2, 1 <= sj <= il-1.  Coarse longitudes i = 0, si, 2 si, ..., periodic;
+ *                 coarse rows j = 0, sj, 2 sj, ... together with il-1, so the last latitude interval may be shorter than sj.  A
+ *                 coarse column is a grid column j*ix+i with i and j both coarse; the coarse list has them in ascending order.
+ *   stencil       of grid column (i, j): i0 = (i/si) si, i1 = (i0 + si) mod ix, a = (i - i0)/si; j0 the largest coarse row <= j, j1
+ *                 the next coarse row, or j0 itself when j == il-1; b = (j - j0)/(j1 - j0), 0 when j1 == j0.  The points (j0,i0)
+ *                 (j0,i1) (j1,i0) (j1,i1) with weights (1-a)(1-b), a(1-b), (1-a)b, ab: the operator's order and form.  The
+ *                 interpolation is in index space: longitude is uniform and the Gaussian rows are uniform to within a fraction
+ *                 of a percent, so no latitude enters.
+ *   transform     for level k, T[f][e] = ((w0 T0[f][e] + w1 T1[f][e]) + w2 T2[f][e]) + w3 T3[f][e]; a term whose weight is exactly
+ *                 zero is neither read nor added, and the first term present starts the sum.  So at a coarse column T is 1.0 * T0,
+ *                 bit for bit the solved T; on a coarse row or a coarse longitude only two terms exist; and a column depends on no
+ *                 coarse column outside its stencil.
+ *   increments    exactly those above on the interpolated T: the mean over the members ascending, dx_e = sum_f (x_f - xmean)
+ *                 T[f][e] with f ascending, ps with T of level kx-1.  The local problem at a coarse column is the one above,
+ *                 unchanged: the observations in range of that column, the same ascending sums, the same Jacobi.
+ * Consequences: with no observation and rho = 1 every T is exactly zero and so is every increment; a fine column's result depends
+ * only on the observations in range of its stencil's coarse columns, not on those in its own range; pure inflation by rho != 1 is
+ * exact at coarse columns and holds to a few ulps elsewhere, because the weights do not sum to 1 exactly.
+ * spdy_letkf_set_weight_stride: (1, 1), the default after create, is the path above exactly -- the same kernels, the same launch
+ * count, no weight buffer.  Any other stride builds the coarse list and every column's stencil (indices into the coarse list) on
+ * the host, uploads them and allocates the weight buffer, ncoarse kx nmem nmem doubles laid out [coarse][k][f][e]; stream-ordered
+ * and synchronising like set_obs.  It works on a host-only plan, where it builds the tables only.  A graph captured before a
+ * change of stride has to be captured again.  spdy_letkf_table then also gives "coarse_columns" (the grid indices, as doubles),
+ * "interp_index" (4 per grid column; an entry of weight zero repeats the first index) and "interp_weight" (4 per grid column);
+ * at stride (1, 1) all three have count 0.  spdy_letkf_field gives "weights", the device weight buffer, valid after an analysis
+ * call at a stride other than (1, 1); SPDY_ERR_STATE at stride (1, 1).  At such a stride spdy_letkf_analyse_grid_dev is three
+ * launches -- the observation kernel, the transform kernel on the coarse columns only, which writes T of every level into the
+ * weight buffer instead of increments, and a kernel over all grid columns that interpolates T and forms the increments -- and
+ * spdy_ens_letkf_dev six (seven where the direct batch streams); both remain capturable, nothing is allocated in the call.
  * Checks, in this order -- create: a NULL plan, nmem outside [2, 32], max_obs < 0, a NULL result pointer, max_batch, the LDS
  * size SPDY_ERR_ARG; no sigma levels, an open capture SPDY_ERR_STATE.  set_obs: a NULL object, nobs outside [0, max_obs], NULL
  * observations, the first invalid field of the first invalid observation (var, lev, lon, lat, value, error) SPDY_ERR_ARG; an open
  * capture SPDY_ERR_STATE.  The *_dev calls: a NULL object SPDY_ERR_ARG; no localisation set SPDY_ERR_STATE; a NULL pointer
- * SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last (spdy_letkf_field: after its name check).  create, set_localization,
- * set_obs and table work on a host-only plan.  A failing call enqueues nothing.                                                 */
+ * SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last (spdy_letkf_field: after its name check, and after SPDY_ERR_STATE for "weights" at stride (1, 1)).
+ * set_weight_stride: a NULL object, an invalid stride SPDY_ERR_ARG (nothing changes); an open capture SPDY_ERR_STATE; a failed
+ * allocation or copy SPDY_ERR_HIP, and the object is left at stride (1, 1).  create, set_localization, set_obs, set_weight_stride
+ * and table work on a host-only plan.  A failing call enqueues nothing.                                                         */
 typedef struct spdy_letkf spdy_letkf;
 enum { SPDY_OBS_U, SPDY_OBS_V, SPDY_OBS_T, SPDY_OBS_Q, SPDY_OBS_PS };
 typedef struct {
@@ -989,6 +1023,7 @@ int spdy_letkf_create(spdy_plan *plan, int nmem, int max_obs, spdy_letkf **l);
 int spdy_letkf_destroy(spdy_letkf *l);
 int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h_m, double sigma_v_lnsigma, double rho);
 int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host);
+int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj);
 int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap);
 int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr);
 int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg,

@@ -1,5 +1,6 @@
 // C ABI of the ensemble analysis (include/spdy.h, "ensemble analysis"): the observation ingestion on the host, the
-// analysis of a gridded ensemble and the five-launch analysis of an ensemble's spectral state.  Kernels: csrc/spdy_letkf.hip.
+// analysis of a gridded ensemble, the five-launch analysis of an ensemble's spectral state, and the tables and the buffer of weight
+// interpolation (one launch more).  Kernels: csrc/spdy_letkf.hip.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -82,8 +83,67 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
     c.y = l->d_y; c.dep = l->d_dep;
     for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = dx[v]; }
     KERNEL(spdy::launch_letkf_obs(o, p->stream));
+    if (!l->d_tw) {
+        KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
+        return SPDY_OK;
+    }
+    // weight interpolation: T of the coarse columns, then the increments of every column from them
+    c.nlist = (int)l->h_coarse.size(); c.cols = l->d_coarse; c.tw = l->d_tw;
+    spdy::LetkfApply ap{};
+    ap.nmem = l->nmem; ap.kx = kx; ap.ncol = ncol; ap.nlist = c.nlist;
+    ap.iidx = l->d_iidx; ap.iwgt = l->d_iwgt; ap.tw = l->d_tw;
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) { ap.x[v] = x[v]; ap.dx[v] = dx[v]; }
     KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
+    KERNEL(spdy::launch_letkf_apply(ap, p->stream));
     return SPDY_OK;
+}
+
+// the coarse columns of a stride and every grid column's stencil in them (include/spdy.h, "ensemble analysis": weight interpolation)
+void interp_tables(int ix, int il, int si, int sj, std::vector<int> &coarse, std::vector<int> &idx, std::vector<double> &wgt)
+{
+    std::vector<int> rows;                    // the coarse rows, ascending: 0, sj, 2 sj, ... and il - 1
+    for (int j = 0; j < il - 1; j += sj) rows.push_back(j);
+    rows.push_back(il - 1);
+    const int ni = ix / si;
+    coarse.clear();
+    for (int j : rows)
+        for (int i = 0; i < ix; i += si) coarse.push_back(j * ix + i);
+    idx.assign((size_t)4 * ix * il, 0);
+    wgt.assign((size_t)4 * ix * il, 0.0);
+    size_t r0 = 0;                            // rows[r0] is the largest coarse row <= j
+    for (int j = 0; j < il; ++j) {
+        while (r0 + 1 < rows.size() && rows[r0 + 1] <= j) ++r0;
+        const size_t r1 = j == il - 1 ? r0 : r0 + 1;
+        const int j0 = rows[r0], j1 = rows[r1];
+        const double b = j1 == j0 ? 0.0 : (double)(j - j0) / (double)(j1 - j0);
+        for (int i = 0; i < ix; ++i) {
+            const int c0 = i / si, c1 = (c0 + 1) % ni;
+            const double a = (double)(i - c0 * si) / (double)si;
+            const int e[4] = {(int)r0 * ni + c0, (int)r0 * ni + c1, (int)r1 * ni + c0, (int)r1 * ni + c1};
+            const double w[4] = {(1.0 - a) * (1.0 - b), a * (1.0 - b), (1.0 - a) * b, a * b};
+            const size_t at = 4 * ((size_t)j * ix + i);
+            int first = -1;
+            for (int n = 0; n < 4 && first < 0; ++n)
+                if (w[n] != 0.0) first = e[n];
+            for (int n = 0; n < 4; ++n) {
+                wgt[at + n] = w[n];
+                idx[at + n] = w[n] != 0.0 ? e[n] : first;      // an entry that is not read repeats the first one that is
+            }
+        }
+    }
+}
+
+void drop_interp(spdy_letkf *l)
+{
+    if (l->d_wbase) {
+        (void)hipSetDevice(l->plan->device);
+        (void)hipStreamSynchronize(l->plan->stream);
+        (void)hipFree(l->d_wbase);
+    }
+    l->d_wbase = l->d_tw = l->d_iwgt = nullptr;
+    l->d_iidx = l->d_coarse = nullptr;
+    l->si = l->sj = 1;
+    l->h_coarse.clear(); l->h_iidx.clear(); l->h_iwgt.clear();
 }
 }  // namespace
 
@@ -174,6 +234,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
 int spdy_letkf_destroy(spdy_letkf *l)
 {
     if (!l) return SPDY_OK;
+    drop_interp(l);
     if (l->d_base) {
         (void)hipSetDevice(l->plan->device);
         (void)hipStreamSynchronize(l->plan->stream);
@@ -253,18 +314,63 @@ int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
     return SPDY_OK;
 }
 
+int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
+{
+    NEED_LETKF(l);
+    spdy_plan *p = l->plan;
+    const int ix = p->tab.ix, il = p->tab.il, kx = p->tab.kx;
+    if (si < 1 || si > ix / 2 || ix % si) return fail(SPDY_ERR_ARG, "letkf_set_weight_stride: si=%d must divide ix=%d and lie in [1, %d]", si, ix, ix / 2);
+    if (sj < 1 || sj > il - 1) return fail(SPDY_ERR_ARG, "letkf_set_weight_stride: sj=%d outside [1, %d]", sj, il - 1);
+    NOT_CAPTURING(p, "spdy_letkf_set_weight_stride (allocation + upload)");
+    drop_interp(l);
+    if (si == 1 && sj == 1) return SPDY_OK;
+    std::vector<int> coarse, idx;
+    std::vector<double> wgt;
+    interp_tables(ix, il, si, sj, coarse, idx, wgt);
+    if (p->device >= 0) {
+        HIP_TRY(hipSetDevice(p->device));
+        const size_t nc = coarse.size(), ncol = grid_elems(p), ntw = nc * kx * l->nmem * l->nmem;
+        const size_t bytes = (ntw + 4 * ncol) * sizeof(double) + (4 * ncol + nc) * sizeof(int);
+        if (hipMalloc(reinterpret_cast<void **>(&l->d_wbase), bytes) != hipSuccess) {
+            l->d_wbase = nullptr;
+            return fail(SPDY_ERR_HIP, "letkf_set_weight_stride: hipMalloc of %zu bytes failed", bytes);
+        }
+        l->d_tw = l->d_wbase;
+        l->d_iwgt = l->d_tw + ntw;
+        l->d_iidx = reinterpret_cast<int *>(l->d_iwgt + 4 * ncol);
+        l->d_coarse = l->d_iidx + 4 * ncol;
+        auto all = [&]() -> int {
+            HIP_TRY(hipMemsetAsync(l->d_tw, 0, ntw * sizeof(double), p->stream));
+            RC(upload(p, l->d_iwgt, wgt.data(), 4 * ncol * sizeof(double)));
+            RC(upload(p, l->d_iidx, idx.data(), 4 * ncol * sizeof(int)));
+            RC(upload(p, l->d_coarse, coarse.data(), nc * sizeof(int)));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            return SPDY_OK;
+        };
+        if (const int rc = all()) {
+            drop_interp(l);                   // back at stride (1, 1); no copy is still reading the host arrays when they go
+            return rc;
+        }
+    }
+    l->si = si; l->sj = sj;
+    l->h_coarse.swap(coarse); l->h_iidx.swap(idx); l->h_iwgt.swap(wgt);
+    return SPDY_OK;
+}
+
 int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap)
 {
     NEED_LETKF(l);
     if (!name) return fail(SPDY_ERR_ARG, "null table name");
-    const bool index = !std::strcmp(name, "stencil_index");
+    const std::vector<int> *index = !std::strcmp(name, "stencil_index") ? &l->h_sidx : !std::strcmp(name, "coarse_columns") ? &l->h_coarse
+                                    : !std::strcmp(name, "interp_index") ? &l->h_iidx : nullptr;
     const std::vector<double> *v = !std::strcmp(name, "stencil_weight") ? &l->h_swgt : !std::strcmp(name, "unit") ? &l->h_unit
-                                   : !std::strcmp(name, "lnsigma") ? &l->h_lns : !std::strcmp(name, "rinv") ? &l->h_rinv : nullptr;
+                                   : !std::strcmp(name, "lnsigma") ? &l->h_lns : !std::strcmp(name, "rinv") ? &l->h_rinv
+                                   : !std::strcmp(name, "interp_weight") ? &l->h_iwgt : nullptr;
     if (!index && !v) return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
-    const int n = static_cast<int>(index ? l->h_sidx.size() : v->size());
+    const int n = static_cast<int>(index ? index->size() : v->size());
     if (buf && cap < n) return fail(SPDY_ERR_ARG, "analysis table '%s' has %d values, the buffer %d", name, n, cap);
     if (buf && index)
-        for (int i = 0; i < n; ++i) buf[i] = l->h_sidx[i];
+        for (int i = 0; i < n; ++i) buf[i] = (*index)[i];
     else if (buf && n)
         std::memcpy(buf, v->data(), sizeof(double) * (size_t)n);
     return n;
@@ -275,8 +381,10 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
     NEED_LETKF(l);
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
     double *const *f = !std::strcmp(name, "hx") ? &l->d_hx : !std::strcmp(name, "hxmean") ? &l->d_hxmean
-                       : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep : nullptr;
+                       : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep
+                       : !std::strcmp(name, "weights") ? &l->d_tw : nullptr;
     if (!f) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
+    if (f == &l->d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
     NEED_DEVICE(l->plan);
     *d_ptr = *f;
     return SPDY_OK;

@@ -522,10 +522,27 @@ struct LetkfCols {
     const double *y, *dep;                           // as LetkfObs
     const double *x[LETKF_VARS];
     double *dx[LETKF_VARS];                          // the increments; may be x
+    // weight interpolation (both NULL / 0: every grid column is solved and gets its increments).  With a column list the
+    // workgroups solve the nlist listed columns only and write T of every level, [list][kx][nmem][nmem], instead of increments
+    int nlist;
+    const int *cols;                                 // [nlist] grid columns j * ix + i, ascending
+    double *tw;
 };
 size_t letkf_lds_bytes(int nmem, int kx, int nlv);
 hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s);
 hipError_t letkf_prepare(size_t lds);                // before the first launch on a device: admits a compute unit's whole LDS
+// The increments of every grid column from the transforms of a coarse set: per column a stencil of four list entries and their
+// weights (a zero weight: the entry is not read), T = ((w0 T0 + w1 T1) + w2 T2) + w3 T3 from the first term present, then
+// dx_e = sum_f (x_f - mean) T[f][e] as the transform kernel forms it.
+struct LetkfApply {
+    int nmem, kx, ncol, nlist;
+    const int *iidx;                                 // [ncol][4] entries of the coarse list
+    const double *iwgt;                              // [ncol][4]
+    const double *tw;                                // [nlist][kx][nmem][nmem]
+    const double *x[LETKF_VARS];
+    double *dx[LETKF_VARS];                          // may be x
+};
+hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s);
 // dst[i] += src[i] for nops arrays in one launch; an increment equal to zero leaves the destination's bits (a -0.0 included)
 struct LetkfAdd {
     int nops;

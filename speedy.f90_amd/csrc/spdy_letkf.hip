@@ -1,5 +1,6 @@
 // The ensemble analysis on the device (include/spdy.h, "ensemble analysis"): the observation-space quantities, the
-// local ensemble transforms of every grid column and level, and the kernel that adds the spectral increments to the prognostics.
+// local ensemble transforms of every grid column and level -- or of a coarse list of columns, with the kernel that interpolates them
+// to every column (weight interpolation) -- and the kernel that adds the spectral increments to the prognostics.
 // The transforms around them are the plan's own (csrc/spdy_api_letkf.hip).
 //
 // Everything here is bit-reproducible: no atomics, every sum in a fixed order (observations ascending, members ascending), every
@@ -87,12 +88,17 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObs a
     a.dep[o] = a.value[o] - mean;
 }
 
+// LIST = false: one workgroup per grid column, which gets its increments.  LIST = true (weight interpolation): workgroup b solves
+// grid column cols[b] and writes T of every level to tw, [b][k][f][e] with e fastest, and no increments.  Two instantiations, no
+// run-time branch: the first form is the kernel it was before the second existed.
+template <bool LIST>
 __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const LetkfCols a)
 {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) char letkf_smem[];
     double *const sm = reinterpret_cast<double *>(letkf_smem);
-    const int E = a.nmem, ep = (E + 1) & ~1, ee = ep * ep, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, col = blockIdx.x;
+    const int E = a.nmem, ep = (E + 1) & ~1, ee = ep * ep, kx = a.kx, ncol = a.ncol, tid = threadIdx.x;
+    const int col = LIST ? a.cols[blockIdx.x] : blockIdx.x;
     const LetkfLds L(ep, kx, a.nlv);
     double *const C = sm + L.C, *const B = sm + L.B, *const ty = sm + L.ty, *const rtab = sm + L.rtab, *const td = sm + L.td,
                   *const lwh = sm + L.lwh;
@@ -264,8 +270,17 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
                     acc += (V[f * ep + i] * gf[i]) * V[e * ep + i];
                     i = i + 1 == ep ? 0 : i + 1;
                 }
-                A[el] = (acc + wbar[f]) - (f == e ? 1.0 : 0.0);
+                const double tfe = (acc + wbar[f]) - (f == e ? 1.0 : 0.0);
+                if constexpr (LIST) {
+                    if (f < E && e < E) a.tw[(((size_t)blockIdx.x * kx + k) * E + f) * E + e] = tfe;
+                } else {
+                    A[el] = tfe;
+                }
             }
+        if constexpr (LIST) {
+            __syncthreads();
+            continue;
+        }
         // the increments of u, v, t, q at this level, of ps at the lowest: dx_e = sum_f (x_f - mean) T[f][e]
         const int nvar = act ? (k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1) : 0;
         for (int x = lt; x < nvar * ep; x += tpl) {
@@ -288,6 +303,75 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
     }
 }
 
+// Weight interpolation: the increments of every grid column from the transforms of the coarse columns.  An item is one (level, grid
+// column), the column fastest; it has lpi lanes (E rounded up to a power of two), lane e forms member e's increments, so a
+// workgroup holds 256 / lpi items of neighbouring columns, which mostly share their stencil's coarse columns (L1, L2).  Per f the
+// lanes of an item read a row of T of each stencil entry, contiguous along e; the members' values go through LDS (five doubles per
+// thread, 10 KB per workgroup whatever E), loaded and stored with the column fastest over the lanes.  A streaming kernel: no
+// atomics, every bound a kernel argument, the sums in the order of letkf_transform_kernel's step 4.
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_kernel(const LetkfApply a, const int lpi)
+{
+#pragma clang fp contract(off)
+    __shared__ double X[LETKF_VARS * LETKF_BLOCK];      // [slot][v][lpi]
+    const int E = a.nmem, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, ipb = LETKF_BLOCK / lpi;
+    const long nitem = (long)kx * ncol, first = (long)blockIdx.x * ipb;
+    {   // the members' values: thread -> (member, slot), the slots' columns contiguous
+        const int slot = tid % ipb, f = tid / ipb;
+        const long item = first + slot;
+        if (item < nitem && f < E) {
+            const int k = (int)(item / ncol), col = (int)(item % ncol), nvar = k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1;
+            for (int v = 0; v < nvar; ++v) X[(slot * LETKF_VARS + v) * lpi + f] = a.x[v][letkf_at(v, f, k, kx, ncol, col)];
+        }
+    }
+    __syncthreads();
+    const int slot = tid / lpi, e = tid % lpi;
+    const long item = first + slot;
+    double d[LETKF_VARS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (item < nitem && e < E) {
+        const int k = (int)(item / ncol), col = (int)(item % ncol);
+        const bool sfc = k == kx - 1;
+        const double *const xs = X + slot * LETKF_VARS * lpi;
+        double mean[LETKF_VARS];
+        for (int v = 0; v < LETKF_VARS; ++v) {
+            double sum = 0.0;
+            for (int f = 0; f < E; ++f) sum += xs[v * lpi + f];
+            mean[v] = sum / E;
+        }
+        const double w0 = a.iwgt[4 * (size_t)col], w1 = a.iwgt[4 * (size_t)col + 1], w2 = a.iwgt[4 * (size_t)col + 2],
+                     w3 = a.iwgt[4 * (size_t)col + 3];
+        const size_t ee = (size_t)E * E, lev = (size_t)k * ee + e;
+        const double *const t0 = a.tw + (size_t)a.iidx[4 * (size_t)col] * kx * ee + lev,
+                     *const t1 = a.tw + (size_t)a.iidx[4 * (size_t)col + 1] * kx * ee + lev,
+                     *const t2 = a.tw + (size_t)a.iidx[4 * (size_t)col + 2] * kx * ee + lev,
+                     *const t3 = a.tw + (size_t)a.iidx[4 * (size_t)col + 3] * kx * ee + lev;
+#pragma unroll 4
+        for (int f = 0; f < E; ++f) {
+            const size_t r = (size_t)f * E;
+            double t = w0 * t0[r];            // (1 - a)(1 - b) with a, b < 1: the first term is always present
+            if (w1 != 0.0) t += w1 * t1[r];
+            if (w2 != 0.0) t += w2 * t2[r];
+            if (w3 != 0.0) t += w3 * t3[r];
+            for (int v = 0; v < LETKF_VARS - 1; ++v) d[v] += (xs[v * lpi + f] - mean[v]) * t;
+            if (sfc) d[4] += (xs[4 * lpi + f] - mean[4]) * t;
+        }
+    }
+    __syncthreads();
+    X[(slot * LETKF_VARS + 0) * lpi + e] = d[0];
+    X[(slot * LETKF_VARS + 1) * lpi + e] = d[1];
+    X[(slot * LETKF_VARS + 2) * lpi + e] = d[2];
+    X[(slot * LETKF_VARS + 3) * lpi + e] = d[3];
+    X[(slot * LETKF_VARS + 4) * lpi + e] = d[4];
+    __syncthreads();
+    {
+        const int slot2 = tid % ipb, f = tid / ipb;
+        const long item2 = first + slot2;
+        if (item2 < nitem && f < E) {
+            const int k = (int)(item2 / ncol), col = (int)(item2 % ncol), nvar = k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1;
+            for (int v = 0; v < nvar; ++v) a.dx[v][letkf_at(v, f, k, kx, ncol, col)] = X[(slot2 * LETKF_VARS + v) * lpi + f];
+        }
+    }
+}
+
 __global__ __launch_bounds__(LETKF_BLOCK) void spec_add_kernel(const LetkfAdd a)
 {
     const int op = blockIdx.y;
@@ -306,7 +390,10 @@ hipError_t letkf_prepare(size_t lds)
 {
     constexpr size_t whole = 160 * 1024;
     if (lds > whole) return hipErrorInvalidValue;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(letkf_transform_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole);
+    const hipError_t rc =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(letkf_transform_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole);
+    if (rc != hipSuccess) return rc;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(letkf_transform_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole);
 }
 
 hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s)
@@ -328,9 +415,28 @@ hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s)
         !a.colunit || !a.lnfsg)
         return hipErrorInvalidValue;
     if (a.nobs && (!a.ounit || !a.olns || !a.rinv || !a.y || !a.dep)) return hipErrorInvalidValue;
+    if (a.cols || a.tw || a.nlist) {
+        if (!a.cols || !a.tw || a.nlist < 1 || a.nlist > a.ncol) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(letkf_transform_kernel<true>, dim3(a.nlist), dim3(LETKF_BLOCK), lds, s, a);
+        return hipGetLastError();
+    }
     for (int v = 0; v < LETKF_VARS; ++v)
         if (!a.x[v] || !a.dx[v]) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(letkf_transform_kernel, dim3(a.ncol), dim3(LETKF_BLOCK), lds, s, a);
+    hipLaunchKernelGGL(letkf_transform_kernel<false>, dim3(a.ncol), dim3(LETKF_BLOCK), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s)
+{
+    if (a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 || a.nlist < 1 || a.nlist > a.ncol ||
+        !a.iidx || !a.iwgt || !a.tw)
+        return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!a.x[v] || !a.dx[v]) return hipErrorInvalidValue;
+    int lpi = 2;
+    while (lpi < a.nmem) lpi *= 2;
+    const long nitem = (long)a.kx * a.ncol, ipb = LETKF_BLOCK / lpi;
+    hipLaunchKernelGGL(letkf_apply_kernel, dim3((unsigned)((nitem + ipb - 1) / ipb)), dim3(LETKF_BLOCK), 0, s, a, lpi);
     return hipGetLastError();
 }
 

@@ -122,6 +122,13 @@ struct spdy_letkf {
     double *d_swgt = nullptr, *d_ounit = nullptr, *d_olns = nullptr, *d_rinv = nullptr, *d_value = nullptr;
     double *d_hx = nullptr, *d_hxmean = nullptr, *d_y = nullptr, *d_dep = nullptr;
     int *d_sidx = nullptr, *d_var = nullptr, *d_lev = nullptr;
+    // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
+    int si = 1, sj = 1;
+    std::vector<int> h_coarse, h_iidx;    // [ncoarse] grid columns, ascending; [ncol][4] entries of that list
+    std::vector<double> h_iwgt;           // [ncol][4]
+    double *d_wbase = nullptr;            // one allocation: tw | iwgt | iidx | coarse
+    double *d_tw = nullptr, *d_iwgt = nullptr;     // [ncoarse][kx][nmem][nmem]; [ncol][4]
+    int *d_iidx = nullptr, *d_coarse = nullptr;
 };
 
 namespace spdy_detail {

@@ -1176,6 +1176,12 @@ module spdy_c
             integer(c_int), value :: nobs
             integer(c_int) :: rc
         end function
+        function spdy_letkf_set_weight_stride(l, si, sj) bind(C, name="spdy_letkf_set_weight_stride") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l
+            integer(c_int), value :: si, sj
+            integer(c_int) :: rc
+        end function
         function spdy_letkf_table(l, name, buf, cap) bind(C, name="spdy_letkf_table") result(rc)
             import :: c_int, c_ptr, c_char
             type(c_ptr), value :: l, buf

@@ -3,7 +3,9 @@
 A Letkf belongs to a plan and an ensemble size.  One analysis: set_obs(...), then Ensemble.analyse(letkf) on the spectral state
 (five launches, six where the direct batch is of streaming size; in place, time level 1) or analyse_grid(...) on a gridded
 ensemble; fields() gives the observation-space quantities of that call, so observation-minus-background statistics need no
-second operator.  After an analysis the run continues
+second operator.  weight_stride=(si, sj) solves the local problems on every si-th longitude and sj-th row only and gives the
+other columns the bilinear interpolation of those columns' transforms (one launch more); (1, 1), the default, solves every column.
+After an analysis the run continues
 with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled: build the analysis ensemble from
 members the guard has not stopped, a non-finite member makes every column it touches non-finite."""
 import ctypes
@@ -15,8 +17,8 @@ from ._lib import check
 from .columns import DeviceField, _p
 
 OBS_U, OBS_V, OBS_T, OBS_Q, OBS_PS = range(5)
-LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv")
-LETKF_FIELDS = ("hx", "hxmean", "y", "departure")
+LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv", "coarse_columns", "interp_index", "interp_weight")
+LETKF_FIELDS = ("hx", "hxmean", "y", "departure", "weights")
 
 
 class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
@@ -33,9 +35,10 @@ class _DeviceView:
 
 class Letkf:
     """sigma_h: horizontal localisation scale in metres; sigma_v: vertical scale in ln sigma (<= 0: none); rho: multiplicative
-    inflation of the background covariance.  2 <= nmem <= 32; the plan needs max_batch >= nmem (2 kx + 1)."""
+    inflation of the background covariance; weight_stride: set_weight_stride.  2 <= nmem <= 32; the plan needs max_batch >= nmem
+    (2 kx + 1)."""
 
-    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0):
+    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1)):
         self.sp, self.lib = sp, sp.lib
         if sp.device >= 0:
             sp._sync_stream()
@@ -44,7 +47,10 @@ class Letkf:
         self.h, self.nmem, self.max_obs, self.nobs = h, int(nmem), int(max_obs), 0
         # the plan closes its objects first (as its surface models)
         sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
+        self.weight_stride = (1, 1)
         self.set_localization(sigma_h, sigma_v, rho)
+        if tuple(weight_stride) != (1, 1):
+            self.set_weight_stride(*weight_stride)
 
     def close(self):
         if getattr(self, "h", None):
@@ -60,6 +66,20 @@ class Letkf:
     def set_localization(self, sigma_h, sigma_v=0.0, rho=1.0):
         """read when an analysis is enqueued: a captured analysis keeps the values of its capture"""
         check(self.lib.spdy_letkf_set_localization(self.h, float(sigma_h), float(sigma_v), float(rho)))
+
+    def set_weight_stride(self, si, sj):
+        """Weight interpolation: the local problems are solved at longitudes 0, si, 2 si, ... (si divides ix, si <= ix/2) and rows 0,
+        sj, 2 sj, ... and il-1 (1 <= sj <= il-1); every other column gets the bilinear interpolation, in index space, of the
+        transforms of the four coarse columns around it.  (1, 1): every column is solved, as without this call.  Builds and uploads
+        the tables and allocates the weight buffer; synchronises the plan's stream; not inside a capture, and a graph captured
+        before the call has to be captured again."""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        rc = self.lib.spdy_letkf_set_weight_stride(self.h, int(si), int(sj))
+        if rc == -4:                  # SPDY_ERR_HIP: the object is left at stride (1, 1)
+            self.weight_stride = (1, 1)
+        check(rc)
+        self.weight_stride = (int(si), int(sj))
 
     def set_obs(self, var, lev, lon, lat, value, error):
         """The observations of the next analysis, arrays of one length (0 .. max_obs): var OBS_U .. OBS_PS, lev 0 .. kx-1 (ignored
@@ -84,19 +104,27 @@ class Letkf:
 
     def table(self, name):
         """A host table of the current observations (LETKF_TABLES): stencil_index [nobs, 4] (grid points j*ix+i, int64),
-        stencil_weight [nobs, 4], unit [nobs, 3], lnsigma [nobs], rinv [nobs]."""
+        stencil_weight [nobs, 4], unit [nobs, 3], lnsigma [nobs], rinv [nobs]; or of the weight interpolation: coarse_columns
+        [ncoarse] (grid columns j*ix+i, int64, ascending), interp_index [ncol, 4] (entries of coarse_columns, int64; an entry of
+        weight zero repeats the first), interp_weight [ncol, 4]; all three are empty at stride (1, 1)."""
         n = check(self.lib.spdy_letkf_table(self.h, name.encode(), None, 0))
         out = np.zeros(n)
         check(self.lib.spdy_letkf_table(self.h, name.encode(), _p(out), n))
-        if name == "stencil_index":
+        if name in ("stencil_index", "interp_index"):
             return out.astype(np.int64).reshape(-1, 4)
-        return out.reshape(-1, 4) if name == "stencil_weight" else out.reshape(-1, 3) if name == "unit" else out
+        if name == "coarse_columns":
+            return out.astype(np.int64)
+        return out.reshape(-1, 4) if name in ("stencil_weight", "interp_weight") else out.reshape(-1, 3) if name == "unit" else out
 
     def field(self, name):
         """A device field of the latest analysis call (LETKF_FIELDS): hx, y [nobs, nmem], hxmean, departure [nobs]; a DeviceField
-        in the object's own memory, the pointers never change."""
+        in the object's own memory, the pointers never change.  weights [ncoarse, kx, nmem, nmem]: the transforms T[f][e] of the
+        coarse columns, at a weight stride other than (1, 1) only; set_weight_stride moves it."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
+        if name == "weights":
+            ncoarse = check(self.lib.spdy_letkf_table(self.h, b"coarse_columns", None, 0))
+            return DeviceField(self.sp, p.value, (ncoarse, self.sp.kx, self.nmem, self.nmem))
         return DeviceField(self.sp, p.value, (self.nobs, self.nmem) if name in ("hx", "y") else (self.nobs,))
 
     def fields(self):
@@ -112,7 +140,7 @@ class Letkf:
     def analyse_grid(self, ug, vg, tg, qg, psg, out=None):
         """The increments (du, dv, dt, dq, dps) of a gridded ensemble: ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] float64
         device tensors; out: five tensors of those shapes to write into (they may be the inputs), by default fresh ones.
-        Two launches; capturable when `out` is given."""
+        Two launches, three at a weight stride other than (1, 1); capturable when `out` is given."""
         import torch
         sp, E = self.sp, self.nmem
         x = (ug, vg, tg, qg, psg)

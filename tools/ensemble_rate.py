@@ -35,7 +35,10 @@ unless told otherwise): graph replays of Ensemble.analyse -- five launches, six 
 observes u, v, t, q at every level and ps, 13 728 observations, sigma_h = 500 km, sigma_v = 0.1, rho = 1.1; each observation has the
 members' spread at its place as error and a value one such error around their mean.  Next to it the captured ensemble step with
 the whole physics, whose 36 replays are the model side of one six-hour cycle.  Every repeat starts from the same state; inside a
-repeat the replays analyse the state the replay before left.
+repeat the replays analyse the state the replay before left.  --stride SI SJ sets the analysis' weight stride (one launch more:
+the local problems on the coarse columns, then the kernel that interpolates their transforms to every column); the row then has
+the number of coarse columns and the byte count of that kernel's reads -- per grid column and level one E x E transform per
+stencil entry of non-zero weight, and the members' values -- to set against its time from a kernel trace.
 
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
@@ -43,6 +46,7 @@ repeat the replays analyse the state the replay before left.
     python tools/ensemble_rate.py --output --json profiles/ensemble_output_rate.json
     python tools/ensemble_rate.py --sppt --json profiles/ensemble_sppt_rate.json
     python tools/ensemble_rate.py --letkf --json profiles/ensemble_letkf_rate.json
+    python tools/ensemble_rate.py --letkf --stride 2 2
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
 import ctypes
@@ -441,7 +445,7 @@ def run_sppt(tag, members, reps, repeats, label, rows):
     sp.close()
 
 
-def run_letkf(tag, members, reps, repeats, label, rows):
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1)):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle)"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
@@ -468,7 +472,7 @@ def run_letkf(tag, members, reps, repeats, label, rows):
     cols = [np.tile(var, nloc), np.tile(lev, nloc), np.repeat(lon.ravel(), per), np.repeat(lat.ravel(), per)]
     nobs = nloc * per
     rng = np.random.default_rng(0)
-    fns, nodes, rearms, keep = {}, {}, [], []
+    fns, nodes, rearms, keep, interp = {}, {}, [], [], {}
     for E in members:
         # the members: the case's state plus a hundredth of the differences between seeded states (0.3 K in t)
         ms = ensemblestep.member_states(sp, E + 1)
@@ -477,7 +481,7 @@ def run_letkf(tag, members, reps, repeats, label, rows):
         for e in range(E):
             en.set_member(e, {n: case.st[n] + 0.01 * (ms[e + 1][n] - ms[0][n]) for n in modelstep.PROG})
         start = {n: getattr(en, n).clone() for n in modelstep.PROG}
-        lt = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1)
+        lt = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, **({} if stride == (1, 1) else {"weight_stride": stride}))
         lt.set_obs(*cols, np.zeros(nobs), np.ones(nobs))
         en.analyse(lt)                                        # a first call gives H x of every member: the values come from it
         torch.cuda.synchronize()
@@ -494,6 +498,10 @@ def run_letkf(tag, members, reps, repeats, label, rows):
         with sp.graph_capture() as g:
             en.analyse(lt)
         fns["analysis E=%d" % E], nodes["analysis E=%d" % E] = g.launch, g.num_nodes()
+        if stride != (1, 1):
+            terms = int(np.count_nonzero(lt.table("interp_weight")))
+            interp[E] = {"coarse_columns": int(lt.table("coarse_columns").size),
+                         "apply_read_bytes": 8 * (terms * kx * E * E + (4 * kx + 1) * E * sp.il * sp.ix)}
         with sp.graph_capture() as gs:
             en.step(2, 2, dt, PE, eps=modelstep.ROB)
         fns["step E=%d physics" % E], nodes["step E=%d physics" % E] = gs.launch, gs.num_nodes()
@@ -510,6 +518,7 @@ def run_letkf(tag, members, reps, repeats, label, rows):
         row = {"label": label, "size": tag, "form": name, "members": E, "observations": nobs, "nodes": nodes[name], "us": round(med, 2),
                "us_min": round(lo, 2), "us_max": round(hi, 2)}
         if name.startswith("analysis"):
+            row.update(stride=list(stride), **interp.get(E, {}))
             cycle = 36 * t["step E=%d physics" % E][0]
             row.update(us_36_steps=round(cycle, 1), analysis_share_of_cycle=round(med / (med + cycle), 4))
         rows.append(row)
@@ -528,6 +537,7 @@ def main():
     ap.add_argument("--output", action="store_true")
     ap.add_argument("--sppt", action="store_true")
     ap.add_argument("--letkf", action="store_true")
+    ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
     ap.add_argument("--reps", type=int)
@@ -548,7 +558,7 @@ def main():
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
             if a.letkf:
-                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows)
+                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride))
             elif a.sppt:
                 run_sppt(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.output:

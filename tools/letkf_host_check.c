@@ -1,5 +1,6 @@
 /* Host check of the observation ingestion (include/spdy.h, "ensemble analysis"): spdy_letkf_set_obs and spdy_letkf_table on a
- * host-only plan, fed the operator's edge cases, nobs = 0 and nobs = max_obs.  Built by `make hostcheck` in speedy.f90_amd with
+ * host-only plan, fed the operator's edge cases, nobs = 0 and nobs = max_obs; and of the tables of weight interpolation
+ * (spdy_letkf_set_weight_stride) at the smallest and largest strides and with a short last latitude interval.  Built by `make hostcheck` in speedy.f90_amd with
  * the address and undefined-behaviour sanitizers on the host code of the plan, the tables and the analysis; exits 0 when every
  * stencil is a convex combination of four grid points and every rejection is the documented code. */
 #include <math.h>
@@ -42,6 +43,30 @@ static int tables_ok(spdy_letkf *l, int nobs, int ncol)
     return 1;
 }
 
+/* the coarse list ascending and inside the grid; every stencil entry inside the list, every weight in [0, 1], their sum 1 */
+static int interp_ok(spdy_letkf *l, int si, int sj, int ix, int il)
+{
+    const int ncol = ix * il, nc = spdy_letkf_table(l, "coarse_columns", NULL, 0);
+    if (si == 1 && sj == 1)
+        return nc == 0 && spdy_letkf_table(l, "interp_index", NULL, 0) == 0 && spdy_letkf_table(l, "interp_weight", NULL, 0) == 0;
+    if (nc != (ix / si) * ((il - 2) / sj + 2)) return 0;
+    double *c = malloc(sizeof(double) * (size_t)nc), *idx = malloc(sizeof(double) * 4 * (size_t)ncol),
+           *w = malloc(sizeof(double) * 4 * (size_t)ncol);
+    int ok = spdy_letkf_table(l, "coarse_columns", c, nc) == nc && spdy_letkf_table(l, "interp_index", idx, 4 * ncol) == 4 * ncol &&
+             spdy_letkf_table(l, "interp_weight", w, 4 * ncol) == 4 * ncol && spdy_letkf_table(l, "interp_weight", w, 4 * ncol - 1) == SPDY_ERR_ARG;
+    for (int n = 0; ok && n < nc; ++n) ok = c[n] >= 0 && c[n] < ncol && (n == 0 || c[n] > c[n - 1]);
+    for (int n = 0; ok && n < ncol; ++n) {
+        double sum = 0.0;
+        for (int t = 0; t < 4; ++t) {
+            ok = ok && idx[4 * n + t] >= 0 && idx[4 * n + t] < nc && w[4 * n + t] >= 0.0 && w[4 * n + t] <= 1.0;
+            sum += w[4 * n + t];
+        }
+        ok = ok && fabs(sum - 1.0) <= 1e-15;
+    }
+    free(c); free(idx); free(w);
+    return ok;
+}
+
 int main(void)
 {
     enum { KX = 5, IX = 96, IY = 24, MAXOBS = 64 };
@@ -81,6 +106,18 @@ int main(void)
     double *d = NULL;
     CHECK(spdy_letkf_field(l, "hx", &d) == SPDY_ERR_NO_DEVICE);
     CHECK(spdy_ens_letkf_dev(l, (double *)obs, (double *)obs, (double *)obs, (double *)obs, (double *)obs) == SPDY_ERR_NO_DEVICE);
+    /* weight interpolation: the tables of every kind of stride, the rejections, back to (1, 1) */
+    static const int strides[][2] = {{1, 1}, {2, 2}, {3, 5}, {4, 47}, {1, 3}, {48, 1}, {48, 47}, {1, 1}};
+    CHECK(interp_ok(l, 1, 1, IX, 2 * IY) && spdy_letkf_field(l, "weights", &d) == SPDY_ERR_STATE);
+    for (int n = 0; n < (int)(sizeof(strides) / sizeof(strides[0])); ++n) {
+        CHECK(spdy_letkf_set_weight_stride(l, strides[n][0], strides[n][1]) == SPDY_OK);
+        CHECK(interp_ok(l, strides[n][0], strides[n][1], IX, 2 * IY));
+    }
+    CHECK(spdy_letkf_set_weight_stride(l, 3, 5) == SPDY_OK && spdy_letkf_field(l, "weights", &d) == SPDY_ERR_NO_DEVICE);
+    CHECK(spdy_letkf_set_weight_stride(NULL, 2, 2) == SPDY_ERR_ARG && spdy_letkf_set_weight_stride(l, 5, 1) == SPDY_ERR_ARG);
+    CHECK(spdy_letkf_set_weight_stride(l, 96, 1) == SPDY_ERR_ARG && spdy_letkf_set_weight_stride(l, 0, 1) == SPDY_ERR_ARG);
+    CHECK(spdy_letkf_set_weight_stride(l, 2, 0) == SPDY_ERR_ARG && spdy_letkf_set_weight_stride(l, 2, 2 * IY) == SPDY_ERR_ARG);
+    CHECK(interp_ok(l, 3, 5, IX, 2 * IY));
     CHECK(spdy_letkf_destroy(l) == SPDY_OK && spdy_plan_destroy(p) == SPDY_OK);
     printf("letkf host check ok: %d edge observations, 0 and %d observations\n", npts, (int)MAXOBS);
     return 0;
