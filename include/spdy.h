@@ -68,7 +68,10 @@ enum {
  * (model-shaped plans: a graph capture then needs no warm-up) and at the first call that needs it otherwise (allocation
  * inside an open capture is refused with SPDY_ERR_STATE).  Destroying a plan also invalidates the graphs captured
  * from it (spdy_graph_launch then returns SPDY_ERR_STATE) and shuts down its communicators (spdy_comm_*: the handles
- * stay valid for spdy_comm_destroy, every other call on them returns SPDY_ERR_STATE).                              */
+ * stay valid for spdy_comm_destroy, every other call on them returns SPDY_ERR_STATE).
+ * The same rule holds for every object made on a plan (spdy_surface_model, spdy_sppt, spdy_diagnostics, spdy_letkf): its
+ * device memory is the plan's and goes with it, the handle stays valid for its _destroy, and every other call on it returns
+ * SPDY_ERR_STATE.  A plan and what was made on it may so be destroyed in any order.                                  */
 /* Environment read by the library (measurement and debugging aids; none changes results beyond rounding-level path choices).
  * The launch-policy switches (SPDY_T30_*, SPDY_T63_*, SPDY_WT_MIN_MB) are read ONCE per plan, in spdy_plan_create; a plan's
  * values are changed afterwards with spdy_plan_set_option.
@@ -704,7 +707,7 @@ int spdy_ens_physics_dev(spdy_plan *plan, int nmem, int compute_sw, const double
  *             "f0" (1) = sqrt(stddev**2 (1 - phi**2) / (2 sum_{n=1..trunc} (2n+1) exp(-0.5 (len_decorr/rearth)**2 n(n+1)))) with
  *             stddev = 0.33 (float32, widened) and len_decorr = 500000; "sigma" (mx,nx) = f0 exp(-0.25 len_decorr**2 el2) over the
  *             whole rectangle, sigma(1,1) = f0 (the reference perturbs the global mean too), the same on every level; "mu" (kx);
- *             "first" (1) = (1 - phi**2)**(-0.5).  Destroy the pattern before its plan.
+ *             "first" (1) = (1 - phi**2)**(-0.5).  Lifetime: the plan section's rule.
  *   advance   gen_sppt() without its return copy, three launches: (1) eta is drawn, or copied from d_eta ((mx,nx,kx) complex,
  *             device; NULL = draw), and each part clipped to +-10; the counter `draws` (64 bits, in the object's DEVICE memory) is
  *             read on the device: 0 gives spec = first * sigma * eta, otherwise spec = phi * spec + sigma * eta; (2) the plan's
@@ -798,7 +801,7 @@ int spdy_ens_physics_sppt_dev(spdy_plan *plan, int nmem, spdy_sppt *s, int compu
  *             like spdy_get_table.  flags: SPDY_SURFACE_LAND_COUPLING (land_coupling_flag), SPDY_SURFACE_ICE_COUPLING
  *             (ice_coupling_flag), SPDY_SURFACE_SST_ANOMALY (sst_anomaly_coupling_flag); the reference's defaults are all
  *             three (SPDY_SURFACE_DEFAULT).  On a host-only plan create builds the tables; every device call is then
- *             SPDY_ERR_NO_DEVICE.  Destroy the model before its plan.
+ *             SPDY_ERR_NO_DEVICE.  Lifetime: the plan section's rule.
  *   set_date  imont1 (1 .. 12), tmonth and tyear as date.f90:147-151 makes them (float32 expressions, widened): the host
  *             computes the weights and months of forin5 / forint (interpolation.f90:16-69) and copies them to model memory on
  *             the plan's stream, then calls spdy_radiation_set_date(tyear).  Not callable during a capture; a captured call
@@ -871,7 +874,7 @@ int spdy_surface_model_members(const spdy_surface_model *m, const char *name);
  *             diag(kx,3); step s goes to row s mod capacity --, the four limits, and per level a state: the number of the next
  *             step (64 bits; first_step >= 0 at first), the level's first offending step with the mask of what tripped there, and
  *             the level's three numbers of the run's first offending step, outside the ring so that no wrap overwrites them.  On a
- *             host-only plan create succeeds and every device call is SPDY_ERR_NO_DEVICE.  Destroy the object before its plan.
+ *             host-only plan create succeeds and every device call is SPDY_ERR_NO_DEVICE.  Lifetime: the plan section's rule.
  *   check_dev ONE launch on three device arrays of (mx,nx,kx) complex spectra and the plan's elm2; one workgroup per level.  It
  *             allocates nothing and takes no host value that changes from step to step: a captured call records step s, s + 1, ...
  *             on successive replays, with the pointers it was captured with.  temp is one load and one multiply, bit for bit the

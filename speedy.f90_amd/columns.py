@@ -7,7 +7,6 @@ stack (ix,il,kx) is [kx, il, ix]; nb states lie back to back along a leading axi
 ColumnPhysics is a mixin of spectral.Spectral: it uses the plan's lib, h, kx, grid_shape, device, _dp and _sync_stream.
 """
 import ctypes
-import weakref
 
 import numpy as np
 
@@ -140,7 +139,33 @@ SURFACE_FIELDS = ("stlcl_ob", "snowdcl_ob", "soilwcl_ob", "stl_lm", "stl_am", "s
                   "snowc", "alb_l", "alb_s", "albsfc", "corh")
 
 
-class SurfaceModel:
+class PlanObject:
+    """What the objects made on a plan share (include/spdy.h, "plan"): the handle `h`, its release, and the two-call query of a
+    host table.  PREFIX names the C calls.  A handle outlives its plan: once the plan is closed every call but close raises
+    SpdyError (SPDY_ERR_STATE), so the objects and their plan may be closed, or collected, in any order."""
+    PREFIX = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self.PREFIX + "_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _table(self, name):
+        """the table as the flat float64 array the library returns"""
+        query = getattr(self.lib, self.PREFIX + "_table")
+        n = check(query(self.h, name.encode(), None, 0))
+        out = np.zeros(n)
+        check(query(self.h, name.encode(), _p(out), n))
+        return out
+
+
+class SurfaceModel(PlanObject):
     """The slab land, sea and ice models and the daily forcing on the device (spdy_surface_model_* in include/spdy.h).
 
     clim: dict of host arrays fmask, alb0 [il, ix]; stl12, snowd12, soilw12, sst12, sice12 [12, il, ix]; sstan3 [3, il, ix] (may
@@ -149,6 +174,7 @@ class SurfaceModel:
 
     nmem > 1: the models of an ensemble's members in one object, one launch per call.  What no kernel writes (the constants, the
     climatologies, the date) is held once; every field couple_dev or forcing_dev writes, and fmask_l, is [nmem, il, ix]."""
+    PREFIX = "spdy_surface_model"
 
     def __init__(self, sp, clim, delt, flags=SURFACE_DEFAULT, nmem=1):
         self.sp, self.lib, self.flags, self.nmem = sp, sp.lib, int(flags), int(nmem)
@@ -166,26 +192,10 @@ class SurfaceModel:
         h = ctypes.c_void_p()
         check(self.lib.spdy_ens_surface_model_create(sp.h, self.nmem, ctypes.byref(c), float(delt), self.flags, ctypes.byref(h)))
         self.h = h
-        # the plan closes its models first; the references of models that are gone are dropped here
-        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.spdy_surface_model_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def table(self, name):
         """A host table of land_model_init / sea_model_init (SURFACE_TABLES), [il, ix]."""
-        n = check(self.lib.spdy_surface_model_table(self.h, name.encode(), None, 0))
-        out = np.zeros(n)
-        check(self.lib.spdy_surface_model_table(self.h, name.encode(), _p(out), n))
-        return out.reshape(self.sp.grid_shape)
+        return self._table(name).reshape(self.sp.grid_shape)
 
     def set_date(self, imont1, tmonth, tyear):
         """The date of the interpolations and of the zonal radiation forcing (date.f90:147-151's imont1, tmonth, tyear); the
@@ -246,7 +256,7 @@ SPPT_TABLES = ("phi", "f0", "first", "sigma", "mu")
 SPPT_FIELDS = ("eta", "spec", "pattern")
 
 
-class Sppt:
+class Sppt(PlanObject):
     """The SPPT pattern on the device (spdy_sppt_* in include/spdy.h): gen_sppt of sppt.f90 with a counter-based generator.
 
     nsteps: steps per day; mu: the taper per level, kx values top down (None = all ones).  One step of a run: advance_dev(), then
@@ -255,6 +265,7 @@ class Sppt:
     nmem > 1 (or seeds given): one pattern per member of an ensemble, member-major, advanced together by the same three launches;
     seeds: one per member (default seed + e), each member drawing what a one-member object with its seed draws.  The step is then
     advance_dev() and Spectral.ens_physics_sppt_dev(nmem, self, ...): Ensemble.step does both when its physics has "sppt"."""
+    PREFIX = "spdy_sppt"
 
     def __init__(self, sp, nsteps, mu=None, seed=0, nmem=1, seeds=None):
         self.sp, self.lib = sp, sp.lib
@@ -273,26 +284,11 @@ class Sppt:
         h = ctypes.c_void_p()
         check(self.lib.spdy_ens_sppt_create(sp.h, nmem, int(nsteps), None if mu is None else _p(mu), _p(seeds), ctypes.byref(h)))
         self.h, self.nmem = h, nmem
-        # the plan closes its objects first (as its surface models)
-        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.spdy_sppt_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def table(self, name):
         """A host table (SPPT_TABLES): phi, f0, first as floats, sigma [nx, mx], mu [kx]."""
-        n = check(self.lib.spdy_sppt_table(self.h, name.encode(), None, 0))
-        out = np.zeros(n)
-        check(self.lib.spdy_sppt_table(self.h, name.encode(), _p(out), n))
-        return float(out[0]) if n == 1 and name != "mu" else out.reshape((self.sp.nx, self.sp.mx)) if name == "sigma" else out
+        out = self._table(name)
+        return float(out[0]) if out.size == 1 and name != "mu" else out.reshape((self.sp.nx, self.sp.mx)) if name == "sigma" else out
 
     def members(self):
         """the number of patterns the object holds"""
@@ -346,7 +342,7 @@ class DiagnosticsStop(RuntimeError):
         self.status = status
 
 
-class Diagnostics:
+class Diagnostics(PlanObject):
     """check_diagnostics on the device (spdy_diagnostics_* in include/spdy.h): per level reke, deke and temp of each checked step
     in a ring of `capacity` rows, the step counter and the sticky first offence, all in device memory.
 
@@ -355,6 +351,7 @@ class Diagnostics:
 
     nmem > 1: the guard of an ensemble's members in one object and one launch.  Every member has its own rows, counter and sticky
     first offence; the limits are shared.  status and read then take the member."""
+    PREFIX = "spdy_diagnostics"
 
     def __init__(self, sp, capacity=64, first_step=0, nmem=1):
         self.sp, self.lib, self.capacity, self.nmem = sp, sp.lib, int(capacity), int(nmem)
@@ -363,19 +360,6 @@ class Diagnostics:
         h = ctypes.c_void_p()
         check(self.lib.spdy_ens_diagnostics_create(sp.h, self.nmem, self.capacity, int(first_step), ctypes.byref(h)))
         self.h = h
-        # the plan closes its objects first (as its surface models)
-        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.spdy_diagnostics_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_limits(self, limits=None):
         """reke, deke, temp low, temp high (None = the reference's 500, 500, 180, 320).  Stream-ordered; not during a capture."""

@@ -45,6 +45,53 @@ int dev_alloc(spdy_plan *p, size_t bytes, void **out)
     return SPDY_OK;
 }
 
+int dev_release(spdy_plan *p, void *ptr)
+{
+    if (!ptr) return SPDY_OK;
+    NEED_DEVICE(p);
+    const auto it = std::find(p->allocs.begin(), p->allocs.end(), ptr);
+    if (it == p->allocs.end()) return fail(SPDY_ERR_ARG, "spdy_dev_free: not a live spdy_dev_alloc buffer of this plan");
+    RC(sync(p));               // work queued on the plan's stream may still use it
+    p->allocs.erase(it);
+    HIP_TRY(hipFree(ptr));
+    return SPDY_OK;
+}
+
+void retire(PlanObject *o, std::initializer_list<void *> buffers)
+{
+    spdy_plan *p = o->plan;
+    if (!p) return;
+    p->objects.erase(std::find(p->objects.begin(), p->objects.end(), o));
+    for (void *b : buffers) (void)dev_release(p, b);
+    o->plan = nullptr;
+}
+
+int ensure_workspace(spdy_plan *p, Workspace *w, size_t doubles, const char *what, bool with_four)
+{
+    NEED_DEVICE(p);
+    if (w->g && w->doubles >= doubles) return SPDY_OK;
+    NOT_CAPTURING(p, what);
+    if (with_four) RC(ensure_four(p));
+    double *g;
+    RC(dev_alloc(p, doubles * sizeof(double), &g));
+    *w = {g, doubles};
+    return SPDY_OK;
+}
+
+int upload_sync(spdy_plan *p, void *dst, const void *src, size_t bytes)
+{
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
+int download_sync(spdy_plan *p, void *dst, const void *src, size_t bytes)
+{
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
 }  // namespace spdy_detail
 
 namespace {
@@ -819,6 +866,10 @@ int spdy_plan_destroy(spdy_plan *p)
         // communicators enqueue on this plan's stream and read its dimensions: they are shut down with it (the handles stay
         // valid for spdy_comm_destroy; every other call on them returns SPDY_ERR_STATE)
         release_comms(p);
+    }
+    // objects made on this plan keep their handles, dead: their memory is among the plan's allocations
+    for (PlanObject *o : p->objects) { o->plan = nullptr; o->forget_device(); }
+    if (p->device >= 0) {
         for (void *a : p->allocs) (void)hipFree(a);
         for (double *h : p->hstage) if (h) (void)hipHostFree(h);
         if (p->h_stamp) (void)hipHostFree(p->h_stamp);
@@ -872,14 +923,7 @@ int spdy_dev_free(spdy_plan *p, void *d_ptr)
     if (!d_ptr) return SPDY_OK;
     NEED_DEVICE(p);
     NOT_CAPTURING(p, "spdy_dev_free");
-    for (auto it = p->allocs.begin(); it != p->allocs.end(); ++it)
-        if (*it == d_ptr) {
-            RC(sync(p));               // work queued on the plan's stream may still use it
-            p->allocs.erase(it);
-            HIP_TRY(hipFree(d_ptr));
-            return SPDY_OK;
-        }
-    return fail(SPDY_ERR_ARG, "spdy_dev_free: not a live spdy_dev_alloc buffer of this plan");
+    return dev_release(p, d_ptr);
 }
 
 int spdy_dev_upload(spdy_plan *p, void *d_dst, const void *src, size_t bytes)

@@ -11,11 +11,6 @@
 using namespace spdy_detail;
 
 namespace {
-#define NEED_DIAG(d)                                                        \
-    do {                                                                    \
-        if (!(d)) return fail(SPDY_ERR_ARG, "null diagnostics object");     \
-    } while (0)
-
 constexpr int MAX_CAPACITY = 1 << 20;
 
 size_t row_doubles(const spdy_diagnostics *d) { return (size_t)3 * d->plan->tab.kx; }           // one member's (3, kx) block
@@ -29,8 +24,7 @@ int restart(spdy_diagnostics *d, long long next_step)
     l.next_step = next_step; l.bad_step = -1; l.row_step = -1;
     const std::vector<spdy::DiagLevel> h(levels(d), l);
     HIP_TRY(hipMemsetAsync(d->d_history, 0, (size_t)d->capacity * d->nmem * row_doubles(d) * sizeof(double), p->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_state, h.data(), h.size() * sizeof(l), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    RC(upload_sync(p, d->d_state, h.data(), h.size() * sizeof(l)));
     d->start_step = next_step;
     return SPDY_OK;
 }
@@ -38,18 +32,13 @@ int restart(spdy_diagnostics *d, long long next_step)
 int upload_limits(spdy_diagnostics *d, const double *limits)
 {
     static const double stock[4] = {500.0, 500.0, 180.0, 320.0};             // diagnostics.f90:61-62
-    spdy_plan *p = d->plan;
-    HIP_TRY(hipMemcpyAsync(d->d_limits, limits ? limits : stock, sizeof(stock), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return SPDY_OK;
+    return upload_sync(d->plan, d->d_limits, limits ? limits : stock, sizeof(stock));
 }
 
 int download_state(spdy_diagnostics *d, std::vector<spdy::DiagLevel> &h)
 {
-    spdy_plan *p = d->plan;
     h.resize(levels(d));
-    HIP_TRY(hipMemcpyAsync(h.data(), d->d_state, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    RC(download_sync(d->plan, h.data(), d->d_state, h.size() * sizeof(h[0])));
     for (const auto &l : h)
         if (l.next_step != h[0].next_step) return fail(SPDY_ERR_STATE, "the levels' step counters disagree (%lld, %lld)", h[0].next_step, l.next_step);
     return SPDY_OK;
@@ -103,15 +92,15 @@ int spdy_ens_diagnostics_create(spdy_plan *p, int nmem, int capacity, long long 
     if (first_step < 0) return fail(SPDY_ERR_ARG, "diagnostics_create: first_step %lld is negative", first_step);
     NOT_CAPTURING(p, "spdy_diagnostics_create (allocation + upload)");
     spdy_diagnostics *d = new spdy_diagnostics;
-    d->plan = p; d->capacity = capacity; d->nmem = nmem; d->start_step = first_step;
+    adopt(p, d);
+    d->capacity = capacity; d->nmem = nmem; d->start_step = first_step;
     *out = d;
     if (p->device < 0) return SPDY_OK;
     auto cleanup = [&](int rc) { spdy_diagnostics_destroy(d); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
     const size_t nhist = (size_t)capacity * nmem * row_doubles(d);
     const size_t bytes = (nhist + 4) * sizeof(double) + levels(d) * sizeof(spdy::DiagLevel);
-    if (hipMalloc(reinterpret_cast<void **>(&d->d_history), bytes) != hipSuccess)
-        return cleanup(fail(SPDY_ERR_HIP, "diagnostics_create: hipMalloc of %zu bytes failed", bytes));
+    if (int rc = dev_alloc(p, bytes, &d->d_history)) return cleanup(rc);
     d->d_limits = d->d_history + nhist;
     d->d_state = reinterpret_cast<spdy::DiagLevel *>(d->d_limits + 4);
     int rc = upload_limits(d, nullptr);
@@ -122,18 +111,14 @@ int spdy_ens_diagnostics_create(spdy_plan *p, int nmem, int capacity, long long 
 int spdy_diagnostics_destroy(spdy_diagnostics *d)
 {
     if (!d) return SPDY_OK;
-    if (d->d_history) {
-        (void)hipSetDevice(d->plan->device);
-        (void)hipStreamSynchronize(d->plan->stream);
-        (void)hipFree(d->d_history);
-    }
+    retire(d, {d->d_history});
     delete d;
     return SPDY_OK;
 }
 
 int spdy_diagnostics_set_limits(spdy_diagnostics *d, const double *limits)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     spdy_plan *p = d->plan;
     NOT_CAPTURING(p, "spdy_diagnostics_set_limits (upload)");
     NEED_DEVICE(p);
@@ -142,7 +127,7 @@ int spdy_diagnostics_set_limits(spdy_diagnostics *d, const double *limits)
 
 int spdy_diagnostics_reset(spdy_diagnostics *d, long long next_step)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     if (next_step < 0) return fail(SPDY_ERR_ARG, "diagnostics_reset: next_step %lld is negative", next_step);
     spdy_plan *p = d->plan;
     NOT_CAPTURING(p, "spdy_diagnostics_reset (upload)");
@@ -152,7 +137,7 @@ int spdy_diagnostics_reset(spdy_diagnostics *d, long long next_step)
 
 int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const double *div, const double *t)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     if (!vor || !div || !t) return fail(SPDY_ERR_ARG, "diagnostics_check_dev: null spectra");
     spdy_plan *p = d->plan;
     NEED_DEVICE(p);
@@ -166,7 +151,7 @@ int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const dou
 
 int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask, double *bad_row)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     RC(need_single(d, "diagnostics_status", "spdy_ens_diagnostics_status"));
     return spdy_ens_diagnostics_status(d, 0, next_step, bad_step, bad_level, bad_mask, bad_row);
 }
@@ -174,7 +159,7 @@ int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long
 int spdy_ens_diagnostics_status(spdy_diagnostics *d, int member, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask,
                                 double *bad_row)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     RC(need_member(d, member, "diagnostics_status"));
     spdy_plan *p = d->plan;
     NOT_CAPTURING(p, "spdy_diagnostics_status (download)");
@@ -203,14 +188,14 @@ int spdy_ens_diagnostics_status(spdy_diagnostics *d, int member, long long *next
 
 int spdy_diagnostics_read(spdy_diagnostics *d, long long step, int count, double *rows)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     RC(need_single(d, "diagnostics_read", "spdy_ens_diagnostics_read"));
     return spdy_ens_diagnostics_read(d, 0, step, count, rows);
 }
 
 int spdy_ens_diagnostics_read(spdy_diagnostics *d, int member, long long step, int count, double *rows)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     RC(need_member(d, member, "diagnostics_read"));
     if (!rows) return fail(SPDY_ERR_ARG, "null result pointer");
     if (count < 1) return fail(SPDY_ERR_ARG, "diagnostics_read: count %d", count);
@@ -232,7 +217,7 @@ int spdy_ens_diagnostics_read(spdy_diagnostics *d, int member, long long step, i
 
 int spdy_ens_diagnostics_stopped(spdy_diagnostics *d, long long *bad_step)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     if (!bad_step) return fail(SPDY_ERR_ARG, "null result pointer");
     spdy_plan *p = d->plan;
     NOT_CAPTURING(p, "spdy_ens_diagnostics_stopped (download)");
@@ -249,7 +234,7 @@ int spdy_ens_diagnostics_stopped(spdy_diagnostics *d, long long *bad_step)
 
 int spdy_diagnostics_field(spdy_diagnostics *d, const char *name, void **d_ptr)
 {
-    NEED_DIAG(d);
+    NEED_LIVE(d, "diagnostics object");
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
     const int which = !std::strcmp(name, "history") ? 0 : !std::strcmp(name, "state") ? 1 : !std::strcmp(name, "limits") ? 2 : -1;
     if (which < 0) return fail(SPDY_ERR_ARG, "unknown diagnostics field '%s'", name);

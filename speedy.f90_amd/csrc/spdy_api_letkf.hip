@@ -10,11 +10,6 @@
 using namespace spdy_detail;
 
 namespace {
-#define NEED_LETKF(l)                                                   \
-    do {                                                                \
-        if (!(l)) return fail(SPDY_ERR_ARG, "null analysis object");    \
-    } while (0)
-
 constexpr double kPi = 3.14159265358979323846;
 constexpr size_t kLdsLimit = 160 * 1024;      // LDS of a gfx950 compute unit
 
@@ -60,7 +55,7 @@ int upload(spdy_plan *p, void *dst, const void *src, size_t bytes)
 // the argument checks the two analysis calls share, in the documented order; the device last
 int analysis_ready(spdy_letkf *l, bool ptrs_ok)
 {
-    NEED_LETKF(l);
+    NEED_LIVE(l, "analysis object");
     if (!l->loc_set) return fail(SPDY_ERR_STATE, "letkf: spdy_letkf_set_localization first");
     if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
     NEED_DEVICE(l->plan);
@@ -135,11 +130,7 @@ void interp_tables(int ix, int il, int si, int sj, std::vector<int> &coarse, std
 
 void drop_interp(spdy_letkf *l)
 {
-    if (l->d_wbase) {
-        (void)hipSetDevice(l->plan->device);
-        (void)hipStreamSynchronize(l->plan->stream);
-        (void)hipFree(l->d_wbase);
-    }
+    (void)dev_release(l->plan, l->d_wbase);
     l->d_wbase = l->d_tw = l->d_iwgt = nullptr;
     l->d_iidx = l->d_coarse = nullptr;
     l->si = l->sj = 1;
@@ -169,7 +160,8 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     if (!t.sigma_ready) return fail(SPDY_ERR_STATE, "letkf_create needs sigma levels");
     NOT_CAPTURING(p, "spdy_letkf_create (allocation + upload)");
     spdy_letkf *l = new spdy_letkf;
-    l->plan = p; l->nmem = nmem; l->max_obs = max_obs; l->nlv = nlv; l->lds = spdy::letkf_lds_bytes(nmem, kx, nlv);
+    adopt(p, l);
+    l->nmem = nmem; l->max_obs = max_obs; l->nlv = nlv; l->lds = spdy::letkf_lds_bytes(nmem, kx, nlv);
     // geometry.f90:70-75: sia(j) = -sia_half(j), sia(il+1-j) = sia_half(j), radang = asin(sia); in degrees, south first
     l->lat.resize(il);
     for (int j = 0; j < il; ++j) {
@@ -185,8 +177,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     const size_t ncol = grid_elems(p), nf = (size_t)(4 * kx + 1) * nmem, M = (size_t)(max_obs > 0 ? max_obs : 1), E = (size_t)nmem;
     // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | value | hx | hxmean | y | dep ; then the ints
     const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 2 * E), ni = 6 * M;
-    if (hipMalloc(reinterpret_cast<void **>(&l->d_base), nd * sizeof(double) + ni * sizeof(int)) != hipSuccess)
-        return cleanup(fail(SPDY_ERR_HIP, "letkf_create: hipMalloc of %zu bytes failed", nd * sizeof(double) + ni * sizeof(int)));
+    if (int rc = dev_alloc(p, nd * sizeof(double) + ni * sizeof(int), &l->d_base)) return cleanup(rc);
     double *d = l->d_base;
     l->d_grid = d; d += nf * ncol;
     l->d_spec = d; d += nf * spec_elems(p);
@@ -234,19 +225,14 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
 int spdy_letkf_destroy(spdy_letkf *l)
 {
     if (!l) return SPDY_OK;
-    drop_interp(l);
-    if (l->d_base) {
-        (void)hipSetDevice(l->plan->device);
-        (void)hipStreamSynchronize(l->plan->stream);
-        (void)hipFree(l->d_base);
-    }
+    retire(l, {l->d_wbase, l->d_base});
     delete l;
     return SPDY_OK;
 }
 
 int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h, double sigma_v, double rho)
 {
-    NEED_LETKF(l);
+    NEED_LIVE(l, "analysis object");
     if (!(sigma_h > 0.0) || !std::isfinite(sigma_h)) return fail(SPDY_ERR_ARG, "letkf: sigma_h must be finite and > 0");
     if (!std::isfinite(sigma_v)) return fail(SPDY_ERR_ARG, "letkf: sigma_v must be finite (<= 0: no vertical localisation)");
     if (!(rho > 0.0) || !std::isfinite(rho)) return fail(SPDY_ERR_ARG, "letkf: rho must be finite and > 0");
@@ -256,7 +242,7 @@ int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h, double sigma_v, d
 
 int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
 {
-    NEED_LETKF(l);
+    NEED_LIVE(l, "analysis object");
     if (nobs < 0 || nobs > l->max_obs) return fail(SPDY_ERR_ARG, "letkf_set_obs: nobs=%d outside [0, max_obs=%d]", nobs, l->max_obs);
     if (nobs && !host) return fail(SPDY_ERR_ARG, "null observations");
     spdy_plan *p = l->plan;
@@ -316,7 +302,7 @@ int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
 
 int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
 {
-    NEED_LETKF(l);
+    NEED_LIVE(l, "analysis object");
     spdy_plan *p = l->plan;
     const int ix = p->tab.ix, il = p->tab.il, kx = p->tab.kx;
     if (si < 1 || si > ix / 2 || ix % si) return fail(SPDY_ERR_ARG, "letkf_set_weight_stride: si=%d must divide ix=%d and lie in [1, %d]", si, ix, ix / 2);
@@ -331,10 +317,7 @@ int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
         HIP_TRY(hipSetDevice(p->device));
         const size_t nc = coarse.size(), ncol = grid_elems(p), ntw = nc * kx * l->nmem * l->nmem;
         const size_t bytes = (ntw + 4 * ncol) * sizeof(double) + (4 * ncol + nc) * sizeof(int);
-        if (hipMalloc(reinterpret_cast<void **>(&l->d_wbase), bytes) != hipSuccess) {
-            l->d_wbase = nullptr;
-            return fail(SPDY_ERR_HIP, "letkf_set_weight_stride: hipMalloc of %zu bytes failed", bytes);
-        }
+        RC(dev_alloc(p, bytes, &l->d_wbase));
         l->d_tw = l->d_wbase;
         l->d_iwgt = l->d_tw + ntw;
         l->d_iidx = reinterpret_cast<int *>(l->d_iwgt + 4 * ncol);
@@ -359,7 +342,7 @@ int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
 
 int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap)
 {
-    NEED_LETKF(l);
+    NEED_LIVE(l, "analysis object");
     if (!name) return fail(SPDY_ERR_ARG, "null table name");
     const std::vector<int> *index = !std::strcmp(name, "stencil_index") ? &l->h_sidx : !std::strcmp(name, "coarse_columns") ? &l->h_coarse
                                     : !std::strcmp(name, "interp_index") ? &l->h_iidx : nullptr;
@@ -378,7 +361,7 @@ int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap
 
 int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
 {
-    NEED_LETKF(l);
+    NEED_LIVE(l, "analysis object");
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
     double *const *f = !std::strcmp(name, "hx") ? &l->d_hx : !std::strcmp(name, "hxmean") ? &l->d_hxmean
                        : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep

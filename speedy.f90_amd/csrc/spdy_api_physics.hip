@@ -211,17 +211,11 @@ int column_chain(spdy_plan *p, bool fused, int nb, int compute_sw, const double 
     return SPDY_OK;
 }
 
-int sppt_workspace(spdy_plan *p, double **ws, size_t states, const char *scheme, const char *what)
+int sppt_workspace(spdy_plan *p, Workspace *w, size_t states, const char *scheme, const char *what)
 {
     NEED_PLAN(p);
     RC(check_kx(p, scheme));
-    NEED_DEVICE(p);
-    if (*ws) return SPDY_OK;
-    NOT_CAPTURING(p, what);
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(2 * p->tab.kx + 2) * grid_elems(p) * states * sizeof(double), &ptr));
-    *ws = static_cast<double *>(ptr);
-    return SPDY_OK;
+    return ensure_workspace(p, w, (size_t)(2 * p->tab.kx + 2) * grid_elems(p) * states, what);
 }
 
 // ---- the physics of nmem states from their spectra: one body for spdy_physics_dev, spdy_ens_physics_dev and their SPPT forms ----
@@ -255,29 +249,23 @@ int physics_args(const spdy_plan *p, int nmem, bool ens, const FromSpectra &a, b
                     (!a.compute_sw || a.albsfc) && a.rad_state && a.utend && a.vtend && a.ttend && a.qtend;
     if (ens) RC(physics_members(p, nmem, true));
     RC(column_args(p, ens ? "ens_physics" : "physics", nmem, true, ok, true));
+    if (sppt) NEED_LIVE(sppt, "SPPT pattern");
     if (sppt && sppt->plan != p) return fail(SPDY_ERR_ARG, "the SPPT pattern belongs to another plan");
     if (sppt && sppt->nmem != nmem) return fail(SPDY_ERR_ARG, "the SPPT object holds %d patterns, the call has %d states", sppt->nmem, nmem);
     return ens ? SPDY_OK : physics_members(p, 1, false);
 }
 
-// the workspace w (spdy_plan::PhysicsGrids) for at least nmem states; the plan and kx are checked
-int physics_grids(spdy_plan *p, spdy_plan::PhysicsGrids *w, int nmem, const char *what)
+// the workspace w for at least nmem states; the plan and kx are checked.  With the Fourier workspace: the operator route of the
+// T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
+int physics_grids(spdy_plan *p, Workspace *w, int nmem, const char *what)
 {
-    NEED_DEVICE(p);
-    if (w->nmem >= nmem) return SPDY_OK;
-    NOT_CAPTURING(p, what);
-    RC(ensure_four(p));   // the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
-    // a smaller earlier workspace stays with the plan until it is destroyed: a captured graph may still point into it
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * nmem * sizeof(double), &ptr));
-    *w = {static_cast<double *>(ptr), nmem};
-    return SPDY_OK;
+    return ensure_workspace(p, w, (size_t)(8 * p->tab.kx + 13) * grid_elems(p) * nmem, what, true);
 }
 
 // physics.f90:94-205 for nmem states, arguments checked and w allocated: ONE inverse launch of time level 1 -- nmem kx (vor, div)
 // pairs through uvspec with kcos 2; t, q, phi (nmem kx each) and ps (nmem) with kcos 1 (physics.f90:94-104) -- into w's grids, nmem
 // states back to back at state stride kx, then the chain with nb = nmem on w's chain workspace.
-int physics_from_spectra(spdy_plan *p, int nmem, const spdy_plan::PhysicsGrids &w, const SpptUse *sppt, const FromSpectra &a)
+int physics_from_spectra(spdy_plan *p, int nmem, const Workspace &w, const SpptUse *sppt, const FromSpectra &a)
 {
     const int kx = p->tab.kx, nk = nmem * kx;
     const size_t g1 = grid_elems(p) * nmem, L = (size_t)kx * g1;
@@ -303,13 +291,9 @@ int spdy_moist_columns_dev(spdy_plan *p, int nb, const double *tg, const double 
 
 int spdy_moist_workspace(spdy_plan *p)
 {
-    NEED_DEVICE(p);
-    if (p->moist_grid) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the moist-physics workspace (call spdy_moist_workspace before the capture)");
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(3 * p->tab.kx + 1) * grid_elems(p) * sizeof(double), &ptr));
-    p->moist_grid = static_cast<double *>(ptr);
-    return SPDY_OK;
+    NEED_PLAN(p);
+    return ensure_workspace(p, &p->moist_grid, (size_t)(3 * p->tab.kx + 1) * grid_elems(p),
+                            "allocating the moist-physics workspace (call spdy_moist_workspace before the capture)");
 }
 
 int spdy_moist_physics_dev(spdy_plan *p, const double *t, const double *q, const double *phi, const double *ps, double *ttend,
@@ -322,9 +306,9 @@ int spdy_moist_physics_dev(spdy_plan *p, const double *t, const double *q, const
     RC(spdy_moist_workspace(p));
     // physics.f90:102-107 for the fields the block reads: ONE inverse launch of t, q, phi (kx levels each) and ps, kcos 1
     const spdy_spec_seg segs[4] = {{kx, t}, {kx, q}, {kx, phi}, {1, ps}};
-    RC(inverse_plain_one(p, 4, segs, p->moist_grid));
+    RC(inverse_plain_one(p, 4, segs, p->moist_grid.g));
     const size_t L = (size_t)kx * grid_elems(p);
-    const double *g = p->moist_grid;
+    const double *g = p->moist_grid.g;
     KERNEL(spdy::launch_moist_columns(moist_cols(p, 1, g, g + L, g + 2 * L, g + 3 * L, ttend, qtend, out), p->stream));
     return SPDY_OK;
 }
@@ -340,19 +324,13 @@ int spdy_radiation_set_date(spdy_plan *p, double tyear)
     HIP_TRY(hipSetDevice(p->device));
     const HostTables &t = p->tab;
     const size_t n = (size_t)5 * t.il;
-    if (!p->d_radzonal) {
-        void *ptr;
-        RC(dev_alloc(p, n * sizeof(double), &ptr));
-        p->d_radzonal = static_cast<double *>(ptr);
-    }
+    if (!p->d_radzonal) RC(dev_alloc(p, n * sizeof(double), &p->d_radzonal));
     // stream-ordered: work enqueued (or a graph replayed) before this call still reads the previous date, work after it the
     // new one.  The synchronisation keeps the host staging vector alive until the copy is done.
     std::vector<double> h(n);
     const std::vector<double> *f[5] = {&t.fsol, &t.ozone, &t.ozupp, &t.zenit, &t.stratz};
     for (int i = 0; i < 5; ++i) std::memcpy(h.data() + (size_t)i * t.il, f[i]->data(), sizeof(double) * t.il);
-    HIP_TRY(hipMemcpyAsync(p->d_radzonal, h.data(), n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return SPDY_OK;
+    return upload_sync(p, p->d_radzonal, h.data(), n * sizeof(double));
 }
 
 int spdy_radiation_state_size(const spdy_plan *p)
@@ -401,19 +379,13 @@ int spdy_surface_set_orography(spdy_plan *p, const double *phis0)
     HIP_TRY(hipSetDevice(p->device));
     const HostTables &t = p->tab;
     const size_t ncol = (size_t)t.ix * t.il, n = 2 * ncol + t.il;
-    if (!p->d_orog) {
-        void *ptr;
-        RC(dev_alloc(p, n * sizeof(double), &ptr));
-        p->d_orog = static_cast<double *>(ptr);
-    }
+    if (!p->d_orog) RC(dev_alloc(p, n * sizeof(double), &p->d_orog));
     // stream-ordered like spdy_radiation_set_date's fields; sqrt(coa(j)) per latitude, coa symmetric (geometry.f90:68-73)
     std::vector<double> h(n);
     std::memcpy(h.data(), t.phis0.data(), sizeof(double) * ncol);
     std::memcpy(h.data() + ncol, t.forog.data(), sizeof(double) * ncol);
     for (int j = 0; j < t.il; ++j) h[2 * ncol + j] = std::sqrt(t.coa_half[j < t.iy ? j : t.il - 1 - j]);
-    HIP_TRY(hipMemcpyAsync(p->d_orog, h.data(), n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return SPDY_OK;
+    return upload_sync(p, p->d_orog, h.data(), n * sizeof(double));
 }
 
 int spdy_surface_fluxes_dev(spdy_plan *p, int nb, const double *ug, const double *vg, const double *tg, const double *qg,
@@ -443,13 +415,8 @@ int spdy_column_physics_workspace(spdy_plan *p)
 {
     NEED_PLAN(p);
     RC(check_kx(p, "column physics"));
-    NEED_DEVICE(p);
-    if (p->physics_ws) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the column-physics workspace (call spdy_column_physics_workspace before the capture)");
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(3 * p->tab.kx + 12) * grid_elems(p) * p->max_batch * sizeof(double), &ptr));
-    p->physics_ws = static_cast<double *>(ptr);
-    return SPDY_OK;
+    return ensure_workspace(p, &p->physics_ws, (size_t)(3 * p->tab.kx + 12) * grid_elems(p) * p->max_batch,
+                            "allocating the column-physics workspace (call spdy_column_physics_workspace before the capture)");
 }
 
 int spdy_column_physics_dev(spdy_plan *p, int nb, int compute_sw, const double *ug, const double *vg, const double *tg,
@@ -464,7 +431,7 @@ int spdy_column_physics_dev(spdy_plan *p, int nb, int compute_sw, const double *
     RC(spdy_column_physics_workspace(p));
     // the workspace fields are each max_batch states long, so that a field's place does not depend on nb
     return column_chain(p, p->physics_fused == 1, nb, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend,
-                        ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch);
+                        ttend, qtend, out, p->physics_ws.g, grid_elems(p) * p->max_batch);
 }
 
 int spdy_column_physics_sppt_workspace(spdy_plan *p)
@@ -484,9 +451,9 @@ int spdy_column_physics_sppt_dev(spdy_plan *p, int nb, const double *d_pattern, 
     RC(column_args(p, "column physics", nb, true, !nb || ok, true));
     NEED_DEVICE(p);
     RC(spdy_column_physics_sppt_workspace(p));
-    const SpptUse use{d_pattern, mu, p->sppt_ws};
+    const SpptUse use{d_pattern, mu, p->sppt_ws.g};
     return column_chain(p, p->physics_fused == 1, nb, compute_sw, ug, vg, tg, qg, phig, pslg, bnd, albsfc, rad_state, utend, vtend,
-                        ttend, qtend, out, p->physics_ws, grid_elems(p) * p->max_batch, &use);
+                        ttend, qtend, out, p->physics_ws.g, grid_elems(p) * p->max_batch, &use);
 }
 
 /* ---------------------------------------------------------------- the physics from spectra (physics.f90:94-205): one state, nmem members, each with SPPT */
@@ -539,21 +506,15 @@ int spdy_physics_sppt_dev(spdy_plan *p, spdy_sppt *sp, int compute_sw, const dou
     const FromSpectra a{compute_sw, vor, div, t, q, phi, ps, bnd, albsfc, rad_state, utend, vtend, ttend, qtend, out};
     RC(physics_args(p, 1, false, a, true, sp));
     RC(spdy_physics_sppt_workspace(p));
-    const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->sppt_grid};   // the pattern the last spdy_sppt_advance_dev left
+    const SpptUse use{sp->d_pattern, sp->tab.mu.data(), p->sppt_grid.g};   // the pattern the last spdy_sppt_advance_dev left
     return physics_from_spectra(p, 1, p->physics_grid, &use, a);
 }
 
 int spdy_ens_physics_sppt_workspace(spdy_plan *p, int nmem)
 {
     RC(spdy_ens_physics_workspace(p, nmem));
-    spdy_plan::SpptGrids *w = &p->ens_sppt_grid;
-    if (w->nmem >= nmem) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the ensemble SPPT workspace (call spdy_ens_physics_sppt_workspace before the capture)");
-    // like the physics workspace, a smaller earlier one stays with the plan: a captured graph may still point into it
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(2 * p->tab.kx + 2) * grid_elems(p) * nmem * sizeof(double), &ptr));
-    *w = {static_cast<double *>(ptr), nmem};
-    return SPDY_OK;
+    return sppt_workspace(p, &p->ens_sppt_grid, nmem, "ens_physics",
+                          "allocating the ensemble SPPT workspace (call spdy_ens_physics_sppt_workspace before the capture)");
 }
 
 int spdy_ens_physics_sppt_dev(spdy_plan *p, int nmem, spdy_sppt *sp, int compute_sw, const double *vor, const double *div,

@@ -638,10 +638,8 @@ int spdy_sharded_step_workspace(spdy_comm *c)
     const int kx = p->tab.kx;
     const size_t P = (size_t)3 * s.nl;
     auto alloc0 = [&](double **dst, size_t n) -> int {         // zero-filled plan-owned device memory
-        void *ptr;
-        RC(dev_alloc(p, std::max<size_t>(n, 2) * sizeof(double), &ptr));
-        HIP_TRY(hipMemsetAsync(ptr, 0, std::max<size_t>(n, 2) * sizeof(double), p->stream));
-        *dst = static_cast<double *>(ptr);
+        RC(dev_alloc(p, std::max<size_t>(n, 2) * sizeof(double), dst));
+        HIP_TRY(hipMemsetAsync(*dst, 0, std::max<size_t>(n, 2) * sizeof(double), p->stream));
         return SPDY_OK;
     };
     if (!c->T) {

@@ -9,23 +9,15 @@
 using namespace spdy_detail;
 
 namespace {
-#define NEED_SPPT(s)                                                    \
-    do {                                                                \
-        if (!(s)) return fail(SPDY_ERR_ARG, "null SPPT pattern");       \
-    } while (0)
-
 size_t coefs(const spdy_plan *p) { return (size_t)p->tab.mx * p->tab.nx * p->tab.kx; }
 
 // the counters and the seeds of members [first, first + n), stream-ordered as spdy_radiation_set_date's fields; a pattern is zero
 // until its first advance
 int restart(spdy_sppt *s, int first, int n, const unsigned long long *seeds)
 {
-    spdy_plan *p = s->plan;
     std::vector<spdy::SpptState> h((size_t)n);
     for (int e = 0; e < n; ++e) h[e] = spdy::SpptState{0ull, seeds[e]};
-    HIP_TRY(hipMemcpyAsync(s->d_state + first, h.data(), sizeof(spdy::SpptState) * (size_t)n, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return SPDY_OK;
+    return upload_sync(s->plan, s->d_state + first, h.data(), sizeof(spdy::SpptState) * (size_t)n);
 }
 
 int need_member(const spdy_sppt *s, int member)
@@ -44,21 +36,21 @@ int spdy_ens_sppt_create(spdy_plan *p, int nmem, int nsteps, const double *mu, c
     if (!seeds || !out) return fail(SPDY_ERR_ARG, "null seeds or result pointer");
     NOT_CAPTURING(p, "spdy_sppt_create (host table build + upload)");
     spdy_sppt *s = new spdy_sppt;
-    s->plan = p; s->nmem = nmem;
+    adopt(p, s);
+    s->nmem = nmem;
+    auto cleanup = [&](int rc) { spdy_sppt_destroy(s); *out = nullptr; return rc; };
     const std::string err = s->tab.build(p->tab, nsteps, mu);
-    if (!err.empty()) { delete s; return fail(SPDY_ERR_ARG, "sppt_create: %s", err.c_str()); }
+    if (!err.empty()) return cleanup(fail(SPDY_ERR_ARG, "sppt_create: %s", err.c_str()));
     *out = s;
     if (p->device < 0) return SPDY_OK;
-    auto cleanup = [&](int rc) { spdy_sppt_destroy(s); *out = nullptr; return rc; };
     const long nk = (long)nmem * p->tab.kx;
     if (p->max_batch < nk)
         return cleanup(fail(SPDY_ERR_ARG, "max_batch=%d must be >= nmem*kx=%ld for the SPPT patterns' transform", p->max_batch, nk));
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
     const size_t nc = coefs(p) * nmem, ng = grid_elems(p) * nk, nsig = s->tab.sigma.size();
     const size_t bytes = (4 * nc + ng + nsig) * sizeof(double);
-    if (hipMalloc(reinterpret_cast<void **>(&s->d_eta), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(spdy::SpptState) * (size_t)nmem) != hipSuccess)
-        return cleanup(fail(SPDY_ERR_HIP, "sppt_create: hipMalloc of %zu bytes failed", bytes));
+    if (int rc = dev_alloc(p, bytes, &s->d_eta)) return cleanup(rc);
+    if (int rc = dev_alloc(p, sizeof(spdy::SpptState) * (size_t)nmem, &s->d_state)) return cleanup(rc);
     s->d_spec = s->d_eta + 2 * nc; s->d_pattern = s->d_spec + 2 * nc; s->d_sigma = s->d_pattern + ng;
     if (hipMemsetAsync(s->d_eta, 0, bytes, p->stream) != hipSuccess ||
         hipMemcpyAsync(s->d_sigma, s->tab.sigma.data(), nsig * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess)
@@ -78,26 +70,21 @@ int spdy_sppt_create(spdy_plan *p, int nsteps, const double *mu, unsigned long l
 
 int spdy_sppt_members(const spdy_sppt *s)
 {
-    NEED_SPPT(s);
+    NEED_LIVE(s, "SPPT pattern");
     return s->nmem;
 }
 
 int spdy_sppt_destroy(spdy_sppt *s)
 {
     if (!s) return SPDY_OK;
-    if (s->d_eta || s->d_state) {
-        (void)hipSetDevice(s->plan->device);
-        (void)hipStreamSynchronize(s->plan->stream);
-        if (s->d_eta) (void)hipFree(s->d_eta);
-        if (s->d_state) (void)hipFree(s->d_state);
-    }
+    retire(s, {s->d_eta, s->d_state});
     delete s;
     return SPDY_OK;
 }
 
 int spdy_ens_sppt_reset(spdy_sppt *s, int member, unsigned long long seed)
 {
-    NEED_SPPT(s);
+    NEED_LIVE(s, "SPPT pattern");
     RC(need_member(s, member));
     spdy_plan *p = s->plan;
     NOT_CAPTURING(p, "spdy_sppt_reset (upload)");
@@ -109,7 +96,7 @@ int spdy_sppt_reset(spdy_sppt *s, unsigned long long seed) { return spdy_ens_spp
 
 int spdy_sppt_table(const spdy_sppt *s, const char *name, double *buf, int cap)
 {
-    NEED_SPPT(s);
+    NEED_LIVE(s, "SPPT pattern");
     if (!name) return fail(SPDY_ERR_ARG, "null table name");
     const std::vector<double> *v = s->tab.lookup(name);
     if (!v) return fail(SPDY_ERR_ARG, "unknown SPPT table '%s'", name);
@@ -121,7 +108,7 @@ int spdy_sppt_table(const spdy_sppt *s, const char *name, double *buf, int cap)
 
 int spdy_sppt_field(spdy_sppt *s, const char *name, double **d_ptr)
 {
-    NEED_SPPT(s);
+    NEED_LIVE(s, "SPPT pattern");
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
     double *const *f = !std::strcmp(name, "eta") ? &s->d_eta : !std::strcmp(name, "spec") ? &s->d_spec
                        : !std::strcmp(name, "pattern") ? &s->d_pattern : nullptr;
@@ -133,15 +120,14 @@ int spdy_sppt_field(spdy_sppt *s, const char *name, double **d_ptr)
 
 int spdy_ens_sppt_draws(spdy_sppt *s, int member, long long *draws)
 {
-    NEED_SPPT(s);
+    NEED_LIVE(s, "SPPT pattern");
     RC(need_member(s, member));
     if (!draws) return fail(SPDY_ERR_ARG, "null result pointer");
     spdy_plan *p = s->plan;
     NOT_CAPTURING(p, "spdy_sppt_draws (download)");
     NEED_DEVICE(p);
     spdy::SpptState h{};
-    HIP_TRY(hipMemcpyAsync(&h, s->d_state + member, sizeof(h), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    RC(download_sync(p, &h, s->d_state + member, sizeof(h)));
     *draws = (long long)h.draws;
     return SPDY_OK;
 }
@@ -150,7 +136,7 @@ int spdy_sppt_draws(spdy_sppt *s, long long *draws) { return spdy_ens_sppt_draws
 
 int spdy_sppt_advance_dev(spdy_sppt *s, const double *d_eta)
 {
-    NEED_SPPT(s);
+    NEED_LIVE(s, "SPPT pattern");
     spdy_plan *p = s->plan;
     NEED_DEVICE(p);
     const int nk = s->nmem * p->tab.kx;

@@ -404,16 +404,11 @@ int spdy_ens_direct_batch_spectral_step_dev(spdy_plan *p, int nmem, const double
 /* ---------------------------------------------------------------- output path */
 int spdy_output_workspace(spdy_plan *p)
 {
-    NEED_DEVICE(p);
-    if (p->out_grid) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the output workspace (call spdy_output_workspace before the capture)");
+    NEED_PLAN(p);
+    const char *what = "allocating the output workspace (call spdy_output_workspace before the capture)";
     const int kx = p->tab.kx;
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(5 * kx + 1) * grid_elems(p) * sizeof(double), &ptr));
-    p->out_grid = static_cast<double *>(ptr);
-    RC(dev_alloc(p, (size_t)(3 * kx + 1) * spec_elems(p) * sizeof(double), &ptr));
-    p->out_spec = static_cast<double *>(ptr);
-    return SPDY_OK;
+    RC(ensure_workspace(p, &p->out_grid, (size_t)(5 * kx + 1) * grid_elems(p), what));
+    return ensure_workspace(p, &p->out_spec, (size_t)(3 * kx + 1) * spec_elems(p), what);
 }
 
 int spdy_output_batch_dev(spdy_plan *p, const double *vor, const double *div, const double *t, const double *q, const double *phi,
@@ -430,10 +425,10 @@ int spdy_output_batch_dev(spdy_plan *p, const double *vor, const double *div, co
     spdy::GatherOps g{};
     g.nops = 4;
     const double *src[4] = {t, q, phi, ps};
-    for (int i = 0; i < 4; ++i) { g.nfld[i] = i < 3 ? kx : 1; g.src[i] = src[i]; g.dst[i] = p->out_spec + (size_t)i * kx * ss; }
+    for (int i = 0; i < 4; ++i) { g.nfld[i] = i < 3 ? kx : 1; g.src[i] = src[i]; g.dst[i] = p->out_spec.g + (size_t)i * kx * ss; }
     KERNEL(spdy::launch_gather_spectra(p->dev, g, p->stream));
-    double *ug = p->out_grid, *vg = ug + (size_t)kx * gs, *plain = vg + (size_t)kx * gs;
-    RC(spdy_inverse_batch_dev(p, kx, vor, div, ug, vg, 2, 3 * kx + 1, p->out_spec, nullptr, 1, plain));
+    double *ug = p->out_grid.g, *vg = ug + (size_t)kx * gs, *plain = vg + (size_t)kx * gs;
+    RC(spdy_inverse_batch_dev(p, kx, vor, div, ug, vg, 2, 3 * kx + 1, p->out_spec.g, nullptr, 1, plain));
     // input_output.f90:200-206: u, v, t as they are; q*1.0e-3; phi/grav; p0*exp(ps) -- then real(., sp)
     spdy::OutputCast c{};
     c.nops = 6;
@@ -442,7 +437,7 @@ int spdy_output_batch_dev(spdy_plan *p, const double *vor, const double *div, co
     const double fac[6] = {1.0, 1.0, 1.0, static_cast<double>(1.0e-3f), p->tab.grav, static_cast<double>(1.e+5f)};
     for (int i = 0; i < 6; ++i) {
         c.nfld[i] = i < 5 ? kx : 1; c.kind[i] = kind[i]; c.factor[i] = fac[i];
-        c.src[i] = p->out_grid + (size_t)i * kx * gs; c.dst[i] = dst[i];
+        c.src[i] = p->out_grid.g + (size_t)i * kx * gs; c.dst[i] = dst[i];
     }
     KERNEL(spdy::launch_output_cast(p->dev, c, p->stream));
     return SPDY_OK;
@@ -452,15 +447,9 @@ int spdy_output_batch_dev(spdy_plan *p, const double *vor, const double *div, co
 int spdy_ens_output_workspace(spdy_plan *p, int nmem)
 {
     RC(ens_output_members(p, nmem));
-    NEED_DEVICE(p);
-    if (p->ens_out_grid.nmem >= nmem) return SPDY_OK;
-    NOT_CAPTURING(p, "allocating the ensemble output workspace (call spdy_ens_output_workspace before the capture)");
-    RC(ensure_four(p));   // the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
-    // a smaller earlier workspace stays with the plan until it is destroyed: a captured graph may still point into it
-    void *ptr;
-    RC(dev_alloc(p, (size_t)(5 * p->tab.kx + 1) * grid_elems(p) * nmem * sizeof(double), &ptr));
-    p->ens_out_grid = {static_cast<double *>(ptr), nmem};
-    return SPDY_OK;
+    // with the Fourier workspace: the operator route of the T63 inverse launch keeps (vor, div) -> (U, V) in the plan's temporaries
+    return ensure_workspace(p, &p->ens_out_grid, (size_t)(5 * p->tab.kx + 1) * grid_elems(p) * nmem,
+                            "allocating the ensemble output workspace (call spdy_ens_output_workspace before the capture)", true);
 }
 
 int spdy_ens_output_batch_dev(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q,

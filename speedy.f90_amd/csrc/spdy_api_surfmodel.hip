@@ -7,34 +7,9 @@
 
 using namespace spdy_detail;
 
-struct spdy_surface_model {
-    spdy_plan *plan = nullptr;
-    int flags = 0;
-    int nmem = 1;                     // members: every field a kernel writes, and fmask_l, is held (nmem, il, ix)
-    size_t ncol = 0;
-    spdy::SurfaceTables tab;
-    double *d_f = nullptr;            // surf_total(nmem) fields of ncol doubles (csrc/spdy_kernels.hpp: SurfField, surf_slot)
-    spdy::SurfDate *d_date = nullptr;
-    bool date_ready = false;          // spdy_surface_model_set_date has run
-    bool started = false;             // spdy_surface_model_couple_dev(day = 0) has been issued
-};
-
 namespace {
-#define NEED_MODEL(m)                                                   \
-    do {                                                                \
-        if (!(m)) return fail(SPDY_ERR_ARG, "null surface model");      \
-    } while (0)
-
 // member 0 of a field held per member (the base of its (nmem, il, ix) stack), the field itself where it is held once
 double *field(const spdy_surface_model *m, int n) { return m->d_f + (size_t)spdy::surf_slot(n, m->nmem, 0) * m->ncol; }
-
-// stream-ordered upload as spdy_radiation_set_date's: the synchronisation keeps the caller's array alive until the copy is done
-int upload(spdy_surface_model *m, void *dst, const void *src, size_t bytes)
-{
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, m->plan->stream));
-    HIP_TRY(hipStreamSynchronize(m->plan->stream));
-    return SPDY_OK;
-}
 
 int field_index(const char *name)
 {
@@ -69,17 +44,17 @@ int spdy_ens_surface_model_create(spdy_plan *p, int nmem, const spdy_surface_cli
         return fail(SPDY_ERR_ARG, "surface_model_create: null field");
     NOT_CAPTURING(p, "spdy_surface_model_create (host table build + upload)");
     spdy_surface_model *m = new spdy_surface_model;
-    m->plan = p; m->flags = flags; m->nmem = nmem; m->ncol = grid_elems(p);
+    adopt(p, m);
+    m->flags = flags; m->nmem = nmem; m->ncol = grid_elems(p);
+    auto cleanup = [&](int rc) { spdy_surface_model_destroy(m); *out = nullptr; return rc; };
     const std::string err = m->tab.build(p->tab, host->fmask, host->alb0, delt);
-    if (!err.empty()) { delete m; return fail(SPDY_ERR_ARG, "surface_model_create: %s", err.c_str()); }
+    if (!err.empty()) return cleanup(fail(SPDY_ERR_ARG, "surface_model_create: %s", err.c_str()));
     *out = m;
     if (p->device < 0) return SPDY_OK;
-    auto cleanup = [&](int rc) { spdy_surface_model_destroy(m); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
     const size_t n = m->ncol, total = (size_t)spdy::surf_total(nmem) * n, bytes = total * sizeof(double);
-    if (hipMalloc(reinterpret_cast<void **>(&m->d_f), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&m->d_date), sizeof(spdy::SurfDate)) != hipSuccess)
-        return cleanup(fail(SPDY_ERR_HIP, "surface_model_create: hipMalloc of %zu bytes failed", bytes));
+    if (int rc = dev_alloc(p, bytes, &m->d_f)) return cleanup(rc);
+    if (int rc = dev_alloc(p, sizeof(spdy::SurfDate), &m->d_date)) return cleanup(rc);
     // one staging array: the constants, zeros for the model's own fields, the climatologies
     std::vector<double> h(total, 0.0);
     auto put = [&](int at, const double *src, int nf, int e = 0) {
@@ -93,26 +68,21 @@ int spdy_ens_surface_model_create(spdy_plan *p, int nmem, const spdy_surface_cli
     put(spdy::SM_STL12, host->stl12, 12); put(spdy::SM_SNOWD12, host->snowd12, 12); put(spdy::SM_SOILW12, host->soilw12, 12);
     put(spdy::SM_SST12, host->sst12, 12); put(spdy::SM_SICE12, host->sice12, 12);
     if (ssta) put(spdy::SM_SSTAN3, host->sstan3, 3);
-    const int rc = upload(m, m->d_f, h.data(), bytes);
+    const int rc = upload_sync(p, m->d_f, h.data(), bytes);
     return rc ? cleanup(rc) : SPDY_OK;
 }
 
 int spdy_surface_model_destroy(spdy_surface_model *m)
 {
     if (!m) return SPDY_OK;
-    if (m->d_f || m->d_date) {
-        (void)hipSetDevice(m->plan->device);
-        (void)hipStreamSynchronize(m->plan->stream);
-        if (m->d_f) (void)hipFree(m->d_f);
-        if (m->d_date) (void)hipFree(m->d_date);
-    }
+    retire(m, {m->d_f, m->d_date});
     delete m;
     return SPDY_OK;
 }
 
 int spdy_surface_model_table(const spdy_surface_model *m, const char *name, double *buf, int cap)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     if (!name) return fail(SPDY_ERR_ARG, "null table name");
     const std::vector<double> *v = m->tab.lookup(name);
     if (!v) return fail(SPDY_ERR_ARG, "unknown surface-model table '%s'", name);
@@ -123,7 +93,7 @@ int spdy_surface_model_table(const spdy_surface_model *m, const char *name, doub
 
 int spdy_surface_model_set_date(spdy_surface_model *m, int imont1, double tmonth, double tyear)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     spdy_plan *p = m->plan;
     NOT_CAPTURING(p, "spdy_surface_model_set_date (host weights + upload)");
     spdy::SurfaceDateWeights w;
@@ -135,25 +105,25 @@ int spdy_surface_model_set_date(spdy_surface_model *m, int imont1, double tmonth
     spdy::SurfDate d{};
     for (int k = 0; k < 5; ++k) { d.w5[k] = w.w5[k]; d.m5[k] = w.m5[k]; }
     d.wmon = w.wmon; d.m2[0] = w.m2[0]; d.m2[1] = w.m2[1]; d.s2 = w.s2;
-    RC(upload(m, m->d_date, &d, sizeof(d)));
+    RC(upload_sync(p, m->d_date, &d, sizeof(d)));
     m->date_ready = true;
     return SPDY_OK;
 }
 
 int spdy_surface_model_set_sst_anomaly(spdy_surface_model *m, const double *sstan3)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     if (!sstan3) return fail(SPDY_ERR_ARG, "null sstan3");
     spdy_plan *p = m->plan;
     NOT_CAPTURING(p, "spdy_surface_model_set_sst_anomaly (upload)");
     NEED_DEVICE(p);
-    return upload(m, field(m, spdy::SM_SSTAN3), sstan3, 3 * m->ncol * sizeof(double));
+    return upload_sync(p, field(m, spdy::SM_SSTAN3), sstan3, 3 * m->ncol * sizeof(double));
 }
 
 int spdy_surface_model_couple_dev(spdy_surface_model *m, int day, const double *hfluxn, const double *shf, const double *evap,
                                   const double *ssrd)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     spdy_plan *p = m->plan;
     if (day < 0) return fail(SPDY_ERR_ARG, "surface_model_couple: day %d", day);
     if (day > 0 && !(hfluxn && shf && evap && ssrd)) return fail(SPDY_ERR_ARG, "null device pointer");
@@ -172,7 +142,7 @@ int spdy_surface_model_couple_dev(spdy_surface_model *m, int day, const double *
 
 int spdy_surface_model_forcing_dev(spdy_surface_model *m, double *qcorh)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     spdy_plan *p = m->plan;
     if (!qcorh) return fail(SPDY_ERR_ARG, "null device pointer");
     if (m->nmem > p->max_batch) return fail(SPDY_ERR_ARG, "surface_model_forcing: nmem=%d exceeds the plan's max_batch=%d", m->nmem, p->max_batch);
@@ -192,7 +162,7 @@ int spdy_surface_model_forcing_dev(spdy_surface_model *m, double *qcorh)
 
 int spdy_surface_model_boundary(spdy_surface_model *m, spdy_sfc_boundary *bnd, const double **albsfc)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     if (!bnd || !albsfc) return fail(SPDY_ERR_ARG, "null result pointer");
     NEED_DEVICE(m->plan);
     bnd->fmask = field(m, spdy::SM_FMASK_L); bnd->sst = field(m, spdy::SM_SST_AM); bnd->stl = field(m, spdy::SM_STL_AM);
@@ -204,7 +174,7 @@ int spdy_surface_model_boundary(spdy_surface_model *m, spdy_sfc_boundary *bnd, c
 
 int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d_ptr)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
     const int i = field_index(name);
     if (i < 0) return fail(SPDY_ERR_ARG, "unknown surface-model field '%s'", name);
@@ -215,7 +185,7 @@ int spdy_surface_model_field(spdy_surface_model *m, const char *name, double **d
 
 int spdy_surface_model_members(const spdy_surface_model *m, const char *name)
 {
-    NEED_MODEL(m);
+    NEED_LIVE(m, "surface model");
     if (!name) return m->nmem;
     const int i = field_index(name);
     if (i < 0) return fail(SPDY_ERR_ARG, "unknown surface-model field '%s'", name);

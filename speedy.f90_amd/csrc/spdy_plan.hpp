@@ -1,10 +1,11 @@
 // Internal: the plan object behind include/spdy.h and the helpers shared by the C-ABI translation units
 // (spdy_api.hip: plan, transforms, operators, graphs; spdy_api_step.hip: time-step tail, output; spdy_api_shard.hip:
 // collectives; spdy_api_physics.hip: column physics; spdy_api_surfmodel.hip, spdy_api_sppt.hip,
-// spdy_api_diagnostics.hip: the objects made on a plan).
+// spdy_api_diagnostics.hip, spdy_api_letkf.hip: the objects made on a plan).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,21 @@ struct spdy_graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
 };
+
+namespace spdy_detail {
+// What every object made on a plan starts with (surface model, SPPT pattern, diagnostics, analysis).  The plan lists its live
+// objects; their device memory is the plan's (dev_alloc / dev_release).  spdy_plan_destroy sets plan = nullptr in each: the handle
+// stays valid but dead, every call but _destroy then returns SPDY_ERR_STATE (NEED_LIVE), as with graphs and communicators.
+struct PlanObject {
+    spdy_plan *plan = nullptr;
+    virtual void forget_device() = 0;   // null every device pointer: the plan has freed what they pointed at
+protected:
+    ~PlanObject() = default;
+};
+
+// A device workspace allocated at its first use and grown when a larger one is asked for (ensure_workspace).
+struct Workspace { double *g = nullptr; size_t doubles = 0; };
+}  // namespace spdy_detail
 
 struct spdy_plan {
     spdy::HostTables tab;
@@ -44,22 +60,24 @@ struct spdy_plan {
     std::vector<Pending> pending;     // device-written host-stage results still to be copied to the caller's arrays
     const double *d_zero_spec = nullptr;         // one all-zero spectrum (gradient tiles of the mixed inverse kernel)
     double *tmp_c = nullptr, *tmp_d = nullptr;   // max_batch spectra each; allocated with `four` (multi-kernel operator sequences)
-    double *out_grid = nullptr, *out_spec = nullptr;   // output path: (5kx+1) grids, (3kx+1) spectra (spdy_output_workspace)
-    // ensemble output: (5kx+1) grids per member, u | v | t | q | phi (nmem*kx each) | ps (nmem) (spdy_ens_output_workspace)
-    struct EnsOutGrids { double *g = nullptr; int nmem = 0; } ens_out_grid;
-    double *moist_grid = nullptr;     // moist physics from spectra: (3kx+1) grids t | q | phi | ln ps (spdy_moist_workspace)
+    // On-demand workspaces (ensure_workspace).  One that has to grow is allocated anew: the smaller earlier one stays with the plan
+    // until it is destroyed, a captured graph may still point into it.
+    using Workspace = spdy_detail::Workspace;
+    Workspace out_grid, out_spec;     // output path: (5kx+1) grids, (3kx+1) spectra (spdy_output_workspace)
+    Workspace ens_out_grid;           // ensemble output: (5kx+1) grids per member, u | v | t | q | phi (nmem*kx each) | ps (nmem) (spdy_ens_output_workspace)
+    Workspace moist_grid;             // moist physics from spectra: (3kx+1) grids t | q | phi | ln ps (spdy_moist_workspace)
     double *d_radzonal = nullptr;     // [5][il] zonal radiation forcing fsol | ozone | ozupp | zenit | stratz (spdy_radiation_set_date)
     double *d_orog = nullptr;         // phis0 (ix,il) | forog (ix,il) | sqrt(coa(j)) [il] (spdy_surface_set_orography)
-    double *physics_ws = nullptr;     // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
+    Workspace physics_ws;             // column-physics chain: (3kx+12) grids per state, max_batch states (spdy_column_physics_workspace)
     // physics from spectra of nmem states: u | v | t | q | phi (nmem*kx grids each) | ln ps (nmem), then the chain workspace of
     // (3kx+12) fields of nmem grids.  The chain's part is not scratch: it holds ssrd from one shortwave step to the next, so the
     // single state and the ensemble each keep their own (spdy_physics_workspace, spdy_ens_physics_workspace)
-    struct PhysicsGrids { double *g = nullptr; int nmem = 0; } physics_grid, ens_physics_grid;
-    double *sppt_ws = nullptr;        // SPPT on gridded states: the dynamics tendencies, (2kx+2) grids per state, max_batch states
+    Workspace physics_grid, ens_physics_grid;
+    Workspace sppt_ws;                // SPPT on gridded states: the dynamics tendencies, (2kx+2) grids per state, max_batch states
                                       // (spdy_column_physics_sppt_workspace)
-    double *sppt_grid = nullptr;      // SPPT from spectra: one state's (2kx+2) grids (spdy_physics_sppt_workspace)
+    Workspace sppt_grid;              // SPPT from spectra: one state's (2kx+2) grids (spdy_physics_sppt_workspace)
     // SPPT from the spectra of nmem members: (2kx+2) fields of nmem grids; grows like ens_physics_grid (spdy_ens_physics_sppt_workspace)
-    struct SpptGrids { double *g = nullptr; int nmem = 0; } ens_sppt_grid;
+    Workspace ens_sppt_grid;
     int physics_fused = -1;           // column physics in one launch: -1 unset (spdy_physics_dev only), 0 never, 1 always (spdy_plan_set_option)
     int *d_kcos = nullptr;
     // device copies of dt-dependent tables
@@ -79,35 +97,48 @@ struct spdy_plan {
     std::vector<Span> spans;
     std::vector<spdy_graph *> graphs; // graphs captured from this plan that are still alive
     std::vector<struct spdy_comm *> comms;   // communicators created on this plan that are still alive (spdy_api_shard.hip)
+    std::vector<spdy_detail::PlanObject *> objects;   // objects made on this plan that are still alive (spdy_detail::PlanObject)
+};
+
+// The surface models behind include/spdy.h's spdy_surface_model (csrc/spdy_api_surfmodel.hip).
+struct spdy_surface_model final : spdy_detail::PlanObject {
+    int flags = 0;
+    int nmem = 1;                     // members: every field a kernel writes, and fmask_l, is held (nmem, il, ix)
+    size_t ncol = 0;
+    spdy::SurfaceTables tab;
+    double *d_f = nullptr;            // surf_total(nmem) fields of ncol doubles (csrc/spdy_kernels.hpp: SurfField, surf_slot)
+    spdy::SurfDate *d_date = nullptr;
+    bool date_ready = false;          // spdy_surface_model_set_date has run
+    bool started = false;             // spdy_surface_model_couple_dev(day = 0) has been issued
+    void forget_device() override { d_f = nullptr; d_date = nullptr; }
 };
 
 // The SPPT patterns behind include/spdy.h's spdy_sppt (csrc/spdy_api_sppt.hip), one per member, member-major like every ensemble
 // array; spdy_physics_sppt_dev and spdy_ens_physics_sppt_dev read pattern and mu.  The tables are shared by the members.
-struct spdy_sppt {
-    spdy_plan *plan = nullptr;
+struct spdy_sppt final : spdy_detail::PlanObject {
     int nmem = 1;
     spdy::SpptTables tab;
     spdy::SpptState *d_state = nullptr;   // [nmem] each member's counter and seed
     double *d_sigma = nullptr;            // (mx, nx)
     double *d_eta = nullptr, *d_spec = nullptr;   // (mx, nx, kx, nmem) complex
     double *d_pattern = nullptr;          // (ix, il, kx, nmem)
+    void forget_device() override { d_state = nullptr; d_sigma = d_eta = d_spec = d_pattern = nullptr; }
 };
 
 // The run's guard behind include/spdy.h's spdy_diagnostics (csrc/spdy_api_diagnostics.hip): one device allocation, history | limits | state.
-struct spdy_diagnostics {
-    spdy_plan *plan = nullptr;
+struct spdy_diagnostics final : spdy_detail::PlanObject {
     int capacity = 0;
     int nmem = 1;                         // members checked by one launch (spdy_ens_diagnostics_create)
     long long start_step = 0;             // the first step since create / reset: nothing before it is in the ring
     double *d_history = nullptr;          // [capacity][nmem][3][kx]
     double *d_limits = nullptr;           // reke, deke, temp low, temp high: shared by the members
     spdy::DiagLevel *d_state = nullptr;   // [nmem][kx]
+    void forget_device() override { d_history = d_limits = nullptr; d_state = nullptr; }
 };
 
 // The ensemble analysis behind include/spdy.h's spdy_letkf (csrc/spdy_api_letkf.hip): the observation tables on the host, and
 // one device allocation that holds their copies, the observation-space fields and the analysis' two workspaces.
-struct spdy_letkf {
-    spdy_plan *plan = nullptr;
+struct spdy_letkf final : spdy_detail::PlanObject {
     int nmem = 0, max_obs = 0, nobs = 0;
     int nlv = 1;                          // levels whose eigenproblems a workgroup keeps in flight
     size_t lds = 0;                       // dynamic LDS of the transform kernel
@@ -129,12 +160,40 @@ struct spdy_letkf {
     double *d_wbase = nullptr;            // one allocation: tw | iwgt | iidx | coarse
     double *d_tw = nullptr, *d_iwgt = nullptr;     // [ncoarse][kx][nmem][nmem]; [ncol][4]
     int *d_iidx = nullptr, *d_coarse = nullptr;
+    void forget_device() override
+    {
+        d_base = d_grid = d_spec = d_colunit = d_lnfsg = d_swgt = d_ounit = d_olns = d_rinv = d_value = nullptr;
+        d_hx = d_hxmean = d_y = d_dep = d_wbase = d_tw = d_iwgt = nullptr;
+        d_sidx = d_var = d_lev = d_iidx = d_coarse = nullptr;
+    }
 };
 
 namespace spdy_detail {
 
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int dev_alloc(spdy_plan *p, size_t bytes, void **out);
+// gives a dev_alloc'ed buffer back before the plan goes: the plan's stream is synchronised first (queued work may still use it).
+// Null is fine; a buffer that cannot be released now (an open capture) stays with the plan.
+int dev_release(spdy_plan *p, void *ptr);
+template <class T> int dev_alloc(spdy_plan *p, size_t bytes, T **out)
+{
+    void *ptr = nullptr;
+    const int rc = dev_alloc(p, bytes, &ptr);
+    *out = static_cast<T *>(ptr);
+    return rc;
+}
+// w holds at least `doubles` doubles afterwards: NEED_DEVICE, nothing to do if it is large enough, NOT_CAPTURING(p, what),
+// [ensure_four], dev_alloc (see spdy_plan::Workspace for what becomes of a smaller earlier one)
+int ensure_workspace(spdy_plan *p, Workspace *w, size_t doubles, const char *what, bool with_four = false);
+// one copy on the plan's stream and its synchronisation: the caller's host array is free (upload) or filled (download) on return.
+// Stream-ordered: work enqueued, or a graph replayed, before the call sees the old contents, work after it the new ones.
+int upload_sync(spdy_plan *p, void *dst, const void *src, size_t bytes);
+int download_sync(spdy_plan *p, void *dst, const void *src, size_t bytes);
+// An object joins its plan where it is `new`ed, on a host-only plan too and before anything can fail.  Its _destroy calls retire
+// with the device buffers it owns and then deletes the handle: a live object leaves the plan's list and gives the buffers back
+// (dev_release), a dead one has nothing left to give.
+inline void adopt(spdy_plan *p, PlanObject *o) { o->plan = p; p->objects.push_back(o); }
+void retire(PlanObject *o, std::initializer_list<void *> buffers);
 int check_batch(const spdy_plan *p, int nb);
 int h2d(spdy_plan *p, double *dst, const double *src, size_t n);
 int d2h(spdy_plan *p, double *dst, const double *src, size_t n);
@@ -175,6 +234,12 @@ inline size_t four_elems(const spdy_plan *p) { return (size_t)2 * p->tab.mx * p-
         NEED_PLAN(p);                                                                                        \
         if ((p)->device < 0) return spdy_detail::fail(SPDY_ERR_NO_DEVICE, "host-only plan: no HIP device, no CPU fallback"); \
         HIP_TRY(hipSetDevice((p)->device));                                                                  \
+    } while (0)
+// the first check of every call on an object made on a plan but _destroy (spdy_detail::PlanObject)
+#define NEED_LIVE(x, what)                                                                                   \
+    do {                                                                                                     \
+        if (!(x)) return spdy_detail::fail(SPDY_ERR_ARG, "null %s", what);                                   \
+        if (!(x)->plan) return spdy_detail::fail(SPDY_ERR_STATE, "the plan this %s was made on has been destroyed", what); \
     } while (0)
 #define NOT_CAPTURING(p, what)                                                                               \
     do {                                                                                                     \

@@ -9,12 +9,11 @@ After an analysis the run continues
 with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled: build the analysis ensemble from
 members the guard has not stopped, a non-finite member makes every column it touches non-finite."""
 import ctypes
-import weakref
 
 import numpy as np
 
 from ._lib import check
-from .columns import DeviceField, _p
+from .columns import DeviceField, PlanObject
 
 OBS_U, OBS_V, OBS_T, OBS_Q, OBS_PS = range(5)
 LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv", "coarse_columns", "interp_index", "interp_weight")
@@ -33,10 +32,11 @@ class _DeviceView:
         self.__cuda_array_interface__ = {"shape": f.shape, "typestr": "<f8", "data": (f.ptr, False), "version": 2}
 
 
-class Letkf:
+class Letkf(PlanObject):
     """sigma_h: horizontal localisation scale in metres; sigma_v: vertical scale in ln sigma (<= 0: none); rho: multiplicative
     inflation of the background covariance; weight_stride: set_weight_stride.  2 <= nmem <= 32; the plan needs max_batch >= nmem
     (2 kx + 1)."""
+    PREFIX = "spdy_letkf"
 
     def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1)):
         self.sp, self.lib = sp, sp.lib
@@ -45,23 +45,10 @@ class Letkf:
         h = ctypes.c_void_p()
         check(self.lib.spdy_letkf_create(sp.h, int(nmem), int(max_obs), ctypes.byref(h)))
         self.h, self.nmem, self.max_obs, self.nobs = h, int(nmem), int(max_obs), 0
-        # the plan closes its objects first (as its surface models)
-        sp._models = [r for r in getattr(sp, "_models", []) if r() is not None and r().h] + [weakref.ref(self)]
         self.weight_stride = (1, 1)
         self.set_localization(sigma_h, sigma_v, rho)
         if tuple(weight_stride) != (1, 1):
             self.set_weight_stride(*weight_stride)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.spdy_letkf_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_localization(self, sigma_h, sigma_v=0.0, rho=1.0):
         """read when an analysis is enqueued: a captured analysis keeps the values of its capture"""
@@ -107,9 +94,7 @@ class Letkf:
         stencil_weight [nobs, 4], unit [nobs, 3], lnsigma [nobs], rinv [nobs]; or of the weight interpolation: coarse_columns
         [ncoarse] (grid columns j*ix+i, int64, ascending), interp_index [ncol, 4] (entries of coarse_columns, int64; an entry of
         weight zero repeats the first), interp_weight [ncol, 4]; all three are empty at stride (1, 1)."""
-        n = check(self.lib.spdy_letkf_table(self.h, name.encode(), None, 0))
-        out = np.zeros(n)
-        check(self.lib.spdy_letkf_table(self.h, name.encode(), _p(out), n))
+        out = self._table(name)
         if name in ("stencil_index", "interp_index"):
             return out.astype(np.int64).reshape(-1, 4)
         if name == "coarse_columns":

@@ -115,10 +115,6 @@ class Spectral(ColumnPhysics):
 
     def close(self):
         if getattr(self, "h", None):
-            for ref in getattr(self, "_models", []):       # a surface model must go before its plan (include/spdy.h)
-                m = ref()
-                if m is not None:
-                    m.close()
             self.lib.spdy_plan_destroy(self.h)
             self.h = None
 
@@ -311,7 +307,8 @@ class Spectral(ColumnPhysics):
 
     def _sync_stream(self):
         # (while a capture is open the plan's stream is pinned: spdy_plan_set_stream would fail with SPDY_ERR_STATE)
-        if not getattr(self, "_follow", True) or getattr(self, "_capturing", False):
+        # (a closed plan has no stream: the call that follows reports what it was asked on)
+        if not getattr(self, "_follow", True) or getattr(self, "_capturing", False) or not self.h:
             return
         import torch
         h = torch.cuda.current_stream().cuda_stream
