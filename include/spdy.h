@@ -69,8 +69,8 @@ enum {
  * inside an open capture is refused with SPDY_ERR_STATE).  Destroying a plan also invalidates the graphs captured
  * from it (spdy_graph_launch then returns SPDY_ERR_STATE) and shuts down its communicators (spdy_comm_*: the handles
  * stay valid for spdy_comm_destroy, every other call on them returns SPDY_ERR_STATE).
- * The same rule holds for every object made on a plan (spdy_surface_model, spdy_sppt, spdy_diagnostics, spdy_letkf): its
- * device memory is the plan's and goes with it, the handle stays valid for its _destroy, and every other call on it returns
+ * The same rule holds for every object made on a plan (spdy_surface_model, spdy_sppt, spdy_diagnostics, spdy_letkf, spdy_nature):
+ * its device memory is the plan's and goes with it, the handle stays valid for its _destroy, and every other call on it returns
  * SPDY_ERR_STATE.  A plan and what was made on it may so be destroyed in any order.                                  */
 /* Environment read by the library (measurement and debugging aids; none changes results beyond rounding-level path choices).
  * The launch-policy switches (SPDY_T30_*, SPDY_T63_*, SPDY_WT_MIN_MB) are read ONCE per plan, in spdy_plan_create; a plan's
@@ -957,10 +957,13 @@ int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf
  * captured graph keeps the values of its capture.  spdy_letkf_set_obs validates every field of every observation before it
  * changes anything, builds the stencils, unit vectors, ln sigma_o and 1/error^2 on the host and uploads them (stream-ordered,
  * synchronising; not inside a capture; should a copy fail, SPDY_ERR_HIP, the object is left with no observations, not with a
- * mixture); the device arrays do not move, so a captured analysis replays with the observations of
+ * mixture; the errors themselves are kept on the device too, for spdy_nature_observe_dev, which may write the values in
+ * set_obs' place: "nature run" below); the device arrays do not move, so a captured analysis replays with the observations of
  * the latest set_obs as long as their number is that of the capture.  spdy_letkf_table (the host side; returns the count; buf NULL
  * = count only): "stencil_index" (4 per observation, j*ix+i as doubles), "stencil_weight" (4), "unit" (3), "lnsigma", "rinv".
- * spdy_letkf_field (device, valid after an analysis call): "hx" (nmem per observation), "hxmean", "y" (nmem), "departure".
+ * spdy_letkf_field (device, valid after an analysis call): "hx" (nmem per observation), "hxmean", "y" (nmem), "departure"; and
+ * "value", the observation values the next analysis reads (valid after set_obs or spdy_nature_observe_dev); "grid", the grid
+ * workspace of (4 kx + 1) nmem grids (the gridded ensemble after spdy_nature_verify_dev, the increments after spdy_ens_letkf_dev).
  * spdy_letkf_analyse_grid_dev: the ensemble on the grid, member-major, u .. q (ix,il,kx,nmem), ps (ix,il,nmem); the increments in
  * the same shapes; an output may be its input.  Two launches: the observation kernel, then one workgroup per grid column that
  * scans the observations in chunks, keeps those in range in ascending order (ballot and prefix counts, no atomics), forms C and b
@@ -1032,6 +1035,65 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr);
 int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg,
                                 const double *psg, double *du, double *dv, double *dt, double *dq, double *dps);
 int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps);
+
+/* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
+ * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
+ * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a
+ * sequence of enqueues that one captured graph can hold; the host reads 3 (4 kx + 1) doubles per verified ensemble.
+ * A spdy_nature is an object made on a plan (the plan section: one lifetime rule).  It owns, in one device block,
+ *   truth         the gridded truth: u, v (true wind), t, q (g/kg) at kx levels and ps = log(p/p0), (4 kx + 1) grids -- one member
+ *                 of the analysis' gridded layout; row f = v kx + k for variable v = 0..3 and level k, row 4 kx for ps;
+ *   state         two 64-bit words {seed, draws};
+ *   scores        a table [capacity][3][4 kx + 1] of doubles: rmse | bias | spread of every row, one slot per verified ensemble.
+ * spdy_nature_create(plan, seed, capacity >= 1, &n): needs the sigma levels and max_batch >= 2 kx + 1, allocates everything and
+ * runs the inverse batch of spdy_nature_set_state_dev once on zero spectra, so nothing is allocated afterwards and every *_dev call
+ * can be captured; draws = 0.  spdy_nature_reset(n, seed): the seed, and draws = 0 (stream-ordered upload, synchronising, not in a
+ * capture).  spdy_nature_draws: the counter (synchronising).  spdy_nature_field: "truth", "scores", "state" (the two words).
+ * spdy_nature_set_state_dev(n, vor, div, t, q, ps): the single-state spectra of time level 1.  ONE spdy_inverse_batch_segs_dev,
+ * the call spdy_ens_letkf_dev makes with nmem = 1 (kx pairs as true wind, the segments t | q of kx fields and ps of 1), into truth.
+ * spdy_nature_observe_dev(n, letkf, noise): for the nobs observations of letkf's latest spdy_letkf_set_obs -- their values are
+ * ignored, zeros will do: they define the network -- it writes letkf's device value table,
+ *       h_o     = ((w0 x0 + w1 x1) + w2 x2) + w3 x3           the operator of the analysis, on the truth
+ *       value_o = h_o + (noise * error_o) * z_o
+ * error_o the error given to set_obs (the analysis object keeps it on the device), z_o the real part of SPPT's draw: Philox4x32-10
+ * with counter (o, 0, draws lo, draws hi) and key (seed lo, seed hi) through the same randn, so the noise of an observation depends
+ * on (seed, draws, o) only.  With noise == 0 the product is not formed: value_o has the bits of h_o.  A second launch then sets
+ * draws += 1, so every replay of a captured observe draws fresh noise.  nobs == 0 writes nothing and still counts.  One thread per
+ * observation, two launches (one with nobs == 0).  The next analysis call reads these values; set_obs overwrites them.
+ * spdy_nature_verify_dev(n, letkf, vor, div, t, q, ps, slot): time level 1 of an ensemble of letkf's nmem members in the layout of
+ * spdy_ens_letkf_dev goes to the grid by the call the analysis makes, into letkf's grid workspace (the next analysis overwrites it
+ * anyway), and every row f is scored against the truth.  With g_j the plan's Gaussian weights of the rows, south first, divided by
+ * their sum over j ascending, <a> = sum_j g_j ((sum_i a[j][i]) / ix) over j ascending, and per grid point
+ *       d_e  = x_e - truth                                    the members' errors
+ *       mbar = (sum_e d_e, e ascending) / E                   the error of the ensemble mean m: m - truth
+ *       s2   = (sum_e (d_e - mbar)^2, e ascending) / (E - 1)  the sample variance: d_e - mbar is x_e - m
+ *       rmse_f = sqrt(<mbar^2>)     bias_f = <mbar>     spread_f = sqrt(<s2>)
+ * The mean is formed on the errors and not on the members because E equal values do not in general sum to E times the value in
+ * floating point: on the errors an ensemble whose members all equal the truth scores exactly 0 in all three, and the subtraction
+ * that cancels is done once, exactly where the members are close to the truth, before anything is rounded.
+ * spdy_nature_verify_grid_dev(n, nmem, ug, vg, tg, qg, psg, slot) scores an ensemble that is on the grid already, in the layout of
+ * spdy_letkf_analyse_grid_dev, 2 <= nmem <= 32: the two score launches alone, no analysis object.
+ * scores[slot] receives rmse | bias | spread, (4 kx + 1) each.  Three launches: the inverse batch, one workgroup per (row,
+ * latitude) that sums a latitude's points in a fixed tree, one thread per row that adds the latitudes.  No atomics; every sum is in
+ * an order that does not depend on the launch; two runs are bit-equal; a row's scores depend on that row's grids only, so a
+ * non-finite value makes the three scores of its row NaN and touches no other row.
+ * Checks, in this order -- create: a NULL plan, capacity < 1, a NULL result pointer, max_batch SPDY_ERR_ARG; no sigma levels, an
+ * open capture SPDY_ERR_STATE.  Every other call: a NULL object SPDY_ERR_ARG, a destroyed plan SPDY_ERR_STATE; observe and verify
+ * then the analysis object in the same way and SPDY_ERR_ARG if it is of another plan; then noise < 0 or not finite, nmem outside [2, 32], slot
+ * outside [0, capacity), a NULL pointer, an unknown field name SPDY_ERR_ARG; an open capture SPDY_ERR_STATE (reset, draws); a host-only
+ * plan SPDY_ERR_NO_DEVICE last.  create works on a host-only plan.  A failing call enqueues nothing.                            */
+typedef struct spdy_nature spdy_nature;
+int spdy_nature_create(spdy_plan *plan, unsigned long long seed, int capacity, spdy_nature **n);
+int spdy_nature_destroy(spdy_nature *n);
+int spdy_nature_reset(spdy_nature *n, unsigned long long seed);
+int spdy_nature_draws(spdy_nature *n, long long *count);
+int spdy_nature_field(spdy_nature *n, const char *name, double **d_ptr);
+int spdy_nature_set_state_dev(spdy_nature *n, const double *vor, const double *div, const double *t, const double *q, const double *ps);
+int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *letkf, double noise);
+int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *letkf, const double *vor, const double *div, const double *t, const double *q,
+                           const double *ps, int slot);
+int spdy_nature_verify_grid_dev(spdy_nature *n, int nmem, const double *ug, const double *vg, const double *tg, const double *qg,
+                                const double *psg, int slot);
 
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,

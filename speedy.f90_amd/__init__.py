@@ -9,6 +9,7 @@ Only what the hot path needs lives here:
                  the ctypes structures and output buffers derived from it
     ensemble.py  E model states through one time step's launches: the layout, the views, the step
     letkf.py     the ensemble analysis: observations in, the LETKF update of all members on the device
+    nature.py    the nature run of a twin experiment: the truth, observations drawn from it, an ensemble's scores against it
 
 The directory name contains a dot, so import it through the repo-root shim
 ``import speedy_f90_amd`` (speedy_f90_amd.py).
@@ -18,4 +19,5 @@ from .spectral import (RESOLUTIONS, DeviceField, Diagnostics, DiagnosticsStop, G
                        check)
 from .ensemble import Ensemble  # noqa: F401
 from .letkf import OBS_PS, OBS_Q, OBS_T, OBS_U, OBS_V, Letkf  # noqa: F401
+from .nature import Nature  # noqa: F401
 from . import sharding  # noqa: F401

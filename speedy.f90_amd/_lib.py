@@ -181,6 +181,15 @@ SIGNATURES = {
     "spdy_letkf_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
     "spdy_letkf_analyse_grid_dev": [c_void_p] * 11,
     "spdy_ens_letkf_dev": [c_void_p] * 6,
+    "spdy_nature_create": [c_void_p, ctypes.c_ulonglong, c_int, ctypes.POINTER(c_void_p)],
+    "spdy_nature_destroy": [c_void_p],
+    "spdy_nature_reset": [c_void_p, ctypes.c_ulonglong],
+    "spdy_nature_draws": [c_void_p, ctypes.POINTER(ctypes.c_longlong)],
+    "spdy_nature_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
+    "spdy_nature_set_state_dev": [c_void_p] * 6,
+    "spdy_nature_observe_dev": [c_void_p, c_void_p, c_double],
+    "spdy_nature_verify_dev": [c_void_p] * 7 + [c_int],
+    "spdy_nature_verify_grid_dev": [c_void_p, c_int] + [c_void_p] * 5 + [c_int],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

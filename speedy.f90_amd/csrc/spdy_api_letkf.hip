@@ -175,8 +175,8 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     auto cleanup = [&](int rc) { spdy_letkf_destroy(l); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
     const size_t ncol = grid_elems(p), nf = (size_t)(4 * kx + 1) * nmem, M = (size_t)(max_obs > 0 ? max_obs : 1), E = (size_t)nmem;
-    // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | value | hx | hxmean | y | dep ; then the ints
-    const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 2 * E), ni = 6 * M;
+    // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | err | value | hx | hxmean | y | dep ; then the ints
+    const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 1 + 2 * E), ni = 6 * M;
     if (int rc = dev_alloc(p, nd * sizeof(double) + ni * sizeof(int), &l->d_base)) return cleanup(rc);
     double *d = l->d_base;
     l->d_grid = d; d += nf * ncol;
@@ -187,6 +187,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     l->d_ounit = d; d += 3 * M;
     l->d_olns = d; d += M;
     l->d_rinv = d; d += M;
+    l->d_err = d; d += M;
     l->d_value = d; d += M;
     l->d_hx = d; d += M * E;
     l->d_hxmean = d; d += M;
@@ -261,7 +262,7 @@ int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
     NOT_CAPTURING(p, "spdy_letkf_set_obs (upload)");
     const size_t n = (size_t)nobs;
     std::vector<int> sidx(4 * n), var(n), lev(n);
-    std::vector<double> swgt(4 * n), unit(3 * n), lns(n), rinv(n), value(n);
+    std::vector<double> swgt(4 * n), unit(3 * n), lns(n), rinv(n), err(n), value(n);
     for (size_t o = 0; o < n; ++o) {
         const spdy_obs &b = host[o];
         stencil(l, b.lon, b.lat, &sidx[4 * o], &swgt[4 * o]);
@@ -270,6 +271,7 @@ int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
         lev[o] = b.var == SPDY_OBS_PS ? 0 : b.lev;
         lns[o] = b.var == SPDY_OBS_PS ? 0.0 : l->lnfsg[b.lev];
         rinv[o] = 1.0 / (b.error * b.error);
+        err[o] = b.error;
         value[o] = b.value;
     }
     if (p->device >= 0) {
@@ -282,6 +284,7 @@ int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
             RC(upload(p, l->d_ounit, unit.data(), 3 * n * sizeof(double)));
             RC(upload(p, l->d_olns, lns.data(), n * sizeof(double)));
             RC(upload(p, l->d_rinv, rinv.data(), n * sizeof(double)));
+            RC(upload(p, l->d_err, err.data(), n * sizeof(double)));
             RC(upload(p, l->d_value, value.data(), n * sizeof(double)));
             HIP_TRY(hipStreamSynchronize(p->stream));
             return SPDY_OK;
@@ -365,7 +368,8 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
     double *const *f = !std::strcmp(name, "hx") ? &l->d_hx : !std::strcmp(name, "hxmean") ? &l->d_hxmean
                        : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep
-                       : !std::strcmp(name, "weights") ? &l->d_tw : nullptr;
+                       : !std::strcmp(name, "weights") ? &l->d_tw : !std::strcmp(name, "value") ? &l->d_value
+                       : !std::strcmp(name, "grid") ? &l->d_grid : nullptr;
     if (!f) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f == &l->d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
     NEED_DEVICE(l->plan);

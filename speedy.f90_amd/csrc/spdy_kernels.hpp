@@ -552,4 +552,32 @@ struct LetkfAdd {
 };
 hipError_t launch_spec_add(const LetkfAdd &a, hipStream_t s);
 
+// The nature run (csrc/spdy_nature.hip; include/spdy.h, "nature run").  The truth is one member of the analysis'
+// gridded layout: row f = v * kx + k of u, v, t, q, then ps, (4 kx + 1) grids.  state = {seed, draws}.
+// The observation values of an analysis object's network from the truth, one thread each: h in letkf_obs_kernel's order, then
+// value = h + (noise * error) * z with z = sppt_randn(o, 0, draws, seed); noise == 0 stores h.  Reads state, does not advance it.
+struct NatureObs {
+    int nobs, kx, ncol;
+    const int *var, *lev, *sidx;                     // the analysis object's tables, as LetkfObs
+    const double *swgt, *error;                      // [nobs][4], [nobs]
+    const double *truth;                             // (4 kx + 1) grids
+    const unsigned long long *state;
+    double noise;
+    double *value;                                   // [nobs]
+};
+hipError_t launch_nature_draw(const NatureObs &a, hipStream_t s);
+// draws += 1 by one thread: every launch before it on the stream has read the counter, every launch after it sees the new one
+hipError_t launch_nature_count(unsigned long long *state, hipStream_t s);
+// The scores of an ensemble on the grid (x: LetkfObs::x) against the truth, two launches.  One workgroup per (row, latitude) forms
+// the zonal sums of mbar, mbar^2 and sum_e (d_e - mbar)^2 / (E - 1), d_e = x_e - truth, mbar = (sum_e d_e, e ascending) / E, in a
+// fixed tree into part [nrows][il][3]; one thread per row then adds them over the latitudes in ascending order with gw [il] and
+// writes rmse | bias | spread of its row into scores [3][nrows].  No atomics.
+struct NatureScore {
+    int nmem, kx, ix, il;
+    const double *x[LETKF_VARS];
+    const double *truth, *gw;
+    double *part, *scores;
+};
+hipError_t launch_nature_score(const NatureScore &a, hipStream_t s);
+
 }  // namespace spdy

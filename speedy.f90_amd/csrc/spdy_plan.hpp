@@ -1,7 +1,7 @@
 // Internal: the plan object behind include/spdy.h and the helpers shared by the C-ABI translation units
 // (spdy_api.hip: plan, transforms, operators, graphs; spdy_api_step.hip: time-step tail, output; spdy_api_shard.hip:
 // collectives; spdy_api_physics.hip: column physics; spdy_api_surfmodel.hip, spdy_api_sppt.hip,
-// spdy_api_diagnostics.hip, spdy_api_letkf.hip: the objects made on a plan).
+// spdy_api_diagnostics.hip, spdy_api_letkf.hip, spdy_api_nature.hip: the objects made on a plan).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,7 +20,7 @@ struct spdy_graph {
 };
 
 namespace spdy_detail {
-// What every object made on a plan starts with (surface model, SPPT pattern, diagnostics, analysis).  The plan lists its live
+// What every object made on a plan starts with (surface model, SPPT pattern, diagnostics, analysis, nature run).  The plan lists its live
 // objects; their device memory is the plan's (dev_alloc / dev_release).  spdy_plan_destroy sets plan = nullptr in each: the handle
 // stays valid but dead, every call but _destroy then returns SPDY_ERR_STATE (NEED_LIVE), as with graphs and communicators.
 struct PlanObject {
@@ -151,6 +151,7 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     double *d_grid = nullptr, *d_spec = nullptr;   // (4kx+1) nmem grids u | v | t | q | ps, and as many spectra
     double *d_colunit = nullptr, *d_lnfsg = nullptr;
     double *d_swgt = nullptr, *d_ounit = nullptr, *d_olns = nullptr, *d_rinv = nullptr, *d_value = nullptr;
+    double *d_err = nullptr;              // [max_obs] the errors set_obs was given, next to rinv (spdy_nature_observe_dev reads them)
     double *d_hx = nullptr, *d_hxmean = nullptr, *d_y = nullptr, *d_dep = nullptr;
     int *d_sidx = nullptr, *d_var = nullptr, *d_lev = nullptr;
     // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
@@ -163,9 +164,22 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     void forget_device() override
     {
         d_base = d_grid = d_spec = d_colunit = d_lnfsg = d_swgt = d_ounit = d_olns = d_rinv = d_value = nullptr;
-        d_hx = d_hxmean = d_y = d_dep = d_wbase = d_tw = d_iwgt = nullptr;
+        d_hx = d_hxmean = d_y = d_dep = d_wbase = d_tw = d_iwgt = d_err = nullptr;
         d_sidx = d_var = d_lev = d_iidx = d_coarse = nullptr;
     }
+};
+
+// The nature run behind include/spdy.h's spdy_nature (csrc/spdy_api_nature.hip): one device allocation, truth | zero spectra |
+// zonal partial sums | normalised Gaussian weights | scores | state.
+struct spdy_nature final : spdy_detail::PlanObject {
+    int capacity = 0;
+    double *d_base = nullptr;
+    double *d_truth = nullptr;            // (4 kx + 1) grids u | v | t | q (kx each) | ps
+    double *d_part = nullptr;             // [4 kx + 1][il][3] zonal sums of a verify call
+    double *d_gw = nullptr;               // [il] Gaussian weights / their sum, south first
+    double *d_scores = nullptr;           // [capacity][3][4 kx + 1]
+    unsigned long long *d_state = nullptr;   // {seed, draws}
+    void forget_device() override { d_base = d_truth = d_part = d_gw = d_scores = nullptr; d_state = nullptr; }
 };
 
 namespace spdy_detail {

@@ -2,45 +2,15 @@
 // update in spectral space, the clip of the transformed pattern, and the save / apply kernels that bracket the five calls of
 // the column physics.  The inverse transform between the update and the clip is the plan's own (csrc/spdy_api_sppt.hip).
 //
-// The generator is Philox4x32-10 as include/spdy.h defines it: key (seed lo, seed hi), counter (coefficient index in storage
-// order inside the member, part, draws lo, draws hi), so a coefficient's noise depends on (seed, draws, index) only -- not on the
-// launch geometry, and not on the ensemble the member travels in.
-// randn is the reference's (sppt.f90:102-116), float32 literals widened: u = sqrt(-2 log r1), v = (2.0f * 6.28318530718f) r2
-// (4 pi: the reference's factor), u sin v.  Full-precision log, sqrt and sin, no contraction.
-#include "spdy_columns.hpp"
+// The generator is Philox4x32-10 as include/spdy.h defines it (csrc/spdy_philox.hpp, with the reference's randn): key (seed lo,
+// seed hi), counter (coefficient index in storage order inside the member, part, draws lo, draws hi), so a coefficient's noise
+// depends on (seed, draws, index) only -- not on the launch geometry, and not on the ensemble the member travels in.
+#include "spdy_philox.hpp"
 
 namespace spdy {
 namespace {
 
 constexpr int SPPT_BLOCK = 256;
-
-struct Philox4 { unsigned w[4]; };
-
-__device__ inline Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
-{
-    constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += W0; k1 += W1;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
-// one part of eta before the clip: the coefficient's draw number `part` (0 real, 1 imaginary)
-__device__ inline double sppt_randn(unsigned idx, unsigned part, unsigned long long draws, unsigned long long seed)
-{
-#pragma clang fp contract(off)
-    const Philox4 x = philox4x32_10(idx, part, (unsigned)draws, (unsigned)(draws >> 32), (unsigned)seed, (unsigned)(seed >> 32));
-    const double two26 = 67108864.0, twom53 = 1.0 / 9007199254740992.0;
-    const double r1 = ((double)(x.w[0] >> 5) * two26 + (double)(x.w[1] >> 6) + 1.0) * twom53;      // (0, 1]
-    const double r2 = ((double)(x.w[2] >> 5) * two26 + (double)(x.w[3] >> 6)) * twom53;            // [0, 1)
-    const double u = sqrt(F(-2.0f) * log(r1));
-    const double v = F(2.0f * 6.28318530718f) * r2;
-    return u * sin(v);
-}
 
 // min(lim, |x|) * sign(1, x) (sppt.f90:66-68, :98)
 __device__ inline double sppt_clip(double x, double lim) { return fmin(lim, fabs(x)) * copysign(1.0, x); }

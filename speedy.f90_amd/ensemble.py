@@ -27,7 +27,8 @@ model.couple_dev(day, hfluxn, shf, evap, ssrd).
 `step` is step(j1, j2, dt) of time_stepping.f90:35-121 and `startup` first_step of :12-24.  `output` gives every member's float32
 snapshot (input_output.f90:184-206) and the ensemble mean and spread from one call (include/spdy.h, "ensemble output").  SPPT:
 physics["sppt"], a Sppt with one pattern per member, is advanced and applied by `step` (include/spdy.h, "SPPT").  `analyse` is the
-LETKF update of time level 1 from a Letkf's observations (include/spdy.h, "ensemble analysis").  Not covered: the level-sharded
+LETKF update of time level 1 from a Letkf's observations (include/spdy.h, "ensemble analysis"), `verify` its scores against a
+Nature's truth (include/spdy.h, "nature run").  Not covered: the level-sharded
 step."""
 import numpy as np
 
@@ -208,6 +209,16 @@ class Ensemble:
         if letkf.nmem != self.nmem:
             raise ValueError("analyse: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
         letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0])
+
+    def verify(self, letkf, nature, slot=0):
+        """The scores of time level 1 against a Nature's truth (include/spdy.h, "nature run"): rmse and bias of the ensemble mean and
+        the spread, per variable and level, into nature.scores(slot).  Three launches, capturable; nothing of the ensemble changes.
+        letkf: a Letkf of this plan with nmem == E, whose grid workspace the call uses; nature: a Nature of this plan."""
+        if getattr(letkf, "sp", None) is not self.sp or getattr(nature, "sp", None) is not self.sp:
+            raise ValueError("verify: the Letkf and the Nature must belong to the ensemble's plan")
+        if letkf.nmem != self.nmem:
+            raise ValueError("verify: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
+        nature.verify(letkf, self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], slot)
 
     def startup(self, delt, physics=None):
         """first_step (time_stepping.f90:12-24): the forward half step, the first leapfrog step and the three initialize_implicit

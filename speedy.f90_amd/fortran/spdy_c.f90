@@ -1207,6 +1207,63 @@ module spdy_c
             type(c_ptr), value :: l, vor, div, t, q, ps
             integer(c_int) :: rc
         end function
+        ! the nature run (include/spdy.h): the truth of a twin experiment, the observation values of an analysis object's network
+        ! drawn from it, an ensemble's scores against it; the device pointers are those of time level 1
+        function spdy_nature_create(plan, seed, capacity, n) bind(C, name="spdy_nature_create") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: plan
+            integer(c_long_long), value :: seed
+            integer(c_int), value :: capacity
+            type(c_ptr), intent(out) :: n
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_destroy(n) bind(C, name="spdy_nature_destroy") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: n
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_reset(n, seed) bind(C, name="spdy_nature_reset") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: n
+            integer(c_long_long), value :: seed
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_draws(n, count) bind(C, name="spdy_nature_draws") result(rc)
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: n
+            integer(c_long_long), intent(out) :: count
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_field(n, name, d_ptr) bind(C, name="spdy_nature_field") result(rc)
+            import :: c_int, c_ptr, c_char
+            type(c_ptr), value :: n
+            character(kind=c_char), intent(in) :: name(*)
+            type(c_ptr), intent(out) :: d_ptr
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_set_state_dev(n, vor, div, t, q, ps) bind(C, name="spdy_nature_set_state_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: n, vor, div, t, q, ps
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_observe_dev(n, letkf, noise) bind(C, name="spdy_nature_observe_dev") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: n, letkf
+            real(c_double), value :: noise
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_verify_dev(n, letkf, vor, div, t, q, ps, slot) bind(C, name="spdy_nature_verify_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: n, letkf, vor, div, t, q, ps
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
+        function spdy_nature_verify_grid_dev(n, nmem, ug, vg, tg, qg, psg, slot) bind(C, name="spdy_nature_verify_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: n, ug, vg, tg, qg, psg
+            integer(c_int), value :: nmem, slot
+            integer(c_int) :: rc
+        end function
     end interface
 
     integer(c_int), parameter :: SPDY_OBS_U = 0_c_int, SPDY_OBS_V = 1_c_int, SPDY_OBS_T = 2_c_int, SPDY_OBS_Q = 3_c_int, &

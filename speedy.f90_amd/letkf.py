@@ -17,7 +17,7 @@ from .columns import DeviceField, PlanObject
 
 OBS_U, OBS_V, OBS_T, OBS_Q, OBS_PS = range(5)
 LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv", "coarse_columns", "interp_index", "interp_weight")
-LETKF_FIELDS = ("hx", "hxmean", "y", "departure", "weights")
+LETKF_FIELDS = ("hx", "hxmean", "y", "departure", "weights", "value", "grid")
 
 
 class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
@@ -104,12 +104,17 @@ class Letkf(PlanObject):
     def field(self, name):
         """A device field of the latest analysis call (LETKF_FIELDS): hx, y [nobs, nmem], hxmean, departure [nobs]; a DeviceField
         in the object's own memory, the pointers never change.  weights [ncoarse, kx, nmem, nmem]: the transforms T[f][e] of the
-        coarse columns, at a weight stride other than (1, 1) only; set_weight_stride moves it."""
+        coarse columns, at a weight stride other than (1, 1) only; set_weight_stride moves it.  value [nobs]: the observation values
+        the next analysis reads, as set_obs or Nature.observe wrote them (valid at once, not only after an analysis).  grid
+        [(4 kx + 1) nmem, il, ix]: the grid workspace, u | v | t | q (nmem kx grids each, member-major) | ps (nmem) -- the gridded
+        ensemble after Nature.verify, the increments after Ensemble.analyse."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         if name == "weights":
             ncoarse = check(self.lib.spdy_letkf_table(self.h, b"coarse_columns", None, 0))
             return DeviceField(self.sp, p.value, (ncoarse, self.sp.kx, self.nmem, self.nmem))
+        if name == "grid":
+            return DeviceField(self.sp, p.value, ((4 * self.sp.kx + 1) * self.nmem,) + self.sp.grid_shape)
         return DeviceField(self.sp, p.value, (self.nobs, self.nmem) if name in ("hx", "y") else (self.nobs,))
 
     def fields(self):

@@ -40,6 +40,14 @@ the local problems on the coarse columns, then the kernel that interpolates thei
 the number of coarse columns and the byte count of that kernel's reads -- per grid column and level one E x E transform per
 stencil entry of non-zero weight, and the members' values -- to set against its time from a kernel trace.
 
+--osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
+to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
+three launches; (b) the captured Ensemble.verify -- the inverse batch of all members and the two score launches; (c) the host route
+to the same values that a build without the nature run offers, wall-clock with its synchronisations: the single-state output call,
+the download of its float32 grids, the operator and the noise in vectorised NumPy on the stencils the Letkf already holds, and
+Letkf.set_obs (median of --repeats calls after one warm-up).  The rows of (a) and (b) give their share of the cycle {36 steps,
+analysis}; the row of (c) its ratio to (a).
+
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
     python tools/ensemble_rate.py --coupled --members 1 2 4 8 16
@@ -47,6 +55,7 @@ stencil entry of non-zero weight, and the members' values -- to set against its 
     python tools/ensemble_rate.py --sppt --json profiles/ensemble_sppt_rate.json
     python tools/ensemble_rate.py --letkf --json profiles/ensemble_letkf_rate.json
     python tools/ensemble_rate.py --letkf --stride 2 2
+    python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
 import ctypes
@@ -445,8 +454,34 @@ def run_sppt(tag, members, reps, repeats, label, rows):
     sp.close()
 
 
-def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1)):
-    """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle)"""
+def host_observations(sp, lt, tr, cols, err, repeats):
+    """the host route to a nature run's observation values, microseconds wall-clock (median, min, max): the single-state output of
+    the truth's spectra `tr`, its download, H and the noise in NumPy, Letkf.set_obs"""
+    import time
+    kx = sp.kx
+    s.check(sp.lib.spdy_output_workspace(sp.h))
+    out = [torch.empty((kx, sp.il, sp.ix), dtype=torch.float32, device="cuda") for _ in range(5)]
+    out.append(torch.empty((sp.il, sp.ix), dtype=torch.float32, device="cuda"))
+    phi = torch.zeros_like(tr[0])
+    idx, w = lt.table("stencil_index"), lt.table("stencil_weight")
+    row = np.where(cols[0] == 4, 4 * kx, cols[0] * kx + cols[1])[:, None]
+    rng = np.random.default_rng(1)
+    us = []
+    for _ in range(repeats + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sp.output_batch_dev(tr[0], tr[1], tr[2], tr[3], phi, tr[4], *out)
+        u, v, t, q, _, ps = [a.cpu().numpy().astype(np.float64) for a in out]
+        f = np.concatenate([u, v, t, q, ps[None]]).reshape(4 * kx + 1, -1)[row, idx]
+        h = ((w[:, 0] * f[:, 0] + w[:, 1] * f[:, 1]) + w[:, 2] * f[:, 2]) + w[:, 3] * f[:, 3]
+        lt.set_obs(*cols, h + err * rng.standard_normal(h.size), err)
+        us.append((time.perf_counter() - t0) * 1e6)
+    return float(np.median(us[1:])), min(us[1:]), max(us[1:])
+
+
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False):
+    """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
+    of the nature run's observe and verify, and the host route to the same observation values"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
     build()
@@ -472,7 +507,7 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1)):
     cols = [np.tile(var, nloc), np.tile(lev, nloc), np.repeat(lon.ravel(), per), np.repeat(lat.ravel(), per)]
     nobs = nloc * per
     rng = np.random.default_rng(0)
-    fns, nodes, rearms, keep, interp = {}, {}, [], [], {}
+    fns, nodes, rearms, keep, interp, host = {}, {}, [], [], {}, {}
     for E in members:
         # the members: the case's state plus a hundredth of the differences between seeded states (0.3 K in t)
         ms = ensemblestep.member_states(sp, E + 1)
@@ -505,6 +540,18 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1)):
         with sp.graph_capture() as gs:
             en.step(2, 2, dt, PE, eps=modelstep.ROB)
         fns["step E=%d physics" % E], nodes["step E=%d physics" % E] = gs.launch, gs.num_nodes()
+        if osse:                                              # the truth: member 0's state at the start
+            nat = s.Nature(sp, seed=E, capacity=2)
+            tr = [start[n][0, 0].clone() for n in modelstep.PROG]
+            with sp.graph_capture() as ga:
+                nat.set_state(*tr)
+                nat.observe(lt, 1.0)
+            with sp.graph_capture() as gb:
+                en.verify(lt, nat, 0)
+            fns["observe E=%d" % E], nodes["observe E=%d" % E] = ga.launch, ga.num_nodes()
+            fns["verify E=%d" % E], nodes["verify E=%d" % E] = gb.launch, gb.num_nodes()
+            host[E] = host_observations(sp, lt, tr, cols, spread, repeats)
+            keep.append((en, nat, PE, ga, gb))
 
         def rearm(en=en, start=start, PE=PE, E=E):
             for n, v in start.items():
@@ -521,6 +568,14 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1)):
             row.update(stride=list(stride), **interp.get(E, {}))
             cycle = 36 * t["step E=%d physics" % E][0]
             row.update(us_36_steps=round(cycle, 1), analysis_share_of_cycle=round(med / (med + cycle), 4))
+        if name.startswith(("observe", "verify")):
+            cycle = 36 * t["step E=%d physics" % E][0] + t["analysis E=%d" % E][0]
+            row.update(us_cycle=round(cycle, 1), share_of_cycle=round(med / cycle, 5))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for E, (med, lo, hi) in host.items():
+        row = {"label": label, "size": tag, "form": "host route E=%d" % E, "members": E, "observations": nobs, "us": round(med, 1),
+               "us_min": round(lo, 1), "us_max": round(hi, 1), "clock": "wall", "times_observe": round(med / t["observe E=%d" % E][0], 1)}
         rows.append(row)
         print(json.dumps(row), flush=True)
     for _, lt, _, g, gs in keep:
@@ -537,6 +592,7 @@ def main():
     ap.add_argument("--output", action="store_true")
     ap.add_argument("--sppt", action="store_true")
     ap.add_argument("--letkf", action="store_true")
+    ap.add_argument("--osse", action="store_true")
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
@@ -544,6 +600,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--json")
     a = ap.parse_args()
+    a.letkf = a.letkf or a.osse
     a.sizes = a.sizes or (["t30"] if a.sppt or a.letkf else ["t30", "t63k16"])
     a.members = a.members or ([4, 16, 32] if a.letkf else [1, 4, 16] if a.sppt else [1, 2, 4, 8, 16, 32])
     a.reps = a.reps or (100 if a.sppt or a.letkf else 200)
@@ -558,7 +615,7 @@ def main():
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
             if a.letkf:
-                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride))
+                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse)
             elif a.sppt:
                 run_sppt(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.output:

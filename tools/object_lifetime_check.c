@@ -1,8 +1,8 @@
 /* Host check of the lifetime rule of the objects made on a plan (include/spdy.h, the plan section): a surface model, an SPPT
- * pattern, a diagnostics object and an analysis object on a host-only plan, in both teardown orders; every entry point on a dead
+ * pattern, a diagnostics object, an analysis object and a nature run on a host-only plan, in both teardown orders; every entry point on a dead
  * handle; creates that fail after the object has joined its plan; and 100 create/destroy rounds on one plan.  Built by
  * `make hostcheck` in speedy.f90_amd with the address and undefined-behaviour sanitizers on the host code of the plan and of the
- * four kinds; exits 0 when every call returns the documented code, and the sanitizers' leak check sees whether an object stayed
+ * five kinds; exits 0 when every call returns the documented code, and the sanitizers' leak check sees whether an object stayed
  * on its plan. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,6 +30,7 @@ typedef struct {
     spdy_sppt *s;
     spdy_diagnostics *d, *d1;         /* NMEM members; one member, for the calls that take no member */
     spdy_letkf *l;
+    spdy_nature *n;
 } objects;
 
 static int create(spdy_plan *p, objects *o)
@@ -39,6 +40,7 @@ static int create(spdy_plan *p, objects *o)
     CHECK(spdy_ens_sppt_create(p, NMEM, 36, NULL, seeds, &o->s) == SPDY_OK);
     CHECK(spdy_ens_diagnostics_create(p, NMEM, 4, 0, &o->d) == SPDY_OK && spdy_diagnostics_create(p, 4, 0, &o->d1) == SPDY_OK);
     CHECK(spdy_letkf_create(p, NMEM, 4, &o->l) == SPDY_OK && spdy_letkf_set_localization(o->l, 1.0e6, 0.0, 1.0) == SPDY_OK);
+    CHECK(spdy_nature_create(p, 7, 2, &o->n) == SPDY_OK);
     return 0;
 }
 
@@ -46,7 +48,7 @@ static int destroy(objects *o)
 {
     CHECK(spdy_surface_model_destroy(o->m) == SPDY_OK && spdy_sppt_destroy(o->s) == SPDY_OK);
     CHECK(spdy_diagnostics_destroy(o->d) == SPDY_OK && spdy_diagnostics_destroy(o->d1) == SPDY_OK);
-    CHECK(spdy_letkf_destroy(o->l) == SPDY_OK);
+    CHECK(spdy_letkf_destroy(o->l) == SPDY_OK && spdy_nature_destroy(o->n) == SPDY_OK);
     return 0;
 }
 
@@ -102,6 +104,13 @@ static int every_call(const objects *o, int want)
     CALL(spdy_letkf_field(o->l, "hx", &ptr));
     CALL(spdy_letkf_analyse_grid_dev(o->l, q, q, q, q, q, q, q, q, q, q));
     CALL(spdy_ens_letkf_dev(o->l, q, q, q, q, q));
+    CALL(spdy_nature_reset(o->n, 7));
+    CALL(spdy_nature_draws(o->n, &a));
+    CALL(spdy_nature_field(o->n, "truth", &ptr));
+    CALL(spdy_nature_set_state_dev(o->n, q, q, q, q, q));
+    CALL(spdy_nature_observe_dev(o->n, o->l, 1.0));
+    CALL(spdy_nature_verify_dev(o->n, o->l, q, q, q, q, q, 1));
+    CALL(spdy_nature_verify_grid_dev(o->n, NMEM, q, q, q, q, q, 1));
 #undef CALL
     return bad;
 }
@@ -129,6 +138,14 @@ int main(void)
         const spdy_sfc_boundary bnd = {q, q, q, q, q, q, q};
         DEAD(spdy_ens_physics_sppt_dev(p, NMEM, o.s, 1, q, q, q, q, q, q, &bnd, q, q, q, q, q, q, NULL));
     }
+    /* a live nature run with the analysis object of the destroyed plan */
+    {
+        spdy_nature *live = NULL;
+        CHECK(spdy_nature_create(p, 7, 1, &live) == SPDY_OK);
+        DEAD(spdy_nature_observe_dev(live, o.l, 1.0));
+        DEAD(spdy_nature_verify_dev(live, o.l, fields, fields, fields, fields, fields, 0));
+        CHECK(spdy_nature_destroy(live) == SPDY_OK);
+    }
     if (destroy(&o)) return 1;
     /* creates that fail after the object has joined its plan */
     spdy_sppt *s = NULL;
@@ -144,12 +161,17 @@ int main(void)
     CHECK(spdy_sppt_members(NULL) == SPDY_ERR_ARG && !strcmp(spdy_last_error(), "null SPPT pattern"));
     CHECK(spdy_diagnostics_reset(NULL, 0) == SPDY_ERR_ARG && !strcmp(spdy_last_error(), "null diagnostics object"));
     CHECK(spdy_letkf_table(NULL, "unit", NULL, 0) == SPDY_ERR_ARG && !strcmp(spdy_last_error(), "null analysis object"));
+    CHECK(spdy_nature_reset(NULL, 7) == SPDY_ERR_ARG && !strcmp(spdy_last_error(), "null nature run"));
+    {
+        spdy_nature *n = NULL;
+        CHECK(spdy_nature_create(p, 7, 0, &n) == SPDY_ERR_ARG && !n);
+    }
     /* 100 rounds on the plan the failed creates left: an object that stayed on the plan's list would be written to at the end */
     for (int r = 0; r < 100; ++r)
         if (create(p, &o) || destroy(&o)) return 1;
     if (create(p, &o)) return 1;
     CHECK(spdy_plan_destroy(p) == SPDY_OK);
     if (every_call(&o, SPDY_ERR_STATE) || destroy(&o)) return 1;
-    printf("object lifetime check ok: 4 kinds, both teardown orders, 100 rounds\n");
+    printf("object lifetime check ok: 5 kinds, both teardown orders, 100 rounds\n");
     return 0;
 }
