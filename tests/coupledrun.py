@@ -8,15 +8,22 @@ held ssrd.  Three days (108 steps) from 30 January: over the month boundary, whe
 import numpy as np
 
 import longrun
+import modelstep
 import physstep
 import radiation
+import support
 import surface
 import surfmodel as sm
-from dynstep import ROB, oracle_dynamics_step
+import synth
+from dynstep import PROG, ROB, oracle_dynamics_step
 
 START = sm.WINDOWS["month"]
 NSTEPS = 3 * sm.NSTEPS
 CHECKPOINTS = (36, 72, 108)                       # each day's end
+SKIP_AT, LATE_AT = 5, 37          # the faults: no couple_dev after step 5; the forcing of day 2 after step 37 instead of before it
+# late_forcing moves forcing_dev behind the WHOLE of step 37 (its graph and its couple), not merely behind its physics_dev: step 37
+# alone then runs with the albedos, snowc and qcorh of day 1, one day stale, and every later step has the right ones.  The test
+# relies on that single step being noticed at the end of day 2 (step 72), 35 steps later.
 
 
 def zonal(sp, case, tyear):
@@ -73,3 +80,77 @@ def reference_run(sp, o, name):
     for n in cps:
         cps[n].update(extra[n])
     return cps, log, events
+
+
+# ------------------------------------------------------------------------------------------------ device side (torch)
+def device_run(sp, case, c, events, fault=None):
+    """The run on the device in the order of calls of DESIGN s14, as graph replays.  fault: None, "skip_couple" or "late_forcing" (SKIP_AT,
+    LATE_AT).  Returns ({n: prognostics, rad, qcorh, surf
+    at CHECKPOINTS}, node counts of the step graph without / with couple_dev)."""
+    import torch
+    s = support.package()
+    il, ix, dt = sp.il, sp.ix, longrun.DELT
+    shaped = {k: np.ascontiguousarray(v).reshape(v.shape[:-1] + (il, ix)) for k, v in c.items()}
+    M = s.SurfaceModel(sp, shaped, sm.DELT)
+    D, W = modelstep.device_state(case.st), modelstep.Workspace(sp)
+    out = sp.column_outputs(1, ("sfc", "rad"), names=("hfluxn", "shf", "evap", "ssrd"))
+    F = dict(out["sfc"], **out["rad"])
+    bnd, albsfc = M.boundary()
+    P = {"bnd": dict(bnd, albsfc=albsfc), "rad": modelstep.radiation_state(sp)}
+    phys = lambda sw: modelstep.whole_physics(P, sw, out)
+    torch.cuda.synchronize()
+    date = sm.Date(*START)
+    M.set_date(date.imont1, date.tmonth, date.tyear)
+    M.couple_dev(0)                                           # initialize_coupler
+    M.forcing_dev(D["qcorh"])                                 # set_forcing(0)
+    modelstep.startup(sp, dt, lambda j1, j2, dt_, n: modelstep.step(sp, D, W, dt_, j1, j2, 0.0, phys(physstep.shortwave_step(n))))
+    couple = lambda: M.couple_dev(1, F["hfluxn"], F["shf"], F["evap"], F["ssrd"])     # day only tells 0 from > 0
+    graphs = {}
+    for sw in (True, False):
+        for last in (False, True):
+            with sp.graph_capture() as g:
+                modelstep.step(sp, D, W, 2.0 * dt, physics=phys(sw))
+                if last:
+                    couple()
+            graphs[sw, last] = g
+    nodes = {k: g.num_nodes() for k, g in graphs.items()}
+    res = {}
+    for n in range(1, NSTEPS + 1):
+        sw = physstep.shortwave_step(n)
+        first = (n - 1) % sm.NSTEPS == 0
+        if first and not (fault == "late_forcing" and n == LATE_AT):
+            M.forcing_dev(D["qcorh"])
+        (imont1, tmonth, tyear), new_day, sstan3 = events[n]
+        if sstan3 is not None:                                # obs_ssta ran: the window the couple of this step reads
+            M.set_sst_anomaly(sstan3.reshape(3, il, ix))
+        if fault == "skip_couple" and n == SKIP_AT:
+            graphs[sw, False].launch()
+        elif new_day:                                         # the date changes between the step and its couple
+            graphs[sw, False].launch()
+            M.set_date(imont1, tmonth, tyear)
+            couple()
+        else:
+            graphs[sw, True].launch()
+        if fault == "late_forcing" and n == LATE_AT:
+            M.forcing_dev(D["qcorh"])
+        if n in CHECKPOINTS:
+            sp.synchronize()
+            res[n] = dict({k: D[k].clone() for k in PROG}, rad=P["rad"].clone(), qcorh=D["qcorh"].clone(),
+                          surf={k: M.field(k).numpy().reshape(-1) for k in sm.FIELDS + sm.FORCING})
+            torch.cuda.synchronize()
+    for g in graphs.values():
+        g.close()
+    M.close()
+    return res, nodes
+
+
+def errors(got, ref, ncol):
+    """physstep.checkpoint_errors plus qcorh and every field of the surface model (an all-zero reference field: the absolute error)"""
+    e = physstep.checkpoint_errors(got, ref, ncol)
+    e["qcorh"] = synth.relerr(got["qcorh"].cpu().numpy(), ref["qcorh"])
+    for k, v in ref["surf"].items():
+        x = got["surf"][k]
+        assert np.all(np.isfinite(x)), "%s of the surface model is not finite at the checkpoint" % k
+        s = np.abs(v).max()
+        e[k] = float(np.abs(x - v).max() / s) if s > 0 else float(np.abs(x).max())
+    return e

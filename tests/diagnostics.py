@@ -7,6 +7,8 @@ reference by tests/golden/ref_diagnostics.npz (tests/golden/make_golden_diagnost
 reference's: a spectrum (mx,nx,kx) is [kx, nx, mx], diag(kx,3) is [3, kx]."""
 import numpy as np
 
+import dynstep
+
 SQRT_HALF = float(np.sqrt(np.float32(0.5)))            # 0.707106769084930419921875
 LIMITS = (500.0, 500.0, 180.0, 320.0)                  # reke, deke, temp low, temp high (diagnostics.f90:61-62)
 REKE, DEKE, TEMP_LOW, TEMP_HIGH, NONFINITE = 1, 2, 4, 8, 16
@@ -64,3 +66,10 @@ def lines(step, d):
         out.append(head + "".join(f[:10]))
         out.extend("".join(f[j:j + 10]) for j in range(10, len(f), 10))
     return "".join(l + "\n" for l in out)
+
+
+def state(sp, seed):
+    """time level 2 of the seeded model state: vor, div, t [kx, nx, mx], the winds scaled down into the accepted range (the seeded
+    state's own reke is of order 1e4)"""
+    st = dynstep.state(sp, seed)
+    return {n: np.ascontiguousarray(st[n][1]) * f for n, f in (("vor", 1e-2), ("div", 1e-1), ("t", 1.0))}

@@ -2,13 +2,15 @@
 model state it runs on.  Shared by the GPU step tests, the Fortran drop-in test and the golden-vector generator.  Pinned bit for
 bit to the flang-built reference (time_stepping.f90 unchanged on tendencies.f90 minus its three physics lines):
 tests/test_oracle_golden.py::test_dynamics_step_pinned."""
+import os
+
 import numpy as np
 
 import synth
 
 ROB, WIL = float(np.float32(0.05)), float(np.float32(0.53))          # params.f90:32-33 (float32 literals widened)
 SDRAG = 1.0 / (float(np.float32(24.0 * 30.0)) * 3600.0)              # time_stepping.f90:77, dynamical_constants.f90:22
-
+PROG = ("vor", "div", "t", "tr", "ps")                                # the prognostics of state(), both time levels each
 
 
 def state(sp, seed):
@@ -72,3 +74,19 @@ def wave_relerr(x, ref):
     x[..., 0, 0] = 0.0
     ref[..., 0, 0] = 0.0
     return synth.relerr(x, ref)
+
+
+# ---- spdy_step_fields against the reference's own step_field_3d / step_field_2d: the cases of tests/golden/ref_step.npz
+# tag -> the part of the 3-D arrays the fixture keeps (None: all of it, but see STEP_J1_SUB)
+STEP_CASES = {"t30": None, "t30k5": (slice(None), slice(None, None, 2), slice(None, None, 2)),
+              "t63k16": (slice(None), slice(None, None, 5), slice(None, None, 3))}
+STEP_J1_SUB = (slice(None), slice(None, None, 2), slice(None, None, 2))     # T30 L8, j1 = 1 (tests/golden/make_golden.py)
+
+
+def step_golden():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_step.npz"))
+
+
+def step_inputs(kx, nx, mx):
+    return (synth.cfield((2, kx, nx, mx), 11), synth.cfield((kx, nx, mx), 12, 1e-4),
+            synth.cfield((2, nx, mx), 13), synth.cfield((nx, mx), 14, 1e-4))

@@ -49,11 +49,6 @@ def ulps(a, b):
     return int(np.max(np.abs(ordered(a) - ordered(b))))
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and bool(np.array_equal(a.view(np.int32), b.view(np.int32)))
-
-
 def within(dev, ref, scale, contract=1e-12):
     """(b)'s bound: |device - float32(ref)| <= contract * max|x| + one float32 ulp of the reference value, compared in FP64.
     -> the largest excess over the bound (<= 0: met)"""

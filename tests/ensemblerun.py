@@ -5,6 +5,7 @@ through the single-state step (modelstep.step), a single SurfaceModel and a sing
 import numpy as np
 
 import longrun
+import support
 import surfmodel as sm
 
 FLUXES = ("hfluxn", "shf", "evap", "ssrd")
@@ -160,10 +161,10 @@ def member_differences(es, snaps, rows, e, ref_snaps, ref_rows, size):
     bad = []
     for n, (got, want) in enumerate(zip(snaps, ref_snaps)):
         m = es.member_of(got, e)
-        bad += [(n, k) for k in es.COMPARED if not es.same_bits(m[k], want[k])]
-        if not es.same_bits(got["rad"][e * size:(e + 1) * size], want["rad"]):
+        bad += [(n, k) for k in es.COMPARED if not support.same_bits(m[k], want[k])]
+        if not support.same_bits(got["rad"][e * size:(e + 1) * size], want["rad"]):
             bad.append((n, "rad"))
-        if not es.same_bits(got["qcorh"][e], want["qcorh"]):
+        if not support.same_bits(got["qcorh"][e], want["qcorh"]):
             bad.append((n, "qcorh"))
         E = got["qcorh"].shape[0]
         for k in SURF:

@@ -2,8 +2,8 @@
 members' layout, the single objects every member is compared with, and a stand-in that leaves an advance out of a step."""
 import numpy as np
 
-import poison
 import sppt
+import support
 
 SEED = 0x5EED0123456789AB
 FIELDS = ("eta", "spec", "pattern")
@@ -43,7 +43,7 @@ def singles(sp, seed_list, mu=None):
 def differing(got, e, one):
     """the fields where member e of the ensemble object's copies `got` is not bit-equal to the single object `one`"""
     want = fields(one)
-    return [n for n in FIELDS if not poison.same_bits(got[n][e], want[n][0])]
+    return [n for n in FIELDS if not support.same_bits(got[n][e], want[n][0])]
 
 
 def injected(nmem, d, shp, scale=4.0, base=SEED + 7):

@@ -3,7 +3,11 @@ about addressing), the ensemble built from them, a member's part of an ensemble 
 single-state run (modelstep.step) that every member is compared with."""
 import numpy as np
 
+import levels
 import modelstep
+import moist
+import physstep
+import support
 from dynstep import ROB
 from dynstep import state as dyn_state
 
@@ -11,6 +15,12 @@ PROG = ("vor", "div", "t", "tr", "ps")
 COMPARED = PROG + ("phi", "U", "V", "PL")
 LEAPFROG = ((2, 2, 1.0), (2, 2, 1.0))        # (j1, j2, dt / delt): two consecutive leapfrog steps ...
 STARTUP = ((1, 1, 0.5), (1, 2, 1.0))         # ... and the start-up pair of first_step (time_stepping.f90:12-24)
+TAGS = {8: "t30", 5: "t30k5", 7: "t30k7"}    # kx -> the variant with the reference's own half levels
+
+
+def plan_of_levels(kx, nmem):
+    """the T30 plan of kx levels for nmem members: the reference's own sets (TAGS), any other count on tests/levels.py's half levels"""
+    return support.ensemble_plan(TAGS[kx], nmem) if kx in TAGS else levels.plan("t30", kx, nmem * (4 * kx + 4))
 
 
 def member_states(sp, nmem, seed=8000):
@@ -57,16 +67,6 @@ def single_snapshot(D, W):
     return out
 
 
-def same_bits(a, b):
-    """bit for bit, NaN payloads included"""
-    import torch
-    if a.shape != b.shape:
-        return False
-    if a.is_complex():
-        a, b = torch.view_as_real(a.contiguous()), torch.view_as_real(b.contiguous())
-    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-
-
 def run_ensemble(sp, ens, seq, delt, eps=ROB, physics=None):
     """the steps of seq (initialize_implicit before each, as first_step does) on the ensemble; returns the snapshot after each"""
     snaps = []
@@ -95,10 +95,35 @@ def differing(sp, ens_snaps, e, st, seq, delt, eps=ROB, names=COMPARED):
     bad = []
     for n, (got, want) in enumerate(zip(ens_snaps, run_single(sp, st, seq, delt, eps))):
         m = member_of(got, e)
-        bad += [(n, k) for k in names if not same_bits(m[k], want[k])]
+        bad += [(n, k) for k in names if not support.same_bits(m[k], want[k])]
     return bad
 
 
 def relerr(a, b):
     a, b = a.cpu().numpy(), b.cpu().numpy()
     return float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
+
+
+def physics_members(sp, o, E, hsg=None, seeds=None):
+    """E physically shaped states over member 0's orography, per-member boundary fields; member 0 is physstep's own case.  hsg,
+    seeds: the half levels of sp and o and the case's seeds at a count of tests/levels.py"""
+    d0, m0, b0 = seeds = physstep.SEEDS["t30"] if seeds is None else seeds
+    case = physstep.Case("t30", sp, o, hsg=hsg, seeds=seeds)
+    sts, bnds = [case.st], [case.bnd]
+    for e in range(1, E):
+        st = moist.state(o, dyn_state(sp, d0 + 1000 * e), m0 + 10 * e)
+        for n in ("phis", "tcorh", "qcorh"):
+            st[n] = case.st[n]
+        sts.append(st)
+        bnds.append(physstep.draw_boundary(physstep.grids_of(o, st)["tg"][-1].reshape(-1), b0 + 100 * e))
+    sp.surface_set_orography(case.phis0)
+    return sts, bnds
+
+
+def ens_physics(sp, bnds):
+    """the ensemble's physics dict: every boundary field (E, il, ix), E radiation states back to back"""
+    import torch
+    dev = [physstep.device_boundary(b, sp.il, sp.ix) for b in bnds]
+    bnd = {n: torch.cat([d[n] for d in dev]) for n in dev[0]}
+    rad = torch.full((len(bnds) * sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
+    return {"bnd": bnd, "albsfc": bnd["albsfc"], "rad": rad}

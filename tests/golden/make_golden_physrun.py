@@ -39,9 +39,9 @@ import make_golden_moist as mg  # noqa: E402
 import make_golden_radiation as mr  # noqa: E402
 import make_golden_surface as ms  # noqa: E402
 import longrun  # noqa: E402
-import moist  # noqa: E402
 import physstep  # noqa: E402
 import radiation  # noqa: E402
+import support  # noqa: E402
 import surface  # noqa: E402
 from dynstep import ROB, oracle_dynamics_step  # noqa: E402
 
@@ -93,10 +93,10 @@ def run(lib):
     from oracle.pyoracle import Oracle, build
     from conftest import VARIANTS
     build()
-    ix, il, kx = moist.VARIANTS[TAG]
+    ix, il, kx = support.grid(TAG)
     ncol = il * ix
     o = Oracle(*VARIANTS[TAG])
-    sp = moist.plan(TAG, 4 * kx + 4, device=-1)
+    sp = support.plan(TAG, 4 * kx + 4, device=-1)
     case = physstep.run_case(sp, o, "wind")
     tab = case.tab
     # the reference's own initialisation, as in make_golden_surface.run

@@ -7,6 +7,8 @@ Arrays are C-order views of the library's: a gridded ensemble is {"u", "v", "t",
 observation set is a dict of equal-length arrays var, lev, lon, lat, value, error."""
 import numpy as np
 
+import support
+
 U, V, T, Q, PS = range(5)
 VARS = ("u", "v", "t", "q", "ps")
 REARTH = 6.371e6
@@ -326,3 +328,58 @@ def columns_for(g, obs, sigma_h, most=48, outside=16, seed=11):
         inside = np.concatenate([inside[:most // 2], inside[-(most // 4):], rng.choice(inside[most // 2:-(most // 4)], most // 4, False)])
     out = np.nonzero(dmin >= 2.0 * sigma_h * np.sqrt(10.0 / 3.0))[0]
     return np.concatenate([inside, rng.choice(out, min(outside, len(out)), False)]).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ what the GPU tests share
+SIGMA_H, RHO = 5.0e5, 1.1
+C_H = SIGMA_H * np.sqrt(10.0 / 3.0)
+
+
+def make(sp, E, obs, sigma_v=0.0, rho=RHO, sigma_h=SIGMA_H):
+    """the analysis object of E members with the observations obs set"""
+    import speedy_f90_amd as s
+    lt = s.Letkf(sp, E, max(len(obs["var"]), 1), sigma_h, sigma_v, rho)
+    lt.set_obs(*args(obs))
+    return lt
+
+
+def analyse_grid(sp, lt, x):
+    """Letkf.analyse_grid on the gridded ensemble x (NumPy) -> the increments as NumPy arrays"""
+    import torch
+    out = lt.analyse_grid(*[support.dev(x[v]) for v in VARS])
+    torch.cuda.synchronize()
+    return {v: a.cpu().numpy() for v, a in zip(VARS, out)}
+
+
+def limits(g, x, C, b, rho, cols, E):
+    """per variable max(16 x the difference of the restatement's two routes on these inputs, 64 E eps max|x - mean|), the eigh
+    route's increments and the largest condition number"""
+    a, kappa = increments(g, x, C, b, rho, "eigh", cols)
+    j, _ = increments(g, x, C, b, rho, "jacobi", cols)
+    sc = perturbation_scale(x)
+    return {v: max(16 * float(np.max(np.abs(a[v] - j[v]))), 64 * E * EPS * sc[v]) for v in VARS}, a, kappa
+
+
+def oracle_grids(o, sts):
+    """time level 1 of the member states on the grid by the oracle's transforms: true wind, t, q, ps"""
+    x = {v: [] for v in VARS}
+    for st in sts:
+        uv = [o.uvspec(st["vor"][0, k], st["div"][0, k]) for k in range(o.kx)]
+        x["u"].append(np.stack([o.spec_to_grid(a, 2) for a, _ in uv]))
+        x["v"].append(np.stack([o.spec_to_grid(b, 2) for _, b in uv]))
+        x["t"].append(np.stack([o.spec_to_grid(st["t"][0, k], 1) for k in range(o.kx)]))
+        x["q"].append(np.stack([o.spec_to_grid(st["tr"][0, k], 1) for k in range(o.kx)]))
+        x["ps"].append(o.spec_to_grid(st["ps"][0], 1))
+    return {v: np.stack(a) for v, a in x.items()}
+
+
+def spread_obs(g, x, n, seed):
+    """n observations over the globe (the operator's edge points first), each with half the members' spread at its place as error"""
+    rng = np.random.default_rng(seed)
+    pts = (edge_points(g) + [(float(rng.uniform(0, 360)), float(rng.uniform(-85, 85))) for _ in range(n)])[:n]
+    obs = make_obs([o % 5 for o in range(n)], [(3 * o) % g.kx for o in range(n)], [p[0] for p in pts], [p[1] for p in pts],
+                   np.zeros(n), np.ones(n))
+    hx, _, _, _ = obs_space(g, x, obs)
+    obs["error"] = 0.5 * hx.std(axis=1, ddof=1) + 1e-300
+    obs["value"] = hx[:, 0] + obs["error"] * rng.standard_normal(n)
+    return obs

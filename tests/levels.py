@@ -16,8 +16,9 @@ LEVELS: 1 (kx - 1 = 0 clamps, kxp = 2, a 16-thread block), 2 (the recurrence row
 one level), 22 (first count above 64 KiB of LDS), 32 (the maximum: two full passes, 96 KiB)."""
 import numpy as np
 
+from conftest import VARIANTS
+
 LEVELS = (1, 2, 4, 6, 9, 12, 15, 17, 22, 32)
-RES = {"t30": (30, 96, 24), "t63": (63, 192, 48)}
 
 _oracles = {}
 
@@ -34,7 +35,7 @@ def sigma(kx):
 def plan(trunc_tag, kx, max_batch, device=0):
     """a plan of kx levels on sigma(kx); device = -1: a host plan (tables only)"""
     import speedy_f90_amd as s
-    sp = s.Spectral(RES[trunc_tag], kx=kx, max_batch=max_batch, device=device)
+    sp = s.Spectral(VARIANTS[trunc_tag][:3], kx=kx, max_batch=max_batch, device=device)
     sp.set_sigma(sigma(kx))
     return sp
 
@@ -45,7 +46,7 @@ def oracle(trunc_tag, kx):
     if key not in _oracles:
         from oracle.pyoracle import Oracle, build
         build()
-        o = Oracle(*RES[trunc_tag], kx)
+        o = Oracle(*VARIANTS[trunc_tag][:3], kx)
         o.set_sigma(sigma(kx))
         _oracles[key] = o
     return _oracles[key]

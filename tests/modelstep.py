@@ -5,12 +5,11 @@ A step is step(j1, j2, dt) of time_stepping.f90:35-121: the inverse batch with g
 (tendencies.f90:89-197), optionally the geopotential and the physics (tendencies.f90:203-206), the direct batch with the spectral
 step.  bench.py keeps its own two copies of this sequence on purpose: the benchmark is the yardstick and depends on no test helper,
 so it is not a call site of this module."""
-import moist
 import physstep
-from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, wave_relerr
+import support
+from dynstep import PROG, ROB, SDRAG, WIL, oracle_dynamics_step, wave_relerr
 from dynstep import state as dyn_state
 
-PROG = ("vor", "div", "t", "tr", "ps")
 FORMS = ("composite", "one_launch", "separate")
 
 
@@ -39,7 +38,7 @@ class Workspace:
 
 def device_state(st):
     """the state dict on the device"""
-    return {n: moist.dev(st[n]) for n in st}
+    return {n: support.dev(st[n]) for n in st}
 
 
 def radiation_state(sp, fill=float("nan")):

@@ -7,7 +7,6 @@ Arrays are NumPy C-order views of the reference's column-major ones: a level sta
 works on [kx, ncol] (any number of columns), vectorised over columns and looping over k as the reference does.  Default-real
 literals of the reference are float32 values widened to double: f32(x) below."""
 import contextlib
-import os
 
 import numpy as np
 
@@ -31,34 +30,6 @@ HSG = {5: np.array([0.000, 0.150, 0.350, 0.650, 0.900, 1.000], np.float32).astyp
        7: np.array([0.020, 0.140, 0.260, 0.420, 0.600, 0.770, 0.900, 1.000], np.float32).astype(np.float64),
        8: np.array([0.000, 0.050, 0.140, 0.260, 0.420, 0.600, 0.770, 0.900, 1.000], np.float32).astype(np.float64),
        16: synth.SIGMA_L16}
-# fixture variants: tag -> (ix, il, kx); the plans of the physics tests: tag -> (resolution, kx)
-VARIANTS = {"t30": (96, 48, 8), "t30k5": (96, 48, 5), "t30k7": (96, 48, 7), "t63k16": (192, 96, 16)}
-RES = {"t30": ("t30", 8), "t30k5": ("t30", 5), "t30k7": ("t30", 7), "t63k16": ("t63", 16)}
-
-
-def package():
-    """speedy_f90_amd, with libspdy.so built if it is not there yet"""
-    import speedy_f90_amd as s
-    if not os.path.exists(s.LIB_PATH):
-        s.build()
-    return s
-
-
-def plan(tag, max_batch=64, device=0):
-    """the plan of the variant tag (device -1: host-only), with the sigma levels of tests/synth.py at kx = 16"""
-    import speedy_f90_amd as s
-    res, kx = RES[tag]
-    sp = s.Spectral(res, kx=kx, max_batch=max_batch, device=device)
-    if kx == 16:
-        sp.set_sigma(synth.SIGMA_L16)
-    return sp
-
-
-def dev(a, dtype=None):
-    """a NumPy array as a CUDA tensor (optionally converted to dtype)"""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
 
 
 def tables(hsg):

@@ -1,4 +1,4 @@
-"""Level counts of the column physics outside moist.RES: one count per class of the column kernels' two instantiations
+"""Level counts of the column physics outside support.PHYSICS_TAGS: one count per class of the column kernels' two instantiations
 (csrc/spdy_columns.hpp launch_columns: <8> for kx <= 8, <16> for kx <= 16), on tests/levels.py's half levels at T30.
 
     kx     instantiation   what the count is
@@ -8,10 +8,11 @@
     12     <16>            the middle of the class, even
     15     <16>            one short of full: a single unused level
 
-moist.RES has 5, 7, 8 (<8>) and 16 (<16> with k < kx the same as k < KMAX).  The variants here are named "t30k<kx>"; they are not in
-moist.RES or conftest.VARIANTS, and their fixture is tests/golden/ref_physlevels.npz (tests/golden/make_golden_physlevels.py)."""
+support.PHYSICS_TAGS has 5, 7, 8 (<8>) and 16 (<16> with k < kx the same as k < KMAX).  The variants here are named "t30k<kx>"; they are not in
+conftest.VARIANTS, and their fixture is tests/golden/ref_physlevels.npz (tests/golden/make_golden_physlevels.py)."""
 import levels
 import moist
+import support
 
 COUNTS = (6, 9, 12, 15)
 TAGS = tuple("t30k%d" % kx for kx in COUNTS)
@@ -52,9 +53,14 @@ def plan(kx, max_batch=64, device=0):
 
 
 def variant(tag):
-    """(ix, il, kx, half levels, the reference has its own set) of a tag of moist.VARIANTS or of TAGS"""
+    """(ix, il, kx, half levels, the reference has its own set) of a tag of support.PHYSICS_TAGS or of TAGS"""
     if tag in TAGS:
         kx = kx_of(tag)
         return IX, IL, kx, hsg(kx), False
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     return ix, il, kx, moist.HSG[kx], kx != 16
+
+
+def levels_case(kx, max_batch=None):
+    """(plan, oracle, half levels, physstep.Case seeds) of a count of CASE_SEEDS: what physstep.plan_case takes as levels_case"""
+    return plan(kx, max_batch or 4 * kx + 4), levels.oracle("t30", kx), hsg(kx), CASE_SEEDS[kx]

@@ -14,9 +14,11 @@ import numpy as np
 import longrun
 import moist
 import radiation
+import support
 import surface
 import synth
-from dynstep import ROB, oracle_dynamics_step
+from conftest import TOL, VARIANTS
+from dynstep import PROG, ROB, oracle_dynamics_step, wave_relerr
 from dynstep import state as dyn_state
 
 MIN_MARGIN = surface.MIN_MARGIN
@@ -248,4 +250,144 @@ def flat_outs(out):
 
 
 def device_boundary(bnd, il, ix):
-    return {n: moist.dev(np.ascontiguousarray(v).reshape(1, il, ix)) for n, v in bnd.items()}
+    return {n: support.dev(np.ascontiguousarray(v).reshape(1, il, ix)) for n, v in bnd.items()}
+
+
+TEND = ("utend", "vtend", "ttend", "qtend")
+KX = 8                    # the level count of the two-day and three-day runs (T30 L8)
+
+
+def plan_case(tag, oracle_factory, levels_case=None):
+    """(plan, oracle, Case, kx) of the tests that run the physics from spectra.  levels_case: (sp, o, half levels, Case seeds) of a
+    count outside conftest.VARIANTS (tests/levels.py)"""
+    if levels_case is None:
+        kx = VARIANTS[tag][3]
+        sp, o = support.plan(tag, 4 * kx + 4), oracle_factory(tag)
+        case = Case(tag, sp, o)
+    else:
+        sp, o, hsg, seeds = levels_case
+        kx, case = sp.kx, Case(tag, sp, o, hsg=hsg, seeds=seeds)
+    sp.surface_set_orography(case.phis0)
+    return sp, o, case, kx
+
+
+def errors(out, exp, errs, label):
+    """every optional output against the reference: integers identical; the floats' relative errors into errs"""
+    got, want = flat_outs(out), flat_outs(exp)
+    for n, w in want.items():
+        g = got[n].cpu().numpy()[0]
+        if g.dtype == np.int32:
+            assert np.array_equal(g, w.astype(np.int32)), "%s: the device's %s is not the reference's (integers)" % (label, n)
+        else:
+            errs["%s %s" % (label, n)] = synth.relerr(g, w)
+
+
+def check_physics_from_spectra(tag, sp, o, case, kx):
+    """spdy_physics_dev on a shortwave call and a call without shortwave on the held state, on a plan, its oracle and their Case: the
+    four tendencies, every optional output of every block and the radiation state against the reference within TOL, integers
+    identical; returns the worst (array, error)"""
+    import torch
+    il, ix = sp.il, sp.ix
+    st = case.st
+    phi = o.geopotential(st["t"][0], st["phis"])
+    spec = [support.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])]
+    bnd = device_boundary(case.bnd, il, ix)
+    S = torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
+    rs, errs = {}, {}
+    for step, sw in ((1, True), (2, False)):
+        t0 = [synth.splitmix64(70 + 4 * step + i, kx * il * ix).reshape(kx, il, ix) * s for i, s in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
+        ref_t = [a.copy() for a in t0]
+        r = case.physics(st, sw, rs, *ref_t)
+        if step == 1:
+            check_coverage(r, tag)
+        margin = float(r["margin"].min())
+        assert margin >= MIN_MARGIN, "%s step %d: smallest decision margin %.3e below MIN_MARGIN %.1e" % (tag, step, margin, MIN_MARGIN)
+        T, out = [support.dev(a) for a in t0], sp.column_outputs(1)
+        if sw:
+            ssrd = out["rad"]["ssrd"]
+        else:                          # ssrd stays where the shortwave call put it (include/spdy.h)
+            out["rad"]["ssrd"] = ssrd
+        sp.physics_dev(sw, *spec, bnd, bnd["albsfc"], S, *T, out)
+        torch.cuda.synchronize()
+        for n, a, b in zip(TEND, T, ref_t):
+            errs["step %d %s" % (step, n)] = synth.relerr(a.cpu().numpy(), b)
+        exp = expected(r, kx, il, ix)
+        if not sw:                     # written by shortwave calls only: the device leaves them as they were
+            for n in ("cloudc", "clstr", "icltop", "ssrd", "ssr", "tsr", "tt_rsw"):
+                exp["rad"].pop(n, None)
+        errors(out, exp, errs, "step %d" % step)
+        errs["step %d radiation state" % step] = synth.relerr(S.cpu().numpy().reshape(6 * kx + 7, il * ix), rad_state_array(rs, kx))
+    top = sorted(errs.items(), key=lambda kv: -kv[1])
+    print("\n[physics from spectra %s] %d arrays, worst %.1e; largest: %s" % (tag, len(errs), top[0][1],
+                                                                             ", ".join("%s %.1e" % kv for kv in top[:8])))
+    assert top[0][1] <= TOL, "%s: %s differs from the reference by %.3e, above TOL %.1e" % (tag, top[0][0], top[0][1], TOL)
+    sp.close()
+    return top[0]
+
+
+def gridded(tag, nb, seed, plan=None, keep=None):
+    """nb gridded states of surface.columns with the plan that holds their date and orography.  plan: (sp, its half levels) of a
+    count outside support.PHYSICS_TAGS (tests/levels.py), used in place of the plan of tag.  keep: a dict that receives the reference
+    side of the states (tab, zon, sqcoa, and the columns c1, c2 of the two calls)"""
+    if plan is None:
+        ix, il, kx = support.grid(tag)
+        sp, hsg = support.plan(tag, 64), moist.HSG[kx]
+    else:
+        sp, hsg = plan
+        ix, il, kx = sp.ix, sp.il, sp.kx
+    sp.radiation_set_date(radiation.DATES[0])
+    tab = moist.tables(hsg)
+    zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, nb, il, ix)
+    sqcoa = surface.sqcoa_columns(sp.table("coa_half"), nb, il, ix)
+    c = surface.columns(tab, nb * il * ix, seed, zon, sqcoa)
+    ph = c["phis0"].reshape(nb, il * ix)
+    ph[:] = ph[0]
+    sp.surface_set_orography(ph[0].reshape(il, ix))
+    G = lambda a: support.dev(radiation.grids(a, nb, il, ix))
+    c2 = dict(c, tg=c["tg2"], ug=c["vg"], vg=c["ug"], sst=c["sst"] + 0.5, stl=c["stl"] - 0.5, ttend=c["ttend2"])
+    names = ("ug", "vg", "tg", "qg", "phig", "pslg", "albsfc") + TEND + surface.BOUNDARY
+    if keep is not None:
+        keep.update(tab=tab, zon=zon, sqcoa=sqcoa, c1=c, c2=c2)
+    return sp, kx, il, ix, {n: G(c[n]) for n in names}, {n: G(c2[n]) for n in names}
+
+
+def run_gridded(sp, nb, kx, il, ix, d1, d2, with_out):
+    """a shortwave call, then a call without shortwave on the held state; returns everything written, by name"""
+    import torch
+    S = torch.full((nb * sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
+    res = {"state": S}
+    for i, d, sw in ((1, d1, True), (2, d2, False)):
+        T = [d[n].clone() for n in TEND]
+        out = sp.column_outputs(nb) if with_out else None
+        if with_out and i == 2:        # ssrd stays where the shortwave call put it (include/spdy.h)
+            out["rad"]["ssrd"] = res["out1.rad.ssrd"]
+        sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T, out)
+        res.update({"%s%d" % (n, i): t for n, t in zip(TEND, T)})
+        if with_out:
+            res.update({"out%d.%s" % (i, n): t for n, t in flat_outs(out).items()})
+        if i == 1:
+            torch.cuda.synchronize()
+            res["state1"] = S.clone()
+    torch.cuda.synchronize()
+    return res
+
+
+def rad_errors(got, ref):
+    """got, ref [6 KX + 7, ncol]: the relative error of each part of the radiation state (tt_rsw is 1e-7 of the fluxes' size: one
+    norm over the whole array would not see it)"""
+    assert np.all(np.isfinite(got)), "radiation state not finite"
+    return {n: synth.relerr(got[r], ref[r]) for n, r in rad_state_rows(KX).items()}
+
+
+def checkpoint_errors(got, ref, ncol):
+    """got: device tensors, ref: arrays, of one checkpoint -> {name: relative error, the larger of the plain and the mean-free norm}"""
+    e = {}
+    for k in PROG:
+        g = got[k].cpu().numpy()
+        assert np.all(np.isfinite(g.real)) and np.all(np.isfinite(g.imag)), "%s of the checkpoint is not finite" % k
+        e[k] = max(synth.relerr(g, ref[k]), wave_relerr(g, ref[k]))
+    rad = rad_errors(got["rad"].cpu().numpy().reshape(-1, ncol), ref["rad"])
+    e["rad"] = max(rad.values())
+    assert all(v == v for v in list(e.values()) + list(rad.values())), (          # max() drops a NaN
+        "a relative error of the checkpoint is NaN", e, rad)
+    return e

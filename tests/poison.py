@@ -77,21 +77,6 @@ def reached(x, kind):
     return float(r.abs().max() if _is_torch(r) else np.abs(r).max()) >= HUGE
 
 
-def same_bits(a, b):
-    """bit for bit, NaN payloads and signs of zero included; integers identical (tensors or NumPy arrays)"""
-    if _is_torch(a):
-        import torch
-        if a.shape != b.shape or a.dtype != b.dtype:
-            return False
-        if not a.dtype.is_floating_point and not a.is_complex():
-            return torch.equal(a, b)
-        a, b = _real(a).contiguous(), _real(b).contiguous()
-        bits = {4: torch.int32, 8: torch.int64}[a.element_size()]
-        return torch.equal(a.view(bits), b.view(bits))
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def dead_mask(nx, mx, trunc):
     """[nx, mx] True where l = n + m' > trunc + 1: the entries the inverse transform never reads (legendre.f90:93)"""
     return np.add.outer(np.arange(nx), np.arange(mx)) > trunc + 1

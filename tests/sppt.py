@@ -99,3 +99,10 @@ def apply(tend, tend_dyn, pattern, mu):
     """physics.f90:212-221 on [kx, ...] arrays"""
     mu = np.asarray(mu, np.float64).reshape((-1,) + (1,) * (tend.ndim - 1))
     return (1 + pattern * mu) * (tend - tend_dyn) + tend_dyn
+
+
+def mu(kx):
+    """a taper with 0, fractions and 1 in it"""
+    m = np.clip(np.linspace(-0.5, 1.5, kx), 0.0, 1.0)
+    assert m[0] == 0.0 and m[-1] == 1.0 and ((m > 0) & (m < 1)).any(), "the taper of %d levels lacks 0, a fraction or 1: %s" % (kx, m)
+    return m

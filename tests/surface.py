@@ -12,6 +12,7 @@ import numpy as np
 
 import moist
 import radiation
+import support
 import synth
 from moist import ALHC, CP, GRAV, P0, f32, get_qsat
 from radiation import EMISFC, SBC
@@ -300,3 +301,26 @@ def branch_cols(r):
     b = dict(r["sfc"]["branch_cols"])
     b.update(r["pbl"]["branch_cols"])
     return b
+
+
+# ------------------------------------------------------------------------------------------------ what the GPU tests share
+ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
+SFC_OUT = SFC_3 + ("hfluxn",) + SFC_2D
+PBL_OUT = ("ut_pbl", "vt_pbl", "tt_pbl", "qt_pbl", "utend", "vtend", "ttend", "qtend")
+
+
+def case(tag, seed, nb=1, date=0, plan=None):
+    """(plan with date and no orography yet, tables, columns, zonal and sqrt(coa) per column).  plan: (sp, its half levels) of a
+    count outside support.PHYSICS_TAGS (tests/levels.py), used in place of the plan of tag"""
+    if plan is None:
+        ix, il, kx = support.grid(tag)
+        sp, hsg = support.plan(tag, 64), moist.HSG[kx]
+    else:
+        sp, hsg = plan
+        ix, il = sp.ix, sp.il
+    sp.radiation_set_date(radiation.DATES[date])
+    tab = moist.tables(hsg)
+    zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, nb, il, ix)
+    sqcoa = sqcoa_columns(sp.table("coa_half"), nb, il, ix)
+    c = columns(tab, nb * il * ix, seed, zon, sqcoa)
+    return sp, tab, c, zon, sqcoa

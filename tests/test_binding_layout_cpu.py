@@ -3,16 +3,15 @@ that cross the C-ABI; a ctypes mirror with two members swapped would silently ex
 header are parsed here (members in order, their C type, the shape their comment gives) and compared with the ctypes structures,
 with the dtypes of speedy.f90_amd/columns.py's FIELDS and with the public name tuples, which are also spelled out as literals."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
 import speedy_f90_amd as s
+import support
 from speedy_f90_amd import columns, spectral
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "spdy.h")
 MIRRORS = {"spdy_moist_out": spectral.MoistOut, "spdy_rad_surface": spectral.RadSurface, "spdy_rad_out": spectral.RadOut,
            "spdy_sfc_boundary": spectral.SfcBoundary, "spdy_sfc_out": spectral.SfcOut, "spdy_pbl_out": spectral.PblOut,
            "spdy_column_physics_out": spectral.ColumnPhysicsOut, "spdy_surface_clim": spectral.SurfaceClim,
@@ -42,8 +41,7 @@ def parse_header(text):
 
 @pytest.fixture(scope="module")
 def header():
-    with open(HEADER) as f:
-        return parse_header(f.read())
+    return parse_header(support.header(comments=True))
 
 
 def test_parser_reads_every_mirrored_struct(header):

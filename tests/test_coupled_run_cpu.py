@@ -7,14 +7,14 @@ import pytest
 
 import coupledrun
 import longrun
-import moist
 import physstep
+import support
 import surfmodel as sm
 
 
 @pytest.mark.parametrize("name", list(longrun.CASES))
 def test_coupled_reference_run_conditions(name, oracle_factory):
-    sp = moist.plan("t30", 36, device=-1)
+    sp = support.plan("t30", 36, device=-1)
     cps, log, events = coupledrun.reference_run(sp, oracle_factory("t30"), name)
     assert len(log) == coupledrun.NSTEPS + 2 and sorted(cps) == list(coupledrun.CHECKPOINTS)
     worst = min(log, key=lambda e: e["margin"])

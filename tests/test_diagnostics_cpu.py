@@ -2,26 +2,17 @@
 ref_diagnostics.npz: the two sums, temp bit for bit, the printed lines), its predicate on the limits, spdy_diagnostics_format
 against the reference's text and Fortran's format reversion, the error codes on a host-only plan, and the Fortran interfaces."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
 import diagnostics as dg
-import moist
-from conftest import ROOT
+import support
+from support import host_plan  # noqa: F401
 
 ARG, NO_DEVICE = -1, -3
 NEW = ("create", "destroy", "set_limits", "reset", "check_dev", "status", "read", "field", "format")
-
-
-@pytest.fixture(scope="module")
-def host_plan():
-    moist.package()
-    sp = moist.plan("t30", max_batch=4, device=-1)
-    yield sp
-    sp.close()
 
 
 def test_restatement_against_the_reference(golden, host_plan):
@@ -135,10 +126,9 @@ def test_host_only_plan_and_error_codes(host_plan):
 
 
 def test_header_mask_bits_and_fortran_interfaces():
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
+    hdr, declared, bound = support.header(comments=True), support.declared(), support.fortran_bound()
     for name, bit in (("REKE", dg.REKE), ("DEKE", dg.DEKE), ("TEMP_LOW", dg.TEMP_LOW), ("TEMP_HIGH", dg.TEMP_HIGH), ("NONFINITE", dg.NONFINITE)):
         assert re.search(r"SPDY_DIAG_%s = %d\b" % (name, bit), hdr), name
-    f90 = open(os.path.join(ROOT, "speedy.f90_amd", "fortran", "spdy_c.f90")).read()
     for n in NEW:
-        assert 'bind(C, name="spdy_diagnostics_%s")' % n in f90, n
-        assert re.search(r"\bspdy_diagnostics_%s\s*\(" % n, hdr), n
+        assert "spdy_diagnostics_%s" % n in bound, n
+        assert "spdy_diagnostics_%s" % n in declared, n

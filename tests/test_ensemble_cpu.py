@@ -2,16 +2,15 @@
 Fortran binding; a host-only plan answers their argument checks in the documented order (include/spdy.h, "ensemble time step"); and
 the layout that speedy.f90_amd/ensemble.py owns is the one the kernels index, pinned as shapes, strides and offsets."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
 import speedy_f90_amd as s
+import support
 from speedy_f90_amd import _lib, ensemble
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARG, NO_DEVICE, STATE = -1, -3, -5
 NEW = ("grid_tendencies_dev", "spectral_step_dev", "direct_batch_spectral_step_dev", "geopotential_dev", "physics_workspace",
        "physics_dev")
@@ -19,13 +18,12 @@ NEW = ("grid_tendencies_dev", "spectral_step_dev", "direct_batch_spectral_step_d
 
 def test_symbols_in_library_header_loader_and_fortran():
     lib = s.load()
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
-    f90 = open(os.path.join(ROOT, "speedy.f90_amd", "fortran", "spdy_c.f90")).read()
+    bound = support.fortran_bound()
     for n in NEW:
         name = "spdy_ens_" + n
         assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        assert re.search(r"\bint %s\s*\(spdy_plan \*plan, int nmem\b" % name, hdr), name          # nmem right after the plan
-        assert 'bind(C, name="%s")' % name in f90, name
+        assert re.match(r"spdy_plan \*plan, int nmem\b", support.declaration(name)), name             # nmem right after the plan
+        assert name in bound, name
         assert _lib.SIGNATURES[name][:2] == [ctypes.c_void_p, ctypes.c_int], name
     # each generalises its neighbour: the single-state signature with nmem inserted
     for n in NEW:

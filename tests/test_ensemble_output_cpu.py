@@ -1,28 +1,26 @@
 """CPU: the ensemble output's interface without a device -- the entry points exist in the library, the header, the loader and the
 Fortran binding, and a host-only plan answers their argument checks in the documented order (include/spdy.h, "ensemble output")."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
 import speedy_f90_amd as s
+import support
 from speedy_f90_amd import _lib, spectral
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARG, NO_DEVICE = -1, -3
 NEW = ("spdy_ens_output_workspace", "spdy_ens_output_batch_dev")
 
 
 def test_symbols_in_library_header_loader_and_fortran():
     lib = s.load()
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
-    f90 = open(os.path.join(ROOT, "speedy.f90_amd", "fortran", "spdy_c.f90")).read()
+    hdr, f90, bound = support.header(comments=True), support.fortran_binding(), support.fortran_bound()
     for name in NEW:
         assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        assert re.search(r"\bint %s\s*\(spdy_plan \*plan, int nmem\b" % name, hdr), name          # nmem right after the plan
-        assert 'bind(C, name="%s")' % name in f90, name
+        assert re.match(r"spdy_plan \*plan, int nmem\b", support.declaration(name)), name             # nmem right after the plan
+        assert name in bound, name
         assert _lib.SIGNATURES[name][:2] == [ctypes.c_void_p, ctypes.c_int], name
     assert len(_lib.SIGNATURES["spdy_ens_output_batch_dev"]) == 12
     # the struct: six float pointers in the header's order, in the loader and in the Fortran binding

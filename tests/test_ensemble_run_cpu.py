@@ -3,54 +3,36 @@ spdy_ens_diagnostics_*, the plan option "ens_member_qcorh") without a device -- 
 ctypes table and the Fortran binding; the two creates against their single forms; the error codes on a host-only plan; the layout
 rule of the surface model's array (tests/ensemblerun.py restates it); the Python shapes."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
 import ensemblerun as er
-import moist
-from conftest import ROOT
+import support
+from support import host_plan  # noqa: F401
 
 ARG, NO_DEVICE = -1, -3
 NEW = ("spdy_ens_surface_model_create", "spdy_surface_model_members", "spdy_ens_diagnostics_create", "spdy_ens_diagnostics_status",
        "spdy_ens_diagnostics_read", "spdy_ens_diagnostics_stopped")
 
 
-@pytest.fixture(scope="module")
-def host_plan():
-    moist.package()
-    sp = moist.plan("t30", max_batch=4, device=-1)
-    yield sp
-    sp.close()
-
-
-def _decl(hdr, name):
-    """the parameter list of a function declared in the header, blanks squeezed"""
-    m = re.search(r"\bint %s\s*\(([^;]*)\);" % name, hdr)
-    assert m, name
-    return re.sub(r"\s+", " ", m.group(1)).strip()
-
-
 def test_every_new_symbol_everywhere(host_plan):
     import speedy_f90_amd as s
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
-    f90 = open(os.path.join(ROOT, "speedy.f90_amd", "fortran", "spdy_c.f90")).read()
+    bound = support.fortran_bound()
     for n in NEW:
         assert hasattr(host_plan.lib, n), n
         assert n in s._lib.SIGNATURES, n
-        assert re.search(r"\bint %s\s*\(" % n, hdr), n
-        assert 'bind(C, name="%s")' % n in f90, n
-    assert '"ens_member_qcorh"' in hdr
+        assert support.declaration(n) is not None, n
+        assert n in bound, n
+    assert '"ens_member_qcorh"' in support.header(comments=True)
 
 
 def test_creates_are_the_single_forms_with_nmem_after_the_plan():
     import speedy_f90_amd as s
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
     for one, ens in (("spdy_surface_model_create", "spdy_ens_surface_model_create"),
                      ("spdy_diagnostics_create", "spdy_ens_diagnostics_create")):
-        a, b = _decl(hdr, one), _decl(hdr, ens)
+        a, b = support.declaration(one), support.declaration(ens)
+        assert a is not None and b is not None, (one, ens)
         assert b == a.replace("spdy_plan *plan,", "spdy_plan *plan, int nmem,", 1), (a, b)
         sa, sb = s._lib.SIGNATURES[one], s._lib.SIGNATURES[ens]
         assert sb == sa[:1] + [ctypes.c_int] + sa[1:], ens

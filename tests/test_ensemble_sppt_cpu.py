@@ -3,27 +3,17 @@ spdy_ens_sppt_draws, spdy_ens_physics_sppt_workspace, spdy_ens_physics_sppt_dev)
 symbols in the library, the header, the ctypes table and the Fortran binding; the documented error codes and their order; the
 tables of an object of three members against a single object's."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-import moist
-from conftest import ROOT
+import support
+from support import host_plan  # noqa: F401
 
 ARG, NO_DEVICE, STATE = -1, -3, -5
 NEW = ("spdy_ens_sppt_create", "spdy_sppt_members", "spdy_ens_sppt_reset", "spdy_ens_sppt_draws", "spdy_ens_physics_sppt_workspace",
        "spdy_ens_physics_sppt_dev")
 TABLES = ("phi", "f0", "first", "sigma", "mu")
-
-
-@pytest.fixture(scope="module")
-def host_plan():
-    moist.package()
-    sp = moist.plan("t30", max_batch=4, device=-1)
-    yield sp
-    sp.close()
 
 
 def _seeds(*values):
@@ -35,18 +25,17 @@ def test_every_new_symbol_everywhere(host_plan):
     lib = host_plan.lib
     for n in NEW:                                   # the first lookup: fails here without the feature
         assert hasattr(lib, n), n
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
-    f90 = open(os.path.join(ROOT, "speedy.f90_amd", "fortran", "spdy_c.f90")).read()
+    bound = support.fortran_bound()
     for n in NEW:
         assert n in s._lib.SIGNATURES, n
-        assert re.search(r"\bint %s\s*\(" % n, hdr), n
-        assert 'bind(C, name="%s")' % n in f90, n
+        assert support.declaration(n) is not None, n
+        assert n in bound, n
     sig = s._lib.SIGNATURES
     # the ensemble physics with SPPT is spdy_ens_physics_dev with the object after nmem, and the single form with nmem after the plan
     assert sig["spdy_ens_physics_sppt_dev"] == sig["spdy_ens_physics_dev"][:2] + [ctypes.c_void_p] + sig["spdy_ens_physics_dev"][2:]
     assert sig["spdy_ens_physics_sppt_dev"] == sig["spdy_physics_sppt_dev"][:1] + [ctypes.c_int] + sig["spdy_physics_sppt_dev"][1:]
     assert sig["spdy_ens_physics_sppt_workspace"] == sig["spdy_ens_physics_workspace"]
-    assert "SPPT (a pattern object holds one pattern)" not in hdr
+    assert "SPPT (a pattern object holds one pattern)" not in support.header(comments=True)
 
 
 def test_create_members_and_error_codes(host_plan):

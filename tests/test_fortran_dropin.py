@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import support
 import synth
 from conftest import ROOT, TOL
 from synth import tail_inputs
@@ -27,7 +28,7 @@ def test_fortran_sources_keep_reference_api():
         assert name in src.split("contains")[0], name
     assert "function spec_to_grid(vorm, kcos) result(vorg)" in src
     assert "function grid_to_spec(vorg) result(vorm)" in src
-    assert "bind(c" in open(os.path.join(FDIR, "spdy_c.f90")).read().lower()
+    assert "bind(c" in support.fortran_binding().lower()
     # the tail modules: reference module names and full public sets (horizontal_diffusion.f90:10-11, implicit.f90:10-11,
     # geopotential.f90:11)
     for mod, names in (("horizontal_diffusion", ("initialize_horizontal_diffusion", "do_horizontal_diffusion", "dmp", "dmpd", "dmps",
@@ -45,10 +46,7 @@ def test_fortran_sources_keep_reference_api():
     assert "module time_stepping" in src and "public first_step, step" in src
     assert "subroutine step(j1, j2, dt)" in src and "subroutine first_step" in src
     # spdy_c.f90 is one-to-one with include/spdy.h: every entry point has a bind(C) interface
-    import re
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "spdy.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(spdy_[a-z0-9_]+)\s*\(", hdr))
-    bound = set(re.findall(r'name="(spdy_[a-z0-9_]+)"', open(os.path.join(FDIR, "spdy_c.f90")).read()))
+    declared, bound = support.declared(), support.fortran_bound()
     assert declared == bound, (sorted(declared - bound), sorted(bound - declared))
 
 

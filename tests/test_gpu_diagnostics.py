@@ -14,8 +14,8 @@ import pytest
 import diagnostics as dg
 import dynstep
 import modelstep
-import moist
-from conftest import TOL, VARIANTS
+import support
+from conftest import TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -25,22 +25,8 @@ ARG, STATE = -1, -5
 @pytest.fixture(scope="module")
 def plans():
     """one plan per variant for the whole module"""
-    cache = {}
-
-    def get(tag):
-        if tag not in cache:
-            cache[tag] = moist.plan(tag, 4 * VARIANTS[tag][3] + 4)
-        return cache[tag]
-    yield get
-    for sp in cache.values():
-        sp.close()
-
-
-def _state(sp, seed):
-    """time level 2 of the seeded model state: vor, div, t [kx, nx, mx], the winds scaled down into the accepted range (the seeded
-    state's own reke is of order 1e4)"""
-    st = dynstep.state(sp, seed)
-    return {n: np.ascontiguousarray(st[n][1]) * f for n, f in (("vor", 1e-2), ("div", 1e-1), ("t", 1.0))}
+    with support.plan_cache(lambda tag: support.ensemble_plan(tag, 1)) as get:
+        yield get
 
 
 def _restated(sp, x):
@@ -50,7 +36,7 @@ def _restated(sp, x):
 def _check(d, x):
     """one eager check_dev on host arrays; returns the step's row [3, kx]"""
     step = d.status()["next_step"]
-    d.check_dev(*[moist.dev(x[n]) for n in ("vor", "div", "t")])
+    d.check_dev(*[support.dev(x[n]) for n in ("vor", "div", "t")])
     return d.read(step, 1)[0]
 
 
@@ -73,7 +59,7 @@ def _diag(sp, **kw):
 def test_parity(tag, plans, golden):
     """the golden levels placed in a T30 L8 state, a T30 state of 5 levels, a T63 L16 state"""
     sp = plans("t30" if tag == "golden" else tag)
-    x = _state(sp, 5100)
+    x = dg.state(sp, 5100)
     if tag == "golden":
         g = golden("diagnostics")
         for n in x:
@@ -93,7 +79,7 @@ def test_edges_of_the_sum(plans):
     kx, nx, mx = sp.kx, sp.nx, sp.mx
     elm2 = sp.table("elm2").reshape(nx, mx)
     d = _diag(sp, capacity=2)
-    base = _state(sp, 5200)
+    base = dg.state(sp, 5200)
     # energy in the zonal column m = 1 only: both sums are 0.0 exactly
     zonal = {n: np.zeros_like(a) for n, a in base.items()}
     for n in ("vor", "div"):
@@ -124,8 +110,8 @@ def test_edges_of_the_sum(plans):
 def test_counter_and_ring(plans):
     import torch
     sp = plans("t30k5")
-    x = _state(sp, 5300)
-    D = {n: moist.dev(a) for n, a in x.items()}
+    x = dg.state(sp, 5300)
+    D = {n: support.dev(a) for n, a in x.items()}
     d = _diag(sp, capacity=4, first_step=1)
     sp.use_own_stream()
     torch.cuda.synchronize()
@@ -195,7 +181,7 @@ def test_sticky_stop_on_the_temperature_limits(bit, plans):
     sp = plans("t30")
     lev, other = 5, 2
     eq, beyond = _temp_inputs(dg.LIMITS[3 if bit == dg.TEMP_HIGH else 2], bit == dg.TEMP_HIGH)
-    x = _state(sp, 5400)
+    x = dg.state(sp, 5400)
     d = _diag(sp, capacity=3, first_step=10)
     x["t"][lev, 0, 0] = eq
     row = _check(d, x)                                      # step 10: on the limit, no trip
@@ -226,7 +212,7 @@ def test_sticky_stop_on_the_temperature_limits(bit, plans):
 
 def test_energy_limits_and_the_order_of_offences(plans):
     sp = plans("t30")
-    x = _state(sp, 5500)
+    x = dg.state(sp, 5500)
     want = _restated(sp, x)
     d = _diag(sp, capacity=2)
     for i, bit in ((0, dg.REKE), (1, dg.DEKE)):
@@ -267,7 +253,7 @@ def test_energy_limits_and_the_order_of_offences(plans):
 
 def test_non_finite(plans):
     sp = plans("t30")
-    x = _state(sp, 5600)
+    x = dg.state(sp, 5600)
     d = _diag(sp, capacity=4)
     base = _check(d, x)
     lev = 4
@@ -289,7 +275,7 @@ def _step_with_the_guard():
     """The T30 L8 adiabatic step captured without and with check_dev on time level 2 as its last node, three replays each ->
     (prognostics equal bit for bit, nodes without, nodes with, history [3, 3, kx], restated rows of the downloaded states)"""
     import torch
-    sp = moist.plan("t30", 4 * 8 + 4)
+    sp = support.plan("t30", 4 * 8 + 4)
     dt = 2400.0
     sp.initialize_implicit(dt)
     st = dynstep.state(sp, 8000)

@@ -6,10 +6,9 @@ import numpy as np
 import pytest
 
 import ensemblestep as es
-import levels
 import modelstep
-import moist
 import physstep
+import support
 import synth
 from conftest import TOL
 from dynstep import ROB, oracle_dynamics_step, wave_relerr
@@ -17,17 +16,6 @@ from dynstep import ROB, oracle_dynamics_step, wave_relerr
 pytestmark = pytest.mark.gpu
 
 DELT = 2400.0
-TAGS = {8: "t30", 5: "t30k5", 7: "t30k7"}
-
-
-def _plan(tag, nmem):
-    kx = moist.RES[tag][1]
-    return moist.plan(tag, nmem * (4 * kx + 4))
-
-
-def _plan_of_levels(kx, nmem):
-    """the plan of kx levels: the reference's own sets (TAGS), any other count on tests/levels.py's half levels"""
-    return _plan(TAGS[kx], nmem) if kx in TAGS else levels.plan("t30", kx, nmem * (4 * kx + 4))
 
 
 @pytest.mark.parametrize("E,kx", [(3, 8), (2, 5), (2, 7), (17, 8), (2, 1), (3, 4), (2, 6), (2, 9), (3, 12), (2, 15)])
@@ -37,7 +25,7 @@ def test_member_equals_single_adiabatic(E, kx, seq):
     to the single-state step on that member's state.  kx = 5, 7: the FULL = false kernels; E = 17 pushes the transform launches
     out of the model-sized form.  kx = 1, 4, 6: the small blocks of the 8-bound kernels; 9, 12, 15: the 16-bound kernels' FULL =
     false forms, which nothing else runs with members (tests/levels.py)."""
-    sp = _plan_of_levels(kx, E)
+    sp = es.plan_of_levels(kx, E)
     steps = es.LEAPFROG if seq == "leapfrog" else es.STARTUP
     sts = es.member_states(sp, E)
     snaps = es.run_ensemble(sp, es.build(sp, sts), steps, DELT)
@@ -60,7 +48,7 @@ def test_t63_member_equals_single():
     Those arrays are held to 1e-13 of the array's maximum, the bound tests/test_gpu_fused_ops.py holds the T63 launch forms to
     against each other; each one that is bit-equal all the same, and each difference, is printed."""
     E = 2
-    sp = _plan("t63k16", E)
+    sp = support.ensemble_plan("t63k16", E)
     sts = es.member_states(sp, E)
     snaps = es.run_ensemble(sp, es.build(sp, sts), es.LEAPFROG, 1200.0)
     worst, equal, must = 0.0, [], []
@@ -69,7 +57,7 @@ def test_t63_member_equals_single():
         for n, (got, want) in enumerate(zip(snaps, ref)):
             m = es.member_of(got, e)
             for k in es.COMPARED:
-                if es.same_bits(m[k], want[k]):
+                if support.same_bits(m[k], want[k]):
                     equal.append((e, n, k))
                     continue
                 err = es.relerr(m[k], want[k])
@@ -86,7 +74,7 @@ def test_t63_member_equals_single():
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
 def test_one_member_equals_existing_entry_points(tag):
     """E = 1 through the new entry points: the existing entry points' bits (also the regression check on nmem = 1)"""
-    sp = _plan(tag, 1)
+    sp = support.ensemble_plan(tag, 1)
     sts = es.member_states(sp, 1)
     for steps in (es.LEAPFROG, es.STARTUP):
         snaps = es.run_ensemble(sp, es.build(sp, sts), steps, 1200.0)
@@ -98,7 +86,7 @@ def test_isolation():
     """Member 1 of 3 all NaN: members 0 and 2 come out as on their own, and the shared inputs are untouched"""
     import torch
     E = 3
-    sp = _plan("t30", E)
+    sp = support.ensemble_plan("t30", E)
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
     for n in es.PROG:
@@ -109,7 +97,7 @@ def test_isolation():
         assert es.differing(sp, snaps, e, sts[e], es.LEAPFROG, DELT) == [], e
     assert torch.isnan(torch.view_as_real(snaps[-1]["vor"][:, 1])).all()
     for n, v in shared.items():
-        assert es.same_bits(getattr(ens, n), v), n
+        assert support.same_bits(getattr(ens, n), v), n
     sp.close()
 
 
@@ -117,7 +105,7 @@ def test_member_zero_against_oracle(oracle_factory):
     """The absolute anchor: member 0 of the (3, 8) case against the oracle's call-by-call step, at the tolerance and in the norms of
     tests/test_gpu_step.py::test_dynamical_core_step_graph"""
     E = 3
-    sp, o = _plan("t30", E), oracle_factory("t30")
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
     sts = es.member_states(sp, E)
     o.tail_init(DELT)
     snaps = es.run_ensemble(sp, es.build(sp, sts), es.LEAPFROG[:1], DELT)
@@ -133,31 +121,6 @@ def test_member_zero_against_oracle(oracle_factory):
 
 
 # ---------------------------------------------------------------------------------------------- with the whole physics
-def _physics_members(sp, o, E, hsg=None, seeds=None):
-    """E physically shaped states over member 0's orography, per-member boundary fields; member 0 is physstep's own case.  hsg,
-    seeds: the half levels of sp and o and the case's seeds at a count of tests/levels.py"""
-    d0, m0, b0 = seeds = physstep.SEEDS["t30"] if seeds is None else seeds
-    case = physstep.Case("t30", sp, o, hsg=hsg, seeds=seeds)
-    sts, bnds = [case.st], [case.bnd]
-    for e in range(1, E):
-        st = moist.state(o, es.dyn_state(sp, d0 + 1000 * e), m0 + 10 * e)
-        for n in ("phis", "tcorh", "qcorh"):
-            st[n] = case.st[n]
-        sts.append(st)
-        bnds.append(physstep.draw_boundary(physstep.grids_of(o, st)["tg"][-1].reshape(-1), b0 + 100 * e))
-    sp.surface_set_orography(case.phis0)
-    return sts, bnds
-
-
-def _ens_physics(sp, bnds):
-    """the ensemble's physics dict: every boundary field (E, il, ix), E radiation states back to back"""
-    import torch
-    dev = [physstep.device_boundary(b, sp.il, sp.ix) for b in bnds]
-    bnd = {n: torch.cat([d[n] for d in dev]) for n in dev[0]}
-    rad = torch.full((len(bnds) * sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
-    return {"bnd": bnd, "albsfc": bnd["albsfc"], "rad": rad}
-
-
 def _single_physics_run(sp, st, bnd, dt, nsteps=3):
     """three single-state steps with spdy_physics_dev, shortwave on the first; the snapshots and the radiation state after each"""
     D, W = modelstep.device_state(st), modelstep.Workspace(sp)
@@ -174,10 +137,10 @@ def test_full_physics(oracle_factory):
     """T30 L8, E = 3, three steps, shortwave on the first, per-member boundary fields and radiation states: every member bit-equal
     to spdy_physics_dev plus the single step on that member, radiation state included"""
     E, dt = 3, physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
-    sts, bnds = _physics_members(sp, o, E)
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
+    sts, bnds = es.physics_members(sp, o, E)
     sp.initialize_implicit(dt)
-    ens, P = es.build(sp, sts), _ens_physics(sp, bnds)
+    ens, P = es.build(sp, sts), es.ens_physics(sp, bnds)
     snaps = []
     for n in range(3):
         ens.step(2, 2, dt, dict(P, sw=n == 0), eps=ROB)
@@ -189,9 +152,9 @@ def test_full_physics(oracle_factory):
         ref = _single_physics_run(sp, sts[e], bnds[e], dt)
         for n in range(3):
             m = es.member_of(snaps[n], e)
-            bad = [k for k in es.COMPARED if not es.same_bits(m[k], ref[n][k])]
+            bad = [k for k in es.COMPARED if not support.same_bits(m[k], ref[n][k])]
             assert bad == [], (e, n, bad)
-            assert es.same_bits(snaps[n]["rad"][e * size:(e + 1) * size], ref[n]["rad"]), (e, n, "radiation state")
+            assert support.same_bits(snaps[n]["rad"][e * size:(e + 1) * size], ref[n]["rad"]), (e, n, "radiation state")
     sp.close()
 
 
@@ -200,12 +163,12 @@ def test_graph(oracle_factory):
     neither graph has more nodes than the single-state step captured by the same sequence"""
     import torch
     E, dt = 3, physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
-    sts, bnds = _physics_members(sp, o, E)
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
+    sts, bnds = es.physics_members(sp, o, E)
     sp.initialize_implicit(dt)
     sp.use_own_stream()
     for with_physics in (False, True):
-        P = _ens_physics(sp, bnds)
+        P = es.ens_physics(sp, bnds)
         phys = (lambda sw: dict(P, sw=sw)) if with_physics else (lambda sw: None)
         ens = es.build(sp, sts)
         eager = []
@@ -228,7 +191,7 @@ def test_graph(oracle_factory):
             graphs[with_physics and n == 0].launch()
             sp.synchronize()
             got = dict(es.snapshot(ens2), rad=P["rad"])
-            bad = [k for k in got if not es.same_bits(got[k], eager[n][k])]
+            bad = [k for k in got if not support.same_bits(got[k], eager[n][k])]
             assert bad == [], (with_physics, n, bad)
         # the single-state step, captured by the same sequence of calls
         D, W, P1 = modelstep.device_state(sts[0]), modelstep.Workspace(sp), modelstep.physics_buffers(sp, bnds[0])
@@ -253,8 +216,8 @@ def test_per_member_guard_and_coupling(oracle_factory):
     import surfmodel as sm
     import speedy_f90_amd as s
     E, dt = 2, physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
-    sts, bnds = _physics_members(sp, o, E)
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
+    sts, bnds = es.physics_members(sp, o, E)
     sp.initialize_implicit(dt)
     phis0 = o.spec_to_grid(sts[0]["phis"], 1)
     c = sm.climatology(phis0, longrun.latitudes(sp.table("sia_half")))
@@ -272,7 +235,7 @@ def test_per_member_guard_and_coupling(oracle_factory):
         return dict(out["sfc"], **out["rad"])
 
     # the ensemble: one pair of objects per member, on the member's views
-    ens, P = es.build(sp, sts), _ens_physics(sp, bnds)
+    ens, P = es.build(sp, sts), es.ens_physics(sp, bnds)
     P["out"] = sp.column_outputs(E, ("sfc", "rad"), names=flux_names)
     F = flat(P["out"])
     assert F["hfluxn"].shape == (E, 2) + sp.grid_shape and F["ssrd"].shape == (E,) + sp.grid_shape
@@ -321,14 +284,14 @@ def test_single_state_and_ensemble_interleaved_on_one_plan(oracle_factory):
     workspace would hand the one run the other's ssrd on steps 2 and 3.  All three states differ."""
     import radiation
     E, dt = 2, physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
-    sts, bnds = _physics_members(sp, o, E + 1)               # members 0, 1; the single state is the third
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
+    sts, bnds = es.physics_members(sp, o, E + 1)               # members 0, 1; the single state is the third
     phis0 = o.spec_to_grid(sts[0]["phis"], 1)
 
     def run(sp, single, ensemble):
         sp.initialize_implicit(dt)
         D, W, P1 = modelstep.device_state(sts[E]), modelstep.Workspace(sp), modelstep.physics_buffers(sp, bnds[E])
-        ens, P = es.build(sp, sts[:E]), _ens_physics(sp, bnds[:E])
+        ens, P = es.build(sp, sts[:E]), es.ens_physics(sp, bnds[:E])
         one, many = [], []
         for n in range(3):
             if single:
@@ -345,17 +308,17 @@ def test_single_state_and_ensemble_interleaved_on_one_plan(oracle_factory):
     sp.close()
     alone = {}
     for which in ("single", "ensemble"):
-        sp = _plan("t30", E)
+        sp = support.ensemble_plan("t30", E)
         sp.radiation_set_date(radiation.DATES[0])
         sp.surface_set_orography(phis0)
         alone[which] = run(sp, which == "single", which == "ensemble")[which == "ensemble"]
         sp.close()
     assert np.isfinite(one[-1]["vor"].cpu().numpy()).all() and np.isfinite(many[-1]["vor"].cpu().numpy()).all()
     for n in range(3):
-        bad = [k for k in one[n] if not es.same_bits(one[n][k], alone["single"][n][k])]
+        bad = [k for k in one[n] if not support.same_bits(one[n][k], alone["single"][n][k])]
         assert bad == [], ("single state", n, bad)
         for e in range(E):
             got, want = es.member_of(many[n], e), es.member_of(alone["ensemble"][n], e)
-            bad = [k for k in es.COMPARED if not es.same_bits(got[k], want[k])]
+            bad = [k for k in es.COMPARED if not support.same_bits(got[k], want[k])]
             assert bad == [], ("member", e, n, bad)
-        assert es.same_bits(many[n]["rad"], alone["ensemble"][n]["rad"]), ("radiation states", n)
+        assert support.same_bits(many[n]["rad"], alone["ensemble"][n]["rad"]), ("radiation states", n)

@@ -7,7 +7,7 @@ import pytest
 
 import ensembleoutput as eo
 import ensemblestep as es
-import moist
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -21,8 +21,7 @@ class Case:
 
     def __init__(self, tag, E, oracle_factory):
         self.tag, self.E = tag, E
-        kx = moist.RES[tag][1]
-        self.sp, self.o = moist.plan(tag, E * (4 * kx + 4)), oracle_factory(tag)
+        self.sp, self.o = support.ensemble_plan(tag, E), oracle_factory(tag)
         self.sts = es.member_states(self.sp, E)
         self.ens, self.ins = eo.build(self.sp, self.o, self.sts)
         self.got = run(self.ens)
@@ -39,15 +38,8 @@ def run(ens, **kw):
 
 @pytest.fixture(scope="module")
 def cases(oracle_factory):
-    made = {}
-
-    def get(tag, E):
-        if (tag, E) not in made:
-            made[(tag, E)] = Case(tag, E, oracle_factory)
-        return made[(tag, E)]
-    yield get
-    for c in made.values():
-        c.sp.close()
+    with support.plan_cache(lambda tag, E: Case(tag, E, oracle_factory), plan_of=lambda c: c.sp) as get:
+        yield get
 
 
 @pytest.mark.parametrize("tag,E", CONFIGS, ids=CONFIG_IDS)
@@ -63,7 +55,7 @@ def test_members(tag, E, cases):
             d_single, d_ref = eo.ulps(mine, single[n]), eo.ulps(mine, ref[n])
             print("[ens output %s E=%d] member %d %s: %d ulp from the single call, %d from the oracle" % (tag, E, e, n, d_single, d_ref))
             if tag.startswith("t30"):
-                assert eo.same_bits(mine, single[n]), (e, n)
+                assert support.same_bits(mine, single[n]), (e, n)
             assert d_single <= 1 and d_ref <= 1, (e, n, d_single, d_ref)
 
 
@@ -83,9 +75,9 @@ def test_one_member(cases):
     """(b) E = 1: the mean is the member's output, bit for bit, and the spread exactly +0"""
     c = cases("t30", 1)
     for n in eo.FIELDS:
-        assert eo.same_bits(c.got["mean"][n], c.got["members"][n][0]), n
+        assert support.same_bits(c.got["mean"][n], c.got["members"][n][0]), n
         assert not c.got["spread"][n].view(np.int32).any(), n
-        assert eo.same_bits(c.got["members"][n][0], eo.single_output(c.sp, c.ins[0])[n]), n
+        assert support.same_bits(c.got["members"][n][0], eo.single_output(c.sp, c.ins[0])[n]), n
 
 
 def poisoned(c):
@@ -111,22 +103,22 @@ def test_mask_and_isolation(cases):
     for n in eo.FIELDS:
         for got in (masked, unmasked):
             for e in (0, 2):
-                assert eo.same_bits(got["members"][n][e], c.got["members"][n][e]), (n, e)
+                assert support.same_bits(got["members"][n][e], c.got["members"][n][e]), (n, e)
         for grp in ("mean", "spread"):
-            assert eo.same_bits(masked[grp][n], pair[grp][n]), (grp, n)
+            assert support.same_bits(masked[grp][n], pair[grp][n]), (grp, n)
             assert np.isfinite(masked[grp][n]).all(), (grp, n)
             if n != "ps":
                 assert np.isnan(unmasked[grp][n]).all(), (grp, n)
     # the mask is the same whether it comes as a sequence or as a device tensor
     import torch
     again = run(bad, use=torch.tensor([7, 0, -1], dtype=torch.int32, device="cuda"))
-    assert all(eo.same_bits(again[g][n], masked[g][n]) for g in ("mean", "spread") for n in eo.FIELDS)
+    assert all(support.same_bits(again[g][n], masked[g][n]) for g in ("mean", "spread") for n in eo.FIELDS)
     one, none = run(c.ens, use=[0, 1, 0]), run(c.ens, use=[0, 0, 0])
     for n in eo.FIELDS:
-        assert eo.same_bits(one["mean"][n], c.got["members"][n][1]), n
+        assert support.same_bits(one["mean"][n], c.got["members"][n][1]), n
         assert not one["spread"][n].view(np.int32).any(), n
         assert np.isnan(none["mean"][n]).all() and np.isnan(none["spread"][n]).all(), n
-        assert eo.same_bits(none["members"][n], c.got["members"][n]), n          # the members are written whatever the mask says
+        assert support.same_bits(none["members"][n], c.got["members"][n]), n          # the members are written whatever the mask says
 
 
 def test_cancellation(cases, oracle_factory):
@@ -167,7 +159,7 @@ def test_capture_and_determinism(cases):
     second = run(ens)
     for g in GROUPS:
         for n in eo.FIELDS:
-            assert eo.same_bits(second[g][n], c.got[g][n]), (g, n)
+            assert support.same_bits(second[g][n], c.got[g][n]), (g, n)
     flat = lambda a: a.view((-1,) + tuple(a.shape[-2:]))
     new = lambda shapes: {n: torch.zeros(sh, dtype=torch.float32, device="cuda") for n, sh in shapes.items()}
     shapes = ens.output_shapes()
@@ -178,8 +170,8 @@ def test_capture_and_determinism(cases):
     sp.ens_output_batch_dev(E, *ins, members=only_members)
     torch.cuda.synchronize()
     for n in eo.FIELDS:
-        assert eo.same_bits(only_mean[n].cpu().numpy(), c.got["mean"][n]), n
-        assert eo.same_bits(only_members[n].cpu().numpy(), c.got["members"][n]), n
+        assert support.same_bits(only_mean[n].cpu().numpy(), c.got["mean"][n]), n
+        assert support.same_bits(only_members[n].cpu().numpy(), c.got["members"][n]), n
     # the capture
     out = {g: new(shapes[g]) for g in GROUPS}
     use = torch.ones(E, dtype=torch.int32, device="cuda")
@@ -201,7 +193,7 @@ def test_capture_and_determinism(cases):
         sp.synchronize()
         for grp in GROUPS:
             for n in eo.FIELDS:
-                assert eo.same_bits(out[grp][n].cpu().numpy(), c.got[grp][n]), (grp, n)
+                assert support.same_bits(out[grp][n].cpu().numpy(), c.got[grp][n]), (grp, n)
         # the workspace cannot grow inside a capture: SPDY_ERR_STATE, and the plan goes on working
         with pytest.raises(s.SpdyError) as err:
             with sp.graph_capture():
@@ -211,4 +203,4 @@ def test_capture_and_determinism(cases):
     finally:
         sp.use_torch_stream()
     third = run(ens)
-    assert all(eo.same_bits(third[grp][n], c.got[grp][n]) for grp in GROUPS for n in eo.FIELDS)
+    assert all(support.same_bits(third[grp][n], c.got[grp][n]) for grp in GROUPS for n in eo.FIELDS)

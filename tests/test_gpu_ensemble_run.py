@@ -14,14 +14,11 @@ import ensemblerun as er
 import ensemblestep as es
 import longrun
 import modelstep
-import moist
 import physstep
+import support
 import surfmodel as sm
 from conftest import TOL
 from dynstep import ROB
-from test_gpu_coupled_run import _device_run, _errors
-from test_gpu_diagnostics import _state
-from test_gpu_ensemble import _physics_members, _plan
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +29,7 @@ FORCING_ENTRIES = [n for n, (what, _) in enumerate(er.SEQUENCE) if what == "forc
 
 def _coupled_members(sp, o, E):
     """E physically shaped states with per-member boundary fields over member 0's orography, and the climatology over it"""
-    sts, bnds = _physics_members(sp, o, E)
+    sts, bnds = es.physics_members(sp, o, E)
     phis0 = o.spec_to_grid(sts[0]["phis"], 1)
     clim = er.shaped(sm.climatology(phis0, longrun.latitudes(sp.table("sia_half"))), sp.grid_shape)
     return sts, bnds, clim
@@ -45,9 +42,9 @@ def test_member_equals_its_single_objects(E, oracle_factory):
     state, surface-model fields, qcorh and guard rows are bit-equal to the single-state run of that member.  E = 1: the new creates
     and the option set against the existing entry points.  The test notices what it is for: after the second forcing the members'
     qcorh differ, and with member 0's qcorh in every slot the other members' third-step tr comes out differently."""
-    s = moist.package()
+    s = support.package()
     dt = physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
     sts, bnds, clim = _coupled_members(sp, o, E)
     sp.initialize_implicit(dt)
     snaps, rows, _ = er.run_ensemble(sp, s, es, sts, bnds, clim, dt, ROB)
@@ -61,20 +58,20 @@ def test_member_equals_its_single_objects(E, oracle_factory):
     if E > 1:
         q = snaps[FORCING_ENTRIES[1]]["qcorh"]
         for e in range(1, E):
-            assert not es.same_bits(q[e], q[0]), e
+            assert not support.same_bits(q[e], q[0]), e
             assert not np.array_equal(last["surf"]["sst_am"][e], last["surf"]["sst_am"][0]), e
         assert not np.array_equal(rows[0], rows[1])
         shared, _, _ = er.run_ensemble(sp, s, es, sts, bnds, clim, dt, ROB, same_qcorh=True)
-        assert es.same_bits(shared[-1]["tr"][:, 0], last["tr"][:, 0])               # member 0 has its own either way
+        assert support.same_bits(shared[-1]["tr"][:, 0], last["tr"][:, 0])               # member 0 has its own either way
         for e in range(1, E):
-            assert not es.same_bits(shared[-1]["tr"][:, e], last["tr"][:, e]), e
+            assert not support.same_bits(shared[-1]["tr"][:, e], last["tr"][:, e]), e
     sp.close()
 
 
 def _guard_inputs(sp, E):
     """three checked steps of E members [step][name] -> (E, kx, nx, mx) host arrays: step 0 in range; step 1 member 1 too warm at
     level 3 and with reke > 500 at level 5; step 2 member 1 back in range and member 2 too cold at level 0"""
-    base = [_state(sp, 5100 + 100 * e) for e in range(E)]
+    base = [dg.state(sp, 5100 + 100 * e) for e in range(E)]
     elm2 = sp.table("elm2")
     steps = [{n: np.stack([b[n] for b in base]) for n in ("vor", "div", "t")} for _ in range(3)]
     x = steps[1]
@@ -87,9 +84,9 @@ def _guard_inputs(sp, E):
 
 def test_guard_isolation_stickiness_and_ring():
     """E = 3, capacity 2, three check_dev calls on constructed spectra (finite values only)."""
-    s = moist.package()
+    s = support.package()
     E = 3
-    sp = _plan("t30", E)
+    sp = support.ensemble_plan("t30", E)
     kx, elm2 = sp.kx, sp.table("elm2")
     steps = _guard_inputs(sp, E)
     want = np.array([[dg.diag(x["vor"][e], x["div"][e], x["t"][e], elm2) for x in steps] for e in range(E)])     # [E, 3, 3, kx]
@@ -100,7 +97,7 @@ def test_guard_isolation_stickiness_and_ring():
     G = s.Diagnostics(sp, capacity=2, first_step=0, nmem=E)
     got = np.zeros_like(want)
     for n, x in enumerate(steps):
-        G.check_dev(*[moist.dev(x[k]) for k in ("vor", "div", "t")])
+        G.check_dev(*[support.dev(x[k]) for k in ("vor", "div", "t")])
         for e in range(E):
             got[e, n] = G.read(n, 1, member=e)[0]
     bad = (ctypes.c_longlong * E)()
@@ -127,7 +124,7 @@ def test_guard_isolation_stickiness_and_ring():
     for e in range(E):
         d = s.Diagnostics(sp, capacity=2, first_step=0)
         for n, x in enumerate(steps):
-            d.check_dev(*[moist.dev(np.ascontiguousarray(x[k][e])) for k in ("vor", "div", "t")])
+            d.check_dev(*[support.dev(np.ascontiguousarray(x[k][e])) for k in ("vor", "div", "t")])
             assert np.array_equal(d.read(n, 1)[0], got[e, n]), (e, n)
         assert d.status()["bad_step"] == st[e]["bad_step"] and d.status()["bad_mask"] == st[e]["bad_mask"]
         d.close()
@@ -171,9 +168,9 @@ def _surface_run(sp, s, clim, F, nmem):
 
 def test_coupler_isolation():
     """E = 3, member 1's flux inputs all NaN: members 0 and 2 come out as in the clean run, the shared fields are untouched"""
-    s = moist.package()
+    s = support.package()
     E = 3
-    sp = moist.plan("t30", max_batch=4)
+    sp = support.plan("t30", max_batch=4)
     clim, F = _surface_setup(sp, E, s)
     clean, q0, _, _ = _surface_run(sp, s, clim, F, E)
     bad = {k: v.clone() for k, v in F.items()}
@@ -183,7 +180,7 @@ def test_coupler_isolation():
     for e in (0, 2):
         for k in er.SURF + ("fmask_l",):
             assert np.array_equal(got[k][e], clean[k][e], equal_nan=True), (e, k)
-        assert es.same_bits(q1[e], q0[e]), e
+        assert support.same_bits(q1[e], q0[e]), e
     assert np.isnan(got["stl_lm"][1]).any() and np.isfinite(clean["stl_lm"]).all()
     assert not np.array_equal(clean["stl_lm"][0], clean["stl_lm"][2])             # the members' fluxes differ
     for k in er.SHARED_FIELDS:
@@ -197,9 +194,9 @@ def test_graph(oracle_factory):
     """{the coupled ensemble step, check_dev, couple_dev(1)} captured as one graph per shortwave setting: exactly the nodes of the
     single-state step captured by the same sequence with its two single objects; the replays (the graph without shortwave runs
     twice) give the eager calls' bits; the guard's counter advances by one per replay for every member."""
-    s = moist.package()
+    s = support.package()
     E, dt = 3, physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
     sts, bnds, clim = _coupled_members(sp, o, E)
     sp.initialize_implicit(dt)
     sp.use_own_stream()
@@ -209,7 +206,7 @@ def test_graph(oracle_factory):
     print("[graph nodes of step + check_dev + couple_dev, shortwave / not] ensemble of %d: %s, single state: %s" % (E, nodes, nodes1))
     assert nodes == nodes1 and len(nodes) == 2
     for n, (a, b) in enumerate(zip(snaps, eager)):
-        bad = [k for k in es.COMPARED + ("rad", "qcorh") if not es.same_bits(a[k], b[k])]
+        bad = [k for k in es.COMPARED + ("rad", "qcorh") if not support.same_bits(a[k], b[k])]
         bad += [k for k in er.SURF if not np.array_equal(a["surf"][k], b["surf"][k], equal_nan=True)]
         assert bad == [], (n, bad)
     assert np.array_equal(grows, rows, equal_nan=True)
@@ -224,7 +221,7 @@ def _ensemble_days(sp, cases, c, events):
     """test_gpu_coupled_run._device_run for the members of an ensemble, in the order of calls of DESIGN s17: ONE surface model and
     ONE guard.  Returns ({n: [per member: prognostics, rad, qcorh, surf]}, node counts, the guard's state at the end)."""
     import torch
-    s = moist.package()
+    s = support.package()
     E, dt = len(cases), longrun.DELT
     M = s.SurfaceModel(sp, er.shaped(c, sp.grid_shape), sm.DELT, nmem=E)
     G = s.Diagnostics(sp, capacity=8, first_step=1, nmem=E)
@@ -290,12 +287,12 @@ def test_coupled_days_against_the_reference(oracle_factory):
     """E = 2: member 0 is longrun's "rest" case, member 1 its "wind" case, over the same seeded orography and climatology.  Driven as
     tests/test_gpu_coupled_run.py drives one state: the start-up steps, then the three days of coupledrun (108 steps, the whole
     run) as graph replays, forcing_dev before a day's first step, set_date / set_sst_anomaly from the reference run's events.  At
-    every checkpoint each member is within conftest.TOL of coupledrun.reference_run of its case and bit-equal to _device_run of its
+    every checkpoint each member is within conftest.TOL of coupledrun.reference_run of its case and bit-equal to coupledrun.device_run of its
     case.  The run uses the batched objects: the guard and the coupler add two nodes to the step's graph, whatever E."""
     names = ("rest", "wind")
     E = len(names)
     o = oracle_factory("t30")
-    sp = _plan("t30", E)
+    sp = support.ensemble_plan("t30", E)
     refs = [coupledrun.reference_run(sp, o, name) for name in names]
     setups = [coupledrun.setup(sp, o, name) for name in names]
     cases, c = [x[0] for x in setups], setups[0][1]
@@ -314,14 +311,14 @@ def test_coupled_days_against_the_reference(oracle_factory):
     sp.use_own_stream()
     ncol = sp.il * sp.ix
     got, nodes, guard = _ensemble_days(sp, cases, c, events)
-    singles = [_device_run(sp, cases[e], c, refs[e][2]) for e in range(E)]
+    singles = [coupledrun.device_run(sp, cases[e], c, refs[e][2]) for e in range(E)]
     worst = ("", 0.0)
     for e, name in enumerate(names):
         for n in coupledrun.CHECKPOINTS:
-            err = _errors(got[n][e], refs[e][0][n], ncol)
+            err = coupledrun.errors(got[n][e], refs[e][0][n], ncol)
             worst = max([worst] + [("%s step %d %s" % (name, n, k), v) for k, v in err.items()], key=lambda x: x[1])
             one = singles[e][0][n]
-            bad = [k for k in es.PROG + ("rad", "qcorh") if not es.same_bits(got[n][e][k], one[k])]
+            bad = [k for k in es.PROG + ("rad", "qcorh") if not support.same_bits(got[n][e][k], one[k])]
             bad += [k for k in er.SURF if not np.array_equal(got[n][e]["surf"][k], one["surf"][k], equal_nan=True)]
             assert bad == [], (name, n, bad)
     print("\n[coupled ensemble days vs the reference side] largest relative error %.1e (%s)" % (worst[1], worst[0]))
@@ -332,7 +329,7 @@ def test_coupled_days_against_the_reference(oracle_factory):
     for sw in (True, False):
         assert nodes[sw, False] == nodes[sw, "step"] + 1 and nodes[sw, True] == nodes[sw, "step"] + 2, nodes
         assert nodes[sw, "step"] <= singles[0][1][sw, False], (nodes, singles[0][1])
-    assert not es.same_bits(got[108][0]["qcorh"], got[108][1]["qcorh"])           # the members' corrections have parted
+    assert not support.same_bits(got[108][0]["qcorh"], got[108][1]["qcorh"])           # the members' corrections have parted
     assert guard["stopped"] == [-1] * E and guard["next_step"] == [coupledrun.NSTEPS + 1] * E, guard
     sp.close()
 
@@ -342,9 +339,9 @@ def test_t63_members_equal_single_objects():
     single objects on the same inputs.  The members' qcorh is held to the single call's within 1e-13 of the field's maximum where
     the transform of two fields takes another launch form than that of one (the bound tests/test_gpu_fused_ops.py holds the T63
     forms to); which case occurred is printed."""
-    s = moist.package()
+    s = support.package()
     E = 2
-    sp = moist.plan("t63k16", max_batch=4)
+    sp = support.plan("t63k16", max_batch=4)
     clim, F = _surface_setup(sp, E, s)
     got, q, _, _ = _surface_run(sp, s, clim, F, E)
     assert not np.array_equal(got["sst_om"][0], got["sst_om"][1]) and np.isfinite(q.cpu().numpy()).all()
@@ -352,18 +349,18 @@ def test_t63_members_equal_single_objects():
         one, q1, _, _ = _surface_run(sp, s, clim, {k: v[e:e + 1].contiguous() for k, v in F.items()}, 1)
         for k in er.SURF + ("fmask_l",):
             assert np.array_equal(got[k][e], one[k][0], equal_nan=True), (e, k)
-        if es.same_bits(q[e], q1[0]):
+        if support.same_bits(q[e], q1[0]):
             print("[t63 forcing] member %d: qcorh bit-equal to the single call's" % e)
         else:
             err = es.relerr(q[e], q1[0])
             print("[t63 forcing] member %d: qcorh differs from the single call's by %.2e of its maximum" % (e, err))
             assert err <= 1e-13, (e, err)
-    x = [_state(sp, 5400 + 100 * e) for e in range(E)]
+    x = [dg.state(sp, 5400 + 100 * e) for e in range(E)]
     G = s.Diagnostics(sp, capacity=2, nmem=E)
-    G.check_dev(*[moist.dev(np.stack([m[k] for m in x])) for k in ("vor", "div", "t")])
+    G.check_dev(*[support.dev(np.stack([m[k] for m in x])) for k in ("vor", "div", "t")])
     for e in range(E):
         d = s.Diagnostics(sp, capacity=2)
-        d.check_dev(*[moist.dev(x[e][k]) for k in ("vor", "div", "t")])
+        d.check_dev(*[support.dev(x[e][k]) for k in ("vor", "div", "t")])
         assert np.array_equal(d.read(0, 1), G.read(0, 1, member=e)), e
         d.close()
     assert not np.array_equal(G.read(0, 1, member=0), G.read(0, 1, member=1))

@@ -9,15 +9,13 @@ import pytest
 
 import ensemblesppt as esp
 import ensemblestep as es
-import moist
 import physstep
-import poison
 import sppt
+import support
 import synth
 from conftest import TOL
 from dynstep import ROB
 from ensemblesppt import FIELDS, NSTEPS, SEED
-from test_gpu_ensemble import _ens_physics, _physics_members, _plan
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +31,7 @@ def test_member_equals_single(tag, E, nadv):
     both sides cannot be wrong together.  E = 17: 136 fields push the inverse launch out of the model-sized form.  Two members with
     the same seed are bit-equal to each other, wherever they sit."""
     import speedy_f90_amd as s
-    sp = _plan(tag, E)
+    sp = support.ensemble_plan(tag, E)
     sd = esp.seeds(E)
     pat, one = s.Sppt(sp, NSTEPS, seeds=sd), esp.singles(sp, sd)
     assert pat.members() == E and all(pat.draws(e) == 0 for e in range(E))
@@ -57,8 +55,8 @@ def test_member_equals_single(tag, E, nadv):
         twin.advance_dev()
         got = esp.fields(twin)
         for n in FIELDS:
-            assert poison.same_bits(got[n][0], got[n][1]), n
-            assert poison.same_bits(got[n][0], first[n][1]) and poison.same_bits(got[n][2], first[n][0]), n
+            assert support.same_bits(got[n][0], got[n][1]), n
+            assert support.same_bits(got[n][0], first[n][1]) and support.same_bits(got[n][2], first[n][0]), n
     sp.close()
 
 
@@ -68,13 +66,13 @@ def test_injected_noise_with_both_clips(oracle_factory):
     member: spec and pattern of each member against the restatement on the oracle; |pattern| <= 1 exactly."""
     import speedy_f90_amd as s
     E = 2
-    sp, o = _plan("t30", E), oracle_factory("t30")
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
     pat, ref = s.Sppt(sp, NSTEPS, seeds=[1, 2]), [sppt.Pattern(o) for _ in range(E)]
     worst = 0.0
     for d in range(3):
         eta = esp.injected(E, d, esp.shape(sp))
         assert np.abs(eta.real).max(axis=(1, 2, 3)).min() > 10.0                    # the first clip has work to do in every member
-        pat.advance_dev(moist.dev(eta))
+        pat.advance_dev(support.dev(eta))
         got = esp.fields(pat)
         for e in range(E):
             want = ref[e].advance(eta[e])
@@ -97,7 +95,7 @@ def test_mixed_branches_in_one_launch():
     members 0 and 2 -- bit-equal to the fourth advance of a run without the reset.  Draws are (4, 1, 4)."""
     import speedy_f90_amd as s
     E, other = 3, SEED ^ 0xABCDEF
-    sp = _plan("t30", E)
+    sp = support.ensemble_plan("t30", E)
     sd = esp.seeds(E)
     pat, plain, one = s.Sppt(sp, NSTEPS, seeds=sd), s.Sppt(sp, NSTEPS, seeds=sd), s.Sppt(sp, NSTEPS, seed=other)
     for _ in range(3):
@@ -106,12 +104,12 @@ def test_mixed_branches_in_one_launch():
     pat.reset(other, member=1)
     assert [pat.draws(e) for e in range(E)] == [3, 0, 3]
     for n in FIELDS:                                               # the reset touches the counter and the seed, nothing else
-        assert poison.same_bits(esp.fields(pat)[n], before[n]), n
+        assert support.same_bits(esp.fields(pat)[n], before[n]), n
     pat.advance_dev(); plain.advance_dev(); one.advance_dev()
     got, want = esp.fields(pat), esp.fields(plain)
     for e in (0, 2):
         for n in FIELDS:
-            assert poison.same_bits(got[n][e], want[n][e]), (e, n)
+            assert support.same_bits(got[n][e], want[n][e]), (e, n)
     assert esp.differing(got, 1, one) == []
     assert not np.array_equal(got["spec"][1], want["spec"][1])
     assert [pat.draws(e) for e in range(E)] == [4, 1, 4] and [plain.draws(e) for e in range(E)] == [4, 4, 4]
@@ -124,7 +122,7 @@ def test_isolation():
     bit-equal to the same run with finite values there, on that advance and on the drawn advance that follows."""
     import speedy_f90_amd as s
     E = 3
-    sp = _plan("t30", E)
+    sp = support.ensemble_plan("t30", E)
     sd, kx = esp.seeds(E), sp.kx
     clean, bad = s.Sppt(sp, NSTEPS, seeds=sd), s.Sppt(sp, NSTEPS, seeds=sd)
     eta = esp.injected(E, 0, esp.shape(sp))
@@ -132,15 +130,15 @@ def test_isolation():
     dirty[1, :kx // 2] = complex(float("nan"), float("nan"))
     dirty[1, kx // 2:] = complex(float("inf"), -float("inf"))
     for step, (a, b) in enumerate(((eta, dirty), (None, None))):
-        clean.advance_dev(None if a is None else moist.dev(a))
-        bad.advance_dev(None if b is None else moist.dev(b))
+        clean.advance_dev(None if a is None else support.dev(a))
+        bad.advance_dev(None if b is None else support.dev(b))
         got, want = esp.fields(bad), esp.fields(clean)
         for e in (0, 2):
             for n in FIELDS:
-                assert poison.same_bits(got[n][e], want[n][e]), (step, e, n)
+                assert support.same_bits(got[n][e], want[n][e]), (step, e, n)
             assert bad.draws(e) == clean.draws(e) == step + 1
         assert np.isfinite(want["pattern"]).all()
-        assert not poison.same_bits(got["spec"][1], want["spec"][1]), step          # the poison was there
+        assert not support.same_bits(got["spec"][1], want["spec"][1]), step          # the poison was there
     assert bad.draws(1) == 2
     sp.close()
 
@@ -166,12 +164,12 @@ def test_application(tag, E, forms, oracle_factory):
     evaluated in NumPy on ens_physics_dev's own result and the entry tendencies."""
     import torch
     import speedy_f90_amd as s
-    sp, o = _plan(tag, E), oracle_factory(tag)
+    sp, o = support.ensemble_plan(tag, E), oracle_factory(tag)
     kx, size = sp.kx, sp.radiation_state_size()
-    sts, bnds = _physics_members(sp, o, E)
+    sts, bnds = es.physics_members(sp, o, E)
     spec = _spectra(o, sts)
-    dspec = [moist.dev(a) for a in spec]
-    P = _ens_physics(sp, bnds)
+    dspec = [support.dev(a) for a in spec]
+    P = es.ens_physics(sp, bnds)
     t0 = [synth.splitmix64(170 + i, E * kx * sp.il * sp.ix).reshape((E, kx) + sp.grid_shape) * f
           for i, f in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
     sd, mu = esp.seeds(E), esp.mu(kx)
@@ -182,30 +180,30 @@ def test_application(tag, E, forms, oracle_factory):
     pattern = pat.numpy("pattern")
     assert pattern.std() > 0.05 and not np.array_equal(pattern[0], pattern[1])
     # without SPPT, for the anchor
-    T, S = [moist.dev(a) for a in t0], _nan_state(sp, E)
+    T, S = [support.dev(a) for a in t0], _nan_state(sp, E)
     sp.ens_physics_dev(E, True, *dspec, P["bnd"], P["albsfc"], S, *T)
     torch.cuda.synchronize()
     anchor = [sppt.apply(t.cpu().numpy()[0], d[0], pattern[0], mu) for t, d in zip(T, t0)]
     assert all(not np.array_equal(w, t.cpu().numpy()[0]) for w, t in zip(anchor[2:], T[2:]))
     for fused in forms:
         sp.set_option("physics_fused", fused)
-        T2, out2, S2 = [moist.dev(a) for a in t0], sp.column_outputs(E), _nan_state(sp, E)
+        T2, out2, S2 = [support.dev(a) for a in t0], sp.column_outputs(E), _nan_state(sp, E)
         sp.ens_physics_sppt_dev(E, pat, True, *dspec, P["bnd"], P["albsfc"], S2, *T2, out2)
         torch.cuda.synchronize()
         for n, t, w in zip(TEND, T2, anchor):
             assert np.array_equal(t.cpu().numpy()[0], w), (fused, n, "anchor")
-        assert poison.same_bits(S2, S) and not torch.isnan(S2).any()
+        assert support.same_bits(S2, S) and not torch.isnan(S2).any()
         flat2 = physstep.flat_outs(out2)
         for e in range(E):
             bnd = physstep.device_boundary(bnds[e], sp.il, sp.ix)
-            T1, out1, S1 = [moist.dev(a[e]) for a in t0], sp.column_outputs(1), _nan_state(sp, 1)
-            sp.physics_sppt_dev(one[e], True, *[moist.dev(a[e]) for a in spec], bnd, bnd["albsfc"], S1, *T1, out1)
+            T1, out1, S1 = [support.dev(a[e]) for a in t0], sp.column_outputs(1), _nan_state(sp, 1)
+            sp.physics_sppt_dev(one[e], True, *[support.dev(a[e]) for a in spec], bnd, bnd["albsfc"], S1, *T1, out1)
             torch.cuda.synchronize()
             for n, t2, t1 in zip(TEND, T2, T1):
-                assert poison.same_bits(t2[e], t1), (fused, e, n)
-            assert poison.same_bits(S2[e * size:(e + 1) * size], S1), (fused, e, "radiation state")
+                assert support.same_bits(t2[e], t1), (fused, e, n)
+            assert support.same_bits(S2[e * size:(e + 1) * size], S1), (fused, e, "radiation state")
             for n, t1 in physstep.flat_outs(out1).items():
-                assert poison.same_bits(flat2[n][e], t1[0]), (fused, e, n)
+                assert support.same_bits(flat2[n][e], t1[0]), (fused, e, n)
     assert [pat.draws(e) for e in range(E)] == [1] * E and np.array_equal(pat.numpy("pattern"), pattern)      # not advanced
     sp.close()
 
@@ -227,14 +225,14 @@ def test_captured_step(oracle_factory):
     import torch
     import speedy_f90_amd as s
     E, dt = 2, physstep.DT["t30"]
-    sp, o = _plan("t30", E), oracle_factory("t30")
-    sts, bnds = _physics_members(sp, o, E)
+    sp, o = support.ensemble_plan("t30", E), oracle_factory("t30")
+    sts, bnds = es.physics_members(sp, o, E)
     sp.initialize_implicit(dt)
     sp.use_own_stream()
     sd, mu = esp.seeds(E), esp.mu(sp.kx)
 
     def start():
-        return es.build(sp, sts), _ens_physics(sp, bnds), s.Sppt(sp, NSTEPS, mu, seeds=sd)
+        return es.build(sp, sts), es.ens_physics(sp, bnds), s.Sppt(sp, NSTEPS, mu, seeds=sd)
 
     def snap(ens, P, pat):
         sp.synchronize()
@@ -259,14 +257,14 @@ def test_captured_step(oracle_factory):
     for n in range(3):
         g.launch()
         got = snap(ens, P, pat)
-        bad = [k for k in got if not es.same_bits(got[k], want[n][k])]
+        bad = [k for k in got if not support.same_bits(got[k], want[n][k])]
         assert bad == [], (n, bad)
     assert [pat.draws(e) for e in range(E)] == [3, 3]
     assert np.isfinite(want[-1]["vor"][:, 0].cpu().numpy()).all()
     skipped, draws = eager(skip=1)
     assert draws == [2, 2]
-    assert es.same_bits(skipped[0]["vor"], want[0]["vor"]) and not es.same_bits(skipped[1]["vor"], want[1]["vor"])
-    assert not es.same_bits(skipped[2]["pattern"], want[2]["pattern"])
+    assert support.same_bits(skipped[0]["vor"], want[0]["vor"]) and not support.same_bits(skipped[1]["vor"], want[1]["vor"])
+    assert not support.same_bits(skipped[2]["pattern"], want[2]["pattern"])
     # node counts
     n_step = g.num_nodes()
     n_plain = _nodes(sp, lambda: ens.step(2, 2, dt, dict(P, sw=True), eps=ROB))
@@ -284,7 +282,7 @@ def test_captured_step(oracle_factory):
 def test_advance_is_three_nodes_whatever_the_members():
     """the captured advance of E = 1, 2 and 17 members: noise, ONE inverse launch, clip"""
     import speedy_f90_amd as s
-    sp = _plan("t30", 17)
+    sp = support.ensemble_plan("t30", 17)
     sp.use_own_stream()
     for E in (1, 2, 17):
         pat = s.Sppt(sp, NSTEPS, nmem=E, seed=SEED)
@@ -301,7 +299,7 @@ def test_t63_member_equals_single(oracle_factory):
     required."""
     import speedy_f90_amd as s
     E = 2
-    sp, o = _plan("t63k16", E), oracle_factory("t63k16")
+    sp, o = support.ensemble_plan("t63k16", E), oracle_factory("t63k16")
     sd = esp.seeds(E)
     pat, one, ref = s.Sppt(sp, NSTEPS, seeds=sd), esp.singles(sp, sd), [sppt.Pattern(o) for _ in range(E)]
     worst = 0.0
@@ -329,7 +327,7 @@ def test_error_codes_on_a_device_plan():
     import torch
     import speedy_f90_amd as s
     E, kx = 2, 8
-    sp, other, small = _plan("t30", E), _plan("t30", E), moist.plan("t30", 20)
+    sp, other, small = support.ensemble_plan("t30", E), support.ensemble_plan("t30", E), support.plan("t30", 20)
     lib = sp.lib
     sp.radiation_set_date(0.0)
     sp.surface_set_orography(np.zeros(sp.grid_shape))

@@ -26,10 +26,14 @@ pairs than half the CUs holds 36 MiB of grids or more, and streams).
 import numpy as np
 import pytest
 
+import diagnostics as dg
 import ensemblestep as es
 import levels
 import moist
+import physlevels as pl
+import physstep
 import poison
+import support
 import synth
 from conftest import TOL
 from dynstep import ROB, oracle_dynamics_step, wave_relerr
@@ -117,20 +121,21 @@ def many(make, n, uniq=32):
     return (base.repeat((reps,) + (1,) * (base.dim() - 1))[:n] * scale.view((n,) + (1,) * (base.dim() - 1))).contiguous()
 
 
+def _pinned_plan(tag):
+    import speedy_f90_amd as s
+    sp = s.Spectral(tag, kx=8, max_batch=MAX_BATCH, device=0)
+    pin_launch_options(sp)
+    return sp
+
+
 @pytest.fixture(scope="module")
 def plans():
-    import speedy_f90_amd as s
-    cache = {}
-
-    def get(tag, fused=-1):
-        if tag not in cache:
-            cache[tag] = s.Spectral(tag, kx=8, max_batch=MAX_BATCH, device=0)
-            pin_launch_options(cache[tag])
-        cache[tag].set_fused(fused)
-        return cache[tag]
-    yield get
-    for p in cache.values():
-        p.close()
+    with support.plan_cache(_pinned_plan) as cached:
+        def get(tag, fused=-1):
+            sp = cached(tag)
+            sp.set_fused(fused)
+            return sp
+        yield get
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -294,7 +299,7 @@ def check_poisoned(label, call, clean, kind, position):
     call.run(x, out)
     assert out.intact(), "%s: sentinel fields overwritten at (band, field) %s" % (label, out.hits()[:8])
     for n, v in x.items():
-        assert poison.same_bits(v, copies[n]), "%s: input %s changed" % (label, n)
+        assert support.same_bits(v, copies[n]), "%s: input %s changed" % (label, n)
     hit, shown = call.reaches(name, k), []
     for i, (got, want) in enumerate(zip(out.outs, clean)):
         mine = [f for j, f in hit if j == i]
@@ -412,12 +417,12 @@ def test_stage_call(tag, stage, kind, position, plans, oracle_factory):
     copy = bad.copy()
     got = stage_call(sp, stage, bad)
     sp.set_fused(-1)
-    assert poison.same_bits(bad, copy), "input changed"
+    assert support.same_bits(bad, copy), "input changed"
     for b in range(3):
         if b == position:
             assert poison.reached(got[b], kind), (tag, stage, kind, "field %d does not show the poison" % b)
         else:
-            assert poison.same_bits(got[b], clean[b]), (tag, stage, kind, "field %d poisoned, field %d changed" % (position, b))
+            assert support.same_bits(got[b], clean[b]), (tag, stage, kind, "field %d poisoned, field %d changed" % (position, b))
 
 
 # ------------------------------------------------------------------------------- part 2: the entries the reference never reads
@@ -461,7 +466,7 @@ def test_dead_entries_every_inverse_form(tag, op, form, n, what, plans, oracle_f
     call.run(x, out)
     assert out.intact(), out.hits()[:8]
     for k, v in x.items():
-        assert poison.same_bits(v, copies[k]), "input %s changed" % k
+        assert support.same_bits(v, copies[k]), "input %s changed" % k
     for i, (got, want) in enumerate(zip(out.outs, clean)):
         diff = (got.view(torch.int64) != want.view(torch.int64)).flatten(1).any(1)
         assert not bool(diff.any()), "%s %s %s n=%d %s: output %d fields %s changed" % (tag, op, form, n, what, i, diff.nonzero().flatten().tolist()[:8])
@@ -473,13 +478,12 @@ def test_guard_ignores_the_zonal_column(what):
     s16: "dropped by a select, not multiplied by zero").  One Diagnostics of three members: with that column of member 1's vor and
     div NaN, or +inf / -inf, every member's row -- member 1's too -- has the clean check's bits and no member is flagged.  A NaN in a
     coefficient that is read flags member 1 alone and leaves the rows of members 0 and 2 as they were."""
-    from test_gpu_diagnostics import _state
-    s = moist.package()
+    s = support.package()
     E = 3
-    sp = moist.plan("t30", max_batch=4)
-    x = {n: np.stack([_state(sp, 5700 + 100 * e)[n] for e in range(E)]) for n in ("vor", "div", "t")}
+    sp = support.plan("t30", max_batch=4)
+    x = {n: np.stack([dg.state(sp, 5700 + 100 * e)[n] for e in range(E)]) for n in ("vor", "div", "t")}
     G = s.Diagnostics(sp, capacity=4, first_step=0, nmem=E)
-    check = lambda y: G.check_dev(*[moist.dev(y[n]) for n in ("vor", "div", "t")])
+    check = lambda y: G.check_dev(*[support.dev(y[n]) for n in ("vor", "div", "t")])
     check(x)
     clean = np.stack([G.read(0, 1, member=e)[0] for e in range(E)])
     assert np.isfinite(clean).all() and not np.array_equal(clean[0], clean[2])
@@ -488,12 +492,12 @@ def test_guard_ignores_the_zonal_column(what):
         y[n][1, :, :, 0] = complex(float("nan"), float("nan")) if what == "nan" else complex(float("inf"), -float("inf"))
     check(y)
     got = np.stack([G.read(1, 1, member=e)[0] for e in range(E)])
-    assert poison.same_bits(got, clean), "a value in the zonal column reached a sum"
+    assert support.same_bits(got, clean), "a value in the zonal column reached a sum"
     assert G.stopped() == [-1] * E
     y["div"][1, 2, 3, 2] = complex(float("nan"), 0.0)
     check(y)
     got = np.stack([G.read(2, 1, member=e)[0] for e in range(E)])
-    assert poison.same_bits(got[[0, 2]], clean[[0, 2]]) and np.isnan(got[1, 1, 2]) and G.stopped() == [-1, 2, -1]
+    assert support.same_bits(got[[0, 2]], clean[[0, 2]]) and np.isnan(got[1, 1, 2]) and G.stopped() == [-1, 2, -1]
     G.close()
     sp.close()
 
@@ -504,8 +508,8 @@ def _t63_9(nmem):
     return levels.plan("t63", 9, nmem * (4 * 9 + 4))
 
 
-ENSEMBLES = {"t30k5-E3": (lambda E: moist.plan("t30k5", E * (4 * 5 + 4)), lambda f: f("t30k5"), 3, 2400.0),
-             "t63k16-E3": (lambda E: moist.plan("t63k16", E * (4 * 16 + 4)), lambda f: f("t63k16"), 3, 1200.0),
+ENSEMBLES = {"t30k5-E3": (lambda E: support.plan("t30k5", E * (4 * 5 + 4)), lambda f: f("t30k5"), 3, 2400.0),
+             "t63k16-E3": (lambda E: support.plan("t63k16", E * (4 * 16 + 4)), lambda f: f("t63k16"), 3, 1200.0),
              "t63k9-E2": (_t63_9, lambda f: levels.oracle("t63", 9), 2, 1200.0)}
 ENS_CASES = [("t30k5-E3", 1), ("t63k16-E3", 1), ("t63k9-E2", 1), ("t63k9-E2", 0)]
 ENS_POISON = ("all-nan", "ps-inf", "t11-inf")
@@ -565,11 +569,11 @@ def test_ensemble_step_member_isolated(name, member, how, oracle_factory):
             continue
         for n, (got, want) in enumerate(zip(snaps, clean)):
             a, b = es.member_of(got, e), es.member_of(want, e)
-            bad = [k for k in es.COMPARED if not es.same_bits(a[k], b[k])]
+            bad = [k for k in es.COMPARED if not support.same_bits(a[k], b[k])]
             assert bad == [], "%s, member %d %s: member %d step %d differs in %s" % (name, member, how, e, n + 1, bad)
     assert poison.nonfinite(snaps[-1]["vor"][:, member]), "%s, member %d %s: its vor is finite at the end" % (name, member, how)
     for n, v in shared.items():
-        assert es.same_bits(getattr(ens, n), v), n
+        assert support.same_bits(getattr(ens, n), v), n
 
 
 # --------------------------------------------------------------------- part 4: the column physics beside a non-finite state
@@ -582,8 +586,7 @@ _phys_clean = {}
 
 
 def _phys_plan(kx, max_batch=64):
-    import physlevels as pl
-    return (moist.plan("t30", max_batch), moist.HSG[8]) if kx == 8 else (pl.plan(kx, max_batch), pl.hsg(kx))
+    return (support.plan("t30", max_batch), moist.HSG[8]) if kx == 8 else (pl.plan(kx, max_batch), pl.hsg(kx))
 
 
 def poison_state(d, b, how):
@@ -614,17 +617,15 @@ def run_chain(sp, nb, calls, sppt=None):
     radiation state, with the state, the tendencies and every optional output inside guard bands.  Returns (name -> tensor, the
     Guarded allocation)."""
     import torch
-    import physstep
-    from test_gpu_physics_step import TEND
     S0 = torch.empty((nb * sp.radiation_state_size(),), dtype=torch.float64, device="cuda")
     outs = [sp.column_outputs(nb) for _ in calls]
     flat = [physstep.flat_outs(o) for o in outs]
-    names = [("state", S0)] + [("%s%d" % (n, i + 1), d[n]) for i, (d, _) in enumerate(calls) for n in TEND]
+    names = [("state", S0)] + [("%s%d" % (n, i + 1), d[n]) for i, (d, _) in enumerate(calls) for n in physstep.TEND]
     names += [("out%d.%s" % (i + 1, n), t) for i in range(len(calls)) for n, t in flat[i].items()]
     g, views = guarded_like([t for _, t in names], sp.grid_shape)
     V = dict(zip([n for n, _ in names], views))
     for i, (d, _) in enumerate(calls):
-        for n in TEND:
+        for n in physstep.TEND:
             V["%s%d" % (n, i + 1)].copy_(d[n])
     for i, (d, sw) in enumerate(calls):
         out = {b: ({n: V["out%d.%s.%s" % (i + 1, b, n)] for n in v} if isinstance(v, dict) else V["out%d.%s" % (i + 1, b)])
@@ -632,7 +633,7 @@ def run_chain(sp, nb, calls, sppt=None):
         if not sw:                         # ssrd stays where the shortwave call put it (include/spdy.h)
             out["rad"]["ssrd"] = V["out1.rad.ssrd"]
         args = (sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], V["state"],
-                *[V["%s%d" % (n, i + 1)] for n in TEND], out)
+                *[V["%s%d" % (n, i + 1)] for n in physstep.TEND], out)
         if sppt is None:
             sp.column_physics_dev(*args)
         else:
@@ -654,28 +655,26 @@ def phys_clean(kx, form, sppt):
     import radiation
     import sppt as spptref
     import surface
-    from test_gpu_physics_step import TEND, _gridded
-    from test_gpu_sppt import _mu
     key = (kx, form, sppt)
     if _phys_clean.get("key") != key:
         if "sp" in _phys_clean:
             _phys_clean["sp"].close()
         _phys_clean.clear()
         nb, keep = 3, {}
-        sp, _, il, ix, d1, d2 = _gridded("t30k%d" % kx, nb, 9700 + kx, plan=_phys_plan(kx), keep=keep)
+        sp, _, il, ix, d1, d2 = physstep.gridded("t30k%d" % kx, nb, 9700 + kx, plan=_phys_plan(kx), keep=keep)
         sp.column_physics_workspace()
         sp.set_option("physics_fused", 1 if form == "one-launch" else 0)
         pattern = None
         if sppt:
             sp.column_physics_sppt_workspace()
             P = np.clip(1.5 * (2.0 * synth.splitmix64(9760 + kx, nb * kx * il * ix) - 1.0), -1.0, 1.0).reshape(nb, kx, il, ix)
-            pattern = (moist.dev(P), _mu(kx))
+            pattern = (support.dev(P), spptref.mu(kx))
         calls = [(d1, True)] if sppt else [(d1, True), (d2, False)]
         V, g = run_chain(sp, nb, calls, pattern)
         assert g.intact(), g.hits()[:8]
         r, _ = surface.chain(keep["tab"], keep["c1"], keep["zon"], keep["sqcoa"])
         assert float(r["margin"].min()) >= surface.MIN_MARGIN
-        for n in TEND:
+        for n in physstep.TEND:
             want = radiation.grids(r["pbl"][n], nb, il, ix)
             if sppt:                       # physics.f90:212-221 on the restatements' tendencies and the tendencies at entry
                 want = np.moveaxis(spptref.apply(want.swapaxes(0, 1), np.moveaxis(d1[n].cpu().numpy(), 1, 0), np.moveaxis(P, 1, 0),
@@ -695,7 +694,6 @@ def test_column_physics_state_isolated(kx, form, sppt, how):
     radiation state, and spdy_column_physics_sppt_dev: three states, state 1 poisoned in both calls.  States 0 and 2 have the clean
     run's bits in the tendencies, every optional output (the integers iptop, icnv, icltop among them) and their slices of the
     radiation state; state 1's temperature tendency is non-finite; inputs and guard bands are unchanged."""
-    from test_gpu_physics_step import TEND
     c = phys_clean(kx, form, sppt)
     sp, nb = c["sp"], c["nb"]
     calls = [({n: v.clone() for n, v in d.items()}, sw) for d, sw in c["calls"]]
@@ -706,10 +704,10 @@ def test_column_physics_state_isolated(kx, form, sppt, how):
     assert g.intact(), g.hits()[:8]
     for (d, _), cp in zip(calls, copies):
         for n, v in d.items():
-            assert poison.same_bits(v, cp[n]), "input %s changed" % n
+            assert support.same_bits(v, cp[n]), "input %s changed" % n
     for b in (0, 2):
         got, want = state_slices(V, nb, b), state_slices(c["V"], nb, b)
-        bad = [n for n in want if not poison.same_bits(got[n], want[n])]
+        bad = [n for n in want if not support.same_bits(got[n], want[n])]
         assert bad == [], "%d levels %s sppt=%s %s: state %d differs in %s" % (kx, form, sppt, how, b, bad)
     mine = state_slices(V, nb, 1)
     for i in range(len(calls)):
@@ -724,8 +722,6 @@ def ens_phys_run(sp, E, espec, ebnd, t0):
     """spdy_ens_physics_dev, a shortwave call and a call on the held state: every tendency, optional output and the radiation
     states, by name"""
     import torch
-    import physstep
-    from test_gpu_physics_step import TEND
     S = torch.full((E * sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
     res, ssrd = {"state": S}, None
     for i, sw in ((1, True), (2, False)):
@@ -735,7 +731,7 @@ def ens_phys_run(sp, E, espec, ebnd, t0):
         else:
             out["rad"]["ssrd"] = ssrd
         sp.ens_physics_dev(E, sw, *espec, ebnd, ebnd["albsfc"], S, *T, out)
-        res.update({"%s%d" % (n, i): t for n, t in zip(TEND, T)})
+        res.update({"%s%d" % (n, i): t for n, t in zip(physstep.TEND, T)})
         res.update({"out%d.%s" % (i, n): t for n, t in physstep.flat_outs(out).items()})
     torch.cuda.synchronize()
     return res
@@ -745,35 +741,31 @@ def ens_phys_clean(kx, oracle_factory):
     """members, inputs and the clean run of spdy_ens_physics_dev at kx levels; member 0's tendencies of the shortwave call are
     anchored to the oracle's transforms and the chain of restatements (physstep.Case.physics)"""
     import torch
-    import physstep
-    from test_gpu_ensemble import _physics_members
-    from test_gpu_physics_step import TEND
     if _ens_phys_clean.get("kx") != kx:
         if "sp" in _ens_phys_clean:
             _ens_phys_clean["sp"].close()
         _ens_phys_clean.clear()
         E = 3
         if kx == 8:
-            sp, o, hsg, seeds = moist.plan("t30", E * (4 * kx + 4)), oracle_factory("t30"), None, None
+            sp, o, hsg, seeds = support.plan("t30", E * (4 * kx + 4)), oracle_factory("t30"), None, None
         else:
-            from test_gpu_physics_levels import _levels_case
-            sp, o, hsg, seeds = _levels_case(kx, E * (4 * kx + 4))
-        sts, bnds = _physics_members(sp, o, E, hsg, seeds)
+            sp, o, hsg, seeds = pl.levels_case(kx, E * (4 * kx + 4))
+        sts, bnds = es.physics_members(sp, o, E, hsg, seeds)
         il, ix = sp.il, sp.ix
         dev = [physstep.device_boundary(b, il, ix) for b in bnds]
         ebnd = {n: torch.cat([b[n] for b in dev]) for n in dev[0]}
         spec = [[a for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], o.geopotential(st["t"][0], st["phis"]), st["ps"][0])]
                 for st in sts]
-        espec = [moist.dev(np.stack([spec[e][i] for e in range(E)])) for i in range(6)]
+        espec = [support.dev(np.stack([spec[e][i] for e in range(E)])) for i in range(6)]
         host_t0 = [np.stack([synth.splitmix64(270 + 4 * e + i, kx * il * ix).reshape(kx, il, ix) * f for e in range(E)])
                    for i, f in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
-        t0 = [moist.dev(a) for a in host_t0]
+        t0 = [support.dev(a) for a in host_t0]
         sp.ens_physics_workspace(E)
         clean = ens_phys_run(sp, E, espec, ebnd, t0)
         case = physstep.Case("t30", sp, o, st=sts[0], bnd=bnds[0], hsg=hsg)
         ref_t = [a[0].copy() for a in host_t0]
         case.physics(sts[0], True, {}, *ref_t)
-        for n, w in zip(TEND, ref_t):
+        for n, w in zip(physstep.TEND, ref_t):
             e = synth.relerr(clean[n + "1"][0].cpu().numpy(), w)
             assert e <= TOL, (kx, n, e)
         _ens_phys_clean.update(kx=kx, sp=sp, E=E, espec=espec, ebnd=ebnd, t0=t0, clean=clean)
@@ -801,10 +793,10 @@ def test_ensemble_physics_member_isolated(kx, how, oracle_factory):
     copies = [x.clone() for x in espec + list(ebnd.values()) + t0]
     got = ens_phys_run(sp, E, espec, ebnd, t0)
     for x, cp in zip(espec + list(ebnd.values()) + t0, copies):
-        assert poison.same_bits(x, cp), "an input changed"
+        assert support.same_bits(x, cp), "an input changed"
     for b in (0, 2):
         a, w = state_slices(got, E, b), state_slices(c["clean"], E, b)
-        bad = [n for n in w if not poison.same_bits(a[n], w[n])]
+        bad = [n for n in w if not support.same_bits(a[n], w[n])]
         assert bad == [], "%d levels %s: member %d differs in %s" % (kx, how, b, bad)
     mine = state_slices(got, E, 1)
     assert poison.nonfinite(mine["ttend1"]) and poison.nonfinite(mine["ttend2"])
@@ -825,7 +817,7 @@ def coupled_setup(oracle_factory):
     import surfmodel as sm
     if not _coupled:
         E = len(RUN_WINDS)
-        sp, o = moist.plan("t30", E * (4 * 8 + 4)), oracle_factory("t30")
+        sp, o = support.plan("t30", E * (4 * 8 + 4)), oracle_factory("t30")
         sts = [longrun.rest_state(o, wind=w) for w in RUN_WINDS]
         phis0 = o.spec_to_grid(sts[0]["phis"], 1)
         lat = longrun.latitudes(sp.table("sia_half"))
@@ -846,7 +838,7 @@ def coupled_run(c, inject, graph):
     import torch
     import ensemblerun as er
     import surfmodel as sm
-    s = moist.package()
+    s = support.package()
     sp, sts, bnds, dt = c["sp"], c["sts"], c["bnds"], c["dt"]
     E = len(sts)
     ens = s.Ensemble(sp, E, member_qcorh=True)
@@ -909,7 +901,6 @@ def anchor_first_step(c, o, clean, start):
     step with the chain of restatements as its physics (physstep.Case.hook), on the member's state, the boundary fields and qcorh the
     surface model held before the step and the zonal forcing of the run's date.  Prognostics and PL operands within TOL."""
     import coupledrun
-    import physstep
     sp, dt = c["sp"], c["dt"]
     st = dict(c["sts"][0], qcorh=start["qcorh"])
     case = physstep.Case("t30", sp, o, st=st, bnd=start["bnd"])
@@ -941,7 +932,6 @@ def test_member_goes_nonfinite_in_a_coupled_run(graph, oracle_factory):
     reference's rest state with a different seeded wind each (member 0 and 1: the states of the coupled three-day run), not the
     seeded states of the other parts: those are not balanced and overflow within three steps with the physics at any but a very short
     time step (tests/physstep.py, DT), and eight steps at the model's own 2400 s are what this test is about."""
-    import diagnostics as dg
     import ensemblerun as er
     c = coupled_setup(oracle_factory)
     sp, E = c["sp"], len(c["sts"])
@@ -951,19 +941,19 @@ def test_member_goes_nonfinite_in_a_coupled_run(graph, oracle_factory):
     clean, clean_final = c["runs"]["clean", graph]
     assert clean_final["count"] == 0 and clean_final["stopped"] == [-1] * E, clean_final
     assert all(not poison.nonfinite(clean[-1][k]) for k in es.PROG) and np.isfinite(clean[-1]["rows"]).all()
-    assert not es.same_bits(clean[-1]["vor"][:, 0], clean[-1]["vor"][:, 2])
+    assert not support.same_bits(clean[-1]["vor"][:, 0], clean[-1]["vor"][:, 2])
     anchor_first_step(c, oracle_factory("t30"), clean, clean_final["start"])
     got, final = coupled_run(c, True, graph)
     first_bad = INJECT_AFTER                 # the guard's number (from 0) of the first step that starts from the NaN
     for n in range(RUN_STEPS):
         for e in (0, 2):
             a, b = es.member_of(got[n], e), es.member_of(clean[n], e)
-            bad = [k for k in es.COMPARED if not es.same_bits(a[k], b[k])]
-            bad += [k for k in ("qcorh",) if not es.same_bits(got[n][k][e], clean[n][k][e])]
-            bad += ["flux " + k for k in er.FLUXES if not es.same_bits(got[n]["flux"][k][e], clean[n]["flux"][k][e])]
-            bad += ["rad"] if not es.same_bits(got[n]["rad"][e * size:(e + 1) * size], clean[n]["rad"][e * size:(e + 1) * size]) else []
-            bad += [k for k in er.SURF if not poison.same_bits(got[n]["surf"][k][e], clean[n]["surf"][k][e])]
-            bad += ["guard row"] if not poison.same_bits(got[n]["rows"][e], clean[n]["rows"][e]) else []
+            bad = [k for k in es.COMPARED if not support.same_bits(a[k], b[k])]
+            bad += [k for k in ("qcorh",) if not support.same_bits(got[n][k][e], clean[n][k][e])]
+            bad += ["flux " + k for k in er.FLUXES if not support.same_bits(got[n]["flux"][k][e], clean[n]["flux"][k][e])]
+            bad += ["rad"] if not support.same_bits(got[n]["rad"][e * size:(e + 1) * size], clean[n]["rad"][e * size:(e + 1) * size]) else []
+            bad += [k for k in er.SURF if not support.same_bits(got[n]["surf"][k][e], clean[n]["surf"][k][e])]
+            bad += ["guard row"] if not support.same_bits(got[n]["rows"][e], clean[n]["rows"][e]) else []
             assert bad == [], "step %d (from 1), member %d differs from the clean run in %s" % (n + 1, e, bad)
         if n >= first_bad:
             assert poison.nonfinite(got[n]["t"][:, 1]), n
@@ -972,8 +962,8 @@ def test_member_goes_nonfinite_in_a_coupled_run(graph, oracle_factory):
     st, one = final["status"][1], final["single"]
     assert st["bad_mask"] & dg.NONFINITE and st["bad_step"] == first_bad == one["bad_step"], (st, one)
     assert st["bad_level"] == one["bad_level"] and st["bad_mask"] == one["bad_mask"], (st, one)
-    assert poison.same_bits(np.asarray(st["bad_row"]), np.asarray(one["bad_row"]))
-    assert poison.same_bits(np.stack([x["rows"][1] for x in got]), final["single_rows"])
+    assert support.same_bits(np.asarray(st["bad_row"]), np.asarray(one["bad_row"]))
+    assert support.same_bits(np.stack([x["rows"][1] for x in got]), final["single_rows"])
     for e in (0, 2):
         assert final["status"][e]["bad_step"] == -1 and final["status"][e]["bad_mask"] == 0, (e, final["status"][e])
     assert poison.nonfinite(got[-1]["surf"]["stl_lm"][1]) and not poison.nonfinite(got[-1]["surf"]["stl_lm"][0])

@@ -7,47 +7,22 @@ import pytest
 
 import ensemblestep as es
 import letkf as lk
-import moist
+import support
 
 pytestmark = pytest.mark.gpu
 
-SIGMA_H, RHO = 5.0e5, 1.1
-C_H = SIGMA_H * np.sqrt(10.0 / 3.0)
 DELT = 2400.0
+
+
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
+    return sp, lk.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
-    made = {}
-
-    def get(tag="t30k5", nmem=32):
-        if tag not in made:
-            kx = moist.RES[tag][1]
-            sp = moist.plan(tag, nmem * (4 * kx + 4))
-            made[tag] = (sp, lk.Geometry(sp))
-        return made[tag]
-    yield get
-    for sp, _ in made.values():
-        sp.close()
-
-
-def analyse_grid(sp, lt, x):
-    """Letkf.analyse_grid on the gridded ensemble x (NumPy) -> the increments as NumPy arrays"""
-    import torch
-    out = lt.analyse_grid(*[moist.dev(x[v]) for v in lk.VARS])
-    torch.cuda.synchronize()
-    return {v: a.cpu().numpy() for v, a in zip(lk.VARS, out)}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool(np.array_equal(a.view(np.int64), b.view(np.int64)))
-
-
-def make(sp, E, obs, sigma_v=0.0, rho=RHO, sigma_h=SIGMA_H):
-    import speedy_f90_amd as s
-    lt = s.Letkf(sp, E, max(len(obs["var"]), 1), sigma_h, sigma_v, rho)
-    lt.set_obs(*lk.args(obs))
-    return lt
+    with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
+        yield lambda tag="t30k5", nmem=32: get(tag, nmem)
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the operator
@@ -59,8 +34,8 @@ def test_operator(E, plans):
     sp, g = plans()
     x = lk.ensemble(g, E, seed=40 + E)
     obs = lk.edge_obs(g, x)
-    lt = make(sp, E, obs)
-    analyse_grid(sp, lt, x)
+    lt = lk.make(sp, E, obs)
+    lk.analyse_grid(sp, lt, x)
     got = {n: a.cpu().numpy() for n, a in lt.fields().items()}
     hx, hxmean, _, dep = lk.obs_space(g, x, obs)
     scale = np.array([np.max(np.abs(x[lk.VARS[v]])) for v in obs["var"]])
@@ -69,25 +44,16 @@ def test_operator(E, plans):
         worst = float(np.max(np.abs(mine - ref) / (16 * lk.EPS * sc)))
         print("[letkf operator E=%d] %s: %.3f of the bound" % (E, name, worst))
         assert mine.shape == ref.shape and worst <= 1.0, (name, worst)
-    assert same_bits(lt.field("y").numpy(), got["hx"] - got["hxmean"][:, None])
+    assert support.same_bits(lt.field("y").numpy(), got["hx"] - got["hxmean"][:, None])
     lt.close()
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the analysis on grids
-def limits(g, x, C, b, rho, cols, E):
-    """per variable max(16 x the difference of the restatement's two routes on these inputs, 64 E eps max|x - mean|), the eigh
-    route's increments and the largest condition number"""
-    a, kappa = lk.increments(g, x, C, b, rho, "eigh", cols)
-    j, _ = lk.increments(g, x, C, b, rho, "jacobi", cols)
-    sc = lk.perturbation_scale(x)
-    return {v: max(16 * float(np.max(np.abs(a[v] - j[v]))), 64 * E * lk.EPS * sc[v]) for v in lk.VARS}, a, kappa
-
-
-def compare(tag, sp, g, x, obs, E, sigma_v, cols, rho=RHO):
-    C, b = lk.problems(g, x, obs, SIGMA_H, sigma_v, cols)
-    lim, ref, kappa = limits(g, x, C, b, rho, cols, E)
-    lt = make(sp, E, obs, sigma_v, rho)
-    got = analyse_grid(sp, lt, x)
+def compare(tag, sp, g, x, obs, E, sigma_v, cols, rho=lk.RHO):
+    C, b = lk.problems(g, x, obs, lk.SIGMA_H, sigma_v, cols)
+    lim, ref, kappa = lk.limits(g, x, C, b, rho, cols, E)
+    lt = lk.make(sp, E, obs, sigma_v, rho)
+    got = lk.analyse_grid(sp, lt, x)
     lt.close()
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v], cols) - ref[v]))) / lim[v] for v in lk.VARS}
     print("[letkf grid %s E=%d sigma_v=%g] %d observations, %d columns, kappa %.2e, ratio to the limit: %s"
@@ -110,8 +76,8 @@ def test_analysis_on_grids(E, sigma_v, plans):
         if tag == "clustered":
             centre = lk.distance(g.colunit, lk.unit([100.0], [20.0]))[:, 0].argmin()
             d = lk.distance(g.colunit[centre:centre + 1], lk.unit(obs["lon"], obs["lat"]))
-            assert len(obs["var"]) > 3 * lk.CHUNK and float(d.max()) < 2.0 * C_H        # all of them in range of one column
-        cols = lk.columns_for(g, obs, SIGMA_H, most=most)
+            assert len(obs["var"]) > 3 * lk.CHUNK and float(d.max()) < 2.0 * lk.C_H        # all of them in range of one column
+        cols = lk.columns_for(g, obs, lk.SIGMA_H, most=most)
         worst, kappa = compare(tag, sp, g, x, obs, E, sigma_v, cols)
         kappas.append(kappa)
         assert max(worst.values()) <= 1.0, (tag, worst)
@@ -125,7 +91,7 @@ def test_analysis_small_errors(plans):
     x = lk.ensemble(g, E, seed=E)
     obs = lk.sparse_obs(g, x)
     obs["error"][:] = 1.0e-4
-    worst, kappa = compare("small errors", sp, g, x, obs, E, 0.1, lk.columns_for(g, obs, SIGMA_H))
+    worst, kappa = compare("small errors", sp, g, x, obs, E, 0.1, lk.columns_for(g, obs, lk.SIGMA_H))
     assert 1e8 <= kappa <= 1e10, kappa
     assert max(worst.values()) <= 1.0, worst
 
@@ -142,7 +108,7 @@ def test_analysis_many_levels(kx):
     g = lk.Geometry(sp)
     x = lk.ensemble(g, E, seed=kx)
     obs = lk.concat(lk.clustered_obs(g, x, n=300), lk.sparse_obs(g, x))
-    worst, kappa = compare("kx=%d" % kx, sp, g, x, obs, E, 0.1, lk.columns_for(g, obs, SIGMA_H, most=12, outside=4))
+    worst, kappa = compare("kx=%d" % kx, sp, g, x, obs, E, 0.1, lk.columns_for(g, obs, lk.SIGMA_H, most=12, outside=4))
     sp.close()
     assert max(worst.values()) <= 1.0, worst
 
@@ -159,10 +125,10 @@ def test_exact_zero_out_of_range(plans):
     obs = lk.observe(g, x, [lk.T] * 5, [2] * 5, lon, lat, 0.5)
     c_v = 0.1 * np.sqrt(10.0 / 3.0)
     assert all(abs(g.lnfsg[k] - g.lnfsg[2]) > 2.0 * c_v for k in range(g.kx) if k != 2)
-    lt = make(sp, E, obs, 0.1, 1.0)
-    got = analyse_grid(sp, lt, x)
+    lt = lk.make(sp, E, obs, 0.1, 1.0)
+    got = lk.analyse_grid(sp, lt, x)
     lt.close()
-    far = lk.distance(g.colunit, lk.unit(lon, lat)).min(axis=1) > 2.0 * C_H * (1.0 + 1e-12)
+    far = lk.distance(g.colunit, lk.unit(lon, lat)).min(axis=1) > 2.0 * lk.C_H * (1.0 + 1e-12)
     assert far.sum() > 4000
     for v in lk.VARS:
         a = lk.at_columns(got[v], np.arange(g.ix * g.il))
@@ -181,20 +147,20 @@ def test_appended_observations_and_two_runs(plans):
     x = lk.ensemble(g, E, seed=32)
     base = lk.clustered_obs(g, x, n=600)
     more = lk.clustered_obs(g, x, n=300, centre=(280.0, -20.0), seed=6)
-    lt = make(sp, E, lk.concat(base, more), 0.1, 1.0)
+    lt = lk.make(sp, E, lk.concat(base, more), 0.1, 1.0)
     lt.set_obs(*lk.args(base))
-    first, again = analyse_grid(sp, lt, x), analyse_grid(sp, lt, x)
+    first, again = lk.analyse_grid(sp, lt, x), lk.analyse_grid(sp, lt, x)
     lt.set_obs(*lk.args(lk.concat(base, more)))
-    both = analyse_grid(sp, lt, x)
+    both = lk.analyse_grid(sp, lt, x)
     lt.close()
-    untouched = lk.distance(g.colunit, lk.unit(more["lon"], more["lat"])).min(axis=1) > 2.0 * C_H * (1.0 + 1e-12)
-    near = lk.distance(g.colunit, lk.unit(base["lon"], base["lat"])).min(axis=1) < C_H
+    untouched = lk.distance(g.colunit, lk.unit(more["lon"], more["lat"])).min(axis=1) > 2.0 * lk.C_H * (1.0 + 1e-12)
+    near = lk.distance(g.colunit, lk.unit(base["lon"], base["lat"])).min(axis=1) < lk.C_H
     assert (untouched & near).sum() > 20
     for v in lk.VARS:
-        assert same_bits(first[v], again[v]), v
+        assert support.same_bits(first[v], again[v]), v
         a, c = (lk.at_columns(r[v], np.nonzero(untouched)[0]) for r in (first, both))
-        assert same_bits(np.ascontiguousarray(a), np.ascontiguousarray(c)), v
-        assert not same_bits(first[v], both[v]), v                  # the appended observations do act where they reach
+        assert support.same_bits(np.ascontiguousarray(a), np.ascontiguousarray(c)), v
+        assert not support.same_bits(first[v], both[v]), v                  # the appended observations do act where they reach
         assert lk.at_columns(first[v], np.nonzero(near)[0]).any(), v
 
 
@@ -204,8 +170,8 @@ def test_pure_inflation(plans):
     sp, g = plans()
     for E in (2, 17):
         x = lk.ensemble(g, E, seed=33)
-        lt = make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.21)
-        got = analyse_grid(sp, lt, x)
+        lt = lk.make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.21)
+        got = lk.analyse_grid(sp, lt, x)
         lt.close()
         for v in lk.VARS:
             s = np.zeros(x[v].shape[1:])
@@ -231,39 +197,26 @@ def test_closed_form(plans):
     tv = x["t"][:, k].reshape(E, -1)[:, col]
     err = 0.7
     obs = lk.make_obs([lk.T], [k], [g.lon[i]], [g.lat[j]], [tv.mean() + 1.3], [err])
-    lt = make(sp, E, obs, 0.1)
-    got = analyse_grid(sp, lt, x)
+    lt = lk.make(sp, E, obs, 0.1)
+    got = lk.analyse_grid(sp, lt, x)
     lt.close()
     inc = got["t"][:, k].reshape(E, -1)[:, col]
     s2 = tv.var(ddof=1)
-    gg = RHO * s2
+    gg = lk.RHO * s2
     d = obs["value"][0] - tv.mean()
     bound = 64 * E * lk.EPS * np.max(np.abs(tv - tv.mean()))
     mean_err = abs(inc.mean() - d * gg / (err * err + gg))
-    var_err = abs((tv + inc).var(ddof=1) - RHO * s2 * err * err / (err * err + gg))
+    var_err = abs((tv + inc).var(ddof=1) - lk.RHO * s2 * err * err / (err * err + gg))
     print("[letkf closed form] mean %.3e (bound %.3e), variance %.3e (bound %.3e)" % (mean_err, bound, var_err,
                                                                                      4 * bound * np.max(np.abs(tv - tv.mean()))))
     assert mean_err <= bound and var_err <= 4 * bound * np.max(np.abs(tv - tv.mean()))
 
 
 # ---------------------------------------------------------------------------------------------------- 5. the state
-def oracle_grids(o, sts):
-    """time level 1 of the member states on the grid by the oracle's transforms: true wind, t, q, ps"""
-    x = {v: [] for v in lk.VARS}
-    for st in sts:
-        uv = [o.uvspec(st["vor"][0, k], st["div"][0, k]) for k in range(o.kx)]
-        x["u"].append(np.stack([o.spec_to_grid(a, 2) for a, _ in uv]))
-        x["v"].append(np.stack([o.spec_to_grid(b, 2) for _, b in uv]))
-        x["t"].append(np.stack([o.spec_to_grid(st["t"][0, k], 1) for k in range(o.kx)]))
-        x["q"].append(np.stack([o.spec_to_grid(st["tr"][0, k], 1) for k in range(o.kx)]))
-        x["ps"].append(o.spec_to_grid(st["ps"][0], 1))
-    return {v: np.stack(a) for v, a in x.items()}
-
-
 def oracle_analysis(o, g, sts, obs, sigma_v, rho):
     """the analysed time level 1 of every member: the restatement's increments through the oracle's vdspec and grid_to_spec"""
-    x = oracle_grids(o, sts)
-    inc, _ = lk.analyse(g, x, obs, SIGMA_H, sigma_v, rho)
+    x = lk.oracle_grids(o, sts)
+    inc, _ = lk.analyse(g, x, obs, lk.SIGMA_H, sigma_v, rho)
     grid = lambda a: a.reshape(a.shape[:-1] + (g.il, g.ix))
     out = []
     for e, st in enumerate(sts):
@@ -275,18 +228,6 @@ def oracle_analysis(o, g, sts, obs, sigma_v, rho):
     return x, out
 
 
-def spread_obs(g, x, n, seed):
-    """n observations over the globe (the operator's edge points first), each with half the members' spread at its place as error"""
-    rng = np.random.default_rng(seed)
-    pts = (lk.edge_points(g) + [(float(rng.uniform(0, 360)), float(rng.uniform(-85, 85))) for _ in range(n)])[:n]
-    obs = lk.make_obs([o % 5 for o in range(n)], [(3 * o) % g.kx for o in range(n)], [p[0] for p in pts], [p[1] for p in pts],
-                      np.zeros(n), np.ones(n))
-    hx, _, _, _ = lk.obs_space(g, x, obs)
-    obs["error"] = 0.5 * hx.std(axis=1, ddof=1) + 1e-300
-    obs["value"] = hx[:, 0] + obs["error"] * rng.standard_normal(n)
-    return obs
-
-
 @pytest.mark.parametrize("tag,E,nobs", [("t30k5", 3, 40), ("t63k16", 2, 20)], ids=["t30k5-E3", "t63k16-E2"])
 def test_state(tag, E, nobs, plans, oracle_factory):
     """Ensemble.analyse on seeded states (E = 3, kx = 5: odd stacks; T63 L16, E = 2) against the restatement fed by the oracle's
@@ -296,17 +237,17 @@ def test_state(tag, E, nobs, plans, oracle_factory):
     o = oracle_factory(tag)
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
-    x = oracle_grids(o, sts)
-    obs = spread_obs(g, x, nobs, seed=50)
-    _, want = oracle_analysis(o, g, sts, obs, 0.1, RHO)
-    lt = make(sp, E, obs, 0.1)
+    x = lk.oracle_grids(o, sts)
+    obs = lk.spread_obs(g, x, nobs, seed=50)
+    _, want = oracle_analysis(o, g, sts, obs, 0.1, lk.RHO)
+    lt = lk.make(sp, E, obs, 0.1)
     before = {n: getattr(ens, n).clone() for n in es.PROG}
     ens.analyse(lt)
     torch.cuda.synchronize()
     for n in es.PROG:
         a = getattr(ens, n)
-        assert es.same_bits(a[1], before[n][1]), n                  # time level 2
-        assert not es.same_bits(a[0], before[n][0]), n
+        assert support.same_bits(a[1], before[n][1]), n                  # time level 2
+        assert not support.same_bits(a[0], before[n][0]), n
         for e in range(E):
             ref = want[e][n]
             err = float(np.max(np.abs(a[0, e].cpu().numpy() - ref)) / np.max(np.abs(ref)))
@@ -324,20 +265,20 @@ def test_state_unchanged_and_restart(plans, oracle_factory):
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
     before = {n: getattr(ens, n).clone() for n in es.PROG}
-    lt = make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.0)
+    lt = lk.make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.0)
     ens.analyse(lt)
     torch.cuda.synchronize()
     for n in es.PROG:
-        assert es.same_bits(getattr(ens, n), before[n]), n
+        assert support.same_bits(getattr(ens, n), before[n]), n
     lt.close()
-    lt = make(sp, E, spread_obs(g, oracle_grids(oracle_factory("t30k5"), sts), 20, seed=51), 0.1)
+    lt = lk.make(sp, E, lk.spread_obs(g, lk.oracle_grids(oracle_factory("t30k5"), sts), 20, seed=51), 0.1)
     ens.analyse(lt)
     ens.startup(DELT)
     for _ in range(2):
         ens.step(2, 2, 2.0 * DELT)
     torch.cuda.synchronize()
     for n in es.PROG:
-        assert not es.same_bits(getattr(ens, n)[0], before[n][0]), n
+        assert not support.same_bits(getattr(ens, n)[0], before[n][0]), n
         assert bool(torch.isfinite(torch.view_as_real(getattr(ens, n))).all()), n
     lt.close()
 
@@ -352,11 +293,11 @@ def test_capture(E, plans, oracle_factory):
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
     x0 = {n: getattr(ens, n).clone() for n in es.PROG}
-    lt = make(sp, E, spread_obs(g, oracle_grids(oracle_factory("t30k5"), sts), 20, seed=52), 0.1)
+    lt = lk.make(sp, E, lk.spread_obs(g, lk.oracle_grids(oracle_factory("t30k5"), sts), 20, seed=52), 0.1)
     ens.analyse(lt)
     torch.cuda.synchronize()
     eager = {n: getattr(ens, n).clone() for n in es.PROG}
-    assert not es.same_bits(eager["t"], x0["t"])
+    assert not support.same_bits(eager["t"], x0["t"])
     sp.use_own_stream()
     torch.cuda.synchronize()
     try:
@@ -370,7 +311,7 @@ def test_capture(E, plans, oracle_factory):
             gr.launch()
             sp.synchronize()
             for n in es.PROG:
-                assert es.same_bits(getattr(ens, n), eager[n]), n
+                assert support.same_bits(getattr(ens, n), eager[n]), n
         gr.close()
     finally:
         sp.use_torch_stream()

@@ -9,8 +9,7 @@ import pytest
 import ensemblestep as es
 import letkf as lk
 import letkfinterp as li
-import moist
-from test_gpu_letkf import C_H, RHO, SIGMA_H, analyse_grid, make, oracle_grids, same_bits, spread_obs
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -18,19 +17,15 @@ STRIDES = [(2, 2), (3, 5), (4, 47)]
 CENTRE, POLAR = (100.0, 20.0), (357.0, 83.0)
 
 
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
+    return sp, lk.Geometry(sp)
+
+
 @pytest.fixture(scope="module")
 def plans():
-    made = {}
-
-    def get(tag="t30k5", nmem=32):
-        if tag not in made:
-            kx = moist.RES[tag][1]
-            sp = moist.plan(tag, nmem * (4 * kx + 4))
-            made[tag] = (sp, lk.Geometry(sp))
-        return made[tag]
-    yield get
-    for sp, _ in made.values():
-        sp.close()
+    with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
+        yield lambda tag="t30k5", nmem=32: get(tag, nmem)
 
 
 def observations(g, x, n=600):
@@ -78,14 +73,14 @@ def reference(g, E, sigma_v):
             cols = np.unique(np.concatenate(list(cls.values())))
             per[(si, sj)] = (idx, wgt, cls, cols, li.needed(idx, wgt, cols))
         union = np.unique(np.concatenate([li.coarse_columns(g, *st)[p[4]] for st, p in per.items()]))
-        T = {r: li.transforms(g, x, obs, SIGMA_H, sigma_v, RHO, union, r) for r in ("eigh", "jacobi")}
+        T = {r: li.transforms(g, x, obs, lk.SIGMA_H, sigma_v, lk.RHO, union, r) for r in ("eigh", "jacobi")}
         _REFERENCE[(E, sigma_v)] = (x, obs, per, union, T)
     return _REFERENCE[(E, sigma_v)]
 
 
 def run_at(sp, lt, x, si, sj):
     lt.set_weight_stride(si, sj)
-    return analyse_grid(sp, lt, x)
+    return lk.analyse_grid(sp, lt, x)
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the coarse columns
@@ -95,19 +90,19 @@ def test_coarse_columns_bit_equal(E, plans):
     same inputs, and the other columns are not all equal to it; back at (1, 1) the object gives the first result again"""
     sp, g = plans()
     x = lk.ensemble(g, E, seed=60 + E)
-    lt = make(sp, E, observations(g, x), 0.1)
-    full = analyse_grid(sp, lt, x)
+    lt = lk.make(sp, E, observations(g, x), 0.1)
+    full = lk.analyse_grid(sp, lt, x)
     for si, sj in STRIDES[:2]:
         got = run_at(sp, lt, x, si, sj)
         coarse = lt.table("coarse_columns")
         assert np.array_equal(coarse, li.coarse_columns(g, si, sj))
         for v in lk.VARS:
             a, b = (np.ascontiguousarray(lk.at_columns(r[v], coarse)) for r in (got, full))
-            assert a.any() and same_bits(a, b), (si, sj, v)
-            assert not same_bits(got[v], full[v]), (si, sj, v)
+            assert a.any() and support.same_bits(a, b), (si, sj, v)
+            assert not support.same_bits(got[v], full[v]), (si, sj, v)
     again = run_at(sp, lt, x, 1, 1)
     for v in lk.VARS:
-        assert same_bits(again[v], full[v]), v
+        assert support.same_bits(again[v], full[v]), v
     lt.close()
 
 
@@ -123,10 +118,10 @@ def test_against_the_restatement(E, sigma_v, plans):
     sp, g = plans()
     x, obs, per, union, T = reference(g, E, sigma_v)
     sc = lk.perturbation_scale(x)
-    lt = make(sp, E, obs, sigma_v)
+    lt = lk.make(sp, E, obs, sigma_v)
     d = np.minimum(*(lk.distance(g.colunit, lk.unit([p[0]], [p[1]]))[:, 0] for p in (CENTRE, POLAR)))
     for (si, sj), (idx, wgt, cls, cols, entries) in per.items():
-        assert len(cls) == (7 if sj < g.il - 1 else 6) and (d[cols] < C_H).sum() >= 4 and (d[cols] > 2.0 * C_H).sum() >= 2
+        assert len(cls) == (7 if sj < g.il - 1 else 6) and (d[cols] < lk.C_H).sum() >= 4 and (d[cols] > 2.0 * lk.C_H).sum() >= 2
         got = run_at(sp, lt, x, si, sj)
         assert np.array_equal(lt.table("interp_index"), idx) and np.max(np.abs(lt.table("interp_weight") - wgt)) <= 2 * lk.EPS
         at = np.searchsorted(union, li.coarse_columns(g, si, sj)[entries])
@@ -158,11 +153,11 @@ def test_many_levels_with_a_column_list():
     obs = lk.concat(lk.clustered_obs(g, x, n=300), lk.sparse_obs(g, x))
     cols = np.unique(np.concatenate([c[:1] for c in list(class_columns(g, si, sj).values())[:3]]))      # interior, coarse longitude, coarse row
     idx, wgt = li.stencils(g, si, sj)
-    ref, entries, Te = li.analyse(g, x, obs, SIGMA_H, 0.1, RHO, si, sj, "eigh", cols, (idx, wgt))
-    alt, _, _ = li.analyse(g, x, obs, SIGMA_H, 0.1, RHO, si, sj, "jacobi", cols, (idx, wgt))
-    lt = s.Letkf(sp, E, len(obs["var"]), SIGMA_H, 0.1, RHO, weight_stride=(si, sj))
+    ref, entries, Te = li.analyse(g, x, obs, lk.SIGMA_H, 0.1, lk.RHO, si, sj, "eigh", cols, (idx, wgt))
+    alt, _, _ = li.analyse(g, x, obs, lk.SIGMA_H, 0.1, lk.RHO, si, sj, "jacobi", cols, (idx, wgt))
+    lt = s.Letkf(sp, E, len(obs["var"]), lk.SIGMA_H, 0.1, lk.RHO, weight_stride=(si, sj))
     lt.set_obs(*lk.args(obs))
-    got = analyse_grid(sp, lt, x)
+    got = lk.analyse_grid(sp, lt, x)
     sc = lk.perturbation_scale(x)
     lim = {v: max(16 * float(np.max(np.abs(ref[v] - alt[v]))), 64 * E * lk.EPS * sc[v]) for v in lk.VARS}
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v], cols) - ref[v]))) / lim[v] for v in lk.VARS}
@@ -178,7 +173,7 @@ def test_no_observation_is_exactly_zero(plans):
     sp, g = plans()
     E = 17
     x = lk.ensemble(g, E, seed=70)
-    lt = make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.0)
+    lt = lk.make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.0)
     got = run_at(sp, lt, x, 3, 5)
     assert not lt.field("weights").numpy().any()
     for v in lk.VARS:
@@ -197,26 +192,26 @@ def test_appended_observations_and_two_runs(plans):
     col = 24 * g.ix + 26
     more = lk.clustered_obs(g, x, n=300, centre=(float(g.lon[26]), float(g.lat[24])), seed=8)
     both = lk.concat(base, more)
-    lt = make(sp, E, both, 0.1, 1.0)
+    lt = lk.make(sp, E, both, 0.1, 1.0)
     lt.set_obs(*lk.args(base))
-    first, again = run_at(sp, lt, x, si, sj), analyse_grid(sp, lt, x)
+    first, again = run_at(sp, lt, x, si, sj), lk.analyse_grid(sp, lt, x)
     idx, wgt = lt.table("interp_index"), lt.table("interp_weight")
     four = lt.table("coarse_columns")[idx[col]]
     assert (wgt[col] != 0.0).all() and len(set(four)) == 4
     dist = lk.distance(g.colunit[np.append(four, col)], lk.unit(more["lon"], more["lat"]))
-    assert float(dist[:4].min()) > 2.0 * C_H * (1.0 + 1e-12) and float(dist[4].max()) < C_H
+    assert float(dist[:4].min()) > 2.0 * lk.C_H * (1.0 + 1e-12) and float(dist[4].max()) < lk.C_H
     lt.set_obs(*lk.args(both))
-    second = analyse_grid(sp, lt, x)
+    second = lk.analyse_grid(sp, lt, x)
     full_both = run_at(sp, lt, x, 1, 1)
     lt.set_obs(*lk.args(base))
-    full_base = analyse_grid(sp, lt, x)
+    full_base = lk.analyse_grid(sp, lt, x)
     lt.close()
     for v in lk.VARS:
-        assert same_bits(first[v], again[v]), v
+        assert support.same_bits(first[v], again[v]), v
         a, b = (np.ascontiguousarray(lk.at_columns(r[v], [col])) for r in (first, second))
-        assert a.any() and same_bits(a, b), v
+        assert a.any() and support.same_bits(a, b), v
         a, b = (np.ascontiguousarray(lk.at_columns(r[v], [col])) for r in (full_base, full_both))
-        assert not same_bits(a, b), v
+        assert not support.same_bits(a, b), v
 
 
 # ---------------------------------------------------------------------------------------------------- 4. the state
@@ -229,11 +224,11 @@ def test_state(plans, oracle_factory):
     o = oracle_factory("t30k5")
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
-    x = oracle_grids(o, sts)
-    obs = spread_obs(g, x, 40, seed=50)
-    inc, _, _ = li.analyse(g, x, obs, SIGMA_H, 0.1, RHO, 2, 2)
+    x = lk.oracle_grids(o, sts)
+    obs = lk.spread_obs(g, x, 40, seed=50)
+    inc, _, _ = li.analyse(g, x, obs, lk.SIGMA_H, 0.1, lk.RHO, 2, 2)
     grid = lambda a: a.reshape(a.shape[:-1] + (g.il, g.ix))
-    lt = make(sp, E, obs, 0.1)
+    lt = lk.make(sp, E, obs, 0.1)
     lt.set_weight_stride(2, 2)
     before = {n: getattr(ens, n).clone() for n in es.PROG}
     ens.analyse(lt)
@@ -246,7 +241,7 @@ def test_state(plans, oracle_factory):
                 "ps": st["ps"][0] + o.grid_to_spec(grid(inc["ps"][e]))}
         for n in es.PROG:
             a = getattr(ens, n)
-            assert es.same_bits(a[1], before[n][1]) and not es.same_bits(a[0], before[n][0]), n
+            assert support.same_bits(a[1], before[n][1]) and not support.same_bits(a[0], before[n][0]), n
             err = float(np.max(np.abs(a[0, e].cpu().numpy() - want[n])) / np.max(np.abs(want[n])))
             print("[letkf interp state] member %d %s: %.3e" % (e, n, err))
             assert err <= 1e-12, (n, e, err)
@@ -263,9 +258,9 @@ def test_capture(plans, oracle_factory):
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
     x0 = {n: getattr(ens, n).clone() for n in es.PROG}
-    xg = oracle_grids(oracle_factory("t30k5"), sts)
-    obs, other = spread_obs(g, xg, 20, seed=52), spread_obs(g, xg, 20, seed=53)
-    lt = make(sp, E, obs, 0.1)
+    xg = lk.oracle_grids(oracle_factory("t30k5"), sts)
+    obs, other = lk.spread_obs(g, xg, 20, seed=52), lk.spread_obs(g, xg, 20, seed=53)
+    lt = lk.make(sp, E, obs, 0.1)
     lt.set_weight_stride(2, 2)
 
     def eager(o):
@@ -276,7 +271,7 @@ def test_capture(plans, oracle_factory):
         torch.cuda.synchronize()
         return {n: getattr(ens, n).clone() for n in es.PROG}
     want_other, want = eager(other), eager(obs)
-    assert not es.same_bits(want["t"], x0["t"]) and not es.same_bits(want["t"], want_other["t"])
+    assert not support.same_bits(want["t"], x0["t"]) and not support.same_bits(want["t"], want_other["t"])
     sp.use_own_stream()
     torch.cuda.synchronize()
     try:
@@ -292,7 +287,7 @@ def test_capture(plans, oracle_factory):
             gr.launch()
             sp.synchronize()
             for n in es.PROG:
-                assert es.same_bits(getattr(ens, n), w[n]), n
+                assert support.same_bits(getattr(ens, n), w[n]), n
         gr.close()
     finally:
         sp.use_torch_stream()

@@ -14,6 +14,8 @@ import ensemblestep as es
 import guards
 import levels
 import modelstep
+import shardedstep
+import support
 import synth
 from conftest import TOL
 from dynstep import ROB, SDRAG, WIL, state, wave_relerr
@@ -135,7 +137,7 @@ def test_entry_points_vs_oracle(kx):
     assert C.intact(), ("spectral outputs", C.hits())
     assert G.intact(), ("grid outputs", G.hits())
     for n in d_in:
-        assert es.same_bits(d_in[n], keep[n]), n
+        assert support.same_bits(d_in[n], keep[n]), n
     for a, b in zip(g_in, h_in):
         assert np.array_equal(host(a), b)
     sp.close()
@@ -306,8 +308,7 @@ SHARDED = [(12, 5), (9, 2), (15, 4), (6, 4)]       # (kx, world): uneven level b
 def test_sharded_step_in_process_ranks(kx, world, oracle_factory, monkeypatch):
     """tests/test_gpu_sharded_step.py::test_sharded_step_in_process_ranks (the all-gather form) on a (trunc, kx) pair: bit-equal
     to the unsharded step, and within TOL of the oracle"""
-    import test_gpu_sharded_step as sh
-    sh.test_sharded_step_in_process_ranks(("t30", kx), world, oracle_factory, monkeypatch)
+    shardedstep.in_process_ranks(("t30", kx), world, oracle_factory, monkeypatch)
 
 
 @pytest.mark.parametrize("kx,world", SHARDED)
@@ -316,5 +317,4 @@ def test_sharded_step_transposed_in_process_ranks(kx, world, oracle_factory, mon
     from four ranks on -- belongs to its equal level blocks: spdy_comm_describe charges the all-gather form the average block and
     the transposed form the rank's own, so with ragged blocks the rank holding an extra level sits higher (6 levels on 4 ranks:
     0.6005 at the ranks with two levels).  Here every rank is held to receiving less than in the all-gather form."""
-    import test_gpu_sharded_step as sh
-    sh.transposed_in_process_ranks(("t30", kx), world, oracle_factory, monkeypatch, pays=1.0)
+    shardedstep.transposed_in_process_ranks(("t30", kx), world, oracle_factory, monkeypatch, pays=1.0)

@@ -8,6 +8,7 @@ import pytest
 import guards
 import modelstep
 import moist
+import support
 import synth
 from conftest import GOLDEN, TOL, VARIANTS
 from dynstep import ROB, oracle_dynamics_step, wave_relerr
@@ -19,16 +20,16 @@ FLOATS = ("ttend", "qtend", "precnv", "precls", "cbmf", "qsat", "rh", "se")
 INTS = ("iptop", "icnv")
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_moist_columns_vs_reference(tag):
     """spdy_moist_columns_dev with every optional output against the reference on the stored sample, and against the restatement
     on EVERY column (array norm and, per column by its own scale, guards.column_err): integers identical, floats within TOL."""
     z = np.load(os.path.join(GOLDEN, "ref_moist.npz"))
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
     ins = moist.grid_inputs(tab, (1, il, ix), int(z[tag + "_seed"]))
     sub = z[tag + "_sub"]
-    sp = moist.plan(tag)
+    sp = support.plan(tag)
     r = sp.moist_columns(*ins)
     sp.close()
     worst = 0.0
@@ -62,11 +63,11 @@ def test_null_outputs_and_batch_composition():
     """All optional outputs NULL leaves ttend / qtend bit-equal to the full call; nb = 1, 7, 64 states in one launch are each
     bit-equal to the same state launched alone."""
     import torch
-    sp = moist.plan("t30", 64)
-    ix, il, kx = moist.VARIANTS["t30"]
+    sp = support.plan("t30", 64)
+    ix, il, kx = support.grid("t30")
     tab = moist.tables(moist.HSG[kx])
     for nb in (1, 7, 64):
-        tg, qg, phig, pslg, tt, qt = (moist.dev(a) for a in moist.grid_inputs(tab, (nb, il, ix), 9100 + nb))
+        tg, qg, phig, pslg, tt, qt = (support.dev(a) for a in moist.grid_inputs(tab, (nb, il, ix), 9100 + nb))
         T, Q, out = tt.clone(), qt.clone(), sp.column_outputs(nb, "moist")
         sp.moist_columns_dev(tg, qg, phig, pslg, T, Q, out)
         T0, Q0 = tt.clone(), qt.clone()
@@ -87,8 +88,8 @@ def test_null_outputs_and_batch_composition():
 def test_moist_physics_from_spectra(tag, oracle_factory):
     """spdy_moist_physics_dev (one inverse launch + the column kernel) against the restatement on the oracle's transforms."""
     import torch
-    kx = moist.RES[tag][1]
-    sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
+    kx = support.grid(tag)[2]
+    sp, o = support.plan(tag, 4 * kx + 4), oracle_factory(tag)
     st = moist.state(o, dyn_state(sp, 8000), 4242)
     phi = o.geopotential(st["t"][0], st["phis"])
     il, ix = sp.il, sp.ix
@@ -98,8 +99,8 @@ def test_moist_physics_from_spectra(tag, oracle_factory):
     tt, qt = tt0.copy(), qt0.copy()
     moist.make_hook(rec)(o, st, None, None, tt, qt)
     assert rec["margin"].min() >= moist.MIN_MARGIN
-    T, Q, out = moist.dev(tt0), moist.dev(qt0), sp.column_outputs(1, "moist")
-    sp.moist_physics_dev(moist.dev(st["t"][0]), moist.dev(st["tr"][0]), moist.dev(phi), moist.dev(st["ps"][0]), T, Q, out)
+    T, Q, out = support.dev(tt0), support.dev(qt0), sp.column_outputs(1, "moist")
+    sp.moist_physics_dev(support.dev(st["t"][0]), support.dev(st["tr"][0]), support.dev(phi), support.dev(st["ps"][0]), T, Q, out)
     torch.cuda.synchronize()
     worst = max(synth.relerr(T.cpu().numpy(), tt), synth.relerr(Q.cpu().numpy(), qt))
     for n in ("precnv", "precls", "cbmf", "qsat", "rh", "se"):
@@ -118,7 +119,7 @@ def test_step_with_moist_physics(tag, oracle_factory):
     and its graph has exactly 3 nodes more than the adiabatic step's (geopotential, the inverse launch, the column kernel)."""
     import torch
     kx = VARIANTS[tag][3]
-    sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
+    sp, o = support.plan(tag, 4 * kx + 4), oracle_factory(tag)
     dt = 2400.0
     sp.initialize_implicit(dt); o.tail_init(dt)
     st = moist.state(o, dyn_state(sp, 8000), 5150)

@@ -8,11 +8,10 @@ import pytest
 
 import ensemblestep as es
 import letkf as lk
-import moist
 import nature as nt
+import support
 from conftest import TOL
 from dynstep import state as dyn_state
-from test_gpu_letkf import limits, oracle_grids
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +22,6 @@ EPS = lk.EPS
 LEVEL1 = ("vor", "div", "t", "tr", "ps")
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
-    return a.shape == b.shape and bool(np.array_equal(a.view(np.int64), b.view(np.int64)))
-
-
 def level1(D):
     """time level 1 of a single-state dict of device views (Ensemble.member), in set_state's order"""
     return [D[n][0] for n in LEVEL1]
@@ -35,7 +29,7 @@ def level1(D):
 
 def spectra(st):
     """time level 1 of a host state as device tensors, in set_state's order"""
-    return [moist.dev(np.ascontiguousarray(st[n][0], np.complex128)) for n in LEVEL1]
+    return [support.dev(np.ascontiguousarray(st[n][0], np.complex128)) for n in LEVEL1]
 
 
 def gridded(lt, sp):
@@ -76,19 +70,15 @@ def compare_scores(tag, got, want, rel, bias_abs):
     return r
 
 
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
+    return sp, lk.Geometry(sp), nt.gaussian_weights(sp)
+
+
 @pytest.fixture(scope="module")
 def plans():
-    made = {}
-
-    def get(tag="t30k5", nmem=32):
-        if tag not in made:
-            kx = moist.RES[tag][1]
-            sp = moist.plan(tag, nmem * (4 * kx + 4))
-            made[tag] = (sp, lk.Geometry(sp), nt.gaussian_weights(sp))
-        return made[tag]
-    yield get
-    for sp, _, _ in made.values():
-        sp.close()
+    with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
+        yield lambda tag="t30k5", nmem=32: get(tag, nmem)
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +87,7 @@ def case(plans, oracle_factory):
     the members (computed once, read only) and the 300-observation network"""
     sp, g, w = plans()
     sts = es.member_states(sp, E0)
-    x = oracle_grids(oracle_factory("t30k5"), sts)
+    x = lk.oracle_grids(oracle_factory("t30k5"), sts)
     return {"sp": sp, "g": g, "w": w, "sts": sts, "x": x, "truth_state": dyn_state(sp, 7000), "net": network(g, x)}
 
 
@@ -138,8 +128,8 @@ def test_truth(case, oracle_factory):
     ens.analyse(lt)
     torch.cuda.synchronize()
     hx = lt.field("hx").numpy()
-    assert same_bits(hx[:, 1], value)
-    assert not same_bits(hx[:, 0], value)
+    assert support.same_bits(hx[:, 1], value)
+    assert not support.same_bits(hx[:, 0], value)
     nat.close(); lt.close()
 
 
@@ -188,16 +178,16 @@ def test_noise(case):
         worst = float(np.max(np.abs(z - ref) / noise_limit(ref, h, net["error"])))
         print("[nature noise] draw %d: error / limit %.3f, mean %.3f, std %.3f" % (d, worst, z.mean(), z.std()))
         assert worst <= 1.0, (d, worst)
-    assert nat.draws() == 2 and not same_bits(values[0], values[1])
+    assert nat.draws() == 2 and not support.same_bits(values[0], values[1])
     nat.reset(SEED)
     nat.observe(lt, 1.0)
-    assert same_bits(lt.field("value").numpy(), values[0])
+    assert support.same_bits(lt.field("value").numpy(), values[0])
     nat.observe(lt, 0.5)                          # draw 1 at half the amplitude
     half = (lt.field("value").numpy() - h) / net["error"]
     assert float(np.max(np.abs(half - 0.5 * nt.draw(SEED, 1, NOBS)) / noise_limit(nt.draw(SEED, 1, NOBS), h, net["error"]))) <= 1.0
     nat.reset(SEED + 1)
     nat.observe(lt, 1.0)
-    assert not same_bits(lt.field("value").numpy(), values[0])
+    assert not support.same_bits(lt.field("value").numpy(), values[0])
     state = nat.field("state").numpy().view(np.uint64)
     assert int(state[0]) == SEED + 1 and int(state[1]) == 1
     nat.close(); lt.close()
@@ -218,7 +208,7 @@ def test_scores_of_a_state(case):
     assert not got[0].any()                       # slot 0 was never written
     sc = nat.scores(1)
     assert sc["rmse"]["t"].shape == (sp.kx,) and isinstance(sc["spread"]["ps"], float) and nat.scores()["bias"]["u"].shape == (2, sp.kx)
-    assert same_bits(nt.flat(sc), got[1])
+    assert support.same_bits(np.asarray(nt.flat(sc), np.float64), got[1])
     with pytest.raises(ValueError):               # the member count is the Letkf's
         es.build(sp, case["sts"][:2]).verify(lt, nat)
     nat.close(); lt.close()
@@ -235,7 +225,7 @@ def test_scores_member_extremes(E):
     x, truth = lk.ensemble(g, E, seed=60 + E), nt.as_truth(lk.ensemble(g, 1, seed=59))
     nat = s.Nature(sp, capacity=1)
     nat.field("truth").upload(nt.rows(truth))
-    nat.verify_grid(*[moist.dev(x[v]) for v in lk.VARS], slot=0)
+    nat.verify_grid(*[support.dev(x[v]) for v in lk.VARS], slot=0)
     rel, bias_abs = score_limits(g, x, truth, w, E)
     compare_scores("t30k2 E=%d" % E, nat.field("scores").numpy()[0], nt.flat(nt.scores(g, x, truth, w)), rel, bias_abs)
     nat.close(); sp.close()
@@ -270,11 +260,11 @@ def test_exact_statements(case):
     first = nat.field("scores").numpy()
     assert first[0].all() and not first[1].any()
     ens.verify(lt, nat, 0)
-    assert same_bits(nat.field("scores").numpy(), first)
+    assert support.same_bits(nat.field("scores").numpy(), first)
     nat.set_state(*spectra(case["truth_state"]))
     ens.verify(lt, nat, 1)
     after = nat.field("scores").numpy()
-    assert same_bits(after[0], first[0]) and after[1].all() and not same_bits(after[1], first[0])
+    assert support.same_bits(after[0], first[0]) and after[1].all() and not support.same_bits(after[1], first[0])
     nat.close(); lt.close()
 
 
@@ -294,7 +284,7 @@ def test_nonfinite_row_stays_in_its_row(case):
     row = 2 * kx + k
     others = np.arange(4 * kx + 1) != row
     assert np.isnan(got[:, row]).all() and np.isfinite(clean).all()
-    assert same_bits(got[:, others], clean[:, others])
+    assert support.same_bits(got[:, others], clean[:, others])
     nat.close(); lt.close()
 
 
@@ -336,16 +326,16 @@ def test_capture(case):
             gr.launch()
             sp.synchronize()
             got = nat.field("scores").numpy()
-            assert same_bits(got[0], eager[0]), r
+            assert support.same_bits(got[0], eager[0]), r
             slot1.append(got[1])
             if r == 0:
-                assert same_bits(got[1], eager[1]) and same_bits(lt.field("value").numpy(), eager_value)
+                assert support.same_bits(got[1], eager[1]) and support.same_bits(lt.field("value").numpy(), eager_value)
         assert nat.draws() == 3
         z, ref = (lt.field("value").numpy() - h) / net["error"], nt.draw(SEED, 2, NOBS)
         worst = float(np.max(np.abs(z - ref) / noise_limit(ref, h, net["error"])))
         print("[nature capture] draw 2 of the third replay: error / limit %.3f" % worst)
         assert worst <= 1.0
-        assert not same_bits(slot1[0], slot1[1]) and not same_bits(slot1[1], slot1[2])
+        assert not support.same_bits(slot1[0], slot1[1]) and not support.same_bits(slot1[1], slot1[2])
         gr.close()
     finally:
         sp.use_torch_stream()
@@ -355,11 +345,11 @@ def test_capture(case):
 # ---------------------------------------------------------------------------------------------------- 8. the twin condition
 def test_twin_condition_on_the_device():
     """The inputs of tests/test_nature_cpu.py's twin test through observe, Letkf.analyse_grid and the device scores.  The values
-    are the restatement's within the noise limit.  The background scores match the restatement's within the limits of the scores.
+    are the restatement's within the noise limit.  The background scores match the restatement's within the lk.limits of the scores.
     The analysis side: the device's increments are held to the restatement's (fed the device's own values) by tests/
     test_gpu_letkf.py's limit L_v per variable; a change of every member's error by at most L moves mbar by at most L, so rmse and
     bias by at most L (the weights sum to 1), and the deviations d_e - mbar by at most 2 L, so spread by at most 2 sqrt(E / (E -
-    1)) L <= 3 L; those are added to the scores' own limits.  And the analysis' rmse of t and ps is below the background's."""
+    1)) L <= 3 L; those are added to the scores' own lk.limits.  And the analysis' rmse of t and ps is below the background's."""
     import speedy_f90_amd as s
     c = nt.TWIN
     kx, E = c["kx"], c["E"]
@@ -375,7 +365,7 @@ def test_twin_condition_on_the_device():
     value = lt.field("value").numpy()
     h, zref = nt.operator(g, truth, net), nt.draw(c["noise_seed"], 0, c["nobs"])
     assert float(np.max(np.abs((value - h) / net["error"] - zref) / noise_limit(zref, h, net["error"]))) <= 1.0
-    xd = [moist.dev(x[v]) for v in lk.VARS]
+    xd = [support.dev(x[v]) for v in lk.VARS]
     nat.verify_grid(*xd, slot=0)
     inc = lt.analyse_grid(*xd)
     nat.verify_grid(*[a + b for a, b in zip(xd, inc)], slot=1)
@@ -384,7 +374,7 @@ def test_twin_condition_on_the_device():
     obs = dict(net)
     obs["value"] = value
     C, b = lk.problems(g, x, obs, c["sigma_h"], c["sigma_v"])
-    lim, ref_inc, kappa = limits(g, x, C, b, c["rho"], np.arange(g.ix * g.il), E)
+    lim, ref_inc, kappa = lk.limits(g, x, C, b, c["rho"], np.arange(g.ix * g.il), E)
     worst = {v: float(np.max(np.abs(lk.at_columns(a.cpu().numpy(), np.arange(g.ix * g.il)) - ref_inc[v]))) / lim[v]
              for v, a in zip(lk.VARS, inc)}
     print("[nature twin, device] kappa %.1f, increments / limit: %s" % (kappa, " ".join("%s %.3f" % kv for kv in worst.items())))

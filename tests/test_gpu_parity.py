@@ -7,6 +7,7 @@ tests/test_oracle_golden.py); nothing here reads /root/reference.
 import numpy as np
 import pytest
 
+import support
 import synth
 from conftest import TOL
 from synth import tail_inputs
@@ -18,17 +19,12 @@ TAGS = ("t30", "t63")
 @pytest.fixture(scope="module")
 def plans():
     import speedy_f90_amd as s
-    cache = {}
-
-    def get(tag, max_batch=256, fused=-1):
-        key = (tag, max_batch)
-        if key not in cache:
-            cache[key] = s.Spectral(tag, kx=8, max_batch=max_batch, device=0)
-        cache[key].set_fused(fused)      # 1 = fused single-pass kernels (T30), 0 = four-kernel path
-        return cache[key]
-    yield get
-    for p in cache.values():
-        p.close()
+    with support.plan_cache(lambda tag, max_batch: s.Spectral(tag, kx=8, max_batch=max_batch, device=0)) as cached:
+        def get(tag, max_batch=256, fused=-1):
+            sp = cached(tag, max_batch)
+            sp.set_fused(fused)      # 1 = fused single-pass kernels (T30), 0 = four-kernel path
+            return sp
+        yield get
 
 
 def ok(x, ref, tol=TOL):

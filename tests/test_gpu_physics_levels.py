@@ -20,25 +20,21 @@ import os
 import numpy as np
 import pytest
 
+import ensemblestep as es
 import guards
-import levels
 import modelstep
 import moist
 import physlevels as pl
 import physstep
 import radiation
 import sppt
+import support
 import surface
 import synth
-import thresholds
+import thresholds as th
 from conftest import GOLDEN, TOL
 from dynstep import ROB, oracle_dynamics_step, wave_relerr
 from modelstep import PROG
-from test_gpu_ensemble import _physics_members
-from test_gpu_physics_step import TEND, _gridded, _plan_case, _run_gridded, check_physics_from_spectra
-from test_gpu_sppt import _mu
-from test_gpu_surface import PBL_OUT, SFC_OUT, _case
-from test_gpu_thresholds import check_threshold_columns
 
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +53,7 @@ def _tag(kx):
 
 
 def _levels_plan(kx, max_batch=64):
-    """(plan, its half levels): what the helpers of the other physics tests take for a count outside moist.VARIANTS"""
+    """(plan, its half levels): what the helpers of the other physics tests take for a count outside support.PHYSICS_TAGS"""
     return pl.plan(kx, max_batch), pl.hsg(kx)
 
 
@@ -151,7 +147,7 @@ def test_surface_and_pbl_columns(kx, ref):
     """spdy_surface_fluxes_dev and spdy_pbl_dev with every optional output: the stored sample against the reference, every
     column against the restatement; utend and vtend above level kx untouched."""
     tag = _tag(kx)
-    sp, tab, c, zon, sqcoa = _case(tag, int(ref["sfc_%s_seed" % tag]), plan=_levels_plan(kx))
+    sp, tab, c, zon, sqcoa = surface.case(tag, int(ref["sfc_%s_seed" % tag]), plan=_levels_plan(kx))
     sub = ref["sfc_%s_sub" % tag]
     sp.surface_set_orography(c["phis0"].reshape(IL, IX))
     r, _ = surface.chain(tab, c, zon, sqcoa)
@@ -161,7 +157,7 @@ def test_surface_and_pbl_columns(kx, ref):
     errs = {}
     s = sp.surface_columns(G(c["ug"]), G(c["vg"]), G(c["tg"]), G(c["qg"]), G(c["phig"]), G(c["pslg"]), G(r["ssrd"]),
                            G(r["down"]["slrd"]), bnd)
-    for n in SFC_OUT:
+    for n in surface.SFC_OUT:
         got = s[n].reshape(-1, NCOL).squeeze()
         _err(errs, n + " vs reference", got[..., sub], ref["sfc_%s_%s" % (tag, n)])
         _err(errs, n, got, r["sfc"][n])
@@ -170,7 +166,7 @@ def test_surface_and_pbl_columns(kx, ref):
     m, up = r["moist"], r["up"]
     p = sp.pbl_columns(G(c["qg"]), G(c["phig"]), G(c["pslg"]), G(m["se"]), G(m["rh"]), G(m["qsat"]), G(m["icnv"]),
                        np.stack([G(f) for f in r["flux3"]]), G(c["utend"]), G(c["vtend"]), G(up["ttend"]), G(m["qtend"]))
-    for n in PBL_OUT:
+    for n in surface.PBL_OUT:
         got, want = p[n].reshape(-1, NCOL).squeeze(), r["pbl"][n]
         if n in ("utend", "vtend"):
             assert np.array_equal(got[:kx - 1], np.asarray(c[n])[:kx - 1]), n     # untouched above level kx
@@ -204,20 +200,20 @@ def test_nothing_written_outside_kx_levels(kx):
     an unused level of a KMAX = 16 kernel could reach.  The bands are unchanged, every output is written (none left NaN) and
     equals the one an ordinary allocation receives."""
     import torch
-    sp, _, il, ix, d1, d2 = _gridded(_tag(kx), 1, pl.CHAIN_SEED[kx], plan=_levels_plan(kx))
+    sp, _, il, ix, d1, d2 = physstep.gridded(_tag(kx), 1, pl.CHAIN_SEED[kx], plan=_levels_plan(kx))
     sp.column_physics_workspace()
-    plain = _run_gridded(sp, 1, kx, il, ix, d1, d2, True)
+    plain = physstep.run_gridded(sp, 1, kx, il, ix, d1, d2, True)
     for fused in (1, 0):
         sp.set_option("physics_fused", fused)
         S0 = torch.empty((sp.radiation_state_size(),), dtype=torch.float64, device="cuda")
         outs = [sp.column_outputs(1), sp.column_outputs(1)]
         flat = [physstep.flat_outs(o) for o in outs]
-        names = [("state", S0)] + [("%s%d" % (n, i), d[n]) for i, d in ((1, d1), (2, d2)) for n in TEND]
+        names = [("state", S0)] + [("%s%d" % (n, i), d[n]) for i, d in ((1, d1), (2, d2)) for n in physstep.TEND]
         names += [("out%d.%s" % (i + 1, n), t) for i in range(2) for n, t in flat[i].items()]
         g, views = _guarded_like(torch, [t for _, t in names], 16 - kx + 1)
         V = dict(zip([n for n, _ in names], views))
         for i, d in ((1, d1), (2, d2)):
-            for n in TEND:
+            for n in physstep.TEND:
                 V["%s%d" % (n, i)].copy_(d[n])
         assert g.intact()
         for i, d, sw in ((1, d1, True), (2, d2, False)):
@@ -226,11 +222,11 @@ def test_nothing_written_outside_kx_levels(kx):
             if i == 2:                     # ssrd stays where the shortwave call put it (include/spdy.h)
                 out["rad"]["ssrd"] = V["out1.rad.ssrd"]
             sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], V["state"],
-                                  *[V["%s%d" % (n, i)] for n in TEND], out)
+                                  *[V["%s%d" % (n, i)] for n in physstep.TEND], out)
         torch.cuda.synchronize()
         assert g.intact(), (fused, [(names[min(b, len(names) - 1)][0], j) for b, j in g.hits()])
         for n, v in V.items():
-            if n.startswith("out2.") and n[5:] in thresholds.SW_ONLY:
+            if n.startswith("out2.") and n[5:] in th.SW_ONLY:
                 continue                   # written by shortwave calls only
             assert torch.equal(v, plain[n]), (fused, n)
     sp.close()
@@ -244,13 +240,13 @@ def test_one_launch_equals_five_calls(kx, nb):
     shortwave call and then a call without shortwave on the held state; torch.equal on the tendencies, every output and the
     radiation state; with out = NULL the tendencies and the radiation state equal those of the all-outputs run."""
     import torch
-    sp, _, il, ix, d1, d2 = _gridded(_tag(kx), nb, 9800 + 10 * kx + nb, plan=_levels_plan(kx))
+    sp, _, il, ix, d1, d2 = physstep.gridded(_tag(kx), nb, 9800 + 10 * kx + nb, plan=_levels_plan(kx))
     sp.column_physics_workspace()
     runs = {}
     for fused in (1, 0):
         sp.set_option("physics_fused", fused)
         for with_out in (True, False):
-            runs[fused, with_out] = _run_gridded(sp, nb, kx, il, ix, d1, d2, with_out)
+            runs[fused, with_out] = physstep.run_gridded(sp, nb, kx, il, ix, d1, d2, with_out)
     full = runs[0, True]
     assert len(full) > 60
     for n, v in full.items():
@@ -267,13 +263,13 @@ def test_batch_composition_at_12_levels():
     against each state alone, both calls, the radiation state included."""
     import torch
     kx, nb = 12, 3
-    sp, _, il, ix, d1, d2 = _gridded(_tag(kx), nb, 9900 + kx, plan=_levels_plan(kx))
+    sp, _, il, ix, d1, d2 = physstep.gridded(_tag(kx), nb, 9900 + kx, plan=_levels_plan(kx))
     sp.column_physics_workspace()
-    full = _run_gridded(sp, nb, kx, il, ix, d1, d2, True)
+    full = physstep.run_gridded(sp, nb, kx, il, ix, d1, d2, True)
     size = sp.radiation_state_size()
     assert not torch.equal(full["ttend1"][0], full["ttend1"][1])
     for b in range(nb):
-        one = _run_gridded(sp, 1, kx, il, ix, *[{n: v[b:b + 1].contiguous() for n, v in d.items()} for d in (d1, d2)], True)
+        one = physstep.run_gridded(sp, 1, kx, il, ix, *[{n: v[b:b + 1].contiguous() for n, v in d.items()} for d in (d1, d2)], True)
         for n, v in one.items():
             want = full[n][b * size:(b + 1) * size] if n.startswith("state") else full[n][b:b + 1]
             assert torch.equal(v, want), (b, n)
@@ -281,15 +277,11 @@ def test_batch_composition_at_12_levels():
 
 
 # ------------------------------------------------------------------------------------------------------ from spectra
-def _levels_case(kx, max_batch=None):
-    return pl.plan(kx, max_batch or 4 * kx + 4), levels.oracle("t30", kx), pl.hsg(kx), pl.CASE_SEEDS[kx]
-
-
 @pytest.mark.parametrize("kx", sorted(pl.CASE_SEEDS))
 def test_physics_from_spectra(kx):
     """spdy_physics_dev against tests/levels.py's oracle transforms and the chain of restatements, a shortwave call and a call
     without shortwave, after check_coverage: tests/test_gpu_physics_step.py::test_physics_from_spectra's body."""
-    name, worst = check_physics_from_spectra(_tag(kx), *_plan_case(_tag(kx), None, _levels_case(kx)))
+    name, worst = physstep.check_physics_from_spectra(_tag(kx), *physstep.plan_case(_tag(kx), None, pl.levels_case(kx)))
     assert worst <= TOL, (name, worst)
 
 
@@ -300,7 +292,7 @@ def test_step_with_whole_physics_at_12_levels():
     import torch
     kx = 12
     tag = _tag(kx)
-    sp, o, case, _ = _plan_case(tag, None, _levels_case(kx))
+    sp, o, case, _ = physstep.plan_case(tag, None, pl.levels_case(kx))
     dt = pl.DT
     sp.initialize_implicit(dt); o.tail_init(dt)
     sp.physics_workspace()
@@ -348,30 +340,30 @@ def test_sppt_on_gridded_states(kx):
     call without SPPT.  At 12 levels the first run of the SPPT kernel's <16> form with unused levels."""
     import torch
     nb, keep = 2, {}
-    sp, _, il, ix, d, _ = _gridded(_tag(kx), nb, 9950 + kx, plan=_levels_plan(kx), keep=keep)
+    sp, _, il, ix, d, _ = physstep.gridded(_tag(kx), nb, 9950 + kx, plan=_levels_plan(kx), keep=keep)
     r, _ = surface.chain(keep["tab"], keep["c1"], keep["zon"], keep["sqcoa"])
     physstep.check_coverage(r, "%s sppt" % _tag(kx))
-    mu = _mu(kx)
+    mu = sppt.mu(kx)
     P = np.clip(1.5 * (2.0 * synth.splitmix64(9960 + kx, nb * kx * il * ix) - 1.0), -1.0, 1.0).reshape(nb, kx, il, ix)
     assert (P == 1.0).any() and (P == -1.0).any() and ((P > -1.0) & (P < 1.0)).mean() > 0.5
-    dP = moist.dev(P)
+    dP = support.dev(P)
     sp.column_physics_sppt_workspace()
     nan_state = lambda: torch.full((nb * sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
     args = lambda T, S: (True, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T)
-    T0 = [d[n].cpu().numpy() for n in TEND]
-    T, S = [d[n].clone() for n in TEND], nan_state()
+    T0 = [d[n].cpu().numpy() for n in physstep.TEND]
+    T, S = [d[n].clone() for n in physstep.TEND], nan_state()
     sp.column_physics_dev(*args(T, S))
     torch.cuda.synchronize()
     own = [sppt.apply(np.moveaxis(t.cpu().numpy(), 1, 0), np.moveaxis(t0, 1, 0), np.moveaxis(P, 1, 0), mu) for t, t0 in zip(T, T0)]
     want = [sppt.apply(radiation.grids(r["pbl"][n], nb, il, ix).swapaxes(0, 1), np.moveaxis(t0, 1, 0), np.moveaxis(P, 1, 0), mu)
-            for n, t0 in zip(TEND, T0)]
+            for n, t0 in zip(physstep.TEND, T0)]
     errs = {}
     for fused in (1, 0):
         sp.set_option("physics_fused", fused)
-        T2, S2 = [d[n].clone() for n in TEND], nan_state()
+        T2, S2 = [d[n].clone() for n in physstep.TEND], nan_state()
         sp.column_physics_sppt_dev(dP, mu, *args(T2, S2))
         torch.cuda.synchronize()
-        for n, t, a, w in zip(TEND, T2, own, want):
+        for n, t, a, w in zip(physstep.TEND, T2, own, want):
             g = np.moveaxis(t.cpu().numpy(), 1, 0)
             assert np.array_equal(g, a), (fused, n)
             _err(errs, n, g, w)
@@ -387,14 +379,14 @@ def test_ensemble_physics_at_12_levels():
     call without: each member's tendencies, optional outputs and radiation state bit-equal to spdy_physics_dev on its own."""
     import torch
     kx, E = 12, 2
-    sp, o, hsg, seeds = _levels_case(kx, E * (4 * kx + 4))
-    sts, bnds = _physics_members(sp, o, E, hsg, seeds)
+    sp, o, hsg, seeds = pl.levels_case(kx, E * (4 * kx + 4))
+    sts, bnds = es.physics_members(sp, o, E, hsg, seeds)
     il, ix = sp.il, sp.ix
     dev = [physstep.device_boundary(b, il, ix) for b in bnds]
-    spec = [[moist.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], o.geopotential(st["t"][0], st["phis"]),
-                                    st["ps"][0])] for st in sts]
+    spec = [[support.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], o.geopotential(st["t"][0], st["phis"]),
+                                      st["ps"][0])] for st in sts]
     assert not torch.equal(spec[0][2], spec[1][2])
-    t0 = [[moist.dev(synth.splitmix64(270 + 4 * e + i, kx * il * ix).reshape(kx, il, ix) * f) for i, f in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
+    t0 = [[support.dev(synth.splitmix64(270 + 4 * e + i, kx * il * ix).reshape(kx, il, ix) * f) for i, f in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
           for e in range(E)]
     size = sp.radiation_state_size()
     nan_state = lambda n: torch.full((n * size,), float("nan"), dtype=torch.float64, device="cuda")
@@ -421,7 +413,7 @@ def test_ensemble_physics_at_12_levels():
                 out["rad"]["ssrd"] = ssrd[e]
             sp.physics_dev(sw, *spec[e], dev[e], dev[e]["albsfc"], S[e], *T, out)
             torch.cuda.synchronize()
-            for n, a, b in zip(TEND, eT, T):
+            for n, a, b in zip(physstep.TEND, eT, T):
                 assert torch.equal(a[e], b), (sw, e, n)
             for n, t in physstep.flat_outs(out).items():
                 assert torch.equal(flat[n][e:e + 1], t), (sw, e, n)
@@ -437,4 +429,4 @@ def test_threshold_columns_at_12_levels(ref):
     kx = pl.THRESHOLD_COUNT
     pre = "thr_%s_" % _tag(kx)
     stored = lambda step: {k[len(pre) + 3:]: ref[k] for k in ref.files if k.startswith("%sc%d_" % (pre, step))}
-    check_threshold_columns(_tag(kx), pl.plan(kx, 4), pl.tables(kx), int(ref[pre + "seed"]), ref[pre + "sub"], stored)
+    th.check_threshold_columns(_tag(kx), pl.plan(kx, 4), pl.tables(kx), int(ref[pre + "seed"]), ref[pre + "sub"], stored)

@@ -9,47 +9,25 @@ import pytest
 
 import longrun
 import modelstep
-import moist
 import physstep
+import support
 import synth
 from conftest import TOL
 from dynstep import wave_relerr
 from modelstep import PROG
-from test_gpu_physics_step import TEND, _errors
+from physstep import KX, TEND
 
 pytestmark = pytest.mark.gpu
-
-KX = 8
 
 
 def _setup(name, oracle_factory):
     o = oracle_factory("t30")
-    sp = moist.plan("t30", 4 * KX + 4)
+    sp = support.plan("t30", 4 * KX + 4)
     case = physstep.run_case(sp, o, name)
     sp.surface_set_orography(case.phis0)
     sp.physics_workspace()
     sp.use_own_stream()
     return sp, o, case
-
-
-def _rad_errors(got, ref):
-    """got, ref [6 kx + 7, ncol]: the relative error of each part of the radiation state (tt_rsw is 1e-7 of the fluxes' size: one
-    norm over the whole array would not see it)"""
-    assert np.all(np.isfinite(got)), "radiation state not finite"
-    return {n: synth.relerr(got[r], ref[r]) for n, r in physstep.rad_state_rows(KX).items()}
-
-
-def _checkpoint_errors(got, ref, ncol):
-    """got: device tensors, ref: arrays, of one checkpoint -> {name: relative error, the larger of the plain and the mean-free norm}"""
-    e = {}
-    for k in PROG:
-        g = got[k].cpu().numpy()
-        assert np.all(np.isfinite(g.real)) and np.all(np.isfinite(g.imag)), k
-        e[k] = max(synth.relerr(g, ref[k]), wave_relerr(g, ref[k]))
-    rad = _rad_errors(got["rad"].cpu().numpy().reshape(-1, ncol), ref["rad"])
-    e["rad"] = max(rad.values())
-    assert all(v == v for v in list(e.values()) + list(rad.values())), (e, rad)          # max() drops a NaN
-    return e
 
 
 def _device_run(sp, case, adiabatic_nodes=False):
@@ -108,7 +86,7 @@ def test_two_day_run_with_physics(name, oracle_factory):
     got, nodes = _device_run(sp, case, adiabatic_nodes=True)
     lines, worst = [], ("", 0.0)
     for n in longrun.CHECKPOINTS:
-        e = _checkpoint_errors(got[n], cps[n], ncol)
+        e = physstep.checkpoint_errors(got[n], cps[n], ncol)
         lines.append("step %2d: " % n + " ".join("%s %.1e" % kv for kv in e.items()))
         worst = max([worst] + [("step %d %s" % (n, k), v) for k, v in e.items()], key=lambda x: x[1])
     print("\n[2-day run with the whole physics '%s' vs the reference side, relative error (max of plain and mean-free norm); "
@@ -154,11 +132,11 @@ def test_resynchronised_steps(name, oracle_factory):
         ref_t = [np.zeros((KX, il, ix)) for _ in TEND]
         r = case.physics(st, sw, rs, *ref_t)
         assert float(r["margin"].min()) >= physstep.RUN_MARGIN
-        held = moist.dev(pre[n]["rs"]["ssrd_held"].reshape(1, il, ix))
-        S = moist.dev(physstep.rad_state_array(pre[n]["rs"], KX).reshape(-1))
+        held = support.dev(pre[n]["rs"]["ssrd_held"].reshape(1, il, ix))
+        S = support.dev(physstep.rad_state_array(pre[n]["rs"], KX).reshape(-1))
         phi = o.geopotential(st["t"][0], st["phis"])
-        spec = [moist.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])]
-        T, out = [moist.dev(a * 0.0) for a in ref_t], sp.column_outputs(1)
+        spec = [support.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])]
+        T, out = [support.dev(a * 0.0) for a in ref_t], sp.column_outputs(1)
         if not sw:                      # ssrd stays where the last shortwave call put it (include/spdy.h): the reference's
             out["rad"]["ssrd"] = held.clone()
         torch.cuda.synchronize()        # the uploads are torch's stream's, the calls the plan's
@@ -172,13 +150,13 @@ def test_resynchronised_steps(name, oracle_factory):
             for name in ("cloudc", "clstr", "icltop", "ssrd", "ssr", "tsr", "tt_rsw"):
                 exp["rad"].pop(name, None)
             assert torch.equal(out["rad"]["ssrd"], held)
-        _errors(out, exp, errs, label)
+        physstep.errors(out, exp, errs, label)
         after = physstep.rad_state_array(rs, KX)
-        for name, e in _rad_errors(S.cpu().numpy().reshape(-1, ncol), after).items():
+        for name, e in physstep.rad_errors(S.cpu().numpy().reshape(-1, ncol), after).items():
             errs["%s state %s" % (label, name)] = e
         # (ii) the whole step
         D = modelstep.device_state(st)
-        P = {"bnd": bnd, "rad": moist.dev(physstep.rad_state_array(pre[n]["rs"], KX).reshape(-1))}
+        P = {"bnd": bnd, "rad": support.dev(physstep.rad_state_array(pre[n]["rs"], KX).reshape(-1))}
         torch.cuda.synchronize()
         modelstep.step(sp, D, W, dt, physics=modelstep.whole_physics(P, sw, out={"rad": {"ssrd": held}}))
         sp.synchronize()
@@ -187,7 +165,7 @@ def test_resynchronised_steps(name, oracle_factory):
             g = D[k].cpu().numpy()
             errs["%s %s" % (label, k)] = max(synth.relerr(g, pre[n]["new"][k]), wave_relerr(g, pre[n]["new"][k]))
         errs["%s PL" % label] = synth.relerr(W.PL.cpu().numpy(), pre[n]["out"]["PL"])
-        for name, e in _rad_errors(P["rad"].cpu().numpy().reshape(-1, ncol), after).items():
+        for name, e in physstep.rad_errors(P["rad"].cpu().numpy().reshape(-1, ncol), after).items():
             errs["%s state %s" % (label, name)] = e
     assert all(v == v for v in errs.values()), [k for k, v in errs.items() if v != v]
     top = sorted(errs.items(), key=lambda kv: -kv[1])

@@ -2,46 +2,18 @@
 csrc/spdy_column_chain.hip) from spectra against the oracle's transforms and the chain of restatements (tests/physstep.py); the
 one-launch kernel against the five calls bit for bit; a whole time step with the whole physics for three consecutive steps
 against oracle_dynamics_step, captured and replayed, and twice from the same inputs."""
-import numpy as np
 import pytest
 
 import modelstep
-import moist
 import physstep
 import radiation
-import surface
+import support
 import synth
-from conftest import TOL, VARIANTS
+from conftest import TOL
 from dynstep import ROB, oracle_dynamics_step, wave_relerr
 from modelstep import PROG
 
 pytestmark = pytest.mark.gpu
-
-TEND = ("utend", "vtend", "ttend", "qtend")
-
-
-def _plan_case(tag, oracle_factory, levels_case=None):
-    """levels_case: (sp, o, half levels, physstep.Case seeds) of a count outside conftest.VARIANTS (tests/levels.py)"""
-    if levels_case is None:
-        kx = VARIANTS[tag][3]
-        sp, o = moist.plan(tag, 4 * kx + 4), oracle_factory(tag)
-        case = physstep.Case(tag, sp, o)
-    else:
-        sp, o, hsg, seeds = levels_case
-        kx, case = sp.kx, physstep.Case(tag, sp, o, hsg=hsg, seeds=seeds)
-    sp.surface_set_orography(case.phis0)
-    return sp, o, case, kx
-
-
-def _errors(out, exp, errs, label):
-    """every optional output against the reference: integers identical; the floats' relative errors into errs"""
-    got, want = physstep.flat_outs(out), physstep.flat_outs(exp)
-    for n, w in want.items():
-        g = got[n].cpu().numpy()[0]
-        if g.dtype == np.int32:
-            assert np.array_equal(g, w.astype(np.int32)), (label, n)
-        else:
-            errs["%s %s" % (label, n)] = synth.relerr(g, w)
 
 
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
@@ -49,96 +21,7 @@ def test_physics_from_spectra(tag, oracle_factory):
     """spdy_physics_dev on a shortwave call and a call without shortwave on the held state: the four tendencies, every optional
     output of every block and the radiation state against the reference within TOL, integers identical.
     Measured on MI355X: worst 4.3e-14 (t30), 8.8e-14 (t63k16) over 68 arrays."""
-    check_physics_from_spectra(tag, *_plan_case(tag, oracle_factory))
-
-
-def check_physics_from_spectra(tag, sp, o, case, kx):
-    """the body of test_physics_from_spectra on a plan, its oracle and their physstep.Case; returns the worst (array, error)"""
-    import torch
-    il, ix = sp.il, sp.ix
-    st = case.st
-    phi = o.geopotential(st["t"][0], st["phis"])
-    spec = [moist.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])]
-    bnd = physstep.device_boundary(case.bnd, il, ix)
-    S = torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
-    rs, errs = {}, {}
-    for step, sw in ((1, True), (2, False)):
-        t0 = [synth.splitmix64(70 + 4 * step + i, kx * il * ix).reshape(kx, il, ix) * s for i, s in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
-        ref_t = [a.copy() for a in t0]
-        r = case.physics(st, sw, rs, *ref_t)
-        if step == 1:
-            physstep.check_coverage(r, tag)
-        assert float(r["margin"].min()) >= physstep.MIN_MARGIN
-        T, out = [moist.dev(a) for a in t0], sp.column_outputs(1)
-        if sw:
-            ssrd = out["rad"]["ssrd"]
-        else:                          # ssrd stays where the shortwave call put it (include/spdy.h)
-            out["rad"]["ssrd"] = ssrd
-        sp.physics_dev(sw, *spec, bnd, bnd["albsfc"], S, *T, out)
-        torch.cuda.synchronize()
-        for n, a, b in zip(TEND, T, ref_t):
-            errs["step %d %s" % (step, n)] = synth.relerr(a.cpu().numpy(), b)
-        exp = physstep.expected(r, kx, il, ix)
-        if not sw:                     # written by shortwave calls only: the device leaves them as they were
-            for n in ("cloudc", "clstr", "icltop", "ssrd", "ssr", "tsr", "tt_rsw"):
-                exp["rad"].pop(n, None)
-        _errors(out, exp, errs, "step %d" % step)
-        errs["step %d radiation state" % step] = synth.relerr(S.cpu().numpy().reshape(6 * kx + 7, il * ix),
-                                                              physstep.rad_state_array(rs, kx))
-    top = sorted(errs.items(), key=lambda kv: -kv[1])
-    print("\n[physics from spectra %s] %d arrays, worst %.1e; largest: %s" % (tag, len(errs), top[0][1],
-                                                                             ", ".join("%s %.1e" % kv for kv in top[:8])))
-    assert top[0][1] <= TOL, top[0]
-    sp.close()
-    return top[0]
-
-
-def _gridded(tag, nb, seed, plan=None, keep=None):
-    """nb gridded states of surface.columns with the plan that holds their date and orography.  plan: (sp, its half levels) of a
-    count outside moist.VARIANTS (tests/levels.py), used in place of the plan of tag.  keep: a dict that receives the reference
-    side of the states (tab, zon, sqcoa, and the columns c1, c2 of the two calls)"""
-    import torch
-    if plan is None:
-        ix, il, kx = moist.VARIANTS[tag]
-        sp, hsg = moist.plan(tag, 64), moist.HSG[kx]
-    else:
-        sp, hsg = plan
-        ix, il, kx = sp.ix, sp.il, sp.kx
-    sp.radiation_set_date(radiation.DATES[0])
-    tab = moist.tables(hsg)
-    zon = radiation.zonal_columns({n: sp.table(n) for n in physstep.ZON}, nb, il, ix)
-    sqcoa = surface.sqcoa_columns(sp.table("coa_half"), nb, il, ix)
-    c = surface.columns(tab, nb * il * ix, seed, zon, sqcoa)
-    ph = c["phis0"].reshape(nb, il * ix)
-    ph[:] = ph[0]
-    sp.surface_set_orography(ph[0].reshape(il, ix))
-    G = lambda a: moist.dev(radiation.grids(a, nb, il, ix))
-    c2 = dict(c, tg=c["tg2"], ug=c["vg"], vg=c["ug"], sst=c["sst"] + 0.5, stl=c["stl"] - 0.5, ttend=c["ttend2"])
-    names = ("ug", "vg", "tg", "qg", "phig", "pslg", "albsfc") + TEND + surface.BOUNDARY
-    if keep is not None:
-        keep.update(tab=tab, zon=zon, sqcoa=sqcoa, c1=c, c2=c2)
-    return sp, kx, il, ix, {n: G(c[n]) for n in names}, {n: G(c2[n]) for n in names}
-
-
-def _run_gridded(sp, nb, kx, il, ix, d1, d2, with_out):
-    """a shortwave call, then a call without shortwave on the held state; returns everything written, by name"""
-    import torch
-    S = torch.full((nb * sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
-    res = {"state": S}
-    for i, d, sw in ((1, d1, True), (2, d2, False)):
-        T = [d[n].clone() for n in TEND]
-        out = sp.column_outputs(nb) if with_out else None
-        if with_out and i == 2:        # ssrd stays where the shortwave call put it (include/spdy.h)
-            out["rad"]["ssrd"] = res["out1.rad.ssrd"]
-        sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T, out)
-        res.update({"%s%d" % (n, i): t for n, t in zip(TEND, T)})
-        if with_out:
-            res.update({"out%d.%s" % (i, n): t for n, t in physstep.flat_outs(out).items()})
-        if i == 1:
-            torch.cuda.synchronize()
-            res["state1"] = S.clone()
-    torch.cuda.synchronize()
-    return res
+    physstep.check_physics_from_spectra(tag, *physstep.plan_case(tag, oracle_factory))
 
 
 @pytest.mark.parametrize("nb", [1, 3])
@@ -148,13 +31,13 @@ def test_one_launch_equals_five_calls(tag, nb):
     held state: torch.equal on the tendencies, every requested output and the radiation state; with out = NULL the tendencies
     and the radiation state also equal those of the all-outputs run."""
     import torch
-    sp, kx, il, ix, d1, d2 = _gridded(tag, nb, 9800 + nb)
+    sp, kx, il, ix, d1, d2 = physstep.gridded(tag, nb, 9800 + nb)
     sp.column_physics_workspace()
     runs = {}
     for fused in (1, 0):
         sp.set_option("physics_fused", fused)
         for with_out in (True, False):
-            runs[fused, with_out] = _run_gridded(sp, nb, kx, il, ix, d1, d2, with_out)
+            runs[fused, with_out] = physstep.run_gridded(sp, nb, kx, il, ix, d1, d2, with_out)
     full = runs[0, True]
     assert len(full) > 60
     for n, v in full.items():
@@ -174,7 +57,7 @@ def test_step_with_whole_physics(tag, oracle_factory):
     date and new boundary values; with the one-launch kernel the graph has exactly 3 nodes more than the adiabatic step's.
     Measured on MI355X: worst 2.9e-13 (t30, third step), 1.4e-14 (t63k16); nodes 4 -> 7 (t30), 5 -> 8 (t63k16), 12 / 13 as five calls."""
     import torch
-    sp, o, case, kx = _plan_case(tag, oracle_factory)
+    sp, o, case, kx = physstep.plan_case(tag, oracle_factory)
     dt = physstep.DT[tag]
     sp.initialize_implicit(dt); o.tail_init(dt)
     sp.physics_workspace()
@@ -223,7 +106,7 @@ def test_step_with_whole_physics(tag, oracle_factory):
     for n, v in physstep.device_boundary(bnd2, sp.il, sp.ix).items():
         P["bnd"][n].copy_(v)
     for n in case.st:
-        D[n].copy_(moist.dev(case.st[n]))
+        D[n].copy_(support.dev(case.st[n]))
     P["rad"].fill_(float("nan"))
     torch.cuda.synchronize()
     rep = []

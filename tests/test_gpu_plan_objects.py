@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import longrun
-import moist
+import support
 import surfmodel as sm
 import synth
 from conftest import TOL
@@ -18,7 +18,7 @@ KX, MAX_BATCH, NMEM = 8, 64, 2
 
 def test_plan_closed_before_its_objects_and_their_graph(oracle_factory):
     import torch
-    s = moist.package()
+    s = support.package()
     sp = s.Spectral("t30", kx=KX, max_batch=MAX_BATCH, device=0)
     # one object of each kind, each where its capturable call is legal
     phis0 = sm.orography(sp)

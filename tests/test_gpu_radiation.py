@@ -8,6 +8,7 @@ import pytest
 
 import moist
 import radiation
+import support
 import synth
 from conftest import GOLDEN, TOL
 
@@ -29,19 +30,19 @@ def _assert_close(got, want, key):
     return e
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_radiation_columns_vs_reference(tag):
     """radiation_columns with every optional output against the reference at both dates (integers identical, floats within TOL),
     then the step without shortwave on the held state against the reference and the restatement."""
     z = np.load(os.path.join(GOLDEN, "ref_radiation.npz"))
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     ncol = il * ix
     tab = moist.tables(moist.HSG[kx])
     zon0 = radiation.zonal_columns({n: z["%s_d0_%s" % (tag, n)] for n in ZON}, 1, il, ix)
     c = radiation.columns(tab, ncol, int(z[tag + "_seed"]), zon0)
     sub = z[tag + "_sub"]
     G = lambda n: _g(c, n, il, ix)
-    sp = moist.plan(tag)
+    sp = support.plan(tag)
     worst = 0.0
     for di, ty in enumerate(radiation.DATES):
         sp.radiation_set_date(ty)
@@ -67,8 +68,8 @@ def _inputs(tab, nb, il, ix, seed, sp):
     zl = {n: sp.table(n) for n in ZON}
     zon = radiation.zonal_columns(zl, nb, il, ix)
     c = radiation.columns(tab, nb * il * ix, seed, zon)
-    d = {n: moist.dev(radiation.grids(c[n], nb, il, ix)) for n in c if n != "iptop"}
-    d["iptop"] = moist.dev(radiation.grids(c["iptop"], nb, il, ix).astype(np.int32))
+    d = {n: support.dev(radiation.grids(c[n], nb, il, ix)) for n in c if n != "iptop"}
+    d["iptop"] = support.dev(radiation.grids(c["iptop"], nb, il, ix).astype(np.int32))
     return d, c, zon
 
 
@@ -82,9 +83,9 @@ def test_batch_composition_and_null_outputs():
     """A state's output bits do not depend on nb or on its position in the batch; NULL outputs leave ttend and the state
     bit-equal."""
     import torch
-    sp = moist.plan("t30", 64)
+    sp = support.plan("t30", 64)
     sp.radiation_set_date(radiation.DATES[0])
-    ix, il, kx = moist.VARIANTS["t30"]
+    ix, il, kx = support.grid("t30")
     tab = moist.tables(moist.HSG[kx])
     S = sp.radiation_state_size()
     for nb in (1, 5, 64):
@@ -117,8 +118,8 @@ def test_chain_capture_and_date(tag):
     between two replays changes the replayed result to the new date's."""
     import torch
     nb = 2
-    sp = moist.plan(tag, 64)
-    ix, il, kx = moist.VARIANTS[tag]
+    sp = support.plan(tag, 64)
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
     sp.radiation_set_date(radiation.DATES[0])
     d, c, zon = _inputs(tab, nb, il, ix, 9400, sp)
@@ -191,8 +192,8 @@ def test_argument_checks_and_index_clamp():
     values equal to the clamped restatement."""
     import torch
     import speedy_f90_amd as s
-    sp = moist.plan("t30", 8)
-    ix, il, kx = moist.VARIANTS["t30"]
+    sp = support.plan("t30", 8)
+    ix, il, kx = support.grid("t30")
     tab = moist.tables(moist.HSG[kx])
     S = sp.radiation_state_size()
     st = torch.zeros(S, dtype=torch.float64, device="cuda")
@@ -217,7 +218,7 @@ def test_argument_checks_and_index_clamp():
     sp.close()
 
     # out-of-range temperatures: the index is clamped to [100, 400] (rows 200 / 320 of the table)
-    sp = moist.plan("t30", 8)
+    sp = support.plan("t30", 8)
     sp.radiation_set_date(radiation.DATES[1])
     zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
     c = radiation.columns(tab, il * ix, 9500, zon)

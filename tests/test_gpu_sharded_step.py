@@ -23,154 +23,18 @@ import threading
 import numpy as np
 import pytest
 
-import levels
 import modelstep
+import shardedstep as sh
 import synth
 from conftest import TOL, VARIANTS
 from dynstep import ROB, SDRAG, WIL, oracle_dynamics_step, state, wave_relerr
 
 pytestmark = pytest.mark.gpu
-DT = 2400.0
-PROGS = ("vor", "div", "t", "tr", "ps")
-
-
-def level_count(tag):
-    """tag: a key of conftest.VARIANTS, or a (trunc_tag, kx) pair of tests/levels.py"""
-    return tag[1] if isinstance(tag, tuple) else VARIANTS[tag][3]
-
-
-def is_t30(tag):
-    return (tag[0] if isinstance(tag, tuple) else tag).startswith("t30")
-
-
-def oracle_of(tag, oracle_factory):
-    return levels.oracle(*tag) if isinstance(tag, tuple) else oracle_factory(tag)
-
-
-def make_plan(tag, device=0):
-    import speedy_f90_amd as s
-    if isinstance(tag, tuple):
-        sp = levels.plan(tag[0], tag[1], 4 * tag[1] + 4, device)
-        sp.initialize_implicit(DT)
-        return sp
-    trunc, ix, iy, kx = VARIANTS[tag]
-    sp = s.Spectral((trunc, ix, iy), kx=kx, max_batch=4 * kx + 4, device=device)
-    if tag in synth.SIGMA_SETS:
-        sp.set_sigma(synth.SIGMA_SETS[tag])
-    sp.initialize_implicit(DT)
-    return sp
-
-
-def unsharded_device_steps(sp, st, nsteps):
-    """The three-call device step (tests/modelstep.py) on one plan: prognostics, tendencies and direct-batch operands."""
-    import torch
-    kx = sp.kx
-    D, W = modelstep.device_state(st), modelstep.Workspace(sp)
-    for _ in range(nsteps):
-        modelstep.step(sp, D, W, DT)
-    torch.cuda.synchronize()
-    out = {n: D[n].cpu().numpy() for n in PROGS}
-    out["phi"] = W.phi.cpu().numpy()
-    out["tend"] = np.concatenate([W.pvor[:kx].cpu().numpy(), W.pdiv.cpu().numpy(), W.pspec[3 * kx:].cpu().numpy()])   # vordt | divdt | tdt | trdt | psdt
-    out["U"], out["V"], out["PL"] = W.U.cpu().numpy(), W.V.cpu().numpy(), W.PL.cpu().numpy()
-    return out
-
-
-def _rank_thread(rank, group, tag, st, nsteps, results, errors, device=0, transpose=False):
-    import torch
-    import speedy_f90_amd as s
-    try:
-        torch.cuda.set_device(device)          # (per thread: the tensors below live on the rank's device)
-        sp = make_plan(tag, device)
-        sp.use_own_stream()
-        comm = s.sharding.LevelComm(sp, group=group, rank=rank)
-        if transpose:
-            comm.set_option("transpose", 1)
-        comm.sharded_step_workspace()
-        kx, nx, mx = sp.kx, sp.nx, sp.mx
-        D = {n: torch.from_numpy(np.ascontiguousarray(st[n])).cuda() for n in st}
-        phi = torch.zeros((kx, nx, mx), dtype=torch.complex128, device="cuda")
-        tend = torch.zeros((4 * kx + 1, nx, mx), dtype=torch.complex128, device="cuda")
-        G, T = comm.sharded_step_stacks()
-        torch.cuda.synchronize()
-        for step in range(nsteps):
-            G.fill_(float("nan")); T.fill_(float("nan"))          # whatever a rank does not compute must ARRIVE, or it poisons the step
-            torch.cuda.synchronize()
-            if step == 0:                                         # the one call ...
-                comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, DT, ROB, WIL,
-                                   phi, tend)
-            else:                                                 # ... and its two halves (the physics hook sits between them)
-                comm.sharded_step_grid_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], 2)
-                comm.sharded_step_spectral_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, DT, ROB,
-                                            WIL, phi, tend)
-            sp.synchronize()
-        U, V, PL, lo, hi = comm.sharded_step_operands()
-        out = {}
-        if transpose:
-            # what the rank holds BEFORE the gather: its coefficient range of every level is current (both time levels)
-            desc = comm.describe()
-            e0, e1 = desc["coefficients"]
-            out["own_range"] = (e0, e1)
-            out["before"] = {n: D[n].reshape(D[n].shape[:-2] + (-1,))[..., e0:e1].cpu().numpy() for n in PROGS}
-            out["describe"] = desc
-            comm.state_gather_(D["vor"], D["div"], D["t"], D["tr"], D["ps"])
-            comm.gather_ranges_(phi, tend)
-            sp.synchronize()
-        out.update({n: D[n].cpu().numpy() for n in PROGS})
-        out.update(phi=phi.cpu().numpy(), tend=tend.cpu().numpy(), U=U.cpu().numpy(), V=V.cpu().numpy(), PL=PL.cpu().numpy(), lo=lo, hi=hi)
-        results[rank] = out
-        comm.close(); sp.close()
-    except Exception as e:          # a missing rank would leave the others waiting for the group's timeout
-        errors[rank] = e
 
 
 @pytest.mark.parametrize("tag,world", [(t, w) for t in ("t30", "t30k5", "t63k16") for w in (1, 2, 3)] + [("t30", 8), ("t63k16", 8)])
 def test_sharded_step_in_process_ranks(tag, world, oracle_factory, monkeypatch):
-    import speedy_f90_amd as s
-    monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
-    kx = level_count(tag)
-    o = oracle_of(tag, oracle_factory)
-    o.tail_init(DT)
-    sp0 = make_plan(tag)
-    st = state(sp0, 8000)
-    nsteps = 2
-    whole = unsharded_device_steps(sp0, st, nsteps)
-    group = s.sharding.LocalGroup(sp0.lib, world)
-    results, errors = {}, {}
-    threads = [threading.Thread(target=_rank_thread, args=(r, group, tag, st, nsteps, results, errors)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(600)
-    assert not errors, errors
-    assert sorted(results) == list(range(world))
-    group.close(); sp0.close()
-    ref = st
-    for _ in range(nsteps):
-        ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
-    ref_tend = np.concatenate([out["vordt"], out["divdt"], out["tdt"], out["trdt"], out["psdt"][None]])
-    worst = 0.0
-    for r in range(world):
-        got = results[r]
-        assert (got["lo"], got["hi"]) == s.sharding.shard_range(kx, r, world)
-        own = [g * kx + k for g in range(3) for k in range(got["lo"], got["hi"])]
-        # vs the oracle's call-by-call step: the north star's bar
-        for n in PROGS:
-            worst = max(worst, synth.relerr(got[n], ref[n]), wave_relerr(got[n], ref[n]))
-        worst = max(worst, wave_relerr(got["phi"], out["phi"]))
-        for a in range(4):
-            worst = max(worst, wave_relerr(got["tend"][a * kx:(a + 1) * kx], ref_tend[a * kx:(a + 1) * kx]))
-        worst = max(worst, synth.relerr(got["tend"][4 * kx], ref_tend[4 * kx]))
-        worst = max(worst, synth.relerr(got["U"], out["U"][own]), synth.relerr(got["V"], out["V"][own]),
-                    synth.relerr(got["PL"], np.concatenate([out["PL"][own], out["PL"][3 * kx:]])))
-        # vs the unsharded device step: same bits, whatever the rank count
-        for n in PROGS + ("phi", "tend"):
-            assert np.array_equal(got[n], whole[n]), (tag, world, r, n, synth.relerr(got[n], whole[n]))
-        assert np.array_equal(got["U"], whole["U"][own]) and np.array_equal(got["V"], whole["V"][own])
-        assert np.array_equal(got["PL"], np.concatenate([whole["PL"][own], whole["PL"][3 * kx:]]))
-    print("\n[sharded step %s, %d in-process ranks] worst relative error vs the oracle %.1e; bits equal to the unsharded device step"
-          % (tag, world, worst))
-    assert worst <= TOL, (tag, world, worst)
+    sh.in_process_ranks(tag, world, oracle_factory, monkeypatch)
 
 
 @pytest.mark.parametrize("tag,world", [(t, w) for t in ("t30", "t30k5", "t63k16") for w in (1, 2, 3)] + [("t30", 8), ("t63k16", 8)])
@@ -182,76 +46,7 @@ def test_sharded_step_transposed_in_process_ranks(tag, world, oracle_factory, mo
     on the first one's whole state it moves values that are already there), then the state gather.  Against the oracle's call-by-call step at 1e-12; against the unsharded device step
     BIT FOR BIT at T30 (same kernels' expressions on the same values, whatever the rank count) and to rounding at T63 L16 (there
     the unsharded step applies vds inside the spectral step, the transposed form before its exchange)."""
-    transposed_in_process_ranks(tag, world, oracle_factory, monkeypatch)
-
-
-def transposed_in_process_ranks(tag, world, oracle_factory, monkeypatch, pays=0.6):
-    """the body of test_sharded_step_transposed_in_process_ranks.  pays: from four ranks on every rank of the transposed form
-    receives less than this part of the all-gather form's bytes (0.6 for the equal level blocks of that test's cases)"""
-    import speedy_f90_amd as s
-    monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
-    kx = level_count(tag)
-    o = oracle_of(tag, oracle_factory)
-    o.tail_init(DT)
-    sp0 = make_plan(tag)
-    st = state(sp0, 8000)
-    nsteps = 2
-    whole = unsharded_device_steps(sp0, st, nsteps)
-    group = s.sharding.LocalGroup(sp0.lib, world)
-    results, errors = {}, {}
-    threads = [threading.Thread(target=_rank_thread, args=(r, group, tag, st, nsteps, results, errors, 0, True)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(600)
-    assert not errors, errors
-    assert sorted(results) == list(range(world))
-    group.close(); sp0.close()
-    ref = st
-    for _ in range(nsteps):
-        ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
-    ref_tend = np.concatenate([out["vordt"], out["divdt"], out["tdt"], out["trdt"], out["psdt"][None]])
-    exact = is_t30(tag)
-    worst, covered = 0.0, 0
-    for r in range(world):
-        got = results[r]
-        own = [g * kx + k for g in range(3) for k in range(got["lo"], got["hi"])]
-        for n in PROGS:
-            worst = max(worst, synth.relerr(got[n], ref[n]), wave_relerr(got[n], ref[n]))
-        worst = max(worst, wave_relerr(got["phi"], out["phi"]))
-        for a in range(4):
-            worst = max(worst, wave_relerr(got["tend"][a * kx:(a + 1) * kx], ref_tend[a * kx:(a + 1) * kx]))
-        worst = max(worst, synth.relerr(got["tend"][4 * kx], ref_tend[4 * kx]))
-        worst = max(worst, synth.relerr(got["U"], out["U"][own]), synth.relerr(got["V"], out["V"][own]),
-                    synth.relerr(got["PL"], np.concatenate([out["PL"][own], out["PL"][3 * kx:]])))
-        # the ranks' coefficient ranges tile the spectrum, and each rank's range was current before the gather
-        e0, e1 = got["own_range"]
-        covered += e1 - e0
-        for n in PROGS:
-            flat = whole[n].reshape(whole[n].shape[:-2] + (-1,))[..., e0:e1]
-            if exact:
-                assert np.array_equal(got["before"][n], flat), (tag, world, r, n)
-            else:
-                assert synth.relerr(got["before"][n], flat) <= 1e-13, (tag, world, r, n)
-        for n in PROGS + ("phi", "tend"):
-            if exact:
-                assert np.array_equal(got[n], whole[n]), (tag, world, r, n, synth.relerr(got[n], whole[n]))
-            else:
-                assert synth.relerr(got[n], whole[n]) <= 1e-13, (tag, world, r, n, synth.relerr(got[n], whole[n]))
-        # the direct-batch operands of the rank's levels came home complete (exchange 2)
-        wpl = np.concatenate([whole["PL"][own], whole["PL"][3 * kx:]])
-        if exact:
-            assert np.array_equal(got["U"], whole["U"][own]) and np.array_equal(got["V"], whole["V"][own]) and np.array_equal(got["PL"], wpl)
-        else:   # (second step: its inputs already differ by the first step's rounding)
-            assert max(synth.relerr(got["U"], whole["U"][own]), synth.relerr(got["V"], whole["V"][own]), synth.relerr(got["PL"], wpl)) <= 1e-13
-        d = got["describe"]
-        assert d["form"] == "transpose" and d["nranks"] == world and d["rank"] == r
-        if world >= 4:      # (at two ranks the four exchanges move about what the two all-gathers do; the form pays from four ranks on)
-            assert d["bytes_received_per_step_transposed_form"] < pays * d["bytes_received_per_step_allgather_form"], d
-    assert covered == results[0]["vor"].shape[-1] * results[0]["vor"].shape[-2]
-    print("\n[transposed sharded step %s, %d in-process ranks] worst relative error vs the oracle %.1e; %s the unsharded device step"
-          % (tag, world, worst, "bits equal to" if exact else "within 1e-13 of"))
-    assert worst <= TOL, (tag, world, worst)
+    sh.transposed_in_process_ranks(tag, world, oracle_factory, monkeypatch)
 
 
 @pytest.mark.parametrize("transpose", [False, True])
@@ -266,13 +61,13 @@ def test_sharded_step_in_process_ranks_on_several_devices(transpose, oracle_fact
     monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
     tag, nsteps = "t30", 2
     o = oracle_factory(tag)
-    o.tail_init(DT)
-    sp0 = make_plan(tag)
+    o.tail_init(sh.DT)
+    sp0 = sh.make_plan(tag)
     st = state(sp0, 8000)
-    whole = unsharded_device_steps(sp0, st, nsteps)
+    whole = sh.unsharded_device_steps(sp0, st, nsteps)
     group = s.sharding.LocalGroup(sp0.lib, world)
     results, errors = {}, {}
-    threads = [threading.Thread(target=_rank_thread, args=(r, group, tag, st, nsteps, results, errors, r, transpose)) for r in range(world)]
+    threads = [threading.Thread(target=sh.rank_thread, args=(r, group, tag, st, nsteps, results, errors, r, transpose)) for r in range(world)]
     for t in threads:
         t.start()
     for t in threads:
@@ -280,7 +75,7 @@ def test_sharded_step_in_process_ranks_on_several_devices(transpose, oracle_fact
     assert not errors, errors
     group.close(); sp0.close()
     for r in range(world):
-        for n in PROGS + ("phi", "tend"):
+        for n in sh.PROGS + ("phi", "tend"):
             assert np.array_equal(results[r][n], whole[n]), (r, n)
 
 
@@ -294,7 +89,7 @@ def _hook_thread(rank, group, st, results, errors):
     import torch
     import speedy_f90_amd as s
     try:
-        sp = make_plan("t30")
+        sp = sh.make_plan("t30")
         sp.use_own_stream()
         comm = s.sharding.LevelComm(sp, group=group, rank=rank)
         kx = sp.kx
@@ -308,9 +103,9 @@ def _hook_thread(rank, group, st, results, errors):
         nl = hi - lo
         U[:nl] += inc[0][lo:hi]; V[:nl] += inc[1][lo:hi]; PL[nl:2 * nl] += inc[2][lo:hi]; PL[2 * nl:3 * nl] += inc[3][lo:hi]
         torch.cuda.synchronize()
-        comm.sharded_step_spectral_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, DT, ROB, WIL, phi)
+        comm.sharded_step_spectral_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, sh.DT, ROB, WIL, phi)
         sp.synchronize()
-        results[rank] = {n: D[n].cpu().numpy() for n in PROGS}
+        results[rank] = {n: D[n].cpu().numpy() for n in sh.PROGS}
         comm.close(); sp.close()
     except Exception as e:
         errors[rank] = e
@@ -323,16 +118,16 @@ def test_sharded_step_physics_hook(monkeypatch):
     import torch
     import speedy_f90_amd as s
     monkeypatch.setenv("SPDY_COMM_TIMEOUT_S", "60")
-    sp = make_plan("t30")
+    sp = sh.make_plan("t30")
     st = state(sp, 8000)
     D, W = modelstep.device_state(st), modelstep.Workspace(sp)
     inc = [torch.from_numpy(a).cuda() for a in _physics_increment(sp.kx, sp.il, sp.ix)]
 
     def add_increments(sp, D, W):
         W.utend += inc[0]; W.vtend += inc[1]; W.ttend += inc[2]; W.qtend += inc[3]
-    modelstep.step(sp, D, W, DT, physics=add_increments)
+    modelstep.step(sp, D, W, sh.DT, physics=add_increments)
     torch.cuda.synchronize()
-    whole = {n: D[n].cpu().numpy() for n in PROGS}
+    whole = {n: D[n].cpu().numpy() for n in sh.PROGS}
     group = s.sharding.LocalGroup(sp.lib, 2)
     results, errors = {}, {}
     threads = [threading.Thread(target=_hook_thread, args=(r, group, st, results, errors)) for r in range(2)]
@@ -343,7 +138,7 @@ def test_sharded_step_physics_hook(monkeypatch):
     assert not errors, errors
     group.close(); sp.close()
     for r in range(2):
-        for n in PROGS:
+        for n in sh.PROGS:
             assert np.array_equal(results[r][n], whole[n]), (r, n, synth.relerr(results[r][n], whole[n]))
             assert not np.array_equal(whole[n], st[n])
 
@@ -356,7 +151,7 @@ def test_in_process_group_errors():
     from speedy_f90_amd._lib import SpdyError
     os.environ["SPDY_COMM_TIMEOUT_S"] = "2"
     try:
-        sp = make_plan("t30")
+        sp = sh.make_plan("t30")
         sp.use_own_stream()
         group = s.sharding.LocalGroup(sp.lib, 2)
         comm = s.sharding.LevelComm(sp, group=group, rank=0)
@@ -405,17 +200,17 @@ def test_sharded_step_rccl_graph_world1(tag, nccl_world1, oracle_factory, monkey
     import speedy_f90_amd as s
     kx = VARIANTS[tag][3]
     o = oracle_factory(tag)
-    o.tail_init(DT)
-    sp0 = make_plan(tag)
+    o.tail_init(sh.DT)
+    sp0 = sh.make_plan(tag)
     st = state(sp0, 8000)
-    whole = unsharded_device_steps(sp0, st, 2)
+    whole = sh.unsharded_device_steps(sp0, st, 2)
     sp0.close()
     ref = st
     for _ in range(2):
-        ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
+        ref, out = oracle_dynamics_step(o, ref, 2, sh.DT, ROB)
     for force in ("1", "2"):
         monkeypatch.setenv("SPDY_COMM_FORCE", force)
-        sp = make_plan(tag)
+        sp = sh.make_plan(tag)
         sp.use_own_stream()
         comm = s.sharding.LevelComm(sp)
         comm.sharded_step_workspace()
@@ -424,11 +219,11 @@ def test_sharded_step_rccl_graph_world1(tag, nccl_world1, oracle_factory, monkey
         tend = torch.zeros((4 * kx + 1, sp.nx, sp.mx), dtype=torch.complex128, device="cuda")
         torch.cuda.synchronize()
         with sp.graph_capture() as g:
-            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, DT, ROB, WIL, phi, tend)
+            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, sh.DT, ROB, WIL, phi, tend)
         for _ in range(2):
             g.launch()
         sp.synchronize()
-        for n in PROGS:
+        for n in sh.PROGS:
             got = D[n].cpu().numpy()
             assert max(synth.relerr(got, ref[n]), wave_relerr(got, ref[n])) <= TOL, (force, n)
             assert np.array_equal(got, whole[n]), (force, n)
@@ -447,17 +242,17 @@ def test_sharded_step_transposed_rccl_world1_in_graph(tag, oracle_factory, monke
     from speedy_f90_amd._lib import SpdyError
     kx = VARIANTS[tag][3]
     o = oracle_factory(tag)
-    o.tail_init(DT)
-    sp0 = make_plan(tag)
+    o.tail_init(sh.DT)
+    sp0 = sh.make_plan(tag)
     st = state(sp0, 8000)
-    whole = unsharded_device_steps(sp0, st, 2)
+    whole = sh.unsharded_device_steps(sp0, st, 2)
     sp0.close()
     ref = st
     for _ in range(2):
-        ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
+        ref, out = oracle_dynamics_step(o, ref, 2, sh.DT, ROB)
     monkeypatch.setenv("SPDY_COMM_FORCE", "1")
     monkeypatch.setenv("SPDY_SHARD_TRANSPOSE", "1")
-    sp = make_plan(tag)
+    sp = sh.make_plan(tag)
     sp.use_own_stream()
     comm = s.sharding.LevelComm(sp)
     comm.sharded_step_workspace()
@@ -468,7 +263,7 @@ def test_sharded_step_transposed_rccl_world1_in_graph(tag, oracle_factory, monke
     tend = torch.zeros((4 * kx + 1, sp.nx, sp.mx), dtype=torch.complex128, device="cuda")
     torch.cuda.synchronize()
     with sp.graph_capture() as g:
-        comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, DT, ROB, WIL, phi, tend)
+        comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, sh.DT, ROB, WIL, phi, tend)
     nodes = g.num_nodes()
     for _ in range(2):
         g.launch()
@@ -477,7 +272,7 @@ def test_sharded_step_transposed_rccl_world1_in_graph(tag, oracle_factory, monke
     comm.gather_ranges_(phi, tend)
     sp.synchronize()
     exact = tag.startswith("t30")
-    for n in PROGS:
+    for n in sh.PROGS:
         got = D[n].cpu().numpy()
         assert max(synth.relerr(got, ref[n]), wave_relerr(got, ref[n])) <= TOL, n
         assert np.array_equal(got, whole[n]) if exact else synth.relerr(got, whole[n]) <= 1e-13, n
@@ -509,8 +304,8 @@ def _rccl_rank(rank, world, port, tag, q, transpose=False):
         o = Oracle(*VARIANTS[tag])
         if tag in synth.SIGMA_SETS:
             o.set_sigma(synth.SIGMA_SETS[tag])
-        o.tail_init(DT)
-        sp = make_plan(tag, device=rank)
+        o.tail_init(sh.DT)
+        sp = sh.make_plan(tag, device=rank)
         sp.use_own_stream()
         comm = s.sharding.LevelComm(sp)
         if transpose:
@@ -523,26 +318,26 @@ def _rccl_rank(rank, world, port, tag, q, transpose=False):
         G.fill_(float("nan")); T.fill_(float("nan"))
         torch.cuda.synchronize()
         with sp.graph_capture() as g:
-            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, DT, ROB, WIL, phi)
+            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, sh.DT, ROB, WIL, phi)
         ref = st
         for _ in range(2):
             g.launch()
-            ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
+            ref, out = oracle_dynamics_step(o, ref, 2, sh.DT, ROB)
         sp.synchronize()
         if transpose:
             comm.state_gather_(D["vor"], D["div"], D["t"], D["tr"], D["ps"])
             sp.synchronize()
-        worst_err = lambda: max(max(synth.relerr(D[n].cpu().numpy(), ref[n]), wave_relerr(D[n].cpu().numpy(), ref[n])) for n in PROGS)
+        worst_err = lambda: max(max(synth.relerr(D[n].cpu().numpy(), ref[n]), wave_relerr(D[n].cpu().numpy(), ref[n])) for n in sh.PROGS)
         err = worst_err()
         if transpose:
             # a replay after the gather leaves the state range-sharded again without the host knowing: the eager step after it
             # must still bring in the other ranks' coefficients first (exchange 4), or it reads stale ones
             g.launch()
-            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, DT, ROB, WIL, phi)
+            comm.sharded_step_(D["vor"], D["div"], D["t"], D["tr"], D["ps"], D["phis"], D["tcorh"], D["qcorh"], SDRAG, 2, 2, sh.DT, ROB, WIL, phi)
             comm.state_gather_(D["vor"], D["div"], D["t"], D["tr"], D["ps"])
             sp.synchronize()
             for _ in range(2):
-                ref, out = oracle_dynamics_step(o, ref, 2, DT, ROB)
+                ref, out = oracle_dynamics_step(o, ref, 2, sh.DT, ROB)
             err = max(err, worst_err())
         g.close(); comm.close(); sp.close()
         q.put((rank, err))

@@ -6,27 +6,20 @@ import numpy as np
 import pytest
 
 import modelstep
-import moist
 import physstep
 import sppt
+import support
 import synth
 from conftest import TOL, VARIANTS
 from dynstep import ROB, oracle_dynamics_step, wave_relerr
 from modelstep import PROG
-from test_gpu_physics_step import TEND, _gridded, _plan_case
+from physstep import TEND
 
 pytestmark = pytest.mark.gpu
 
 TAGS = ["t30", "t63k16"]
 SEED = 0x5EED0123456789AB
 FIELDS = ("eta", "spec", "pattern")
-
-
-def _mu(kx):
-    """a taper with 0, fractions and 1 in it"""
-    mu = np.clip(np.linspace(-0.5, 1.5, kx), 0.0, 1.0)
-    assert mu[0] == 0.0 and mu[-1] == 1.0 and ((mu > 0) & (mu < 1)).any()
-    return mu
 
 
 def _shape(sp):
@@ -38,7 +31,7 @@ def test_noise(tag):
     """Two drawn advances: eta against the restated generator within TOL; a second object with the same seed gives the same bits,
     another seed does not; reset reproduces the first run; draws counts the advances."""
     import speedy_f90_amd as s
-    sp = moist.plan(tag, 4 * VARIANTS[tag][3] + 4)
+    sp = support.plan(tag, 4 * VARIANTS[tag][3] + 4)
     a, b, c = s.Sppt(sp, 36, seed=SEED), s.Sppt(sp, 36, seed=SEED), s.Sppt(sp, 36, seed=SEED + 1)
     assert a.draws() == 0
     first = []
@@ -74,7 +67,7 @@ def test_ar1_transform_clip(tag, oracle_factory):
     """Three advances on injected noise, scaled so that the clip to +-1 is at work (and the clip to +-10 too): spec and pattern
     against the restatement after each; |pattern| <= 1 exactly; draws counts injected advances too."""
     import speedy_f90_amd as s
-    sp, o = moist.plan(tag, 4 * VARIANTS[tag][3] + 4), oracle_factory(tag)
+    sp, o = support.plan(tag, 4 * VARIANTS[tag][3] + 4), oracle_factory(tag)
     pat, ref = s.Sppt(sp, 36, seed=1), sppt.Pattern(o)
     worst = 0.0
     for d in range(3):
@@ -83,7 +76,7 @@ def test_ar1_transform_clip(tag, oracle_factory):
         want = ref.advance(eta)
         frac = float((np.abs(ref.grid) > 1.0).mean())
         assert 0.01 <= frac <= 0.99, frac
-        pat.advance_dev(moist.dev(eta))
+        pat.advance_dev(support.dev(eta))
         got = pat.numpy("pattern")
         es, ep = synth.relerr(pat.numpy("spec"), ref.spec), synth.relerr(got, want)
         print("[sppt AR(1) %s] advance %d: spec %.1e, pattern %.1e, clipped %.1f %%" % (tag, d, es, ep, 100 * frac))
@@ -97,7 +90,7 @@ def test_ar1_transform_clip(tag, oracle_factory):
 def _physics_inputs(sp, o, case, kx):
     st = case.st
     phi = o.geopotential(st["t"][0], st["phis"])
-    spec = [moist.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])]
+    spec = [support.dev(a) for a in (st["vor"][0], st["div"][0], st["t"][0], st["tr"][0], phi, st["ps"][0])]
     bnd = physstep.device_boundary(case.bnd, sp.il, sp.ix)
     t0 = [synth.splitmix64(170 + i, kx * sp.il * sp.ix).reshape(kx, sp.il, sp.ix) * f for i, f in enumerate((1e-4, 1e-4, 1e-4, 1e-7))]
     return spec, bnd, t0
@@ -115,14 +108,14 @@ def test_application_from_spectra(tag, oracle_factory):
     without SPPT; the pattern object is not advanced."""
     import torch
     import speedy_f90_amd as s
-    sp, o, case, kx = _plan_case(tag, oracle_factory)
+    sp, o, case, kx = physstep.plan_case(tag, oracle_factory)
     spec, bnd, t0 = _physics_inputs(sp, o, case, kx)
-    mu = _mu(kx)
+    mu = sppt.mu(kx)
     pat = s.Sppt(sp, 36, mu, seed=SEED)
     pat.advance_dev()
     P = pat.numpy("pattern")
     assert P.std() > 0.05
-    T, out, S = [moist.dev(a) for a in t0], sp.column_outputs(1), _nan_state(sp)
+    T, out, S = [support.dev(a) for a in t0], sp.column_outputs(1), _nan_state(sp)
     sp.physics_dev(True, *spec, bnd, bnd["albsfc"], S, *T, out)
     torch.cuda.synchronize()
     want = [sppt.apply(t.cpu().numpy(), d, P, mu) for t, d in zip(T, t0)]
@@ -130,7 +123,7 @@ def test_application_from_spectra(tag, oracle_factory):
     plain = physstep.flat_outs(out)
     for fused in (1, 0):
         sp.set_option("physics_fused", fused)
-        T2, out2, S2 = [moist.dev(a) for a in t0], sp.column_outputs(1), _nan_state(sp)
+        T2, out2, S2 = [support.dev(a) for a in t0], sp.column_outputs(1), _nan_state(sp)
         sp.physics_sppt_dev(pat, True, *spec, bnd, bnd["albsfc"], S2, *T2, out2)
         torch.cuda.synchronize()
         for n, t, w in zip(TEND, T2, want):
@@ -149,7 +142,7 @@ def test_application_on_gridded_states(tag):
     import torch
     import speedy_f90_amd as s
     nb = 3
-    sp, kx, il, ix, d, _ = _gridded(tag, nb, 9950)
+    sp, kx, il, ix, d, _ = physstep.gridded(tag, nb, 9950)
     pat = s.Sppt(sp, 36, seed=SEED + 3)
     pats = []
     for _ in range(nb):
@@ -157,14 +150,14 @@ def test_application_on_gridded_states(tag):
         pats.append(pat.numpy("pattern"))
     P = np.stack(pats)
     assert not np.array_equal(P[0], P[1]) and not np.array_equal(P[1], P[2])
-    dP = moist.dev(P)
+    dP = support.dev(P)
     sp.column_physics_sppt_workspace()
     args = lambda T, S: (True, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T)
     T0 = [d[n].cpu().numpy() for n in TEND]
     T, S = [d[n].clone() for n in TEND], _nan_state(sp, nb)
     sp.column_physics_dev(*args(T, S))
     torch.cuda.synchronize()
-    for mu in (_mu(kx), None):
+    for mu in (sppt.mu(kx), None):
         m = np.ones(kx) if mu is None else mu
         want = [np.stack([sppt.apply(t.cpu().numpy()[b], t0[b], P[b], m) for b in range(nb)]) for t, t0 in zip(T, T0)]
         for fused in (1, 0):
@@ -185,15 +178,15 @@ def test_captured_advance_and_physics(tag, oracle_factory):
     3 nodes; the one-launch physics with SPPT adds none to spdy_physics_dev's graph, the five calls add their save and apply."""
     import torch
     import speedy_f90_amd as s
-    sp, o, case, kx = _plan_case(tag, oracle_factory)
+    sp, o, case, kx = physstep.plan_case(tag, oracle_factory)
     spec, bnd, t0 = _physics_inputs(sp, o, case, kx)
-    mu = _mu(kx)
+    mu = sppt.mu(kx)
     sp.physics_sppt_workspace()
     sp.use_own_stream()
     a, b = s.Sppt(sp, 36, mu, seed=SEED), s.Sppt(sp, 36, mu, seed=SEED)
 
     def rounds(step):
-        T, S, after = [moist.dev(x) for x in t0], _nan_state(sp), []
+        T, S, after = [support.dev(x) for x in t0], _nan_state(sp), []
         torch.cuda.synchronize()
         for _ in range(3):
             step(T, S)
@@ -248,8 +241,8 @@ def test_three_steps_with_sppt(tag, oracle_factory):
     oracle_dynamics_step with a physics hook that applies the restated pattern: vor, div, t, tr, ps and the PL operands within TOL
     after each step.  With the advance left out on the second step the error is far over the bar: the test sees the pattern."""
     import speedy_f90_amd as s
-    sp, o, case, kx = _plan_case(tag, oracle_factory)
-    dt, mu = physstep.DT[tag], _mu(kx)
+    sp, o, case, kx = physstep.plan_case(tag, oracle_factory)
+    dt, mu = physstep.DT[tag], sppt.mu(kx)
     sp.initialize_implicit(dt); o.tail_init(dt)
     sp.physics_sppt_workspace()
     sp.use_own_stream()

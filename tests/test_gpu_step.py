@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import dynstep
 import modelstep
 import synth
 from conftest import TOL, VARIANTS
@@ -94,14 +95,13 @@ def test_step_fields_vs_golden(tag):
     (time_stepping.f90:126-167, flang build of the two functions cut from the reference file; tests/golden/ref_step.npz):
     j1 = 1 (forward step) and j1 = 2 (leapfrog + Robert-Asselin-Williams filter) -- pinned, not restated."""
     import torch
-    from test_oracle_golden import STEP_CASES, STEP_J1_SUB, step_golden, step_inputs
-    z, sp = step_golden(), make_plan(tag, 64)
+    z, sp = dynstep.step_golden(), make_plan(tag, 64)
     wil, rob = z[tag + "_wil_rob"]
-    F3, D3, F2, D2 = step_inputs(sp.kx, sp.nx, sp.mx)
+    F3, D3, F2, D2 = dynstep.step_inputs(sp.kx, sp.nx, sp.mx)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     for j1, dt, eps in ((1, 2400.0, 0.0), (2, 4800.0, rob)):
         key = "%s_j%d_" % (tag, j1)
-        sub = STEP_CASES[tag] if STEP_CASES[tag] else (STEP_J1_SUB if j1 == 1 else None)
+        sub = dynstep.STEP_CASES[tag] if dynstep.STEP_CASES[tag] else (dynstep.STEP_J1_SUB if j1 == 1 else None)
         cut = (lambda a: a[(Ellipsis,) + sub]) if sub else (lambda a: a)
         f3, d3, f2, d2 = dev(F3), dev(D3), dev(F2), dev(D2)
         sp.step_fields_dev([(f2, d2), (f3, d3)], j1, dt, eps, wil)

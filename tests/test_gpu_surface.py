@@ -7,17 +7,13 @@ import os
 import numpy as np
 import pytest
 
-import moist
 import radiation
+import support
 import surface
 import synth
 from conftest import GOLDEN, TOL
 
 pytestmark = pytest.mark.gpu
-
-ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
-SFC_OUT = surface.SFC_3 + ("hfluxn",) + surface.SFC_2D
-PBL_OUT = ("ut_pbl", "vt_pbl", "tt_pbl", "qt_pbl", "utend", "vtend", "ttend", "qtend")
 
 
 def _close(got, want, key):
@@ -25,23 +21,6 @@ def _close(got, want, key):
     print("  %-8s %.2e" % (key, e))
     assert e <= TOL, (key, e)
     return e
-
-
-def _case(tag, seed, nb=1, date=0, plan=None):
-    """(plan with date and no orography yet, tables, columns, zonal and sqrt(coa) per column).  plan: (sp, its half levels) of a
-    count outside moist.VARIANTS (tests/levels.py), used in place of the plan of tag"""
-    if plan is None:
-        ix, il, kx = moist.VARIANTS[tag]
-        sp, hsg = moist.plan(tag, 64), moist.HSG[kx]
-    else:
-        sp, hsg = plan
-        ix, il = sp.ix, sp.il
-    sp.radiation_set_date(radiation.DATES[date])
-    tab = moist.tables(hsg)
-    zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, nb, il, ix)
-    sqcoa = surface.sqcoa_columns(sp.table("coa_half"), nb, il, ix)
-    c = surface.columns(tab, nb * il * ix, seed, zon, sqcoa)
-    return sp, tab, c, zon, sqcoa
 
 
 def _orography(sp, c, il, ix, nb=1):
@@ -60,13 +39,13 @@ def _kx_level(a, kx):
     return np.asarray(a)[:, kx - 1].reshape(-1)
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_kernels_vs_reference_and_restatement(tag):
     """surface_columns and pbl_columns with every optional output: the stored sample against the reference, every column
     against the restatement."""
     z = np.load(os.path.join(GOLDEN, "ref_surface.npz"))
-    ix, il, kx = moist.VARIANTS[tag]
-    sp, tab, c, zon, sqcoa = _case(tag, int(z[tag + "_seed"]))
+    ix, il, kx = support.grid(tag)
+    sp, tab, c, zon, sqcoa = surface.case(tag, int(z[tag + "_seed"]))
     sub = z[tag + "_sub"]
     sp.surface_set_orography(c["phis0"].reshape(il, ix))
     r, _ = surface.chain(tab, c, zon, sqcoa)
@@ -75,7 +54,7 @@ def test_kernels_vs_reference_and_restatement(tag):
     worst = 0.0
     s = sp.surface_columns(G(c["ug"]), G(c["vg"]), G(c["tg"]), G(c["qg"]), G(c["phig"]), G(c["pslg"]), G(r["ssrd"]),
                            G(r["down"]["slrd"]), bnd)
-    for n in SFC_OUT:
+    for n in surface.SFC_OUT:
         got = s[n].reshape(-1, il * ix).squeeze()
         worst = max(worst, _close(got[..., sub], z["%s_%s" % (tag, n)], n), _close(got, r["sfc"][n], n))
     assert np.array_equal(s["fsfcu"].reshape(-1), s["slru"][2].reshape(-1))
@@ -83,7 +62,7 @@ def test_kernels_vs_reference_and_restatement(tag):
     m, up = r["moist"], r["up"]
     p = sp.pbl_columns(G(c["qg"]), G(c["phig"]), G(c["pslg"]), G(m["se"]), G(m["rh"]), G(m["qsat"]), G(m["icnv"]),
                        np.stack([G(f) for f in r["flux3"]]), G(c["utend"]), G(c["vtend"]), G(up["ttend"]), G(m["qtend"]))
-    for n in PBL_OUT:
+    for n in surface.PBL_OUT:
         got = p[n].reshape(-1, il * ix).squeeze()
         want = r["pbl"][n]
         if n in ("utend", "vtend"):
@@ -96,16 +75,16 @@ def test_kernels_vs_reference_and_restatement(tag):
 
 def _device_inputs(c, r, nb, kx, il, ix):
     import torch
-    d = {n: moist.dev(radiation.grids(c[n], nb, il, ix)) for n in ("ug", "vg", "tg", "qg", "phig", "pslg", "utend", "vtend", "ttend",
-                                                                   "qtend", "albsfc") + surface.BOUNDARY}
+    d = {n: support.dev(radiation.grids(c[n], nb, il, ix)) for n in ("ug", "vg", "tg", "qg", "phig", "pslg", "utend", "vtend", "ttend",
+                                                                     "qtend", "albsfc") + surface.BOUNDARY}
     if r is not None:
-        d.update(ssrd=moist.dev(radiation.grids(r["ssrd"], nb, il, ix)), slrd=moist.dev(radiation.grids(r["down"]["slrd"], nb, il, ix)))
+        d.update(ssrd=support.dev(radiation.grids(r["ssrd"], nb, il, ix)), slrd=support.dev(radiation.grids(r["down"]["slrd"], nb, il, ix)))
         m = r["moist"]
-        d.update({n: moist.dev(radiation.grids(m[n], nb, il, ix)) for n in ("se", "rh", "qsat")})
-        d["icnv"] = moist.dev(radiation.grids(m["icnv"], nb, il, ix).astype(np.int32))
-        d["flux3"] = moist.dev(np.ascontiguousarray(np.moveaxis(np.stack([radiation.grids(f, nb, il, ix) for f in r["flux3"]]), 0, 1)))
-        d["ttend_up"] = moist.dev(radiation.grids(r["up"]["ttend"], nb, il, ix))
-        d["qtend_m"] = moist.dev(radiation.grids(m["qtend"], nb, il, ix))
+        d.update({n: support.dev(radiation.grids(m[n], nb, il, ix)) for n in ("se", "rh", "qsat")})
+        d["icnv"] = support.dev(radiation.grids(m["icnv"], nb, il, ix).astype(np.int32))
+        d["flux3"] = support.dev(np.ascontiguousarray(np.moveaxis(np.stack([radiation.grids(f, nb, il, ix) for f in r["flux3"]]), 0, 1)))
+        d["ttend_up"] = support.dev(radiation.grids(r["up"]["ttend"], nb, il, ix))
+        d["qtend_m"] = support.dev(radiation.grids(m["qtend"], nb, il, ix))
     return d
 
 
@@ -113,8 +92,8 @@ def test_batch_composition():
     """A state's output bits do not depend on nb or on its position in the batch (nb = 1 against the same state inside nb = 3)."""
     import torch
     nb = 3
-    ix, il, kx = moist.VARIANTS["t30"]
-    sp, tab, c, zon, sqcoa = _case("t30", 9600, nb)
+    ix, il, kx = support.grid("t30")
+    sp, tab, c, zon, sqcoa = surface.case("t30", 9600, nb)
     _orography(sp, c, il, ix, nb)
     r, _ = surface.chain(tab, c, zon, sqcoa)
     d = _device_inputs(c, r, nb, kx, il, ix)
@@ -155,8 +134,8 @@ def test_column_physics_chain_and_capture(tag):
     moist + radiation node count plus 2 per step."""
     import torch
     nb = 2
-    ix, il, kx = moist.VARIANTS[tag]
-    sp, tab, c, zon, sqcoa = _case(tag, 9700, nb)
+    ix, il, kx = support.grid(tag)
+    sp, tab, c, zon, sqcoa = surface.case(tag, 9700, nb)
     _orography(sp, c, il, ix, nb)
     c2 = _second_step(c, tab, kx)
     d1, d2 = _device_inputs(c, None, nb, kx, il, ix), _device_inputs(c2, None, nb, kx, il, ix)
@@ -167,7 +146,7 @@ def test_column_physics_chain_and_capture(tag):
         D = {"st": torch.full((nb * S,), float("nan"), dtype=torch.float64, device="cuda")}
         for i, d in ((1, d1), (2, d2)):
             D["t%d" % i] = [d[n].clone() for n in ("utend", "vtend", "ttend", "qtend")]
-            D["o%d" % i] = sp.column_outputs(nb, names=SFC_OUT + PBL_OUT + ("slrd", "olr", "icnv", "precnv"))
+            D["o%d" % i] = sp.column_outputs(nb, names=surface.SFC_OUT + surface.PBL_OUT + ("slrd", "olr", "icnv", "precnv"))
         return D
 
     def chain(D):
@@ -279,8 +258,8 @@ def test_column_physics_chain_and_capture(tag):
 def test_state_errors_on_device():
     """SPDY_ERR_STATE without the orography on a device plan; the boundary layer needs none."""
     import speedy_f90_amd as s
-    ix, il, kx = moist.VARIANTS["t30"]
-    sp = moist.plan("t30", 4)
+    ix, il, kx = support.grid("t30")
+    sp = support.plan("t30", 4)
     import torch
     g3, g2, g4 = (torch.zeros((1,) + lead + (il, ix), dtype=torch.float64, device="cuda") for lead in ((kx,), (), (4,)))
     bnd = {n: g2 for n in surface.BOUNDARY}
@@ -297,12 +276,12 @@ def test_column_physics_numpy_form_equals_device_form():
     same kernels on the same bytes."""
     import torch
     nb, tag = 2, "t30k5"
-    ix, il, kx = moist.VARIANTS[tag]
-    sp, tab, c, zon, sqcoa = _case(tag, 9800, nb)
+    ix, il, kx = support.grid(tag)
+    sp, tab, c, zon, sqcoa = surface.case(tag, 9800, nb)
     _orography(sp, c, il, ix, nb)
     tend, sw_only = ("utend", "vtend", "ttend", "qtend"), {"cloudc", "clstr", "icltop", "ssr", "tsr", "tt_rsw"}
     always = set(tend + ("state", "ts", "fsfcu", "precnv", "precls", "cbmf", "iptop", "icnv", "qsat", "rh", "se", "slrd", "slr", "olr",
-                         "tt_rlw", "ut_pbl", "vt_pbl", "tt_pbl", "qt_pbl") + SFC_OUT)       # rad.ssrd stays in the plan's workspace
+                         "tt_rlw", "ut_pbl", "vt_pbl", "tt_pbl", "qt_pbl") + surface.SFC_OUT)       # rad.ssrd stays in the plan's workspace
     out = sp.column_outputs(nb)            # one set for both steps: the caller's rad.ssrd is read by the step without shortwave
     by_name = {n: t for b in ("moist", "rad", "sfc", "pbl") for n, t in out[b].items()}
     by_name.update(ts=out["ts"], fsfcu=out["fsfcu"])
@@ -314,7 +293,7 @@ def test_column_physics_numpy_form_equals_device_form():
                                 g["albsfc"] if sw else None, *[g[n] for n in tend], compute_sw=sw, state=state)
         state = res["state"]
         assert set(res) == always | (sw_only if sw else set()), sorted(set(res) ^ always)
-        d = {n: moist.dev(a) for n, a in g.items()}
+        d = {n: support.dev(a) for n, a in g.items()}
         sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"] if sw else None,
                               by_name["state"], *[d[n] for n in tend], out)
         torch.cuda.synchronize()

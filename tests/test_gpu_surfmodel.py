@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import longrun
-import moist
 import physstep
+import support
 import surfmodel as sm
 import synth
 from conftest import TOL
@@ -25,8 +25,8 @@ def shaped(c, shape):
 
 
 def setup(tag, start, flags=sm.DEFAULT, sp=None):
-    s = moist.package()
-    sp = sp or moist.plan(tag, max_batch=4)
+    s = support.package()
+    sp = sp or support.plan(tag, max_batch=4)
     phis0 = sm.orography(sp)
     sp.surface_set_orography(phis0)
     lat = longrun.latitudes(sp.table("sia_half"))
@@ -172,7 +172,7 @@ def test_captured_couple_across_date_change(tag):
 
 def test_error_codes():
     import torch
-    s = moist.package()
+    s = support.package()
     start = sm.WINDOWS["month"]
     sp, phis0, ref, dev = setup("t30", start)
     il, ix = sp.grid_shape
@@ -225,7 +225,7 @@ def test_error_codes():
     assert code(e) == ARG
     s.SurfaceModel(sp, shaped(c, sp.grid_shape), sm.DELT, sm.DEFAULT & ~sm.SSTAN).close()
     # forcing needs the orography; couple(0) cannot be recorded (it must have run before anything relies on it)
-    bare = moist.plan("t30", max_batch=4)
+    bare = support.plan("t30", max_batch=4)
     c["sstan3"] = np.zeros((3, phis0.size))
     bm = s.SurfaceModel(bare, shaped(c, bare.grid_shape), sm.DELT)
     bm.set_date(d.imont1, d.tmonth, d.tyear)
@@ -248,7 +248,7 @@ def test_error_codes():
     dev.couple_dev(1, **fl)                                  # and the model is usable again
     sp.synchronize()
     # a host-only plan: the tables exist, every device call is refused
-    hp = moist.plan("t30", max_batch=4, device=-1)
+    hp = support.plan("t30", max_batch=4, device=-1)
     c = sm.climatology(phis0, longrun.latitudes(hp.table("sia_half")), start=start[:2])
     hm = s.SurfaceModel(hp, shaped(c, hp.grid_shape), sm.DELT)
     assert np.array_equal(hm.table("cdsea"), dev.table("cdsea"))

@@ -18,115 +18,23 @@ import os
 import numpy as np
 import pytest
 
-import guards
 import moist
-import physstep
 import radiation
+import support
 import surface
-import synth
 import thresholds as th
-from conftest import GOLDEN, TOL
+from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
-INT_OUT = ("moist.iptop", "moist.icnv", "rad.icltop")
-NAMES = ("ug", "vg", "tg", "qg", "phig", "pslg", "albsfc") + th.TEND + surface.BOUNDARY
-
 
 def _plan(tag, tyear, c, il, ix, sp=None):
-    sp = sp or moist.plan(tag, 4)
+    sp = sp or support.plan(tag, 4)
     sp.radiation_set_date(tyear)
     sp.surface_set_orography(c["phis0"].reshape(il, ix))
-    zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
+    zon = radiation.zonal_columns({n: sp.table(n) for n in th.ZON}, 1, il, ix)
     sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, il, ix)
     return sp, zon, sqcoa
-
-
-def _dev(c, il, ix):
-    return {n: moist.dev(radiation.grids(c[n], 1, il, ix)) for n in NAMES}
-
-
-def _columns(t, kx):
-    """a device output of one state as columns [.., ncol]"""
-    a = t.cpu().numpy()[0]
-    return a.reshape(-1, a.shape[-2] * a.shape[-1]).squeeze() if a.ndim == 3 else a.reshape(-1)
-
-
-def _chain(sp, kx, il, ix, calls, fused):
-    """column_physics_dev on the calls [(inputs, compute_sw)] with one radiation state; {"<call>.<name>": tensor}"""
-    import torch
-    sp.set_option("physics_fused", fused)
-    S = torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
-    res, ssrd = {}, None
-    for i, (d, sw) in enumerate(calls, 1):
-        T = [d[n].clone() for n in th.TEND]
-        out = sp.column_outputs(1)
-        if sw:
-            ssrd = out["rad"]["ssrd"]
-        else:                              # ssrd stays where the shortwave call put it (include/spdy.h)
-            out["rad"]["ssrd"] = ssrd
-        sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T, out)
-        torch.cuda.synchronize()
-        res.update({"%d.%s" % (i, n): t for n, t in zip(th.TEND, T)})
-        res.update({"%d.%s" % (i, n): (t.clone() if n in th.SW_ONLY else t) for n, t in physstep.flat_outs(out).items()
-                    if sw or n not in th.SW_ONLY})
-        res["%d.state" % i] = S.clone()
-    return res
-
-
-def _single_calls(sp, kx, il, ix, calls):
-    """the same through the five single entry points"""
-    import torch
-    S = torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
-    res, ssrd = {}, None
-    for i, (d, sw) in enumerate(calls, 1):
-        U, V, T, Q = [d[n].clone() for n in th.TEND]
-        o = sp.column_outputs(1)
-        if sw:
-            ssrd = o["rad"]["ssrd"]
-        else:
-            o["rad"]["ssrd"] = ssrd
-        mo, ro = o["moist"], o["rad"]
-        flux3 = torch.zeros((1, 4, il, ix), dtype=torch.float64, device="cuda")
-        sp.moist_columns_dev(d["tg"], d["qg"], d["phig"], d["pslg"], T, Q, mo)
-        sp.radiation_down_dev(sw, d["tg"], d["qg"], d["phig"], d["pslg"], mo["rh"], mo["precnv"], mo["precls"], mo["iptop"],
-                              d["fmask"], d["albsfc"], S, ro)
-        sp.surface_fluxes_dev(d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], ssrd, ro["slrd"], d, o["ts"], o["fsfcu"],
-                              flux3, o["sfc"])
-        sp.radiation_up_dev(d["tg"], d["pslg"], o["ts"], o["fsfcu"], S, T, ro)
-        sp.pbl_dev(d["qg"], d["phig"], d["pslg"], mo["se"], mo["rh"], mo["qsat"], mo["icnv"], flux3, U, V, T, Q, o["pbl"])
-        torch.cuda.synchronize()
-        res.update({"%d.%s" % (i, n): t for n, t in zip(th.TEND, (U, V, T, Q))})
-        res.update({"%d.%s" % (i, n): (t.clone() if n in th.SW_ONLY else t) for n, t in physstep.flat_outs(o).items()
-                    if sw or n not in th.SW_ONLY})
-        res["%d.state" % i] = S.clone()
-    return res
-
-
-def _against(got, want, kx, scales, cols, stored, label, worst):
-    """got {name: tensor} of one call on the columns `cols` (an index array or a mask) against want {name: array}: [.., ncol]
-    arrays, or with stored=True the fixture's arrays, which hold the columns `cols` only and level kx only of utend and vtend.
-    Integers identical, floats within TOL in the array norm and per column; the worst per-column error per block into `worst`."""
-    for n, w in want.items():
-        g, w = _columns(got[n], kx), np.asarray(w)
-        if n in ("utend", "vtend") and stored:         # the fixture keeps level kx; the restatement has every level
-            g = g[kx - 1]
-        g = g[..., cols]
-        w = w if stored else w[..., cols]
-        assert g.shape == w.shape, (label, n, g.shape, w.shape)
-        if n in ("utend", "vtend") and not stored:     # untouched above level kx: the restatement keeps the input there
-            assert np.array_equal(g[:kx - 1], w[:kx - 1]), (label, n, "above level kx")
-        if n in INT_OUT:
-            assert np.array_equal(g, w), (label, n, int(np.sum(g != w)))
-            continue
-        e = synth.relerr(g, w)
-        ec = guards.column_err(g, w, scales[n][..., cols] if n in scales else None)
-        blk = n.split(".")[0] if "." in n else "tend" if n in th.TEND else "sfc"
-        if float(ec.max()) >= worst.get(blk, (-1.0, ""))[0]:
-            worst[blk] = (float(ec.max()), n)
-        assert e <= TOL, (label, n, "array norm", e)
-        assert float(ec.max()) <= TOL, (label, n, "per column", float(ec.max()), int(np.argmax(ec)))
 
 
 def _stored(ref, tag, step):
@@ -140,47 +48,9 @@ def test_threshold_columns_on_device(tag):
     rad 1.4e-15 / 4.1e-16, sfc 3.9e-16 / 2.1e-15, pbl and tendencies 1.6e-16 / 1.1e-15; every column against the restatement
     moist 1.9e-13 / 3.5e-14 (precls), rad 2.7e-14 / 2.1e-14, sfc 2.8e-15 / 3.8e-15, pbl and tendencies 1.3e-15 / 2.9e-15."""
     ref = np.load(os.path.join(GOLDEN, "ref_thresholds.npz"))
-    ix, il, kx = moist.VARIANTS[tag]
-    check_threshold_columns(tag, moist.plan(tag, 4), moist.tables(moist.HSG[kx]), int(ref[tag + "_seed"]), ref[tag + "_sub"],
-                            lambda step: _stored(ref, tag, step))
-
-
-def check_threshold_columns(tag, sp, tab, seed, ref_sub, stored):
-    """the body of test_threshold_columns_on_device on a plan sp with the tables tab of its levels: thresholds.build(seed), whose
-    stored columns are ref_sub; stored(step) gives the fixture's outputs of call 1 / 2 by name"""
-    import torch
-    ix, il, kx = sp.ix, sp.il, sp.kx
-    sp.radiation_set_date(radiation.DATES[0])
-    zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
-    sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, il, ix)
-    c, sub, r1, r2 = th.build(tab, il * ix, seed, zon, sqcoa)
-    assert np.array_equal(sub, ref_sub)
-    sp.surface_set_orography(c["phis0"].reshape(il, ix))
-    c2 = th.second(c)
-    calls = [(_dev(c, il, ix), True), (_dev(c2, il, ix), False)]
-    sp.column_physics_workspace()
-    one = _chain(sp, kx, il, ix, calls, 1)
-    five = _chain(sp, kx, il, ix, calls, 0)
-    single = _single_calls(sp, kx, il, ix, calls)
-    assert len(one) > 70 and set(one) == set(five) == set(single)
-    for n, v in one.items():
-        assert torch.equal(v, five[n]), ("one launch against five kernels", n)
-        assert torch.equal(v, single[n]), ("one launch against the single entry points", n)
-    assert not torch.isnan(one["2.state"]).any()
-    worst_ref, worst_all = {}, {}
-    everything = np.arange(il * ix)
-    for step, cc, r in ((1, c, r1), (2, c2, r2)):
-        got = {n[2:]: v for n, v in one.items() if n.startswith("%d." % step) and not n.endswith("state")}
-        sc = th.scales(tab, cc, r)
-        _against(got, stored(step), kx, sc, sub, True, "call %d vs reference" % step, worst_ref)
-        mine = th.flat(r, kx)
-        if step == 2:
-            mine = {n: v for n, v in mine.items() if n not in th.SW_ONLY}
-        _against(got, mine, kx, sc, everything, False, "call %d vs restatement" % step, worst_all)
-    sp.close()
-    fmt = lambda w: ", ".join("%s %.1e (%s)" % (b, e, n) for b, (e, n) in sorted(w.items()))
-    print("\n[threshold columns %s on the device, worst per-column error per block] vs reference: %s; vs restatement, every column: %s"
-          % (tag, fmt(worst_ref), fmt(worst_all)))
+    ix, il, kx = support.grid(tag)
+    th.check_threshold_columns(tag, support.plan(tag, 4), moist.tables(moist.HSG[kx]), int(ref[tag + "_seed"]), ref[tag + "_sub"],
+                               lambda step: _stored(ref, tag, step))
 
 
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
@@ -189,19 +59,19 @@ def test_regimes_every_column(tag):
     floats within TOL per column by the column's own scale; near-tie columns are left out (at most 1 % of a regime, asserted).
     Measured on MI355X: no column left out; worst per-column error 3.0e-13 (t30, solstice_dec, moist.precls) and 2.9e-13 (t63k16,
     high_orography, moist.precls); radiation at most 1.1e-13 (clstr), surface 4.2e-14 (evap), tendencies 1.3e-14 (qtend)."""
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
-    sp = moist.plan(tag, 4)
+    sp = support.plan(tag, 4)
     sp.column_physics_workspace()
     for name, (seed, tyear) in th.REGIMES.items():
         c = th.regime(name, tab, il * ix)
         sp, zon, sqcoa = _plan(tag, tyear, c, il, ix, sp)
         r, keep = th.regime_run(tab, c, zon, sqcoa)
         share = th.check_regime(name, r, keep)
-        one = _chain(sp, kx, il, ix, [(_dev(c, il, ix), True)], 1)
+        one = th.chain(sp, kx, il, ix, [(th.dev(c, il, ix), True)], 1)
         got = {n[2:]: v for n, v in one.items() if not n.endswith("state")}
         worst = {}
-        _against(got, th.flat(r, kx), kx, th.scales(tab, c, r), keep, False, "%s %s" % (tag, name), worst)
+        th.against(got, th.flat(r, kx), kx, th.scales(tab, c, r), keep, False, "%s %s" % (tag, name), worst)
         print("[regime %s %s] %.3f %% of the columns left out; worst per-column error per block: %s"
               % (tag, name, 100 * share, ", ".join("%s %.1e (%s)" % (b, e, n) for b, (e, n) in sorted(worst.items()))))
     sp.close()

@@ -1,30 +1,21 @@
 """CPU: host logic of the product -- C-ABI surface, table generation, loud failure without a GPU."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+import support
 import synth
 from conftest import ROOT
+from support import pkg  # noqa: F401
 
 TAGS = ("t30", "t63")
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import speedy_f90_amd as s
-    if not os.path.exists(s.LIB_PATH):
-        s.build()
-    return s
-
-
 def test_cabi_exports_every_declared_symbol(pkg):
     """include/spdy.h is the contract: every function it declares must be exported and bound."""
-    hdr = open(os.path.join(ROOT, "include", "spdy.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(spdy_[a-z0-9_]+)\s*\(", hdr))
+    declared = support.declared()
     assert len(declared) >= 35
     lib = ctypes.CDLL(pkg.LIB_PATH)
     for name in sorted(declared):

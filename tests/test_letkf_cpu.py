@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import letkf as lk
-import moist
+import support
 
 SIZES = [2, 3, 17, 32]
 ERR_ARG, ERR_NO_DEVICE, ERR_STATE = -1, -3, -5
@@ -112,8 +112,8 @@ def test_gaspari_cohn():
 # ---------------------------------------------------------------------------------------------------- a host-only plan
 @pytest.fixture(scope="module")
 def host():
-    s = moist.package()
-    sp = moist.plan("t30k5", 32 * 11, device=-1)
+    s = support.package()
+    sp = support.plan("t30k5", 32 * 11, device=-1)
     yield s, sp, lk.Geometry(sp)
     sp.close()
 
@@ -134,7 +134,7 @@ def test_create_checks(host):
         assert lib.spdy_letkf_create(sp.h, nmem, -1, None) == ERR_ARG and b"nmem" in lib.spdy_last_error()
     assert lib.spdy_letkf_create(sp.h, 2, -1, None) == ERR_ARG and b"max_obs" in lib.spdy_last_error()
     assert lib.spdy_letkf_create(sp.h, 2, 0, None) == ERR_ARG and b"null result" in lib.spdy_last_error()
-    small = moist.plan("t30k5", 2 * 11 - 1, device=-1)
+    small = support.plan("t30k5", 2 * 11 - 1, device=-1)
     assert lib.spdy_letkf_create(small.h, 2, 0, ctypes.byref(h)) == ERR_ARG and b"max_batch" in lib.spdy_last_error()
     small.close()
     tall = s.Spectral("t30", kx=17, max_batch=32 * 35, device=-1)      # E = 32 at kx = 17: more LDS than a compute unit has
@@ -263,7 +263,7 @@ def test_shape_errors(host):
     ens = s.Ensemble(sp, 2, device="cpu")
     with pytest.raises(ValueError):
         ens.analyse(lt)                                              # three members against two
-    other = moist.plan("t30k5", 3 * 20, device=-1)
+    other = support.plan("t30k5", 3 * 20, device=-1)
     with pytest.raises(ValueError):
         s.Ensemble(other, 3, device="cpu").analyse(lt)               # another plan
     other.close()

@@ -9,7 +9,7 @@ import pytest
 
 import letkf as lk
 import letkfinterp as li
-import moist
+import support
 
 ERR_ARG, ERR_NO_DEVICE, ERR_STATE = -1, -3, -5
 STRIDES = [(2, 2), (3, 5), (4, 47), (1, 3), (48, 1)]
@@ -18,8 +18,8 @@ TABLES = ("coarse_columns", "interp_index", "interp_weight")
 
 @pytest.fixture(scope="module")
 def host():
-    s = moist.package()
-    sp = moist.plan("t30k5", 3 * 11, device=-1)
+    s = support.package()
+    sp = support.plan("t30k5", 3 * 11, device=-1)
     yield s, sp, lk.Geometry(sp)
     sp.close()
 

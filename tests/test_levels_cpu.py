@@ -5,15 +5,8 @@ import numpy as np
 import pytest
 
 import levels
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import os
-    import speedy_f90_amd as s
-    if not os.path.exists(s.LIB_PATH):
-        s.build()
-    return s
+from conftest import VARIANTS
+from support import pkg  # noqa: F401
 
 
 def test_sigma_sets():
@@ -26,7 +19,7 @@ def test_sigma_sets():
 
 @pytest.mark.parametrize("kx", levels.LEVELS)
 def test_level_tables_match_oracle(kx, pkg):
-    sp = pkg.Spectral(levels.RES["t30"], kx=kx, device=-1)
+    sp = pkg.Spectral(VARIANTS["t30"][:3], kx=kx, device=-1)
     with pytest.raises(pkg.SpdyError, match="no sigma levels"):      # the reference has no set at this count (geometry.f90:42-48)
         sp.initialize_implicit(2400.0)
     sp.set_sigma(levels.sigma(kx))
@@ -50,8 +43,8 @@ def test_level_tables_match_oracle(kx, pkg):
 def test_level_count_range(pkg):
     """1 <= kx <= SPDY_MAX_KX = 32: 33 and 0 are refused"""
     with pytest.raises(pkg.SpdyError) as e:
-        pkg.Spectral(levels.RES["t30"], kx=33, device=-1)
+        pkg.Spectral(VARIANTS["t30"][:3], kx=33, device=-1)
     assert e.value.code == -2                        # SPDY_ERR_UNSUPPORTED
     with pytest.raises(pkg.SpdyError):
-        pkg.Spectral(levels.RES["t30"], kx=0, device=-1)
-    pkg.Spectral(levels.RES["t30"], kx=32, device=-1).close()
+        pkg.Spectral(VARIANTS["t30"][:3], kx=0, device=-1)
+    pkg.Spectral(VARIANTS["t30"][:3], kx=32, device=-1).close()

@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 import moist
+import support
 import synth
 from conftest import GOLDEN
+from support import pkg  # noqa: F401
 
 TABLES = ("sigl", "sigh", "grdsig", "grdscp", "wvi", "entr")
 FLOATS = ("ttend", "qtend", "precnv", "precls", "cbmf", "qsat", "rh", "se")
@@ -16,18 +18,13 @@ INTS = ("iptop", "icnv")
 
 
 @pytest.fixture(scope="module")
-def pkg():
-    return moist.package()
-
-
-@pytest.fixture(scope="module")
 def ref():
     return np.load(os.path.join(GOLDEN, "ref_moist.npz"))
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_physics_tables_bit_equal(tag, pkg, ref):
-    sp = moist.plan(tag, device=-1)
+    sp = support.plan(tag, device=-1)
     for n in TABLES:
         assert np.array_equal(sp.table(n), ref["%s_tab_%s" % (tag, n)]), n
 
@@ -41,13 +38,13 @@ def test_fixture_coverage(ref):
     for n in ("psmin_cut", "conv_ktop2", "conv_lqthr", "no_conv", "secondary_flux", "lsc_kx", "lsc_interior", "qsat_warm",
               "qsat_cold", "q_clamp"):
         assert counts[n] >= 0.01 * ncol, (n, counts[n])
-    for tag in moist.RES:
+    for tag in support.PHYSICS_TAGS:
         assert float(ref[tag + "_min_margin"]) >= moist.MIN_MARGIN, tag
 
 
 def reference_case(tag, ref):
     """(tables, inputs regenerated from the seed [1, kx, il, ix], column sample) -- the regeneration checked against the stored inputs."""
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
     ins = moist.grid_inputs(tab, (1, il, ix), int(ref[tag + "_seed"]))
     sub, insub = ref[tag + "_sub"], ref[tag + "_insub"]
@@ -60,7 +57,7 @@ def pick(a, sub, ncol):
     return np.asarray(a).reshape(-1, ncol)[:, sub].squeeze()
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_restatement_matches_reference(tag, ref):
     tab, ins, sub = reference_case(tag, ref)
     ncol = ins[3].size
@@ -84,16 +81,16 @@ def test_cabi_argument_checks(pkg):
         sp = pkg.Spectral("t30", kx=kx, max_batch=64, device=-1)
         assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs, None) == -1
         assert lib.spdy_moist_physics_dev(sp.h, *ptrs, None) == -1
-    sp = moist.plan("t30", 4, device=-1)
+    sp = support.plan("t30", 4, device=-1)
     assert lib.spdy_moist_columns_dev(sp.h, 5, *ptrs, None) == -1            # nb > max_batch
     assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs[:4], None, dummy, None) == -1   # NULL ttend
     assert lib.spdy_moist_columns_dev(sp.h, 4, *ptrs, None) == -3            # valid: no device
     assert lib.spdy_moist_physics_dev(sp.h, *ptrs, None) == -1               # max_batch < 3 kx + 1
-    sp = moist.plan("t30", 25, device=-1)
+    sp = support.plan("t30", 25, device=-1)
     assert lib.spdy_moist_physics_dev(sp.h, *ptrs[:4], None, dummy, None) == -1      # NULL ttend
     assert lib.spdy_moist_physics_dev(sp.h, *ptrs, None) == -3
     assert lib.spdy_moist_workspace(sp.h) == -3
     out = pkg.spectral.MoistOut()
     assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs, ctypes.byref(out)) == -3
-    sp = moist.plan("t63k16", device=-1)
+    sp = support.plan("t63k16", device=-1)
     assert lib.spdy_moist_columns_dev(sp.h, 1, *ptrs, None) == -3

@@ -2,6 +2,7 @@
 against closed forms, the library's argument checks and their order on a host-only plan, the lifetime rule of the new object
 (modelled on tests/test_plan_objects_cpu.py), and the twin condition on the restatement alone: the analysis of observations drawn
 from a truth brings the ensemble mean closer to that truth."""
+from support import package
 import ctypes
 
 import numpy as np
@@ -16,11 +17,6 @@ KX, NMEM = 5, 3
 MAX_BATCH = NMEM * (2 * KX + 1)
 SEED = 0x5EED0123456789AB
 EPS = lk.EPS
-
-
-def package():
-    import speedy_f90_amd as s
-    return s
 
 
 def host_plan(kx=KX, max_batch=MAX_BATCH):

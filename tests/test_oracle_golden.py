@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import dynstep
 import synth
 from conftest import GOLDEN
 from golden.make_golden import tail_inputs
@@ -193,32 +194,18 @@ def test_other_level_counts_live(tag, oracle_factory):
     pinned(o.geopotential(T, phis), z, "lev_%s_geop" % tag)
 
 
-STEP_CASES = {"t30": None, "t30k5": (slice(None), slice(None, None, 2), slice(None, None, 2)),
-              "t63k16": (slice(None), slice(None, None, 5), slice(None, None, 3))}
-STEP_J1_SUB = (slice(None), slice(None, None, 2), slice(None, None, 2))     # T30 L8, j1 = 1 (tests/golden/make_golden.py)
-
-
-def step_golden():
-    return np.load(os.path.join(GOLDEN, "ref_step.npz"))
-
-
-def step_inputs(kx, nx, mx):
-    return (synth.cfield((2, kx, nx, mx), 11), synth.cfield((kx, nx, mx), 12, 1e-4),
-            synth.cfield((2, nx, mx), 13), synth.cfield((nx, mx), 14, 1e-4))
-
-
-@pytest.mark.parametrize("tag", sorted(STEP_CASES))
+@pytest.mark.parametrize("tag", sorted(dynstep.STEP_CASES))
 def test_step_field_pinned(tag, oracle_factory):
     """step_field_2d / step_field_3d (time_stepping.f90:126-167): the C oracle against the reference's own two functions,
     compiled by flang from the reference file (oracle/build_ref.sh cuts them into a scratch module) -- golden vectors for
     j1 = 1 (forward step) and j1 = 2 (leapfrog + Robert-Asselin-Williams filter), 8, 5 and 16 levels."""
-    z, o = step_golden(), oracle_factory(tag)
+    z, o = dynstep.step_golden(), oracle_factory(tag)
     wil, rob = z[tag + "_wil_rob"]
     assert wil == float(np.float32(0.53)) and rob == float(np.float32(0.05))      # params.f90:32-33: float32 literals
-    F3, D3, F2, D2 = step_inputs(o.kx, o.nx, o.mx)
+    F3, D3, F2, D2 = dynstep.step_inputs(o.kx, o.nx, o.mx)
     for j1, dt, eps in ((1, 2400.0, 0.0), (2, 4800.0, rob)):
         key = "%s_j%d_" % (tag, j1)
-        sub = STEP_CASES[tag] if STEP_CASES[tag] else (STEP_J1_SUB if j1 == 1 else None)
+        sub = dynstep.STEP_CASES[tag] if dynstep.STEP_CASES[tag] else (dynstep.STEP_J1_SUB if j1 == 1 else None)
         cut = (lambda a: a[(Ellipsis,) + sub]) if sub else (lambda a: a)
         f3, d3 = o.step_field(j1, dt, eps, wil, F3, D3)
         f2, d2 = o.step_field(j1, dt, eps, wil, F2, D2)
@@ -233,7 +220,7 @@ def test_step_field_live(oracle_factory):
     from golden.make_golden import LIVE_STEP_CASES
     z, o = live_golden(), oracle_factory("t30")
     wil, rob = z["sf_wil_rob"]
-    F3, D3, F2, D2 = step_inputs(o.kx, o.nx, o.mx)
+    F3, D3, F2, D2 = dynstep.step_inputs(o.kx, o.nx, o.mx)
     for c, (j1, dt, filtered) in enumerate(LIVE_STEP_CASES):
         for dim, (F, D) in ((3, (F3, D3)), (2, (F2, D2))):
             a, b = o.step_field(j1, dt, rob if filtered else 0.0, wil, F, D)
@@ -254,7 +241,7 @@ def test_spectral_tendencies_pinned(tag, oracle_factory):
     div, t, ps, phis, divdt, tdt, psdt = spectend_inputs(o.kx, o.nx, o.mx)
     a, b, c, phi = o.spectral_tendencies(div, t, ps, phis, divdt, tdt, psdt)
     for j2 in (1, 2):
-        sub = SPECTEND_CASES[tag] or (STEP_J1_SUB if j2 == 2 else None)
+        sub = SPECTEND_CASES[tag] or (dynstep.STEP_J1_SUB if j2 == 2 else None)
         cut = (lambda x: x[sub]) if sub else (lambda x: x)
         key = "%s_j%d_" % (tag, j2)
         for mine, name in ((cut(a), "divdt"), (cut(b), "tdt"), (c, "psdt"), (cut(phi), "phi")):

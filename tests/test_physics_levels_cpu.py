@@ -21,6 +21,7 @@ import surface
 import synth
 import thresholds as th
 from conftest import GOLDEN, TOL
+from support import pkg  # noqa: F401
 
 ZON = physstep.ZON
 MOIST_TABLES = ("sigl", "sigh", "grdsig", "grdscp", "wvi", "entr")
@@ -32,11 +33,6 @@ SFC_IN = ("ug", "vg", "tg", "qg", "phig", "pslg", "utend", "vtend", "ttend", "qt
 SFC_OUT = surface.SFC_3 + ("hfluxn",) + surface.SFC_2D
 INT_OUT = ("moist.iptop", "moist.icnv", "rad.icltop")
 NCOL = pl.IL * pl.IX
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    return moist.package()
 
 
 @pytest.fixture(scope="module")

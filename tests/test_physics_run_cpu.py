@@ -10,6 +10,7 @@ import pytest
 import longrun
 import moist
 import physstep
+import support
 import surface
 import synth
 from conftest import ROOT, TOL
@@ -19,7 +20,7 @@ PROG = ("vor", "div", "t", "tr", "ps")
 
 @pytest.fixture(scope="module")
 def plan():
-    return moist.plan("t30", 36, device=-1)
+    return support.plan("t30", 36, device=-1)
 
 
 def test_shortwave_cadence():

@@ -6,14 +6,10 @@ import ctypes
 import numpy as np
 import pytest
 
-import moist
 import physstep
+import support
 from conftest import VARIANTS
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    return moist.package()
+from support import pkg  # noqa: F401
 
 
 def test_cabi_argument_checks(pkg):
@@ -33,7 +29,7 @@ def test_cabi_argument_checks(pkg):
     sp = pkg.Spectral("t30", kx=6, max_batch=64, device=-1)
     assert phys(sp) == -5                                                        # no sigma levels
     assert lib.spdy_physics_workspace(sp.h) == -3                                # the workspace needs none: no device
-    sp = moist.plan("t30", 4, device=-1)                                         # max_batch 4 < 3 kx + 1: comes late
+    sp = support.plan("t30", 4, device=-1)                                         # max_batch 4 < 3 kx + 1: comes late
     assert phys(sp) == -5                                                        # no date
     sp.radiation_set_date(0.25)
     assert phys(sp) == -5                                                        # ... then no orography
@@ -48,18 +44,18 @@ def test_cabi_argument_checks(pkg):
         assert phys(sp, tend=[d] * i + [None] + [d] * (3 - i)) == -1, i
     assert phys(sp) == -1                                                        # max_batch < 3 kx + 1
     assert b"3*kx+1" in lib.spdy_last_error()
-    sp = moist.plan("t30", 25, device=-1)                                        # exactly 3 kx + 1
+    sp = support.plan("t30", 25, device=-1)                                        # exactly 3 kx + 1
     assert phys(sp, ptrs=[None] + [d] * 5) == -5                                 # state errors before pointers
     sp.radiation_set_date(0.25)
     sp.surface_set_orography(np.zeros((48, 96)))
     assert phys(sp, ptrs=[None] + [d] * 5) == -1
     assert phys(sp) == -3 and phys(sp, 0, alb=None) == -3                        # valid: no device
     assert lib.spdy_physics_workspace(sp.h) == -3
-    sp = moist.plan("t63k16", 49, device=-1)
+    sp = support.plan("t63k16", 49, device=-1)
     sp.radiation_set_date(0.5)
     sp.surface_set_orography(np.zeros((96, 192)))
     assert phys(sp) == -3
-    sp = moist.plan("t63k16", 48, device=-1)
+    sp = support.plan("t63k16", 48, device=-1)
     sp.radiation_set_date(0.5)
     sp.surface_set_orography(np.zeros((96, 192)))
     assert phys(sp) == -1
@@ -67,7 +63,7 @@ def test_cabi_argument_checks(pkg):
 
 def test_physics_fused_option(pkg):
     lib = pkg.load()
-    sp = moist.plan("t30", 4, device=-1)
+    sp = support.plan("t30", 4, device=-1)
     for v in (0, 1, 1, 0):
         assert lib.spdy_plan_set_option(sp.h, b"physics_fused", v) == 0
     for v in (-1, 2, 7):
@@ -77,7 +73,7 @@ def test_physics_fused_option(pkg):
 
 def test_python_binding(pkg):
     """physics_workspace / physics_dev reach the library (a host-only plan answers SPDY_ERR_NO_DEVICE)."""
-    sp = moist.plan("t30", 4, device=-1)
+    sp = support.plan("t30", 4, device=-1)
     with pytest.raises(pkg.SpdyError) as e:
         sp.physics_workspace()
     assert e.value.code == -3
@@ -90,7 +86,7 @@ def test_reference_side_first_step(oracle_factory):
     tag = "t30"
     kx = VARIANTS[tag][3]
     o = oracle_factory(tag)
-    sp = moist.plan(tag, 4 * kx + 4, device=-1)
+    sp = support.plan(tag, 4 * kx + 4, device=-1)
     case = physstep.Case(tag, sp, o)
     z = lambda: np.zeros((kx, o.il, o.ix))
     st = {}

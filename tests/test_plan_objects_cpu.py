@@ -9,6 +9,7 @@ import pytest
 
 import longrun
 import surfmodel as sm
+from support import package
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_STATE = 0, -1, -3, -5
 KX, MAX_BATCH, NMEM = 8, 64, 2
@@ -17,11 +18,6 @@ PREFIXES = {"surface_model": ("spdy_surface_model_", "spdy_ens_surface_model_"),
 NO_HANDLE = {"spdy_diagnostics_format"}          # formats a row the caller passes: takes no object
 NULL_TEXT = {"surface_model": b"null surface model", "sppt": b"null SPPT pattern", "diagnostics": b"null diagnostics object",
              "letkf": b"null analysis object"}
-
-
-def package():
-    import speedy_f90_amd as s
-    return s
 
 
 def entry_points(kind):

@@ -8,15 +8,12 @@ import pytest
 
 import moist
 import radiation
+import support
 import synth
 from conftest import GOLDEN, TOL
+from support import pkg  # noqa: F401
 
 ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    return moist.package()
 
 
 @pytest.fixture(scope="module")
@@ -28,10 +25,10 @@ def zonal_ref(ref, tag, di):
     return {n: ref["%s_d%d_%s" % (tag, di, n)] for n in ZON}
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_radiation_tables_bit_equal(tag, pkg, ref):
     """fband and, after spdy_radiation_set_date, the zonal forcing of both dates, bit for bit."""
-    sp = moist.plan(tag, device=-1)
+    sp = support.plan(tag, device=-1)
     assert np.array_equal(sp.table("fband"), ref["fband"].ravel())
     assert np.array_equal(radiation.FBAND, ref["fband"])
     for n in ZON:
@@ -52,8 +49,8 @@ def test_fixture_coverage(ref):
     assert ncol == 96 * 48
     for n in ("cltop_nl1", "cltop_mid", "cltop_iptop", "cltop_2", "cltop_none", "strat_land", "strat_sea", "polar_night"):
         assert counts[n] >= 0.01 * ncol, (n, counts[n])
-    for tag in moist.RES:
-        il = moist.VARIANTS[tag][1]
+    for tag in support.PHYSICS_TAGS:
+        il = support.grid(tag)[1]
         s0, s1 = ref["%s_d0_stratz" % tag], ref["%s_d1_stratz" % tag]
         assert np.any(s0[il // 2:] > 0) and np.any(s1[:il // 2] > 0), tag
 
@@ -61,7 +58,7 @@ def test_fixture_coverage(ref):
 def reference_case(tag, ref, di=0):
     """(tables, columns regenerated from the seed, column sample, zonal fields per column) -- the regeneration checked against
     the stored inputs."""
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
     zon = radiation.zonal_columns(zonal_ref(ref, tag, di), 1, il, ix)
     c = radiation.columns(tab, il * ix, int(ref[tag + "_seed"]), radiation.zonal_columns(zonal_ref(ref, tag, 0), 1, il, ix))
@@ -81,7 +78,7 @@ def check(got, ref, key, sub):
 
 
 @pytest.mark.parametrize("di", [0, 1])
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_restatement_matches_reference(tag, di, ref):
     tab, c, sub, zon = reference_case(tag, ref, di)
     r1, r2 = radiation.two_steps(tab, c, zon)
@@ -106,7 +103,7 @@ def test_cabi_argument_checks(pkg):
     sp = pkg.Spectral("t30", kx=6, max_batch=64, device=-1)
     lib.spdy_radiation_set_date(sp.h, ctypes.c_double(0.1))
     assert down(sp, 1) == -5 and upc(sp, 1) == -5        # no sigma levels
-    sp = moist.plan("t30", 4, device=-1)
+    sp = support.plan("t30", 4, device=-1)
     assert lib.spdy_radiation_state_size(sp.h) == (6 * 8 + 7) * 96 * 48
     assert down(sp, 1) == -5 and upc(sp, 1) == -5        # no date
     assert lib.spdy_radiation_set_date(sp.h, ctypes.c_double(0.25)) == 0
@@ -117,6 +114,6 @@ def test_cabi_argument_checks(pkg):
     assert upc(sp, 1, ptrs=[d] * 5 + [None]) == -1                    # NULL ttend
     assert down(sp, 4) == -3 and upc(sp, 4) == -3                     # valid: no device
     assert down(sp, 0, ptrs=[None] * 8) == -3                         # nb = 0 needs no pointers
-    sp = moist.plan("t63k16", device=-1)
+    sp = support.plan("t63k16", device=-1)
     sp.radiation_set_date(0.5)
     assert down(sp, 1) == -3 and upc(sp, 1) == -3

@@ -7,8 +7,8 @@ import ctypes
 import numpy as np
 import pytest
 
-import moist
 import sppt
+import support
 from conftest import TOL, VARIANTS
 
 KAT = (((0, 0, 0, 0), (0, 0), "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),
@@ -35,7 +35,7 @@ def test_uniform_mapping_at_the_extreme_words():
 def test_tables_on_a_host_plan(tag):
     import speedy_f90_amd as s
     kx = VARIANTS[tag][3]
-    sp = moist.plan(tag, max_batch=4, device=-1)
+    sp = support.plan(tag, max_batch=4, device=-1)
     mu = np.linspace(0.0, 1.0, kx)
     for nsteps, m in ((36, None), (48, mu)):
         pat = s.Sppt(sp, nsteps, m, seed=1)
@@ -70,7 +70,7 @@ def test_restatement_against_the_reference(golden, oracle_factory):
 
 def test_error_codes():
     import speedy_f90_amd as s
-    sp = moist.plan("t30", max_batch=4, device=-1)
+    sp = support.plan("t30", max_batch=4, device=-1)
     lib, h = sp.lib, ctypes.c_void_p()
     ARG = -1
     assert lib.spdy_sppt_create(None, 36, None, 1, ctypes.byref(h)) == ARG

@@ -11,19 +11,16 @@ import pytest
 
 import moist
 import radiation
+import support
 import surface
 import synth
 from conftest import GOLDEN, TOL
+from support import pkg  # noqa: F401
 
 ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
 TABLES = ("vd_scalars", "vd_rsig", "vd_rsig1", "vd_drh0", "vd_fvdiq2")
 INPUTS = ("ug", "vg", "tg", "qg", "phig", "pslg", "utend", "vtend", "ttend", "qtend", "albsfc", "phis0") + surface.BOUNDARY
 SFC_OUT = surface.SFC_3 + ("hfluxn",) + surface.SFC_2D
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    return moist.package()
 
 
 @pytest.fixture(scope="module")
@@ -34,9 +31,9 @@ def ref():
 def reference_case(tag, ref):
     """(tables, columns regenerated from the seed, column sample, zonal fields and sqrt(coa) per column, the restated chain) -- the
     regeneration checked against the stored inputs."""
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
-    sp = moist.plan(tag, device=-1)
+    sp = support.plan(tag, device=-1)
     sp.radiation_set_date(radiation.DATES[0])
     zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
     sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, il, ix)
@@ -57,11 +54,11 @@ def restated(r, kx):
     return out
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_surface_tables_bit_equal(tag, pkg, ref):
     """The vertical-diffusion scalars and rows and, after spdy_surface_set_orography, forog: bit for bit."""
-    ix, il, kx = moist.VARIANTS[tag]
-    sp = moist.plan(tag, device=-1)
+    ix, il, kx = support.grid(tag)
+    sp = support.plan(tag, device=-1)
     tab = moist.tables(moist.HSG[kx])
     for n in TABLES:
         assert np.array_equal(sp.table(n), ref["%s_tab_%s" % (tag, n)]), n
@@ -83,11 +80,11 @@ def test_fixture_coverage(ref):
     assert set(counts) == set(surface.SFC_BRANCHES + surface.PBL_BRANCHES)
     for n, v in counts.items():
         assert v >= 0.01 * ncol, (n, v)
-    for tag in moist.RES:
+    for tag in support.PHYSICS_TAGS:
         assert float(ref[tag + "_min_margin"]) >= surface.MIN_MARGIN == 1e-9, tag
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_restatement_matches_reference(tag, ref):
     tab, c, sub, zon, sqcoa, r = reference_case(tag, ref)
     assert float(r["margin"].min()) == float(ref[tag + "_min_margin"])
@@ -120,7 +117,7 @@ def test_cabi_argument_checks(pkg):
         assert lib.spdy_column_physics_workspace(sp.h) == -1
     sp = pkg.Spectral("t30", kx=6, max_batch=64, device=-1)
     assert sfc(sp, 1) == -5 and pbl(sp, 1) == -5 and chain(sp, 1) == -5        # no sigma levels
-    sp = moist.plan("t30", 4, device=-1)
+    sp = support.plan("t30", 4, device=-1)
     phis0 = np.zeros((48, 96))
     assert sfc(sp, 5) == -1 and pbl(sp, 5) == -1 and chain(sp, 5) == -1        # nb > max_batch comes first
     assert sfc(sp, 1) == -5                                                    # no orography
@@ -147,7 +144,7 @@ def test_cabi_argument_checks(pkg):
     assert sfc(sp, 4) == -3 and pbl(sp, 4) == -3 and chain(sp, 4) == -3        # valid: no device
     assert sfc(sp, 0, ptrs=[None] * 8) == -3 and pbl(sp, 0, ptrs=[None] * 12) == -3   # nb = 0 needs no pointers
     assert lib.spdy_column_physics_workspace(sp.h) == -3
-    sp = moist.plan("t63k16", device=-1)
+    sp = support.plan("t63k16", device=-1)
     sp.radiation_set_date(0.5)
     sp.surface_set_orography(np.zeros((96, 192)))
     assert sfc(sp, 1) == -3 and pbl(sp, 1) == -3 and chain(sp, 1) == -3

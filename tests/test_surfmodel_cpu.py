@@ -8,6 +8,7 @@ import pytest
 import longrun
 import moist
 import physstep
+import support
 import surfmodel as sm
 import synth
 from conftest import TOL
@@ -20,8 +21,8 @@ def shaped(c, shape):
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
 def test_host_tables_match_restatement(tag, oracle_factory):
     """land_model_init's and sea_model_init's constant fields as the library builds them on a host-only plan"""
-    s = moist.package()
-    sp = moist.plan(tag, max_batch=4, device=-1)
+    s = support.package()
+    sp = support.plan(tag, max_batch=4, device=-1)
     phis0 = sm.orography(oracle_factory(tag))      # a host-only plan does not transform
     c = sm.climatology(phis0, longrun.latitudes(sp.table("sia_half")))
     tab = sm.tables(c["fmask"], c["alb0"], sp.table("sia_half"), sp.ix)
@@ -66,7 +67,7 @@ def test_dates_and_weights():
 @pytest.mark.parametrize("wname", list(sm.WINDOWS))
 @pytest.mark.parametrize("tag", ["t30", "t63k16"])
 def test_windows_conditions(tag, wname, oracle_factory):
-    sp = moist.plan(tag, max_batch=4, device=-1)
+    sp = support.plan(tag, max_batch=4, device=-1)
     phis0 = sm.orography(oracle_factory(tag))      # a host-only plan does not transform
     n = phis0.size
     start = sm.WINDOWS[wname]

@@ -16,18 +16,15 @@ import pytest
 import guards
 import moist
 import radiation
+import support
 import surface
 import synth
 import thresholds as th
 from conftest import GOLDEN, TOL
+from support import pkg  # noqa: F401
 
 ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
 INT_OUT = ("moist.iptop", "moist.icnv", "rad.icltop")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    return moist.package()
 
 
 @pytest.fixture(scope="module")
@@ -36,9 +33,9 @@ def ref():
 
 
 def case(tag, date=radiation.DATES[0]):
-    ix, il, kx = moist.VARIANTS[tag]
+    ix, il, kx = support.grid(tag)
     tab = moist.tables(moist.HSG[kx])
-    sp = moist.plan(tag, device=-1)
+    sp = support.plan(tag, device=-1)
     sp.radiation_set_date(date)
     zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
     sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, il, ix)
@@ -130,7 +127,7 @@ def test_restatement_matches_reference_on_thresholds(tag, pkg, ref):
 def test_regime_near_tie_shares(tag, pkg):
     """Each regime's state has at most 1 % of its columns near a tie (they are left out, not drawn again), no branch loses all
     its columns, and the regime is what its name says."""
-    kx = moist.VARIANTS[tag][2]
+    kx = support.grid(tag)[2]
     for name, (seed, tyear) in th.REGIMES.items():
         tab, zon, sqcoa, ncol = case(tag, tyear)
         c = th.regime(name, tab, ncol)
@@ -155,7 +152,7 @@ def test_regime_near_tie_shares(tag, pkg):
         assert all(np.isfinite(v).all() for v in th.flat(r, kx).values()), name
 
 
-@pytest.mark.parametrize("tag", sorted(moist.RES))
+@pytest.mark.parametrize("tag", support.PHYSICS_TAGS)
 def test_date_table_over_a_year(tag, pkg, ref):
     """fsol, ozone, ozupp, zenit, stratz of spdy_radiation_set_date bit for bit equal to the flang-built reference at every stored
     tyear (0, the solstices and equinoxes, the values closest below 1, the two dates in use, every 12th of the year), and the
@@ -163,7 +160,7 @@ def test_date_table_over_a_year(tag, pkg, ref):
     ty = ref[tag + "_tyear"]
     assert ty.size >= 20 and ty[0] == 0.0 and ty[-1] == np.nextafter(1.0, 0.0) and set(radiation.DATES) <= set(ty.tolist())
     assert {th.SOLSTICE_JUN, th.SOLSTICE_DEC, th.EQUINOX_MAR} <= set(ty.tolist())
-    sp = moist.plan(tag, device=-1)
+    sp = support.plan(tag, device=-1)
     got, mine = [], []
     for t in ty:
         sp.radiation_set_date(float(t))

@@ -21,10 +21,14 @@ land); REGIME_SEEDS are those for which the restatement alone leaves at most 1 %
 (tests/test_thresholds_cpu.py checks it)."""
 import numpy as np
 
+import guards
 import moist
+import physstep
 import radiation
+import support
 import surface
 import synth
+from conftest import TOL
 from moist import T0
 from radiation import QACL
 
@@ -465,3 +469,134 @@ def check_regime(name, r, keep):
     for k, mask in br.items():
         assert not mask.any() or (mask & keep).any(), (name, k)
     return share
+
+
+# ------------------------------------------------------------------------------------------------ device side (torch)
+ZON = ("fsol", "ozone", "ozupp", "zenit", "stratz")
+INT_OUT = ("moist.iptop", "moist.icnv", "rad.icltop")
+NAMES = ("ug", "vg", "tg", "qg", "phig", "pslg", "albsfc") + TEND + surface.BOUNDARY
+
+
+def dev(c, il, ix):
+    return {n: support.dev(radiation.grids(c[n], 1, il, ix)) for n in NAMES}
+
+
+def device_columns(t, kx):
+    """a device output of one state as columns [.., ncol]"""
+    a = t.cpu().numpy()[0]
+    return a.reshape(-1, a.shape[-2] * a.shape[-1]).squeeze() if a.ndim == 3 else a.reshape(-1)
+
+
+def chain(sp, kx, il, ix, calls, fused):
+    """column_physics_dev on the calls [(inputs, compute_sw)] with one radiation state; {"<call>.<name>": tensor}"""
+    import torch
+    sp.set_option("physics_fused", fused)
+    S = torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
+    res, ssrd = {}, None
+    for i, (d, sw) in enumerate(calls, 1):
+        T = [d[n].clone() for n in TEND]
+        out = sp.column_outputs(1)
+        if sw:
+            ssrd = out["rad"]["ssrd"]
+        else:                              # ssrd stays where the shortwave call put it (include/spdy.h)
+            out["rad"]["ssrd"] = ssrd
+        sp.column_physics_dev(sw, d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], d, d["albsfc"], S, *T, out)
+        torch.cuda.synchronize()
+        res.update({"%d.%s" % (i, n): t for n, t in zip(TEND, T)})
+        res.update({"%d.%s" % (i, n): (t.clone() if n in SW_ONLY else t) for n, t in physstep.flat_outs(out).items()
+                    if sw or n not in SW_ONLY})
+        res["%d.state" % i] = S.clone()
+    return res
+
+
+def single_calls(sp, kx, il, ix, calls):
+    """the same through the five single entry points"""
+    import torch
+    S = torch.full((sp.radiation_state_size(),), float("nan"), dtype=torch.float64, device="cuda")
+    res, ssrd = {}, None
+    for i, (d, sw) in enumerate(calls, 1):
+        U, V, T, Q = [d[n].clone() for n in TEND]
+        o = sp.column_outputs(1)
+        if sw:
+            ssrd = o["rad"]["ssrd"]
+        else:
+            o["rad"]["ssrd"] = ssrd
+        mo, ro = o["moist"], o["rad"]
+        flux3 = torch.zeros((1, 4, il, ix), dtype=torch.float64, device="cuda")
+        sp.moist_columns_dev(d["tg"], d["qg"], d["phig"], d["pslg"], T, Q, mo)
+        sp.radiation_down_dev(sw, d["tg"], d["qg"], d["phig"], d["pslg"], mo["rh"], mo["precnv"], mo["precls"], mo["iptop"],
+                              d["fmask"], d["albsfc"], S, ro)
+        sp.surface_fluxes_dev(d["ug"], d["vg"], d["tg"], d["qg"], d["phig"], d["pslg"], ssrd, ro["slrd"], d, o["ts"], o["fsfcu"],
+                              flux3, o["sfc"])
+        sp.radiation_up_dev(d["tg"], d["pslg"], o["ts"], o["fsfcu"], S, T, ro)
+        sp.pbl_dev(d["qg"], d["phig"], d["pslg"], mo["se"], mo["rh"], mo["qsat"], mo["icnv"], flux3, U, V, T, Q, o["pbl"])
+        torch.cuda.synchronize()
+        res.update({"%d.%s" % (i, n): t for n, t in zip(TEND, (U, V, T, Q))})
+        res.update({"%d.%s" % (i, n): (t.clone() if n in SW_ONLY else t) for n, t in physstep.flat_outs(o).items()
+                    if sw or n not in SW_ONLY})
+        res["%d.state" % i] = S.clone()
+    return res
+
+
+def against(got, want, kx, scales, cols, stored, label, worst):
+    """got {name: tensor} of one call on the columns `cols` (an index array or a mask) against want {name: array}: [.., ncol]
+    arrays, or with stored=True the fixture's arrays, which hold the columns `cols` only and level kx only of utend and vtend.
+    Integers identical, floats within TOL in the array norm and per column; the worst per-column error per block into `worst`."""
+    for n, w in want.items():
+        g, w = device_columns(got[n], kx), np.asarray(w)
+        if n in ("utend", "vtend") and stored:         # the fixture keeps level kx; the restatement has every level
+            g = g[kx - 1]
+        g = g[..., cols]
+        w = w if stored else w[..., cols]
+        assert g.shape == w.shape, (label, n, g.shape, w.shape)
+        if n in ("utend", "vtend") and not stored:     # untouched above level kx: the restatement keeps the input there
+            assert np.array_equal(g[:kx - 1], w[:kx - 1]), (label, n, "above level kx")
+        if n in INT_OUT:
+            assert np.array_equal(g, w), (label, n, int(np.sum(g != w)))
+            continue
+        e = synth.relerr(g, w)
+        ec = guards.column_err(g, w, scales[n][..., cols] if n in scales else None)
+        blk = n.split(".")[0] if "." in n else "tend" if n in TEND else "sfc"
+        if float(ec.max()) >= worst.get(blk, (-1.0, ""))[0]:
+            worst[blk] = (float(ec.max()), n)
+        assert e <= TOL, (label, n, "array norm", e)
+        assert float(ec.max()) <= TOL, (label, n, "per column", float(ec.max()), int(np.argmax(ec)))
+
+
+def check_threshold_columns(tag, sp, tab, seed, ref_sub, stored):
+    """the body of test_threshold_columns_on_device on a plan sp with the tables tab of its levels: thresholds.build(seed), whose
+    stored columns are ref_sub; stored(step) gives the fixture's outputs of call 1 / 2 by name"""
+    import torch
+    ix, il, kx = sp.ix, sp.il, sp.kx
+    sp.radiation_set_date(radiation.DATES[0])
+    zon = radiation.zonal_columns({n: sp.table(n) for n in ZON}, 1, il, ix)
+    sqcoa = surface.sqcoa_columns(sp.table("coa_half"), 1, il, ix)
+    c, sub, r1, r2 = build(tab, il * ix, seed, zon, sqcoa)
+    assert np.array_equal(sub, ref_sub), "%s: the constructed columns build() chose are not the fixture's stored ones" % tag
+    sp.surface_set_orography(c["phis0"].reshape(il, ix))
+    c2 = second(c)
+    calls = [(dev(c, il, ix), True), (dev(c2, il, ix), False)]
+    sp.column_physics_workspace()
+    one = chain(sp, kx, il, ix, calls, 1)
+    five = chain(sp, kx, il, ix, calls, 0)
+    single = single_calls(sp, kx, il, ix, calls)
+    assert len(one) > 70 and set(one) == set(five) == set(single), (
+        "%s: the three routes wrote different sets of outputs" % tag, len(one), len(five), len(single))
+    for n, v in one.items():
+        assert torch.equal(v, five[n]), ("one launch against five kernels", n)
+        assert torch.equal(v, single[n]), ("one launch against the single entry points", n)
+    assert not torch.isnan(one["2.state"]).any(), "%s: NaN left in the radiation state after call 2" % tag
+    worst_ref, worst_all = {}, {}
+    everything = np.arange(il * ix)
+    for step, cc, r in ((1, c, r1), (2, c2, r2)):
+        got = {n[2:]: v for n, v in one.items() if n.startswith("%d." % step) and not n.endswith("state")}
+        sc = scales(tab, cc, r)
+        against(got, stored(step), kx, sc, sub, True, "call %d vs reference" % step, worst_ref)
+        mine = flat(r, kx)
+        if step == 2:
+            mine = {n: v for n, v in mine.items() if n not in SW_ONLY}
+        against(got, mine, kx, sc, everything, False, "call %d vs restatement" % step, worst_all)
+    sp.close()
+    fmt = lambda w: ", ".join("%s %.1e (%s)" % (b, e, n) for b, (e, n) in sorted(w.items()))
+    print("\n[threshold columns %s on the device, worst per-column error per block] vs reference: %s; vs restatement, every column: %s"
+          % (tag, fmt(worst_ref), fmt(worst_all)))

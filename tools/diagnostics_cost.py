@@ -19,15 +19,15 @@ import torch  # noqa: E402
 
 import dynstep  # noqa: E402
 import modelstep  # noqa: E402
-import moist  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
+import support  # noqa: E402
 from conftest import VARIANTS  # noqa: E402
 from physics_step_rate import report, time_interleaved  # noqa: E402
 
 
 def run(tag, reps, repeats, rows, guard):
     kx = VARIANTS[tag][3]
-    sp = moist.plan(tag, 4 * kx + 4)
+    sp = support.plan(tag, 4 * kx + 4)
     dt = 2400.0 if tag == "t30" else 1200.0
     sp.initialize_implicit(dt)
     st = dynstep.state(sp, 8000)

@@ -71,8 +71,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import torch  # noqa: E402
 
 import modelstep  # noqa: E402
-import moist  # noqa: E402
 import physstep  # noqa: E402
+import support  # noqa: E402
 import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
 from conftest import VARIANTS  # noqa: E402
@@ -122,7 +122,7 @@ def run(tag, members, reps, repeats, label, rows):
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
     emax = max(members) if members else 1
-    sp = moist.plan(tag, emax * (4 * kx + 4))
+    sp = support.plan(tag, emax * (4 * kx + 4))
     case = physstep.Case(tag, sp, o)
     sp.surface_set_orography(case.phis0)
     dt = physstep.DT[tag]
@@ -220,7 +220,7 @@ def run_coupled(tag, members, reps, repeats, label, rows, batched):
     o = Oracle(*VARIANTS[tag])
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
-    sp = moist.plan(tag, max(members) * (4 * kx + 4))
+    sp = support.plan(tag, max(members) * (4 * kx + 4))
     case = physstep.Case(tag, sp, o)
     sp.surface_set_orography(case.phis0)
     dt = physstep.DT[tag]
@@ -303,7 +303,7 @@ def run_output(tag, members, reps, repeats, label, rows):
     """graph replays of the ensemble output call, of E single-state output calls, and of the call's inverse batch alone"""
     import ensemblestep
     kx = VARIANTS[tag][3]
-    sp = moist.plan(tag, max(members) * (4 * kx + 4))
+    sp = support.plan(tag, max(members) * (4 * kx + 4))
     spec, grid = sp.nx * sp.mx * 16, sp.il * sp.ix
     graphs, keep = {}, []
     for E in members:
@@ -362,7 +362,7 @@ def run_sppt(tag, members, reps, repeats, label, rows):
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
     emax = max(members)
-    sp = moist.plan(tag, emax * (4 * kx + 4))
+    sp = support.plan(tag, emax * (4 * kx + 4))
     case = physstep.Case(tag, sp, o)
     sp.surface_set_orography(case.phis0)
     dt = physstep.DT[tag]
@@ -489,7 +489,7 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
     o = Oracle(*VARIANTS[tag])
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
-    sp = moist.plan(tag, max(members) * (4 * kx + 4))
+    sp = support.plan(tag, max(members) * (4 * kx + 4))
     case = physstep.Case(tag, sp, o)
     sp.surface_set_orography(case.phis0)
     dt = physstep.DT[tag]

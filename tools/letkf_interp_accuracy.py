@@ -25,7 +25,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import ensemblestep  # noqa: E402
 import letkf as lk  # noqa: E402
 import letkfinterp as li  # noqa: E402
-import moist  # noqa: E402
+import support  # noqa: E402
 import synth  # noqa: E402
 from conftest import VARIANTS  # noqa: E402
 
@@ -75,7 +75,7 @@ def main():
     o = Oracle(*VARIANTS[tag])
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
-    sp = moist.plan(tag, E * (2 * kx + 1), device=-1)
+    sp = support.plan(tag, E * (2 * kx + 1), device=-1)
     g = lk.Geometry(sp)
     ms = ensemblestep.member_states(sp, E + 1)
     x = grids(o, [{n: ms[0][n] + 0.01 * (ms[e + 1][n] - ms[0][n]) for n in ("vor", "div", "t", "tr", "ps")} for e in range(E)])

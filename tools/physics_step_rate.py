@@ -25,6 +25,7 @@ import modelstep  # noqa: E402
 import moist  # noqa: E402
 import physstep  # noqa: E402
 import radiation  # noqa: E402
+import support  # noqa: E402
 import surface  # noqa: E402
 import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
@@ -103,7 +104,7 @@ def step(tag, reps, repeats, rows):
     o = Oracle(*VARIANTS[tag])
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
-    sp = moist.plan(tag, 4 * kx + 4)
+    sp = support.plan(tag, 4 * kx + 4)
     case = physstep.Case(tag, sp, o)
     sp.surface_set_orography(case.phis0)
     dt = physstep.DT[tag]

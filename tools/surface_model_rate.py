@@ -25,8 +25,8 @@ import torch  # noqa: E402
 
 import longrun  # noqa: E402
 import modelstep  # noqa: E402
-import moist  # noqa: E402
 import physstep  # noqa: E402
+import support  # noqa: E402
 import surfmodel as sm  # noqa: E402
 import synth  # noqa: E402
 import speedy_f90_amd as s  # noqa: E402
@@ -41,7 +41,7 @@ def run(tag, reps, repeats, rows):
     o = Oracle(*VARIANTS[tag])
     if tag in synth.SIGMA_SETS:
         o.set_sigma(synth.SIGMA_SETS[tag])
-    sp = moist.plan(tag, 4 * kx + 4)
+    sp = support.plan(tag, 4 * kx + 4)
     case = physstep.Case(tag, sp, o)
     il, ix = sp.il, sp.ix
     sp.surface_set_orography(case.phis0)
