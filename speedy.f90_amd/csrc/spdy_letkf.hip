@@ -14,7 +14,7 @@ namespace {
 constexpr int LETKF_BLOCK = 256;     // threads of a column's workgroup: four waves
 constexpr int LETKF_CHUNK = 256;     // observations scanned per step: one per thread
 constexpr int LETKF_TILE = 16;       // observations in range staged in LDS per accumulation step
-constexpr int LETKF_SWEEPS = 16;     // the most Jacobi sweeps (E = 32 converges in 7 to 9)
+constexpr int LETKF_SWEEPS = 16;     // the most Jacobi sweeps (E = 32: 9 to 13 with many observations, up to 16 with fewer than members)
 constexpr int LETKF_MAX_KX = 32;
 constexpr double LETKF_REARTH = 6.371e6;
 constexpr double LETKF_TOL = 0x1p-53;   // a pair with |a_pq| <= tol * sqrt(a_pp a_qq) is not rotated

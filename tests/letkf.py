@@ -146,10 +146,22 @@ def pair(m, r, n):
     return (r + m) % (n - 1), (r - m + n - 1) % (n - 1)
 
 
-def jacobi(A, sweeps=30):
+SLAB = 128           # matrices `jacobi` turns at a time
+SWEEPS = 16          # LETKF_SWEEPS of csrc/spdy_letkf.hip: the most sweeps the kernel runs
+
+
+def jacobi(A, sweeps=30, counts=False):
     """cyclic Jacobi on a batch of symmetric matrices (N, n, n) -> (lam (N, n), V (N, n, n)): round-robin pairs, an odd n padded by
-    a decoupled row, a pair rotated unless |a_pq| <= eps/2 sqrt(a_pp a_qq), sweeps until no pair of any matrix rotates"""
+    a decoupled row, a pair rotated unless |a_pq| <= eps/2 sqrt(a_pp a_qq), sweeps until no pair of any matrix rotates.  With
+    counts also the sweeps each matrix ran (N,): its last sweep with a rotation and the idle one that closes it, `sweeps` at the most.
+    A large batch goes slab by slab, each of a size that stays in cache and each until its own matrices are done: a sweep
+    without a rotation changes no value, so a matrix's result does not depend on its neighbours"""
     N, n0 = A.shape[0], A.shape[1]
+    if N > SLAB:
+        parts = [jacobi(A[i:i + SLAB], sweeps, True) for i in range(0, N, SLAB)]
+        lam, Vv, ran = (np.concatenate([part[n] for part in parts]) for n in range(3))
+        return (lam, Vv, ran) if counts else (lam, Vv)
+    ran = np.ones(N, np.int64)
     n = n0 + (n0 & 1)
     M = np.zeros((n, n, N))                                      # the batch last: a pair's rows and columns are whole slabs
     M[:n0, :n0] = np.moveaxis(A, 0, -1)
@@ -157,8 +169,8 @@ def jacobi(A, sweeps=30):
         M[n0, n0] = 1.0
     Vv = np.zeros((n, n, N))
     Vv[np.arange(n), np.arange(n)] = 1.0
-    for _ in range(sweeps):
-        rotated = False
+    for sweep in range(sweeps):
+        turned = np.zeros(N, bool)
         for r in range(n - 1):
             pq = [pair(m, r, n) for m in range(n // 2)]
             p, q = np.array([a for a, _ in pq]), np.array([b for _, b in pq])
@@ -169,7 +181,7 @@ def jacobi(A, sweeps=30):
                 t = np.copysign(1.0, theta) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
             c = np.where(rot, 1.0 / np.sqrt(t * t + 1.0), 1.0)
             s = np.where(rot, t * c, 0.0)
-            rotated = rotated or bool(rot.any())
+            turned |= rot.any(axis=0)
             Mp, Mq = M[p], M[q]
             M[p], M[q] = c[:, None] * Mp - s[:, None] * Mq, s[:, None] * Mp + c[:, None] * Mq
             Mp, Mq = M[:, p], M[:, q]
@@ -178,13 +190,12 @@ def jacobi(A, sweeps=30):
             M[q, p] = np.where(rot, 0.0, M[q, p])
             Vp, Vq = Vv[:, p], Vv[:, q]
             Vv[:, p], Vv[:, q] = c[None] * Vp - s[None] * Vq, s[None] * Vp + c[None] * Vq
-        if not rotated:
+        ran[turned] = min(sweep + 2, sweeps)
+        if not turned.any():
             break
-    lam = np.moveaxis(M[np.arange(n), np.arange(n)], -1, 0)
-    Vv = np.moveaxis(Vv, -1, 0)
-    if n != n0:      # the decoupled row keeps its place: column n0 of V stays e_n0
-        return lam[:, :n0], Vv[:, :n0, :n0]
-    return lam, Vv
+    lam = np.moveaxis(M[np.arange(n), np.arange(n)], -1, 0)[:, :n0]
+    Vv = np.moveaxis(Vv, -1, 0)[:, :n0, :n0]      # the decoupled row keeps its place: column n0 of V stays e_n0
+    return (lam, Vv, ran) if counts else (lam, Vv)
 
 
 def local_problem(Y, d, r):
@@ -218,6 +229,24 @@ def problems(g, x, obs, sigma_h, sigma_v, cols=None):
         for o in np.nonzero((r != 0.0).any(axis=(0, 1)))[0]:      # ascending; r == 0 adds an exact zero
             C += r[:, :, o, None, None] * (Y[o][:, None] * Y[o][None, :])
             b += r[:, :, o, None] * (Y[o] * d[o])
+    return C, b
+
+
+def local_problems(g, x, obs, sigma_h, sigma_v, cols):
+    """`problems` column by column: each column adds only the observations with r != 0 at one of its levels, in ascending order.
+    The ones it leaves out add an exact zero in `problems`, so the bits are the same; the cost goes with the observations in range
+    of a column, not with all of them"""
+    cols = np.asarray(cols)
+    E, kx, nc, n = x["ps"].shape[0], g.kx, len(cols), len(obs["var"])
+    C, b = np.zeros((nc, kx, E, E)), np.zeros((nc, kx, E))
+    if n:
+        _, _, Y, d = obs_space(g, x, obs)
+        r = weights(g, obs, cols, sigma_h, sigma_v) * (1.0 / (obs["error"] * obs["error"]))[None, None, :]
+        YY, Yd = Y[:, :, None] * Y[:, None, :], Y * d[:, None]
+        for c in range(nc):
+            for o in np.nonzero((r[c] != 0.0).any(axis=0))[0]:
+                C[c] += r[c, :, o, None, None] * YY[o]
+                b[c] += r[c, :, o, None] * Yd[o]
     return C, b
 
 
@@ -330,9 +359,119 @@ def columns_for(g, obs, sigma_h, most=48, outside=16, seed=11):
     return np.concatenate([inside, rng.choice(out, min(outside, len(out)), False)]).astype(np.int64)
 
 
+def edge_columns(g):
+    """every column of rows 0, 1, il-2, il-1 and of longitudes 0 and ix-1, ascending: where the column unit vectors, the latitude
+    table and the periodic wrap meet"""
+    jj, ii = np.divmod(np.arange(g.ix * g.il), g.ix)
+    return np.nonzero(np.isin(jj, (0, 1, g.il - 2, g.il - 1)) | np.isin(ii, (0, g.ix - 1)))[0]
+
+
+def pad_obs(g, x, n, centre, err_factor=0.125, seed=13):
+    """n observations within 1 degree (great circle) of centre, variables and levels cycling, values and errors as `observe` gives"""
+    rng = np.random.default_rng(seed)
+    lat = centre[1] + rng.uniform(-0.7, 0.7, n)
+    lon = centre[0] + rng.uniform(-0.7, 0.7, n) / np.cos(np.radians(centre[1]))
+    return observe(g, x, [o % 5 for o in range(n)], [(3 * o) % g.kx for o in range(n)], lon, lat, err_factor, seed)
+
+
+PATTERNS = ("front1", "front255", "front256", "alternate", "wave3", "hole")
+
+
+def interleave(real, pad, pattern, total=None):
+    """-> (the set, the places of real's observations in it): `real` in its order with observations of `pad`, taken in theirs,
+    inserted -- front1, front255, front256: so many in front (256: the kernel's first chunk has no survivor); alternate: one
+    before every real one; wave3: in every chunk of 256, 192 of pad and then 64 real ones (survivors in the chunk's last wave
+    only); hole: 256 real ones, a whole chunk of pad, the other real ones.  `total`: pad appended at the end up to that size"""
+    nr = len(real["var"])
+    if pattern in ("front1", "front255", "front256"):
+        places = int(pattern[5:]) + np.arange(nr)
+    elif pattern == "alternate":
+        places = 2 * np.arange(nr) + 1
+    elif pattern == "wave3":
+        places = (np.arange(nr) // 64) * CHUNK + 192 + np.arange(nr) % 64
+    elif pattern == "hole":
+        places = np.arange(nr) + np.where(np.arange(nr) < CHUNK, 0, CHUNK)
+    else:
+        raise ValueError(pattern)
+    n = max(int(places[-1]) + 1, total or 0)
+    assert total is None or n == total, (pattern, n, total)
+    isreal = np.zeros(n, bool)
+    isreal[places] = True
+    assert n - nr <= len(pad["var"]), (pattern, n - nr)
+    out = {}
+    for k in real:
+        out[k] = np.zeros(n, real[k].dtype)
+        out[k][places] = real[k]
+        out[k][~isreal] = pad[k][:n - nr]
+    return out, places
+
+
 # ------------------------------------------------------------------------------------------------ what the GPU tests share
 SIGMA_H, RHO = 5.0e5, 1.1
 C_H = SIGMA_H * np.sqrt(10.0 / 3.0)
+WRAP, CLUSTER, PAD_CENTRE, HARD_CENTRE = (359.5, 0.0), (100.0, 20.0), (280.0, -60.0), (30, 15)
+
+
+EDGE_SIGMA_H = 3.0e5      # of the edge-column tests: at 5e5 edge_obs alone leaves no column of longitudes 0 and ix-1 out of range
+
+
+def in_range(g, obs, cols=None, sigma_h=SIGMA_H):
+    """(ncols, nobs): the observation has a non-zero horizontal weight at the column"""
+    pc = g.colunit if cols is None else g.colunit[cols]
+    return gc(distance(pc, unit(obs["lon"], obs["lat"])) / (sigma_h * np.sqrt(10.0 / 3.0))) != 0.0
+
+
+def edge_inputs(g, x):
+    """the observations of the edge-column tests as (name, set): edge_obs; 200 within 2 degrees of WRAP, between columns ix-1 and
+    0 on the equator; 200 within 1.5 degrees of latitude +88 at longitudes all around the circle; the same at -88"""
+    sets = [("edge", edge_obs(g, x)), ("wrap", clustered_obs(g, x, n=200, centre=WRAP, half_width=2.0 / np.sqrt(2.0), seed=21))]
+    for name, lat, seed in (("north", 88.0, 22), ("south", -88.0, 23)):
+        rng = np.random.default_rng(seed)
+        sets.append((name, observe(g, x, rng.integers(0, 5, 200), rng.integers(0, g.kx, 200), rng.uniform(0.0, 360.0, 200),
+                                   lat + rng.uniform(-1.5, 1.5, 200), 0.125, seed)))
+    return sets
+
+
+def edge_conditions(g, sets):
+    """what the edge-column tests need of their inputs at sigma_h = EDGE_SIGMA_H, asserted: at least 90 % of the columns of rows 0
+    and il-1 in range of 50 observations or more, columns of i = 0 and of i = ix-1 in range of the wrap cluster, edge columns out
+    of range of everything; -> (the observations, edge_columns, which of those are out of range of everything)"""
+    obs, cols = concat(*[s for _, s in sets]), edge_columns(g)
+    jj, ii = np.divmod(cols, g.ix)
+    near = in_range(g, obs, cols, EDGE_SIGMA_H)
+    polar = np.isin(jj, (0, g.il - 1))
+    assert polar.sum() == 2 * g.ix and (near[polar].sum(axis=1) >= 50).sum() >= 0.9 * polar.sum()
+    wrap = in_range(g, dict(sets)["wrap"], cols, EDGE_SIGMA_H).any(axis=1)
+    assert (wrap & (ii == 0)).any() and (wrap & (ii == g.ix - 1)).any()
+    out = ~near.any(axis=1)
+    assert out.sum() >= 8, out.sum()
+    return obs, cols, out
+
+
+def padded_inputs(g, x):
+    """the padded-scan tests' sets -> (real, pad): real is a cluster of 320 around CLUSTER and the sparse set's observations farther
+    than 4 c_h from PAD_CENTRE (at least 40 of its 60), pad is 1 200 observations within a degree of PAD_CENTRE"""
+    sparse = sparse_obs(g, x)
+    keep = distance(unit([PAD_CENTRE[0]], [PAD_CENTRE[1]]), unit(sparse["lon"], sparse["lat"]))[0] > 4.0 * C_H
+    assert keep.sum() >= 40, keep.sum()
+    real = concat(clustered_obs(g, x, n=320, centre=CLUSTER), {k: v[keep] for k, v in sparse.items()})
+    return real, pad_obs(g, x, 1200, PAD_CENTRE)
+
+
+def padded_conditions(g, real, pad, least=4300):
+    """-> (far, acted): the columns farther than 2 c_h (1 + 1e-12) from every pad observation -- at least `least`, every column in
+    range of real's cluster among them -- and the columns in range of a pad observation"""
+    far = distance(g.colunit, unit(pad["lon"], pad["lat"])).min(axis=1) > 2.0 * C_H * (1.0 + 1e-12)
+    cluster = in_range(g, {k: v[:320] for k, v in real.items()}).any(axis=1)
+    assert far.sum() >= least and cluster.sum() >= 64 and far[cluster].all(), (far.sum(), cluster.sum())
+    return far, in_range(g, pad).any(axis=1)
+
+
+def hard_obs(g, x, err_factor):
+    """16 observations of cycling variables within a degree of the grid point HARD_CENTRE, errors err_factor x SCALE's spread: C of
+    rank 16 among E = 31 or 32 members, far above the diagonal (E-1)/rho"""
+    i, j = HARD_CENTRE
+    return pad_obs(g, x, 16, (float(g.lon[i]), float(g.lat[j])), err_factor, seed=17)
 
 
 def make(sp, E, obs, sigma_v=0.0, rho=RHO, sigma_h=SIGMA_H):
@@ -351,13 +490,26 @@ def analyse_grid(sp, lt, x):
     return {v: a.cpu().numpy() for v, a in zip(VARS, out)}
 
 
-def limits(g, x, C, b, rho, cols, E):
+def limits(g, x, C, b, rho, cols, E, sample=None):
     """per variable max(16 x the difference of the restatement's two routes on these inputs, 64 E eps max|x - mean|), the eigh
-    route's increments and the largest condition number"""
+    route's increments and the largest condition number.  `sample` (places in cols): the Jacobi route, the costly one, runs at
+    those columns only; a largest difference over fewer columns is no larger, so the limit is the same or stricter"""
+    cols = np.asarray(cols)
     a, kappa = increments(g, x, C, b, rho, "eigh", cols)
-    j, _ = increments(g, x, C, b, rho, "jacobi", cols)
+    at = np.arange(len(cols)) if sample is None else np.asarray(sample)
+    j, _ = increments(g, x, C[at], b[at], rho, "jacobi", cols[at])
     sc = perturbation_scale(x)
-    return {v: max(16 * float(np.max(np.abs(a[v] - j[v]))), 64 * E * EPS * sc[v]) for v in VARS}, a, kappa
+    return {v: max(16 * float(np.max(np.abs(a[v][..., at] - j[v]))), 64 * E * EPS * sc[v]) for v in VARS}, a, kappa
+
+
+def hardest(C, rho, n):
+    """places of n columns for `limits`' sample: the n/2 whose A = (E-1)/rho I + C has the largest condition number at some level,
+    and as many spread evenly over the rest"""
+    E = C.shape[-1]
+    lam = np.linalg.eigvalsh(C + ((E - 1) / rho) * np.eye(E))
+    order = np.argsort((lam[..., -1] / lam[..., 0]).max(axis=1))
+    rest = order[:len(order) - n // 2]
+    return np.unique(np.concatenate([order[len(order) - n // 2:], rest[::max(1, len(rest) // (n - n // 2))]]))
 
 
 def oracle_grids(o, sts):

@@ -108,13 +108,14 @@ def test_coarse_columns_bit_equal(E, plans):
 
 # ---------------------------------------------------------------------------------------------------- 2. against the restatement
 @pytest.mark.parametrize("sigma_v", [0.0, 0.1])
-@pytest.mark.parametrize("E", [2, 3, 17, 32])
+@pytest.mark.parametrize("E", [2, 3, 8, 16, 17, 32])
 def test_against_the_restatement(E, sigma_v, plans):
     """rho = 1.1, strides (2, 2), (3, 5) and (4, 47); grid columns of every stencil class -- interior, on a coarse row only, on a
     coarse longitude only, in the last longitude cell (i1 wraps to 0), in the short last latitude interval, j = 0, j = il-1 -- in
     range of a cluster and out of it.  field("weights") at the coarse columns those stencils read: within max(16 x the difference of
     the restatement's two eigen routes in T, 64 E eps max|T|).  The increments of each variable: within max(16 x the difference of
-    the restatement's two routes, 64 E eps max|x - mean|)."""
+    the restatement's two routes, 64 E eps max|x - mean|).  E = 2, 3 | 8 | 16 | 17, 32: an item of letkf_apply_kernel has 2, 4 | 8 |
+    16 | 32 lanes."""
     sp, g = plans()
     x, obs, per, union, T = reference(g, E, sigma_v)
     sc = lk.perturbation_scale(x)
@@ -212,6 +213,39 @@ def test_appended_observations_and_two_runs(plans):
         assert a.any() and support.same_bits(a, b), v
         a, b = (np.ascontiguousarray(lk.at_columns(r[v], [col])) for r in (full_base, full_both))
         assert not support.same_bits(a, b), v
+
+
+@pytest.mark.parametrize("pattern", ["front255", "wave3", "hole"])
+def test_padded_scans(pattern, plans):
+    """E = 17, stride (2, 2), rho = 1.1, sigma_v = 0.1: the padded sets of tests/test_gpu_letkf.py::test_padded_scans (255 pad
+    observations in front; 192 in front of every 64 real ones; a whole chunk between two chunks of real ones).  Every grid column
+    whose stencil reads only coarse columns farther than 2 c_h (1 + 1e-12) from the pad keeps the bits of the unpadded run, in all
+    five variables at every level, and so do the transforms of those coarse columns; the columns in range of the cluster are among
+    them, and there are at least 4 300.  Where a stencil reads a coarse column in range of the pad the increments differ."""
+    sp, g = plans()
+    E = 17
+    x = lk.ensemble(g, E, seed=90 + E)
+    real, pad = lk.padded_inputs(g, x)
+    far, acted = lk.padded_conditions(g, real, pad)
+    lt = lk.make(sp, E, lk.concat(real, pad), 0.1)
+    lt.set_obs(*lk.args(real))
+    first = run_at(sp, lt, x, 2, 2)
+    W = lt.field("weights").numpy().copy()
+    coarse, idx = lt.table("coarse_columns"), lt.table("interp_index")
+    reads = coarse[idx]                                  # (ncol, 4) grid columns a stencil reads: an entry of weight zero repeats one that is read
+    keep, changed = np.nonzero(far[reads].all(axis=1))[0], np.nonzero(acted[reads].any(axis=1))[0]
+    cluster = lk.in_range(g, {k: v[:320] for k, v in real.items()}).any(axis=1)
+    assert len(keep) >= 4300 and np.isin(np.nonzero(cluster)[0], keep).all() and len(changed) >= 20, (len(keep), len(changed))
+    obs, at = lk.interleave(real, pad, pattern)
+    lt.set_obs(*lk.args(obs))
+    got = lk.analyse_grid(sp, lt, x)
+    assert support.same_bits(np.ascontiguousarray(lt.field("weights").numpy()[far[coarse]]), np.ascontiguousarray(W[far[coarse]]))
+    for v in lk.VARS:
+        a, b = (np.ascontiguousarray(lk.at_columns(r[v], keep)) for r in (got, first))
+        assert b.any() and support.same_bits(a, b), (pattern, v)
+    assert any(not np.array_equal(lk.at_columns(got[v], changed), lk.at_columns(first[v], changed)) for v in lk.VARS), pattern
+    print("[letkf interp padded %s] %d observations: %d columns bit-equal, %d differ" % (pattern, len(obs["var"]), len(keep), len(changed)))
+    lt.close()
 
 
 # ---------------------------------------------------------------------------------------------------- 4. the state
