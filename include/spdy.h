@@ -536,6 +536,56 @@ int spdy_ens_output_batch_dev(spdy_plan *plan, int nmem, const double *vor, cons
                               const spdy_output_fields *members, const spdy_output_fields *mean,
                               const spdy_output_fields *spread);
 
+/* ---- pressure-level output: every member's fields on pressure surfaces, their ensemble mean and spread ------
+ * The fields people read and verify are on pressure surfaces; the reference's post-processing (scripts/sigma_to_pressure.py) runs,
+ * per column of a snapshot, np.interp(p_levels, ps/100 * sigma, field).  This is that product from the device-resident ensemble in
+ * one capturable call, and the mean and spread ON the pressure levels -- which are not the interpolation of the sigma-level mean
+ * and spread: each member has its own surface pressure and so its own bracket.
+ * Inputs: those of spdy_ens_output_batch_dev (time level 1 of nmem members, phi, ps, d_use), and
+ *     nlev   the number of pressure levels, 1 <= nlev <= SPDY_MAX_PLEV
+ *     plev   nlev pressures in Pa on the HOST, each finite and > 0, in any order; read when the call is enqueued (a captured call
+ *            keeps its values)
+ *     coord  SPDY_PLEV_LINEAR_P: linear in p, the reference script's choice; SPDY_PLEV_LOG_P: linear in ln p
+ * Per member e, grid point and quantity x -- u, v, t, q * (double)1.0e-3f, phi / grav: the FP64 values x_e[k] the ensemble output
+ * forms before its float rounding, on the full levels k = 0 .. kx-1 (fsg ascending) -- the coordinate of the model levels and of
+ * the target is
+ *     linear   X_k = ((double)1.e+5f * exp(ps_e)) * fsg[k]      x = plev[l]
+ *     log      X_k = ps_e + ln fsg[k]                           x = ln(plev[l] / (double)1.e+5f)      (logarithms formed on the host)
+ * and the value on the level follows np.interp:
+ *     x <= X_0        x_e[0]      (that level's bits, not an arithmetic result)
+ *     x >= X_{kx-1}   x_e[kx-1]   (likewise)
+ *     otherwise       the k with X_k <= x < X_{k+1}:  w = (x - X_k) / (X_{k+1} - X_k),  y_e = x_e[k] + w * (x_e[k+1] - x_e[k])
+ * each operation rounded once, without contraction; kx = 1: every level gets x_e[0].  A member whose ps_e is not finite gets NaN on
+ * every level (no loop bound and no address depends on ps_e).
+ * Outputs, float, the three optional groups of the ensemble output: the fields of `members` u .. phi (ix,il,nlev,nmem), its ps
+ * (ix,il,nmem); of `mean` and `spread` u .. phi (ix,il,nlev), ps (ix,il).  Mean and spread are formed over the members in use from
+ * the y_e in FP64 exactly as the ensemble output forms them from x_e: two passes, ascending member order, a select and never a
+ * multiplication for a member not in use, n = 1 gives +0, n = 0 NaN.  The three ps fields are the surface pressure, with the bits
+ * of spdy_ens_output_batch_dev's.  `below` (ix,il,nlev), float, or NULL = not wanted: the number of members in use for which
+ * x > X_{kx-1} -- the level lies below that member's lowest model level and its value there is the clamped one: what a user masks
+ * with.  All output pointers 8-byte aligned.
+ * spdy_ens_output_pressure_dev: the ensemble output's inverse batch into its workspace, then ONE kernel; capturable after
+ * spdy_ens_output_workspace(plan, nmem).  spdy_ens_output_pressure_grid_dev: that kernel alone on the caller's device array `grid`
+ * of (5 kx + 1) nmem FP64 grids in the workspace's layout -- u | v | t | q | phi with nmem*kx grids each, member-major, then ps with
+ * nmem grids -- holding the model's raw values as the inverse batch leaves them (q in g/kg, phi in m2/s2, ps as log(p/p0)); 16-byte
+ * aligned; no max_batch check (it runs no transform).  spdy_output_pressure_dev: the single state, which is the one-member case of
+ * the ensemble call with the `members` group only (as every single-state step call is the one-member case of its ensemble call).
+ * Checks, in this order: a NULL plan, nmem < 1, max_batch < nmem*(3*kx+1) SPDY_ERR_ARG; nlev outside [1, SPDY_MAX_PLEV], a NULL
+ * plev, a level that is not finite or not > 0, an unknown coord SPDY_ERR_ARG; no sigma levels SPDY_ERR_STATE; a NULL required
+ * pointer, no output group, an output pointer not 8-byte aligned SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last.  A
+ * failing call enqueues nothing and sets the text of spdy_last_error.                                                            */
+enum { SPDY_MAX_PLEV = 32, SPDY_PLEV_LINEAR_P = 0, SPDY_PLEV_LOG_P = 1 };
+int spdy_ens_output_pressure_dev(spdy_plan *plan, int nmem, const double *vor, const double *div, const double *t,
+                                 const double *q, const double *phi, const double *ps, const int *d_use, int nlev,
+                                 const double *plev, int coord, const spdy_output_fields *members,
+                                 const spdy_output_fields *mean, const spdy_output_fields *spread, float *below);
+int spdy_ens_output_pressure_grid_dev(spdy_plan *plan, int nmem, const double *grid, const int *d_use, int nlev,
+                                      const double *plev, int coord, const spdy_output_fields *members,
+                                      const spdy_output_fields *mean, const spdy_output_fields *spread, float *below);
+int spdy_output_pressure_dev(spdy_plan *plan, const double *vor, const double *div, const double *t, const double *q,
+                             const double *phi, const double *ps, int nlev, const double *plev, int coord, float *u_out,
+                             float *v_out, float *t_out, float *q_out, float *phi_out, float *ps_out);
+
 /* Column physics (spdy_moist_columns_dev, spdy_moist_physics_dev, spdy_radiation_down_dev, spdy_radiation_up_dev,
  * spdy_surface_fluxes_dev, spdy_pbl_dev, spdy_column_physics_dev, spdy_physics_dev) checks its arguments in one order, and the first check that
  * fails gives the code: a NULL plan, kx outside [5, 16] and nb outside [0, max_batch] SPDY_ERR_ARG; no sigma levels, then

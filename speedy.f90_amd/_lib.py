@@ -115,6 +115,9 @@ SIGNATURES = {
     "spdy_output_batch_dev": [c_void_p] * 13,
     "spdy_ens_output_workspace": [c_void_p, c_int],
     "spdy_ens_output_batch_dev": [c_void_p, c_int] + [c_void_p] * 10,
+    "spdy_ens_output_pressure_dev": [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_void_p, c_int] + [c_void_p] * 4,
+    "spdy_ens_output_pressure_grid_dev": [c_void_p, c_int] + [c_void_p] * 2 + [c_int, c_void_p, c_int] + [c_void_p] * 4,
+    "spdy_output_pressure_dev": [c_void_p] * 7 + [c_int, c_void_p, c_int] + [c_void_p] * 6,
     "spdy_moist_columns_dev": [c_void_p, c_int] + [c_void_p] * 7,
     "spdy_moist_workspace": [c_void_p],
     "spdy_moist_physics_dev": [c_void_p] * 8,

@@ -4,6 +4,7 @@
 // the single-state call and its ensemble form are one argument check (step_args) and one call of it, with nmem = 1 or nmem.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -109,6 +110,70 @@ int ens_output_members(const spdy_plan *p, int nmem)
     if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_output: nmem=%d < 1", nmem);
     const long need = (long)nmem * (3 * p->tab.kx + 1);
     if (p->max_batch < need) return fail(SPDY_ERR_ARG, "ens_output: max_batch=%d must be >= nmem*(3*kx+1)=%ld", p->max_batch, need);
+    return SPDY_OK;
+}
+
+// the output groups of the ensemble output calls into a kernel's pointer tables: at least one, and in a given one all six fields,
+// 8-byte aligned (a pair of floats per store)
+int ens_output_groups(const spdy_output_fields *members, const spdy_output_fields *mean, const spdy_output_fields *spread, float **dm,
+                      float **da, float **ds)
+{
+    if (!members && !mean && !spread) return fail(SPDY_ERR_ARG, "ens_output: no output group (members, mean, spread all NULL)");
+    const spdy_output_fields *grp[3] = {members, mean, spread};
+    float **dst[3] = {dm, da, ds};
+    for (int g = 0; g < 3; ++g) {
+        if (!grp[g]) continue;
+        float *f[6] = {grp[g]->u, grp[g]->v, grp[g]->t, grp[g]->q, grp[g]->phi, grp[g]->ps};
+        for (int i = 0; i < 6; ++i) {
+            if (!f[i]) return fail(SPDY_ERR_ARG, "null device pointer");
+            if (reinterpret_cast<uintptr_t>(f[i]) % 8) return fail(SPDY_ERR_ARG, "ens_output: output fields must be 8-byte aligned");
+            dst[g][i] = f[i];
+        }
+    }
+    return SPDY_OK;
+}
+
+// What the two ensemble output calls share in front of their epilogue kernel: the workspace (the device is checked here, last), then
+// time level 1 of all members to the grid as ONE inverse batch, read in place: nmem*kx pairs, the segments t | q | phi | ps, into
+// ens_out_grid as u | v | t | q | phi (nmem*kx grids each) | ps (nmem)
+int ens_output_inverse(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q, const double *phi,
+                       const double *ps)
+{
+    RC(spdy_ens_output_workspace(p, nmem));
+    const int nk = nmem * p->tab.kx;
+    const size_t L = (size_t)nk * grid_elems(p);
+    double *ug = p->ens_out_grid.g, *vg = ug + L, *tg = ug + 2 * L;
+    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{nk, t}, {nk, q}, {nk, phi}, {nmem, ps}};
+    return spdy_inverse_batch_segs_dev(p, nk, vor, div, ug, vg, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, tg, 0, nullptr, nullptr, nullptr, 2);
+}
+
+// the pressure-level calls' own checks, in the header's order, and what they give the kernel: the targets (the logarithms of the
+// log-p coordinate are formed here, on the host: the values a captured call keeps) and the plan's level table
+int plev_levels(const spdy_plan *p, int nlev, const double *plev, int coord, spdy::PlevOutput *c)
+{
+    const double p0 = static_cast<double>(1.e+5f);
+    if (nlev < 1 || nlev > SPDY_MAX_PLEV) return fail(SPDY_ERR_ARG, "ens_output_pressure: nlev=%d outside [1, %d]", nlev, (int)SPDY_MAX_PLEV);
+    if (!plev) return fail(SPDY_ERR_ARG, "ens_output_pressure: null plev");
+    for (int l = 0; l < nlev; ++l)
+        if (!std::isfinite(plev[l]) || !(plev[l] > 0.0))
+            return fail(SPDY_ERR_ARG, "ens_output_pressure: plev[%d]=%g must be finite and > 0", l, plev[l]);
+    if (coord != SPDY_PLEV_LINEAR_P && coord != SPDY_PLEV_LOG_P) return fail(SPDY_ERR_ARG, "ens_output_pressure: unknown coord=%d", coord);
+    if (!p->tab.sigma_ready) return fail(SPDY_ERR_STATE, "ens_output_pressure needs sigma levels");
+    const bool log_p = coord == SPDY_PLEV_LOG_P;
+    c->nlev = nlev; c->log_p = log_p ? 1 : 0;
+    c->qfac = static_cast<double>(1.0e-3f); c->grav = p->tab.grav; c->p0 = p0;
+    c->lv.kx = p->tab.kx;
+    for (int k = 0; k < p->tab.kx; ++k) c->lv.lev[k] = log_p ? std::log(p->tab.fsg[k]) : p->tab.fsg[k];
+    for (int l = 0; l < nlev; ++l) c->x[l] = log_p ? std::log(plev[l] / p0) : plev[l];
+    return SPDY_OK;
+}
+
+int plev_outputs(const spdy_output_fields *members, const spdy_output_fields *mean, const spdy_output_fields *spread, float *below,
+                 spdy::PlevOutput *c)
+{
+    RC(ens_output_groups(members, mean, spread, c->members, c->mean, c->spread));
+    if (reinterpret_cast<uintptr_t>(below) % 8) return fail(SPDY_ERR_ARG, "ens_output: output fields must be 8-byte aligned");
+    c->below = below;
     return SPDY_OK;
 }
 }  // namespace
@@ -458,33 +523,60 @@ int spdy_ens_output_batch_dev(spdy_plan *p, int nmem, const double *vor, const d
 {
     RC(ens_output_members(p, nmem));
     if (!vor || !div || !t || !q || !phi || !ps) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (!members && !mean && !spread) return fail(SPDY_ERR_ARG, "ens_output: no output group (members, mean, spread all NULL)");
     spdy::EnsOutput c{};
-    const spdy_output_fields *grp[3] = {members, mean, spread};
-    float **dst[3] = {c.members, c.mean, c.spread};
-    for (int g = 0; g < 3; ++g) {
-        if (!grp[g]) continue;
-        float *f[6] = {grp[g]->u, grp[g]->v, grp[g]->t, grp[g]->q, grp[g]->phi, grp[g]->ps};
-        for (int i = 0; i < 6; ++i) {
-            if (!f[i]) return fail(SPDY_ERR_ARG, "null device pointer");
-            if (reinterpret_cast<uintptr_t>(f[i]) % 8) return fail(SPDY_ERR_ARG, "ens_output: output fields must be 8-byte aligned");
-            dst[g][i] = f[i];
-        }
-    }
-    RC(spdy_ens_output_workspace(p, nmem));
-    // time level 1 of all members to the grid as ONE inverse batch, read in place: nmem*kx pairs, the segments t | q | phi | ps
-    const int kx = p->tab.kx, nk = nmem * kx;
-    const size_t L = (size_t)nk * grid_elems(p);
-    double *ug = p->ens_out_grid.g, *vg = ug + L, *tg = ug + 2 * L;
-    const spdy_spec_seg segs[SPDY_MAX_SPEC_SEGS] = {{nk, t}, {nk, q}, {nk, phi}, {nmem, ps}};
-    RC(spdy_inverse_batch_segs_dev(p, nk, vor, div, ug, vg, 2, SPDY_MAX_SPEC_SEGS, segs, nullptr, 1, tg, 0, nullptr, nullptr, nullptr, 2));
+    RC(ens_output_groups(members, mean, spread, c.members, c.mean, c.spread));
+    RC(ens_output_inverse(p, nmem, vor, div, t, q, phi, ps));
     // input_output.f90:200-206, as spdy_output_batch_dev: u, v, t as they are; q*1.0e-3; phi/grav; p0*exp(ps) -- then real(., sp)
     const int kind[6] = {0, 0, 0, 1, 2, 3};
     const double fac[6] = {1.0, 1.0, 1.0, static_cast<double>(1.0e-3f), p->tab.grav, static_cast<double>(1.e+5f)};
     for (int i = 0; i < 6; ++i) { c.kind[i] = kind[i]; c.factor[i] = fac[i]; }
-    c.nmem = nmem; c.kx = kx; c.src = ug; c.use = d_use;
+    c.nmem = nmem; c.kx = p->tab.kx; c.src = p->ens_out_grid.g; c.use = d_use;
     KERNEL(spdy::launch_ens_output(p->dev, c, p->stream));
     return SPDY_OK;
+}
+
+/* ---------------------------------------------------------------- pressure-level output (include/spdy.h, "pressure-level output") */
+int spdy_ens_output_pressure_grid_dev(spdy_plan *p, int nmem, const double *grid, const int *d_use, int nlev, const double *plev, int coord,
+                                      const spdy_output_fields *members, const spdy_output_fields *mean,
+                                      const spdy_output_fields *spread, float *below)
+{
+    NEED_PLAN(p);
+    if (nmem < 1) return fail(SPDY_ERR_ARG, "ens_output_pressure: nmem=%d < 1", nmem);
+    spdy::PlevOutput c{};
+    RC(plev_levels(p, nlev, plev, coord, &c));
+    if (!grid) return fail(SPDY_ERR_ARG, "null device pointer");
+    if (reinterpret_cast<uintptr_t>(grid) % 16) return fail(SPDY_ERR_ARG, "ens_output_pressure: the grids must be 16-byte aligned");
+    RC(plev_outputs(members, mean, spread, below, &c));
+    NEED_DEVICE(p);
+    c.nmem = nmem; c.src = grid; c.use = d_use;
+    KERNEL(spdy::launch_plev_output(p->dev, c, p->stream));
+    return SPDY_OK;
+}
+
+int spdy_ens_output_pressure_dev(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q,
+                                 const double *phi, const double *ps, const int *d_use, int nlev, const double *plev, int coord,
+                                 const spdy_output_fields *members, const spdy_output_fields *mean, const spdy_output_fields *spread,
+                                 float *below)
+{
+    RC(ens_output_members(p, nmem));
+    spdy::PlevOutput c{};
+    RC(plev_levels(p, nlev, plev, coord, &c));
+    if (!vor || !div || !t || !q || !phi || !ps) return fail(SPDY_ERR_ARG, "null device pointer");
+    RC(plev_outputs(members, mean, spread, below, &c));
+    RC(ens_output_inverse(p, nmem, vor, div, t, q, phi, ps));
+    c.nmem = nmem; c.src = p->ens_out_grid.g; c.use = d_use;
+    KERNEL(spdy::launch_plev_output(p->dev, c, p->stream));
+    return SPDY_OK;
+}
+
+// The single state: the one-member case of the ensemble call with the `members` group only, as every single-state call of the
+// step is the one-member case of its ensemble form.
+int spdy_output_pressure_dev(spdy_plan *p, const double *vor, const double *div, const double *t, const double *q, const double *phi,
+                             const double *ps, int nlev, const double *plev, int coord, float *u_out, float *v_out, float *t_out,
+                             float *q_out, float *phi_out, float *ps_out)
+{
+    const spdy_output_fields one{u_out, v_out, t_out, q_out, phi_out, ps_out};
+    return spdy_ens_output_pressure_dev(p, 1, vor, div, t, q, phi, ps, nullptr, nlev, plev, coord, &one, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

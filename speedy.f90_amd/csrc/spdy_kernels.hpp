@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "spdy_vinterp.hpp"
+
 namespace spdy {
 
 // Launch-policy switches of a plan (host-side use: which kernel form a launcher picks; none changes results beyond the
@@ -291,6 +293,21 @@ struct EnsOutput {
     float *members[6], *mean[6], *spread[6];
 };
 hipError_t launch_ens_output(const DevPlan &p, const EnsOutput &c, hipStream_t s);
+// Pressure-level output: EnsOutput's values interpolated in the vertical to nlev targets per member, and the mean and the spread of
+// the interpolated values.  src, use: as EnsOutput's.  lv: fsg (log_p 0) or ln fsg (log_p 1); x[l]: the target, plev[l] in Pa or
+// ln(plev[l] / p0).  qfac, grav, p0: the factors of q, phi and ps.  members[i]: (ix,il,nlev,nmem) float, ps (ix,il,nmem); mean[i],
+// spread[i]: (ix,il,nlev), ps (ix,il); below: null or (ix,il,nlev), the members in use whose lowest level lies above the target.
+constexpr int PLEV_MAX_LEVELS = 32;       // SPDY_MAX_PLEV (include/spdy.h)
+struct PlevOutput {
+    int nmem, nlev, log_p;
+    double qfac, grav, p0;
+    VLevels lv;
+    double x[PLEV_MAX_LEVELS];
+    const double *src;
+    const int *use;
+    float *members[6], *mean[6], *spread[6], *below;
+};
+hipError_t launch_plev_output(const DevPlan &p, const PlevOutput &c, hipStream_t s);
 // once per device, before the first launch: raises the dynamic-LDS limit of every kernel that needs > 64 KB
 hipError_t prepare_device_kernels();
 hipError_t prepare_device_step_kernels(int kx);

@@ -1050,4 +1050,199 @@ hipError_t launch_ens_output(const DevPlan &p, const EnsOutput &c, hipStream_t s
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Pressure-level output (include/spdy.h, "pressure-level output"): ens_output_kernel's values x_e[k], interpolated
+// in the vertical to nlev caller-given pressures per member (spdy_vinterp.hpp), and the mean and the spread of the INTERPOLATED
+// values.  One thread owns one pair of adjacent grid points and one target level (blockIdx.y) and walks the members in ascending
+// order, PLEV_CHUNK at a time: the chunk's surface pressures are loaded first and give, per member and point, ONE bracket and
+// weight for all five quantities; then the two levels the bracket names are loaded by address, for all five quantities of the
+// whole chunk (40 loads) before the first is used (a T30 launch has less than a wave per SIMD: the latencies must overlap inside
+// the thread; neighbouring points nearly always share a bracket: the loads stay coalesced).  No column is held in registers, no
+// array is indexed by the bracket.  exp's constants fill the scalar registers in the member loop of the linear coordinate: what is
+// wave-uniform and need not be scalar is kept in vector registers, so that nothing is spilled (resources).
+// The statistics are ens_output_kernel's: two passes, the second recomputing
+// bracket and value from the same bits (nmem is not bounded, nothing is kept per member), a select for a member not in use, n = 1
+// spread +0, n = 0 NaN, no atomics, no cross-thread reduction.  A member whose ps is not finite gets NaN on every level by a
+// select after the interpolation: its bracket stays inside the column whatever ps holds.  The row blockIdx.y == nlev writes the
+// three surface-pressure fields by ens_output_kernel's expressions, in its order: the same bits.
+// ------------------------------------------------------------------------------------------
+constexpr int PLEV_CHUNK = 2;
+
+// the launch's wave-uniform doubles, held in vector registers (plev_output_kernel): the target and the factors of ps, q and phi
+struct PlevScalars { double x, p0, qfac, grav; };
+
+// SECOND false: members' fields, sums s and counts; SECOND true: squared deviations from the finished means m into s
+template <bool WT, bool LOG, bool SECOND>
+__device__ __forceinline__ void plev_pass(const PlevOutput &c, int gsz, int l, long i, const PlevScalars &u, double (&s)[5][2],
+                                          const double (&m)[5][2], int &n, int (&nbelow)[2])
+{
+#pragma clang fp contract(off)
+    int nmem = c.nmem;
+    asm volatile("" : "+s"(nmem));       // opaque per pass: the strides are formed again, not kept in scalar registers across a pass
+    const int kx = c.lv.kx, nlev = c.nlev;
+    const long L = (long)nmem * kx * gsz, cstride = (long)kx * gsz;           // a quantity's stack; a member's column in it
+    const double *__restrict__ ps = c.src + 5 * L + i;
+    const int *__restrict__ use = c.use;
+    const bool wanted = c.members[0] != nullptr;                              // the group, and then all of its fields
+    _Pragma("nounroll") for (int e0 = 0; e0 < nmem; e0 += PLEV_CHUNK) {
+        double2 pv[PLEV_CHUNK];
+        UNROLL for (int j = 0; j < PLEV_CHUNK; ++j)
+            pv[j] = *reinterpret_cast<const double2 *>(ps + (long)min(e0 + j, nmem - 1) * gsz);
+        // one bracket and weight per member and point, for all five quantities
+        double a[2 * PLEV_CHUNK];
+        VBracket b[2 * PLEV_CHUNK];
+        UNROLL for (int j = 0; j < PLEV_CHUNK; ++j) {
+            a[2 * j] = LOG ? pv[j].x : u.p0 * exp(pv[j].x);
+            a[2 * j + 1] = LOG ? pv[j].y : u.p0 * exp(pv[j].y);
+        }
+        vinterp_brackets<LOG, 2 * PLEV_CHUNK>(c.lv, a, u.x, b);
+        int o0[2 * PLEV_CHUNK], o1[2 * PLEV_CHUNK];                           // the two levels' grids in a column, and the point
+        int in[PLEV_CHUNK];                                                   // (a flag in a vector register, as PlevScalars)
+        UNROLL for (int j = 0; j < PLEV_CHUNK; ++j) {
+            UNROLL for (int t = 0; t < 2; ++t) {
+                const int r = 2 * j + t;
+                b[r].cls |= isfinite(t ? pv[j].y : pv[j].x) ? 0 : VINTERP_NAN;
+                o0[r] = b[r].kb * gsz + t;
+                o1[r] = min(b[r].kb + 1, kx - 1) * gsz + t;
+            }
+            const int e = e0 + j;
+            in[j] = e < nmem && (!use || use[e] != 0) ? 1 : 0;
+            asm volatile("" : "+v"(in[j]));
+            if (!SECOND) {
+                n += in[j];
+                nbelow[0] += in[j] && (b[2 * j].cls & VINTERP_BELOW) ? 1 : 0;
+                nbelow[1] += in[j] && (b[2 * j + 1].cls & VINTERP_BELOW) ? 1 : 0;
+            }
+        }
+        // every load of the chunk before the first is used: 5 quantities x 2 levels x 2 points per member
+        double v[5][2 * PLEV_CHUNK][2];
+        UNROLL for (int q = 0; q < 5; ++q)
+            UNROLL for (int j = 0; j < PLEV_CHUNK; ++j) {
+                const double *__restrict__ col = c.src + q * L + (long)min(e0 + j, nmem - 1) * cstride + i;
+                UNROLL for (int t = 0; t < 2; ++t) {
+                    v[q][2 * j + t][0] = col[o0[2 * j + t]];
+                    v[q][2 * j + t][1] = col[o1[2 * j + t]];
+                }
+            }
+        UNROLL for (int q = 0; q < 5; ++q) {
+            const int kind = q == 3 ? 1 : (q == 4 ? 2 : 0);
+            const double f = q == 3 ? u.qfac : u.grav;
+            UNROLL for (int j = 0; j < PLEV_CHUNK; ++j) {
+                const int e = e0 + j;
+                double y[2];
+                UNROLL for (int t = 0; t < 2; ++t) {
+                    const double2 xv = ens_out_value(kind, f, make_double2(v[q][2 * j + t][0], v[q][2 * j + t][1]));   // x_e[kb], x_e[kb+1]
+                    y[t] = vinterp_value(b[2 * j + t], xv.x, xv.y);
+                }
+                if (!SECOND && e < nmem && wanted) ens_out_store<WT>(c.members[q] + ((long)e * nlev + l) * gsz + i, y[0], y[1]);
+                if (SECOND) {
+                    const double da = y[0] - m[q][0], db = y[1] - m[q][1];
+                    s[q][0] = in[j] ? s[q][0] + da * da : s[q][0]; s[q][1] = in[j] ? s[q][1] + db * db : s[q][1];
+                } else {
+                    s[q][0] = in[j] ? s[q][0] + y[0] : s[q][0]; s[q][1] = in[j] ? s[q][1] + y[1] : s[q][1];
+                }
+            }
+        }
+    }
+}
+
+// the surface-pressure row: ens_output_kernel's walk for the quantity ps (kind 3), operation for operation
+template <bool WT>
+__device__ __forceinline__ void plev_ps_row(const PlevOutput &c, int gsz, long i)
+{
+#pragma clang fp contract(off)
+    const int nmem = c.nmem;
+    const double *__restrict__ src = c.src + 5L * nmem * c.lv.kx * gsz + i;
+    const int *__restrict__ use = c.use;
+    float *mem = c.members[5], *mean_out = c.mean[5], *spread_out = c.spread[5];
+    double sa = 0.0, sb = 0.0;
+    int n = 0;
+    for (int e0 = 0; e0 < nmem; e0 += ENS_OUT_CHUNK) {
+        double2 v[ENS_OUT_CHUNK];
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j)
+            v[j] = *reinterpret_cast<const double2 *>(src + (long)min(e0 + j, nmem - 1) * gsz);
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j) {
+            const int e = e0 + j;
+            if (e < nmem) {
+                const double2 x = ens_out_value(3, c.p0, v[j]);
+                if (mem) ens_out_store<WT>(mem + i + (long)e * gsz, x.x, x.y);
+                if (!use || use[e] != 0) { sa = sa + x.x; sb = sb + x.y; ++n; }
+            }
+        }
+    }
+    if (!mean_out && !spread_out) return;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const double ma = n > 0 ? sa / (double)n : qnan, mb = n > 0 ? sb / (double)n : qnan;
+    if (mean_out) ens_out_store<WT>(mean_out + i, ma, mb);
+    if (!spread_out) return;
+    double qa = 0.0, qb = 0.0;
+    for (int e0 = 0; n > 1 && e0 < nmem; e0 += ENS_OUT_CHUNK) {
+        double2 v[ENS_OUT_CHUNK];
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j)
+            v[j] = *reinterpret_cast<const double2 *>(src + (long)min(e0 + j, nmem - 1) * gsz);
+        UNROLL for (int j = 0; j < ENS_OUT_CHUNK; ++j) {
+            const int e = e0 + j;
+            if (e < nmem && (!use || use[e] != 0)) {
+                const double2 x = ens_out_value(3, c.p0, v[j]);
+                const double da = x.x - ma, db = x.y - mb;
+                qa = qa + da * da; qb = qb + db * db;
+            }
+        }
+    }
+    const double m1 = (double)(n - 1);
+    ens_out_store<WT>(spread_out + i, n > 1 ? sqrt(qa / m1) : (n == 1 ? 0.0 : qnan), n > 1 ? sqrt(qb / m1) : (n == 1 ? 0.0 : qnan));
+}
+
+template <bool WT, bool LOG>
+__global__ __launch_bounds__(256) void plev_output_kernel(PlevOutput c, int gsz)
+{
+#pragma clang fp contract(off)
+    const int l = blockIdx.y;
+    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (i >= gsz || l > c.nlev) return;
+    if (l == c.nlev) { plev_ps_row<WT>(c, gsz, i); return; }
+    // (wave-uniform values in vector registers: exp's constants fill the scalar file in the member loop, and these would be spilled)
+    PlevScalars u{c.x[l], c.p0, c.qfac, c.grav};
+    asm volatile("" : "+v"(u.x), "+v"(u.p0), "+v"(u.qfac), "+v"(u.grav));
+    const long at = (long)l * gsz + i;
+    double s[5][2], m[5][2];
+    UNROLL for (int q = 0; q < 5; ++q) { s[q][0] = s[q][1] = 0.0; m[q][0] = m[q][1] = 0.0; }
+    int n = 0, nbelow[2] = {0, 0};
+    const bool stats = c.mean[0] || c.spread[0];
+    plev_pass<WT, LOG, false>(c, gsz, l, i, u, s, m, n, nbelow);
+    if (c.below) ens_out_store<WT>(c.below + at, (double)nbelow[0], (double)nbelow[1]);
+    if (!stats) return;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    UNROLL for (int q = 0; q < 5; ++q) {
+        m[q][0] = n > 0 ? s[q][0] / (double)n : qnan; m[q][1] = n > 0 ? s[q][1] / (double)n : qnan;
+        if (c.mean[q]) ens_out_store<WT>(c.mean[q] + at, m[q][0], m[q][1]);
+        s[q][0] = s[q][1] = 0.0;
+    }
+    if (!c.spread[0]) return;
+    if (n > 1) plev_pass<WT, LOG, true>(c, gsz, l, i, u, s, m, n, nbelow);
+    const double m1 = (double)(n - 1);
+    UNROLL for (int q = 0; q < 5; ++q)
+        ens_out_store<WT>(c.spread[q] + at, n > 1 ? sqrt(s[q][0] / m1) : (n == 1 ? 0.0 : qnan), n > 1 ? sqrt(s[q][1] / m1) : (n == 1 ? 0.0 : qnan));
+}
+
+hipError_t launch_plev_output(const DevPlan &p, const PlevOutput &c, hipStream_t s)
+{
+    const int gsz = p.ix * p.il;                                    // even
+    if (c.nmem < 1 || c.lv.kx < 1 || c.lv.kx > VINTERP_KMAX || c.nlev < 1 || c.nlev > PLEV_MAX_LEVELS || !c.src || gsz % 2)
+        return hipErrorInvalidValue;
+    const int groups = (c.members[0] ? c.nmem : 0) + (c.mean[0] ? 1 : 0) + (c.spread[0] ? 1 : 0);
+    if (groups == 0) return hipErrorInvalidValue;
+    const dim3 grd((unsigned)((gsz / 2 + 255) / 256), c.nlev + 1), blk(256);
+    // the launch's output: float32, 5 nlev + 1 grids per member and per statistic, and the counts
+    const bool wt = write_through_policy(p, ((long)groups * (5 * c.nlev + 1) + (c.below ? c.nlev : 0)) * gsz * 4);
+    if (c.log_p) {
+        if (wt) hipLaunchKernelGGL((plev_output_kernel<true, true>), grd, blk, 0, s, c, gsz);
+        else hipLaunchKernelGGL((plev_output_kernel<false, true>), grd, blk, 0, s, c, gsz);
+    } else {
+        if (wt) hipLaunchKernelGGL((plev_output_kernel<true, false>), grd, blk, 0, s, c, gsz);
+        else hipLaunchKernelGGL((plev_output_kernel<false, false>), grd, blk, 0, s, c, gsz);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace spdy

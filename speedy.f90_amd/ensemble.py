@@ -32,6 +32,8 @@ Nature's truth (include/spdy.h, "nature run").  Not covered: the level-sharded
 step."""
 import numpy as np
 
+from .spectral import MAX_PLEV
+
 PROG = ("vor", "div", "t", "tr", "ps")
 SHARED = ("phis", "tcorh", "qcorh")
 ROB, WIL = float(np.float32(0.05)), float(np.float32(0.53))          # params.f90:32-33 (float32 literals widened)
@@ -196,6 +198,56 @@ class Ensemble:
             res[grp] = given
         self.sp.ens_output_batch_dev(self.nmem, self.vor[0], self.div[0], self.t[0], self.tr[0], self.phi if phi is None else phi,
                                      self.ps[0], res.get("members"), res.get("mean"), res.get("spread"), use)
+        return res
+
+    def output_pressure_shapes(self, nlev):
+        """group -> {field: shape} of what output_pressure returns for nlev pressure levels (float32); "below" -> its shape"""
+        E, g = self.nmem, (self.sp.il, self.sp.ix)
+        lev = lambda lead: dict({n: lead + (int(nlev),) + g for n in ("u", "v", "t", "q", "phi")}, ps=lead + g)
+        return {"members": lev((E,)), "mean": lev(()), "spread": lev(()), "below": (int(nlev),) + g}
+
+    def output_pressure(self, plev, coord="p", members=True, stats=True, use=None, phi=None, below=False, out=None):
+        """output() on pressure levels (include/spdy.h, "pressure-level output"): every member's u, v, t, q, phi interpolated in the
+        vertical to the pressures plev (Pa, a host sequence of 1 .. 32 levels in any order) by np.interp's rule -- coord "p": linear
+        in p, what the reference's scripts/sigma_to_pressure.py does; "logp": linear in ln p -- and the mean and spread of the
+        INTERPOLATED values over the members in use.  A level outside a member's column gets that member's end level's value.
+        -> {"members": {u .. phi (E, nlev, il, ix), ps (E, il, ix)}, "mean": {.. (nlev, il, ix), ps (il, ix)}, "spread": {..},
+        "below": (nlev, il, ix)} of float32 device tensors; without `members` / `stats` / `below` the entries are left out.  below:
+        the number of members in use whose lowest model level lies above the level (the value there is the clamped one): the mask.
+        members, stats, use, phi, out: as output(), out with the shapes of output_pressure_shapes(nlev) and "below" a tensor.  plev
+        is read by this call: a captured call keeps its values."""
+        import torch
+        if not members and not stats:
+            raise ValueError("output_pressure: neither members nor stats wanted")
+        dev = self.vor.device
+        if use is not None and not torch.is_tensor(use):
+            use = torch.tensor([1 if u else 0 for u in use], dtype=torch.int32, device=dev)
+        if use is not None and (use.dtype != torch.int32 or use.numel() != self.nmem or not use.is_contiguous()):
+            raise ValueError("use must be %d contiguous int32 entries" % self.nmem)
+        nlev = int(np.atleast_1d(plev).size)
+        if not 1 <= nlev <= MAX_PLEV:
+            raise ValueError("output_pressure: %d levels, not 1 .. %d" % (nlev, MAX_PLEV))
+        res, shapes = {}, self.output_pressure_shapes(nlev)
+        fits = lambda a, sh: tuple(a.shape) == sh and a.dtype == torch.float32 and a.is_contiguous()
+        for grp in ("members", "mean", "spread"):
+            if not (members if grp == "members" else stats):
+                continue
+            given = (out or {}).get(grp)
+            if given is None:
+                given = {n: torch.empty(sh, dtype=torch.float32, device=dev) for n, sh in shapes[grp].items()}
+            for n, sh in shapes[grp].items():
+                if not fits(given[n], sh):
+                    raise ValueError("out[%s][%s] must be a contiguous float32 tensor of shape %s" % (grp, n, sh))
+            res[grp] = given
+        if below:
+            res["below"] = (out or {}).get("below")
+            if res["below"] is None:
+                res["below"] = torch.empty(shapes["below"], dtype=torch.float32, device=dev)
+            if not fits(res["below"], shapes["below"]):
+                raise ValueError("out[below] must be a contiguous float32 tensor of shape %s" % (shapes["below"],))
+        self.sp.ens_output_pressure_dev(self.nmem, self.vor[0], self.div[0], self.t[0], self.tr[0], self.phi if phi is None else phi,
+                                        self.ps[0], plev, coord, res.get("members"), res.get("mean"), res.get("spread"),
+                                        res.get("below"), use)
         return res
 
     # ------------------------------------------------------------------ analysis

@@ -1150,6 +1150,29 @@ module spdy_c
             integer(c_int), value :: nmem
             integer(c_int) :: rc
         end function
+        ! the pressure-level output (include/spdy.h): plev is c_loc of nlev c_double on the HOST, in Pa; coord is SPDY_PLEV_LINEAR_P
+        ! or SPDY_PLEV_LOG_P; below is a device array of c_float (ix,il,nlev), or c_null_ptr = not wanted; the groups as above
+        function spdy_ens_output_pressure_dev(plan, nmem, vor, div, t, q, phi, ps, d_use, nlev, plev, coord, members, mean, spread, &
+                & below) bind(C, name="spdy_ens_output_pressure_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, vor, div, t, q, phi, ps, d_use, plev, members, mean, spread, below
+            integer(c_int), value :: nmem, nlev, coord
+            integer(c_int) :: rc
+        end function
+        function spdy_ens_output_pressure_grid_dev(plan, nmem, grid, d_use, nlev, plev, coord, members, mean, spread, below) &
+                & bind(C, name="spdy_ens_output_pressure_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, grid, d_use, plev, members, mean, spread, below
+            integer(c_int), value :: nmem, nlev, coord
+            integer(c_int) :: rc
+        end function
+        function spdy_output_pressure_dev(plan, vor, div, t, q, phi, ps, nlev, plev, coord, u_out, v_out, t_out, q_out, phi_out, &
+                & ps_out) bind(C, name="spdy_output_pressure_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: plan, vor, div, t, q, phi, ps, plev, u_out, v_out, t_out, q_out, phi_out, ps_out
+            integer(c_int), value :: nlev, coord
+            integer(c_int) :: rc
+        end function
         ! the ensemble analysis (include/spdy.h): host is c_loc of an array of spdy_obs; the device pointers are those of time
         ! level 1 of the ensemble (spdy_ens_letkf_dev) or of a gridded ensemble (spdy_letkf_analyse_grid_dev)
         function spdy_letkf_create(plan, nmem, max_obs, l) bind(C, name="spdy_letkf_create") result(rc)
@@ -1269,6 +1292,8 @@ module spdy_c
     integer(c_int), parameter :: SPDY_OBS_U = 0_c_int, SPDY_OBS_V = 1_c_int, SPDY_OBS_T = 2_c_int, SPDY_OBS_Q = 3_c_int, &
         & SPDY_OBS_PS = 4_c_int                                !! spdy_obs%var (include/spdy.h)
     integer(c_int), parameter :: SPDY_DEVICE_AUTO = -2_c_int   !! $SPDY_DEVICE, else the launcher's local rank (include/spdy.h)
+    integer(c_int), parameter :: SPDY_MAX_PLEV = 32_c_int, SPDY_PLEV_LINEAR_P = 0_c_int, SPDY_PLEV_LOG_P = 1_c_int
+                                                               !! pressure-level output: the level count's bound, coord (include/spdy.h)
 
     !> Work a drop-in module has deferred on the device and that must be issued before the plan's tables change (time_stepping's
     !  collected leapfrog steps under steps_per_launch > 1): the module registers its flush routine here, and every wrapper that

@@ -27,6 +27,8 @@ from .columns import (DIAG_DEKE, DIAG_FIELDS, DIAG_NONFINITE, DIAG_REFERENCE, DI
 from .letkf import LETKF_FIELDS, LETKF_TABLES, Letkf, Obs  # noqa: F401,E402
 
 RESOLUTIONS = {"t30": (30, 96, 24), "t63": (63, 192, 48)}   # trunc, ix, iy
+MAX_PLEV = 32                                               # SPDY_MAX_PLEV
+PLEV_COORDS = {"p": 0, "logp": 1}                           # SPDY_PLEV_LINEAR_P, SPDY_PLEV_LOG_P
 
 
 class SpecSeg(ctypes.Structure):      # spdy_spec_seg (include/spdy.h)
@@ -506,6 +508,52 @@ class Spectral(ColumnPhysics):
         groups = [None if g is None else OutputFields(*[g[n].data_ptr() for n in OutputFields.NAMES]) for g in (members, mean, spread)]
         check(self.lib.spdy_ens_output_batch_dev(self.h, int(nmem), *[self._dp(x) for x in (vor, div, t, q, phi, ps, use)],
                                                  *[None if g is None else ctypes.byref(g) for g in groups]))
+
+    # ------------------------------------------------------------------ pressure-level output (include/spdy.h, "pressure-level output")
+    @staticmethod
+    def _plev(plev, coord):
+        """(nlev, the host array of pressures in Pa and its pointer, the C value of coord): coord "p" (linear in p) or "logp"""
+        if coord not in PLEV_COORDS:
+            raise ValueError("coord must be one of %s" % (sorted(PLEV_COORDS),))
+        p = np.ascontiguousarray(np.atleast_1d(plev), np.float64)
+        if p.ndim != 1:
+            raise ValueError("plev must be a sequence of pressures in Pa")
+        return p.size, p, p.ctypes.data_as(ctypes.c_void_p), PLEV_COORDS[coord]
+
+    @staticmethod
+    def _groups(*groups):
+        structs = [None if g is None else OutputFields(*[g[n].data_ptr() for n in OutputFields.NAMES]) for g in groups]
+        return structs, [None if g is None else ctypes.byref(g) for g in structs]
+
+    def ens_output_pressure_dev(self, nmem, vor, div, t, q, phi, ps, plev, coord="p", members=None, mean=None, spread=None, below=None,
+                                use=None):
+        """ens_output_batch_dev on pressure levels: plev, a host sequence of nlev pressures in Pa (read now: a captured call keeps
+        its values); coord "p" (linear in p, the reference script's) or "logp".  members: u .. phi (nmem, nlev, il, ix), ps (nmem,
+        il, ix); mean and spread: (nlev, il, ix), ps (il, ix); below: None or a float32 tensor (nlev, il, ix), the number of members
+        in use whose lowest model level lies above the level."""
+        nlev, keep, pp, cc = self._plev(plev, coord)
+        self._sync_stream()
+        structs, refs = self._groups(members, mean, spread)
+        check(self.lib.spdy_ens_output_pressure_dev(self.h, int(nmem), *[self._dp(x) for x in (vor, div, t, q, phi, ps, use)], nlev, pp, cc,
+                                                    *refs, self._dp(below)))
+
+    def ens_output_pressure_grid_dev(self, nmem, grid, plev, coord="p", members=None, mean=None, spread=None, below=None, use=None):
+        """ens_output_pressure_dev's kernel alone on a gridded ensemble: grid, float64, the (5 kx + 1) nmem grids u | v | t | q | phi
+        (nmem, kx, il, ix) each | ps (nmem, il, ix) back to back, the model's raw values (q in g/kg, phi in m2/s2, ps as log(p/p0))"""
+        nlev, keep, pp, cc = self._plev(plev, coord)
+        self._sync_stream()
+        structs, refs = self._groups(members, mean, spread)
+        check(self.lib.spdy_ens_output_pressure_grid_dev(self.h, int(nmem), self._dp(grid), self._dp(use), nlev, pp, cc, *refs,
+                                                         self._dp(below)))
+
+    def output_pressure_dev(self, vor, div, t, q, phi, ps, plev, coord, u_out, v_out, t_out, q_out, phi_out, ps_out):
+        """output_batch_dev on pressure levels, the one-member case of ens_output_pressure_dev: float32 [nlev,il,ix] (ps_out
+        [il,ix]) out"""
+        nlev, keep, pp, cc = self._plev(plev, coord)
+        self._sync_stream()
+        args = (vor, div, t, q, phi, ps)
+        outs = (u_out, v_out, t_out, q_out, phi_out, ps_out)
+        check(self.lib.spdy_output_pressure_dev(self.h, *[self._dp(x) for x in args], nlev, pp, cc, *[self._dp(x) for x in outs]))
 
     def geopotential_dev(self, t, phis, phi):
         self._members("geopotential_dev", None, t, phis, phi)

@@ -48,6 +48,14 @@ the download of its float32 grids, the operator and the noise in vectorised NumP
 Letkf.set_obs (median of --repeats calls after one warm-up).  The rows of (a) and (b) give their share of the cycle {36 steps,
 analysis}; the row of (c) its ratio to (a).
 
+--pressure measures the pressure-level output instead (include/spdy.h, "pressure-level output"; T30 L8, the reference
+script's eight levels, E = 4, 16 and 32, 100 replays per timing unless told otherwise): graph replays of Ensemble.output_pressure with
+members, statistics and `below`, in both coordinates, next to (a) Ensemble.output on the same build, and (b) the route a build without
+the call offers to the same fields -- Ensemble.output, the download of its float32 members, np.interp's rule vectorised over the
+columns in NumPy, and mean and spread on the host -- wall-clock with its synchronisation (median of --repeats calls after one
+warm-up).  The kernel's byte model: per level (5 * 2 + 1) E FP64 grids read in the first pass and again in the second, (E + 2) 5 + 1
+float32 grids written; and the surface-pressure row.
+
     python tools/ensemble_rate.py [--sizes t30 t63k16] [--members 1 2 4 8 16 32] [--reps 200] [--repeats 5] [--json out.json]
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --single-only --label parent
     python tools/ensemble_rate.py --coupled --members 1 2 4 8 16
@@ -56,6 +64,7 @@ analysis}; the row of (c) its ratio to (a).
     python tools/ensemble_rate.py --letkf --json profiles/ensemble_letkf_rate.json
     python tools/ensemble_rate.py --letkf --stride 2 2
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
+    python tools/ensemble_rate.py --pressure --json profiles/ensemble_pressure_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
 import argparse
 import ctypes
@@ -352,6 +361,77 @@ def run_output(tag, members, reps, repeats, label, rows):
     sp.close()
 
 
+def host_pressure_levels(en, sigma, plev, repeats):
+    """the host route to the pressure-level members, mean and spread, microseconds wall-clock (median, min, max): Ensemble.output,
+    the download of its float32 members, np.interp's rule on (ps / 100) * sigma vectorised over the columns, the statistics in NumPy"""
+    import time
+    names = ("u", "v", "t", "q", "phi")
+    p_hpa = np.asarray(plev, np.float64) / 100.0
+    us = []
+    for _ in range(repeats + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m = {n: a.cpu().numpy() for n, a in en.output(stats=False)["members"].items()}
+        X = (m["ps"][:, None] / np.float32(100.0)) * sigma[None, :, None, None]             # (E, kx, il, ix)
+        res = {}
+        for x in p_hpa:
+            kb = np.clip(np.sum(X <= x, axis=1) - 1, 0, X.shape[1] - 2)[:, None]
+            x0, x1 = np.take_along_axis(X, kb, 1)[:, 0], np.take_along_axis(X, kb + 1, 1)[:, 0]
+            w = np.clip((x - x0) / (x1 - x0), 0.0, 1.0).astype(np.float64)
+            for n in names:
+                f0, f1 = np.take_along_axis(m[n], kb, 1)[:, 0], np.take_along_axis(m[n], kb + 1, 1)[:, 0]
+                y = f0 + w * (f1 - f0)
+                res.setdefault(n, []).append((y.astype(np.float32), y.mean(axis=0).astype(np.float32), y.std(axis=0, ddof=1).astype(np.float32)))
+        us.append((time.perf_counter() - t0) * 1e6)
+    return float(np.median(us[1:])), min(us[1:]), max(us[1:])
+
+
+def run_pressure(tag, members, reps, repeats, label, rows):
+    """graph replays of the pressure-level output in both coordinates and of the sigma-level output, and the host route"""
+    import ensemblestep
+    import pressurelevels
+    kx = VARIANTS[tag][3]
+    sp = support.plan(tag, max(members) * (4 * kx + 4))
+    plev = list(pressurelevels.SCRIPT_LEVELS)
+    nlev, grid = len(plev), sp.il * sp.ix
+    sigma = sp.table("fsg").astype(np.float32)
+    graphs, keep, host = {}, [], {}
+    for E in members:
+        en = ensemblestep.build(sp, ensemblestep.member_states(sp, E))
+        sp.ens_geopotential_dev(E, en.t[0], en.phis, en.phi)                 # phi of time level 1: an input of the snapshot
+        zeros = lambda sh: torch.zeros(sh, dtype=torch.float32, device="cuda")
+        group = lambda shapes: {g: ({n: zeros(x) for n, x in sh.items()} if isinstance(sh, dict) else zeros(sh)) for g, sh in shapes.items()}
+        out_s, out_p = group(en.output_shapes()), {c: group(en.output_pressure_shapes(nlev)) for c in ("p", "logp")}
+        en.output_workspace()
+        torch.cuda.synchronize()
+        with sp.graph_capture() as g:
+            en.output(out=out_s)
+        graphs["pressure E=%d sigma-level output" % E] = g
+        for c in ("p", "logp"):
+            with sp.graph_capture() as g:
+                en.output_pressure(plev, c, below=True, out=out_p[c])
+            graphs["pressure E=%d output_pressure %s" % (E, c)] = g
+        host[E] = host_pressure_levels(en, sigma, plev, repeats)
+        keep.append((en, out_s, out_p))
+    nodes = {n: g.num_nodes() for n, g in graphs.items()}
+    t = time_interleaved({n: g.launch for n, g in graphs.items()}, lambda: None, reps, repeats)
+    for name, (med, lo, hi) in t.items():
+        E = int(name.split("=")[1].split()[0])
+        row = {"label": label, "size": tag, "form": name, "members": E, "levels": nlev, "nodes": nodes[name], "us_per_call": round(med, 2),
+               "us_min": round(lo, 2), "us_max": round(hi, 2)}
+        if "output_pressure" in name:
+            sig = t["pressure E=%d sigma-level output" % E][0]
+            kernel_bytes = grid * (nlev * (2 * 11 * E * 8 + ((E + 2) * 5 + 1) * 4) + 2 * E * 8 + (E + 2) * 4)
+            row.update(ratio_to_sigma_level_output=round(med / sig, 3), host_route_us_wall=round(host[E][0], 1),
+                       host_route_us_min=round(host[E][1], 1), host_route_us_max=round(host[E][2], 1),
+                       host_route_times_this=round(host[E][0] / med, 1), kernel_bytes=kernel_bytes)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for g in graphs.values():
+        g.close()
+    sp.close()
+
+
 def run_sppt(tag, members, reps, repeats, label, rows):
     """graph replays of (a) the ensemble advance and E single advances, (b) the ensemble step with the physics without and with SPPT
     and E single-state steps with SPPT"""
@@ -593,6 +673,7 @@ def main():
     ap.add_argument("--sppt", action="store_true")
     ap.add_argument("--letkf", action="store_true")
     ap.add_argument("--osse", action="store_true")
+    ap.add_argument("--pressure", action="store_true")
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
@@ -601,9 +682,9 @@ def main():
     ap.add_argument("--json")
     a = ap.parse_args()
     a.letkf = a.letkf or a.osse
-    a.sizes = a.sizes or (["t30"] if a.sppt or a.letkf else ["t30", "t63k16"])
-    a.members = a.members or ([4, 16, 32] if a.letkf else [1, 4, 16] if a.sppt else [1, 2, 4, 8, 16, 32])
-    a.reps = a.reps or (100 if a.sppt or a.letkf else 200)
+    a.sizes = a.sizes or (["t30"] if a.sppt or a.letkf or a.pressure else ["t30", "t63k16"])
+    a.members = a.members or ([4, 16, 32] if a.letkf or a.pressure else [1, 4, 16] if a.sppt else [1, 2, 4, 8, 16, 32])
+    a.reps = a.reps or (100 if a.sppt or a.letkf or a.pressure else 200)
     if a.single_only:          # a library from before the ensemble entry points: bind (on first use) without them
         from speedy_f90_amd import _lib
         for n in [n for n in _lib.SIGNATURES if n.startswith("spdy_ens_") or n == "spdy_sppt_members"]:
@@ -616,6 +697,8 @@ def main():
         for tag in a.sizes:
             if a.letkf:
                 run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse)
+            elif a.pressure:
+                run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:
                 run_sppt(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.output:
