@@ -1086,6 +1086,55 @@ int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *v
                                 const double *psg, double *du, double *dv, double *dt, double *dq, double *dps);
 int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps);
 
+/* ---- ensemble analysis, observations at a pressure --------------------------------------------------------------
+ * Radiosondes, aircraft and satellite winds report at a pressure.  In a sigma model the level that brackets a pressure differs from
+ * member to member and from column to column, because every member has its own surface pressure; so the operator interpolates in
+ * the vertical per member.  tests/letkfpressure.py restates this subsection in NumPy.
+ * spdy_pobs_set is spdy_letkf_set_obs for a network in which any observation of u, v, t or q may be given at a pressure: with
+ * lev == SPDY_OBS_AT_P the observation sits at p, in Pa, finite and > 0; with lev in 0..kx-1 it is the model-level observation
+ * above and p is ignored; for SPDY_OBS_PS lev and p are both ignored.  Checks, in this order: a NULL object SPDY_ERR_ARG ("null
+ * analysis object"), a destroyed plan SPDY_ERR_STATE, nobs outside [0, max_obs], NULL observations, the first invalid field of the
+ * first invalid observation -- var, lev (an at-pressure observation on a plan with kx < 2 fails here), p, lon, lat, value, error --
+ * SPDY_ERR_ARG; an open capture SPDY_ERR_STATE.  A rejected call changes nothing.  Stream-ordered and synchronising like set_obs;
+ * works on a host-only plan.  A set without any at-pressure observation leaves the object exactly as spdy_letkf_set_obs would: the
+ * same kernels, the same launch count, the same bits.  A later spdy_letkf_set_obs returns it to a pure model-level network.  The
+ * arrays this needs come with spdy_letkf_create: nothing is allocated here or in an analysis call.  A graph captured with a network
+ * of one kind has to be captured again after a set of the other kind; between networks of one kind it replays as before.  (A
+ * stale graph computes something else, it does not leave its arrays: on the device an at-pressure observation has level 0 and a
+ * flag of its own, so the plain observation kernel reads it as an observation on level 0.)
+ *   operator      linear in ln p only.  x_o = ln(p_o / p0), p0 = 1e5 Pa, formed on the host by the C library's log at
+ *                 spdy_pobs_set, so the device needs no transcendental.  For member e and stencil point s (the four points and
+ *                 weights of the operator above, all four evaluated whatever their weight) the column's coordinate is X_k =
+ *                 ps_e[s] + ln fsg[k], and z_{e,s} is the value at x_o by np.interp's rule ("pressure-level output" above, linear
+ *                 in ln p): with kb the number of k in 1..kx-2 with X_k <= x_o, level 0's bits where x_o <= X_0, level kx-1's
+ *                 bits where x_o >= X_{kx-1}, else f[kb] + w (f[kb+1] - f[kb]) with w = (x_o - X_kb) / (X_{kb+1} - X_kb), every
+ *                 operation rounded once.  hx_e = ((w0 z0 + w1 z1) + w2 z2) + w3 z3; hxmean, Y and d as above, e ascending.
+ *   localisation  the observation's vertical position is that of its pressure under the ensemble-mean surface pressure at its
+ *                 place: pb_e = ((w0 ps_e[i0] + w1 ps_e[i1]) + w2 ps_e[i2]) + w3 ps_e[i3], psbar = (sum of pb_e, e ascending) / E,
+ *                 ln sigma_o = x_o - psbar.  It is written, on every analysis call, to the device array the local analyses read:
+ *                 a captured analysis localises with the ensemble of the replay.  Model-level and PS observations keep theirs.
+ *   use           an at-pressure observation is out of column in a call if for some member and some of its four points x_o < X_0
+ *                 or x_o > X_{kx-1}; a target exactly on an end level is in the column; a non-finite ps makes neither comparison
+ *                 true, rejects nothing and propagates as NaN.  The values of an out-of-column observation would be an end
+ *                 level's, an extrapolation: its r is exactly 0 in this call -- it enters no sum, by "an observation with w == 0
+ *                 takes no part" -- while its hx, hxmean, Y and d are still written, for diagnostics.  The local analyses read a
+ *                 per-call copy of 1/error^2 for this; the host table "rinv" stays 1/error^2.
+ * spdy_letkf_table: "lnp", ln(p/p0) of the at-pressure observations and 0 for the others, one per observation after spdy_pobs_set,
+ * count 0 after spdy_letkf_set_obs; "lnsigma" gives ln(p/p0) for an at-pressure observation, its ln sigma_o at ps = 0.
+ * spdy_letkf_field: "obs_lnsigma", ln sigma_o of every observation as the latest analysis call localised with it (for a
+ * model-level network the uploaded table); "obs_used", 1.0 or 0.0 per observation (all 1.0 after a set and for a model-level
+ * network).  The kernel, in the observation kernel's place only when the current network holds an at-pressure observation: a
+ * workgroup owns whole observations, one thread per (observation, member) finds the four brackets from the four ps and loads the
+ * levels they name by address, one thread per observation sums over the members; no atomics.  The launch counts above hold.
+ * spdy_nature_observe_dev on such a network writes value_o = h_o + (noise * error_o) * z_o with h_o the same operator on the truth
+ * and its ps, clamped to the end level where the truth is out of column; noise, counter and launch count as in "nature run".    */
+enum { SPDY_OBS_AT_P = -1 };
+typedef struct {
+    int var, lev;
+    double p, lon, lat, value, error;
+} spdy_pobs;
+int spdy_pobs_set(spdy_letkf *l, int nobs, const spdy_pobs *host);
+
 /* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
  * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
  * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a

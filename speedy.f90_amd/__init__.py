@@ -18,6 +18,6 @@ from ._lib import LIB_PATH, SpdyError, build, load  # noqa: F401
 from .spectral import (RESOLUTIONS, DeviceField, Diagnostics, DiagnosticsStop, Graph, Spectral, Sppt, SurfaceModel,  # noqa: F401
                        check)
 from .ensemble import Ensemble  # noqa: F401
-from .letkf import OBS_PS, OBS_Q, OBS_T, OBS_U, OBS_V, Letkf  # noqa: F401
+from .letkf import OBS_AT_P, OBS_PS, OBS_Q, OBS_T, OBS_U, OBS_V, Letkf, PObs  # noqa: F401
 from .nature import Nature  # noqa: F401
 from . import sharding  # noqa: F401

@@ -179,6 +179,7 @@ SIGNATURES = {
     "spdy_letkf_destroy": [c_void_p],
     "spdy_letkf_set_localization": [c_void_p, c_double, c_double, c_double],
     "spdy_letkf_set_obs": [c_void_p, c_int, c_void_p],
+    "spdy_pobs_set": [c_void_p, c_int, c_void_p],
     "spdy_letkf_set_weight_stride": [c_void_p, c_int, c_int],
     "spdy_letkf_table": [c_void_p, c_char_p, c_void_p, c_int],
     "spdy_letkf_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],

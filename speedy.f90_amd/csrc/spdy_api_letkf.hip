@@ -77,7 +77,18 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
     c.colunit = l->d_colunit; c.lnfsg = l->d_lnfsg; c.ounit = l->d_ounit; c.olns = l->d_olns; c.rinv = l->d_rinv;
     c.y = l->d_y; c.dep = l->d_dep;
     for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = dx[v]; }
-    KERNEL(spdy::launch_letkf_obs(o, p->stream));
+    if (l->npobs) {
+        // observations at a pressure: the kernel that interpolates per member, in letkf_obs_kernel's place; it writes ln sigma_o of
+        // those observations into olns and this call's copy of rinv, 0 where an observation is out of its column
+        spdy::LetkfPObs po{};
+        po.o = o; po.atp = l->d_atp; po.lnp = l->d_lnp; po.rinv = l->d_rinv; po.olns = l->d_olns; po.used = l->d_used; po.reff = l->d_reff;
+        po.lv.kx = kx;
+        for (int k = 0; k < kx; ++k) po.lv.lev[k] = l->lnfsg[k];
+        c.rinv = l->d_reff;
+        KERNEL(spdy::launch_letkf_pobs(po, p->stream));
+    } else {
+        KERNEL(spdy::launch_letkf_obs(o, p->stream));
+    }
     if (!l->d_tw) {
         KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
         return SPDY_OK;
@@ -136,6 +147,100 @@ void drop_interp(spdy_letkf *l)
     l->si = l->sj = 1;
     l->h_coarse.clear(); l->h_iidx.clear(); l->h_iwgt.clear();
 }
+
+// an observation of either entry point as the ingestion reads it
+inline double pressure_of(const spdy_obs &) { return 0.0; }
+inline double pressure_of(const spdy_pobs &b) { return b.p; }
+constexpr bool takes_pressure(const spdy_obs *) { return false; }
+constexpr bool takes_pressure(const spdy_pobs *) { return true; }
+
+// spdy_letkf_set_obs and spdy_pobs_set: every field of every observation is validated before anything changes; then the tables
+// are built on the host and uploaded.  OBS = spdy_obs: no observation is at a pressure, and the object is left as it always was.
+template <class OBS>
+int ingest(spdy_letkf *l, int nobs, const OBS *host, const char *call, const char *what)
+{
+    NEED_LIVE(l, "analysis object");
+    if (nobs < 0 || nobs > l->max_obs) return fail(SPDY_ERR_ARG, "%s: nobs=%d outside [0, max_obs=%d]", call, nobs, l->max_obs);
+    if (nobs && !host) return fail(SPDY_ERR_ARG, "null observations");
+    spdy_plan *p = l->plan;
+    const int kx = p->tab.kx;
+    constexpr bool PRES = takes_pressure(static_cast<const OBS *>(nullptr));
+    auto at_p = [&](const OBS &b) { return PRES && b.var != SPDY_OBS_PS && b.lev == SPDY_OBS_AT_P; };
+    for (int o = 0; o < nobs; ++o) {
+        const OBS &b = host[o];
+        if (b.var < SPDY_OBS_U || b.var > SPDY_OBS_PS) return fail(SPDY_ERR_ARG, "%s: observation %d: var=%d", call, o, b.var);
+        if (at_p(b)) {
+            if (kx < 2) return fail(SPDY_ERR_ARG, "%s: observation %d: an observation at a pressure needs kx >= 2", call, o);
+            const double pr = pressure_of(b);
+            if (!(pr > 0.0) || !std::isfinite(pr)) return fail(SPDY_ERR_ARG, "%s: observation %d: p must be finite and > 0", call, o);
+        } else if (b.var != SPDY_OBS_PS && (b.lev < 0 || b.lev >= kx))
+            return fail(SPDY_ERR_ARG, "%s: observation %d: lev=%d outside [0, %d)", call, o, b.lev, kx);
+        if (!std::isfinite(b.lon)) return fail(SPDY_ERR_ARG, "%s: observation %d: lon is not finite", call, o);
+        if (!(std::fabs(b.lat) <= 90.0)) return fail(SPDY_ERR_ARG, "%s: observation %d: lat outside [-90, 90]", call, o);
+        if (!std::isfinite(b.value)) return fail(SPDY_ERR_ARG, "%s: observation %d: value is not finite", call, o);
+        if (!(b.error > 0.0) || !std::isfinite(b.error))
+            return fail(SPDY_ERR_ARG, "%s: observation %d: error must be finite and > 0", call, o);
+    }
+    NOT_CAPTURING(p, what);
+    const size_t n = (size_t)nobs;
+    const double p0 = static_cast<double>(1.e+5f);
+    std::vector<int> sidx(4 * n), var(n), lev(n), atp(PRES ? n : 0);
+    std::vector<double> swgt(4 * n), unit(3 * n), lns(n), rinv(n), err(n), value(n), lnp(PRES ? n : 0);
+    // obs_used is all ones from create on; only an analysis of a network with at-pressure observations writes anything else
+    const bool reset_used = p->device >= 0 && (PRES || l->npobs > 0);
+    std::vector<double> ones(reset_used ? n : 0, 1.0);
+    int npobs = 0;
+    for (size_t o = 0; o < n; ++o) {
+        const OBS &b = host[o];
+        stencil(l, b.lon, b.lat, &sidx[4 * o], &swgt[4 * o]);
+        unit_vector(b.lon, b.lat, &unit[3 * o]);
+        var[o] = b.var;
+        if (at_p(b)) {
+            lev[o] = 0;                                   // the device's level stays a level: atp marks the observation
+            atp[o] = 1;
+            lnp[o] = lns[o] = std::log(pressure_of(b) / p0);      // ln sigma_o at ps = 0; the analysis call forms its own
+            ++npobs;
+        } else {
+            lev[o] = b.var == SPDY_OBS_PS ? 0 : b.lev;
+            lns[o] = b.var == SPDY_OBS_PS ? 0.0 : l->lnfsg[b.lev];
+        }
+        rinv[o] = 1.0 / (b.error * b.error);
+        err[o] = b.error;
+        value[o] = b.value;
+    }
+    if (p->device >= 0) {
+        HIP_TRY(hipSetDevice(p->device));
+        auto all = [&]() -> int {
+            RC(upload(p, l->d_sidx, sidx.data(), 4 * n * sizeof(int)));
+            RC(upload(p, l->d_var, var.data(), n * sizeof(int)));
+            RC(upload(p, l->d_lev, lev.data(), n * sizeof(int)));
+            RC(upload(p, l->d_swgt, swgt.data(), 4 * n * sizeof(double)));
+            RC(upload(p, l->d_ounit, unit.data(), 3 * n * sizeof(double)));
+            RC(upload(p, l->d_olns, lns.data(), n * sizeof(double)));
+            RC(upload(p, l->d_rinv, rinv.data(), n * sizeof(double)));
+            RC(upload(p, l->d_err, err.data(), n * sizeof(double)));
+            RC(upload(p, l->d_value, value.data(), n * sizeof(double)));
+            if (reset_used) { RC(upload(p, l->d_used, ones.data(), n * sizeof(double))); }
+            if (PRES) {
+                RC(upload(p, l->d_lnp, lnp.data(), n * sizeof(double)));
+                RC(upload(p, l->d_atp, atp.data(), n * sizeof(int)));
+            }
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            return SPDY_OK;
+        };
+        if (const int rc = all()) {
+            // the device tables may be partly new: the object holds no observations now, and no copy is still reading the host
+            // arrays when they go
+            (void)hipStreamSynchronize(p->stream);
+            l->nobs = 0; l->npobs = 0;
+            l->h_sidx.clear(); l->h_swgt.clear(); l->h_unit.clear(); l->h_lns.clear(); l->h_rinv.clear(); l->h_lnp.clear();
+            return rc;
+        }
+    }
+    l->nobs = nobs; l->npobs = npobs;
+    l->h_sidx.swap(sidx); l->h_swgt.swap(swgt); l->h_unit.swap(unit); l->h_lns.swap(lns); l->h_rinv.swap(rinv); l->h_lnp.swap(lnp);
+    return SPDY_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -175,8 +280,9 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     auto cleanup = [&](int rc) { spdy_letkf_destroy(l); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
     const size_t ncol = grid_elems(p), nf = (size_t)(4 * kx + 1) * nmem, M = (size_t)(max_obs > 0 ? max_obs : 1), E = (size_t)nmem;
-    // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | err | value | hx | hxmean | y | dep ; then the ints
-    const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 1 + 2 * E), ni = 6 * M;
+    // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | err | value | hx | hxmean | y | dep | lnp | used |
+    // reff ; then the ints
+    const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 1 + 2 * E + 3), ni = 7 * M;
     if (int rc = dev_alloc(p, nd * sizeof(double) + ni * sizeof(int), &l->d_base)) return cleanup(rc);
     double *d = l->d_base;
     l->d_grid = d; d += nf * ncol;
@@ -193,10 +299,14 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     l->d_hxmean = d; d += M;
     l->d_y = d; d += M * E;
     l->d_dep = d; d += M;
+    l->d_lnp = d; d += M;
+    l->d_used = d; d += M;
+    l->d_reff = d; d += M;
     int *q = reinterpret_cast<int *>(d);
     l->d_sidx = q; q += 4 * M;
     l->d_var = q; q += M;
-    l->d_lev = q;
+    l->d_lev = q; q += M;
+    l->d_atp = q;
     std::vector<double> cu(3 * ncol);
     for (int j = 0; j < il; ++j)
         for (int i = 0; i < ix; ++i) {
@@ -204,7 +314,9 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
             unit_vector(i * (360.0 / ix), l->lat[j], u);
             for (int c = 0; c < 3; ++c) cu[c * ncol + (size_t)j * ix + i] = u[c];
         }
+    const std::vector<double> ones(M, 1.0);   // obs_used: spdy_letkf_set_obs never has to write it
     if (hipMemsetAsync(l->d_base, 0, nd * sizeof(double) + ni * sizeof(int), p->stream) != hipSuccess ||
+        hipMemcpyAsync(l->d_used, ones.data(), M * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_colunit, cu.data(), cu.size() * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_lnfsg, l->lnfsg.data(), kx * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipStreamSynchronize(p->stream) != hipSuccess)
@@ -243,64 +355,12 @@ int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h, double sigma_v, d
 
 int spdy_letkf_set_obs(spdy_letkf *l, int nobs, const spdy_obs *host)
 {
-    NEED_LIVE(l, "analysis object");
-    if (nobs < 0 || nobs > l->max_obs) return fail(SPDY_ERR_ARG, "letkf_set_obs: nobs=%d outside [0, max_obs=%d]", nobs, l->max_obs);
-    if (nobs && !host) return fail(SPDY_ERR_ARG, "null observations");
-    spdy_plan *p = l->plan;
-    const int kx = p->tab.kx;
-    for (int o = 0; o < nobs; ++o) {
-        const spdy_obs &b = host[o];
-        if (b.var < SPDY_OBS_U || b.var > SPDY_OBS_PS) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: var=%d", o, b.var);
-        if (b.var != SPDY_OBS_PS && (b.lev < 0 || b.lev >= kx))
-            return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: lev=%d outside [0, %d)", o, b.lev, kx);
-        if (!std::isfinite(b.lon)) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: lon is not finite", o);
-        if (!(std::fabs(b.lat) <= 90.0)) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: lat outside [-90, 90]", o);
-        if (!std::isfinite(b.value)) return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: value is not finite", o);
-        if (!(b.error > 0.0) || !std::isfinite(b.error))
-            return fail(SPDY_ERR_ARG, "letkf_set_obs: observation %d: error must be finite and > 0", o);
-    }
-    NOT_CAPTURING(p, "spdy_letkf_set_obs (upload)");
-    const size_t n = (size_t)nobs;
-    std::vector<int> sidx(4 * n), var(n), lev(n);
-    std::vector<double> swgt(4 * n), unit(3 * n), lns(n), rinv(n), err(n), value(n);
-    for (size_t o = 0; o < n; ++o) {
-        const spdy_obs &b = host[o];
-        stencil(l, b.lon, b.lat, &sidx[4 * o], &swgt[4 * o]);
-        unit_vector(b.lon, b.lat, &unit[3 * o]);
-        var[o] = b.var;
-        lev[o] = b.var == SPDY_OBS_PS ? 0 : b.lev;
-        lns[o] = b.var == SPDY_OBS_PS ? 0.0 : l->lnfsg[b.lev];
-        rinv[o] = 1.0 / (b.error * b.error);
-        err[o] = b.error;
-        value[o] = b.value;
-    }
-    if (p->device >= 0) {
-        HIP_TRY(hipSetDevice(p->device));
-        auto all = [&]() -> int {
-            RC(upload(p, l->d_sidx, sidx.data(), 4 * n * sizeof(int)));
-            RC(upload(p, l->d_var, var.data(), n * sizeof(int)));
-            RC(upload(p, l->d_lev, lev.data(), n * sizeof(int)));
-            RC(upload(p, l->d_swgt, swgt.data(), 4 * n * sizeof(double)));
-            RC(upload(p, l->d_ounit, unit.data(), 3 * n * sizeof(double)));
-            RC(upload(p, l->d_olns, lns.data(), n * sizeof(double)));
-            RC(upload(p, l->d_rinv, rinv.data(), n * sizeof(double)));
-            RC(upload(p, l->d_err, err.data(), n * sizeof(double)));
-            RC(upload(p, l->d_value, value.data(), n * sizeof(double)));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            return SPDY_OK;
-        };
-        if (const int rc = all()) {
-            // the device tables may be partly new: the object holds no observations now, and no copy is still reading the host
-            // arrays when they go
-            (void)hipStreamSynchronize(p->stream);
-            l->nobs = 0;
-            l->h_sidx.clear(); l->h_swgt.clear(); l->h_unit.clear(); l->h_lns.clear(); l->h_rinv.clear();
-            return rc;
-        }
-    }
-    l->nobs = nobs;
-    l->h_sidx.swap(sidx); l->h_swgt.swap(swgt); l->h_unit.swap(unit); l->h_lns.swap(lns); l->h_rinv.swap(rinv);
-    return SPDY_OK;
+    return ingest(l, nobs, host, "letkf_set_obs", "spdy_letkf_set_obs (upload)");
+}
+
+int spdy_pobs_set(spdy_letkf *l, int nobs, const spdy_pobs *host)
+{
+    return ingest(l, nobs, host, "pobs_set", "spdy_pobs_set (upload)");
 }
 
 int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
@@ -351,7 +411,7 @@ int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap
                                     : !std::strcmp(name, "interp_index") ? &l->h_iidx : nullptr;
     const std::vector<double> *v = !std::strcmp(name, "stencil_weight") ? &l->h_swgt : !std::strcmp(name, "unit") ? &l->h_unit
                                    : !std::strcmp(name, "lnsigma") ? &l->h_lns : !std::strcmp(name, "rinv") ? &l->h_rinv
-                                   : !std::strcmp(name, "interp_weight") ? &l->h_iwgt : nullptr;
+                                   : !std::strcmp(name, "interp_weight") ? &l->h_iwgt : !std::strcmp(name, "lnp") ? &l->h_lnp : nullptr;
     if (!index && !v) return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
     const int n = static_cast<int>(index ? index->size() : v->size());
     if (buf && cap < n) return fail(SPDY_ERR_ARG, "analysis table '%s' has %d values, the buffer %d", name, n, cap);
@@ -369,7 +429,8 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
     double *const *f = !std::strcmp(name, "hx") ? &l->d_hx : !std::strcmp(name, "hxmean") ? &l->d_hxmean
                        : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep
                        : !std::strcmp(name, "weights") ? &l->d_tw : !std::strcmp(name, "value") ? &l->d_value
-                       : !std::strcmp(name, "grid") ? &l->d_grid : nullptr;
+                       : !std::strcmp(name, "grid") ? &l->d_grid : !std::strcmp(name, "obs_lnsigma") ? &l->d_olns
+                       : !std::strcmp(name, "obs_used") ? &l->d_used : nullptr;
     if (!f) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f == &l->d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
     NEED_DEVICE(l->plan);

@@ -166,7 +166,15 @@ int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *l, double noise)
     o.nobs = l->nobs; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
     o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.error = l->d_err;
     o.truth = n->d_truth; o.state = n->d_state; o.noise = noise; o.value = l->d_value;
-    KERNEL(spdy::launch_nature_draw(o, p->stream));
+    if (l->npobs) {
+        // observations at a pressure: the draw kernel that interpolates the truth's columns, in nature_draw_kernel's place
+        spdy::VLevels lv{};
+        lv.kx = o.kx;
+        for (int k = 0; k < o.kx; ++k) lv.lev[k] = l->lnfsg[k];
+        KERNEL(spdy::launch_nature_pdraw(o, l->d_atp, l->d_lnp, lv, p->stream));
+    } else {
+        KERNEL(spdy::launch_nature_draw(o, p->stream));
+    }
     KERNEL(spdy::launch_nature_count(n->d_state, p->stream));
     return SPDY_OK;
 }

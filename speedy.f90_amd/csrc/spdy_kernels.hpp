@@ -529,6 +529,20 @@ struct LetkfObs {
     double *hx, *hxmean, *y, *dep;                   // [nobs][nmem], [nobs], [nobs][nmem], [nobs]
 };
 hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s);
+// The same quantities for a network that holds observations given at a pressure (include/spdy.h, "observations at a pressure";
+// DESIGN.md s22): atp[o] != 0 marks one (its lev[o] is 0: a kernel that does not know of it stays in bounds), lnp[o] = ln(p_o /
+// p0) is its target.  A workgroup owns whole observations, one thread per
+// (observation, member) interpolates the four stencil columns of its member (vinterp_brackets<true, 4>), one thread per observation
+// then sums over the members in ascending order.  Written besides LetkfObs' outputs: olns[o] = lnp[o] - psbar_o of the at-pressure
+// observations only (the others keep what set_obs uploaded), used[o] (1.0 / 0.0) and reff[o] = used ? rinv[o] : 0.0 of all.
+struct LetkfPObs {
+    LetkfObs o;
+    const int *atp;                                  // [nobs]
+    const double *lnp, *rinv;                        // [nobs], [nobs] 1 / error^2
+    double *olns, *used, *reff;                      // [nobs] each
+    VLevels lv;                                      // ln fsg
+};
+hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s);
 // The local analyses: one workgroup per grid column.  nlv levels' eigenproblems are in flight at a time (1, 2 or 4: what the LDS
 // holds; the results do not depend on it); lds = letkf_lds_bytes(nmem, kx, nlv).
 struct LetkfCols {
@@ -583,6 +597,10 @@ struct NatureObs {
     double *value;                                   // [nobs]
 };
 hipError_t launch_nature_draw(const NatureObs &a, hipStream_t s);
+// The same for a network that holds observations given at a pressure (atp[o] != 0, target lnp[o]): h is the bilinear sum of the four
+// columns' values interpolated to the target with the truth's ps, clamped to the end level outside the column; noise and counter
+// as above.
+hipError_t launch_nature_pdraw(const NatureObs &a, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s);
 // draws += 1 by one thread: every launch before it on the stream has read the counter, every launch after it sees the new one
 hipError_t launch_nature_count(unsigned long long *state, hipStream_t s);
 // The scores of an ensemble on the grid (x: LetkfObs::x) against the truth, two launches.  One workgroup per (row, latitude) forms

@@ -88,6 +88,82 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObs a
     a.dep[o] = a.value[o] - mean;
 }
 
+// The observation-space quantities of a network that holds observations given at a pressure (include/spdy.h, "observations at a
+// pressure").  A workgroup owns LETKF_BLOCK / E whole observations.  Thread (observation, member) finds the brackets
+// of the target in its member's four stencil columns from their four ps (one loop of kx trips, csrc/spdy_vinterp.hpp), loads the
+// two levels each bracket names by address, all eight loads before the first use, and leaves hx_e, the stencil's ps_e and its
+// out-of-column flag in LDS; thread (observation) then sums over the members in ascending order.  An observation on a model level
+// or of ps takes the same path with its bracket replaced by {lev, the level's own bits}, so the lanes of a wave do not diverge and
+// its hx has letkf_obs_kernel's bits.  No atomics, no array indexed by a bracket, every bound a kernel argument.
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_pobs_kernel(const LetkfPObs a)
+{
+#pragma clang fp contract(off)
+    __shared__ double shx[LETKF_BLOCK], spb[LETKF_BLOCK], smean[LETKF_BLOCK / 2];
+    __shared__ int sout[LETKF_BLOCK];
+    const int E = a.o.nmem, kx = a.o.kx, ncol = a.o.ncol, tid = threadIdx.x, opb = LETKF_BLOCK / E;
+    const int slot = tid / E, e = tid - slot * E, o = blockIdx.x * opb + slot;
+    const bool act = slot < opb && o < a.o.nobs;
+    double h = 0.0;
+    if (act) {
+        const int v = a.o.var[o], lev = a.o.lev[o];
+        const bool atp = a.atp[o] != 0;
+        // the variable's field by selects: a pointer array indexed per lane would go to scratch
+        const double *const xv = v == 0 ? a.o.x[0] : v == 1 ? a.o.x[1] : v == 2 ? a.o.x[2] : v == 3 ? a.o.x[3] : a.o.x[4];
+        const int kl = v < 4 ? kx : 1;                             // levels of the field: ps has one
+        const double *const f = xv + (size_t)e * kl * ncol;
+        const double *const pse = a.o.x[4] + (size_t)e * ncol;
+        int idx[4];
+        double w[4], ps[4], f0[4], f1[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            idx[s] = a.o.sidx[4 * (size_t)o + s];
+            w[s] = a.o.swgt[4 * (size_t)o + s];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) ps[s] = pse[idx[s]];
+        const double xo = a.lnp[o], l0 = a.lv.lev[0];
+        VBracket b[4];
+        vinterp_brackets<true, 4>(a.lv, ps, xo, b);
+        int out = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
+            f0[s] = f[(size_t)k0 * ncol + idx[s]];
+            f1[s] = f[(size_t)k1 * ncol + idx[s]];
+            out |= (atp && (xo < vinterp_coord<true>(ps[s], l0) || (b[s].cls & VINTERP_BELOW))) ? 1 : 0;
+            b[s].cls = atp ? b[s].cls : VINTERP_LO;                // a model level: f0's bits
+        }
+        double z[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
+        h = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
+        a.o.hx[(size_t)o * E + e] = h;
+        shx[tid] = h;
+        spb[tid] = ((w[0] * ps[0] + w[1] * ps[1]) + w[2] * ps[2]) + w[3] * ps[3];
+        sout[tid] = out;
+    }
+    __syncthreads();
+    const int o1 = blockIdx.x * opb + tid;
+    if (tid < opb && o1 < a.o.nobs) {
+        double sum = 0.0, psum = 0.0;
+        int out = 0;
+        for (int m = 0; m < E; ++m) {
+            sum += shx[tid * E + m];
+            psum += spb[tid * E + m];
+            out |= sout[tid * E + m];
+        }
+        const double mean = sum / E;
+        smean[tid] = mean;
+        a.o.hxmean[o1] = mean;
+        a.o.dep[o1] = a.o.value[o1] - mean;
+        if (a.atp[o1] != 0) a.olns[o1] = a.lnp[o1] - psum / E;
+        a.used[o1] = out ? 0.0 : 1.0;
+        a.reff[o1] = out ? 0.0 : a.rinv[o1];
+    }
+    __syncthreads();
+    if (act) a.o.y[(size_t)o * E + e] = h - smean[slot];
+}
+
 // LIST = false: one workgroup per grid column, which gets its increments.  LIST = true (weight interpolation): workgroup b solves
 // grid column cols[b] and writes T of every level to tw, [b][k][f][e] with e fastest, and no increments.  Two instantiations, no
 // run-time branch: the first form is the kernel it was before the second existed.
@@ -405,6 +481,21 @@ hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s)
     if (!a.nobs) return hipSuccess;
     if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.value) return hipErrorInvalidValue;
     hipLaunchKernelGGL(letkf_obs_kernel, dim3((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s)
+{
+    const LetkfObs &o = a.o;
+    if (o.nobs < 0 || o.nmem < 2 || o.nmem > LETKF_MAX_MEMBERS || o.kx < 2 || o.kx > VINTERP_KMAX || a.lv.kx != o.kx || o.ncol < 1 ||
+        !o.hx || !o.hxmean || !o.y || !o.dep)
+        return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!o.x[v]) return hipErrorInvalidValue;
+    if (!o.nobs) return hipSuccess;
+    if (!o.var || !o.lev || !o.sidx || !o.swgt || !o.value || !a.atp || !a.lnp || !a.rinv || !a.olns || !a.used || !a.reff) return hipErrorInvalidValue;
+    const int opb = LETKF_BLOCK / o.nmem;
+    hipLaunchKernelGGL(letkf_pobs_kernel, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -32,6 +32,47 @@ __global__ __launch_bounds__(NATURE_BLOCK) void nature_draw_kernel(const NatureO
     a.value[o] = h + (a.noise * a.error[o]) * z;
 }
 
+// nature_draw_kernel for a network with observations given at a pressure (atp != 0): the four columns' values at the target by
+// csrc/spdy_vinterp.hpp's rule with the truth's ps, clamped to the end level outside the column; an observation on a model level
+// or of ps goes the same way with its bracket replaced by {lev, the level's own bits}.  One thread per observation: one member.
+__global__ __launch_bounds__(NATURE_BLOCK) void nature_pdraw_kernel(const NatureObs a, const int *const atpo, const double *const lnp, const VLevels lv)
+{
+#pragma clang fp contract(off)
+    const int o = blockIdx.x * NATURE_BLOCK + threadIdx.x;
+    if (o >= a.nobs) return;
+    const int v = a.var[o], lev = a.lev[o], kl = v < 4 ? a.kx : 1;
+    const bool atp = atpo[o] != 0;
+    const double *const f = a.truth + (size_t)v * a.kx * a.ncol, *const pst = a.truth + (size_t)4 * a.kx * a.ncol;
+    int idx[4];
+    double w[4], ps[4], f0[4], f1[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        idx[s] = a.sidx[4 * (size_t)o + s];
+        w[s] = a.swgt[4 * (size_t)o + s];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) ps[s] = pst[idx[s]];
+    VBracket b[4];
+    vinterp_brackets<true, 4>(lv, ps, lnp[o], b);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
+        f0[s] = f[(size_t)k0 * a.ncol + idx[s]];
+        f1[s] = f[(size_t)k1 * a.ncol + idx[s]];
+        b[s].cls = atp ? b[s].cls : VINTERP_LO;
+    }
+    double z[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
+    const double h = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
+    if (a.noise == 0.0) {
+        a.value[o] = h;
+        return;
+    }
+    const double zz = sppt_randn((unsigned)o, 0u, a.state[1], a.state[0]);
+    a.value[o] = h + (a.noise * a.error[o]) * zz;
+}
+
 __global__ void nature_count_kernel(unsigned long long *state)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) state[1] = state[1] + 1;
@@ -116,6 +157,16 @@ hipError_t launch_nature_draw(const NatureObs &a, hipStream_t s)
     if (!a.nobs) return hipSuccess;
     if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nature_draw_kernel, dim3((a.nobs + NATURE_BLOCK - 1) / NATURE_BLOCK), dim3(NATURE_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_nature_pdraw(const NatureObs &a, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s)
+{
+    if (a.nobs < 0 || a.kx < 2 || a.kx > VINTERP_KMAX || lv.kx != a.kx || a.ncol < 1 || !a.truth || !a.state || !a.value || !(a.noise >= 0.0))
+        return hipErrorInvalidValue;
+    if (!a.nobs) return hipSuccess;
+    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error || !atp || !lnp) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nature_pdraw_kernel, dim3((a.nobs + NATURE_BLOCK - 1) / NATURE_BLOCK), dim3(NATURE_BLOCK), 0, s, a, atp, lnp, lv);
     return hipGetLastError();
 }
 

@@ -147,13 +147,21 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     std::vector<double> lat, lnfsg;       // [il] latitudes in degrees, south first; [kx] ln fsg
     std::vector<int> h_sidx;              // the tables of spdy_letkf_table
     std::vector<double> h_swgt, h_unit, h_lns, h_rinv;
+    // observations at a pressure (spdy_pobs_set): how many of the current network are, and ln(p/p0) of each (0 for the others);
+    // h_lnp is empty after spdy_letkf_set_obs
+    int npobs = 0;
+    std::vector<double> h_lnp;
     double *d_base = nullptr;
     double *d_grid = nullptr, *d_spec = nullptr;   // (4kx+1) nmem grids u | v | t | q | ps, and as many spectra
     double *d_colunit = nullptr, *d_lnfsg = nullptr;
     double *d_swgt = nullptr, *d_ounit = nullptr, *d_olns = nullptr, *d_rinv = nullptr, *d_value = nullptr;
     double *d_err = nullptr;              // [max_obs] the errors set_obs was given, next to rinv (spdy_nature_observe_dev reads them)
     double *d_hx = nullptr, *d_hxmean = nullptr, *d_y = nullptr, *d_dep = nullptr;
+    // [max_obs] each: ln(p/p0) of the at-pressure observations; 1.0 / 0.0, the observation took part in the latest analysis call;
+    // the 1/error^2 that call's transform kernel read (0 where it did not) -- written by letkf_pobs_kernel only
+    double *d_lnp = nullptr, *d_used = nullptr, *d_reff = nullptr;
     int *d_sidx = nullptr, *d_var = nullptr, *d_lev = nullptr;
+    int *d_atp = nullptr;                 // [max_obs] 1: the observation is at a pressure (its d_lev is 0); written by spdy_pobs_set only
     // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
     int si = 1, sj = 1;
     std::vector<int> h_coarse, h_iidx;    // [ncoarse] grid columns, ascending; [ncol][4] entries of that list
@@ -164,8 +172,8 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     void forget_device() override
     {
         d_base = d_grid = d_spec = d_colunit = d_lnfsg = d_swgt = d_ounit = d_olns = d_rinv = d_value = nullptr;
-        d_hx = d_hxmean = d_y = d_dep = d_wbase = d_tw = d_iwgt = d_err = nullptr;
-        d_sidx = d_var = d_lev = d_iidx = d_coarse = nullptr;
+        d_hx = d_hxmean = d_y = d_dep = d_wbase = d_tw = d_iwgt = d_err = d_lnp = d_used = d_reff = nullptr;
+        d_sidx = d_var = d_lev = d_atp = d_iidx = d_coarse = nullptr;
     }
 };
 

@@ -86,6 +86,12 @@ module spdy_c
         real(c_double) :: lon = 0.0_c_double, lat = 0.0_c_double, value = 0.0_c_double, error = 1.0_c_double
     end type
 
+    !> spdy_pobs (include/spdy.h, "observations at a pressure"): spdy_obs with p in Pa, read where lev = SPDY_OBS_AT_P
+    type, bind(C) :: spdy_pobs
+        integer(c_int) :: var = 0_c_int, lev = 0_c_int
+        real(c_double) :: p = 0.0_c_double, lon = 0.0_c_double, lat = 0.0_c_double, value = 0.0_c_double, error = 1.0_c_double
+    end type
+
     interface
         function spdy_plan_create(trunc, ix, iy, kx, max_batch, device, plan) bind(C, name="spdy_plan_create") result(rc)
             import :: c_int, c_ptr
@@ -1199,6 +1205,13 @@ module spdy_c
             integer(c_int), value :: nobs
             integer(c_int) :: rc
         end function
+        ! host is c_loc of an array of spdy_pobs: observations that may be given at a pressure (lev = SPDY_OBS_AT_P, p in Pa)
+        function spdy_pobs_set(l, nobs, host) bind(C, name="spdy_pobs_set") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, host
+            integer(c_int), value :: nobs
+            integer(c_int) :: rc
+        end function
         function spdy_letkf_set_weight_stride(l, si, sj) bind(C, name="spdy_letkf_set_weight_stride") result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: l
@@ -1291,6 +1304,7 @@ module spdy_c
 
     integer(c_int), parameter :: SPDY_OBS_U = 0_c_int, SPDY_OBS_V = 1_c_int, SPDY_OBS_T = 2_c_int, SPDY_OBS_Q = 3_c_int, &
         & SPDY_OBS_PS = 4_c_int                                !! spdy_obs%var (include/spdy.h)
+    integer(c_int), parameter :: SPDY_OBS_AT_P = -1_c_int      !! spdy_pobs%lev: the observation sits at p (include/spdy.h)
     integer(c_int), parameter :: SPDY_DEVICE_AUTO = -2_c_int   !! $SPDY_DEVICE, else the launcher's local rank (include/spdy.h)
     integer(c_int), parameter :: SPDY_MAX_PLEV = 32_c_int, SPDY_PLEV_LINEAR_P = 0_c_int, SPDY_PLEV_LOG_P = 1_c_int
                                                                !! pressure-level output: the level count's bound, coord (include/spdy.h)

@@ -5,7 +5,8 @@ A Letkf belongs to a plan and an ensemble size.  One analysis: set_obs(...), the
 ensemble; fields() gives the observation-space quantities of that call, so observation-minus-background statistics need no
 second operator.  weight_stride=(si, sj) solves the local problems on every si-th longitude and sj-th row only and gives the
 other columns the bilinear interpolation of those columns' transforms (one launch more); (1, 1), the default, solves every column.
-After an analysis the run continues
+set_obs(..., p=...) takes observations of u, v, t or q given at a pressure (lev == OBS_AT_P): they are interpolated in the vertical
+per member, linearly in ln p (include/spdy.h, "observations at a pressure").  After an analysis the run continues
 with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled: build the analysis ensemble from
 members the guard has not stopped, a non-finite member makes every column it touches non-finite."""
 import ctypes
@@ -16,13 +17,19 @@ from ._lib import check
 from .columns import DeviceField, PlanObject
 
 OBS_U, OBS_V, OBS_T, OBS_Q, OBS_PS = range(5)
-LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv", "coarse_columns", "interp_index", "interp_weight")
-LETKF_FIELDS = ("hx", "hxmean", "y", "departure", "weights", "value", "grid")
+OBS_AT_P = -1                         # SPDY_OBS_AT_P: as lev, the observation sits at the pressure p
+LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv", "coarse_columns", "interp_index", "interp_weight", "lnp")
+LETKF_FIELDS = ("hx", "hxmean", "y", "departure", "weights", "value", "grid", "obs_lnsigma", "obs_used")
 
 
 class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
     _fields_ = [("var", ctypes.c_int), ("lev", ctypes.c_int), ("lon", ctypes.c_double), ("lat", ctypes.c_double),
                 ("value", ctypes.c_double), ("error", ctypes.c_double)]
+
+
+class PObs(ctypes.Structure):         # spdy_pobs (include/spdy.h)
+    _fields_ = [("var", ctypes.c_int), ("lev", ctypes.c_int), ("p", ctypes.c_double), ("lon", ctypes.c_double),
+                ("lat", ctypes.c_double), ("value", ctypes.c_double), ("error", ctypes.c_double)]
 
 
 class _DeviceView:
@@ -68,22 +75,37 @@ class Letkf(PlanObject):
         check(rc)
         self.weight_stride = (int(si), int(sj))
 
-    def set_obs(self, var, lev, lon, lat, value, error):
+    def set_obs(self, var, lev, lon, lat, value, error, p=None):
         """The observations of the next analysis, arrays of one length (0 .. max_obs): var OBS_U .. OBS_PS, lev 0 .. kx-1 (ignored
         for OBS_PS), lon, lat in degrees, value and error in the model's units (q in g/kg, ps as log(p/p0)).  Every field is
-        validated before anything changes.  Synchronises the plan's stream; not inside a capture."""
-        cols = [np.atleast_1d(np.asarray(a)) for a in (var, lev, lon, lat, value, error)]
+        validated before anything changes.  Synchronises the plan's stream; not inside a capture.
+        p (spdy_pobs_set; include/spdy.h, "observations at a pressure"): an array of pressures in Pa of the same length; an
+        observation of u, v, t or q with lev == OBS_AT_P then sits at its p (finite, > 0) and is interpolated in the vertical,
+        linearly in ln p, member by member; the others are as without p, their p is ignored.  An at-pressure observation that is
+        above the top level or below the lowest one of any member at any of its four points takes no part in that analysis
+        (field("obs_used")).  Without an at-pressure observation the object is left exactly as without p."""
+        names = (var, lev, lon, lat, value, error) + (() if p is None else (p,))
+        cols = [np.atleast_1d(np.asarray(a)) for a in names]
         n = cols[0].shape[0]
         if any(c.ndim != 1 or c.shape[0] != n for c in cols):
-            raise ValueError("set_obs: var, lev, lon, lat, value, error must be one-dimensional arrays of one length")
+            raise ValueError("set_obs: var, lev, lon, lat, value, error%s must be one-dimensional arrays of one length"
+                             % ("" if p is None else ", p"))
         if n > self.max_obs:
             raise ValueError("set_obs: %d observations, the object holds %d" % (n, self.max_obs))
-        obs = (Obs * max(n, 1))()
-        for o in range(n):
-            obs[o] = Obs(int(cols[0][o]), int(cols[1][o]), float(cols[2][o]), float(cols[3][o]), float(cols[4][o]), float(cols[5][o]))
+        if p is None:
+            obs = (Obs * max(n, 1))()
+            for o in range(n):
+                obs[o] = Obs(int(cols[0][o]), int(cols[1][o]), float(cols[2][o]), float(cols[3][o]), float(cols[4][o]), float(cols[5][o]))
+            call = self.lib.spdy_letkf_set_obs
+        else:
+            obs = (PObs * max(n, 1))()
+            for o in range(n):
+                obs[o] = PObs(int(cols[0][o]), int(cols[1][o]), float(cols[6][o]), float(cols[2][o]), float(cols[3][o]),
+                              float(cols[4][o]), float(cols[5][o]))
+            call = self.lib.spdy_pobs_set
         if self.sp.device >= 0:
             self.sp._sync_stream()
-        rc = self.lib.spdy_letkf_set_obs(self.h, n, ctypes.cast(obs, ctypes.c_void_p))
+        rc = call(self.h, n, ctypes.cast(obs, ctypes.c_void_p))
         if rc == -4:                  # SPDY_ERR_HIP: a copy failed, the object holds no observations now
             self.nobs = 0
         check(rc)
@@ -91,7 +113,9 @@ class Letkf(PlanObject):
 
     def table(self, name):
         """A host table of the current observations (LETKF_TABLES): stencil_index [nobs, 4] (grid points j*ix+i, int64),
-        stencil_weight [nobs, 4], unit [nobs, 3], lnsigma [nobs], rinv [nobs]; or of the weight interpolation: coarse_columns
+        stencil_weight [nobs, 4], unit [nobs, 3], lnsigma [nobs] (ln(p/p0) for an observation at a pressure: its value at ps = 0),
+        rinv [nobs], lnp [nobs] (ln(p/p0) of the observations at a pressure, 0 for the others; empty after a set_obs without p);
+        or of the weight interpolation: coarse_columns
         [ncoarse] (grid columns j*ix+i, int64, ascending), interp_index [ncol, 4] (entries of coarse_columns, int64; an entry of
         weight zero repeats the first), interp_weight [ncol, 4]; all three are empty at stride (1, 1)."""
         out = self._table(name)
@@ -107,7 +131,9 @@ class Letkf(PlanObject):
         coarse columns, at a weight stride other than (1, 1) only; set_weight_stride moves it.  value [nobs]: the observation values
         the next analysis reads, as set_obs or Nature.observe wrote them (valid at once, not only after an analysis).  grid
         [(4 kx + 1) nmem, il, ix]: the grid workspace, u | v | t | q (nmem kx grids each, member-major) | ps (nmem) -- the gridded
-        ensemble after Nature.verify, the increments after Ensemble.analyse."""
+        ensemble after Nature.verify, the increments after Ensemble.analyse.  obs_lnsigma [nobs]: ln sigma_o the latest analysis
+        call localised with (for an observation at a pressure ln(p/p0) minus the ensemble-mean ps at its place, formed in that
+        call); obs_used [nobs]: 1.0, or 0.0 for an at-pressure observation that was out of some member's column in that call."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         if name == "weights":

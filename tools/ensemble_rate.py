@@ -38,7 +38,10 @@ the whole physics, whose 36 replays are the model side of one six-hour cycle.  E
 repeat the replays analyse the state the replay before left.  --stride SI SJ sets the analysis' weight stride (one launch more:
 the local problems on the coarse columns, then the kernel that interpolates their transforms to every column); the row then has
 the number of coarse columns and the byte count of that kernel's reads -- per grid column and level one E x E transform per
-stencil entry of non-zero weight, and the members' values -- to set against its time from a kernel trace.
+stencil entry of non-zero weight, and the members' values -- to set against its time from a kernel trace.  --at-pressure adds the
+analysis of the same stations with u, v, t and q given at the pressures p0 fsg[k] instead of on the levels k (include/spdy.h,
+"observations at a pressure"): the observation kernel that interpolates per member in the plain one's place, the
+same launch count; the row has the number of observations that are in column on the starting state.
 
 --osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
 to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
@@ -63,6 +66,7 @@ float32 grids written; and the surface-pressure row.
     python tools/ensemble_rate.py --sppt --json profiles/ensemble_sppt_rate.json
     python tools/ensemble_rate.py --letkf --json profiles/ensemble_letkf_rate.json
     python tools/ensemble_rate.py --letkf --stride 2 2
+    python tools/ensemble_rate.py --letkf --at-pressure --members 4 32 --json profiles/ensemble_letkf_pobs_rate.json
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
     python tools/ensemble_rate.py --pressure --json profiles/ensemble_pressure_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
@@ -559,9 +563,10 @@ def host_observations(sp, lt, tr, cols, err, repeats):
     return float(np.median(us[1:])), min(us[1:]), max(us[1:])
 
 
-def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False):
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
-    of the nature run's observe and verify, and the host route to the same observation values"""
+    of the nature run's observe and verify, and the host route to the same observation values; at_pressure: and of the analysis of
+    the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
     build()
@@ -587,7 +592,7 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
     cols = [np.tile(var, nloc), np.tile(lev, nloc), np.repeat(lon.ravel(), per), np.repeat(lat.ravel(), per)]
     nobs = nloc * per
     rng = np.random.default_rng(0)
-    fns, nodes, rearms, keep, interp, host = {}, {}, [], [], {}, {}
+    fns, nodes, rearms, keep, interp, host, used, pressure_objects = {}, {}, [], [], {}, {}, {}, []
     for E in members:
         # the members: the case's state plus a hundredth of the differences between seeded states (0.3 K in t)
         ms = ensemblestep.member_states(sp, E + 1)
@@ -613,6 +618,20 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
         with sp.graph_capture() as g:
             en.analyse(lt)
         fns["analysis E=%d" % E], nodes["analysis E=%d" % E] = g.launch, g.num_nodes()
+        if at_pressure:
+            ltp = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, **({} if stride == (1, 1) else {"weight_stride": stride}))
+            ltp.set_obs(cols[0], np.where(cols[0] == 4, 0, s.OBS_AT_P), cols[2], cols[3], lt.field("value").numpy(), spread,
+                        p=1.0e5 * sp.table("fsg")[cols[1]])
+            en.analyse(ltp)                                   # once eagerly: how many of them are in column on this state
+            torch.cuda.synchronize()
+            used[E] = int(ltp.field("obs_used").numpy().sum())
+            for n, v in start.items():
+                getattr(en, n).copy_(v)
+            torch.cuda.synchronize()
+            with sp.graph_capture() as gp:
+                en.analyse(ltp)
+            fns["analysis at p E=%d" % E], nodes["analysis at p E=%d" % E] = gp.launch, gp.num_nodes()
+            pressure_objects.append((ltp, gp))
         if stride != (1, 1):
             terms = int(np.count_nonzero(lt.table("interp_weight")))
             interp[E] = {"coarse_columns": int(lt.table("coarse_columns").size),
@@ -646,6 +665,8 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                "us_min": round(lo, 2), "us_max": round(hi, 2)}
         if name.startswith("analysis"):
             row.update(stride=list(stride), **interp.get(E, {}))
+            if name.startswith("analysis at p"):
+                row.update(observations_in_column=used[E])
             cycle = 36 * t["step E=%d physics" % E][0]
             row.update(us_36_steps=round(cycle, 1), analysis_share_of_cycle=round(med / (med + cycle), 4))
         if name.startswith(("observe", "verify")):
@@ -660,6 +681,8 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
         print(json.dumps(row), flush=True)
     for _, lt, _, g, gs in keep:
         g.close(); gs.close(); lt.close()
+    for ltp, gp in pressure_objects:
+        gp.close(); ltp.close()
     sp.close()
 
 
@@ -673,6 +696,7 @@ def main():
     ap.add_argument("--sppt", action="store_true")
     ap.add_argument("--letkf", action="store_true")
     ap.add_argument("--osse", action="store_true")
+    ap.add_argument("--at-pressure", action="store_true")
     ap.add_argument("--pressure", action="store_true")
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
@@ -696,7 +720,7 @@ def main():
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
             if a.letkf:
-                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse)
+                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure)
             elif a.pressure:
                 run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:
