@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPDY_LIB") or os.path.join(HERE, "libspdy.so")   # SPDY_LIB: an alternative build (experiments)
 
 c_void_p, c_int, c_double, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_char_p
+ERR_HIP = -4                          # SPDY_ERR_HIP (include/spdy.h): a HIP runtime call failed
 
 # name -> argtypes (restype is int everywhere except spdy_last_error)
 SIGNATURES = {

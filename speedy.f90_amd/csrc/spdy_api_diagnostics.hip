@@ -98,11 +98,7 @@ int spdy_ens_diagnostics_create(spdy_plan *p, int nmem, int capacity, long long 
     if (p->device < 0) return SPDY_OK;
     auto cleanup = [&](int rc) { spdy_diagnostics_destroy(d); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
-    const size_t nhist = (size_t)capacity * nmem * row_doubles(d);
-    const size_t bytes = (nhist + 4) * sizeof(double) + levels(d) * sizeof(spdy::DiagLevel);
-    if (int rc = dev_alloc(p, bytes, &d->d_history)) return cleanup(rc);
-    d->d_limits = d->d_history + nhist;
-    d->d_state = reinterpret_cast<spdy::DiagLevel *>(d->d_limits + 4);
+    if (int rc = dev_carve(p, [&](auto &&v) { d->arrays(v, (size_t)p->tab.kx); })) return cleanup(rc);
     int rc = upload_limits(d, nullptr);
     if (!rc) rc = restart(d, first_step);
     return rc ? cleanup(rc) : SPDY_OK;

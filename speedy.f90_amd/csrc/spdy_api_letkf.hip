@@ -1,6 +1,7 @@
 // C ABI of the ensemble analysis (include/spdy.h, "ensemble analysis"): the observation ingestion on the host, the
 // analysis of a gridded ensemble, the five-launch analysis of an ensemble's spectral state, and the tables and the buffer of weight
 // interpolation (one launch more).  Kernels: csrc/spdy_letkf.hip.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -82,8 +83,7 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
         // those observations into olns and this call's copy of rinv, 0 where an observation is out of its column
         spdy::LetkfPObs po{};
         po.o = o; po.atp = l->d_atp; po.lnp = l->d_lnp; po.rinv = l->d_rinv; po.olns = l->d_olns; po.used = l->d_used; po.reff = l->d_reff;
-        po.lv.kx = kx;
-        for (int k = 0; k < kx; ++k) po.lv.lev[k] = l->lnfsg[k];
+        po.lv = l->lv;
         c.rinv = l->d_reff;
         KERNEL(spdy::launch_letkf_pobs(po, p->stream));
     } else {
@@ -94,7 +94,7 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
         return SPDY_OK;
     }
     // weight interpolation: T of the coarse columns, then the increments of every column from them
-    c.nlist = (int)l->h_coarse.size(); c.cols = l->d_coarse; c.tw = l->d_tw;
+    c.nlist = (int)l->interp.coarse.size(); c.cols = l->d_coarse; c.tw = l->d_tw;
     spdy::LetkfApply ap{};
     ap.nmem = l->nmem; ap.kx = kx; ap.ncol = ncol; ap.nlist = c.nlist;
     ap.iidx = l->d_iidx; ap.iwgt = l->d_iwgt; ap.tw = l->d_tw;
@@ -105,17 +105,17 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
 }
 
 // the coarse columns of a stride and every grid column's stencil in them (include/spdy.h, "ensemble analysis": weight interpolation)
-void interp_tables(int ix, int il, int si, int sj, std::vector<int> &coarse, std::vector<int> &idx, std::vector<double> &wgt)
+spdy_letkf::InterpTables interp_tables(int ix, int il, int si, int sj)
 {
+    spdy_letkf::InterpTables tab;
     std::vector<int> rows;                    // the coarse rows, ascending: 0, sj, 2 sj, ... and il - 1
     for (int j = 0; j < il - 1; j += sj) rows.push_back(j);
     rows.push_back(il - 1);
     const int ni = ix / si;
-    coarse.clear();
     for (int j : rows)
-        for (int i = 0; i < ix; i += si) coarse.push_back(j * ix + i);
-    idx.assign((size_t)4 * ix * il, 0);
-    wgt.assign((size_t)4 * ix * il, 0.0);
+        for (int i = 0; i < ix; i += si) tab.coarse.push_back(j * ix + i);
+    tab.iidx.assign((size_t)4 * ix * il, 0);
+    tab.iwgt.assign((size_t)4 * ix * il, 0.0);
     size_t r0 = 0;                            // rows[r0] is the largest coarse row <= j
     for (int j = 0; j < il; ++j) {
         while (r0 + 1 < rows.size() && rows[r0 + 1] <= j) ++r0;
@@ -132,20 +132,20 @@ void interp_tables(int ix, int il, int si, int sj, std::vector<int> &coarse, std
             for (int n = 0; n < 4 && first < 0; ++n)
                 if (w[n] != 0.0) first = e[n];
             for (int n = 0; n < 4; ++n) {
-                wgt[at + n] = w[n];
-                idx[at + n] = w[n] != 0.0 ? e[n] : first;      // an entry that is not read repeats the first one that is
+                tab.iwgt[at + n] = w[n];
+                tab.iidx[at + n] = w[n] != 0.0 ? e[n] : first;      // an entry that is not read repeats the first one that is
             }
         }
     }
+    return tab;
 }
 
 void drop_interp(spdy_letkf *l)
 {
-    (void)dev_release(l->plan, l->d_wbase);
-    l->d_wbase = l->d_tw = l->d_iwgt = nullptr;
-    l->d_iidx = l->d_coarse = nullptr;
+    (void)dev_release(l->plan, l->d_tw);
+    l->interp_arrays(Carve{});
     l->si = l->sj = 1;
-    l->h_coarse.clear(); l->h_iidx.clear(); l->h_iwgt.clear();
+    l->interp = {};
 }
 
 // an observation of either entry point as the ingestion reads it
@@ -184,45 +184,47 @@ int ingest(spdy_letkf *l, int nobs, const OBS *host, const char *call, const cha
     NOT_CAPTURING(p, what);
     const size_t n = (size_t)nobs;
     const double p0 = static_cast<double>(1.e+5f);
-    std::vector<int> sidx(4 * n), var(n), lev(n), atp(PRES ? n : 0);
-    std::vector<double> swgt(4 * n), unit(3 * n), lns(n), rinv(n), err(n), value(n), lnp(PRES ? n : 0);
+    std::vector<int> var(n), lev(n), atp(PRES ? n : 0);
+    std::vector<double> err(n), value(n);
+    spdy_letkf::ObsTables tab;                // the object's next tables: moved in once every copy has succeeded
+    tab.sidx.resize(4 * n); tab.swgt.resize(4 * n); tab.unit.resize(3 * n); tab.lns.resize(n); tab.rinv.resize(n); tab.lnp.resize(PRES ? n : 0);
     // obs_used is all ones from create on; only an analysis of a network with at-pressure observations writes anything else
     const bool reset_used = p->device >= 0 && (PRES || l->npobs > 0);
     std::vector<double> ones(reset_used ? n : 0, 1.0);
     int npobs = 0;
     for (size_t o = 0; o < n; ++o) {
         const OBS &b = host[o];
-        stencil(l, b.lon, b.lat, &sidx[4 * o], &swgt[4 * o]);
-        unit_vector(b.lon, b.lat, &unit[3 * o]);
+        stencil(l, b.lon, b.lat, &tab.sidx[4 * o], &tab.swgt[4 * o]);
+        unit_vector(b.lon, b.lat, &tab.unit[3 * o]);
         var[o] = b.var;
         if (at_p(b)) {
             lev[o] = 0;                                   // the device's level stays a level: atp marks the observation
             atp[o] = 1;
-            lnp[o] = lns[o] = std::log(pressure_of(b) / p0);      // ln sigma_o at ps = 0; the analysis call forms its own
+            tab.lnp[o] = tab.lns[o] = std::log(pressure_of(b) / p0);      // ln sigma_o at ps = 0; the analysis call forms its own
             ++npobs;
         } else {
             lev[o] = b.var == SPDY_OBS_PS ? 0 : b.lev;
-            lns[o] = b.var == SPDY_OBS_PS ? 0.0 : l->lnfsg[b.lev];
+            tab.lns[o] = b.var == SPDY_OBS_PS ? 0.0 : l->lv.lev[b.lev];
         }
-        rinv[o] = 1.0 / (b.error * b.error);
+        tab.rinv[o] = 1.0 / (b.error * b.error);
         err[o] = b.error;
         value[o] = b.value;
     }
     if (p->device >= 0) {
         HIP_TRY(hipSetDevice(p->device));
         auto all = [&]() -> int {
-            RC(upload(p, l->d_sidx, sidx.data(), 4 * n * sizeof(int)));
+            RC(upload(p, l->d_sidx, tab.sidx.data(), 4 * n * sizeof(int)));
             RC(upload(p, l->d_var, var.data(), n * sizeof(int)));
             RC(upload(p, l->d_lev, lev.data(), n * sizeof(int)));
-            RC(upload(p, l->d_swgt, swgt.data(), 4 * n * sizeof(double)));
-            RC(upload(p, l->d_ounit, unit.data(), 3 * n * sizeof(double)));
-            RC(upload(p, l->d_olns, lns.data(), n * sizeof(double)));
-            RC(upload(p, l->d_rinv, rinv.data(), n * sizeof(double)));
+            RC(upload(p, l->d_swgt, tab.swgt.data(), 4 * n * sizeof(double)));
+            RC(upload(p, l->d_ounit, tab.unit.data(), 3 * n * sizeof(double)));
+            RC(upload(p, l->d_olns, tab.lns.data(), n * sizeof(double)));
+            RC(upload(p, l->d_rinv, tab.rinv.data(), n * sizeof(double)));
             RC(upload(p, l->d_err, err.data(), n * sizeof(double)));
             RC(upload(p, l->d_value, value.data(), n * sizeof(double)));
             if (reset_used) { RC(upload(p, l->d_used, ones.data(), n * sizeof(double))); }
             if (PRES) {
-                RC(upload(p, l->d_lnp, lnp.data(), n * sizeof(double)));
+                RC(upload(p, l->d_lnp, tab.lnp.data(), n * sizeof(double)));
                 RC(upload(p, l->d_atp, atp.data(), n * sizeof(int)));
             }
             HIP_TRY(hipStreamSynchronize(p->stream));
@@ -232,16 +234,23 @@ int ingest(spdy_letkf *l, int nobs, const OBS *host, const char *call, const cha
             // the device tables may be partly new: the object holds no observations now, and no copy is still reading the host
             // arrays when they go
             (void)hipStreamSynchronize(p->stream);
-            l->nobs = 0; l->npobs = 0;
-            l->h_sidx.clear(); l->h_swgt.clear(); l->h_unit.clear(); l->h_lns.clear(); l->h_rinv.clear(); l->h_lnp.clear();
+            l->nobs = 0; l->npobs = 0; l->obs = {};
             return rc;
         }
     }
     l->nobs = nobs; l->npobs = npobs;
-    l->h_sidx.swap(sidx); l->h_swgt.swap(swgt); l->h_unit.swap(unit); l->h_lns.swap(lns); l->h_rinv.swap(rinv); l->h_lnp.swap(lnp);
+    l->obs = std::move(tab);
     return SPDY_OK;
 }
 }  // namespace
+
+int spdy_detail::ens_to_grid(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q, const double *ps, double *g)
+{
+    const int nk = nmem * p->tab.kx;
+    const size_t L = (size_t)nk * grid_elems(p);
+    const spdy_spec_seg segs[3] = {{nk, t}, {nk, q}, {nmem, ps}};
+    return spdy_inverse_batch_segs_dev(p, nk, vor, div, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2);
+}
 
 extern "C" {
 
@@ -273,40 +282,15 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
         const int h = j < t.iy ? j : il - 1 - j;
         l->lat[j] = (j < t.iy ? -std::asin(t.sia_half[h]) : std::asin(t.sia_half[h])) * (180.0 / kPi);
     }
-    l->lnfsg.resize(kx);
-    for (int k = 0; k < kx; ++k) l->lnfsg[k] = std::log(t.fsg[k]);
+    l->lv.kx = kx;
+    for (int k = 0; k < kx; ++k) l->lv.lev[k] = std::log(t.fsg[k]);
     *out = l;
     if (p->device < 0) return SPDY_OK;
     auto cleanup = [&](int rc) { spdy_letkf_destroy(l); *out = nullptr; return rc; };
     if (hipSetDevice(p->device) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "hipSetDevice failed"));
-    const size_t ncol = grid_elems(p), nf = (size_t)(4 * kx + 1) * nmem, M = (size_t)(max_obs > 0 ? max_obs : 1), E = (size_t)nmem;
-    // doubles: grids | spectra | colunit | lnfsg | swgt | ounit | olns | rinv | err | value | hx | hxmean | y | dep | lnp | used |
-    // reff ; then the ints
-    const size_t nd = nf * ncol + nf * spec_elems(p) + 3 * ncol + (size_t)kx + M * (4 + 3 + 1 + 1 + 1 + 1 + 1 + 1 + 2 * E + 3), ni = 7 * M;
-    if (int rc = dev_alloc(p, nd * sizeof(double) + ni * sizeof(int), &l->d_base)) return cleanup(rc);
-    double *d = l->d_base;
-    l->d_grid = d; d += nf * ncol;
-    l->d_spec = d; d += nf * spec_elems(p);
-    l->d_colunit = d; d += 3 * ncol;
-    l->d_lnfsg = d; d += kx;
-    l->d_swgt = d; d += 4 * M;
-    l->d_ounit = d; d += 3 * M;
-    l->d_olns = d; d += M;
-    l->d_rinv = d; d += M;
-    l->d_err = d; d += M;
-    l->d_value = d; d += M;
-    l->d_hx = d; d += M * E;
-    l->d_hxmean = d; d += M;
-    l->d_y = d; d += M * E;
-    l->d_dep = d; d += M;
-    l->d_lnp = d; d += M;
-    l->d_used = d; d += M;
-    l->d_reff = d; d += M;
-    int *q = reinterpret_cast<int *>(d);
-    l->d_sidx = q; q += 4 * M;
-    l->d_var = q; q += M;
-    l->d_lev = q; q += M;
-    l->d_atp = q;
+    const size_t ncol = grid_elems(p), M = (size_t)(max_obs > 0 ? max_obs : 1);
+    size_t bytes = 0;
+    if (int rc = dev_carve(p, [&](auto &&v) { l->arrays(v, ncol, spec_elems(p), kx); }, &bytes)) return cleanup(rc);
     std::vector<double> cu(3 * ncol);
     for (int j = 0; j < il; ++j)
         for (int i = 0; i < ix; ++i) {
@@ -315,10 +299,10 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
             for (int c = 0; c < 3; ++c) cu[c * ncol + (size_t)j * ix + i] = u[c];
         }
     const std::vector<double> ones(M, 1.0);   // obs_used: spdy_letkf_set_obs never has to write it
-    if (hipMemsetAsync(l->d_base, 0, nd * sizeof(double) + ni * sizeof(int), p->stream) != hipSuccess ||
+    if (hipMemsetAsync(l->d_grid, 0, bytes, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_used, ones.data(), M * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_colunit, cu.data(), cu.size() * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
-        hipMemcpyAsync(l->d_lnfsg, l->lnfsg.data(), kx * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+        hipMemcpyAsync(l->d_lnfsg, l->lv.lev, kx * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipStreamSynchronize(p->stream) != hipSuccess)
         return cleanup(fail(SPDY_ERR_HIP, "letkf_create: upload failed"));
     if (spdy::letkf_prepare(l->lds) != hipSuccess) return cleanup(fail(SPDY_ERR_HIP, "letkf_create: %zu bytes of LDS refused", l->lds));
@@ -328,8 +312,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
     const size_t L = (size_t)nk * ncol, LS = (size_t)nk * spec_elems(p);
     double *g = l->d_grid, *s = l->d_spec;
     int rc = ensure_four(p);
-    const spdy_spec_seg segs[3] = {{nk, s + 2 * LS}, {nk, s + 3 * LS}, {nmem, s + 4 * LS}};
-    if (!rc) rc = spdy_inverse_batch_segs_dev(p, nk, s, s + LS, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2);
+    if (!rc) rc = ens_to_grid(p, nmem, s, s + LS, s + 2 * LS, s + 3 * LS, s + 4 * LS, g);
     if (!rc) rc = spdy_direct_batch_dev(p, nk, g, g + L, s, s + LS, 2, 2 * nk + nmem, g + 2 * L, s + 2 * LS);
     if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(SPDY_ERR_HIP, "letkf_create: the first transforms failed");
     return rc ? cleanup(rc) : SPDY_OK;
@@ -338,7 +321,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
 int spdy_letkf_destroy(spdy_letkf *l)
 {
     if (!l) return SPDY_OK;
-    retire(l, {l->d_wbase, l->d_base});
+    retire(l, {l->d_tw, l->d_grid});
     delete l;
     return SPDY_OK;
 }
@@ -373,23 +356,16 @@ int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
     NOT_CAPTURING(p, "spdy_letkf_set_weight_stride (allocation + upload)");
     drop_interp(l);
     if (si == 1 && sj == 1) return SPDY_OK;
-    std::vector<int> coarse, idx;
-    std::vector<double> wgt;
-    interp_tables(ix, il, si, sj, coarse, idx, wgt);
+    spdy_letkf::InterpTables tab = interp_tables(ix, il, si, sj);
     if (p->device >= 0) {
         HIP_TRY(hipSetDevice(p->device));
-        const size_t nc = coarse.size(), ncol = grid_elems(p), ntw = nc * kx * l->nmem * l->nmem;
-        const size_t bytes = (ntw + 4 * ncol) * sizeof(double) + (4 * ncol + nc) * sizeof(int);
-        RC(dev_alloc(p, bytes, &l->d_wbase));
-        l->d_tw = l->d_wbase;
-        l->d_iwgt = l->d_tw + ntw;
-        l->d_iidx = reinterpret_cast<int *>(l->d_iwgt + 4 * ncol);
-        l->d_coarse = l->d_iidx + 4 * ncol;
+        const size_t nc = tab.coarse.size(), ncol = grid_elems(p), ntw = nc * kx * l->nmem * l->nmem;
+        RC(dev_carve(p, [&](auto &&v) { l->interp_arrays(v, nc, ncol, kx); }));
         auto all = [&]() -> int {
             HIP_TRY(hipMemsetAsync(l->d_tw, 0, ntw * sizeof(double), p->stream));
-            RC(upload(p, l->d_iwgt, wgt.data(), 4 * ncol * sizeof(double)));
-            RC(upload(p, l->d_iidx, idx.data(), 4 * ncol * sizeof(int)));
-            RC(upload(p, l->d_coarse, coarse.data(), nc * sizeof(int)));
+            RC(upload(p, l->d_iwgt, tab.iwgt.data(), 4 * ncol * sizeof(double)));
+            RC(upload(p, l->d_iidx, tab.iidx.data(), 4 * ncol * sizeof(int)));
+            RC(upload(p, l->d_coarse, tab.coarse.data(), nc * sizeof(int)));
             HIP_TRY(hipStreamSynchronize(p->stream));
             return SPDY_OK;
         };
@@ -399,7 +375,7 @@ int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
         }
     }
     l->si = si; l->sj = sj;
-    l->h_coarse.swap(coarse); l->h_iidx.swap(idx); l->h_iwgt.swap(wgt);
+    l->interp = std::move(tab);
     return SPDY_OK;
 }
 
@@ -407,34 +383,34 @@ int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap
 {
     NEED_LIVE(l, "analysis object");
     if (!name) return fail(SPDY_ERR_ARG, "null table name");
-    const std::vector<int> *index = !std::strcmp(name, "stencil_index") ? &l->h_sidx : !std::strcmp(name, "coarse_columns") ? &l->h_coarse
-                                    : !std::strcmp(name, "interp_index") ? &l->h_iidx : nullptr;
-    const std::vector<double> *v = !std::strcmp(name, "stencil_weight") ? &l->h_swgt : !std::strcmp(name, "unit") ? &l->h_unit
-                                   : !std::strcmp(name, "lnsigma") ? &l->h_lns : !std::strcmp(name, "rinv") ? &l->h_rinv
-                                   : !std::strcmp(name, "interp_weight") ? &l->h_iwgt : !std::strcmp(name, "lnp") ? &l->h_lnp : nullptr;
-    if (!index && !v) return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
-    const int n = static_cast<int>(index ? index->size() : v->size());
-    if (buf && cap < n) return fail(SPDY_ERR_ARG, "analysis table '%s' has %d values, the buffer %d", name, n, cap);
-    if (buf && index)
-        for (int i = 0; i < n; ++i) buf[i] = (*index)[i];
-    else if (buf && n)
-        std::memcpy(buf, v->data(), sizeof(double) * (size_t)n);
-    return n;
+    const struct { const char *name; const std::vector<int> *index; const std::vector<double> *v; } tables[] = {
+        {"stencil_index", &l->obs.sidx, nullptr}, {"coarse_columns", &l->interp.coarse, nullptr}, {"interp_index", &l->interp.iidx, nullptr},
+        {"stencil_weight", nullptr, &l->obs.swgt}, {"unit", nullptr, &l->obs.unit}, {"lnsigma", nullptr, &l->obs.lns},
+        {"rinv", nullptr, &l->obs.rinv}, {"interp_weight", nullptr, &l->interp.iwgt}, {"lnp", nullptr, &l->obs.lnp}};
+    auto give = [&](const auto &v) {          // the table as doubles, whichever it holds
+        const int n = static_cast<int>(v.size());
+        if (buf && cap < n) return fail(SPDY_ERR_ARG, "analysis table '%s' has %d values, the buffer %d", name, n, cap);
+        if (buf) std::copy(v.begin(), v.end(), buf);
+        return n;
+    };
+    for (const auto &t : tables)
+        if (!std::strcmp(name, t.name)) return t.index ? give(*t.index) : give(*t.v);
+    return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
 }
 
 int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
 {
     NEED_LIVE(l, "analysis object");
     if (!name || !d_ptr) return fail(SPDY_ERR_ARG, "null name or result pointer");
-    double *const *f = !std::strcmp(name, "hx") ? &l->d_hx : !std::strcmp(name, "hxmean") ? &l->d_hxmean
-                       : !std::strcmp(name, "y") ? &l->d_y : !std::strcmp(name, "departure") ? &l->d_dep
-                       : !std::strcmp(name, "weights") ? &l->d_tw : !std::strcmp(name, "value") ? &l->d_value
-                       : !std::strcmp(name, "grid") ? &l->d_grid : !std::strcmp(name, "obs_lnsigma") ? &l->d_olns
-                       : !std::strcmp(name, "obs_used") ? &l->d_used : nullptr;
-    if (!f) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
-    if (f == &l->d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
+    static const struct { const char *name; double *spdy_letkf::*ptr; } fields[] = {
+        {"hx", &spdy_letkf::d_hx}, {"hxmean", &spdy_letkf::d_hxmean}, {"y", &spdy_letkf::d_y}, {"departure", &spdy_letkf::d_dep},
+        {"weights", &spdy_letkf::d_tw}, {"value", &spdy_letkf::d_value}, {"grid", &spdy_letkf::d_grid},
+        {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}};
+    const auto *f = std::find_if(std::begin(fields), std::end(fields), [&](const auto &t) { return !std::strcmp(name, t.name); });
+    if (f == std::end(fields)) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
+    if (f->ptr == &spdy_letkf::d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
     NEED_DEVICE(l->plan);
-    *d_ptr = *f;
+    *d_ptr = l->*(f->ptr);
     return SPDY_OK;
 }
 
@@ -454,9 +430,7 @@ int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, doubl
     const int kx = p->tab.kx, nmem = l->nmem, nk = nmem * kx;
     const size_t L = (size_t)nk * grid_elems(p), LS = (size_t)nk * spec_elems(p);
     double *g = l->d_grid, *s = l->d_spec;
-    // time level 1 of all members to the grid, read in place: nmem*kx pairs (true wind), the segments t | q | ps
-    const spdy_spec_seg segs[3] = {{nk, t}, {nk, q}, {nmem, ps}};
-    RC(spdy_inverse_batch_segs_dev(p, nk, vor, div, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2));
+    RC(ens_to_grid(p, nmem, vor, div, t, q, ps, g));
     // the increments take the place of the gridded ensemble
     double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
     RC(analyse_grid(l, x, x));

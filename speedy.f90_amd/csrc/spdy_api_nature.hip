@@ -20,16 +20,6 @@ int need_pair(spdy_nature *n, spdy_letkf *l)
     return SPDY_OK;
 }
 
-// time level 1 of nmem states to the grid, read in place: the call spdy_ens_letkf_dev makes (nmem * kx pairs as true wind, the
-// segments t | q | ps), into g = u | v | t | q | ps
-int to_grid(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q, const double *ps, double *g)
-{
-    const int nk = nmem * p->tab.kx;
-    const size_t L = (size_t)nk * grid_elems(p);
-    const spdy_spec_seg segs[3] = {{nk, t}, {nk, q}, {nmem, ps}};
-    return spdy_inverse_batch_segs_dev(p, nk, vor, div, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2);
-}
-
 // the scores of a gridded ensemble x = u | v | t | q | ps into scores[slot]: two launches
 int score(spdy_nature *n, int nmem, const double *const *x, int slot)
 {
@@ -83,17 +73,9 @@ int spdy_nature_create(spdy_plan *p, unsigned long long seed, int capacity, spdy
     }
     for (int j = 0; j < il; ++j) gw[j] /= sum;
     const size_t ncol = grid_elems(p), ns = spec_elems(p);
-    // doubles: truth | zero spectra of the first transform | part | gw | scores ; then the two state words
-    const size_t nd = nf * ncol + nf * ns + (size_t)nf * il * 3 + il + (size_t)capacity * 3 * nf;
-    if (int rc = dev_alloc(p, nd * sizeof(double) + 2 * sizeof(unsigned long long), &n->d_base)) return cleanup(rc);
-    double *d = n->d_base;
-    n->d_truth = d; d += nf * ncol;
-    double *const s = d; d += nf * ns;
-    n->d_part = d; d += (size_t)nf * il * 3;
-    n->d_gw = d; d += il;
-    n->d_scores = d; d += (size_t)capacity * 3 * nf;
-    n->d_state = reinterpret_cast<unsigned long long *>(d);
-    if (hipMemsetAsync(n->d_base, 0, nd * sizeof(double) + 2 * sizeof(unsigned long long), p->stream) != hipSuccess ||
+    size_t bytes = 0;
+    if (int rc = dev_carve(p, [&](auto &&v) { n->arrays(v, (size_t)nf, ncol, ns, (size_t)il); }, &bytes)) return cleanup(rc);
+    if (hipMemsetAsync(n->d_truth, 0, bytes, p->stream) != hipSuccess ||
         hipMemcpyAsync(n->d_gw, gw.data(), il * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess)
         return cleanup(fail(SPDY_ERR_HIP, "nature_create: upload failed"));
     int rc = restart(n, seed);
@@ -101,7 +83,8 @@ int spdy_nature_create(spdy_plan *p, unsigned long long seed, int capacity, spdy
     // size exists before a capture (verify's shape is the analysis object's, which its create has run)
     if (!rc) rc = ensure_four(p);
     const size_t LS = (size_t)kx * ns;
-    if (!rc) rc = to_grid(p, 1, s, s + LS, s + 2 * LS, s + 3 * LS, s + 4 * LS, n->d_truth);
+    const double *s = n->d_zero;
+    if (!rc) rc = ens_to_grid(p, 1, s, s + LS, s + 2 * LS, s + 3 * LS, s + 4 * LS, n->d_truth);
     if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(SPDY_ERR_HIP, "nature_create: the first transform failed");
     return rc ? cleanup(rc) : SPDY_OK;
 }
@@ -109,7 +92,7 @@ int spdy_nature_create(spdy_plan *p, unsigned long long seed, int capacity, spdy
 int spdy_nature_destroy(spdy_nature *n)
 {
     if (!n) return SPDY_OK;
-    retire(n, {n->d_base});
+    retire(n, {n->d_truth});
     delete n;
     return SPDY_OK;
 }
@@ -153,7 +136,7 @@ int spdy_nature_set_state_dev(spdy_nature *n, const double *vor, const double *d
     if (!vor || !div || !t || !q || !ps) return fail(SPDY_ERR_ARG, "null device pointer");
     spdy_plan *p = n->plan;
     NEED_DEVICE(p);
-    return to_grid(p, 1, vor, div, t, q, ps, n->d_truth);
+    return ens_to_grid(p, 1, vor, div, t, q, ps, n->d_truth);
 }
 
 int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *l, double noise)
@@ -168,10 +151,7 @@ int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *l, double noise)
     o.truth = n->d_truth; o.state = n->d_state; o.noise = noise; o.value = l->d_value;
     if (l->npobs) {
         // observations at a pressure: the draw kernel that interpolates the truth's columns, in nature_draw_kernel's place
-        spdy::VLevels lv{};
-        lv.kx = o.kx;
-        for (int k = 0; k < o.kx; ++k) lv.lev[k] = l->lnfsg[k];
-        KERNEL(spdy::launch_nature_pdraw(o, l->d_atp, l->d_lnp, lv, p->stream));
+        KERNEL(spdy::launch_nature_pdraw(o, l->d_atp, l->d_lnp, l->lv, p->stream));
     } else {
         KERNEL(spdy::launch_nature_draw(o, p->stream));
     }
@@ -190,7 +170,7 @@ int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *l, const double *vor, con
     const int nmem = l->nmem;
     const size_t L = (size_t)nmem * p->tab.kx * grid_elems(p);
     double *g = l->d_grid;
-    RC(to_grid(p, nmem, vor, div, t, q, ps, g));
+    RC(ens_to_grid(p, nmem, vor, div, t, q, ps, g));
     const double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
     return score(n, nmem, x, slot);
 }

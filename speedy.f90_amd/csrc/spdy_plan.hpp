@@ -32,6 +32,24 @@ protected:
 
 // A device workspace allocated at its first use and grown when a larger one is asked for (ensure_workspace).
 struct Workspace { double *g = nullptr; size_t doubles = 0; };
+
+// An object that keeps several arrays in one device allocation (diagnostics, analysis, nature run) declares them once, in a
+// member template `arrays(v, counts...)` that calls v(pointer member, element count) for each array in memory order.  Carve is
+// the visitor: it hands out array after array from `base`, or null pointers without one (forget_device; the counts default to 0
+// where only the pointers matter), adds up the bytes and notes an array that would start off its element's alignment
+// (dev_carve).  The first array is the allocation's base, what retire and dev_release are given.  Adding an array to such an
+// object: the member and its line in `arrays`; its upload if it has one; its public name if it has one.
+struct Carve {
+    char *base = nullptr;
+    size_t bytes = 0;
+    bool aligned = true;
+    template <class T> void operator()(T *&ptr, size_t n)
+    {
+        aligned = aligned && bytes % alignof(T) == 0;
+        ptr = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
+        bytes += n * sizeof(T);
+    }
+};
 }  // namespace spdy_detail
 
 struct spdy_plan {
@@ -125,7 +143,7 @@ struct spdy_sppt final : spdy_detail::PlanObject {
     void forget_device() override { d_state = nullptr; d_sigma = d_eta = d_spec = d_pattern = nullptr; }
 };
 
-// The run's guard behind include/spdy.h's spdy_diagnostics (csrc/spdy_api_diagnostics.hip): one device allocation, history | limits | state.
+// The run's guard behind include/spdy.h's spdy_diagnostics (csrc/spdy_api_diagnostics.hip): one device allocation.
 struct spdy_diagnostics final : spdy_detail::PlanObject {
     int capacity = 0;
     int nmem = 1;                         // members checked by one launch (spdy_ens_diagnostics_create)
@@ -133,7 +151,11 @@ struct spdy_diagnostics final : spdy_detail::PlanObject {
     double *d_history = nullptr;          // [capacity][nmem][3][kx]
     double *d_limits = nullptr;           // reke, deke, temp low, temp high: shared by the members
     spdy::DiagLevel *d_state = nullptr;   // [nmem][kx]
-    void forget_device() override { d_history = d_limits = nullptr; d_state = nullptr; }
+    template <class V> void arrays(V &&v, size_t kx = 0)
+    {
+        v(d_history, (size_t)capacity * nmem * 3 * kx); v(d_limits, 4); v(d_state, (size_t)nmem * kx);
+    }
+    void forget_device() override { arrays(spdy_detail::Carve{}); }
 };
 
 // The ensemble analysis behind include/spdy.h's spdy_letkf (csrc/spdy_api_letkf.hip): the observation tables on the host, and
@@ -144,14 +166,12 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     size_t lds = 0;                       // dynamic LDS of the transform kernel
     double sigma_h = 0.0, sigma_v = 0.0, rho = 1.0;
     bool loc_set = false;
-    std::vector<double> lat, lnfsg;       // [il] latitudes in degrees, south first; [kx] ln fsg
-    std::vector<int> h_sidx;              // the tables of spdy_letkf_table
-    std::vector<double> h_swgt, h_unit, h_lns, h_rinv;
-    // observations at a pressure (spdy_pobs_set): how many of the current network are, and ln(p/p0) of each (0 for the others);
-    // h_lnp is empty after spdy_letkf_set_obs
-    int npobs = 0;
-    std::vector<double> h_lnp;
-    double *d_base = nullptr;
+    std::vector<double> lat;              // [il] latitudes in degrees, south first
+    spdy::VLevels lv{};                   // [kx] ln fsg, as the at-pressure kernels take it as an argument
+    // the tables of spdy_letkf_table of the current network, replaced as one value (spdy_letkf_set_obs, spdy_pobs_set); lnp:
+    // ln(p/p0) of each observation at a pressure (0 for the others), empty after spdy_letkf_set_obs
+    struct ObsTables { std::vector<int> sidx; std::vector<double> swgt, unit, lns, rinv, lnp; } obs;
+    int npobs = 0;                        // how many observations of the current network are at a pressure (spdy_pobs_set)
     double *d_grid = nullptr, *d_spec = nullptr;   // (4kx+1) nmem grids u | v | t | q | ps, and as many spectra
     double *d_colunit = nullptr, *d_lnfsg = nullptr;
     double *d_swgt = nullptr, *d_ounit = nullptr, *d_olns = nullptr, *d_rinv = nullptr, *d_value = nullptr;
@@ -162,32 +182,44 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     double *d_lnp = nullptr, *d_used = nullptr, *d_reff = nullptr;
     int *d_sidx = nullptr, *d_var = nullptr, *d_lev = nullptr;
     int *d_atp = nullptr;                 // [max_obs] 1: the observation is at a pressure (its d_lev is 0); written by spdy_pobs_set only
+    // the main allocation: the doubles, then the ints; ncol, ns: elements of a grid and of a spectrum
+    template <class V> void arrays(V &&v, size_t ncol = 0, size_t ns = 0, size_t kx = 0)
+    {
+        const size_t nf = (4 * kx + 1) * nmem, M = max_obs > 0 ? max_obs : 1, E = nmem;
+        v(d_grid, nf * ncol); v(d_spec, nf * ns); v(d_colunit, 3 * ncol); v(d_lnfsg, kx);
+        v(d_swgt, 4 * M); v(d_ounit, 3 * M); v(d_olns, M); v(d_rinv, M); v(d_err, M); v(d_value, M);
+        v(d_hx, M * E); v(d_hxmean, M); v(d_y, M * E); v(d_dep, M);
+        v(d_lnp, M); v(d_used, M); v(d_reff, M);
+        v(d_sidx, 4 * M); v(d_var, M); v(d_lev, M); v(d_atp, M);
+    }
     // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
     int si = 1, sj = 1;
-    std::vector<int> h_coarse, h_iidx;    // [ncoarse] grid columns, ascending; [ncol][4] entries of that list
-    std::vector<double> h_iwgt;           // [ncol][4]
-    double *d_wbase = nullptr;            // one allocation: tw | iwgt | iidx | coarse
+    // coarse [ncoarse] grid columns, ascending; iidx [ncol][4] entries of that list; iwgt [ncol][4]
+    struct InterpTables { std::vector<int> coarse, iidx; std::vector<double> iwgt; } interp;
     double *d_tw = nullptr, *d_iwgt = nullptr;     // [ncoarse][kx][nmem][nmem]; [ncol][4]
     int *d_iidx = nullptr, *d_coarse = nullptr;
-    void forget_device() override
+    template <class V> void interp_arrays(V &&v, size_t ncoarse = 0, size_t ncol = 0, size_t kx = 0)
     {
-        d_base = d_grid = d_spec = d_colunit = d_lnfsg = d_swgt = d_ounit = d_olns = d_rinv = d_value = nullptr;
-        d_hx = d_hxmean = d_y = d_dep = d_wbase = d_tw = d_iwgt = d_err = d_lnp = d_used = d_reff = nullptr;
-        d_sidx = d_var = d_lev = d_atp = d_iidx = d_coarse = nullptr;
+        v(d_tw, ncoarse * kx * nmem * nmem); v(d_iwgt, 4 * ncol); v(d_iidx, 4 * ncol); v(d_coarse, ncoarse);
     }
+    void forget_device() override { arrays(spdy_detail::Carve{}); interp_arrays(spdy_detail::Carve{}); }
 };
 
-// The nature run behind include/spdy.h's spdy_nature (csrc/spdy_api_nature.hip): one device allocation, truth | zero spectra |
-// zonal partial sums | normalised Gaussian weights | scores | state.
+// The nature run behind include/spdy.h's spdy_nature (csrc/spdy_api_nature.hip): one device allocation.
 struct spdy_nature final : spdy_detail::PlanObject {
     int capacity = 0;
-    double *d_base = nullptr;
     double *d_truth = nullptr;            // (4 kx + 1) grids u | v | t | q (kx each) | ps
+    double *d_zero = nullptr;             // (4 kx + 1) zero spectra: what create's first transform reads
     double *d_part = nullptr;             // [4 kx + 1][il][3] zonal sums of a verify call
     double *d_gw = nullptr;               // [il] Gaussian weights / their sum, south first
     double *d_scores = nullptr;           // [capacity][3][4 kx + 1]
     unsigned long long *d_state = nullptr;   // {seed, draws}
-    void forget_device() override { d_base = d_truth = d_part = d_gw = d_scores = nullptr; d_state = nullptr; }
+    template <class V> void arrays(V &&v, size_t nf = 0, size_t ncol = 0, size_t ns = 0, size_t il = 0)
+    {
+        v(d_truth, nf * ncol); v(d_zero, nf * ns); v(d_part, nf * il * 3); v(d_gw, il); v(d_scores, (size_t)capacity * 3 * nf);
+        v(d_state, 2);
+    }
+    void forget_device() override { arrays(spdy_detail::Carve{}); }
 };
 
 namespace spdy_detail {
@@ -202,6 +234,19 @@ template <class T> int dev_alloc(spdy_plan *p, size_t bytes, T **out)
     void *ptr = nullptr;
     const int rc = dev_alloc(p, bytes, &ptr);
     *out = static_cast<T *>(ptr);
+    return rc;
+}
+// One dev_alloc for the arrays that walk(visitor) visits, handed out in the walk's order; refused (SPDY_ERR_ARG) if an array
+// would start off its element's alignment.  *bytes: the allocation's size (for the caller's memset).
+template <class Walk> int dev_carve(spdy_plan *p, Walk &&walk, size_t *bytes = nullptr)
+{
+    Carve sum;
+    walk(sum);
+    if (!sum.aligned) return fail(SPDY_ERR_ARG, "dev_carve: an array of the allocation would be misaligned");
+    char *base = nullptr;
+    const int rc = dev_alloc(p, sum.bytes, &base);
+    if (!rc) walk(Carve{base});
+    if (bytes) *bytes = sum.bytes;
     return rc;
 }
 // w holds at least `doubles` doubles afterwards: NEED_DEVICE, nothing to do if it is large enough, NOT_CAPTURING(p, what),
@@ -232,6 +277,9 @@ int direct_batch_raw63(spdy_plan *p, int npairs, const double *ug, const double 
 bool use_raw63(const spdy_plan *p, int npairs);   // whether a step's direct batch of npairs (u, v) pairs takes that route
 // the plain spectra of nseg segments (kcos 1) -> ONE grid stack, as one launch of the fused inverse kernels (spdy_moist_physics_dev)
 int inverse_plain_one(spdy_plan *p, int nseg, const spdy_spec_seg *segs, double *grid);
+// time level 1 of nmem members (vor, div, t, q [nmem][kx] spectra, ps [nmem], read in place) to the grid stack g = u | v | t | q |
+// ps: one inverse batch, nmem * kx pairs as true wind next to the segments t | q | ps (spdy_api_letkf.hip; the nature run's too)
+int ens_to_grid(spdy_plan *p, int nmem, const double *vor, const double *div, const double *t, const double *q, const double *ps, double *g);
 int upload_level_tables(spdy_plan *p);
 void release_comms(spdy_plan *p);     // plan teardown: RCCL communicators of this plan are shut down, their handles stay valid but dead
 

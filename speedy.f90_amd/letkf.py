@@ -13,13 +13,22 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check
+from ._lib import ERR_HIP, check
 from .columns import DeviceField, PlanObject
 
 OBS_U, OBS_V, OBS_T, OBS_Q, OBS_PS = range(5)
 OBS_AT_P = -1                         # SPDY_OBS_AT_P: as lev, the observation sits at the pressure p
-LETKF_TABLES = ("stencil_index", "stencil_weight", "unit", "lnsigma", "rinv", "coarse_columns", "interp_index", "interp_weight", "lnp")
-LETKF_FIELDS = ("hx", "hxmean", "y", "departure", "weights", "value", "grid", "obs_lnsigma", "obs_used")
+# host table -> (dtype, shape); -1: what the library's count leaves
+_TABLES = {"stencil_index": (np.int64, (-1, 4)), "stencil_weight": (np.float64, (-1, 4)), "unit": (np.float64, (-1, 3)),
+           "lnsigma": (np.float64, (-1,)), "rinv": (np.float64, (-1,)), "coarse_columns": (np.int64, (-1,)),
+           "interp_index": (np.int64, (-1, 4)), "interp_weight": (np.float64, (-1, 4)), "lnp": (np.float64, (-1,))}
+_PER_OBS, _PER_OBS_MEMBER = (lambda l: (l.nobs,)), (lambda l: (l.nobs, l.nmem))
+# device field -> the shape of a Letkf's, all float64
+_FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "departure": _PER_OBS,
+           "weights": lambda l: (check(l.lib.spdy_letkf_table(l.h, b"coarse_columns", None, 0)), l.sp.kx, l.nmem, l.nmem),
+           "value": _PER_OBS, "grid": lambda l: ((4 * l.sp.kx + 1) * l.nmem,) + l.sp.grid_shape,
+           "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS}
+LETKF_TABLES, LETKF_FIELDS = tuple(_TABLES), tuple(_FIELDS)
 
 
 class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
@@ -70,7 +79,7 @@ class Letkf(PlanObject):
         if self.sp.device >= 0:
             self.sp._sync_stream()
         rc = self.lib.spdy_letkf_set_weight_stride(self.h, int(si), int(sj))
-        if rc == -4:                  # SPDY_ERR_HIP: the object is left at stride (1, 1)
+        if rc == ERR_HIP:             # the object is left at stride (1, 1)
             self.weight_stride = (1, 1)
         check(rc)
         self.weight_stride = (int(si), int(sj))
@@ -106,7 +115,7 @@ class Letkf(PlanObject):
         if self.sp.device >= 0:
             self.sp._sync_stream()
         rc = call(self.h, n, ctypes.cast(obs, ctypes.c_void_p))
-        if rc == -4:                  # SPDY_ERR_HIP: a copy failed, the object holds no observations now
+        if rc == ERR_HIP:             # a copy failed, the object holds no observations now
             self.nobs = 0
         check(rc)
         self.nobs = n
@@ -118,12 +127,9 @@ class Letkf(PlanObject):
         or of the weight interpolation: coarse_columns
         [ncoarse] (grid columns j*ix+i, int64, ascending), interp_index [ncol, 4] (entries of coarse_columns, int64; an entry of
         weight zero repeats the first), interp_weight [ncol, 4]; all three are empty at stride (1, 1)."""
-        out = self._table(name)
-        if name in ("stencil_index", "interp_index"):
-            return out.astype(np.int64).reshape(-1, 4)
-        if name == "coarse_columns":
-            return out.astype(np.int64)
-        return out.reshape(-1, 4) if name in ("stencil_weight", "interp_weight") else out.reshape(-1, 3) if name == "unit" else out
+        out = self._table(name)           # an unknown name is the library's to refuse
+        dtype, shape = _TABLES[name]
+        return out.astype(dtype, copy=False).reshape(shape)
 
     def field(self, name):
         """A device field of the latest analysis call (LETKF_FIELDS): hx, y [nobs, nmem], hxmean, departure [nobs]; a DeviceField
@@ -136,12 +142,7 @@ class Letkf(PlanObject):
         call); obs_used [nobs]: 1.0, or 0.0 for an at-pressure observation that was out of some member's column in that call."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
-        if name == "weights":
-            ncoarse = check(self.lib.spdy_letkf_table(self.h, b"coarse_columns", None, 0))
-            return DeviceField(self.sp, p.value, (ncoarse, self.sp.kx, self.nmem, self.nmem))
-        if name == "grid":
-            return DeviceField(self.sp, p.value, ((4 * self.sp.kx + 1) * self.nmem,) + self.sp.grid_shape)
-        return DeviceField(self.sp, p.value, (self.nobs, self.nmem) if name in ("hx", "y") else (self.nobs,))
+        return DeviceField(self.sp, p.value, _FIELDS[name](self))
 
     def fields(self):
         """{"hx": [nobs, nmem], "hxmean": [nobs], "departure": [nobs]} of the latest analysis call: float64 device tensors that

@@ -14,7 +14,9 @@ import ctypes
 from ._lib import check
 from .columns import DeviceField, PlanObject
 
-NATURE_FIELDS = ("truth", "scores", "state")
+_FIELDS = {"truth": lambda n: (4 * n.sp.kx + 1,) + n.sp.grid_shape, "scores": lambda n: (n.capacity, 3, 4 * n.sp.kx + 1),
+           "state": lambda n: (2,)}   # device field -> its shape for a Nature n, all float64
+NATURE_FIELDS = tuple(_FIELDS)
 SCORES = ("rmse", "bias", "spread")
 
 
@@ -90,9 +92,7 @@ class Nature(PlanObject):
         scores [capacity, 3, 4 kx + 1], state [2] (the words seed and draws, as the bits of two doubles)."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_nature_field(self.h, name.encode(), ctypes.byref(p)))
-        sp, nf = self.sp, 4 * self.sp.kx + 1
-        shape = (nf,) + sp.grid_shape if name == "truth" else (self.capacity, 3, nf) if name == "scores" else (2,)
-        return DeviceField(sp, p.value, shape)
+        return DeviceField(self.sp, p.value, _FIELDS[name](self))
 
     def truth(self):
         """{"u", "v", "t", "q": [kx, il, ix], "ps": [il, ix]} as NumPy (synchronising)"""

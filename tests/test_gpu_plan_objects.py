@@ -63,3 +63,32 @@ def test_plan_closed_before_its_objects_and_their_graph(oracle_factory):
     G = sp.spec_to_grid(S, 1)
     assert synth.relerr(G[0], oracle_factory("t30").spec_to_grid(S[0], 1)) <= TOL
     sp.close()
+
+
+def test_every_named_array_is_its_own():
+    """The analysis object, the nature run and the diagnostics object each keep their arrays in one device allocation (two with a
+    weight stride).  Every field a name reaches is filled over its full documented shape with values no other field holds, then all
+    are read back: each holds what was written to it, so no two arrays overlap, and every address is a multiple of 8.  nmem and
+    nobs = max_obs are odd, so the analysis object's int arrays start after an odd number of per-observation doubles."""
+    s = support.package()
+    kx, nmem, nobs = 5, 3, 5
+    sp = s.Spectral("t30", kx=kx, max_batch=64, device=0)
+    sp.set_sigma(np.linspace(0.0, 1.0, kx + 1) ** 1.5)
+    letkf = s.Letkf(sp, nmem, nobs, 1.0e6, weight_stride=(2, 2))
+    letkf.set_obs([s.OBS_T] * nobs, [2] * nobs, 30.0 * np.arange(nobs), 10.0 * np.arange(nobs) - 20.0, [250.0] * nobs, [1.0] * nobs)
+    nat = s.Nature(sp, capacity=3)
+    diag = s.Diagnostics(sp, capacity=3, nmem=nmem)
+    fields = [(o, n, o.field(n)) for o, names in ((letkf, s.letkf.LETKF_FIELDS), (nat, s.nature.NATURE_FIELDS), (diag, s.columns.DIAG_FIELDS))
+              for n in names]
+    fields = [(o, n, f) for o, n, f in fields if isinstance(f, s.DeviceField)]
+    assert len(fields) == len(s.letkf.LETKF_FIELDS) + len(s.nature.NATURE_FIELDS) + 2
+    assert letkf.field("hx").shape == (nobs, nmem) and letkf.field("weights").shape[1:] == (kx, nmem, nmem)
+    want = []
+    for k, (o, n, f) in enumerate(fields):
+        assert f.ptr % 8 == 0, (n, hex(f.ptr))
+        want.append(1.0e7 * (k + 1) + np.arange(int(np.prod(f.shape)), dtype=np.float64).reshape(f.shape))
+        f.upload(want[k])
+    for (o, n, f), w in zip(fields, want):
+        assert np.array_equal(o.field(n).numpy(), w), n
+    for o in (diag, nat, letkf, sp):
+        o.close()
