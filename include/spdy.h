@@ -1028,7 +1028,7 @@ int spdy_diagnostics_format(int kx, long long step, const double *row, char *buf
  * direct batch streams (16 MB of grids or more: spdy_direct_batch_dev then goes out as its two launches).  Time level 2
  * is not touched and phi is stale afterwards: the run continues with first_step, as a model started from an analysis does.
  * Members are coupled by construction: a non-finite member makes every column it touches non-finite (as NaN, after the full
- * count of sweeps), and there is no member mask -- the caller builds the analysis ensemble from members the guard has not stopped.
+ * count of sweeps); spdy_mask_ens_letkf_dev ("member mask" below) analyses the members a device mask names and leaves the others alone.
  * Weight interpolation (Yang, Kalnay, Hunt and Bowler 2009): T varies slowly in space, because the localisation function is smooth
  * over several grid spacings, so the local problems may be solved on a coarse subset of the columns only, and every other column
  * gets T by bilinear interpolation from the four coarse columns around it.
@@ -1135,6 +1135,48 @@ typedef struct {
 } spdy_pobs;
 int spdy_pobs_set(spdy_letkf *l, int nobs, const spdy_pobs *host);
 
+/* ---- ensemble analysis and scores, member mask --------------------------------------------------------------------
+ * The guard stops a member that leaves the range, and the output takes a mask ("ensemble output"); with these calls the analysis and
+ * the scores do too, so a captured cycle keeps running when a member is lost.  d_use is nmem ints in device memory, non-zero = the
+ * member is in use; it is read by the kernels when they run, not when the call is enqueued; NULL = all members, and the call is then
+ * the unsuffixed one exactly: spdy_letkf_analyse_grid_dev, spdy_ens_letkf_dev, spdy_nature_verify_dev and
+ * spdy_nature_verify_grid_dev are these calls with d_use = NULL, and launch the kernels they always launched, in the same number,
+ * with the same bits.  Let U = (u_0 < u_1 < ... < u_{n-1}) be the members in use.
+ *   n >= 2        the call is "ensemble analysis" (and "observations at a pressure") applied to the n-member ensemble (x_{u_0}, ...,
+ *                 x_{u_{n-1}}), with every E of those definitions replaced by n: hxmean and Y over U ascending; A = (n-1)/rho I + C
+ *                 with (n-1)/rho one IEEE division; W with sqrt((n-1)/lambda); the padded size n rounded up to even and the
+ *                 round-robin order of that size; the means of the increment step over U; for an at-pressure network the
+ *                 out-of-column test and the mean ps of ln sigma_o over U only.  So the results for the members in use are bit
+ *                 for bit those of the unmasked call of an n-member object on the compacted members.
+ *   not in use    such a member enters no operation whose result reaches another member or any shared quantity: it is skipped by
+ *                 a select, never by a multiplication with zero, so it may hold NaN or anything else.  Its increments are written
+ *                 as exactly 0.0 over its grids (spdy_mask_ens_letkf_dev: in the workspace, so the kernel that adds the spectral
+ *                 increments leaves every bit of its spectra, NaN payloads included).  Its y is 0.0, its hx its own H x_e.
+ *   n < 2         zero increments for every member, the state keeps its bits; hxmean and departure are the sums the rule gives
+ *                 (n = 1: the member's own hx; n = 0: NaN, as the output's mean).
+ *   weights       at a weight stride the buffer keeps its shape [ncoarse][kx][nmem][nmem]; the leading n x n block of each matrix,
+ *                 in compact indices (f, e < n stand for u_f, u_e), is T, the rest is neither written nor read.
+ *   scores        mbar = (sum over U ascending) / n, s2 = sum / (n - 1); n = 1 gives spread +0, n = 0 NaN in all three.  A member
+ *                 not in use is never read into a score.
+ * spdy_letkf_field "members_used": one double, nmem after an unmasked analysis call and n after a masked one -- two words of the
+ * object's memory, the pointer is that of the kind of call enqueued (or captured) last, so ask after the call.
+ * spdy_mask_from_diagnostics_dev(d, d_use): d_use[e] = 1 if member e of the guard has no sticky first offence at any level, else 0
+ * (what spdy_ens_diagnostics_stopped reports as -1).  ONE launch, capturable, nothing allocated: {check_dev, this, masked verify,
+ * masked analysis} needs no host.
+ * Launches: a masked analysis call is its unmasked form with ONE small launch in front, which turns d_use into a table in the
+ * object's memory (n, U and every member's compact index) that the masked forms of the kernels read: three launches for
+ * spdy_mask_letkf_analyse_grid_dev (four at a weight stride), SIX for spdy_mask_ens_letkf_dev (seven at a weight stride; one more
+ * each where the direct batch streams).  The launch shapes, the levels in flight and the LDS request stay those of nmem; the LDS
+ * layout inside is that of n.  The masked verify calls read d_use as it is: three launches and two, as unmasked.  Nothing is
+ * allocated; a captured graph holds the pointer d_use, not its contents: writing new contents and replaying is the supported way
+ * to drop a member.  The calls carry a prefix of their own, spdy_mask_, not their objects' (DESIGN.md s23 says why).
+ * Checks: those of the unsuffixed call in its order (d_use cannot be checked on the host); spdy_mask_from_diagnostics_dev: a NULL
+ * object SPDY_ERR_ARG, a destroyed plan SPDY_ERR_STATE, a NULL d_use SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last.        */
+int spdy_mask_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg,
+                                     const double *psg, double *du, double *dv, double *dt, double *dq, double *dps, const int *d_use);
+int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use);
+int spdy_mask_from_diagnostics_dev(spdy_diagnostics *d, int *d_use);
+
 /* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
  * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
  * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a
@@ -1193,6 +1235,11 @@ int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *letkf, const double *vor,
                            const double *ps, int slot);
 int spdy_nature_verify_grid_dev(spdy_nature *n, int nmem, const double *ug, const double *vg, const double *tg, const double *qg,
                                 const double *psg, int slot);
+/* the two verify calls under a member mask ("member mask" above): d_use NULL = the calls above */
+int spdy_mask_nature_verify_dev(spdy_nature *n, spdy_letkf *letkf, const double *vor, const double *div, const double *t, const double *q,
+                                const double *ps, const int *d_use, int slot);
+int spdy_mask_nature_verify_grid_dev(spdy_nature *n, int nmem, const double *ug, const double *vg, const double *tg, const double *qg,
+                                     const double *psg, const int *d_use, int slot);
 
 /* ---- HIP graphs: replaying a fixed sequence of device-resident calls --------------------------------
  * A model step is the same sequence of small launches every time (tendencies.f90:89-107, :212-234,

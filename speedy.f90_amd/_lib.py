@@ -195,6 +195,11 @@ SIGNATURES = {
     "spdy_nature_observe_dev": [c_void_p, c_void_p, c_double],
     "spdy_nature_verify_dev": [c_void_p] * 7 + [c_int],
     "spdy_nature_verify_grid_dev": [c_void_p, c_int] + [c_void_p] * 5 + [c_int],
+    "spdy_mask_letkf_analyse_grid_dev": [c_void_p] * 12,
+    "spdy_mask_ens_letkf_dev": [c_void_p] * 7,
+    "spdy_mask_from_diagnostics_dev": [c_void_p, c_void_p],
+    "spdy_mask_nature_verify_dev": [c_void_p] * 8 + [c_int],
+    "spdy_mask_nature_verify_grid_dev": [c_void_p, c_int] + [c_void_p] * 6 + [c_int],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

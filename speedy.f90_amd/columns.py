@@ -407,6 +407,19 @@ class Diagnostics(PlanObject):
         check(self.lib.spdy_ens_diagnostics_stopped(self.h, bad))
         return list(bad)
 
+    def use_dev(self, out=None):
+        """The members' sticky records as a member mask (include/spdy.h, "member mask"): an int32 device tensor of nmem entries, 1
+        where the member has not tripped at any level (stopped() gives -1 there), else 0 -- what Ensemble.analyse, verify and
+        output take as `use`.  One launch and no synchronisation; capturable when `out` (such a tensor) is given."""
+        import torch
+        if out is None:
+            out = torch.empty(self.nmem, dtype=torch.int32, device="cuda:%d" % self.sp.device)
+        if not torch.is_tensor(out) or out.dtype != torch.int32 or out.numel() != self.nmem or not out.is_contiguous():
+            raise ValueError("use_dev: out must be %d contiguous int32 entries" % self.nmem)
+        self.sp._sync_stream()
+        check(self.lib.spdy_mask_from_diagnostics_dev(self.h, ctypes.c_void_p(out.data_ptr())))
+        return out
+
     def field(self, name):
         """"history" as a DeviceField [capacity, 3, kx] ([capacity, nmem, 3, kx] with nmem > 1 members), "limits" [4]; "state" as
         the device address (per-level records)."""

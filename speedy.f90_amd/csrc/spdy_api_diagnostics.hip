@@ -145,6 +145,16 @@ int spdy_diagnostics_check_dev(spdy_diagnostics *d, const double *vor, const dou
     return SPDY_OK;
 }
 
+int spdy_mask_from_diagnostics_dev(spdy_diagnostics *d, int *d_use)
+{
+    NEED_LIVE(d, "diagnostics object");
+    if (!d_use) return fail(SPDY_ERR_ARG, "mask_from_diagnostics_dev: null mask");
+    spdy_plan *p = d->plan;
+    NEED_DEVICE(p);
+    KERNEL(spdy::launch_diagnostics_use(d->d_state, d->nmem, p->tab.kx, d_use, p->stream));
+    return SPDY_OK;
+}
+
 int spdy_diagnostics_status(spdy_diagnostics *d, long long *next_step, long long *bad_step, int *bad_level, int *bad_mask, double *bad_row)
 {
     NEED_LIVE(d, "diagnostics object");

@@ -63,9 +63,13 @@ int analysis_ready(spdy_letkf *l, bool ptrs_ok)
     return SPDY_OK;
 }
 
-int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
+// d_use: NULL, or the member mask -- one launch more in front, which builds the table the masked forms of the kernels read
+int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const int *d_use = nullptr)
 {
     spdy_plan *p = l->plan;
+    const int *const umap = d_use ? l->d_umap : nullptr;
+    if (d_use) KERNEL(spdy::launch_letkf_mask(d_use, l->nmem, l->d_umap, l->d_nused + 1, p->stream));
+    l->masked_last = d_use != nullptr;
     const int kx = p->tab.kx, ncol = (int)grid_elems(p);
     spdy::LetkfObs o{};
     o.nobs = l->nobs; o.nmem = l->nmem; o.kx = kx; o.ncol = ncol;
@@ -83,24 +87,31 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx)
         // those observations into olns and this call's copy of rinv, 0 where an observation is out of its column
         spdy::LetkfPObs po{};
         po.o = o; po.atp = l->d_atp; po.lnp = l->d_lnp; po.rinv = l->d_rinv; po.olns = l->d_olns; po.used = l->d_used; po.reff = l->d_reff;
-        po.lv = l->lv;
+        po.lv = l->lv; po.umap = umap;
         c.rinv = l->d_reff;
         KERNEL(spdy::launch_letkf_pobs(po, p->stream));
+    } else if (umap) {
+        KERNEL(spdy::launch_letkf_obs_masked(o, umap, p->stream));
     } else {
         KERNEL(spdy::launch_letkf_obs(o, p->stream));
     }
-    if (!l->d_tw) {
-        KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
+    auto transform = [&]() -> int {
+        if (umap) {
+            KERNEL(spdy::launch_letkf_transform_masked(spdy::LetkfMaskedCols{c, l->rho, umap}, l->lds, p->stream));
+        } else {
+            KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
+        }
         return SPDY_OK;
-    }
+    };
+    if (!l->d_tw) return transform();
     // weight interpolation: T of the coarse columns, then the increments of every column from them
     c.nlist = (int)l->interp.coarse.size(); c.cols = l->d_coarse; c.tw = l->d_tw;
     spdy::LetkfApply ap{};
     ap.nmem = l->nmem; ap.kx = kx; ap.ncol = ncol; ap.nlist = c.nlist;
     ap.iidx = l->d_iidx; ap.iwgt = l->d_iwgt; ap.tw = l->d_tw;
     for (int v = 0; v < spdy::LETKF_VARS; ++v) { ap.x[v] = x[v]; ap.dx[v] = dx[v]; }
-    KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
-    KERNEL(spdy::launch_letkf_apply(ap, p->stream));
+    RC(transform());
+    KERNEL(spdy::launch_letkf_apply(ap, p->stream, umap));
     return SPDY_OK;
 }
 
@@ -299,7 +310,9 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
             for (int c = 0; c < 3; ++c) cu[c * ncol + (size_t)j * ix + i] = u[c];
         }
     const std::vector<double> ones(M, 1.0);   // obs_used: spdy_letkf_set_obs never has to write it
+    const double nused[2] = {(double)nmem, (double)nmem};      // members_used: all of them until a masked call says otherwise
     if (hipMemsetAsync(l->d_grid, 0, bytes, p->stream) != hipSuccess ||
+        hipMemcpyAsync(l->d_nused, nused, sizeof(nused), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_used, ones.data(), M * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_colunit, cu.data(), cu.size() * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
         hipMemcpyAsync(l->d_lnfsg, l->lv.lev, kx * sizeof(double), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
@@ -405,25 +418,37 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
     static const struct { const char *name; double *spdy_letkf::*ptr; } fields[] = {
         {"hx", &spdy_letkf::d_hx}, {"hxmean", &spdy_letkf::d_hxmean}, {"y", &spdy_letkf::d_y}, {"departure", &spdy_letkf::d_dep},
         {"weights", &spdy_letkf::d_tw}, {"value", &spdy_letkf::d_value}, {"grid", &spdy_letkf::d_grid},
-        {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}};
+        {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}, {"members_used", &spdy_letkf::d_nused}};
     const auto *f = std::find_if(std::begin(fields), std::end(fields), [&](const auto &t) { return !std::strcmp(name, t.name); });
     if (f == std::end(fields)) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f->ptr == &spdy_letkf::d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
     NEED_DEVICE(l->plan);
     *d_ptr = l->*(f->ptr);
+    if (f->ptr == &spdy_letkf::d_nused && l->masked_last) *d_ptr += 1;      // the count of the kind of call enqueued last
     return SPDY_OK;
 }
 
 int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
                                 double *du, double *dv, double *dt, double *dq, double *dps)
 {
+    return spdy_mask_letkf_analyse_grid_dev(l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps, nullptr);
+}
+
+int spdy_mask_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
+                                     double *du, double *dv, double *dt, double *dq, double *dps, const int *d_use)
+{
     RC(analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps));
     const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
     double *dx[spdy::LETKF_VARS] = {du, dv, dt, dq, dps};
-    return analyse_grid(l, x, dx);
+    return analyse_grid(l, x, dx, d_use);
 }
 
 int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps)
+{
+    return spdy_mask_ens_letkf_dev(l, vor, div, t, q, ps, nullptr);
+}
+
+int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use)
 {
     RC(analysis_ready(l, vor && div && t && q && ps));
     spdy_plan *p = l->plan;
@@ -433,7 +458,7 @@ int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, doubl
     RC(ens_to_grid(p, nmem, vor, div, t, q, ps, g));
     // the increments take the place of the gridded ensemble
     double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
-    RC(analyse_grid(l, x, x));
+    RC(analyse_grid(l, x, x, d_use));
     // vdspec(du, dv, 2) next to grid_to_spec(dt | dq | dps), then into the prognostics
     RC(spdy_direct_batch_dev(p, nk, g, g + L, s, s + LS, 2, 2 * nk + nmem, g + 2 * L, s + 2 * LS));
     spdy::LetkfAdd a{};

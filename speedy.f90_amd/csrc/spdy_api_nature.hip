@@ -20,13 +20,14 @@ int need_pair(spdy_nature *n, spdy_letkf *l)
     return SPDY_OK;
 }
 
-// the scores of a gridded ensemble x = u | v | t | q | ps into scores[slot]: two launches
-int score(spdy_nature *n, int nmem, const double *const *x, int slot)
+// the scores of a gridded ensemble x = u | v | t | q | ps into scores[slot]: two launches; d_use: NULL, or the member mask
+int score(spdy_nature *n, int nmem, const double *const *x, int slot, const int *d_use)
 {
     spdy_plan *p = n->plan;
     spdy::NatureScore a{};
     a.nmem = nmem; a.kx = p->tab.kx; a.ix = p->tab.ix; a.il = p->tab.il;
     for (int v = 0; v < spdy::LETKF_VARS; ++v) a.x[v] = x[v];
+    a.use = d_use;
     a.truth = n->d_truth; a.gw = n->d_gw; a.part = n->d_part; a.scores = n->d_scores + (size_t)slot * 3 * rows(p);
     KERNEL(spdy::launch_nature_score(a, p->stream));
     return SPDY_OK;
@@ -162,6 +163,12 @@ int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *l, double noise)
 int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q,
                            const double *ps, int slot)
 {
+    return spdy_mask_nature_verify_dev(n, l, vor, div, t, q, ps, nullptr, slot);
+}
+
+int spdy_mask_nature_verify_dev(spdy_nature *n, spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q,
+                                const double *ps, const int *d_use, int slot)
+{
     RC(need_pair(n, l));
     RC(need_slot(n, "nature_verify", slot));
     if (!vor || !div || !t || !q || !ps) return fail(SPDY_ERR_ARG, "null device pointer");
@@ -172,11 +179,17 @@ int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *l, const double *vor, con
     double *g = l->d_grid;
     RC(ens_to_grid(p, nmem, vor, div, t, q, ps, g));
     const double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
-    return score(n, nmem, x, slot);
+    return score(n, nmem, x, slot, d_use);
 }
 
 int spdy_nature_verify_grid_dev(spdy_nature *n, int nmem, const double *ug, const double *vg, const double *tg, const double *qg,
                                 const double *psg, int slot)
+{
+    return spdy_mask_nature_verify_grid_dev(n, nmem, ug, vg, tg, qg, psg, nullptr, slot);
+}
+
+int spdy_mask_nature_verify_grid_dev(spdy_nature *n, int nmem, const double *ug, const double *vg, const double *tg, const double *qg,
+                                     const double *psg, const int *d_use, int slot)
 {
     NEED_LIVE(n, "nature run");
     if (nmem < 2 || nmem > spdy::LETKF_MAX_MEMBERS)
@@ -185,7 +198,7 @@ int spdy_nature_verify_grid_dev(spdy_nature *n, int nmem, const double *ug, cons
     if (!ug || !vg || !tg || !qg || !psg) return fail(SPDY_ERR_ARG, "null device pointer");
     NEED_DEVICE(n->plan);
     const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
-    return score(n, nmem, x, slot);
+    return score(n, nmem, x, slot, d_use);
 }
 
 }  // extern "C"

@@ -79,7 +79,24 @@ __global__ __launch_bounds__(DIAG_BLOCK) void diagnostics_kernel(const DiagArgs 
     me->next_step = s + 1;
 }
 
+// The guard's sticky records as a member mask (include/spdy.h, "member mask"): one thread per member reads its kx records.
+__global__ __launch_bounds__(64) void diagnostics_use_kernel(const DiagLevel *const state, const int nmem, const int kx, int *const use)
+{
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= nmem) return;
+    int ok = 1;
+    for (int k = 0; k < kx; ++k) ok = state[(size_t)e * kx + k].bad_step < 0 ? ok : 0;
+    use[e] = ok;
+}
+
 }  // namespace
+
+hipError_t launch_diagnostics_use(const DiagLevel *state, int nmem, int kx, int *use, hipStream_t s)
+{
+    if (!state || !use || nmem < 1 || kx < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(diagnostics_use_kernel, dim3((unsigned)((nmem + 63) / 64)), dim3(64), 0, s, state, nmem, kx, use);
+    return hipGetLastError();
+}
 
 hipError_t launch_diagnostics(const DiagArgs &a, hipStream_t s)
 {

@@ -514,6 +514,9 @@ struct DiagArgs {
     int nmem;
 };
 hipError_t launch_diagnostics(const DiagArgs &a, hipStream_t s);
+// use[e] = 1 if none of member e's kx levels holds a first offence, else 0: one launch, one thread per member (include/spdy.h,
+// "member mask")
+hipError_t launch_diagnostics_use(const DiagLevel *state, int nmem, int kx, int *use, hipStream_t s);
 
 // The ensemble analysis (csrc/spdy_letkf.hip; include/spdy.h, "ensemble analysis").  Gridded ensemble arrays are
 // member-major: field (e, k) of a level variable starts (e * kx + k) * ncol doubles in, the surface field of member e e * ncol.
@@ -529,6 +532,13 @@ struct LetkfObs {
     double *hx, *hxmean, *y, *dep;                   // [nobs][nmem], [nobs], [nobs][nmem], [nobs]
 };
 hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s);
+// The member mask (include/spdy.h, "member mask").  One small launch turns the caller's use[nmem] into the table the
+// masked kernels read, umap [LETKF_UMAP]: umap[0] = n, the members in use; umap[1 + c] = u_c, the member of compact index c < n,
+// ascending; umap[LETKF_URANK + e] = member e's compact index, -1 for a member not in use; *nused = n as a double.
+enum { LETKF_URANK = 33, LETKF_UMAP = 66 };
+hipError_t launch_letkf_mask(const int *use, int nmem, int *umap, double *nused, hipStream_t s);
+// launch_letkf_obs over the members in use: hx of every member, hxmean, y and dep over umap's members, y = 0.0 for the others
+hipError_t launch_letkf_obs_masked(const LetkfObs &a, const int *umap, hipStream_t s);
 // The same quantities for a network that holds observations given at a pressure (include/spdy.h, "observations at a pressure";
 // DESIGN.md s22): atp[o] != 0 marks one (its lev[o] is 0: a kernel that does not know of it stays in bounds), lnp[o] = ln(p_o /
 // p0) is its target.  A workgroup owns whole observations, one thread per
@@ -541,6 +551,7 @@ struct LetkfPObs {
     const double *lnp, *rinv;                        // [nobs], [nobs] 1 / error^2
     double *olns, *used, *reff;                      // [nobs] each
     VLevels lv;                                      // ln fsg
+    const int *umap;                                 // NULL, or the member mask's table: the sums and the out-of-column test over its members
 };
 hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s);
 // The local analyses: one workgroup per grid column.  nlv levels' eigenproblems are in flight at a time (1, 2 or 4: what the LDS
@@ -559,8 +570,17 @@ struct LetkfCols {
     const int *cols;                                 // [nlist] grid columns j * ix + i, ascending
     double *tw;
 };
+// LetkfCols under the member mask: the kernel solves the problem of umap's n members in compact indices, with (n - 1) / rho formed
+// on the device (c.diag is not read), in the LDS layout of n; y, x, dx and tw keep the strides of c.nmem.  A type of its own, so
+// that the unmasked kernels' argument is the one it was.
+struct LetkfMaskedCols {
+    LetkfCols c;
+    double rho;
+    const int *umap;
+};
 size_t letkf_lds_bytes(int nmem, int kx, int nlv);
 hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s);
+hipError_t launch_letkf_transform_masked(const LetkfMaskedCols &a, size_t lds, hipStream_t s);
 hipError_t letkf_prepare(size_t lds);                // before the first launch on a device: admits a compute unit's whole LDS
 // The increments of every grid column from the transforms of a coarse set: per column a stencil of four list entries and their
 // weights (a zero weight: the entry is not read), T = ((w0 T0 + w1 T1) + w2 T2) + w3 T3 from the first term present, then
@@ -573,7 +593,8 @@ struct LetkfApply {
     const double *x[LETKF_VARS];
     double *dx[LETKF_VARS];                          // may be x
 };
-hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s);
+// umap: NULL, or the member mask's table -- the members in use from the leading n x n block of each T, 0.0 for the others
+hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s, const int *umap = nullptr);
 // dst[i] += src[i] for nops arrays in one launch; an increment equal to zero leaves the destination's bits (a -0.0 included)
 struct LetkfAdd {
     int nops;
@@ -612,6 +633,7 @@ struct NatureScore {
     const double *x[LETKF_VARS];
     const double *truth, *gw;
     double *part, *scores;
+    const int *use;                                  // NULL, or [nmem]: non-zero = the member is scored (the caller's array, read as it is)
 };
 hipError_t launch_nature_score(const NatureScore &a, hipStream_t s);
 

@@ -6,6 +6,8 @@
 // Everything here is bit-reproducible: no atomics, every sum in a fixed order (observations ascending, members ascending), every
 // loop with a fixed bound.  The Jacobi sweeps end at the convergence test or after LETKF_SWEEPS; a NaN fails every test, so a
 // non-finite input runs the full count and leaves NaN, it does not hang.  No contraction, as in the other column kernels.
+#include <type_traits>
+
 #include "spdy_kernels.hpp"
 
 namespace spdy {
@@ -88,6 +90,44 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObs a
     a.dep[o] = a.value[o] - mean;
 }
 
+// The member mask's table from the caller's use[nmem] (include/spdy.h, "member mask"): one wave, lane e owns member e; the compact
+// index of a member in use is the number of members in use below it (ballot and prefix count, no atomics).
+__global__ __launch_bounds__(64) void letkf_mask_kernel(const int *const use, const int nmem, int *const umap, double *const nused)
+{
+    const int e = threadIdx.x;
+    const bool u = e < nmem && use[e] != 0;
+    const unsigned long long mask = __ballot(u);
+    const int rank = __popcll(mask & ((1ull << e) - 1ull)), n = __popcll(mask);
+    if (u) umap[1 + rank] = e;
+    if (e < nmem) umap[LETKF_URANK + e] = u ? rank : -1;
+    if (e == 0) { umap[0] = n; *nused = (double)n; }
+}
+
+// letkf_obs_kernel over the members in use: every member's hx is its own H x_e; the sum, by a select, takes the members in use in
+// ascending order, so hxmean, y and dep have the bits an object of those n members gives; y of a member not in use is 0.0.
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_masked_kernel(const LetkfObs a, const int *const umap)
+{
+#pragma clang fp contract(off)
+    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (o >= a.nobs) return;
+    const int v = a.var[o], k = a.lev[o], n = umap[0];
+    const int *const rank = umap + LETKF_URANK;
+    const double *const x = a.x[v];
+    const int i0 = a.sidx[4 * o], i1 = a.sidx[4 * o + 1], i2 = a.sidx[4 * o + 2], i3 = a.sidx[4 * o + 3];
+    const double w0 = a.swgt[4 * o], w1 = a.swgt[4 * o + 1], w2 = a.swgt[4 * o + 2], w3 = a.swgt[4 * o + 3];
+    double sum = 0.0;
+    for (int e = 0; e < a.nmem; ++e) {
+        const double *const f = x + letkf_at(v, e, k, a.kx, a.ncol, 0);
+        const double h = ((w0 * f[i0] + w1 * f[i1]) + w2 * f[i2]) + w3 * f[i3];
+        a.hx[(size_t)o * a.nmem + e] = h;
+        sum = rank[e] >= 0 ? sum + h : sum;
+    }
+    const double mean = sum / n;
+    a.hxmean[o] = mean;
+    for (int e = 0; e < a.nmem; ++e) a.y[(size_t)o * a.nmem + e] = rank[e] >= 0 ? a.hx[(size_t)o * a.nmem + e] - mean : 0.0;
+    a.dep[o] = a.value[o] - mean;
+}
+
 // The observation-space quantities of a network that holds observations given at a pressure (include/spdy.h, "observations at a
 // pressure").  A workgroup owns LETKF_BLOCK / E whole observations.  Thread (observation, member) finds the brackets
 // of the target in its member's four stencil columns from their four ps (one loop of kx trips, csrc/spdy_vinterp.hpp), loads the
@@ -95,6 +135,10 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObs a
 // out-of-column flag in LDS; thread (observation) then sums over the members in ascending order.  An observation on a model level
 // or of ps takes the same path with its bracket replaced by {lev, the level's own bits}, so the lanes of a wave do not diverge and
 // its hx has letkf_obs_kernel's bits.  No atomics, no array indexed by a bracket, every bound a kernel argument.
+// MASK (the member mask, a.umap): the thread layout is that of nmem and every member's hx is its own; the sums, psum and the
+// out-of-column OR take the members in use by a select, ascending, and divide by their number; y of a member not in use is 0.0.
+// Two instantiations, no run-time branch: MASK = false is the kernel it was.
+template <bool MASK>
 __global__ __launch_bounds__(LETKF_BLOCK) void letkf_pobs_kernel(const LetkfPObs a)
 {
 #pragma clang fp contract(off)
@@ -148,33 +192,77 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_pobs_kernel(const LetkfPObs
         double sum = 0.0, psum = 0.0;
         int out = 0;
         for (int m = 0; m < E; ++m) {
-            sum += shx[tid * E + m];
-            psum += spb[tid * E + m];
-            out |= sout[tid * E + m];
+            if constexpr (MASK) {
+                const bool u = a.umap[LETKF_URANK + m] >= 0;
+                sum = u ? sum + shx[tid * E + m] : sum;
+                psum = u ? psum + spb[tid * E + m] : psum;
+                out |= u ? sout[tid * E + m] : 0;
+            } else {
+                sum += shx[tid * E + m];
+                psum += spb[tid * E + m];
+                out |= sout[tid * E + m];
+            }
         }
-        const double mean = sum / E;
+        const int n = MASK ? a.umap[0] : E;
+        const double mean = sum / n;
         smean[tid] = mean;
         a.o.hxmean[o1] = mean;
         a.o.dep[o1] = a.o.value[o1] - mean;
-        if (a.atp[o1] != 0) a.olns[o1] = a.lnp[o1] - psum / E;
+        if (a.atp[o1] != 0) a.olns[o1] = a.lnp[o1] - psum / n;
         a.used[o1] = out ? 0.0 : 1.0;
         a.reff[o1] = out ? 0.0 : a.rinv[o1];
     }
     __syncthreads();
-    if (act) a.o.y[(size_t)o * E + e] = h - smean[slot];
+    if constexpr (MASK) {
+        if (act) a.o.y[(size_t)o * E + e] = a.umap[LETKF_URANK + e] >= 0 ? h - smean[slot] : 0.0;
+    } else {
+        if (act) a.o.y[(size_t)o * E + e] = h - smean[slot];
+    }
 }
 
 // LIST = false: one workgroup per grid column, which gets its increments.  LIST = true (weight interpolation): workgroup b solves
-// grid column cols[b] and writes T of every level to tw, [b][k][f][e] with e fastest, and no increments.  Two instantiations, no
-// run-time branch: the first form is the kernel it was before the second existed.
-template <bool LIST>
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const LetkfCols a)
+// grid column cols[b] and writes T of every level to tw, [b][k][f][e] with e fastest, and no increments.
+// ARGS = LetkfMaskedCols (the member mask: MASK; include/spdy.h, "member mask"): E is n = umap[0], read once and the same for the workgroup,
+// and everything below -- the diagonal, the padded size, the LDS layout, the pair schedule, the means -- is that of an object of n
+// members; compact index e stands for member umap[1 + e] in every load of y and x and every store of dx; the members not in use
+// get 0.0.  y, x, dx and tw keep the strides of NM = nmem members, and the launch shape, nlv and the LDS request are those of nmem
+// (the layout of a smaller E fits).  n < 2: zero increments, nothing else.  Four instantiations, no run-time branch: those on
+// LetkfCols are the kernels they were before the mask existed, instruction for instruction.
+__device__ inline const LetkfCols &letkf_cols(const LetkfCols &a) { return a; }
+__device__ inline const LetkfCols &letkf_cols(const LetkfMaskedCols &a) { return a.c; }
+__device__ inline const int *letkf_umap(const LetkfCols &) { return nullptr; }
+__device__ inline const int *letkf_umap(const LetkfMaskedCols &a) { return a.umap; }
+__device__ inline double letkf_diag(const LetkfCols &a, int) { return a.diag; }
+// (n - 1) / rho as one IEEE division: the bits the host gives an object of n members
+__device__ inline double letkf_diag(const LetkfMaskedCols &a, int n) { return (double)(n - 1) / a.rho; }
+
+template <bool LIST, class ARGS>
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const ARGS args)
 {
 #pragma clang fp contract(off)
+    constexpr bool MASK = !std::is_same<ARGS, LetkfCols>::value;
+    const LetkfCols &a = letkf_cols(args);
+    const int *const umap = letkf_umap(args);
     extern __shared__ __attribute__((aligned(16))) char letkf_smem[];
     double *const sm = reinterpret_cast<double *>(letkf_smem);
-    const int E = a.nmem, ep = (E + 1) & ~1, ee = ep * ep, kx = a.kx, ncol = a.ncol, tid = threadIdx.x;
+    const int E = MASK ? umap[0] : a.nmem, NM = MASK ? a.nmem : E, ep = (E + 1) & ~1, ee = ep * ep, kx = a.kx, ncol = a.ncol, tid = threadIdx.x;
     const int col = LIST ? a.cols[blockIdx.x] : blockIdx.x;
+    const int *const um = MASK ? umap + 1 : nullptr, *const urank = MASK ? umap + LETKF_URANK : nullptr;
+    int me0 = 0, me1 = 0;                     // MASK: the members of this thread's two elements of a staged tile of Y
+    if constexpr (MASK) {
+        if (E < 2) {                          // nothing to analyse: every member's increments are 0.0
+            if constexpr (!LIST)
+                for (int x = tid; x < (4 * kx + 1) * NM; x += LETKF_BLOCK) {
+                    const int f = x / NM, m = x % NM, v = f < 4 * kx ? f / kx : 4, k = f < 4 * kx ? f % kx : 0;
+                    a.dx[v][letkf_at(v, m, k, kx, ncol, col)] = 0.0;
+                }
+            return;
+        }
+        const int e0 = tid % ep, e1 = (tid + LETKF_BLOCK) % ep;
+        me0 = e0 < E ? um[e0] : 0;
+        me1 = e1 < E ? um[e1] : 0;
+    }
+    const double mdiag = MASK ? letkf_diag(args, E) : 0.0;      // unmasked: a.diag is read where it is used, as it always was
     const LetkfLds L(ep, kx, a.nlv);
     double *const C = sm + L.C, *const B = sm + L.B, *const ty = sm + L.ty, *const rtab = sm + L.rtab, *const td = sm + L.td,
                   *const lwh = sm + L.lwh;
@@ -184,7 +272,7 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
     // A = (E - 1) / rho I (an odd E: one decoupled row more), b = 0
     for (int el = tid; el < kx * ee; el += LETKF_BLOCK) {
         const int i = (el % ee) / ep, j = el % ep;
-        C[el] = i == j ? (i < E ? a.diag : 1.0) : 0.0;
+        C[el] = i == j ? (i < E ? (MASK ? mdiag : a.diag) : 1.0) : 0.0;
     }
     for (int el = tid; el < kx * ep; el += LETKF_BLOCK) B[el] = 0.0;
     if (tid < kx) touched[tid] = 0;
@@ -225,7 +313,10 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
             }
             for (int x = tid; x < nt * ep; x += LETKF_BLOCK) {
                 const int t = x / ep, e = x % ep;
-                ty[x] = e < E ? a.y[(size_t)lidx[t0 + t] * E + e] : 0.0;
+                if constexpr (MASK)       // LETKF_TILE * ep <= 2 LETKF_BLOCK: x is tid or tid + LETKF_BLOCK
+                    ty[x] = e < E ? a.y[(size_t)lidx[t0 + t] * NM + (x < LETKF_BLOCK ? me0 : me1)] : 0.0;
+                else
+                    ty[x] = e < E ? a.y[(size_t)lidx[t0 + t] * E + e] : 0.0;
             }
             if (tid < nt) td[tid] = a.dep[lidx[t0 + tid]];
             __syncthreads();
@@ -348,7 +439,7 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
                 }
                 const double tfe = (acc + wbar[f]) - (f == e ? 1.0 : 0.0);
                 if constexpr (LIST) {
-                    if (f < E && e < E) a.tw[(((size_t)blockIdx.x * kx + k) * E + f) * E + e] = tfe;
+                    if (f < E && e < E) a.tw[(((size_t)blockIdx.x * kx + k) * NM + f) * NM + e] = tfe;
                 } else {
                     A[el] = tfe;
                 }
@@ -361,7 +452,10 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
         const int nvar = act ? (k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1) : 0;
         for (int x = lt; x < nvar * ep; x += tpl) {
             const int v = x / ep, e = x % ep;
-            X[x] = e < E ? a.x[v][letkf_at(v, e, k, kx, ncol, col)] : 0.0;
+            if constexpr (MASK)
+                X[x] = e < E ? a.x[v][letkf_at(v, um[e], k, kx, ncol, col)] : 0.0;
+            else
+                X[x] = e < E ? a.x[v][letkf_at(v, e, k, kx, ncol, col)] : 0.0;
         }
         __syncthreads();
         for (int x = lt; x < nvar * ep; x += tpl) {
@@ -373,8 +467,13 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const Letk
             const double mean = sum / E;
             double d = 0.0;
             for (int f = 0; f < E; ++f) d += (xv[f] - mean) * A[f * ep + e];
-            a.dx[v][letkf_at(v, e, k, kx, ncol, col)] = d;
+            a.dx[v][letkf_at(v, MASK ? um[e] : e, k, kx, ncol, col)] = d;
         }
+        if constexpr (MASK)                    // a member not in use: nobody reads its values, its increments are exactly 0.0
+            for (int x = lt; x < nvar * NM; x += tpl) {
+                const int v = x / NM, m = x % NM;
+                if (urank[m] < 0) a.dx[v][letkf_at(v, m, k, kx, ncol, col)] = 0.0;
+            }
         __syncthreads();
     }
 }
@@ -448,6 +547,76 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_kernel(const LetkfApp
     }
 }
 
+// letkf_apply_kernel under the member mask (umap): a sibling, the kernel above is as it was.  The launch shape and the LDS slots
+// are those of nmem.  Lane e still owns member e: a member in use has the compact index c = rank[e] and forms dx from the leading
+// n x n block of each T (strides of nmem) and the values of the members umap[1 + f], f < n ascending, with the means over them; a
+// member not in use reads nothing and gets 0.0, and so does every member when n < 2 (the weight buffer is then not read at all).
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_masked_kernel(const LetkfApply a, const int lpi, const int *const umap)
+{
+#pragma clang fp contract(off)
+    __shared__ double X[LETKF_VARS * LETKF_BLOCK];      // [slot][v][lpi]
+    const int NM = a.nmem, E = umap[0], kx = a.kx, ncol = a.ncol, tid = threadIdx.x, ipb = LETKF_BLOCK / lpi;
+    const int *const um = umap + 1;
+    const long nitem = (long)kx * ncol, first = (long)blockIdx.x * ipb;
+    {
+        const int slot = tid % ipb, f = tid / ipb;
+        const long item = first + slot;
+        if (item < nitem && f < NM) {
+            const int k = (int)(item / ncol), col = (int)(item % ncol), nvar = k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1;
+            for (int v = 0; v < nvar; ++v) X[(slot * LETKF_VARS + v) * lpi + f] = a.x[v][letkf_at(v, f, k, kx, ncol, col)];
+        }
+    }
+    __syncthreads();
+    const int slot = tid / lpi, e = tid % lpi;
+    const long item = first + slot;
+    const int c = e < NM ? umap[LETKF_URANK + e] : -1;
+    double d[LETKF_VARS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (item < nitem && c >= 0 && E >= 2) {
+        const int k = (int)(item / ncol), col = (int)(item % ncol);
+        const bool sfc = k == kx - 1;
+        const double *const xs = X + slot * LETKF_VARS * lpi;
+        double mean[LETKF_VARS];
+        for (int v = 0; v < LETKF_VARS; ++v) {
+            double sum = 0.0;
+            for (int f = 0; f < E; ++f) sum += xs[v * lpi + um[f]];
+            mean[v] = sum / E;
+        }
+        const double w0 = a.iwgt[4 * (size_t)col], w1 = a.iwgt[4 * (size_t)col + 1], w2 = a.iwgt[4 * (size_t)col + 2],
+                     w3 = a.iwgt[4 * (size_t)col + 3];
+        const size_t ee = (size_t)NM * NM, lev = (size_t)k * ee + c;
+        const double *const t0 = a.tw + (size_t)a.iidx[4 * (size_t)col] * kx * ee + lev,
+                     *const t1 = a.tw + (size_t)a.iidx[4 * (size_t)col + 1] * kx * ee + lev,
+                     *const t2 = a.tw + (size_t)a.iidx[4 * (size_t)col + 2] * kx * ee + lev,
+                     *const t3 = a.tw + (size_t)a.iidx[4 * (size_t)col + 3] * kx * ee + lev;
+#pragma unroll 4
+        for (int f = 0; f < E; ++f) {
+            const size_t r = (size_t)f * NM;
+            const int mf = um[f];
+            double t = w0 * t0[r];
+            if (w1 != 0.0) t += w1 * t1[r];
+            if (w2 != 0.0) t += w2 * t2[r];
+            if (w3 != 0.0) t += w3 * t3[r];
+            for (int v = 0; v < LETKF_VARS - 1; ++v) d[v] += (xs[v * lpi + mf] - mean[v]) * t;
+            if (sfc) d[4] += (xs[4 * lpi + mf] - mean[4]) * t;
+        }
+    }
+    __syncthreads();
+    X[(slot * LETKF_VARS + 0) * lpi + e] = d[0];
+    X[(slot * LETKF_VARS + 1) * lpi + e] = d[1];
+    X[(slot * LETKF_VARS + 2) * lpi + e] = d[2];
+    X[(slot * LETKF_VARS + 3) * lpi + e] = d[3];
+    X[(slot * LETKF_VARS + 4) * lpi + e] = d[4];
+    __syncthreads();
+    {
+        const int slot2 = tid % ipb, f = tid / ipb;
+        const long item2 = first + slot2;
+        if (item2 < nitem && f < NM) {
+            const int k = (int)(item2 / ncol), col = (int)(item2 % ncol), nvar = k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1;
+            for (int v = 0; v < nvar; ++v) a.dx[v][letkf_at(v, f, k, kx, ncol, col)] = X[(slot2 * LETKF_VARS + v) * lpi + f];
+        }
+    }
+}
+
 __global__ __launch_bounds__(LETKF_BLOCK) void spec_add_kernel(const LetkfAdd a)
 {
     const int op = blockIdx.y;
@@ -466,10 +635,32 @@ hipError_t letkf_prepare(size_t lds)
 {
     constexpr size_t whole = 160 * 1024;
     if (lds > whole) return hipErrorInvalidValue;
-    const hipError_t rc =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(letkf_transform_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole);
-    if (rc != hipSuccess) return rc;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(letkf_transform_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole);
+    const void *const forms[4] = {reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfMaskedCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfMaskedCols>)};
+    for (const void *f : forms)
+        if (const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole)) return rc;
+    return hipSuccess;
+}
+
+hipError_t launch_letkf_mask(const int *use, int nmem, int *umap, double *nused, hipStream_t s)
+{
+    if (!use || nmem < 2 || nmem > LETKF_MAX_MEMBERS || !umap || !nused) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(letkf_mask_kernel, dim3(1), dim3(64), 0, s, use, nmem, umap, nused);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_obs_masked(const LetkfObs &a, const int *umap, hipStream_t s)
+{
+    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.ncol < 1 || !a.hx || !a.hxmean || !a.y || !a.dep || !umap)
+        return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!a.x[v]) return hipErrorInvalidValue;
+    if (!a.nobs) return hipSuccess;
+    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.value) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(letkf_obs_masked_kernel, dim3((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), dim3(LETKF_BLOCK), 0, s, a, umap);
+    return hipGetLastError();
 }
 
 hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s)
@@ -495,29 +686,54 @@ hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s)
     if (!o.nobs) return hipSuccess;
     if (!o.var || !o.lev || !o.sidx || !o.swgt || !o.value || !a.atp || !a.lnp || !a.rinv || !a.olns || !a.used || !a.reff) return hipErrorInvalidValue;
     const int opb = LETKF_BLOCK / o.nmem;
-    hipLaunchKernelGGL(letkf_pobs_kernel, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
+    if (a.umap)
+        hipLaunchKernelGGL(letkf_pobs_kernel<true>, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(letkf_pobs_kernel<false>, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s)
+namespace {
+// the checks of a transform launch, masked or not; *list: the column-list form
+hipError_t transform_ready(const LetkfCols &a, size_t lds, bool *list)
 {
     if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 ||
         (a.nlv != 1 && a.nlv != 2 && a.nlv != 4) || lds != letkf_lds_bytes(a.nmem, a.kx, a.nlv) || !(a.ch > 0.0) || !(a.diag > 0.0) ||
         !a.colunit || !a.lnfsg)
         return hipErrorInvalidValue;
     if (a.nobs && (!a.ounit || !a.olns || !a.rinv || !a.y || !a.dep)) return hipErrorInvalidValue;
-    if (a.cols || a.tw || a.nlist) {
-        if (!a.cols || !a.tw || a.nlist < 1 || a.nlist > a.ncol) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(letkf_transform_kernel<true>, dim3(a.nlist), dim3(LETKF_BLOCK), lds, s, a);
-        return hipGetLastError();
-    }
+    *list = a.cols || a.tw || a.nlist;
+    if (*list) return !a.cols || !a.tw || a.nlist < 1 || a.nlist > a.ncol ? hipErrorInvalidValue : hipSuccess;
     for (int v = 0; v < LETKF_VARS; ++v)
         if (!a.x[v] || !a.dx[v]) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(letkf_transform_kernel<false>, dim3(a.ncol), dim3(LETKF_BLOCK), lds, s, a);
+    return hipSuccess;
+}
+}  // namespace
+
+hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s)
+{
+    bool list = false;
+    if (const hipError_t rc = transform_ready(a, lds, &list)) return rc;
+    if (list)
+        hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfCols>), dim3(a.nlist), dim3(LETKF_BLOCK), lds, s, a);
+    else
+        hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfCols>), dim3(a.ncol), dim3(LETKF_BLOCK), lds, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s)
+hipError_t launch_letkf_transform_masked(const LetkfMaskedCols &a, size_t lds, hipStream_t s)
+{
+    bool list = false;
+    if (!a.umap || !(a.rho > 0.0)) return hipErrorInvalidValue;
+    if (const hipError_t rc = transform_ready(a.c, lds, &list)) return rc;
+    if (list)
+        hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfMaskedCols>), dim3(a.c.nlist), dim3(LETKF_BLOCK), lds, s, a);
+    else
+        hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfMaskedCols>), dim3(a.c.ncol), dim3(LETKF_BLOCK), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s, const int *umap)
 {
     if (a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 || a.nlist < 1 || a.nlist > a.ncol ||
         !a.iidx || !a.iwgt || !a.tw)
@@ -527,7 +743,10 @@ hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s)
     int lpi = 2;
     while (lpi < a.nmem) lpi *= 2;
     const long nitem = (long)a.kx * a.ncol, ipb = LETKF_BLOCK / lpi;
-    hipLaunchKernelGGL(letkf_apply_kernel, dim3((unsigned)((nitem + ipb - 1) / ipb)), dim3(LETKF_BLOCK), 0, s, a, lpi);
+    if (umap)
+        hipLaunchKernelGGL(letkf_apply_masked_kernel, dim3((unsigned)((nitem + ipb - 1) / ipb)), dim3(LETKF_BLOCK), 0, s, a, lpi, umap);
+    else
+        hipLaunchKernelGGL(letkf_apply_kernel, dim3((unsigned)((nitem + ipb - 1) / ipb)), dim3(LETKF_BLOCK), 0, s, a, lpi);
     return hipGetLastError();
 }
 

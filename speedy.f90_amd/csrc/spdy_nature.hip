@@ -79,8 +79,10 @@ __global__ void nature_count_kernel(unsigned long long *state)
 }
 
 // one workgroup per (latitude j, row f); EMAX bounds the members a thread keeps in registers (two passes: the mean, then the
-// squared deviations from it)
-template <int EMAX>
+// squared deviations from it).  MASK (include/spdy.h, "member mask"): a.use is read as it is, n counts its non-zero entries, a member
+// not in use is never loaded and is skipped by a select, the sums take the others in ascending order, mbar = sum / n and s2 = sum /
+// (n - 1); n = 1 gives s2 = +0, n = 0 NaN in all three.  No run-time branch: MASK = false is the kernel it was.
+template <int EMAX, bool MASK>
 __global__ __launch_bounds__(NATURE_SCORE_BLOCK) void nature_zonal_kernel(const NatureScore a)
 {
 #pragma clang fp contract(off)
@@ -92,27 +94,38 @@ __global__ __launch_bounds__(NATURE_SCORE_BLOCK) void nature_zonal_kernel(const 
     const size_t member = v < 4 ? (size_t)kx * ncol : ncol;
     const double *const truth = a.truth + (size_t)f * ncol + (size_t)j * a.ix;
     double s_m = 0.0, s_mm = 0.0, s_var = 0.0;
+    unsigned in_use = 0xffffffffu;           // MASK: bit e = member e is in use; n of them
+    int n = E;
+    if constexpr (MASK) {
+        in_use = 0u;
+        n = 0;
+        for (int e = 0; e < E; ++e)
+            if (a.use[e] != 0) { in_use |= 1u << e; ++n; }
+    }
     for (int i = tid; i < a.ix; i += NATURE_SCORE_BLOCK) {
         const double t = truth[i];
         double d[EMAX];
 #pragma unroll
         for (int e = 0; e < EMAX; ++e)
-            if (e < E) d[e] = x[e * member + i] - t;
+            if (e < E && (!MASK || (in_use >> e & 1u))) d[e] = x[e * member + i] - t;
         double sum = 0.0;
 #pragma unroll
         for (int e = 0; e < EMAX; ++e)
-            if (e < E) sum = sum + d[e];
-        const double m = sum / E;
+            if (e < E && (!MASK || (in_use >> e & 1u))) sum = sum + d[e];
+        const double m = sum / n;
         double q = 0.0;
 #pragma unroll
         for (int e = 0; e < EMAX; ++e)
-            if (e < E) {
+            if (e < E && (!MASK || (in_use >> e & 1u))) {
                 const double r = d[e] - m;
                 q = q + r * r;
             }
         s_m = s_m + m;
         s_mm = s_mm + m * m;
-        s_var = s_var + q / (E - 1);
+        if constexpr (MASK)
+            s_var = s_var + (n >= 2 ? q / (n - 1) : n == 1 ? 0.0 : m);      // n = 0: m is NaN
+        else
+            s_var = s_var + q / (E - 1);
     }
     // a fixed tree: lanes 32 apart, 16, ... 1, then the waves in ascending order
     for (int off = 32; off > 0; off >>= 1) {
@@ -185,10 +198,15 @@ hipError_t launch_nature_score(const NatureScore &a, hipStream_t s)
         if (!a.x[v]) return hipErrorInvalidValue;
     const int nrows = 4 * a.kx + 1;
     const dim3 grid(a.il, nrows), block(NATURE_SCORE_BLOCK);
-    if (a.nmem <= 8)
-        hipLaunchKernelGGL(nature_zonal_kernel<8>, grid, block, 0, s, a);
+    if (a.use) {
+        if (a.nmem <= 8)
+            hipLaunchKernelGGL((nature_zonal_kernel<8, true>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((nature_zonal_kernel<LETKF_MAX_MEMBERS, true>), grid, block, 0, s, a);
+    } else if (a.nmem <= 8)
+        hipLaunchKernelGGL((nature_zonal_kernel<8, false>), grid, block, 0, s, a);
     else
-        hipLaunchKernelGGL(nature_zonal_kernel<LETKF_MAX_MEMBERS>, grid, block, 0, s, a);
+        hipLaunchKernelGGL((nature_zonal_kernel<LETKF_MAX_MEMBERS, false>), grid, block, 0, s, a);
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(nature_final_kernel, dim3((nrows + NATURE_BLOCK - 1) / NATURE_BLOCK), dim3(NATURE_BLOCK), 0, s, a);
     return hipGetLastError();

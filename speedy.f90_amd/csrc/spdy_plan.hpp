@@ -182,6 +182,12 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     double *d_lnp = nullptr, *d_used = nullptr, *d_reff = nullptr;
     int *d_sidx = nullptr, *d_var = nullptr, *d_lev = nullptr;
     int *d_atp = nullptr;                 // [max_obs] 1: the observation is at a pressure (its d_lev is 0); written by spdy_pobs_set only
+    // the member mask (include/spdy.h, "member mask"): d_nused = {nmem, n of the latest masked call} as doubles -- an unmasked call
+    // launches what it always did and writes neither, so "members_used" is the word of the kind of call enqueued last (masked_last);
+    // d_umap [LETKF_UMAP] is the table a masked call's first launch builds from the caller's d_use (csrc/spdy_kernels.hpp)
+    double *d_nused = nullptr;
+    int *d_umap = nullptr;
+    bool masked_last = false;
     // the main allocation: the doubles, then the ints; ncol, ns: elements of a grid and of a spectrum
     template <class V> void arrays(V &&v, size_t ncol = 0, size_t ns = 0, size_t kx = 0)
     {
@@ -189,8 +195,8 @@ struct spdy_letkf final : spdy_detail::PlanObject {
         v(d_grid, nf * ncol); v(d_spec, nf * ns); v(d_colunit, 3 * ncol); v(d_lnfsg, kx);
         v(d_swgt, 4 * M); v(d_ounit, 3 * M); v(d_olns, M); v(d_rinv, M); v(d_err, M); v(d_value, M);
         v(d_hx, M * E); v(d_hxmean, M); v(d_y, M * E); v(d_dep, M);
-        v(d_lnp, M); v(d_used, M); v(d_reff, M);
-        v(d_sidx, 4 * M); v(d_var, M); v(d_lev, M); v(d_atp, M);
+        v(d_lnp, M); v(d_used, M); v(d_reff, M); v(d_nused, 2);
+        v(d_sidx, 4 * M); v(d_var, M); v(d_lev, M); v(d_atp, M); v(d_umap, spdy::LETKF_UMAP);
     }
     // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
     int si = 1, sj = 1;

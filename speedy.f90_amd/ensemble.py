@@ -251,26 +251,32 @@ class Ensemble:
         return res
 
     # ------------------------------------------------------------------ analysis
-    def analyse(self, letkf):
+    def analyse(self, letkf, use=None):
         """The LETKF update of time level 1 of every member, in place (include/spdy.h, "ensemble analysis"): five launches whatever
         E is (six once the direct batch is of streaming size), capturable.  letkf: a Letkf of this plan with nmem == E, its
         observations set.  Time level 2 and phi are stale afterwards: continue with startup(delt).  Members are coupled: every
-        member must be finite."""
+        member analysed must be finite.
+        use: None (all members), or as output()'s: a sequence or an int32 device tensor of E entries, non-zero = the member is
+        analysed (include/spdy.h, "member mask"; guard.use_dev() gives the guard's on the device).  The n members in use get, bit
+        for bit, what an n-member Ensemble and Letkf give them; a member not in use is read into nothing shared and keeps every
+        bit of its state; n < 2 leaves the whole state.  One launch more.  The tensor is read when the kernels run: a captured
+        analysis follows its contents."""
         if getattr(letkf, "sp", None) is not self.sp:
             raise ValueError("analyse: the Letkf must belong to the ensemble's plan")
         if letkf.nmem != self.nmem:
             raise ValueError("analyse: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
-        letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0])
+        letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], use)
 
-    def verify(self, letkf, nature, slot=0):
+    def verify(self, letkf, nature, slot=0, use=None):
         """The scores of time level 1 against a Nature's truth (include/spdy.h, "nature run"): rmse and bias of the ensemble mean and
         the spread, per variable and level, into nature.scores(slot).  Three launches, capturable; nothing of the ensemble changes.
-        letkf: a Letkf of this plan with nmem == E, whose grid workspace the call uses; nature: a Nature of this plan."""
+        letkf: a Letkf of this plan with nmem == E, whose grid workspace the call uses; nature: a Nature of this plan.  use: as
+        analyse's: the scores over the members in use."""
         if getattr(letkf, "sp", None) is not self.sp or getattr(nature, "sp", None) is not self.sp:
             raise ValueError("verify: the Letkf and the Nature must belong to the ensemble's plan")
         if letkf.nmem != self.nmem:
             raise ValueError("verify: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
-        nature.verify(letkf, self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], slot)
+        nature.verify(letkf, self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], slot, use)
 
     def startup(self, delt, physics=None):
         """first_step (time_stepping.f90:12-24): the forward half step, the first leapfrog step and the three initialize_implicit

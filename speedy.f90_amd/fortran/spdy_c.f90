@@ -1243,6 +1243,39 @@ module spdy_c
             type(c_ptr), value :: l, vor, div, t, q, ps
             integer(c_int) :: rc
         end function
+        ! the member mask (include/spdy.h): d_use is nmem C ints in device memory, non-zero = the member is in use, read when
+        ! the kernels run; c_null_ptr = all members.  The analysis and the scores over the members in use, and the guard's
+        ! sticky records as such a mask
+        function spdy_mask_letkf_analyse_grid_dev(l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps, d_use) &
+                & bind(C, name="spdy_mask_letkf_analyse_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps, d_use
+            integer(c_int) :: rc
+        end function
+        function spdy_mask_ens_letkf_dev(l, vor, div, t, q, ps, d_use) bind(C, name="spdy_mask_ens_letkf_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, vor, div, t, q, ps, d_use
+            integer(c_int) :: rc
+        end function
+        function spdy_mask_nature_verify_dev(n, letkf, vor, div, t, q, ps, d_use, slot) &
+                & bind(C, name="spdy_mask_nature_verify_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: n, letkf, vor, div, t, q, ps, d_use
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
+        function spdy_mask_nature_verify_grid_dev(n, nmem, ug, vg, tg, qg, psg, d_use, slot) &
+                & bind(C, name="spdy_mask_nature_verify_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: n, ug, vg, tg, qg, psg, d_use
+            integer(c_int), value :: nmem, slot
+            integer(c_int) :: rc
+        end function
+        function spdy_mask_from_diagnostics_dev(d, d_use) bind(C, name="spdy_mask_from_diagnostics_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: d, d_use
+            integer(c_int) :: rc
+        end function
         ! the nature run (include/spdy.h): the truth of a twin experiment, the observation values of an analysis object's network
         ! drawn from it, an ensemble's scores against it; the device pointers are those of time level 1
         function spdy_nature_create(plan, seed, capacity, n) bind(C, name="spdy_nature_create") result(rc)

@@ -7,8 +7,9 @@ second operator.  weight_stride=(si, sj) solves the local problems on every si-t
 other columns the bilinear interpolation of those columns' transforms (one launch more); (1, 1), the default, solves every column.
 set_obs(..., p=...) takes observations of u, v, t or q given at a pressure (lev == OBS_AT_P): they are interpolated in the vertical
 per member, linearly in ln p (include/spdy.h, "observations at a pressure").  After an analysis the run continues
-with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled: build the analysis ensemble from
-members the guard has not stopped, a non-finite member makes every column it touches non-finite."""
+with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled, a non-finite member makes every
+column it touches non-finite: pass use=, a member mask on the device (Diagnostics.use_dev gives the guard's), to analyse the
+members the guard has not stopped and leave the others alone, bit for bit (include/spdy.h, "member mask")."""
 import ctypes
 
 import numpy as np
@@ -27,7 +28,7 @@ _PER_OBS, _PER_OBS_MEMBER = (lambda l: (l.nobs,)), (lambda l: (l.nobs, l.nmem))
 _FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "departure": _PER_OBS,
            "weights": lambda l: (check(l.lib.spdy_letkf_table(l.h, b"coarse_columns", None, 0)), l.sp.kx, l.nmem, l.nmem),
            "value": _PER_OBS, "grid": lambda l: ((4 * l.sp.kx + 1) * l.nmem,) + l.sp.grid_shape,
-           "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS}
+           "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS, "members_used": lambda l: (1,)}
 LETKF_TABLES, LETKF_FIELDS = tuple(_TABLES), tuple(_FIELDS)
 
 
@@ -39,6 +40,22 @@ class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
 class PObs(ctypes.Structure):         # spdy_pobs (include/spdy.h)
     _fields_ = [("var", ctypes.c_int), ("lev", ctypes.c_int), ("p", ctypes.c_double), ("lon", ctypes.c_double),
                 ("lat", ctypes.c_double), ("value", ctypes.c_double), ("error", ctypes.c_double)]
+
+
+def use_mask(use, nmem, device):
+    """`use` of a masked call as Ensemble.output takes it -> None (all members) or a contiguous int32 tensor of nmem entries on
+    `device`: a sequence becomes one (non-zero / true = in use), a tensor is checked"""
+    import torch
+    if use is None:
+        return None
+    if not torch.is_tensor(use):
+        use = list(use)
+        if len(use) != nmem:
+            raise ValueError("use must be %d contiguous int32 entries" % nmem)
+        use = torch.tensor([1 if u else 0 for u in use], dtype=torch.int32, device=device)
+    if use.dtype != torch.int32 or use.numel() != nmem or not use.is_contiguous():
+        raise ValueError("use must be %d contiguous int32 entries" % nmem)
+    return use
 
 
 class _DeviceView:
@@ -139,7 +156,9 @@ class Letkf(PlanObject):
         [(4 kx + 1) nmem, il, ix]: the grid workspace, u | v | t | q (nmem kx grids each, member-major) | ps (nmem) -- the gridded
         ensemble after Nature.verify, the increments after Ensemble.analyse.  obs_lnsigma [nobs]: ln sigma_o the latest analysis
         call localised with (for an observation at a pressure ln(p/p0) minus the ensemble-mean ps at its place, formed in that
-        call); obs_used [nobs]: 1.0, or 0.0 for an at-pressure observation that was out of some member's column in that call."""
+        call); obs_used [nobs]: 1.0, or 0.0 for an at-pressure observation that was out of some member's column in that call.
+        members_used [1]: the members the latest analysis call analysed, nmem without a mask; ask for it after the call -- it is
+        one of two words, that of the kind of call (masked or not) enqueued last."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         return DeviceField(self.sp, p.value, _FIELDS[name](self))
@@ -154,12 +173,20 @@ class Letkf(PlanObject):
             out[name] = torch.as_tensor(_DeviceView(f), device=dev) if self.nobs else torch.empty(f.shape, dtype=torch.float64, device=dev)
         return out
 
-    def analyse_grid(self, ug, vg, tg, qg, psg, out=None):
+    def _device(self):
+        return "cuda:%d" % self.sp.device if self.sp.device >= 0 else "cpu"
+
+    def analyse_grid(self, ug, vg, tg, qg, psg, out=None, use=None):
         """The increments (du, dv, dt, dq, dps) of a gridded ensemble: ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] float64
         device tensors; out: five tensors of those shapes to write into (they may be the inputs), by default fresh ones.
-        Two launches, three at a weight stride other than (1, 1); capturable when `out` is given."""
+        Two launches, three at a weight stride other than (1, 1); capturable when `out` is given.
+        use: None (all members), or a sequence or a contiguous int32 device tensor of nmem entries, non-zero = in use (include/spdy.h,
+        "member mask"): the n members in use get the increments an n-member Letkf gives them, bit for bit, the others exactly 0.0
+        and are not read into anything shared; n < 2: all zero.  One launch more; the tensor is read when the kernels run, so a
+        captured call follows its contents."""
         import torch
         sp, E = self.sp, self.nmem
+        use = use_mask(use, E, self._device())
         x = (ug, vg, tg, qg, psg)
         shp = [(E, sp.kx) + sp.grid_shape] * 4 + [(E,) + sp.grid_shape]
         if out is None:
@@ -171,11 +198,21 @@ class Letkf(PlanObject):
                 raise ValueError("analyse_grid: expected a contiguous float64 tensor of shape %s, got %s" % (s, tuple(a.shape)))
         if sp.device >= 0:
             sp._sync_stream()
-        check(self.lib.spdy_letkf_analyse_grid_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in x + tuple(out)]))
+        ptrs = [ctypes.c_void_p(a.data_ptr()) for a in x + tuple(out)]
+        if use is None:
+            check(self.lib.spdy_letkf_analyse_grid_dev(self.h, *ptrs))
+        else:
+            check(self.lib.spdy_mask_letkf_analyse_grid_dev(self.h, *ptrs, ctypes.c_void_p(use.data_ptr())))
         return tuple(out)
 
-    def analyse_dev(self, vor, div, t, q, ps):
-        """spdy_ens_letkf_dev: time level 1 of an ensemble, in place (Ensemble.analyse)"""
+    def analyse_dev(self, vor, div, t, q, ps, use=None):
+        """spdy_ens_letkf_dev: time level 1 of an ensemble, in place (Ensemble.analyse); use: as analyse_grid's, the members not in
+        use keep every bit (spdy_mask_ens_letkf_dev)"""
+        use = use_mask(use, self.nmem, self._device())
         if self.sp.device >= 0:
             self.sp._sync_stream()
-        check(self.lib.spdy_ens_letkf_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]))
+        ptrs = [ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]
+        if use is None:
+            check(self.lib.spdy_ens_letkf_dev(self.h, *ptrs))
+        else:
+            check(self.lib.spdy_mask_ens_letkf_dev(self.h, *ptrs, ctypes.c_void_p(use.data_ptr())))

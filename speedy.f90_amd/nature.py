@@ -13,6 +13,7 @@ import ctypes
 
 from ._lib import check
 from .columns import DeviceField, PlanObject
+from .letkf import use_mask
 
 _FIELDS = {"truth": lambda n: (4 * n.sp.kx + 1,) + n.sp.grid_shape, "scores": lambda n: (n.capacity, 3, 4 * n.sp.kx + 1),
            "state": lambda n: (2,)}   # device field -> its shape for a Nature n, all float64
@@ -65,27 +66,41 @@ class Nature(PlanObject):
         self._sync()
         check(self.lib.spdy_nature_observe_dev(self.h, letkf.h, float(noise)))
 
-    def verify(self, letkf, vor, div, t, q, ps, slot=0):
+    def _device(self):
+        return "cuda:%d" % self.sp.device if self.sp.device >= 0 else "cpu"
+
+    def verify(self, letkf, vor, div, t, q, ps, slot=0, use=None):
         """Scores time level 1 of an ensemble of letkf.nmem members (vor .. q [nmem, kx, nx, mx], ps [nmem, nx, mx]) against the
         truth into scores[slot]; uses letkf's grid workspace, which the next analysis overwrites anyway.  Three launches;
-        capturable.  Ensemble.verify passes the ensemble's arrays."""
+        capturable.  Ensemble.verify passes the ensemble's arrays.  use: None, or the member mask (include/spdy.h, "member mask"; a
+        sequence or a contiguous int32 device tensor of nmem entries): mean error, bias and spread over the members in use only;
+        one of them gives spread 0, none NaN."""
         if getattr(letkf, "sp", None) is not self.sp:
             raise ValueError("verify: the Letkf must belong to the nature run's plan")
+        use = use_mask(use, letkf.nmem, self._device())
         ptrs = self._spectra("verify", (vor, div, t, q, ps), (letkf.nmem,))
         self._sync()
-        check(self.lib.spdy_nature_verify_dev(self.h, letkf.h, *ptrs, int(slot)))
+        if use is None:
+            check(self.lib.spdy_nature_verify_dev(self.h, letkf.h, *ptrs, int(slot)))
+        else:
+            check(self.lib.spdy_mask_nature_verify_dev(self.h, letkf.h, *ptrs, ctypes.c_void_p(use.data_ptr()), int(slot)))
 
-    def verify_grid(self, ug, vg, tg, qg, psg, slot=0):
+    def verify_grid(self, ug, vg, tg, qg, psg, slot=0, use=None):
         """Scores an ensemble that is on the grid already (ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] float64 device tensors,
-        Letkf.analyse_grid's layout) into scores[slot].  Two launches; capturable."""
+        Letkf.analyse_grid's layout) into scores[slot].  Two launches; capturable.  use: as verify's."""
         import torch
         sp, E = self.sp, int(psg.shape[0])
+        use = use_mask(use, E, self._device())
         x = (ug, vg, tg, qg, psg)
         for a, s in zip(x, [(E, sp.kx) + sp.grid_shape] * 4 + [(E,) + sp.grid_shape]):
             if tuple(a.shape) != s or a.dtype != torch.float64 or not a.is_contiguous():
                 raise ValueError("verify_grid: expected a contiguous float64 tensor of shape %s, got %s" % (s, tuple(a.shape)))
         self._sync()
-        check(self.lib.spdy_nature_verify_grid_dev(self.h, E, *[ctypes.c_void_p(a.data_ptr()) for a in x], int(slot)))
+        ptrs = [ctypes.c_void_p(a.data_ptr()) for a in x]
+        if use is None:
+            check(self.lib.spdy_nature_verify_grid_dev(self.h, E, *ptrs, int(slot)))
+        else:
+            check(self.lib.spdy_mask_nature_verify_grid_dev(self.h, E, *ptrs, ctypes.c_void_p(use.data_ptr()), int(slot)))
 
     def field(self, name):
         """A DeviceField in the object's own memory (NATURE_FIELDS): truth [4 kx + 1, il, ix] (u, v, t, q by level, then ps),

@@ -41,7 +41,10 @@ the number of coarse columns and the byte count of that kernel's reads -- per gr
 stencil entry of non-zero weight, and the members' values -- to set against its time from a kernel trace.  --at-pressure adds the
 analysis of the same stations with u, v, t and q given at the pressures p0 fsg[k] instead of on the levels k (include/spdy.h,
 "observations at a pressure"): the observation kernel that interpolates per member in the plain one's place, the
-same launch count; the row has the number of observations that are in column on the starting state.
+same launch count; the row has the number of observations that are in column on the starting state.  --mask K [K ...] adds, for
+every K, the analysis under a member mask that drops the last K members (K = half: E / 2; K = 0: the masked call with every member
+in use, the price of the indirection alone; include/spdy.h, "member mask"): one launch more, and the local problems
+of E - K members in the launch shape of E.  Set them against the plain analysis of E - K members: --members 31 15 3 16 8 2.
 
 --osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
 to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
@@ -67,6 +70,8 @@ float32 grids written; and the surface-pressure row.
     python tools/ensemble_rate.py --letkf --json profiles/ensemble_letkf_rate.json
     python tools/ensemble_rate.py --letkf --stride 2 2
     python tools/ensemble_rate.py --letkf --at-pressure --members 4 32 --json profiles/ensemble_letkf_pobs_rate.json
+    python tools/ensemble_rate.py --letkf --mask 0 1 half
+    SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --letkf --earlier-library --label parent
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
     python tools/ensemble_rate.py --pressure --json profiles/ensemble_pressure_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --coupled --earlier-library --label parent"""
@@ -563,7 +568,7 @@ def host_observations(sp, lt, tr, cols, err, repeats):
     return float(np.median(us[1:])), min(us[1:]), max(us[1:])
 
 
-def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False):
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=()):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
     of the nature run's observe and verify, and the host route to the same observation values; at_pressure: and of the analysis of
     the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged"""
@@ -592,7 +597,7 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
     cols = [np.tile(var, nloc), np.tile(lev, nloc), np.repeat(lon.ravel(), per), np.repeat(lat.ravel(), per)]
     nobs = nloc * per
     rng = np.random.default_rng(0)
-    fns, nodes, rearms, keep, interp, host, used, pressure_objects = {}, {}, [], [], {}, {}, {}, []
+    fns, nodes, rearms, keep, interp, host, used, pressure_objects, mask_objects = {}, {}, [], [], {}, {}, {}, [], []
     for E in members:
         # the members: the case's state plus a hundredth of the differences between seeded states (0.3 K in t)
         ms = ensemblestep.member_states(sp, E + 1)
@@ -618,6 +623,14 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
         with sp.graph_capture() as g:
             en.analyse(lt)
         fns["analysis E=%d" % E], nodes["analysis E=%d" % E] = g.launch, g.num_nodes()
+        for K in sorted({E // 2 if m == "half" else int(m) for m in masks}):
+            use = torch.ones(E, dtype=torch.int32, device="cuda")
+            use[E - K:] = 0                                   # the last K members are not in use
+            with sp.graph_capture() as gm:
+                en.analyse(lt, use=use)
+            name = "analysis E=%d mask K=%d" % (E, K)
+            fns[name], nodes[name] = gm.launch, gm.num_nodes()
+            mask_objects.append((use, gm))
         if at_pressure:
             ltp = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, **({} if stride == (1, 1) else {"weight_stride": stride}))
             ltp.set_obs(cols[0], np.where(cols[0] == 4, 0, s.OBS_AT_P), cols[2], cols[3], lt.field("value").numpy(), spread,
@@ -667,6 +680,8 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
             row.update(stride=list(stride), **interp.get(E, {}))
             if name.startswith("analysis at p"):
                 row.update(observations_in_column=used[E])
+            if " mask K=" in name:
+                row.update(members_used=E - int(name.split("K=")[1]))
             cycle = 36 * t["step E=%d physics" % E][0]
             row.update(us_36_steps=round(cycle, 1), analysis_share_of_cycle=round(med / (med + cycle), 4))
         if name.startswith(("observe", "verify")):
@@ -679,6 +694,8 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                "us_min": round(lo, 1), "us_max": round(hi, 1), "clock": "wall", "times_observe": round(med / t["observe E=%d" % E][0], 1)}
         rows.append(row)
         print(json.dumps(row), flush=True)
+    for _, gm in mask_objects:
+        gm.close()
     for _, lt, _, g, gs in keep:
         g.close(); gs.close(); lt.close()
     for ltp, gp in pressure_objects:
@@ -697,6 +714,7 @@ def main():
     ap.add_argument("--letkf", action="store_true")
     ap.add_argument("--osse", action="store_true")
     ap.add_argument("--at-pressure", action="store_true")
+    ap.add_argument("--mask", nargs="+", default=[], metavar="K")
     ap.add_argument("--pressure", action="store_true")
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
@@ -720,7 +738,7 @@ def main():
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
             if a.letkf:
-                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure)
+                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure, a.mask)
             elif a.pressure:
                 run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:
