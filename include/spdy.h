@@ -1177,6 +1177,43 @@ int spdy_mask_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const doub
 int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use);
 int spdy_mask_from_diagnostics_dev(spdy_diagnostics *d, int *d_use);
 
+/* ---- ensemble analysis, relaxation to the prior perturbations and spread ----------------------------------------
+ * rho of spdy_letkf_set_localization inflates every column, observed or not.  Relaxation (RTPP: Zhang et al. 2004; RTPS: Whitaker
+ * and Hamill 2012) acts where the analysis acted and is exactly 1 elsewhere.  tests/letkfrelax.py restates this section in NumPy.
+ * It acts on the raw increments dx an analysis call forms, grid item by grid item; an item is one variable, one level and one
+ * column, (4 kx + 1) per column in the order u | v | t | q | ps.  U: the members in use, all nmem without a mask, otherwise the
+ * mask's ("member mask" above); n = |U|; every sum runs over U in ascending member order, every operation is one IEEE operation,
+ * nothing is contracted:
+ *     xm  = (sum x_e) / n            b_e = x_e - xm
+ *     dm  = (sum dx_e) / n           a_e = b_e + (1 - rtpp) (dx_e - dm)          1 - rtpp is formed once, on the host
+ *     sb  = sqrt((sum b_e^2) / (n - 1))
+ *     sa  = sqrt((sum a_e^2) / (n - 1))
+ *     f   = sa > 0 ? 1 + (rtps (sb - sa)) / sa : 1
+ *     dx'_e = dm + (f a_e - b_e)
+ * rtpp is applied first, rtps acts on the perturbations rtpp has relaxed; rtps = 0 gives f = 1.  A NaN propagates, as in the
+ * analysis (sa = NaN gives f = 1 and NaN increments).  A member not in use keeps the exact 0.0 the analysis writes for it and is
+ * not read; n < 2: zero increments for every member, as the masked analysis leaves them, and f = 1.  Three statements hold exactly:
+ *   untouched     an item whose raw increments are all +0.0 (a column out of every observation's range with rho = 1) has a_e = b_e
+ *                 up to the sign of a zero, so sa == sb, f == 1.0 and dx'_e == 0.0: the state keeps its bits there.
+ *   rtpp = 1      a_e = b_e, so f == 1.0 and every member in use gets the same bits, dm: only the mean moves.
+ *   both 0        the relaxation launch is not enqueued: the call has the launches, the graph nodes and the bits it always had.
+ * spdy_relax_set(l, rtpp, rtps): both finite and in [0, 1], otherwise SPDY_ERR_ARG and nothing changes.  (0, 0) is the
+ * state after create.  The values are read when an analysis call is enqueued, so a captured analysis keeps the values of its
+ * capture.  The first setting that is not (0, 0) allocates a workspace of (4 kx + 1) nmem grids for the raw increments (307 MB
+ * at T63 L16 with nmem = 32), which the object keeps from then on: that call synchronises the plan's stream and is refused with
+ * SPDY_ERR_STATE inside a capture; if the allocation fails the object is left at (0, 0).  A host-only plan stores the values and
+ * allocates nothing.  Every later setting changes two numbers and may be made at any time.  Checks: a NULL object SPDY_ERR_ARG, a
+ * destroyed plan SPDY_ERR_STATE, then rtpp, then rtps.  The call carries a prefix of its own, as spdy_pobs_set and the spdy_mask_
+ * calls do (DESIGN.md s23 says why).
+ * With a setting other than (0, 0) every analysis call -- spdy_letkf_analyse_grid_dev, spdy_ens_letkf_dev and their masked forms,
+ * at any weight stride, with any network -- has its transform or apply kernel write the raw increments into the workspace and
+ * enqueues ONE launch more, which reads the ensemble and the workspace and writes the relaxed increments where the raw ones went
+ * before; the increments may still take the place of the ensemble.  The masked form's results for the members in use are bit for
+ * bit those of the relaxed call of an n-member object on the compacted members.  Bit-reproducible run to run.
+ * spdy_letkf_field "inflation": f of every item of the latest relaxed call, (4 kx + 1) grids in the item order (ix,il each); part
+ * of the object's main block, so the name is valid on every object (zero until the first relaxed call).                          */
+int spdy_relax_set(spdy_letkf *l, double rtpp, double rtps);
+
 /* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
  * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
  * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a

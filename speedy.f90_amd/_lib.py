@@ -182,6 +182,7 @@ SIGNATURES = {
     "spdy_letkf_set_obs": [c_void_p, c_int, c_void_p],
     "spdy_pobs_set": [c_void_p, c_int, c_void_p],
     "spdy_letkf_set_weight_stride": [c_void_p, c_int, c_int],
+    "spdy_relax_set": [c_void_p, c_double, c_double],
     "spdy_letkf_table": [c_void_p, c_char_p, c_void_p, c_int],
     "spdy_letkf_field": [c_void_p, c_char_p, ctypes.POINTER(c_void_p)],
     "spdy_letkf_analyse_grid_dev": [c_void_p] * 11,

@@ -81,7 +81,22 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
     c.diag = (double)(l->nmem - 1) / l->rho;
     c.colunit = l->d_colunit; c.lnfsg = l->d_lnfsg; c.ounit = l->d_ounit; c.olns = l->d_olns; c.rinv = l->d_rinv;
     c.y = l->d_y; c.dep = l->d_dep;
-    for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = dx[v]; }
+    // relaxation: the transform or apply kernel writes the raw increments into the object's workspace, one launch more relaxes
+    // them into dx (which may be x).  Both values 0: dx is written as always and nothing more is enqueued.
+    const bool relaxed = l->rtpp != 0.0 || l->rtps != 0.0;
+    if (relaxed && !l->d_raw) return fail(SPDY_ERR_STATE, "letkf: relaxation is on without its workspace");
+    double *raw[spdy::LETKF_VARS];
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) raw[v] = relaxed ? l->d_raw + (size_t)v * l->nmem * kx * ncol : dx[v];
+    auto relax = [&]() -> int {
+        if (!relaxed) return SPDY_OK;
+        spdy::LetkfRelax r{};
+        r.nmem = l->nmem; r.kx = kx; r.ncol = ncol; r.omr = 1.0 - l->rtpp; r.rtps = l->rtps;
+        r.inflation = l->d_infl; r.umap = umap;
+        for (int v = 0; v < spdy::LETKF_VARS; ++v) { r.x[v] = x[v]; r.raw[v] = raw[v]; r.dx[v] = dx[v]; }
+        KERNEL(spdy::launch_letkf_relax(r, p->stream));
+        return SPDY_OK;
+    };
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = raw[v]; }
     if (l->npobs) {
         // observations at a pressure: the kernel that interpolates per member, in letkf_obs_kernel's place; it writes ln sigma_o of
         // those observations into olns and this call's copy of rinv, 0 where an observation is out of its column
@@ -103,16 +118,19 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
         }
         return SPDY_OK;
     };
-    if (!l->d_tw) return transform();
+    if (!l->d_tw) {
+        RC(transform());
+        return relax();
+    }
     // weight interpolation: T of the coarse columns, then the increments of every column from them
     c.nlist = (int)l->interp.coarse.size(); c.cols = l->d_coarse; c.tw = l->d_tw;
     spdy::LetkfApply ap{};
     ap.nmem = l->nmem; ap.kx = kx; ap.ncol = ncol; ap.nlist = c.nlist;
     ap.iidx = l->d_iidx; ap.iwgt = l->d_iwgt; ap.tw = l->d_tw;
-    for (int v = 0; v < spdy::LETKF_VARS; ++v) { ap.x[v] = x[v]; ap.dx[v] = dx[v]; }
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) { ap.x[v] = x[v]; ap.dx[v] = raw[v]; }
     RC(transform());
     KERNEL(spdy::launch_letkf_apply(ap, p->stream, umap));
-    return SPDY_OK;
+    return relax();
 }
 
 // the coarse columns of a stride and every grid column's stencil in them (include/spdy.h, "ensemble analysis": weight interpolation)
@@ -334,7 +352,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
 int spdy_letkf_destroy(spdy_letkf *l)
 {
     if (!l) return SPDY_OK;
-    retire(l, {l->d_tw, l->d_grid});
+    retire(l, {l->d_tw, l->d_raw, l->d_grid});
     delete l;
     return SPDY_OK;
 }
@@ -346,6 +364,34 @@ int spdy_letkf_set_localization(spdy_letkf *l, double sigma_h, double sigma_v, d
     if (!std::isfinite(sigma_v)) return fail(SPDY_ERR_ARG, "letkf: sigma_v must be finite (<= 0: no vertical localisation)");
     if (!(rho > 0.0) || !std::isfinite(rho)) return fail(SPDY_ERR_ARG, "letkf: rho must be finite and > 0");
     l->sigma_h = sigma_h; l->sigma_v = sigma_v; l->rho = rho; l->loc_set = true;
+    return SPDY_OK;
+}
+
+int spdy_relax_set(spdy_letkf *l, double rtpp, double rtps)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!(rtpp >= 0.0 && rtpp <= 1.0)) return fail(SPDY_ERR_ARG, "relax_set: rtpp must lie in [0, 1]");
+    if (!(rtps >= 0.0 && rtps <= 1.0)) return fail(SPDY_ERR_ARG, "relax_set: rtps must lie in [0, 1]");
+    spdy_plan *p = l->plan;
+    if ((rtpp != 0.0 || rtps != 0.0) && p->device >= 0 && !l->d_raw) {
+        // the first non-zero setting: the workspace of the raw increments, zeroed once so that no call ever reads what it did not write
+        NOT_CAPTURING(p, "spdy_relax_set (allocation)");
+        HIP_TRY(hipSetDevice(p->device));
+        size_t bytes = 0;
+        auto all = [&]() -> int {
+            RC(dev_carve(p, [&](auto &&v) { l->relax_arrays(v, grid_elems(p), (size_t)p->tab.kx); }, &bytes));
+            HIP_TRY(hipMemsetAsync(l->d_raw, 0, bytes, p->stream));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            return SPDY_OK;
+        };
+        if (const int rc = all()) {
+            (void)dev_release(p, l->d_raw);
+            l->relax_arrays(Carve{});
+            l->rtpp = l->rtps = 0.0;              // the object is left at (0, 0)
+            return rc;
+        }
+    }
+    l->rtpp = rtpp; l->rtps = rtps;
     return SPDY_OK;
 }
 
@@ -418,7 +464,8 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
     static const struct { const char *name; double *spdy_letkf::*ptr; } fields[] = {
         {"hx", &spdy_letkf::d_hx}, {"hxmean", &spdy_letkf::d_hxmean}, {"y", &spdy_letkf::d_y}, {"departure", &spdy_letkf::d_dep},
         {"weights", &spdy_letkf::d_tw}, {"value", &spdy_letkf::d_value}, {"grid", &spdy_letkf::d_grid},
-        {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}, {"members_used", &spdy_letkf::d_nused}};
+        {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}, {"members_used", &spdy_letkf::d_nused},
+        {"inflation", &spdy_letkf::d_infl}};
     const auto *f = std::find_if(std::begin(fields), std::end(fields), [&](const auto &t) { return !std::strcmp(name, t.name); });
     if (f == std::end(fields)) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f->ptr == &spdy_letkf::d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");

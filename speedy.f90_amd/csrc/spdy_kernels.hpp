@@ -603,6 +603,19 @@ struct LetkfAdd {
     const double *src[LETKF_VARS];
 };
 hipError_t launch_spec_add(const LetkfAdd &a, hipStream_t s);
+// Relaxation to the prior perturbations and spread (include/spdy.h, "relaxation"): one launch over the (4 kx + 1)
+// ncol grid items after the increments have been formed.  raw: the increments as the transform or apply kernel wrote them; dx: the
+// relaxed increments, which may be x (never raw); inflation [(4 kx + 1)][ncol]: the factor f of every item.
+struct LetkfRelax {
+    int nmem, kx, ncol;
+    double omr, rtps;                                // 1 - rtpp, formed on the host; rtps
+    const double *x[LETKF_VARS];
+    const double *raw[LETKF_VARS];
+    double *dx[LETKF_VARS];
+    double *inflation;
+    const int *umap;                                 // NULL, or the member mask's table
+};
+hipError_t launch_letkf_relax(const LetkfRelax &a, hipStream_t s);
 
 // The nature run (csrc/spdy_nature.hip; include/spdy.h, "nature run").  The truth is one member of the analysis'
 // gridded layout: row f = v * kx + k of u, v, t, q, then ps, (4 kx + 1) grids.  state = {seed, draws}.

@@ -626,6 +626,83 @@ __global__ __launch_bounds__(LETKF_BLOCK) void spec_add_kernel(const LetkfAdd a)
     if (d != 0.0) a.dst[op][i] = a.dst[op][i] + d;
 }
 
+// Relaxation of the raw increments (include/spdy.h, "relaxation"): one lane per grid item, blockIdx.y the item's
+// field (variable and level, u | v | t | q | ps), the columns across the lanes, so every member's load is coalesced.  The members'
+// values stay in registers under their compact index c < n: every loop over them is unrolled to LETKF_MAX_MEMBERS and leaves at
+// c == n, which is the same for the whole launch, so no register index is a run-time one, nothing goes to scratch and no
+// predicate has to be kept (a bit per member, tested in every loop, cost 52 spilled SGPRs).  All of an item's x and raw values are
+// loaded before the first sum and long before the first store: dx may be x.  MASK (the member mask, a.umap): n and the member of
+// each compact index come from the table instead of nmem; a member not in use is not read and gets 0.0, and so does every member
+// when n < 2.  One body, two instantiations.  No atomics, the sums in ascending member order.
+template <bool MASK>
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_relax_kernel(const LetkfRelax a)
+{
+#pragma clang fp contract(off)
+    const int col = blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (col >= a.ncol) return;
+    const int item = blockIdx.y, kx = a.kx, ncol = a.ncol, E = a.nmem;
+    const int v = item < 4 * kx ? item / kx : 4, k = item - v * kx;
+    // the variable's fields by selects, as letkf_pobs_kernel does it
+    const double *const xv = v == 0 ? a.x[0] : v == 1 ? a.x[1] : v == 2 ? a.x[2] : v == 3 ? a.x[3] : a.x[4];
+    const double *const rv = v == 0 ? a.raw[0] : v == 1 ? a.raw[1] : v == 2 ? a.raw[2] : v == 3 ? a.raw[3] : a.raw[4];
+    double *const dv = v == 0 ? a.dx[0] : v == 1 ? a.dx[1] : v == 2 ? a.dx[2] : v == 3 ? a.dx[3] : a.dx[4];
+    const size_t at = letkf_at(v, 0, k, kx, ncol, col), step = (size_t)(v < 4 ? kx : 1) * ncol;
+    const int n = MASK ? a.umap[0] : E;
+    if constexpr (MASK) {
+        if (n < 2) {
+            for (int e = 0; e < E; ++e) dv[at + e * step] = 0.0;
+            a.inflation[(size_t)item * ncol + col] = 1.0;
+            return;
+        }
+    }
+    // compact index c stands for member m: c itself without a mask, umap[1 + c] with one; both ascending.  Without a mask the
+    // lane's own offset walks the members: 32 scalar offsets held from the loads to the stores would not fit the SGPRs
+    double x[LETKF_MAX_MEMBERS], d[LETKF_MAX_MEMBERS];
+    size_t walk = at;
+#pragma unroll
+    for (int c = 0; c < LETKF_MAX_MEMBERS; ++c) {
+        x[c] = d[c] = 0.0;
+        if (c < n) {
+            const size_t off = MASK ? at + a.umap[1 + c] * step : walk;
+            x[c] = xv[off];
+            d[c] = rv[off];
+        }
+        walk += step;
+    }
+    double sx = 0.0, sd = 0.0;
+#pragma unroll
+    for (int c = 0; c < LETKF_MAX_MEMBERS; ++c)
+        if (c < n) {
+            sx += x[c];
+            sd += d[c];
+        }
+    const double xm = sx / n, dm = sd / n;
+    double sb2 = 0.0, sa2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < LETKF_MAX_MEMBERS; ++c)
+        if (c < n) {
+            const double b = x[c] - xm, p = b + a.omr * (d[c] - dm);
+            sb2 += b * b;
+            sa2 += p * p;
+            x[c] = b;
+            d[c] = p;
+        }
+    const double sb = sqrt(sb2 / (n - 1)), sa = sqrt(sa2 / (n - 1));
+    const double f = sa > 0.0 ? 1.0 + a.rtps * (sb - sa) / sa : 1.0;
+    walk = at;
+#pragma unroll
+    for (int c = 0; c < LETKF_MAX_MEMBERS; ++c) {
+        if (c < n) dv[MASK ? at + a.umap[1 + c] * step : walk] = dm + (f * d[c] - x[c]);
+        walk += step;
+    }
+    if constexpr (MASK) {
+        // the members not in use keep the 0.0 the analysis wrote for them
+        for (int e = 0; e < E; ++e)
+            if (a.umap[LETKF_URANK + e] < 0) dv[at + e * step] = 0.0;
+    }
+    a.inflation[(size_t)item * ncol + col] = f;
+}
+
 }  // namespace
 
 size_t letkf_lds_bytes(int nmem, int kx, int nlv) { return sizeof(double) * (size_t)LetkfLds((nmem + 1) & ~1, kx, nlv).total; }
@@ -760,6 +837,21 @@ hipError_t launch_spec_add(const LetkfAdd &a, hipStream_t s)
     }
     if (!most) return hipSuccess;
     hipLaunchKernelGGL(spec_add_kernel, dim3((unsigned)((most + LETKF_BLOCK - 1) / LETKF_BLOCK), a.nops), dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_relax(const LetkfRelax &a, hipStream_t s)
+{
+    if (a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 || !a.inflation || !(a.omr >= 0.0) ||
+        !(a.omr <= 1.0) || !(a.rtps >= 0.0) || !(a.rtps <= 1.0))
+        return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!a.x[v] || !a.raw[v] || !a.dx[v]) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.ncol + LETKF_BLOCK - 1) / LETKF_BLOCK), (unsigned)(4 * a.kx + 1));
+    if (a.umap)
+        hipLaunchKernelGGL(letkf_relax_kernel<true>, grid, dim3(LETKF_BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(letkf_relax_kernel<false>, grid, dim3(LETKF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

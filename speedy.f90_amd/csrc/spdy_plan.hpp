@@ -195,7 +195,7 @@ struct spdy_letkf final : spdy_detail::PlanObject {
         v(d_grid, nf * ncol); v(d_spec, nf * ns); v(d_colunit, 3 * ncol); v(d_lnfsg, kx);
         v(d_swgt, 4 * M); v(d_ounit, 3 * M); v(d_olns, M); v(d_rinv, M); v(d_err, M); v(d_value, M);
         v(d_hx, M * E); v(d_hxmean, M); v(d_y, M * E); v(d_dep, M);
-        v(d_lnp, M); v(d_used, M); v(d_reff, M); v(d_nused, 2);
+        v(d_lnp, M); v(d_used, M); v(d_reff, M); v(d_nused, 2); v(d_infl, (4 * kx + 1) * ncol);
         v(d_sidx, 4 * M); v(d_var, M); v(d_lev, M); v(d_atp, M); v(d_umap, spdy::LETKF_UMAP);
     }
     // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
@@ -208,7 +208,17 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     {
         v(d_tw, ncoarse * kx * nmem * nmem); v(d_iwgt, 4 * ncol); v(d_iidx, 4 * ncol); v(d_coarse, ncoarse);
     }
-    void forget_device() override { arrays(spdy_detail::Carve{}); interp_arrays(spdy_detail::Carve{}); }
+    // relaxation (spdy_relax_set): read when an analysis is enqueued; both 0: the analysis launches what it always did.
+    // d_infl [(4 kx + 1)][ncol], the factor f of the latest relaxed call, is part of the main allocation.  d_raw, (4 kx + 1) nmem
+    // grids in d_grid's layout, takes the raw increments of a relaxed call: an allocation of its own, made when relaxation is first
+    // switched on and kept from then on (a captured graph may point into it)
+    double rtpp = 0.0, rtps = 0.0;
+    double *d_infl = nullptr, *d_raw = nullptr;
+    template <class V> void relax_arrays(V &&v, size_t ncol = 0, size_t kx = 0) { v(d_raw, (4 * kx + 1) * nmem * ncol); }
+    void forget_device() override
+    {
+        arrays(spdy_detail::Carve{}); interp_arrays(spdy_detail::Carve{}); relax_arrays(spdy_detail::Carve{});
+    }
 };
 
 // The nature run behind include/spdy.h's spdy_nature (csrc/spdy_api_nature.hip): one device allocation.

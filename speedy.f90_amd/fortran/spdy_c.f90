@@ -1218,6 +1218,13 @@ module spdy_c
             integer(c_int), value :: si, sj
             integer(c_int) :: rc
         end function
+        ! relaxation to the prior perturbations (rtpp) and spread (rtps), both in [0, 1]; (0, 0): none
+        function spdy_relax_set(l, rtpp, rtps) bind(C, name="spdy_relax_set") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: l
+            real(c_double), value :: rtpp, rtps
+            integer(c_int) :: rc
+        end function
         function spdy_letkf_table(l, name, buf, cap) bind(C, name="spdy_letkf_table") result(rc)
             import :: c_int, c_ptr, c_char
             type(c_ptr), value :: l, buf

@@ -9,7 +9,9 @@ set_obs(..., p=...) takes observations of u, v, t or q given at a pressure (lev 
 per member, linearly in ln p (include/spdy.h, "observations at a pressure").  After an analysis the run continues
 with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members are coupled, a non-finite member makes every
 column it touches non-finite: pass use=, a member mask on the device (Diagnostics.use_dev gives the guard's), to analyse the
-members the guard has not stopped and leave the others alone, bit for bit (include/spdy.h, "member mask")."""
+members the guard has not stopped and leave the others alone, bit for bit (include/spdy.h, "member mask").
+set_relaxation(rtpp, rtps) relaxes the analysis towards the background where observations acted, one launch more (include/spdy.h,
+"relaxation")."""
 import ctypes
 
 import numpy as np
@@ -28,7 +30,8 @@ _PER_OBS, _PER_OBS_MEMBER = (lambda l: (l.nobs,)), (lambda l: (l.nobs, l.nmem))
 _FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "departure": _PER_OBS,
            "weights": lambda l: (check(l.lib.spdy_letkf_table(l.h, b"coarse_columns", None, 0)), l.sp.kx, l.nmem, l.nmem),
            "value": _PER_OBS, "grid": lambda l: ((4 * l.sp.kx + 1) * l.nmem,) + l.sp.grid_shape,
-           "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS, "members_used": lambda l: (1,)}
+           "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS, "members_used": lambda l: (1,),
+           "inflation": lambda l: (4 * l.sp.kx + 1,) + l.sp.grid_shape}
 LETKF_TABLES, LETKF_FIELDS = tuple(_TABLES), tuple(_FIELDS)
 
 
@@ -67,11 +70,11 @@ class _DeviceView:
 
 class Letkf(PlanObject):
     """sigma_h: horizontal localisation scale in metres; sigma_v: vertical scale in ln sigma (<= 0: none); rho: multiplicative
-    inflation of the background covariance; weight_stride: set_weight_stride.  2 <= nmem <= 32; the plan needs max_batch >= nmem
-    (2 kx + 1)."""
+    inflation of the background covariance; weight_stride: set_weight_stride; rtpp, rtps: set_relaxation.  2 <= nmem <= 32; the
+    plan needs max_batch >= nmem (2 kx + 1)."""
     PREFIX = "spdy_letkf"
 
-    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1)):
+    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1), rtpp=0.0, rtps=0.0):
         self.sp, self.lib = sp, sp.lib
         if sp.device >= 0:
             sp._sync_stream()
@@ -82,6 +85,24 @@ class Letkf(PlanObject):
         self.set_localization(sigma_h, sigma_v, rho)
         if tuple(weight_stride) != (1, 1):
             self.set_weight_stride(*weight_stride)
+        self.relaxation = (0.0, 0.0)
+        if (rtpp, rtps) != (0.0, 0.0):
+            self.set_relaxation(rtpp, rtps)
+
+    def set_relaxation(self, rtpp=0.0, rtps=0.0):
+        """Relaxation of the analysis towards the background (include/spdy.h, "relaxation"), both in [0, 1]: rtpp
+        relaxes the analysis perturbations to the background perturbations (1: only the mean moves), rtps then relaxes their
+        spread to the background spread (1: the spread is restored).  Both are exactly 1 where the analysis changed nothing.
+        (0, 0), the default: none, the analysis is the one it always was.  Read when an analysis is enqueued: a captured analysis
+        keeps the values of its capture.  The first setting other than (0, 0) allocates a workspace of (4 kx + 1) nmem grids: it
+        synchronises the plan's stream and is not possible inside a capture; later settings only change the two numbers."""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        rc = self.lib.spdy_relax_set(self.h, float(rtpp), float(rtps))
+        if rc == ERR_HIP:             # the allocation failed: the object is left at (0, 0)
+            self.relaxation = (0.0, 0.0)
+        check(rc)
+        self.relaxation = (float(rtpp), float(rtps))
 
     def set_localization(self, sigma_h, sigma_v=0.0, rho=1.0):
         """read when an analysis is enqueued: a captured analysis keeps the values of its capture"""
@@ -158,7 +179,9 @@ class Letkf(PlanObject):
         call localised with (for an observation at a pressure ln(p/p0) minus the ensemble-mean ps at its place, formed in that
         call); obs_used [nobs]: 1.0, or 0.0 for an at-pressure observation that was out of some member's column in that call.
         members_used [1]: the members the latest analysis call analysed, nmem without a mask; ask for it after the call -- it is
-        one of two words, that of the kind of call (masked or not) enqueued last."""
+        one of two words, that of the kind of call (masked or not) enqueued last.  inflation [4 kx + 1, il, ix]: the factor f
+        of every grid item (u | v | t | q at kx levels, then ps) in the latest analysis call with relaxation on, exactly 1.0 where
+        the analysis changed nothing; zero until the first such call."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         return DeviceField(self.sp, p.value, _FIELDS[name](self))
@@ -179,7 +202,8 @@ class Letkf(PlanObject):
     def analyse_grid(self, ug, vg, tg, qg, psg, out=None, use=None):
         """The increments (du, dv, dt, dq, dps) of a gridded ensemble: ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] float64
         device tensors; out: five tensors of those shapes to write into (they may be the inputs), by default fresh ones.
-        Two launches, three at a weight stride other than (1, 1); capturable when `out` is given.
+        Two launches, three at a weight stride other than (1, 1), one more with relaxation on (set_relaxation: the increments are
+        then the relaxed ones, and field("inflation") holds their factors); capturable when `out` is given.
         use: None (all members), or a sequence or a contiguous int32 device tensor of nmem entries, non-zero = in use (include/spdy.h,
         "member mask"): the n members in use get the increments an n-member Letkf gives them, bit for bit, the others exactly 0.0
         and are not read into anything shared; n < 2: all zero.  One launch more; the tensor is read when the kernels run, so a
@@ -207,7 +231,8 @@ class Letkf(PlanObject):
 
     def analyse_dev(self, vor, div, t, q, ps, use=None):
         """spdy_ens_letkf_dev: time level 1 of an ensemble, in place (Ensemble.analyse); use: as analyse_grid's, the members not in
-        use keep every bit (spdy_mask_ens_letkf_dev)"""
+        use keep every bit (spdy_mask_ens_letkf_dev).  With relaxation on (set_relaxation) the increments are relaxed on the grid,
+        one launch more, before they go back to spectra."""
         use = use_mask(use, self.nmem, self._device())
         if self.sp.device >= 0:
             self.sp._sync_stream()

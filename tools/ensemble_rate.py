@@ -45,6 +45,12 @@ same launch count; the row has the number of observations that are in column on 
 every K, the analysis under a member mask that drops the last K members (K = half: E / 2; K = 0: the masked call with every member
 in use, the price of the indirection alone; include/spdy.h, "member mask"): one launch more, and the local problems
 of E - K members in the launch shape of E.  Set them against the plain analysis of E - K members: --members 31 15 3 16 8 2.
+--relax RTPP RTPS adds the analysis of the same network by an object with relaxation on (include/spdy.h, "relaxation"; DESIGN.md
+s24), next to the one with relaxation off in the same run: one launch more; the row has the difference of the two medians, the
+relaxation kernel's bytes -- the ensemble and the raw increments read, the relaxed increments and the factors written -- and
+their time at 8 TB/s.  Replays of Ensemble.analyse analyse the state the replay before left, which a relaxed ensemble changes, so
+that pair of rows compares two different workloads; the pair "grid analysis" / "grid analysis relaxed" replays Letkf.analyse_grid
+of both objects on one gridded ensemble, the start state's, and its difference is the relaxation's own cost.
 
 --osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
 to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
@@ -71,6 +77,7 @@ float32 grids written; and the surface-pressure row.
     python tools/ensemble_rate.py --letkf --stride 2 2
     python tools/ensemble_rate.py --letkf --at-pressure --members 4 32 --json profiles/ensemble_letkf_pobs_rate.json
     python tools/ensemble_rate.py --letkf --mask 0 1 half
+    python tools/ensemble_rate.py --letkf --relax 0 0.9 --json profiles/ensemble_letkf_relax_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --letkf --earlier-library --label parent
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
     python tools/ensemble_rate.py --pressure --json profiles/ensemble_pressure_rate.json
@@ -568,10 +575,11 @@ def host_observations(sp, lt, tr, cols, err, repeats):
     return float(np.median(us[1:])), min(us[1:]), max(us[1:])
 
 
-def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=()):
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=(), relax=None):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
     of the nature run's observe and verify, and the host route to the same observation values; at_pressure: and of the analysis of
-    the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged"""
+    the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged; relax
+    = (rtpp, rtps): and of the analysis of the same network by an object with that relaxation on"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
     build()
@@ -645,6 +653,30 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                 en.analyse(ltp)
             fns["analysis at p E=%d" % E], nodes["analysis at p E=%d" % E] = gp.launch, gp.num_nodes()
             pressure_objects.append((ltp, gp))
+        if relax is not None:
+            ltr = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, rtpp=relax[0], rtps=relax[1],
+                          **({} if stride == (1, 1) else {"weight_stride": stride}))
+            ltr.set_obs(*cols, lt.field("value").numpy(), spread)
+            with sp.graph_capture() as gr:
+                en.analyse(ltr)
+            fns["analysis relaxed E=%d" % E], nodes["analysis relaxed E=%d" % E] = gr.launch, gr.num_nodes()
+            pressure_objects.append((ltr, gr))
+            # Replays of Ensemble.analyse analyse the state the replay before left, and a relaxed ensemble keeps another spread
+            # than an unrelaxed one: the two graphs above do different work in the Jacobi sweeps.  The relaxation's own cost is the
+            # difference of Letkf.analyse_grid on ONE gridded ensemble, the start state's, which every replay reads again
+            nat = s.Nature(sp, capacity=1)
+            en.verify(ltr, nat, 0)
+            torch.cuda.synchronize()
+            grid = torch.from_numpy(ltr.field("grid").numpy()).cuda()
+            L = E * kx
+            xs = [grid[v * L:(v + 1) * L].reshape((E, kx) + sp.grid_shape) for v in range(4)] + [grid[4 * L:]]
+            out = [torch.empty_like(a) for a in xs]
+            nat.close()
+            for name, obj in (("grid analysis E=%d" % E, lt), ("grid analysis relaxed E=%d" % E, ltr)):
+                with sp.graph_capture() as gg:
+                    obj.analyse_grid(*xs, out=out)
+                fns[name], nodes[name] = gg.launch, gg.num_nodes()
+                mask_objects.append(((xs, out), gg))
         if stride != (1, 1):
             terms = int(np.count_nonzero(lt.table("interp_weight")))
             interp[E] = {"coarse_columns": int(lt.table("coarse_columns").size),
@@ -684,6 +716,13 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                 row.update(members_used=E - int(name.split("K=")[1]))
             cycle = 36 * t["step E=%d physics" % E][0]
             row.update(us_36_steps=round(cycle, 1), analysis_share_of_cycle=round(med / (med + cycle), 4))
+        if "relaxed" in name:
+            # next to the unrelaxed form of the same call: the difference of two graph replays; the relaxation kernel's bytes:
+            # the ensemble and the raw increments read, the relaxed increments and the factors written
+            extra = med - t[name.replace(" relaxed", "")][0]
+            moved = 8 * (3 * E + 1) * (4 * kx + 1) * sp.il * sp.ix
+            row.update(rtpp=relax[0], rtps=relax[1], us_over_unrelaxed=round(extra, 2), relax_bytes=moved,
+                       relax_us_at_hbm_peak=round(moved / HBM * 1e6, 2))
         if name.startswith(("observe", "verify")):
             cycle = 36 * t["step E=%d physics" % E][0] + t["analysis E=%d" % E][0]
             row.update(us_cycle=round(cycle, 1), share_of_cycle=round(med / cycle, 5))
@@ -716,6 +755,7 @@ def main():
     ap.add_argument("--at-pressure", action="store_true")
     ap.add_argument("--mask", nargs="+", default=[], metavar="K")
     ap.add_argument("--pressure", action="store_true")
+    ap.add_argument("--relax", nargs=2, type=float, metavar=("RTPP", "RTPS"))
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
@@ -738,7 +778,8 @@ def main():
     with torch.cuda.stream(torch.cuda.Stream()):      # the plan follows torch's stream: captures are legal, the events sit on it
         for tag in a.sizes:
             if a.letkf:
-                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure, a.mask)
+                run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure, a.mask,
+                          tuple(a.relax) if a.relax else None)
             elif a.pressure:
                 run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:

@@ -1,6 +1,7 @@
 /* Host check of the observation ingestion (include/spdy.h, "ensemble analysis"): spdy_letkf_set_obs and spdy_letkf_table on a
  * host-only plan, fed the operator's edge cases, nobs = 0 and nobs = max_obs; and of the tables of weight interpolation
- * (spdy_letkf_set_weight_stride) at the smallest and largest strides and with a short last latitude interval.  Built by `make hostcheck` in speedy.f90_amd with
+ * (spdy_letkf_set_weight_stride) at the smallest and largest strides and with a short last latitude interval; and of
+ * spdy_relax_set's rejections and its setting on a host-only plan.  Built by `make hostcheck` in speedy.f90_amd with
  * the address and undefined-behaviour sanitizers on the host code of the plan, the tables and the analysis; exits 0 when every
  * stencil is a convex combination of four grid points and every rejection is the documented code. */
 #include <math.h>
@@ -118,6 +119,16 @@ int main(void)
     CHECK(spdy_letkf_set_weight_stride(l, 96, 1) == SPDY_ERR_ARG && spdy_letkf_set_weight_stride(l, 0, 1) == SPDY_ERR_ARG);
     CHECK(spdy_letkf_set_weight_stride(l, 2, 0) == SPDY_ERR_ARG && spdy_letkf_set_weight_stride(l, 2, 2 * IY) == SPDY_ERR_ARG);
     CHECK(interp_ok(l, 3, 5, IX, 2 * IY));
+    /* relaxation: a host-only plan stores a setting and allocates nothing; each argument alone is refused outside [0, 1] */
+    static const double outside[4] = {NAN, -0.1, 1.5, INFINITY};
+    CHECK(spdy_relax_set(NULL, 0.5, 0.5) == SPDY_ERR_ARG);
+    CHECK(spdy_relax_set(l, 0.3, 0.9) == SPDY_OK && spdy_relax_set(l, 1.0, 1.0) == SPDY_OK);
+    for (int n = 0; n < 4; ++n) {
+        CHECK(spdy_relax_set(l, outside[n], 0.5) == SPDY_ERR_ARG);
+        CHECK(spdy_relax_set(l, 0.5, outside[n]) == SPDY_ERR_ARG);
+    }
+    CHECK(spdy_relax_set(l, 0.0, 0.0) == SPDY_OK);
+    CHECK(spdy_letkf_field(l, "inflation", &d) == SPDY_ERR_NO_DEVICE);
     CHECK(spdy_letkf_destroy(l) == SPDY_OK && spdy_plan_destroy(p) == SPDY_OK);
     printf("letkf host check ok: %d edge observations, 0 and %d observations\n", npts, (int)MAXOBS);
     return 0;
