@@ -1214,6 +1214,87 @@ int spdy_mask_from_diagnostics_dev(spdy_diagnostics *d, int *d_use);
  * of the object's main block, so the name is valid on every object (zero until the first relaxed call).                          */
 int spdy_relax_set(spdy_letkf *l, double rtpp, double rtps);
 
+/* ---- ensemble analysis, observations in time slots -----------------------------------------------------------------
+ * The calls above take every observation as valid at the analysis time.  With these an observation is compared with each member's
+ * forecast at the observation's own time, and one update uses all of them: the 4D-LETKF (Hunt et al. 2004; Hunt, Kostelich and
+ * Szunyogh 2007, s4).  What is kept from an observation's time is per member only; everything that couples members is formed once,
+ * at analysis time.  tests/letkfslots.py restates this section in NumPy.
+ *   slots         the observations of the current network (spdy_letkf_set_obs or spdy_pobs_set) are divided into S contiguous
+ *                 ranges by first[0..S]: first[0] = 0, first non-decreasing, first[S] = nobs; observation o is of slot s iff
+ *                 first[s] <= o < first[s+1]; a slot may be empty; 1 <= S <= SPDY_MAX_SLOTS.  The order of the observations is not
+ *                 touched: every sum over observations stays "o ascending".
+ *   observing     a slot on an ensemble, for every observation o of the slot and every member e of nmem, in use later or not:
+ *                 hx[o][e], the operator of "ensemble analysis" for a model-level or PS observation, that of "observations at a
+ *                 pressure" for one at a pressure, every operation in that section's order -- the bits the plain analysis call
+ *                 writes for the same member and state.  Only when the network holds an at-pressure observation (npobs > 0) also
+ *                     slot_ps[o][e]  = ((w0 ps_e[i0] + w1 ps_e[i1]) + w2 ps_e[i2]) + w3 ps_e[i3]            the pb_e of that section
+ *                     slot_out[o][e] = 1.0 if o is at a pressure and for some of its four points x_o < X_0 or x_o > X_{kx-1} with
+ *                                      this member's ps, else 0.0; a target on an end level is in the column, a non-finite ps
+ *                                      rejects nothing.
+ *                 Nothing outside the slot's rows of these three arrays is written, and nothing per observation: hxmean, y,
+ *                 departure, obs_lnsigma, obs_used and the per-call 1/error^2 stay as they are.
+ *   analysis      an analysis call whose observation kernel is replaced by the finish kernel.  U: the members in use, all nmem
+ *                 without a mask, otherwise the mask's ("member mask"); n = |U|; every sum over U ascending, by select:
+ *                     hxmean_o = (sum_U hx[o][e]) / n        y[o][e] = e in U ? hx[o][e] - hxmean_o : 0.0
+ *                     d_o      = value_o - hxmean_o          value as it stands when the kernel runs
+ *                 and only when npobs > 0, ln sigma_o only for an at-pressure o:
+ *                     ln sigma_o = x_o - (sum_U slot_ps[o][e]) / n
+ *                     used_o   = (any e in U with slot_out[o][e] != 0) ? 0.0 : 1.0        reff_o = used_o ? rinv_o : 0.0
+ *                 Everything after it is the analysis as it is -- transform, apply, relaxation, direct batch, spectral add -- masked
+ *                 or not, at any weight stride, with any relaxation: C = sum_o r_o Y_o Y_o^T and b = sum_o r_o Y_o d_o with Y from
+ *                 the slots' times, the increments dx_e = sum_f (x_f - xmean) T[f][e] on the ensemble passed to the analysis call.
+ *                 For an at-pressure observation the vertical localisation and the out-of-column test use the surface pressure of
+ *                 the slot's time: that is where the observation was.  n < 2: as under "member mask".
+ * Four statements hold exactly:
+ *   same state    if every non-empty slot was observed on the ensemble the slot analysis then gets, with the same mask, stride and
+ *                 relaxation, the increments are bit for bit those of the plain call, and so are hx, hxmean, y, departure,
+ *                 obs_lnsigma, obs_used, members_used, inflation and weights.
+ *   isolation     observing slot s leaves every bit of the rows of hx, slot_ps and slot_out outside [first[s], first[s+1]) and of
+ *                 every per-observation array; observing it again on another ensemble changes those rows only.
+ *   late mask     a member the mask of the analysis call drops may hold NaN in its rows from any slot on: it enters nothing, and
+ *                 the members in use get the bits of an n-member object that observed the same slots on the compacted members.
+ *   one slot      S = 1 with first = {0, nobs}, observed on the analysed ensemble, is "same state"; a network with nobs == 0 gives
+ *                 the plain call's result, zero increments at rho = 1.
+ * spdy_slot_set(l, nslots, first): first has nslots + 1 entries; (0, NULL) returns the object to "no slots".  Host only, works on a
+ * host-only plan, allocates nothing, may be called at any time.  The ranges are launch arguments, read when a call is enqueued: a
+ * captured graph keeps the ranges of its capture and has to be captured again after a change.  Checks, in this order: a NULL object
+ * SPDY_ERR_ARG ("null analysis object"), a destroyed plan SPDY_ERR_STATE; nslots outside [0, SPDY_MAX_SLOTS], a NULL first with
+ * nslots > 0, first[0] != 0, a decreasing pair, first[nslots] != nobs SPDY_ERR_ARG.  A rejected call changes nothing.  The call
+ * clears every slot's "observed" mark.  spdy_letkf_set_obs and spdy_pobs_set return the object to "no slots": their nobs and order
+ * define the ranges.  spdy_letkf_table "slot_first": the nslots + 1 entries, count 0 with no slots.
+ * spdy_slot_observe_grid_dev(l, slot, ug, vg, tg, qg, psg): the slot kernel on the caller's grids (the layout of
+ * spdy_letkf_analyse_grid_dev).  spdy_slot_observe_dev(l, slot, vor, div, t, q, ps): time level 1 of the ensemble goes to the
+ * object's grid workspace by the analysis' own inverse batch ("grid" then holds the gridded ensemble of that time, as after a
+ * verify), and the slot kernel runs on it.  ONE launch after the transform: one thread per (observation of the slot, member), no
+ * LDS, no atomics.  Nothing is allocated; both are capturable.  An empty slot enqueues nothing at all and is marked observed.  No
+ * mask is needed: nothing shared is formed.  Checks: a NULL object SPDY_ERR_ARG, a destroyed plan SPDY_ERR_STATE; no slots set
+ * SPDY_ERR_STATE; slot outside [0, nslots) SPDY_ERR_ARG; a NULL pointer SPDY_ERR_ARG; a host-only plan SPDY_ERR_NO_DEVICE last.
+ * spdy_slot_analyse_grid_dev and spdy_slot_ens_letkf_dev: spdy_mask_letkf_analyse_grid_dev and spdy_mask_ens_letkf_dev as the
+ * slot analysis; d_use NULL = all members.  The checks of those calls in their order and, before the device check: no slots set
+ * SPDY_ERR_STATE; a non-empty slot not observed since the latest spdy_slot_set SPDY_ERR_STATE, the message names the slot.  The
+ * marks are host-side, set when an observe is enqueued and not cleared by an analysis, so eager cycles and captured ones work alike.
+ * Launches: those of the plain call of the same kind -- two on grids, five or six from spectra, one more at a weight stride, with
+ * relaxation, with a mask -- with the finish kernel, one thread per observation over all nobs, in the observation kernel's place.
+ * spdy_slot_nature_observe_dev(n, letkf, slot, noise): spdy_nature_observe_dev on the slot's range only -- value_o for o in the range
+ * from the current truth by the same operator (an at-pressure observation clamped as there), the same draw, Philox counter (o, 0,
+ * draws), then draws += 1; values outside the range keep their bits; an empty slot writes nothing and still counts.  Checks as
+ * spdy_nature_observe_dev's, then no slots set SPDY_ERR_STATE, slot outside [0, nslots) SPDY_ERR_ARG, the device last.
+ * spdy_letkf_field: "slot_ps", "slot_out", [nobs][nmem] each, part of the object's main block: the names are valid on every object.
+ * The window ends at the analysis time: the analysed state is whatever arrays the analysis call gets.  A window centred on the
+ * analysis time means handing spdy_slot_ens_letkf_dev a copy of the spectra kept at the centre; that is the caller's to do.
+ * The calls carry a prefix of their own, as spdy_pobs_set and the spdy_mask_ calls do (DESIGN.md s23 says why).                  */
+enum { SPDY_MAX_SLOTS = 32 };
+int spdy_slot_set(spdy_letkf *l, int nslots, const int *first);
+int spdy_slot_observe_grid_dev(spdy_letkf *l, int slot, const double *ug, const double *vg, const double *tg, const double *qg,
+                               const double *psg);
+int spdy_slot_observe_dev(spdy_letkf *l, int slot, const double *vor, const double *div, const double *t, const double *q,
+                          const double *ps);
+int spdy_slot_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
+                               double *du, double *dv, double *dt, double *dq, double *dps, const int *d_use);
+int spdy_slot_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use);
+struct spdy_nature;                   /* the nature run, "nature run" below */
+int spdy_slot_nature_observe_dev(struct spdy_nature *n, spdy_letkf *letkf, int slot, double noise);
+
 /* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
  * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
  * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a

@@ -201,6 +201,12 @@ SIGNATURES = {
     "spdy_mask_from_diagnostics_dev": [c_void_p, c_void_p],
     "spdy_mask_nature_verify_dev": [c_void_p] * 8 + [c_int],
     "spdy_mask_nature_verify_grid_dev": [c_void_p, c_int] + [c_void_p] * 6 + [c_int],
+    "spdy_slot_set": [c_void_p, c_int, c_void_p],
+    "spdy_slot_observe_grid_dev": [c_void_p, c_int] + [c_void_p] * 5,
+    "spdy_slot_observe_dev": [c_void_p, c_int] + [c_void_p] * 5,
+    "spdy_slot_analyse_grid_dev": [c_void_p] * 12,
+    "spdy_slot_ens_letkf_dev": [c_void_p] * 7,
+    "spdy_slot_nature_observe_dev": [c_void_p, c_void_p, c_int, c_double],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

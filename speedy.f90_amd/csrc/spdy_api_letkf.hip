@@ -1,6 +1,7 @@
 // C ABI of the ensemble analysis (include/spdy.h, "ensemble analysis"): the observation ingestion on the host, the
 // analysis of a gridded ensemble, the five-launch analysis of an ensemble's spectral state, and the tables and the buffer of weight
-// interpolation (one launch more).  Kernels: csrc/spdy_letkf.hip.
+// interpolation (one launch more), and observations in time slots: the ranges on the host, the observe calls and the
+// two analysis calls that finish what the slots kept.  Kernels: csrc/spdy_letkf.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -63,8 +64,48 @@ int analysis_ready(spdy_letkf *l, bool ptrs_ok)
     return SPDY_OK;
 }
 
-// d_use: NULL, or the member mask -- one launch more in front, which builds the table the masked forms of the kernels read
-int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const int *d_use = nullptr)
+// the slot analysis' checks: analysis_ready's, and before the device every non-empty slot observed since the latest spdy_slot_set
+int slot_analysis_ready(spdy_letkf *l, bool ptrs_ok)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!l->loc_set) return fail(SPDY_ERR_STATE, "letkf: spdy_letkf_set_localization first");
+    if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
+    if (!l->nslots) return fail(SPDY_ERR_STATE, "slot analysis: spdy_slot_set first");
+    for (int s = 0; s < l->nslots; ++s)
+        if (l->slot_first[s + 1] > l->slot_first[s] && !l->slot_observed[s])
+            return fail(SPDY_ERR_STATE, "slot analysis: slot %d has not been observed since spdy_slot_set", s);
+    NEED_DEVICE(l->plan);
+    return SPDY_OK;
+}
+
+// the two observe calls' checks in the documented order, the device last
+int observe_ready(spdy_letkf *l, int slot, bool ptrs_ok)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!l->nslots) return fail(SPDY_ERR_STATE, "slot_observe: spdy_slot_set first");
+    if (slot < 0 || slot >= l->nslots) return fail(SPDY_ERR_ARG, "slot_observe: slot=%d outside [0, nslots=%d)", slot, l->nslots);
+    if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
+    NEED_DEVICE(l->plan);
+    return SPDY_OK;
+}
+
+// the slot kernel on a gridded ensemble: ONE launch, none for an empty slot; the slot is marked observed
+int observe_grid(spdy_letkf *l, int slot, const double *const *x)
+{
+    spdy_plan *p = l->plan;
+    spdy::LetkfSlotObs o{};
+    o.first = l->slot_first[slot]; o.last = l->slot_first[slot + 1]; o.nmem = l->nmem; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
+    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.hx = l->d_hx;
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) o.x[v] = x[v];
+    if (l->npobs) { o.atp = l->d_atp; o.lnp = l->d_lnp; o.slot_ps = l->d_slot_ps; o.slot_out = l->d_slot_out; o.lv = l->lv; }
+    KERNEL(spdy::launch_letkf_slot_obs(o, p->stream));
+    l->slot_observed[slot] = true;
+    return SPDY_OK;
+}
+
+// d_use: NULL, or the member mask -- one launch more in front, which builds the table the masked forms of the kernels read.
+// slots: the finish kernel of "observations in time slots" in the observation kernel's place, everything else as it is
+int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const int *d_use = nullptr, bool slots = false)
 {
     spdy_plan *p = l->plan;
     const int *const umap = d_use ? l->d_umap : nullptr;
@@ -97,7 +138,18 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
         return SPDY_OK;
     };
     for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = raw[v]; }
-    if (l->npobs) {
+    if (slots) {
+        // hx (and the stencils' ps and out-of-column flags) are the slots': only what couples members is formed here
+        spdy::LetkfSlotFinish f{};
+        f.nobs = l->nobs; f.nmem = l->nmem; f.hx = l->d_hx; f.value = l->d_value; f.hxmean = l->d_hxmean; f.y = l->d_y; f.dep = l->d_dep;
+        f.umap = umap;
+        if (l->npobs) {
+            f.atp = l->d_atp; f.lnp = l->d_lnp; f.rinv = l->d_rinv; f.slot_ps = l->d_slot_ps; f.slot_out = l->d_slot_out;
+            f.olns = l->d_olns; f.used = l->d_used; f.reff = l->d_reff;
+            c.rinv = l->d_reff;
+        }
+        KERNEL(spdy::launch_letkf_slot_finish(f, p->stream));
+    } else if (l->npobs) {
         // observations at a pressure: the kernel that interpolates per member, in letkf_obs_kernel's place; it writes ln sigma_o of
         // those observations into olns and this call's copy of rinv, 0 where an observation is out of its column
         spdy::LetkfPObs po{};
@@ -263,12 +315,13 @@ int ingest(spdy_letkf *l, int nobs, const OBS *host, const char *call, const cha
             // the device tables may be partly new: the object holds no observations now, and no copy is still reading the host
             // arrays when they go
             (void)hipStreamSynchronize(p->stream);
-            l->nobs = 0; l->npobs = 0; l->obs = {};
+            l->nobs = 0; l->npobs = 0; l->obs = {}; l->nslots = 0;
             return rc;
         }
     }
     l->nobs = nobs; l->npobs = npobs;
     l->obs = std::move(tab);
+    l->nslots = 0;                            // the ranges were of the network that has just gone
     return SPDY_OK;
 }
 }  // namespace
@@ -280,6 +333,8 @@ int spdy_detail::ens_to_grid(spdy_plan *p, int nmem, const double *vor, const do
     const spdy_spec_seg segs[3] = {{nk, t}, {nk, q}, {nmem, ps}};
     return spdy_inverse_batch_segs_dev(p, nk, vor, div, g, g + L, 2, 3, segs, nullptr, 1, g + 2 * L, 0, nullptr, nullptr, nullptr, 2);
 }
+
+static int ens_analyse(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use, bool slots);
 
 extern "C" {
 
@@ -454,6 +509,8 @@ int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap
     };
     for (const auto &t : tables)
         if (!std::strcmp(name, t.name)) return t.index ? give(*t.index) : give(*t.v);
+    if (!std::strcmp(name, "slot_first"))
+        return give(std::vector<int>(l->slot_first, l->slot_first + (l->nslots ? l->nslots + 1 : 0)));
     return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
 }
 
@@ -465,7 +522,7 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
         {"hx", &spdy_letkf::d_hx}, {"hxmean", &spdy_letkf::d_hxmean}, {"y", &spdy_letkf::d_y}, {"departure", &spdy_letkf::d_dep},
         {"weights", &spdy_letkf::d_tw}, {"value", &spdy_letkf::d_value}, {"grid", &spdy_letkf::d_grid},
         {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}, {"members_used", &spdy_letkf::d_nused},
-        {"inflation", &spdy_letkf::d_infl}};
+        {"inflation", &spdy_letkf::d_infl}, {"slot_ps", &spdy_letkf::d_slot_ps}, {"slot_out", &spdy_letkf::d_slot_out}};
     const auto *f = std::find_if(std::begin(fields), std::end(fields), [&](const auto &t) { return !std::strcmp(name, t.name); });
     if (f == std::end(fields)) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f->ptr == &spdy_letkf::d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
@@ -498,6 +555,69 @@ int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, doubl
 int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use)
 {
     RC(analysis_ready(l, vor && div && t && q && ps));
+    return ens_analyse(l, vor, div, t, q, ps, d_use, false);
+}
+
+int spdy_slot_set(spdy_letkf *l, int nslots, const int *first)
+{
+    NEED_LIVE(l, "analysis object");
+    if (nslots < 0 || nslots > SPDY_MAX_SLOTS) return fail(SPDY_ERR_ARG, "slot_set: nslots=%d outside [0, %d]", nslots, SPDY_MAX_SLOTS);
+    if (nslots) {
+        if (!first) return fail(SPDY_ERR_ARG, "slot_set: null ranges");
+        if (first[0] != 0) return fail(SPDY_ERR_ARG, "slot_set: first[0]=%d must be 0", first[0]);
+        for (int s = 0; s < nslots; ++s)
+            if (first[s + 1] < first[s]) return fail(SPDY_ERR_ARG, "slot_set: first[%d]=%d < first[%d]=%d", s + 1, first[s + 1], s, first[s]);
+        if (first[nslots] != l->nobs) return fail(SPDY_ERR_ARG, "slot_set: first[%d]=%d must be nobs=%d", nslots, first[nslots], l->nobs);
+    }
+    l->nslots = nslots;
+    for (int s = 0; s <= nslots; ++s) l->slot_first[s] = nslots ? first[s] : 0;
+    for (int s = 0; s < SPDY_MAX_SLOTS; ++s) l->slot_observed[s] = false;
+    return SPDY_OK;
+}
+
+int spdy_slot_observe_grid_dev(spdy_letkf *l, int slot, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg)
+{
+    RC(observe_ready(l, slot, ug && vg && tg && qg && psg));
+    const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
+    return observe_grid(l, slot, x);
+}
+
+int spdy_slot_observe_dev(spdy_letkf *l, int slot, const double *vor, const double *div, const double *t, const double *q, const double *ps)
+{
+    RC(observe_ready(l, slot, vor && div && t && q && ps));
+    if (l->slot_first[slot + 1] == l->slot_first[slot]) {      // an empty slot: nothing is enqueued, the transform neither
+        l->slot_observed[slot] = true;
+        return SPDY_OK;
+    }
+    spdy_plan *p = l->plan;
+    const size_t L = (size_t)l->nmem * p->tab.kx * grid_elems(p);
+    double *g = l->d_grid;
+    RC(ens_to_grid(p, l->nmem, vor, div, t, q, ps, g));
+    const double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
+    return observe_grid(l, slot, x);
+}
+
+int spdy_slot_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
+                               double *du, double *dv, double *dt, double *dq, double *dps, const int *d_use)
+{
+    RC(slot_analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps));
+    const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
+    double *dx[spdy::LETKF_VARS] = {du, dv, dt, dq, dps};
+    return analyse_grid(l, x, dx, d_use, true);
+}
+
+int spdy_slot_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use)
+{
+    RC(slot_analysis_ready(l, vor && div && t && q && ps));
+    return ens_analyse(l, vor, div, t, q, ps, d_use, true);
+}
+
+}  // extern "C"
+
+// spdy_ens_letkf_dev behind its checks: the inverse batch, the analysis on the grid workspace (slots: with the finish kernel in the
+// observation kernel's place), the direct batch and the kernel that adds the spectral increments
+static int ens_analyse(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use, bool slots)
+{
     spdy_plan *p = l->plan;
     const int kx = p->tab.kx, nmem = l->nmem, nk = nmem * kx;
     const size_t L = (size_t)nk * grid_elems(p), LS = (size_t)nk * spec_elems(p);
@@ -505,7 +625,7 @@ int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, 
     RC(ens_to_grid(p, nmem, vor, div, t, q, ps, g));
     // the increments take the place of the gridded ensemble
     double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
-    RC(analyse_grid(l, x, x, d_use));
+    RC(analyse_grid(l, x, x, d_use, slots));
     // vdspec(du, dv, 2) next to grid_to_spec(dt | dq | dps), then into the prognostics
     RC(spdy_direct_batch_dev(p, nk, g, g + L, s, s + LS, 2, 2 * nk + nmem, g + 2 * L, s + 2 * LS));
     spdy::LetkfAdd a{};
@@ -518,5 +638,3 @@ int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, 
     KERNEL(spdy::launch_spec_add(a, p->stream));
     return SPDY_OK;
 }
-
-}  // extern "C"

@@ -160,6 +160,25 @@ int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *l, double noise)
     return SPDY_OK;
 }
 
+int spdy_slot_nature_observe_dev(spdy_nature *n, spdy_letkf *l, int slot, double noise)
+{
+    RC(need_pair(n, l));
+    if (!(noise >= 0.0) || !std::isfinite(noise)) return fail(SPDY_ERR_ARG, "slot_nature_observe: noise must be finite and >= 0");
+    if (!l->nslots) return fail(SPDY_ERR_STATE, "slot_nature_observe: spdy_slot_set first");
+    if (slot < 0 || slot >= l->nslots) return fail(SPDY_ERR_ARG, "slot_nature_observe: slot=%d outside [0, nslots=%d)", slot, l->nslots);
+    spdy_plan *p = n->plan;
+    NEED_DEVICE(p);
+    spdy::NatureObs o{};
+    o.nobs = l->nobs; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
+    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.error = l->d_err;
+    o.truth = n->d_truth; o.state = n->d_state; o.noise = noise; o.value = l->d_value;
+    // the draw of the slot's range, by the network's kind; an empty slot launches the count alone
+    KERNEL(spdy::launch_nature_slot_draw(o, l->slot_first[slot], l->slot_first[slot + 1], l->npobs ? l->d_atp : nullptr, l->d_lnp, l->lv,
+                                         p->stream));
+    KERNEL(spdy::launch_nature_count(n->d_state, p->stream));
+    return SPDY_OK;
+}
+
 int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q,
                            const double *ps, int slot)
 {

@@ -616,6 +616,35 @@ struct LetkfRelax {
     const int *umap;                                 // NULL, or the member mask's table
 };
 hipError_t launch_letkf_relax(const LetkfRelax &a, hipStream_t s);
+// Observations in time slots (include/spdy.h, "observations in time slots").  Observing a slot: what is per member
+// only, of the observations [first, last) and every member, one thread per (observation, member) in letkf_pobs_kernel's layout --
+// hx[o][e] with the bits letkf_obs_kernel / letkf_pobs_kernel give it and, when atp is not NULL (the network holds an observation at a
+// pressure), slot_ps[o][e], the stencil's ps_e, and slot_out[o][e], 1.0 / 0.0, the member's out-of-column flag.  Nothing else is written.
+struct LetkfSlotObs {
+    int first, last, nmem, kx, ncol;
+    const int *var, *lev, *sidx;                     // as LetkfObs
+    const double *swgt;
+    const double *x[LETKF_VARS];                     // the gridded ensemble of the slot's time
+    double *hx;                                      // [nobs][nmem]
+    const int *atp;                                  // NULL: a model-level network, nothing below is read or written
+    const double *lnp;
+    double *slot_ps, *slot_out;                      // [nobs][nmem] each
+    VLevels lv;
+};
+hipError_t launch_letkf_slot_obs(const LetkfSlotObs &a, hipStream_t s);
+// The finish, in the observation kernel's place of an analysis call: everything that couples members, from the slots' rows -- hxmean,
+// y and dep of all nobs observations over the members in use (umap NULL: all), ascending, by select; with atp not NULL also olns of
+// the at-pressure observations, used and reff, as letkf_pobs_kernel's second half forms them.  One thread per observation.
+struct LetkfSlotFinish {
+    int nobs, nmem;
+    const double *hx, *value;
+    double *hxmean, *y, *dep;
+    const int *atp;                                  // NULL: a model-level network, nothing below is read or written
+    const double *lnp, *rinv, *slot_ps, *slot_out;
+    double *olns, *used, *reff;
+    const int *umap;                                 // NULL, or the member mask's table
+};
+hipError_t launch_letkf_slot_finish(const LetkfSlotFinish &a, hipStream_t s);
 
 // The nature run (csrc/spdy_nature.hip; include/spdy.h, "nature run").  The truth is one member of the analysis'
 // gridded layout: row f = v * kx + k of u, v, t, q, then ps, (4 kx + 1) grids.  state = {seed, draws}.
@@ -635,6 +664,10 @@ hipError_t launch_nature_draw(const NatureObs &a, hipStream_t s);
 // columns' values interpolated to the target with the truth's ps, clamped to the end level outside the column; noise and counter
 // as above.
 hipError_t launch_nature_pdraw(const NatureObs &a, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s);
+// Either of the two for the observations [first, last) of the network only (include/spdy.h, "observations in time slots"): the
+// thread of observation o forms what the kernels above form for it, counter (o, 0, draws) included; atp NULL: a model-level network.
+hipError_t launch_nature_slot_draw(const NatureObs &a, int first, int last, const int *atp, const double *lnp, const VLevels &lv,
+                                   hipStream_t s);
 // draws += 1 by one thread: every launch before it on the stream has read the counter, every launch after it sees the new one
 hipError_t launch_nature_count(unsigned long long *state, hipStream_t s);
 // The scores of an ensemble on the grid (x: LetkfObs::x) against the truth, two launches.  One workgroup per (row, latitude) forms

@@ -1,6 +1,7 @@
 // The ensemble analysis on the device (include/spdy.h, "ensemble analysis"): the observation-space quantities, the
 // local ensemble transforms of every grid column and level -- or of a coarse list of columns, with the kernel that interpolates them
-// to every column (weight interpolation) -- and the kernel that adds the spectral increments to the prognostics.
+// to every column (weight interpolation) -- the kernel that adds the spectral increments to the prognostics, and the two kernels of
+// observations in time slots: one keeps what is per member at a slot's time, one finishes it at analysis time.
 // The transforms around them are the plan's own (csrc/spdy_api_letkf.hip).
 //
 // Everything here is bit-reproducible: no atomics, every sum in a fixed order (observations ascending, members ascending), every
@@ -217,6 +218,109 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_pobs_kernel(const LetkfPObs
         if (act) a.o.y[(size_t)o * E + e] = a.umap[LETKF_URANK + e] >= 0 ? h - smean[slot] : 0.0;
     } else {
         if (act) a.o.y[(size_t)o * E + e] = h - smean[slot];
+    }
+}
+
+// Observing a time slot (include/spdy.h, "observations in time slots"): what letkf_obs_kernel and the first half of
+// letkf_pobs_kernel form per member, and nothing that couples members.  Thread (observation of the slot, member) in
+// letkf_pobs_kernel's layout, a workgroup owns LETKF_BLOCK / E whole observations of [first, last); no LDS, no barrier.
+// PRESSURE = false (a model-level network): the four stencil loads and the bilinear sum, letkf_obs_kernel's bits.  PRESSURE = true:
+// letkf_pobs_kernel's first half, expression for expression -- the brackets from the member's four ps, the eight loads before the
+// first use, a model-level observation through the same path with its bracket replaced -- and the stencil's ps_e and the member's
+// out-of-column flag go to slot_ps and slot_out, as doubles, in the place of LDS.  No atomics, every bound a kernel argument.
+template <bool PRESSURE>
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_slot_obs_kernel(const LetkfSlotObs a)
+{
+#pragma clang fp contract(off)
+    const int E = a.nmem, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, opb = LETKF_BLOCK / E;
+    const int slot = tid / E, e = tid - slot * E, o = a.first + blockIdx.x * opb + slot;
+    if (slot >= opb || o >= a.last) return;
+    const int v = a.var[o], lev = a.lev[o];
+    // the variable's field by selects: a pointer array indexed per lane would go to scratch
+    const double *const xv = v == 0 ? a.x[0] : v == 1 ? a.x[1] : v == 2 ? a.x[2] : v == 3 ? a.x[3] : a.x[4];
+    const int kl = v < 4 ? kx : 1;                                 // levels of the field: ps has one
+    const double *const f = xv + (size_t)e * kl * ncol;
+    int idx[4];
+    double w[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        idx[s] = a.sidx[4 * (size_t)o + s];
+        w[s] = a.swgt[4 * (size_t)o + s];
+    }
+    if constexpr (!PRESSURE) {
+        const double *const fk = f + (size_t)min(lev, kl - 1) * ncol;
+        const double z0 = fk[idx[0]], z1 = fk[idx[1]], z2 = fk[idx[2]], z3 = fk[idx[3]];
+        a.hx[(size_t)o * E + e] = ((w[0] * z0 + w[1] * z1) + w[2] * z2) + w[3] * z3;
+    } else {
+        const bool atp = a.atp[o] != 0;
+        const double *const pse = a.x[4] + (size_t)e * ncol;
+        double ps[4], f0[4], f1[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) ps[s] = pse[idx[s]];
+        const double xo = a.lnp[o], l0 = a.lv.lev[0];
+        VBracket b[4];
+        vinterp_brackets<true, 4>(a.lv, ps, xo, b);
+        int out = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
+            f0[s] = f[(size_t)k0 * ncol + idx[s]];
+            f1[s] = f[(size_t)k1 * ncol + idx[s]];
+            out |= (atp && (xo < vinterp_coord<true>(ps[s], l0) || (b[s].cls & VINTERP_BELOW))) ? 1 : 0;
+            b[s].cls = atp ? b[s].cls : VINTERP_LO;                // a model level: f0's bits
+        }
+        double z[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
+        a.hx[(size_t)o * E + e] = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
+        a.slot_ps[(size_t)o * E + e] = ((w[0] * ps[0] + w[1] * ps[1]) + w[2] * ps[2]) + w[3] * ps[3];
+        a.slot_out[(size_t)o * E + e] = out ? 1.0 : 0.0;
+    }
+}
+
+// The finish of a slot analysis, in the observation kernel's place: one thread per observation reads its row of hx (and, PRESSURE,
+// of slot_ps and slot_out) from memory and forms what couples members -- the tail of letkf_obs_kernel / letkf_obs_masked_kernel and
+// the second half of letkf_pobs_kernel<MASK>, expression for expression: the sums over the members in use in ascending order, by a
+// select under MASK, so a member not in use may hold anything.  y is written row by row.  Four instantiations, no run-time branch.
+template <bool MASK, bool PRESSURE>
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_slot_finish_kernel(const LetkfSlotFinish a)
+{
+#pragma clang fp contract(off)
+    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (o >= a.nobs) return;
+    const int E = a.nmem, n = MASK ? a.umap[0] : E;
+    const int *const rank = MASK ? a.umap + LETKF_URANK : nullptr;
+    const double *const hx = a.hx + (size_t)o * E;
+    double sum = 0.0;
+    for (int e = 0; e < E; ++e) {
+        const double h = hx[e];
+        if constexpr (MASK) sum = rank[e] >= 0 ? sum + h : sum;
+        else sum += h;
+    }
+    const double mean = sum / n;
+    a.hxmean[o] = mean;
+    for (int e = 0; e < E; ++e) {
+        if constexpr (MASK) a.y[(size_t)o * E + e] = rank[e] >= 0 ? hx[e] - mean : 0.0;
+        else a.y[(size_t)o * E + e] = hx[e] - mean;
+    }
+    a.dep[o] = a.value[o] - mean;
+    if constexpr (PRESSURE) {
+        const double *const pb = a.slot_ps + (size_t)o * E, *const so = a.slot_out + (size_t)o * E;
+        double psum = 0.0;
+        int out = 0;
+        for (int e = 0; e < E; ++e) {
+            if constexpr (MASK) {
+                const bool u = rank[e] >= 0;
+                psum = u ? psum + pb[e] : psum;
+                out |= u ? (so[e] != 0.0 ? 1 : 0) : 0;
+            } else {
+                psum += pb[e];
+                out |= so[e] != 0.0 ? 1 : 0;
+            }
+        }
+        if (a.atp[o] != 0) a.olns[o] = a.lnp[o] - psum / n;
+        a.used[o] = out ? 0.0 : 1.0;
+        a.reff[o] = out ? 0.0 : a.rinv[o];
     }
 }
 
@@ -767,6 +871,40 @@ hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s)
         hipLaunchKernelGGL(letkf_pobs_kernel<true>, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
     else
         hipLaunchKernelGGL(letkf_pobs_kernel<false>, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_slot_obs(const LetkfSlotObs &a, hipStream_t s)
+{
+    if (a.first < 0 || a.last < a.first || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 || !a.hx)
+        return hipErrorInvalidValue;
+    for (int v = 0; v < LETKF_VARS; ++v)
+        if (!a.x[v]) return hipErrorInvalidValue;
+    if (a.atp && (a.kx < 2 || a.kx > VINTERP_KMAX || a.lv.kx != a.kx || !a.lnp || !a.slot_ps || !a.slot_out)) return hipErrorInvalidValue;
+    if (a.last == a.first) return hipSuccess;
+    if (!a.var || !a.lev || !a.sidx || !a.swgt) return hipErrorInvalidValue;
+    const int opb = LETKF_BLOCK / a.nmem, n = a.last - a.first;
+    if (a.atp)
+        hipLaunchKernelGGL(letkf_slot_obs_kernel<true>, dim3((n + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(letkf_slot_obs_kernel<false>, dim3((n + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_slot_finish(const LetkfSlotFinish &a, hipStream_t s)
+{
+    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || !a.hx || !a.hxmean || !a.y || !a.dep) return hipErrorInvalidValue;
+    if (!a.nobs) return hipSuccess;
+    if (!a.value) return hipErrorInvalidValue;
+    if (a.atp && (!a.lnp || !a.rinv || !a.slot_ps || !a.slot_out || !a.olns || !a.used || !a.reff)) return hipErrorInvalidValue;
+    const dim3 grid((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), block(LETKF_BLOCK);
+    if (a.umap) {
+        if (a.atp) hipLaunchKernelGGL((letkf_slot_finish_kernel<true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((letkf_slot_finish_kernel<true, false>), grid, block, 0, s, a);
+    } else {
+        if (a.atp) hipLaunchKernelGGL((letkf_slot_finish_kernel<false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((letkf_slot_finish_kernel<false, false>), grid, block, 0, s, a);
+    }
     return hipGetLastError();
 }
 

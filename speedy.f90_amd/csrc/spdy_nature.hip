@@ -73,6 +73,57 @@ __global__ __launch_bounds__(NATURE_BLOCK) void nature_pdraw_kernel(const Nature
     a.value[o] = h + (a.noise * a.error[o]) * zz;
 }
 
+// The two kernels above for the observations [first, last) of the network only (include/spdy.h, "observations in time slots"):
+// thread o - first forms value_o as they do, expression for expression, with the counter of o itself, so a slot's draw is the
+// whole network's draw on its range.  PRESSURE: the network holds an observation at a pressure (nature_pdraw_kernel's path).
+template <bool PRESSURE>
+__global__ __launch_bounds__(NATURE_BLOCK) void nature_slot_draw_kernel(const NatureObs a, const int first, const int last, const int *const atpo,
+                                                                        const double *const lnp, const VLevels lv)
+{
+#pragma clang fp contract(off)
+    const int o = first + blockIdx.x * NATURE_BLOCK + threadIdx.x;
+    if (o >= last) return;
+    const int v = a.var[o], lev = a.lev[o];
+    int idx[4];
+    double w[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        idx[s] = a.sidx[4 * (size_t)o + s];
+        w[s] = a.swgt[4 * (size_t)o + s];
+    }
+    double h;
+    if constexpr (!PRESSURE) {
+        const double *const f = a.truth + ((size_t)v * a.kx + lev) * a.ncol;       // row v * kx + k of the truth; lev is 0 for ps
+        h = ((w[0] * f[idx[0]] + w[1] * f[idx[1]]) + w[2] * f[idx[2]]) + w[3] * f[idx[3]];
+    } else {
+        const int kl = v < 4 ? a.kx : 1;
+        const bool atp = atpo[o] != 0;
+        const double *const f = a.truth + (size_t)v * a.kx * a.ncol, *const pst = a.truth + (size_t)4 * a.kx * a.ncol;
+        double ps[4], f0[4], f1[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) ps[s] = pst[idx[s]];
+        VBracket b[4];
+        vinterp_brackets<true, 4>(lv, ps, lnp[o], b);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
+            f0[s] = f[(size_t)k0 * a.ncol + idx[s]];
+            f1[s] = f[(size_t)k1 * a.ncol + idx[s]];
+            b[s].cls = atp ? b[s].cls : VINTERP_LO;
+        }
+        double z[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
+        h = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
+    }
+    if (a.noise == 0.0) {
+        a.value[o] = h;
+        return;
+    }
+    const double zz = sppt_randn((unsigned)o, 0u, a.state[1], a.state[0]);
+    a.value[o] = h + (a.noise * a.error[o]) * zz;
+}
+
 __global__ void nature_count_kernel(unsigned long long *state)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) state[1] = state[1] + 1;
@@ -180,6 +231,21 @@ hipError_t launch_nature_pdraw(const NatureObs &a, const int *atp, const double 
     if (!a.nobs) return hipSuccess;
     if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error || !atp || !lnp) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nature_pdraw_kernel, dim3((a.nobs + NATURE_BLOCK - 1) / NATURE_BLOCK), dim3(NATURE_BLOCK), 0, s, a, atp, lnp, lv);
+    return hipGetLastError();
+}
+
+hipError_t launch_nature_slot_draw(const NatureObs &a, int first, int last, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s)
+{
+    if (first < 0 || last < first || last > a.nobs || a.kx < 1 || a.ncol < 1 || !a.truth || !a.state || !a.value || !(a.noise >= 0.0))
+        return hipErrorInvalidValue;
+    if (atp && (a.kx < 2 || a.kx > VINTERP_KMAX || lv.kx != a.kx || !lnp)) return hipErrorInvalidValue;
+    if (last == first) return hipSuccess;
+    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error) return hipErrorInvalidValue;
+    const dim3 grid((last - first + NATURE_BLOCK - 1) / NATURE_BLOCK), block(NATURE_BLOCK);
+    if (atp)
+        hipLaunchKernelGGL(nature_slot_draw_kernel<true>, grid, block, 0, s, a, first, last, atp, lnp, lv);
+    else
+        hipLaunchKernelGGL(nature_slot_draw_kernel<false>, grid, block, 0, s, a, first, last, atp, lnp, lv);
     return hipGetLastError();
 }
 

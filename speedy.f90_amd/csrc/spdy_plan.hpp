@@ -196,8 +196,17 @@ struct spdy_letkf final : spdy_detail::PlanObject {
         v(d_swgt, 4 * M); v(d_ounit, 3 * M); v(d_olns, M); v(d_rinv, M); v(d_err, M); v(d_value, M);
         v(d_hx, M * E); v(d_hxmean, M); v(d_y, M * E); v(d_dep, M);
         v(d_lnp, M); v(d_used, M); v(d_reff, M); v(d_nused, 2); v(d_infl, (4 * kx + 1) * ncol);
+        v(d_slot_ps, M * E); v(d_slot_out, M * E);
         v(d_sidx, 4 * M); v(d_var, M); v(d_lev, M); v(d_atp, M); v(d_umap, spdy::LETKF_UMAP);
     }
+    // observations in time slots (include/spdy.h, "observations in time slots"; spdy_slot_set): the ranges first[0 .. nslots] of the
+    // current network, nslots == 0: none, and whether a slot has been observed since they were set -- host side, read when a call is
+    // enqueued.  d_slot_ps, d_slot_out [max_obs][nmem], part of the main allocation: the stencil's ps_e and the out-of-column flag
+    // (1.0 / 0.0) of every member at the slot's time, written next to d_hx by an observe of an at-pressure network
+    int nslots = 0;
+    int slot_first[SPDY_MAX_SLOTS + 1] = {0};
+    bool slot_observed[SPDY_MAX_SLOTS] = {false};
+    double *d_slot_ps = nullptr, *d_slot_out = nullptr;
     // weight interpolation (spdy_letkf_set_weight_stride); at stride (1, 1) the tables are empty and nothing is allocated
     int si = 1, sj = 1;
     // coarse [ncoarse] grid columns, ascending; iidx [ncol][4] entries of that list; iwgt [ncol][4]

@@ -251,7 +251,18 @@ class Ensemble:
         return res
 
     # ------------------------------------------------------------------ analysis
-    def analyse(self, letkf, use=None):
+    def observe(self, letkf, slot):
+        """Observes time slot `slot` of letkf's network on time level 1 as it stands now (include/spdy.h, "observations in time
+        slots"): the analysis' inverse batch into letkf's grid workspace and one launch that keeps every member's H x_e of the
+        slot's observations; nothing of the ensemble changes.  Capturable; an empty slot enqueues nothing.  After every slot has
+        been observed during the forecast, analyse(letkf, slots=True) is the 4D-LETKF update."""
+        if getattr(letkf, "sp", None) is not self.sp:
+            raise ValueError("observe: the Letkf must belong to the ensemble's plan")
+        if letkf.nmem != self.nmem:
+            raise ValueError("observe: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
+        letkf.observe_dev(slot, self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0])
+
+    def analyse(self, letkf, use=None, slots=False):
         """The LETKF update of time level 1 of every member, in place (include/spdy.h, "ensemble analysis"): five launches whatever
         E is (six once the direct batch is of streaming size), capturable.  letkf: a Letkf of this plan with nmem == E, its
         observations set.  Time level 2 and phi are stale afterwards: continue with startup(delt).  Members are coupled: every
@@ -260,12 +271,14 @@ class Ensemble:
         analysed (include/spdy.h, "member mask"; guard.use_dev() gives the guard's on the device).  The n members in use get, bit
         for bit, what an n-member Ensemble and Letkf give them; a member not in use is read into nothing shared and keeps every
         bit of its state; n < 2 leaves the whole state.  One launch more.  The tensor is read when the kernels run: a captured
-        analysis follows its contents."""
+        analysis follows its contents.
+        slots=True: the slot analysis (include/spdy.h, "observations in time slots"): H x_e of every observation is what
+        observe(letkf, s) kept at its slot's time, the increments are formed on the state as it stands now; the same launches."""
         if getattr(letkf, "sp", None) is not self.sp:
             raise ValueError("analyse: the Letkf must belong to the ensemble's plan")
         if letkf.nmem != self.nmem:
             raise ValueError("analyse: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
-        letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], use)
+        letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], use, slots)
 
     def verify(self, letkf, nature, slot=0, use=None):
         """The scores of time level 1 against a Nature's truth (include/spdy.h, "nature run"): rmse and bias of the ensemble mean and

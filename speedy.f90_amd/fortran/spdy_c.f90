@@ -1225,6 +1225,43 @@ module spdy_c
             real(c_double), value :: rtpp, rtps
             integer(c_int) :: rc
         end function
+        ! observations in time slots (include/spdy.h, "observations in time slots"): first is c_loc of nslots + 1 integers
+        function spdy_slot_set(l, nslots, first) bind(C, name="spdy_slot_set") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, first
+            integer(c_int), value :: nslots
+            integer(c_int) :: rc
+        end function
+        function spdy_slot_observe_grid_dev(l, slot, ug, vg, tg, qg, psg) bind(C, name="spdy_slot_observe_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, ug, vg, tg, qg, psg
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
+        function spdy_slot_observe_dev(l, slot, vor, div, t, q, ps) bind(C, name="spdy_slot_observe_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, vor, div, t, q, ps
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
+        function spdy_slot_analyse_grid_dev(l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps, d_use) &
+                & bind(C, name="spdy_slot_analyse_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, ug, vg, tg, qg, psg, du, dv, dt, dq, dps, d_use
+            integer(c_int) :: rc
+        end function
+        function spdy_slot_ens_letkf_dev(l, vor, div, t, q, ps, d_use) bind(C, name="spdy_slot_ens_letkf_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, vor, div, t, q, ps, d_use
+            integer(c_int) :: rc
+        end function
+        function spdy_slot_nature_observe_dev(n, letkf, slot, noise) bind(C, name="spdy_slot_nature_observe_dev") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: n, letkf
+            integer(c_int), value :: slot
+            real(c_double), value :: noise
+            integer(c_int) :: rc
+        end function
         function spdy_letkf_table(l, name, buf, cap) bind(C, name="spdy_letkf_table") result(rc)
             import :: c_int, c_ptr, c_char
             type(c_ptr), value :: l, buf
@@ -1344,6 +1381,7 @@ module spdy_c
 
     integer(c_int), parameter :: SPDY_OBS_U = 0_c_int, SPDY_OBS_V = 1_c_int, SPDY_OBS_T = 2_c_int, SPDY_OBS_Q = 3_c_int, &
         & SPDY_OBS_PS = 4_c_int                                !! spdy_obs%var (include/spdy.h)
+    integer(c_int), parameter :: SPDY_MAX_SLOTS = 32_c_int     !! the most time slots of spdy_slot_set (include/spdy.h)
     integer(c_int), parameter :: SPDY_OBS_AT_P = -1_c_int      !! spdy_pobs%lev: the observation sits at p (include/spdy.h)
     integer(c_int), parameter :: SPDY_DEVICE_AUTO = -2_c_int   !! $SPDY_DEVICE, else the launcher's local rank (include/spdy.h)
     integer(c_int), parameter :: SPDY_MAX_PLEV = 32_c_int, SPDY_PLEV_LINEAR_P = 0_c_int, SPDY_PLEV_LOG_P = 1_c_int

@@ -11,7 +11,9 @@ with Ensemble.startup(delt): time level 2 and phi are stale until then.  Members
 column it touches non-finite: pass use=, a member mask on the device (Diagnostics.use_dev gives the guard's), to analyse the
 members the guard has not stopped and leave the others alone, bit for bit (include/spdy.h, "member mask").
 set_relaxation(rtpp, rtps) relaxes the analysis towards the background where observations acted, one launch more (include/spdy.h,
-"relaxation")."""
+"relaxation").  set_slots(first) divides the observations into time slots: Ensemble.observe(letkf, s) during the
+forecast takes each member's H x_e at the slot's own time, Ensemble.analyse(letkf, slots=True) is then one update from all of them,
+the 4D-LETKF (include/spdy.h, "observations in time slots")."""
 import ctypes
 
 import numpy as np
@@ -24,14 +26,15 @@ OBS_AT_P = -1                         # SPDY_OBS_AT_P: as lev, the observation s
 # host table -> (dtype, shape); -1: what the library's count leaves
 _TABLES = {"stencil_index": (np.int64, (-1, 4)), "stencil_weight": (np.float64, (-1, 4)), "unit": (np.float64, (-1, 3)),
            "lnsigma": (np.float64, (-1,)), "rinv": (np.float64, (-1,)), "coarse_columns": (np.int64, (-1,)),
-           "interp_index": (np.int64, (-1, 4)), "interp_weight": (np.float64, (-1, 4)), "lnp": (np.float64, (-1,))}
+           "interp_index": (np.int64, (-1, 4)), "interp_weight": (np.float64, (-1, 4)), "lnp": (np.float64, (-1,)),
+           "slot_first": (np.int64, (-1,))}
 _PER_OBS, _PER_OBS_MEMBER = (lambda l: (l.nobs,)), (lambda l: (l.nobs, l.nmem))
 # device field -> the shape of a Letkf's, all float64
 _FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "departure": _PER_OBS,
            "weights": lambda l: (check(l.lib.spdy_letkf_table(l.h, b"coarse_columns", None, 0)), l.sp.kx, l.nmem, l.nmem),
            "value": _PER_OBS, "grid": lambda l: ((4 * l.sp.kx + 1) * l.nmem,) + l.sp.grid_shape,
            "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS, "members_used": lambda l: (1,),
-           "inflation": lambda l: (4 * l.sp.kx + 1,) + l.sp.grid_shape}
+           "inflation": lambda l: (4 * l.sp.kx + 1,) + l.sp.grid_shape, "slot_ps": _PER_OBS_MEMBER, "slot_out": _PER_OBS_MEMBER}
 LETKF_TABLES, LETKF_FIELDS = tuple(_TABLES), tuple(_FIELDS)
 
 
@@ -81,6 +84,7 @@ class Letkf(PlanObject):
         h = ctypes.c_void_p()
         check(self.lib.spdy_letkf_create(sp.h, int(nmem), int(max_obs), ctypes.byref(h)))
         self.h, self.nmem, self.max_obs, self.nobs = h, int(nmem), int(max_obs), 0
+        self.slots = None
         self.weight_stride = (1, 1)
         self.set_localization(sigma_h, sigma_v, rho)
         if tuple(weight_stride) != (1, 1):
@@ -154,9 +158,53 @@ class Letkf(PlanObject):
             self.sp._sync_stream()
         rc = call(self.h, n, ctypes.cast(obs, ctypes.c_void_p))
         if rc == ERR_HIP:             # a copy failed, the object holds no observations now
-            self.nobs = 0
+            self.nobs, self.slots = 0, None
         check(rc)
-        self.nobs = n
+        self.nobs, self.slots = n, None
+
+    def set_slots(self, first):
+        """Divides the current observations into len(first) - 1 time slots (include/spdy.h, "observations in time slots"): slot s is
+        the observations first[s] <= o < first[s+1]; first[0] == 0, non-decreasing, first[-1] == nobs, at most 32 slots, a slot may
+        be empty.  None: no slots.  Host only: nothing is launched, allocated or synchronised, and it may be called at any time; the
+        ranges are read when a call is enqueued, so a captured graph keeps those of its capture.  Every slot then counts as not
+        observed.  set_obs returns the object to no slots.  self.slots: the ranges as a tuple, or None."""
+        if first is None:
+            check(self.lib.spdy_slot_set(self.h, 0, None))
+            self.slots = None
+            return
+        f = np.atleast_1d(np.asarray(first))
+        if f.ndim != 1 or f.shape[0] < 2 or not np.issubdtype(f.dtype, np.integer):
+            raise ValueError("set_slots: first must be a one-dimensional array of nslots + 1 >= 2 integers")
+        arr = (ctypes.c_int * f.shape[0])(*[int(v) for v in f])
+        check(self.lib.spdy_slot_set(self.h, f.shape[0] - 1, ctypes.cast(arr, ctypes.c_void_p)))
+        self.slots = tuple(int(v) for v in f)
+
+    def _grids(self, what, x):
+        """the five grids of an ensemble checked: ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] contiguous float64 tensors"""
+        import torch
+        sp, E = self.sp, self.nmem
+        for a, s in zip(x, [(E, sp.kx) + sp.grid_shape] * 4 + [(E,) + sp.grid_shape]):
+            if tuple(a.shape) != s or a.dtype != torch.float64 or not a.is_contiguous():
+                raise ValueError("%s: expected a contiguous float64 tensor of shape %s, got %s" % (what, s, tuple(a.shape)))
+
+    def observe_grid(self, slot, ug, vg, tg, qg, psg):
+        """Observes time slot `slot` on a gridded ensemble (analyse_grid's layout): every member's H x_e of the slot's observations
+        goes to its rows of field("hx") -- for a network with observations at a pressure also the members' ps at the stations and
+        their out-of-column flags, field("slot_ps") and field("slot_out") -- and nothing else is written.  One launch, none for an
+        empty slot; capturable; nothing synchronises.  The analysis with slots=True then uses these rows."""
+        x = (ug, vg, tg, qg, psg)
+        self._grids("observe_grid", x)
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        check(self.lib.spdy_slot_observe_grid_dev(self.h, int(slot), *[ctypes.c_void_p(a.data_ptr()) for a in x]))
+
+    def observe_dev(self, slot, vor, div, t, q, ps):
+        """spdy_slot_observe_dev: observe_grid on time level 1 of an ensemble's spectra (Ensemble.observe): the analysis' inverse batch
+        into the grid workspace -- field("grid") then holds the gridded ensemble of that time -- and the slot's launch.  Nothing of
+        the ensemble changes; capturable; an empty slot enqueues nothing."""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        check(self.lib.spdy_slot_observe_dev(self.h, int(slot), *[ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]))
 
     def table(self, name):
         """A host table of the current observations (LETKF_TABLES): stencil_index [nobs, 4] (grid points j*ix+i, int64),
@@ -164,7 +212,8 @@ class Letkf(PlanObject):
         rinv [nobs], lnp [nobs] (ln(p/p0) of the observations at a pressure, 0 for the others; empty after a set_obs without p);
         or of the weight interpolation: coarse_columns
         [ncoarse] (grid columns j*ix+i, int64, ascending), interp_index [ncol, 4] (entries of coarse_columns, int64; an entry of
-        weight zero repeats the first), interp_weight [ncol, 4]; all three are empty at stride (1, 1)."""
+        weight zero repeats the first), interp_weight [ncol, 4]; all three are empty at stride (1, 1); or of the time slots:
+        slot_first [nslots + 1] (int64), the ranges of set_slots, empty with no slots."""
         out = self._table(name)           # an unknown name is the library's to refuse
         dtype, shape = _TABLES[name]
         return out.astype(dtype, copy=False).reshape(shape)
@@ -181,7 +230,9 @@ class Letkf(PlanObject):
         members_used [1]: the members the latest analysis call analysed, nmem without a mask; ask for it after the call -- it is
         one of two words, that of the kind of call (masked or not) enqueued last.  inflation [4 kx + 1, il, ix]: the factor f
         of every grid item (u | v | t | q at kx levels, then ps) in the latest analysis call with relaxation on, exactly 1.0 where
-        the analysis changed nothing; zero until the first such call."""
+        the analysis changed nothing; zero until the first such call.  slot_ps, slot_out [nobs, nmem]: for a network with
+        observations at a pressure, every member's ps at the station and its out-of-column flag (1.0 / 0.0) as observe_grid /
+        observe_dev left them for the observation's slot (include/spdy.h, "observations in time slots"); otherwise not written."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         return DeviceField(self.sp, p.value, _FIELDS[name](self))
@@ -199,7 +250,7 @@ class Letkf(PlanObject):
     def _device(self):
         return "cuda:%d" % self.sp.device if self.sp.device >= 0 else "cpu"
 
-    def analyse_grid(self, ug, vg, tg, qg, psg, out=None, use=None):
+    def analyse_grid(self, ug, vg, tg, qg, psg, out=None, use=None, slots=False):
         """The increments (du, dv, dt, dq, dps) of a gridded ensemble: ug .. qg [nmem, kx, il, ix], psg [nmem, il, ix] float64
         device tensors; out: five tensors of those shapes to write into (they may be the inputs), by default fresh ones.
         Two launches, three at a weight stride other than (1, 1), one more with relaxation on (set_relaxation: the increments are
@@ -207,7 +258,11 @@ class Letkf(PlanObject):
         use: None (all members), or a sequence or a contiguous int32 device tensor of nmem entries, non-zero = in use (include/spdy.h,
         "member mask"): the n members in use get the increments an n-member Letkf gives them, bit for bit, the others exactly 0.0
         and are not read into anything shared; n < 2: all zero.  One launch more; the tensor is read when the kernels run, so a
-        captured call follows its contents."""
+        captured call follows its contents.
+        slots=True: the slot analysis (include/spdy.h, "observations in time slots") -- H x_e of every observation is what
+        observe_grid / observe_dev left for its slot, the increments are formed on this ensemble; the same launches, with the kernel
+        that finishes the observation-space quantities in the observation kernel's place.  Every non-empty slot must have been
+        observed since set_slots."""
         import torch
         sp, E = self.sp, self.nmem
         use = use_mask(use, E, self._device())
@@ -223,21 +278,26 @@ class Letkf(PlanObject):
         if sp.device >= 0:
             sp._sync_stream()
         ptrs = [ctypes.c_void_p(a.data_ptr()) for a in x + tuple(out)]
-        if use is None:
+        if slots:
+            check(self.lib.spdy_slot_analyse_grid_dev(self.h, *ptrs, None if use is None else ctypes.c_void_p(use.data_ptr())))
+        elif use is None:
             check(self.lib.spdy_letkf_analyse_grid_dev(self.h, *ptrs))
         else:
             check(self.lib.spdy_mask_letkf_analyse_grid_dev(self.h, *ptrs, ctypes.c_void_p(use.data_ptr())))
         return tuple(out)
 
-    def analyse_dev(self, vor, div, t, q, ps, use=None):
+    def analyse_dev(self, vor, div, t, q, ps, use=None, slots=False):
         """spdy_ens_letkf_dev: time level 1 of an ensemble, in place (Ensemble.analyse); use: as analyse_grid's, the members not in
         use keep every bit (spdy_mask_ens_letkf_dev).  With relaxation on (set_relaxation) the increments are relaxed on the grid,
-        one launch more, before they go back to spectra."""
+        one launch more, before they go back to spectra.  slots=True: the slot analysis (spdy_slot_ens_letkf_dev), as
+        analyse_grid's; the launch count is that of the plain call."""
         use = use_mask(use, self.nmem, self._device())
         if self.sp.device >= 0:
             self.sp._sync_stream()
         ptrs = [ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]
-        if use is None:
+        if slots:
+            check(self.lib.spdy_slot_ens_letkf_dev(self.h, *ptrs, None if use is None else ctypes.c_void_p(use.data_ptr())))
+        elif use is None:
             check(self.lib.spdy_ens_letkf_dev(self.h, *ptrs))
         else:
             check(self.lib.spdy_mask_ens_letkf_dev(self.h, *ptrs, ctypes.c_void_p(use.data_ptr())))

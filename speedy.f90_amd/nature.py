@@ -57,14 +57,20 @@ class Nature(PlanObject):
         self._sync()
         check(self.lib.spdy_nature_set_state_dev(self.h, *ptrs))
 
-    def observe(self, letkf, noise=1.0):
+    def observe(self, letkf, noise=1.0, slot=None):
         """The values of letkf's current network (the latest set_obs; its values are ignored) from the truth: H(truth) + noise *
         error * z, z the standard normal draw of (seed, draws, observation).  Advances draws on the stream, so every replay of a
-        captured observe draws fresh noise; noise = 0 gives H(truth) to the bit.  Two launches; capturable."""
+        captured observe draws fresh noise; noise = 0 gives H(truth) to the bit.  Two launches; capturable.
+        slot: None, or a time slot of letkf.set_slots (include/spdy.h, "observations in time slots"): only that slot's observations
+        get their values, from the truth as it stands now, with the draw the whole network's call would give them; the other values
+        keep their bits; draws advances all the same.  Two launches, one for an empty slot."""
         if getattr(letkf, "sp", None) is not self.sp:
             raise ValueError("observe: the Letkf must belong to the nature run's plan")
         self._sync()
-        check(self.lib.spdy_nature_observe_dev(self.h, letkf.h, float(noise)))
+        if slot is None:
+            check(self.lib.spdy_nature_observe_dev(self.h, letkf.h, float(noise)))
+        else:
+            check(self.lib.spdy_slot_nature_observe_dev(self.h, letkf.h, int(slot), float(noise)))
 
     def _device(self):
         return "cuda:%d" % self.sp.device if self.sp.device >= 0 else "cpu"

@@ -51,6 +51,13 @@ relaxation kernel's bytes -- the ensemble and the raw increments read, the relax
 their time at 8 TB/s.  Replays of Ensemble.analyse analyse the state the replay before left, which a relaxed ensemble changes, so
 that pair of rows compares two different workloads; the pair "grid analysis" / "grid analysis relaxed" replays Letkf.analyse_grid
 of both objects on one gridded ensemble, the start state's, and its difference is the relaxation's own cost.
+--slots S divides the network into S equal time slots (include/spdy.h, "observations in time slots") and adds the
+captured Ensemble.observe of the middle slot -- the inverse batch and the slot's one launch -- and the captured slot analysis,
+Ensemble.analyse(slots=True), next to the plain analysis of the same object.  Replays of Ensemble.analyse analyse the state the
+replay before left while the slots keep the start state's hx, so that pair compares two different workloads; the pair "grid analysis
+plain" / "grid analysis slots" replays Letkf.analyse_grid of the object on one gridded ensemble, the start state's, with every slot
+observed on it -- the same bits and so the same work -- and its difference is the finish kernel against the observation kernel it
+replaces.  With --at-pressure the same rows for the at-pressure object.
 
 --osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
 to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
@@ -77,6 +84,7 @@ float32 grids written; and the surface-pressure row.
     python tools/ensemble_rate.py --letkf --stride 2 2
     python tools/ensemble_rate.py --letkf --at-pressure --members 4 32 --json profiles/ensemble_letkf_pobs_rate.json
     python tools/ensemble_rate.py --letkf --mask 0 1 half
+    python tools/ensemble_rate.py --letkf --slots 6 --at-pressure --json profiles/ensemble_letkf_slots_rate.json
     python tools/ensemble_rate.py --letkf --relax 0 0.9 --json profiles/ensemble_letkf_relax_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --letkf --earlier-library --label parent
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
@@ -575,11 +583,13 @@ def host_observations(sp, lt, tr, cols, err, repeats):
     return float(np.median(us[1:])), min(us[1:]), max(us[1:])
 
 
-def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=(), relax=None):
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=(), relax=None, slots=0):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
     of the nature run's observe and verify, and the host route to the same observation values; at_pressure: and of the analysis of
     the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged; relax
-    = (rtpp, rtps): and of the analysis of the same network by an object with that relaxation on"""
+    = (rtpp, rtps): and of the analysis of the same network by an object with that relaxation on; slots = S: and, with the network
+    divided into S equal time slots, of one slot's Ensemble.observe and of the slot analysis, next to the plain analysis of the same
+    object (with at_pressure also for that object)"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
     build()
@@ -653,6 +663,33 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                 en.analyse(ltp)
             fns["analysis at p E=%d" % E], nodes["analysis at p E=%d" % E] = gp.launch, gp.num_nodes()
             pressure_objects.append((ltp, gp))
+        for kind, obj in ((("", lt),) + ((" at p", ltp),) * at_pressure) * (slots > 0):
+            obj.set_slots([nobs * k // slots for k in range(slots + 1)])
+            for k in range(slots):                            # every slot once, on the start state: the analysis asks for it
+                en.observe(obj, k)
+            torch.cuda.synchronize()
+            with sp.graph_capture() as go:
+                en.observe(obj, slots // 2)
+            with sp.graph_capture() as gf:
+                en.analyse(obj, slots=True)
+            for name, gr in (("slot observe%s E=%d" % (kind, E), go), ("analysis slots%s E=%d" % (kind, E), gf)):
+                fns[name], nodes[name] = gr.launch, gr.num_nodes()
+                mask_objects.append((obj, gr))
+            # Replays of Ensemble.analyse analyse the state the replay before left, while the slots keep the start state's hx: the
+            # two graphs above solve different eigenproblems.  The finish kernel's own cost against the observation kernel's is the
+            # difference of Letkf.analyse_grid, plain and by slots, on ONE gridded ensemble -- the start state's, which the last
+            # observe left in the grid workspace -- with every slot observed on it: the same bits, so the same work after it
+            grid = torch.from_numpy(obj.field("grid").numpy()).cuda()
+            L = E * kx
+            xs = [grid[v * L:(v + 1) * L].reshape((E, kx) + sp.grid_shape) for v in range(4)] + [grid[4 * L:]]
+            out = [torch.empty_like(a) for a in xs]
+            for k in range(slots):
+                obj.observe_grid(k, *xs)
+            for name, how in (("grid analysis plain%s E=%d" % (kind, E), False), ("grid analysis slots%s E=%d" % (kind, E), True)):
+                with sp.graph_capture() as gg:
+                    obj.analyse_grid(*xs, out=out, slots=how)
+                fns[name], nodes[name] = gg.launch, gg.num_nodes()
+                mask_objects.append(((xs, out), gg))
         if relax is not None:
             ltr = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, rtpp=relax[0], rtps=relax[1],
                           **({} if stride == (1, 1) else {"weight_stride": stride}))
@@ -712,6 +749,9 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
             row.update(stride=list(stride), **interp.get(E, {}))
             if name.startswith("analysis at p"):
                 row.update(observations_in_column=used[E])
+            if name.startswith("analysis slots"):
+                plain = t[name.replace("analysis slots", "analysis")][0]
+                row.update(slots=slots, us_over_plain=round(med - plain, 2))
             if " mask K=" in name:
                 row.update(members_used=E - int(name.split("K=")[1]))
             cycle = 36 * t["step E=%d physics" % E][0]
@@ -723,6 +763,10 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
             moved = 8 * (3 * E + 1) * (4 * kx + 1) * sp.il * sp.ix
             row.update(rtpp=relax[0], rtps=relax[1], us_over_unrelaxed=round(extra, 2), relax_bytes=moved,
                        relax_us_at_hbm_peak=round(moved / HBM * 1e6, 2))
+        if name.startswith("grid analysis slots"):
+            row.update(slots=slots, us_over_plain=round(med - t[name.replace("grid analysis slots", "grid analysis plain")][0], 2))
+        if name.startswith("slot observe"):
+            row.update(slots=slots, observations_in_slot=nobs * (slots // 2 + 1) // slots - nobs * (slots // 2) // slots)
         if name.startswith(("observe", "verify")):
             cycle = 36 * t["step E=%d physics" % E][0] + t["analysis E=%d" % E][0]
             row.update(us_cycle=round(cycle, 1), share_of_cycle=round(med / cycle, 5))
@@ -753,6 +797,7 @@ def main():
     ap.add_argument("--letkf", action="store_true")
     ap.add_argument("--osse", action="store_true")
     ap.add_argument("--at-pressure", action="store_true")
+    ap.add_argument("--slots", type=int, default=0, metavar="S")
     ap.add_argument("--mask", nargs="+", default=[], metavar="K")
     ap.add_argument("--pressure", action="store_true")
     ap.add_argument("--relax", nargs=2, type=float, metavar=("RTPP", "RTPS"))
@@ -779,7 +824,7 @@ def main():
         for tag in a.sizes:
             if a.letkf:
                 run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure, a.mask,
-                          tuple(a.relax) if a.relax else None)
+                          tuple(a.relax) if a.relax else None, a.slots)
             elif a.pressure:
                 run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:
