@@ -1,0 +1,272 @@
+"""The twin cycle on the host: a truth and E members that real model steps carry through two windows of a 4D-LETKF cycle, every
+piece the host reference of its device call -- the C oracle's step (tests/dynstep.py) from a state real steps keep bounded
+(tests/longrun.py), the observation values and the scores of tests/nature.py, the slot analysis of tests/letkfslots.py.  What the
+two test files of the cycle share ("the cycle on real forecasts").
+
+The set-up, T30 L5: longrun.rest_state(wind = 1e-5) plus a seeded smooth vorticity perturbation per state (amplitude 4e-6, spectrum
+(1 + l)^-1.5: with a flat spectrum or fewer than 8 members the analysis is worse than the background, the adiabatic core has no
+drag and too few members span the error); the start-up sequence and 9 leapfrog steps of spin-up; then windows of 9 leapfrog steps,
+observed after steps 3, 6 and 9 (600 stations in three slots of 200), analysed after step 9, the members started up again from the
+analysed time level 1 while the truth keeps stepping.
+
+Time level 1 is what is observed and analysed, as on the device: after leapfrog step n of a window it is one delt behind time
+level 2, and right after a start-up it is the analysed state itself.
+
+A state is tests/dynstep.py's dict; `sts` is a list of them, the members in ascending order; the oracle's implicit tables are set
+for one time step at a time, so all states go through a step together."""
+import numpy as np
+
+import dynstep
+import letkf as lk
+import letkfslots as ls
+import longrun
+import nature as nt
+import synth
+
+TAG = "t30k5"
+E = 12
+NOBS, FIRST, SLOT_STEPS, WINDOW, SPINUP = 600, [0, 200, 400, 600], (3, 6, 9), 9, 9
+DELT = longrun.DELT
+SIGMA_H, SIGMA_V, RHO = 1.0e6, 0.0, 1.0
+WIND, AMPLITUDE, SLOPE = 1.0e-5, 4.0e-6, 1.5
+TRUTH_SEED, MEMBER_SEED, NETWORK_SEED, NOISE_SEED = 900, 1000, 5, 77
+ERR_FACTOR = 0.25
+OBSERVED = (lk.U, lk.V, lk.T, lk.PS)
+SCORED = ("u", "t", "ps")
+
+
+# ---------------------------------------------------------------------------------------------------- states and steps
+def initial_states(o, nmem=E):
+    """-> (truth, members): the rest state with its seeded vorticity plus the state's own perturbation on both time levels;
+    orography, tcorh and qcorh are the rest state's in all"""
+    base = longrun.rest_state(o, wind=WIND)
+    l = np.arange(o.mx)[None, :] + np.arange(o.nx)[:, None]
+
+    def one(seed):
+        p = synth.spectra(o.kx, o.trunc, first=seed) * (1.0 + l) ** -SLOPE * AMPLITUDE
+        p[:, 0, 0] = 0.0
+        return dict(base, vor=base["vor"] + p[None])
+    return one(TRUTH_SEED), [one(MEMBER_SEED + e) for e in range(nmem)]
+
+
+def step_all(o, sts, j1, j2, dt):
+    """step(j1, j2, dt) of every state -> (the new states, the step's geopotential of each)"""
+    eps = 0.0 if j1 == 1 else dynstep.ROB
+    done = [dynstep.oracle_dynamics_step(o, st, j1, dt, eps, j2=j2) for st in sts]
+    return [new for new, _ in done], [aux["phi"] for _, aux in done]
+
+
+def startup(o, sts):
+    """first_step (time_stepping.f90:12-24) of every state -> (the states, phi of the second step); leaves the oracle's implicit
+    tables at 2 delt, where the leapfrog steps need them"""
+    o.tail_init(0.5 * DELT)
+    sts, _ = step_all(o, sts, 1, 1, 0.5 * DELT)
+    o.tail_init(DELT)
+    sts, phi = step_all(o, sts, 1, 2, DELT)
+    o.tail_init(2.0 * DELT)
+    return sts, phi
+
+
+def leapfrog(o, sts, nsteps):
+    """-> [sts after 0, 1, .. nsteps leapfrog steps]; the oracle's implicit tables are at 2 delt"""
+    out = [sts]
+    for _ in range(nsteps):
+        out.append(step_all(o, out[-1], 2, 2, 2.0 * DELT)[0])
+    return out
+
+
+def spun_up(o, nmem=E):
+    """-> (truth, members) after the start-up sequence and SPINUP leapfrog steps"""
+    truth, members = initial_states(o, nmem)
+    sts, _ = startup(o, [truth] + members)
+    sts = leapfrog(o, sts, SPINUP)[-1]
+    return sts[0], sts[1:]
+
+
+def level1(sts, name):
+    """time level 1 of `name` of the states, member axis first: what Ensemble holds as getattr(ens, name)[0]"""
+    return np.stack([st[name][0] for st in sts])
+
+
+# ---------------------------------------------------------------------------------------------------- the network
+def network(g, x):
+    """NOBS stations: longitude uniform, latitude arcsin of U(-0.98, 0.98), variables cycling u, v, t, ps, level o mod kx (0 for
+    ps), error ERR_FACTOR x the members' sample standard deviation of H x on the gridded ensemble x; the values are zero"""
+    rng = np.random.default_rng(NETWORK_SEED)
+    lon = rng.uniform(0.0, 360.0, NOBS)
+    lat = np.degrees(np.arcsin(rng.uniform(-0.98, 0.98, NOBS)))
+    var = np.array([OBSERVED[n % 4] for n in range(NOBS)])
+    lev = np.where(var == lk.PS, 0, np.arange(NOBS) % g.kx)
+    net = lk.make_obs(var, lev, lon, lat, np.zeros(NOBS), np.ones(NOBS))
+    net["error"] = ERR_FACTOR * lk.obs_space(g, x, net)[0].std(axis=1, ddof=1)
+    assert (net["error"] > 0.0).all()
+    return net
+
+
+def rows(s):
+    return slice(FIRST[s], FIRST[s + 1])
+
+
+def values(g, truths, net, cycle):
+    """the values of a window: slot s from the gridded truth truths[s], draw 3 cycle + s of seed NOISE_SEED at noise 1 on the
+    slot's rows -- what one Nature.observe(slot=s) per slot draws, a reset Nature before cycle 0"""
+    value = np.zeros(NOBS)
+    for s, truth in enumerate(truths):
+        value[rows(s)] = nt.observe(g, truth, net, net["error"], NOISE_SEED, 3 * cycle + s, 1.0)[rows(s)]
+    return value
+
+
+# ---------------------------------------------------------------------------------------------------- the analysis
+def analyse(g, x, xs, obs, cols=None):
+    """the slot analysis of the gridded ensemble x, the slots observed on xs -> (the increments on the grid, (E, kx, il, ix) and
+    (E, il, ix), the obs_space_slots dict, the largest condition number)"""
+    C, b, space = ls.problems_slots(g, xs, obs, FIRST, SIGMA_H, SIGMA_V, cols)
+    inc, kappa = lk.increments(g, x, C, b, RHO, "eigh", cols)
+    return {v: inc[v].reshape(x[v].shape) for v in lk.VARS}, space, kappa
+
+
+def add_increments(o, sts, inc):
+    """the gridded increments as spectra -- vor and div by the oracle's vdspec(du, dv, 2), t, q and ps by grid_to_spec -- added to
+    time level 1 of copies of the states; time level 2 is left, stale, for the start-up to overwrite"""
+    out = []
+    for e, st in enumerate(sts):
+        new = {n: np.array(st[n], copy=True) for n in dynstep.PROG}
+        for k in range(o.kx):
+            dvor, ddiv = o.vdspec(inc["u"][e, k], inc["v"][e, k], 2)
+            new["vor"][0, k] += dvor
+            new["div"][0, k] += ddiv
+            new["t"][0, k] += o.grid_to_spec(inc["t"][e, k])
+            new["tr"][0, k] += o.grid_to_spec(inc["q"][e, k])
+        new["ps"][0] += o.grid_to_spec(inc["ps"][e])
+        out.append(dict(st, **new))
+    return out
+
+
+def truth_of(o, st):
+    return nt.as_truth(lk.oracle_grids(o, [st]))
+
+
+def ratios(after, before):
+    """rmse of `after` over rmse of `before`, the mean over the levels, for the variables SCORED"""
+    return {v: float(np.mean(np.atleast_1d(after["rmse"][v]) / np.atleast_1d(before["rmse"][v]))) for v in SCORED}
+
+
+# ---------------------------------------------------------------------------------------------------- a window and the cycle
+def forecast(o, members, truth, nsteps=WINDOW + 1):
+    """members and truth through nsteps leapfrog steps (one past the window: the tests need the analysis time's neighbour too)
+    -> {"members": [sts after step 0 .. nsteps], "truth": [...], "x": their gridded ensembles, "xt": the gridded truths}"""
+    run = leapfrog(o, [truth] + members, nsteps)
+    out = {"truth": [sts[0] for sts in run], "members": [sts[1:] for sts in run]}
+    out["x"] = [lk.oracle_grids(o, sts) for sts in out["members"]]
+    out["xt"] = [truth_of(o, st) for st in out["truth"]]
+    return out
+
+
+def window(o, g, w, members, truth, net, cycle, misdated=False):
+    """One window from the members' and the truth's states at its start: the forecast, the values, the slot analysis at step
+    WINDOW, the analysed states.  -> the forecast's dict with "obs" (the network with the window's values), "obs_space", "inc",
+    "kappa", "analysed" (states), "xa" (their gridded ensemble), "scores" {"background", "analysis"} at the analysis time; with
+    misdated also "misdated": {"inc", "scores"}, the same values with every H x taken at the analysis time"""
+    out = forecast(o, members, truth)
+    x = out["x"][WINDOW]
+    out["obs"] = dict(net, value=values(g, [out["xt"][n] for n in SLOT_STEPS], net, cycle))
+    out["inc"], out["obs_space"], out["kappa"] = analyse(g, x, [out["x"][n] for n in SLOT_STEPS], out["obs"])
+    out["analysed"] = add_increments(o, out["members"][WINDOW], out["inc"])
+    out["xa"] = lk.oracle_grids(o, out["analysed"])
+    xt = out["xt"][WINDOW]
+    out["scores"] = {"background": nt.scores(g, x, xt, w), "analysis": nt.scores(g, out["xa"], xt, w)}
+    if misdated:
+        inc, _, _ = analyse(g, x, [x] * len(SLOT_STEPS), out["obs"])
+        xa = lk.oracle_grids(o, add_increments(o, out["members"][WINDOW], inc))
+        out["misdated"] = {"inc": inc, "scores": nt.scores(g, xa, xt, w)}
+    return out
+
+
+def cycle(o, g, w, nmem=E):
+    """Two windows -> {"start": (truth, members) after the spin-up, "net", "windows": [window 0, window 1], "restart": (the
+    members after the start-up from window 0's analysed states, that start-up's phi), "free": the scores of the members never
+    analysed at the second analysis time}.  Window 0 carries the misdated control"""
+    truth, members = spun_up(o, nmem)
+    net = network(g, lk.oracle_grids(o, members))
+    first = window(o, g, w, members, truth, net, 0, misdated=True)
+    restarted, phi = startup(o, first["analysed"])
+    second = window(o, g, w, restarted, first["truth"][WINDOW], net, 1)
+    free = leapfrog(o, first["members"][WINDOW], WINDOW)[-1]
+    return {"start": (truth, members), "net": net, "windows": [first, second], "restart": (restarted, phi),
+            "free": nt.scores(g, lk.oracle_grids(o, free), second["xt"][WINDOW], w)}
+
+
+def separation(g, win, net):
+    """per slot and observed variable, the smaller of max |hx(step n) - hx(step n - 1)| and max |hx(step n) - hx(step n + 1)| over
+    the slot's rows of the variable, divided by the variable's scale max |x| -> {(slot, variable): ratio}"""
+    out = {}
+    for s, n in enumerate(SLOT_STEPS):
+        sub = {k: a[rows(s)] for k, a in net.items()}
+        hx = {m: lk.obs_space(g, win["x"][m], sub)[0] for m in (n - 1, n, n + 1)}
+        for v in OBSERVED:
+            at = sub["var"] == v
+            scale = float(np.max(np.abs(win["x"][n][lk.VARS[v]])))
+            out[(s, lk.VARS[v])] = min(float(np.max(np.abs(hx[n][at] - hx[m][at]))) for m in (n - 1, n + 1)) / scale
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- measured on the reference
+# rmse ratios of the host cycle at E = 12 (tests/test_twin_cycle_cpu.py prints them), and the thresholds both test files assert:
+# the midpoint between the measured value and 1.  The device differs from the reference by rounding; a dating error lands on
+# the other side of 1.  "4d", "misdated": analysis over background, first window; "restart": the second window's background over
+# the free run (t and ps: u's ratio is below 1 as well, but the issue of the cycle is stated on the mass field).
+MEASURED = {"4d": {"u": 0.706, "t": 0.561, "ps": 0.672}, "misdated": {"u": 3.415, "t": 2.231, "ps": 3.425},
+            "restart": {"t": 0.834, "ps": 0.912}}
+THRESHOLD = {k: {v: 0.5 * (r + 1.0) for v, r in m.items()} for k, m in MEASURED.items()}
+
+
+# ---------------------------------------------------------------------------------------------------- what the GPU tests share
+def gridded(G, nmem, kx):
+    """an analysis object's grid workspace, downloaded (Letkf.field("grid"): u, v, t, q of every member and level, then ps), as a
+    gridded ensemble; after Ensemble.observe or verify it holds the members on the grid"""
+    shape = G.shape[-2:]
+    x = {v: G[n * nmem * kx:(n + 1) * nmem * kx].reshape((nmem, kx) + shape).copy() for n, v in enumerate(lk.VARS[:4])}
+    x["ps"] = G[4 * nmem * kx:].copy()
+    return x
+
+
+def host_states(level1_of, level2_of, shared):
+    """states for the oracle from device downloads: level1_of, level2_of {name: (E, ...)} -> a list of E states"""
+    nmem = level1_of["ps"].shape[0]
+    return [dict(shared, **{n: np.stack([level1_of[n][e], level2_of[n][e]]) for n in dynstep.PROG}) for e in range(nmem)]
+
+
+def spectral_errors(got, sts, lv):
+    """the largest of relerr and wave_relerr over the members, of the device's time level lv (0, 1) `got` {name: (E, ...)} against
+    the host states -> {name: error}"""
+    out = {}
+    for n in dynstep.PROG:
+        out[n] = max(max(synth.relerr(got[n][e], st[n][lv]), dynstep.wave_relerr(got[n][e], st[n][lv])) for e, st in enumerate(sts))
+    return out
+
+
+def grid_errors(x, ref):
+    """max |x - ref| / max |ref| per variable"""
+    return {v: synth.relerr(x[v], ref[v]) for v in lk.VARS}
+
+
+# ---------------------------------------------------------------------------------------------------- the scores' limits
+def score_limits(g, x, truth, w, nmem):
+    """(relative limit of rmse and spread, absolute limit of the bias per row (4 kx + 1)) of the device scores against
+    tests/nature.py's: rmse and spread are roots of sums of ncol non-negative terms, each an nmem-term sum and a handful of
+    operations, and the root halves the relative error: 4 (ncol + nmem + 8) eps; the bias is a sum of ncol terms that cancels, so
+    its error scales with <|m - truth|>: 4 (ncol + nmem) eps of it"""
+    ncol = g.ix * g.il
+    absm = {v: np.abs(np.sum(x[v].reshape(nmem, -1, g.il, g.ix) - truth[v].reshape(-1, g.il, g.ix)[None], axis=0) / nmem) for v in lk.VARS}
+    gw = nt.normalised(w)
+    mean = np.concatenate([np.einsum("j,kj->k", gw, absm[v].sum(axis=-1) / g.ix) for v in lk.VARS])
+    return 4 * (ncol + nmem + 8) * lk.EPS, 4 * (ncol + nmem) * lk.EPS * mean
+
+
+def score_ratios(got, want, rel, bias_abs):
+    """got, want: (3, 4 kx + 1) tables rmse | bias | spread -> the largest error-to-limit ratio of each.  A row whose limit is 0 --
+    q on the two stratospheric levels, where truth and members hold exactly 0 -- has to be met exactly: ratio 0, or infinite"""
+    def worst(err, lim):
+        return float(np.max(np.where(lim > 0.0, err / np.where(lim > 0.0, lim, 1.0), np.where(err == 0.0, 0.0, np.inf))))
+    return {"rmse": worst(np.abs(got[0] - want[0]), rel * want[0]), "bias": worst(np.abs(got[1] - want[1]), bias_abs),
+            "spread": worst(np.abs(got[2] - want[2]), rel * want[2])}
