@@ -54,26 +54,19 @@ int upload(spdy_plan *p, void *dst, const void *src, size_t bytes)
     return SPDY_OK;
 }
 
-// the argument checks the two analysis calls share, in the documented order; the device last
-int analysis_ready(spdy_letkf *l, bool ptrs_ok)
+// the argument checks the analysis calls share, in the documented order; slots: a slot analysis, which needs before the device
+// every non-empty slot observed since the latest spdy_slot_set; the device last
+int analysis_ready(spdy_letkf *l, bool ptrs_ok, bool slots)
 {
     NEED_LIVE(l, "analysis object");
     if (!l->loc_set) return fail(SPDY_ERR_STATE, "letkf: spdy_letkf_set_localization first");
     if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
-    NEED_DEVICE(l->plan);
-    return SPDY_OK;
-}
-
-// the slot analysis' checks: analysis_ready's, and before the device every non-empty slot observed since the latest spdy_slot_set
-int slot_analysis_ready(spdy_letkf *l, bool ptrs_ok)
-{
-    NEED_LIVE(l, "analysis object");
-    if (!l->loc_set) return fail(SPDY_ERR_STATE, "letkf: spdy_letkf_set_localization first");
-    if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
-    if (!l->nslots) return fail(SPDY_ERR_STATE, "slot analysis: spdy_slot_set first");
-    for (int s = 0; s < l->nslots; ++s)
-        if (l->slot_first[s + 1] > l->slot_first[s] && !l->slot_observed[s])
-            return fail(SPDY_ERR_STATE, "slot analysis: slot %d has not been observed since spdy_slot_set", s);
+    if (slots) {
+        if (!l->nslots) return fail(SPDY_ERR_STATE, "slot analysis: spdy_slot_set first");
+        for (int s = 0; s < l->nslots; ++s)
+            if (l->slot_first[s + 1] > l->slot_first[s] && !l->slot_observed[s])
+                return fail(SPDY_ERR_STATE, "slot analysis: slot %d has not been observed since spdy_slot_set", s);
+    }
     NEED_DEVICE(l->plan);
     return SPDY_OK;
 }
@@ -89,22 +82,34 @@ int observe_ready(spdy_letkf *l, int slot, bool ptrs_ok)
     return SPDY_OK;
 }
 
+// the observation stage's argument for the observations [first, last) of l's network on the gridded ensemble x: the tables, the
+// outputs and, for a network that holds an observation at a pressure, the pressure part
+spdy::LetkfObserve observe_args(spdy_letkf *l, const double *const *x, int first, int last)
+{
+    spdy_plan *p = l->plan;
+    spdy::LetkfObserve o{};
+    o.first = first; o.last = last; o.nmem = l->nmem; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
+    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.value = l->d_value;
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) o.x[v] = x[v];
+    o.hx = l->d_hx; o.hxmean = l->d_hxmean; o.y = l->d_y; o.dep = l->d_dep;
+    if (l->npobs) {
+        o.atp = l->d_atp; o.lnp = l->d_lnp; o.rinv = l->d_rinv; o.olns = l->d_olns; o.used = l->d_used; o.reff = l->d_reff;
+        o.slot_ps = l->d_slot_ps; o.slot_out = l->d_slot_out; o.lv = l->lv;
+    }
+    return o;
+}
+
 // the slot kernel on a gridded ensemble: ONE launch, none for an empty slot; the slot is marked observed
 int observe_grid(spdy_letkf *l, int slot, const double *const *x)
 {
-    spdy_plan *p = l->plan;
-    spdy::LetkfSlotObs o{};
-    o.first = l->slot_first[slot]; o.last = l->slot_first[slot + 1]; o.nmem = l->nmem; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
-    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.hx = l->d_hx;
-    for (int v = 0; v < spdy::LETKF_VARS; ++v) o.x[v] = x[v];
-    if (l->npobs) { o.atp = l->d_atp; o.lnp = l->d_lnp; o.slot_ps = l->d_slot_ps; o.slot_out = l->d_slot_out; o.lv = l->lv; }
-    KERNEL(spdy::launch_letkf_slot_obs(o, p->stream));
+    KERNEL(spdy::launch_letkf_slot_obs(observe_args(l, x, l->slot_first[slot], l->slot_first[slot + 1]), l->plan->stream));
     l->slot_observed[slot] = true;
     return SPDY_OK;
 }
 
 // d_use: NULL, or the member mask -- one launch more in front, which builds the table the masked forms of the kernels read.
-// slots: the finish kernel of "observations in time slots" in the observation kernel's place, everything else as it is
+// slots: the finish kernel of "observations in time slots" in the observation kernel's place, everything else as it is.
+// The observation stage's argument is filled once (observe_args); one branch: observe now, or finish what the slots kept
 int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const int *d_use = nullptr, bool slots = false)
 {
     spdy_plan *p = l->plan;
@@ -112,10 +117,8 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
     if (d_use) KERNEL(spdy::launch_letkf_mask(d_use, l->nmem, l->d_umap, l->d_nused + 1, p->stream));
     l->masked_last = d_use != nullptr;
     const int kx = p->tab.kx, ncol = (int)grid_elems(p);
-    spdy::LetkfObs o{};
-    o.nobs = l->nobs; o.nmem = l->nmem; o.kx = kx; o.ncol = ncol;
-    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.value = l->d_value;
-    o.hx = l->d_hx; o.hxmean = l->d_hxmean; o.y = l->d_y; o.dep = l->d_dep;
+    spdy::LetkfObserve o = observe_args(l, x, 0, l->nobs);
+    o.umap = umap;
     spdy::LetkfCols c{};
     c.nobs = l->nobs; c.nmem = l->nmem; c.kx = kx; c.ncol = ncol; c.nlv = l->nlv;
     c.ch = l->sigma_h * std::sqrt(10.0 / 3.0); c.cv = l->sigma_v > 0.0 ? l->sigma_v * std::sqrt(10.0 / 3.0) : 0.0;
@@ -137,30 +140,15 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
         KERNEL(spdy::launch_letkf_relax(r, p->stream));
         return SPDY_OK;
     };
-    for (int v = 0; v < spdy::LETKF_VARS; ++v) { o.x[v] = x[v]; c.x[v] = x[v]; c.dx[v] = raw[v]; }
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) { c.x[v] = x[v]; c.dx[v] = raw[v]; }
+    // A network that holds an observation at a pressure: the observation stage writes ln sigma_o of those observations into olns and
+    // this call's copy of rinv, 0 where an observation is out of its column.  slots: hx (and the stencils' ps and out-of-column
+    // flags) are the slots', and only what couples members is formed here.
+    if (l->npobs) c.rinv = l->d_reff;
     if (slots) {
-        // hx (and the stencils' ps and out-of-column flags) are the slots': only what couples members is formed here
-        spdy::LetkfSlotFinish f{};
-        f.nobs = l->nobs; f.nmem = l->nmem; f.hx = l->d_hx; f.value = l->d_value; f.hxmean = l->d_hxmean; f.y = l->d_y; f.dep = l->d_dep;
-        f.umap = umap;
-        if (l->npobs) {
-            f.atp = l->d_atp; f.lnp = l->d_lnp; f.rinv = l->d_rinv; f.slot_ps = l->d_slot_ps; f.slot_out = l->d_slot_out;
-            f.olns = l->d_olns; f.used = l->d_used; f.reff = l->d_reff;
-            c.rinv = l->d_reff;
-        }
-        KERNEL(spdy::launch_letkf_slot_finish(f, p->stream));
-    } else if (l->npobs) {
-        // observations at a pressure: the kernel that interpolates per member, in letkf_obs_kernel's place; it writes ln sigma_o of
-        // those observations into olns and this call's copy of rinv, 0 where an observation is out of its column
-        spdy::LetkfPObs po{};
-        po.o = o; po.atp = l->d_atp; po.lnp = l->d_lnp; po.rinv = l->d_rinv; po.olns = l->d_olns; po.used = l->d_used; po.reff = l->d_reff;
-        po.lv = l->lv; po.umap = umap;
-        c.rinv = l->d_reff;
-        KERNEL(spdy::launch_letkf_pobs(po, p->stream));
-    } else if (umap) {
-        KERNEL(spdy::launch_letkf_obs_masked(o, umap, p->stream));
+        KERNEL(spdy::launch_letkf_slot_finish(o, p->stream));
     } else {
-        KERNEL(spdy::launch_letkf_obs(o, p->stream));
+        KERNEL(spdy::launch_letkf_observe(o, p->stream));
     }
     auto transform = [&]() -> int {
         if (umap) {
@@ -541,7 +529,7 @@ int spdy_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *v
 int spdy_mask_letkf_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
                                      double *du, double *dv, double *dt, double *dq, double *dps, const int *d_use)
 {
-    RC(analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps));
+    RC(analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps, false));
     const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
     double *dx[spdy::LETKF_VARS] = {du, dv, dt, dq, dps};
     return analyse_grid(l, x, dx, d_use);
@@ -554,7 +542,7 @@ int spdy_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, doubl
 
 int spdy_mask_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use)
 {
-    RC(analysis_ready(l, vor && div && t && q && ps));
+    RC(analysis_ready(l, vor && div && t && q && ps, false));
     return ens_analyse(l, vor, div, t, q, ps, d_use, false);
 }
 
@@ -600,7 +588,7 @@ int spdy_slot_observe_dev(spdy_letkf *l, int slot, const double *vor, const doub
 int spdy_slot_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
                                double *du, double *dv, double *dt, double *dq, double *dps, const int *d_use)
 {
-    RC(slot_analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps));
+    RC(analysis_ready(l, ug && vg && tg && qg && psg && du && dv && dt && dq && dps, true));
     const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
     double *dx[spdy::LETKF_VARS] = {du, dv, dt, dq, dps};
     return analyse_grid(l, x, dx, d_use, true);
@@ -608,7 +596,7 @@ int spdy_slot_analyse_grid_dev(spdy_letkf *l, const double *ug, const double *vg
 
 int spdy_slot_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, double *q, double *ps, const int *d_use)
 {
-    RC(slot_analysis_ready(l, vor && div && t && q && ps));
+    RC(analysis_ready(l, vor && div && t && q && ps, true));
     return ens_analyse(l, vor, div, t, q, ps, d_use, true);
 }
 

@@ -39,6 +39,21 @@ int need_slot(const spdy_nature *n, const char *call, int slot)
     return SPDY_OK;
 }
 
+// the values of the observations [first, last) of l's network, by the network's kind, then the counter: two launches; an empty
+// range launches the count alone
+int draw(spdy_nature *n, spdy_letkf *l, int first, int last, double noise)
+{
+    spdy_plan *p = n->plan;
+    spdy::NatureObs o{};
+    o.first = first; o.last = last; o.nobs = l->nobs; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
+    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.error = l->d_err;
+    o.truth = n->d_truth; o.state = n->d_state; o.noise = noise; o.value = l->d_value;
+    if (l->npobs) { o.atp = l->d_atp; o.lnp = l->d_lnp; o.lv = l->lv; }
+    KERNEL(spdy::launch_nature_slot_draw(o, p->stream));
+    KERNEL(spdy::launch_nature_count(n->d_state, p->stream));
+    return SPDY_OK;
+}
+
 int restart(spdy_nature *n, unsigned long long seed)
 {
     const unsigned long long h[2] = {seed, 0ull};
@@ -146,18 +161,7 @@ int spdy_nature_observe_dev(spdy_nature *n, spdy_letkf *l, double noise)
     if (!(noise >= 0.0) || !std::isfinite(noise)) return fail(SPDY_ERR_ARG, "nature_observe: noise must be finite and >= 0");
     spdy_plan *p = n->plan;
     NEED_DEVICE(p);
-    spdy::NatureObs o{};
-    o.nobs = l->nobs; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
-    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.error = l->d_err;
-    o.truth = n->d_truth; o.state = n->d_state; o.noise = noise; o.value = l->d_value;
-    if (l->npobs) {
-        // observations at a pressure: the draw kernel that interpolates the truth's columns, in nature_draw_kernel's place
-        KERNEL(spdy::launch_nature_pdraw(o, l->d_atp, l->d_lnp, l->lv, p->stream));
-    } else {
-        KERNEL(spdy::launch_nature_draw(o, p->stream));
-    }
-    KERNEL(spdy::launch_nature_count(n->d_state, p->stream));
-    return SPDY_OK;
+    return draw(n, l, 0, l->nobs, noise);
 }
 
 int spdy_slot_nature_observe_dev(spdy_nature *n, spdy_letkf *l, int slot, double noise)
@@ -168,15 +172,7 @@ int spdy_slot_nature_observe_dev(spdy_nature *n, spdy_letkf *l, int slot, double
     if (slot < 0 || slot >= l->nslots) return fail(SPDY_ERR_ARG, "slot_nature_observe: slot=%d outside [0, nslots=%d)", slot, l->nslots);
     spdy_plan *p = n->plan;
     NEED_DEVICE(p);
-    spdy::NatureObs o{};
-    o.nobs = l->nobs; o.kx = p->tab.kx; o.ncol = (int)grid_elems(p);
-    o.var = l->d_var; o.lev = l->d_lev; o.sidx = l->d_sidx; o.swgt = l->d_swgt; o.error = l->d_err;
-    o.truth = n->d_truth; o.state = n->d_state; o.noise = noise; o.value = l->d_value;
-    // the draw of the slot's range, by the network's kind; an empty slot launches the count alone
-    KERNEL(spdy::launch_nature_slot_draw(o, l->slot_first[slot], l->slot_first[slot + 1], l->npobs ? l->d_atp : nullptr, l->d_lnp, l->lv,
-                                         p->stream));
-    KERNEL(spdy::launch_nature_count(n->d_state, p->stream));
-    return SPDY_OK;
+    return draw(n, l, l->slot_first[slot], l->slot_first[slot + 1], noise);
 }
 
 int spdy_nature_verify_dev(spdy_nature *n, spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q,

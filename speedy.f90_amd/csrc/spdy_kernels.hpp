@@ -522,38 +522,43 @@ hipError_t launch_diagnostics_use(const DiagLevel *state, int nmem, int kx, int 
 // member-major: field (e, k) of a level variable starts (e * kx + k) * ncol doubles in, the surface field of member e e * ncol.
 enum { LETKF_VARS = 5 };                             // u, v, t, q, ps: the SPDY_OBS_* order
 constexpr int LETKF_MAX_MEMBERS = 32;
-// hx, hxmean, y, departure of every observation, one thread each: the four-point stencil the host made, the members in ascending
-// order.
-struct LetkfObs {
-    int nobs, nmem, kx, ncol;
+// The observation stage (csrc/spdy_obsop.hpp): one argument for every launch that observes or couples.  The
+// observations [first, last) of the network: the four-point stencil the host made, the members in ascending order.  atp NULL: a
+// model-level network, and nothing of the pressure part is read or written.  Otherwise (include/spdy.h, "observations at a
+// pressure") atp[o] != 0 marks an observation given at a pressure (its lev[o] is 0: a kernel that does not know of it
+// stays in bounds) and lnp[o] = ln(p_o / p0) is its target.
+struct LetkfObserve {
+    int first, last, nmem, kx, ncol;
     const int *var, *lev, *sidx;                     // [nobs], [nobs] (0 for ps), [nobs][4] grid points j * ix + i
     const double *swgt, *value;                      // [nobs][4], [nobs]
     const double *x[LETKF_VARS];                     // the gridded ensemble
     double *hx, *hxmean, *y, *dep;                   // [nobs][nmem], [nobs], [nobs][nmem], [nobs]
+    const int *atp;                                  // [nobs], or NULL
+    const double *lnp, *rinv;                        // [nobs], [nobs] 1 / error^2
+    double *olns, *used, *reff;                      // [nobs] each
+    double *slot_ps, *slot_out;                      // [nobs][nmem] each: what a slot keeps per member besides hx
+    VLevels lv;                                      // ln fsg
+    const int *umap;                                 // NULL, or the member mask's table (below)
 };
-hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s);
+// hx, hxmean, y and departure of every observation of the range in one launch.  A model-level network: one thread per observation.
+// With atp: a workgroup owns whole observations, one thread per (observation, member) interpolates the four stencil columns of its
+// member, one thread per observation then couples the members; written besides: olns[o] = lnp[o] - psbar_o of the at-pressure
+// observations only (the others keep what set_obs uploaded), used[o] (1.0 / 0.0) and reff[o] = used ? rinv[o] : 0.0 of all.
+// umap: the sums and the out-of-column test over its members, y = 0.0 for the others; hx is every member's own.
+hipError_t launch_letkf_observe(const LetkfObserve &a, hipStream_t s);
+// Observations in time slots (include/spdy.h, "observations in time slots"; DESIGN.md s25).  Observing a slot: what is per member
+// only, one thread per (observation of the range, member) -- hx[o][e] with the bits launch_letkf_observe gives it and, with atp,
+// slot_ps[o][e], the stencil's ps_e, and slot_out[o][e], 1.0 / 0.0, the member's out-of-column flag.  Nothing else is written, and
+// umap is not read.
+hipError_t launch_letkf_slot_obs(const LetkfObserve &a, hipStream_t s);
+// The finish, in the observation launch's place of an analysis call: everything that couples members, from the rows the slots kept
+// -- what launch_letkf_observe writes besides hx, with its bits.  x is not read.  One thread per observation.
+hipError_t launch_letkf_slot_finish(const LetkfObserve &a, hipStream_t s);
 // The member mask (include/spdy.h, "member mask").  One small launch turns the caller's use[nmem] into the table the
 // masked kernels read, umap [LETKF_UMAP]: umap[0] = n, the members in use; umap[1 + c] = u_c, the member of compact index c < n,
 // ascending; umap[LETKF_URANK + e] = member e's compact index, -1 for a member not in use; *nused = n as a double.
 enum { LETKF_URANK = 33, LETKF_UMAP = 66 };
 hipError_t launch_letkf_mask(const int *use, int nmem, int *umap, double *nused, hipStream_t s);
-// launch_letkf_obs over the members in use: hx of every member, hxmean, y and dep over umap's members, y = 0.0 for the others
-hipError_t launch_letkf_obs_masked(const LetkfObs &a, const int *umap, hipStream_t s);
-// The same quantities for a network that holds observations given at a pressure (include/spdy.h, "observations at a pressure";
-// DESIGN.md s22): atp[o] != 0 marks one (its lev[o] is 0: a kernel that does not know of it stays in bounds), lnp[o] = ln(p_o /
-// p0) is its target.  A workgroup owns whole observations, one thread per
-// (observation, member) interpolates the four stencil columns of its member (vinterp_brackets<true, 4>), one thread per observation
-// then sums over the members in ascending order.  Written besides LetkfObs' outputs: olns[o] = lnp[o] - psbar_o of the at-pressure
-// observations only (the others keep what set_obs uploaded), used[o] (1.0 / 0.0) and reff[o] = used ? rinv[o] : 0.0 of all.
-struct LetkfPObs {
-    LetkfObs o;
-    const int *atp;                                  // [nobs]
-    const double *lnp, *rinv;                        // [nobs], [nobs] 1 / error^2
-    double *olns, *used, *reff;                      // [nobs] each
-    VLevels lv;                                      // ln fsg
-    const int *umap;                                 // NULL, or the member mask's table: the sums and the out-of-column test over its members
-};
-hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s);
 // The local analyses: one workgroup per grid column.  nlv levels' eigenproblems are in flight at a time (1, 2 or 4: what the LDS
 // holds; the results do not depend on it); lds = letkf_lds_bytes(nmem, kx, nlv).
 struct LetkfCols {
@@ -561,7 +566,7 @@ struct LetkfCols {
     double ch, cv, diag;                             // c_h in metres, c_v (<= 0: no vertical factor), (nmem - 1) / rho
     const double *colunit, *lnfsg;                   // [3][ncol] unit vectors of the columns, [kx] ln fsg
     const double *ounit, *olns, *rinv;               // [nobs][3], [nobs] ln sigma_o, [nobs] 1 / error^2
-    const double *y, *dep;                           // as LetkfObs
+    const double *y, *dep;                           // as LetkfObserve
     const double *x[LETKF_VARS];
     double *dx[LETKF_VARS];                          // the increments; may be x
     // weight interpolation (both NULL / 0: every grid column is solved and gets its increments).  With a column list the
@@ -616,61 +621,31 @@ struct LetkfRelax {
     const int *umap;                                 // NULL, or the member mask's table
 };
 hipError_t launch_letkf_relax(const LetkfRelax &a, hipStream_t s);
-// Observations in time slots (include/spdy.h, "observations in time slots"; DESIGN.md s25).  Observing a slot: what is per member
-// only, of the observations [first, last) and every member, one thread per (observation, member) in letkf_pobs_kernel's layout --
-// hx[o][e] with the bits letkf_obs_kernel / letkf_pobs_kernel give it and, when atp is not NULL (the network holds an observation at a
-// pressure), slot_ps[o][e], the stencil's ps_e, and slot_out[o][e], 1.0 / 0.0, the member's out-of-column flag.  Nothing else is written.
-struct LetkfSlotObs {
-    int first, last, nmem, kx, ncol;
-    const int *var, *lev, *sidx;                     // as LetkfObs
-    const double *swgt;
-    const double *x[LETKF_VARS];                     // the gridded ensemble of the slot's time
-    double *hx;                                      // [nobs][nmem]
-    const int *atp;                                  // NULL: a model-level network, nothing below is read or written
-    const double *lnp;
-    double *slot_ps, *slot_out;                      // [nobs][nmem] each
-    VLevels lv;
-};
-hipError_t launch_letkf_slot_obs(const LetkfSlotObs &a, hipStream_t s);
-// The finish, in the observation kernel's place of an analysis call: everything that couples members, from the slots' rows -- hxmean,
-// y and dep of all nobs observations over the members in use (umap NULL: all), ascending, by select; with atp not NULL also olns of
-// the at-pressure observations, used and reff, as letkf_pobs_kernel's second half forms them.  One thread per observation.
-struct LetkfSlotFinish {
-    int nobs, nmem;
-    const double *hx, *value;
-    double *hxmean, *y, *dep;
-    const int *atp;                                  // NULL: a model-level network, nothing below is read or written
-    const double *lnp, *rinv, *slot_ps, *slot_out;
-    double *olns, *used, *reff;
-    const int *umap;                                 // NULL, or the member mask's table
-};
-hipError_t launch_letkf_slot_finish(const LetkfSlotFinish &a, hipStream_t s);
 
 // The nature run (csrc/spdy_nature.hip; include/spdy.h, "nature run").  The truth is one member of the analysis'
 // gridded layout: row f = v * kx + k of u, v, t, q, then ps, (4 kx + 1) grids.  state = {seed, draws}.
-// The observation values of an analysis object's network from the truth, one thread each: h in letkf_obs_kernel's order, then
-// value = h + (noise * error) * z with z = sppt_randn(o, 0, draws, seed); noise == 0 stores h.  Reads state, does not advance it.
+// The observation values of the observations [first, last) of an analysis object's network from the truth, one thread each
+// (include/spdy.h, "observations in time slots": a slot's draw is the whole network's draw on its range): h as the analysis forms
+// hx, the truth being the one member (csrc/spdy_obsop.hpp), then value = h + (noise * error) * z with z = sppt_randn(o, 0, draws,
+// seed); noise == 0 stores h.  Reads state, does not advance it.  atp NULL: a model-level network.  Otherwise atp[o] != 0 marks an
+// observation given at a pressure with the target lnp[o]: h is the bilinear sum of the four columns' values interpolated to the
+// target with the truth's ps, clamped to the end level outside the column.
 struct NatureObs {
-    int nobs, kx, ncol;
-    const int *var, *lev, *sidx;                     // the analysis object's tables, as LetkfObs
+    int first, last, nobs, kx, ncol;
+    const int *var, *lev, *sidx;                     // the analysis object's tables, as LetkfObserve
     const double *swgt, *error;                      // [nobs][4], [nobs]
     const double *truth;                             // (4 kx + 1) grids
     const unsigned long long *state;
     double noise;
     double *value;                                   // [nobs]
+    const int *atp;                                  // [nobs], or NULL
+    const double *lnp;                               // [nobs]
+    VLevels lv;                                      // ln fsg
 };
-hipError_t launch_nature_draw(const NatureObs &a, hipStream_t s);
-// The same for a network that holds observations given at a pressure (atp[o] != 0, target lnp[o]): h is the bilinear sum of the four
-// columns' values interpolated to the target with the truth's ps, clamped to the end level outside the column; noise and counter
-// as above.
-hipError_t launch_nature_pdraw(const NatureObs &a, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s);
-// Either of the two for the observations [first, last) of the network only (include/spdy.h, "observations in time slots"): the
-// thread of observation o forms what the kernels above form for it, counter (o, 0, draws) included; atp NULL: a model-level network.
-hipError_t launch_nature_slot_draw(const NatureObs &a, int first, int last, const int *atp, const double *lnp, const VLevels &lv,
-                                   hipStream_t s);
+hipError_t launch_nature_slot_draw(const NatureObs &a, hipStream_t s);
 // draws += 1 by one thread: every launch before it on the stream has read the counter, every launch after it sees the new one
 hipError_t launch_nature_count(unsigned long long *state, hipStream_t s);
-// The scores of an ensemble on the grid (x: LetkfObs::x) against the truth, two launches.  One workgroup per (row, latitude) forms
+// The scores of an ensemble on the grid (x: LetkfObserve::x) against the truth, two launches.  One workgroup per (row, latitude) forms
 // the zonal sums of mbar, mbar^2 and sum_e (d_e - mbar)^2 / (E - 1), d_e = x_e - truth, mbar = (sum_e d_e, e ascending) / E, in a
 // fixed tree into part [nrows][il][3]; one thread per row then adds them over the latitudes in ascending order with gw [il] and
 // writes rmse | bias | spread of its row into scores [3][nrows].  No atomics.

@@ -2,14 +2,15 @@
 // local ensemble transforms of every grid column and level -- or of a coarse list of columns, with the kernel that interpolates them
 // to every column (weight interpolation) -- the kernel that adds the spectral increments to the prognostics, and the two kernels of
 // observations in time slots: one keeps what is per member at a slot's time, one finishes it at analysis time.
-// The transforms around them are the plan's own (csrc/spdy_api_letkf.hip).
+// What the observation kernels compute is csrc/spdy_obsop.hpp's; here are their thread layouts.  The transforms
+// around them are the plan's own (csrc/spdy_api_letkf.hip).
 //
 // Everything here is bit-reproducible: no atomics, every sum in a fixed order (observations ascending, members ascending), every
 // loop with a fixed bound.  The Jacobi sweeps end at the convergence test or after LETKF_SWEEPS; a NaN fails every test, so a
 // non-finite input runs the full count and leaves NaN, it does not hang.  No contraction, as in the other column kernels.
 #include <type_traits>
 
-#include "spdy_kernels.hpp"
+#include "spdy_obsop.hpp"
 
 namespace spdy {
 namespace {
@@ -69,26 +70,29 @@ __device__ inline size_t letkf_at(int v, int e, int k, int kx, int ncol, int col
     return v < 4 ? ((size_t)e * kx + k) * ncol + col : (size_t)e * ncol + col;
 }
 
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObs a)
+// The observation-space quantities of a model-level network: one thread per observation, the members in a loop.  Every member's
+// hx is its own H x_e, formed and stored while the coupling step sums it (the accessor below); y is then written from the stored
+// row.  MASK (the member mask, a.umap): the sums take the members in use, y of a member not in use is 0.0.  One body, two
+// instantiations, no run-time branch.
+struct LetkfLevelRow {
+    const double *row0;      // member 0's level of the observed field
+    size_t step;             // doubles from a member to the next
+    const ObsStencil &s;
+    double *hxo;             // the observation's row of hx
+    __device__ __forceinline__ double hx(int e) const { return hxo[e] = obsop_level(row0 + e * step, s); }
+};
+
+template <bool MASK>
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_kernel(const LetkfObserve a)
 {
 #pragma clang fp contract(off)
-    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x;
-    if (o >= a.nobs) return;
-    const int v = a.var[o], k = a.lev[o];
-    const double *const x = a.x[v];
-    const int i0 = a.sidx[4 * o], i1 = a.sidx[4 * o + 1], i2 = a.sidx[4 * o + 2], i3 = a.sidx[4 * o + 3];
-    const double w0 = a.swgt[4 * o], w1 = a.swgt[4 * o + 1], w2 = a.swgt[4 * o + 2], w3 = a.swgt[4 * o + 3];
-    double sum = 0.0;
-    for (int e = 0; e < a.nmem; ++e) {
-        const double *const f = x + letkf_at(v, e, k, a.kx, a.ncol, 0);
-        const double h = ((w0 * f[i0] + w1 * f[i1]) + w2 * f[i2]) + w3 * f[i3];
-        a.hx[(size_t)o * a.nmem + e] = h;
-        sum += h;
-    }
-    const double mean = sum / a.nmem;
-    a.hxmean[o] = mean;
-    for (int e = 0; e < a.nmem; ++e) a.y[(size_t)o * a.nmem + e] = a.hx[(size_t)o * a.nmem + e] - mean;
-    a.dep[o] = a.value[o] - mean;
+    const int o = a.first + blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (o >= a.last) return;
+    const int v = a.var[o], k = a.lev[o], E = a.nmem, kl = v < 4 ? a.kx : 1;      // levels of the field: ps has one, and lev 0
+    const ObsStencil st = obsop_stencil(a.sidx, a.swgt, o);
+    double *const hx = a.hx + (size_t)o * E;
+    const double mean = obsop_couple<MASK, false>(a, o, LetkfLevelRow{obsop_field(a.x, v) + (size_t)k * a.ncol, (size_t)kl * a.ncol, st, hx});
+    for (int e = 0; e < E; ++e) a.y[(size_t)o * E + e] = obsop_anomaly<MASK>(a, e, hx[e], mean);
 }
 
 // The member mask's table from the caller's use[nmem] (include/spdy.h, "member mask"): one wave, lane e owns member e; the compact
@@ -104,224 +108,77 @@ __global__ __launch_bounds__(64) void letkf_mask_kernel(const int *const use, co
     if (e == 0) { umap[0] = n; *nused = (double)n; }
 }
 
-// letkf_obs_kernel over the members in use: every member's hx is its own H x_e; the sum, by a select, takes the members in use in
-// ascending order, so hxmean, y and dep have the bits an object of those n members gives; y of a member not in use is 0.0.
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_obs_masked_kernel(const LetkfObs a, const int *const umap)
-{
-#pragma clang fp contract(off)
-    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x;
-    if (o >= a.nobs) return;
-    const int v = a.var[o], k = a.lev[o], n = umap[0];
-    const int *const rank = umap + LETKF_URANK;
-    const double *const x = a.x[v];
-    const int i0 = a.sidx[4 * o], i1 = a.sidx[4 * o + 1], i2 = a.sidx[4 * o + 2], i3 = a.sidx[4 * o + 3];
-    const double w0 = a.swgt[4 * o], w1 = a.swgt[4 * o + 1], w2 = a.swgt[4 * o + 2], w3 = a.swgt[4 * o + 3];
-    double sum = 0.0;
-    for (int e = 0; e < a.nmem; ++e) {
-        const double *const f = x + letkf_at(v, e, k, a.kx, a.ncol, 0);
-        const double h = ((w0 * f[i0] + w1 * f[i1]) + w2 * f[i2]) + w3 * f[i3];
-        a.hx[(size_t)o * a.nmem + e] = h;
-        sum = rank[e] >= 0 ? sum + h : sum;
-    }
-    const double mean = sum / n;
-    a.hxmean[o] = mean;
-    for (int e = 0; e < a.nmem; ++e) a.y[(size_t)o * a.nmem + e] = rank[e] >= 0 ? a.hx[(size_t)o * a.nmem + e] - mean : 0.0;
-    a.dep[o] = a.value[o] - mean;
-}
-
 // The observation-space quantities of a network that holds observations given at a pressure (include/spdy.h, "observations at a
-// pressure").  A workgroup owns LETKF_BLOCK / E whole observations.  Thread (observation, member) finds the brackets
-// of the target in its member's four stencil columns from their four ps (one loop of kx trips, csrc/spdy_vinterp.hpp), loads the
-// two levels each bracket names by address, all eight loads before the first use, and leaves hx_e, the stencil's ps_e and its
-// out-of-column flag in LDS; thread (observation) then sums over the members in ascending order.  An observation on a model level
-// or of ps takes the same path with its bracket replaced by {lev, the level's own bits}, so the lanes of a wave do not diverge and
-// its hx has letkf_obs_kernel's bits.  No atomics, no array indexed by a bracket, every bound a kernel argument.
-// MASK (the member mask, a.umap): the thread layout is that of nmem and every member's hx is its own; the sums, psum and the
-// out-of-column OR take the members in use by a select, ascending, and divide by their number; y of a member not in use is 0.0.
-// Two instantiations, no run-time branch: MASK = false is the kernel it was.
+// pressure").  A workgroup owns LETKF_BLOCK / E whole observations.  Thread (observation, member) forms its member's
+// value (obsop_pressure: an observation on a model level or of ps takes the same path, so the lanes of a wave do not diverge) and
+// leaves hx_e, the stencil's ps_e and its out-of-column flag in LDS; thread (observation) then couples the members.  No atomics,
+// every bound a kernel argument.  MASK (the member mask, a.umap): the thread layout is that of nmem and every member's hx is its
+// own.  Two instantiations, no run-time branch.
 template <bool MASK>
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_pobs_kernel(const LetkfPObs a)
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_pobs_kernel(const LetkfObserve a)
 {
 #pragma clang fp contract(off)
     __shared__ double shx[LETKF_BLOCK], spb[LETKF_BLOCK], smean[LETKF_BLOCK / 2];
     __shared__ int sout[LETKF_BLOCK];
-    const int E = a.o.nmem, kx = a.o.kx, ncol = a.o.ncol, tid = threadIdx.x, opb = LETKF_BLOCK / E;
-    const int slot = tid / E, e = tid - slot * E, o = blockIdx.x * opb + slot;
-    const bool act = slot < opb && o < a.o.nobs;
+    const int E = a.nmem, tid = threadIdx.x, opb = LETKF_BLOCK / E;
+    const int slot = tid / E, e = tid - slot * E, o = a.first + blockIdx.x * opb + slot;
+    const bool act = slot < opb && o < a.last;
     double h = 0.0;
     if (act) {
-        const int v = a.o.var[o], lev = a.o.lev[o];
-        const bool atp = a.atp[o] != 0;
-        // the variable's field by selects: a pointer array indexed per lane would go to scratch
-        const double *const xv = v == 0 ? a.o.x[0] : v == 1 ? a.o.x[1] : v == 2 ? a.o.x[2] : v == 3 ? a.o.x[3] : a.o.x[4];
-        const int kl = v < 4 ? kx : 1;                             // levels of the field: ps has one
-        const double *const f = xv + (size_t)e * kl * ncol;
-        const double *const pse = a.o.x[4] + (size_t)e * ncol;
-        int idx[4];
-        double w[4], ps[4], f0[4], f1[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            idx[s] = a.o.sidx[4 * (size_t)o + s];
-            w[s] = a.o.swgt[4 * (size_t)o + s];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) ps[s] = pse[idx[s]];
-        const double xo = a.lnp[o], l0 = a.lv.lev[0];
-        VBracket b[4];
-        vinterp_brackets<true, 4>(a.lv, ps, xo, b);
-        int out = 0;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
-            f0[s] = f[(size_t)k0 * ncol + idx[s]];
-            f1[s] = f[(size_t)k1 * ncol + idx[s]];
-            out |= (atp && (xo < vinterp_coord<true>(ps[s], l0) || (b[s].cls & VINTERP_BELOW))) ? 1 : 0;
-            b[s].cls = atp ? b[s].cls : VINTERP_LO;                // a model level: f0's bits
-        }
-        double z[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
-        h = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
-        a.o.hx[(size_t)o * E + e] = h;
+        const int v = a.var[o], kl = v < 4 ? a.kx : 1;             // levels of the field: ps has one
+        const ObsAtPressure m = obsop_pressure(obsop_field(a.x, v) + (size_t)e * kl * a.ncol, a.x[4] + (size_t)e * a.ncol, kl, a.ncol,
+                                               a.atp[o] != 0, a.lev[o], a.lnp[o], a.lv, obsop_stencil(a.sidx, a.swgt, o));
+        h = m.h;
+        a.hx[(size_t)o * E + e] = h;
         shx[tid] = h;
-        spb[tid] = ((w[0] * ps[0] + w[1] * ps[1]) + w[2] * ps[2]) + w[3] * ps[3];
-        sout[tid] = out;
+        spb[tid] = m.ps;
+        sout[tid] = m.out;
     }
     __syncthreads();
-    const int o1 = blockIdx.x * opb + tid;
-    if (tid < opb && o1 < a.o.nobs) {
-        double sum = 0.0, psum = 0.0;
-        int out = 0;
-        for (int m = 0; m < E; ++m) {
-            if constexpr (MASK) {
-                const bool u = a.umap[LETKF_URANK + m] >= 0;
-                sum = u ? sum + shx[tid * E + m] : sum;
-                psum = u ? psum + spb[tid * E + m] : psum;
-                out |= u ? sout[tid * E + m] : 0;
-            } else {
-                sum += shx[tid * E + m];
-                psum += spb[tid * E + m];
-                out |= sout[tid * E + m];
-            }
-        }
-        const int n = MASK ? a.umap[0] : E;
-        const double mean = sum / n;
-        smean[tid] = mean;
-        a.o.hxmean[o1] = mean;
-        a.o.dep[o1] = a.o.value[o1] - mean;
-        if (a.atp[o1] != 0) a.olns[o1] = a.lnp[o1] - psum / n;
-        a.used[o1] = out ? 0.0 : 1.0;
-        a.reff[o1] = out ? 0.0 : a.rinv[o1];
-    }
+    const int o1 = a.first + blockIdx.x * opb + tid;
+    if (tid < opb && o1 < a.last) smean[tid] = obsop_couple<MASK, true>(a, o1, ObsRow<int>{shx + tid * E, spb + tid * E, sout + tid * E});
     __syncthreads();
-    if constexpr (MASK) {
-        if (act) a.o.y[(size_t)o * E + e] = a.umap[LETKF_URANK + e] >= 0 ? h - smean[slot] : 0.0;
-    } else {
-        if (act) a.o.y[(size_t)o * E + e] = h - smean[slot];
-    }
+    if (act) a.y[(size_t)o * E + e] = obsop_anomaly<MASK>(a, e, h, smean[slot]);
 }
 
-// Observing a time slot (include/spdy.h, "observations in time slots"): what letkf_obs_kernel and the first half of
-// letkf_pobs_kernel form per member, and nothing that couples members.  Thread (observation of the slot, member) in
-// letkf_pobs_kernel's layout, a workgroup owns LETKF_BLOCK / E whole observations of [first, last); no LDS, no barrier.
-// PRESSURE = false (a model-level network): the four stencil loads and the bilinear sum, letkf_obs_kernel's bits.  PRESSURE = true:
-// letkf_pobs_kernel's first half, expression for expression -- the brackets from the member's four ps, the eight loads before the
-// first use, a model-level observation through the same path with its bracket replaced -- and the stencil's ps_e and the member's
-// out-of-column flag go to slot_ps and slot_out, as doubles, in the place of LDS.  No atomics, every bound a kernel argument.
+// Observing a time slot (include/spdy.h, "observations in time slots"): what is per member, and nothing that
+// couples members.  Thread (observation of the slot, member) in letkf_pobs_kernel's layout, a workgroup owns LETKF_BLOCK / E whole
+// observations of [first, last); no LDS, no barrier.  PRESSURE = false (a model-level network): obsop_level, it does not pay for
+// brackets.  PRESSURE = true: obsop_pressure, and the stencil's ps_e and the member's out-of-column flag go to slot_ps and
+// slot_out, as doubles, in the place of LDS.  No atomics, every bound a kernel argument.
 template <bool PRESSURE>
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_slot_obs_kernel(const LetkfSlotObs a)
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_slot_obs_kernel(const LetkfObserve a)
 {
 #pragma clang fp contract(off)
-    const int E = a.nmem, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, opb = LETKF_BLOCK / E;
+    const int E = a.nmem, tid = threadIdx.x, opb = LETKF_BLOCK / E;
     const int slot = tid / E, e = tid - slot * E, o = a.first + blockIdx.x * opb + slot;
     if (slot >= opb || o >= a.last) return;
-    const int v = a.var[o], lev = a.lev[o];
-    // the variable's field by selects: a pointer array indexed per lane would go to scratch
-    const double *const xv = v == 0 ? a.x[0] : v == 1 ? a.x[1] : v == 2 ? a.x[2] : v == 3 ? a.x[3] : a.x[4];
-    const int kl = v < 4 ? kx : 1;                                 // levels of the field: ps has one
-    const double *const f = xv + (size_t)e * kl * ncol;
-    int idx[4];
-    double w[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        idx[s] = a.sidx[4 * (size_t)o + s];
-        w[s] = a.swgt[4 * (size_t)o + s];
-    }
+    const int v = a.var[o], lev = a.lev[o], kl = v < 4 ? a.kx : 1;  // levels of the field: ps has one
+    const double *const f = obsop_field(a.x, v) + (size_t)e * kl * a.ncol;
+    const ObsStencil st = obsop_stencil(a.sidx, a.swgt, o);
     if constexpr (!PRESSURE) {
-        const double *const fk = f + (size_t)min(lev, kl - 1) * ncol;
-        const double z0 = fk[idx[0]], z1 = fk[idx[1]], z2 = fk[idx[2]], z3 = fk[idx[3]];
-        a.hx[(size_t)o * E + e] = ((w[0] * z0 + w[1] * z1) + w[2] * z2) + w[3] * z3;
+        a.hx[(size_t)o * E + e] = obsop_level(f + (size_t)min(lev, kl - 1) * a.ncol, st);
     } else {
-        const bool atp = a.atp[o] != 0;
-        const double *const pse = a.x[4] + (size_t)e * ncol;
-        double ps[4], f0[4], f1[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) ps[s] = pse[idx[s]];
-        const double xo = a.lnp[o], l0 = a.lv.lev[0];
-        VBracket b[4];
-        vinterp_brackets<true, 4>(a.lv, ps, xo, b);
-        int out = 0;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
-            f0[s] = f[(size_t)k0 * ncol + idx[s]];
-            f1[s] = f[(size_t)k1 * ncol + idx[s]];
-            out |= (atp && (xo < vinterp_coord<true>(ps[s], l0) || (b[s].cls & VINTERP_BELOW))) ? 1 : 0;
-            b[s].cls = atp ? b[s].cls : VINTERP_LO;                // a model level: f0's bits
-        }
-        double z[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
-        a.hx[(size_t)o * E + e] = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
-        a.slot_ps[(size_t)o * E + e] = ((w[0] * ps[0] + w[1] * ps[1]) + w[2] * ps[2]) + w[3] * ps[3];
-        a.slot_out[(size_t)o * E + e] = out ? 1.0 : 0.0;
+        const ObsAtPressure m = obsop_pressure(f, a.x[4] + (size_t)e * a.ncol, kl, a.ncol, a.atp[o] != 0, lev, a.lnp[o], a.lv, st);
+        a.hx[(size_t)o * E + e] = m.h;
+        a.slot_ps[(size_t)o * E + e] = m.ps;
+        a.slot_out[(size_t)o * E + e] = m.out ? 1.0 : 0.0;
     }
 }
 
-// The finish of a slot analysis, in the observation kernel's place: one thread per observation reads its row of hx (and, PRESSURE,
-// of slot_ps and slot_out) from memory and forms what couples members -- the tail of letkf_obs_kernel / letkf_obs_masked_kernel and
-// the second half of letkf_pobs_kernel<MASK>, expression for expression: the sums over the members in use in ascending order, by a
-// select under MASK, so a member not in use may hold anything.  y is written row by row.  Four instantiations, no run-time branch.
+// The finish of a slot analysis, in the observation kernel's place: one thread per observation couples the members from its row
+// of hx (and, PRESSURE, of slot_ps and slot_out) in memory, so a member not in use may hold anything.  y is written row by row.
+// Four instantiations, no run-time branch.
 template <bool MASK, bool PRESSURE>
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_slot_finish_kernel(const LetkfSlotFinish a)
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_slot_finish_kernel(const LetkfObserve a)
 {
 #pragma clang fp contract(off)
-    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x;
-    if (o >= a.nobs) return;
-    const int E = a.nmem, n = MASK ? a.umap[0] : E;
-    const int *const rank = MASK ? a.umap + LETKF_URANK : nullptr;
+    const int o = a.first + blockIdx.x * LETKF_BLOCK + threadIdx.x;
+    if (o >= a.last) return;
+    const int E = a.nmem;
     const double *const hx = a.hx + (size_t)o * E;
-    double sum = 0.0;
-    for (int e = 0; e < E; ++e) {
-        const double h = hx[e];
-        if constexpr (MASK) sum = rank[e] >= 0 ? sum + h : sum;
-        else sum += h;
-    }
-    const double mean = sum / n;
-    a.hxmean[o] = mean;
-    for (int e = 0; e < E; ++e) {
-        if constexpr (MASK) a.y[(size_t)o * E + e] = rank[e] >= 0 ? hx[e] - mean : 0.0;
-        else a.y[(size_t)o * E + e] = hx[e] - mean;
-    }
-    a.dep[o] = a.value[o] - mean;
-    if constexpr (PRESSURE) {
-        const double *const pb = a.slot_ps + (size_t)o * E, *const so = a.slot_out + (size_t)o * E;
-        double psum = 0.0;
-        int out = 0;
-        for (int e = 0; e < E; ++e) {
-            if constexpr (MASK) {
-                const bool u = rank[e] >= 0;
-                psum = u ? psum + pb[e] : psum;
-                out |= u ? (so[e] != 0.0 ? 1 : 0) : 0;
-            } else {
-                psum += pb[e];
-                out |= so[e] != 0.0 ? 1 : 0;
-            }
-        }
-        if (a.atp[o] != 0) a.olns[o] = a.lnp[o] - psum / n;
-        a.used[o] = out ? 0.0 : 1.0;
-        a.reff[o] = out ? 0.0 : a.rinv[o];
-    }
+    const double mean = obsop_couple<MASK, PRESSURE>(a, o, ObsRow<double>{hx, a.slot_ps + (size_t)o * E, a.slot_out + (size_t)o * E});
+    for (int e = 0; e < E; ++e) a.y[(size_t)o * E + e] = obsop_anomaly<MASK>(a, e, hx[e], mean);
 }
 
 // LIST = false: one workgroup per grid column, which gets its increments.  LIST = true (weight interpolation): workgroup b solves
@@ -588,81 +445,19 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const ARGS
 // lanes of an item read a row of T of each stencil entry, contiguous along e; the members' values go through LDS (five doubles per
 // thread, 10 KB per workgroup whatever E), loaded and stored with the column fastest over the lanes.  A streaming kernel: no
 // atomics, every bound a kernel argument, the sums in the order of letkf_transform_kernel's step 4.
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_kernel(const LetkfApply a, const int lpi)
+// MASK (the member mask, umap): the launch shape, the LDS slots and the strides of T are those of nmem.  Lane e still owns member
+// e: a member in use has the compact index c = rank[e] and forms dx from the leading n x n block of each T and the values of the
+// members umap[1 + f], f < n ascending, with the means over them; a member not in use reads nothing and gets 0.0, and so does
+// every member when n < 2 (the weight buffer is then not read at all).  One body, two instantiations, no run-time branch.
+template <bool MASK>
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_kernel(const LetkfApply a, const int lpi, const int *const umap)
 {
 #pragma clang fp contract(off)
     __shared__ double X[LETKF_VARS * LETKF_BLOCK];      // [slot][v][lpi]
-    const int E = a.nmem, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, ipb = LETKF_BLOCK / lpi;
+    const int NM = a.nmem, E = MASK ? umap[0] : NM, kx = a.kx, ncol = a.ncol, tid = threadIdx.x, ipb = LETKF_BLOCK / lpi;
+    const int *const um = MASK ? umap + 1 : nullptr;
     const long nitem = (long)kx * ncol, first = (long)blockIdx.x * ipb;
     {   // the members' values: thread -> (member, slot), the slots' columns contiguous
-        const int slot = tid % ipb, f = tid / ipb;
-        const long item = first + slot;
-        if (item < nitem && f < E) {
-            const int k = (int)(item / ncol), col = (int)(item % ncol), nvar = k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1;
-            for (int v = 0; v < nvar; ++v) X[(slot * LETKF_VARS + v) * lpi + f] = a.x[v][letkf_at(v, f, k, kx, ncol, col)];
-        }
-    }
-    __syncthreads();
-    const int slot = tid / lpi, e = tid % lpi;
-    const long item = first + slot;
-    double d[LETKF_VARS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    if (item < nitem && e < E) {
-        const int k = (int)(item / ncol), col = (int)(item % ncol);
-        const bool sfc = k == kx - 1;
-        const double *const xs = X + slot * LETKF_VARS * lpi;
-        double mean[LETKF_VARS];
-        for (int v = 0; v < LETKF_VARS; ++v) {
-            double sum = 0.0;
-            for (int f = 0; f < E; ++f) sum += xs[v * lpi + f];
-            mean[v] = sum / E;
-        }
-        const double w0 = a.iwgt[4 * (size_t)col], w1 = a.iwgt[4 * (size_t)col + 1], w2 = a.iwgt[4 * (size_t)col + 2],
-                     w3 = a.iwgt[4 * (size_t)col + 3];
-        const size_t ee = (size_t)E * E, lev = (size_t)k * ee + e;
-        const double *const t0 = a.tw + (size_t)a.iidx[4 * (size_t)col] * kx * ee + lev,
-                     *const t1 = a.tw + (size_t)a.iidx[4 * (size_t)col + 1] * kx * ee + lev,
-                     *const t2 = a.tw + (size_t)a.iidx[4 * (size_t)col + 2] * kx * ee + lev,
-                     *const t3 = a.tw + (size_t)a.iidx[4 * (size_t)col + 3] * kx * ee + lev;
-#pragma unroll 4
-        for (int f = 0; f < E; ++f) {
-            const size_t r = (size_t)f * E;
-            double t = w0 * t0[r];            // (1 - a)(1 - b) with a, b < 1: the first term is always present
-            if (w1 != 0.0) t += w1 * t1[r];
-            if (w2 != 0.0) t += w2 * t2[r];
-            if (w3 != 0.0) t += w3 * t3[r];
-            for (int v = 0; v < LETKF_VARS - 1; ++v) d[v] += (xs[v * lpi + f] - mean[v]) * t;
-            if (sfc) d[4] += (xs[4 * lpi + f] - mean[4]) * t;
-        }
-    }
-    __syncthreads();
-    X[(slot * LETKF_VARS + 0) * lpi + e] = d[0];
-    X[(slot * LETKF_VARS + 1) * lpi + e] = d[1];
-    X[(slot * LETKF_VARS + 2) * lpi + e] = d[2];
-    X[(slot * LETKF_VARS + 3) * lpi + e] = d[3];
-    X[(slot * LETKF_VARS + 4) * lpi + e] = d[4];
-    __syncthreads();
-    {
-        const int slot2 = tid % ipb, f = tid / ipb;
-        const long item2 = first + slot2;
-        if (item2 < nitem && f < E) {
-            const int k = (int)(item2 / ncol), col = (int)(item2 % ncol), nvar = k == kx - 1 ? LETKF_VARS : LETKF_VARS - 1;
-            for (int v = 0; v < nvar; ++v) a.dx[v][letkf_at(v, f, k, kx, ncol, col)] = X[(slot2 * LETKF_VARS + v) * lpi + f];
-        }
-    }
-}
-
-// letkf_apply_kernel under the member mask (umap): a sibling, the kernel above is as it was.  The launch shape and the LDS slots
-// are those of nmem.  Lane e still owns member e: a member in use has the compact index c = rank[e] and forms dx from the leading
-// n x n block of each T (strides of nmem) and the values of the members umap[1 + f], f < n ascending, with the means over them; a
-// member not in use reads nothing and gets 0.0, and so does every member when n < 2 (the weight buffer is then not read at all).
-__global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_masked_kernel(const LetkfApply a, const int lpi, const int *const umap)
-{
-#pragma clang fp contract(off)
-    __shared__ double X[LETKF_VARS * LETKF_BLOCK];      // [slot][v][lpi]
-    const int NM = a.nmem, E = umap[0], kx = a.kx, ncol = a.ncol, tid = threadIdx.x, ipb = LETKF_BLOCK / lpi;
-    const int *const um = umap + 1;
-    const long nitem = (long)kx * ncol, first = (long)blockIdx.x * ipb;
-    {
         const int slot = tid % ipb, f = tid / ipb;
         const long item = first + slot;
         if (item < nitem && f < NM) {
@@ -673,16 +468,16 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_masked_kernel(const L
     __syncthreads();
     const int slot = tid / lpi, e = tid % lpi;
     const long item = first + slot;
-    const int c = e < NM ? umap[LETKF_URANK + e] : -1;
+    const int c = e < NM ? (MASK ? umap[LETKF_URANK + e] : e) : -1;
     double d[LETKF_VARS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    if (item < nitem && c >= 0 && E >= 2) {
+    if (item < nitem && c >= 0 && (!MASK || E >= 2)) {
         const int k = (int)(item / ncol), col = (int)(item % ncol);
         const bool sfc = k == kx - 1;
         const double *const xs = X + slot * LETKF_VARS * lpi;
         double mean[LETKF_VARS];
         for (int v = 0; v < LETKF_VARS; ++v) {
             double sum = 0.0;
-            for (int f = 0; f < E; ++f) sum += xs[v * lpi + um[f]];
+            for (int f = 0; f < E; ++f) sum += xs[v * lpi + (MASK ? um[f] : f)];
             mean[v] = sum / E;
         }
         const double w0 = a.iwgt[4 * (size_t)col], w1 = a.iwgt[4 * (size_t)col + 1], w2 = a.iwgt[4 * (size_t)col + 2],
@@ -695,8 +490,8 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_apply_masked_kernel(const L
 #pragma unroll 4
         for (int f = 0; f < E; ++f) {
             const size_t r = (size_t)f * NM;
-            const int mf = um[f];
-            double t = w0 * t0[r];
+            const int mf = MASK ? um[f] : f;
+            double t = w0 * t0[r];            // (1 - a)(1 - b) with a, b < 1: the first term is always present
             if (w1 != 0.0) t += w1 * t1[r];
             if (w2 != 0.0) t += w2 * t2[r];
             if (w3 != 0.0) t += w3 * t3[r];
@@ -832,57 +627,53 @@ hipError_t launch_letkf_mask(const int *use, int nmem, int *umap, double *nused,
     return hipGetLastError();
 }
 
-hipError_t launch_letkf_obs_masked(const LetkfObs &a, const int *umap, hipStream_t s)
+namespace {
+// The checks of the three launches of the observation stage.  observes: the launch forms hx from the ensemble; couples: it forms
+// what couples members; a launch that does one of the two keeps, or reads, the slots' rows.  *empty: nothing to launch.
+hipError_t observe_ready(const LetkfObserve &a, bool observes, bool couples, bool *empty)
 {
-    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.ncol < 1 || !a.hx || !a.hxmean || !a.y || !a.dep || !umap)
-        return hipErrorInvalidValue;
-    for (int v = 0; v < LETKF_VARS; ++v)
-        if (!a.x[v]) return hipErrorInvalidValue;
-    if (!a.nobs) return hipSuccess;
-    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.value) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(letkf_obs_masked_kernel, dim3((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), dim3(LETKF_BLOCK), 0, s, a, umap);
+    if (a.first < 0 || a.last < a.first || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || !a.hx) return hipErrorInvalidValue;
+    if (observes) {
+        if (a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1) return hipErrorInvalidValue;
+        for (int v = 0; v < LETKF_VARS; ++v)
+            if (!a.x[v]) return hipErrorInvalidValue;
+        if (a.atp && (a.kx < 2 || a.kx > VINTERP_KMAX || a.lv.kx != a.kx)) return hipErrorInvalidValue;
+    }
+    if (couples && (!a.hxmean || !a.y || !a.dep)) return hipErrorInvalidValue;
+    if (a.atp) {
+        if (!a.lnp || (couples && (!a.rinv || !a.olns || !a.used || !a.reff))) return hipErrorInvalidValue;
+        if (observes != couples && (!a.slot_ps || !a.slot_out)) return hipErrorInvalidValue;
+    }
+    *empty = a.last == a.first;
+    if (*empty) return hipSuccess;
+    if (observes && (!a.var || !a.lev || !a.sidx || !a.swgt)) return hipErrorInvalidValue;
+    if (couples && !a.value) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+}  // namespace
+
+hipError_t launch_letkf_observe(const LetkfObserve &a, hipStream_t s)
+{
+    bool empty = false;
+    if (const hipError_t rc = observe_ready(a, true, true, &empty)) return rc;
+    if (empty) return hipSuccess;
+    const int n = a.last - a.first, opb = LETKF_BLOCK / a.nmem;
+    const dim3 each((n + LETKF_BLOCK - 1) / LETKF_BLOCK), whole((n + opb - 1) / opb), block(LETKF_BLOCK);
+    if (a.atp) {
+        if (a.umap) hipLaunchKernelGGL(letkf_pobs_kernel<true>, whole, block, 0, s, a);
+        else hipLaunchKernelGGL(letkf_pobs_kernel<false>, whole, block, 0, s, a);
+    } else {
+        if (a.umap) hipLaunchKernelGGL(letkf_obs_kernel<true>, each, block, 0, s, a);
+        else hipLaunchKernelGGL(letkf_obs_kernel<false>, each, block, 0, s, a);
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_letkf_obs(const LetkfObs &a, hipStream_t s)
+hipError_t launch_letkf_slot_obs(const LetkfObserve &a, hipStream_t s)
 {
-    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.ncol < 1 || !a.hx || !a.hxmean || !a.y || !a.dep)
-        return hipErrorInvalidValue;
-    for (int v = 0; v < LETKF_VARS; ++v)
-        if (!a.x[v]) return hipErrorInvalidValue;
-    if (!a.nobs) return hipSuccess;
-    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.value) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(letkf_obs_kernel, dim3((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), dim3(LETKF_BLOCK), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_letkf_pobs(const LetkfPObs &a, hipStream_t s)
-{
-    const LetkfObs &o = a.o;
-    if (o.nobs < 0 || o.nmem < 2 || o.nmem > LETKF_MAX_MEMBERS || o.kx < 2 || o.kx > VINTERP_KMAX || a.lv.kx != o.kx || o.ncol < 1 ||
-        !o.hx || !o.hxmean || !o.y || !o.dep)
-        return hipErrorInvalidValue;
-    for (int v = 0; v < LETKF_VARS; ++v)
-        if (!o.x[v]) return hipErrorInvalidValue;
-    if (!o.nobs) return hipSuccess;
-    if (!o.var || !o.lev || !o.sidx || !o.swgt || !o.value || !a.atp || !a.lnp || !a.rinv || !a.olns || !a.used || !a.reff) return hipErrorInvalidValue;
-    const int opb = LETKF_BLOCK / o.nmem;
-    if (a.umap)
-        hipLaunchKernelGGL(letkf_pobs_kernel<true>, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
-    else
-        hipLaunchKernelGGL(letkf_pobs_kernel<false>, dim3((o.nobs + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_letkf_slot_obs(const LetkfSlotObs &a, hipStream_t s)
-{
-    if (a.first < 0 || a.last < a.first || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 || !a.hx)
-        return hipErrorInvalidValue;
-    for (int v = 0; v < LETKF_VARS; ++v)
-        if (!a.x[v]) return hipErrorInvalidValue;
-    if (a.atp && (a.kx < 2 || a.kx > VINTERP_KMAX || a.lv.kx != a.kx || !a.lnp || !a.slot_ps || !a.slot_out)) return hipErrorInvalidValue;
-    if (a.last == a.first) return hipSuccess;
-    if (!a.var || !a.lev || !a.sidx || !a.swgt) return hipErrorInvalidValue;
+    bool empty = false;
+    if (const hipError_t rc = observe_ready(a, true, false, &empty)) return rc;
+    if (empty) return hipSuccess;
     const int opb = LETKF_BLOCK / a.nmem, n = a.last - a.first;
     if (a.atp)
         hipLaunchKernelGGL(letkf_slot_obs_kernel<true>, dim3((n + opb - 1) / opb), dim3(LETKF_BLOCK), 0, s, a);
@@ -891,13 +682,12 @@ hipError_t launch_letkf_slot_obs(const LetkfSlotObs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_letkf_slot_finish(const LetkfSlotFinish &a, hipStream_t s)
+hipError_t launch_letkf_slot_finish(const LetkfObserve &a, hipStream_t s)
 {
-    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || !a.hx || !a.hxmean || !a.y || !a.dep) return hipErrorInvalidValue;
-    if (!a.nobs) return hipSuccess;
-    if (!a.value) return hipErrorInvalidValue;
-    if (a.atp && (!a.lnp || !a.rinv || !a.slot_ps || !a.slot_out || !a.olns || !a.used || !a.reff)) return hipErrorInvalidValue;
-    const dim3 grid((a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK), block(LETKF_BLOCK);
+    bool empty = false;
+    if (const hipError_t rc = observe_ready(a, false, true, &empty)) return rc;
+    if (empty) return hipSuccess;
+    const dim3 grid((a.last - a.first + LETKF_BLOCK - 1) / LETKF_BLOCK), block(LETKF_BLOCK);
     if (a.umap) {
         if (a.atp) hipLaunchKernelGGL((letkf_slot_finish_kernel<true, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((letkf_slot_finish_kernel<true, false>), grid, block, 0, s, a);
@@ -958,10 +748,11 @@ hipError_t launch_letkf_apply(const LetkfApply &a, hipStream_t s, const int *uma
     int lpi = 2;
     while (lpi < a.nmem) lpi *= 2;
     const long nitem = (long)a.kx * a.ncol, ipb = LETKF_BLOCK / lpi;
+    const dim3 grid((unsigned)((nitem + ipb - 1) / ipb)), block(LETKF_BLOCK);
     if (umap)
-        hipLaunchKernelGGL(letkf_apply_masked_kernel, dim3((unsigned)((nitem + ipb - 1) / ipb)), dim3(LETKF_BLOCK), 0, s, a, lpi, umap);
+        hipLaunchKernelGGL(letkf_apply_kernel<true>, grid, block, 0, s, a, lpi, umap);
     else
-        hipLaunchKernelGGL(letkf_apply_kernel, dim3((unsigned)((nitem + ipb - 1) / ipb)), dim3(LETKF_BLOCK), 0, s, a, lpi);
+        hipLaunchKernelGGL(letkf_apply_kernel<false>, grid, block, 0, s, a, lpi, umap);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 // Everything here is bit-reproducible: no atomics, every sum in a fixed order (members ascending, a fixed tree over a latitude's
 // points, latitudes ascending), every loop with a fixed bound.  A row's scores are formed from that row's grids by that row's
 // workgroups and thread only, so a non-finite value stays in its row.  No contraction, as in the other column kernels.
+#include "spdy_obsop.hpp"
 #include "spdy_philox.hpp"
 
 namespace spdy {
@@ -13,115 +14,31 @@ namespace {
 constexpr int NATURE_BLOCK = 256;        // observations per workgroup of the draw kernel, rows per workgroup of the final sums
 constexpr int NATURE_SCORE_BLOCK = 128;  // threads of a (row, latitude) workgroup: two waves, one pass over T30's 96 longitudes
 
-__global__ __launch_bounds__(NATURE_BLOCK) void nature_draw_kernel(const NatureObs a)
+// The draw of the observations [first, last) of the network (the whole network: [0, nobs); include/spdy.h, "observations in time
+// slots"): thread o - first forms h as the analysis forms a member's hx (csrc/spdy_obsop.hpp), the truth being the one member --
+// row v * kx + k of it on a model level (lev is 0 for ps); PRESSURE, a network that holds an observation at a pressure, by
+// obsop_pressure with the truth's ps, clamped to the end level outside the column -- and adds the noise with the counter of o
+// itself, so a slot's draw is the whole network's draw on its range.
+template <bool PRESSURE>
+__global__ __launch_bounds__(NATURE_BLOCK) void nature_slot_draw_kernel(const NatureObs a)
 {
 #pragma clang fp contract(off)
-    const int o = blockIdx.x * NATURE_BLOCK + threadIdx.x;
-    if (o >= a.nobs) return;
-    const int v = a.var[o], k = a.lev[o];
-    // row v * kx + k of the truth; lev is 0 for ps
-    const double *const f = a.truth + ((size_t)v * a.kx + k) * a.ncol;
-    const int i0 = a.sidx[4 * o], i1 = a.sidx[4 * o + 1], i2 = a.sidx[4 * o + 2], i3 = a.sidx[4 * o + 3];
-    const double w0 = a.swgt[4 * o], w1 = a.swgt[4 * o + 1], w2 = a.swgt[4 * o + 2], w3 = a.swgt[4 * o + 3];
-    const double h = ((w0 * f[i0] + w1 * f[i1]) + w2 * f[i2]) + w3 * f[i3];
+    const int o = a.first + blockIdx.x * NATURE_BLOCK + threadIdx.x;
+    if (o >= a.last) return;
+    const int v = a.var[o], lev = a.lev[o];
+    const ObsStencil st = obsop_stencil(a.sidx, a.swgt, o);
+    const double *const f = a.truth + (size_t)v * a.kx * a.ncol;
+    double h;
+    if constexpr (!PRESSURE)
+        h = obsop_level(f + (size_t)lev * a.ncol, st);
+    else
+        h = obsop_pressure(f, a.truth + (size_t)4 * a.kx * a.ncol, v < 4 ? a.kx : 1, a.ncol, a.atp[o] != 0, lev, a.lnp[o], a.lv, st).h;
     if (a.noise == 0.0) {
         a.value[o] = h;
         return;
     }
     const double z = sppt_randn((unsigned)o, 0u, a.state[1], a.state[0]);
     a.value[o] = h + (a.noise * a.error[o]) * z;
-}
-
-// nature_draw_kernel for a network with observations given at a pressure (atp != 0): the four columns' values at the target by
-// csrc/spdy_vinterp.hpp's rule with the truth's ps, clamped to the end level outside the column; an observation on a model level
-// or of ps goes the same way with its bracket replaced by {lev, the level's own bits}.  One thread per observation: one member.
-__global__ __launch_bounds__(NATURE_BLOCK) void nature_pdraw_kernel(const NatureObs a, const int *const atpo, const double *const lnp, const VLevels lv)
-{
-#pragma clang fp contract(off)
-    const int o = blockIdx.x * NATURE_BLOCK + threadIdx.x;
-    if (o >= a.nobs) return;
-    const int v = a.var[o], lev = a.lev[o], kl = v < 4 ? a.kx : 1;
-    const bool atp = atpo[o] != 0;
-    const double *const f = a.truth + (size_t)v * a.kx * a.ncol, *const pst = a.truth + (size_t)4 * a.kx * a.ncol;
-    int idx[4];
-    double w[4], ps[4], f0[4], f1[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        idx[s] = a.sidx[4 * (size_t)o + s];
-        w[s] = a.swgt[4 * (size_t)o + s];
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) ps[s] = pst[idx[s]];
-    VBracket b[4];
-    vinterp_brackets<true, 4>(lv, ps, lnp[o], b);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
-        f0[s] = f[(size_t)k0 * a.ncol + idx[s]];
-        f1[s] = f[(size_t)k1 * a.ncol + idx[s]];
-        b[s].cls = atp ? b[s].cls : VINTERP_LO;
-    }
-    double z[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
-    const double h = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
-    if (a.noise == 0.0) {
-        a.value[o] = h;
-        return;
-    }
-    const double zz = sppt_randn((unsigned)o, 0u, a.state[1], a.state[0]);
-    a.value[o] = h + (a.noise * a.error[o]) * zz;
-}
-
-// The two kernels above for the observations [first, last) of the network only (include/spdy.h, "observations in time slots"):
-// thread o - first forms value_o as they do, expression for expression, with the counter of o itself, so a slot's draw is the
-// whole network's draw on its range.  PRESSURE: the network holds an observation at a pressure (nature_pdraw_kernel's path).
-template <bool PRESSURE>
-__global__ __launch_bounds__(NATURE_BLOCK) void nature_slot_draw_kernel(const NatureObs a, const int first, const int last, const int *const atpo,
-                                                                        const double *const lnp, const VLevels lv)
-{
-#pragma clang fp contract(off)
-    const int o = first + blockIdx.x * NATURE_BLOCK + threadIdx.x;
-    if (o >= last) return;
-    const int v = a.var[o], lev = a.lev[o];
-    int idx[4];
-    double w[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        idx[s] = a.sidx[4 * (size_t)o + s];
-        w[s] = a.swgt[4 * (size_t)o + s];
-    }
-    double h;
-    if constexpr (!PRESSURE) {
-        const double *const f = a.truth + ((size_t)v * a.kx + lev) * a.ncol;       // row v * kx + k of the truth; lev is 0 for ps
-        h = ((w[0] * f[idx[0]] + w[1] * f[idx[1]]) + w[2] * f[idx[2]]) + w[3] * f[idx[3]];
-    } else {
-        const int kl = v < 4 ? a.kx : 1;
-        const bool atp = atpo[o] != 0;
-        const double *const f = a.truth + (size_t)v * a.kx * a.ncol, *const pst = a.truth + (size_t)4 * a.kx * a.ncol;
-        double ps[4], f0[4], f1[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) ps[s] = pst[idx[s]];
-        VBracket b[4];
-        vinterp_brackets<true, 4>(lv, ps, lnp[o], b);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int k0 = min(atp ? b[s].kb : lev, kl - 1), k1 = min(k0 + 1, kl - 1);
-            f0[s] = f[(size_t)k0 * a.ncol + idx[s]];
-            f1[s] = f[(size_t)k1 * a.ncol + idx[s]];
-            b[s].cls = atp ? b[s].cls : VINTERP_LO;
-        }
-        double z[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) z[s] = vinterp_value(b[s], f0[s], f1[s]);
-        h = ((w[0] * z[0] + w[1] * z[1]) + w[2] * z[2]) + w[3] * z[3];
-    }
-    if (a.noise == 0.0) {
-        a.value[o] = h;
-        return;
-    }
-    const double zz = sppt_randn((unsigned)o, 0u, a.state[1], a.state[0]);
-    a.value[o] = h + (a.noise * a.error[o]) * zz;
 }
 
 __global__ void nature_count_kernel(unsigned long long *state)
@@ -215,37 +132,18 @@ __global__ __launch_bounds__(NATURE_BLOCK) void nature_final_kernel(const Nature
 
 }  // namespace
 
-hipError_t launch_nature_draw(const NatureObs &a, hipStream_t s)
+hipError_t launch_nature_slot_draw(const NatureObs &a, hipStream_t s)
 {
-    if (a.nobs < 0 || a.kx < 1 || a.ncol < 1 || !a.truth || !a.state || !a.value || !(a.noise >= 0.0)) return hipErrorInvalidValue;
-    if (!a.nobs) return hipSuccess;
-    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nature_draw_kernel, dim3((a.nobs + NATURE_BLOCK - 1) / NATURE_BLOCK), dim3(NATURE_BLOCK), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_nature_pdraw(const NatureObs &a, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s)
-{
-    if (a.nobs < 0 || a.kx < 2 || a.kx > VINTERP_KMAX || lv.kx != a.kx || a.ncol < 1 || !a.truth || !a.state || !a.value || !(a.noise >= 0.0))
+    if (a.first < 0 || a.last < a.first || a.last > a.nobs || a.kx < 1 || a.ncol < 1 || !a.truth || !a.state || !a.value || !(a.noise >= 0.0))
         return hipErrorInvalidValue;
-    if (!a.nobs) return hipSuccess;
-    if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error || !atp || !lnp) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nature_pdraw_kernel, dim3((a.nobs + NATURE_BLOCK - 1) / NATURE_BLOCK), dim3(NATURE_BLOCK), 0, s, a, atp, lnp, lv);
-    return hipGetLastError();
-}
-
-hipError_t launch_nature_slot_draw(const NatureObs &a, int first, int last, const int *atp, const double *lnp, const VLevels &lv, hipStream_t s)
-{
-    if (first < 0 || last < first || last > a.nobs || a.kx < 1 || a.ncol < 1 || !a.truth || !a.state || !a.value || !(a.noise >= 0.0))
-        return hipErrorInvalidValue;
-    if (atp && (a.kx < 2 || a.kx > VINTERP_KMAX || lv.kx != a.kx || !lnp)) return hipErrorInvalidValue;
-    if (last == first) return hipSuccess;
+    if (a.atp && (a.kx < 2 || a.kx > VINTERP_KMAX || a.lv.kx != a.kx || !a.lnp)) return hipErrorInvalidValue;
+    if (a.last == a.first) return hipSuccess;
     if (!a.var || !a.lev || !a.sidx || !a.swgt || !a.error) return hipErrorInvalidValue;
-    const dim3 grid((last - first + NATURE_BLOCK - 1) / NATURE_BLOCK), block(NATURE_BLOCK);
-    if (atp)
-        hipLaunchKernelGGL(nature_slot_draw_kernel<true>, grid, block, 0, s, a, first, last, atp, lnp, lv);
+    const dim3 grid((a.last - a.first + NATURE_BLOCK - 1) / NATURE_BLOCK), block(NATURE_BLOCK);
+    if (a.atp)
+        hipLaunchKernelGGL(nature_slot_draw_kernel<true>, grid, block, 0, s, a);
     else
-        hipLaunchKernelGGL(nature_slot_draw_kernel<false>, grid, block, 0, s, a, first, last, atp, lnp, lv);
+        hipLaunchKernelGGL(nature_slot_draw_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 

@@ -267,14 +267,12 @@ class Letkf(PlanObject):
         sp, E = self.sp, self.nmem
         use = use_mask(use, E, self._device())
         x = (ug, vg, tg, qg, psg)
-        shp = [(E, sp.kx) + sp.grid_shape] * 4 + [(E,) + sp.grid_shape]
         if out is None:
             out = tuple(torch.empty_like(a) for a in x)
         if len(out) != 5:
             raise ValueError("analyse_grid: out must hold five tensors")
-        for a, s in list(zip(x, shp)) + list(zip(out, shp)):
-            if tuple(a.shape) != s or a.dtype != torch.float64 or not a.is_contiguous():
-                raise ValueError("analyse_grid: expected a contiguous float64 tensor of shape %s, got %s" % (s, tuple(a.shape)))
+        self._grids("analyse_grid", x)
+        self._grids("analyse_grid", out)
         if sp.device >= 0:
             sp._sync_stream()
         ptrs = [ctypes.c_void_p(a.data_ptr()) for a in x + tuple(out)]

@@ -236,7 +236,7 @@ def test_from_spectra(E, plans, oracle_factory):
 
 # ---------------------------------------------------------------------------------------------------- 6. the nature run
 def device_draws(sp, n, seed, draws):
-    """z_o of the device for draw number `draws`, bit for bit: nature_draw_kernel on a model-level network with error 1 and a truth
+    """z_o of the device for draw number `draws`, bit for bit: nature_slot_draw_kernel on a model-level network with error 1 and a truth
     of zeros stores 0 + (1 * 1) * z_o"""
     import speedy_f90_amd as s
     nat = s.Nature(sp, seed=seed, capacity=1)
@@ -255,7 +255,7 @@ def test_nature_values(plans):
     z with the device's own draws of the model-level kernel to the bit, and those draws are tests/nature.py's within the limit
     tests/test_gpu_nature.py holds them to; draws advances by one per call.  Measured on an MI355X: the device's draws differ from
     NumPy's by at most 2.2e-16 and are not bit-equal to them (the device's randn is its own logarithm and cosine), so bits are asked
-    against the draws nature_draw_kernel itself stores, and NumPy's are held to that limit"""
+    against the draws nature_slot_draw_kernel itself stores, and NumPy's are held to that limit"""
     import speedy_f90_amd as s
     sp, g = plans(8)
     seed = 0x51DE

@@ -649,6 +649,7 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
             name = "analysis E=%d mask K=%d" % (E, K)
             fns[name], nodes[name] = gm.launch, gm.num_nodes()
             mask_objects.append((use, gm))
+        ltp = None
         if at_pressure:
             ltp = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, **({} if stride == (1, 1) else {"weight_stride": stride}))
             ltp.set_obs(cols[0], np.where(cols[0] == 4, 0, s.OBS_AT_P), cols[2], cols[3], lt.field("value").numpy(), spread,
