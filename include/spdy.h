@@ -1295,6 +1295,84 @@ int spdy_slot_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, 
 struct spdy_nature;                   /* the nature run, "nature run" below */
 int spdy_slot_nature_observe_dev(struct spdy_nature *n, spdy_letkf *letkf, int slot, double noise);
 
+/* ---- ensemble analysis, background check and observation statistics ------------------------------------------------
+ * The calls above take every observation at face value; one gross error damages every column within 2 c_h of it.  With these the
+ * analysis tests every departure against spread plus error before the local analyses see it, and keeps, per group of observations,
+ * the counts and sums an innovation table is made of -- on the device, so a captured cycle needs no host.  tests/letkfqc.py restates
+ * this subsection in NumPy.  U: the members in use, all nmem without a mask, otherwise the mask's ("member mask"); n = |U|; every
+ * sum over members runs over U ascending, by a select; every operation is one IEEE operation, nothing is contracted.
+ *   check         after the observation stage of an analysis call -- the plain kernel, the at-pressure kernel or the slots' finish
+ *                 kernel -- has written y_e and dep_o, for every observation o of the current network:
+ *                     s2_o   = (sum_U y_e^2) / (n - 1)               each square rounded, then the sum, then one division
+ *                     v_o    = s2_o + err_o * err_o                   err_o: the device's own copy of the error set_obs was given
+ *                     rej_o  = dep_o * dep_o > g2 * v_o               g2 = gross * gross, formed once on the host
+ *                     used_o = in_column_o && !rej_o                  in_column_o: what the observation stage wrote to obs_used
+ *                                                                     (1 for a model-level network)
+ *                     reff_o = used_o ? rinv_o : 0.0
+ *                 A NaN makes the comparison false: it rejects nothing and propagates, as the out-of-column test does.  With
+ *                 n < 2, or with gross == 0 (statistics only, below), the test is not made and nothing is rejected.  The local
+ *                 analyses read reff: a rejected observation has r exactly 0 and, by "an observation with w == 0 takes no part",
+ *                 enters no sum, so the increments are bit for bit those of the unchecked call on the network without the
+ *                 rejected observations.  Its hx, hxmean, y and departure remain written, for diagnostics.
+ *   groups        every observation has a group g_o in [0, ngroups), 1 <= ngroups <= SPDY_QC_MAX_GROUPS.  The default group is
+ *                 the observation's variable (ngroups = 5); a caller may give a host table of nobs ints instead, for example the
+ *                 instrument type or var * kx + lev.
+ *   statistics    the object holds stats[SPDY_QC_SLOTS][SPDY_QC_MAX_GROUPS][10] doubles.  A call fills, of the slot it was enqueued
+ *                 with (spdy_qc_set_slot), the ten numbers of every group g < ngroups, every time:
+ *                     0 n_all   1 n_out   2 n_rej   3 n_used          counts, as doubles (check_o == 2, == 1, == 0 below)
+ *                     4 sum dep   5 sum dep*dep   6 sum s2   7 sum err*err   8 sum dep*dep_b   9 sum dep_b
+ *                 the sums over the group's used observations; each term is rounded once before it is added; dep_b is dep in an
+ *                 analysis call ("stats-only" below otherwise).  An empty group gets exact zeros, a non-finite value stays in its
+ *                 group's row.  The order of every sum is fixed: partial t, t = 0..1023, starts at +0.0 and takes the terms of the
+ *                 group's used observations with o mod 1024 == t, o ascending; then for h = 512, 256, ..., 1 partial t becomes
+ *                 partial t + partial (t + h) for every t < h; partial 0 is the sum.  The counts are formed the same way from
+ *                 terms 1.0.  No atomics: two runs give the same bits, whatever the launch.
+ * spdy_qc_set(l, gross, ngroups, group): gross finite and >= 0; group NULL: the default grouping, ngroups is ignored; otherwise
+ * 1 <= ngroups <= SPDY_QC_MAX_GROUPS and group holds nobs ints for the current network, each in [0, ngroups); the table is copied.
+ * A later spdy_letkf_set_obs or spdy_pobs_set returns the grouping to the default and keeps gross.  gross == 0 with the default
+ * grouping is the state after create: OFF -- nothing more is enqueued, and every call above has the launches, graph nodes and bits
+ * it always had.  gross == 0 with a grouping given: statistics without rejection, used_o is the observation stage's.  Checks, in this
+ * order: a NULL object SPDY_ERR_ARG ("null analysis object"), a destroyed plan SPDY_ERR_STATE, gross, then with a grouping ngroups
+ * and the first entry out of range SPDY_ERR_ARG; on a device plan an open capture SPDY_ERR_STATE.  A rejected call changes nothing.
+ * On a device plan the call is stream-ordered and synchronises the plan's stream, like spdy_letkf_set_obs: it uploads the grouping,
+ * and a setting that turns the check off gives "obs_used" back what the observation stage left (all 1.0 for a model-level
+ * network).  The first setting that turns anything on allocates the qc block -- the grouping, the record, the kept departure and
+ * the statistics, 20 bytes per observation of max_obs and 20 KB -- which the object keeps from then on; if the allocation fails the
+ * object is left off.  A host-only plan stores the values and allocates nothing.
+ * spdy_qc_set_slot(l, slot): the row of the statistics the next calls fill, 0 <= slot < SPDY_QC_SLOTS (0 after create).  Host only;
+ * read when a call is enqueued, so a captured call keeps its slot.  Checks: a NULL object, a destroyed plan, then slot.
+ * Once on, every analysis call on every route -- plain, masked, weight-interpolated, relaxed, from slots, on grids and from spectra
+ * -- enqueues ONE launch more, between the observation stage and the transform, and the transform reads the per-call copy of
+ * 1/error^2 whatever the network's kind.  One workgroup of 1024 threads per group walks the network in chunks of 1024; a thread
+ * decides and writes the observations of its own group and keeps its partial sums in registers; one tree in LDS at the end.
+ * spdy_letkf_field: "obs_used" reports used_o; "obs_check" [nobs]: 0.0 passed, 1.0 rejected by the check, 2.0 out of column -- out of
+ * column wins -- of the latest analysis call with the check on; "obs_stats": the whole table.  Both names are of the qc block and
+ * valid on every object of a device plan: asked for before any setting has made the block, the call makes it (it synchronises the
+ * plan's stream then, and is refused with SPDY_ERR_STATE inside a capture) and leaves the check off; the arrays hold zeros.  "obs_rinv" [nobs]: reff_o, the per-call
+ * copy of 1/error^2 the local analyses read -- part of the main block, written by every analysis call with the check on and by
+ * every analysis of a network with observations at a pressure, zero until then.
+ *   stats-only    spdy_qc_stats_grid_dev(l, ug, vg, tg, qg, psg, d_use, slot) and spdy_qc_stats_dev(l, vor, div, t, q, ps, d_use,
+ *                 slot), for observation-minus-analysis and the products of Desroziers et al. (2005): the observation stage of the
+ *                 analysis on the given ensemble (from spectra: after the analysis' inverse batch into the grid workspace), then the
+ *                 check's launch in a mode that decides nothing.  used_o and check_o are those of the latest analysis call with
+ *                 the check on, dep_b is that call's departure: both are kept in the qc block, which every such analysis call
+ *                 writes.  Row `slot` is filled as above with dep the departure on the given state, so on the analysed state
+ *                 sum dep*dep_b is sum d_oa d_ob over the analysis' used set.  It overwrites hx, hxmean, y and departure (and, for
+ *                 a network with observations at a pressure, obs_lnsigma), as an analysis call does; obs_used and obs_check stay the
+ *                 analysis'; no state changes.  It observes every observation on the state given, whatever slots are set.
+ *                 d_use may be NULL.  Two launches on grids, one more with a mask; capturable.  Checks, in this order: a NULL
+ *                 object SPDY_ERR_ARG, a destroyed plan SPDY_ERR_STATE; the check off, or no analysis call with the check on since
+ *                 the network was set, SPDY_ERR_STATE; a NULL pointer, slot outside [0, SPDY_QC_SLOTS) SPDY_ERR_ARG; a host-only
+ *                 plan SPDY_ERR_NO_DEVICE last.
+ * The calls carry a prefix of their own, as spdy_pobs_set and the spdy_mask_ calls do (DESIGN.md s23 says why).                  */
+enum { SPDY_QC_MAX_GROUPS = 64, SPDY_QC_SLOTS = 4 };
+int spdy_qc_set(spdy_letkf *l, double gross, int ngroups, const int *group);
+int spdy_qc_set_slot(spdy_letkf *l, int slot);
+int spdy_qc_stats_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
+                           const int *d_use, int slot);
+int spdy_qc_stats_dev(spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q, const double *ps,
+                      const int *d_use, int slot);
+
 /* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
  * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
  * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a

@@ -207,6 +207,10 @@ SIGNATURES = {
     "spdy_slot_analyse_grid_dev": [c_void_p] * 12,
     "spdy_slot_ens_letkf_dev": [c_void_p] * 7,
     "spdy_slot_nature_observe_dev": [c_void_p, c_void_p, c_int, c_double],
+    "spdy_qc_set": [c_void_p, c_double, c_int, c_void_p],
+    "spdy_qc_set_slot": [c_void_p, c_int],
+    "spdy_qc_stats_grid_dev": [c_void_p] * 7 + [c_int],
+    "spdy_qc_stats_dev": [c_void_p] * 7 + [c_int],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

@@ -107,6 +107,23 @@ int observe_grid(spdy_letkf *l, int slot, const double *const *x)
     return SPDY_OK;
 }
 
+// the check's launch on what the observation stage has just written (include/spdy.h, "background check and observation
+// statistics"): decide -- an analysis call; otherwise the stats-only call.  The row of the statistics is that of `slot`
+int check_obs(spdy_letkf *l, const int *umap, bool decide, int slot)
+{
+    if (!l->d_qc_stats) return fail(SPDY_ERR_STATE, "letkf: the background check is on without its block");
+    spdy::LetkfQc q{};
+    q.nobs = l->nobs; q.nmem = l->nmem; q.ngroups = l->qc_ngroups; q.g2 = l->gross * l->gross;
+    q.group = l->qc_group.empty() ? nullptr : l->d_qc_group; q.var = l->d_var;
+    q.y = l->d_y; q.dep = l->d_dep; q.err = l->d_err; q.rinv = l->d_rinv;
+    q.incol = l->npobs ? l->d_used : nullptr;
+    q.used = l->d_used; q.reff = l->d_reff; q.check = l->d_qc_check; q.depb = l->d_qc_depb;
+    q.stats = l->d_qc_stats + (size_t)slot * SPDY_QC_MAX_GROUPS * spdy::QC_STATS;
+    q.umap = umap;
+    KERNEL(spdy::launch_letkf_qc(q, decide, l->plan->stream));
+    return SPDY_OK;
+}
+
 // d_use: NULL, or the member mask -- one launch more in front, which builds the table the masked forms of the kernels read.
 // slots: the finish kernel of "observations in time slots" in the observation kernel's place, everything else as it is.
 // The observation stage's argument is filled once (observe_args); one branch: observe now, or finish what the slots kept
@@ -150,6 +167,12 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
     } else {
         KERNEL(spdy::launch_letkf_observe(o, p->stream));
     }
+    // the background check: one launch more, and the transform reads the per-call 1 / error^2 whatever the network's kind
+    if (l->qc_on()) {
+        RC(check_obs(l, umap, true, l->qc_slot));
+        c.rinv = l->d_reff;
+        l->qc_analysed = true;
+    }
     auto transform = [&]() -> int {
         if (umap) {
             KERNEL(spdy::launch_letkf_transform_masked(spdy::LetkfMaskedCols{c, l->rho, umap}, l->lds, p->stream));
@@ -171,6 +194,53 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
     RC(transform());
     KERNEL(spdy::launch_letkf_apply(ap, p->stream, umap));
     return relax();
+}
+
+// the qc block of a device plan's object, made once: the statistics, the record, the kept departure and the grouping, zeroed so that
+// no call ever reads what it did not write.  The caller has checked that no capture is open; a failure leaves no block
+int qc_block(spdy_letkf *l)
+{
+    if (l->d_qc_stats) return SPDY_OK;
+    spdy_plan *p = l->plan;
+    size_t bytes = 0;
+    auto all = [&]() -> int {
+        RC(dev_carve(p, [&](auto &&v) { l->qc_arrays(v, (size_t)(l->max_obs > 0 ? l->max_obs : 1)); }, &bytes));
+        HIP_TRY(hipMemsetAsync(l->d_qc_stats, 0, bytes, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return SPDY_OK;
+    };
+    if (const int rc = all()) {
+        (void)dev_release(p, l->d_qc_stats);
+        l->qc_arrays(Carve{});
+        return rc;
+    }
+    return SPDY_OK;
+}
+
+// the stats-only calls' checks in the documented order, the device last
+int stats_ready(spdy_letkf *l, bool ptrs_ok, int slot)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!l->qc_on()) return fail(SPDY_ERR_STATE, "qc_stats: spdy_qc_set first");
+    if (!l->qc_analysed) return fail(SPDY_ERR_STATE, "qc_stats: no analysis call with the check on since the network was set");
+    if (!ptrs_ok) return fail(SPDY_ERR_ARG, "null device pointer");
+    if (slot < 0 || slot >= SPDY_QC_SLOTS) return fail(SPDY_ERR_ARG, "qc_stats: slot=%d outside [0, %d)", slot, SPDY_QC_SLOTS);
+    NEED_DEVICE(l->plan);
+    return SPDY_OK;
+}
+
+// the stats-only call on a gridded ensemble: [the mask's launch,] the observation stage on every observation, the check's launch
+// in the mode that decides nothing
+int stats_grid(spdy_letkf *l, const double *const *x, const int *d_use, int slot)
+{
+    spdy_plan *p = l->plan;
+    const int *const umap = d_use ? l->d_umap : nullptr;
+    if (d_use) KERNEL(spdy::launch_letkf_mask(d_use, l->nmem, l->d_umap, l->d_nused + 1, p->stream));
+    l->masked_last = d_use != nullptr;
+    spdy::LetkfObserve o = observe_args(l, x, 0, l->nobs);
+    o.umap = umap;
+    KERNEL(spdy::launch_letkf_observe(o, p->stream));
+    return check_obs(l, umap, false, slot);
 }
 
 // the coarse columns of a stride and every grid column's stencil in them (include/spdy.h, "ensemble analysis": weight interpolation)
@@ -258,7 +328,7 @@ int ingest(spdy_letkf *l, int nobs, const OBS *host, const char *call, const cha
     spdy_letkf::ObsTables tab;                // the object's next tables: moved in once every copy has succeeded
     tab.sidx.resize(4 * n); tab.swgt.resize(4 * n); tab.unit.resize(3 * n); tab.lns.resize(n); tab.rinv.resize(n); tab.lnp.resize(PRES ? n : 0);
     // obs_used is all ones from create on; only an analysis of a network with at-pressure observations writes anything else
-    const bool reset_used = p->device >= 0 && (PRES || l->npobs > 0);
+    const bool reset_used = p->device >= 0 && (PRES || l->npobs > 0 || l->d_qc_stats);
     std::vector<double> ones(reset_used ? n : 0, 1.0);
     int npobs = 0;
     for (size_t o = 0; o < n; ++o) {
@@ -304,12 +374,14 @@ int ingest(spdy_letkf *l, int nobs, const OBS *host, const char *call, const cha
             // arrays when they go
             (void)hipStreamSynchronize(p->stream);
             l->nobs = 0; l->npobs = 0; l->obs = {}; l->nslots = 0;
+            l->qc_group.clear(); l->qc_ngroups = spdy::LETKF_VARS; l->qc_analysed = false;
             return rc;
         }
     }
     l->nobs = nobs; l->npobs = npobs;
     l->obs = std::move(tab);
     l->nslots = 0;                            // the ranges were of the network that has just gone
+    l->qc_group.clear(); l->qc_ngroups = spdy::LETKF_VARS; l->qc_analysed = false;      // and so were the grouping and what the check kept
     return SPDY_OK;
 }
 }  // namespace
@@ -395,7 +467,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
 int spdy_letkf_destroy(spdy_letkf *l)
 {
     if (!l) return SPDY_OK;
-    retire(l, {l->d_tw, l->d_raw, l->d_grid});
+    retire(l, {l->d_tw, l->d_raw, l->d_qc_stats, l->d_grid});
     delete l;
     return SPDY_OK;
 }
@@ -510,11 +582,17 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
         {"hx", &spdy_letkf::d_hx}, {"hxmean", &spdy_letkf::d_hxmean}, {"y", &spdy_letkf::d_y}, {"departure", &spdy_letkf::d_dep},
         {"weights", &spdy_letkf::d_tw}, {"value", &spdy_letkf::d_value}, {"grid", &spdy_letkf::d_grid},
         {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}, {"members_used", &spdy_letkf::d_nused},
-        {"inflation", &spdy_letkf::d_infl}, {"slot_ps", &spdy_letkf::d_slot_ps}, {"slot_out", &spdy_letkf::d_slot_out}};
+        {"inflation", &spdy_letkf::d_infl}, {"slot_ps", &spdy_letkf::d_slot_ps}, {"slot_out", &spdy_letkf::d_slot_out},
+        {"obs_check", &spdy_letkf::d_qc_check}, {"obs_stats", &spdy_letkf::d_qc_stats}, {"obs_rinv", &spdy_letkf::d_reff}};
     const auto *f = std::find_if(std::begin(fields), std::end(fields), [&](const auto &t) { return !std::strcmp(name, t.name); });
     if (f == std::end(fields)) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f->ptr == &spdy_letkf::d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
     NEED_DEVICE(l->plan);
+    if ((f->ptr == &spdy_letkf::d_qc_check || f->ptr == &spdy_letkf::d_qc_stats) && !l->d_qc_stats) {
+        // the names of the qc block are valid on every object: asking for one makes the block, and leaves the check off
+        NOT_CAPTURING(l->plan, "spdy_letkf_field (allocation of the qc block)");
+        RC(qc_block(l));
+    }
     *d_ptr = l->*(f->ptr);
     if (f->ptr == &spdy_letkf::d_nused && l->masked_last) *d_ptr += 1;      // the count of the kind of call enqueued last
     return SPDY_OK;
@@ -598,6 +676,76 @@ int spdy_slot_ens_letkf_dev(spdy_letkf *l, double *vor, double *div, double *t, 
 {
     RC(analysis_ready(l, vor && div && t && q && ps, true));
     return ens_analyse(l, vor, div, t, q, ps, d_use, true);
+}
+
+int spdy_qc_set(spdy_letkf *l, double gross, int ngroups, const int *group)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!(gross >= 0.0) || !std::isfinite(gross)) return fail(SPDY_ERR_ARG, "qc_set: gross must be finite and >= 0");
+    if (group) {
+        if (ngroups < 1 || ngroups > SPDY_QC_MAX_GROUPS) return fail(SPDY_ERR_ARG, "qc_set: ngroups=%d outside [1, %d]", ngroups, SPDY_QC_MAX_GROUPS);
+        for (int o = 0; o < l->nobs; ++o)
+            if (group[o] < 0 || group[o] >= ngroups) return fail(SPDY_ERR_ARG, "qc_set: observation %d: group=%d outside [0, %d)", o, group[o], ngroups);
+    }
+    spdy_plan *p = l->plan;
+    // a grouping of an empty network is still a grouping: one entry keeps it apart from the default
+    std::vector<int> table;
+    if (group) table.assign(group, group + l->nobs);
+    if (group && table.empty()) table.push_back(0);
+    const bool on = gross != 0.0 || group;
+    if (p->device >= 0) {
+        NOT_CAPTURING(p, "spdy_qc_set (upload)");
+        HIP_TRY(hipSetDevice(p->device));
+        auto all = [&]() -> int {
+            if (on) RC(qc_block(l));              // the first setting that turns anything on makes the block
+            if (group) RC(upload(p, l->d_qc_group, table.data(), (size_t)l->nobs * sizeof(int)));
+            if (!on && l->qc_on() && !l->npobs) {
+                // off again: a model-level network's obs_used is all ones, as the observation stage leaves it
+                const std::vector<double> ones((size_t)l->nobs, 1.0);
+                RC(upload(p, l->d_used, ones.data(), ones.size() * sizeof(double)));
+                HIP_TRY(hipStreamSynchronize(p->stream));       // ones goes with this scope
+            }
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            return SPDY_OK;
+        };
+        if (const int rc = all()) {
+            (void)hipStreamSynchronize(p->stream);        // no copy is still reading the host arrays when they go
+            l->gross = 0.0; l->qc_group.clear(); l->qc_ngroups = spdy::LETKF_VARS;      // the object is left off
+            return rc;
+        }
+    }
+    l->gross = gross;
+    l->qc_ngroups = group ? ngroups : (int)spdy::LETKF_VARS;
+    l->qc_group = std::move(table);
+    return SPDY_OK;
+}
+
+int spdy_qc_set_slot(spdy_letkf *l, int slot)
+{
+    NEED_LIVE(l, "analysis object");
+    if (slot < 0 || slot >= SPDY_QC_SLOTS) return fail(SPDY_ERR_ARG, "qc_set_slot: slot=%d outside [0, %d)", slot, SPDY_QC_SLOTS);
+    l->qc_slot = slot;
+    return SPDY_OK;
+}
+
+int spdy_qc_stats_grid_dev(spdy_letkf *l, const double *ug, const double *vg, const double *tg, const double *qg, const double *psg,
+                           const int *d_use, int slot)
+{
+    RC(stats_ready(l, ug && vg && tg && qg && psg, slot));
+    const double *x[spdy::LETKF_VARS] = {ug, vg, tg, qg, psg};
+    return stats_grid(l, x, d_use, slot);
+}
+
+int spdy_qc_stats_dev(spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q, const double *ps,
+                      const int *d_use, int slot)
+{
+    RC(stats_ready(l, vor && div && t && q && ps, slot));
+    spdy_plan *p = l->plan;
+    const size_t L = (size_t)l->nmem * p->tab.kx * grid_elems(p);
+    double *g = l->d_grid;
+    RC(ens_to_grid(p, l->nmem, vor, div, t, q, ps, g));
+    const double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
+    return stats_grid(l, x, d_use, slot);
 }
 
 }  // extern "C"

@@ -621,6 +621,27 @@ struct LetkfRelax {
     const int *umap;                                 // NULL, or the member mask's table
 };
 hipError_t launch_letkf_relax(const LetkfRelax &a, hipStream_t s);
+// The background check and the observation statistics (include/spdy.h, "background check and observation statistics"; DESIGN.md
+// s27): ONE launch between the observation stage and the transform, one workgroup per group.  Per observation of the network, from
+// the y and dep the observation stage has just written: s2 = (sum_U y_e^2) / (n - 1), v = s2 + err^2, rejected if dep^2 > g2 v
+// (g2 == 0 or n < 2: the test is not made); check[o] = 0.0 passed, 1.0 rejected, 2.0 out of column (incol[o] == 0, which wins;
+// incol NULL: every observation is in its column); used[o] = check == 0 ? 1.0 : 0.0, reff[o] = used ? rinv[o] : 0.0, depb[o] =
+// dep[o].  decide false (the stats-only call): check and depb are read, not written, and used and reff follow them.  stats
+// [ngroups][QC_STATS]: n_all, n_out, n_rej, n_used, then over the used ones sum dep, dep^2, s2, err^2, dep depb, depb -- thread t of
+// 1024 takes the group's observations o = t (mod 1024) ascending, then a halving tree in LDS; no atomics.  group NULL: var.
+enum { QC_STATS = 10, QC_MAX_GROUPS = 64 };
+struct LetkfQc {
+    int nobs, nmem, ngroups;
+    double g2;                                       // gross * gross, formed on the host
+    const int *group, *var;                          // [nobs] each; group may be NULL
+    const double *y, *dep, *err, *rinv;              // [nobs][nmem], [nobs], [nobs], [nobs]
+    const double *incol;                             // [nobs] what the observation stage wrote to used, or NULL; may be used
+    double *used, *reff;                             // [nobs] each
+    double *check, *depb;                            // [nobs] each: the record and the departure of the latest checked analysis
+    double *stats;                                   // [ngroups][QC_STATS]: the row of the call's slot
+    const int *umap;                                 // NULL, or the member mask's table
+};
+hipError_t launch_letkf_qc(const LetkfQc &a, bool decide, hipStream_t s);
 
 // The nature run (csrc/spdy_nature.hip; include/spdy.h, "nature run").  The truth is one member of the analysis'
 // gridded layout: row f = v * kx + k of u, v, t, q, then ps, (4 kx + 1) grids.  state = {seed, draws}.

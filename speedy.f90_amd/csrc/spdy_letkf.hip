@@ -602,6 +602,94 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_relax_kernel(const LetkfRel
     a.inflation[(size_t)item * ncol + col] = f;
 }
 
+// The background check and the observation-space statistics (include/spdy.h, "background check and observation statistics";
+// DESIGN.md s27), between the observation stage and the transform.  Workgroup g owns group g: its QC_BLOCK = 1024 threads walk the
+// network in chunks of QC_BLOCK, thread t looks at observation base + t and takes it if it is of group g, so thread t holds the
+// partial sums of the group's observations o = t (mod QC_BLOCK), o ascending; then a halving tree in LDS, s[t] = s[t] + s[t + h]
+// for h = 512, 256, ..., 1, five of the ten numbers at a time.  (With 256 threads the walk of 13 728 observations was a chain of 54
+// dependent steps per thread, 87 us at E = 4; the sums' order is part of the definition, so the block size is too.)  An observation
+// is of one group only: what is written per observation has one writer.  DECIDE: an analysis call -- the test is made (g2 > 0,
+// n >= 2), used, reff and the check's record are written, and the departure is kept.  Otherwise the stats-only call: the record and
+// the kept departure of the latest checked analysis are read and nothing is decided; used and reff are given back what that
+// analysis left (the observation stage of an at-pressure network has just overwritten them).  MASK (the member mask, a.umap): n
+// and the members of the spread's sum are the mask's, by a select.  One body, four instantiations, no run-time branch on either.
+// No atomics; every bound a kernel argument or a constant.
+constexpr int QC_BLOCK = 1024, QC_PASS = QC_STATS / 2;
+
+template <bool MASK, bool DECIDE>
+__global__ __launch_bounds__(QC_BLOCK) void letkf_qc_kernel(const LetkfQc a)
+{
+#pragma clang fp contract(off)
+    __shared__ double part[QC_PASS][QC_BLOCK];
+    const int g = blockIdx.x, tid = threadIdx.x, E = a.nmem, n = MASK ? a.umap[0] : E;
+    const double nm1 = (double)(n - 1);
+    const bool test = DECIDE && a.g2 > 0.0 && n >= 2;
+    double acc[QC_STATS];
+#pragma unroll
+    for (int i = 0; i < QC_STATS; ++i) acc[i] = 0.0;
+    // the group of the next chunk's observation is asked for before this chunk's is worked on, and everything an observation
+    // needs is loaded before the first store: the walk is a chain of one memory latency per chunk, not of three
+    const int *const gid = a.group ? a.group : a.var;
+    int mine = tid < a.nobs ? gid[tid] : -1;
+    for (int base = 0; base < a.nobs; base += QC_BLOCK) {
+        const int o = base + tid, onext = o + QC_BLOCK, here = mine;
+        mine = onext < a.nobs ? gid[onext] : -1;
+        if (here != g) continue;
+        const double *const y = a.y + (size_t)o * E;
+        const double err = a.err[o], dep = a.dep[o], rinv = a.rinv[o];
+        const double kept0 = DECIDE ? (a.incol ? a.incol[o] : 1.0) : a.check[o], kept1 = DECIDE ? 0.0 : a.depb[o];
+        double ss = 0.0;
+        for (int e = 0; e < E; ++e) {
+            const bool u = !MASK || a.umap[LETKF_URANK + e] >= 0;
+            const double ye = y[e];
+            ss = u ? ss + ye * ye : ss;
+        }
+        const double s2 = ss / nm1, e2 = err * err;
+        double code, depb;
+        if constexpr (DECIDE) {
+            const bool incol = kept0 != 0.0;
+            const bool rej = test && dep * dep > a.g2 * (s2 + e2);
+            code = !incol ? 2.0 : rej ? 1.0 : 0.0;
+            depb = dep;
+            a.check[o] = code;
+            a.depb[o] = dep;
+        } else {
+            code = kept0;
+            depb = kept1;
+        }
+        const bool used = code == 0.0;
+        a.used[o] = used ? 1.0 : 0.0;
+        a.reff[o] = used ? rinv : 0.0;
+        acc[0] += 1.0;
+        acc[1] = code == 2.0 ? acc[1] + 1.0 : acc[1];
+        acc[2] = code == 1.0 ? acc[2] + 1.0 : acc[2];
+        if (used) {
+            acc[3] += 1.0;
+            acc[4] += dep;
+            acc[5] += dep * dep;
+            acc[6] += s2;
+            acc[7] += e2;
+            acc[8] += dep * depb;
+            acc[9] += depb;
+        }
+    }
+#pragma unroll
+    for (int pass = 0; pass < QC_STATS / QC_PASS; ++pass) {
+#pragma unroll
+        for (int i = 0; i < QC_PASS; ++i) part[i][tid] = acc[pass * QC_PASS + i];
+        __syncthreads();
+        for (int h = QC_BLOCK / 2; h >= 1; h >>= 1) {
+            if (tid < h) {
+#pragma unroll
+                for (int i = 0; i < QC_PASS; ++i) part[i][tid] = part[i][tid] + part[i][tid + h];
+            }
+            __syncthreads();
+        }
+        if (tid < QC_PASS) a.stats[(size_t)g * QC_STATS + pass * QC_PASS + tid] = part[tid][0];
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 size_t letkf_lds_bytes(int nmem, int kx, int nlv) { return sizeof(double) * (size_t)LetkfLds((nmem + 1) & ~1, kx, nlv).total; }
@@ -781,6 +869,23 @@ hipError_t launch_letkf_relax(const LetkfRelax &a, hipStream_t s)
         hipLaunchKernelGGL(letkf_relax_kernel<true>, grid, dim3(LETKF_BLOCK), 0, s, a);
     else
         hipLaunchKernelGGL(letkf_relax_kernel<false>, grid, dim3(LETKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_qc(const LetkfQc &a, bool decide, hipStream_t s)
+{
+    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.ngroups < 1 || a.ngroups > QC_MAX_GROUPS || !(a.g2 >= 0.0) ||
+        !a.stats || !a.check || !a.depb)
+        return hipErrorInvalidValue;
+    if (a.nobs && (!a.var || !a.y || !a.dep || !a.err || !a.rinv || !a.used || !a.reff)) return hipErrorInvalidValue;
+    const dim3 grid(a.ngroups), block(QC_BLOCK);
+    if (a.umap) {
+        if (decide) hipLaunchKernelGGL((letkf_qc_kernel<true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((letkf_qc_kernel<true, false>), grid, block, 0, s, a);
+    } else {
+        if (decide) hipLaunchKernelGGL((letkf_qc_kernel<false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((letkf_qc_kernel<false, false>), grid, block, 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -224,9 +224,30 @@ struct spdy_letkf final : spdy_detail::PlanObject {
     double rtpp = 0.0, rtps = 0.0;
     double *d_infl = nullptr, *d_raw = nullptr;
     template <class V> void relax_arrays(V &&v, size_t ncol = 0, size_t kx = 0) { v(d_raw, (4 * kx + 1) * nmem * ncol); }
+    // the background check and the observation statistics (spdy_qc_set, spdy_qc_set_slot): read when a call is enqueued.  gross 0
+    // and no grouping: off, the analysis launches what it always did.  qc_group: the caller's group of every observation of the
+    // current network, empty: the default, the observation's variable (qc_ngroups is then LETKF_VARS); set_obs and pobs_set
+    // return it to the default.  qc_analysed: an analysis call with the check on has been enqueued for the current network, so
+    // the kept record and departure are its.  The qc block is an allocation of its own, made by the first setting that turns
+    // anything on and kept from then on (a captured graph may point into it): d_qc_stats [SPDY_QC_SLOTS][SPDY_QC_MAX_GROUPS][10],
+    // d_qc_check, d_qc_depb [max_obs] the record (0.0 passed, 1.0 rejected, 2.0 out of column) and the departure of the latest
+    // checked analysis, d_qc_group [max_obs] the uploaded grouping
+    double gross = 0.0;
+    int qc_ngroups = spdy::LETKF_VARS, qc_slot = 0;
+    std::vector<int> qc_group;
+    bool qc_analysed = false;
+    double *d_qc_stats = nullptr, *d_qc_check = nullptr, *d_qc_depb = nullptr;
+    int *d_qc_group = nullptr;
+    bool qc_on() const { return gross != 0.0 || !qc_group.empty(); }
+    template <class V> void qc_arrays(V &&v, size_t M = 0)
+    {
+        v(d_qc_stats, M ? (size_t)SPDY_QC_SLOTS * SPDY_QC_MAX_GROUPS * spdy::QC_STATS : 0); v(d_qc_check, M); v(d_qc_depb, M);
+        v(d_qc_group, M);
+    }
     void forget_device() override
     {
         arrays(spdy_detail::Carve{}); interp_arrays(spdy_detail::Carve{}); relax_arrays(spdy_detail::Carve{});
+        qc_arrays(spdy_detail::Carve{});
     }
 };
 

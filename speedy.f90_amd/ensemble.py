@@ -280,6 +280,17 @@ class Ensemble:
             raise ValueError("analyse: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
         letkf.analyse_dev(self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], use, slots)
 
+    def obs_stats(self, letkf, slot, use=None):
+        """The stats-only call on time level 1 as it stands now (include/spdy.h, "background check and observation statistics"):
+        the analysis' inverse batch and observation stage, then the statistics of row `slot` over the used set of letkf's latest
+        checked analysis, with that analysis' departure as dep_b -- after analyse(letkf) this is observation-minus-analysis, and
+        sum_dep_depb the Desroziers product.  Nothing of the ensemble changes; capturable.  letkf.obs_stats(slot) downloads the row."""
+        if getattr(letkf, "sp", None) is not self.sp:
+            raise ValueError("obs_stats: the Letkf must belong to the ensemble's plan")
+        if letkf.nmem != self.nmem:
+            raise ValueError("obs_stats: the Letkf holds %d members, the ensemble %d" % (letkf.nmem, self.nmem))
+        letkf.stats_dev(slot, self.vor[0], self.div[0], self.t[0], self.tr[0], self.ps[0], use)
+
     def verify(self, letkf, nature, slot=0, use=None):
         """The scores of time level 1 against a Nature's truth (include/spdy.h, "nature run"): rmse and bias of the ensemble mean and
         the spread, per variable and level, into nature.scores(slot).  Three launches, capturable; nothing of the ensemble changes.

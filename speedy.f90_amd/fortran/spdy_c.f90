@@ -1262,6 +1262,33 @@ module spdy_c
             real(c_double), value :: noise
             integer(c_int) :: rc
         end function
+        ! background check and observation statistics (include/spdy.h): group is c_null_ptr (the default grouping, the
+        ! observation's variable) or c_loc of nobs integers in [0, ngroups)
+        function spdy_qc_set(l, gross, ngroups, group) bind(C, name="spdy_qc_set") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: l, group
+            real(c_double), value :: gross
+            integer(c_int), value :: ngroups
+            integer(c_int) :: rc
+        end function
+        function spdy_qc_set_slot(l, slot) bind(C, name="spdy_qc_set_slot") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
+        function spdy_qc_stats_grid_dev(l, ug, vg, tg, qg, psg, d_use, slot) bind(C, name="spdy_qc_stats_grid_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, ug, vg, tg, qg, psg, d_use
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
+        function spdy_qc_stats_dev(l, vor, div, t, q, ps, d_use, slot) bind(C, name="spdy_qc_stats_dev") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: l, vor, div, t, q, ps, d_use
+            integer(c_int), value :: slot
+            integer(c_int) :: rc
+        end function
         function spdy_letkf_table(l, name, buf, cap) bind(C, name="spdy_letkf_table") result(rc)
             import :: c_int, c_ptr, c_char
             type(c_ptr), value :: l, buf
@@ -1382,6 +1409,8 @@ module spdy_c
     integer(c_int), parameter :: SPDY_OBS_U = 0_c_int, SPDY_OBS_V = 1_c_int, SPDY_OBS_T = 2_c_int, SPDY_OBS_Q = 3_c_int, &
         & SPDY_OBS_PS = 4_c_int                                !! spdy_obs%var (include/spdy.h)
     integer(c_int), parameter :: SPDY_MAX_SLOTS = 32_c_int     !! the most time slots of spdy_slot_set (include/spdy.h)
+    integer(c_int), parameter :: SPDY_QC_MAX_GROUPS = 64_c_int, SPDY_QC_SLOTS = 4_c_int
+                                                               !! background check: the most groups, the statistics' rows (include/spdy.h)
     integer(c_int), parameter :: SPDY_OBS_AT_P = -1_c_int      !! spdy_pobs%lev: the observation sits at p (include/spdy.h)
     integer(c_int), parameter :: SPDY_DEVICE_AUTO = -2_c_int   !! $SPDY_DEVICE, else the launcher's local rank (include/spdy.h)
     integer(c_int), parameter :: SPDY_MAX_PLEV = 32_c_int, SPDY_PLEV_LINEAR_P = 0_c_int, SPDY_PLEV_LOG_P = 1_c_int

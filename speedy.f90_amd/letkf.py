@@ -13,7 +13,10 @@ members the guard has not stopped and leave the others alone, bit for bit (inclu
 set_relaxation(rtpp, rtps) relaxes the analysis towards the background where observations acted, one launch more (include/spdy.h,
 "relaxation").  set_slots(first) divides the observations into time slots: Ensemble.observe(letkf, s) during the
 forecast takes each member's H x_e at the slot's own time, Ensemble.analyse(letkf, slots=True) is then one update from all of them,
-the 4D-LETKF (include/spdy.h, "observations in time slots")."""
+the 4D-LETKF (include/spdy.h, "observations in time slots").  set_background_check(gross) tests every departure
+against spread plus error before the local analyses read it and keeps the counts and sums of an innovation table per group of
+observations, one launch more; obs_stats() downloads them (include/spdy.h, "background check and observation statistics";
+DESIGN.md s27)."""
 import ctypes
 
 import numpy as np
@@ -34,8 +37,12 @@ _FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "dep
            "weights": lambda l: (check(l.lib.spdy_letkf_table(l.h, b"coarse_columns", None, 0)), l.sp.kx, l.nmem, l.nmem),
            "value": _PER_OBS, "grid": lambda l: ((4 * l.sp.kx + 1) * l.nmem,) + l.sp.grid_shape,
            "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS, "members_used": lambda l: (1,),
-           "inflation": lambda l: (4 * l.sp.kx + 1,) + l.sp.grid_shape, "slot_ps": _PER_OBS_MEMBER, "slot_out": _PER_OBS_MEMBER}
+           "inflation": lambda l: (4 * l.sp.kx + 1,) + l.sp.grid_shape, "obs_check": _PER_OBS, "obs_rinv": _PER_OBS,
+           "obs_stats": lambda l: (QC_SLOTS, QC_MAX_GROUPS, len(QC_COLUMNS)), "slot_ps": _PER_OBS_MEMBER, "slot_out": _PER_OBS_MEMBER}
 LETKF_TABLES, LETKF_FIELDS = tuple(_TABLES), tuple(_FIELDS)
+QC_MAX_GROUPS, QC_SLOTS = 64, 4       # SPDY_QC_MAX_GROUPS, SPDY_QC_SLOTS
+# the ten numbers of a group's row of the statistics, in the header's order
+QC_COLUMNS = ("n_all", "n_out", "n_rej", "n_used", "sum_dep", "sum_dep2", "sum_s2", "sum_err2", "sum_dep_depb", "sum_depb")
 
 
 class Obs(ctypes.Structure):          # spdy_obs (include/spdy.h)
@@ -73,11 +80,13 @@ class _DeviceView:
 
 class Letkf(PlanObject):
     """sigma_h: horizontal localisation scale in metres; sigma_v: vertical scale in ln sigma (<= 0: none); rho: multiplicative
-    inflation of the background covariance; weight_stride: set_weight_stride; rtpp, rtps: set_relaxation.  2 <= nmem <= 32; the
-    plan needs max_batch >= nmem (2 kx + 1)."""
+    inflation of the background covariance; weight_stride: set_weight_stride; rtpp, rtps: set_relaxation; gross, groups:
+    set_background_check (groups needs observations, so here it must be None unless max_obs == 0).  2 <= nmem <= 32; the plan needs
+    max_batch >= nmem (2 kx + 1)."""
     PREFIX = "spdy_letkf"
 
-    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1), rtpp=0.0, rtps=0.0):
+    def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1), rtpp=0.0, rtps=0.0, gross=0.0,
+                 groups=None):
         self.sp, self.lib = sp, sp.lib
         if sp.device >= 0:
             sp._sync_stream()
@@ -92,6 +101,66 @@ class Letkf(PlanObject):
         self.relaxation = (0.0, 0.0)
         if (rtpp, rtps) != (0.0, 0.0):
             self.set_relaxation(rtpp, rtps)
+        self.gross, self.ngroups, self.stats_slot = 0.0, 5, 0
+        if gross != 0.0 or groups is not None:
+            self.set_background_check(gross, groups)
+
+    def set_background_check(self, gross=0.0, groups=None, slot=0):
+        """The background check and the observation statistics (include/spdy.h, "background check and observation statistics";
+        DESIGN.md s27).  gross (finite, >= 0): an observation whose squared departure exceeds gross^2 (s2 + error^2), s2 the
+        ensemble's variance at the observation, takes no part in the analysis (field("obs_check"): 0 passed, 1 rejected, 2 out of
+        column; field("obs_used")); 0: nothing is rejected.  groups: None, the observation's variable (5 groups), or nobs integers
+        in [0, max + 1) for the current observations, at most 64 groups -- the rows of obs_stats(); set_obs returns them to the
+        default.  slot: which of the 4 rows of statistics the next calls fill, read when a call is enqueued.  (0, None), the
+        default: off, the analysis is the one it always was; otherwise every analysis call has one launch more.  Synchronises the
+        plan's stream; not inside a capture.  The first setting that turns anything on allocates a small block."""
+        table, n = None, 0
+        if groups is not None:
+            g = np.atleast_1d(np.asarray(groups))
+            if g.ndim != 1 or g.shape[0] != self.nobs or (g.size and not np.issubdtype(g.dtype, np.integer)):
+                raise ValueError("set_background_check: groups must be %d integers, one per observation" % self.nobs)
+            n = int(g.max()) + 1 if g.size else 1
+            table = (ctypes.c_int * max(g.shape[0], 1))(*[int(v) for v in g])
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        rc = self.lib.spdy_qc_set(self.h, float(gross), n, None if table is None else ctypes.cast(table, ctypes.c_void_p))
+        if rc == ERR_HIP:             # the object is left off
+            self.gross, self.ngroups = 0.0, 5
+        check(rc)
+        self.gross, self.ngroups = float(gross), n if table is not None else 5
+        check(self.lib.spdy_qc_set_slot(self.h, int(slot)))
+        self.stats_slot = int(slot)
+
+    def obs_stats(self, slot=None):
+        """The statistics of a row (default: the current one) as the latest call that filled it left them: a dict of QC_COLUMNS,
+        each an array of ngroups values -- the counts n_all, n_out, n_rej, n_used and, over the used observations, the sums of
+        the departure, its square, s2, error^2, departure times the analysis call's departure, and that departure.  Downloads:
+        synchronises the plan's stream."""
+        slot = self.stats_slot if slot is None else int(slot)
+        if not 0 <= slot < QC_SLOTS:
+            raise ValueError("obs_stats: slot outside [0, %d)" % QC_SLOTS)
+        rows = self.field("obs_stats").numpy()[slot, :self.ngroups]
+        return {name: rows[:, i].copy() for i, name in enumerate(QC_COLUMNS)}
+
+    def stats_grid(self, slot, ug, vg, tg, qg, psg, use=None):
+        """The stats-only call on a gridded ensemble (spdy_qc_stats_grid_dev): the observation stage on these grids and the
+        statistics of row `slot` with the used set and the departure of the latest checked analysis as dep_b; fields hx, hxmean, y
+        and departure are overwritten, no state changes.  Two launches (three with use); capturable."""
+        x = (ug, vg, tg, qg, psg)
+        self._grids("stats_grid", x)
+        use = use_mask(use, self.nmem, self._device())
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        check(self.lib.spdy_qc_stats_grid_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in x],
+                                              None if use is None else ctypes.c_void_p(use.data_ptr()), int(slot)))
+
+    def stats_dev(self, slot, vor, div, t, q, ps, use=None):
+        """spdy_qc_stats_dev: stats_grid on time level 1 of an ensemble's spectra (Ensemble.obs_stats)."""
+        use = use_mask(use, self.nmem, self._device())
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        check(self.lib.spdy_qc_stats_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)],
+                                         None if use is None else ctypes.c_void_p(use.data_ptr()), int(slot)))
 
     def set_relaxation(self, rtpp=0.0, rtps=0.0):
         """Relaxation of the analysis towards the background (include/spdy.h, "relaxation"), both in [0, 1]: rtpp
@@ -160,7 +229,7 @@ class Letkf(PlanObject):
         if rc == ERR_HIP:             # a copy failed, the object holds no observations now
             self.nobs, self.slots = 0, None
         check(rc)
-        self.nobs, self.slots = n, None
+        self.nobs, self.slots, self.ngroups = n, None, 5
 
     def set_slots(self, first):
         """Divides the current observations into len(first) - 1 time slots (include/spdy.h, "observations in time slots"): slot s is
@@ -232,7 +301,12 @@ class Letkf(PlanObject):
         of every grid item (u | v | t | q at kx levels, then ps) in the latest analysis call with relaxation on, exactly 1.0 where
         the analysis changed nothing; zero until the first such call.  slot_ps, slot_out [nobs, nmem]: for a network with
         observations at a pressure, every member's ps at the station and its out-of-column flag (1.0 / 0.0) as observe_grid /
-        observe_dev left them for the observation's slot (include/spdy.h, "observations in time slots"); otherwise not written."""
+        observe_dev left them for the observation's slot (include/spdy.h, "observations in time slots"); otherwise not written.
+        obs_check [nobs]: 0.0 passed, 1.0 rejected by the background check, 2.0 out of column, of the latest analysis call with the
+        check on; obs_stats [4, 64, 10]: the statistics' table (obs_stats() names its columns); both zero until then (asking for
+        one before set_background_check has made their block makes it: not inside a capture).  obs_rinv [nobs]: the per-call copy of 1/error^2 the local analyses read,
+        exactly 0 for an observation that took no part; written by an analysis of a network with observations at a pressure or
+        with the background check on."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         return DeviceField(self.sp, p.value, _FIELDS[name](self))

@@ -59,6 +59,12 @@ plain" / "grid analysis slots" replays Letkf.analyse_grid of the object on one g
 observed on it -- the same bits and so the same work -- and its difference is the finish kernel against the observation kernel it
 replaces.  With --at-pressure the same rows for the at-pressure object.
 
+--qc [GROSS] adds the analysis of the same network by an object with the background check on (include/spdy.h, "background check and
+observation statistics"; default threshold 5): one launch more.  As with --relax, the pair "grid analysis" / "grid
+analysis checked" replays Letkf.analyse_grid of both objects on one gridded ensemble and its difference is the check's cost less the
+work the rejected observations take out of the transform; "checked none rejected" is the same launch at a threshold nothing
+exceeds, its difference the check's launch alone.
+
 --osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
 to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
 three launches; (b) the captured Ensemble.verify -- the inverse batch of all members and the two score launches; (c) the host route
@@ -86,6 +92,7 @@ float32 grids written; and the surface-pressure row.
     python tools/ensemble_rate.py --letkf --mask 0 1 half
     python tools/ensemble_rate.py --letkf --slots 6 --at-pressure --json profiles/ensemble_letkf_slots_rate.json
     python tools/ensemble_rate.py --letkf --relax 0 0.9 --json profiles/ensemble_letkf_relax_rate.json
+    python tools/ensemble_rate.py --letkf --qc --json profiles/ensemble_letkf_qc_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --letkf --earlier-library --label parent
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
     python tools/ensemble_rate.py --pressure --json profiles/ensemble_pressure_rate.json
@@ -583,13 +590,15 @@ def host_observations(sp, lt, tr, cols, err, repeats):
     return float(np.median(us[1:])), min(us[1:]), max(us[1:])
 
 
-def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=(), relax=None, slots=0):
+def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=(), relax=None, slots=0,
+              qc=None):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
     of the nature run's observe and verify, and the host route to the same observation values; at_pressure: and of the analysis of
     the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged; relax
     = (rtpp, rtps): and of the analysis of the same network by an object with that relaxation on; slots = S: and, with the network
     divided into S equal time slots, of one slot's Ensemble.observe and of the slot analysis, next to the plain analysis of the same
-    object (with at_pressure also for that object)"""
+    object (with at_pressure also for that object); qc = gross: and of the analysis of the same network by an object with the
+    background check on at that threshold"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
     build()
@@ -616,6 +625,7 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
     nobs = nloc * per
     rng = np.random.default_rng(0)
     fns, nodes, rearms, keep, interp, host, used, pressure_objects, mask_objects = {}, {}, [], [], {}, {}, {}, [], []
+    rejected = {}
     for E in members:
         # the members: the case's state plus a hundredth of the differences between seeded states (0.3 K in t)
         ms = ensemblestep.member_states(sp, E + 1)
@@ -715,6 +725,39 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                     obj.analyse_grid(*xs, out=out)
                 fns[name], nodes[name] = gg.launch, gg.num_nodes()
                 mask_objects.append(((xs, out), gg))
+        if qc is not None:
+            ltq = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, **({} if stride == (1, 1) else {"weight_stride": stride}))
+            ltq.set_obs(*cols, lt.field("value").numpy(), spread)
+            ltq.set_background_check(qc)
+            with sp.graph_capture() as gq:
+                en.analyse(ltq)
+            fns["analysis checked E=%d" % E], nodes["analysis checked E=%d" % E] = gq.launch, gq.num_nodes()
+            pressure_objects.append((ltq, gq))
+            # The check's own cost is the difference of Letkf.analyse_grid on ONE gridded ensemble, the start state's, which every
+            # replay reads again: a rejected observation takes work out of the transform, so the pair is taken once more with the
+            # threshold so high that nothing is rejected ("statistics only" has the same launch)
+            nat = s.Nature(sp, capacity=1)
+            en.verify(ltq, nat, 0)
+            torch.cuda.synchronize()
+            grid = torch.from_numpy(ltq.field("grid").numpy()).cuda()
+            L = E * kx
+            xs = [grid[v * L:(v + 1) * L].reshape((E, kx) + sp.grid_shape) for v in range(4)] + [grid[4 * L:]]
+            out = [torch.empty_like(a) for a in xs]
+            nat.close()
+            for name, obj, gross in (("grid analysis E=%d" % E, lt, None), ("grid analysis checked E=%d" % E, ltq, qc),
+                                     ("grid analysis checked none rejected E=%d" % E, ltq, 1.0e6)):
+                if name in fns:
+                    continue
+                if gross is not None:
+                    obj.set_background_check(gross)
+                with sp.graph_capture() as gg:
+                    obj.analyse_grid(*xs, out=out)
+                fns[name], nodes[name] = gg.launch, gg.num_nodes()
+                mask_objects.append(((xs, out), gg))
+                if gross is not None:
+                    gg.launch()
+                    torch.cuda.synchronize()
+                    rejected["%s" % name] = int(obj.obs_stats()["n_rej"].sum())
         if stride != (1, 1):
             terms = int(np.count_nonzero(lt.table("interp_weight")))
             interp[E] = {"coarse_columns": int(lt.table("coarse_columns").size),
@@ -764,6 +807,12 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
             moved = 8 * (3 * E + 1) * (4 * kx + 1) * sp.il * sp.ix
             row.update(rtpp=relax[0], rtps=relax[1], us_over_unrelaxed=round(extra, 2), relax_bytes=moved,
                        relax_us_at_hbm_peak=round(moved / HBM * 1e6, 2))
+        if "checked" in name:
+            # next to the unchecked form of the same call: the difference of two graph replays; what the check's launch reads
+            plain = name.replace(" checked none rejected", "").replace(" checked", "")
+            row.update(gross=qc, us_over_unchecked=round(med - t[plain][0], 2), check_read_bytes=8 * nobs * (E + 3) + 4 * nobs)
+            if name in rejected:
+                row.update(rejected=rejected[name])
         if name.startswith("grid analysis slots"):
             row.update(slots=slots, us_over_plain=round(med - t[name.replace("grid analysis slots", "grid analysis plain")][0], 2))
         if name.startswith("slot observe"):
@@ -802,6 +851,7 @@ def main():
     ap.add_argument("--mask", nargs="+", default=[], metavar="K")
     ap.add_argument("--pressure", action="store_true")
     ap.add_argument("--relax", nargs=2, type=float, metavar=("RTPP", "RTPS"))
+    ap.add_argument("--qc", nargs="?", type=float, const=5.0, metavar="GROSS")
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
@@ -825,7 +875,7 @@ def main():
         for tag in a.sizes:
             if a.letkf:
                 run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure, a.mask,
-                          tuple(a.relax) if a.relax else None, a.slots)
+                          tuple(a.relax) if a.relax else None, a.slots, a.qc)
             elif a.pressure:
                 run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:

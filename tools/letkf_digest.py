@@ -10,7 +10,7 @@ three time slots observed on the same ensemble, and at weight stride (2, 2); dig
 obs_used, value and the five increments.  Nature.observe: the whole network and slot by slot, noise 0 and 1; digest over value.
 
     python tools/letkf_digest.py [--json out.json]
-    SPDY_LIB=/path/to/earlier/libspdy.so python tools/letkf_digest.py --label parent"""
+    SPDY_LIB=/path/to/earlier/libspdy.so python tools/letkf_digest.py --earlier-library --label parent"""
 import argparse
 import hashlib
 import json
@@ -56,7 +56,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--label", default="this build")
     ap.add_argument("--json")
+    ap.add_argument("--earlier-library", action="store_true", help="$SPDY_LIB is from before this build's newest entry points")
     a = ap.parse_args()
+    if a.earlier_library:                 # bind without what it lacks; nothing here calls it
+        import ctypes
+        raw = ctypes.CDLL(s._lib.LIB_PATH)
+        for n in [n for n in s._lib.SIGNATURES if not hasattr(raw, n)]:
+            del s._lib.SIGNATURES[n]
     sp = support.ensemble_plan("t30", max(MEMBERS))
     g = lp.Geometry(sp)
     out = {}

@@ -1,7 +1,8 @@
 /* Host check of the observation ingestion (include/spdy.h, "ensemble analysis"): spdy_letkf_set_obs and spdy_letkf_table on a
  * host-only plan, fed the operator's edge cases, nobs = 0 and nobs = max_obs; and of the tables of weight interpolation
  * (spdy_letkf_set_weight_stride) at the smallest and largest strides and with a short last latitude interval; and of
- * spdy_relax_set's rejections and its setting on a host-only plan.  Built by `make hostcheck` in speedy.f90_amd with
+ * spdy_relax_set's rejections and its setting on a host-only plan; and of spdy_qc_set and spdy_qc_set_slot, their rejections in
+ * the documented order, a grouping of the whole network and of an empty one, and the stats-only call's refusals.  Built by `make hostcheck` in speedy.f90_amd with
  * the address and undefined-behaviour sanitizers on the host code of the plan, the tables and the analysis; exits 0 when every
  * stencil is a convex combination of four grid points and every rejection is the documented code. */
 #include <math.h>
@@ -129,6 +130,31 @@ int main(void)
     }
     CHECK(spdy_relax_set(l, 0.0, 0.0) == SPDY_OK);
     CHECK(spdy_letkf_field(l, "inflation", &d) == SPDY_ERR_NO_DEVICE);
+    /* background check: a host-only plan stores a setting and allocates nothing; gross, then ngroups, then the entries; the table
+     * is copied, so the caller's may go at once; set_obs returns the grouping to the default */
+    int *group = malloc(sizeof(int) * MAXOBS);
+    for (int o = 0; o < MAXOBS; ++o) group[o] = o % SPDY_QC_MAX_GROUPS;
+    CHECK(spdy_qc_set(NULL, 5.0, 0, NULL) == SPDY_ERR_ARG);
+    CHECK(spdy_qc_stats_dev(l, d, d, d, d, d, NULL, 0) == SPDY_ERR_STATE);                  /* off: spdy_qc_set first */
+    for (int n = 0; n < 4; ++n)
+        if (n != 2) CHECK(spdy_qc_set(l, outside[n], SPDY_QC_MAX_GROUPS, group) == SPDY_ERR_ARG);
+    CHECK(spdy_qc_set(l, 5.0, 0, group) == SPDY_ERR_ARG && spdy_qc_set(l, 5.0, SPDY_QC_MAX_GROUPS + 1, group) == SPDY_ERR_ARG);
+    CHECK(spdy_qc_set(l, 5.0, SPDY_QC_MAX_GROUPS - 1, group) == SPDY_ERR_ARG);             /* entry 63 is out of [0, 63) */
+    group[MAXOBS - 1] = -1;
+    CHECK(spdy_qc_set(l, 5.0, SPDY_QC_MAX_GROUPS, group) == SPDY_ERR_ARG);
+    group[MAXOBS - 1] = 0;
+    CHECK(spdy_qc_stats_dev(l, d, d, d, d, d, NULL, 0) == SPDY_ERR_STATE);                  /* still off: nothing was accepted */
+    CHECK(spdy_qc_set(l, 0.0, SPDY_QC_MAX_GROUPS, group) == SPDY_OK);                      /* statistics without rejection */
+    free(group);
+    CHECK(spdy_qc_set(l, 5.0, 0, NULL) == SPDY_OK && spdy_qc_set(l, 1.5, 1, NULL) == SPDY_OK);
+    CHECK(spdy_qc_set_slot(NULL, 0) == SPDY_ERR_ARG && spdy_qc_set_slot(l, -1) == SPDY_ERR_ARG);
+    CHECK(spdy_qc_set_slot(l, SPDY_QC_SLOTS) == SPDY_ERR_ARG && spdy_qc_set_slot(l, SPDY_QC_SLOTS - 1) == SPDY_OK);
+    CHECK(spdy_qc_stats_grid_dev(l, NULL, NULL, NULL, NULL, NULL, NULL, 9) == SPDY_ERR_STATE);      /* on, but nothing analysed */
+    CHECK(spdy_letkf_field(l, "obs_check", &d) == SPDY_ERR_NO_DEVICE && spdy_letkf_field(l, "obs_stats", &d) == SPDY_ERR_NO_DEVICE);
+    CHECK(spdy_letkf_set_obs(l, 0, NULL) == SPDY_OK);
+    int none = 7;                                      /* a grouping of an empty network: no entry is read */
+    CHECK(spdy_qc_set(l, 0.0, 1, &none) == SPDY_OK && spdy_qc_stats_dev(l, d, d, d, d, d, NULL, 0) == SPDY_ERR_STATE);
+    CHECK(spdy_letkf_set_obs(l, npts, obs) == SPDY_OK && spdy_qc_set(l, 0.0, 0, NULL) == SPDY_OK);
     CHECK(spdy_letkf_destroy(l) == SPDY_OK && spdy_plan_destroy(p) == SPDY_OK);
     printf("letkf host check ok: %d edge observations, 0 and %d observations\n", npts, (int)MAXOBS);
     return 0;
