@@ -1373,6 +1373,68 @@ int spdy_qc_stats_grid_dev(spdy_letkf *l, const double *ug, const double *vg, co
 int spdy_qc_stats_dev(spdy_letkf *l, const double *vor, const double *div, const double *t, const double *q, const double *ps,
                       const int *d_use, int slot);
 
+/* ---- ensemble analysis, adaptive inflation --------------------------------------------------------------------------
+ * The scalar rho of spdy_letkf_set_localization is one number for a radiosonde-dense continent and an empty ocean.  With these calls
+ * the object carries a field rho[kx][ncol] (level-major, column j * ix + i), which every analysis call reads in the scalar's place
+ * and then advances from the call's own innovation statistics (Miyoshi 2011; Li et al. 2009), on the device: a captured cycle
+ * advances the field on every replay.  tests/letkfinfl.py restates this subsection in NumPy.  U: the members in use, all nmem
+ * without a mask, otherwise the mask's ("member mask"); n = |U|; sums over members run ascending; every operation is one IEEE
+ * operation, nothing is contracted.
+ *   per observation o, once per call:
+ *       s2_o = (sum_e y_oe^2) / (n - 1)                       "background check"'s s2 with its bits: y of a member not in use is 0.0
+ *                                                             and adds an exact zero
+ *   per column c and level k, over the observations ascending, wh, w and r formed with the local analysis' own expressions (the
+ *   chord, asin, Gaspari and Cohn's function, c_h, c_v, ln fsg_k, ln sigma_o) and the 1 / error^2 the call's local analyses read
+ *   (reff: "obs_rinv" for a network with observations at a pressure or with the background check on, rinv otherwise), so the
+ *   observations that enter the sums are exactly those that enter C of that column and level:
+ *       wh = gc(dist(c, o) / c_h)                             skipped if wh == 0
+ *       w  = c_v > 0 ? wh * gc(|ln fsg_k - ln sigma_o| / c_v) : wh
+ *       r  = w * reff_o
+ *       if r != 0:   p1 += r * (dep_o * dep_o);   p2 += r * s2_o;   p3 += w
+ *   the update, with rho = rho[k][c] before the call and vb = sigma_b * sigma_b formed on the host:
+ *       if p3 > 0 and p2 > 0:
+ *           ro  = (p1 - p3) / p2                              the observed inflation: (d^T R^-1 d - trace) / trace(H P H^T R^-1)
+ *           t   = (rho * p2 + p3) / p2
+ *           vo  = (2 / p3) * (t * t)                          its error variance, p3 the effective number of observations
+ *           g   = vb / (vo + vb)
+ *           est = rho + g * (ro - rho)
+ *           rho' = est finite ? fmin(fmax(est, rho_min), rho_max) : rho
+ *       else rho' = rho
+ *   A non-finite estimate leaves rho as it is: here a NaN does NOT propagate, unlike everywhere else in this header.  rho outlives
+ *   the call, and a NaN in it would poison its column for the rest of the run.  (The test is made on est, before the bounds: fmin
+ *   and fmax return their other argument for a NaN, so after them nothing non-finite would be left to see.)  With n < 2 neither
+ *   launch writes anything.  ps is analysed with level kx-1's transform and so uses rho[kx-1].
+ *   order within a call (Miyoshi's): the local analyses of this call use rho as it was before the call; the estimate is enqueued
+ *   after everything else of the call -- after the relaxation's launch, if any -- and writes rho in place for the next call.
+ * spdy_infl_set(l, on, sigma_b, rho_min, rho_max): sigma_b >= 0, 0 < rho_min <= rho_max, all finite.  sigma_b == 0 is legal: g = 0,
+ * the field is used and frozen.  Checks, in this order: a NULL object SPDY_ERR_ARG, a destroyed plan SPDY_ERR_STATE, sigma_b,
+ * rho_min, rho_max SPDY_ERR_ARG; then, where the call has to allocate, an open capture SPDY_ERR_STATE.  A rejected call changes
+ * nothing.  OFF is the state after create: nothing more is enqueued, and every call above has the launches, graph nodes and bits it
+ * always had.  The first "on" on a device plan allocates a block of its own -- rho[kx][ncol], filled with the object's scalar rho of
+ * that moment; infl_parm[3][kx][ncol], p1 | p2 | p3 of the latest call, zeroed; obs_s2[max_obs] -- which the object keeps from then
+ * on; that call synchronises the plan's stream, and if the allocation fails the object is left off.  Later settings change the four
+ * numbers only; they are read when a call is enqueued, so a captured call keeps those of its capture.  A host-only plan stores the
+ * values and allocates nothing.  spdy_letkf_table "adaptive_inflation" gives {on, sigma_b, rho_min, rho_max} as they are stored.
+ * spdy_infl_fill(l, rho0): rho0 finite and > 0; fills the field uniformly (it makes the block if there is none, and leaves the
+ * feature off then).  Stream-ordered, synchronises the plan's stream, refused inside a capture.  Checks: a NULL object, a destroyed
+ * plan, rho0, a host-only plan SPDY_ERR_NO_DEVICE, an open capture.
+ * While adaptive inflation is on the scalar rho is not read by the local analyses; spdy_letkf_set_localization, spdy_letkf_set_obs,
+ * spdy_pobs_set, spdy_slot_set and spdy_qc_set leave the field alone, and so do the stats-only calls and spdy_slot_observe*,
+ * which enqueue nothing of this.
+ * Once on, every analysis call on every route -- plain, masked, weight-interpolated, relaxed, from slots, at-pressure, with the
+ * background check, on grids and from spectra -- launches the local analyses in a form that reads the field (the diagonal of level
+ * k of column c is (n - 1) / rho[k][c], one IEEE division: the bits an object with that scalar has) and enqueues TWO launches
+ * more, last: one thread per observation writes obs_s2; one workgroup per grid column -- every column, whatever the weight stride:
+ * the estimate does not depend on where transforms are solved -- scans the network as the local analysis does, lane k carries
+ * level k's sums in registers, and updates rho.  An adaptive analysis has two graph nodes more than the same call with the
+ * feature off, whatever the route and also for an empty network.  No atomics: two runs give the same bits.
+ * spdy_letkf_field: "rho" [kx][ncol], writable -- a caller sets any field with a device copy and restarts a run from a saved one;
+ * "infl_parm" [3][kx][ncol]; "obs_s2" [nobs].  The three names are valid on every object of a device plan: asked for before the
+ * block exists, the call makes it (it synchronises then, and is refused with SPDY_ERR_STATE inside a capture) and leaves the
+ * feature off.  The calls carry a prefix of their own (DESIGN.md s23 says why).                                                    */
+int spdy_infl_set(spdy_letkf *l, int on, double sigma_b, double rho_min, double rho_max);
+int spdy_infl_fill(spdy_letkf *l, double rho0);
+
 /* ---- nature run: the truth of a twin experiment, observations drawn from it, an ensemble scored against it ------
  * The reference has none of this; this section defines it, and tests/nature.py restates it in NumPy.  With it a twin experiment's
  * cycle {nature step, ensemble steps, observe, verify the background, spdy_ens_letkf_dev, verify the analysis, first_step} is a

@@ -211,6 +211,8 @@ SIGNATURES = {
     "spdy_qc_set_slot": [c_void_p, c_int],
     "spdy_qc_stats_grid_dev": [c_void_p] * 7 + [c_int],
     "spdy_qc_stats_dev": [c_void_p] * 7 + [c_int],
+    "spdy_infl_set": [c_void_p, c_int, c_double, c_double, c_double],
+    "spdy_infl_fill": [c_void_p, c_double],
     "spdy_graph_begin": [c_void_p],
     "spdy_graph_end": [c_void_p, ctypes.POINTER(c_void_p)],
     "spdy_graph_launch": [c_void_p],

@@ -173,17 +173,34 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
         c.rinv = l->d_reff;
         l->qc_analysed = true;
     }
+    // adaptive inflation: the transform reads the field as it is before this call; the estimate's two launches come last and
+    // write it in place for the next call (include/spdy.h, "adaptive inflation")
+    const bool adaptive = l->infl_on;
+    if (adaptive && !l->d_rho) return fail(SPDY_ERR_STATE, "letkf: adaptive inflation is on without its block");
     auto transform = [&]() -> int {
-        if (umap) {
+        if (adaptive) {
+            KERNEL(spdy::launch_letkf_transform_adaptive(c, l->d_rho, umap, l->lds, p->stream));
+        } else if (umap) {
             KERNEL(spdy::launch_letkf_transform_masked(spdy::LetkfMaskedCols{c, l->rho, umap}, l->lds, p->stream));
         } else {
             KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
         }
         return SPDY_OK;
     };
+    auto finish = [&]() -> int {
+        RC(relax());
+        if (!adaptive) return SPDY_OK;
+        spdy::LetkfInfl e{};
+        e.nobs = l->nobs; e.nmem = l->nmem; e.kx = kx; e.ncol = ncol; e.ch = c.ch; e.cv = c.cv;
+        e.vb = l->infl_sigma_b * l->infl_sigma_b; e.rho_min = l->infl_min; e.rho_max = l->infl_max;
+        e.colunit = c.colunit; e.lnfsg = c.lnfsg; e.ounit = c.ounit; e.olns = c.olns; e.reff = c.rinv; e.y = c.y; e.dep = c.dep;
+        e.s2 = l->d_obs_s2; e.rho = l->d_rho; e.parm = l->d_infl_parm; e.umap = umap;
+        KERNEL(spdy::launch_letkf_infl(e, p->stream));
+        return SPDY_OK;
+    };
     if (!l->d_tw) {
         RC(transform());
-        return relax();
+        return finish();
     }
     // weight interpolation: T of the coarse columns, then the increments of every column from them
     c.nlist = (int)l->interp.coarse.size(); c.cols = l->d_coarse; c.tw = l->d_tw;
@@ -193,7 +210,32 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
     for (int v = 0; v < spdy::LETKF_VARS; ++v) { ap.x[v] = x[v]; ap.dx[v] = raw[v]; }
     RC(transform());
     KERNEL(spdy::launch_letkf_apply(ap, p->stream, umap));
-    return relax();
+    return finish();
+}
+
+// the block of adaptive inflation of a device plan's object, made once: the field filled with the object's scalar rho, the sums
+// and s2 zeroed.  The caller has checked that no capture is open; a failure leaves no block
+int infl_block(spdy_letkf *l)
+{
+    if (l->d_rho) return SPDY_OK;
+    spdy_plan *p = l->plan;
+    const size_t n = (size_t)p->tab.kx * grid_elems(p);
+    const std::vector<double> fill(n, l->rho);
+    size_t bytes = 0;
+    auto all = [&]() -> int {
+        RC(dev_carve(p, [&](auto &&v) { l->infl_arrays(v, grid_elems(p), (size_t)p->tab.kx, (size_t)(l->max_obs > 0 ? l->max_obs : 1)); }, &bytes));
+        HIP_TRY(hipMemsetAsync(l->d_rho, 0, bytes, p->stream));
+        RC(upload(p, l->d_rho, fill.data(), n * sizeof(double)));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return SPDY_OK;
+    };
+    if (const int rc = all()) {
+        (void)hipStreamSynchronize(p->stream);        // no copy is still reading the host array when it goes
+        (void)dev_release(p, l->d_rho);
+        l->infl_arrays(Carve{});
+        return rc;
+    }
+    return SPDY_OK;
 }
 
 // the qc block of a device plan's object, made once: the statistics, the record, the kept departure and the grouping, zeroed so that
@@ -467,7 +509,7 @@ int spdy_letkf_create(spdy_plan *p, int nmem, int max_obs, spdy_letkf **out)
 int spdy_letkf_destroy(spdy_letkf *l)
 {
     if (!l) return SPDY_OK;
-    retire(l, {l->d_tw, l->d_raw, l->d_qc_stats, l->d_grid});
+    retire(l, {l->d_tw, l->d_raw, l->d_qc_stats, l->d_rho, l->d_grid});
     delete l;
     return SPDY_OK;
 }
@@ -571,6 +613,8 @@ int spdy_letkf_table(const spdy_letkf *l, const char *name, double *buf, int cap
         if (!std::strcmp(name, t.name)) return t.index ? give(*t.index) : give(*t.v);
     if (!std::strcmp(name, "slot_first"))
         return give(std::vector<int>(l->slot_first, l->slot_first + (l->nslots ? l->nslots + 1 : 0)));
+    if (!std::strcmp(name, "adaptive_inflation"))
+        return give(std::vector<double>{l->infl_on ? 1.0 : 0.0, l->infl_sigma_b, l->infl_min, l->infl_max});
     return fail(SPDY_ERR_ARG, "unknown analysis table '%s'", name);
 }
 
@@ -583,7 +627,8 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
         {"weights", &spdy_letkf::d_tw}, {"value", &spdy_letkf::d_value}, {"grid", &spdy_letkf::d_grid},
         {"obs_lnsigma", &spdy_letkf::d_olns}, {"obs_used", &spdy_letkf::d_used}, {"members_used", &spdy_letkf::d_nused},
         {"inflation", &spdy_letkf::d_infl}, {"slot_ps", &spdy_letkf::d_slot_ps}, {"slot_out", &spdy_letkf::d_slot_out},
-        {"obs_check", &spdy_letkf::d_qc_check}, {"obs_stats", &spdy_letkf::d_qc_stats}, {"obs_rinv", &spdy_letkf::d_reff}};
+        {"obs_check", &spdy_letkf::d_qc_check}, {"obs_stats", &spdy_letkf::d_qc_stats}, {"obs_rinv", &spdy_letkf::d_reff},
+        {"rho", &spdy_letkf::d_rho}, {"infl_parm", &spdy_letkf::d_infl_parm}, {"obs_s2", &spdy_letkf::d_obs_s2}};
     const auto *f = std::find_if(std::begin(fields), std::end(fields), [&](const auto &t) { return !std::strcmp(name, t.name); });
     if (f == std::end(fields)) return fail(SPDY_ERR_ARG, "unknown analysis field '%s'", name);
     if (f->ptr == &spdy_letkf::d_tw && l->si == 1 && l->sj == 1) return fail(SPDY_ERR_STATE, "letkf: no weight buffer at stride (1, 1)");
@@ -592,6 +637,11 @@ int spdy_letkf_field(spdy_letkf *l, const char *name, double **d_ptr)
         // the names of the qc block are valid on every object: asking for one makes the block, and leaves the check off
         NOT_CAPTURING(l->plan, "spdy_letkf_field (allocation of the qc block)");
         RC(qc_block(l));
+    }
+    if ((f->ptr == &spdy_letkf::d_rho || f->ptr == &spdy_letkf::d_infl_parm || f->ptr == &spdy_letkf::d_obs_s2) && !l->d_rho) {
+        // and so are the names of adaptive inflation's block: asking for one makes it, and leaves the feature off
+        NOT_CAPTURING(l->plan, "spdy_letkf_field (allocation of the adaptive-inflation block)");
+        RC(infl_block(l));
     }
     *d_ptr = l->*(f->ptr);
     if (f->ptr == &spdy_letkf::d_nused && l->masked_last) *d_ptr += 1;      // the count of the kind of call enqueued last
@@ -717,6 +767,43 @@ int spdy_qc_set(spdy_letkf *l, double gross, int ngroups, const int *group)
     l->gross = gross;
     l->qc_ngroups = group ? ngroups : (int)spdy::LETKF_VARS;
     l->qc_group = std::move(table);
+    return SPDY_OK;
+}
+
+int spdy_infl_set(spdy_letkf *l, int on, double sigma_b, double rho_min, double rho_max)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!(sigma_b >= 0.0) || !std::isfinite(sigma_b)) return fail(SPDY_ERR_ARG, "infl_set: sigma_b must be finite and >= 0");
+    if (!(rho_min > 0.0) || !std::isfinite(rho_min)) return fail(SPDY_ERR_ARG, "infl_set: rho_min must be finite and > 0");
+    if (!(rho_max >= rho_min) || !std::isfinite(rho_max)) return fail(SPDY_ERR_ARG, "infl_set: rho_max must be finite and >= rho_min");
+    spdy_plan *p = l->plan;
+    if (on && p->device >= 0 && !l->d_rho) {
+        // the first "on": the block, the field filled with the scalar rho
+        NOT_CAPTURING(p, "spdy_infl_set (allocation)");
+        HIP_TRY(hipSetDevice(p->device));
+        if (const int rc = infl_block(l)) {
+            l->infl_on = false;                       // the object is left off
+            return rc;
+        }
+    }
+    l->infl_on = on != 0; l->infl_sigma_b = sigma_b; l->infl_min = rho_min; l->infl_max = rho_max;
+    return SPDY_OK;
+}
+
+int spdy_infl_fill(spdy_letkf *l, double rho0)
+{
+    NEED_LIVE(l, "analysis object");
+    if (!(rho0 > 0.0) || !std::isfinite(rho0)) return fail(SPDY_ERR_ARG, "infl_fill: rho0 must be finite and > 0");
+    spdy_plan *p = l->plan;
+    NEED_DEVICE(p);
+    NOT_CAPTURING(p, "spdy_infl_fill (upload)");
+    RC(infl_block(l));
+    const size_t n = (size_t)p->tab.kx * grid_elems(p);
+    const std::vector<double> fill(n, rho0);
+    const int rc = upload(p, l->d_rho, fill.data(), n * sizeof(double));
+    const hipError_t done = hipStreamSynchronize(p->stream);      // fill goes with this scope
+    if (rc) return rc;
+    HIP_TRY(done);
     return SPDY_OK;
 }
 

@@ -642,6 +642,32 @@ struct LetkfQc {
     const int *umap;                                 // NULL, or the member mask's table
 };
 hipError_t launch_letkf_qc(const LetkfQc &a, bool decide, hipStream_t s);
+// Adaptive inflation (include/spdy.h, "adaptive inflation").  The transform under a field rho [kx][ncol]: LetkfCols
+// with the diagonal of level k of column col formed on the device as (n - 1) / rho[k * ncol + col] (c.diag is not read), without
+// and with the member mask.  Types of their own, as LetkfMaskedCols is: the kernels on the other two arguments stay what they were.
+struct LetkfAdaptiveCols {
+    LetkfCols c;
+    const double *rho;
+};
+struct LetkfAdaptiveMaskedCols {
+    LetkfCols c;
+    const double *rho;
+    const int *umap;
+};
+hipError_t launch_letkf_transform_adaptive(const LetkfCols &c, const double *rho, const int *umap, size_t lds, hipStream_t s);
+// The estimate, TWO launches after everything else of an analysis call: s2[o] of every observation, one thread each; then one
+// workgroup per grid column scans the network as the transform kernel does and lane k < kx sums p1, p2, p3 of level k over the
+// observations in range, ascending, updates rho[k][col] in place and stores parm [3][kx][ncol].  reff: the 1 / error^2 the call's
+// transform read.  n < 2 under the mask: neither launch writes anything.
+struct LetkfInfl {
+    int nobs, nmem, kx, ncol;
+    double ch, cv;                                   // as LetkfCols
+    double vb, rho_min, rho_max;                     // sigma_b^2, formed on the host; the bounds
+    const double *colunit, *lnfsg, *ounit, *olns, *reff, *y, *dep;
+    double *s2, *rho, *parm;                         // [nobs], [kx][ncol], [3][kx][ncol]
+    const int *umap;                                 // NULL, or the member mask's table
+};
+hipError_t launch_letkf_infl(const LetkfInfl &a, hipStream_t s);
 
 // The nature run (csrc/spdy_nature.hip; include/spdy.h, "nature run").  The truth is one member of the analysis'
 // gridded layout: row f = v * kx + k of u, v, t, q, then ps, (4 kx + 1) grids.  state = {seed, draws}.

@@ -196,12 +196,26 @@ __device__ inline const int *letkf_umap(const LetkfMaskedCols &a) { return a.uma
 __device__ inline double letkf_diag(const LetkfCols &a, int) { return a.diag; }
 // (n - 1) / rho as one IEEE division: the bits the host gives an object of n members
 __device__ inline double letkf_diag(const LetkfMaskedCols &a, int n) { return (double)(n - 1) / a.rho; }
+// ARGS = LetkfAdaptiveCols, LetkfAdaptiveMaskedCols (adaptive inflation: ADAPT; include/spdy.h, "adaptive inflation"): the diagonal
+// of level k is (n - 1) / rho[k][col], one IEEE division where C's diagonal is initialised -- the bits of an object whose scalar
+// rho is that value; everything else is the plain or the masked kernel.  Four instantiations more, no LDS more.
+__device__ inline const LetkfCols &letkf_cols(const LetkfAdaptiveCols &a) { return a.c; }
+__device__ inline const LetkfCols &letkf_cols(const LetkfAdaptiveMaskedCols &a) { return a.c; }
+__device__ inline const int *letkf_umap(const LetkfAdaptiveCols &) { return nullptr; }
+__device__ inline const int *letkf_umap(const LetkfAdaptiveMaskedCols &a) { return a.umap; }
+__device__ inline double letkf_diag(const LetkfAdaptiveCols &, int) { return 0.0; }            // not read: the diagonal is per level
+__device__ inline double letkf_diag(const LetkfAdaptiveMaskedCols &, int) { return 0.0; }
+template <class ARGS> __device__ inline double letkf_diag(const ARGS &a, int n, int k, int ncol, int col)
+{
+    return (double)(n - 1) / a.rho[(size_t)k * ncol + col];
+}
 
 template <bool LIST, class ARGS>
 __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const ARGS args)
 {
 #pragma clang fp contract(off)
-    constexpr bool MASK = !std::is_same<ARGS, LetkfCols>::value;
+    constexpr bool MASK = std::is_same<ARGS, LetkfMaskedCols>::value || std::is_same<ARGS, LetkfAdaptiveMaskedCols>::value;
+    constexpr bool ADAPT = std::is_same<ARGS, LetkfAdaptiveCols>::value || std::is_same<ARGS, LetkfAdaptiveMaskedCols>::value;
     const LetkfCols &a = letkf_cols(args);
     const int *const umap = letkf_umap(args);
     extern __shared__ __attribute__((aligned(16))) char letkf_smem[];
@@ -233,7 +247,10 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_transform_kernel(const ARGS
     // A = (E - 1) / rho I (an odd E: one decoupled row more), b = 0
     for (int el = tid; el < kx * ee; el += LETKF_BLOCK) {
         const int i = (el % ee) / ep, j = el % ep;
-        C[el] = i == j ? (i < E ? (MASK ? mdiag : a.diag) : 1.0) : 0.0;
+        if constexpr (ADAPT)
+            C[el] = i == j ? (i < E ? letkf_diag(args, E, el / ee, ncol, col) : 1.0) : 0.0;
+        else
+            C[el] = i == j ? (i < E ? (MASK ? mdiag : a.diag) : 1.0) : 0.0;
     }
     for (int el = tid; el < kx * ep; el += LETKF_BLOCK) B[el] = 0.0;
     if (tid < kx) touched[tid] = 0;
@@ -690,6 +707,96 @@ __global__ __launch_bounds__(QC_BLOCK) void letkf_qc_kernel(const LetkfQc a)
     }
 }
 
+// Adaptive inflation (include/spdy.h, "adaptive inflation"), the estimate's two launches.  The first: s2 of every
+// observation, one thread each, the members ascending; y of a member not in use is 0.0 and adds an exact zero, so there is no
+// mask form: only n is the mask's.  n < 2: nothing is written.
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_infl_obs_kernel(const LetkfInfl a)
+{
+#pragma clang fp contract(off)
+    const int o = blockIdx.x * LETKF_BLOCK + threadIdx.x, E = a.nmem, n = a.umap ? a.umap[0] : E;
+    if (o >= a.nobs || n < 2) return;
+    const double *const y = a.y + (size_t)o * E;
+    double ss = 0.0;
+    for (int e = 0; e < E; ++e) {
+        const double ye = y[e];
+        ss += ye * ye;
+    }
+    a.s2[o] = ss / (double)(n - 1);
+}
+
+// The second: one workgroup per grid column, at every column whatever the weight stride.  The scan is the transform kernel's, with
+// its expressions: chunks of LETKF_CHUNK, the horizontal weight, ballot and prefix compaction in ascending order; the thread that
+// keeps an observation stages what the sums need of it in LDS.  Lane k < kx then carries p1, p2, p3 of level k in registers over
+// the chunk's compacted observations, ascending, and after the last chunk updates rho[k][col] in place and stores the sums.  No
+// atomics; every loop bound a kernel argument or a constant; 10 KB of static LDS.
+__global__ __launch_bounds__(LETKF_BLOCK) void letkf_infl_kernel(const LetkfInfl a)
+{
+#pragma clang fp contract(off)
+    __shared__ double lwh[LETKF_CHUNK], lolns[LETKF_CHUNK], lreff[LETKF_CHUNK], ld2[LETKF_CHUNK], ls2[LETKF_CHUNK];
+    __shared__ int wcount[LETKF_BLOCK / 64];
+    const int n = a.umap ? a.umap[0] : a.nmem;
+    if (n < 2) return;                            // the same for every thread of the launch
+    const int tid = threadIdx.x, col = blockIdx.x, kx = a.kx, ncol = a.ncol;
+    const double cx = a.colunit[col], cy = a.colunit[ncol + col], cz = a.colunit[2 * ncol + col];
+    const double lnk = tid < kx ? a.lnfsg[tid] : 0.0;
+    double p1 = 0.0, p2 = 0.0, p3 = 0.0;
+    for (int base = 0; base < a.nobs; base += LETKF_CHUNK) {
+        const int o = base + tid;
+        double wh = 0.0;
+        if (o < a.nobs) {
+            const double dx = cx - a.ounit[3 * (size_t)o], dy = cy - a.ounit[3 * (size_t)o + 1], dz = cz - a.ounit[3 * (size_t)o + 2];
+            const double chord = sqrt((dx * dx + dy * dy) + dz * dz);
+            const double dist = 2.0 * LETKF_REARTH * asin(fmin(1.0, 0.5 * chord));
+            wh = letkf_gc(dist / a.ch);
+        }
+        const bool keep = wh != 0.0;
+        const unsigned long long mask = __ballot(keep);
+        const int lane = tid & 63, wave = tid >> 6;
+        if (lane == 0) wcount[wave] = __popcll(mask);
+        __syncthreads();
+        int pos = __popcll(mask & ((1ull << lane) - 1ull)), nc = 0;
+        for (int w = 0; w < LETKF_BLOCK / 64; ++w) {
+            const int c = wcount[w];
+            if (w < wave) pos += c;
+            nc += c;
+        }
+        if (keep) {
+            const double dep = a.dep[o];
+            lwh[pos] = wh; lolns[pos] = a.olns[o]; lreff[pos] = a.reff[o]; ld2[pos] = dep * dep; ls2[pos] = a.s2[o];
+        }
+        __syncthreads();
+        if (tid < kx)
+            for (int t = 0; t < nc; ++t) {
+                double w = lwh[t];
+                if (a.cv > 0.0) w = w * letkf_gc(fabs(lnk - lolns[t]) / a.cv);
+                const double r = w * lreff[t];
+                if (r != 0.0) {
+                    p1 += r * ld2[t];
+                    p2 += r * ls2[t];
+                    p3 += w;
+                }
+            }
+        __syncthreads();
+    }
+    if (tid >= kx) return;
+    const size_t at = (size_t)tid * ncol + col, plane = (size_t)kx * ncol;
+    const double rho = a.rho[at];
+    double out = rho;
+    if (p3 > 0.0 && p2 > 0.0) {
+        const double ro = (p1 - p3) / p2;
+        const double t = (rho * p2 + p3) / p2;
+        const double vo = (2.0 / p3) * (t * t);
+        const double g = a.vb / (vo + a.vb);
+        const double est = rho + g * (ro - rho);
+        // fmin and fmax drop a NaN, so the estimate is tested before the bounds: a non-finite one leaves rho as it is
+        if (__builtin_isfinite(est)) out =fmin(fmax(est, a.rho_min), a.rho_max);
+    }
+    a.rho[at] = out;
+    a.parm[at] = p1;
+    a.parm[plane + at] = p2;
+    a.parm[2 * plane + at] = p3;
+}
+
 }  // namespace
 
 size_t letkf_lds_bytes(int nmem, int kx, int nlv) { return sizeof(double) * (size_t)LetkfLds((nmem + 1) & ~1, kx, nlv).total; }
@@ -699,10 +806,14 @@ hipError_t letkf_prepare(size_t lds)
 {
     constexpr size_t whole = 160 * 1024;
     if (lds > whole) return hipErrorInvalidValue;
-    const void *const forms[4] = {reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfCols>),
+    const void *const forms[8] = {reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfCols>),
                                   reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfCols>),
                                   reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfMaskedCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfMaskedCols>)};
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfMaskedCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfAdaptiveCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfAdaptiveCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfAdaptiveMaskedCols>),
+                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfAdaptiveMaskedCols>)};
     for (const void *f : forms)
         if (const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole)) return rc;
     return hipSuccess;
@@ -823,6 +934,38 @@ hipError_t launch_letkf_transform_masked(const LetkfMaskedCols &a, size_t lds, h
         hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfMaskedCols>), dim3(a.c.nlist), dim3(LETKF_BLOCK), lds, s, a);
     else
         hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfMaskedCols>), dim3(a.c.ncol), dim3(LETKF_BLOCK), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_letkf_transform_adaptive(const LetkfCols &c, const double *rho, const int *umap, size_t lds, hipStream_t s)
+{
+    bool list = false;
+    if (!rho) return hipErrorInvalidValue;
+    if (const hipError_t rc = transform_ready(c, lds, &list)) return rc;
+    const dim3 grid(list ? c.nlist : c.ncol), block(LETKF_BLOCK);
+    if (umap) {
+        const LetkfAdaptiveMaskedCols a{c, rho, umap};
+        if (list) hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfAdaptiveMaskedCols>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfAdaptiveMaskedCols>), grid, block, lds, s, a);
+    } else {
+        const LetkfAdaptiveCols a{c, rho};
+        if (list) hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfAdaptiveCols>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfAdaptiveCols>), grid, block, lds, s, a);
+    }
+    return hipGetLastError();
+}
+
+// both launches of the estimate; an empty network still gets both (the first with one idle workgroup): the node count is fixed
+hipError_t launch_letkf_infl(const LetkfInfl &a, hipStream_t s)
+{
+    if (a.nobs < 0 || a.nmem < 2 || a.nmem > LETKF_MAX_MEMBERS || a.kx < 1 || a.kx > LETKF_MAX_KX || a.ncol < 1 || !(a.ch > 0.0) ||
+        !(a.vb >= 0.0) || !(a.rho_min > 0.0) || !(a.rho_max >= a.rho_min) || !a.colunit || !a.lnfsg || !a.s2 || !a.rho || !a.parm)
+        return hipErrorInvalidValue;
+    if (a.nobs && (!a.ounit || !a.olns || !a.reff || !a.y || !a.dep)) return hipErrorInvalidValue;
+    const int nb = a.nobs ? (a.nobs + LETKF_BLOCK - 1) / LETKF_BLOCK : 1;
+    hipLaunchKernelGGL(letkf_infl_obs_kernel, dim3(nb), dim3(LETKF_BLOCK), 0, s, a);
+    if (const hipError_t rc = hipGetLastError()) return rc;
+    hipLaunchKernelGGL(letkf_infl_kernel, dim3(a.ncol), dim3(LETKF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

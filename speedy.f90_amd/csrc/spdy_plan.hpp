@@ -244,10 +244,21 @@ struct spdy_letkf final : spdy_detail::PlanObject {
         v(d_qc_stats, M ? (size_t)SPDY_QC_SLOTS * SPDY_QC_MAX_GROUPS * spdy::QC_STATS : 0); v(d_qc_check, M); v(d_qc_depb, M);
         v(d_qc_group, M);
     }
+    // adaptive inflation (spdy_infl_set, spdy_infl_fill): read when an analysis is enqueued; off: the analysis launches what it
+    // always did and the scalar rho above is the transform's.  The block is an allocation of its own, made by the first "on" (or
+    // by asking spdy_letkf_field for one of its names) and kept from then on (a captured graph may point into it): d_rho [kx][ncol]
+    // the field, filled with the scalar rho of that moment; d_infl_parm [3][kx][ncol] p1, p2, p3 of the latest call; d_obs_s2 [max_obs]
+    bool infl_on = false;
+    double infl_sigma_b = 0.0, infl_min = 0.0, infl_max = 0.0;
+    double *d_rho = nullptr, *d_infl_parm = nullptr, *d_obs_s2 = nullptr;
+    template <class V> void infl_arrays(V &&v, size_t ncol = 0, size_t kx = 0, size_t M = 0)
+    {
+        v(d_rho, kx * ncol); v(d_infl_parm, 3 * kx * ncol); v(d_obs_s2, M);
+    }
     void forget_device() override
     {
         arrays(spdy_detail::Carve{}); interp_arrays(spdy_detail::Carve{}); relax_arrays(spdy_detail::Carve{});
-        qc_arrays(spdy_detail::Carve{});
+        qc_arrays(spdy_detail::Carve{}); infl_arrays(spdy_detail::Carve{});
     }
 };
 

@@ -1289,6 +1289,20 @@ module spdy_c
             integer(c_int), value :: slot
             integer(c_int) :: rc
         end function
+        ! adaptive inflation (include/spdy.h): on /= 0 switches the field rho[kx][ncol] on in the scalar rho's place
+        function spdy_infl_set(l, on, sigma_b, rho_min, rho_max) bind(C, name="spdy_infl_set") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: l
+            integer(c_int), value :: on
+            real(c_double), value :: sigma_b, rho_min, rho_max
+            integer(c_int) :: rc
+        end function
+        function spdy_infl_fill(l, rho0) bind(C, name="spdy_infl_fill") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: l
+            real(c_double), value :: rho0
+            integer(c_int) :: rc
+        end function
         function spdy_letkf_table(l, name, buf, cap) bind(C, name="spdy_letkf_table") result(rc)
             import :: c_int, c_ptr, c_char
             type(c_ptr), value :: l, buf

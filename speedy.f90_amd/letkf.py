@@ -16,7 +16,8 @@ forecast takes each member's H x_e at the slot's own time, Ensemble.analyse(letk
 the 4D-LETKF (include/spdy.h, "observations in time slots").  set_background_check(gross) tests every departure
 against spread plus error before the local analyses read it and keeps the counts and sums of an innovation table per group of
 observations, one launch more; obs_stats() downloads them (include/spdy.h, "background check and observation statistics";
-DESIGN.md s27)."""
+DESIGN.md s27).  set_adaptive_inflation() replaces the scalar rho by a field per level and column that every analysis reads
+and then advances from its own innovation statistics, two launches more (include/spdy.h, "adaptive inflation")."""
 import ctypes
 
 import numpy as np
@@ -30,7 +31,7 @@ OBS_AT_P = -1                         # SPDY_OBS_AT_P: as lev, the observation s
 _TABLES = {"stencil_index": (np.int64, (-1, 4)), "stencil_weight": (np.float64, (-1, 4)), "unit": (np.float64, (-1, 3)),
            "lnsigma": (np.float64, (-1,)), "rinv": (np.float64, (-1,)), "coarse_columns": (np.int64, (-1,)),
            "interp_index": (np.int64, (-1, 4)), "interp_weight": (np.float64, (-1, 4)), "lnp": (np.float64, (-1,)),
-           "slot_first": (np.int64, (-1,))}
+           "adaptive_inflation": (np.float64, (-1,)), "slot_first": (np.int64, (-1,))}
 _PER_OBS, _PER_OBS_MEMBER = (lambda l: (l.nobs,)), (lambda l: (l.nobs, l.nmem))
 # device field -> the shape of a Letkf's, all float64
 _FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "departure": _PER_OBS,
@@ -38,7 +39,9 @@ _FIELDS = {"hx": _PER_OBS_MEMBER, "hxmean": _PER_OBS, "y": _PER_OBS_MEMBER, "dep
            "value": _PER_OBS, "grid": lambda l: ((4 * l.sp.kx + 1) * l.nmem,) + l.sp.grid_shape,
            "obs_lnsigma": _PER_OBS, "obs_used": _PER_OBS, "members_used": lambda l: (1,),
            "inflation": lambda l: (4 * l.sp.kx + 1,) + l.sp.grid_shape, "obs_check": _PER_OBS, "obs_rinv": _PER_OBS,
-           "obs_stats": lambda l: (QC_SLOTS, QC_MAX_GROUPS, len(QC_COLUMNS)), "slot_ps": _PER_OBS_MEMBER, "slot_out": _PER_OBS_MEMBER}
+           "obs_stats": lambda l: (QC_SLOTS, QC_MAX_GROUPS, len(QC_COLUMNS)),
+           "rho": lambda l: (l.sp.kx,) + l.sp.grid_shape, "infl_parm": lambda l: (3, l.sp.kx) + l.sp.grid_shape, "obs_s2": _PER_OBS,
+           "slot_ps": _PER_OBS_MEMBER, "slot_out": _PER_OBS_MEMBER}
 LETKF_TABLES, LETKF_FIELDS = tuple(_TABLES), tuple(_FIELDS)
 QC_MAX_GROUPS, QC_SLOTS = 64, 4       # SPDY_QC_MAX_GROUPS, SPDY_QC_SLOTS
 # the ten numbers of a group's row of the statistics, in the header's order
@@ -81,12 +84,13 @@ class _DeviceView:
 class Letkf(PlanObject):
     """sigma_h: horizontal localisation scale in metres; sigma_v: vertical scale in ln sigma (<= 0: none); rho: multiplicative
     inflation of the background covariance; weight_stride: set_weight_stride; rtpp, rtps: set_relaxation; gross, groups:
-    set_background_check (groups needs observations, so here it must be None unless max_obs == 0).  2 <= nmem <= 32; the plan needs
+    set_background_check (groups needs observations, so here it must be None unless max_obs == 0); adaptive: False, True
+    (set_adaptive_inflation with its defaults) or a dict of its arguments.  2 <= nmem <= 32; the plan needs
     max_batch >= nmem (2 kx + 1)."""
     PREFIX = "spdy_letkf"
 
     def __init__(self, sp, nmem, max_obs, sigma_h, sigma_v=0.0, rho=1.0, weight_stride=(1, 1), rtpp=0.0, rtps=0.0, gross=0.0,
-                 groups=None):
+                 groups=None, adaptive=False):
         self.sp, self.lib = sp, sp.lib
         if sp.device >= 0:
             sp._sync_stream()
@@ -104,6 +108,40 @@ class Letkf(PlanObject):
         self.gross, self.ngroups, self.stats_slot = 0.0, 5, 0
         if gross != 0.0 or groups is not None:
             self.set_background_check(gross, groups)
+        self.adaptive = None
+        if adaptive:
+            self.set_adaptive_inflation(**(adaptive if isinstance(adaptive, dict) else {}))
+
+    def set_adaptive_inflation(self, sigma_b=0.04, rho_min=0.9, rho_max=3.0, on=True):
+        """Adaptive inflation (include/spdy.h, "adaptive inflation"): the analysis reads a field rho [kx, il, ix]
+        in the scalar rho's place and every analysis call then advances it from its own innovation statistics, two launches more,
+        last.  sigma_b (finite, >= 0): the standard deviation given to the prior rho, 0.04 as in Miyoshi (2011): with a few hundred
+        effective observations the field moves a few per cent of the way to the observed value per analysis; 0 freezes the field.
+        rho_min, rho_max (0 < rho_min <= rho_max): the estimate is a ratio of noisy sums, so it is kept in a range -- by default
+        [0.9, 3.0]: a little deflation is allowed, since an estimate that may not go below 1 is biased upwards wherever the true
+        value is 1, and 3.0 (1.7 in spread) bounds what a run of unrepresentative departures can do before the next analyses
+        bring it back.  on=False: the scalar rho again; the field is kept.  The first on=True allocates the field, filled with the
+        object's scalar rho: it synchronises the plan's stream and is not possible inside a capture; later settings only change
+        the numbers, read when an analysis is enqueued.  self.adaptive: (sigma_b, rho_min, rho_max), or None while off."""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        rc = self.lib.spdy_infl_set(self.h, 1 if on else 0, float(sigma_b), float(rho_min), float(rho_max))
+        if rc == ERR_HIP:             # the allocation failed: the object is left off
+            self.adaptive = None
+        check(rc)
+        self.adaptive = (float(sigma_b), float(rho_min), float(rho_max)) if on else None
+
+    def fill_inflation(self, rho0):
+        """The field rho set to rho0 (finite, > 0) everywhere (spdy_infl_fill); allocates it if need be and leaves adaptive
+        inflation as it is, on or off.  Synchronises the plan's stream; not inside a capture."""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        check(self.lib.spdy_infl_fill(self.h, float(rho0)))
+
+    def inflation_field(self):
+        """field("rho"): the inflation field [kx, il, ix] in the object's own memory, writable -- upload() sets any field, numpy()
+        saves one for a restart.  Valid on every object of a device plan (asking makes the block; not inside a capture)."""
+        return self.field("rho")
 
     def set_background_check(self, gross=0.0, groups=None, slot=0):
         """The background check and the observation statistics (include/spdy.h, "background check and observation statistics";
@@ -306,7 +344,10 @@ class Letkf(PlanObject):
         check on; obs_stats [4, 64, 10]: the statistics' table (obs_stats() names its columns); both zero until then (asking for
         one before set_background_check has made their block makes it: not inside a capture).  obs_rinv [nobs]: the per-call copy of 1/error^2 the local analyses read,
         exactly 0 for an observation that took no part; written by an analysis of a network with observations at a pressure or
-        with the background check on."""
+        with the background check on.  rho [kx, il, ix]: the field of adaptive inflation, which the next analysis call reads
+        and then advances (writable); infl_parm [3, kx, il, ix]: the sums p1, p2, p3 of the latest adaptive call; obs_s2 [nobs]: the
+        ensemble variance at every observation in that call; all three are of one block that asking for any of them makes (not
+        inside a capture), adaptive inflation stays off then."""
         p = ctypes.c_void_p()
         check(self.lib.spdy_letkf_field(self.h, name.encode(), ctypes.byref(p)))
         return DeviceField(self.sp, p.value, _FIELDS[name](self))

@@ -65,6 +65,9 @@ analysis checked" replays Letkf.analyse_grid of both objects on one gridded ense
 work the rejected observations take out of the transform; "checked none rejected" is the same launch at a threshold nothing
 exceeds, its difference the check's launch alone.
 
+--adaptive adds the analysis of the same network by an object with adaptive inflation on (include/spdy.h, "adaptive inflation";
+DESIGN.md s28): two launches more, last.  As with --relax, the pair "grid analysis" / "grid analysis adaptive" on one gridded ensemble
+is the one whose difference is the feature's own cost.
 --osse measures what a twin experiment adds to that cycle (include/spdy.h, "nature run"), in the --letkf set-up and next
 to its two graphs: (a) the captured {Nature.set_state, Nature.observe} -- the truth to the grid and the 13 728 values drawn from it,
 three launches; (b) the captured Ensemble.verify -- the inverse batch of all members and the two score launches; (c) the host route
@@ -93,6 +96,7 @@ float32 grids written; and the surface-pressure row.
     python tools/ensemble_rate.py --letkf --slots 6 --at-pressure --json profiles/ensemble_letkf_slots_rate.json
     python tools/ensemble_rate.py --letkf --relax 0 0.9 --json profiles/ensemble_letkf_relax_rate.json
     python tools/ensemble_rate.py --letkf --qc --json profiles/ensemble_letkf_qc_rate.json
+    python tools/ensemble_rate.py --letkf --adaptive --json profiles/ensemble_letkf_infl_rate.json
     SPDY_LIB=/path/to/earlier/libspdy.so python tools/ensemble_rate.py --letkf --earlier-library --label parent
     python tools/ensemble_rate.py --osse --json profiles/ensemble_osse_rate.json
     python tools/ensemble_rate.py --pressure --json profiles/ensemble_pressure_rate.json
@@ -591,14 +595,15 @@ def host_observations(sp, lt, tr, cols, err, repeats):
 
 
 def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=False, at_pressure=False, masks=(), relax=None, slots=0,
-              qc=None):
+              qc=None, adaptive=False):
     """graph replays of the ensemble analysis and of the ensemble step with the physics (36 of them: one six-hour cycle); osse: and
     of the nature run's observe and verify, and the host route to the same observation values; at_pressure: and of the analysis of
     the same stations with u, v, t, q given at the pressures p0 fsg[k] (Letkf.set_obs(p=...)), values and errors unchanged; relax
     = (rtpp, rtps): and of the analysis of the same network by an object with that relaxation on; slots = S: and, with the network
     divided into S equal time slots, of one slot's Ensemble.observe and of the slot analysis, next to the plain analysis of the same
     object (with at_pressure also for that object); qc = gross: and of the analysis of the same network by an object with the
-    background check on at that threshold"""
+    background check on at that threshold; adaptive: and of the analysis of the same network by an object with adaptive inflation
+    on (Letkf.set_adaptive_inflation's defaults): two launches more"""
     import ensemblestep
     from oracle.pyoracle import Oracle, build
     build()
@@ -758,6 +763,31 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
                     gg.launch()
                     torch.cuda.synchronize()
                     rejected["%s" % name] = int(obj.obs_stats()["n_rej"].sum())
+        if adaptive:
+            lta = s.Letkf(sp, E, nobs, 5.0e5, 0.1, 1.1, adaptive=True, **({} if stride == (1, 1) else {"weight_stride": stride}))
+            lta.set_obs(*cols, lt.field("value").numpy(), spread)
+            with sp.graph_capture() as ga:
+                en.analyse(lta)
+            fns["analysis adaptive E=%d" % E], nodes["analysis adaptive E=%d" % E] = ga.launch, ga.num_nodes()
+            pressure_objects.append((lta, ga))
+            # Replays of Ensemble.analyse analyse the state the replay before left, and the field moves from replay to replay: the
+            # two graphs above solve different eigenproblems.  What the two launches and the per-item diagonal add is the
+            # difference of Letkf.analyse_grid on ONE gridded ensemble, the start state's, which every replay reads again
+            nat = s.Nature(sp, capacity=1)
+            en.verify(lta, nat, 0)
+            torch.cuda.synchronize()
+            grid = torch.from_numpy(lta.field("grid").numpy()).cuda()
+            L = E * kx
+            xs = [grid[v * L:(v + 1) * L].reshape((E, kx) + sp.grid_shape) for v in range(4)] + [grid[4 * L:]]
+            out = [torch.empty_like(a) for a in xs]
+            nat.close()
+            for name, obj in (("grid analysis E=%d" % E, lt), ("grid analysis adaptive E=%d" % E, lta)):
+                if name in fns:
+                    continue
+                with sp.graph_capture() as gg:
+                    obj.analyse_grid(*xs, out=out)
+                fns[name], nodes[name] = gg.launch, gg.num_nodes()
+                mask_objects.append(((xs, out), gg))
         if stride != (1, 1):
             terms = int(np.count_nonzero(lt.table("interp_weight")))
             interp[E] = {"coarse_columns": int(lt.table("coarse_columns").size),
@@ -813,6 +843,9 @@ def run_letkf(tag, members, reps, repeats, label, rows, stride=(1, 1), osse=Fals
             row.update(gross=qc, us_over_unchecked=round(med - t[plain][0], 2), check_read_bytes=8 * nobs * (E + 3) + 4 * nobs)
             if name in rejected:
                 row.update(rejected=rejected[name])
+        if "adaptive" in name:
+            # next to the same call with the scalar rho: the difference of two graph replays
+            row.update(us_over_scalar_rho=round(med - t[name.replace(" adaptive", "")][0], 2))
         if name.startswith("grid analysis slots"):
             row.update(slots=slots, us_over_plain=round(med - t[name.replace("grid analysis slots", "grid analysis plain")][0], 2))
         if name.startswith("slot observe"):
@@ -852,6 +885,7 @@ def main():
     ap.add_argument("--pressure", action="store_true")
     ap.add_argument("--relax", nargs=2, type=float, metavar=("RTPP", "RTPS"))
     ap.add_argument("--qc", nargs="?", type=float, const=5.0, metavar="GROSS")
+    ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--stride", nargs=2, type=int, default=[1, 1], metavar=("SI", "SJ"))
     ap.add_argument("--earlier-library", action="store_true")
     ap.add_argument("--label", default="this build")
@@ -875,7 +909,7 @@ def main():
         for tag in a.sizes:
             if a.letkf:
                 run_letkf(tag, a.members, a.reps, a.repeats, a.label, rows, tuple(a.stride), a.osse, a.at_pressure, a.mask,
-                          tuple(a.relax) if a.relax else None, a.slots, a.qc)
+                          tuple(a.relax) if a.relax else None, a.slots, a.qc, a.adaptive)
             elif a.pressure:
                 run_pressure(tag, a.members, a.reps, a.repeats, a.label, rows)
             elif a.sppt:
