@@ -54,6 +54,48 @@ int upload(spdy_plan *p, void *dst, const void *src, size_t bytes)
     return SPDY_OK;
 }
 
+// An optional allocation of an object's, made once: carved by `arrays` (one of the object's *_arrays visitors with its sizes; base:
+// the first array), zeroed, so that no call ever reads what it did not write, then the caller's uploads and one synchronisation.
+// On any failure: synchronise -- no copy still reads a host array when the caller's go out of scope --, release, forget the
+// pointers, the code: nothing is left.  The caller has checked that no capture is open
+template <class T, class ARRAYS, class UPLOADS>
+int optional_block(spdy_plan *p, T *&base, ARRAYS &&arrays, UPLOADS &&uploads)
+{
+    size_t bytes = 0;
+    auto all = [&]() -> int {
+        RC(dev_carve(p, arrays, &bytes));
+        HIP_TRY(hipMemsetAsync(base, 0, bytes, p->stream));
+        RC(uploads());
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return SPDY_OK;
+    };
+    const int rc = all();
+    if (rc) {
+        (void)hipStreamSynchronize(p->stream);
+        (void)dev_release(p, base);
+        arrays(Carve{});
+    }
+    return rc;
+}
+const auto no_uploads = []() -> int { return SPDY_OK; };
+
+// the object's grid workspace as the five fields of a gridded ensemble: u | v | t | q (nmem kx grids each, member-major) | ps
+void grid_workspace(spdy_letkf *l, double **x)
+{
+    const size_t L = (size_t)l->nmem * l->plan->tab.kx * grid_elems(l->plan);
+    for (int v = 0; v < spdy::LETKF_VARS; ++v) x[v] = l->d_grid + (size_t)v * L;
+}
+
+// d_use: NULL, or the member mask -- one launch in front, which builds the table the masked forms of the kernels read (*umap: that
+// table, or NULL); the object remembers which kind of call was enqueued last
+int mask_table(spdy_letkf *l, const int *d_use, const int **umap)
+{
+    if (d_use) KERNEL(spdy::launch_letkf_mask(d_use, l->nmem, l->d_umap, l->d_nused + 1, l->plan->stream));
+    l->masked_last = d_use != nullptr;
+    *umap = d_use ? l->d_umap : nullptr;
+    return SPDY_OK;
+}
+
 // the argument checks the analysis calls share, in the documented order; slots: a slot analysis, which needs before the device
 // every non-empty slot observed since the latest spdy_slot_set; the device last
 int analysis_ready(spdy_letkf *l, bool ptrs_ok, bool slots)
@@ -124,15 +166,13 @@ int check_obs(spdy_letkf *l, const int *umap, bool decide, int slot)
     return SPDY_OK;
 }
 
-// d_use: NULL, or the member mask -- one launch more in front, which builds the table the masked forms of the kernels read.
-// slots: the finish kernel of "observations in time slots" in the observation kernel's place, everything else as it is.
+// d_use: mask_table's.  slots: the finish kernel of "observations in time slots" in the observation kernel's place, everything else as it is.
 // The observation stage's argument is filled once (observe_args); one branch: observe now, or finish what the slots kept
 int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const int *d_use = nullptr, bool slots = false)
 {
     spdy_plan *p = l->plan;
-    const int *const umap = d_use ? l->d_umap : nullptr;
-    if (d_use) KERNEL(spdy::launch_letkf_mask(d_use, l->nmem, l->d_umap, l->d_nused + 1, p->stream));
-    l->masked_last = d_use != nullptr;
+    const int *umap = nullptr;
+    RC(mask_table(l, d_use, &umap));
     const int kx = p->tab.kx, ncol = (int)grid_elems(p);
     spdy::LetkfObserve o = observe_args(l, x, 0, l->nobs);
     o.umap = umap;
@@ -178,13 +218,7 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
     const bool adaptive = l->infl_on;
     if (adaptive && !l->d_rho) return fail(SPDY_ERR_STATE, "letkf: adaptive inflation is on without its block");
     auto transform = [&]() -> int {
-        if (adaptive) {
-            KERNEL(spdy::launch_letkf_transform_adaptive(c, l->d_rho, umap, l->lds, p->stream));
-        } else if (umap) {
-            KERNEL(spdy::launch_letkf_transform_masked(spdy::LetkfMaskedCols{c, l->rho, umap}, l->lds, p->stream));
-        } else {
-            KERNEL(spdy::launch_letkf_transform(c, l->lds, p->stream));
-        }
+        KERNEL(spdy::launch_letkf_transform(c, l->rho, adaptive ? l->d_rho : nullptr, umap, l->lds, p->stream));
         return SPDY_OK;
     };
     auto finish = [&]() -> int {
@@ -214,49 +248,22 @@ int analyse_grid(spdy_letkf *l, const double *const *x, double *const *dx, const
 }
 
 // the block of adaptive inflation of a device plan's object, made once: the field filled with the object's scalar rho, the sums
-// and s2 zeroed.  The caller has checked that no capture is open; a failure leaves no block
+// and s2 zero
 int infl_block(spdy_letkf *l)
 {
     if (l->d_rho) return SPDY_OK;
     spdy_plan *p = l->plan;
     const size_t n = (size_t)p->tab.kx * grid_elems(p);
     const std::vector<double> fill(n, l->rho);
-    size_t bytes = 0;
-    auto all = [&]() -> int {
-        RC(dev_carve(p, [&](auto &&v) { l->infl_arrays(v, grid_elems(p), (size_t)p->tab.kx, (size_t)(l->max_obs > 0 ? l->max_obs : 1)); }, &bytes));
-        HIP_TRY(hipMemsetAsync(l->d_rho, 0, bytes, p->stream));
-        RC(upload(p, l->d_rho, fill.data(), n * sizeof(double)));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return SPDY_OK;
-    };
-    if (const int rc = all()) {
-        (void)hipStreamSynchronize(p->stream);        // no copy is still reading the host array when it goes
-        (void)dev_release(p, l->d_rho);
-        l->infl_arrays(Carve{});
-        return rc;
-    }
-    return SPDY_OK;
+    return optional_block(p, l->d_rho, [&](auto &&v) { l->infl_arrays(v, grid_elems(p), (size_t)p->tab.kx, (size_t)(l->max_obs > 0 ? l->max_obs : 1)); },
+                          [&]() -> int { return upload(p, l->d_rho, fill.data(), n * sizeof(double)); });
 }
 
-// the qc block of a device plan's object, made once: the statistics, the record, the kept departure and the grouping, zeroed so that
-// no call ever reads what it did not write.  The caller has checked that no capture is open; a failure leaves no block
+// the qc block of a device plan's object, made once: the statistics, the record, the kept departure and the grouping
 int qc_block(spdy_letkf *l)
 {
     if (l->d_qc_stats) return SPDY_OK;
-    spdy_plan *p = l->plan;
-    size_t bytes = 0;
-    auto all = [&]() -> int {
-        RC(dev_carve(p, [&](auto &&v) { l->qc_arrays(v, (size_t)(l->max_obs > 0 ? l->max_obs : 1)); }, &bytes));
-        HIP_TRY(hipMemsetAsync(l->d_qc_stats, 0, bytes, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return SPDY_OK;
-    };
-    if (const int rc = all()) {
-        (void)dev_release(p, l->d_qc_stats);
-        l->qc_arrays(Carve{});
-        return rc;
-    }
-    return SPDY_OK;
+    return optional_block(l->plan, l->d_qc_stats, [&](auto &&v) { l->qc_arrays(v, (size_t)(l->max_obs > 0 ? l->max_obs : 1)); }, no_uploads);
 }
 
 // the stats-only calls' checks in the documented order, the device last
@@ -275,13 +282,11 @@ int stats_ready(spdy_letkf *l, bool ptrs_ok, int slot)
 // in the mode that decides nothing
 int stats_grid(spdy_letkf *l, const double *const *x, const int *d_use, int slot)
 {
-    spdy_plan *p = l->plan;
-    const int *const umap = d_use ? l->d_umap : nullptr;
-    if (d_use) KERNEL(spdy::launch_letkf_mask(d_use, l->nmem, l->d_umap, l->d_nused + 1, p->stream));
-    l->masked_last = d_use != nullptr;
+    const int *umap = nullptr;
+    RC(mask_table(l, d_use, &umap));
     spdy::LetkfObserve o = observe_args(l, x, 0, l->nobs);
     o.umap = umap;
-    KERNEL(spdy::launch_letkf_observe(o, p->stream));
+    KERNEL(spdy::launch_letkf_observe(o, l->plan->stream));
     return check_obs(l, umap, false, slot);
 }
 
@@ -531,19 +536,10 @@ int spdy_relax_set(spdy_letkf *l, double rtpp, double rtps)
     if (!(rtps >= 0.0 && rtps <= 1.0)) return fail(SPDY_ERR_ARG, "relax_set: rtps must lie in [0, 1]");
     spdy_plan *p = l->plan;
     if ((rtpp != 0.0 || rtps != 0.0) && p->device >= 0 && !l->d_raw) {
-        // the first non-zero setting: the workspace of the raw increments, zeroed once so that no call ever reads what it did not write
+        // the first non-zero setting: the workspace of the raw increments
         NOT_CAPTURING(p, "spdy_relax_set (allocation)");
         HIP_TRY(hipSetDevice(p->device));
-        size_t bytes = 0;
-        auto all = [&]() -> int {
-            RC(dev_carve(p, [&](auto &&v) { l->relax_arrays(v, grid_elems(p), (size_t)p->tab.kx); }, &bytes));
-            HIP_TRY(hipMemsetAsync(l->d_raw, 0, bytes, p->stream));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            return SPDY_OK;
-        };
-        if (const int rc = all()) {
-            (void)dev_release(p, l->d_raw);
-            l->relax_arrays(Carve{});
+        if (const int rc = optional_block(p, l->d_raw, [&](auto &&v) { l->relax_arrays(v, grid_elems(p), (size_t)p->tab.kx); }, no_uploads)) {
             l->rtpp = l->rtps = 0.0;              // the object is left at (0, 0)
             return rc;
         }
@@ -575,20 +571,12 @@ int spdy_letkf_set_weight_stride(spdy_letkf *l, int si, int sj)
     spdy_letkf::InterpTables tab = interp_tables(ix, il, si, sj);
     if (p->device >= 0) {
         HIP_TRY(hipSetDevice(p->device));
-        const size_t nc = tab.coarse.size(), ncol = grid_elems(p), ntw = nc * kx * l->nmem * l->nmem;
-        RC(dev_carve(p, [&](auto &&v) { l->interp_arrays(v, nc, ncol, kx); }));
-        auto all = [&]() -> int {
-            HIP_TRY(hipMemsetAsync(l->d_tw, 0, ntw * sizeof(double), p->stream));
+        const size_t nc = tab.coarse.size(), ncol = grid_elems(p);
+        RC(optional_block(p, l->d_tw, [&](auto &&v) { l->interp_arrays(v, nc, ncol, kx); }, [&]() -> int {
             RC(upload(p, l->d_iwgt, tab.iwgt.data(), 4 * ncol * sizeof(double)));
             RC(upload(p, l->d_iidx, tab.iidx.data(), 4 * ncol * sizeof(int)));
-            RC(upload(p, l->d_coarse, tab.coarse.data(), nc * sizeof(int)));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            return SPDY_OK;
-        };
-        if (const int rc = all()) {
-            drop_interp(l);                   // back at stride (1, 1); no copy is still reading the host arrays when they go
-            return rc;
-        }
+            return upload(p, l->d_coarse, tab.coarse.data(), nc * sizeof(int));
+        }));                                  // a failure leaves the object at stride (1, 1), where drop_interp has put it
     }
     l->si = si; l->sj = sj;
     l->interp = std::move(tab);
@@ -705,11 +693,9 @@ int spdy_slot_observe_dev(spdy_letkf *l, int slot, const double *vor, const doub
         l->slot_observed[slot] = true;
         return SPDY_OK;
     }
-    spdy_plan *p = l->plan;
-    const size_t L = (size_t)l->nmem * p->tab.kx * grid_elems(p);
-    double *g = l->d_grid;
-    RC(ens_to_grid(p, l->nmem, vor, div, t, q, ps, g));
-    const double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
+    RC(ens_to_grid(l->plan, l->nmem, vor, div, t, q, ps, l->d_grid));
+    double *x[spdy::LETKF_VARS];
+    grid_workspace(l, x);
     return observe_grid(l, slot, x);
 }
 
@@ -827,11 +813,9 @@ int spdy_qc_stats_dev(spdy_letkf *l, const double *vor, const double *div, const
                       const int *d_use, int slot)
 {
     RC(stats_ready(l, vor && div && t && q && ps, slot));
-    spdy_plan *p = l->plan;
-    const size_t L = (size_t)l->nmem * p->tab.kx * grid_elems(p);
-    double *g = l->d_grid;
-    RC(ens_to_grid(p, l->nmem, vor, div, t, q, ps, g));
-    const double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
+    RC(ens_to_grid(l->plan, l->nmem, vor, div, t, q, ps, l->d_grid));
+    double *x[spdy::LETKF_VARS];
+    grid_workspace(l, x);
     return stats_grid(l, x, d_use, slot);
 }
 
@@ -847,7 +831,8 @@ static int ens_analyse(spdy_letkf *l, double *vor, double *div, double *t, doubl
     double *g = l->d_grid, *s = l->d_spec;
     RC(ens_to_grid(p, nmem, vor, div, t, q, ps, g));
     // the increments take the place of the gridded ensemble
-    double *x[spdy::LETKF_VARS] = {g, g + L, g + 2 * L, g + 3 * L, g + 4 * L};
+    double *x[spdy::LETKF_VARS];
+    grid_workspace(l, x);
     RC(analyse_grid(l, x, x, d_use, slots));
     // vdspec(du, dv, 2) next to grid_to_spec(dt | dq | dps), then into the prognostics
     RC(spdy_direct_batch_dev(p, nk, g, g + L, s, s + LS, 2, 2 * nk + nmem, g + 2 * L, s + 2 * LS));

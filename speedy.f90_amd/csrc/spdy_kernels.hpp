@@ -584,8 +584,6 @@ struct LetkfMaskedCols {
     const int *umap;
 };
 size_t letkf_lds_bytes(int nmem, int kx, int nlv);
-hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s);
-hipError_t launch_letkf_transform_masked(const LetkfMaskedCols &a, size_t lds, hipStream_t s);
 hipError_t letkf_prepare(size_t lds);                // before the first launch on a device: admits a compute unit's whole LDS
 // The increments of every grid column from the transforms of a coarse set: per column a stencil of four list entries and their
 // weights (a zero weight: the entry is not read), T = ((w0 T0 + w1 T1) + w2 T2) + w3 T3 from the first term present, then
@@ -654,7 +652,9 @@ struct LetkfAdaptiveMaskedCols {
     const double *rho;
     const int *umap;
 };
-hipError_t launch_letkf_transform_adaptive(const LetkfCols &c, const double *rho, const int *umap, size_t lds, hipStream_t s);
+// The transform's one launcher: LetkfCols with the scalar rho (read by the masked form; c.diag has it for the plain one), under the
+// field `field` if not NULL, under the member mask's table umap if not NULL -- the kernel on the argument struct of that route.
+hipError_t launch_letkf_transform(const LetkfCols &c, double rho, const double *field, const int *umap, size_t lds, hipStream_t s);
 // The estimate, TWO launches after everything else of an analysis call: s2[o] of every observation, one thread each; then one
 // workgroup per grid column scans the network as the transform kernel does and lane k < kx sums p1, p2, p3 of level k over the
 // observations in range, ascending, updates rho[k][col] in place and stores parm [3][kx][ncol].  reff: the 1 / error^2 the call's

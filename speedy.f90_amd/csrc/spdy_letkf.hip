@@ -801,21 +801,25 @@ __global__ __launch_bounds__(LETKF_BLOCK) void letkf_infl_kernel(const LetkfInfl
 
 size_t letkf_lds_bytes(int nmem, int kx, int nlv) { return sizeof(double) * (size_t)LetkfLds((nmem + 1) & ~1, kx, nlv).total; }
 
+namespace {
+// The transform kernel's eight instantiations, named here and nowhere else: [adaptive][masked][list].  launch_letkf_transform picks
+// from the table and letkf_prepare walks it, so no form can be launched without its LDS attribute.
+#define SPDY_TRANSFORM_FORMS(ARGS)                                                                                     \
+    {reinterpret_cast<const void *>(letkf_transform_kernel<false, ARGS>), reinterpret_cast<const void *>(letkf_transform_kernel<true, ARGS>)}
+const void *const transform_forms[2][2][2] = {{SPDY_TRANSFORM_FORMS(LetkfCols), SPDY_TRANSFORM_FORMS(LetkfMaskedCols)},
+                                              {SPDY_TRANSFORM_FORMS(LetkfAdaptiveCols), SPDY_TRANSFORM_FORMS(LetkfAdaptiveMaskedCols)}};
+#undef SPDY_TRANSFORM_FORMS
+}  // namespace
+
 // the whole LDS of a compute unit, whatever this object needs: objects of other sizes launch the same kernel
 hipError_t letkf_prepare(size_t lds)
 {
     constexpr size_t whole = 160 * 1024;
     if (lds > whole) return hipErrorInvalidValue;
-    const void *const forms[8] = {reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfMaskedCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfMaskedCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfAdaptiveCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfAdaptiveCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<false, LetkfAdaptiveMaskedCols>),
-                                  reinterpret_cast<const void *>(letkf_transform_kernel<true, LetkfAdaptiveMaskedCols>)};
-    for (const void *f : forms)
-        if (const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole)) return rc;
+    for (const auto &adaptive : transform_forms)
+        for (const auto &masked : adaptive)
+            for (const void *f : masked)
+                if (const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole)) return rc;
     return hipSuccess;
 }
 
@@ -914,44 +918,19 @@ hipError_t transform_ready(const LetkfCols &a, size_t lds, bool *list)
 }
 }  // namespace
 
-hipError_t launch_letkf_transform(const LetkfCols &a, size_t lds, hipStream_t s)
+// One launch of the form the route names: field: adaptive inflation's, or NULL and the scalar rho holds (c.diag has it; the masked
+// form reads rho itself); umap: the member mask's table, or NULL.  Each form gets the argument struct it is instantiated on.
+hipError_t launch_letkf_transform(const LetkfCols &c, double rho, const double *field, const int *umap, size_t lds, hipStream_t s)
 {
     bool list = false;
-    if (const hipError_t rc = transform_ready(a, lds, &list)) return rc;
-    if (list)
-        hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfCols>), dim3(a.nlist), dim3(LETKF_BLOCK), lds, s, a);
-    else
-        hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfCols>), dim3(a.ncol), dim3(LETKF_BLOCK), lds, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_letkf_transform_masked(const LetkfMaskedCols &a, size_t lds, hipStream_t s)
-{
-    bool list = false;
-    if (!a.umap || !(a.rho > 0.0)) return hipErrorInvalidValue;
-    if (const hipError_t rc = transform_ready(a.c, lds, &list)) return rc;
-    if (list)
-        hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfMaskedCols>), dim3(a.c.nlist), dim3(LETKF_BLOCK), lds, s, a);
-    else
-        hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfMaskedCols>), dim3(a.c.ncol), dim3(LETKF_BLOCK), lds, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_letkf_transform_adaptive(const LetkfCols &c, const double *rho, const int *umap, size_t lds, hipStream_t s)
-{
-    bool list = false;
-    if (!rho) return hipErrorInvalidValue;
+    if (!field && umap && !(rho > 0.0)) return hipErrorInvalidValue;
     if (const hipError_t rc = transform_ready(c, lds, &list)) return rc;
-    const dim3 grid(list ? c.nlist : c.ncol), block(LETKF_BLOCK);
-    if (umap) {
-        const LetkfAdaptiveMaskedCols a{c, rho, umap};
-        if (list) hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfAdaptiveMaskedCols>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfAdaptiveMaskedCols>), grid, block, lds, s, a);
-    } else {
-        const LetkfAdaptiveCols a{c, rho};
-        if (list) hipLaunchKernelGGL((letkf_transform_kernel<true, LetkfAdaptiveCols>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((letkf_transform_kernel<false, LetkfAdaptiveCols>), grid, block, lds, s, a);
-    }
+    const LetkfMaskedCols m{c, rho, umap};
+    const LetkfAdaptiveCols a{c, field};
+    const LetkfAdaptiveMaskedCols am{c, field, umap};
+    const void *const arg[2][2] = {{&c, &m}, {&a, &am}};
+    void *args[1] = {const_cast<void *>(arg[field != nullptr][umap != nullptr])};
+    (void)hipLaunchKernel(transform_forms[field != nullptr][umap != nullptr][list], dim3(list ? c.nlist : c.ncol), dim3(LETKF_BLOCK), args, lds, s);
     return hipGetLastError();
 }
 

@@ -74,6 +74,13 @@ def use_mask(use, nmem, device):
     return use
 
 
+def _ptrs(tensors, use=False):
+    """The device pointers of five or ten tensors as an entry point's arguments.  use: False, the entry point takes no member mask;
+    otherwise its pointer goes last, NULL for None (all members)"""
+    p = [ctypes.c_void_p(a.data_ptr()) for a in tensors]
+    return p if use is False else p + [None if use is None else ctypes.c_void_p(use.data_ptr())]
+
+
 class _DeviceView:
     """a DeviceField of float64 as the array interface torch.as_tensor wraps without a copy"""
 
@@ -112,6 +119,27 @@ class Letkf(PlanObject):
         if adaptive:
             self.set_adaptive_inflation(**(adaptive if isinstance(adaptive, dict) else {}))
 
+    def _call(self, fn, *args, reset=None):
+        """One call of the library on this object, after whatever the caller's torch stream holds (the plan's stream synchronised
+        with it).  reset: the mirrored attributes as the library leaves the object where a setter's allocation or copy fails
+        (SPDY_ERR_HIP), set before the error is raised"""
+        if self.sp.device >= 0:
+            self.sp._sync_stream()
+        rc = fn(self.h, *args)
+        if rc == ERR_HIP and reset:
+            for name, value in reset.items():
+                setattr(self, name, value)
+        check(rc)
+
+    def _analyse(self, plain, masked, slotted, tensors, use, slots):
+        """the analysis entry point of the route: the slot call takes the mask or NULL, the plain call none"""
+        if slots:
+            self._call(slotted, *_ptrs(tensors, use))
+        elif use is None:
+            self._call(plain, *_ptrs(tensors))
+        else:
+            self._call(masked, *_ptrs(tensors, use))
+
     def set_adaptive_inflation(self, sigma_b=0.04, rho_min=0.9, rho_max=3.0, on=True):
         """Adaptive inflation (include/spdy.h, "adaptive inflation"): the analysis reads a field rho [kx, il, ix]
         in the scalar rho's place and every analysis call then advances it from its own innovation statistics, two launches more,
@@ -123,20 +151,14 @@ class Letkf(PlanObject):
         bring it back.  on=False: the scalar rho again; the field is kept.  The first on=True allocates the field, filled with the
         object's scalar rho: it synchronises the plan's stream and is not possible inside a capture; later settings only change
         the numbers, read when an analysis is enqueued.  self.adaptive: (sigma_b, rho_min, rho_max), or None while off."""
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        rc = self.lib.spdy_infl_set(self.h, 1 if on else 0, float(sigma_b), float(rho_min), float(rho_max))
-        if rc == ERR_HIP:             # the allocation failed: the object is left off
-            self.adaptive = None
-        check(rc)
+        self._call(self.lib.spdy_infl_set, 1 if on else 0, float(sigma_b), float(rho_min), float(rho_max),
+                   reset={"adaptive": None})                 # the allocation failed: the object is left off
         self.adaptive = (float(sigma_b), float(rho_min), float(rho_max)) if on else None
 
     def fill_inflation(self, rho0):
         """The field rho set to rho0 (finite, > 0) everywhere (spdy_infl_fill); allocates it if need be and leaves adaptive
         inflation as it is, on or off.  Synchronises the plan's stream; not inside a capture."""
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        check(self.lib.spdy_infl_fill(self.h, float(rho0)))
+        self._call(self.lib.spdy_infl_fill, float(rho0))
 
     def inflation_field(self):
         """field("rho"): the inflation field [kx, il, ix] in the object's own memory, writable -- upload() sets any field, numpy()
@@ -159,12 +181,8 @@ class Letkf(PlanObject):
                 raise ValueError("set_background_check: groups must be %d integers, one per observation" % self.nobs)
             n = int(g.max()) + 1 if g.size else 1
             table = (ctypes.c_int * max(g.shape[0], 1))(*[int(v) for v in g])
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        rc = self.lib.spdy_qc_set(self.h, float(gross), n, None if table is None else ctypes.cast(table, ctypes.c_void_p))
-        if rc == ERR_HIP:             # the object is left off
-            self.gross, self.ngroups = 0.0, 5
-        check(rc)
+        self._call(self.lib.spdy_qc_set, float(gross), n, None if table is None else ctypes.cast(table, ctypes.c_void_p),
+                   reset={"gross": 0.0, "ngroups": 5})         # the object is left off
         self.gross, self.ngroups = float(gross), n if table is not None else 5
         check(self.lib.spdy_qc_set_slot(self.h, int(slot)))
         self.stats_slot = int(slot)
@@ -186,19 +204,11 @@ class Letkf(PlanObject):
         and departure are overwritten, no state changes.  Two launches (three with use); capturable."""
         x = (ug, vg, tg, qg, psg)
         self._grids("stats_grid", x)
-        use = use_mask(use, self.nmem, self._device())
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        check(self.lib.spdy_qc_stats_grid_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in x],
-                                              None if use is None else ctypes.c_void_p(use.data_ptr()), int(slot)))
+        self._call(self.lib.spdy_qc_stats_grid_dev, *_ptrs(x, use_mask(use, self.nmem, self._device())), int(slot))
 
     def stats_dev(self, slot, vor, div, t, q, ps, use=None):
         """spdy_qc_stats_dev: stats_grid on time level 1 of an ensemble's spectra (Ensemble.obs_stats)."""
-        use = use_mask(use, self.nmem, self._device())
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        check(self.lib.spdy_qc_stats_dev(self.h, *[ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)],
-                                         None if use is None else ctypes.c_void_p(use.data_ptr()), int(slot)))
+        self._call(self.lib.spdy_qc_stats_dev, *_ptrs((vor, div, t, q, ps), use_mask(use, self.nmem, self._device())), int(slot))
 
     def set_relaxation(self, rtpp=0.0, rtps=0.0):
         """Relaxation of the analysis towards the background (include/spdy.h, "relaxation"), both in [0, 1]: rtpp
@@ -207,12 +217,8 @@ class Letkf(PlanObject):
         (0, 0), the default: none, the analysis is the one it always was.  Read when an analysis is enqueued: a captured analysis
         keeps the values of its capture.  The first setting other than (0, 0) allocates a workspace of (4 kx + 1) nmem grids: it
         synchronises the plan's stream and is not possible inside a capture; later settings only change the two numbers."""
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        rc = self.lib.spdy_relax_set(self.h, float(rtpp), float(rtps))
-        if rc == ERR_HIP:             # the allocation failed: the object is left at (0, 0)
-            self.relaxation = (0.0, 0.0)
-        check(rc)
+        self._call(self.lib.spdy_relax_set, float(rtpp), float(rtps),
+                   reset={"relaxation": (0.0, 0.0)})          # the allocation failed: the object is left at (0, 0)
         self.relaxation = (float(rtpp), float(rtps))
 
     def set_localization(self, sigma_h, sigma_v=0.0, rho=1.0):
@@ -225,12 +231,8 @@ class Letkf(PlanObject):
         transforms of the four coarse columns around it.  (1, 1): every column is solved, as without this call.  Builds and uploads
         the tables and allocates the weight buffer; synchronises the plan's stream; not inside a capture, and a graph captured
         before the call has to be captured again."""
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        rc = self.lib.spdy_letkf_set_weight_stride(self.h, int(si), int(sj))
-        if rc == ERR_HIP:             # the object is left at stride (1, 1)
-            self.weight_stride = (1, 1)
-        check(rc)
+        self._call(self.lib.spdy_letkf_set_weight_stride, int(si), int(sj),
+                   reset={"weight_stride": (1, 1)})            # the object is left at stride (1, 1)
         self.weight_stride = (int(si), int(sj))
 
     def set_obs(self, var, lev, lon, lat, value, error, p=None):
@@ -261,12 +263,8 @@ class Letkf(PlanObject):
                 obs[o] = PObs(int(cols[0][o]), int(cols[1][o]), float(cols[6][o]), float(cols[2][o]), float(cols[3][o]),
                               float(cols[4][o]), float(cols[5][o]))
             call = self.lib.spdy_pobs_set
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        rc = call(self.h, n, ctypes.cast(obs, ctypes.c_void_p))
-        if rc == ERR_HIP:             # a copy failed, the object holds no observations now
-            self.nobs, self.slots = 0, None
-        check(rc)
+        self._call(call, n, ctypes.cast(obs, ctypes.c_void_p),
+                   reset={"nobs": 0, "slots": None})           # a copy failed, the object holds no observations now
         self.nobs, self.slots, self.ngroups = n, None, 5
 
     def set_slots(self, first):
@@ -301,17 +299,13 @@ class Letkf(PlanObject):
         empty slot; capturable; nothing synchronises.  The analysis with slots=True then uses these rows."""
         x = (ug, vg, tg, qg, psg)
         self._grids("observe_grid", x)
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        check(self.lib.spdy_slot_observe_grid_dev(self.h, int(slot), *[ctypes.c_void_p(a.data_ptr()) for a in x]))
+        self._call(self.lib.spdy_slot_observe_grid_dev, int(slot), *_ptrs(x))
 
     def observe_dev(self, slot, vor, div, t, q, ps):
         """spdy_slot_observe_dev: observe_grid on time level 1 of an ensemble's spectra (Ensemble.observe): the analysis' inverse batch
         into the grid workspace -- field("grid") then holds the gridded ensemble of that time -- and the slot's launch.  Nothing of
         the ensemble changes; capturable; an empty slot enqueues nothing."""
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        check(self.lib.spdy_slot_observe_dev(self.h, int(slot), *[ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]))
+        self._call(self.lib.spdy_slot_observe_dev, int(slot), *_ptrs((vor, div, t, q, ps)))
 
     def table(self, name):
         """A host table of the current observations (LETKF_TABLES): stencil_index [nobs, 4] (grid points j*ix+i, int64),
@@ -388,15 +382,8 @@ class Letkf(PlanObject):
             raise ValueError("analyse_grid: out must hold five tensors")
         self._grids("analyse_grid", x)
         self._grids("analyse_grid", out)
-        if sp.device >= 0:
-            sp._sync_stream()
-        ptrs = [ctypes.c_void_p(a.data_ptr()) for a in x + tuple(out)]
-        if slots:
-            check(self.lib.spdy_slot_analyse_grid_dev(self.h, *ptrs, None if use is None else ctypes.c_void_p(use.data_ptr())))
-        elif use is None:
-            check(self.lib.spdy_letkf_analyse_grid_dev(self.h, *ptrs))
-        else:
-            check(self.lib.spdy_mask_letkf_analyse_grid_dev(self.h, *ptrs, ctypes.c_void_p(use.data_ptr())))
+        self._analyse(self.lib.spdy_letkf_analyse_grid_dev, self.lib.spdy_mask_letkf_analyse_grid_dev, self.lib.spdy_slot_analyse_grid_dev,
+                      x + tuple(out), use, slots)
         return tuple(out)
 
     def analyse_dev(self, vor, div, t, q, ps, use=None, slots=False):
@@ -404,13 +391,5 @@ class Letkf(PlanObject):
         use keep every bit (spdy_mask_ens_letkf_dev).  With relaxation on (set_relaxation) the increments are relaxed on the grid,
         one launch more, before they go back to spectra.  slots=True: the slot analysis (spdy_slot_ens_letkf_dev), as
         analyse_grid's; the launch count is that of the plain call."""
-        use = use_mask(use, self.nmem, self._device())
-        if self.sp.device >= 0:
-            self.sp._sync_stream()
-        ptrs = [ctypes.c_void_p(a.data_ptr()) for a in (vor, div, t, q, ps)]
-        if slots:
-            check(self.lib.spdy_slot_ens_letkf_dev(self.h, *ptrs, None if use is None else ctypes.c_void_p(use.data_ptr())))
-        elif use is None:
-            check(self.lib.spdy_ens_letkf_dev(self.h, *ptrs))
-        else:
-            check(self.lib.spdy_mask_ens_letkf_dev(self.h, *ptrs, ctypes.c_void_p(use.data_ptr())))
+        self._analyse(self.lib.spdy_ens_letkf_dev, self.lib.spdy_mask_ens_letkf_dev, self.lib.spdy_slot_ens_letkf_dev,
+                      (vor, div, t, q, ps), use_mask(use, self.nmem, self._device()), slots)

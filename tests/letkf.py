@@ -1,15 +1,30 @@
-"""The ensemble analysis restated in NumPy (include/spdy.h, "ensemble analysis"): the observation operator, the localisation
-weights, the local problem and the increments, exactly as the header defines them, with two routes for the eigenproblem --
-numpy.linalg.eigh and a cyclic Jacobi of its own -- whose difference measures what rounding alone does on given inputs.  Also the
+"""The ensemble analysis restated in NumPy (include/spdy.h, "ensemble analysis" and the sections after it), exactly as the header
+defines it, ONCE, as stages that feed each other and take the optional arguments the features need:
+
+    observe    what is per member: hx, and for a network with observations at a pressure the members' ps and out-of-column flags
+               (stencil: the library's own tables for bit comparisons)
+    couple     what couples members, summed over the members in use in ascending order -> the obs_space dict (keep: the member mask)
+    weights    the localisation weight of unit vectors and ln sigma_o at grid columns
+    problems   C and b of the local problems from an obs_space dict (keep; r_eff: the background check's 1 / error^2)
+    increments the transform and the increments, with two routes for the eigenproblem -- numpy.linalg.eigh and a cyclic Jacobi of
+               its own -- whose difference measures what rounding alone does on given inputs
+
+obs_space is couple(observe(...)), row range by row range on the slots' ensembles when xs and first are given; analyse is
+increments(problems(obs_space(...))).  `run` is the device side of a comparison: Letkf.analyse_grid on a NumPy ensemble and what
+the object holds afterwards.  The modules tests/letkf*.py next to this one keep what is a feature's own (the vertical
+interpolation, the check's decisions and statistics, the relaxation, the inflation estimate, the interpolation tables).  Also the
 helpers that build small observation sets and gridded ensembles for the tests.
 
 Arrays are C-order views of the library's: a gridded ensemble is {"u", "v", "t", "q": (E, kx, il, ix), "ps": (E, il, ix)}; an
-observation set is a dict of equal-length arrays var, lev, lon, lat, value, error."""
+observation set is a dict of equal-length arrays var, lev, lon, lat, value, error, and "p" in Pa where the network may hold
+observations at a pressure (lev == AT_P)."""
 import numpy as np
 
 import support
 
 U, V, T, Q, PS = range(5)
+AT_P = -1            # as lev: the observation sits at its pressure "p" (tests/letkfpressure.py)
+FIELDS = ("hx", "hxmean", "y", "departure", "obs_lnsigma", "obs_used")      # of an obs_space dict, and the device fields of those names
 VARS = ("u", "v", "t", "q", "ps")
 REARTH = 6.371e6
 EPS = float(np.finfo(np.float64).eps)
@@ -84,21 +99,114 @@ def dense_rows(g, idx, wgt):
     return H
 
 
-def obs_space(g, x, obs):
-    """-> hx (nobs, E), hxmean, Y (nobs, E), d"""
-    idx, w = stencil(g, obs["lon"], obs["lat"])
+_grid_stencil = stencil      # `observe` takes the stencils to use under this name
+
+
+def subset(obs, keep):
+    """the network with the observations keep (a mask, a slice or indices) only, in their order"""
+    return {k: v[keep] for k, v in obs.items()}
+
+
+def members(E, keep=None):
+    """the members in use, ascending (default: all)"""
+    return list(range(E)) if keep is None else sorted(int(e) for e in keep)
+
+
+def compact(x, keep):
+    """the gridded ensemble of the members in use"""
+    return x if keep is None else {v: np.ascontiguousarray(x[v][members(0, keep)]) for v in VARS}
+
+
+def at_pressure(obs):
+    """which observations sit at their pressure "p" (tests/letkfpressure.py); none of a set without "p" """
+    return (obs["lev"] == AT_P) & (obs["var"] != PS) if "p" in obs else np.zeros(len(obs["var"]), bool)
+
+
+def bilinear(w, z):
+    """w (4) and z (E, 4) -> (E)"""
+    return ((w[0] * z[:, 0] + w[1] * z[:, 1]) + w[2] * z[:, 2]) + w[3] * z[:, 3]
+
+
+def observe(g, x, obs, stencil=None, pressure=None):
+    """What is per member -> (hx (nobs, E), ps (nobs, E), out (nobs, E)).  A model-level or ps observation is the bilinear sum of its
+    four points; one at a pressure that of tests/letkfpressure.py's per-column interpolation.  ps, the members' ps at the station,
+    and out, 1.0 where the observation is out of the member's column at one of the points, are None unless the network has an
+    observation at a pressure (pressure: whether it has, for a part of a network; default: whether obs has).  stencil: (index, weight)
+    to use in the place of `stencil`'s (Letkf.table's: bit comparisons against the device)"""
+    idx, w = _grid_stencil(g, obs["lon"], obs["lat"]) if stencil is None else stencil
     E, n = x["ps"].shape[0], len(obs["var"])
-    hx = np.zeros((n, E))
+    atp = at_pressure(obs)
+    hx, ps, out = np.zeros((n, E)), None, None
+    if atp.any() if pressure is None else pressure:
+        import letkfpressure as lp               # it imports this module
+        xo, ps, out = lp.lnp(obs), np.zeros((n, E)), np.zeros((n, E))
     for o in range(n):
         v = int(obs["var"][o])
-        f = x[VARS[v]].reshape(E, -1, g.il * g.ix)[:, 0 if v == PS else int(obs["lev"][o])]
-        i = idx[o]
-        hx[o] = ((w[o, 0] * f[:, i[0]] + w[o, 1] * f[:, i[1]]) + w[o, 2] * f[:, i[2]]) + w[o, 3] * f[:, i[3]]
-    s = np.zeros(n)
-    for e in range(E):
+        if ps is not None:
+            ps[o] = bilinear(w[o], x["ps"].reshape(E, -1)[:, idx[o]])
+        if atp[o]:
+            _, X, f = lp.stencil_columns(g, x, obs, o, idx)
+            z, _, _, _, far = lp.column_values(X, f, xo[o])
+            out[o] = far.any(axis=1)
+        else:
+            z = x[VARS[v]].reshape(E, -1, g.il * g.ix)[:, 0 if v == PS else int(obs["lev"][o])][:, idx[o]]
+        hx[o] = bilinear(w[o], z)
+    return hx, ps, out
+
+
+def couple(g, obs, hx, ps=None, out=None, keep=None):
+    """Everything that couples members, the sums over the members `keep` (default: all) in ascending order -> {"hx", "hxmean", "y"
+    (0.0 for a member not in use), "departure", "obs_lnsigma" (for an observation at a pressure ln(p/p0) minus the mean of ps),
+    "obs_used" (0.0 for one out of the column of a member in use)}, and ps and out as "slot_ps" and "slot_out" when given"""
+    use = members(hx.shape[1], keep)
+    n, nobs = len(use), hx.shape[0]
+    s = np.zeros(nobs)
+    for e in use:
         s = s + hx[:, e]
-    hxmean = s / E
-    return hx, hxmean, hx - hxmean[:, None], obs["value"] - hxmean
+    with np.errstate(all="ignore"):
+        hxmean = s / n if n else np.full(nobs, np.nan)
+        y = np.zeros_like(hx)
+        y[:, use] = hx[:, use] - hxmean[:, None]
+    atp = at_pressure(obs)
+    lns, used = lnsigma(g, dict(obs, lev=np.where(atp, 0, obs["lev"]))), np.ones(nobs)
+    if atp.any():
+        import letkfpressure as lp
+        p = np.zeros(nobs)
+        for e in use:
+            p = p + ps[:, e]
+        with np.errstate(all="ignore"):
+            lns = np.where(atp, lp.lnp(obs) - p / n, lns) if n else np.where(atp, np.nan, lns)
+        used = np.where((out[:, use] != 0.0).any(axis=1), 0.0, 1.0)
+    s = {"hx": hx, "hxmean": hxmean, "y": y, "departure": obs["value"] - hxmean, "obs_lnsigma": lns, "obs_used": used}
+    return s if ps is None else dict(s, slot_ps=ps, slot_out=out)
+
+
+def slot_rows(first, nobs):
+    """the slots' ranges checked: S + 1 integers from 0 to nobs that do not decrease"""
+    first = [int(f) for f in first]
+    assert len(first) >= 2 and first[0] == 0 and first[-1] == nobs and all(a <= b for a, b in zip(first, first[1:])), (first, nobs)
+    return first
+
+
+def obs_space(g, x, obs, keep=None, stencil=None, xs=None, first=None):
+    """`couple` of `observe`: the observation-space quantities of one analysis call.  xs, first (tests/letkfslots.py): the rows
+    first[s] <= o < first[s+1] are observed on xs[s] in x's place, and ps and out are kept for every network, zero for one without
+    an observation at a pressure"""
+    if xs is None:
+        return couple(g, obs, *observe(g, x, obs, stencil), keep=keep)
+    nobs, E = len(obs["var"]), xs[0]["ps"].shape[0]
+    first = slot_rows(first, nobs)
+    assert len(xs) == len(first) - 1
+    pressure = bool(at_pressure(obs).any())
+    hx, ps, out = np.zeros((nobs, E)), np.zeros((nobs, E)), np.zeros((nobs, E))
+    for s, xsl in enumerate(xs):
+        rows = slice(first[s], first[s + 1])
+        if first[s + 1] > first[s]:
+            got = observe(g, xsl, subset(obs, rows), None if stencil is None else (stencil[0][rows], stencil[1][rows]), pressure)
+            hx[rows] = got[0]
+            if pressure:
+                ps[rows], out[rows] = got[1:]
+    return couple(g, obs, hx, ps, out, keep)
 
 
 def gc(r):
@@ -130,13 +238,17 @@ def lnsigma(g, obs):
     return np.where(obs["var"] == PS, 0.0, g.lnfsg[np.where(obs["var"] == PS, 0, obs["lev"])])
 
 
-def weights(g, obs, cols, sigma_h, sigma_v):
-    """-> w (ncols, kx, nobs)"""
-    wh = gc(distance(g.colunit[cols], unit(obs["lon"], obs["lat"])) / (sigma_h * np.sqrt(10.0 / 3.0)))
-    if sigma_v > 0.0:
-        wv = gc(np.abs(g.lnfsg[:, None] - lnsigma(g, obs)[None, :]) / (sigma_v * np.sqrt(10.0 / 3.0)))
-        return wh[:, None, :] * wv[None, :, :]
-    return np.repeat(wh[:, None, :], g.kx, axis=1)
+def weights(g, unit, lnsigma, cols, sigma_h, sigma_v):
+    """The localisation weight gc(dist / c_h) gc(|ln fsg_k - ln sigma_o| / c_v) of the observations at the unit vectors `unit`
+    (nobs, 3) and vertical positions `lnsigma` (nobs) at the grid columns `cols` (None: all) -> w (ncols, kx, nobs); sigma_v <= 0:
+    the horizontal factor alone at every level, and lnsigma is not read"""
+    pc = g.colunit if cols is None else g.colunit[np.asarray(cols)]
+    with np.errstate(invalid="ignore"):
+        wh = gc(distance(pc, np.asarray(unit, np.float64).reshape(-1, 3)) / (sigma_h * np.sqrt(10.0 / 3.0)))
+        if sigma_v > 0.0:
+            wv = gc(np.abs(g.lnfsg[:, None] - np.asarray(lnsigma, np.float64)[None, :]) / (sigma_v * np.sqrt(10.0 / 3.0)))
+            return wh[:, None, :] * wv[None, :, :]
+    return np.broadcast_to(wh[:, None, :], (wh.shape[0], g.kx, wh.shape[1]))
 
 
 def pair(m, r, n):
@@ -218,35 +330,24 @@ def transform(C, b, E, rho, route="eigh"):
     return W + wbar[:, :, None] - np.eye(E), W, wbar, lam
 
 
-def problems(g, x, obs, sigma_h, sigma_v, cols=None):
-    """C (ncols, kx, E, E) and b (ncols, kx, E) of the local problems at the grid columns `cols` (default: all)"""
+def problems(g, obs, s, sigma_h, sigma_v, cols=None, keep=None, r_eff=None):
+    """C (ncols, kx, n, n) and b (ncols, kx, n) of the local problems at the grid columns `cols` (default: all) from the obs_space
+    dict s: Y of the n members `keep` (default: all), d, ln sigma_o, and r = w r_eff with r_eff the 1/error^2 of this call, by
+    default obs_used / error^2.  An observation is added in ascending order at the columns it reaches (r != 0 at some level) and
+    nowhere else, as on the device: a non-finite Y stays within its range"""
     cols = np.arange(g.ix * g.il) if cols is None else np.asarray(cols)
-    E, kx, nc, n = x["ps"].shape[0], g.kx, len(cols), len(obs["var"])
-    C, b = np.zeros((nc, kx, E, E)), np.zeros((nc, kx, E))
-    if n:
-        _, _, Y, d = obs_space(g, x, obs)
-        r = weights(g, obs, cols, sigma_h, sigma_v) * (1.0 / (obs["error"] * obs["error"]))[None, None, :]
-        for o in np.nonzero((r != 0.0).any(axis=(0, 1)))[0]:      # ascending; r == 0 adds an exact zero
-            C += r[:, :, o, None, None] * (Y[o][:, None] * Y[o][None, :])
-            b += r[:, :, o, None] * (Y[o] * d[o])
-    return C, b
-
-
-def local_problems(g, x, obs, sigma_h, sigma_v, cols):
-    """`problems` column by column: each column adds only the observations with r != 0 at one of its levels, in ascending order.
-    The ones it leaves out add an exact zero in `problems`, so the bits are the same; the cost goes with the observations in range
-    of a column, not with all of them"""
-    cols = np.asarray(cols)
-    E, kx, nc, n = x["ps"].shape[0], g.kx, len(cols), len(obs["var"])
-    C, b = np.zeros((nc, kx, E, E)), np.zeros((nc, kx, E))
-    if n:
-        _, _, Y, d = obs_space(g, x, obs)
-        r = weights(g, obs, cols, sigma_h, sigma_v) * (1.0 / (obs["error"] * obs["error"]))[None, None, :]
-        YY, Yd = Y[:, :, None] * Y[:, None, :], Y * d[:, None]
-        for c in range(nc):
-            for o in np.nonzero((r[c] != 0.0).any(axis=0))[0]:
-                C[c] += r[c, :, o, None, None] * YY[o]
-                b[c] += r[c, :, o, None] * Yd[o]
+    use = members(s["hx"].shape[1], keep)
+    n, kx, nc = len(use), g.kx, len(cols)
+    C, b = np.zeros((nc, kx, n, n)), np.zeros((nc, kx, n))
+    if len(obs["var"]):
+        Y, d = s["y"][:, use], s["departure"]
+        r_eff = s["obs_used"] * (1.0 / (obs["error"] * obs["error"])) if r_eff is None else np.asarray(r_eff, np.float64)
+        r = weights(g, unit(obs["lon"], obs["lat"]), s["obs_lnsigma"], cols, sigma_h, sigma_v) * r_eff[None, None, :]
+        with np.errstate(invalid="ignore"):
+            for o in np.nonzero((r != 0.0).any(axis=(0, 1)))[0]:
+                at = (r[:, :, o] != 0.0).any(axis=1)
+                C[at] += r[at, :, o, None, None] * (Y[o][:, None] * Y[o][None, :])
+                b[at] += r[at, :, o, None] * (Y[o] * d[o])
     return C, b
 
 
@@ -269,10 +370,12 @@ def increments(g, x, C, b, rho, route="eigh", cols=None):
     return out, float(np.max(lam.max(axis=1) / lam.min(axis=1)))
 
 
-def analyse(g, x, obs, sigma_h, sigma_v, rho, route="eigh", cols=None):
-    """The increments of the gridded ensemble x at the grid columns `cols` (default: all), and the largest condition number"""
-    C, b = problems(g, x, obs, sigma_h, sigma_v, cols)
-    return increments(g, x, C, b, rho, route, cols)
+def analyse(g, x, obs, sigma_h, sigma_v, rho, route="eigh", cols=None, keep=None, stencil=None, r_eff=None, xs=None, first=None):
+    """The increments of the members in use of the gridded ensemble x at the grid columns `cols` (default: all), and the largest
+    condition number.  keep: the members in use; stencil: `observe`'s; r_eff: `problems`'; xs, first: `obs_space`'s, Y and d are
+    then from the slots' times and the increments are formed on x"""
+    C, b = problems(g, obs, obs_space(g, x, obs, keep, stencil, xs, first), sigma_h, sigma_v, cols, keep, r_eff)
+    return increments(g, compact(x, keep), C, b, rho, route, cols)
 
 
 def at_columns(a, cols):
@@ -302,13 +405,12 @@ def ensemble(g, E, seed=0):
     return x
 
 
-def observe(g, x, var, lev, lon, lat, err_factor, seed=1):
+def observations(g, x, var, lev, lon, lat, err_factor, seed=1):
     """observations of member 0 with errors err_factor * SCALE's spread: value = H x_0 + error * noise"""
     rng = np.random.default_rng(seed)
     err = err_factor * np.array([SCALE[VARS[v]][1] for v in var])
     obs = make_obs(var, lev, lon, lat, np.zeros(len(var)), err)
-    hx, _, _, _ = obs_space(g, x, obs)
-    obs["value"] = hx[:, 0] + err * rng.standard_normal(len(var))
+    obs["value"] = observe(g, x, obs)[0][:, 0] + err * rng.standard_normal(len(var))
     return obs
 
 
@@ -326,7 +428,7 @@ def edge_obs(g, x, nrandom=26, err_factor=0.5, seed=3):
     pts = edge_points(g) + [(float(rng.uniform(-400, 400)), float(rng.uniform(-90, 90))) for _ in range(nrandom)]
     var = [o % 5 for o in range(len(pts))]
     lev = [(3 * o) % g.kx for o in range(len(pts))]
-    return observe(g, x, var, lev, [p[0] for p in pts], [p[1] for p in pts], err_factor, seed)
+    return observations(g, x, var, lev, [p[0] for p in pts], [p[1] for p in pts], err_factor, seed)
 
 
 def clustered_obs(g, x, n=1500, centre=(100.0, 20.0), half_width=3.0, err_factor=0.125, seed=5):
@@ -336,13 +438,13 @@ def clustered_obs(g, x, n=1500, centre=(100.0, 20.0), half_width=3.0, err_factor
     lev = rng.integers(0, g.kx, n)
     lon = centre[0] + rng.uniform(-half_width, half_width, n)
     lat = centre[1] + rng.uniform(-half_width, half_width, n)
-    return observe(g, x, var, lev, lon, lat, err_factor, seed)
+    return observations(g, x, var, lev, lon, lat, err_factor, seed)
 
 
 def sparse_obs(g, x, n=60, err_factor=0.125, seed=7):
     """n observations spread over the globe"""
     rng = np.random.default_rng(seed)
-    return observe(g, x, rng.integers(0, 5, n), rng.integers(0, g.kx, n), rng.uniform(0, 360, n),
+    return observations(g, x, rng.integers(0, 5, n), rng.integers(0, g.kx, n), rng.uniform(0, 360, n),
                    np.degrees(np.arcsin(rng.uniform(-1, 1, n))), err_factor, seed)
 
 
@@ -371,7 +473,7 @@ def pad_obs(g, x, n, centre, err_factor=0.125, seed=13):
     rng = np.random.default_rng(seed)
     lat = centre[1] + rng.uniform(-0.7, 0.7, n)
     lon = centre[0] + rng.uniform(-0.7, 0.7, n) / np.cos(np.radians(centre[1]))
-    return observe(g, x, [o % 5 for o in range(n)], [(3 * o) % g.kx for o in range(n)], lon, lat, err_factor, seed)
+    return observations(g, x, [o % 5 for o in range(n)], [(3 * o) % g.kx for o in range(n)], lon, lat, err_factor, seed)
 
 
 PATTERNS = ("front1", "front255", "front256", "alternate", "wave3", "hole")
@@ -417,8 +519,7 @@ EDGE_SIGMA_H = 3.0e5      # of the edge-column tests: at 5e5 edge_obs alone leav
 
 def in_range(g, obs, cols=None, sigma_h=SIGMA_H):
     """(ncols, nobs): the observation has a non-zero horizontal weight at the column"""
-    pc = g.colunit if cols is None else g.colunit[cols]
-    return gc(distance(pc, unit(obs["lon"], obs["lat"])) / (sigma_h * np.sqrt(10.0 / 3.0))) != 0.0
+    return weights(g, unit(obs["lon"], obs["lat"]), None, cols, sigma_h, 0.0)[:, 0] != 0.0
 
 
 def edge_inputs(g, x):
@@ -427,7 +528,7 @@ def edge_inputs(g, x):
     sets = [("edge", edge_obs(g, x)), ("wrap", clustered_obs(g, x, n=200, centre=WRAP, half_width=2.0 / np.sqrt(2.0), seed=21))]
     for name, lat, seed in (("north", 88.0, 22), ("south", -88.0, 23)):
         rng = np.random.default_rng(seed)
-        sets.append((name, observe(g, x, rng.integers(0, 5, 200), rng.integers(0, g.kx, 200), rng.uniform(0.0, 360.0, 200),
+        sets.append((name, observations(g, x, rng.integers(0, 5, 200), rng.integers(0, g.kx, 200), rng.uniform(0.0, 360.0, 200),
                                    lat + rng.uniform(-1.5, 1.5, 200), 0.125, seed)))
     return sets
 
@@ -482,12 +583,26 @@ def make(sp, E, obs, sigma_v=0.0, rho=RHO, sigma_h=SIGMA_H):
     return lt
 
 
-def analyse_grid(sp, lt, x):
-    """Letkf.analyse_grid on the gridded ensemble x (NumPy) -> the increments as NumPy arrays"""
+def grids(x):
+    """the gridded ensemble x (NumPy) as the five device tensors of Letkf.analyse_grid"""
+    return [support.dev(x[v]) for v in VARS]
+
+
+def run(lt, x, use=None, slots=False, out=None, names=FIELDS):
+    """Letkf.analyse_grid on the gridded ensemble x (NumPy) -> the increments under VARS, the fields `names` (those with an item:
+    none per observation of an empty network), members_used, and what the object's settings add -- inflation with relaxation on,
+    weights at a weight stride, rho, infl_parm and obs_s2 with adaptive inflation on -- as NumPy arrays"""
     import torch
-    out = lt.analyse_grid(*[support.dev(x[v]) for v in VARS])
+    got = lt.analyse_grid(*grids(x), out=out, use=use, slots=slots)
     torch.cuda.synchronize()
-    return {v: a.cpu().numpy() for v, a in zip(VARS, out)}
+    got = {v: a.cpu().numpy() for v, a in zip(VARS, got)}
+    names = tuple(names) + ("members_used",) + (("inflation",) if lt.relaxation != (0.0, 0.0) else ())
+    names += (("weights",) if lt.weight_stride != (1, 1) else ()) + (("rho", "infl_parm", "obs_s2") if lt.adaptive is not None else ())
+    for n in dict.fromkeys(names):
+        f = lt.field(n)
+        if 0 not in f.shape:
+            got[n] = f.numpy().copy()
+    return got
 
 
 def limits(g, x, C, b, rho, cols, E, sample=None):
@@ -531,7 +646,7 @@ def spread_obs(g, x, n, seed):
     pts = (edge_points(g) + [(float(rng.uniform(0, 360)), float(rng.uniform(-85, 85))) for _ in range(n)])[:n]
     obs = make_obs([o % 5 for o in range(n)], [(3 * o) % g.kx for o in range(n)], [p[0] for p in pts], [p[1] for p in pts],
                    np.zeros(n), np.ones(n))
-    hx, _, _, _ = obs_space(g, x, obs)
+    hx = observe(g, x, obs)[0]
     obs["error"] = 0.5 * hx.std(axis=1, ddof=1) + 1e-300
     obs["value"] = hx[:, 0] + obs["error"] * rng.standard_normal(n)
     return obs

@@ -16,10 +16,8 @@ def s2(y, keep=None):
 
 
 def horizontal(g, ounit, sigma_h, cols=None):
-    """wh (ncols, nobs) with the transform kernel's expressions"""
-    cols = np.arange(g.ix * g.il) if cols is None else np.asarray(cols)
-    with np.errstate(invalid="ignore"):
-        return lk.gc(lk.distance(g.colunit[cols], np.asarray(ounit, np.float64).reshape(-1, 3)) / (sigma_h * np.sqrt(10.0 / 3.0)))
+    """wh (ncols, nobs): letkf.weights without a vertical scale"""
+    return lk.weights(g, ounit, None, cols, sigma_h, 0.0)[:, 0]
 
 
 def sums(g, ounit, olns, reff, dep, s2o, sigma_h, sigma_v, cols=None):
@@ -27,18 +25,15 @@ def sums(g, ounit, olns, reff, dep, s2o, sigma_h, sigma_v, cols=None):
     (skipped if 0), w = c_v > 0 ? wh gc(|ln fsg_k - ln sigma_o| / c_v) : wh, r = w reff_o, and an observation with r == 0 taking no
     part.  ounit (nobs, 3), olns, reff, dep, s2o (nobs): what the analysis call read -- the object's unit table, obs_lnsigma, the
     per-call 1 / error^2, departure, obs_s2"""
+    ounit, dep, s2o, reff, olns = (np.asarray(a, np.float64) for a in (ounit, dep, s2o, reff, olns))
+    ounit = ounit.reshape(-1, 3)
     wh = horizontal(g, ounit, sigma_h, cols)
-    nc, n = wh.shape
-    cv = sigma_v * np.sqrt(10.0 / 3.0) if sigma_v > 0.0 else 0.0
-    p = np.zeros((3, g.kx, nc))
-    dep, s2o, reff, olns = (np.asarray(a, np.float64) for a in (dep, s2o, reff, olns))
+    p = np.zeros((3, g.kx, wh.shape[0]))
     d2 = dep * dep
     with np.errstate(invalid="ignore", over="ignore"):
         for o in np.nonzero((wh != 0.0).any(axis=0))[0]:
             near = wh[:, o] != 0.0
-            w = np.repeat(wh[None, :, o], g.kx, axis=0)
-            if cv > 0.0:
-                w = w * lk.gc(np.abs(g.lnfsg - olns[o]) / cv)[:, None]
+            w = lk.weights(g, ounit[o:o + 1], olns[o:o + 1], cols, sigma_h, sigma_v)[:, :, 0].T
             r = w * reff[o]
             take = near[None, :] & (r != 0.0)
             p[0] = np.where(take, p[0] + r * d2[o], p[0])

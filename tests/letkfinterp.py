@@ -45,7 +45,7 @@ def needed(idx, wgt, cols):
 
 def transforms(g, x, obs, sigma_h, sigma_v, rho, gridcols, route="eigh"):
     """T (n, kx, E, E) of the local problems at the grid columns `gridcols`"""
-    C, b = lk.problems(g, x, obs, sigma_h, sigma_v, gridcols)
+    C, b = lk.problems(g, obs, lk.obs_space(g, x, obs), sigma_h, sigma_v, gridcols)
     n, kx, E = b.shape
     return lk.transform(C.reshape(-1, E, E), b.reshape(-1, E), E, rho, route)[0].reshape(n, kx, E, E)
 

@@ -14,26 +14,6 @@ def flags(E, keep):
     return [1 if e in set(keep) else 0 for e in range(E)]
 
 
-def compact(x, keep):
-    return {v: np.ascontiguousarray(x[v][list(keep)]) for v in lk.VARS}
-
-
-def grids(x):
-    return [support.dev(x[v]) for v in lk.VARS]
-
-
-def analyse(lt, x, use=None):
-    """Letkf.analyse_grid on the NumPy ensemble x -> the increments and the observation-space fields as NumPy arrays"""
-    import torch
-    out = lt.analyse_grid(*grids(x), use=use)
-    torch.cuda.synchronize()
-    got = {v: a.cpu().numpy() for v, a in zip(lk.VARS, out)}
-    if lt.nobs:
-        got.update({n: lt.field(n).numpy().copy() for n in OBS_FIELDS + ("y", "hx")})
-    got["members_used"] = lt.field("members_used").numpy().copy()
-    return got
-
-
 def zero_bits(a):
     """every value is +0.0"""
     return not np.ascontiguousarray(a).view(np.int64).any()
@@ -60,7 +40,7 @@ def same_as_compact(got, ref, E, keep, tag=""):
 def pair(sp, g, E, keep, obs_of, sigma_v, seed=None, make=lk.make, ensemble=lk.ensemble, stride=None):
     """-> (x, obs, the object of E members, the object of len(keep) members, the compacted ensemble); obs_of(g, compacted x)"""
     x = ensemble(g, E, seed=E if seed is None else seed)
-    xc = compact(x, keep)
+    xc = lk.compact(x, keep)
     obs = obs_of(g, xc)
     lt, ltc = make(sp, E, obs, sigma_v), make(sp, len(keep), obs, sigma_v)
     if stride is not None:

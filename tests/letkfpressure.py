@@ -1,8 +1,9 @@
 """Observations given at a pressure, restated in NumPy (include/spdy.h, "ensemble analysis, observations at a pressure") in the
 header's operation order: the per-member vertical interpolation of the four stencil columns by np.interp's rule, linear in ln p
 (tests/pressurelevels.py has the bracket), the bilinear sum, the vertical position the localisation uses and which observations
-take part.  The rest of the analysis is tests/letkf.py's, fed with that position and with r = 0 for an observation left out.  Also
-the crafted gridded ensembles and networks of the tests and the classes they hold.
+take part.  tests/letkf.py's `observe` calls the interpolation here for an observation at a pressure, and its `couple` forms the
+position and the use; the rest of the analysis is that module's.  Also the crafted gridded ensembles and networks of the tests and
+the classes they hold.
 
 An observation set is tests/letkf.py's dict with one array more, "p" in Pa; lev == AT_P marks an observation at its p."""
 import math
@@ -13,7 +14,7 @@ import letkf as lk
 import pressurelevels as pl
 from ensembleoutput import P0
 
-AT_P = -1
+AT_P, at_pressure = lk.AT_P, lk.at_pressure
 SOUNDING = (92500.0, 85000.0, 70000.0, 50000.0, 30000.0, 20000.0, 10000.0)      # Pa: a radiosonde's mandatory levels
 
 
@@ -37,17 +38,9 @@ def args(obs):
     return lk.args(obs) + [obs["p"]]
 
 
-def at_pressure(obs):
-    return (obs["lev"] == AT_P) & (obs["var"] != lk.PS)
-
-
 def lnp(obs):
     """x_o = ln(p_o / p0) by the C library's log; 0 for an observation that is not at a pressure"""
     return np.array([math.log(float(p) / P0) if a else 0.0 for p, a in zip(obs["p"], at_pressure(obs))])
-
-
-def subset(obs, keep):
-    return {k: v[keep] for k, v in obs.items()}
 
 
 def column_values(X, f, x):
@@ -73,67 +66,14 @@ def stencil_columns(g, x, obs, o, idx):
 
 
 def tables(lt):
-    """the stencils an analysis object built for its observations, for `obs_space`: the library's own bits (tests/letkf.py's
+    """the stencils an analysis object built for its observations, for letkf.observe: the library's own bits (tests/letkf.py's
     stencil agrees with them to a few ulps, tests/test_letkf_cpu.py)"""
     return lt.table("stencil_index"), lt.table("stencil_weight")
 
 
-def obs_space(g, x, obs, stencil=None):
-    """-> {"hx" (nobs, E), "hxmean", "y" (nobs, E), "departure", "obs_lnsigma", "obs_used"} of one analysis call.  stencil: (index,
-    weight) to use in the place of tests/letkf.py's (`tables`: bit comparisons against the device)"""
-    idx, w = lk.stencil(g, obs["lon"], obs["lat"]) if stencil is None else stencil
-    E, n = x["ps"].shape[0], len(obs["var"])
-    atp, xo = at_pressure(obs), lnp(obs)
-    hx, used = np.zeros((n, E)), np.ones(n)
-    lns = lk.lnsigma(g, dict(obs, lev=np.where(atp, 0, obs["lev"])))
-    for o in range(n):
-        v = int(obs["var"][o])
-        if atp[o]:
-            ps4, X, f = stencil_columns(g, x, obs, o, idx)
-            z, _, _, _, out = column_values(X, f, xo[o])
-            pb = ((w[o, 0] * ps4[:, 0] + w[o, 1] * ps4[:, 1]) + w[o, 2] * ps4[:, 2]) + w[o, 3] * ps4[:, 3]
-            s = 0.0
-            for e in range(E):
-                s = s + pb[e]
-            lns[o] = xo[o] - s / E
-            used[o] = 0.0 if out.any() else 1.0
-        else:
-            z = x[lk.VARS[v]].reshape(E, -1, g.il * g.ix)[:, 0 if v == lk.PS else int(obs["lev"][o])][:, idx[o]]
-        hx[o] = ((w[o, 0] * z[:, 0] + w[o, 1] * z[:, 1]) + w[o, 2] * z[:, 2]) + w[o, 3] * z[:, 3]
-    s = np.zeros(n)
-    for e in range(E):
-        s = s + hx[:, e]
-    hxmean = s / E
-    return {"hx": hx, "hxmean": hxmean, "y": hx - hxmean[:, None], "departure": obs["value"] - hxmean, "obs_lnsigma": lns,
-            "obs_used": used}
-
-
 def truth_values(g, truth, obs, stencil=None):
     """h_o of the nature run: the operator on the truth with the truth's ps, clamped where the truth is out of column"""
-    return obs_space(g, {v: truth[v][None] for v in lk.VARS}, dict(obs, value=np.zeros(len(obs["var"]))), stencil)["hx"][:, 0]
-
-
-def problems(g, x, obs, sigma_h, sigma_v, cols=None, stencil=None):
-    """letkf.problems with the vertical position and the use of this call: r = (wh wv) (used / error^2)"""
-    cols = np.arange(g.ix * g.il) if cols is None else np.asarray(cols)
-    E, kx, nc, n = x["ps"].shape[0], g.kx, len(cols), len(obs["var"])
-    C, b = np.zeros((nc, kx, E, E)), np.zeros((nc, kx, E))
-    if n:
-        s = obs_space(g, x, obs, stencil)
-        Y, d = s["y"], s["departure"]
-        wh = lk.gc(lk.distance(g.colunit[cols], lk.unit(obs["lon"], obs["lat"])) / (sigma_h * np.sqrt(10.0 / 3.0)))
-        if sigma_v > 0.0:
-            wv = lk.gc(np.abs(g.lnfsg[:, None] - s["obs_lnsigma"][None, :]) / (sigma_v * np.sqrt(10.0 / 3.0)))
-            wt = wh[:, None, :] * wv[None, :, :]
-        else:
-            wt = np.repeat(wh[:, None, :], kx, axis=1)
-        r = wt * (s["obs_used"] * (1.0 / (obs["error"] * obs["error"])))[None, None, :]
-        with np.errstate(invalid="ignore"):
-            for o in np.nonzero((r != 0.0).any(axis=(0, 1)))[0]:      # ascending; at the columns it reaches: elsewhere r == 0 adds an exact zero
-                at = (r[:, :, o] != 0.0).any(axis=1)
-                C[at] += r[at, :, o, None, None] * (Y[o][:, None] * Y[o][None, :])
-                b[at] += r[at, :, o, None] * (Y[o] * d[o])
-    return C, b
+    return lk.observe(g, {v: truth[v][None] for v in lk.VARS}, obs, stencil)[0][:, 0]
 
 
 # ---------------------------------------------------------------------------------------------------- crafted inputs
@@ -191,7 +131,7 @@ def network(g, x, seed=5, nrandom=16, err_factor=0.5):
     obs = make_pobs(var[order], take([r[1] for r in rows], model["lev"]), take([r[2] for r in rows], np.zeros(len(model["var"]))),
                     take([r[3] for r in rows], model["lon"]), take([r[4] for r in rows], model["lat"]), np.zeros(len(var)),
                     err_factor * np.array([lk.SCALE[lk.VARS[v]][1] for v in var[order]]))
-    obs["value"] = obs_space(g, x, obs)["hx"][:, 0] + obs["error"] * rng.standard_normal(len(var))
+    obs["value"] = lk.observe(g, x, obs)[0][:, 0] + obs["error"] * rng.standard_normal(len(var))
     return obs
 
 
@@ -287,7 +227,7 @@ def spectral_case(sp, o, g, E):
     sts = es.member_states(sp, E)
     x = lk.oracle_grids(o, sts)
     net = sounding_network(g, SPECTRAL_STATIONS, seed=90, variables=(lk.U, lk.V, lk.T, lk.Q))
-    hx = obs_space(g, x, net)["hx"]
+    hx = lk.observe(g, x, net)[0]
     net["error"] = 0.5 * hx.std(axis=1, ddof=1) + 1e-300
     net["value"] = hx[:, 0] + net["error"] * np.random.default_rng(91).standard_normal(len(net["var"]))
     return sts, x, net
@@ -296,7 +236,8 @@ def spectral_case(sp, o, g, E):
 def spectral_analysis(o, g, sts, x, net, rho=lk.RHO):
     """the analysed time level 1 of every member: the restatement's increments on the oracle's grids through the oracle's vdspec and
     grid_to_spec (tests/test_gpu_letkf.py's route for a model-level network) -> (per member {vor, div, t, tr, ps}, obs_space)"""
-    C, b = problems(g, x, net, lk.SIGMA_H, SPECTRAL_SIGMA_V)
+    space = lk.obs_space(g, x, net)
+    C, b = lk.problems(g, net, space, lk.SIGMA_H, SPECTRAL_SIGMA_V)
     inc, _ = lk.increments(g, x, C, b, rho)
     grid = lambda a: a.reshape(a.shape[:-1] + (g.il, g.ix))
     out = []
@@ -306,7 +247,7 @@ def spectral_analysis(o, g, sts, x, net, rho=lk.RHO):
                     "t": st["t"][0] + np.stack([o.grid_to_spec(grid(inc["t"][e])[k]) for k in range(o.kx)]),
                     "tr": st["tr"][0] + np.stack([o.grid_to_spec(grid(inc["q"][e])[k]) for k in range(o.kx)]),
                     "ps": st["ps"][0] + o.grid_to_spec(grid(inc["ps"][e]))})
-    return out, obs_space(g, x, net)
+    return out, space
 
 
 def make(sp, E, obs, sigma_v=0.0, rho=lk.RHO, sigma_h=lk.SIGMA_H):

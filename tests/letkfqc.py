@@ -2,7 +2,8 @@
 statistics"): the decision per observation from y, the departure and the error, the per-call 1/error^2 the local
 analyses read, and the statistics of every group in the header's summation order -- partial t of 1024 takes the group's used
 observations with o mod 1024 == t, o ascending, then a halving tree -- so the device's sums can be held to the bit.  Every operation
-is one IEEE operation, as NumPy's element-wise arithmetic is.  Also the helpers the tests of the check share."""
+is one IEEE operation, as NumPy's element-wise arithmetic is.  The checked analysis is tests/letkf.py's with r_eff = reff(used,
+1 / error^2).  Also the helpers the tests of the check share."""
 import numpy as np
 
 import letkf as lk
@@ -13,16 +14,11 @@ COLUMNS = ("n_all", "n_out", "n_rej", "n_used", "sum_dep", "sum_dep2", "sum_s2",
 PASSED, REJECTED, OUT = 0.0, 1.0, 2.0
 
 
-def members(E, keep=None):
-    """U: the members in use, ascending"""
-    return list(range(E)) if keep is None else sorted(int(e) for e in keep)
-
-
 def spread2(y, keep=None):
     """s2_o = (sum_U y_e^2) / (n - 1): each square rounded, summed over U ascending, one division; n < 2 divides by 0 or -1, as
     the device does (the test is not made then)"""
     y = np.asarray(y, np.float64)
-    U = members(y.shape[1], keep)
+    U = lk.members(y.shape[1], keep)
     s = np.zeros(y.shape[0])
     for e in U:
         s = s + y[:, e] * y[:, e]
@@ -34,7 +30,7 @@ def check(y, dep, err, gross, in_column=None, keep=None):
     """-> {"s2", "v", "rej", "used" (bool), "check" (0.0 passed, 1.0 rejected, 2.0 out of column: out of column wins)}.  A NaN
     makes the comparison false; n < 2 or gross == 0: the test is not made"""
     y, dep, err = np.asarray(y, np.float64), np.asarray(dep, np.float64), np.asarray(err, np.float64)
-    n = len(members(y.shape[1], keep))
+    n = len(lk.members(y.shape[1], keep))
     s2 = spread2(y, keep)
     g2 = np.float64(gross) * np.float64(gross)
     v = s2 + err * err
@@ -87,33 +83,6 @@ def stats(group, ngroups, code, dep, s2, err, depb=None):
         for i, t in enumerate(terms):
             out[g, 4 + i] = tree(t, used)
     return out
-
-
-def subset(obs, keep):
-    """the network with the observations keep (a mask or indices) only, in their order"""
-    return {k: v[keep] for k, v in obs.items()}
-
-
-def problems(g, x, obs, r_eff, sigma_h, sigma_v, cols=None):
-    """letkf.problems with the per-call 1/error^2: C and b of the local problems, an observation with r == 0 taking no part"""
-    cols = np.arange(g.ix * g.il) if cols is None else np.asarray(cols)
-    E, kx, nc, n = x["ps"].shape[0], g.kx, len(cols), len(obs["var"])
-    C, b = np.zeros((nc, kx, E, E)), np.zeros((nc, kx, E))
-    if n:
-        _, _, Y, d = lk.obs_space(g, x, obs)
-        r = lk.weights(g, obs, cols, sigma_h, sigma_v) * np.asarray(r_eff)[None, None, :]
-        for o in np.nonzero((r != 0.0).any(axis=(0, 1)))[0]:
-            C += r[:, :, o, None, None] * (Y[o][:, None] * Y[o][None, :])
-            b += r[:, :, o, None] * (Y[o] * d[o])
-    return C, b
-
-
-def analyse(g, x, obs, gross, sigma_h, sigma_v, rho, cols=None):
-    """the checked analysis: the decisions on the restatement's own y and departure, then the increments -> (dx, decisions)"""
-    _, _, Y, d = lk.obs_space(g, x, obs)
-    dec = check(Y, d, obs["error"], gross)
-    C, b = problems(g, x, obs, reff(dec["used"], 1.0 / (obs["error"] * obs["error"])), sigma_h, sigma_v, cols)
-    return lk.increments(g, x, C, b, rho, cols=cols)[0], dec
 
 
 def plant(obs, hxmean, s2, gross, seed, groups=None, ngroups=5):

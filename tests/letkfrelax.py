@@ -87,21 +87,13 @@ def same_bits_everywhere(a):
 
 
 # ------------------------------------------------------------------------------------------------ what the GPU tests share
-def analyse(lt, x, use=None, out=None):
-    """Letkf.analyse_grid on the NumPy ensemble x -> (the increments as NumPy arrays, the "inflation" field)"""
-    import torch
-    got = lt.analyse_grid(*[support.dev(x[v]) for v in lk.VARS], out=out, use=use)
-    torch.cuda.synchronize()
-    return {v: a.cpu().numpy() for v, a in zip(lk.VARS, got)}, lt.field("inflation").numpy().copy()
-
-
 def raw_and_relaxed(lt, x, rtpp, rtps, use=None):
     """the raw increments of the object at (0, 0) and its relaxed call at (rtpp, rtps) -> (raw, relaxed, inflation)"""
     lt.set_relaxation(0.0, 0.0)
-    raw, _ = analyse(lt, x, use)
+    raw = lk.run(lt, x, use, names=())
     lt.set_relaxation(rtpp, rtps)
-    got, infl = analyse(lt, x, use)
-    return raw, got, infl
+    got = lk.run(lt, x, use, names=())
+    return raw, got, got["inflation"]
 
 
 def compare(x, raw, got, infl, rtpp, rtps, E, keep=None):

@@ -37,9 +37,10 @@ def test_operator(E, plans):
     x = lk.ensemble(g, E, seed=40 + E)
     obs = lk.edge_obs(g, x)
     lt = lk.make(sp, E, obs)
-    lk.analyse_grid(sp, lt, x)
+    lk.run(lt, x)
     got = {n: a.cpu().numpy() for n, a in lt.fields().items()}
-    hx, hxmean, _, dep = lk.obs_space(g, x, obs)
+    ref = lk.obs_space(g, x, obs)
+    hx, hxmean, dep = ref["hx"], ref["hxmean"], ref["departure"]
     scale = np.array([np.max(np.abs(x[lk.VARS[v]])) for v in obs["var"]])
     for name, mine, ref, sc in (("hx", got["hx"], hx, scale[:, None]), ("hxmean", got["hxmean"], hxmean, scale),
                                 ("departure", got["departure"], dep, scale)):
@@ -51,14 +52,13 @@ def test_operator(E, plans):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the analysis on grids
-def run(tag, sp, g, x, obs, E, sigma_v, cols, rho=lk.RHO, sigma_h=lk.SIGMA_H, local=False, sample=None):
+def run(tag, sp, g, x, obs, E, sigma_v, cols, rho=lk.RHO, sigma_h=lk.SIGMA_H, sample=None):
     """the device's increments, the restatement's at the columns cols, the limits (lk.limits) and kappa; the ratios are printed.
-    local: the reference's problems column by column (lk.local_problems, the same bits); sample: the limits' Jacobi route at so
-    many of the columns (lk.hardest), which can only make them stricter"""
-    C, b = (lk.local_problems if local else lk.problems)(g, x, obs, sigma_h, sigma_v, cols)
+    sample: the limits' Jacobi route at so many of the columns (lk.hardest), which can only make them stricter"""
+    C, b = lk.problems(g, obs, lk.obs_space(g, x, obs), sigma_h, sigma_v, cols)
     lim, ref, kappa = lk.limits(g, x, C, b, rho, cols, E, None if sample is None else lk.hardest(C, rho, sample))
     lt = lk.make(sp, E, obs, sigma_v, rho, sigma_h)
-    got = lk.analyse_grid(sp, lt, x)
+    got = lk.run(lt, x)
     lt.close()
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v], cols) - ref[v]))) / lim[v] for v in lk.VARS}
     print("[letkf grid %s E=%d sigma_v=%g] %d observations, %d columns, kappa %.2e, ratio to the limit: %s"
@@ -165,7 +165,7 @@ def test_analysis_t63_edges(plans):
     edge = edge[lk.in_range(g, obs, edge).any(axis=1)]
     cols = np.unique(np.concatenate([lk.columns_for(g, obs, lk.SIGMA_H), edge]))
     assert len(edge) >= 100
-    worst, kappa = compare("T63 L16", sp, g, x, obs, E, 0.1, cols, local=True, sample=48)
+    worst, kappa = compare("T63 L16", sp, g, x, obs, E, 0.1, cols, sample=48)
     assert max(worst.values()) <= 1.0, worst
 
 
@@ -175,13 +175,13 @@ def test_edge_columns(E, plans):
     """kx = 5, sigma_v = 0.1, sigma_h = lk.EDGE_SIGMA_H (at 5e5 edge_obs alone reaches every column of longitudes 0 and ix-1, and
     the test wants some out of range): edge_obs, 200 observations around (359.5, 0) between columns ix-1 and 0, 200 around latitude
     +88 and 200 around -88 at longitudes all around the circle.  Compared at every column of rows 0, 1, il-2, il-1 and of
-    longitudes 0 and ix-1 (472), the reference from lk.local_problems, under the rule of test_analysis_on_grids (E = 32: the
+    longitudes 0 and ix-1 (472), the reference from lk.problems, under the rule of test_analysis_on_grids (E = 32: the
     limits' Jacobi route at 64 of the columns).  The conditions on the inputs are lk.edge_conditions'; the columns out of range of
     everything also equal pure inflation X' (sqrt(rho) - 1) within the same limits."""
     sp, g = plans()
     x = lk.ensemble(g, E, seed=80 + E)
     obs, cols, out = lk.edge_conditions(g, lk.edge_inputs(g, x))
-    got, ref, lim, worst, kappa = run("edge columns", sp, g, x, obs, E, 0.1, cols, sigma_h=lk.EDGE_SIGMA_H, local=True,
+    got, ref, lim, worst, kappa = run("edge columns", sp, g, x, obs, E, 0.1, cols, sigma_h=lk.EDGE_SIGMA_H,
                                       sample=None if E < 32 else 64)
     assert max(worst.values()) <= 1.0, worst
     for v in lk.VARS:
@@ -208,9 +208,9 @@ def test_hard_local_problems(E, factor, plans):
     x = lk.ensemble(g, E, seed=E)
     obs = lk.hard_obs(g, x, factor)
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=24, outside=4)
-    C, _ = lk.local_problems(g, x, obs, lk.SIGMA_H, 0.0, cols)
+    C, _ = lk.problems(g, obs, lk.obs_space(g, x, obs), lk.SIGMA_H, 0.0, cols)
     ran = lk.jacobi(C[:, 0] + ((E - 1) / lk.RHO) * np.eye(E), counts=True)[2]          # sigma_v = 0: every level has this A
-    worst, kappa = compare("hard, error %g" % factor, sp, g, x, obs, E, 0.0, cols, local=True)
+    worst, kappa = compare("hard, error %g" % factor, sp, g, x, obs, E, 0.0, cols)
     print("[letkf hard E=%d error=%g] sweeps of the restatement: up to %d" % (E, factor, ran.max()))
     assert 1e6 <= kappa <= 1e10, kappa
     assert 9 < int(ran.max()) <= lk.SWEEPS, ran.max()
@@ -229,7 +229,7 @@ def unpadded(sp, g, E):
         real, pad = lk.padded_inputs(g, x)
         lt = lk.make(sp, E, lk.concat(real, pad), 0.1)
         lt.set_obs(*lk.args(real))
-        inc = lk.analyse_grid(sp, lt, x)
+        inc = lk.run(lt, x)
         _UNPADDED[E] = (x, real, pad, lt, inc, lt.field("y").numpy().copy(), lt.fields()["departure"].cpu().numpy())
     return _UNPADDED[E]
 
@@ -254,7 +254,7 @@ def test_padded_scans(E, pattern, plans):
         obs, at = lk.interleave(real, pad, pattern, total)
         assert len(obs["var"]) == (total or natural[pattern])
         lt.set_obs(*lk.args(obs))
-        got = lk.analyse_grid(sp, lt, x)
+        got = lk.run(lt, x)
         assert support.same_bits(np.ascontiguousarray(lt.field("y").numpy()[at]), y)
         assert support.same_bits(np.ascontiguousarray(lt.fields()["departure"].cpu().numpy()[at]), dep)
         for v in lk.VARS:
@@ -273,11 +273,11 @@ def test_exact_zero_out_of_range(plans):
     E = 3
     x = lk.ensemble(g, E, seed=31)
     lon, lat = np.array([100.0, 101.0, 99.0, 100.5, 102.0]), np.array([20.0, 21.0, 19.5, 18.0, 22.0])
-    obs = lk.observe(g, x, [lk.T] * 5, [2] * 5, lon, lat, 0.5)
+    obs = lk.observations(g, x, [lk.T] * 5, [2] * 5, lon, lat, 0.5)
     c_v = 0.1 * np.sqrt(10.0 / 3.0)
     assert all(abs(g.lnfsg[k] - g.lnfsg[2]) > 2.0 * c_v for k in range(g.kx) if k != 2)
     lt = lk.make(sp, E, obs, 0.1, 1.0)
-    got = lk.analyse_grid(sp, lt, x)
+    got = lk.run(lt, x)
     lt.close()
     far = lk.distance(g.colunit, lk.unit(lon, lat)).min(axis=1) > 2.0 * lk.C_H * (1.0 + 1e-12)
     assert far.sum() > 4000
@@ -300,9 +300,9 @@ def test_appended_observations_and_two_runs(plans):
     more = lk.clustered_obs(g, x, n=300, centre=(280.0, -20.0), seed=6)
     lt = lk.make(sp, E, lk.concat(base, more), 0.1, 1.0)
     lt.set_obs(*lk.args(base))
-    first, again = lk.analyse_grid(sp, lt, x), lk.analyse_grid(sp, lt, x)
+    first, again = lk.run(lt, x), lk.run(lt, x)
     lt.set_obs(*lk.args(lk.concat(base, more)))
-    both = lk.analyse_grid(sp, lt, x)
+    both = lk.run(lt, x)
     lt.close()
     untouched = lk.distance(g.colunit, lk.unit(more["lon"], more["lat"])).min(axis=1) > 2.0 * lk.C_H * (1.0 + 1e-12)
     near = lk.distance(g.colunit, lk.unit(base["lon"], base["lat"])).min(axis=1) < lk.C_H
@@ -322,7 +322,7 @@ def test_pure_inflation(plans):
     for E in (2, 17):
         x = lk.ensemble(g, E, seed=33)
         lt = lk.make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, 1.21)
-        got = lk.analyse_grid(sp, lt, x)
+        got = lk.run(lt, x)
         lt.close()
         for v in lk.VARS:
             s = np.zeros(x[v].shape[1:])
@@ -349,7 +349,7 @@ def test_closed_form(plans):
     err = 0.7
     obs = lk.make_obs([lk.T], [k], [g.lon[i]], [g.lat[j]], [tv.mean() + 1.3], [err])
     lt = lk.make(sp, E, obs, 0.1)
-    got = lk.analyse_grid(sp, lt, x)
+    got = lk.run(lt, x)
     lt.close()
     inc = got["t"][:, k].reshape(E, -1)[:, col]
     s2 = tv.var(ddof=1)

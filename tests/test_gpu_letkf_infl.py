@@ -46,25 +46,23 @@ def big(plans):
         if E not in made:
             _, g = plans()
             x = lk.ensemble(g, E, seed=80 + E)
-            made[E] = (x, qc.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=700)), slice(0, 700)))
+            made[E] = (x, lk.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=700)), slice(0, 700)))
         return made[E]
     return get
 
 
+STATE = ("rho", "infl_parm", "obs_s2")
+
+
 def state(lt):
     """the block's three arrays, downloaded"""
-    return {n: lt.field(n).numpy() for n in ("rho", "infl_parm", "obs_s2")}
+    return {n: lt.field(n).numpy() for n in STATE}
 
 
 def analyse(lt, x, **how):
-    """Letkf.analyse_grid on the NumPy ensemble x -> the increments, the field before the call and the block after it"""
-    import torch
+    """lk.run with the block's three arrays, adaptive inflation on or off, and the field before the call"""
     before = lt.field("rho").numpy()
-    got = lt.analyse_grid(*ls.grids(x), **how)
-    torch.cuda.synchronize()
-    res = {v: a.cpu().numpy() for v, a in zip(lk.VARS, got)}
-    res.update(state(lt), before=before)
-    return res
+    return dict(lk.run(lt, x, names=STATE, **how), before=before)
 
 
 def against_restatement(tag, g, lt, got, sigma_h, sigma_v, sigma_b, bounds=(li.RHO_MIN, li.RHO_MAX), keep=None, reff_field=False):
@@ -87,7 +85,7 @@ def test_sums(E, nobs, plans, big):
     of the scan's chunk of 256 and a network of more than two chunks; an empty network leaves exact zeros and the field's bits"""
     sp, g = plans()
     x, all_obs = big(E)
-    obs = qc.subset(all_obs, slice(0, nobs))
+    obs = lk.subset(all_obs, slice(0, nobs))
     lt = lk.make(sp, E, obs, 0.0)
     lt.set_adaptive_inflation(0.5)
     assert (lt.field("rho").numpy() == lk.RHO).all()
@@ -270,7 +268,7 @@ def test_transform_patches(stride, plans, big):
     refs = []
     for rho in values:
         lt.set_localization(lk.SIGMA_H, SIGMA_V, rho)
-        refs.append(lk.analyse_grid(sp, lt, x))
+        refs.append(lk.run(lt, x))
     lt.set_adaptive_inflation(0.0)
     lt.inflation_field().upload(field.reshape((g.kx,) + sp.grid_shape))
     got = analyse(lt, x)
@@ -370,10 +368,10 @@ def test_names_are_valid_on_every_object(plans):
     assert lt.field("infl_parm").shape == (3, 5) + sp.grid_shape and lt.field("obs_s2").shape == (lt.nobs,)
     assert (lt.inflation_field().numpy() == 1.25).all() and lm.zero_bits(lt.field("infl_parm").numpy())
     assert lt.adaptive is None and lt.table("adaptive_inflation")[0] == 0.0
-    before = lk.analyse_grid(sp, lt, x)
+    before = lk.run(lt, x)
     assert (lt.field("rho").numpy() == 1.25).all() and lm.zero_bits(lt.field("infl_parm").numpy())
     lt.fill_inflation(2.0)                                       # off: the field is not read
-    after = lk.analyse_grid(sp, lt, x)
+    after = lk.run(lt, x)
     for v in lk.VARS:
         assert support.same_bits(before[v], after[v]), v
     lt.close()

@@ -80,7 +80,7 @@ def reference(g, E, sigma_v):
 
 def run_at(sp, lt, x, si, sj):
     lt.set_weight_stride(si, sj)
-    return lk.analyse_grid(sp, lt, x)
+    return lk.run(lt, x)
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the coarse columns
@@ -91,7 +91,7 @@ def test_coarse_columns_bit_equal(E, plans):
     sp, g = plans()
     x = lk.ensemble(g, E, seed=60 + E)
     lt = lk.make(sp, E, observations(g, x), 0.1)
-    full = lk.analyse_grid(sp, lt, x)
+    full = lk.run(lt, x)
     for si, sj in STRIDES[:2]:
         got = run_at(sp, lt, x, si, sj)
         coarse = lt.table("coarse_columns")
@@ -158,7 +158,7 @@ def test_many_levels_with_a_column_list():
     alt, _, _ = li.analyse(g, x, obs, lk.SIGMA_H, 0.1, lk.RHO, si, sj, "jacobi", cols, (idx, wgt))
     lt = s.Letkf(sp, E, len(obs["var"]), lk.SIGMA_H, 0.1, lk.RHO, weight_stride=(si, sj))
     lt.set_obs(*lk.args(obs))
-    got = lk.analyse_grid(sp, lt, x)
+    got = lk.run(lt, x)
     sc = lk.perturbation_scale(x)
     lim = {v: max(16 * float(np.max(np.abs(ref[v] - alt[v]))), 64 * E * lk.EPS * sc[v]) for v in lk.VARS}
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v], cols) - ref[v]))) / lim[v] for v in lk.VARS}
@@ -195,17 +195,17 @@ def test_appended_observations_and_two_runs(plans):
     both = lk.concat(base, more)
     lt = lk.make(sp, E, both, 0.1, 1.0)
     lt.set_obs(*lk.args(base))
-    first, again = run_at(sp, lt, x, si, sj), lk.analyse_grid(sp, lt, x)
+    first, again = run_at(sp, lt, x, si, sj), lk.run(lt, x)
     idx, wgt = lt.table("interp_index"), lt.table("interp_weight")
     four = lt.table("coarse_columns")[idx[col]]
     assert (wgt[col] != 0.0).all() and len(set(four)) == 4
     dist = lk.distance(g.colunit[np.append(four, col)], lk.unit(more["lon"], more["lat"]))
     assert float(dist[:4].min()) > 2.0 * lk.C_H * (1.0 + 1e-12) and float(dist[4].max()) < lk.C_H
     lt.set_obs(*lk.args(both))
-    second = lk.analyse_grid(sp, lt, x)
+    second = lk.run(lt, x)
     full_both = run_at(sp, lt, x, 1, 1)
     lt.set_obs(*lk.args(base))
-    full_base = lk.analyse_grid(sp, lt, x)
+    full_base = lk.run(lt, x)
     lt.close()
     for v in lk.VARS:
         assert support.same_bits(first[v], again[v]), v
@@ -238,7 +238,7 @@ def test_padded_scans(pattern, plans):
     assert len(keep) >= 4300 and np.isin(np.nonzero(cluster)[0], keep).all() and len(changed) >= 20, (len(keep), len(changed))
     obs, at = lk.interleave(real, pad, pattern)
     lt.set_obs(*lk.args(obs))
-    got = lk.analyse_grid(sp, lt, x)
+    got = lk.run(lt, x)
     assert support.same_bits(np.ascontiguousarray(lt.field("weights").numpy()[far[coarse]]), np.ascontiguousarray(W[far[coarse]]))
     for v in lk.VARS:
         a, b = (np.ascontiguousarray(lk.at_columns(r[v], keep)) for r in (got, first))

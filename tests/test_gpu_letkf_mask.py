@@ -46,11 +46,11 @@ def test_masked_equals_compact(E, keep, plans):
     of the n-member object; the members not in use get exactly 0.0"""
     sp, g = plans()
     x = lk.ensemble(g, E, seed=E)
-    xc = lm.compact(x, keep)
+    xc = lk.compact(x, keep)
     for tag, obs in both_sets(g, xc):
         for sigma_v in (0.0, 0.1):
             lt, ltc = lk.make(sp, E, obs, sigma_v), lk.make(sp, len(keep), obs, sigma_v)
-            got, ref = lm.analyse(lt, x, lm.flags(E, keep)), lm.analyse(ltc, xc)
+            got, ref = lk.run(lt, x, lm.flags(E, keep)), lk.run(ltc, xc)
             lm.same_as_compact(got, ref, E, keep, (tag, sigma_v))
             lt.close(); ltc.close()
 
@@ -65,7 +65,7 @@ def test_masked_equals_compact_many_levels(kx):
     sp.set_sigma(np.linspace(0.0, 1.0, kx + 1) ** 1.5)
     g = lk.Geometry(sp)
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lambda g, xc: lk.concat(lk.clustered_obs(g, xc, n=300), lk.sparse_obs(g, xc)), 0.1)
-    lm.same_as_compact(lm.analyse(lt, x, lm.flags(E, keep)), lm.analyse(ltc, xc), E, keep, kx)
+    lm.same_as_compact(lk.run(lt, x, lm.flags(E, keep)), lk.run(ltc, xc), E, keep, kx)
     sp.close()
 
 
@@ -78,9 +78,9 @@ def test_masked_against_restatement(plans):
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lk.clustered_obs, 0.1)
     ltc.close()
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=32)
-    C, b = lk.problems(g, xc, obs, lk.SIGMA_H, 0.1, cols)
+    C, b = lk.problems(g, obs, lk.obs_space(g, xc, obs), lk.SIGMA_H, 0.1, cols)
     lim, ref, kappa = lk.limits(g, xc, C, b, lk.RHO, cols, len(keep))
-    got = lm.analyse(lt, x, lm.flags(E, keep))
+    got = lk.run(lt, x, lm.flags(E, keep))
     lt.close()
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v][list(keep)], cols) - ref[v]))) / lim[v] for v in lk.VARS}
     print("[letkf mask E=8 n=7] kappa %.2e, ratio to the limit: %s" % (kappa, " ".join("%s %.3f" % kv for kv in worst.items())))
@@ -97,13 +97,13 @@ def test_unused_member_reaches_nothing_on_grids(drop, plans):
     keep = tuple(e for e in range(E) if e != drop)
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lambda g, xc: lk.concat(lk.clustered_obs(g, xc, n=300), lk.sparse_obs(g, xc)), 0.1)
     ltc.close()
-    clean = lm.analyse(lt, x, lm.flags(E, keep))
+    clean = lk.run(lt, x, lm.flags(E, keep))
     for kind in ("nan", "inf", "1e300"):
         y = {v: a.copy() for v, a in x.items()}
         for v in lk.VARS:
             for f in y[v][drop].reshape((-1,) + y[v].shape[-2:]):
                 poison.poison(f, kind)
-        got = lm.analyse(lt, y, lm.flags(E, keep))
+        got = lk.run(lt, y, lm.flags(E, keep))
         for v in lk.VARS:
             assert support.same_bits(got[v], clean[v]), (kind, v)
         for n in lm.OBS_FIELDS + ("y", "members_used"):
@@ -153,9 +153,9 @@ def test_unmasked_paths_are_what_they_were(plans):
     x = lk.ensemble(g, E, seed=3)
     obs = lk.concat(lk.clustered_obs(g, x, n=300), lk.sparse_obs(g, x))
     lt = lk.make(sp, E, obs, 0.1)
-    none = lm.analyse(lt, x)
-    ones = lm.analyse(lt, x, [1] * E)
-    xs = lm.grids(x)
+    none = lk.run(lt, x)
+    ones = lk.run(lt, x, [1] * E)
+    xs = lk.grids(x)
     out = [torch.empty_like(a) for a in xs]
     sp._sync_stream()
     assert sp.lib.spdy_letkf_analyse_grid_dev(lt.h, *[ctypes.c_void_p(a.data_ptr()) for a in xs + out]) == 0
@@ -223,11 +223,11 @@ def test_pressure_network(plans):
     E, drop = 5, lp.PATCH_MEMBER
     keep = tuple(e for e in range(E) if e != drop)
     x = lp.craft(g, E, seed=21)
-    xc = lm.compact(x, keep)
+    xc = lk.compact(x, keep)
     obs = lp.network(g, xc)
     lt, ltc = lp.make(sp, E, obs, 0.1), lp.make(sp, len(keep), obs, 0.1)
-    full = lm.analyse(lt, x)
-    got, ref = lm.analyse(lt, x, lm.flags(E, keep)), lm.analyse(ltc, xc)
+    full = lk.run(lt, x)
+    got, ref = lk.run(lt, x, lm.flags(E, keep)), lk.run(ltc, xc)
     regained = (full["obs_used"] == 0.0) & (got["obs_used"] == 1.0)
     assert regained.sum() >= 8 and (got["obs_used"] == 0.0).sum() >= 10, (regained.sum(), (got["obs_used"] == 0.0).sum())
     assert not support.same_bits(full["obs_lnsigma"], got["obs_lnsigma"])
@@ -243,7 +243,7 @@ def test_weight_stride(plans):
     E, keep = 17, KEEP17
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lambda g, xc: lk.concat(lk.clustered_obs(g, xc, n=300), lk.sparse_obs(g, xc)), 0.1,
                                   stride=(2, 2))
-    got, ref = lm.analyse(lt, x, lm.flags(E, keep)), lm.analyse(ltc, xc)
+    got, ref = lk.run(lt, x, lm.flags(E, keep)), lk.run(ltc, xc)
     lm.same_as_compact(got, ref, E, keep, "stride")
     w, wc = lt.field("weights").numpy(), ltc.field("weights").numpy()
     assert w.shape[2:] == (E, E) and wc.shape[2:] == (14, 14) and wc.any()
@@ -263,7 +263,7 @@ def test_fewer_than_two_members(keep, stride, plans, oracle_factory):
     x = lk.ensemble(g, E, seed=9)
     lt = lk.make(sp, E, lk.clustered_obs(g, x, n=300), 0.1)
     lt.set_weight_stride(*stride)
-    got = lm.analyse(lt, x, lm.flags(E, keep))
+    got = lk.run(lt, x, lm.flags(E, keep))
     for v in lk.VARS:
         assert lm.zero_bits(got[v]), v
     assert got["members_used"].tolist() == [float(len(keep))]
@@ -293,20 +293,20 @@ def test_scores(plans, oracle_factory):
     nat = s.Nature(sp, capacity=3)
     x = lk.ensemble(g, E, seed=77)
     nat.field("truth").upload(nt.rows(nt.as_truth(lk.ensemble(g, 1, seed=78))))
-    xc = lm.compact(x, keep)
-    nat.verify_grid(*lm.grids(x), slot=0, use=lm.flags(E, keep))
-    nat.verify_grid(*lm.grids(xc), slot=1)
-    nat.verify_grid(*lm.grids(x), slot=2)
+    xc = lk.compact(x, keep)
+    nat.verify_grid(*lk.grids(x), slot=0, use=lm.flags(E, keep))
+    nat.verify_grid(*lk.grids(xc), slot=1)
+    nat.verify_grid(*lk.grids(x), slot=2)
     sc = nat.field("scores").numpy()
     assert support.same_bits(sc[0], sc[1]) and not support.same_bits(sc[0], sc[2]) and np.isfinite(sc).all() and sc[0].all()
     y = {v: a.copy() for v, a in x.items()}
     for v in lk.VARS:
         y[v][[2, 5]] = np.nan
-    nat.verify_grid(*lm.grids(y), slot=2, use=lm.flags(E, keep))
+    nat.verify_grid(*lk.grids(y), slot=2, use=lm.flags(E, keep))
     sc = nat.field("scores").numpy()
     assert support.same_bits(sc[2], sc[1])
-    nat.verify_grid(*lm.grids(y), slot=0, use=lm.flags(E, (4,)))
-    nat.verify_grid(*lm.grids(y), slot=2, use=[0] * E)
+    nat.verify_grid(*lk.grids(y), slot=0, use=lm.flags(E, (4,)))
+    nat.verify_grid(*lk.grids(y), slot=2, use=[0] * E)
     sc = nat.field("scores").numpy()
     assert np.isfinite(sc[0]).all() and sc[0, :2].all() and lm.zero_bits(sc[0, 2]) and np.isnan(sc[2]).all()
     # from spectra: the masked verify against verify_grid of the grids that call left in the analysis object's workspace
@@ -321,7 +321,7 @@ def test_scores(plans, oracle_factory):
     kx = sp.kx
     gx = {v: grid[i * E * kx:(i + 1) * E * kx].reshape((E, kx) + sp.grid_shape) for i, v in enumerate(lk.VARS[:4])}
     gx["ps"] = grid[4 * E * kx:]
-    nat.verify_grid(*lm.grids(lm.compact(gx, keep)), slot=1)
+    nat.verify_grid(*lk.grids(lk.compact(gx, keep)), slot=1)
     sc = nat.field("scores").numpy()
     assert support.same_bits(sc[0], sc[1]) and np.isfinite(sc[0]).all() and sc[0, 2].all()
     lt.close(); nat.close()
@@ -377,7 +377,7 @@ def test_two_masked_runs_are_bit_equal(plans):
     E, keep = 17, KEEP17
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lk.clustered_obs, 0.1)
     ltc.close()
-    a, b = lm.analyse(lt, x, lm.flags(E, keep)), lm.analyse(lt, x, lm.flags(E, keep))
+    a, b = lk.run(lt, x, lm.flags(E, keep)), lk.run(lt, x, lm.flags(E, keep))
     for n in a:
         assert support.same_bits(a[n], b[n]), n
     lt.close()

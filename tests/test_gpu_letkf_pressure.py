@@ -48,7 +48,8 @@ def same_but_nan_bits(a, b):
 
 
 def increments(sp, lt, x):
-    return lk.analyse_grid(sp, lt, x)
+    got = lk.run(lt, x, names=())
+    return {v: got[v] for v in lk.VARS}
 
 
 # ---------------------------------------------------------------------------------------------------- 1. observation space
@@ -62,11 +63,11 @@ def test_observation_space(kx, E, plans):
     x = lp.craft(g, E, seed=7 + E)
     full = lp.network(g, x)
     for n in (0, 1, min(257, len(full["var"]) - 1), len(full["var"])):
-        obs = lp.subset(full, np.arange(len(full["var"])) < n)
+        obs = lk.subset(full, np.arange(len(full["var"])) < n)
         lt = lp.make(sp, E, obs)
         inc = increments(sp, lt, x)
         assert all(np.isfinite(a).all() for a in inc.values())
-        want = lp.obs_space(g, x, obs, lp.tables(lt))
+        want = lk.obs_space(g, x, obs, stencil=lp.tables(lt))
         got = device_fields(lt) if n else want               # no observation: nothing to read, the call itself is the test
         for name in FIELDS:
             assert support.same_bits(got[name], want[name]), (kx, E, n, name, np.nonzero(got[name] != want[name]))
@@ -92,10 +93,10 @@ def test_tie_to_model_levels(stride, plans):
     tg = [names[n] for n in names if n != "above"]
     n = len(pts) * 3
     var = np.arange(n) % 5
-    plain = lk.observe(g, x, var, np.arange(n) % g.kx, [pts[o % len(pts)][0] for o in range(n)], [pts[o % len(pts)][1] for o in range(n)], 0.5)
+    plain = lk.observations(g, x, var, np.arange(n) % g.kx, [pts[o % len(pts)][0] for o in range(n)], [pts[o % len(pts)][1] for o in range(n)], 0.5)
     atp = dict(plain, lev=np.where(np.arange(n) % 3 == 2, plain["lev"], lp.AT_P),
                p=np.array([pl.P0 * np.exp(tg[o % len(tg)]) for o in range(n)]))
-    assert lp.at_pressure(atp).sum() > n // 2 and (lp.obs_space(g, x, atp)["obs_used"] == 1.0).all()
+    assert lp.at_pressure(atp).sum() > n // 2 and (lk.obs_space(g, x, atp)["obs_used"] == 1.0).all()
     res = []
     for obs, make in ((plain, lk.make), (atp, lp.make)):
         lt = s.Letkf(sp, E, n, lk.SIGMA_H, 0.0, lk.RHO, weight_stride=stride)
@@ -126,19 +127,19 @@ def test_rejected_observations_take_no_part(E, plans):
     x["t"].reshape(E, g.kx, -1)[:, 0, mine[0]] = np.nan
     n = len(obs["var"])
     both = {k: np.insert(obs[k], n // 2, lone[k]) for k in obs}
-    want = lp.obs_space(g, x, both)
+    want = lk.obs_space(g, x, both)
     used = want["obs_used"] == 1.0
     assert (~used).sum() >= 10 and (used[:-1] != used[1:]).sum() >= 10                               # interleaved
     assert not used[n // 2] and np.isnan(want["hx"][n // 2]).all() and np.isfinite(want["hx"][used]).all()
     lt = lp.make(sp, E, both)
     a = increments(sp, lt, x)
-    got, want = device_fields(lt), lp.obs_space(g, x, both, lp.tables(lt))
+    got, want = device_fields(lt), lk.obs_space(g, x, both, stencil=lp.tables(lt))
     assert np.array_equal(want["obs_used"] == 1.0, used)
     for name in FIELDS:
         assert same_but_nan_bits(got[name], want[name]), name
     assert np.isnan(got["departure"][n // 2]) and np.isnan(got["hx"][n // 2]).all()
     lt.close()
-    lt = lp.make(sp, E, lp.subset(both, used))
+    lt = lp.make(sp, E, lk.subset(both, used))
     b = increments(sp, lt, x)
     assert (lt.field("obs_used").numpy() == 1.0).all()
     lt.close()
@@ -158,7 +159,7 @@ def test_vertical_localisation(plans):
     x = lp.craft(g, E, seed=31)
     obs = lp.network(g, x)
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=32, outside=8)
-    C, b = lp.problems(g, x, obs, lk.SIGMA_H, sigma_v, cols)
+    C, b = lk.problems(g, obs, lk.obs_space(g, x, obs), lk.SIGMA_H, sigma_v, cols)
     lim, ref, kappa = lk.limits(g, x, C, b, lk.RHO, cols, E, lk.hardest(C, lk.RHO, 12))
     lt = lp.make(sp, E, obs, sigma_v)
     got = increments(sp, lt, x)
@@ -184,7 +185,7 @@ def test_vertical_factor_of_zero_changes_nothing(plans):
     mid = pl.P0 * np.exp(dict(lp.targets(g))["mid0"])
     more = lp.make_pobs([lk.T, lk.U, lk.Q], [lp.AT_P] * 3, [mid] * 3, [100.0, 101.0, 250.0], [20.0, 21.0, -30.0], [260.0, 5.0, 4.0], [0.1] * 3)
     both = {k: np.concatenate([obs[k], more[k]]) for k in obs}
-    s = lp.obs_space(g, x, both)
+    s = lk.obs_space(g, x, both)
     assert (s["obs_used"][-3:] == 1.0).all()
     assert float(np.min(np.abs(g.lnfsg[:, None] - s["obs_lnsigma"][None, -3:]))) >= 2.0 * sigma_v * np.sqrt(10.0 / 3.0)
     res = []
@@ -264,7 +265,7 @@ def test_nature_values(plans):
     net = lp.network(g, x)
     n = len(net["var"])
     h = lp.truth_values(g, truth, net)
-    alone = lp.obs_space(g, {v: np.stack([truth[v], truth[v]]) for v in lk.VARS}, net)
+    alone = lk.obs_space(g, {v: np.stack([truth[v], truth[v]]) for v in lk.VARS}, net)
     out = alone["obs_used"] == 0.0
     assert out.sum() >= 10 and np.isfinite(h).all()
     nat = s.Nature(sp, seed=seed, capacity=1)
@@ -298,10 +299,10 @@ def test_capture(plans):
     x1 = lp.craft(g, E, seed=61)
     x2 = dict(x1, ps=np.random.default_rng(62).uniform(-0.05, 0.05, x1["ps"].shape))
     obs = lp.network(g, x1)
-    want = [lp.obs_space(g, x, obs) for x in (x1, x2)]
+    want = [lk.obs_space(g, x, obs) for x in (x1, x2)]
     assert not np.array_equal(want[0]["obs_used"], want[1]["obs_used"])
     lt = lp.make(sp, E, obs, 0.3)
-    want = [lp.obs_space(g, x, obs, lp.tables(lt)) for x in (x1, x2)]
+    want = [lk.obs_space(g, x, obs, stencil=lp.tables(lt)) for x in (x1, x2)]
     eager = []
     for x in (x1, x2):
         inc = increments(sp, lt, x)
@@ -344,7 +345,7 @@ def test_capture(plans):
         gm.launch()
         sp.synchronize()
         level0 = lk.make_obs(np.full(n, lk.T), np.zeros(n), obs["lon"][:n], obs["lat"][:n], np.full(n, 250.0), np.ones(n))
-        assert support.same_bits(plain.field("hx").numpy(), lp.obs_space(g, x1, dict(level0, p=np.zeros(n)), lp.tables(plain))["hx"])
+        assert support.same_bits(plain.field("hx").numpy(), lk.observe(g, x1, level0, lp.tables(plain))[0])
         assert all(bool(torch.isfinite(a).all()) for a in out)
         gr.close(); gm.close()
     finally:
@@ -374,7 +375,7 @@ def test_twin_step():
     inc = lt.analyse_grid(*xd)
     nat.verify_grid(*[a + b for a, b in zip(xd, inc)], slot=1)
     got = nat.field("scores").numpy()
-    assert np.array_equal(lt.field("obs_used").numpy(), lp.obs_space(g, x, net, lp.tables(lt))["obs_used"])
+    assert np.array_equal(lt.field("obs_used").numpy(), lk.obs_space(g, x, net, stencil=lp.tables(lt))["obs_used"])
     ratios = {v: got[1][0][n * kx:(n + 1) * kx] / got[0][0][n * kx:(n + 1) * kx] for n, v in enumerate(lk.VARS[:3])}
     print("[pobs twin, device] rmse analysis / background: %s" % " ".join("%s %s" % (v, np.round(r, 3)) for v, r in ratios.items()))
     assert all((r < 1.0).all() for r in ratios.values()), ratios

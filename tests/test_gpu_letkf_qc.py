@@ -46,21 +46,17 @@ def big(plans):
         if E not in made:
             _, g = plans()
             x = lk.ensemble(g, E, seed=60 + E)
-            made[E] = (x, qc.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=2100)), slice(0, 2100)))
+            made[E] = (x, lk.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=2100)), slice(0, 2100)))
         return made[E]
     return get
 
 
+CHECKED = ("y", "departure", "hxmean", "value", "obs_used", "obs_check", "obs_rinv")
+
+
 def analyse(lt, x, out=None, **how):
-    """Letkf.analyse_grid on the NumPy ensemble x -> the increments and what the check read and wrote, as NumPy arrays"""
-    import torch
-    got = lt.analyse_grid(*ls.grids(x), out=out, **how)
-    torch.cuda.synchronize()
-    res = {v: a.cpu().numpy() for v, a in zip(lk.VARS, got)}
-    if lt.nobs:
-        res.update({n: lt.field(n).numpy() for n in ("y", "departure", "hxmean", "value", "obs_used", "obs_check", "obs_rinv")})
-    res["stats"] = lt.obs_stats()
-    return res
+    """lk.run with what the check read and wrote, and the statistics"""
+    return dict(lk.run(lt, x, out=out, names=CHECKED, **how), stats=lt.obs_stats())
 
 
 def restated(got, obs, gross, groups=None, ngroups=5, in_column=None, keep=None, depb=None, code=None):
@@ -92,7 +88,7 @@ def test_decisions_and_fields(E, nobs, plans, big):
     own chunk of 1024, and a network of more than two chunks"""
     sp, g = plans()
     x, all_obs = big(E)
-    obs = qc.subset(all_obs, slice(0, nobs))
+    obs = lk.subset(all_obs, slice(0, nobs))
     lt = lk.make(sp, E, obs, SIGMA_V)
     lt.set_background_check(GROSS)
     first = analyse(lt, x)
@@ -135,11 +131,11 @@ def test_analysis_equals_the_analysis_without_the_rejected(plans, big):
     got = analyse(lt, x)
     rejected = got["obs_check"] == qc.REJECTED
     assert rejected[outside].all() and 10 <= rejected.sum() < 100
-    without = lk.make(sp, E, qc.subset(obs, ~rejected), SIGMA_V)
-    ref = lk.analyse_grid(sp, without, x)
+    without = lk.make(sp, E, lk.subset(obs, ~rejected), SIGMA_V)
+    ref = lk.run(without, x)
     lt.set_background_check(0.0)
-    plain = lk.analyse_grid(sp, lt, x)
-    near = lk.in_range(g, qc.subset(obs, rejected)).any(axis=1)
+    plain = lk.run(lt, x)
+    near = lk.in_range(g, lk.subset(obs, rejected)).any(axis=1)
     assert near.sum() >= 64 and (~near).sum() >= 64
     for v in lk.VARS:
         assert support.same_bits(got[v], ref[v]) and ref[v].any(), v
@@ -167,7 +163,7 @@ def route(sp, lt, x, obs, in_column=None, keep=None, expect_rejections=True, **h
     assert same_decisions(eager, dec, obs), how
     assert qc.same_rows(table(eager["stats"]), rows), how
     assert bool((eager["obs_check"] == qc.REJECTED).any()) == expect_rejections
-    xs = ls.grids(x)
+    xs = lk.grids(x)
     out = [torch.empty_like(a) for a in xs]
     sp.use_own_stream()
     torch.cuda.synchronize()
@@ -276,7 +272,7 @@ def test_route_at_pressure(plans):
     x = lp.craft(g, E, 45)
     obs = gross_errors(lp.network(g, x), every=3)
     lt = lp.make(sp, E, obs, SIGMA_V)
-    in_column = lp.obs_space(g, x, obs)["obs_used"]
+    in_column = lk.obs_space(g, x, obs)["obs_used"]
     eager, nodes = route(sp, lt, x, obs, in_column=in_column)
     assert nodes == 2
     out = in_column == 0.0
@@ -324,7 +320,7 @@ def test_off_is_off(plans, oracle_factory):
     for kind, x, net, make in tool.networks(g8, E):
         lt = make(sp8, E, net, tool.SIGMA_V)
         lt.set_background_check(GROSS, np.arange(len(net["var"])) % 7)
-        ls.analyse(lt, x)
+        lk.run(lt, x)
         lt.set_background_check(0.0)
         assert tool.analysis(lt, x) == recorded["%s E=%d plain" % (kind, E)], kind
         lt.close()
@@ -373,11 +369,11 @@ def test_stats_only_call(plans, big):
     lt = lk.make(sp, E, obs, SIGMA_V)
     lt.set_background_check(GROSS)
     with pytest.raises(s.SpdyError) as err:
-        lt.stats_grid(1, *ls.grids(x))
+        lt.stats_grid(1, *lk.grids(x))
     assert err.value.code == -5 and "no analysis call with the check on" in str(err.value)
     got = analyse(lt, x)
     xa = {v: x[v] + got[v] for v in lk.VARS}
-    lt.stats_grid(3, *ls.grids(xa))
+    lt.stats_grid(3, *lk.grids(xa))
     torch.cuda.synchronize()
     after = {n: lt.field(n).numpy() for n in ("y", "departure", "obs_used", "obs_check", "obs_rinv")}
     for name in ("obs_used", "obs_check", "obs_rinv"):
@@ -392,7 +388,7 @@ def test_stats_only_call(plans, big):
     assert (oa[:, 5] < table(got["stats"])[:, 5]).all()      # the analysis fits the used observations better than the background
     lt.set_obs(*lk.args(obs))
     with pytest.raises(s.SpdyError):
-        lt.stats_grid(3, *ls.grids(xa))
+        lt.stats_grid(3, *lk.grids(xa))
     lt.close()
 
 
@@ -424,7 +420,8 @@ def test_twin_experiment(oracle_factory):
     nat.observe(lt, 1.0)
     value = lt.field("value").numpy()
     # the restatement alone, on the host's own operator
-    _, hxmean, Y, _ = lk.obs_space(g, x, net)
+    space = lk.obs_space(g, x, net)
+    hxmean, Y = space["hxmean"], space["y"]
     v = qc.spread2(Y) + net["error"] * net["error"]
     shifted = np.zeros(tc.NOBS, bool)
     shifted[np.random.default_rng(27).choice(tc.NOBS, tc.NOBS // 50, replace=False)] = True

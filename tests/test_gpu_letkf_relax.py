@@ -46,10 +46,11 @@ def test_kernel_against_restatement(E, kx, plans):
     worst, fmax = 0.0, 0.0
     for tag, obs in both_sets(g, x):
         lt = lk.make(sp, E, obs, SIGMA_V)
-        raw, _ = lr.analyse(lt, x)
+        raw = lk.run(lt, x)
         for rtpp, rtps in lr.SETTINGS:
             lt.set_relaxation(rtpp, rtps)
-            got, infl = lr.analyse(lt, x)
+            got = lk.run(lt, x)
+            infl = got["inflation"]
             w, f = lr.compare(x, raw, got, infl, rtpp, rtps, E)
             print("[letkf relax E=%d kx=%d %s rtpp=%.1f rtps=%.1f] ratio to the limit %.2e, largest f %.3f" % (E, kx, tag, rtpp, rtps, w, f))
             assert any(not support.same_bits(got[v], raw[v]) for v in lk.VARS), (tag, rtpp, rtps)
@@ -73,7 +74,8 @@ def test_untouched_columns_keep_their_bits(plans):
     lt = lk.make(sp, E, obs, SIGMA_V, rho=1.0)
     for rtpp, rtps in lr.SETTINGS + ((1.0, 1.0),):
         lt.set_relaxation(rtpp, rtps)
-        got, infl = lr.analyse(lt, x)
+        got = lk.run(lt, x)
+        infl = got["inflation"]
         for v in lk.VARS:
             assert lm.zero_bits(lk.at_columns(got[v], far)), (rtpp, rtps, v)
             assert lk.at_columns(got[v], near).any(), (rtpp, rtps, v)
@@ -90,7 +92,8 @@ def test_rtpp_one_moves_only_the_mean(E, plans):
     lt = lk.make(sp, E, mixed(g, x), SIGMA_V)
     for rtps in (0.0, 0.9):
         lt.set_relaxation(1.0, rtps)
-        got, infl = lr.analyse(lt, x)
+        got = lk.run(lt, x)
+        infl = got["inflation"]
         for v in lk.VARS:
             assert lr.same_bits_everywhere(got[v]) and got[v].any(), (rtps, v)
         assert (infl == 1.0).all(), rtps
@@ -104,11 +107,11 @@ def test_both_zero_is_the_analysis_it_was(plans):
     x = lk.ensemble(g, E, seed=E)
     obs = mixed(g, x)
     never, lt = lk.make(sp, E, obs, SIGMA_V), lk.make(sp, E, obs, SIGMA_V)
-    ref, _ = lr.analyse(never, x)
+    ref = lk.run(never, x)
     lt.set_relaxation(0.3, 0.9)
-    relaxed, _ = lr.analyse(lt, x)
+    relaxed = lk.run(lt, x)
     lt.set_relaxation(0.0, 0.0)
-    got, _ = lr.analyse(lt, x)
+    got = lk.run(lt, x)
     for v in lk.VARS:
         assert support.same_bits(got[v], ref[v]) and not support.same_bits(relaxed[v], ref[v]), v
     never.close(); lt.close()
@@ -139,7 +142,8 @@ def test_outputs_may_be_the_inputs(stride, plans):
     lt = lk.make(sp, E, mixed(g, x), SIGMA_V)
     lt.set_weight_stride(*stride)
     lt.set_relaxation(0.3, 0.9)
-    ref, finf = lr.analyse(lt, x)
+    ref = lk.run(lt, x)
+    finf = ref["inflation"]
     xs = [support.dev(x[v]) for v in lk.VARS]
     lt.analyse_grid(*xs, out=xs)
     torch.cuda.synchronize()
@@ -181,8 +185,10 @@ def test_masked_equals_compact(E, keep, plans):
     for rtpp, rtps in ((0.3, 0.9), (0.0, 0.9)):
         lt.set_relaxation(rtpp, rtps)
         ltc.set_relaxation(rtpp, rtps)
-        got, infl = lr.analyse(lt, x, lm.flags(E, keep))
-        ref, finf = lr.analyse(ltc, xc)
+        got = lk.run(lt, x, lm.flags(E, keep))
+        infl = got["inflation"]
+        ref = lk.run(ltc, xc)
+        finf = ref["inflation"]
         for v in lk.VARS:
             assert support.same_bits(np.ascontiguousarray(got[v][list(keep)]), ref[v]) and ref[v].any(), (rtpp, rtps, v)
             assert lm.zero_bits(got[v][drop]), (rtpp, rtps, v)
@@ -190,7 +196,8 @@ def test_masked_equals_compact(E, keep, plans):
     y = {v: a.copy() for v, a in x.items()}
     for v in lk.VARS:
         y[v][drop] = np.nan
-    again, ainf = lr.analyse(lt, y, lm.flags(E, keep))
+    again = lk.run(lt, y, lm.flags(E, keep))
+    ainf = again["inflation"]
     for v in lk.VARS:
         assert support.same_bits(again[v], got[v]), v
     assert support.same_bits(ainf, infl)
@@ -206,7 +213,8 @@ def test_one_member_in_use(stride, plans):
     lt = lk.make(sp, E, lk.clustered_obs(g, x, n=300), SIGMA_V)
     lt.set_weight_stride(*stride)
     lt.set_relaxation(0.3, 0.9)
-    got, infl = lr.analyse(lt, x, lm.flags(E, (2,)))
+    got = lk.run(lt, x, lm.flags(E, (2,)))
+    infl = got["inflation"]
     for v in lk.VARS:
         assert lm.zero_bits(got[v]), v
     assert (infl == 1.0).all()
@@ -245,9 +253,9 @@ def test_ensemble_state(plans, oracle_factory):
     torch.cuda.synchronize()
     gx = grids_of(sp, lt, E)
     lt.set_relaxation(0.3, 0.9)
-    ref, _ = lr.analyse(lt, gx)
+    ref = lk.run(lt, gx)
     lt.set_relaxation(0.0, 0.0)
-    plain, _ = lr.analyse(lt, gx)
+    plain = lk.run(lt, gx)
     lt.set_relaxation(0.3, 0.9)
     ens.analyse(lt)
     torch.cuda.synchronize()

@@ -67,19 +67,19 @@ def test_same_state_is_the_plain_call(case, plans):
     sp, g = plans()
     if pres:
         x, obs = pressure_case(g, E)
-        used = lp.obs_space(g, x, obs)["obs_used"]
+        used = lk.obs_space(g, x, obs)["obs_used"]
         assert (used == 0.0).sum() >= 10 and (used == 1.0).sum() >= 100          # a station is out of some member's column
     else:
         x = lk.ensemble(g, E, seed=E)
         obs = lk.clustered_obs(g, x)
     n = len(obs["var"])
     use = None if keep is None else lm.flags(E, keep)
-    xd = ls.grids(x)
+    xd = lk.grids(x)
     for sigma_v in sigma_vs:
         plain, lt = make(sp, E, obs, sigma_v, stride, relax), make(sp, E, obs, sigma_v, stride, relax)
-        ref = ls.analyse(plain, x, use)
+        ref = lk.run(plain, x, use)
         ls.observe_all(lt, [xd] * 4, ls.FIRST(n))
-        got = ls.analyse(lt, x, use, slots=True)
+        got = lk.run(lt, x, use, slots=True)
         assert set(got) == set(ref) and ("inflation" in ref) == (relax is not None) and ("weights" in ref) == (stride is not None)
         same(got, ref, sorted(ref), (tag, sigma_v))
         assert all(ref[v].any() for v in lk.VARS) and ref["members_used"].tolist() == [float(E if keep is None else len(keep))]
@@ -88,7 +88,7 @@ def test_same_state_is_the_plain_call(case, plans):
         # statement 4: one slot is no slot
         lt.set_slots([0, n])
         lt.observe_grid(0, *xd)
-        same(ls.analyse(lt, x, use, slots=True), ref, sorted(ref), (tag, sigma_v, "one slot"))
+        same(lk.run(lt, x, use, slots=True), ref, sorted(ref), (tag, sigma_v, "one slot"))
         plain.close(); lt.close()
 
 
@@ -98,9 +98,9 @@ def test_no_observation_is_the_plain_call(plans):
     E = 3
     x = lk.ensemble(g, E, seed=1)
     lt = lk.make(sp, E, lk.make_obs([], [], [], [], [], []), 0.1, rho=1.0)
-    ref = ls.analyse(lt, x)
+    ref = lk.run(lt, x)
     lt.set_slots([0, 0, 0])
-    got = ls.analyse(lt, x, slots=True)
+    got = lk.run(lt, x, slots=True)
     for v in lk.VARS:
         assert support.same_bits(got[v], ref[v]) and lm.zero_bits(got[v]), v
     lt.close()
@@ -132,23 +132,24 @@ def test_same_state_from_spectra(plans, oracle_factory):
     torch.cuda.synchronize()
     for n in es.PROG:
         assert support.same_bits(getattr(ens, n), getattr(copy, n)) and not support.same_bits(getattr(ens, n)[0], before[n][0]), n
-    for n in ls.FIELDS:
+    for n in lk.FIELDS:
         assert support.same_bits(lt.field(n).numpy(), plain.field(n).numpy()), n
     lt.close(); plain.close()
 
 
 # ---------------------------------------------------------------------------------------------------- 2. different times
 def held_to_the_restatement(sp, g, lt, x, xs, obs, first, E, sigma_v, tag, most=32):
-    """The slots observed on xs, the analysis on x = xs[-1], against tests/letkfslots.py with the library's own stencils: hx, slot_ps,
+    """The slots observed on xs, the analysis on x = xs[-1], against tests/letkf.py with the library's own stencils: hx, slot_ps,
     slot_out and obs_used exactly; hxmean, y, departure and obs_lnsigma within 16 eps of their scale; every variable's increments
     within lk.limits(...) on the restatement's C and b and the analysis-time ensemble, at the columns lk.columns_for picks
     -> the restatement's obs_space dict and the largest ratio of an error to its limit"""
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=most)
-    C, b, want = ls.problems_slots(g, xs, obs, first, lk.SIGMA_H, sigma_v, cols, stencil=lp.tables(lt))
+    want = lk.obs_space(g, x, obs, stencil=lp.tables(lt), xs=xs, first=first)
+    C, b = lk.problems(g, obs, want, lk.SIGMA_H, sigma_v, cols)
     lim, ref, kappa = lk.limits(g, x, C, b, lk.RHO, cols, E)
     ls.observe_all(lt, xs, first)
-    got = ls.analyse(lt, x, slots=True, names=ls.FIELDS + ("slot_ps", "slot_out"))
-    for n in ("hx", "obs_used") + (("slot_ps", "slot_out") if ls.at_pressure(obs).any() else ()):
+    got = lk.run(lt, x, slots=True, names=lk.FIELDS + ("slot_ps", "slot_out"))
+    for n in ("hx", "obs_used") + (("slot_ps", "slot_out") if lk.at_pressure(obs).any() else ()):
         assert support.same_bits(got[n], want[n]), (tag, n)
     scale = np.array([np.max(np.abs(x[lk.VARS[v]])) for v in obs["var"]])
     lnscale = np.maximum(np.abs(want["obs_lnsigma"]), 1.0)
@@ -172,7 +173,7 @@ def test_different_times_against_restatement(E, plans):
     for tag, obs, first in (("clustered", lk.clustered_obs(g, x), [0, 300, 701, 1500]), ("sparse", lk.sparse_obs(g, x), [0, 20, 41, 60])):
         lt = lk.make(sp, E, obs, 0.1)
         want, got = held_to_the_restatement(sp, g, lt, x, xs, obs, first, E, 0.1, "E=%d %s" % (E, tag))
-        now = lk.obs_space(g, x, obs)[0]
+        now = lk.observe(g, x, obs)[0]
         assert np.max(np.abs(want["hx"][:first[1]] - now[:first[1]])) > 1e-3 and support.same_bits(got["hx"][first[2]:], want["hx"][first[2]:])
         lt.close()
 
@@ -192,7 +193,7 @@ def test_different_times_at_pressure(plans):
     lt = lp.make(sp, E, obs, 0.1)
     want, got = held_to_the_restatement(sp, g, lt, x, xs, obs, first, E, 0.1, "E=4 at pressure")
     assert want["slot_out"][o].tolist() == [1.0 if e == member else 0.0 for e in range(E)] and want["obs_used"][o] == 0.0
-    assert lp.obs_space(g, x, obs, lp.tables(lt))["obs_used"][o] == 1.0
+    assert lk.obs_space(g, x, obs, stencil=lp.tables(lt))["obs_used"][o] == 1.0
     assert got["obs_used"][o] == 0.0 and (got["obs_used"] == 0.0).sum() >= 10 and (got["obs_used"] == 1.0).sum() >= 100
     lt.close()
 
@@ -225,9 +226,10 @@ def test_an_observe_writes_its_rows_only(kind, plans):
     written = ls.SLOT_FIELDS if kind == "pressure" else ("hx",)
     seen = {}
     for tag, y in (("first", x), ("second", ls.drifting(g, x, 2, seed=3)[0])):
-        lt.observe_grid(2, *ls.grids(y))
+        lt.observe_grid(2, *lk.grids(y))
         now = {name: lt.field(name).numpy() for name in names}
-        want = ls.observe_slot(g, y, obs, slice(r0, r1), lp.tables(lt))
+        idx, wgt = lp.tables(lt)
+        want = lk.observe(g, y, lk.subset(obs, slice(r0, r1)), (idx[r0:r1], wgt[r0:r1]), kind == "pressure")
         for name in names:
             if name in written:
                 assert support.same_bits(now[name][:r0], sent[name][:r0]) and support.same_bits(now[name][r1:], sent[name][r1:]), (tag, name)
@@ -250,16 +252,16 @@ def test_a_member_dropped_at_the_analysis_may_hold_anything(kind, plans):
     keep = tuple(e for e in range(E) if e != drop)
     if kind == "pressure":
         x = lp.craft(g, E, seed=27)
-        obs = lp.network(g, lm.compact(x, keep))
+        obs = lp.network(g, lk.compact(x, keep))
     else:
         x = lk.ensemble(g, E, seed=8)
-        obs = lk.concat(lk.clustered_obs(g, lm.compact(x, keep), n=600), lk.sparse_obs(g, lm.compact(x, keep)))
+        obs = lk.concat(lk.clustered_obs(g, lk.compact(x, keep), n=600), lk.sparse_obs(g, lk.compact(x, keep)))
     n = len(obs["var"])
     first = [0, 150, 333, n]
     xs = ls.drifting(g, x, 3, seed=12)
     lt, ltc = make(sp, E, obs, 0.1), make(sp, len(keep), obs, 0.1)
-    ls.observe_all(ltc, [lm.compact(a, keep) for a in xs], first)
-    ref = ls.analyse(ltc, lm.compact(x, keep), slots=True)
+    ls.observe_all(ltc, [lk.compact(a, keep) for a in xs], first)
+    ref = lk.run(ltc, lk.compact(x, keep), slots=True)
     if kind == "pressure":
         assert (ref["obs_used"] == 0.0).sum() >= 5 and (ref["obs_used"] == 1.0).sum() >= 100
     for bad in ("nan", "inf", "1e300"):
@@ -269,7 +271,7 @@ def test_a_member_dropped_at_the_analysis_may_hold_anything(kind, plans):
                 for f in y[v][drop].reshape((-1,) + y[v].shape[-2:]):
                     poison.poison(f, bad)
         ls.observe_all(lt, ys, first)
-        got = ls.analyse(lt, ys[2], lm.flags(E, keep), slots=True)
+        got = lk.run(lt, ys[2], lm.flags(E, keep), slots=True)
         lm.same_as_compact(got, ref, E, keep, (kind, bad))
     lt.close(); ltc.close()
 
@@ -288,7 +290,7 @@ def test_refusals_enqueue_nothing(plans, oracle_factory):
     ens.analyse(lt)                                           # fields of a plain call to be kept
     torch.cuda.synchronize()
     before = {k: getattr(ens, k).clone() for k in es.PROG}
-    fields = {k: lt.field(k).numpy() for k in ls.FIELDS}
+    fields = {k: lt.field(k).numpy() for k in lk.FIELDS}
     lt.set_slots([0, 5, 5, n])
     ens.observe(lt, 0)
     ens.observe(lt, 1)                                        # the empty one
@@ -304,7 +306,7 @@ def test_refusals_enqueue_nothing(plans, oracle_factory):
     torch.cuda.synchronize()
     for k in es.PROG:
         assert support.same_bits(getattr(ens, k), before[k]), k
-    for k in ls.FIELDS:
+    for k in lk.FIELDS:
         assert support.same_bits(lt.field(k).numpy(), fields[k]), k
     assert all(bool((a == 7.0).all()) for a in out)
     ens.observe(lt, 2)
@@ -341,9 +343,9 @@ def test_capture(E, plans):
     for tag, seed in (("a", 1), ("b", 2)):
         xs = ls.drifting(g, x if tag == "a" else lk.ensemble(g, E, seed=77), 2, seed=seed)
         ls.observe_all(lt, xs, first)
-        eager[tag] = (xs, ls.analyse(lt, xs[1], slots=True))
+        eager[tag] = (xs, lk.run(lt, xs[1], slots=True))
     assert not support.same_bits(eager["a"][1]["t"], eager["b"][1]["t"])
-    xa, xb = (ls.grids(y) for y in eager["a"][0])
+    xa, xb = (lk.grids(y) for y in eager["a"][0])
     out = tuple(torch.empty_like(a) for a in xb)
     lt.set_slots(first)
     sp.use_own_stream()
@@ -364,7 +366,7 @@ def test_capture(E, plans):
         assert base == 2 and gr.num_nodes() == base + 2, (base, gr.num_nodes())
         runs = []
         for tag in ("a", "a", "b"):
-            for dst, src in zip(xa + xb, ls.grids(eager[tag][0][0]) + ls.grids(eager[tag][0][1])):
+            for dst, src in zip(xa + xb, lk.grids(eager[tag][0][0]) + lk.grids(eager[tag][0][1])):
                 dst.copy_(src)
             for name in ("hx", "y", "hxmean", "departure"):
                 f = lt.field(name)
@@ -375,10 +377,10 @@ def test_capture(E, plans):
             gr.launch()
             sp.synchronize()
             got = {v: a.cpu().numpy() for v, a in zip(lk.VARS, out)}
-            got.update({name: lt.field(name).numpy() for name in ls.FIELDS})
-            same(got, eager[tag][1], lk.VARS + ls.FIELDS, (E, tag))
+            got.update({name: lt.field(name).numpy() for name in lk.FIELDS})
+            same(got, eager[tag][1], lk.VARS + lk.FIELDS, (E, tag))
             runs.append(got)
-        same(runs[0], runs[1], lk.VARS + ls.FIELDS, (E, "replays"))
+        same(runs[0], runs[1], lk.VARS + lk.FIELDS, (E, "replays"))
         gr.close()
     finally:
         sp.use_torch_stream()
@@ -409,7 +411,7 @@ def test_nature_observes_a_slot(kind, plans):
         nat.field("truth").upload(nt.rows(truths[max(d - 1, 0)]))
         nat.observe(lt, noise)
         whole.append(lt.field("value").numpy())
-    assert nat.draws() == 4 and support.same_bits(whole[1], lp.truth_values(g, truths[0], ls.with_p(obs), lp.tables(lt)))
+    assert nat.draws() == 4 and support.same_bits(whole[1], lp.truth_values(g, truths[0], obs, lp.tables(lt)))
     assert not support.same_bits(whole[2][300:], whole[3][300:])
     lt.set_slots(first)
     sent = np.random.default_rng(4).standard_normal(n) + 500.0

@@ -373,7 +373,7 @@ def test_twin_condition_on_the_device():
     # the restatement, fed the device's values
     obs = dict(net)
     obs["value"] = value
-    C, b = lk.problems(g, x, obs, c["sigma_h"], c["sigma_v"])
+    C, b = lk.problems(g, obs, lk.obs_space(g, x, obs), c["sigma_h"], c["sigma_v"])
     lim, ref_inc, kappa = lk.limits(g, x, C, b, c["rho"], np.arange(g.ix * g.il), E)
     worst = {v: float(np.max(np.abs(lk.at_columns(a.cpu().numpy(), np.arange(g.ix * g.il)) - ref_inc[v]))) / lim[v]
              for v, a in zip(lk.VARS, inc)}

@@ -13,7 +13,6 @@ import letkf as lk
 import letkfmask as lm
 import letkfpressure as lp
 import letkfrelax as lr
-import letkfslots as ls
 import nature as nt
 import support
 import synth
@@ -153,7 +152,7 @@ def run(plan, oracle_factory):
         ens.analyse(lt, slots=True)
         ens.verify(lt, nat, 2 * c + 1)
         win["scores_a"] = the_scores(sp, g, w, lt, nat, 2 * c + 1, R["ratios"], "window %d analysis" % c)
-        win["fields"] = {n: lt.field(n).numpy() for n in ls.FIELDS}
+        win["fields"] = {n: lt.field(n).numpy() for n in lk.FIELDS}
         win["analysed"] = clones(ens)
         win["table"] = nat.field("scores").numpy()
         ens.startup(DELT)
@@ -231,9 +230,9 @@ def test_the_date_of_a_slot(run, plan):
         ref = run["host"]["w%d" % c]
         for sl, n in enumerate(tc.SLOT_STEPS):
             rec, rows = run["dev"]["w%d" % c]["slots"][sl], tc.rows(sl)
-            assert support.same_bits(rec["hx"][rows], ls.observe_slot(g, rec["grid"], net, rows, stencil)[0]), (c, sl)
-            assert support.same_bits(rec["value0"][rows], lp.truth_values(g, rec["truth0"], lp.subset(ls.with_p(net), rows),
-                                                                          (stencil[0][rows], stencil[1][rows]))), (c, sl)
+            sub, st = lk.subset(net, rows), (stencil[0][rows], stencil[1][rows])
+            assert support.same_bits(rec["hx"][rows], lk.observe(g, rec["grid"], sub, st)[0]), (c, sl)
+            assert support.same_bits(rec["value0"][rows], lp.truth_values(g, rec["truth0"], sub, st)), (c, sl)
             h = nt.operator(g, ref["xt"][n], net)[rows]
             scale = np.array([np.max(np.abs(ref["xt"][n][lk.VARS[v]])) for v in net["var"][rows]])
             near = max(near, float(np.max(np.abs(rec["value0"][rows] - h) / ((TOL + 16 * lk.EPS) * scale))))
@@ -294,9 +293,10 @@ def test_the_analysis_on_forecast_states(run, plan, oracle_factory):
     obs = dict(net, value=lt.field("value").numpy())
     assert support.same_bits(obs["value"], run["dev"]["w0"]["value"]) and support.same_bits(lt.field("hx").numpy(), run["dev"]["w0"]["hx"])
     cols = lk.columns_for(g, obs, tc.SIGMA_H, most=32)
-    C, b, want = ls.problems_slots(g, xs, obs, tc.FIRST, tc.SIGMA_H, tc.SIGMA_V, cols, stencil=lp.tables(lt))
+    want = lk.obs_space(g, x, obs, stencil=lp.tables(lt), xs=xs, first=tc.FIRST)
+    C, b = lk.problems(g, obs, want, tc.SIGMA_H, tc.SIGMA_V, cols)
     lim, ref, kappa = lk.limits(g, x, C, b, tc.RHO, cols, E)
-    got = ls.analyse(lt, x, slots=True)
+    got = lk.run(lt, x, slots=True)
     for n in ("hx", "obs_used"):
         assert support.same_bits(got[n], want[n]), n
     scale = np.array([np.max(np.abs(x[lk.VARS[v]])) for v in obs["var"]])
@@ -311,7 +311,7 @@ def test_the_analysis_on_forecast_states(run, plan, oracle_factory):
     assert max(ratios.values()) <= 1.0, ratios
     # the route a cycle would use: relaxed
     lt.set_relaxation(0.3, 0.9)
-    relaxed = ls.analyse(lt, x, slots=True)
+    relaxed = lk.run(lt, x, slots=True)
     raw = {v: got[v] for v in lk.VARS}
     rel, fmax = lr.compare(x, raw, {v: relaxed[v] for v in lk.VARS}, relaxed["inflation"], 0.3, 0.9, E)
     print("[twin cycle] relaxed analysis (0.3, 0.9): ratio to the limit %.3e, largest inflation %.3f" % (rel, fmax))
@@ -321,7 +321,7 @@ def test_the_analysis_on_forecast_states(run, plan, oracle_factory):
     before = clones(ens)
     ens.analyse(lt, slots=True)
     torch.cuda.synchronize()
-    for n in ls.FIELDS:
+    for n in lk.FIELDS:
         assert support.same_bits(lt.field(n).numpy(), got[n]), n
     hosted = tc.add_increments(o, tc.host_states(host(before, 0), host(before, 1), {}), {v: got[v] for v in lk.VARS})
     e = tc.spectral_errors(host(clones(ens), 0), hosted, 0)
@@ -417,7 +417,7 @@ def test_the_window_in_one_graph(run, plan):
             for n in es.PROG:
                 assert support.same_bits(getattr(ens, n), eager["analysed"][n]), (r, n)
             assert support.same_bits(lt.field("value").numpy(), eager["value"]), r
-            for n in ls.FIELDS:
+            for n in lk.FIELDS:
                 assert support.same_bits(lt.field(n).numpy(), eager["fields"][n]), (r, n)
             assert support.same_bits(nat.field("scores").numpy()[:2], eager["table"][:2]), r
             assert nat.draws() == 3

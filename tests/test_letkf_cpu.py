@@ -300,18 +300,21 @@ def test_tables_against_the_restatement(host):
 
 
 def test_local_problems_are_problems(host):
-    """the column-by-column form adds the same terms in the same order: C and b bit-equal to `problems`, at columns in range of a
-    cluster, at the edge of its range and out of range, with and without the vertical factor"""
+    """an observation is added at the columns it reaches and nowhere else, so a column's C and b do not depend on which other columns
+    are asked for: `problems` at a subset of columns is `problems` at all columns restricted to that subset, bit for bit -- at columns
+    in range of a cluster, at the edge of its range and out of range, with and without the vertical factor; an empty network gives
+    zero"""
     _, _, g = host
     x = lk.ensemble(g, 4, seed=44)
     obs = lk.concat(lk.clustered_obs(g, x, n=300), lk.sparse_obs(g, x))
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=24, outside=6)
+    s = lk.obs_space(g, x, obs)
     for sigma_v in (0.0, 0.1):
-        C, b = lk.problems(g, x, obs, lk.SIGMA_H, sigma_v, cols)
-        Cl, bl = lk.local_problems(g, x, obs, lk.SIGMA_H, sigma_v, cols)
-        assert C.any() and not C[-1].any() and support.same_bits(C, Cl) and support.same_bits(b, bl), sigma_v
+        C, b = lk.problems(g, obs, s, lk.SIGMA_H, sigma_v)
+        Cl, bl = lk.problems(g, obs, s, lk.SIGMA_H, sigma_v, cols)
+        assert Cl.any() and not Cl[-1].any() and support.same_bits(C[cols], Cl) and support.same_bits(b[cols], bl), sigma_v
     none = lk.make_obs([], [], [], [], [], [])
-    assert not lk.local_problems(g, x, none, lk.SIGMA_H, 0.1, cols)[0].any()
+    assert not lk.problems(g, none, lk.obs_space(g, x, none), lk.SIGMA_H, 0.1, cols)[0].any()
 
 
 def test_edge_inputs(host):
@@ -342,15 +345,15 @@ def test_padded_inputs_and_the_order_of_the_sums(host):
     assert acted.sum() >= 20 and not (acted & far).any()
     cluster = lk.in_range(g, {k: v[:320] for k, v in real.items()}).any(axis=1)
     cols = np.concatenate([np.nonzero(cluster)[0][::4], np.nonzero(far & ~cluster)[0][::300]])
-    C, b = lk.local_problems(g, x, real, lk.SIGMA_H, 0.1, cols)
+    C, b = lk.problems(g, real, lk.obs_space(g, x, real), lk.SIGMA_H, 0.1, cols)
     for pattern in lk.PATTERNS:
         obs, at = lk.interleave(real, pad, pattern)
-        Cp, bp = lk.local_problems(g, x, obs, lk.SIGMA_H, 0.1, cols)
+        Cp, bp = lk.problems(g, obs, lk.obs_space(g, x, obs), lk.SIGMA_H, 0.1, cols)
         assert support.same_bits(C, Cp) and support.same_bits(b, bp), pattern
     moved = {k: v.copy() for k, v in real.items()}
     for k in moved:
         moved[k][[0, 200]] = moved[k][[200, 0]]
-    Cm, _ = lk.local_problems(g, x, moved, lk.SIGMA_H, 0.1, cols)
+    Cm, _ = lk.problems(g, moved, lk.obs_space(g, x, moved), lk.SIGMA_H, 0.1, cols)
     assert not support.same_bits(C, Cm) and np.max(np.abs(C - Cm)) <= 1e-12 * np.max(np.abs(C))
 
 
@@ -365,7 +368,7 @@ def test_hard_inputs_on_the_grid(E, host):
     for factor in (1e-3, 3e-5):
         obs = lk.hard_obs(g, x, factor)
         cols = lk.columns_for(g, obs, lk.SIGMA_H, most=16, outside=2)
-        C, _ = lk.local_problems(g, x, obs, lk.SIGMA_H, 0.0, cols)
+        C, _ = lk.problems(g, obs, lk.obs_space(g, x, obs), lk.SIGMA_H, 0.0, cols)
         A = C[:, 0] + ((E - 1) / lk.RHO) * np.eye(E)                          # no vertical factor: every level has the same A
         assert support.same_bits(C[:, 0], C[:, g.kx - 1])
         lam, _, ran = lk.jacobi(A, counts=True)

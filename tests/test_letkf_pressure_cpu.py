@@ -86,7 +86,7 @@ def test_crafted_inputs_hold_every_class(kx, hosts):
         x = lp.craft(g, E, seed=7 + E)
         obs = lp.network(g, x)
         assert lp.classes(g, x, obs) == lp.every_class(kx), (kx, E, lp.classes(g, x, obs) ^ lp.every_class(kx))
-        s = lp.obs_space(g, x, obs)
+        s = lk.obs_space(g, x, obs)
         atp = lp.at_pressure(obs)
         assert (550 <= len(obs["var"]) <= 650 if kx == 8 else len(obs["var"]) > 200) and atp.sum() >= 150 and (~atp).sum() >= 50
         assert (s["obs_used"][~atp] == 1.0).all() and 10 <= (s["obs_used"] == 0.0).sum() < atp.sum() / 2
@@ -221,7 +221,7 @@ def test_spectral_inputs_keep_clear_of_the_end_levels(E, hosts, oracle_factory):
     sp, g = get(5)
     sts, x, net = lp.spectral_case(sp, oracle_factory("t30k5"), g, E)
     m = lp.margin(g, x, net)
-    used = lp.obs_space(g, x, net)["obs_used"]
+    used = lk.obs_space(g, x, net)["obs_used"]
     print("[pobs spectral inputs E=%d] margin %.3e, %d of %d used" % (E, m, int(used.sum()), len(used)))
     assert m >= lp.MARGIN and lp.at_pressure(net).all() and 0.2 * len(used) <= used.sum() <= 0.9 * len(used)
 
@@ -238,9 +238,9 @@ def test_twin_condition_on_the_restatement():
     truth, x, net = lp.twin_inputs(g)
     h = lp.truth_values(g, truth, net)
     net["value"] = h + net["error"] * np.random.default_rng(lp.TWIN_VALUE_SEED).standard_normal(len(h))
-    used = lp.obs_space(g, x, net)["obs_used"]
+    used = lk.obs_space(g, x, net)["obs_used"]
     assert used.sum() == 3 * 3 * lp.TWIN_STATIONS and len(h) == 7 * 3 * lp.TWIN_STATIONS
-    C, b = lp.problems(g, x, net, c["sigma_h"], c["sigma_v"])
+    C, b = lk.problems(g, net, lk.obs_space(g, x, net), c["sigma_h"], c["sigma_v"])
     inc, _ = lk.increments(g, x, C, b, c["rho"])
     ratios = lp.twin_ratios(g, x, inc, truth, w)
     print("[pobs twin, restatement] rmse analysis / background: %s" % " ".join("%s %s" % (v, np.round(r, 3)) for v, r in ratios.items()))

@@ -71,18 +71,22 @@ def test_rejected_observation_takes_no_part():
     E = 5
     x = lk.ensemble(g, E, seed=3)
     obs = lk.clustered_obs(g, x, n=120)
-    _, hxmean, Y, _ = lk.obs_space(g, x, obs)
-    obs["value"], outside, inside = qc.plant(obs, hxmean, qc.spread2(Y), 3.0, seed=1)
+    sp0 = lk.obs_space(g, x, obs)
+    obs["value"], outside, inside = qc.plant(obs, sp0["hxmean"], qc.spread2(sp0["y"]), 3.0, seed=1)
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=12, outside=2)
-    _, _, Y, d = lk.obs_space(g, x, obs)
-    dec = qc.check(Y, d, obs["error"], 3.0)
+    sp1 = lk.obs_space(g, x, obs)
+    dec = qc.check(sp1["y"], sp1["departure"], obs["error"], 3.0)
     assert not dec["used"][outside].any() and dec["used"][inside].all() and len(outside) == len(inside) == 10
-    C, b = qc.problems(g, x, obs, qc.reff(dec["used"], 1.0 / (obs["error"] * obs["error"])), lk.SIGMA_H, SIGMA_V, cols)
-    Cs, bs = lk.problems(g, x, qc.subset(obs, dec["used"]), lk.SIGMA_H, SIGMA_V, cols)
-    Ca, _ = lk.problems(g, x, obs, lk.SIGMA_H, SIGMA_V, cols)
+    r_eff = qc.reff(dec["used"], 1.0 / (obs["error"] * obs["error"]))
+    C, b = lk.problems(g, obs, sp1, lk.SIGMA_H, SIGMA_V, cols, r_eff=r_eff)
+    used = lk.subset(obs, dec["used"])
+    Cs, bs = lk.problems(g, used, lk.obs_space(g, x, used), lk.SIGMA_H, SIGMA_V, cols)
+    Ca, _ = lk.problems(g, obs, sp1, lk.SIGMA_H, SIGMA_V, cols)
     assert support.same_bits(C, Cs) and support.same_bits(b, bs) and not support.same_bits(C, Ca)
-    dx, dec2 = qc.analyse(g, x, obs, 3.0, lk.SIGMA_H, SIGMA_V, lk.RHO, cols)
-    ref, _ = lk.analyse(g, x, qc.subset(obs, dec["used"]), lk.SIGMA_H, SIGMA_V, lk.RHO, cols=cols)
+    sp2 = lk.obs_space(g, x, obs)                  # the checked analysis: the decisions on the restatement's own y and departure
+    dec2 = qc.check(sp2["y"], sp2["departure"], obs["error"], 3.0)
+    dx, _ = lk.analyse(g, x, obs, lk.SIGMA_H, SIGMA_V, lk.RHO, cols=cols, r_eff=qc.reff(dec2["used"], 1.0 / (obs["error"] * obs["error"])))
+    ref, _ = lk.analyse(g, x, used, lk.SIGMA_H, SIGMA_V, lk.RHO, cols=cols)
     assert (dec2["check"] == dec["check"]).all()
     for v in lk.VARS:
         assert support.same_bits(dx[v], ref[v]) and dx[v].any(), v

@@ -39,26 +39,26 @@ def test_same_state_is_the_plain_analysis(plan):
     obs = lk.concat(lk.clustered_obs(g, x, n=320), lk.sparse_obs(g, x))
     n = len(obs["var"])
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=12, outside=4)
-    hx, hxmean, Y, d = lk.obs_space(g, x, obs)
-    Cp, bp = lk.problems(g, x, obs, lk.SIGMA_H, SIGMA_V, cols)
+    plain = lk.obs_space(g, x, obs)
+    Cp, bp = lk.problems(g, obs, plain, lk.SIGMA_H, SIGMA_V, cols)
     want, _ = lk.analyse(g, x, obs, lk.SIGMA_H, SIGMA_V, lk.RHO, cols=cols)
     for first in (ls.FIRST(n), [0, n], [0, 0, n, n]):
         xs = [x] * (len(first) - 1)
-        C, b, s = ls.problems_slots(g, xs, obs, first, lk.SIGMA_H, SIGMA_V, cols)
-        same_dict(s, {"hx": hx, "hxmean": hxmean, "y": Y, "departure": d, "obs_lnsigma": lk.lnsigma(g, obs), "obs_used": np.ones(n)},
-                  ls.FIELDS)
+        s = lk.obs_space(g, x, obs, xs=xs, first=first)
+        C, b = lk.problems(g, obs, s, lk.SIGMA_H, SIGMA_V, cols)
+        same_dict(s, dict(plain, obs_lnsigma=lk.lnsigma(g, obs), obs_used=np.ones(n)), lk.FIELDS)
         assert support.same_bits(C, Cp) and support.same_bits(b, bp) and not s["slot_ps"].any() and not s["slot_out"].any()
-        got, _ = ls.analyse_slots(g, x, xs, obs, first, lk.SIGMA_H, SIGMA_V, lk.RHO, cols=cols)
+        got, _ = lk.analyse(g, x, obs, lk.SIGMA_H, SIGMA_V, lk.RHO, cols=cols, xs=xs, first=first)
         same_dict(got, want, lk.VARS)
     none = lk.make_obs([], [], [], [], [], [])
-    got, _ = ls.analyse_slots(g, x, [x], none, [0, 0], lk.SIGMA_H, SIGMA_V, 1.0, cols=cols)
+    got, _ = lk.analyse(g, x, none, lk.SIGMA_H, SIGMA_V, 1.0, cols=cols, xs=[x], first=[0, 0])
     want, _ = lk.analyse(g, x, none, lk.SIGMA_H, SIGMA_V, 1.0, cols=cols)
     same_dict(got, want, lk.VARS)
     assert all(np.max(np.abs(a)) <= 64 * E * lk.EPS * lk.perturbation_scale(x)[v] for v, a in got.items())
 
 
 def test_same_state_is_the_plain_analysis_at_pressure(plan):
-    """statement 1 for tests/letkfpressure.py's crafted network: lp.obs_space's fields and lp.problems' C and b bit for bit; the
+    """statement 1 for tests/letkfpressure.py's crafted network: the plain call's fields and its C and b bit for bit; the
     per-member rows say what the shared fields say -- obs_used == 0 exactly where a member's flag is set, and ln sigma_o from the
     mean of slot_ps"""
     _, g = plan
@@ -67,12 +67,13 @@ def test_same_state_is_the_plain_analysis_at_pressure(plan):
     obs = lp.network(g, x)
     n = len(obs["var"])
     cols = lk.columns_for(g, obs, lk.SIGMA_H, most=12, outside=4)
-    want = lp.obs_space(g, x, obs)
-    Cp, bp = lp.problems(g, x, obs, lk.SIGMA_H, SIGMA_V, cols)
+    want = lk.obs_space(g, x, obs)
+    Cp, bp = lk.problems(g, obs, want, lk.SIGMA_H, SIGMA_V, cols)
     assert (want["obs_used"] == 0.0).sum() >= 10
     for first in (ls.FIRST(n), [0, n]):
-        C, b, s = ls.problems_slots(g, [x] * (len(first) - 1), obs, first, lk.SIGMA_H, SIGMA_V, cols)
-        same_dict(s, want, ls.FIELDS)
+        s = lk.obs_space(g, x, obs, xs=[x] * (len(first) - 1), first=first)
+        C, b = lk.problems(g, obs, s, lk.SIGMA_H, SIGMA_V, cols)
+        same_dict(s, want, lk.FIELDS)
         assert support.same_bits(C, Cp) and support.same_bits(b, bp)
         assert np.array_equal(s["slot_out"].any(axis=1), want["obs_used"] == 0.0) and set(np.unique(s["slot_out"])) == {0.0, 1.0}
         assert not s["slot_out"][~lp.at_pressure(obs)].any() and s["slot_ps"].any()
@@ -89,14 +90,14 @@ def test_splitting_a_slot_changes_nothing(kind, plan):
         obs = lk.edge_obs(g, x)
     else:
         x = lp.craft(g, E, seed=22)
-        obs = lp.subset(lp.network(g, x), slice(0, 60))
+        obs = lk.subset(lp.network(g, x), slice(0, 60))
     n = len(obs["var"])
-    whole = ls.obs_space_slots(g, [x], obs, [0, n])
+    whole = lk.obs_space(g, x, obs, xs=[x], first=[0, n])
     for cut in (0, 1, n // 2, n - 1, n):
-        same_dict(ls.obs_space_slots(g, [x, x], obs, [0, cut, n]), whole, ls.FIELDS + ("slot_ps", "slot_out"))
+        same_dict(lk.obs_space(g, x, obs, xs=[x, x], first=[0, cut, n]), whole, lk.FIELDS + ("slot_ps", "slot_out"))
     y = ls.drifting(g, x, 2, seed=9)[0]
-    other, cut = ls.obs_space_slots(g, [y], obs, [0, n]), n // 3
-    mixed = ls.obs_space_slots(g, [y, x], obs, [0, cut, n])
+    other, cut = lk.obs_space(g, x, obs, xs=[y], first=[0, n]), n // 3
+    mixed = lk.obs_space(g, x, obs, xs=[y, x], first=[0, cut, n])
     for name in ls.SLOT_FIELDS:
         assert support.same_bits(mixed[name][:cut], other[name][:cut]) and support.same_bits(mixed[name][cut:], whole[name][cut:]), name
     assert not support.same_bits(whole["hx"], other["hx"])
@@ -115,8 +116,10 @@ def test_late_mask_in_the_restatement(plan):
     bad = [xs[0], {v: a.copy() for v, a in xs[1].items()}]
     for v in lk.VARS:
         bad[1][v][1] = np.nan
-    C, b, s = ls.problems_slots(g, bad, obs, first, lk.SIGMA_H, SIGMA_V, keep=keep)
-    Cc, bc, sc = ls.problems_slots(g, [ls.compact(a, keep) for a in xs], obs, first, lk.SIGMA_H, SIGMA_V)
+    s = lk.obs_space(g, x, obs, keep, xs=bad, first=first)
+    C, b = lk.problems(g, obs, s, lk.SIGMA_H, SIGMA_V, keep=keep)
+    sc = lk.obs_space(g, x, obs, xs=[lk.compact(a, keep) for a in xs], first=first)
+    Cc, bc = lk.problems(g, obs, sc, lk.SIGMA_H, SIGMA_V)
     assert support.same_bits(C, Cc) and support.same_bits(b, bc) and np.isfinite(C).all()
     same_dict(s, sc, ls.PER_OBS)
     assert support.same_bits(np.ascontiguousarray(s["y"][:, keep]), sc["y"]) and not s["y"][:, 1].any() and np.isnan(s["hx"][7:, 1]).all()
@@ -146,7 +149,7 @@ class Handles:
         gone.close()
         self.nat = s.Nature(sp, capacity=1)
         x = lk.ensemble(g, NMEM, seed=1)
-        self.obs = lp.subset(lk.edge_obs(g, x), slice(0, 30))
+        self.obs = lk.subset(lk.edge_obs(g, x), slice(0, 30))
         self.buf = np.zeros(16)
         self.q = self.buf.ctypes.data_as(ctypes.c_void_p)      # a non-null "device pointer": no check dereferences one
 

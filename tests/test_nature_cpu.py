@@ -85,7 +85,7 @@ def test_observe_noise_free_and_noise(geo):
     truth = nt.as_truth(x)
     obs = lk.edge_obs(g, x)
     n = len(obs["var"])
-    h, _, _, _ = lk.obs_space(g, x, obs)
+    h = lk.observe(g, x, obs)[0]
     clean = nt.observe(g, truth, obs, obs["error"], SEED, 0, 0.0)
     assert np.array_equal(clean, h[:, 0]) and np.array_equal(clean, nt.operator(g, truth, obs))
     for d in (0, 1, 2 ** 32 + 5):

@@ -18,7 +18,6 @@ import numpy as np
 
 import dynstep
 import letkf as lk
-import letkfslots as ls
 import longrun
 import nature as nt
 import synth
@@ -98,7 +97,7 @@ def network(g, x):
     var = np.array([OBSERVED[n % 4] for n in range(NOBS)])
     lev = np.where(var == lk.PS, 0, np.arange(NOBS) % g.kx)
     net = lk.make_obs(var, lev, lon, lat, np.zeros(NOBS), np.ones(NOBS))
-    net["error"] = ERR_FACTOR * lk.obs_space(g, x, net)[0].std(axis=1, ddof=1)
+    net["error"] = ERR_FACTOR * lk.observe(g, x, net)[0].std(axis=1, ddof=1)
     assert (net["error"] > 0.0).all()
     return net
 
@@ -119,8 +118,9 @@ def values(g, truths, net, cycle):
 # ---------------------------------------------------------------------------------------------------- the analysis
 def analyse(g, x, xs, obs, cols=None):
     """the slot analysis of the gridded ensemble x, the slots observed on xs -> (the increments on the grid, (E, kx, il, ix) and
-    (E, il, ix), the obs_space_slots dict, the largest condition number)"""
-    C, b, space = ls.problems_slots(g, xs, obs, FIRST, SIGMA_H, SIGMA_V, cols)
+    (E, il, ix), the obs_space dict, the largest condition number)"""
+    space = lk.obs_space(g, x, obs, xs=xs, first=FIRST)
+    C, b = lk.problems(g, obs, space, SIGMA_H, SIGMA_V, cols)
     inc, kappa = lk.increments(g, x, C, b, RHO, "eigh", cols)
     return {v: inc[v].reshape(x[v].shape) for v in lk.VARS}, space, kappa
 
@@ -202,7 +202,7 @@ def separation(g, win, net):
     out = {}
     for s, n in enumerate(SLOT_STEPS):
         sub = {k: a[rows(s)] for k, a in net.items()}
-        hx = {m: lk.obs_space(g, win["x"][m], sub)[0] for m in (n - 1, n, n + 1)}
+        hx = {m: lk.observe(g, win["x"][m], sub)[0] for m in (n - 1, n, n + 1)}
         for v in OBSERVED:
             at = sub["var"] == v
             scale = float(np.max(np.abs(win["x"][n][lk.VARS[v]])))

@@ -40,8 +40,11 @@ def sha(arrays):
 
 
 def analysis(lt, x, **how):
-    got = ls.analyse(lt, x, names=FIELDS, **how)
-    return sha([got[n] for n in FIELDS + lk.VARS])
+    """the call and its digest, by the library's calls alone: the tool also serves the tests directory of an earlier commit"""
+    import torch
+    inc = lt.analyse_grid(*[support.dev(x[v]) for v in lk.VARS], **how)
+    torch.cuda.synchronize()
+    return sha([lt.field(n).numpy() for n in FIELDS] + [a.cpu().numpy() for a in inc])
 
 
 def networks(g, E):

@@ -48,15 +48,15 @@ def grids(o, sts):
 def all_transforms(g, x, obs, sigma_h, sigma_v, rho, chunk=256):
     """T (ncol, kx, E, E) at every grid column, the local sums as matrix products over the observations in range of a chunk"""
     E, ncol = x["ps"].shape[0], g.ix * g.il
-    _, _, Y, d = lk.obs_space(g, x, obs)
+    s = lk.obs_space(g, x, obs)
+    Y, d, ounit = s["y"], s["departure"], lk.unit(obs["lon"], obs["lat"])
     rinv = 1.0 / (obs["error"] * obs["error"])
     YY, Yd = (Y[:, :, None] * Y[:, None, :]).reshape(len(d), E * E), Y * d[:, None]
     T = np.zeros((ncol, g.kx, E, E))
     for c0 in range(0, ncol, chunk):
         cols = np.arange(c0, min(c0 + chunk, ncol))
-        near = np.nonzero(lk.distance(g.colunit[cols], lk.unit(obs["lon"], obs["lat"])).min(axis=0) < 2.0 * sigma_h * np.sqrt(10.0 / 3.0))[0]
-        sub = {k: a[near] for k, a in obs.items()}
-        r = (lk.weights(g, sub, cols, sigma_h, sigma_v) * rinv[near][None, None, :]).reshape(-1, len(near))
+        near = np.nonzero(lk.distance(g.colunit[cols], ounit).min(axis=0) < 2.0 * sigma_h * np.sqrt(10.0 / 3.0))[0]
+        r = (lk.weights(g, ounit[near], s["obs_lnsigma"][near], cols, sigma_h, sigma_v) * rinv[near][None, None, :]).reshape(-1, len(near))
         C, b = (r @ YY[near]).reshape(-1, E, E), r @ Yd[near]
         T[cols] = lk.transform(C, b, E, rho)[0].reshape(len(cols), g.kx, E, E)
     return T
@@ -84,7 +84,8 @@ def main():
     nloc, per = lon.size, var.size
     obs = lk.make_obs(np.tile(var, nloc), np.tile(lev, nloc), np.repeat(lon.ravel(), per), np.repeat(lat.ravel(), per),
                       np.zeros(nloc * per), np.ones(nloc * per))
-    hx, hxmean, _, _ = lk.obs_space(g, x, obs)
+    hx = lk.observe(g, x, obs)[0]
+    hxmean = lk.couple(g, obs, hx)["hxmean"]
     obs["error"] = hx.std(axis=1, ddof=1) + 1e-300
     obs["value"] = hxmean + obs["error"] * np.random.default_rng(0).standard_normal(nloc * per)
     allcols = np.arange(g.ix * g.il)
