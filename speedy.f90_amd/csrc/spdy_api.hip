@@ -51,7 +51,7 @@ int dev_release(spdy_plan *p, void *ptr)
     NEED_DEVICE(p);
     const auto it = std::find(p->allocs.begin(), p->allocs.end(), ptr);
     if (it == p->allocs.end()) return fail(SPDY_ERR_ARG, "spdy_dev_free: not a live spdy_dev_alloc buffer of this plan");
-    RC(sync(p));               // work queued on the plan's stream may still use it
+    RC(stream_sync(p));        // work queued on the plan's stream may still use it
     p->allocs.erase(it);
     HIP_TRY(hipFree(ptr));
     return SPDY_OK;
@@ -311,7 +311,7 @@ int upload_all(spdy_plan *p)
     HIP_TRY(spdy::upload_fft_constants(t.ix, fc));
 
     void *ptr;
-    // the Fourier workspace and the host-API staging buffers are allocated on demand (ensure_four / ensure_staging):
+    // the Fourier workspace and the host-API staging buffers are allocated on demand (ensure_four / HostCall::open):
     // a device-resident T30 host needs neither (at the bench configuration they would be 1 GB)
     // At T63 small plans (model-shaped batches: workspace <= 64 MB) get it right away, so that a graph capture needs no
     // warm-up call; a throughput-sized plan (1536 fields: 355 MB) allocates it at the first call that takes that path.
@@ -394,48 +394,51 @@ int ensure_four(spdy_plan *p)
     return SPDY_OK;
 }
 
-int ensure_staging(spdy_plan *p, size_t elems)
+// the plan's two staging sets (spdy_plan::dstage, hstage), at the first host-pointer call
+static int alloc_staging(spdy_plan *p)
+{
+    // four buffers big enough for max_batch grids (the largest array kind)
+    p->stage_elems = (size_t)p->max_batch * p->tab.il * p->tab.ix;
+    void *ptr;
+    for (int i = 0; i < 4; ++i) {
+        RC(dev_alloc(p, p->stage_elems * sizeof(double), &ptr));
+        p->dstage[i] = static_cast<double *>(ptr);
+    }
+    // the host-mapped twin set for small calls; any failure here just leaves the route off
+    size_t kb = 512;
+    if (const char *env = getenv("SPDY_HOST_STAGE_KB")) kb = (size_t)(atol(env) > 0 ? atol(env) : 0);
+    const size_t want = std::min(p->stage_elems, kb * 1024 / sizeof(double));
+    if (want < grid_elems(p)) return SPDY_OK;
+    bool ok = true;
+    for (int i = 0; i < 4 && ok; ++i) {
+        ok = hipHostMalloc(&ptr, want * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+        if (ok) p->hstage[i] = static_cast<double *>(ptr);
+    }
+    if (ok) ok = hipHostMalloc(&ptr, sizeof(int) * (size_t)p->max_batch, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+    if (ok) {
+        p->h_kcos = static_cast<int *>(ptr);
+        p->hstage_elems = want;
+        // the completion stamp is optional: without it HostCall::finish ends host-staged calls in hipStreamSynchronize
+        if (hipHostMalloc(&ptr, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+            p->h_stamp = static_cast<unsigned *>(ptr);
+            *p->h_stamp = 0;
+        } else
+            (void)hipGetLastError();
+    } else {
+        // the route stays off as a whole: no buffers, no size, no kcos twin
+        (void)hipGetLastError();
+        for (int i = 0; i < 4; ++i) { if (p->hstage[i]) (void)hipHostFree(p->hstage[i]); p->hstage[i] = nullptr; }
+        p->hstage_elems = 0;
+    }
+    return SPDY_OK;
+}
+
+int HostCall::open(size_t elems)
 {
     NOT_CAPTURING(p, "a host-pointer entry point");
-    p->pending.clear();               // (a call that failed between its d2h and its sync must not leave copies behind)
-    if (!p->dstage[0]) {
-        // four buffers big enough for max_batch grids (the largest array kind)
-        p->stage_elems = (size_t)p->max_batch * p->tab.il * p->tab.ix;
-        void *ptr;
-        for (int i = 0; i < 4; ++i) {
-            RC(dev_alloc(p, p->stage_elems * sizeof(double), &ptr));
-            p->dstage[i] = static_cast<double *>(ptr);
-        }
-        // the host-mapped twin set for small calls (spdy_plan::hstage); any failure here just leaves the route off
-        size_t kb = 512;
-        if (const char *env = getenv("SPDY_HOST_STAGE_KB")) kb = (size_t)(atol(env) > 0 ? atol(env) : 0);
-        const size_t want = std::min(p->stage_elems, kb * 1024 / sizeof(double));
-        if (want >= grid_elems(p)) {
-            bool ok = true;
-            for (int i = 0; i < 4 && ok; ++i) {
-                ok = hipHostMalloc(&ptr, want * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-                if (ok) p->hstage[i] = static_cast<double *>(ptr);
-            }
-            if (ok) ok = hipHostMalloc(&ptr, sizeof(int) * (size_t)p->max_batch, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-            if (ok) {
-                p->h_kcos = static_cast<int *>(ptr);
-                p->hstage_elems = want;
-                // the completion stamp is optional: without it sync() ends host-staged calls in hipStreamSynchronize
-                if (hipHostMalloc(&ptr, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-                    p->h_stamp = static_cast<unsigned *>(ptr);
-                    *p->h_stamp = 0;
-                } else
-                    (void)hipGetLastError();
-            } else {
-                // the route stays off as a whole: no buffers, no size, no kcos twin
-                (void)hipGetLastError();
-                for (int i = 0; i < 4; ++i) { if (p->hstage[i]) (void)hipHostFree(p->hstage[i]); p->hstage[i] = nullptr; }
-                p->hstage_elems = 0;
-            }
-        }
-    }
-    double *const *set = (p->hstage_elems && elems <= p->hstage_elems) ? p->hstage : p->dstage;
-    p->stage_a = set[0]; p->stage_b = set[1]; p->stage_c = set[2]; p->stage_d = set[3];
+    if (!p->dstage[0]) RC(alloc_staging(p));
+    host = p->hstage_elems && elems <= p->hstage_elems;
+    for (int i = 0; i < 4; ++i) buf[i] = host ? p->hstage[i] : p->dstage[i];
     return SPDY_OK;
 }
 
@@ -445,6 +448,7 @@ int check_batch(const spdy_plan *p, int nb)
     return SPDY_OK;
 }
 
+// (a _dev form's question whether it was handed a host-mapped buffer: spdy_grid_to_spec_dev)
 static bool in_host_stage(const spdy_plan *p, const double *ptr)
 {
     for (int i = 0; i < 4; ++i)
@@ -452,21 +456,20 @@ static bool in_host_stage(const spdy_plan *p, const double *ptr)
     return false;
 }
 
-int h2d(spdy_plan *p, double *dst, const double *src, size_t n)
+int HostCall::in(int slot, const double *src, size_t n, size_t offset)
 {
-    NOT_CAPTURING(p, "a host-pointer entry point");
     if (!n) return SPDY_OK;
-    // host-mapped staging: nothing is in flight on it (every host-pointer call ends with sync), the kernels read it in place
-    if (in_host_stage(p, dst)) std::memcpy(dst, src, n * sizeof(double));
-    else HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    // host-mapped staging: nothing is in flight on it (every host-pointer call ends with finish), the kernels read it in place
+    if (host) std::memcpy(buf[slot] + offset, src, n * sizeof(double));
+    else HIP_TRY(hipMemcpyAsync(buf[slot] + offset, src, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
     return SPDY_OK;
 }
-int d2h(spdy_plan *p, double *dst, const double *src, size_t n)
+int HostCall::out(double *dst, int slot, size_t n)
 {
-    NOT_CAPTURING(p, "a host-pointer entry point");
     if (!n) return SPDY_OK;
-    if (in_host_stage(p, src)) p->pending.push_back({dst, src, n * sizeof(double)});   // copied out by sync()
-    else HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (!host) HIP_TRY(hipMemcpyAsync(dst, buf[slot], n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    else if (nouts == (int)(sizeof(outs) / sizeof(outs[0]))) return fail(SPDY_ERR_STATE, "a host-pointer call with more than three outputs");
+    else outs[nouts++] = {dst, buf[slot], n * sizeof(double)};   // copied out by finish
     return SPDY_OK;
 }
 // A one-thread kernel behind a host-staged call's kernels writes the call's sequence number into host-mapped memory; the calling
@@ -477,13 +480,20 @@ __global__ void stamp_kernel(unsigned *stamp, unsigned seq)
     __hip_atomic_store(stamp, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-int sync(spdy_plan *p)
+int stream_sync(spdy_plan *p)
 {
     NOT_CAPTURING(p, "synchronising");
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPDY_OK;
+}
+
+int HostCall::finish()
+{
     // ($SPDY_HOST_SPIN=0: always hipStreamSynchronize.  Measured round 5, flang-built hosts: one-field round trips 22.0 -> 28.8 k/s
     // at T30, 15.9 -> 17.8 k/s at T63; stacks of eight 112 -> 125 k/s at T30.)
     static const bool spin = !(getenv("SPDY_HOST_SPIN") && atoi(getenv("SPDY_HOST_SPIN")) == 0);
-    if (spin && p->h_stamp && !p->pending.empty()) {
+    bool done = false;
+    if (spin && p->h_stamp && nouts) {
         const unsigned seq = ++p->stamp_seq;
         hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, p->stream, p->h_stamp, seq);
         if (hipPeekAtLastError() == hipSuccess) {          // (peek: an earlier sticky error stays for hipStreamSynchronize below to report)
@@ -502,18 +512,11 @@ int sync(spdy_plan *p)
 #endif
                 if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) break;   // fall back to the runtime
             }
-            if (__atomic_load_n(p->h_stamp, __ATOMIC_ACQUIRE) == seq) {
-                for (const auto &c : p->pending) std::memcpy(c.dst, c.src, c.bytes);
-                p->pending.clear();
-                return SPDY_OK;
-            }
+            done = __atomic_load_n(p->h_stamp, __ATOMIC_ACQUIRE) == seq;
         }
     }
-    const hipError_t e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) p->pending.clear();
-    HIP_TRY(e);
-    for (const auto &c : p->pending) std::memcpy(c.dst, c.src, c.bytes);
-    p->pending.clear();
+    if (!done) RC(stream_sync(p));
+    for (int i = 0; i < nouts; ++i) std::memcpy(outs[i].dst, outs[i].src, outs[i].bytes);
     return SPDY_OK;
 }
 
@@ -521,10 +524,10 @@ int sync(spdy_plan *p)
 
 namespace {
 
-// Fourier workspace rows are fs doubles apart; the reference layout packs 2*mx per row.
+// The stage calls' copies out of and into the Fourier workspace, on the plan's stream inside their HostCall: its rows are fs
+// doubles apart, the reference layout packs 2*mx per row.
 int four_to_host(spdy_plan *p, double *dst, int nb)
 {
-    NOT_CAPTURING(p, "a host-pointer entry point");
     const size_t w = 2 * (size_t)p->tab.mx * sizeof(double);
     if (nb) HIP_TRY(hipMemcpy2DAsync(dst, w, p->four, p->dev.fs * sizeof(double), w, (size_t)nb * p->tab.il,
                                      hipMemcpyDeviceToHost, p->stream));
@@ -532,11 +535,52 @@ int four_to_host(spdy_plan *p, double *dst, int nb)
 }
 int four_from_host(spdy_plan *p, const double *src, int nb)
 {
-    NOT_CAPTURING(p, "a host-pointer entry point");
     const size_t w = 2 * (size_t)p->tab.mx * sizeof(double);
     if (nb) HIP_TRY(hipMemcpy2DAsync(p->four, p->dev.fs * sizeof(double), src, w, w, (size_t)nb * p->tab.il,
                                      hipMemcpyHostToDevice, p->stream));
     return SPDY_OK;
+}
+
+/* The four stage calls: one operand is nb fields of `kind` in slot 0, the other lies in the Fourier workspace -- device memory, so
+ * these calls state no size and stay on the device set.  four_in: the caller's `in` goes into the workspace and `out` comes back
+ * from slot 0; otherwise `in` goes into slot 0 and the workspace comes back as `out`. */
+enum FieldKind { SPEC, GRID };
+size_t field_elems(const spdy_plan *p, FieldKind kind) { return kind == GRID ? grid_elems(p) : spec_elems(p); }
+template <class Launch>
+int host_stage(spdy_plan *p, int nb, const double *in, double *out, FieldKind kind, bool four_in, Launch &&launch)
+{
+    NEED_DEVICE(p);
+    RC(check_batch(p, nb));
+    HostCall c(p);
+    RC(c.open());
+    RC(ensure_four(p));
+    if (nb && (!in || !out)) return fail(SPDY_ERR_ARG, "null pointer");
+    const size_t n = nb * field_elems(p, kind);
+    RC(four_in ? four_from_host(p, in, nb) : c.in(0, in, n));
+    KERNEL(launch(c[0]));
+    RC(four_in ? c.out(out, 0, n) : four_to_host(p, out, nb));
+    return c.finish();
+}
+
+/* The host-pointer forms of the operators and of the composite transforms (level stacks of the Fortran host).  Every array of
+ * such a call is nb fields, and the call states the larger of its two array kinds as its size.  in[i] goes into slot i where there
+ * is one, the _dev form runs on the call's buffers, out[i] comes back from slot i where there is one. */
+template <class Dev>
+int host_batch(spdy_plan *p, int nb, bool all_given, FieldKind in_kind, const double *const (&in)[4], FieldKind out_kind,
+               double *const (&out)[4], Dev &&dev)
+{
+    NEED_DEVICE(p);
+    RC(check_batch(p, nb));
+    if (nb && !all_given) return fail(SPDY_ERR_ARG, "null pointer");
+    const size_t n_in = nb * field_elems(p, in_kind), n_out = nb * field_elems(p, out_kind);
+    HostCall c(p);
+    RC(c.open(std::max(n_in, n_out)));
+    for (int i = 0; i < 4; ++i)
+        if (in[i]) RC(c.in(i, in[i], n_in));
+    RC(dev(c));
+    for (int i = 0; i < 4; ++i)
+        if (out[i]) RC(c.out(out[i], i, n_out));
+    return c.finish();
 }
 
 // Fused single-pass kernels exist for T30.  Measured on MI355X (tools/small_batch.sh) they beat the
@@ -891,7 +935,7 @@ int spdy_plan_set_stream(spdy_plan *p, void *hip_stream)
 int spdy_plan_synchronize(spdy_plan *p)
 {
     NEED_DEVICE(p);
-    return sync(p);
+    return stream_sync(p);
 }
 
 /* ---- device memory for hosts without a HIP binding of their own (a Fortran model: fortran/time_stepping.f90) ---- */
@@ -908,7 +952,7 @@ int spdy_dev_alloc(spdy_plan *p, size_t bytes, void **d_ptr)
     RC(dev_alloc(p, bytes, &ptr));
     int rc = SPDY_OK;
     if (hipMemsetAsync(ptr, 0, bytes, p->stream) != hipSuccess) rc = fail(SPDY_ERR_HIP, "hipMemsetAsync failed");
-    if (!rc) rc = sync(p);
+    if (!rc) rc = stream_sync(p);
     if (rc) {
         p->allocs.pop_back();
         (void)hipFree(ptr);
@@ -932,7 +976,7 @@ int spdy_dev_upload(spdy_plan *p, void *d_dst, const void *src, size_t bytes)
     NOT_CAPTURING(p, "spdy_dev_upload");
     if (bytes && (!d_dst || !src)) return fail(SPDY_ERR_ARG, "null pointer");
     if (bytes) HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, p->stream));
-    return sync(p);
+    return stream_sync(p);
 }
 
 int spdy_dev_download(spdy_plan *p, void *dst, const void *d_src, size_t bytes)
@@ -941,7 +985,7 @@ int spdy_dev_download(spdy_plan *p, void *dst, const void *d_src, size_t bytes)
     NOT_CAPTURING(p, "spdy_dev_download");
     if (bytes && (!dst || !d_src)) return fail(SPDY_ERR_ARG, "null pointer");
     if (bytes) HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, p->stream));
-    return sync(p);
+    return stream_sync(p);
 }
 
 int spdy_plan_set_profiling(spdy_plan *p, int on)
@@ -1101,32 +1145,34 @@ int spdy_spec_to_grid_batch(spdy_plan *p, int nb, const double *spec, const int 
 {
     NEED_DEVICE(p);
     RC(check_batch(p, nb));
-    RC(ensure_staging(p, nb * grid_elems(p)));
+    HostCall c(p);
+    RC(c.open(nb * grid_elems(p)));
     if (nb && (!spec || !grid)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(h2d(p, p->stage_a, spec, nb * spec_elems(p)));
+    RC(c.in(0, spec, nb * spec_elems(p)));
     // one flag for the whole batch (always so for the reference's one-field calls): passed by value, no array to move
     bool same = true;
     for (int i = 1; kcos && i < nb; ++i) same = same && kcos[i] == kcos[0];
     const int *dk = nullptr;
     if (kcos && nb && !same) {
-        if (on_host_stage(p)) { std::memcpy(p->h_kcos, kcos, sizeof(int) * nb); dk = p->h_kcos; }
+        if (c.on_host_stage()) { std::memcpy(p->h_kcos, kcos, sizeof(int) * nb); dk = p->h_kcos; }
         else { HIP_TRY(hipMemcpyAsync(p->d_kcos, kcos, sizeof(int) * nb, hipMemcpyHostToDevice, p->stream)); dk = p->d_kcos; }
     }
-    RC(spdy_spec_to_grid_dev(p, nb, p->stage_a, dk, (kcos && nb) ? kcos[0] : 1, p->stage_b));
-    RC(d2h(p, grid, p->stage_b, nb * grid_elems(p)));
-    return sync(p);
+    RC(spdy_spec_to_grid_dev(p, nb, c[0], dk, (kcos && nb) ? kcos[0] : 1, c[1]));
+    RC(c.out(grid, 1, nb * grid_elems(p)));
+    return c.finish();
 }
 
 int spdy_grid_to_spec_batch(spdy_plan *p, int nb, const double *grid, double *spec)
 {
     NEED_DEVICE(p);
     RC(check_batch(p, nb));
-    RC(ensure_staging(p, nb * grid_elems(p)));
+    HostCall c(p);
+    RC(c.open(nb * grid_elems(p)));
     if (nb && (!spec || !grid)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(h2d(p, p->stage_a, grid, nb * grid_elems(p)));
-    RC(spdy_grid_to_spec_dev(p, nb, p->stage_a, p->stage_b));
-    RC(d2h(p, spec, p->stage_b, nb * spec_elems(p)));
-    return sync(p);
+    RC(c.in(0, grid, nb * grid_elems(p)));
+    RC(spdy_grid_to_spec_dev(p, nb, c[0], c[1]));
+    RC(c.out(spec, 1, nb * spec_elems(p)));
+    return c.finish();
 }
 
 int spdy_spec_to_grid(spdy_plan *p, const double *spec, int kcos, double *grid)
@@ -1139,59 +1185,24 @@ int spdy_grid_to_spec(spdy_plan *p, const double *grid, double *spec)
     return spdy_grid_to_spec_batch(p, 1, grid, spec);
 }
 
-/* ---------------------------------------------------------------- stages, host pointers */
+/* ---------------------------------------------------------------- stages, host pointers (host_stage above) */
 int spdy_legendre_inv(spdy_plan *p, int nb, const double *spec, double *four)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    RC(ensure_staging(p));
-    RC(ensure_four(p));
-    if (nb && (!spec || !four)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(h2d(p, p->stage_a, spec, nb * spec_elems(p)));
-    KERNEL(spdy::launch_legendre_inv(p->dev, nb, p->stage_a, p->four, p->stream));
-    RC(four_to_host(p, four, nb));
-    RC(sync(p));
-    // Im(m'=0) is produced as an exact 0 +/- 0 by the contraction; nothing to fix up.
-    return SPDY_OK;
+    // (Im(m'=0) is produced as an exact 0 +/- 0 by the contraction; nothing to fix up)
+    return host_stage(p, nb, spec, four, SPEC, false, [&](double *s) { return spdy::launch_legendre_inv(p->dev, nb, s, p->four, p->stream); });
 }
-
 int spdy_legendre_dir(spdy_plan *p, int nb, const double *four, double *spec)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    RC(ensure_staging(p));
-    RC(ensure_four(p));
-    if (nb && (!spec || !four)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(four_from_host(p, four, nb));
-    KERNEL(spdy::launch_legendre_dir(p->dev, nb, p->four, p->stage_a, p->stream));
-    RC(d2h(p, spec, p->stage_a, nb * spec_elems(p)));
-    return sync(p);
+    return host_stage(p, nb, four, spec, SPEC, true, [&](double *s) { return spdy::launch_legendre_dir(p->dev, nb, p->four, s, p->stream); });
 }
-
 int spdy_fourier_inv(spdy_plan *p, int nb, const double *four, int kcos, double *grid)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    RC(ensure_staging(p));
-    RC(ensure_four(p));
-    if (nb && (!grid || !four)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(four_from_host(p, four, nb));
-    KERNEL(spdy::launch_fourier_inv(p->dev, nb, p->four, nullptr, kcos, p->stage_a, p->stream));
-    RC(d2h(p, grid, p->stage_a, nb * grid_elems(p)));
-    return sync(p);
+    return host_stage(p, nb, four, grid, GRID, true,
+                      [&](double *g) { return spdy::launch_fourier_inv(p->dev, nb, p->four, nullptr, kcos, g, p->stream); });
 }
-
 int spdy_fourier_dir(spdy_plan *p, int nb, const double *grid, double *four)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    RC(ensure_staging(p));
-    RC(ensure_four(p));
-    if (nb && (!grid || !four)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(h2d(p, p->stage_a, grid, nb * grid_elems(p)));
-    KERNEL(spdy::launch_fourier_dir(p->dev, nb, p->stage_a, nullptr, p->four, p->stream));
-    RC(four_to_host(p, four, nb));
-    return sync(p);
+    return host_stage(p, nb, grid, four, GRID, false, [&](double *g) { return spdy::launch_fourier_dir(p->dev, nb, g, nullptr, p->four, p->stream); });
 }
 
 /* ---------------------------------------------------------------- spectral operators */
@@ -1250,27 +1261,16 @@ int spdy_grad_to_grid_dev(spdy_plan *p, int nb, const double *psi, double *gx, d
     return derived_to_grid(p, nb, 2, psi, nullptr, gx, gy, kcos);
 }
 
-/* host-pointer forms (level stacks of the Fortran host): inputs to stage_a/b, grids come back from stage_c/d */
-static int derived_to_grid_host(spdy_plan *p, int nb, int mode, const double *in0, const double *in1, double *g0, double *g1, int kcos)
-{
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    if (nb && (!in0 || (mode == 1 && !in1) || !g0 || !g1)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p, nb * grid_elems(p)));
-    RC(h2d(p, p->stage_a, in0, nb * spec_elems(p)));
-    if (mode == 1) RC(h2d(p, p->stage_b, in1, nb * spec_elems(p)));
-    RC(derived_to_grid(p, nb, mode, p->stage_a, p->stage_b, p->stage_c, p->stage_d, kcos));
-    RC(d2h(p, g0, p->stage_c, nb * grid_elems(p)));
-    RC(d2h(p, g1, p->stage_d, nb * grid_elems(p)));
-    return sync(p);
-}
+/* host-pointer forms (level stacks of the Fortran host), on host_batch above */
 int spdy_uvspec_to_grid(spdy_plan *p, int nb, const double *vor, const double *dv, double *ug, double *vg, int kcos)
 {
-    return derived_to_grid_host(p, nb, 1, vor, dv, ug, vg, kcos);
+    return host_batch(p, nb, vor && dv && ug && vg, SPEC, {vor, dv}, GRID, {nullptr, nullptr, ug, vg},
+                      [&](const HostCall &c) { return spdy_uvspec_to_grid_dev(p, nb, c[0], c[1], c[2], c[3], kcos); });
 }
 int spdy_grad_to_grid(spdy_plan *p, int nb, const double *psi, double *gx, double *gy, int kcos)
 {
-    return derived_to_grid_host(p, nb, 2, psi, nullptr, gx, gy, kcos);
+    return host_batch(p, nb, psi && gx && gy, SPEC, {psi}, GRID, {nullptr, nullptr, gx, gy},
+                      [&](const HostCall &c) { return spdy_grad_to_grid_dev(p, nb, c[0], c[2], c[3], kcos); });
 }
 
 /* vdspec: scale on load, two direct transforms, then vds.  The multi-kernel path keeps the two intermediate
@@ -1333,82 +1333,41 @@ int spdy_direct_batch_dev(spdy_plan *p, int npairs, const double *ug, const doub
     return direct_batch(p, DirectReq{npairs, ug, vg, vorm, divm, kcos, false, nplain, grid, spec});
 }
 
-#define HOST_1IN_1OUT(name, devfn)                                                 \
-    int name(spdy_plan *p, int nb, const double *in, double *out)                  \
-    {                                                                              \
-        NEED_DEVICE(p);                                                            \
-        RC(check_batch(p, nb));                                                    \
-        if (nb && (!in || !out)) return fail(SPDY_ERR_ARG, "null pointer");        \
-        RC(ensure_staging(p, nb * spec_elems(p)));                                 \
-        RC(h2d(p, p->stage_a, in, nb * spec_elems(p)));                            \
-        RC(devfn(p, nb, p->stage_a, p->stage_b));                                  \
-        RC(d2h(p, out, p->stage_b, nb * spec_elems(p)));                           \
-        return sync(p);                                                            \
-    }
-HOST_1IN_1OUT(spdy_laplacian, spdy_laplacian_dev)
-HOST_1IN_1OUT(spdy_inverse_laplacian, spdy_inverse_laplacian_dev)
-
+int spdy_laplacian(spdy_plan *p, int nb, const double *in, double *out)
+{
+    return host_batch(p, nb, in && out, SPEC, {in}, SPEC, {nullptr, out},
+                      [&](const HostCall &c) { return spdy_laplacian_dev(p, nb, c[0], c[1]); });
+}
+int spdy_inverse_laplacian(spdy_plan *p, int nb, const double *in, double *out)
+{
+    return host_batch(p, nb, in && out, SPEC, {in}, SPEC, {nullptr, out},
+                      [&](const HostCall &c) { return spdy_inverse_laplacian_dev(p, nb, c[0], c[1]); });
+}
 int spdy_trunct(spdy_plan *p, int nb, double *inout)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    if (nb && !inout) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p, nb * spec_elems(p)));
-    RC(h2d(p, p->stage_a, inout, nb * spec_elems(p)));
-    RC(spdy_trunct_dev(p, nb, p->stage_a));
-    RC(d2h(p, inout, p->stage_a, nb * spec_elems(p)));
-    return sync(p);
+    return host_batch(p, nb, inout != nullptr, SPEC, {inout}, SPEC, {inout}, [&](const HostCall &c) { return spdy_trunct_dev(p, nb, c[0]); });
 }
-
+/* grad, vds, uvspec: the outputs go in as well -- entries the reference leaves untouched keep the caller's values (grad: rows of psdy) */
 int spdy_grad(spdy_plan *p, int nb, const double *psi, double *psdx, double *psdy)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    if (nb && (!psi || !psdx || !psdy)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p, nb * spec_elems(p)));
-    const size_t n = nb * spec_elems(p);
-    RC(h2d(p, p->stage_a, psi, n));
-    // rows of psdy the reference leaves untouched keep the caller's values
-    RC(h2d(p, p->stage_c, psdy, n));
-    RC(spdy_grad_dev(p, nb, p->stage_a, p->stage_b, p->stage_c));
-    RC(d2h(p, psdx, p->stage_b, n));
-    RC(d2h(p, psdy, p->stage_c, n));
-    return sync(p);
+    return host_batch(p, nb, psi && psdx && psdy, SPEC, {psi, nullptr, psdy}, SPEC, {nullptr, psdx, psdy},
+                      [&](const HostCall &c) { return spdy_grad_dev(p, nb, c[0], c[1], c[2]); });
 }
-
-#define HOST_2IN_2OUT(name, devfn)                                                                   \
-    int name(spdy_plan *p, int nb, const double *a, const double *b, double *c, double *d)           \
-    {                                                                                                \
-        NEED_DEVICE(p);                                                                              \
-        RC(check_batch(p, nb));                                                                      \
-        if (nb && (!a || !b || !c || !d)) return fail(SPDY_ERR_ARG, "null pointer");                 \
-        RC(ensure_staging(p, nb * spec_elems(p)));                                                   \
-        const size_t n = nb * spec_elems(p);                                                         \
-        RC(h2d(p, p->stage_a, a, n));                                                                \
-        RC(h2d(p, p->stage_b, b, n));                                                                \
-        RC(h2d(p, p->stage_c, c, n)); /* untouched entries keep the caller's values */              \
-        RC(h2d(p, p->stage_d, d, n));                                                                \
-        RC(devfn(p, nb, p->stage_a, p->stage_b, p->stage_c, p->stage_d));                            \
-        RC(d2h(p, c, p->stage_c, n));                                                                \
-        RC(d2h(p, d, p->stage_d, n));                                                                \
-        return sync(p);                                                                              \
-    }
-HOST_2IN_2OUT(spdy_vds, spdy_vds_dev)
-HOST_2IN_2OUT(spdy_uvspec, spdy_uvspec_dev)
-
+int spdy_vds(spdy_plan *p, int nb, const double *u, const double *v, double *vor, double *dv)
+{
+    return host_batch(p, nb, u && v && vor && dv, SPEC, {u, v, vor, dv}, SPEC, {nullptr, nullptr, vor, dv},
+                      [&](const HostCall &c) { return spdy_vds_dev(p, nb, c[0], c[1], c[2], c[3]); });
+}
+int spdy_uvspec(spdy_plan *p, int nb, const double *vor, const double *dv, double *u, double *v)
+{
+    return host_batch(p, nb, vor && dv && u && v, SPEC, {vor, dv, u, v}, SPEC, {nullptr, nullptr, u, v},
+                      [&](const HostCall &c) { return spdy_uvspec_dev(p, nb, c[0], c[1], c[2], c[3]); });
+}
+/* (the one-pass kernel writes vorticity/divergence while other workgroups still read grids: outputs never alias inputs) */
 int spdy_vdspec(spdy_plan *p, int nb, const double *ug, const double *vg, double *vorm, double *divm, int kcos)
 {
-    NEED_DEVICE(p);
-    RC(check_batch(p, nb));
-    if (nb && (!ug || !vg || !vorm || !divm)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p, nb * grid_elems(p)));
-    RC(h2d(p, p->stage_a, ug, nb * grid_elems(p)));
-    RC(h2d(p, p->stage_b, vg, nb * grid_elems(p)));
-    // (the one-pass kernel writes vorticity/divergence while other workgroups still read grids: outputs never alias inputs)
-    RC(spdy_vdspec_dev(p, nb, p->stage_a, p->stage_b, p->stage_c, p->stage_d, kcos));
-    RC(d2h(p, vorm, p->stage_c, nb * spec_elems(p)));
-    RC(d2h(p, divm, p->stage_d, nb * spec_elems(p)));
-    return sync(p);
+    return host_batch(p, nb, ug && vg && vorm && divm, GRID, {ug, vg}, SPEC, {nullptr, nullptr, vorm, divm},
+                      [&](const HostCall &c) { return spdy_vdspec_dev(p, nb, c[0], c[1], c[2], c[3], kcos); });
 }
 
 /* ---------------------------------------------------------------- HIP graphs */

@@ -226,15 +226,16 @@ int spdy_hdiff(spdy_plan *p, int nlev, const double *field, const double *fdt_in
     NEED_DEVICE(p);
     RC(check_batch(p, nlev));
     if (nlev && (!field || !fdt_in || !dmp || !dmp1 || !fdt_out)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p));
+    HostCall c(p);
+    RC(c.open());
     const size_t n = nlev * spec_elems(p), tn = (size_t)p->tab.mx * p->tab.nx;
-    RC(h2d(p, p->stage_a, field, n));
-    RC(h2d(p, p->stage_b, fdt_in, n));
-    RC(h2d(p, p->stage_c, dmp, tn));            // both damping tables share stage_c (2*mx*nx <= ix*il) ...
-    RC(h2d(p, p->stage_c + tn, dmp1, tn));
-    RC(spdy_hdiff_dev(p, nlev, p->stage_a, p->stage_b, p->stage_c, p->stage_c + tn, p->stage_d));   // ... so the result has its own buffer
-    RC(d2h(p, fdt_out, p->stage_d, n));
-    return sync(p);
+    RC(c.in(0, field, n));
+    RC(c.in(1, fdt_in, n));
+    RC(c.in(2, dmp, tn));                       // both damping tables share slot 2 (2*mx*nx <= ix*il) ...
+    RC(c.in(2, dmp1, tn, tn));
+    RC(spdy_hdiff_dev(p, nlev, c[0], c[1], c[2], c[2] + tn, c[3]));   // ... so the result has its own buffer
+    RC(c.out(fdt_out, 3, n));
+    return c.finish();
 }
 
 int spdy_device_table(spdy_plan *p, const char *name, const double **d_ptr)
@@ -297,16 +298,14 @@ int spdy_implicit_terms(spdy_plan *p, double *divdt, double *tdt, double *psdt)
     NEED_DEVICE(p);
     if (p->max_batch < p->tab.kx) return fail(SPDY_ERR_ARG, "max_batch must be >= kx for the host implicit_terms");
     if (!divdt || !tdt || !psdt) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p));
-    const size_t n = p->tab.kx * spec_elems(p);
-    RC(h2d(p, p->stage_a, divdt, n));
-    RC(h2d(p, p->stage_b, tdt, n));
-    RC(h2d(p, p->stage_c, psdt, spec_elems(p)));
-    RC(spdy_implicit_terms_dev(p, p->stage_a, p->stage_b, p->stage_c));
-    RC(d2h(p, divdt, p->stage_a, n));
-    RC(d2h(p, tdt, p->stage_b, n));
-    RC(d2h(p, psdt, p->stage_c, spec_elems(p)));
-    return sync(p);
+    HostCall c(p);
+    RC(c.open());
+    double *const arr[3] = {divdt, tdt, psdt};
+    const size_t n[3] = {p->tab.kx * spec_elems(p), p->tab.kx * spec_elems(p), spec_elems(p)};
+    for (int i = 0; i < 3; ++i) RC(c.in(i, arr[i], n[i]));
+    RC(spdy_implicit_terms_dev(p, c[0], c[1], c[2]));
+    for (int i = 0; i < 3; ++i) RC(c.out(arr[i], i, n[i]));
+    return c.finish();
 }
 
 /* ---------------------------------------------------------------- spectral side of a time step */
@@ -328,13 +327,14 @@ int spdy_geopotential(spdy_plan *p, const double *t, const double *phis, double 
     NEED_DEVICE(p);
     if (p->max_batch < p->tab.kx) return fail(SPDY_ERR_ARG, "max_batch must be >= kx for the host get_geopotential");
     if (!t || !phis || !phi) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p));
+    HostCall c(p);
+    RC(c.open());
     const size_t n = p->tab.kx * spec_elems(p);
-    RC(h2d(p, p->stage_a, t, n));
-    RC(h2d(p, p->stage_b, phis, spec_elems(p)));
-    RC(spdy_geopotential_dev(p, p->stage_a, p->stage_b, p->stage_c));
-    RC(d2h(p, phi, p->stage_c, n));
-    return sync(p);
+    RC(c.in(0, t, n));
+    RC(c.in(1, phis, spec_elems(p)));
+    RC(spdy_geopotential_dev(p, c[0], c[1], c[2]));
+    RC(c.out(phi, 2, n));
+    return c.finish();
 }
 
 int spdy_spectral_tendencies_dev(spdy_plan *p, const double *div, const double *t, const double *ps, const double *phis,
@@ -384,15 +384,16 @@ int spdy_step_field(spdy_plan *p, int nlev, int j1, double dt, double eps, doubl
     NEED_DEVICE(p);
     RC(check_batch(p, 2 * nlev));
     if (nlev && (!field || !fdt)) return fail(SPDY_ERR_ARG, "null pointer");
-    RC(ensure_staging(p));
+    HostCall c(p);
+    RC(c.open());
     const size_t n = nlev * spec_elems(p);
-    RC(h2d(p, p->stage_a, field, 2 * n));
-    RC(h2d(p, p->stage_b, fdt, n));
-    const spdy_step_op op{nlev, p->stage_a, p->stage_b};
+    RC(c.in(0, field, 2 * n));
+    RC(c.in(1, fdt, n));
+    const spdy_step_op op{nlev, c[0], c[1]};
     RC(spdy_step_fields_dev(p, 1, &op, j1, dt, eps, wil));
-    RC(d2h(p, field, p->stage_a, 2 * n));
-    RC(d2h(p, fdt, p->stage_b, n));
-    return sync(p);
+    RC(c.out(field, 0, 2 * n));
+    RC(c.out(fdt, 1, n));
+    return c.finish();
 }
 
 

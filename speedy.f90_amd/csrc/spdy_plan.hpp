@@ -60,22 +60,15 @@ struct spdy_plan {
     hipStream_t own_stream = nullptr, stream = nullptr;
     std::vector<void *> allocs;       // everything hipMalloc'ed for this plan
     double *four = nullptr;           // [max_batch][il][fs] Fourier workspace (four-kernel path only; allocated on demand)
-    // host-pointer API staging: four buffers of max_batch grids each, allocated at the first host-pointer call
-    double *stage_a = nullptr, *stage_b = nullptr, *stage_c = nullptr, *stage_d = nullptr;   // the set the current call uses
+    // Host-pointer API staging, allocated at the first host-pointer call: two sets of four buffers.  These are the plan's
+    // resources only; which set a call uses, and what it still has to copy out, is the call's own (spdy_detail::HostCall below).
     size_t stage_elems = 0;
-    // Small host-pointer calls (the reference's one-field-per-call pattern, level stacks) skip both PCIe copy engines: their
-    // staging buffers are PINNED HOST memory mapped into the device's address space -- the input is memcpy'ed into it by the
-    // calling thread, the kernels read and write it across the link themselves, and the result is memcpy'ed out after the
-    // stream synchronisation that ends every host-pointer call (`pending`).  $SPDY_HOST_STAGE_KB (default 512; 0 = off) is
-    // the largest per-buffer size that takes this route; larger calls use the device set and hipMemcpyAsync as before.
     double *dstage[4] = {nullptr, nullptr, nullptr, nullptr};   // device memory, max_batch grids each
     double *hstage[4] = {nullptr, nullptr, nullptr, nullptr};   // hipHostMalloc (mapped, coherent), hstage_elems doubles each
     int *h_kcos = nullptr;                                      // hstage-route twin of d_kcos
-    unsigned *h_stamp = nullptr;                                // host-mapped completion stamp of the hstage route (sync())
+    unsigned *h_stamp = nullptr;                                // host-mapped completion stamp of the hstage route (HostCall::finish)
     unsigned stamp_seq = 0;
     size_t hstage_elems = 0;
-    struct Pending { void *dst; const void *src; size_t bytes; };
-    std::vector<Pending> pending;     // device-written host-stage results still to be copied to the caller's arrays
     const double *d_zero_spec = nullptr;         // one all-zero spectrum (gradient tiles of the mixed inverse kernel)
     double *tmp_c = nullptr, *tmp_d = nullptr;   // max_batch spectra each; allocated with `four` (multi-kernel operator sequences)
     // On-demand workspaces (ensure_workspace).  One that has to grow is allocated anew: the smaller earlier one stays with the plan
@@ -319,13 +312,43 @@ int download_sync(spdy_plan *p, void *dst, const void *src, size_t bytes);
 inline void adopt(spdy_plan *p, PlanObject *o) { o->plan = p; p->objects.push_back(o); }
 void retire(PlanObject *o, std::initializer_list<void *> buffers);
 int check_batch(const spdy_plan *p, int nb);
-int h2d(spdy_plan *p, double *dst, const double *src, size_t n);
-int d2h(spdy_plan *p, double *dst, const double *src, size_t n);
-int sync(spdy_plan *p);
-// host-pointer entry points call this first; elems = the largest array (in doubles) the call puts into ONE staging buffer:
-// selects the host-mapped set when it fits (see spdy_plan::hstage), the device set otherwise / by default
-int ensure_staging(spdy_plan *p, size_t elems = (size_t)-1);
-inline bool on_host_stage(const spdy_plan *p) { return p->hstage[0] && p->stage_a == p->hstage[0]; }
+int stream_sync(spdy_plan *p);        // hipStreamSynchronize of the plan's stream; refused while a capture is open
+// One host-pointer call, from its argument checks to its return: open, in..., the _dev form on the call's four staging buffers
+// c[0..3], out..., finish.  The call's route is chosen once, by open, and is the call's own; so is the list of what finish has
+// to copy out.  A call that returns early (a failed step) copies nothing anywhere and leaves nothing behind for the next one.
+//
+// The two routes.  Device: the buffers are device memory (spdy_plan::dstage), in and out are hipMemcpyAsync on the plan's stream
+// and finish is its synchronisation.  Host-mapped, for small calls (the reference's one-field-per-call pattern, level stacks):
+// the buffers are PINNED HOST memory mapped into the device's address space (spdy_plan::hstage) and both PCIe copy engines are
+// skipped -- in is a memcpy by the calling thread, the kernels read and write the buffers across the link themselves, out is
+// remembered, and finish waits (a spin on a host-mapped completion stamp, see there) and then memcpy's the results out.
+// $SPDY_HOST_STAGE_KB (default 512; 0 = off), read when the plan allocates its staging, is the largest per-buffer size that
+// takes the host-mapped route.
+//
+// open(elems): elems is the largest array, in doubles, that the call puts into ONE buffer; the call is host-mapped when that
+// fits, on the device set otherwise -- and always without a stated size.  Who states what:
+//   nb grids      spdy_spec_to_grid[_batch], spdy_grid_to_spec[_batch], spdy_uvspec_to_grid, spdy_grad_to_grid, spdy_vdspec
+//   nb spectra    spdy_laplacian, spdy_inverse_laplacian, spdy_trunct, spdy_grad, spdy_vds, spdy_uvspec
+//   no size       spdy_legendre_inv, spdy_legendre_dir, spdy_fourier_inv, spdy_fourier_dir (their other operand is the Fourier
+//                 workspace, device memory), spdy_hdiff, spdy_implicit_terms, spdy_geopotential, spdy_step_field
+struct HostCall {
+    explicit HostCall(spdy_plan *plan) : p(plan) {}
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    // SPDY_ERR_STATE inside a capture; allocates the plan's staging at its first use; chooses the route
+    int open(size_t elems = (size_t)-1);
+    double *operator[](int slot) const { return buf[slot]; }
+    bool on_host_stage() const { return host; }
+    int in(int slot, const double *src, size_t n, size_t offset = 0);   // n doubles of the caller's into buf[slot] + offset
+    int out(double *dst, int slot, size_t n);                           // n doubles of buf[slot] into the caller's, by finish at the latest
+    int finish();                                                       // on return the caller's output arrays are filled
+private:
+    spdy_plan *p;
+    double *buf[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool host = false;
+    struct Out { double *dst; const double *src; size_t bytes; } outs[3];   // host-mapped route: at most three (spdy_implicit_terms)
+    int nouts = 0;
+};
 int ensure_four(spdy_plan *p);        // four-kernel path workspace
 // T63 fused path: the direct batch WITHOUT vds -- the scaled (u, v) grids' spectra go to raw_u / raw_v (null: p->tmp_c /
 // p->tmp_d), the plain grids' to spec (spdy_direct_batch_spectral_step_dev, the level-sharded step)
