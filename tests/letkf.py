@@ -322,8 +322,10 @@ def local_problem(Y, d, r):
 
 
 def transform(C, b, E, rho, route="eigh"):
-    """batched: C (N, E, E), b (N, E) -> T (N, E, E), W, wbar, lam"""
-    A = C + ((E - 1) / rho) * np.eye(E)
+    """batched: C (N, E, E), b (N, E) -> T (N, E, E), W, wbar, lam; rho: the scalar, or (N,), one value per problem (adaptive
+    inflation: the diagonal of a problem is (E - 1) / rho of its level and column, one division)"""
+    d = (E - 1) / np.asarray(rho, np.float64)
+    A = C + (d[:, None, None] if d.ndim else d) * np.eye(E)
     lam, Vv = np.linalg.eigh(A) if route == "eigh" else jacobi(A)
     W = np.einsum("nfi,ni,nei->nfe", Vv, np.sqrt((E - 1) / lam), Vv)
     wbar = np.einsum("nfi,ni->nf", Vv, np.einsum("ngi,ng->ni", Vv, b) / lam)

@@ -219,26 +219,23 @@ def twin_ratios(g, x, inc, truth, weights):
 SPECTRAL_STATIONS, SPECTRAL_SIGMA_V, MARGIN = 8, 0.3, 1e-9
 
 
-def spectral_case(sp, o, g, E):
+def spectral_case(sp, o, g, E, stations=SPECTRAL_STATIONS):
     """The analysis from spectra: tests/ensemblestep.py's member states (the standard test ensemble), their grids by the oracle's
-    transforms, and SPECTRAL_STATIONS radiosonde-like stations reporting u, v, t and q at SOUNDING's pressures, each with half the
+    transforms, and `stations` radiosonde-like stations reporting u, v, t and q at SOUNDING's pressures, each with half the
     members' spread at its place as error and a value one such error around member 0's -> (states, grids, network)"""
     import ensemblestep as es
     sts = es.member_states(sp, E)
     x = lk.oracle_grids(o, sts)
-    net = sounding_network(g, SPECTRAL_STATIONS, seed=90, variables=(lk.U, lk.V, lk.T, lk.Q))
+    net = sounding_network(g, stations, seed=90, variables=(lk.U, lk.V, lk.T, lk.Q))
     hx = lk.observe(g, x, net)[0]
     net["error"] = 0.5 * hx.std(axis=1, ddof=1) + 1e-300
     net["value"] = hx[:, 0] + net["error"] * np.random.default_rng(91).standard_normal(len(net["var"]))
     return sts, x, net
 
 
-def spectral_analysis(o, g, sts, x, net, rho=lk.RHO):
-    """the analysed time level 1 of every member: the restatement's increments on the oracle's grids through the oracle's vdspec and
-    grid_to_spec (tests/test_gpu_letkf.py's route for a model-level network) -> (per member {vor, div, t, tr, ps}, obs_space)"""
-    space = lk.obs_space(g, x, net)
-    C, b = lk.problems(g, net, space, lk.SIGMA_H, SPECTRAL_SIGMA_V)
-    inc, _ = lk.increments(g, x, C, b, rho)
+def to_spectra(o, g, sts, inc):
+    """the analysed time level 1 of every member: the increments inc on all grid columns through the oracle's vdspec and
+    grid_to_spec (tests/test_gpu_letkf.py's route) -> per member {vor, div, t, tr, ps}"""
     grid = lambda a: a.reshape(a.shape[:-1] + (g.il, g.ix))
     out = []
     for e, st in enumerate(sts):
@@ -247,7 +244,15 @@ def spectral_analysis(o, g, sts, x, net, rho=lk.RHO):
                     "t": st["t"][0] + np.stack([o.grid_to_spec(grid(inc["t"][e])[k]) for k in range(o.kx)]),
                     "tr": st["tr"][0] + np.stack([o.grid_to_spec(grid(inc["q"][e])[k]) for k in range(o.kx)]),
                     "ps": st["ps"][0] + o.grid_to_spec(grid(inc["ps"][e]))})
-    return out, space
+    return out
+
+
+def spectral_analysis(o, g, sts, x, net, rho=lk.RHO):
+    """the restatement's increments on the oracle's grids, through `to_spectra` -> (per member {vor, div, t, tr, ps}, obs_space)"""
+    space = lk.obs_space(g, x, net)
+    C, b = lk.problems(g, net, space, lk.SIGMA_H, SPECTRAL_SIGMA_V)
+    inc, _ = lk.increments(g, x, C, b, rho)
+    return to_spectra(o, g, sts, inc), space
 
 
 def make(sp, E, obs, sigma_v=0.0, rho=lk.RHO, sigma_h=lk.SIGMA_H):

@@ -108,3 +108,22 @@ def same_rows(got, want):
     got, want = np.ascontiguousarray(got, np.float64), np.ascontiguousarray(want, np.float64)
     nan = np.isnan(want)
     return got.shape == want.shape and bool((np.isnan(got) == nan).all()) and support.same_bits(np.where(nan, 0.0, got), np.where(nan, 0.0, want))
+
+
+# ------------------------------------------------------------------------------------------------ what the GPU tests share
+def restated(got, obs, gross, groups=None, ngroups=5, in_column=None, keep=None, depb=None, code=None):
+    """the restatement on the device's own y, departure and errors -> (decisions, the statistics' rows)"""
+    dec = check(got["y"], got["departure"], obs["error"], gross, in_column, keep)
+    code = dec["check"] if code is None else code
+    rows = stats(obs["var"] if groups is None else groups, ngroups, code, got["departure"], dec["s2"], obs["error"], depb)
+    return dec, rows
+
+
+def table(stats):
+    return np.stack([stats[n] for n in COLUMNS], axis=1)
+
+
+def same_decisions(got, dec, obs):
+    rinv = 1.0 / (obs["error"] * obs["error"])
+    return (support.same_bits(got["obs_used"], dec["used"].astype(np.float64)) and support.same_bits(got["obs_check"], dec["check"])
+            and support.same_bits(got["obs_rinv"], reff(dec["used"], rinv)))

@@ -19,15 +19,16 @@ FIRST = lambda nobs: [0, 1, 1, 300, nobs]      # a one-observation slot, an empt
 DRIFT, DRIFT_PASSES = 0.25, 8
 
 
-def drifting(g, x, S, seed, fraction=DRIFT):
+def drifting(g, x, S, seed, fraction=DRIFT, passes=DRIFT_PASSES):
     """S ensembles for a window that ends at x: xs[s] = x + (S - 1 - s) fraction (member spread) (a smooth seeded field of unit
-    standard deviation per member and variable), so the difference grows with the distance from the last slot; the last one is x"""
+    standard deviation per member and variable), so the difference grows with the distance from the last slot; the last one is x.
+    passes: the smoothing of the seeded field, 1-2-1 averages (fewer where a large ensemble on a large grid makes them the cost)"""
     rng = np.random.default_rng(seed)
     xs = []
     for s in range(S - 1):
         y = {}
         for v in lk.VARS:
-            f = nt.smooth(rng.standard_normal(x[v].shape), DRIFT_PASSES)
+            f = nt.smooth(rng.standard_normal(x[v].shape), passes)
             y[v] = x[v] + ((S - 1 - s) * fraction * lk.SCALE[v][1] / f.std()) * f
         xs.append(y)
     return xs + [x]
@@ -58,3 +59,39 @@ def observe_all(lt, xs, first):
     lt.set_slots(first)
     for s, x in enumerate(xs):
         lt.observe_grid(s, *(lk.grids(x) if isinstance(x, dict) else x))
+
+
+# ------------------------------------------------------------------------------------------------ every feature at once
+EVERYTHING = {"E": 8, "drop": 5, "sigma_v": 0.1, "stride": (2, 2), "relaxation": (0.3, 0.9), "gross": 3.0, "sigma_b": 0.5,
+              "patches": (1.0, 1.1, 1.45)}
+
+
+def everything_inputs(g, S=3, first_of=lambda n: [0, 300, 700, n], seed=71):
+    """One analysis with every feature on (EVERYTHING): E = 8 without member 5; tests/letkfpressure.py's crafted ensemble and, from
+    the members in use, its network with observations at a pressure, in S slots on ensembles that drift to the analysed one; values
+    planted on both sides of the background check's threshold (tests/letkfqc.py's plant, from the restatement's own hxmean and
+    spread); an inflation field of three values in patches -> a dict: x, xs, obs, first, keep, field (kx, ncol), outside, inside"""
+    import letkfqc as qc
+    c = EVERYTHING
+    keep = tuple(e for e in range(c["E"]) if e != c["drop"])
+    x = lp.craft(g, c["E"], seed)
+    xs = drifting(g, x, S, seed + 1, passes=2)
+    obs = lp.network(g, lk.compact(x, keep))
+    first = first_of(len(obs["var"]))
+    space = lk.obs_space(g, x, obs, keep, xs=xs, first=first)
+    obs["value"], outside, inside = qc.plant(obs, space["hxmean"], qc.spread2(space["y"], keep), c["gross"], seed)
+    which = (np.arange(g.ix * g.il)[None, :] // 700 + np.arange(g.kx)[:, None]) % 3
+    return {"x": x, "xs": xs, "obs": obs, "first": first, "keep": keep, "field": np.array(c["patches"])[which], "outside": outside,
+            "inside": inside}
+
+
+def everything_object(sp, case):
+    """the analysis object of `everything_inputs` with every setting made and the inflation field uploaded"""
+    c = EVERYTHING
+    lt = lp.make(sp, c["E"], case["obs"], c["sigma_v"])
+    lt.set_weight_stride(*c["stride"])
+    lt.set_relaxation(*c["relaxation"])
+    lt.set_background_check(c["gross"])
+    lt.set_adaptive_inflation(c["sigma_b"])
+    lt.inflation_field().upload(case["field"].reshape((sp.kx,) + sp.grid_shape))
+    return lt

@@ -3,12 +3,21 @@ restatement (tests/letkf.py): the observation operator, the analysis of gridded 
 4, 8, 16, 17, 31, 32) and every level class of the solve (all slots of a round live, idle slots, kx > 16), at the edge columns of
 the grid, on hard local problems near the sweep cap, the exact statements the increment form makes -- the same bits wherever an
 observation sits in the scan among them --, the closed form of one observation, the analysis of an ensemble's spectral state
-against the restatement fed by the oracle's transforms, and the capture.  T30 unless said otherwise."""
+against the restatement fed by the oracle's transforms, and the capture.  T30 unless said otherwise; the section "on the T63 L16
+grid" holds the operator and the plain analysis to the same rules at 192 x 96 x 16 and E = 2, 3, 16, 32, and one object with
+every later feature on at once (test_everything_at_once_t63) to the restatements of all of them."""
 import numpy as np
 import pytest
 
 import ensemblestep as es
 import letkf as lk
+import letkfinfl as lf
+import letkfinterp as li
+import letkfmask as lm
+import letkfpressure as lp
+import letkfqc as qc
+import letkfrelax as lr
+import letkfslots as ls
 import support
 
 pytestmark = pytest.mark.gpu
@@ -28,12 +37,10 @@ def plans():
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the operator
-@pytest.mark.parametrize("E", [3, 32])
-def test_operator(E, plans):
+def operator(tag, sp, g, E):
     """hx, hxmean and departure of about 40 observations -- on a grid point, between columns ix-1 and 0, poleward of the outermost
     rows, at lon = 360 and at negative longitude among them -- within 16 eps max|x| of the restatement: a four-term convex sum and an
-    E-term sum in the same order"""
-    sp, g = plans()
+    E-term sum in the same order; y is hx - hxmean in every bit"""
     x = lk.ensemble(g, E, seed=40 + E)
     obs = lk.edge_obs(g, x)
     lt = lk.make(sp, E, obs)
@@ -45,10 +52,17 @@ def test_operator(E, plans):
     for name, mine, ref, sc in (("hx", got["hx"], hx, scale[:, None]), ("hxmean", got["hxmean"], hxmean, scale),
                                 ("departure", got["departure"], dep, scale)):
         worst = float(np.max(np.abs(mine - ref) / (16 * lk.EPS * sc)))
-        print("[letkf operator E=%d] %s: %.3f of the bound" % (E, name, worst))
+        print("[letkf operator %sE=%d] %s: %.3f of the bound" % (tag, E, name, worst))
         assert mine.shape == ref.shape and worst <= 1.0, (name, worst)
     assert support.same_bits(lt.field("y").numpy(), got["hx"] - got["hxmean"][:, None])
     lt.close()
+
+
+@pytest.mark.parametrize("E", [3, 32])
+def test_operator(E, plans):
+    """kx = 5: `operator`"""
+    sp, g = plans()
+    operator("", sp, g, E)
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the analysis on grids
@@ -466,4 +480,102 @@ def test_capture(E, plans, oracle_factory):
         gr.close()
     finally:
         sp.use_torch_stream()
+    lt.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 7. on the T63 L16 grid
+T63 = "t63k16"
+
+
+@pytest.mark.parametrize("E", [3, 32])
+def test_operator_t63(E, plans):
+    """192 x 96 x 16: `operator` -- the wrap cell between longitude 191 and 0 and the rows poleward of +-88.57 degrees"""
+    sp, g = plans(T63, 32)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    operator("T63 L16 ", sp, g, E)
+
+
+@pytest.mark.parametrize("E", [2, 3, 32])
+def test_analysis_t63(E, plans):
+    """192 x 96 x 16, sigma_v = 0.1, next to test_analysis_t63_edges' E = 16: the clustered set (1 500 observations, more than three
+    chunks of 256) and the sparse set in one network, compared at columns_for's columns and at every edge column in range of an
+    observation, under the rule of test_analysis_on_grids, the limits' Jacobi route at 32 of the columns.  E = 32: one level in
+    flight, all 256 threads on it, the largest LDS request, 18 432 workgroups"""
+    sp, g = plans(T63, 32)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16) and levels_in_flight(E, g.kx) == (1 if E == 32 else 4)
+    x = lk.ensemble(g, E, seed=63 + E)
+    obs = lk.concat(lk.clustered_obs(g, x), lk.sparse_obs(g, x))
+    assert len(obs["var"]) > 3 * lk.CHUNK
+    edge = lk.edge_columns(g)
+    edge = edge[lk.in_range(g, obs, edge).any(axis=1)]
+    cols = np.unique(np.concatenate([lk.columns_for(g, obs, lk.SIGMA_H, most=32), edge]))
+    assert len(edge) >= 100
+    worst, kappa = compare("T63 L16", sp, g, x, obs, E, 0.1, cols, sample=32)
+    assert max(worst.values()) <= 1.0, worst
+
+
+def test_everything_at_once_t63(plans):
+    """192 x 96 x 16, one object with every feature on (tests/letkfslots.py's EVERYTHING): E = 8 without member 5, the crafted network
+    with observations at a pressure in three slots on drifting ensembles, weight stride (2, 2), the background check with planted
+    gross errors, relaxation (0.3, 0.9) and adaptive inflation from a field in patches.  Two analysis calls, the second reads the
+    field the first one wrote.  Each call: hx, slot_ps, slot_out, hxmean, y, departure and obs_lnsigma have the restatement's bits on
+    the library's stencils, and so have the decisions, obs_rinv and the statistics' rows; the increments of the members in use, at a
+    column of every stencil class and at columns_for's, against tests/letkfinterp.py's analysis fed keep, the stencils, r_eff, xs
+    and first and the field the call read, then tests/letkfrelax.py's relaxation, within the larger of the interpolation rule (16 x
+    the difference of the two eigen routes, 64 n eps max|x - mean|) and letkfrelax.limit; obs_s2 to the bit, the sums within
+    letkfinfl.bound, and the field from the device's own sums to the bit"""
+    sp, _ = plans(T63, 32)
+    g = lp.Geometry(sp)                                          # ln fsg by the C library's log, as the host code forms it
+    c, case = ls.EVERYTHING, ls.everything_inputs(g)
+    x, xs, obs, first, keep = (case[n] for n in ("x", "xs", "obs", "first", "keep"))
+    E, n, si, sj = c["E"], len(keep), *c["stride"]
+    lt = ls.everything_object(sp, case)
+    xc = lk.compact(x, keep)
+    sc = lk.perturbation_scale(xc)
+    idx, wgt = li.stencils(g, si, sj)
+    cols = np.unique(np.concatenate(list(li.class_columns(g, si, sj).values()) + [lk.columns_for(g, obs, lk.SIGMA_H, most=24, outside=4)]))
+    names = lk.FIELDS + ("slot_ps", "slot_out", "obs_check", "obs_rinv")
+    last = None
+    for call in range(2):
+        before = lt.field("rho").numpy()
+        assert support.same_bits(before.reshape(g.kx, -1), case["field"]) if call == 0 else support.same_bits(before, last["rho"])
+        ls.observe_all(lt, xs, first)
+        got = lk.run(lt, x, lm.flags(E, keep), slots=True, names=names)
+        stats = qc.table(lt.obs_stats())
+        # observation space, decisions and statistics
+        want = lk.obs_space(g, x, obs, keep, lp.tables(lt), xs, first)
+        for name in ("hx", "slot_ps", "slot_out", "hxmean", "y", "departure", "obs_lnsigma"):
+            assert support.same_bits(got[name], want[name]), (call, name)
+        dec = qc.check(want["y"], want["departure"], obs["error"], c["gross"], want["obs_used"], keep)
+        assert qc.same_decisions(got, dec, obs), call
+        out = want["obs_used"] == 0.0
+        assert out.sum() >= 10 and (got["obs_check"][out] == qc.OUT).all() and (got["obs_check"][case["outside"]] != qc.PASSED).all()
+        assert (got["obs_check"][np.setdiff1d(case["outside"], np.nonzero(out)[0])] == qc.REJECTED).all()
+        assert (got["obs_check"][np.setdiff1d(case["inside"], np.nonzero(out)[0])] == qc.PASSED).all()
+        assert qc.same_rows(stats, qc.stats(obs["var"], 5, dec["check"], want["departure"], dec["s2"], obs["error"])), call
+        assert stats[:, 1].sum() == out.sum() and stats[:, 2].sum() == (dec["check"] == qc.REJECTED).sum() >= 8
+        # the increments
+        how = dict(keep=keep, stencil=lp.tables(lt), r_eff=qc.reff(dec["used"], 1.0 / (obs["error"] * obs["error"])), xs=xs, first=first)
+        res = {}
+        for route in ("eigh", "jacobi"):
+            raw, _, _ = li.analyse(g, x, obs, lk.SIGMA_H, c["sigma_v"], before, si, sj, route, cols, (idx, wgt), **how)
+            res[route] = lr.relax(lr.at_columns(xc, cols), raw, *c["relaxation"])
+        (ref, f), (alt, _) = res["eigh"], res["jacobi"]
+        worst = {}
+        for v in lk.VARS:
+            lim = np.maximum(max(16 * float(np.max(np.abs(ref[v] - alt[v]))), 64 * n * lk.EPS * sc[v]), lr.limit(xc, f, n, v))
+            worst[v] = float(np.max(np.abs(lk.at_columns(got[v][list(keep)], cols) - ref[v]) / lim[None]))
+            assert ref[v].any() and lm.zero_bits(got[v][c["drop"]]), v
+        # adaptive inflation
+        s2o, p, bound, _ = lf.restate(g, lt, before.reshape(g.kx, -1)[:, cols], lk.SIGMA_H, c["sigma_v"], c["sigma_b"], keep=keep,
+                                      reff_field=True, cols=cols)
+        worst["sums"] = lf.worst_ratio(got["infl_parm"].reshape(3, g.kx, -1)[:, :, cols], p, bound)
+        print("[letkf everything T63 L16 call %d] %d columns, %d rejected, %d out of column, largest f %.3f, ratio to the limit: %s"
+              % (call, len(cols), int(stats[:, 2].sum()), int(out.sum()), max(float(a.max()) for a in f.values()),
+                 " ".join("%s %.3f" % kv for kv in worst.items())))
+        assert max(worst.values()) <= 1.0, (call, worst)
+        assert support.same_bits(got["obs_s2"], s2o), call
+        assert support.same_bits(got["rho"], lf.update(before, got["infl_parm"], c["sigma_b"])) and not support.same_bits(got["rho"], before)
+        assert last is None or any(not support.same_bits(got[v], last[v]) for v in lk.VARS)
+        last = got
     lt.close()

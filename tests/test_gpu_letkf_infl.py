@@ -2,7 +2,8 @@
 kernels against the NumPy restatement of tests/letkfinfl.py, fed with the device's own y, departure, 1 / error^2 and ln sigma_o: s2
 bit for bit, the sums within the restatement's absolute bound, the update bit for bit from the device's own sums.  The transform
 under a field against the feature-off object with that scalar, on every route; the member mask; a captured cycle that advances the
-field by itself; a twin experiment of three cycles.  T30."""
+field by itself; a twin experiment of three cycles.  T30; the section "on the T63 L16 grid" holds the sums, the update and the
+transform under a field to the same statements at 192 x 96 x 16."""
 import numpy as np
 import pytest
 
@@ -23,31 +24,35 @@ SIGMA_V = 0.1
 RHO0 = 1.3
 
 
-def _plan(kx, nmem):
-    if kx in (5, 8):
-        sp = support.ensemble_plan({5: "t30k5", 8: "t30"}[kx], nmem)
+T63 = "t63k16"
+
+
+def _plan(tag, nmem):
+    """tag: a variant's, or "t30" at a level count of its own on tests/levels.py's sigma as ("t30", kx)"""
+    if isinstance(tag, tuple):
+        sp = levels.plan(tag[0], tag[1], nmem * (4 * tag[1] + 4))
     else:
-        sp = levels.plan("t30", kx, nmem * (4 * kx + 4))
+        sp = support.ensemble_plan(tag, nmem)
     return sp, lp.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
     with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
-        yield lambda kx=8, nmem=32: get(kx, nmem)
+        yield lambda tag="t30", nmem=32: get(tag, nmem)
 
 
 @pytest.fixture(scope="module")
 def big(plans):
-    """E -> (the ensemble, 700 observations: the operator's edge cases, the sparse set and a cluster); made once, never changed"""
+    """(E, tag) -> (the ensemble, 700 observations: the operator's edge cases, the sparse set and a cluster); made once, never changed"""
     made = {}
 
-    def get(E):
-        if E not in made:
-            _, g = plans()
+    def get(E, tag="t30"):
+        if (E, tag) not in made:
+            _, g = plans(tag)
             x = lk.ensemble(g, E, seed=80 + E)
-            made[E] = (x, lk.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=700)), slice(0, 700)))
-        return made[E]
+            made[(E, tag)] = (x, lk.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=700)), slice(0, 700)))
+        return made[(E, tag)]
     return get
 
 
@@ -65,12 +70,16 @@ def analyse(lt, x, **how):
     return dict(lk.run(lt, x, names=STATE, **how), before=before)
 
 
-def against_restatement(tag, g, lt, got, sigma_h, sigma_v, sigma_b, bounds=(li.RHO_MIN, li.RHO_MAX), keep=None, reff_field=False):
+def against_restatement(tag, g, lt, got, sigma_h, sigma_v, sigma_b, bounds=(li.RHO_MIN, li.RHO_MAX), keep=None, reff_field=False, cols=None):
     """obs_s2 to the bit, infl_parm within the bound, rho' from the device's own infl_parm and the prior field to the bit -> the
-    worst ratio of a sum's error to its bound"""
-    s2o, p, lim, _ = li.restate(g, lt, got["before"].reshape(g.kx, -1), sigma_h, sigma_v, sigma_b, *bounds, keep=keep, reff_field=reff_field)
+    worst ratio of a sum's error to its bound.  cols: the restatement's sums, the costly part, at these grid columns only (the
+    update and obs_s2 are held everywhere)"""
+    before, parm = got["before"].reshape(g.kx, -1), got["infl_parm"].reshape(3, g.kx, -1)
+    if cols is not None:
+        before, parm = before[:, cols], parm[:, :, cols]
+    s2o, p, lim, _ = li.restate(g, lt, before, sigma_h, sigma_v, sigma_b, *bounds, keep=keep, reff_field=reff_field, cols=cols)
     assert support.same_bits(got["obs_s2"], s2o), tag
-    worst = li.worst_ratio(got["infl_parm"], p, lim)
+    worst = li.worst_ratio(parm, p, lim)
     print("[letkf infl] %s: worst error of a sum / bound %.3g" % (tag, worst))
     assert worst <= 1.0, (tag, worst)
     assert support.same_bits(got["rho"], li.update(got["before"], got["infl_parm"], sigma_b, *bounds)), tag
@@ -78,14 +87,10 @@ def against_restatement(tag, g, lt, got, sigma_h, sigma_v, sigma_b, bounds=(li.R
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the sums
-@pytest.mark.parametrize("nobs", [0, 1, 255, 256, 257, 700])
-@pytest.mark.parametrize("E", [2, 3, 5, 32])
-def test_sums(E, nobs, plans, big):
-    """kx = 8, sigma_v = 0 and 0.1 in turn on one object: the second call starts from the field the first one left.  nobs: the edges
-    of the scan's chunk of 256 and a network of more than two chunks; an empty network leaves exact zeros and the field's bits"""
-    sp, g = plans()
-    x, all_obs = big(E)
-    obs = lk.subset(all_obs, slice(0, nobs))
+def sums(tag, sp, g, E, x, obs, cols=None):
+    """sigma_v = 0 and 0.1 in turn on one object: the second call starts from the field the first one left; an empty network leaves
+    exact zeros and the field's bits"""
+    nobs = len(obs["var"])
     lt = lk.make(sp, E, obs, 0.0)
     lt.set_adaptive_inflation(0.5)
     assert (lt.field("rho").numpy() == lk.RHO).all()
@@ -95,15 +100,24 @@ def test_sums(E, nobs, plans, big):
         if nobs == 0:
             assert lm.zero_bits(got["infl_parm"]) and support.same_bits(got["rho"], got["before"])
             continue
-        against_restatement("E=%d nobs=%d sigma_v=%g" % (E, nobs, sigma_v), g, lt, got, lk.SIGMA_H, sigma_v, 0.5)
+        against_restatement("%sE=%d nobs=%d sigma_v=%g" % (tag, E, nobs, sigma_v), g, lt, got, lk.SIGMA_H, sigma_v, 0.5, cols=cols)
         assert not support.same_bits(got["rho"], got["before"]) and (got["infl_parm"][2] > 0.0).any()
     lt.close()
+
+
+@pytest.mark.parametrize("nobs", [0, 1, 255, 256, 257, 700])
+@pytest.mark.parametrize("E", [2, 3, 5, 32])
+def test_sums(E, nobs, plans, big):
+    """kx = 8: `sums`.  nobs: the edges of the scan's chunk of 256 and a network of more than two chunks"""
+    sp, g = plans()
+    x, all_obs = big(E)
+    sums("", sp, g, E, x, lk.subset(all_obs, slice(0, nobs)))
 
 
 @pytest.mark.parametrize("kx,E", [(5, 4), (7, 4), (15, 4), (20, 4), (32, 2)])
 def test_sums_level_classes(kx, E, plans):
     """the level counts of tests/test_gpu_letkf.py's classes and 32, the most: lane k < kx carries level k"""
-    sp, g = plans(kx, E)
+    sp, g = plans({5: "t30k5", 8: "t30"}.get(kx, ("t30", kx)), E)
     x = lk.ensemble(g, E, seed=kx)
     obs = lk.concat(lk.clustered_obs(g, x, n=300), lk.sparse_obs(g, x))
     lt = lk.make(sp, E, obs, SIGMA_V)
@@ -119,7 +133,7 @@ def test_sums_level_classes(kx, E, plans):
 def test_sums_padded_scans(pattern, plans):
     """tests/letkf.py's padded patterns: a first chunk without a survivor, survivors in a chunk's last wave only, a whole chunk
     without one in the middle"""
-    sp, g = plans(5, 3)
+    sp, g = plans("t30k5", 3)
     E = 3
     x = lk.ensemble(g, E, seed=31)
     real, pad = lk.padded_inputs(g, x)
@@ -131,21 +145,26 @@ def test_sums_padded_scans(pattern, plans):
     lt.close()
 
 
-def test_sums_edge_columns(plans):
+def sums_edge_columns(tag, sp, g, edge_only=False):
     """the edge columns and edge observations of tests/letkf.py's edge_inputs at EDGE_SIGMA_H: polar rows, the periodic wrap, edge
-    columns out of range of everything, which keep rho's bits"""
-    sp, g = plans(5, 3)
+    columns out of range of everything, which keep rho's bits.  edge_only: the restatement's sums are formed at the edge columns only"""
     E = 3
     x = lk.ensemble(g, E, seed=32)
     obs, cols, out = lk.edge_conditions(g, lk.edge_inputs(g, x))
     lt = lk.make(sp, E, obs, SIGMA_V, sigma_h=lk.EDGE_SIGMA_H)
     lt.set_adaptive_inflation(0.5)
     got = analyse(lt, x)
-    against_restatement("edge columns", g, lt, got, lk.EDGE_SIGMA_H, SIGMA_V, 0.5)
+    against_restatement(tag + "edge columns", g, lt, got, lk.EDGE_SIGMA_H, SIGMA_V, 0.5, cols=cols if edge_only else None)
     rho, before = got["rho"].reshape(g.kx, -1), got["before"].reshape(g.kx, -1)
     assert support.same_bits(np.ascontiguousarray(rho[:, cols[out]]), np.ascontiguousarray(before[:, cols[out]]))
     assert (got["infl_parm"].reshape(3, g.kx, -1)[2][:, cols[~out]] > 0.0).any(axis=0).all()
     lt.close()
+
+
+def test_sums_edge_columns(plans):
+    """kx = 5: `sums_edge_columns`"""
+    sp, g = plans("t30k5", 3)
+    sums_edge_columns("", sp, g)
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the update
@@ -188,7 +207,7 @@ def gross_errors(obs, every=7, size=40.0):
     return out
 
 
-def uniform_route(tag, g, lt, x, sigma_h=lk.SIGMA_H, keep=None, reff_field=False, **how):
+def uniform_route(tag, g, lt, x, sigma_h=lk.SIGMA_H, keep=None, reff_field=False, cols=None, **how):
     """feature off with the scalar RHO0, then on with the field uniform at RHO0: the same increments in every bit; and the
     estimate of that call against the restatement"""
     lt.set_localization(sigma_h, SIGMA_V, RHO0)
@@ -204,40 +223,43 @@ def uniform_route(tag, g, lt, x, sigma_h=lk.SIGMA_H, keep=None, reff_field=False
         assert support.same_bits(on[v], off[v]), (tag, v)
     assert any(off[v].any() for v in lk.VARS) or (keep is not None and len(keep) < 2), tag
     if keep is None or len(keep) >= 2:
-        against_restatement(tag, g, lt, on, sigma_h, SIGMA_V, 0.5, keep=keep, reff_field=reff_field)
+        against_restatement(tag, g, lt, on, sigma_h, SIGMA_V, 0.5, keep=keep, reff_field=reff_field, cols=cols)
     else:
         assert support.same_bits(on["rho"], on["before"]), tag   # n < 2: rho is untouched
     return on
 
 
-def test_transform_uniform_routes(plans, big):
+def uniform_routes(tag, sp, g, E, x, obs, cols=None):
     """plain, masked (3 of 5 and one member), weight stride (2, 2), relaxed, slots, background check with rejections"""
-    sp, g = plans()
-    E = 5
-    x, obs = big(E)
     lt = lk.make(sp, E, obs, SIGMA_V)
-    plain = uniform_route("plain", g, lt, x)
+    plain = uniform_route(tag + "plain", g, lt, x, cols=cols)
     for keep in ((0, 2, 3), (2,)):
-        uniform_route("masked %s" % (keep,), g, lt, x, keep=keep, use=support.dev(np.array(lm.flags(E, keep), np.int32)))
+        uniform_route(tag + "masked %s" % (keep,), g, lt, x, keep=keep, cols=cols, use=support.dev(np.array(lm.flags(E, keep), np.int32)))
     ls.observe_all(lt, [x] * 4, ls.FIRST(len(obs["var"])))
-    slots = uniform_route("slots", g, lt, x, slots=True)
+    slots = uniform_route(tag + "slots", g, lt, x, cols=cols, slots=True)
     for v in lk.VARS:
         assert support.same_bits(slots[v], plain[v]), v
     assert support.same_bits(slots["rho"], plain["rho"])
     lt.set_slots(None)
     lt.set_relaxation(0.3, 0.9)
-    uniform_route("relaxed", g, lt, x)
+    uniform_route(tag + "relaxed", g, lt, x, cols=cols)
     lt.set_relaxation()
     lt.set_weight_stride(2, 2)
-    strided = uniform_route("weight stride", g, lt, x)
+    strided = uniform_route(tag + "weight stride", g, lt, x, cols=cols)
     assert support.same_bits(strided["rho"], plain["rho"])       # the estimate does not depend on where transforms are solved
     lt.close()
     bad = gross_errors(obs)
     lt = lk.make(sp, E, bad, SIGMA_V)
     lt.set_background_check(3.0)
-    uniform_route("background check", g, lt, x, reff_field=True)
+    uniform_route(tag + "background check", g, lt, x, reff_field=True, cols=cols)
     assert (lt.field("obs_check").numpy() == qc.REJECTED).any()
     lt.close()
+
+
+def test_transform_uniform_routes(plans, big):
+    """kx = 8, E = 5: `uniform_routes`"""
+    sp, g = plans()
+    uniform_routes("", sp, g, 5, *big(5))
 
 
 def test_transform_uniform_at_pressure(plans):
@@ -251,13 +273,9 @@ def test_transform_uniform_at_pressure(plans):
     lt.close()
 
 
-@pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
-def test_transform_patches(stride, plans, big):
+def patches(sp, g, E, x, obs, stride):
     """a field of three values in patches: every (column, level) has the bits of the feature-off object with that scalar; ps those
     of level kx-1's value; at a weight stride at the coarse columns"""
-    sp, g = plans()
-    E = 5
-    x, obs = big(E)
     lt = lk.make(sp, E, obs, SIGMA_V)
     if stride != (1, 1):
         lt.set_weight_stride(*stride)
@@ -283,6 +301,13 @@ def test_transform_patches(stride, plans, big):
             assert at.any() and support.same_bits(a[:, :, cols][:, at], r[:, :, cols][:, at]), (v, n)
         assert not support.same_bits(a, refs[0][v].reshape(E, -1, ncol)), v
     lt.close()
+
+
+@pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
+def test_transform_patches(stride, plans, big):
+    """kx = 8, E = 5: `patches`"""
+    sp, g = plans()
+    patches(sp, g, 5, *big(5), stride)
 
 
 # ---------------------------------------------------------------------------------------------------- 4. the mask
@@ -315,7 +340,7 @@ def test_capture(plans, oracle_factory):
     rho and of the state: the graph advances the field by itself.  It has two nodes more than the feature-off capture, which has
     the five of tests/test_gpu_letkf.py again after set_adaptive_inflation(on=False)"""
     import torch
-    sp, g = plans(5, 3)
+    sp, g = plans("t30k5", 3)
     E = 3
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
@@ -362,7 +387,7 @@ def test_capture(plans, oracle_factory):
 
 def test_names_are_valid_on_every_object(plans):
     """tests/test_gpu_plan_objects.py's rule for the new names: asking makes the block and leaves the feature off"""
-    sp, g = plans(5, 3)
+    sp, g = plans("t30k5", 3)
     x = lk.ensemble(g, 3, seed=33)
     lt = lk.make(sp, 3, lk.sparse_obs(g, x), SIGMA_V, rho=1.25)
     assert lt.field("infl_parm").shape == (3, 5) + sp.grid_shape and lt.field("obs_s2").shape == (lt.nobs,)
@@ -429,3 +454,43 @@ def test_twin_experiment(oracle_factory):
               % (cycle, " ".join("%.4f" % v for v in rho[:, reached].mean(axis=1))))
         ens.startup(tc.DELT)                                     # the truth is stepped on alongside, as in tests/test_gpu_twin_cycle.py
     lt.close(); nat.close(); sp.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 7. on the T63 L16 grid
+def compared_columns(g, obs):
+    """where the restatement's sums are formed on the larger grid: the columns nearest to the observations, those at the edge of
+    their range and some out of range (lk.columns_for), and every eighth edge column in range of an observation"""
+    edge = lk.edge_columns(g)
+    edge = edge[lk.in_range(g, obs, edge).any(axis=1)]
+    return np.unique(np.concatenate([lk.columns_for(g, obs, lk.SIGMA_H, most=96), edge[::8]]))
+
+
+@pytest.mark.parametrize("E", [3, 32])
+def test_sums_t63(E, plans, big):
+    """192 x 96 x 16, 700 observations: `sums` -- letkf_infl_kernel carries level k in lane k < 16"""
+    sp, g = plans(T63)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    x, obs = big(E, T63)
+    cols = compared_columns(g, obs)
+    assert len(cols) >= 150
+    sums("T63 L16 ", sp, g, E, x, obs, cols)
+
+
+def test_sums_edge_columns_t63(plans):
+    """192 x 96 x 16: `sums_edge_columns`"""
+    sp, g = plans(T63)
+    sums_edge_columns("T63 L16 ", sp, g, edge_only=True)
+
+
+def test_transform_uniform_routes_t63(plans, big):
+    """192 x 96 x 16, E = 5: `uniform_routes`"""
+    sp, g = plans(T63)
+    x, obs = big(5, T63)
+    uniform_routes("T63 L16 ", sp, g, 5, x, obs, compared_columns(g, obs))
+
+
+@pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
+def test_transform_patches_t63(stride, plans, big):
+    """192 x 96 x 16, E = 5: `patches`"""
+    sp, g = plans(T63)
+    patches(sp, g, 5, *big(5, T63), stride)

@@ -2,7 +2,7 @@
 Letkf.set_weight_stride) against its NumPy restatement (tests/letkfinterp.py on tests/letkf.py): the coarse columns
 bit for bit against the same object's stride-(1, 1) call, the weight buffer and the increments at every stencil class against the
 restatement, the largest LDS request with a column list, the exact statements, the analysis of an ensemble's spectral state and the
-capture.  T30, kx = 5 unless said otherwise."""
+capture.  T30, kx = 5; the section "on the T63 L16 grid" holds the kernels and the host tables to the same rules at 192 x 96 x 16."""
 import numpy as np
 import pytest
 
@@ -14,7 +14,7 @@ import support
 pytestmark = pytest.mark.gpu
 
 STRIDES = [(2, 2), (3, 5), (4, 47)]
-CENTRE, POLAR = (100.0, 20.0), (357.0, 83.0)
+CENTRE, POLAR, class_columns = li.CENTRE, li.POLAR, li.class_columns
 
 
 def _plan(tag, nmem):
@@ -34,48 +34,25 @@ def observations(g, x, n=600):
     return lk.concat(lk.clustered_obs(g, x, n=n), lk.clustered_obs(g, x, n=200, centre=POLAR, seed=6), lk.sparse_obs(g, x))
 
 
-def class_columns(g, si, sj):
-    """{stencil class: grid columns}: of every class the column nearest to CENTRE, of the last three the one nearest to POLAR, and of
-    the first four also the one farthest from both.  At a stride whose only coarse rows are 0 and il-1 there is no column on a
-    coarse row only other than those of the last two classes, and the one latitude interval is the last one"""
-    rows = li.coarse_rows(g, sj)
-    jj, ii = np.divmod(np.arange(g.ix * g.il), g.ix)
-    crow, clon = np.isin(jj, rows), ii % si == 0
-    inner = (jj > 0) & (jj < (rows[-2] if len(rows) > 2 else g.il - 1))
-    classes = {"interior": ~crow & ~clon & inner & (ii < g.ix - si), "coarse longitude": ~crow & clon & inner,
-               "coarse row": crow & ~clon & inner, "wrap": ~clon & (ii > g.ix - si) & (jj > 0) & (jj < g.il - 1),
-               "last interval": (jj >= rows[-2]) & (jj < g.il - 1) & (~crow if rows[-1] - rows[-2] > 1 else crow) & ~clon,
-               "j = 0": (jj == 0) & ~clon, "j = il-1": (jj == g.il - 1) & ~clon}
-    dc, dp = (lk.distance(g.colunit, lk.unit([p[0]], [p[1]]))[:, 0] for p in (CENTRE, POLAR))
-    out = {}
-    for n, (name, mask) in enumerate(classes.items()):
-        cand = np.nonzero(mask)[0]
-        if name == "coarse row" and len(rows) == 2:
-            continue
-        assert len(cand), name
-        out[name] = np.array([cand[dc[cand].argmin()], cand[dp[cand].argmin()] if n >= 4 else cand[np.minimum(dc, dp)[cand].argmax()]])
-    return out
-
-
 _REFERENCE = {}
 
 
-def reference(g, E, sigma_v):
-    """per (E, sigma_v), once: the ensemble, the observations, per stride the chosen columns, and the restatement's transforms by both
-    eigen routes at every coarse column those columns' stencils read (the union over the strides, solved in one batch)"""
-    if (E, sigma_v) not in _REFERENCE:
+def reference(g, E, sigma_v, tag="t30k5", strides=STRIDES):
+    """per (tag, E, sigma_v), once: the ensemble, the observations, per stride the chosen columns, and the restatement's transforms by
+    both eigen routes at every coarse column those columns' stencils read (the union over the strides, solved in one batch)"""
+    if (tag, E, sigma_v) not in _REFERENCE:
         x = lk.ensemble(g, E, seed=E)
         obs = observations(g, x)
         per = {}
-        for si, sj in STRIDES:
+        for si, sj in strides:
             idx, wgt = li.stencils(g, si, sj)
             cls = class_columns(g, si, sj)
             cols = np.unique(np.concatenate(list(cls.values())))
             per[(si, sj)] = (idx, wgt, cls, cols, li.needed(idx, wgt, cols))
         union = np.unique(np.concatenate([li.coarse_columns(g, *st)[p[4]] for st, p in per.items()]))
         T = {r: li.transforms(g, x, obs, lk.SIGMA_H, sigma_v, lk.RHO, union, r) for r in ("eigh", "jacobi")}
-        _REFERENCE[(E, sigma_v)] = (x, obs, per, union, T)
-    return _REFERENCE[(E, sigma_v)]
+        _REFERENCE[(tag, E, sigma_v)] = (x, obs, per, union, T)
+    return _REFERENCE[(tag, E, sigma_v)]
 
 
 def run_at(sp, lt, x, si, sj):
@@ -84,15 +61,13 @@ def run_at(sp, lt, x, si, sj):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the coarse columns
-@pytest.mark.parametrize("E", [2, 3, 32])
-def test_coarse_columns_bit_equal(E, plans):
-    """strides (2, 2) and (3, 5): the increments at every coarse column are bit-equal to the same object's stride-(1, 1) call on the
-    same inputs, and the other columns are not all equal to it; back at (1, 1) the object gives the first result again"""
-    sp, g = plans()
+def coarse_columns_bit_equal(sp, g, E, strides):
+    """the increments at every coarse column are bit-equal to the same object's stride-(1, 1) call on the same inputs, and the other
+    columns are not all equal to it; back at (1, 1) the object gives the first result again"""
     x = lk.ensemble(g, E, seed=60 + E)
     lt = lk.make(sp, E, observations(g, x), 0.1)
     full = lk.run(lt, x)
-    for si, sj in STRIDES[:2]:
+    for si, sj in strides:
         got = run_at(sp, lt, x, si, sj)
         coarse = lt.table("coarse_columns")
         assert np.array_equal(coarse, li.coarse_columns(g, si, sj))
@@ -106,18 +81,21 @@ def test_coarse_columns_bit_equal(E, plans):
     lt.close()
 
 
-# ---------------------------------------------------------------------------------------------------- 2. against the restatement
-@pytest.mark.parametrize("sigma_v", [0.0, 0.1])
-@pytest.mark.parametrize("E", [2, 3, 8, 16, 17, 32])
-def test_against_the_restatement(E, sigma_v, plans):
-    """rho = 1.1, strides (2, 2), (3, 5) and (4, 47); grid columns of every stencil class -- interior, on a coarse row only, on a
-    coarse longitude only, in the last longitude cell (i1 wraps to 0), in the short last latitude interval, j = 0, j = il-1 -- in
-    range of a cluster and out of it.  field("weights") at the coarse columns those stencils read: within max(16 x the difference of
-    the restatement's two eigen routes in T, 64 E eps max|T|).  The increments of each variable: within max(16 x the difference of
-    the restatement's two routes, 64 E eps max|x - mean|).  E = 2, 3 | 8 | 16 | 17, 32: an item of letkf_apply_kernel has 2, 4 | 8 |
-    16 | 32 lanes."""
+@pytest.mark.parametrize("E", [2, 3, 32])
+def test_coarse_columns_bit_equal(E, plans):
+    """strides (2, 2) and (3, 5): coarse_columns_bit_equal"""
     sp, g = plans()
-    x, obs, per, union, T = reference(g, E, sigma_v)
+    coarse_columns_bit_equal(sp, g, E, STRIDES[:2])
+
+
+# ---------------------------------------------------------------------------------------------------- 2. against the restatement
+def against_the_restatement(sp, g, E, sigma_v, tag="t30k5", strides=STRIDES):
+    """rho = 1.1; grid columns of every stencil class -- interior, on a coarse row only, on a coarse longitude only, in the last
+    longitude cell (i1 wraps to 0), in the short last latitude interval, j = 0, j = il-1 -- in range of a cluster and out of it.
+    field("weights") at the coarse columns those stencils read: within max(16 x the difference of the restatement's two eigen routes
+    in T, 64 E eps max|T|).  The increments of each variable: within max(16 x the difference of the restatement's two routes, 64 E
+    eps max|x - mean|).  The library's tables against the restatement's: the indices equal, the weights within 2 eps"""
+    x, obs, per, union, T = reference(g, E, sigma_v, tag, strides)
     sc = lk.perturbation_scale(x)
     lt = lk.make(sp, E, obs, sigma_v)
     d = np.minimum(*(lk.distance(g.colunit, lk.unit([p[0]], [p[1]]))[:, 0] for p in (CENTRE, POLAR)))
@@ -134,12 +112,22 @@ def test_against_the_restatement(E, sigma_v, plans):
         ref, alt = (li.increments(g, x, li.interpolate(t, entries, idx, wgt, cols), cols) for t in (Te, Tj))
         lim = {v: max(16 * float(np.max(np.abs(ref[v] - alt[v]))), 64 * E * lk.EPS * sc[v]) for v in lk.VARS}
         worst = {v: float(np.max(np.abs(lk.at_columns(got[v], cols) - ref[v]))) / lim[v] for v in lk.VARS}
-        print("[letkf interp E=%d sigma_v=%g stride (%d, %d)] %d columns, %d coarse; ratio to the limit: T %.3f %s"
-              % (E, sigma_v, si, sj, len(cols), len(entries), tworst, " ".join("%s %.3f" % kv for kv in worst.items())))
+        print("[letkf interp %sE=%d sigma_v=%g stride (%d, %d)] %d columns, %d coarse; ratio to the limit: T %.3f %s"
+              % ("" if tag == "t30k5" else tag + " ", E, sigma_v, si, sj, len(cols), len(entries), tworst,
+                 " ".join("%s %.3f" % kv for kv in worst.items())))
         assert all(ref[v].any() for v in lk.VARS)
         assert tworst <= 1.0, (si, sj, tworst)
         assert max(worst.values()) <= 1.0, (si, sj, worst)
     lt.close()
+
+
+@pytest.mark.parametrize("sigma_v", [0.0, 0.1])
+@pytest.mark.parametrize("E", [2, 3, 8, 16, 17, 32])
+def test_against_the_restatement(E, sigma_v, plans):
+    """strides (2, 2), (3, 5) and (4, 47): against_the_restatement.  E = 2, 3 | 8 | 16 | 17, 32: an item of letkf_apply_kernel has
+    2, 4 | 8 | 16 | 32 lanes."""
+    sp, g = plans()
+    against_the_restatement(sp, g, E, sigma_v)
 
 
 def test_many_levels_with_a_column_list():
@@ -326,3 +314,26 @@ def test_capture(plans, oracle_factory):
     finally:
         sp.use_torch_stream()
     lt.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 6. on the T63 L16 grid
+T63 = "t63k16"
+# (2, 2): 96 x 48 coarse columns; (3, 5): the short last interval 95; (96, 7): ni = 2, every cell wraps; (4, 95): rows 0 and il-1 only
+STRIDES_T63 = [(2, 2), (3, 5), (96, 7), (4, 95)]
+
+
+@pytest.mark.parametrize("E", [3, 16, 32])
+def test_against_the_restatement_t63(E, plans):
+    """192 x 96 x 16, sigma_v = 0.1: against_the_restatement at the strides that are only legal here -- si = 96 = ix / 2, where both
+    coarse longitudes' cells wrap, sj = 95, the largest -- and at (2, 2), whose weight buffer is the largest (617 MB at E = 32), and
+    (3, 5).  E = 3, 16, 32: an item of letkf_apply_kernel has 4, 16, 32 lanes and walks kx ncol = 294 912 items"""
+    sp, g = plans(T63, 32)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    against_the_restatement(sp, g, E, 0.1, T63, STRIDES_T63)
+
+
+@pytest.mark.parametrize("E", [3, 16, 32])
+def test_coarse_columns_bit_equal_t63(E, plans):
+    """192 x 96 x 16, strides (2, 2) and (3, 5): coarse_columns_bit_equal"""
+    sp, g = plans(T63, 32)
+    coarse_columns_bit_equal(sp, g, E, STRIDES_T63[:2])

@@ -1,7 +1,8 @@
 """GPU: the member mask of the analysis and the scores (include/spdy.h, "member mask"; use= of Ensemble.analyse, Ensemble.verify,
 Letkf.analyse_grid, Nature.verify_grid; Diagnostics.use_dev).  The central statement needs no tolerance: a masked
 call on E members equals, for the members in use and bit for bit, the unmasked call of an object of those n members on the
-compacted ensemble -- a path the existing tests hold to the NumPy restatement.  T30."""
+compacted ensemble -- a path the existing tests hold to the NumPy restatement.  T30; the section "on the T63 L16 grid" repeats the
+central statement, the restatement and the unread member at 192 x 96 x 16."""
 import numpy as np
 import pytest
 
@@ -23,15 +24,18 @@ IDS = ["E3-drop0", "E8-drop7", "E17-drop0,5,16", "E32-drop13", "E32-keep2,30"]
 KEEP17 = CASES[2][1]
 
 
-def _plan(kx, nmem):
-    sp = support.ensemble_plan({5: "t30k5", 8: "t30"}[kx], nmem)
+T63 = "t63k16"
+
+
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
     return sp, lp.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
     with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
-        yield lambda kx=8, nmem=32: get(kx, nmem)
+        yield lambda tag="t30", nmem=32: get(tag, nmem)
 
 
 def both_sets(g, xc):
@@ -70,10 +74,9 @@ def test_masked_equals_compact_many_levels(kx):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. against the restatement
-def test_masked_against_restatement(plans):
+def masked_against_restatement(tag, sp, g):
     """E = 8 without member 7, the clustered set: the masked increments against tests/letkf.py's analysis of the seven members,
     within that module's limits(...), the bound of the existing analysis tests"""
-    sp, g = plans()
     E, keep = 8, tuple(range(7))
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lk.clustered_obs, 0.1)
     ltc.close()
@@ -83,16 +86,20 @@ def test_masked_against_restatement(plans):
     got = lk.run(lt, x, lm.flags(E, keep))
     lt.close()
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v][list(keep)], cols) - ref[v]))) / lim[v] for v in lk.VARS}
-    print("[letkf mask E=8 n=7] kappa %.2e, ratio to the limit: %s" % (kappa, " ".join("%s %.3f" % kv for kv in worst.items())))
+    print("[letkf mask %sE=8 n=7] kappa %.2e, ratio to the limit: %s" % (tag, kappa, " ".join("%s %.3f" % kv for kv in worst.items())))
     assert max(worst.values()) <= 1.0, worst
 
 
+def test_masked_against_restatement(plans):
+    """kx = 8: `masked_against_restatement`"""
+    sp, g = plans()
+    masked_against_restatement("", sp, g)
+
+
 # ---------------------------------------------------------------------------------------------------- 3. a member not in use is not read
-@pytest.mark.parametrize("drop", [3, 7])
-def test_unused_member_reaches_nothing_on_grids(drop, plans):
+def unused_member_reaches_nothing(sp, g, drop):
     """E = 8, one member not in use holding NaN, infinities of both signs and 1e300: every output for the members in use, and the
     per-observation fields, keep the bits of the call with ordinary values there; its own increments and y are 0.0"""
-    sp, g = plans()
     E = 8
     keep = tuple(e for e in range(E) if e != drop)
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lambda g, xc: lk.concat(lk.clustered_obs(g, xc, n=300), lk.sparse_obs(g, xc)), 0.1)
@@ -113,6 +120,13 @@ def test_unused_member_reaches_nothing_on_grids(drop, plans):
     lt.close()
 
 
+@pytest.mark.parametrize("drop", [3, 7])
+def test_unused_member_reaches_nothing_on_grids(drop, plans):
+    """kx = 8: `unused_member_reaches_nothing`"""
+    sp, g = plans()
+    unused_member_reaches_nothing(sp, g, drop)
+
+
 def state_pair(sp, g, oracle, E, keep, nobs=20, seed=52):
     """an Ensemble of E seeded members, the Ensemble of the members `keep`, and their analysis objects on one network"""
     sts = es.member_states(sp, E)
@@ -125,7 +139,7 @@ def test_unused_member_keeps_its_state(plans, oracle_factory):
     """Ensemble.analyse(use=...), T30 L5, E = 4 without member 2, whose time level 1 is NaN: its vor, div, t, tr, ps are byte-equal
     before and after, and the other three are bit-equal to a 3-member Ensemble analysed by a 3-member Letkf"""
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E, keep, drop = 4, (0, 1, 3), 2
     ens, ensc, lt, ltc = state_pair(sp, g, oracle_factory("t30k5"), E, keep)
     for n in es.PROG:
@@ -174,7 +188,7 @@ def test_capture_follows_the_mask(E, plans, oracle_factory):
     launches).  The masked graph holds the mask's pointer: with other contents written in place, a replay from the same state
     equals the eager call with that mask bit for bit"""
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     first, second = [1] * E, [0 if e == 1 else 1 for e in range(E)]
     ens, _, lt, ltc = state_pair(sp, g, oracle_factory("t30k5"), E, tuple(range(E)))
     ltc.close()
@@ -219,7 +233,7 @@ def test_pressure_network(plans):
     pressures are out of its column and of nobody else's.  With all members they are rejected; with member 1 not in use they
     have obs_used == 1, and every field -- obs_lnsigma, from the mean ps of the members in use, among them -- and every
     increment is bit-equal to the object of the other members"""
-    sp, g = plans(8)
+    sp, g = plans("t30")
     E, drop = 5, lp.PATCH_MEMBER
     keep = tuple(e for e in range(E) if e != drop)
     x = lp.craft(g, E, seed=21)
@@ -236,10 +250,9 @@ def test_pressure_network(plans):
 
 
 # ---------------------------------------------------------------------------------------------------- 7. weight interpolation
-def test_weight_stride(plans):
+def weight_stride(sp, g):
     """stride (2, 2), E = 17 without members 0, 5 and 16: the increments are bit-equal to the 14-member object's at that stride, and
     the leading 14 x 14 block of every matrix of `weights`, in compact indices, is its `weights`"""
-    sp, g = plans()
     E, keep = 17, KEEP17
     x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lambda g, xc: lk.concat(lk.clustered_obs(g, xc, n=300), lk.sparse_obs(g, xc)), 0.1,
                                   stride=(2, 2))
@@ -251,6 +264,12 @@ def test_weight_stride(plans):
     lt.close(); ltc.close()
 
 
+def test_weight_stride(plans):
+    """kx = 8: `weight_stride`"""
+    sp, g = plans()
+    weight_stride(sp, g)
+
+
 # ---------------------------------------------------------------------------------------------------- 8. fewer than two members
 @pytest.mark.parametrize("keep", [(2,), ()], ids=["one", "none"])
 @pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
@@ -258,7 +277,7 @@ def test_fewer_than_two_members(keep, stride, plans, oracle_factory):
     """One member in use and none: all-zero increments with the clustered observations in range, at both kinds of stride, and an
     Ensemble's state keeps its bytes.  hxmean is the member's own hx, and NaN without a member"""
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E = 4
     x = lk.ensemble(g, E, seed=9)
     lt = lk.make(sp, E, lk.clustered_obs(g, x, n=300), 0.1)
@@ -288,7 +307,7 @@ def test_scores(plans, oracle_factory):
     none NaN"""
     import speedy_f90_amd as s
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E, keep = 8, (0, 1, 3, 4, 6, 7)
     nat = s.Nature(sp, capacity=3)
     x = lk.ensemble(g, E, seed=77)
@@ -334,7 +353,7 @@ def test_guard_to_mask(plans):
     member after a later in-range step, because the record is sticky"""
     import speedy_f90_amd as s
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E = 4
     sts = [dg.state(sp, 5100 + 100 * e) for e in range(E)]
     x = {n: np.stack([st[n] for st in sts]) for n in ("vor", "div", "t")}
@@ -381,3 +400,33 @@ def test_two_masked_runs_are_bit_equal(plans):
     for n in a:
         assert support.same_bits(a[n], b[n]), n
     lt.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 12. on the T63 L16 grid
+def test_masked_equals_compact_t63(plans):
+    """192 x 96 x 16, E = 32 without member 0: the launch shape, the one level in flight and the LDS request are those of 32 members
+    on 18 432 columns, the problem solved is that of 31, bit for bit the 31-member object's"""
+    sp, g = plans(T63)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    E, keep = 32, tuple(range(1, 32))
+    x, obs, lt, ltc, xc = lm.pair(sp, g, E, keep, lambda g, xc: lk.concat(lk.clustered_obs(g, xc, n=300), lk.sparse_obs(g, xc)), 0.1)
+    lm.same_as_compact(lk.run(lt, x, lm.flags(E, keep)), lk.run(ltc, xc), E, keep, T63)
+    lt.close(); ltc.close()
+
+
+def test_weight_stride_t63(plans):
+    """192 x 96 x 16: `weight_stride`"""
+    sp, g = plans(T63)
+    weight_stride(sp, g)
+
+
+def test_masked_against_restatement_t63(plans):
+    """192 x 96 x 16: `masked_against_restatement`"""
+    sp, g = plans(T63)
+    masked_against_restatement("T63 L16 ", sp, g)
+
+
+def test_unused_member_reaches_nothing_t63(plans):
+    """192 x 96 x 16, member 3 of 8 not in use: `unused_member_reaches_nothing`"""
+    sp, g = plans(T63)
+    unused_member_reaches_nothing(sp, g, 3)

@@ -2,7 +2,8 @@
 DESIGN.md s22) against the NumPy restatement (tests/letkfpressure.py): the observation-space quantities to the bit on crafted
 ensembles that hold every class of target, the tie to the model-level path, the rejection of out-of-column observations, the
 vertical localisation, the analysis of an ensemble's spectral state against the restatement fed by the oracle's transforms, the
-nature run's values, the capture, and one analysis of the twin experiment.  T30."""
+nature run's values, the capture, and one analysis of the twin experiment.  T30; the section "on the T63 L16 grid" repeats the
+observation space, the vertical localisation, the nature run's values and the analysis from spectra at 192 x 96 x 16."""
 import ctypes
 
 import numpy as np
@@ -20,20 +21,24 @@ FIELDS = ("hx", "hxmean", "y", "departure", "obs_lnsigma", "obs_used")
 ERR_STATE = -5
 
 
-def _plan(kx, nmem):
+TAGS = {2: "t30k2", 5: "t30k5", 8: "t30"}      # the T30 plans by their level count; "t30k2" is this file's, on pl.SIGMA_L2
+T63 = "t63k16"
+
+
+def _plan(tag, nmem):
     import speedy_f90_amd as s
-    if kx == 2:
+    if tag == "t30k2":
         sp = s.Spectral("t30", kx=2, max_batch=nmem * 12, device=0)
         sp.set_sigma(pl.SIGMA_L2)
     else:
-        sp = support.ensemble_plan({5: "t30k5", 8: "t30"}[kx], nmem)
+        sp = support.ensemble_plan(tag, nmem)
     return sp, lp.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
     with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
-        yield lambda kx=8, nmem=32: get(kx, nmem)
+        yield lambda tag="t30", nmem=32: get(tag, nmem)
 
 
 def device_fields(lt):
@@ -53,13 +58,9 @@ def increments(sp, lt, x):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. observation space
-@pytest.mark.parametrize("E", [2, 3, 32])
-@pytest.mark.parametrize("kx", [2, 5, 8])
-def test_observation_space(kx, E, plans):
-    """hx, hxmean, y, departure, obs_lnsigma and obs_used of the crafted network (tests/test_letkf_pressure_cpu.py asserts its
-    classes) bit-equal to the restatement, with 0, 1, 257 (more than one workgroup at every E, the last one partly filled) and all
-    observations: there is no transcendental on the device"""
-    sp, g = plans(kx)
+def observation_space(sp, g, E):
+    """hx, hxmean, y, departure, obs_lnsigma and obs_used of the crafted network bit-equal to the restatement, with 0, 1, 257 (more
+    than one workgroup at every E, the last one partly filled) and all observations: there is no transcendental on the device"""
     x = lp.craft(g, E, seed=7 + E)
     full = lp.network(g, x)
     for n in (0, 1, min(257, len(full["var"]) - 1), len(full["var"])):
@@ -70,10 +71,18 @@ def test_observation_space(kx, E, plans):
         want = lk.obs_space(g, x, obs, stencil=lp.tables(lt))
         got = device_fields(lt) if n else want               # no observation: nothing to read, the call itself is the test
         for name in FIELDS:
-            assert support.same_bits(got[name], want[name]), (kx, E, n, name, np.nonzero(got[name] != want[name]))
+            assert support.same_bits(got[name], want[name]), (g.kx, E, n, name, np.nonzero(got[name] != want[name]))
         assert np.array_equal(lt.table("lnp"), lp.lnp(obs))
         lt.close()
     assert (want["obs_used"] == 0.0).sum() >= 10
+
+
+@pytest.mark.parametrize("E", [2, 3, 32])
+@pytest.mark.parametrize("kx", [2, 5, 8])
+def test_observation_space(kx, E, plans):
+    """`observation_space` (tests/test_letkf_pressure_cpu.py asserts the network's classes)"""
+    sp, g = plans(TAGS[kx])
+    observation_space(sp, g, E)
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the tie to the existing path
@@ -82,7 +91,7 @@ def test_tie_to_model_levels(stride, plans):
     """Every variable constant in the vertical per member and point, every at-pressure observation in column, sigma_v = 0: hx and
     the increments of analyse_grid have the bits of the same stations given on model levels through spdy_letkf_set_obs"""
     import speedy_f90_amd as s
-    sp, g = plans(8)
+    sp, g = plans("t30")
     E = 3
     x = lk.ensemble(g, E, seed=12)
     for v in lk.VARS[:4]:
@@ -117,7 +126,7 @@ def test_rejected_observations_take_no_part(E, plans):
     """The crafted network, rejected observations interleaved with used ones (its order is a permutation), and one more rejected
     observation whose stencil no other shares and whose members hold NaN at level 0, the level its target is clamped to: the
     increments are bit-equal to those of the network with the rejected observations removed"""
-    sp, g = plans(8)
+    sp, g = plans("t30")
     x = lp.craft(g, E, seed=21 + E)
     obs = lp.network(g, x)
     lone = lp.make_pobs([lk.T], [lp.AT_P], [pl.P0 * np.exp(dict(lp.targets(g))["above"])], [200.3], [-47.2], [250.0], [1.0])
@@ -151,10 +160,9 @@ def test_rejected_observations_take_no_part(E, plans):
 
 
 # ---------------------------------------------------------------------------------------------------- 4. vertical localisation
-def test_vertical_localisation(plans):
+def vertical_localisation(tag, sp, g):
     """sigma_v = 0.3: the increments against the restatement, which localises with ln sigma_o = ln(p/p0) - psbar, within
     tests/letkf.py's limits (the Jacobi route sampled at the hardest columns, as tests/test_gpu_letkf.py does)"""
-    sp, g = plans(8)
     E, sigma_v = 3, 0.3
     x = lp.craft(g, E, seed=31)
     obs = lp.network(g, x)
@@ -166,18 +174,24 @@ def test_vertical_localisation(plans):
     lns = lt.field("obs_lnsigma").numpy()
     lt.close()
     worst = {v: float(np.max(np.abs(lk.at_columns(got[v], cols) - ref[v]))) / lim[v] for v in lk.VARS}
-    print("[pobs vertical localisation] %d observations, %d columns, kappa %.2e, ratio to the limit: %s"
-          % (len(obs["var"]), len(cols), kappa, " ".join("%s %.3f" % kv for kv in worst.items())))
+    print("[pobs vertical localisation%s] %d observations, %d columns, kappa %.2e, ratio to the limit: %s"
+          % (tag, len(obs["var"]), len(cols), kappa, " ".join("%s %.3f" % kv for kv in worst.items())))
     assert max(worst.values()) <= 1.0, worst
     # the position differs from the host table's where ps is not 0: the localisation is the call's, not the upload's
     atp = lp.at_pressure(obs)
     assert (lns[atp] != lp.lnp(obs)[atp]).any() and np.array_equal(lns[~atp], lk.lnsigma(g, dict(obs, lev=np.where(atp, 0, obs["lev"])))[~atp])
 
 
+def test_vertical_localisation(plans):
+    """kx = 8: `vertical_localisation`"""
+    sp, g = plans("t30")
+    vertical_localisation("", sp, g)
+
+
 def test_vertical_factor_of_zero_changes_nothing(plans):
     """sigma_v = 0.02, so c_v = 0.0365 and the support 0.073: observations in the middle of the first bracket, at least 0.6 from
     every level in ln sigma, appended to the network, are in column and used, and leave every increment's bits"""
-    sp, g = plans(8)
+    sp, g = plans("t30")
     E, sigma_v = 3, 0.02
     x = lp.craft(g, E, seed=41)
     x["ps"][lp.PATCH_MEMBER] = np.where(x["ps"][lp.PATCH_MEMBER] == lp.HIGH, 0.0, x["ps"][lp.PATCH_MEMBER])
@@ -209,7 +223,7 @@ def test_from_spectra(E, plans, oracle_factory):
     obs_lnsigma, formed from the device's own ps grids, within 1e-12; five graph nodes' worth of launches is test_capture's matter"""
     import torch
     import ensemblestep as es
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     o = oracle_factory("t30k5")
     sts, x, net = lp.spectral_case(sp, o, g, E)
     want, space = lp.spectral_analysis(o, g, sts, x, net)
@@ -258,7 +272,7 @@ def test_nature_values(plans):
     NumPy's by at most 2.2e-16 and are not bit-equal to them (the device's randn is its own logarithm and cosine), so bits are asked
     against the draws nature_slot_draw_kernel itself stores, and NumPy's are held to that limit"""
     import speedy_f90_amd as s
-    sp, g = plans(8)
+    sp, g = plans("t30")
     seed = 0x51DE
     x = lp.craft(g, 2, seed=51)
     truth = nt.as_truth(x, lp.PATCH_MEMBER)
@@ -294,7 +308,7 @@ def test_capture(plans):
     with a model-level network; spdy_pobs_set is refused while a capture is open"""
     import torch
     import speedy_f90_amd as s
-    sp, g = plans(8)
+    sp, g = plans("t30")
     E = 3
     x1 = lp.craft(g, E, seed=61)
     x2 = dict(x1, ps=np.random.default_rng(62).uniform(-0.05, 0.05, x1["ps"].shape))
@@ -380,3 +394,109 @@ def test_twin_step():
     print("[pobs twin, device] rmse analysis / background: %s" % " ".join("%s %s" % (v, np.round(r, 3)) for v, r in ratios.items()))
     assert all((r < 1.0).all() for r in ratios.values()), ratios
     nat.close(); lt.close(); sp.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 9. on the T63 L16 grid
+@pytest.mark.parametrize("E", [2, 3, 32])
+def test_observation_space_t63(E, plans):
+    """192 x 96 x 16: `observation_space` on the crafted network of 1 114 observations -- obsop_pressure runs 16 trips of its bracket
+    search over four stencil columns (tests/test_letkf_t63_cpu.py asserts the network's classes, every bracket of the 15 among them)"""
+    sp, g = plans(T63)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    observation_space(sp, g, E)
+
+
+def test_vertical_localisation_t63(plans):
+    """192 x 96 x 16: `vertical_localisation`"""
+    sp, g = plans(T63)
+    vertical_localisation(" T63 L16", sp, g)
+
+
+def test_nature_values_t63(plans):
+    """192 x 96 x 16: Nature.observe with noise = 0 on the crafted network, the crafted ensemble's high-terrain member as the truth,
+    gives the restatement's bits, clamped where the truth is out of column (test_nature_values' first statement)"""
+    import speedy_f90_amd as s
+    sp, g = plans(T63)
+    x = lp.craft(g, 2, seed=51)
+    truth = nt.as_truth(x, lp.PATCH_MEMBER)
+    net = lp.network(g, x)
+    alone = lk.obs_space(g, {v: np.stack([truth[v], truth[v]]) for v in lk.VARS}, net)
+    assert (alone["obs_used"] == 0.0).sum() >= 10
+    nat = s.Nature(sp, seed=0x51DE, capacity=1)
+    nat.field("truth").upload(nt.rows(truth))
+    lt = lp.make(sp, 2, net)
+    h = lp.truth_values(g, truth, net, lp.tables(lt))
+    assert np.isfinite(h).all() and nat.draws() == 0
+    nat.observe(lt, 0.0)
+    assert support.same_bits(lt.field("value").numpy(), h) and nat.draws() == 1
+    nat.close(); lt.close()
+
+
+def drifted_states(sp, sts, fraction=0.1, seed=8500):
+    """the member states a fraction of the way towards another seeded ensemble's: the state of an earlier time slot"""
+    import ensemblestep as es
+    other = es.member_states(sp, len(sts), seed)
+    return [dict(st, **{n: st[n] + fraction * (ot[n] - st[n]) for n in es.PROG}) for st, ot in zip(sts, other)]
+
+
+@pytest.mark.parametrize("slots", [False, True], ids=["plain", "slots"])
+def test_from_spectra_t63(slots, plans, oracle_factory):
+    """192 x 96 x 16, E = 3, 40 radiosonde-like stations (1 120 observations at a pressure), sigma_v = 0.3, weight stride (2, 2),
+    relaxation (0.3, 0.9): Ensemble.analyse -- and, with slots, Ensemble.observe of two slots on two ensembles' spectra, then
+    analyse(slots=True) -- against the restatement (tests/letkfinterp.py's analysis, tests/letkfrelax.py's relaxation) on the
+    oracle's grids through the oracle's direct transforms, under test_from_spectra's rule: every prognostic of time level 1 within
+    1e-12 of its scale, time level 2 keeps its bits, obs_used equals the restatement's and holds both kinds, obs_lnsigma within
+    1e-12.  The increments go back through the direct transform as E (4 kx + 1) = 195 fields"""
+    import torch
+    import ensemblestep as es
+    import letkfinterp as li
+    import letkfrelax as lr
+    sp, g = plans(T63)
+    o = oracle_factory(T63)
+    E, stride, relax = 3, (2, 2), (0.3, 0.9)
+    sts, x, net = lp.spectral_case(sp, o, g, E, stations=40)
+    n = len(net["var"])
+    assert n == 40 * len(lp.SOUNDING) * 4 and lp.margin(g, x, net) >= lp.MARGIN
+    how, first = {}, [0, n // 2 + 1, n]
+    if slots:
+        earlier = drifted_states(sp, sts)
+        xa = lk.oracle_grids(o, earlier)
+        assert lp.margin(g, xa, net) >= lp.MARGIN
+        how = dict(xs=[xa, x], first=first)
+    space = lk.obs_space(g, x, net, **how)
+    inc, _, _ = li.analyse(g, x, net, lk.SIGMA_H, lp.SPECTRAL_SIGMA_V, lk.RHO, *stride, **how)
+    dx, f = lr.relax(lr.at_columns(x, np.arange(g.ix * g.il)), inc, *relax)
+    assert max(float(a.max()) for a in f.values()) > 1.0
+    want = lp.to_spectra(o, g, sts, dx)
+    ens = es.build(sp, sts)
+    lt = lp.make(sp, E, net, lp.SPECTRAL_SIGMA_V)
+    lt.set_weight_stride(*stride)
+    lt.set_relaxation(*relax)
+    before = {name: getattr(ens, name).clone() for name in es.PROG}
+    if slots:
+        lt.set_slots(first)
+        es.build(sp, earlier).observe(lt, 0)
+        ens.observe(lt, 1)
+        ens.analyse(lt, slots=True)
+    else:
+        ens.analyse(lt)
+    torch.cuda.synchronize()
+    used = lt.field("obs_used").numpy()
+    assert np.array_equal(used, space["obs_used"]) and 0.2 * len(used) <= used.sum() <= 0.9 * len(used)
+    assert float(np.max(np.abs(lt.field("obs_lnsigma").numpy() - space["obs_lnsigma"]))) <= 1e-12
+    if slots:
+        now = lk.observe(g, x, net)[0]
+        assert np.max(np.abs(space["hx"][:first[1]] - now[:first[1]])) > 1e-3       # the earlier slot's time matters
+    worst = 0.0
+    for name in es.PROG:
+        a = getattr(ens, name)
+        assert support.same_bits(a[1], before[name][1]), name
+        assert not support.same_bits(a[0], before[name][0]), name
+        for e in range(E):
+            ref = want[e][name]
+            err = float(np.max(np.abs(a[0, e].cpu().numpy() - ref)) / np.max(np.abs(ref)))
+            worst = max(worst, err)
+            assert err <= 1e-12, (name, e, err)
+    print("[pobs from spectra T63 L16 %s] %d of %d observations used, largest error %.3e of the scale, ratio to the limit %.3f"
+          % ("slots" if slots else "plain", int(used.sum()), len(used), worst, worst / 1e-12))
+    lt.close()

@@ -2,7 +2,8 @@
 Letkf.set_background_check).  The check's kernel against the NumPy restatement of tests/letkfqc.py, fed with the
 device's own y, departure and errors: decisions, fields and statistics bit for bit; the checked analysis against the unchecked one
 of the network without the rejected observations; every route with its flags and one graph node more; off is off; the stats-only
-call; a twin experiment with planted gross errors.  T30."""
+call; a twin experiment with planted gross errors.  T30; the section "on the T63 L16 grid" holds the decisions, the statistics and
+the checked analysis to the same statements at 192 x 96 x 16."""
 import importlib.util
 import json
 import os
@@ -26,28 +27,31 @@ SIGMA_V = 0.1
 GROSS = 3.0
 
 
-def _plan(kx, nmem):
-    sp = support.ensemble_plan({5: "t30k5", 8: "t30"}[kx], nmem)
+T63 = "t63k16"
+
+
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
     return sp, lp.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
     with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
-        yield lambda kx=8, nmem=32: get(kx, nmem)
+        yield lambda tag="t30", nmem=32: get(tag, nmem)
 
 
 @pytest.fixture(scope="module")
 def big(plans):
-    """E -> (the ensemble, 2100 observations: the operator's edge cases, the sparse set and a cluster); made once, never changed"""
+    """(E, tag) -> (the ensemble, 2100 observations: the operator's edge cases, the sparse set and a cluster); made once, never changed"""
     made = {}
 
-    def get(E):
-        if E not in made:
-            _, g = plans()
+    def get(E, tag="t30"):
+        if (E, tag) not in made:
+            _, g = plans(tag)
             x = lk.ensemble(g, E, seed=60 + E)
-            made[E] = (x, lk.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=2100)), slice(0, 2100)))
-        return made[E]
+            made[(E, tag)] = (x, lk.subset(lk.concat(lk.edge_obs(g, x), lk.sparse_obs(g, x), lk.clustered_obs(g, x, n=2100)), slice(0, 2100)))
+        return made[(E, tag)]
     return get
 
 
@@ -59,22 +63,7 @@ def analyse(lt, x, out=None, **how):
     return dict(lk.run(lt, x, out=out, names=CHECKED, **how), stats=lt.obs_stats())
 
 
-def restated(got, obs, gross, groups=None, ngroups=5, in_column=None, keep=None, depb=None, code=None):
-    """the restatement on the device's own y, departure and errors -> (decisions, the statistics' rows)"""
-    dec = qc.check(got["y"], got["departure"], obs["error"], gross, in_column, keep)
-    code = dec["check"] if code is None else code
-    rows = qc.stats(obs["var"] if groups is None else groups, ngroups, code, got["departure"], dec["s2"], obs["error"], depb)
-    return dec, rows
-
-
-def table(stats):
-    return np.stack([stats[n] for n in qc.COLUMNS], axis=1)
-
-
-def same_decisions(got, dec, obs):
-    rinv = 1.0 / (obs["error"] * obs["error"])
-    return (support.same_bits(got["obs_used"], dec["used"].astype(np.float64)) and support.same_bits(got["obs_check"], dec["check"])
-            and support.same_bits(got["obs_rinv"], qc.reff(dec["used"], rinv)))
+restated, table, same_decisions = qc.restated, qc.table, qc.same_decisions
 
 
 # ---------------------------------------------------------------------------------------------------- 1. decisions and fields
@@ -116,12 +105,9 @@ def test_decisions_and_fields(E, nobs, plans, big):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. takes no part
-def test_analysis_equals_the_analysis_without_the_rejected(plans, big):
+def analysis_without_the_rejected(sp, g, E, x, obs):
     """With the check on the increments on the grid equal, bit for bit, those of the unchecked call on the network with the rejected
     observations removed; the columns out of range of every rejected observation keep the unchecked call's bits, the others do not"""
-    sp, g = plans()
-    E = 5
-    x, obs = big(E)
     obs = dict(obs)
     lt = lk.make(sp, E, obs, SIGMA_V)
     lt.set_background_check(GROSS)
@@ -142,6 +128,12 @@ def test_analysis_equals_the_analysis_without_the_rejected(plans, big):
         assert support.same_bits(lk.at_columns(got[v], ~near), lk.at_columns(plain[v], ~near)), v
         assert not support.same_bits(lk.at_columns(got[v], near), lk.at_columns(plain[v], near)), v
     lt.close(); without.close()
+
+
+def test_analysis_equals_the_analysis_without_the_rejected(plans, big):
+    """E = 5: `analysis_without_the_rejected`"""
+    sp, g = plans()
+    analysis_without_the_rejected(sp, g, 5, *big(5))
 
 
 # ---------------------------------------------------------------------------------------------------- 3. every route
@@ -288,7 +280,7 @@ def test_off_is_off(plans, oracle_factory):
     analyse_grid two, and tools/letkf_digest.py's digests of an object that had the check on and off again are the ones recorded
     for the parent commit's library (profiles/letkf_obsop_digests.json)"""
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E = 3
     sts = es.member_states(sp, E)
     ens = es.build(sp, sts)
@@ -455,3 +447,45 @@ def test_twin_experiment(oracle_factory):
         print("[letkf qc twin] %s: rmse checked / unchecked %.3f, checked / background %.3f, unchecked / background %.3f" % (name, c / u, c / b, u / b))
         assert c < u, (name, c, u)
     lt.close(); nat.close(); sp.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 7. on the T63 L16 grid
+@pytest.mark.parametrize("nobs", [1023, 1024, 1025, 2100])
+@pytest.mark.parametrize("E", [3, 32])
+def test_decisions_and_fields_t63(E, nobs, plans, big):
+    """192 x 96 x 16, nobs at the edges of the check's own chunk of 1024 and above two of them, five groups given by the caller of
+    which group 2 is empty: obs_used, obs_check, obs_rinv and the statistics equal the restatement bit for bit on the device's own y
+    and departure, with values planted on both sides of the threshold in every non-empty group and one NaN value, as in
+    test_decisions_and_fields; the empty group's row is all +0.0"""
+    sp, g = plans(T63)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    x, all_obs = big(E, T63)
+    obs = lk.subset(all_obs, slice(0, nobs))
+    groups = (np.arange(nobs) * 7 + obs["var"]) % 5
+    groups = np.where(groups == 2, 4, groups)
+    lt = lk.make(sp, E, obs, SIGMA_V)
+    lt.set_background_check(GROSS, groups)
+    first = analyse(lt, x)
+    value, outside, inside = qc.plant(obs, first["hxmean"], qc.spread2(first["y"]), GROSS, seed=nobs + E, groups=groups)
+    nan_at = int(np.setdiff1d(np.arange(nobs), np.concatenate([outside, inside]))[100])
+    value[nan_at] = np.nan
+    lt.field("value").upload(value)
+    got = analyse(lt, x)
+    dec, rows = restated(got, obs, GROSS, groups, 5)
+    assert same_decisions(got, dec, obs)
+    assert (got["obs_check"][outside] == qc.REJECTED).all() and (got["obs_check"][inside] == qc.PASSED).all()
+    assert len(outside) == len(inside) == 8 and got["obs_check"][nan_at] == qc.PASSED and np.isnan(got["departure"][nan_at])
+    stats = table(got["stats"])
+    bad = np.isnan(stats).any(axis=1)
+    assert bad.sum() == 1 and bad[groups[nan_at]]
+    assert stats.shape == (5, 10) and qc.same_rows(stats, rows)
+    assert not stats[2].view(np.int64).any() and (stats[:, 0] > 0).sum() == 4
+    assert stats[:, 0].sum() == nobs and stats[:, 2].sum() == (got["obs_check"] == qc.REJECTED).sum()
+    lt.close()
+
+
+@pytest.mark.parametrize("E", [3, 32])
+def test_analysis_without_the_rejected_t63(E, plans, big):
+    """192 x 96 x 16, 2 100 observations: `analysis_without_the_rejected`"""
+    sp, g = plans(T63)
+    analysis_without_the_rejected(sp, g, E, *big(E, T63))

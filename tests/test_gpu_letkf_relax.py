@@ -1,7 +1,8 @@
 """GPU: relaxation to the prior perturbations and spread (include/spdy.h, "relaxation"; Letkf.set_relaxation).
 The kernel against the NumPy restatement of tests/letkfrelax.py, fed with the raw increments the same object gives at (0, 0), which
 are bit-reproducible; the three statements the header calls exact; the weight-interpolated route, aliased outputs and an empty
-network; the member mask against the object of the members in use; an Ensemble's state; a captured analysis.  T30."""
+network; the member mask against the object of the members in use; an Ensemble's state; a captured analysis.  T30; the section "on
+the T63 L16 grid" holds the kernel, the weight-interpolated route and the aliased call to the same rules at 192 x 96 x 16."""
 import numpy as np
 import pytest
 
@@ -16,15 +17,18 @@ pytestmark = pytest.mark.gpu
 SIGMA_V = 0.1
 
 
-def _plan(kx, nmem):
-    sp = support.ensemble_plan({5: "t30k5", 8: "t30"}[kx], nmem)
+T63 = "t63k16"
+
+
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
     return sp, lk.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
     with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
-        yield lambda kx=8, nmem=32: get(kx, nmem)
+        yield lambda tag="t30", nmem=32: get(tag, nmem)
 
 
 def both_sets(g, x):
@@ -36,15 +40,13 @@ def mixed(g, x):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. against the restatement
-@pytest.mark.parametrize("E,kx", [(2, 8), (3, 8), (17, 8), (32, 8), (32, 5)])
-def test_kernel_against_restatement(E, kx, plans):
-    """the clustered and the sparse set, sigma_v = 0.1, (rtpp, rtps) = (0.5, 0), (0, 0.9), (0.3, 0.9): the relaxed increments at
-    every column against `relax` of the object's own raw increments, within 64 E eps max|x| max(1, f) per item -- the increment
-    bound of DESIGN.md s18 times the factor that multiplies the rounding of b_e -- and the inflation field against f at 64 E eps"""
-    sp, g = plans(kx)
+def kernel_against_restatement(tag, sp, g, E, sets):
+    """sigma_v = 0.1, (rtpp, rtps) = (0.5, 0), (0, 0.9), (0.3, 0.9): the relaxed increments at every column against `relax` of the
+    object's own raw increments, within 64 E eps max|x| max(1, f) per item -- the increment bound of DESIGN.md s18 times the factor
+    that multiplies the rounding of b_e -- and the inflation field against f at 64 E eps"""
     x = lk.ensemble(g, E, seed=E)
     worst, fmax = 0.0, 0.0
-    for tag, obs in both_sets(g, x):
+    for name, obs in sets(g, x):
         lt = lk.make(sp, E, obs, SIGMA_V)
         raw = lk.run(lt, x)
         for rtpp, rtps in lr.SETTINGS:
@@ -52,12 +54,19 @@ def test_kernel_against_restatement(E, kx, plans):
             got = lk.run(lt, x)
             infl = got["inflation"]
             w, f = lr.compare(x, raw, got, infl, rtpp, rtps, E)
-            print("[letkf relax E=%d kx=%d %s rtpp=%.1f rtps=%.1f] ratio to the limit %.2e, largest f %.3f" % (E, kx, tag, rtpp, rtps, w, f))
-            assert any(not support.same_bits(got[v], raw[v]) for v in lk.VARS), (tag, rtpp, rtps)
+            print("[letkf relax %s %s rtpp=%.1f rtps=%.1f] ratio to the limit %.2e, largest f %.3f" % (tag, name, rtpp, rtps, w, f))
+            assert any(not support.same_bits(got[v], raw[v]) for v in lk.VARS), (name, rtpp, rtps)
             worst, fmax = max(worst, w), max(fmax, f)
         lt.close()
-    print("[letkf relax E=%d kx=%d] largest ratio to the limit %.2e, largest f %.3f" % (E, kx, worst, fmax))
+    print("[letkf relax %s] largest ratio to the limit %.2e, largest f %.3f" % (tag, worst, fmax))
     assert worst <= 1.0, worst
+
+
+@pytest.mark.parametrize("E,kx", [(2, 8), (3, 8), (17, 8), (32, 8), (32, 5)])
+def test_kernel_against_restatement(E, kx, plans):
+    """the clustered and the sparse set: `kernel_against_restatement`"""
+    sp, g = plans({5: "t30k5", 8: "t30"}[kx])
+    kernel_against_restatement("E=%d kx=%d" % (E, kx), sp, g, E, both_sets)
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the exact statements
@@ -118,25 +127,28 @@ def test_both_zero_is_the_analysis_it_was(plans):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. routes
-def test_weight_stride(plans):
+def weight_stride(tag, sp, g):
     """stride (2, 2), E = 17: the apply kernel's raw increments go through the same relaxation"""
-    sp, g = plans()
     E = 17
     x = lk.ensemble(g, E, seed=E)
     lt = lk.make(sp, E, mixed(g, x), SIGMA_V)
     lt.set_weight_stride(2, 2)
     raw, got, infl = lr.raw_and_relaxed(lt, x, 0.3, 0.9)
     w, f = lr.compare(x, raw, got, infl, 0.3, 0.9, E)
-    print("[letkf relax stride (2, 2) E=17] ratio to the limit %.2e, largest f %.3f" % (w, f))
+    print("[letkf relax %sstride (2, 2) E=17] ratio to the limit %.2e, largest f %.3f" % (tag, w, f))
     assert w <= 1.0, w
     lt.close()
 
 
-@pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
-def test_outputs_may_be_the_inputs(stride, plans):
+def test_weight_stride(plans):
+    """kx = 8: `weight_stride`"""
+    sp, g = plans()
+    weight_stride("", sp, g)
+
+
+def outputs_may_be_the_inputs(sp, g, stride):
     """analyse_grid with out = the input tensors: the bits of the call that does not alias"""
     import torch
-    sp, g = plans()
     E = 17
     x = lk.ensemble(g, E, seed=E)
     lt = lk.make(sp, E, mixed(g, x), SIGMA_V)
@@ -151,6 +163,13 @@ def test_outputs_may_be_the_inputs(stride, plans):
         assert support.same_bits(a.cpu().numpy(), ref[v]) and ref[v].any(), v
     assert support.same_bits(lt.field("inflation").numpy(), finf)
     lt.close()
+
+
+@pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
+def test_outputs_may_be_the_inputs(stride, plans):
+    """kx = 8, E = 17: `outputs_may_be_the_inputs`"""
+    sp, g = plans()
+    outputs_may_be_the_inputs(sp, g, stride)
 
 
 def test_rtps_one_takes_pure_inflation_back(plans):
@@ -243,7 +262,7 @@ def test_ensemble_state(plans, oracle_factory):
     agrees between the members to 4 eps max|state|"""
     import speedy_f90_amd as s
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E = 3
     ens, lt = state_of(sp, g, oracle_factory("t30k5"), E)
     nat = s.Nature(sp, capacity=1)
@@ -285,7 +304,7 @@ def test_capture(E, plans, oracle_factory):
     """A captured relaxed Ensemble.analyse has one kernel node more than the unrelaxed capture; its replays are bit-equal to the
     eager call; it keeps the values of its capture when set_relaxation is called afterwards"""
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     ens, lt = state_of(sp, g, oracle_factory("t30k5"), E)
     x0 = {n: getattr(ens, n).clone() for n in es.PROG}
     lt.set_relaxation(0.3, 0.9)
@@ -317,3 +336,26 @@ def test_capture(E, plans, oracle_factory):
     finally:
         sp.use_torch_stream()
     lt.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 7. on the T63 L16 grid
+@pytest.mark.parametrize("E", [3, 32])
+def test_kernel_against_restatement_t63(E, plans):
+    """192 x 96 x 16, a cluster of 300 and the sparse set: `kernel_against_restatement`.  letkf_relax_kernel has 4 kx + 1 = 65 items in
+    blockIdx.y, and at E = 32 the raw-increment workspace is 65 x 32 grids, 307 MB"""
+    sp, g = plans(T63)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    kernel_against_restatement("T63 L16 E=%d" % E, sp, g, E, lambda g, x: (("mixed", mixed(g, x)),))
+
+
+def test_weight_stride_t63(plans):
+    """192 x 96 x 16: `weight_stride`"""
+    sp, g = plans(T63)
+    weight_stride("T63 L16 ", sp, g)
+
+
+@pytest.mark.parametrize("stride", [(1, 1), (2, 2)])
+def test_outputs_may_be_the_inputs_t63(stride, plans):
+    """192 x 96 x 16, E = 17: `outputs_may_be_the_inputs`"""
+    sp, g = plans(T63)
+    outputs_may_be_the_inputs(sp, g, stride)

@@ -2,7 +2,8 @@
 observe_grid, analyse_grid(slots=True), Ensemble.observe, Ensemble.analyse(slots=True), Nature.observe(slot=)).  Four
 statements need no tolerance: slots all observed on the analysed state give the plain analysis bit for bit; an observe writes its
 slot's rows and nothing else; a member dropped at the analysis may hold anything from any slot on; one slot is no slot.  With
-different times the analysis is held to the NumPy restatement (tests/letkfslots.py) by tests/letkf.py's limits(...).  T30."""
+different times the analysis is held to the NumPy restatement (tests/letkfslots.py) by tests/letkf.py's limits(...).  T30; the section
+"on the T63 L16 grid" holds the analysis of different times to the restatement at 192 x 96 x 16."""
 import numpy as np
 import pytest
 
@@ -20,15 +21,18 @@ pytestmark = pytest.mark.gpu
 ERR_STATE = -5
 
 
-def _plan(kx, nmem):
-    sp = support.ensemble_plan({5: "t30k5", 8: "t30"}[kx], nmem)
+T63 = "t63k16"
+
+
+def _plan(tag, nmem):
+    sp = support.ensemble_plan(tag, nmem)
     return sp, lp.Geometry(sp)
 
 
 @pytest.fixture(scope="module")
 def plans():
     with support.plan_cache(_plan, plan_of=lambda made: made[0]) as get:
-        yield lambda kx=8, nmem=32: get(kx, nmem)
+        yield lambda tag="t30", nmem=32: get(tag, nmem)
 
 
 def make(sp, E, obs, sigma_v, stride=None, relax=None):
@@ -117,7 +121,7 @@ def test_same_state_from_spectra(plans, oracle_factory):
     """Ensemble.observe for every slot, then Ensemble.analyse(slots=True), against Ensemble.analyse on a copy: the spectra are
     byte-equal, T30 L5, E = 3; and the observes themselves change nothing of the state"""
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E = 3
     ens, copy, lt, plain, obs = state_pair(sp, g, oracle_factory("t30k5"), E)
     before = {n: getattr(ens, n).clone() for n in es.PROG}
@@ -178,12 +182,11 @@ def test_different_times_against_restatement(E, plans):
         lt.close()
 
 
-def test_different_times_at_pressure(plans):
+def different_times_at_pressure(tag, sp, g):
     """E = 4, tests/letkfpressure.py's network, S = 3.  The drift and a push move member 2's ps at one station of slot 1 so that the
     station is below that member's lowest level at its slot's time and inside every column at the analysis time -- asserted with
     the restatement: the slot analysis leaves it out (obs_used 0, from slot_out of that member alone), a plain analysis of the
     analysed ensemble uses it"""
-    sp, g = plans()
     E, member, slot = 4, 2, 1
     x, obs = pressure_case(g, E, seed=23)
     n = len(obs["var"])
@@ -191,11 +194,17 @@ def test_different_times_at_pressure(plans):
     xs, o = ls.push_out(g, ls.drifting(g, x, 3, seed=44), obs, first, slot, member)
     assert first[slot] <= o < first[slot + 1] and xs[2] is x
     lt = lp.make(sp, E, obs, 0.1)
-    want, got = held_to_the_restatement(sp, g, lt, x, xs, obs, first, E, 0.1, "E=4 at pressure")
+    want, got = held_to_the_restatement(sp, g, lt, x, xs, obs, first, E, 0.1, "%sE=4 at pressure" % tag)
     assert want["slot_out"][o].tolist() == [1.0 if e == member else 0.0 for e in range(E)] and want["obs_used"][o] == 0.0
     assert lk.obs_space(g, x, obs, stencil=lp.tables(lt))["obs_used"][o] == 1.0
     assert got["obs_used"][o] == 0.0 and (got["obs_used"] == 0.0).sum() >= 10 and (got["obs_used"] == 1.0).sum() >= 100
     lt.close()
+
+
+def test_different_times_at_pressure(plans):
+    """kx = 8: `different_times_at_pressure`"""
+    sp, g = plans()
+    different_times_at_pressure("", sp, g)
 
 
 # ---------------------------------------------------------------------------------------------------- 3. slot isolation
@@ -282,7 +291,7 @@ def test_refusals_enqueue_nothing(plans, oracle_factory):
     through; a new set_slots forgets the marks; after set_obs the slots are gone"""
     import speedy_f90_amd as s
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E = 3
     ens, _, lt, plain, obs = state_pair(sp, g, oracle_factory("t30k5"), E)
     plain.close()
@@ -447,7 +456,7 @@ def test_the_cycle_in_one_graph(plans, oracle_factory):
     for bit; and the whole cycle captured as one graph leaves the spectra, the scores, the values and hx of the eager cycle"""
     import speedy_f90_amd as s
     import torch
-    sp, g = plans(5)
+    sp, g = plans("t30k5")
     E, seed = 3, 0x4D
     ens, _, lt, mover, obs = state_pair(sp, g, oracle_factory("t30k5"), E)
     n = len(obs["var"])
@@ -512,3 +521,91 @@ def test_the_cycle_in_one_graph(plans, oracle_factory):
     assert support.same_bits(eager["hx"].numpy()[7:], now[7:]) and not np.array_equal(eager["hx"].numpy()[:7], now[:7])
     assert not support.same_bits(ens.t[0], eager["t"][0])
     nat.close(); lt.close(); mover.close(); plain.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 9. on the T63 L16 grid
+@pytest.mark.parametrize("E", [4, 17])
+def test_different_times_against_restatement_t63(E, plans):
+    """192 x 96 x 16, sigma_v = 0.1: three times on ensembles that drift towards the analysed one, first = FIRST(nobs) -- a
+    one-observation slot, an empty one (it shares the first time), a boundary inside a chunk, a long tail -- on a model-level network
+    of a cluster of 600 and the sparse set: `held_to_the_restatement`"""
+    sp, g = plans(T63)
+    assert (g.ix, g.il, g.kx) == (192, 96, 16)
+    x = lk.ensemble(g, E, seed=E)
+    a, b, _ = ls.drifting(g, x, 3, seed=40 + E, passes=2)
+    xs = [a, a, b, x]
+    obs = lk.concat(lk.clustered_obs(g, x, n=600), lk.sparse_obs(g, x))
+    first = ls.FIRST(len(obs["var"]))
+    lt = lk.make(sp, E, obs, 0.1)
+    want, got = held_to_the_restatement(sp, g, lt, x, xs, obs, first, E, 0.1, "T63 L16 E=%d" % E)
+    now = lk.observe(g, x, obs)[0]
+    assert np.max(np.abs(want["hx"][:first[3]] - now[:first[3]])) > 1e-3 and support.same_bits(got["hx"][first[3]:], want["hx"][first[3]:])
+    lt.close()
+
+
+def test_different_times_at_pressure_t63(plans):
+    """192 x 96 x 16: `different_times_at_pressure`"""
+    sp, g = plans(T63)
+    different_times_at_pressure("T63 L16 ", sp, g)
+
+
+def test_capture_everything_t63(plans):
+    """192 x 96 x 16, the object with every feature on (tests/letkfslots.py's EVERYTHING; tests/test_gpu_letkf.py holds it to the
+    restatement), two slots: {observe slot 0 on the earlier ensemble, observe slot 1 on the analysed one, the masked slot analysis
+    with out= given} as one graph.  Three replays from the restored inflation field equal three eager calls in every bit of the
+    increments, the fields, the statistics and the field, which the graph advances by itself.  The nodes are the header's counts:
+    each observe one; the analysis on grids two, and one more each for the weight stride, the relaxation, the member mask and the
+    background check, two more for adaptive inflation"""
+    import torch
+    sp, g = plans(T63)
+    c = ls.EVERYTHING
+    case = ls.everything_inputs(g, S=2, first_of=lambda n: [0, 400, n])
+    xs, first, keep = case["xs"], case["first"], case["keep"]
+    lt = ls.everything_object(sp, case)
+    field = case["field"].reshape((sp.kx,) + sp.grid_shape)
+    use = torch.tensor(lm.flags(c["E"], keep), dtype=torch.int32, device="cuda")
+    xa, xb = lk.grids(xs[0]), lk.grids(xs[1])
+    out = tuple(torch.empty_like(a) for a in xb)
+    names = lk.FIELDS + ("slot_ps", "slot_out", "obs_check", "obs_rinv", "obs_s2", "rho", "infl_parm", "inflation", "weights", "obs_stats")
+    lt.set_slots(first)
+
+    def cycle():
+        lt.observe_grid(0, *xa)
+        lt.observe_grid(1, *xb)
+        lt.analyse_grid(*xb, out=out, use=use, slots=True)
+
+    def result():
+        got = {v: a.cpu().numpy() for v, a in zip(lk.VARS, out)}
+        got.update({name: lt.field(name).numpy() for name in names})
+        return got
+
+    eager = []
+    for _ in range(3):
+        cycle()
+        torch.cuda.synchronize()
+        eager.append(result())
+    assert all(eager[0][v].any() for v in lk.VARS) and (eager[0]["obs_check"] == 1.0).any() and (eager[0]["obs_check"] == 2.0).any()
+    assert not support.same_bits(eager[0]["rho"], eager[1]["rho"]) and not support.same_bits(eager[1]["rho"], eager[2]["rho"])
+    assert not support.same_bits(eager[0]["t"], eager[1]["t"])
+    sp.use_own_stream()
+    torch.cuda.synchronize()
+    try:
+        with sp.graph_capture() as gr:
+            cycle()
+        assert gr.num_nodes() == 2 + (2 + 1 + 1 + 1 + 1 + 2), gr.num_nodes()
+        lt.inflation_field().upload(field)
+        for r in range(3):
+            for name in ("hx", "y", "hxmean", "departure", "obs_check", "obs_rinv"):
+                f = lt.field(name)
+                f.upload(np.full(f.shape, -3.0))
+            for a in out:
+                a.fill_(-3.0)
+            torch.cuda.synchronize()
+            gr.launch()
+            sp.synchronize()
+            got = result()
+            same(got, eager[r], lk.VARS + names, ("replay", r))
+        gr.close()
+    finally:
+        sp.use_torch_stream()
+    lt.close()
